@@ -6,8 +6,13 @@ in HBM: classify -> GJK kernels -> EPA kernels (or the BVH traversal), through t
 
 Headline (the `value` of the JSON line) = BASELINE.json configs[2], the configuration north_star's target is quoted on:
 1M Convex-Convex (32-vertex hulls, shared 4096-hull library) distance() queries, signed distance (GJK+EPA), Nesterov
-acceleration, fp32.  Without `--workload` the line also carries `secondary`: the other BASELINE configurations, each with
-its own timed region, roofline and (trimmed) CPU baseline --
+acceleration, fp32.
+
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline needs: set-up, W warm-up steps, N timed steps,
+the outputs of the last timed step if `--dump-outputs DIR` is given, and the result line (its `roofline` and `cpu_baseline`
+null).  Everything else is measured and checked with `--full`: the headline's per-kernel durations, roofline, CPU baseline
+and host-buffer rate, N > 1 the exchange check and probe, and without `--workload` the `secondary` rows: the other
+BASELINE configurations, each with its own timed region, roofline and (trimmed) CPU baseline --
   cfg2  1M Box-Capsule collide(), fp64 (+ the same batch through the host-buffer boundary, `host_buffers`)
   cfg4  100k BVHModel<OBBRSS> mesh-mesh collide(), fp64
   cfg5  1.25M (= 10M / 8) mixed pairs from the host broadphase, fp64, per GPU (weak)
@@ -27,6 +32,11 @@ byte budget).  `--scaling strong`: one list, rank r owns sharding.shard_range(n,
 
 Rank 0 prints ONE compact JSON line (<= 4 KB: the contract's fields, the headline's `roofline` and `cpu_baseline`, the
 secondary workloads as short rows) as the LAST line of stdout; the full record goes to bench_full.json.
+
+`--dump-outputs DIR`: rank 0 writes the records of the headline's last timed step -- what a caller of the device entry point
+receives -- as DIR/<field>.npy (distance, normal, p1, p2, ...; float fields as they are, integer fields as exact float64).  The
+inputs are seeded, so two builds run with the same arguments can be compared output for output.  Records beyond DUMP_LIMIT
+bytes are sampled: a fixed, seeded set of records, whose indices go to DIR/index.npy.
 """
 import argparse
 import hashlib
@@ -119,7 +129,14 @@ def parse():
     ap.add_argument("--no-secondary", action="store_true")
     ap.add_argument("--host-buffers", action="store_true", help="with --workload cfg2/cfg5/...: also time the batch through the host-buffer boundary")
     ap.add_argument("--cpu-sample", type=int, default=1_000_000)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: per-kernel "
+                    "durations, roofline, CPU baseline, host-buffer rate, the exchange check and probe (N > 1), the secondary workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the records of the headline's last timed step to "
+                    "DIR/<field>.npy (float32 / float64)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def kernel_source_sha():
@@ -292,14 +309,17 @@ def compact_line(full):
     gc = cfg.get("gather_check")
     if gc:
         line["config"]["gather_check"] = {k: (all(v) if isinstance(v, (list, tuple)) else v) for k, v in gc.items()}
-    rf = full.get("roofline") or {}
-    line["roofline"] = _pick(rf, ("bound", "kernel", "timer_label", "achieved", "peak", "unit", "frac", "traffic", "traffic_ratio", "bytes_per_query",
-                                  "units_per_launch", "kernel_ms", "pipeline_ms", "pipeline_achieved", "step_traffic", "step_traffic_ratio",
-                                  "useful_flop_per_query", "useful_flop_frac", "hbm_side", "l2_side"))
-    if rf.get("traffic_source"):
-        line["roofline"]["traffic_source"] = rf["traffic_source"]
-    if rf.get("valu_issue"):
-        line["roofline"]["valu_frac"] = _r(rf["valu_issue"]["frac"])
+    rf = full.get("roofline")
+    if rf:
+        line["roofline"] = _pick(rf, ("bound", "kernel", "timer_label", "achieved", "peak", "unit", "frac", "traffic", "traffic_ratio", "bytes_per_query",
+                                      "units_per_launch", "kernel_ms", "pipeline_ms", "pipeline_achieved", "step_traffic", "step_traffic_ratio",
+                                      "useful_flop_per_query", "useful_flop_frac", "hbm_side", "l2_side"))
+        if rf.get("traffic_source"):
+            line["roofline"]["traffic_source"] = rf["traffic_source"]
+        if rf.get("valu_issue"):
+            line["roofline"]["valu_frac"] = _r(rf["valu_issue"]["frac"])
+    else:
+        line["roofline"] = None  # (a run without --full)
     cb = full.get("cpu_baseline")
     if cb:
         line["cpu_baseline"] = _pick(cb, ("value", "unit", "cores", "kind", "sample"))
@@ -351,6 +371,26 @@ def compact_line(full):
         line["truncated"] = True
         out = json.dumps(line, separators=(",", ":"))
     return out
+
+
+DUMP_LIMIT = 64_000_000  # bytes of all files --dump-outputs writes
+
+
+def dump_outputs(path, records):
+    """--dump-outputs: one .npy per field of the records (float fields as they are, integer fields as float64, which holds them
+    exactly).  When all records do not fit in DUMP_LIMIT (1 MB of it kept for the .npy headers), a fixed, seeded sample of them does,
+    in record order, with its record indices in index.npy."""
+    os.makedirs(path, exist_ok=True)
+    kinds = {k: (np.float32 if records.dtype[k].base == np.float32 else np.float64) for k in records.dtype.names}
+    per_record = sum(np.dtype(t).itemsize * int(np.prod(records.dtype[k].shape)) for k, t in kinds.items())
+    budget = DUMP_LIMIT - (1 << 20)
+    if per_record * len(records) > budget:
+        keep = budget // (per_record + 8)
+        idx = np.sort(np.random.default_rng(20240611).choice(len(records), keep, replace=False))
+        records = records[idx]
+        np.save(os.path.join(path, "index.npy"), idx.astype(np.float64))
+    for k, t in kinds.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(records[k], dtype=t))
 
 
 def make_batch(ctx, workload, n, strong):
@@ -506,8 +546,10 @@ def host_boundary(pkg, lib, batch, req, device_records, f32=False):
 
 
 def run_workload(ctx, workload, n_arg, steps, warmup, strong=False, cpu_budget_s=10.0, cpu_sample=1_000_000, host_buffers=False,
-                 gather=None, two_streams=False):
-    """One timed region: `steps` passes of the hot path over this rank's batch.  Returns the result dict on rank 0."""
+                 gather=None, two_streams=False, dump_dir=None):
+    """One timed region: `steps` passes of the hot path over this rank's batch.  Returns the result dict on rank 0.  Without
+    --full nothing else runs on the device or the host's oracle: no per-kernel pass, no exchange check or probe, no roofline or
+    CPU baseline."""
     import torch
     import torch.distributed as dist
     args, pkg, dev = ctx.args, ctx.pkg, ctx.dev
@@ -591,12 +633,17 @@ def run_workload(ctx, workload, n_arg, steps, warmup, strong=False, cpu_budget_s
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # what did the exchange deliver?  (outside the timed region)
     last = (steps - 1) & 1
+    # the records of the last timed step, copied before any later pass reuses the buffers
+    res = outs[last][:n * rec_words].cpu().numpy().view(abi.RESULT_F32_DTYPE if dtype == "f32" else abi.RESULT_DTYPE) if ctx.rank == 0 else None
+    if dump_dir and ctx.rank == 0:
+        dump_outputs(dump_dir, res)
+
+    # what did the exchange deliver?  (outside the timed region)
     gather_check = None
-    if gather and steps > 0:
+    if gather and (args.full or args.verify_gather):
         gather_check = {"block_checksums": xch.verify(last, sent[last], ctx.rank)}
-        verify = args.verify_gather if args.verify_gather is not None else ctx.world > 1  # (on by default for every real multi-rank run)
+        verify = args.verify_gather if args.verify_gather is not None else ctx.world > 1  # (on by default for every real multi-rank run with --full)
         if verify and not strong and workload in WALK_BYTES:
             verify = False  # (weak scaling regenerates every rank's batch on rank 0: done for the pair-list workloads, not for the mesh scenes)
         if verify and not strong:
@@ -649,9 +696,9 @@ def run_workload(ctx, workload, n_arg, steps, warmup, strong=False, cpu_budget_s
     # N > 1: what the run can say about itself, outside the timed region -- the ranks the backend reached, the exchange alone, and every
     # rank's steps WITHOUT the exchange (max / min over ranks: weak scaling's per-rank figure is the N = 1 bench's ms_per_step, so the
     # driver can hold a SCALE line against its BENCH line)
-    exchange_probe = xch.probe(sent[last]) if (gather and steps > 0) else None
+    exchange_probe = xch.probe(sent[last]) if (gather and args.full) else None
     rank_ms = None
-    if ctx.dist_on and steps > 0:
+    if ctx.dist_on and args.full:
         sync_all()
         t1 = time.perf_counter()
         for i in range(steps):
@@ -666,104 +713,105 @@ def run_workload(ctx, workload, n_arg, steps, warmup, strong=False, cpu_budget_s
 
     # per-kernel durations (HIP events inside the library, on the launch stream), separate pass so
     # the event reads do not serialise the timed region
-    lib.set_kernel_timing(True)
-    for i in range(min(steps, 10)):
-        one_step(i, True, exchange=False)
-    torch.cuda.synchronize()
+    if args.full:
+        lib.set_kernel_timing(True)
+        for i in range(min(steps, 10)):
+            one_step(i, True, exchange=False)
+        torch.cuda.synchronize()
 
     result = None
     if ctx.rank == 0:
-        res = outs[(steps - 1) & 1][:n * rec_words].cpu().numpy()
-        status = res.view(abi.RESULT_F32_DTYPE if dtype == "f32" else abi.RESULT_DTYPE)["status"]
+        status = res["status"]
         contact_frac = float(abi.status_contact(status).mean()) if n else 0.0
         buckets = lib.last_bucket_counts()
         total_q = steps * (n_total if strong else n * ctx.world)
         qps = total_q / elapsed
         ms_per_step = 1e3 * elapsed / steps
-        avg = {k: float(np.mean(v)) for k, v in kernel_ms.items() if np.mean(v) > 0}
-        dominant = max(avg, key=avg.get) if avg else ""
-        bpq = BYTES_PER_QUERY[workload]
-        if workload in WALK_BYTES:
-            sys.path.insert(0, os.path.join(ROOT, "tests"))
-            import oracle_binding as ob0  # measures N_bv / N_leaf of the reference DFS on a sample (outside the timed region)
-            ns0 = min(2000, n)
-            ML = pkg.bvh_builder.MeshLibrary(batch.meshes)
-            sl = slice(0, ns0)
-            if workload == "cfg4":
-                _, st0 = ob0.bvh_collide_batch(ML, batch.s1[sl], batch.s2[sl], batch.tf1[sl], batch.tf2[sl], req,
-                                               n_threads=os.cpu_count() or 1, want_stats=True)
-            elif workload == "cfg4d":
-                _, st0 = ob0.bvh_distance_batch(ML, batch.s1[sl], batch.s2[sl], batch.tf1[sl], batch.tf2[sl],
-                                                n_threads=os.cpu_count() or 1, want_stats=True)
+        roofline = cpu = None
+        if args.full:
+            avg = {k: float(np.mean(v)) for k, v in kernel_ms.items() if np.mean(v) > 0}
+            dominant = max(avg, key=avg.get) if avg else ""
+            bpq = BYTES_PER_QUERY[workload]
+            if workload in WALK_BYTES:
+                sys.path.insert(0, os.path.join(ROOT, "tests"))
+                import oracle_binding as ob0  # measures N_bv / N_leaf of the reference DFS on a sample (outside the timed region)
+                ns0 = min(2000, n)
+                ML = pkg.bvh_builder.MeshLibrary(batch.meshes)
+                sl = slice(0, ns0)
+                if workload == "cfg4":
+                    _, st0 = ob0.bvh_collide_batch(ML, batch.s1[sl], batch.s2[sl], batch.tf1[sl], batch.tf2[sl], req,
+                                                   n_threads=os.cpu_count() or 1, want_stats=True)
+                elif workload == "cfg4d":
+                    _, st0 = ob0.bvh_distance_batch(ML, batch.s1[sl], batch.s2[sl], batch.tf1[sl], batch.tf2[sl],
+                                                    n_threads=os.cpu_count() or 1, want_stats=True)
+                else:
+                    _, st0 = ob0.mixed_collide_batch(batch.shapes, batch.verts, ML, batch.s1[sl], batch.s2[sl], batch.tf1[sl], batch.tf2[sl], req,
+                                                     n_threads=os.cpu_count() or 1, want_stats=True)
+                nbv, nleaf = float(st0[:, 0].mean()), float(st0[:, 1].mean())
+                bpq = bpq + WALK_BYTES[workload][0] * nbv + WALK_BYTES[workload][1] * nleaf
+                extra_cfg.update({"mean_bv_tests": nbv, "mean_leaf_tests": nleaf, "stats_sample": ns0})
+            # units the dominant kernel processes in one launch
+            if dominant.startswith("k_epa<fast"):
+                units = buckets["epa_queue"]
+            elif dominant.startswith("k_epa<full"):
+                units = buckets["epa_overflow"]
             else:
-                _, st0 = ob0.mixed_collide_batch(batch.shapes, batch.verts, ML, batch.s1[sl], batch.s2[sl], batch.tf1[sl], batch.tf2[sl], req,
-                                                 n_threads=os.cpu_count() or 1, want_stats=True)
-            nbv, nleaf = float(st0[:, 0].mean()), float(st0[:, 1].mean())
-            bpq = bpq + WALK_BYTES[workload][0] * nbv + WALK_BYTES[workload][1] * nleaf
-            extra_cfg.update({"mean_bv_tests": nbv, "mean_leaf_tests": nleaf, "stats_sample": ns0})
-        # units the dominant kernel processes in one launch
-        if dominant.startswith("k_epa<fast"):
-            units = buckets["epa_queue"]
-        elif dominant.startswith("k_epa<full"):
-            units = buckets["epa_overflow"]
-        else:
-            units = n
-        split = lib.last_split_parts()
-        units = units / split  # a launch covers one half of a split batch
-        dom_ms = avg.get(dominant, float("nan"))
-        achieved = (units * bpq) / (dom_ms * 1e-3) / 1e9 if dom_ms == dom_ms and dom_ms > 0 else None
-        pipeline_ms = float(sum(avg.values()))
-        traffic, traffic_note = load_traffic(workload, dominant, n)
-        valu_insts, sq = load_traffic(workload, dominant, n, want="valu")
-        valu = None
-        if valu_insts and dom_ms == dom_ms and dom_ms > 0:
-            # the bound that actually applies to the iterative kernels: wave-level VALU instructions issued per
-            # launch (SQ_INSTS_VALU, committed PMC pass of this code) against the MEASURED issue peak over the live kernel duration
-            valu = {"insts_per_launch": valu_insts, "issue_peak_per_s": VALU_ISSUE_PEAK,
-                    "frac": valu_insts / (dom_ms * 1e-3) / VALU_ISSUE_PEAK, "sq_counters_per_launch": sq,
-                    "note": "wave-level VALU instructions / (kernel time x measured chip-wide issue peak, tools/valu_peak.hip); "
-                            "fp64 arithmetic issues at 0.56 of that rate"}
-        names = rocprof_names(workload, dominant)
-        step_traffic = load_step_traffic(workload, n)
-        useful = None
-        if workload in ("cfg3", "cfg3u") and n:
-            g_it = float(abi.status_gjk_iters(status).mean())
-            e_it = float((abi.status_epa_iters(status) * (abi.status_epa(status) != 15)).mean())
-            ran_epa = float((abi.status_epa(status) != 15).mean())
-            useful = g_it * FLOP_GJK_ITER + e_it * FLOP_EPA_ITER + ran_epa * FLOP_EPA_SETUP
-            extra_cfg.update({"mean_gjk_iterations": g_it, "mean_epa_iterations_over_all_pairs": e_it})
-        roofline = {
-            "bound": "hbm", "kernel": (names[0].split("(")[0].replace("void ", "").strip() if names else dominant), "timer_label": dominant,
-            "kernels_under_label": names,
-            "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": traffic, "traffic_note": traffic_note,
-            "traffic_ratio": (traffic / (units * bpq)) if (traffic and units) else None,
-            "traffic_source": ("profiles/traffic_%s.json (PMC pass of this device code, source_sha %s; replayed, not collected in this run)" % (
-                workload, kernel_source_sha())) if traffic else None,
-            "bytes_per_query": bpq, "units_per_launch": units, "kernel_ms": dom_ms,
-            "pipeline_ms": pipeline_ms, "pipeline_achieved": (n * bpq) / (ms_per_step * 1e-3) / 1e9,
-            "step_traffic": step_traffic, "step_traffic_ratio": (step_traffic / (n * bpq)) if (step_traffic and n) else None,
-            "useful_flop_per_query": useful,
-            "useful_flop_frac": (useful * n / (ms_per_step * 1e-3) / (FP32_VECTOR_PEAK_TFLOPS * 1e12)) if useful else None,
-            "kernels_ms": avg, "valu_issue": valu,
-        }
-        if workload in WALK_BYTES and achieved:
-            # The walks read node records that live in L2 / MALL (8 models x 1.28 MB here): the "algorithmic" rate above is what the
-            # LANES consume (an L2-side figure), the HBM-side figure is what the PMC pass saw leave the memory controllers.  Both
-            # against the HBM peak, both stated -- the single `frac` of earlier rounds mixed them.
-            roofline["l2_side"] = {"GBps": _r(achieved, 4), "frac_of_hbm_peak": _r(achieved / HBM_PEAK_GBS, 3),
-                                   "note": "visited node / triangle records x record size / kernel time"}
-            roofline["hbm_side"] = ({"GBps": _r(traffic / (dom_ms * 1e-3) / 1e9, 4), "frac_of_hbm_peak": _r(traffic / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 3),
-                                     "note": "PMC bytes (2 x FETCH_SIZE + WRITE_SIZE) / kernel time"} if traffic else None)
-        cpu = None
-        if not args.no_cpu_baseline and ctx.world == 1 and cpu_budget_s > 0:  # reported on rank 0 at N=1 only
-            cpu = cpu_baseline(ctx, workload, batch, req, cpu_sample, cpu_budget_s, native=cpu_budget_s >= 5.0)
-        if two_streams:
-            # a throughput-of-two-batches figure: the per-kernel durations above come from the one-stream event pass and do
-            # not describe kernels that overlap another batch's, so this row carries no kernel / roofline figure of its own
-            roofline = {"bound": "hbm", "kernel": None, "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None,
-                        "traffic": None, "bytes_per_query": bpq, "pipeline_achieved": roofline["pipeline_achieved"],
-                        "note": "two batches in flight; see the one-stream row of the same workload for the kernels"}
+                units = n
+            split = lib.last_split_parts()
+            units = units / split  # a launch covers one half of a split batch
+            dom_ms = avg.get(dominant, float("nan"))
+            achieved = (units * bpq) / (dom_ms * 1e-3) / 1e9 if dom_ms == dom_ms and dom_ms > 0 else None
+            pipeline_ms = float(sum(avg.values()))
+            traffic, traffic_note = load_traffic(workload, dominant, n)
+            valu_insts, sq = load_traffic(workload, dominant, n, want="valu")
+            valu = None
+            if valu_insts and dom_ms == dom_ms and dom_ms > 0:
+                # the bound that actually applies to the iterative kernels: wave-level VALU instructions issued per
+                # launch (SQ_INSTS_VALU, committed PMC pass of this code) against the MEASURED issue peak over the live kernel duration
+                valu = {"insts_per_launch": valu_insts, "issue_peak_per_s": VALU_ISSUE_PEAK,
+                        "frac": valu_insts / (dom_ms * 1e-3) / VALU_ISSUE_PEAK, "sq_counters_per_launch": sq,
+                        "note": "wave-level VALU instructions / (kernel time x measured chip-wide issue peak, tools/valu_peak.hip); "
+                                "fp64 arithmetic issues at 0.56 of that rate"}
+            names = rocprof_names(workload, dominant)
+            step_traffic = load_step_traffic(workload, n)
+            useful = None
+            if workload in ("cfg3", "cfg3u") and n:
+                g_it = float(abi.status_gjk_iters(status).mean())
+                e_it = float((abi.status_epa_iters(status) * (abi.status_epa(status) != 15)).mean())
+                ran_epa = float((abi.status_epa(status) != 15).mean())
+                useful = g_it * FLOP_GJK_ITER + e_it * FLOP_EPA_ITER + ran_epa * FLOP_EPA_SETUP
+                extra_cfg.update({"mean_gjk_iterations": g_it, "mean_epa_iterations_over_all_pairs": e_it})
+            roofline = {
+                "bound": "hbm", "kernel": (names[0].split("(")[0].replace("void ", "").strip() if names else dominant), "timer_label": dominant,
+                "kernels_under_label": names,
+                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": traffic, "traffic_note": traffic_note,
+                "traffic_ratio": (traffic / (units * bpq)) if (traffic and units) else None,
+                "traffic_source": ("profiles/traffic_%s.json (PMC pass of this device code, source_sha %s; replayed, not collected in this run)" % (
+                    workload, kernel_source_sha())) if traffic else None,
+                "bytes_per_query": bpq, "units_per_launch": units, "kernel_ms": dom_ms,
+                "pipeline_ms": pipeline_ms, "pipeline_achieved": (n * bpq) / (ms_per_step * 1e-3) / 1e9,
+                "step_traffic": step_traffic, "step_traffic_ratio": (step_traffic / (n * bpq)) if (step_traffic and n) else None,
+                "useful_flop_per_query": useful,
+                "useful_flop_frac": (useful * n / (ms_per_step * 1e-3) / (FP32_VECTOR_PEAK_TFLOPS * 1e12)) if useful else None,
+                "kernels_ms": avg, "valu_issue": valu,
+            }
+            if workload in WALK_BYTES and achieved:
+                # The walks read node records that live in L2 / MALL (8 models x 1.28 MB here): the "algorithmic" rate above is what the
+                # LANES consume (an L2-side figure), the HBM-side figure is what the PMC pass saw leave the memory controllers.  Both
+                # against the HBM peak, both stated -- the single `frac` of earlier rounds mixed them.
+                roofline["l2_side"] = {"GBps": _r(achieved, 4), "frac_of_hbm_peak": _r(achieved / HBM_PEAK_GBS, 3),
+                                       "note": "visited node / triangle records x record size / kernel time"}
+                roofline["hbm_side"] = ({"GBps": _r(traffic / (dom_ms * 1e-3) / 1e9, 4), "frac_of_hbm_peak": _r(traffic / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 3),
+                                         "note": "PMC bytes (2 x FETCH_SIZE + WRITE_SIZE) / kernel time"} if traffic else None)
+            if not args.no_cpu_baseline and ctx.world == 1 and cpu_budget_s > 0:  # reported on rank 0 at N=1 only
+                cpu = cpu_baseline(ctx, workload, batch, req, cpu_sample, cpu_budget_s, native=cpu_budget_s >= 5.0)
+            if two_streams:
+                # a throughput-of-two-batches figure: the per-kernel durations above come from the one-stream event pass and do
+                # not describe kernels that overlap another batch's, so this row carries no kernel / roofline figure of its own
+                roofline = {"bound": "hbm", "kernel": None, "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None,
+                            "traffic": None, "bytes_per_query": bpq, "pipeline_achieved": roofline["pipeline_achieved"],
+                            "note": "two batches in flight; see the one-stream row of the same workload for the kernels"}
         result = {
             "workload": batch.name + (" (two batches in flight: even / odd steps on two streams)" if two_streams else ""),
             "tag": workload + ("/strong" if strong else "") + ("/2streams" if two_streams else "") + (
@@ -845,10 +893,11 @@ def main():
     headline_wl = args.workload or "cfg3"
     strong = args.scaling == "strong"
     head = run_workload(ctx, headline_wl, args.pairs, args.steps, args.warmup, strong=strong,
-                        cpu_budget_s=10.0, cpu_sample=args.cpu_sample, host_buffers=args.host_buffers or args.workload is None,  # (the default line: the headline's PCIe-inclusive rate beside it, never `value`)
-                        two_streams=bool(args.two_streams and args.workload and ctx.world == 1))
+                        cpu_budget_s=10.0, cpu_sample=args.cpu_sample,
+                        host_buffers=args.host_buffers or (args.full and args.workload is None),  # (--full: the headline's PCIe-inclusive rate beside it, never `value`)
+                        two_streams=bool(args.two_streams and args.workload and ctx.world == 1), dump_dir=args.dump_outputs)
     secondary = []
-    if args.workload is None and not args.no_secondary:
+    if args.full and args.workload is None and not args.no_secondary:
         sec_steps = max(3, min(args.steps, 10))
         plan = [("cfg2", 0, False, dict(host_buffers=True)), ("cfg4", 0, False, {}), ("cfg5", 0, False, {}),
                 ("cfg5", 10_000_000, True, {}), ("cfg3u", 0, False, {}), ("cfg2f", 0, False, {})]

@@ -4,7 +4,12 @@ import importlib.util
 import io
 import json
 import os
+import subprocess
+import sys
 from contextlib import redirect_stdout
+
+import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -114,3 +119,81 @@ def test_timer_labels_resolve_to_profiler_names():
     assert names and all(("k_bvh_" in n or "k_tri_leaves" in n) and "true>" not in n for n in names)
     assert b._label_matches("k_bvh_collide", "void k_bvh_walk<double>(Work, ...)") and b._label_matches("k_bvh_collide", "void k_tri_leaves<double>(Work")
     assert not b._label_matches("k_bvh_collide", "void k_bvh_collide<double, false, false, true>(Work")
+
+
+def test_plain_run_line():
+    """A run without --full: the contract's fields as they are, `roofline` and `cpu_baseline` null, no secondary rows."""
+    b = _bench()
+    full = _full_record()
+    full.update(roofline=None, cpu_baseline=None)
+    for k in ("secondary", "host_buffers"):
+        full.pop(k, None)
+    d = json.loads(b.compact_line(full))
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup"):
+        assert d[k] == full[k], k
+    assert abs(d["value"] - full["value"]) <= 1e-4 * full["value"] and abs(d["ms_per_step"] - full["ms_per_step"]) <= 1e-4 * full["ms_per_step"]
+    assert d["roofline"] is None and d["cpu_baseline"] is None and "secondary" not in d
+
+
+def test_steps_must_be_positive():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 2 and "--steps" in p.stderr
+
+
+def test_dump_outputs(pkg, tmp_path, monkeypatch):
+    """--dump-outputs: one float32 / float64 file per record field, integer fields exact; above DUMP_LIMIT the same seeded sample of
+    records every time, its indices in index.npy, all files within the limit."""
+    b = _bench()
+    abi = pkg.abi
+    rng = np.random.default_rng(7)
+    rec = np.zeros(1000, dtype=abi.RESULT_DTYPE)
+    rec.view(np.uint8)[:] = rng.integers(0, 256, rec.nbytes, dtype=np.uint8)
+    b.dump_outputs(str(tmp_path / "all"), rec)
+    assert sorted(os.listdir(tmp_path / "all")) == sorted(k + ".npy" for k in abi.RESULT_DTYPE.names)
+    for k in abi.RESULT_DTYPE.names:
+        got = np.load(tmp_path / "all" / (k + ".npy"))
+        assert got.dtype == np.float64 and got.shape == rec[k].shape
+        assert np.array_equal(got, rec[k].astype(np.float64), equal_nan=True)
+    f32 = np.zeros(500, dtype=abi.RESULT_F32_DTYPE)
+    f32["distance"], f32["status"] = rng.standard_normal(500), rng.integers(0, 2**32, 500, dtype=np.uint32)
+    b.dump_outputs(str(tmp_path / "f32"), f32)
+    assert np.load(tmp_path / "f32" / "distance.npy").dtype == np.float32
+    assert np.array_equal(np.load(tmp_path / "f32" / "status.npy"), f32["status"].astype(np.float64))
+    # sampled: room for 100 fp64 records (112 B of fields + 8 B of index each) beside the 1 MB kept for headers
+    monkeypatch.setattr(b, "DUMP_LIMIT", (1 << 20) + 100 * 120)
+    for d in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / d), rec)
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= b.DUMP_LIMIT
+    idx = np.load(tmp_path / "s1" / "index.npy")
+    assert len(idx) == 100 and np.all(np.diff(idx) > 0) and np.array_equal(idx, np.load(tmp_path / "s2" / "index.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "p1.npy"), rec["p1"][idx.astype(np.int64)], equal_nan=True)
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_last_step(pkg, torch_cuda, tmp_path):
+    """bench.py without --full: exactly --steps timed steps, no roofline or CPU baseline, and --dump-outputs holds the records the
+    device entry point returns for the same seeded batch."""
+    torch = torch_cuda
+    env = dict(os.environ, HFCL_BENCH_FULL_DIR=str(tmp_path))
+    for k in ("WORLD_SIZE", "RANK"):
+        env.pop(k, None)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg3", "--pairs", "65537", "--steps", "2",
+                        "--warmup", "1", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600, env=env)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = json.loads(p.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["roofline"] is None and d["cpu_baseline"] is None
+    abi, wl = pkg.abi, pkg.workloads
+    bt = wl.cfg3_convex_convex(n=65537, seed=1)
+    lib = wl.make_library(pkg, bt, device=0)
+    dev = torch.device("cuda", 0)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    out = torch.zeros(len(bt) * 11, dtype=torch.int32, device=dev)
+    lib.distance_device_f32(t(bt.s1.astype(np.int32)), t(bt.s2.astype(np.int32)), t(bt.pose1_f32), t(bt.pose2_f32), len(bt),
+                            wl.make_request(bt, abi), out)
+    torch.cuda.synchronize()
+    want = out.cpu().numpy().view(abi.RESULT_F32_DTYPE)
+    lib.close()
+    for k in abi.RESULT_F32_DTYPE.names:
+        got = np.load(tmp_path / "out" / (k + ".npy"))
+        assert got.dtype == (np.float32 if k != "status" else np.float64)
+        assert np.array_equal(got, want[k].astype(got.dtype), equal_nan=True), k

@@ -79,7 +79,7 @@ def test_two_ranks_on_one_gpu_strong_cfg5(torch_cuda, gather):
     equals the single-rank records of the whole list byte for byte (full and 24-B compact form)."""
     line = _bench(["--gpus", "2", "--backend", "gloo", "--device-map", "0,0", "--workload", "cfg5", "--scaling", "strong",
                    "--pairs", "100001", "--steps", "3", "--warmup", "1", "--gather", gather, "--verify-gather",
-                   "--no-cpu-baseline"])
+                   "--no-cpu-baseline", "--full"])
     cfg = line["config"]
     assert line["n_gpus"] == 2 and line["scaling"] == "strong"
     assert cfg["shard"] == [0, 50001] and cfg["pairs_per_step_all_gpus"] == 100001
@@ -92,10 +92,10 @@ def test_two_ranks_on_one_gpu_strong_cfg5(torch_cuda, gather):
 
 @pytest.mark.gpu
 def test_two_ranks_on_one_gpu_weak_cfg3(torch_cuda):
-    """The headline's N > 1 form as a driver launches it (no extra flag): own batch per rank, fp32 records all-gathered; block checksums
+    """The headline's N > 1 form as a driver launches it with --full (no other flag): own batch per rank, fp32 records all-gathered; block checksums
     of both ranks agree, and every rank's block equals that rank's batch run alone on rank 0, byte for byte."""
     line = _bench(["--gpus", "2", "--backend", "gloo", "--device-map", "0,0", "--workload", "cfg3", "--pairs", "65537",
-                   "--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
+                   "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"])
     cfg = line["config"]
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and cfg["pairs_per_step_all_gpus"] == 2 * 65537
     assert cfg["gather_check"] == {"block_checksums": True, "equals_single_rank_run": True}
@@ -116,7 +116,7 @@ def test_rccl_exchange_branch_with_one_rank(torch_cuda, gather, monkeypatch):
     monkeypatch.setenv("HFCL_BENCH_FORCE_DIST", "1")
     monkeypatch.setenv("MASTER_PORT", "29577")
     line = _bench(["--workload", "cfg3", "--pairs", "65537", "--steps", "5", "--warmup", "1", "--backend", "nccl", "--gather", gather,
-                   "--no-cpu-baseline"])
+                   "--no-cpu-baseline", "--full"])
     cfg = line["config"]
     assert cfg["backend"] == "nccl" and cfg["all_gather_results"] is True and cfg["gather"] == gather
     assert cfg["gather_check"]["block_checksums"] is True

@@ -5,7 +5,7 @@ out=$1; shift
 mkdir -p $out
 for f in 0 1; do
   for n in 100000 1000000; do
-    env HFCL_BVH_FILTER=$f "$@" python bench.py --workload cfg4 --pairs $n --steps 10 --warmup 2 --no-cpu-baseline > $out/cfg4_f${f}_n${n}.json 2> $out/cfg4_f${f}_n${n}.err
+    env HFCL_BVH_FILTER=$f "$@" python bench.py --workload cfg4 --pairs $n --steps 10 --warmup 2 --full --no-cpu-baseline > $out/cfg4_f${f}_n${n}.json 2> $out/cfg4_f${f}_n${n}.err
     python - <<PY
 import json
 l=[x for x in open("$out/cfg4_f${f}_n${n}.json") if x.startswith("{")]

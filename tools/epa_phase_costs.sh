@@ -6,7 +6,7 @@ mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
 bench() {
   local label=$1 wl=$2; shift 2
-  env "$@" timeout 300 python bench.py --workload $wl --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 | python -c "
+  env "$@" timeout 300 python bench.py --workload $wl --full --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 | python -c "
 import json,sys
 try:
     l=json.loads(sys.stdin.read())

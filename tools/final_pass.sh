@@ -17,7 +17,7 @@ for wl in cfg3 cfg4s cfg4 cfg4d cfg5 cfg2 cfg1; do
   if [ $wl = cfg3 ] || [ $wl = cfg4s ]; then
     if [ $(left) -gt 120 ]; then
       rm -rf $out/prof_$wl
-      timeout 110 rocprofv3 --kernel-trace --stats -d $out/prof_$wl -o $wl -- python bench.py --workload $wl --no-cpu-baseline --no-secondary < /dev/null > $out/prof_$wl.log 2>&1
+      timeout 110 rocprofv3 --kernel-trace --stats -d $out/prof_$wl -o $wl -- python bench.py --workload $wl --full --no-cpu-baseline --no-secondary < /dev/null > $out/prof_$wl.log 2>&1
       db=$(find $out/prof_$wl -name "*.db" | head -1)
       if [ -n "$db" ]; then python tools/rocprof_summary.py $db > $out/${wl}_kernel_trace_stats.txt < /dev/null; tail -1 $out/prof_$wl.log | cut -c1-300; fi
       rm -rf $out/prof_$wl
