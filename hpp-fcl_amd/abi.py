@@ -90,6 +90,27 @@ BVH_NODE_DTYPE = np.dtype([("first_child", "<i4"), ("first_primitive", "<i4"), (
 assert BVH_NODE_DTYPE.itemsize == C.sizeof(BvhNode) == 256
 
 
+class PatchRequest(C.Structure):
+    """hfcl_patch_request = ContactPatchRequest (collision_data.h:726-823)."""
+    _fields_ = [("max_num_patch", C.c_uint32), ("num_samples_curved_shapes", C.c_uint32), ("patch_tolerance", C.c_double)]
+
+
+def default_patch_request(max_num_patch=1, num_samples_curved_shapes=12, patch_tolerance=1e-3):
+    """ContactPatchRequest defaults: 1 patch, 12 = ContactPatch::default_preallocated_size samples, tolerance 1e-3."""
+    r = PatchRequest()
+    r.max_num_patch = max_num_patch
+    r.num_samples_curved_shapes = num_samples_curved_shapes
+    r.patch_tolerance = patch_tolerance
+    return r
+
+
+# hfcl_contact_patch: frame (Transform3f image), depth, point count, status
+PATCH_DTYPE = np.dtype([("tf", "<f8", 12), ("penetration_depth", "<f8"), ("num_points", "<u4"), ("status", "<u4")])
+assert PATCH_DTYPE.itemsize == 112
+PATCH_CLASS_NONE, PATCH_CLASS_POINT, PATCH_CLASS_ONESIDED, PATCH_CLASS_CLIPPED = 0, 1, 2, 3
+PATCH_SWAPPED, PATCH_OVERFLOW, PATCH_SKIPPED = 1 << 2, 1 << 3, 1 << 31
+
+
 def compact_records(records):
     """Host-side image of hfcl_compact_results_device: the fields a compact record keeps (bit copies)."""
     f32 = records.dtype == RESULT_F32_DTYPE

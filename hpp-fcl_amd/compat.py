@@ -739,3 +739,175 @@ class DynamicAABBTreeCollisionManager:  # broadphase_dynamic_AABB_tree.h (candid
         for a, b in cand:
             if callback.collide(a, b):
                 break
+
+
+# ---- contact patches: hpp::fcl::computeContactPatch (src/contact_patch.cpp:48-120, collision_data.h:519-980) -------------
+class ContactPatchRequest:  # collision_data.h:726-823
+    def __init__(self, max_num_patch=1, num_samples_curved_shapes=12, patch_tolerance=1e-3):
+        if isinstance(max_num_patch, CollisionRequest):
+            max_num_patch = max_num_patch.num_max_contacts
+        self.max_num_patch = int(max_num_patch)
+        self.setNumSamplesCurvedShapes(num_samples_curved_shapes)
+        self.setPatchTolerance(patch_tolerance)
+
+    def setNumSamplesCurvedShapes(self, n):
+        self._ns = 3 if n < 3 else int(n)
+
+    def getNumSamplesCurvedShapes(self):
+        return self._ns
+
+    def setPatchTolerance(self, tol):
+        self._tol = 1e-12 if tol < 0 else float(tol)
+
+    def getPatchTolerance(self):
+        return self._tol
+
+    def _abi(self):
+        return abi.default_patch_request(self.max_num_patch, self._ns, self._tol)
+
+
+class ContactPatch:  # collision_data.h:519-717 (the patch frame's z axis is the normal; points are 2-D in that frame)
+    DEFAULT, INVERTED = 0, 1
+
+    def __init__(self, preallocated_size=12):
+        self.tf = Transform3f()
+        self.direction = ContactPatch.DEFAULT
+        self.penetration_depth = 0.0
+        self._points = []
+
+    def size(self):
+        return len(self._points)
+
+    def getNormal(self):
+        n = self.tf.getRotation()[:, 2].copy()
+        return -n if self.direction == ContactPatch.INVERTED else n
+
+    def addPoint(self, p3):
+        q = self.tf.getRotation().T @ (_v3(p3) - self.tf.getTranslation())
+        self._points.append(q[:2].copy())
+
+    def point(self, i):
+        if not self._points:
+            raise RuntimeError("Patch is empty.")
+        return self._points[min(i, len(self._points) - 1)]
+
+    def points(self):
+        return list(self._points)
+
+    def getPoint(self, i):
+        p = self.point(i)
+        return self.tf.transform(np.array([p[0], p[1], 0.0]))
+
+    def getPointShape1(self, i):
+        return self.getPoint(i) - (self.penetration_depth / 2) * self.getNormal()
+
+    def getPointShape2(self, i):
+        return self.getPoint(i) + (self.penetration_depth / 2) * self.getNormal()
+
+    def clear(self):
+        self._points = []
+        self.tf = Transform3f()
+        self.penetration_depth = 0.0
+
+    def isSame(self, other, tol=1e-12):  # collision_data.h:660-704
+        def approx(a, b):
+            return np.linalg.norm(a - b) <= tol * min(np.linalg.norm(a), np.linalg.norm(b))
+        if not approx(self.getNormal(), other.getNormal()):
+            return False
+        if abs(self.penetration_depth - other.penetration_depth) > tol or self.direction != other.direction:
+            return False
+        if self.size() != other.size():
+            return False
+        theirs = [other.getPoint(j) for j in range(other.size())]
+        return all(any(approx(self.getPoint(i), q) for q in theirs) for i in range(self.size()))
+
+
+def constructContactPatchFrameFromContact(contact, patch):  # collision_data.h:706-713 (numpy arithmetic: for building expected patches)
+    n = np.asarray(contact.normal, dtype=np.float64)
+    x, y, z = n
+    if not (abs(x) <= abs(z) * 1e-12) or not (abs(y) <= abs(z) * 1e-12):
+        inv = 1.0 / np.sqrt(x * x + y * y)
+        u = np.array([-y * inv, x * inv, 0.0])
+    else:
+        inv = 1.0 / np.sqrt(y * y + z * z)
+        u = np.array([0.0, -z * inv, y * inv])
+    R = np.zeros((3, 3))
+    R[:, 2] = n / np.sqrt(n @ n) if n @ n > 0 else n
+    R[:, 1] = -u
+    R[:, 0] = np.cross(R[:, 1], n)
+    patch.penetration_depth = contact.penetration_depth
+    patch.tf = Transform3f(R, contact.pos)
+    patch.direction = ContactPatch.DEFAULT
+
+
+class ContactPatchResult:  # collision_data.h:826-981
+    def __init__(self, request=None):
+        self._patches = []
+
+    def numContactPatches(self):
+        return len(self._patches)
+
+    def getContactPatch(self, i):
+        if not self._patches:
+            raise ValueError("The number of contact patches is zero. No ContactPatch can be returned.")
+        return self._patches[min(i, len(self._patches) - 1)]
+
+    def contactPatch(self, i):
+        return self.getContactPatch(i)
+
+    def clear(self):
+        self._patches = []
+
+    def set(self, request):
+        self.clear()
+
+
+def computeContactPatch(*args):
+    """computeContactPatch(o1, tf1, o2, tf2, collision_result, request, result) or (obj1, obj2, collision_result, request, result):
+    one patch per contact of the collision result, at most request.max_num_patch, computed on the device from the contacts."""
+    if len(args) == 5:
+        a, b, col_res, request, result = args
+        o1, tf1, o2, tf2 = a.collisionGeometry(), a.getTransform(), b.collisionGeometry(), b.getTransform()
+    else:
+        o1, tf1, o2, tf2, col_res, request, result = args
+    if not col_res.isCollision() or request.max_num_patch == 0:  # src/contact_patch.cpp:54-57
+        return
+    result.set(request)
+    if not engine.patch_supported(int(o1.getNodeType()), int(o2.getNodeType())):
+        raise ValueError("Contact patch computation between node type %d and node type %d is not yet supported." %
+                         (o1.getNodeType(), o2.getNodeType()))
+    ctx = _context()
+    i1, i2 = ctx.add(o1), ctx.add(o2)
+    lib = ctx.library()
+    contacts = col_res.getContacts()[:request.max_num_patch]
+    n = len(contacts)
+    rec = np.zeros(n, dtype=abi.RESULT_DTYPE)
+    for k, c in enumerate(contacts):
+        rec[k]["distance"] = c.penetration_depth
+        rec[k]["normal"] = c.normal
+        rec[k]["p1"], rec[k]["p2"] = c.nearest_points
+        rec[k]["b1"], rec[k]["b2"] = c.b1, c.b2
+        rec[k]["num_contacts"] = 1
+    guess = np.zeros(n, dtype=abi.GUESS_DTYPE)
+    guess["support_guess"] = np.asarray(col_res.cached_support_func_guess, dtype=np.int32)
+    tfa = np.repeat(tf1._abi().reshape(1, 12), n, axis=0)
+    tfb = np.repeat(tf2._abi().reshape(1, 12), n, axis=0)
+    out, pts = lib.contact_patch(np.full(n, i1, np.uint32), np.full(n, i2, np.uint32), tfa, tfb, rec, guess, request._abi())
+    for k in range(n):
+        p = ContactPatch()
+        tf = out["tf"][k]
+        p.tf = Transform3f(tf[:9].reshape(3, 3).T, tf[9:12])
+        p.penetration_depth = float(out["penetration_depth"][k])
+        p._points = [pts[k, j].copy() for j in range(int(out["num_points"][k]))]
+        result._patches.append(p)
+
+
+class ComputeContactPatch:  # contact_patch.h:80-120
+    def __init__(self, o1, o2):
+        if not engine.patch_supported(int(o1.getNodeType()), int(o2.getNodeType())):
+            raise ValueError("Contact patch computation between node type %d and node type %d is not yet supported." %
+                             (o1.getNodeType(), o2.getNodeType()))
+        self.o1, self.o2 = o1, o2
+
+    def __call__(self, tf1, tf2, collision_result, request, result):
+        return computeContactPatch(self.o1, tf1, self.o2, tf2, collision_result, request, result)

@@ -81,3 +81,32 @@ template <typename T> void launch_bvh_shape_distance_fast(int grid, int grid_fin
 template <typename T> void launch_bvh_shape_fast(int grid, int grid_finish, int coop_grid, hipStream_t st, const Work& wk, const LibView<T>& lv, const BvhView<T>& bv, const IO<T>& io, const QParams<T>& q, const BvhParams& bp, T break_distance2, BvhSplit split, BvhSpill spill, const AsideStream* aside = nullptr);
 template <typename T> void launch_bvh_shape_distance(int grid, hipStream_t st, const Work& wk, const LibView<T>& lv, const BvhView<T>& bv, const IO<T>& io, const QParams<T>& q);
 template <typename T> void launch_triangle(int grid, hipStream_t st, const Work& wk, const LibView<T>& lv, const IO<T>& io, const QParams<T>& q);
+
+// hfcl_k_patch.hip: contact patches of collide() records (hfcl_contact_patch_batch*).  lists: 2 x n record ids (one-sided,
+// clipped), counts: their 2 lengths, zeroed by the caller; ws: nslots workspace slots of slot_bytes (hfcl_patch.hpp: PatchWs)
+struct PatchArgs {
+  const uint32_t* s1;
+  const uint32_t* s2;
+  const double* tf1;
+  const double* tf2;
+  const hfcl_result* rec;
+  const hfcl_guess* guess;
+  uint32_t n, n_shapes;
+  const DShape<double>* shapes;
+  const double* verts;
+  const uint32_t* graph_base;
+  const uint32_t* graph_off;
+  const uint32_t* graph_ent;  // NbrEntry<double> image as 32-bit words
+  uint32_t max_num_patch, num_samples;
+  double tol;
+  uint32_t pcap, plim;  // points per record in out_pts (row stride), points a record may have
+  hfcl_contact_patch* out;
+  double* out_pts;
+  uint32_t* lists;
+  uint32_t* counts;
+  char* ws;
+  size_t slot_bytes;
+  uint32_t nslots, cap, cloud_cap, vis_cap;
+};
+// three launches (classify, one-sided, clipped); names / e0 / e1: three entries (e0 == nullptr: no timing)
+void launch_patch(hipStream_t st, const PatchArgs& a, int max_blocks, const char** names, hipEvent_t* e0, hipEvent_t* e1);

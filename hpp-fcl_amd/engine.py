@@ -28,6 +28,8 @@ EXPORTED_SYMBOLS = [
     "hfcl_multi_set_shapes", "hfcl_multi_set_convex_neighbors", "hfcl_multi_add_bvh", "hfcl_collide_batch_multi", "hfcl_distance_batch_multi",
     "hfcl_collide_batch_multi_device", "hfcl_distance_batch_multi_device", "hfcl_collide_batch_multi_f32", "hfcl_distance_batch_multi_f32",
     "hfcl_lib_set_option", "hfcl_lib_option_key", "hfcl_has_ab_forms", "hfcl_multi_set_option", "hfcl_multi_last_gather",
+    "hfcl_contact_patch_request_init", "hfcl_patch_supported", "hfcl_contact_patch_max_points", "hfcl_contact_patch_max_points_shapes",
+    "hfcl_contact_patch_batch", "hfcl_contact_patch_batch_device",
 ]
 
 
@@ -84,6 +86,27 @@ def last_error():
 
 def device_count():
     return int(dll().hfcl_device_count())
+
+
+def patch_supported(t1, t2):
+    """hfcl_patch_supported: does computeContactPatch have a function for (node_type1, node_type2)?"""
+    return bool(dll().hfcl_patch_supported(C.c_int32(int(t1)), C.c_int32(int(t2))))
+
+
+def contact_patch_request_init():
+    """hfcl_contact_patch_request_init: the C library's ContactPatchRequest defaults."""
+    r = abi.PatchRequest()
+    dll().hfcl_contact_patch_request_init(C.byref(r))
+    return r
+
+
+def contact_patch_max_points_shapes(shapes, req=None):
+    """hfcl_contact_patch_max_points_shapes: the patch-size bound of a shape table (no device needed)."""
+    shapes = np.ascontiguousarray(shapes)
+    cap = C.c_uint32(0)
+    _check(dll().hfcl_contact_patch_max_points_shapes(abi.ptr(shapes), C.c_size_t(len(shapes)),
+                                                      C.byref(req or abi.default_patch_request()), C.byref(cap)))
+    return int(cap.value)
 
 
 def has_ab_forms():
@@ -323,6 +346,48 @@ class Library:
         _check(dll().hfcl_collide_batch_device_f32(self._h, _dptr(d_s1), _dptr(d_s2), _dptr(d_pose1),
                                                     _dptr(d_pose2), C.c_size_t(n), C.byref(req), _dptr(d_out),
                                                     C.c_void_p(stream)))
+
+    # ---- contact patches of collide() records (hfcl_contact_patch_batch*) ----
+    def contact_patch_max_points(self, req=None):
+        """Upper bound on the points of any patch of this library under `req` (hfcl_contact_patch_max_points)."""
+        cap = C.c_uint32(0)
+        _check(dll().hfcl_contact_patch_max_points(self._h, C.byref(req or abi.default_patch_request()), C.byref(cap)))
+        return int(cap.value)
+
+    def contact_patch(self, s1, s2, tf1, tf2, records, guesses=None, req=None, points_capacity=None):
+        """Batched hpp::fcl::computeContactPatch on the records of collide() for the same pairs.  Returns
+        (patches[PATCH_DTYPE], points (n, points_capacity, 2) float64 in each patch's frame).  guesses: the
+        GUESS_DTYPE records collide(..., want_guess=True) returned, or None."""
+        req = req or abi.default_patch_request()
+        s1 = np.ascontiguousarray(s1, dtype=np.uint32)
+        s2 = np.ascontiguousarray(s2, dtype=np.uint32)
+        tf1 = np.ascontiguousarray(tf1, dtype=np.float64).reshape(-1, 12)
+        tf2 = np.ascontiguousarray(tf2, dtype=np.float64).reshape(-1, 12)
+        records = np.ascontiguousarray(records, dtype=abi.RESULT_DTYPE)
+        n = len(s1)
+        if not (len(s2) == len(tf1) == len(tf2) == len(records) == n):
+            raise ValueError("batch arrays must have equal length")
+        if guesses is not None:
+            guesses = np.ascontiguousarray(guesses, dtype=abi.GUESS_DTYPE)
+            if len(guesses) != n:
+                raise ValueError("guesses must have one record per pair")
+        if points_capacity is None:
+            points_capacity = self.contact_patch_max_points(req)
+        out = np.zeros(n, dtype=abi.PATCH_DTYPE)
+        pts = np.zeros((n, int(points_capacity), 2), dtype=np.float64)
+        _check(dll().hfcl_contact_patch_batch(self._h, abi.ptr(s1), abi.ptr(s2), abi.ptr(tf1), abi.ptr(tf2), abi.ptr(records),
+                                              abi.ptr(guesses), C.c_size_t(n), C.byref(req), C.c_uint32(int(points_capacity)),
+                                              abi.ptr(out), abi.ptr(pts)))
+        return out, pts
+
+    def contact_patch_device(self, d_s1, d_s2, d_tf1, d_tf2, d_records, n, req, points_capacity, d_out, d_points,
+                             d_guesses=None, stream=0):
+        """hfcl_contact_patch_batch_device: device buffers (torch tensors or pointers), asynchronous on `stream`.
+        d_out: n * 112 bytes (PATCH_DTYPE records), d_points: n * points_capacity * 2 doubles."""
+        _check(dll().hfcl_contact_patch_batch_device(self._h, _dptr(d_s1), _dptr(d_s2), _dptr(d_tf1), _dptr(d_tf2),
+                                                     _dptr(d_records), _dptr(d_guesses), C.c_size_t(n), C.byref(req),
+                                                     C.c_uint32(int(points_capacity)), _dptr(d_out), _dptr(d_points),
+                                                     C.c_void_p(stream)))
 
     def compact_results_device(self, d_records, n, d_out, f32=False, stream=0):
         """Full device records -> hfcl_result_compact{,_f32} records (24 / 8 B): the multi-GPU exchange format."""

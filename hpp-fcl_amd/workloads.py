@@ -534,3 +534,219 @@ def make_request(batch, abi, **kw):
         else:
             setattr(req.q, k, v)
     return req
+
+
+# ---- resting contacts (contact patches) ------------------------------------------------------------------------------------
+def _rot_axis_angle(axis, ang):
+    a = np.asarray(axis, dtype=np.float64)
+    a = a / np.linalg.norm(a)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    return np.eye(3) + np.sin(ang) * K + (1 - np.cos(ang)) * (K @ K)
+
+
+def _rot_from_to(u, v):
+    """A rotation taking unit vector u onto unit vector v."""
+    u, v = np.asarray(u, float) / np.linalg.norm(u), np.asarray(v, float) / np.linalg.norm(v)
+    c = float(u @ v)
+    w = np.cross(u, v)
+    if np.linalg.norm(w) < 1e-12:
+        if c > 0:
+            return np.eye(3)
+        p = np.cross(u, [1.0, 0, 0]) if abs(u[0]) < 0.9 else np.cross(u, [0, 1.0, 0])
+        return _rot_axis_angle(p, np.pi)
+    return _rot_axis_angle(w, np.arctan2(np.linalg.norm(w), c))
+
+
+def _local_support(s, verts, d):
+    """Support point of a library shape in its own frame along d (swept-sphere radius included)."""
+    from . import abi
+    k, p = int(s["type"]), s["params"]
+    dn = d / np.linalg.norm(d)
+    if k == abi.GEOM_BOX:
+        r = np.sign(d) * p[:3]
+    elif k == abi.GEOM_SPHERE:
+        r = p[0] * dn
+    elif k == abi.GEOM_ELLIPSOID:
+        v = p[:3] ** 2 * d
+        r = v / np.sqrt(v @ d)
+    elif k == abi.GEOM_CAPSULE:
+        r = np.array([0, 0, np.sign(d[2]) * p[1]]) + p[0] * dn
+    elif k in (abi.GEOM_CONE, abi.GEOM_CYLINDER):
+        rad, h = p[0], p[1]
+        xy = np.hypot(d[0], d[1])
+        rim = np.array([0.0, 0.0]) if xy < 1e-15 else rad * d[:2] / xy
+        if k == abi.GEOM_CYLINDER:
+            r = np.array([rim[0], rim[1], np.sign(d[2]) * h])
+        else:
+            tip, base = np.array([0, 0, h]), np.array([rim[0], rim[1], -h])
+            r = tip if tip @ d >= base @ d else base
+    elif k in (abi.GEOM_CONVEX, abi.GEOM_TRIANGLE):
+        o, n = int(s["vertex_offset"]), int(s["num_points"]) if k == abi.GEOM_CONVEX else 3
+        V = verts[o:o + n]
+        r = V[int(np.argmax(V @ d))]
+    else:
+        raise ValueError(k)
+    return r + float(s["swept_sphere_radius"]) * dn
+
+
+def _face_normals(s, verts, rng):
+    """Local outward normals of flat faces of a shape (for face-on-face placements); None: any direction."""
+    from . import abi
+    k = int(s["type"])
+    if k == abi.GEOM_BOX:
+        return np.concatenate([np.eye(3), -np.eye(3)])
+    if k == abi.GEOM_CYLINDER:
+        return np.array([[0, 0, 1.0], [0, 0, -1.0], [1.0, 0, 0]])
+    if k == abi.GEOM_CONE:
+        return np.array([[0, 0, -1.0], [1.0, 0, 0]])
+    if k == abi.GEOM_CAPSULE:
+        return np.array([[1.0, 0, 0], [0, 1.0, 0]])
+    if k == abi.GEOM_CONVEX:
+        from scipy.spatial import ConvexHull
+        o, n = int(s["vertex_offset"]), int(s["num_points"])
+        eq = ConvexHull(verts[o:o + n]).equations[:, :3]
+        return eq[rng.permutation(len(eq))[:8]]
+    if k == abi.GEOM_TRIANGLE:
+        o = int(s["vertex_offset"])
+        a, b, c = verts[o:o + 3]
+        nrm = np.cross(b - a, c - a)
+        nrm /= np.linalg.norm(nrm)
+        return np.array([nrm, -nrm])
+    return None
+
+
+def resting_library(seed=1, nper=8):
+    """Every primitive kind (box, sphere, capsule, cone, cylinder, ellipsoid, triangle, plane, halfspace), 32- and 64-vertex
+    hulls (random, and prisms with large coplanar faces).  Returns (ShapeLibrary, ids of 64-vertex hulls)."""
+    rng = _rng(seed, 21)
+    lib = geometry.ShapeLibrary()
+    for s in rng.uniform(0.2, 0.8, (nper, 3)):
+        lib.add_box(*map(float, s))
+    for r in rng.uniform(0.2, 0.6, nper):
+        lib.add_sphere(float(r))
+    for r, lz in zip(rng.uniform(0.1, 0.4, nper), rng.uniform(0.2, 0.8, nper)):
+        lib.add_capsule(float(r), float(lz))
+    for r, lz in zip(rng.uniform(0.2, 0.6, nper), rng.uniform(0.2, 0.8, nper)):
+        lib.add_cone(float(r), float(lz))
+    for r, lz in zip(rng.uniform(0.2, 0.6, nper), rng.uniform(0.2, 0.8, nper)):
+        lib.add_cylinder(float(r), float(lz))
+    for r in rng.uniform(0.2, 0.6, (nper, 3)):
+        lib.add_ellipsoid(*map(float, r))
+    for _ in range(nper):
+        t = rng.uniform(-0.6, 0.6, (3, 3))
+        lib.add_triangle(t[0], t[1], t[2])
+    large = []
+    for nv in (32, 64):
+        for radii in rng.uniform(0.3, 0.8, (nper // 2, 3)):
+            d = rng.normal(size=(nv, 3))
+            i = lib.add_convex(d / np.linalg.norm(d, axis=1, keepdims=True) * radii)
+            if nv > 32:
+                large.append(len(lib) - 1)
+        for r, h in zip(rng.uniform(0.3, 0.7, nper // 2), rng.uniform(0.2, 0.6, nper // 2)):
+            m = nv // 2
+            a = 2 * np.pi * np.arange(m) / m
+            ring = np.stack([r * np.cos(a), r * np.sin(a)], axis=1)
+            lib.add_convex(np.concatenate([np.c_[ring, np.full(m, h)], np.c_[ring, np.full(m, -h)]]))
+            if nv > 32:
+                large.append(len(lib) - 1)
+    for _ in range(nper // 2):
+        nrm = rng.normal(size=3)
+        lib.add_halfspace(nrm, float(rng.uniform(-0.3, 0.3)))
+        lib.add_plane(rng.normal(size=3), float(rng.uniform(-0.3, 0.3)))
+    return lib, large
+
+
+def resting_contacts(n=20_000, seed=1, nper=8, tilt=3e-3, mesh_frac=0.0):
+    """Shape 2 resting on shape 1 along a face normal of shape 1 (random yaw, penetration 1e-4 .. 1e-2, tilts of the order
+    of patch_tolerance so that support sets gain and lose points), both operand orders.  Random poses almost never give
+    face contacts; these do.  The batch's `large` lists the hulls of more than 32 vertices (register_adjacency).
+    mesh_frac > 0: that fraction of the pairs are BVHModel<OBBRSS> rows instead -- mesh x solid, solid x mesh and mesh x mesh,
+    a small bumpy sphere (radius ~1) against a shape or another mesh placed near its surface (their patches are points; the
+    batch's `meshes` go to make_library)."""
+    from . import abi
+    rng = _rng(seed, 22)
+    lib, large = resting_library(seed, nper)
+    shapes, verts = lib.shapes_array(), lib.vertices_array()
+    flat = np.isin(shapes["type"], [abi.GEOM_PLANE, abi.GEOM_HALFSPACE])
+    solid_ids = np.flatnonzero(~flat)
+    all_ids = np.arange(len(shapes))
+    s1 = rng.choice(all_ids, n)
+    s2 = rng.choice(solid_ids, n)
+    R1s, T1s, R2s, T2s = np.empty((n, 3, 3)), np.empty((n, 3)), np.empty((n, 3, 3)), np.empty((n, 3))
+    for i in range(n):
+        a, b = shapes[s1[i]], shapes[s2[i]]
+        R1 = geometry.quat_to_matrix(uniform_quaternions(rng, 1))[0]
+        T1 = rng.uniform(-0.5, 0.5, 3)
+        if flat[s1[i]]:
+            nl = np.asarray(a["params"][:3], dtype=np.float64)
+            up_l = nl
+            h1 = float(a["params"][3]) + float(a["swept_sphere_radius"])
+        else:
+            fn = _face_normals(a, verts, rng)
+            up_l = fn[rng.integers(len(fn))] if fn is not None else rng.normal(size=3)
+            up_l = up_l / np.linalg.norm(up_l)
+            h1 = float(_local_support(a, verts, up_l) @ up_l)
+        up = R1 @ up_l
+        fn2 = _face_normals(b, verts, rng)
+        down_l = fn2[rng.integers(len(fn2))] if fn2 is not None else rng.normal(size=3)
+        down_l = down_l / np.linalg.norm(down_l)
+        R2 = _rot_axis_angle(up, rng.uniform(0, 2 * np.pi)) @ _rot_from_to(down_l, -up)
+        R2 = _rot_axis_angle(np.cross(up, rng.normal(size=3)), rng.uniform(0, tilt)) @ R2
+        h2 = float(_local_support(b, verts, R2.T @ -up) @ (R2.T @ -up))
+        depth = 10 ** rng.uniform(-4, -2)
+        lateral = rng.normal(size=3) * 0.05
+        lateral -= (lateral @ up) * up
+        T2 = T1 + (h1 - depth + h2) * up + lateral
+        R1s[i], T1s[i], R2s[i], T2s[i] = R1, T1, R2, T2
+    swap = rng.random(n) < 0.5
+    s1o, s2o = np.where(swap, s2, s1), np.where(swap, s1, s2)
+    R1o, R2o = np.where(swap[:, None, None], R2s, R1s), np.where(swap[:, None, None], R1s, R2s)
+    T1o, T2o = np.where(swap[:, None], T2s, T1s), np.where(swap[:, None], T1s, T2s)
+    meshes = None
+    m = int(round(n * mesh_frac))
+    if m > 0:
+        meshes = mesh_variants(2, seg=14, ring=14)
+        bvh_ids = [lib.add_bvh(k, len(mm.vertices)) for k, mm in enumerate(meshes)]
+        u = rng.random(m)
+        mesh_a = rng.choice(bvh_ids, m)
+        mesh_b = rng.choice(bvh_ids, m)
+        # (TriangleP has no collide() function against a BVHModel: collision_func_matrix.cpp)
+        solid = rng.choice(solid_ids[shapes["type"][solid_ids] != abi.GEOM_TRIANGLE], m)
+        first = np.where(u < 0.4, mesh_a, np.where(u < 0.8, solid, mesh_a))
+        second = np.where(u < 0.4, solid, np.where(u < 0.8, mesh_a, mesh_b))
+        d = rng.normal(size=(m, 3))
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        gap = np.where(u < 0.8, rng.uniform(0.9, 1.3, m), rng.uniform(1.7, 2.1, m))  # near the ~1-radius surface
+        Ta = rng.uniform(-0.5, 0.5, (m, 3))
+        s1o[:m], s2o[:m] = first, second
+        R1o[:m] = geometry.quat_to_matrix(uniform_quaternions(rng, m))
+        R2o[:m] = geometry.quat_to_matrix(uniform_quaternions(rng, m))
+        T1o[:m], T2o[:m] = Ta, Ta + gap[:, None] * d
+    b = RestingBatch(lib, s1o, s2o, geometry.make_pose(R=R1o, T=T1o), geometry.make_pose(R=R2o, T=T2o), large)
+    b.meshes = meshes
+    return b
+
+
+class RestingBatch:
+    """collide() pairs with Transform3f poses (no quaternions): resting_contacts."""
+
+    def __init__(self, lib, s1, s2, tf1, tf2, large):
+        self.name, self.kind, self.lib = "resting_contacts", "collide", lib
+        self.shapes, self.verts = lib.shapes_array(), lib.vertices_array()
+        self.s1, self.s2 = np.ascontiguousarray(s1, dtype=np.uint32), np.ascontiguousarray(s2, dtype=np.uint32)
+        self.tf1, self.tf2 = np.ascontiguousarray(tf1), np.ascontiguousarray(tf2)
+        self.large = large
+        self.meshes = None
+        self.request_overrides = {}
+
+    def __len__(self):
+        return len(self.s1)
+
+    def graphs(self):
+        """{shape id: (offsets, ids)} of the hulls of more than 32 vertices (what register_adjacency registers)."""
+        out = {}
+        for i in self.large:
+            s = self.shapes[i]
+            o, k = int(s["vertex_offset"]), int(s["num_points"])
+            out[i] = hull_adjacency(self.verts[o:o + k])
+        return out

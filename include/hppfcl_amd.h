@@ -503,6 +503,73 @@ int hfcl_distance_batch_multi_device(hfcl_multi* m, const uint32_t* const* d_sha
  * (ranks - 1) * bytes_per_rank / ms (what each rank receives; DESIGN.md section 5 holds it against 153 GB/s per xGMI link). */
 int hfcl_multi_last_gather(hfcl_multi* m, int* ranks, double* ms, size_t* bytes_per_rank);
 
+/* ---- contact patches of collide() records: hpp::fcl::computeContactPatch (src/contact_patch.cpp:48-97) ----------------
+ * The contact polygon of a colliding pair (e.g. the four corners of a box resting on a table), computed from the record that
+ * hfcl_collide_batch* produced for it.  One record gives at most one patch: a shape pair has at most one contact.  For the
+ * contacts of a mesh pair (hfcl_collide_batch_contacts) pass one record per contact with the pair repeated; that is how
+ * ContactPatchRequest::max_num_patch > 1 is served.
+ *
+ * ContactPatchRequest, collision_data.h:726-823 (same names, same defaults; hfcl_contact_patch_request_init).  The
+ * reference's setters' clamps are applied by the entry points: num_samples_curved_shapes < 3 is taken as 3,
+ * patch_tolerance < 0 as 1e-12. */
+typedef struct hfcl_patch_request {
+  uint32_t max_num_patch;              /* 1 ; 0: no patch for any record                                   */
+  uint32_t num_samples_curved_shapes;  /* 12 = ContactPatch::default_preallocated_size (cone / cylinder bases) */
+  double   patch_tolerance;            /* 1e-3                                                             */
+} hfcl_patch_request;
+/* One patch (ContactPatch, collision_data.h:519-717).  tf: the patch frame, memory image of Transform3f (12 doubles as the
+ * poses above): column 2 is the normal, the origin is Contact::pos = (p1 + p2) / 2.  The points (ContactPatch::m_points) are
+ * 2-D, in that frame, in a separate caller buffer: record i owns out_points[i * points_capacity * 2 ...], num_points (x, y)
+ * pairs of it.  num_points == 0: no patch (no collision, skipped record, max_num_patch == 0).
+ * Reproduced on purpose:
+ *  - GEOM x BVH pairs run as (BVH, GEOM) and are then mirrored (ContactPatchResult::swapObjects, collision_data.h:968-980):
+ *    columns 0 and 2 of tf are negated, so the normal of such a patch is -Contact::normal (status bit HFCL_PATCH_SWAPPED).
+ *  - Two segments (capsule / cone / cylinder edges, contact_patch_solver.hxx:149-150): the reference's `det` is the boolean
+ *    (b0-a0)(d1-c1) >= (b1-a1)(d0-c0) converted to 0 / 1; whenever that comparison holds the patch is the single point
+ *    Contact::pos. */
+typedef struct hfcl_contact_patch {
+  double   tf[12];
+  double   penetration_depth;
+  uint32_t num_points;
+  uint32_t status;          /* bits 0..1 class (HFCL_PATCH_CLASS_*), HFCL_PATCH_SWAPPED, HFCL_PATCH_OVERFLOW, HFCL_PATCH_SKIPPED */
+} hfcl_contact_patch;       /* 112 bytes */
+enum { HFCL_PATCH_CLASS_NONE = 0, HFCL_PATCH_CLASS_POINT = 1, HFCL_PATCH_CLASS_ONESIDED = 2, HFCL_PATCH_CLASS_CLIPPED = 3 };
+#define HFCL_PATCH_SWAPPED  (1u << 2)   /* GEOM x BVH: the frame is mirrored as above                                      */
+#define HFCL_PATCH_OVERFLOW (1u << 3)   /* a support set outgrew points_capacity (not with the bound below): 0 points      */
+#define HFCL_PATCH_SKIPPED  (1u << 31)  /* device form: a shape id outside the library; 0 points                           */
+void hfcl_contact_patch_request_init(hfcl_patch_request* r);
+/* 1 if computeContactPatch has a function for (node_type1, node_type2) (src/contact_patch_func_matrix.cpp): every pair of
+ * the 10 primitives, HFCL_BV_OBBRSS x primitive in both orders and HFCL_BV_OBBRSS x HFCL_BV_OBBRSS.  Host-only. */
+int hfcl_patch_supported(int32_t node_type1, int32_t node_type2);
+/* Upper bound on the points of any patch of this library under `req`: the largest support set of a first operand plus the
+ * largest of a second (Sutherland-Hodgman's output has at most n1 + n2 points).  Set sizes: box 4, triangle 3, capsule 2,
+ * cone and cylinder max(num_samples_curved_shapes, 2), convex num_points, sphere / ellipsoid / plane / halfspace / BVH 1.
+ * Host-only, needs no device. */
+int hfcl_contact_patch_max_points(const hfcl_lib* lib, const hfcl_patch_request* req, uint32_t* cap);
+/* The same bound for a shape table (what hfcl_lib_create would be given); needs no library and no device. */
+int hfcl_contact_patch_max_points_shapes(const hfcl_shape* shapes, size_t n_shapes, const hfcl_patch_request* req, uint32_t* cap);
+/* Patches of n records, host arrays.  shape1 / shape2 / tf1 / tf2 / records: what went into and came out of
+ * hfcl_collide_batch for the same pairs; guesses: NULL or the hfcl_guess records that call returned (guess_out): the
+ * cached support guesses seed the neighbour walk of convex shapes of more than 32 vertices with registered neighbours, as
+ * the reference seeds it with CollisionResult::cached_support_func_guess (NULL: 0, 0).  points_capacity: points per record
+ * in out_points; below the batch's need -- the largest set of its first operand plus the largest of its second over the
+ * records -- the call returns HFCL_ERR_LIMIT before any work and leaves the outputs untouched (never truncates).
+ * HFCL_ERR_INVALID_ARGUMENT for a shape id outside the library, HFCL_ERR_UNSUPPORTED_PAIR for a pair
+ * hfcl_patch_supported refuses, HFCL_ERR_NO_DEVICE without a device.  The points of a row past its num_points are written
+ * as zeros.  Blocking. */
+int hfcl_contact_patch_batch(hfcl_lib* lib, const uint32_t* shape1, const uint32_t* shape2, const double* tf1, const double* tf2,
+                             const hfcl_result* records, const hfcl_guess* guesses, size_t n, const hfcl_patch_request* req,
+                             uint32_t points_capacity, hfcl_contact_patch* out, double* out_points);
+/* The same with device pointers on the library's device, asynchronous on `stream` (hipStream_t as void*): chains straight
+ * after hfcl_collide_batch_device on one stream.  points_capacity must be at least hfcl_contact_patch_max_points (the shape
+ * ids are not read on the host).  A record whose shape id is outside the library gets 0 points and HFCL_PATCH_SKIPPED.
+ * The points of a row past its num_points are left as they were.
+ * The library's patch workspace is shared by the calls on it: calls on different streams must not overlap. */
+int hfcl_contact_patch_batch_device(hfcl_lib* lib, const uint32_t* d_shape1, const uint32_t* d_shape2, const double* d_tf1,
+                                    const double* d_tf2, const hfcl_result* d_records, const hfcl_guess* d_guesses, size_t n,
+                                    const hfcl_patch_request* req, uint32_t points_capacity, hfcl_contact_patch* d_out,
+                                    double* d_out_points, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

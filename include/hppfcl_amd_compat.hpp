@@ -655,9 +655,8 @@ class BatchQueries {
   const std::vector<hfcl_contact>& contacts() const { return contacts_; }  // filled when num_max_contacts > 1 on meshes
   const std::vector<hfcl_guess>& guesses() const { return guess_; }
 
-  void run(const std::vector<std::pair<uint32_t, uint32_t>>& pairs, const std::vector<Transform3f>& tf1,
-           const std::vector<Transform3f>& tf2, const CollisionRequest* creq, const DistanceRequest* dreq) {
-    if (tf1.size() != pairs.size() || tf2.size() != pairs.size()) throw std::invalid_argument("pairs/poses size mismatch");
+  /// The device library brought up to date with every geometry registered so far (created on first use).
+  void prepare() {
     if (!lib_) {
       lib_ = hfcl_multi_create(devices_.data(), static_cast<int>(devices_.size()), shapes_.data(), shapes_.size(), verts_.data(), verts_.size() / 3);
       if (!lib_) throw std::runtime_error(hfcl_last_error());
@@ -680,6 +679,16 @@ class BatchQueries {
                              r.tris.size() / 3) < 0)
         throw std::runtime_error(hfcl_last_error());
     }
+  }
+  /// The library of the first device (up to date): what the contact-patch calls run on.
+  hfcl_lib* library() {
+    prepare();
+    return hfcl_multi_replica(lib_, 0);
+  }
+  void run(const std::vector<std::pair<uint32_t, uint32_t>>& pairs, const std::vector<Transform3f>& tf1,
+           const std::vector<Transform3f>& tf2, const CollisionRequest* creq, const DistanceRequest* dreq) {
+    if (tf1.size() != pairs.size() || tf2.size() != pairs.size()) throw std::invalid_argument("pairs/poses size mismatch");
+    prepare();
     std::vector<uint32_t> s1(pairs.size()), s2(pairs.size());
     for (size_t i = 0; i < pairs.size(); ++i) {
       s1[i] = pairs[i].first;
@@ -832,6 +841,151 @@ class ComputeDistance {
  protected:
   const CollisionGeometry* o1;
   const CollisionGeometry* o2;
+};
+
+// ---------------------------------------------------------------------------------------------
+// Contact patches (hpp-fcl 3.0: include/hpp/fcl/contact_patch.h, collision_data.h:519-981), forwarded to
+// hfcl_contact_patch_batch on the thread's default context: one patch per contact of the collision result.
+// ---------------------------------------------------------------------------------------------
+struct ContactPatchRequest {  // collision_data.h:726-823
+  size_t max_num_patch;
+  explicit ContactPatchRequest(size_t max_num_patch_ = 1, size_t num_samples_curved_shapes = 12, FCL_REAL patch_tolerance = 1e-3)
+      : max_num_patch(max_num_patch_) {
+    setNumSamplesCurvedShapes(num_samples_curved_shapes);
+    setPatchTolerance(patch_tolerance);
+  }
+  void setNumSamplesCurvedShapes(size_t n) { ns_ = n < 3 ? 3 : n; }
+  size_t getNumSamplesCurvedShapes() const { return ns_; }
+  void setPatchTolerance(FCL_REAL t) { tol_ = t < 0 ? 1e-12 : t; }
+  FCL_REAL getPatchTolerance() const { return tol_; }
+
+ private:
+  size_t ns_ = 12;
+  FCL_REAL tol_ = 1e-3;
+};
+
+struct ContactPatch {  // collision_data.h:519-717: frame (z = normal), depth, 2-D points in the frame
+  enum PatchDirection { DEFAULT = 0, INVERTED = 1 };
+  Transform3f tf;
+  PatchDirection direction = DEFAULT;
+  FCL_REAL penetration_depth = 0;
+  std::vector<std::array<FCL_REAL, 2>> m_points;
+  size_t size() const { return m_points.size(); }
+  Vec3f getNormal() const {
+    const Matrix3f& R = tf.getRotation();
+    const Vec3f n(R(0, 2), R(1, 2), R(2, 2));
+    return direction == INVERTED ? -n : n;
+  }
+  void addPoint(const Vec3f& p) {  // tf.inverseTransform(p).head<2>()
+    const Matrix3f& R = tf.getRotation();
+    const Vec3f d = p - tf.getTranslation();
+    m_points.push_back({{R(0, 0) * d[0] + R(1, 0) * d[1] + R(2, 0) * d[2], R(0, 1) * d[0] + R(1, 1) * d[1] + R(2, 1) * d[2]}});
+  }
+  Vec3f getPoint(size_t i) const {
+    if (m_points.empty()) throw std::logic_error("Patch is empty.");
+    const auto& q = m_points[i < m_points.size() ? i : m_points.size() - 1];
+    return tf.transform(Vec3f(q[0], q[1], 0));
+  }
+  Vec3f getPointShape1(size_t i) const { return getPoint(i) - getNormal() * (penetration_depth / 2); }
+  Vec3f getPointShape2(size_t i) const { return getPoint(i) + getNormal() * (penetration_depth / 2); }
+  bool isSame(const ContactPatch& other, FCL_REAL tol = 1e-12) const {  // collision_data.h:660-704
+    auto approx = [tol](const Vec3f& a, const Vec3f& b) { return (a - b).norm() <= tol * std::min(a.norm(), b.norm()); };
+    if (!approx(getNormal(), other.getNormal())) return false;
+    if (std::abs(penetration_depth - other.penetration_depth) > tol || direction != other.direction || size() != other.size()) return false;
+    for (size_t i = 0; i < size(); ++i) {
+      bool found = false;
+      for (size_t j = 0; j < other.size(); ++j) found = found || approx(getPoint(i), other.getPoint(j));
+      if (!found) return false;
+    }
+    return true;
+  }
+};
+
+struct ContactPatchResult {  // collision_data.h:826-981
+  ContactPatchResult() {}
+  explicit ContactPatchResult(const ContactPatchRequest&) {}
+  size_t numContactPatches() const { return patches.size(); }
+  const ContactPatch& getContactPatch(size_t i) const {
+    if (patches.empty()) throw std::invalid_argument("The number of contact patches is zero. No ContactPatch can be returned.");
+    return patches[i < patches.size() ? i : patches.size() - 1];
+  }
+  void clear() { patches.clear(); }
+  void set(const ContactPatchRequest&) { clear(); }
+  std::vector<ContactPatch> patches;
+};
+
+/// hpp::fcl::computeContactPatch (src/contact_patch.cpp:48-97) on the records of the contacts in `collision_result`.
+inline void computeContactPatch(const CollisionGeometry* o1, const Transform3f& tf1, const CollisionGeometry* o2,
+                                const Transform3f& tf2, const CollisionResult& collision_result, const ContactPatchRequest& request,
+                                ContactPatchResult& result) {
+  if (!collision_result.isCollision() || request.max_num_patch == 0) return;
+  result.set(request);
+  if (!hfcl_patch_supported(o1->getNodeType(), o2->getNodeType()))
+    throw std::invalid_argument("Contact patch computation between these node types is not yet supported.");
+  amd::BatchQueries& ctx = amd::default_context();
+  const uint32_t i1 = ctx.add(o1), i2 = ctx.add(o2);
+  hfcl_lib* lib = ctx.library();
+  const size_t n = std::min(request.max_num_patch, collision_result.numContacts());
+  std::vector<uint32_t> s1(n, i1), s2(n, i2);
+  std::vector<Transform3f> t1(n, tf1), t2(n, tf2);
+  std::vector<hfcl_result> rec(n);
+  std::vector<hfcl_guess> guess(n);
+  for (size_t k = 0; k < n; ++k) {
+    const Contact& c = collision_result.getContact(k);
+    hfcl_result& r = rec[k];
+    std::memset(&r, 0, sizeof(r));
+    r.distance = c.penetration_depth;
+    for (int d = 0; d < 3; ++d) {
+      r.normal[d] = c.normal[d];
+      r.p1[d] = c.nearest_points[0][d];
+      r.p2[d] = c.nearest_points[1][d];
+    }
+    r.b1 = c.b1;
+    r.b2 = c.b2;
+    r.num_contacts = 1;
+    std::memset(&guess[k], 0, sizeof(hfcl_guess));
+    guess[k].support_guess[0] = collision_result.cached_support_func_guess[0];
+    guess[k].support_guess[1] = collision_result.cached_support_func_guess[1];
+  }
+  hfcl_patch_request preq;
+  preq.max_num_patch = static_cast<uint32_t>(request.max_num_patch);
+  preq.num_samples_curved_shapes = static_cast<uint32_t>(request.getNumSamplesCurvedShapes());
+  preq.patch_tolerance = request.getPatchTolerance();
+  uint32_t cap = 0;
+  int rc = hfcl_contact_patch_max_points(lib, &preq, &cap);
+  if (rc) amd::throw_for(rc);
+  std::vector<hfcl_contact_patch> out(n);
+  std::vector<double> pts(n * size_t(cap) * 2);
+  rc = hfcl_contact_patch_batch(lib, s1.data(), s2.data(), reinterpret_cast<const double*>(t1.data()),
+                                reinterpret_cast<const double*>(t2.data()), rec.data(), guess.data(), n, &preq, cap, out.data(),
+                                pts.data());
+  if (rc) amd::throw_for(rc);
+  for (size_t k = 0; k < n; ++k) {
+    ContactPatch p;
+    Matrix3f R;
+    for (int i = 0; i < 9; ++i) R.m[i] = out[k].tf[i];
+    p.tf = Transform3f(R, Vec3f(out[k].tf[9], out[k].tf[10], out[k].tf[11]));
+    p.penetration_depth = out[k].penetration_depth;
+    for (uint32_t j = 0; j < out[k].num_points; ++j) p.m_points.push_back({{pts[(k * cap + j) * 2], pts[(k * cap + j) * 2 + 1]}});
+    result.patches.push_back(p);
+  }
+}
+
+/// ComputeContactPatch (include/hpp/fcl/contact_patch.h): the pair is checked once at construction.
+class ComputeContactPatch {
+ public:
+  ComputeContactPatch(const CollisionGeometry* o1, const CollisionGeometry* o2) : o1_(o1), o2_(o2) {
+    if (!hfcl_patch_supported(o1->getNodeType(), o2->getNodeType()))
+      throw std::invalid_argument("Contact patch computation between these node types is not yet supported.");
+  }
+  void operator()(const Transform3f& tf1, const Transform3f& tf2, const CollisionResult& collision_result,
+                  const ContactPatchRequest& request, ContactPatchResult& result) const {
+    computeContactPatch(o1_, tf1, o2_, tf2, collision_result, request, result);
+  }
+
+ private:
+  const CollisionGeometry* o1_;
+  const CollisionGeometry* o2_;
 };
 
 // ---------------------------------------------------------------------------------------------
