@@ -110,6 +110,38 @@ assert PATCH_DTYPE.itemsize == 112
 PATCH_CLASS_NONE, PATCH_CLASS_POINT, PATCH_CLASS_ONESIDED, PATCH_CLASS_CLIPPED = 0, 1, 2, 3
 PATCH_SWAPPED, PATCH_OVERFLOW, PATCH_SKIPPED = 1 << 2, 1 << 3, 1 << 31
 
+# hfcl_scene_summary: the fold of one configuration's records (scene queries)
+SCENE_SUMMARY_DTYPE = np.dtype([("min_distance", "<f8"), ("min_pair", "<u4"), ("first_contact", "<u4"), ("n_contacts", "<u4"),
+                                ("n_skipped", "<u4")])
+assert SCENE_SUMMARY_DTYPE.itemsize == 24
+SCENE_NONE = 0xFFFFFFFF
+
+
+def fold_records(records, n_pairs, security_margin=None):
+    """Host-side restatement of the scene fold: records of n_conf * n_pairs queries -> SCENE_SUMMARY_DTYPE[n_conf].
+    security_margin: the collision request's margin (collide), None for distance records.  fp32 records: the margin is
+    subtracted in float32 and the result widened, as the device does."""
+    n_pairs = int(n_pairs)
+    n_conf = len(records) // n_pairs if n_pairs else 0
+    out = np.zeros(n_conf, dtype=SCENE_SUMMARY_DTYPE)
+    d = records["distance"]
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = d if security_margin is None else d - d.dtype.type(security_margin)
+    v = v.astype(np.float64).reshape(n_conf, n_pairs)
+    st = records["status"].reshape(n_conf, n_pairs)
+    skipped = (st >> 31) & 1 == 1
+    contact = ((st >> 7) & 1 == 1) & ~skipped
+    valid = ~skipped & ~np.isnan(v)
+    w = np.where(valid, v, np.inf)
+    m = w.min(axis=1) if n_pairs else np.full(n_conf, np.inf)
+    hit = valid & (w == m[:, None])
+    out["min_distance"] = m
+    out["min_pair"] = np.where(hit.any(axis=1), hit.argmax(axis=1), SCENE_NONE)
+    out["first_contact"] = np.where(contact.any(axis=1), contact.argmax(axis=1), SCENE_NONE)
+    out["n_contacts"] = contact.sum(axis=1)
+    out["n_skipped"] = skipped.sum(axis=1)
+    return out
+
 
 def compact_records(records):
     """Host-side image of hfcl_compact_results_device: the fields a compact record keeps (bit copies)."""

@@ -674,6 +674,72 @@ def collide_pairs(pairs, request):
     return out
 
 
+def _scene_run(kind, objects, pair_indices, request, transforms):
+    """The pair list `pair_indices` ((n_pairs, 2) indices into `objects`) for every configuration: ONE scene call."""
+    ctx = _context()
+    geoms = [o.collisionGeometry() for o in objects]
+    ids = np.array([ctx.add(g) for g in geoms], dtype=np.uint32)
+    pr = np.ascontiguousarray(pair_indices, dtype=np.uint32).reshape(-1, 2)
+    if len(pr) and int(pr.max()) >= len(objects):
+        raise ValueError("pair index outside the objects")
+    types = np.array([g.getNodeType() for g in geoms], dtype=np.int64)
+    for t1, t2 in (np.unique(types[pr], axis=0) if len(pr) else ()):  # (the distinct kind pairs: a few, whatever the list's length)
+        if not engine.dll().hfcl_pair_supported(int(t1), int(t2), int(kind == "distance")):
+            raise ValueError("%s function between node type %d and node type %d is not yet supported." %
+                             ("Distance" if kind == "distance" else "Collision", t1, t2))
+    if transforms is None:
+        table = np.concatenate([o.getTransform()._abi().reshape(1, 12) for o in objects]).reshape(1, len(objects), 12)
+    elif isinstance(transforms, np.ndarray):
+        table = np.ascontiguousarray(transforms, dtype=np.float64).reshape(-1, len(objects), 12)
+    else:
+        table = np.stack([np.concatenate([t._abi().reshape(1, 12) for t in conf]) for conf in transforms])
+    lib = ctx.library()
+    sc = lib.scene(ids, pr)
+    try:
+        fn = sc.distance if kind == "distance" else sc.collide
+        rec, summ, g = fn(table, request._abi(), records=True, summary=True, want_guess=True)
+    except engine.EngineError as e:
+        if e.code in (abi.ERR_INVALID_ARGUMENT, abi.ERR_UNSUPPORTED_PAIR):
+            raise ValueError(str(e))  # std::invalid_argument in the reference
+        raise
+    finally:
+        sc.close()
+    return geoms, pr, len(table), rec, summ, g
+
+
+def collide_scene(objects, pair_indices, request, transforms=None):
+    """collide() on the listed pairs of `objects` (CollisionObjects) through a scene: each object's pose goes to the device
+    once per configuration, not once per pair.  transforms: None -- one configuration, the objects' own transforms --, an
+    array (n_conf, n_objects, 12) of Transform3f images, or n_conf lists of Transform3f.  Returns (results, summaries):
+    results[c][p] is the CollisionResult collide_pairs gives for pair p under configuration c (a flat list of n_pairs when
+    transforms is None), summaries the abi.SCENE_SUMMARY_DTYPE record of every configuration (n_contacts > 0: what
+    CollisionCallBackDefault's result.isCollision() says after manager.collide).  The results are Python objects, filled one by
+    one: for lists of 10^5 pairs and more that loop costs far more than the device call -- take the summaries, or the records of
+    engine.Scene.collide, there."""
+    if request.num_max_contacts == 0:
+        raise ValueError("Invalid number of max contacts (current value is 0).")
+    if request.num_max_contacts > 1 and any(isinstance(o.collisionGeometry(), BVHModelOBBRSS) for o in objects):
+        raise ValueError("collide_scene: contact lists of mesh pairs (num_max_contacts > 1) go through collide_pairs")
+    geoms, pr, n_conf, rec, summ, g = _scene_run("collide", objects, pair_indices, request, transforms)
+    out = []
+    for c in range(n_conf):
+        row = []
+        for p, (i, j) in enumerate(pr):
+            r = CollisionResult()
+            q = c * len(pr) + p
+            _fill_collision(r, geoms[i], geoms[j], request, rec[q], g[q], None, p)
+            row.append(r)
+        out.append(row)
+    return (out[0] if transforms is None and out else out), summ
+
+
+def distance_scene(objects, pair_indices, request, transforms=None):
+    """distance() on the listed pairs of `objects`: (min_distance array (n_conf, n_pairs), records, summaries); the
+    summaries' min_distance is DistanceCallBackDefault's answer per configuration."""
+    geoms, pr, n_conf, rec, summ, g = _scene_run("distance", objects, pair_indices, request, transforms)
+    return rec["distance"].reshape(n_conf, len(pr)), rec, summ
+
+
 class DynamicAABBTreeCollisionManager:  # broadphase_dynamic_AABB_tree.h (candidate set = all AABB-overlapping pairs)
     def __init__(self):
         self._objs, self._aabbs = [], None

@@ -43,6 +43,7 @@
 #include "hfcl_dev.hpp"
 #include "hfcl_launch.hpp"
 #include "hfcl_patch.hpp"
+#include "hfcl_scene.hpp"
 
 // =======================================================================================
 // Host side: library object + C ABI
@@ -224,6 +225,35 @@ struct hfcl_lib {
   size_t patch_list_cap = 0;
   uint32_t* d_patch_counts = nullptr;
   hipStream_t patch_st = nullptr;
+  // scene queries (hfcl_scene_*): the workspace of a chunk of queries -- expanded ids and poses, two record / guess buffers (summary-only
+  // calls and the host form), the fold's partials --, the host form's object table and summaries, its two streams and per-chunk counters
+  struct SceneWs {
+    uint32_t *d_s1 = nullptr, *d_s2 = nullptr;
+    void *d_tf1 = nullptr, *d_tf2 = nullptr;
+    size_t cap = 0;                 // queries the four arrays above hold
+    void* d_rec[2] = {nullptr, nullptr};
+    size_t rec_cap[2] = {0, 0};     // records (of 96 B) each holds
+    hfcl_guess *d_gin = nullptr, *d_gout[2] = {nullptr, nullptr};
+    size_t gin_cap = 0, gout_cap[2] = {0, 0};
+    hfcl_scene_summary* d_partials = nullptr;
+    size_t partials_cap = 0;
+    void* d_table = nullptr;        // host form: the object pose table
+    size_t table_bytes = 0;
+    hfcl_scene_summary* d_summary = nullptr;
+    size_t summary_cap = 0;
+    hipStream_t s_cmp = nullptr, s_copy = nullptr;
+    hipEvent_t ev_done[2] = {nullptr, nullptr}, ev_copied[2] = {nullptr, nullptr};
+    static constexpr int COUNT_SLOTS = 8;
+    uint32_t* h_counts = nullptr;   // pinned: COUNT_SLOTS x 2 * N_COUNTERS words of the host form (a chunk, its second half when it ran split);
+                                    // chunk k uses slot k % COUNT_SLOTS once chunk k - COUNT_SLOTS has been added up (ev_counts: its kernels are done)
+    hipEvent_t ev_counts[COUNT_SLOTS] = {};
+  } scene;
+  // Queries per chunk of a scene call (option scene_chunk; 0: automatic -- at most 2^21 queries, the call cut into equal chunks).  The chunks of a
+  // call run one after the other, and the solvers' kernels are chains of dependent steps that fill the chip only with a large batch: cfg5's
+  // 1.07 M queries in chunks of 262144 (the host pipeline's steady chunk) took 5.9 ms against 2.4 ms for the per-pair call on resident arrays,
+  // 9.0 ms of kernel time against 5.5 (profiles/r08_a_scene.md).  2^21 queries are 0.8 GB of workspace, allocated only by calls that large.
+  size_t scene_chunk = 0;
+  uint64_t shapes_epoch = 0;        // hfcl_lib_set_shapes counts: a scene made before the last one is stale
   uint32_t possible_buckets = ~0u;   // bit b: some pair of this library's shape kinds classifies into bucket b
   bool has_flats = true;             // some shape is a Plane / Halfspace: their "very rough" volumes are no lower bounds, so what a mesh walk
                                      // against them reports depends on the ORDER of its visits -- the ordered continuation, not the pool
@@ -529,7 +559,7 @@ static const char* const* option_keys() {
       "bvh_walk_rounds", "bvh_walk_order", "mesh_beside", "mesh_prio", "shape_walk", "shape_walk_sort", "shape_walk_budget", "shape_walk_min", "gjk_beside_max", "epa_direct_max", "bvh_walk_k", "bvh_walk_budget", "shape_dist_leaf_min", "shape_dist_starve", "bvhd_leaf_min", "bvhd_starve",
       "bvhd_part_min", "shape_dist_budget", "bvh_budget0_coop", "shape_budget0", "shape_budget", "shape_leaf_cost", "shape_levels",
       "climb_min", "bvh_budget", "bvh_budget0", "bvh_levels", "cvx_w", "epa_resume_slots", "bvh_task_slots", "bvh_force_wide",
-      "pipe_trace", nullptr};
+      "pipe_trace", "scene_chunk", nullptr};
   return keys;
 }
 // "4,16,16": up to `cap` comma-separated unsigned values into out[first...]; returns how many were read
@@ -610,6 +640,10 @@ static int apply_option(hfcl_lib* lib, const std::string& key, const char* v) {
   else if (key == "bvh_task_slots") lib->bvh_task_slots = size_t(std::max(0ll, i));
   else if (key == "bvh_force_wide") lib->bvh_force_wide = on;
   else if (key == "pipe_trace") lib->pipe_trace = on;
+  else if (key == "scene_chunk") {
+    if (i < 0 || i > 0xFFFFFFF0ll) return HFCL_ERR_INVALID_ARGUMENT;
+    lib->scene_chunk = size_t(i);
+  }
   else return HFCL_ERR_INVALID_ARGUMENT;
   return HFCL_OK;
 }
@@ -674,6 +708,21 @@ void hfcl_lib_destroy(hfcl_lib* lib) {
   hipFree(lib->d_patch_lists);
   hipFree(lib->d_patch_counts);
   if (lib->patch_st) hipStreamDestroy(lib->patch_st);
+  {
+    hfcl_lib::SceneWs& w = lib->scene;
+    hipFree(w.d_s1); hipFree(w.d_s2); hipFree(w.d_tf1); hipFree(w.d_tf2); hipFree(w.d_gin); hipFree(w.d_partials); hipFree(w.d_table); hipFree(w.d_summary);
+    for (int k = 0; k < 2; ++k) {
+      hipFree(w.d_rec[k]);
+      hipFree(w.d_gout[k]);
+      if (w.ev_done[k]) hipEventDestroy(w.ev_done[k]);
+      if (w.ev_copied[k]) hipEventDestroy(w.ev_copied[k]);
+    }
+    if (w.s_cmp) hipStreamDestroy(w.s_cmp);
+    if (w.s_copy) hipStreamDestroy(w.s_copy);
+    if (w.h_counts) hipHostFree(w.h_counts);
+    for (hipEvent_t e : w.ev_counts)
+      if (e) hipEventDestroy(e);
+  }
   hipFree(lib->d_lists);
   hipFree(lib->d_epa_queue);
   hipFree(lib->d_epa_queue2);
@@ -774,6 +823,7 @@ int hfcl_lib_set_shapes(hfcl_lib* lib, const hfcl_shape* shapes, size_t n_shapes
     return HFCL_ERR_HIP;
   }
   if (lib->helper) share_tables(lib->helper, lib);  // the second half of split batches reads the same tables
+  ++lib->shapes_epoch;  // (the scenes of this library hold shape ids of the old table)
   return HFCL_OK;
 }
 
@@ -3179,6 +3229,471 @@ int hfcl_contact_patch_batch(hfcl_lib* lib, const uint32_t* shape1, const uint32
   hipStreamSynchronize(st);
   hipFree(d);
   return rc;
+}
+
+}  // extern "C"
+
+// =======================================================================================
+// Scene queries (include/hppfcl_amd.h: hfcl_scene_*): an object -> shape table and a pair list resident on the library's device; a call
+// evaluates the pair list for n_conf pose tables.  The flat query range q = c * n_pairs + p is cut into chunks; a chunk is expanded into the
+// per-pair arrays of the batch entry points (k_scene_expand*), goes through hfcl_*_batch_device* exactly as a caller's batch of that size
+// would, and its records are folded into the summaries of the configurations it touches (k_scene_fold).  No record changes on the way.
+// =======================================================================================
+struct hfcl_scene {
+  hfcl_lib* lib = nullptr;
+  size_t n_objects = 0, n_pairs = 0;
+  uint32_t* d_object_shape = nullptr;
+  uint32_t* d_pairs = nullptr;
+  uint64_t epoch = 0;  // hfcl_lib::shapes_epoch when the scene was made
+};
+
+static int scene_check_pairs(const char* who, const uint32_t* pairs, size_t n_pairs, size_t n_objects) {
+  if (n_pairs > 0xFFFFFFF0ull) {
+    set_error(std::string(who) + ": pair list too long (max 2^32-16 pairs)");
+    return HFCL_ERR_LIMIT;
+  }
+  if (n_pairs && !pairs) {
+    set_error(std::string(who) + ": null pair list");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  for (size_t k = 0; k < 2 * n_pairs; ++k)
+    if (pairs[k] >= n_objects) {
+      set_error(std::string(who) + ": object index " + std::to_string(pairs[k]) + " of pair " + std::to_string(k / 2) + " is outside the " +
+                std::to_string(n_objects) + " objects");
+      return HFCL_ERR_INVALID_ARGUMENT;
+    }
+  return HFCL_OK;
+}
+static int scene_upload(uint32_t** dst, const uint32_t* src, size_t words) {
+  *dst = nullptr;
+  if (!words) return HFCL_OK;
+  HIP_TRY(hipMalloc(dst, words * sizeof(uint32_t)));
+  if (hipMemcpy(*dst, src, words * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+    hipFree(*dst);
+    *dst = nullptr;
+    set_error("scene: copy to the device failed");
+    return HFCL_ERR_HIP;
+  }
+  return HFCL_OK;
+}
+
+template <typename T> struct SceneTypes;
+template <> struct SceneTypes<double> {
+  using R = hfcl_result;
+  static constexpr size_t WIDTH = 12;
+};
+template <> struct SceneTypes<float> {
+  using R = hfcl_result_f32;
+  static constexpr size_t WIDTH = 7;
+};
+
+// a chunk through the batch entry point of its precision
+static int scene_batch(hfcl_lib* lib, const uint32_t* s1, const uint32_t* s2, const void* tf1, const void* tf2, size_t m,
+                       const hfcl_collision_request* creq, const hfcl_distance_request* dreq, hfcl_result* rec, const hfcl_guess* gin,
+                       hfcl_guess* gout, hipStream_t st) {
+  return creq ? hfcl_collide_batch_device(lib, s1, s2, static_cast<const double*>(tf1), static_cast<const double*>(tf2), m, creq, rec, gin, gout, st)
+              : hfcl_distance_batch_device(lib, s1, s2, static_cast<const double*>(tf1), static_cast<const double*>(tf2), m, dreq, rec, gin, gout, st);
+}
+static int scene_batch(hfcl_lib* lib, const uint32_t* s1, const uint32_t* s2, const void* tf1, const void* tf2, size_t m,
+                       const hfcl_collision_request* creq, const hfcl_distance_request* dreq, hfcl_result_f32* rec, const hfcl_guess*, hfcl_guess*,
+                       hipStream_t st) {
+  return creq ? hfcl_collide_batch_device_f32(lib, s1, s2, static_cast<const float*>(tf1), static_cast<const float*>(tf2), m, creq, rec, st)
+              : hfcl_distance_batch_device_f32(lib, s1, s2, static_cast<const float*>(tf1), static_cast<const float*>(tf2), m, dreq, rec, st);
+}
+
+// everything a scene call refuses before any work; total: n_conf * n_pairs (0: nothing to do)
+template <typename T>
+static int scene_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, const hfcl_collision_request* creq,
+                          const hfcl_distance_request* dreq, const void* out, const void* summary, size_t& total) {
+  total = 0;
+  if (!s) {
+    set_error(std::string(who) + ": null scene");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  QParams<T> q;
+  bool skip;
+  const int rc = creq ? setup_collide<T>(creq, q, skip) : setup_distance<T>(dreq, q);
+  if (rc) return rc;
+  if (!out && !summary) {
+    set_error(std::string(who) + ": records and summaries both NULL");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (s->epoch != s->lib->shapes_epoch) {
+    set_error(std::string(who) + ": the library's shapes were replaced (hfcl_lib_set_shapes) after this scene was created; create a new scene");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (n_conf == 0 || s->n_pairs == 0) return HFCL_OK;
+  if (!table) {
+    set_error(std::string(who) + ": null pose table");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (n_conf > ~size_t(0) / s->n_pairs || n_conf > ~size_t(0) / (s->n_objects * SceneTypes<T>::WIDTH * sizeof(T))) {
+    set_error(std::string(who) + ": n_conf * n_pairs overflows");
+    return HFCL_ERR_LIMIT;
+  }
+  total = n_conf * s->n_pairs;
+  return HFCL_OK;
+}
+// queries per chunk of a call of `total` queries: the option as given, or equal chunks of at most 2^21
+static size_t scene_chunk_size(const hfcl_lib* lib, size_t total) {
+  if (lib->scene_chunk) return std::min<size_t>(std::min<size_t>(lib->scene_chunk, total), 0xFFFFFFF0ull);
+  constexpr size_t AUTO = size_t(1) << 21;
+  const size_t n_chunks = (total + AUTO - 1) / AUTO;
+  return (total + n_chunks - 1) / n_chunks;
+}
+
+template <typename P>
+static int scene_grow(P** p, size_t& cap, size_t need, size_t elem) {
+  if (need <= cap) return HFCL_OK;
+  hipFree(*p);  // (waits for the device: nothing in flight reads the old buffer)
+  *p = nullptr;
+  cap = 0;
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), need * elem));
+  cap = need;
+  return HFCL_OK;
+}
+// workspace of chunks of up to m queries; recs: how many of the two record buffers; pieces: fold partials (0: none)
+static int scene_workspace(hfcl_lib* lib, size_t m, int recs, bool gin, int gouts, size_t pieces) {
+  hfcl_lib::SceneWs& w = lib->scene;
+  if (m > w.cap) {
+    hipFree(w.d_s1); hipFree(w.d_s2); hipFree(w.d_tf1); hipFree(w.d_tf2);
+    w.d_s1 = w.d_s2 = nullptr;
+    w.d_tf1 = w.d_tf2 = nullptr;
+    w.cap = 0;
+    HIP_TRY(hipMalloc(&w.d_s1, m * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(&w.d_s2, m * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(&w.d_tf1, m * 12 * sizeof(double)));  // (rows of either precision)
+    HIP_TRY(hipMalloc(&w.d_tf2, m * 12 * sizeof(double)));
+    w.cap = m;
+  }
+  for (int k = 0; k < recs; ++k) {
+    const int rc = scene_grow(&w.d_rec[k], w.rec_cap[k], m, sizeof(hfcl_result));
+    if (rc) return rc;
+  }
+  if (gin) {
+    const int rc = scene_grow(&w.d_gin, w.gin_cap, m, sizeof(hfcl_guess));
+    if (rc) return rc;
+  }
+  for (int k = 0; k < gouts; ++k) {
+    const int rc = scene_grow(&w.d_gout[k], w.gout_cap[k], m, sizeof(hfcl_guess));
+    if (rc) return rc;
+  }
+  return scene_grow(&w.d_partials, w.partials_cap, pieces, sizeof(hfcl_scene_summary));
+}
+// fold partials a chunk of m queries can need: none when a pair list is one piece
+static size_t scene_pieces_bound(size_t n_pairs, size_t m) {
+  if (scene_shares(uint32_t(n_pairs)) <= 1u) return 0;
+  // whole pieces inside the chunk, a cut one at either end, and one more cut per configuration boundary inside it
+  return m / SCENE_FOLD_SHARE + 2 + 2 * (m / n_pairs + 2);
+}
+
+// expansion of chunk [q0, q0 + m), the batch, the fold: all on st
+template <typename T>
+static int scene_chunk_run(hfcl_scene* s, const void* d_table, size_t q0, size_t m, const hfcl_collision_request* creq,
+                           const hfcl_distance_request* dreq, typename SceneTypes<T>::R* d_rec, hfcl_scene_summary* d_summary,
+                           const hfcl_guess* d_gin, hfcl_guess* d_gout, hipStream_t st) {
+  hfcl_lib* lib = s->lib;
+  hfcl_lib::SceneWs& w = lib->scene;
+  constexpr bool f32 = std::is_same<T, float>::value;
+  const int max_blocks = lib->n_cus * 16;
+  SceneExpandArgs ea;
+  ea.pairs = s->d_pairs;
+  ea.object_shape = s->d_object_shape;
+  ea.object_tf = d_table;
+  ea.n_objects = s->n_objects;
+  ea.n_pairs = uint32_t(s->n_pairs);
+  ea.q0 = q0;
+  scene_query(q0, ea.n_pairs, ea.c0, ea.p0);
+  ea.m = uint32_t(m);
+  ea.s1 = w.d_s1;
+  ea.s2 = w.d_s2;
+  ea.tf1 = w.d_tf1;
+  ea.tf2 = w.d_tf2;
+  launch_scene_expand(st, ea, f32, max_blocks);
+  const int rc = scene_batch(lib, w.d_s1, w.d_s2, w.d_tf1, w.d_tf2, m, creq, dreq, d_rec, d_gin, d_gout, st);
+  if (rc) return rc;
+  if (d_summary) {
+    SceneFoldArgs fa;
+    fa.rec = d_rec;
+    fa.q0 = q0;
+    fa.q1 = q0 + m;
+    fa.n_pairs = uint32_t(s->n_pairs);
+    fa.g0 = scene_piece_of(q0, fa.n_pairs);
+    fa.n_pieces = scene_piece_of(q0 + m - 1, fa.n_pairs) - fa.g0 + 1;
+    fa.margin = creq ? creq->security_margin : 0.0;
+    fa.collide = creq ? 1 : 0;
+    fa.summary = d_summary;
+    fa.partials = scene_shares(fa.n_pairs) > 1u ? w.d_partials : nullptr;
+    launch_scene_fold(st, fa, f32, max_blocks);
+  }
+  return HFCL_OK;
+}
+// An error after work was enqueued: the second half of a split batch may be running on the library's side stream -- the caller's stream
+// waits for it, so that "everything this call started is ordered before what the caller enqueues next" holds on the error path too
+static void scene_join_side(hfcl_lib* lib, hipStream_t st) {
+  if (lib->side && lib->ev_join && hipEventRecord(lib->ev_join, lib->side) == hipSuccess) (void)hipStreamWaitEvent(st, lib->ev_join, 0);
+}
+
+template <typename T>
+static int scene_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const hfcl_collision_request* creq,
+                        const hfcl_distance_request* dreq, typename SceneTypes<T>::R* d_out, hfcl_scene_summary* d_summary,
+                        const hfcl_guess* d_gin, hfcl_guess* d_gout, hipStream_t st) {
+  size_t total;
+  int rc = scene_validate<T>(who, s, d_table, n_conf, creq, dreq, d_out, d_summary, total);
+  if (rc || !total) return rc;
+  hfcl_lib* lib = s->lib;
+  HIP_TRY(hipSetDevice(lib->device));
+  const size_t chunk = scene_chunk_size(lib, total);
+  rc = scene_workspace(lib, chunk, d_out ? 0 : 1, false, 0, d_summary ? scene_pieces_bound(s->n_pairs, chunk) : 0);
+  if (rc) return rc;
+  for (size_t q0 = 0; q0 < total; q0 += chunk) {
+    const size_t m = std::min(chunk, total - q0);
+    auto* rec = d_out ? d_out + q0 : static_cast<typename SceneTypes<T>::R*>(lib->scene.d_rec[0]);
+    rc = scene_chunk_run<T>(s, d_table, q0, m, creq, dreq, rec, d_summary, d_gin ? d_gin + q0 : nullptr, d_gout ? d_gout + q0 : nullptr, st);
+    if (rc) {
+      scene_join_side(lib, st);
+      return rc;
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  return HFCL_OK;
+}
+
+// Host form.  The object table goes in once; chunk k computes on one stream while chunk k - 1's records leave on another from the other of
+// two record buffers (the copy is issued AFTER chunk k's launches: a copy into pageable memory holds its caller until the data has moved);
+// the summaries come back once at the end.  No feeder threads: nothing per pair goes in.
+template <typename T>
+static int scene_host(const char* who, hfcl_scene* s, const void* table, size_t n_conf, const hfcl_collision_request* creq,
+                      const hfcl_distance_request* dreq, typename SceneTypes<T>::R* out, hfcl_scene_summary* summary, const hfcl_guess* gin,
+                      hfcl_guess* gout) {
+  using R = typename SceneTypes<T>::R;
+  size_t total;
+  int rc = scene_validate<T>(who, s, table, n_conf, creq, dreq, out, summary, total);
+  if (rc || !total) return rc;
+  hfcl_lib* lib = s->lib;
+  hfcl_lib::SceneWs& w = lib->scene;
+  HIP_TRY(hipSetDevice(lib->device));
+  if (!w.s_cmp) HIP_TRY(hipStreamCreateWithFlags(&w.s_cmp, hipStreamNonBlocking));
+  if (!w.s_copy) HIP_TRY(hipStreamCreateWithFlags(&w.s_copy, hipStreamNonBlocking));
+  for (int k = 0; k < 2; ++k) {
+    if (!w.ev_done[k]) HIP_TRY(hipEventCreateWithFlags(&w.ev_done[k], hipEventDisableTiming));
+    if (!w.ev_copied[k]) HIP_TRY(hipEventCreateWithFlags(&w.ev_copied[k], hipEventDisableTiming));
+  }
+  const size_t chunk = scene_chunk_size(lib, total);
+  const size_t n_chunks = (total + chunk - 1) / chunk;
+  const bool back = out != nullptr || gout != nullptr;  // something per pair goes back: two buffers, the copy stream
+  rc = scene_workspace(lib, chunk, out ? 2 : 1, gin != nullptr, gout ? 2 : 0, summary ? scene_pieces_bound(s->n_pairs, chunk) : 0);
+  if (rc) return rc;
+  const size_t table_bytes = n_conf * s->n_objects * SceneTypes<T>::WIDTH * sizeof(T);
+  {
+    char* t = static_cast<char*>(w.d_table);
+    rc = scene_grow(&t, w.table_bytes, table_bytes, 1);
+    w.d_table = t;
+    if (rc) return rc;
+  }
+  if (summary) {
+    rc = scene_grow(&w.d_summary, w.summary_cap, n_conf, sizeof(hfcl_scene_summary));
+    if (rc) return rc;
+  }
+  constexpr int CS = hfcl_lib::SceneWs::COUNT_SLOTS;
+  constexpr size_t SLOT_WORDS = 2 * size_t(N_COUNTERS);
+  if (!w.h_counts) HIP_TRY(hipHostMalloc((void**)&w.h_counts, CS * SLOT_WORDS * sizeof(uint32_t), hipHostMallocDefault));
+  for (hipEvent_t& e : w.ev_counts)
+    if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  memset(w.h_counts, 0, CS * SLOT_WORDS * sizeof(uint32_t));  // (a skipped batch -- -inf margin -- copies no counters)
+  bool slot_split[CS] = {};
+  memset(lib->acc_counts, 0, sizeof(lib->acc_counts));
+  auto harvest = [&](int slot) {  // a finished chunk's bucket populations into the call's sums; the slot is free again
+    uint32_t* c = w.h_counts + size_t(slot) * SLOT_WORDS;
+    for (int i = 0; i < N_COUNTERS; ++i) lib->acc_counts[i] += c[i] + (slot_split[slot] ? c[N_COUNTERS + i] : 0u);
+    memset(c, 0, SLOT_WORDS * sizeof(uint32_t));
+  };
+  lib->in_host_batch = true;
+
+  auto finish = [&](int code) {  // nothing of this call stays in flight, whatever happened
+    hipStreamSynchronize(w.s_cmp);
+    hipStreamSynchronize(w.s_copy);
+    if (lib->side) hipStreamSynchronize(lib->side);
+    lib->in_host_batch = false;
+    lib->counts_dst = nullptr;
+    if (lib->helper) lib->helper->counts_dst = nullptr;
+    return code;
+  };
+#define SCENE_TRY(expr)                                                      \
+  do {                                                                       \
+    hipError_t _e = (expr);                                                  \
+    if (_e != hipSuccess) {                                                  \
+      set_error(std::string(#expr) + ": " + hipGetErrorString(_e));          \
+      return finish(HFCL_ERR_HIP);                                           \
+    }                                                                        \
+  } while (0)
+  auto copy_back = [&](size_t k) -> hipError_t {  // chunk k's records (and guesses) to the caller's arrays, behind its kernels
+    const int b = int(k & 1);
+    const size_t q0 = k * chunk, m = std::min(chunk, total - q0);
+    hipError_t e = hipStreamWaitEvent(w.s_copy, w.ev_done[b], 0);
+    if (e == hipSuccess && out) e = hipMemcpyAsync(out + q0, w.d_rec[b], m * sizeof(R), hipMemcpyDeviceToHost, w.s_copy);
+    if (e == hipSuccess && gout) e = hipMemcpyAsync(gout + q0, w.d_gout[b], m * sizeof(hfcl_guess), hipMemcpyDeviceToHost, w.s_copy);
+    if (e == hipSuccess) e = hipEventRecord(w.ev_copied[b], w.s_copy);
+    return e;
+  };
+
+  SCENE_TRY(hipMemcpyAsync(w.d_table, table, table_bytes, hipMemcpyHostToDevice, w.s_cmp));
+  for (size_t k = 0; k < n_chunks; ++k) {
+    const int b = back ? int(k & 1) : 0;
+    const size_t q0 = k * chunk, m = std::min(chunk, total - q0);
+    if (back && k >= 2) SCENE_TRY(hipStreamWaitEvent(w.s_cmp, w.ev_copied[b], 0));  // chunk k - 2 has left the buffers
+    if (gin) SCENE_TRY(hipMemcpyAsync(w.d_gin, gin + q0, m * sizeof(hfcl_guess), hipMemcpyHostToDevice, w.s_cmp));
+    const int slot = int(k % CS);
+    if (k >= size_t(CS)) {  // the chunk that used this slot has run: its counters are on the host
+      SCENE_TRY(hipEventSynchronize(w.ev_counts[slot]));
+      harvest(slot);
+    }
+    lib->counts_dst = w.h_counts + size_t(slot) * SLOT_WORDS;
+    if (batch_splits(lib, m)) {
+      rc = ensure_helper(lib);
+      if (rc) return finish(rc);
+      lib->helper->counts_dst = lib->counts_dst + N_COUNTERS;
+    }
+    rc = scene_chunk_run<T>(s, w.d_table, q0, m, creq, dreq, static_cast<R*>(w.d_rec[out ? b : 0]), summary ? w.d_summary : nullptr,
+                            gin ? w.d_gin : nullptr, gout ? w.d_gout[b] : nullptr, w.s_cmp);
+    if (rc) return finish(rc);
+    slot_split[slot] = lib->last_split;
+    SCENE_TRY(hipEventRecord(w.ev_counts[slot], w.s_cmp));
+    if (back) {
+      SCENE_TRY(hipEventRecord(w.ev_done[b], w.s_cmp));
+      if (k >= 1) SCENE_TRY(copy_back(k - 1));
+    }
+  }
+  if (back) SCENE_TRY(copy_back(n_chunks - 1));
+  if (summary) SCENE_TRY(hipMemcpyAsync(summary, w.d_summary, n_conf * sizeof(hfcl_scene_summary), hipMemcpyDeviceToHost, w.s_cmp));
+  SCENE_TRY(hipStreamSynchronize(w.s_cmp));
+  SCENE_TRY(hipStreamSynchronize(w.s_copy));
+  SCENE_TRY(hipGetLastError());
+#undef SCENE_TRY
+  for (int slot = 0; slot < CS && size_t(slot) < n_chunks; ++slot) harvest(slot);
+  lib->in_host_batch = false;
+  lib->counts_dst = nullptr;
+  if (lib->helper) lib->helper->counts_dst = nullptr;
+  lib->last_host = true;
+  return host_batch_checks(lib, creq, dreq);
+}
+
+extern "C" {
+
+hfcl_scene* hfcl_scene_create(hfcl_lib* lib, const uint32_t* object_shape, size_t n_objects, const uint32_t* pairs, size_t n_pairs) {
+  if (!lib) {
+    set_error("hfcl_scene_create: null library");
+    return nullptr;
+  }
+  if (n_objects && !object_shape) {
+    set_error("hfcl_scene_create: null object table");
+    return nullptr;
+  }
+  for (size_t o = 0; o < n_objects; ++o)
+    if (object_shape[o] >= lib->n_shapes) {
+      set_error("hfcl_scene_create: shape id " + std::to_string(object_shape[o]) + " of object " + std::to_string(o) + " is outside the library");
+      return nullptr;
+    }
+  // (no return code here: the two causes that are not HFCL_ERR_INVALID_ARGUMENT name theirs at the head of the message)
+  if (const int rc = scene_check_pairs("hfcl_scene_create", pairs, n_pairs, n_objects)) {
+    if (rc == HFCL_ERR_LIMIT) set_error("HFCL_ERR_LIMIT: " + g_last_error);
+    return nullptr;
+  }
+  if (hipSetDevice(lib->device) != hipSuccess) {
+    set_error("HFCL_ERR_HIP: hfcl_scene_create: hipSetDevice failed");
+    return nullptr;
+  }
+  hfcl_scene* s = new hfcl_scene();
+  s->lib = lib;
+  s->n_objects = n_objects;
+  s->n_pairs = n_pairs;
+  s->epoch = lib->shapes_epoch;
+  if (scene_upload(&s->d_object_shape, object_shape, n_objects) != HFCL_OK || scene_upload(&s->d_pairs, pairs, 2 * n_pairs) != HFCL_OK) {
+    set_error("HFCL_ERR_HIP: hfcl_scene_create: " + g_last_error);
+    hfcl_scene_destroy(s);
+    return nullptr;
+  }
+  return s;
+}
+
+int hfcl_scene_set_pairs(hfcl_scene* s, const uint32_t* pairs, size_t n_pairs) {
+  if (!s) {
+    set_error("hfcl_scene_set_pairs: null scene");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  int rc = scene_check_pairs("hfcl_scene_set_pairs", pairs, n_pairs, s->n_objects);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(s->lib->device));
+  uint32_t* d = nullptr;
+  rc = scene_upload(&d, pairs, 2 * n_pairs);
+  if (rc) return rc;
+  hipFree(s->d_pairs);  // (waits for the device: a query in flight on some stream may still be reading the old list)
+  s->d_pairs = d;
+  s->n_pairs = n_pairs;
+  return HFCL_OK;
+}
+
+void hfcl_scene_destroy(hfcl_scene* s) {
+  if (!s) return;
+  hipSetDevice(s->lib->device);
+  hipFree(s->d_object_shape);
+  hipFree(s->d_pairs);
+  delete s;
+}
+size_t hfcl_scene_num_objects(const hfcl_scene* s) { return s ? s->n_objects : 0; }
+size_t hfcl_scene_num_pairs(const hfcl_scene* s) { return s ? s->n_pairs : 0; }
+
+int hfcl_scene_collide(hfcl_scene* s, const double* object_tf, size_t n_conf, const hfcl_collision_request* req, hfcl_result* out,
+                       hfcl_scene_summary* summary, const hfcl_guess* guess_in, hfcl_guess* guess_out) {
+  return scene_host<double>("hfcl_scene_collide", s, object_tf, n_conf, req, nullptr, out, summary, guess_in, guess_out);
+}
+int hfcl_scene_distance(hfcl_scene* s, const double* object_tf, size_t n_conf, const hfcl_distance_request* req, hfcl_result* out,
+                        hfcl_scene_summary* summary, const hfcl_guess* guess_in, hfcl_guess* guess_out) {
+  if (s && !req) {
+    set_error("null request");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  return scene_host<double>("hfcl_scene_distance", s, object_tf, n_conf, nullptr, req, out, summary, guess_in, guess_out);
+}
+int hfcl_scene_collide_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const hfcl_collision_request* req, hfcl_result* d_out,
+                              hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in, hfcl_guess* d_guess_out, void* stream) {
+  return scene_device<double>("hfcl_scene_collide_device", s, d_object_tf, n_conf, req, nullptr, d_out, d_summary, d_guess_in, d_guess_out,
+                              (hipStream_t)stream);
+}
+int hfcl_scene_distance_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const hfcl_distance_request* req, hfcl_result* d_out,
+                               hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in, hfcl_guess* d_guess_out, void* stream) {
+  if (s && !req) {
+    set_error("null request");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  return scene_device<double>("hfcl_scene_distance_device", s, d_object_tf, n_conf, nullptr, req, d_out, d_summary, d_guess_in, d_guess_out,
+                              (hipStream_t)stream);
+}
+int hfcl_scene_collide_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, const hfcl_collision_request* req, hfcl_result_f32* out,
+                           hfcl_scene_summary* summary) {
+  return scene_host<float>("hfcl_scene_collide_f32", s, object_pose, n_conf, req, nullptr, out, summary, nullptr, nullptr);
+}
+int hfcl_scene_distance_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, const hfcl_distance_request* req, hfcl_result_f32* out,
+                            hfcl_scene_summary* summary) {
+  if (s && !req) {
+    set_error("null request");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  return scene_host<float>("hfcl_scene_distance_f32", s, object_pose, n_conf, nullptr, req, out, summary, nullptr, nullptr);
+}
+int hfcl_scene_collide_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, const hfcl_collision_request* req,
+                                  hfcl_result_f32* d_out, hfcl_scene_summary* d_summary, void* stream) {
+  return scene_device<float>("hfcl_scene_collide_device_f32", s, d_object_pose, n_conf, req, nullptr, d_out, d_summary, nullptr, nullptr,
+                             (hipStream_t)stream);
+}
+int hfcl_scene_distance_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, const hfcl_distance_request* req,
+                                   hfcl_result_f32* d_out, hfcl_scene_summary* d_summary, void* stream) {
+  if (s && !req) {
+    set_error("null request");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  return scene_device<float>("hfcl_scene_distance_device_f32", s, d_object_pose, n_conf, nullptr, req, d_out, d_summary, nullptr, nullptr,
+                             (hipStream_t)stream);
 }
 
 }  // extern "C"

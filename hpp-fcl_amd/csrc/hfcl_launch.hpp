@@ -110,3 +110,35 @@ struct PatchArgs {
 };
 // three launches (classify, one-sided, clipped); names / e0 / e1: three entries (e0 == nullptr: no timing)
 void launch_patch(hipStream_t st, const PatchArgs& a, int max_blocks, const char** names, hipEvent_t* e0, hipEvent_t* e1);
+
+// hfcl_k_scene.hip: scene queries (hfcl_scene_*).  A chunk [q0, q0 + m) of the flat query range q = c * n_pairs + p ...
+struct SceneExpandArgs {
+  const uint32_t* pairs;         // 2 x n_pairs object indices
+  const uint32_t* object_shape;  // n_objects shape ids
+  const void* object_tf;         // n_conf x n_objects pose rows (12 doubles / 7 floats)
+  uint64_t n_objects;
+  uint32_t n_pairs;
+  uint64_t q0;
+  uint64_t c0;                   // (c0, p0) = scene_query(q0)
+  uint32_t p0;
+  uint32_t m;
+  uint32_t* s1;
+  uint32_t* s2;
+  void* tf1;                     // m rows each, 16-byte aligned
+  void* tf2;
+};
+// ... -> the per-pair arrays of run_batch
+void launch_scene_expand(hipStream_t st, const SceneExpandArgs& a, bool f32, int max_blocks);
+struct SceneFoldArgs {
+  const void* rec;               // the chunk's records (hfcl_result / hfcl_result_f32): rec[0] is query q0's
+  uint64_t q0, q1;
+  uint32_t n_pairs;
+  uint64_t g0;                   // first piece of the chunk (hfcl_scene.hpp: scene_piece_of(q0)) and how many it touches
+  uint64_t n_pieces;
+  double margin;                 // collide: the request's security margin
+  int collide;
+  hfcl_scene_summary* summary;   // by configuration
+  hfcl_scene_summary* partials;  // nullptr (pair lists of one piece) or n_pieces slots
+};
+// ... -> the summaries of the configurations it touches (one launch, or two when a pair list has several pieces)
+void launch_scene_fold(hipStream_t st, const SceneFoldArgs& a, bool f32, int max_blocks);

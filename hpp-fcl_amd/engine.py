@@ -30,6 +30,9 @@ EXPORTED_SYMBOLS = [
     "hfcl_lib_set_option", "hfcl_lib_option_key", "hfcl_has_ab_forms", "hfcl_multi_set_option", "hfcl_multi_last_gather",
     "hfcl_contact_patch_request_init", "hfcl_patch_supported", "hfcl_contact_patch_max_points", "hfcl_contact_patch_max_points_shapes",
     "hfcl_contact_patch_batch", "hfcl_contact_patch_batch_device",
+    "hfcl_scene_create", "hfcl_scene_set_pairs", "hfcl_scene_destroy", "hfcl_scene_num_objects", "hfcl_scene_num_pairs",
+    "hfcl_scene_collide", "hfcl_scene_distance", "hfcl_scene_collide_device", "hfcl_scene_distance_device",
+    "hfcl_scene_collide_f32", "hfcl_scene_distance_f32", "hfcl_scene_collide_device_f32", "hfcl_scene_distance_device_f32",
 ]
 
 
@@ -76,6 +79,10 @@ def dll():
         d.hfcl_pairlist_size.restype = C.c_size_t
         d.hfcl_pairlist_data.restype = C.c_void_p
         d.hfcl_lib_option_key.restype = C.c_char_p
+        if hasattr(d, "hfcl_scene_create"):  # (an A/B build of an older source tree behind HFCL_LIB_PATH has no scenes: Library.scene raises there)
+            d.hfcl_scene_create.restype = C.c_void_p
+            d.hfcl_scene_num_objects.restype = C.c_size_t
+            d.hfcl_scene_num_pairs.restype = C.c_size_t
         _DLL = d
     return _DLL
 
@@ -394,6 +401,11 @@ class Library:
         fn = dll().hfcl_compact_results_device_f32 if f32 else dll().hfcl_compact_results_device
         _check(fn(self._h, _dptr(d_records), C.c_size_t(n), _dptr(d_out), C.c_void_p(stream)))
 
+    def scene(self, object_shape, pairs):
+        """hfcl_scene_create: the object -> shape table and the (n_pairs, 2) list of object pairs, resident on this
+        library's device (see Scene).  Close the scene before the library."""
+        return Scene(self, object_shape, pairs)
+
     # ---- instrumentation ----
     def set_split(self, parts):
         """2: large batches run as two halves on two streams (hfcl_lib_set_split); 1: one stream."""
@@ -434,6 +446,108 @@ class Library:
         out = (C.c_uint32 * 4)()
         dll().hfcl_last_ordered_reruns(self._h, out)
         return dict(zip(["mesh_continued", "mesh_rerun", "solid_continued", "solid_rerun"], [int(v) for v in out]))
+
+
+class Scene:
+    """hfcl_scene: objects (a shape each), a list of object pairs, and queries that evaluate the list for n_conf pose
+    tables.  Query c * n_pairs + p is pair p of configuration c; its record is the per-pair call's record."""
+
+    def __init__(self, library, object_shape, pairs):
+        d = dll()
+        self.library = library
+        ids = np.ascontiguousarray(object_shape, dtype=np.uint32).reshape(-1)
+        pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        h = d.hfcl_scene_create(library._h, abi.ptr(ids), C.c_size_t(len(ids)), abi.ptr(pr), C.c_size_t(len(pr)))
+        if not h:  # (hfcl_scene_create has no return code: its message names the causes that are not an invalid argument)
+            msg = last_error()
+            code = abi.ERR_LIMIT if msg.startswith("HFCL_ERR_LIMIT: ") else abi.ERR_HIP if msg.startswith("HFCL_ERR_HIP: ") else abi.ERR_INVALID_ARGUMENT
+            raise EngineError(code, msg)
+        self._h = C.c_void_p(h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            dll().hfcl_scene_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            if getattr(self.library, "_h", None):  # (a scene must not outlive its library)
+                self.close()
+        except Exception:
+            pass
+
+    @property
+    def n_objects(self):
+        return int(dll().hfcl_scene_num_objects(self._h))
+
+    @property
+    def n_pairs(self):
+        return int(dll().hfcl_scene_num_pairs(self._h))
+
+    def set_pairs(self, pairs):
+        """hfcl_scene_set_pairs: a new pair list over the same objects (a new broadphase pass)."""
+        pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        _check(dll().hfcl_scene_set_pairs(self._h, abi.ptr(pr), C.c_size_t(len(pr))))
+
+    def _table(self, object_tf, dtype, width):
+        tf = np.ascontiguousarray(object_tf, dtype=dtype)
+        if tf.ndim < 2 or tf.shape[-1] != width:
+            raise ValueError("pose table must have shape (n_conf, n_objects, %d) or (n_objects, %d)" % (width, width))
+        tf = tf.reshape(-1, self.n_objects, width) if self.n_objects else tf.reshape(0, 0, width)
+        return tf
+
+    def _host(self, fn, object_tf, req, records, summary, guess_in, want_guess, f32):
+        tf = self._table(object_tf, np.float32 if f32 else np.float64, 7 if f32 else 12)
+        n_conf, n = len(tf), len(tf) * self.n_pairs
+        out = np.zeros(n, dtype=abi.RESULT_F32_DTYPE if f32 else abi.RESULT_DTYPE) if records else None
+        summ = np.zeros(n_conf, dtype=abi.SCENE_SUMMARY_DTYPE) if summary else None
+        args = [self._h, abi.ptr(tf), C.c_size_t(n_conf), C.byref(req), abi.ptr(out), abi.ptr(summ)]
+        gout = None
+        if not f32:
+            if guess_in is not None:
+                guess_in = np.ascontiguousarray(guess_in, dtype=abi.GUESS_DTYPE)
+                if len(guess_in) != n:
+                    raise ValueError("guess_in must have one record per query")
+            gout = np.zeros(n, dtype=abi.GUESS_DTYPE) if want_guess else None
+            args += [abi.ptr(guess_in), abi.ptr(gout)]
+        _check(fn(*args))
+        res = tuple(x for x, on in ((out, records), (summ, summary), (gout, want_guess and not f32)) if on)
+        return res[0] if len(res) == 1 else res
+
+    def collide(self, object_tf, req=None, records=True, summary=True, guess_in=None, want_guess=False):
+        """hfcl_scene_collide.  Returns what was asked for, in the order (records, summaries, guesses); a single item bare."""
+        return self._host(dll().hfcl_scene_collide, object_tf, req or abi.default_collision_request(), records, summary, guess_in,
+                          want_guess, False)
+
+    def distance(self, object_tf, req=None, records=True, summary=True, guess_in=None, want_guess=False):
+        return self._host(dll().hfcl_scene_distance, object_tf, req or abi.default_distance_request(), records, summary, guess_in,
+                          want_guess, False)
+
+    def collide_f32(self, object_pose, req=None, records=True, summary=True):
+        """(n_conf, n_objects, 7) float32 poses (quaternion w, x, y, z + translation), hfcl_result_f32 records."""
+        return self._host(dll().hfcl_scene_collide_f32, object_pose, req or abi.default_collision_request(), records, summary, None,
+                          False, True)
+
+    def distance_f32(self, object_pose, req=None, records=True, summary=True):
+        return self._host(dll().hfcl_scene_distance_f32, object_pose, req or abi.default_distance_request(), records, summary, None,
+                          False, True)
+
+    # device forms: torch tensors or raw device pointers, asynchronous on `stream`; d_out / d_summary may each be None
+    def collide_device(self, d_object_tf, n_conf, req, d_out=None, d_summary=None, d_gin=None, d_gout=None, stream=0):
+        _check(dll().hfcl_scene_collide_device(self._h, _dptr(d_object_tf), C.c_size_t(int(n_conf)), C.byref(req), _dptr(d_out),
+                                               _dptr(d_summary), _dptr(d_gin), _dptr(d_gout), C.c_void_p(stream)))
+
+    def distance_device(self, d_object_tf, n_conf, req, d_out=None, d_summary=None, d_gin=None, d_gout=None, stream=0):
+        _check(dll().hfcl_scene_distance_device(self._h, _dptr(d_object_tf), C.c_size_t(int(n_conf)), C.byref(req), _dptr(d_out),
+                                                _dptr(d_summary), _dptr(d_gin), _dptr(d_gout), C.c_void_p(stream)))
+
+    def collide_device_f32(self, d_object_pose, n_conf, req, d_out=None, d_summary=None, stream=0):
+        _check(dll().hfcl_scene_collide_device_f32(self._h, _dptr(d_object_pose), C.c_size_t(int(n_conf)), C.byref(req), _dptr(d_out),
+                                                   _dptr(d_summary), C.c_void_p(stream)))
+
+    def distance_device_f32(self, d_object_pose, n_conf, req, d_out=None, d_summary=None, stream=0):
+        _check(dll().hfcl_scene_distance_device_f32(self._h, _dptr(d_object_pose), C.c_size_t(int(n_conf)), C.byref(req), _dptr(d_out),
+                                                    _dptr(d_summary), C.c_void_p(stream)))
 
 
 def shard_range(n, rank, world):

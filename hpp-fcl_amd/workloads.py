@@ -478,6 +478,55 @@ def cfg5_broadphase_scene(n_objects=100_000, target_pairs=1_000_000, seed=1, npe
     return b
 
 
+class PlannerScene:
+    """scene_planner's product: lib, obj_shape (G,), pairs (P, 2), quat (n_conf, G, 4), T (n_conf, G, 3)."""
+
+    def __init__(self, lib, obj_shape, pairs, quat, T):
+        self.lib, self.obj_shape, self.pairs, self.quat, self.T = lib, obj_shape, pairs, quat, T
+        self.shapes, self.verts = lib.shapes_array(), lib.vertices_array()
+        self.kind, self.request_overrides, self.meshes = "collide", {}, None
+        self.name = "scene_planner_%dx%d" % (len(quat), len(obj_shape))
+
+    @property
+    def obj_tf(self):
+        """(n_conf, G, 12) Transform3f images"""
+        n_conf, G = self.quat.shape[:2]
+        return geometry.make_pose(quat=self.quat.reshape(-1, 4), T=self.T.reshape(-1, 3)).reshape(n_conf, G, 12)
+
+    @property
+    def obj_pose_f32(self):
+        n_conf, G = self.quat.shape[:2]
+        return geometry.pose_f32_from_quat(self.quat.reshape(-1, 4), self.T.reshape(-1, 3)).reshape(n_conf, G, 7)
+
+    def expand(self):
+        """The per-pair Batch a caller without scenes builds on the host: query c * P + p = pair p of configuration c."""
+        i, j = self.pairs[:, 0], self.pairs[:, 1]
+        f = lambda a, k: a[:, k].reshape(-1, a.shape[-1])  # noqa: E731
+        n_conf = len(self.quat)
+        return Batch(self.name, self.lib, np.tile(self.obj_shape[i], n_conf), np.tile(self.obj_shape[j], n_conf), f(self.quat, i), f(self.T, i),
+                     f(self.quat, j), f(self.T, j), "collide")
+
+
+def scene_planner(n_conf=2048, n_objects=16, seed=1, nper=64, link=1.6, bend=0.8):
+    """What a sampling-based planner asks: n_conf configurations of a chain of n_objects bodies (the cfg5 shape mix), and the
+    fixed list of all G (G - 1) / 2 body pairs minus the chain's neighbours.  A configuration is a bent chain: body k sits
+    `link` away from body k - 1 in the direction e_x + bend * N(0, I), normalised, with a uniformly random orientation.
+    The defaults (bodies reach 0.1 .. 1.8 from their centres) leave a minority of the configurations in collision: 38 % of
+    256 configurations of 16 bodies, 14 % with 8 bodies (oracle, seed 1; tests/test_scene_cpu.py prints and holds the share)."""
+    rng = _rng(seed, 77)
+    lib = _mixed_library(rng, nper)
+    obj_shape = rng.integers(0, 5 * nper, n_objects).astype(np.uint32)
+    quat = uniform_quaternions(rng, n_conf * n_objects).reshape(n_conf, n_objects, 4)
+    step = bend * rng.normal(size=(n_conf, n_objects, 3))
+    step[..., 0] += 1.0
+    step *= link / np.linalg.norm(step, axis=-1, keepdims=True)
+    step[:, 0] = 0.0
+    T = np.cumsum(step, axis=1)
+    i, j = np.triu_indices(n_objects, 2)  # j - i >= 2
+    pairs = np.stack([i, j], axis=1).astype(np.uint32)
+    return PlannerScene(lib, obj_shape, pairs, quat, T)
+
+
 _MESH_CACHE = {}
 
 

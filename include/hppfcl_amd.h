@@ -570,6 +570,84 @@ int hfcl_contact_patch_batch_device(hfcl_lib* lib, const uint32_t* d_shape1, con
                                     const hfcl_patch_request* req, uint32_t points_capacity, hfcl_contact_patch* d_out,
                                     double* d_out_points, void* stream);
 
+/* ---- scene queries: an object pose table, a pair list, per-configuration folds ------------------------------------------
+ * What a caller of hpp-fcl holds is CollisionObjects -- a geometry and ONE transform each (collision_object.h) -- and a list
+ * of object pairs, from a broadphase pass (CollisionCallBackCollect, src/broadphase/default_broadphase_callbacks.cpp:91-123;
+ * hfcl_broadphase_self_pairs) or fixed by a robot model.  A scene keeps, on its library's device, the object -> shape table
+ * and the pair list; a query evaluates the pair list for n_conf configurations of the objects:
+ *   configuration c gives object o the pose object_tf[c * n_objects + o] (12 doubles; the _f32 forms: 7 floats);
+ *   query q = c * n_pairs + p is pair p = (i, j) of configuration c, and record q is what hfcl_collide_batch_device writes
+ *   for (object_shape[i], object_shape[j], tf[c][i], tf[c][j]) -- byte for byte, guess_out included.
+ * Each pose crosses the host link once per configuration instead of once per pair it takes part in, and a caller that only
+ * wants what the default callbacks answer gets one hfcl_scene_summary per configuration back instead of a record per pair.
+ *
+ * The summary is a fold over ALL listed pairs of one configuration, defined so that it can be recomputed from the records
+ * exactly.  n_contacts > 0 is CollisionCallBackDefault's result.isCollision() after manager.collide(&cb)
+ * (default_broadphase_callbacks.cpp:43-75), and min_distance of a distance query is DistanceCallBackDefault's answer (:77-89).
+ * It is NOT the rest of what the default collision callback leaves behind: that callback stops at the first colliding pair of
+ * ITS tree traversal, so which pair it stops at, and the lower bound it has seen by then, are facts of the traversal order
+ * that a flat pair list does not have.  first_contact is defined by list order instead. */
+typedef struct hfcl_scene_summary {
+  double   min_distance;     /* collide: min of (distance - security_margin) = CollisionResult::distance_lower_bound of the pair;
+                                distance: min of min_distance.  Over the computed records whose value is not NaN; +inf if none.
+                                _f32 forms: the float value (margin subtracted in float) widened exactly */
+  uint32_t min_pair;         /* lowest pair index p attaining it; 0xFFFFFFFF if none */
+  uint32_t first_contact;    /* lowest p whose record has the contact flag (HFCL_STATUS_CONTACT); 0xFFFFFFFF if none */
+  uint32_t n_contacts;       /* records with the contact flag */
+  uint32_t n_skipped;        /* records with status bit 31 */
+} hfcl_scene_summary;        /* 24 bytes */
+
+typedef struct hfcl_scene hfcl_scene;   /* opaque: belongs to one library */
+/* object_shape: n_objects shape ids of `lib`; pairs: 2 * n_pairs object indices (i, j) as hfcl_pairlist_data gives them (i == j
+ * is allowed).  Checked on the host before anything is copied: a shape id outside the library or an object index >= n_objects is
+ * HFCL_ERR_INVALID_ARGUMENT, n_pairs > 2^32 - 16 is HFCL_ERR_LIMIT; hfcl_scene_create then returns NULL and, having no return code,
+ * says which in hfcl_last_error (its message starts with "HFCL_ERR_LIMIT: " or "HFCL_ERR_HIP: " for those two causes), and
+ * hfcl_scene_set_pairs -- a new broadphase pass over the same objects -- leaves the scene as it was.
+ * hfcl_lib_set_shapes invalidates the scenes of its library: their next query returns HFCL_ERR_INVALID_ARGUMENT (create a new
+ * scene).  Destroy a library's scenes before the library; destroying the library first is the caller's error. */
+hfcl_scene* hfcl_scene_create(hfcl_lib* lib, const uint32_t* object_shape, size_t n_objects, const uint32_t* pairs, size_t n_pairs);
+int    hfcl_scene_set_pairs(hfcl_scene* s, const uint32_t* pairs, size_t n_pairs);
+void   hfcl_scene_destroy(hfcl_scene* s);
+size_t hfcl_scene_num_objects(const hfcl_scene* s);
+size_t hfcl_scene_num_pairs(const hfcl_scene* s);
+/* Host arrays, blocking.  object_tf: n_conf * n_objects poses.  out: NULL or n_conf * n_pairs records; summary: NULL or n_conf;
+ * not both NULL.  With out == NULL no per-pair record leaves the device.  guess_in / guess_out: NULL or n_conf * n_pairs.
+ * The flat query range is processed in chunks (option `scene_chunk`, by default equal chunks of at most 2^21 queries; n_conf * n_pairs is not bounded by 2^32, and a chunk may
+ * start and end in the middle of a configuration); the library's workspace is sized by a chunk.  The object table crosses the
+ * link once, a chunk's records come back while the next chunk computes, the summaries once at the end.  Synchronises its own
+ * streams only, never the device -- except in a call that has to grow the library's scene workspace (the first call, a larger
+ * chunk or table than any before): freeing and allocating device memory waits for the device.  The same holds for the device forms.
+ * Requests: exactly as hfcl_collide_batch / hfcl_distance_batch (num_max_contacts == 0, epa_max_iterations > 64: refused before
+ * any work; security_margin == -inf: every record skipped; a pair without an evaluator: HFCL_ERR_UNSUPPORTED_PAIR after every
+ * chunk has run, its record with status bit 31 and counted in n_skipped, every other record and the summaries complete).
+ * n_pairs == 0 or n_conf == 0: HFCL_OK, nothing written.
+ * A scene's workspace belongs to its library and is shared by the library's scenes: calls on scenes of one library must not
+ * overlap (different host threads, or device forms on different streams). */
+int hfcl_scene_collide(hfcl_scene* s, const double* object_tf, size_t n_conf, const hfcl_collision_request* req,
+                       hfcl_result* out, hfcl_scene_summary* summary, const hfcl_guess* guess_in, hfcl_guess* guess_out);
+int hfcl_scene_distance(hfcl_scene* s, const double* object_tf, size_t n_conf, const hfcl_distance_request* req,
+                        hfcl_result* out, hfcl_scene_summary* summary, const hfcl_guess* guess_in, hfcl_guess* guess_out);
+/* Device pointers on the library's device, asynchronous on `stream` (hipStream_t as void*); the chunks of a call run in order on
+ * that stream.  With d_out == NULL the records live in a library-owned chunk buffer just long enough to be folded.  As with
+ * hfcl_collide_batch_device, pairs without an evaluator are not reported by the return value (nothing is read back): their
+ * records carry status bit 31 and n_skipped counts them. */
+int hfcl_scene_collide_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const hfcl_collision_request* req,
+                              hfcl_result* d_out, hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in,
+                              hfcl_guess* d_guess_out, void* stream);
+int hfcl_scene_distance_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const hfcl_distance_request* req,
+                               hfcl_result* d_out, hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in,
+                               hfcl_guess* d_guess_out, void* stream);
+/* The fp32 path: 7-float poses (quaternion w, x, y, z + translation), hfcl_result_f32 records, no guesses -- as
+ * hfcl_collide_batch_f32 / hfcl_collide_batch_device_f32. */
+int hfcl_scene_collide_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, const hfcl_collision_request* req,
+                           hfcl_result_f32* out, hfcl_scene_summary* summary);
+int hfcl_scene_distance_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, const hfcl_distance_request* req,
+                            hfcl_result_f32* out, hfcl_scene_summary* summary);
+int hfcl_scene_collide_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, const hfcl_collision_request* req,
+                                  hfcl_result_f32* d_out, hfcl_scene_summary* d_summary, void* stream);
+int hfcl_scene_distance_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, const hfcl_distance_request* req,
+                                   hfcl_result_f32* d_out, hfcl_scene_summary* d_summary, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

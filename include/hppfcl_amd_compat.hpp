@@ -1331,6 +1331,132 @@ inline void collide(const std::vector<CollisionCallBackCollect::CollisionPair>& 
   }
   ctx.collide(ids, tf1, tf2, request, results);
 }
+
+/// A scene (hfcl_scene_*, include/hppfcl_amd.h): CollisionObjects and a list of object pairs -- what a broadphase pass collected, or what a
+/// robot model fixes -- kept on the device; a query evaluates the list for one or many tables of object transforms.  Every transform
+/// crosses the host link once per configuration instead of once per pair, and a caller that only wants the default callbacks' answer
+/// asks for the summaries alone (hfcl_scene_summary: n_contacts > 0 is CollisionCallBackDefault's isCollision(), min_distance of a
+/// distance query DistanceCallBackDefault's answer).
+///   manager.collide(&collect);                                        // host broadphase
+///   amd::Scene scene(objects, collect.getCollisionPairs());           // once per pair list
+///   scene.collide(tables, n_conf, request, nullptr, &summaries);      // per batch of configurations
+/// Runs on the first device of the context.  One contact per pair (contact lists of mesh pairs go through amd::collide).  The scene must
+/// be destroyed before its context, and the context must not be reset() while the scene lives; geometries added to the context later are
+/// followed (the scene is re-created on the next query).
+class Scene {
+ public:
+  Scene(const std::vector<CollisionObject*>& objects, const std::vector<std::pair<size_t, size_t>>& pairs, BatchQueries& ctx = default_context())
+      : ctx_(ctx), objects_(objects) {
+    pairs_.reserve(2 * pairs.size());
+    for (const auto& p : pairs) {
+      if (p.first >= objects.size() || p.second >= objects.size()) throw std::invalid_argument("Scene: pair index outside the objects");
+      pairs_.push_back(static_cast<uint32_t>(p.first));
+      pairs_.push_back(static_cast<uint32_t>(p.second));
+    }
+    init();
+  }
+  /// ... from the pairs a CollisionCallBackCollect holds (every object of a pair must be one of `objects`)
+  Scene(const std::vector<CollisionObject*>& objects, const std::vector<CollisionCallBackCollect::CollisionPair>& pairs,
+        BatchQueries& ctx = default_context())
+      : ctx_(ctx), objects_(objects) {
+    std::map<const CollisionObject*, uint32_t> index;
+    for (size_t i = 0; i < objects.size(); ++i) index.emplace(objects[i], static_cast<uint32_t>(i));
+    pairs_.reserve(2 * pairs.size());
+    for (const auto& p : pairs) {
+      auto a = index.find(p.first), b = index.find(p.second);
+      if (a == index.end() || b == index.end()) throw std::invalid_argument("Scene: a collected pair holds an object that is not in the scene");
+      pairs_.push_back(a->second);
+      pairs_.push_back(b->second);
+    }
+    init();
+  }
+  ~Scene() { hfcl_scene_destroy(scene_); }
+  Scene(const Scene&) = delete;
+  Scene& operator=(const Scene&) = delete;
+  size_t numObjects() const { return objects_.size(); }
+  size_t numPairs() const { return pairs_.size() / 2; }
+
+  /// The objects' current transforms: one configuration.  results: nullptr or numPairs() results, results[p] what
+  /// hpp::fcl::collide gives for pair p; summaries: nullptr or one record.  Not both nullptr.
+  void collide(const CollisionRequest& request, std::vector<CollisionResult>* results, std::vector<hfcl_scene_summary>* summaries) {
+    const std::vector<Transform3f> table = current();
+    collide(table.data(), 1, request, results, summaries);
+  }
+  /// n_conf tables of numObjects() transforms each: results[c * numPairs() + p], summaries[c].
+  void collide(const Transform3f* tables, size_t n_conf, const CollisionRequest& request, std::vector<CollisionResult>* results,
+               std::vector<hfcl_scene_summary>* summaries) {
+    ensure();
+    const hfcl_collision_request a = to_abi(request);
+    const size_t n = n_conf * numPairs();
+    if (results) {
+      rec_.resize(n);
+      guess_.resize(n);
+    }
+    if (summaries) summaries->resize(n_conf);
+    const int rc = hfcl_scene_collide(scene_, reinterpret_cast<const double*>(tables), n_conf, &a, results ? rec_.data() : nullptr,
+                                      summaries ? summaries->data() : nullptr, nullptr, results ? guess_.data() : nullptr);
+    if (rc) throw_for(rc);
+    if (!results) return;
+    results->assign(n, CollisionResult());
+    for (size_t q = 0; q < n; ++q) {
+      hfcl_result r = rec_[q];
+      if (r.num_contacts > 1) r.num_contacts = 1;  // (a mesh pair under num_max_contacts > 1: the record holds its first contact)
+      ctx_.fill((*results)[q], shape_pair(q % numPairs()), request, r, guess_[q]);
+    }
+  }
+  void distance(const DistanceRequest& request, std::vector<DistanceResult>* results, std::vector<hfcl_scene_summary>* summaries) {
+    const std::vector<Transform3f> table = current();
+    distance(table.data(), 1, request, results, summaries);
+  }
+  void distance(const Transform3f* tables, size_t n_conf, const DistanceRequest& request, std::vector<DistanceResult>* results,
+                std::vector<hfcl_scene_summary>* summaries) {
+    ensure();
+    const hfcl_distance_request a = to_abi(request);
+    const size_t n = n_conf * numPairs();
+    if (results) {
+      rec_.resize(n);
+      guess_.resize(n);
+    }
+    if (summaries) summaries->resize(n_conf);
+    const int rc = hfcl_scene_distance(scene_, reinterpret_cast<const double*>(tables), n_conf, &a, results ? rec_.data() : nullptr,
+                                       summaries ? summaries->data() : nullptr, nullptr, results ? guess_.data() : nullptr);
+    if (rc) throw_for(rc);
+    if (!results) return;
+    results->assign(n, DistanceResult());
+    for (size_t q = 0; q < n; ++q) ctx_.fill((*results)[q], shape_pair(q % numPairs()), rec_[q], guess_[q]);
+  }
+  const std::vector<hfcl_result>& records() const { return rec_; }
+
+ private:
+  void init() {
+    shape_.resize(objects_.size());
+    for (size_t i = 0; i < objects_.size(); ++i) shape_[i] = ctx_.add(objects_[i]->collisionGeometryPtr());
+    ensure();
+  }
+  void ensure() {  // the device scene, made for the context's library as it is now
+    hfcl_lib* lib = ctx_.library();
+    if (scene_ && lib == lib_ && geometries_ == ctx_.numGeometries()) return;
+    hfcl_scene_destroy(scene_);
+    scene_ = hfcl_scene_create(lib, shape_.data(), shape_.size(), pairs_.data(), pairs_.size() / 2);
+    if (!scene_) throw_for(HFCL_ERR_INVALID_ARGUMENT);
+    lib_ = lib;
+    geometries_ = ctx_.numGeometries();
+  }
+  std::vector<Transform3f> current() const {
+    std::vector<Transform3f> t(objects_.size());
+    for (size_t i = 0; i < objects_.size(); ++i) t[i] = objects_[i]->getTransform();
+    return t;
+  }
+  std::pair<uint32_t, uint32_t> shape_pair(size_t p) const { return {shape_[pairs_[2 * p]], shape_[pairs_[2 * p + 1]]}; }
+  BatchQueries& ctx_;
+  std::vector<CollisionObject*> objects_;
+  std::vector<uint32_t> shape_, pairs_;
+  hfcl_scene* scene_ = nullptr;
+  hfcl_lib* lib_ = nullptr;
+  size_t geometries_ = 0;
+  std::vector<hfcl_result> rec_;
+  std::vector<hfcl_guess> guess_;
+};
 }  // namespace amd
 
 }  // namespace fcl

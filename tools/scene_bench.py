@@ -1,0 +1,187 @@
+#!/usr/bin/env python3
+"""Scene queries against the per-pair calls: time per call and bytes moved, fp64 collide, on cfg5's broadphase scene (~1 M pairs, one
+configuration) and on workloads.scene_planner at ~1 M queries.
+
+  A  hfcl_collide_batch on host-expanded arrays (host clock; the host expansion is timed separately)
+  B  hfcl_scene_collide, records and summaries (host clock)        C  ... summaries only
+  D  hfcl_collide_batch_device on pre-expanded resident arrays (device events)
+  E  hfcl_scene_collide_device, records and summaries (device events)   F  ... summaries only
+
+Every measurement runs in a child process; A and D also run on a library built from the parent commit's sources (--parent-lib, selected
+with HFCL_LIB_PATH in the child), alternating with the build under test.  Warm-up calls first, then --calls timed calls: median, min, max.
+
+  python tools/scene_bench.py [--parent-lib build/ab/lib_parent.so] [--calls 12] [--rounds 2] [--out profiles/x.json]
+  python tools/scene_bench.py --worker --workload cfg5 --forms A,D     (one child; prints one JSON line)"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _workload(pkg, name):
+    wl = pkg.workloads
+    if name == "cfg5":
+        b = wl.cfg5_broadphase_scene()
+        sc = b.scene
+        return b.lib, sc["obj_shape"], sc["pairs"], sc["obj_tf"].reshape(1, -1, 12)
+    ps = wl.scene_planner(n_conf=9984, n_objects=16)
+    return ps.lib, ps.obj_shape, ps.pairs, ps.obj_tf
+
+
+def _stats(ms):
+    ms = sorted(ms)
+    return {"median_ms": float(np.median(ms)), "min_ms": ms[0], "max_ms": ms[-1], "calls": len(ms)}
+
+
+def worker(args):
+    import torch
+    import __graft_entry__ as ge
+    pkg = ge.load_pkg()
+    abi = pkg.abi
+    L, obj_shape, pairs, table = _workload(pkg, args.workload)
+    n_conf, G, P = table.shape[0], table.shape[1], len(pairs)
+    n = n_conf * P
+    i, j = pairs[:, 0], pairs[:, 1]
+    lib = pkg.Library(L)
+    req = abi.default_collision_request()
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    out = {"workload": args.workload, "lib": os.environ.get("HFCL_LIB_PATH", "in-tree"), "n_conf": n_conf, "n_objects": G, "n_pairs": P, "queries": n,
+           "forms": {}}
+
+    def expand():
+        return (np.tile(obj_shape[i], n_conf), np.tile(obj_shape[j], n_conf), np.ascontiguousarray(table[:, i].reshape(n, 12)),
+                np.ascontiguousarray(table[:, j].reshape(n, 12)))
+
+    def host_clock(fn):
+        for _ in range(args.warmup):
+            fn()
+        ms = []
+        for _ in range(args.calls):
+            t0 = time.perf_counter()
+            fn()
+            ms.append(1e3 * (time.perf_counter() - t0))
+        return _stats(ms)
+
+    def device_clock(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(args.calls):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ms.append(float(e0.elapsed_time(e1)))
+        return _stats(ms)
+
+    forms = args.forms.split(",")
+    scene = lib.scene(obj_shape, pairs) if set(forms) & set("BCEF") else None
+    if "A" in forms or "D" in forms:
+        t0 = time.perf_counter()
+        s1, s2, tf1, tf2 = expand()
+        out["host_expansion_ms"] = 1e3 * (time.perf_counter() - t0)
+    if "A" in forms:
+        out["forms"]["A"] = host_clock(lambda: lib.collide(s1, s2, tf1, tf2, req))
+    if "B" in forms:
+        out["forms"]["B"] = host_clock(lambda: scene.collide(table, req))
+    if "C" in forms:
+        out["forms"]["C"] = host_clock(lambda: scene.collide(table, req, records=False))
+    if "D" in forms:
+        d = [torch.from_numpy(x).to(dev) for x in (s1.astype(np.int32), s2.astype(np.int32), tf1, tf2)]
+        d_out = torch.zeros(n * 24, dtype=torch.int32, device=dev)
+        out["forms"]["D"] = device_clock(lambda: lib.collide_device(*d, n, req, d_out, stream=st))
+    if "E" in forms or "F" in forms:
+        d_tab = torch.from_numpy(np.ascontiguousarray(table)).to(dev)
+        d_sum = torch.zeros(n_conf * 6, dtype=torch.int32, device=dev)
+    if "E" in forms:
+        d_rec = torch.zeros(n * 24, dtype=torch.int32, device=dev)
+        out["forms"]["E"] = device_clock(lambda: scene.collide_device(d_tab, n_conf, req, d_rec, d_sum, stream=st))
+    if "F" in forms:
+        out["forms"]["F"] = device_clock(lambda: scene.collide_device(d_tab, n_conf, req, None, d_sum, stream=st))
+    torch.cuda.synchronize()
+    if scene is not None:
+        scene.close()
+    lib.close()
+    print("SCENE_BENCH " + json.dumps(out), flush=True)
+
+
+def bytes_moved(n_conf, G, P):
+    """Bytes per query over the host link (in / out) and through HBM by the expansion and the fold, from the shapes."""
+    n = n_conf * P
+    table = 96.0 * n_conf * G
+    ids = 8.0 * P + 4.0 * G
+    return {
+        "A": {"link_in": 200.0, "link_out": 96.0},
+        "B": {"link_in": (table + ids) / n, "link_out": 96.0 + 24.0 * n_conf / n},
+        "C": {"link_in": (table + ids) / n, "link_out": 24.0 * n_conf / n},
+        "expand_hbm": 8.0 + 2 * 96.0 + 8.0,       # pair list in (read once per configuration), two pose rows and two ids out (rows come from cache)
+        "fold_hbm": 12.0,                         # distance and status of a record (the lines they sit in: up to 2 x 64 B of a 96-B record)
+    }
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--worker", action="store_true")
+    ap.add_argument("--workload", default="cfg5", choices=["cfg5", "planner"])
+    ap.add_argument("--forms", default="A,B,C,D,E,F")
+    ap.add_argument("--calls", type=int, default=12)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--parent-lib", default=os.path.join(ROOT, "build", "ab", "lib_parent.so"))
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if args.worker:
+        return worker(args)
+    have_parent = os.path.exists(args.parent_lib)
+    results = []
+    for workload in ("cfg5", "planner"):
+        for _ in range(args.rounds):
+            for which in (["parent"] if have_parent else []) + ["new"]:
+                env = dict(os.environ)
+                env.pop("HFCL_LIB_PATH", None)
+                if which == "parent":
+                    env["HFCL_LIB_PATH"] = args.parent_lib
+                cmd = [sys.executable, os.path.abspath(__file__), "--worker", "--workload", workload, "--calls", str(args.calls), "--warmup",
+                       str(args.warmup), "--forms", "A,D" if which == "parent" else args.forms]
+                r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
+                line = [x for x in r.stdout.splitlines() if x.startswith("SCENE_BENCH ")]
+                if r.returncode != 0 or not line:  # a child that failed ends the run: nothing more is started on the device
+                    print(r.stdout[-2000:], r.stderr[-4000:])
+                    sys.exit("worker failed (%s, %s): exit status %d" % (workload, which, r.returncode))
+                res = json.loads(line[0][len("SCENE_BENCH "):])
+                res["build"] = which
+                results.append(res)
+                print(json.dumps(res), flush=True)
+    for workload in ("cfg5", "planner"):
+        rs = [r for r in results if r["workload"] == workload]
+        if not rs:
+            continue
+        r0 = rs[0]
+        print("\n%s: %d configurations x %d pairs = %d queries, %d objects" % (workload, r0["n_conf"], r0["n_pairs"], r0["queries"], r0["n_objects"]))
+        print("| form | build | median ms | min .. max ms (over the runs) |")
+        print("|---|---|---|---|")
+        for which in ("parent", "new"):
+            for f in "ABCDEF":
+                runs = [r["forms"][f] for r in rs if r["build"] == which and f in r["forms"]]
+                if runs:
+                    print("| %s | %s | %s | %.3f .. %.3f |" % (f, which, " / ".join("%.3f" % x["median_ms"] for x in runs),
+                                                          min(x["min_ms"] for x in runs), max(x["max_ms"] for x in runs)))
+        print("host expansion for A: %s ms" % " / ".join("%.1f" % r["host_expansion_ms"] for r in rs if "host_expansion_ms" in r))
+        print("bytes per query: " + json.dumps(bytes_moved(r0["n_conf"], r0["n_objects"], r0["n_pairs"])))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(results, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
