@@ -1392,9 +1392,12 @@ template <typename T, int M>
 static void launch_cvx_m(hfcl_lib* lib, const Work& wk, const LibView<T>& lv, const IO<T>& io, const QParams<T>& q,
                          hipStream_t st, size_t n) {
   const int w = lib->cvx_w ? lib->cvx_w : auto_cvx_w<T, M>();
-  size_t b = (n + size_t(256 / w) - 1) / size_t(256 / w);
+  const size_t nt = size_t(gjk_cvx_threads<T>(w, M));
+  size_t b = (n + nt / w - 1) / (nt / w);
   if (b < 1) b = 1;
-  if (b > size_t(lib->n_cus) * 16) b = size_t(lib->n_cus) * 16;
+  // single-wave workgroups: one per round of pairs, handed out by the dispatcher as waves end (the kernel's grid-stride loop serves what is beyond 2^20 rounds)
+  const size_t cap = nt == 64 ? size_t(1) << 20 : size_t(lib->n_cus) * 16;
+  if (b > cap) b = cap;
   launch_gjk_cvx<T>(M, w, q.guess_mode == HFCL_GUESS_BOUNDING_VOLUME, int(b), st, wk, lv, io, q);
 }
 // (next_stream, optional: called in front of every kernel, returns the stream it goes on -- the solids' kernels of a small batch fan out)
@@ -2955,6 +2958,17 @@ void hfcl_last_ordered_reruns(hfcl_lib* lib, uint32_t* out4) {
   }
 }
 
+// Convex x convex polytopes of the last fp32 call that outgrew k_epa_loop's block and were handed to k_epa_resume_cc (or, past the
+// hand-over area, to the full-capacity tier): CTR_EPA_CC_OVER.  Waits for the device like hfcl_last_bucket_counts.
+uint32_t hfcl_last_epa_handed_over(hfcl_lib* lib) {
+  if (!lib) return 0;
+  hipSetDevice(lib->device);
+  hipDeviceSynchronize();
+  if (lib->last_host) return lib->acc_counts[CTR_EPA_CC_OVER];
+  uint32_t c = lib->h_counts ? lib->h_counts[CTR_EPA_CC_OVER] : 0u;
+  if (lib->last_split && lib->helper && lib->helper->h_counts) c += lib->helper->h_counts[CTR_EPA_CC_OVER];
+  return c;
+}
 
 // ---- contact patches (hfcl_k_patch.hip) ------------------------------------------------------------------------------
 void hfcl_contact_patch_request_init(hfcl_patch_request* r) {

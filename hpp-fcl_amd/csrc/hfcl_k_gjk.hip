@@ -339,11 +339,12 @@ struct HullLds {
 template <typename T, int W, int M> constexpr bool hull_b_in_lds = HFCL_GJK_HULLB_LDS && M == 0 && W <= 4 && (HULL_MAX / W) * sizeof(T) <= 64;
 
 // M: 0 = convex-convex, 1 = prim-convex, 2 = convex-prim
-template <typename T, int W, int M>
+// NT: threads per workgroup (the stride of the LDS slabs)
+template <typename T, int W, int M, int NT>
 struct CvxSupport {
   DShape<T> a, b;
   HullRegs<T, W> h0;
-  typename std::conditional<hull_b_in_lds<T, W, M>, HullLds<T, W, 256>, HullRegs<T, W>>::type h1;
+  typename std::conditional<hull_b_in_lds<T, W, M>, HullLds<T, W, NT>, HullRegs<T, W>>::type h1;
   MDiff<T> md;
   int lig;
   __device__ __forceinline__ void eval(const V3<T>& dir, V3<T>& w, V3<T>& w0) const {
@@ -363,17 +364,17 @@ struct CvxSupport {
   __device__ __forceinline__ void operator()(const V3<T>& dir, V3<T>& w, V3<T>& w0) const { eval(dir, w, w0); }
 };
 
-template <typename T, int W, int M, bool BVG>
+template <typename T, int W, int M, bool BVG, int NT>
 __device__ __forceinline__ void gjk_cvx_body(const Work& wk, const LibView<T>& lib, const IO<T>& io, const QParams<T>& q) {
   constexpr int BUCKET = (M == 0) ? B_CC : (M == 1 ? B_PC : B_CP);
-  HFCL_GJK_W0_SLAB(T, 256, ps);
-  __shared__ T hull_slab[hull_b_in_lds<T, W, M> ? HullLds<T, W, 256>::WORDS : 1];
+  HFCL_GJK_W0_SLAB(T, NT, ps);
+  __shared__ T hull_slab[hull_b_in_lds<T, W, M> ? HullLds<T, W, NT>::WORDS : 1];
   const BucketList list = bucket_list(wk, BUCKET);
   const int lig = threadIdx.x & (W - 1);
   const uint32_t groups = (gridDim.x * blockDim.x) / W;
   for (uint32_t it = (blockIdx.x * blockDim.x + threadIdx.x) / W; it < list.cnt; it += groups) {
     const uint32_t pair = list[it];
-    CvxSupport<T, W, M> sup;
+    CvxSupport<T, W, M, NT> sup;
     if constexpr (hull_b_in_lds<T, W, M>) sup.h1.lane = hull_slab + threadIdx.x;
     sup.a = lib.shapes[wk.shape1[pair]];
     sup.b = lib.shapes[wk.shape2[pair]];
@@ -384,7 +385,7 @@ __device__ __forceinline__ void gjk_cvx_body(const Work& wk, const LibView<T>& l
     sup.md = make_mdiff(tf1, tf2);
     const T r0 = swept_radius(sup.a), r1 = swept_radius(sup.b);
     const V3<T> guess0 = initial_guess<T>(io, q, pair);
-    Gjk<T, typename GjkW0<T, 256>::P> g;
+    Gjk<T, typename GjkW0<T, NT>::P> g;
     // normalize_support_direction only when both are ConvexBase (minkowski_difference.cpp:261-266)
     if constexpr (BVG)
       gjk_run(g, q.gjk, start_guess(q, sup.a, sup.b, sup.md, guess0), r0 + r1, M == 0, sup, ps);
@@ -398,23 +399,26 @@ __device__ __forceinline__ void gjk_cvx_body(const Work& wk, const LibView<T>& l
 
 // Two entry points so that each precision gets its own register budget (waves per SIMD): the fp64
 // instantiation spills heavily at the fp32 setting (A/B in profiles/).
+// The fp32 convex x convex kernel of 2-lane groups runs in workgroups of one wave (gjk_cvx_threads, hfcl_launch.hpp): a wave's
+// round of 32 pairs lasts as long as its slowest pair, and a 256-thread block holds its four wave slots and its 60 KB of LDS until the
+// slowest of four such rounds has ended.  A wave that is a workgroup of its own (15 KB) is replaced the moment it ends.
 template <int W, int M, bool BVG>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W == 2 ? HFCL_WPE_GJK_W2 : HFCL_WPE_GJK, 8)))
+__global__ void __launch_bounds__(gjk_cvx_threads<float>(W, M)) __attribute__((amdgpu_waves_per_eu(W == 2 ? HFCL_WPE_GJK_W2 : HFCL_WPE_GJK, 8)))
 k_gjk_cvx(Work wk, LibView<float> lib, IO<float> io, QParams<float> q) {
-  gjk_cvx_body<float, W, M, BVG>(wk, lib, io, q);
+  gjk_cvx_body<float, W, M, BVG, gjk_cvx_threads<float>(W, M)>(wk, lib, io, q);
 }
 template <int W, int M, bool BVG>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HFCL_WPE_GJK64, 8)))
+__global__ void __launch_bounds__(gjk_cvx_threads<double>(W, M)) __attribute__((amdgpu_waves_per_eu(HFCL_WPE_GJK64, 8)))
 k_gjk_cvx64(Work wk, LibView<double> lib, IO<double> io, QParams<double> q) {
-  gjk_cvx_body<double, W, M, BVG>(wk, lib, io, q);
+  gjk_cvx_body<double, W, M, BVG, gjk_cvx_threads<double>(W, M)>(wk, lib, io, q);
 }
 template <int W, int M, bool BVG = false>
 static void launch_gjk_cvx(int grid, hipStream_t st, const Work& wk, const LibView<float>& lv, const IO<float>& io, const QParams<float>& q) {
-  hipLaunchKernelGGL((k_gjk_cvx<W, M, BVG>), dim3(grid), dim3(256), 0, st, wk, lv, io, q);
+  hipLaunchKernelGGL((k_gjk_cvx<W, M, BVG>), dim3(grid), dim3(gjk_cvx_threads<float>(W, M)), 0, st, wk, lv, io, q);
 }
 template <int W, int M, bool BVG = false>
 static void launch_gjk_cvx(int grid, hipStream_t st, const Work& wk, const LibView<double>& lv, const IO<double>& io, const QParams<double>& q) {
-  hipLaunchKernelGGL((k_gjk_cvx64<W, M, BVG>), dim3(grid), dim3(256), 0, st, wk, lv, io, q);
+  hipLaunchKernelGGL((k_gjk_cvx64<W, M, BVG>), dim3(grid), dim3(gjk_cvx_threads<double>(W, M)), 0, st, wk, lv, io, q);
 }
 template <typename T>
 struct LargeSupport {

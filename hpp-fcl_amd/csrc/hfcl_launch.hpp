@@ -38,6 +38,8 @@ template <typename T> void launch_unsupported(int grid, hipStream_t st, const Wo
 template <typename T> void launch_closed(int grid, hipStream_t st, const Work& wk, const LibView<T>& lv, const IO<T>& io, const QParams<T>& q, bool staged);
 template <typename T> void launch_gjk_prim(int grid, hipStream_t st, const Work& wk, const LibView<T>& lv, const IO<T>& io, const QParams<T>& q, bool bvg);
 // m: 0 = convex-convex, 1 = prim-convex, 2 = convex-prim; w: lanes per pair (2 / 4 / 8 / 16 / 32 / 64)
+// grid: workgroups of gjk_cvx_threads<T>(w, m) threads
+template <typename T> constexpr int gjk_cvx_threads(int w, int m) { return (sizeof(T) == 4 && w == 2 && m == 0) ? 64 : 256; }
 template <typename T> void launch_gjk_cvx(int m, int w, bool bvg, int grid, hipStream_t st, const Work& wk, const LibView<T>& lv, const IO<T>& io, const QParams<T>& q);
 template <typename T> void launch_gjk_large(int grid, hipStream_t st, const Work& wk, const LibView<T>& lv, const IO<T>& io, const QParams<T>& q, bool bvg);
 // 7-double (quaternion w,x,y,z + translation) poses -> 12-double Transform3f images

@@ -422,6 +422,8 @@ void hfcl_last_bucket_counts(hfcl_lib* lib, uint32_t* out12);
  * by a rounding error (see "Mesh distance(): which triangle pair is reported" below).  out4 = {mesh x mesh continued, re-run,
  * mesh x solid continued, re-run}.  Diagnostic; waits for the device. */
 void hfcl_last_ordered_reruns(hfcl_lib* lib, uint32_t* out4);
+/* fp32 convex x convex polytopes of the last call that outgrew the fast EPA block and were continued by the next tier (waits for the device) */
+uint32_t hfcl_last_epa_handed_over(hfcl_lib* lib);
 /* Batches of >= 128k pairs (library without meshes) can run as two halves on two streams -- the caller's and an
  * internal one, forked and joined with events, so the call stays asynchronous and ordered on the caller's stream.
  * Pays when the halves run different kernels side by side (mixed scenes: -6 % per batch) and costs ~3 % when the

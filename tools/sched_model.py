@@ -1,0 +1,168 @@
+#!/usr/bin/env python3
+"""Scheduling model of the two big kernels of the fp32 convex x convex path (cfg3), from the oracle's iteration counts.  No GPU needed.
+
+  k_gjk_cvx<2, 0>   a wave steps 32 pairs in lockstep: a round lasts set-up + the trips of its slowest pair (a pair's trips = its GJK
+                    iterations + 1).  256-thread form: block b owns the rounds of its four waves (it += groups) and frees its slots when
+                    the slowest of the four has ended; single-wave form: every round is a workgroup, placed as slots fall free.
+  k_epa_loop        a wave steps 8 polytopes in lockstep and refills when two groups are idle (a refill = 0.25 trip); blocks strided
+                    over one round of resident waves (the tree), or the last share of them drawn by ticket from a pool of counters:
+                    a design that was built, lost its measurement and is NOT in the tree (profiles/r07_a_wave_scheduling.md, HISTORY.md);
+                    its model stays so that the figures quoted there can be reproduced.
+
+Times are in trips (one lockstep iteration of a wave) and say nothing about waves that share a SIMD speeding up when a partner leaves:
+the device shows less than the model (profiles/r07_a_wave_scheduling.md has both).
+
+usage: tools/sched_model.py [--pairs 1000000] [--seed 1] [--cus 256] [--threads 16]"""
+import argparse
+import heapq
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+EPA_BLOCK_CAP = 17   # EPA_FAST_CAP: a polytope that needs more iterations leaves k_epa_loop (hand-over)
+REFILL = 0.25        # trips per refill (reproduces HFCL_EPA_LOOP_REFILL_MIN 1 ~ 2, 3 = +4 %; profiles/r05_a)
+REFILL_MIN = 2
+
+
+def oracle_counts(n, seed, threads):
+    import __graft_entry__ as ge
+    import oracle_binding as ob
+    pkg = ge.load_pkg()
+    abi, wl = pkg.abi, pkg.workloads
+    ob.build()
+    b = wl.cfg3_convex_convex(n=n, seed=seed)
+    req = wl.make_request(b, abi)
+    ref = ob.distance_batch(b.shapes, b.verts, b.s1, b.s2, b.tf1, b.tf2, req, n_threads=threads)
+    s = ref["status"]
+    pen = abi.status_epa(s) != 15  # HFCL_EPA_DID_NOT_RUN
+    return abi.status_gjk_iters(s).astype(np.int64), abi.status_epa_iters(s)[pen].astype(np.int64)
+
+
+def greedy(durations, slots):
+    """Units placed in order on `slots` servers as they fall free: the time the last one ends, and the busy share of the slots."""
+    free = [0.0] * min(slots, len(durations))
+    heapq.heapify(free)
+    end = 0.0
+    for d in durations:
+        t = heapq.heappop(free) + d
+        end = max(end, t)
+        heapq.heappush(free, t)
+    return end, float(np.sum(durations)) / (slots * end) if end > 0 else 0.0
+
+
+def model_gjk(iters, cus, setup):
+    trips = iters + 1
+    pad = (-len(trips)) % 32
+    rounds = np.concatenate([trips, np.zeros(pad, dtype=trips.dtype)]).reshape(-1, 32).max(axis=1) + setup
+    wave_slots = cus * 8  # two waves per SIMD
+    # 256-thread blocks, grid = 16 per CU: wave w of block b owns the rounds (4 b + w) + k * (4 * grid)
+    grid = min(cus * 16, (len(rounds) + 3) // 4)
+    waves = np.zeros(grid * 4)
+    idx = np.arange(len(rounds)) % (grid * 4)
+    np.add.at(waves, idx, rounds)
+    blocks = waves.reshape(grid, 4).max(axis=1)
+    end_block, _ = greedy(blocks, wave_slots // 4)
+    held = float(blocks.sum() * 4) / wave_slots
+    used = float(rounds.sum()) / wave_slots
+    end_wave, _ = greedy(rounds, wave_slots)
+    return {"trips_per_pair": float(trips.mean()), "round_mean": float(rounds.mean() - setup), "round_sd": float(rounds.std()),
+            "rounds_per_wave": len(rounds) / (grid * 4.0), "held": held, "used": used, "end_256": end_block, "end_64": end_wave}
+
+
+def model_epa(lengths, grid, pool_share, k, min_refills, groups=8):
+    """Event-driven: every wave at its next refill, in time order.  pool_share = 0: the static form of the tree; > 0: the dropped pool."""
+    cnt = len(lengths)
+    L = np.minimum(lengths, EPA_BLOCK_CAP)
+    S = cnt
+    rng_len = 0
+    if pool_share > 0 and cnt >= grid * groups * min_refills:
+        S = int((cnt - int(cnt * pool_share)) // grid * grid)
+        rng_len = (cnt - S + k - 1) // k
+    counters = [0] * k
+    atomics = 0
+    ends = []
+    heap = [(0.0, w) for w in range(grid)]
+    state = {w: {"next": w, "at": w % k, "dry": set() if rng_len else set(range(k)), "live": []} for w in range(grid)}
+    while heap:
+        t, w = heapq.heappop(heap)
+        st = state[w]
+        want = groups - len(st["live"])
+        got = []
+        if st["next"] < S:
+            got = [b for b in range(st["next"], st["next"] + want * grid, grid) if b < S]
+            st["next"] += want * grid
+        elif len(st["dry"]) < k:
+            for j in range(k):
+                if counters[j] >= max(0, min(rng_len, cnt - S - j * rng_len)):
+                    st["dry"].add(j)
+            while len(st["dry"]) < k and not got:
+                j = next((st["at"] + s) % k for s in range(k) if (st["at"] + s) % k not in st["dry"])
+                ticket = counters[j]
+                counters[j] += want
+                atomics += 1
+                length = max(0, min(rng_len, cnt - S - j * rng_len))
+                left = length - ticket
+                if left <= want:
+                    st["dry"].add(j)
+                if left > 0:
+                    got = list(range(S + j * rng_len + ticket, S + j * rng_len + ticket + min(want, left)))
+                st["at"] = j
+        t += REFILL
+        st["live"] += [int(L[b]) for b in got]
+        more = st["next"] < S or len(st["dry"]) < k
+        if not st["live"]:
+            if more:
+                heapq.heappush(heap, (t, w))
+            else:
+                ends.append(t - REFILL)
+            continue
+        # trips until the refill condition holds again
+        live = sorted(st["live"])
+        if more:
+            idle_now = groups - len(live)
+            need = max(0, REFILL_MIN - idle_now)  # groups that have to end first
+            steps = live[need - 1] if need > 0 else live[0]
+            steps = max(steps, 1)
+        else:
+            steps = live[-1]
+        st["live"] = [x - steps for x in live if x - steps > 0]
+        if not more and not st["live"]:
+            ends.append(t + steps)
+            continue
+        heapq.heappush(heap, (t + steps, w))
+    ends = np.array(ends)
+    return {"S": S, "mean_end": float(ends.mean()), "last_end": float(ends.max()), "atomics": atomics}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pairs", type=int, default=1_000_000)
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--cus", type=int, default=256)
+    ap.add_argument("--threads", type=int, default=min(16, os.cpu_count() or 1))
+    a = ap.parse_args()
+    gjk_iters, epa_len = oracle_counts(a.pairs, a.seed, a.threads)
+    print("oracle: %d pairs, %.2f GJK iterations per pair, %d polytopes, %.2f EPA iterations each (%d past the block's %d)" % (
+        len(gjk_iters), gjk_iters.mean(), len(epa_len), epa_len.mean(), int((epa_len > EPA_BLOCK_CAP).sum()), EPA_BLOCK_CAP))
+    for setup in (2, 3, 4):
+        g = model_gjk(gjk_iters, a.cus, setup)
+        print("k_gjk_cvx<2,0>  set-up %d trips: round %.1f +- %.1f trips (%.1f per pair), %.2f rounds per wave; 256-thread blocks hold %.0f "
+              "wave-trips per slot for %.0f used and end at %.0f; single-wave workgroups end at %.0f (-%.1f %%)" % (
+                  setup, g["round_mean"], g["round_sd"], g["trips_per_pair"], g["rounds_per_wave"], g["held"], g["used"], g["end_256"],
+                  g["end_64"], 100 * (1 - g["end_64"] / g["end_256"])))
+    grid = a.cus * 12
+    base = model_epa(epa_len, grid, 0.0, 16, 2)
+    print("k_epa_loop  static: waves end at %.0f trips on average, the last at %.0f" % (base["mean_end"], base["last_end"]))
+    for share, k in ((0.1, 1), (0.1, 16), (0.1, 32), (0.2, 16), (0.05, 16)):
+        m = model_epa(epa_len, grid, share, k, 2)
+        print("k_epa_loop  pool = last %.0f %% (S = %d), %2d counters: mean %.0f, last %.0f (%+.1f %%), %d atomics (%.0f per counter)" % (
+            100 * share, m["S"], k, m["mean_end"], m["last_end"], 100 * (m["last_end"] / base["last_end"] - 1), m["atomics"], m["atomics"] / k))
+
+
+if __name__ == "__main__":
+    main()
