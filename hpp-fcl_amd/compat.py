@@ -674,8 +674,10 @@ def collide_pairs(pairs, request):
     return out
 
 
-def _scene_run(kind, objects, pair_indices, request, transforms):
-    """The pair list `pair_indices` ((n_pairs, 2) indices into `objects`) for every configuration: ONE scene call."""
+def _scene_run(kind, objects, pair_indices, request, transforms, broadphase=False, inflate=0.0):
+    """The pair list `pair_indices` ((n_pairs, 2) indices into `objects`) for every configuration: ONE scene call.  broadphase: the
+    list is culled per configuration on the device first (boxes grown by `inflate`); rec / g then hold the surviving queries only and
+    the last two items are their ids q = c * n_pairs + p and conf_begin (None without broadphase)."""
     ctx = _context()
     geoms = [o.collisionGeometry() for o in objects]
     ids = np.array([ctx.add(g) for g in geoms], dtype=np.uint32)
@@ -696,18 +698,23 @@ def _scene_run(kind, objects, pair_indices, request, transforms):
     lib = ctx.library()
     sc = lib.scene(ids, pr)
     try:
-        fn = sc.distance if kind == "distance" else sc.collide
-        rec, summ, g = fn(table, request._abi(), records=True, summary=True, want_guess=True)
+        ids = conf_begin = None
+        if broadphase:
+            fn = sc.distance_culled if kind == "distance" else sc.collide_culled
+            rec, ids, conf_begin, summ, g = fn(table, float(inflate), request._abi(), records=True, summary=True, want_guess=True)
+        else:
+            fn = sc.distance if kind == "distance" else sc.collide
+            rec, summ, g = fn(table, request._abi(), records=True, summary=True, want_guess=True)
     except engine.EngineError as e:
         if e.code in (abi.ERR_INVALID_ARGUMENT, abi.ERR_UNSUPPORTED_PAIR):
             raise ValueError(str(e))  # std::invalid_argument in the reference
         raise
     finally:
         sc.close()
-    return geoms, pr, len(table), rec, summ, g
+    return geoms, pr, len(table), rec, summ, g, ids, conf_begin
 
 
-def collide_scene(objects, pair_indices, request, transforms=None):
+def collide_scene(objects, pair_indices, request, transforms=None, broadphase=False, inflate=0.0):
     """collide() on the listed pairs of `objects` (CollisionObjects) through a scene: each object's pose goes to the device
     once per configuration, not once per pair.  transforms: None -- one configuration, the objects' own transforms --, an
     array (n_conf, n_objects, 12) of Transform3f images, or n_conf lists of Transform3f.  Returns (results, summaries):
@@ -715,28 +722,46 @@ def collide_scene(objects, pair_indices, request, transforms=None):
     transforms is None), summaries the abi.SCENE_SUMMARY_DTYPE record of every configuration (n_contacts > 0: what
     CollisionCallBackDefault's result.isCollision() says after manager.collide).  The results are Python objects, filled one by
     one: for lists of 10^5 pairs and more that loop costs far more than the device call -- take the summaries, or the records of
-    engine.Scene.collide, there."""
+    engine.Scene.collide, there.
+    broadphase=True: per configuration only the listed pairs whose world AABBs (each grown by `inflate` >= 0 on every side) overlap
+    are evaluated -- with inflate = 0 the pairs DynamicAABBTreeCollisionManager::collide passes to its callback; the test runs on the
+    device (engine.Scene.collide_culled).  results[c] is then a list of (p, CollisionResult) for the surviving pairs, p ascending, and
+    the summaries are folds over those (n_contacts and first_contact as without the broadphase)."""
     if request.num_max_contacts == 0:
         raise ValueError("Invalid number of max contacts (current value is 0).")
     if request.num_max_contacts > 1 and any(isinstance(o.collisionGeometry(), BVHModelOBBRSS) for o in objects):
         raise ValueError("collide_scene: contact lists of mesh pairs (num_max_contacts > 1) go through collide_pairs")
-    geoms, pr, n_conf, rec, summ, g = _scene_run("collide", objects, pair_indices, request, transforms)
+    geoms, pr, n_conf, rec, summ, g, ids, conf_begin = _scene_run("collide", objects, pair_indices, request, transforms, broadphase, inflate)
     out = []
     for c in range(n_conf):
         row = []
-        for p, (i, j) in enumerate(pr):
-            r = CollisionResult()
-            q = c * len(pr) + p
-            _fill_collision(r, geoms[i], geoms[j], request, rec[q], g[q], None, p)
-            row.append(r)
+        if broadphase:  # (p, result) of configuration c's surviving pairs
+            for k in range(int(conf_begin[c]), int(conf_begin[c + 1])):
+                p = int(ids[k]) - c * len(pr)
+                r = CollisionResult()
+                _fill_collision(r, geoms[pr[p][0]], geoms[pr[p][1]], request, rec[k], g[k], None, p)
+                row.append((p, r))
+        else:
+            for p, (i, j) in enumerate(pr):
+                r = CollisionResult()
+                q = c * len(pr) + p
+                _fill_collision(r, geoms[i], geoms[j], request, rec[q], g[q], None, p)
+                row.append(r)
         out.append(row)
     return (out[0] if transforms is None and out else out), summ
 
 
-def distance_scene(objects, pair_indices, request, transforms=None):
+def distance_scene(objects, pair_indices, request, transforms=None, broadphase=False, inflate=0.0):
     """distance() on the listed pairs of `objects`: (min_distance array (n_conf, n_pairs), records, summaries); the
-    summaries' min_distance is DistanceCallBackDefault's answer per configuration."""
-    geoms, pr, n_conf, rec, summ, g = _scene_run("distance", objects, pair_indices, request, transforms)
+    summaries' min_distance is DistanceCallBackDefault's answer per configuration.
+    broadphase=True: only the pairs whose world AABBs, each grown by `inflate`, overlap are evaluated (inflate = D / 2 keeps every pair
+    whose boxes are within D along each axis: a box-shaped filter, not the manager's traversal with its shrinking bound).  Returns
+    (distances, pair indices, summaries): per configuration the array of the surviving pairs' distances and the array of their p."""
+    geoms, pr, n_conf, rec, summ, g, ids, conf_begin = _scene_run("distance", objects, pair_indices, request, transforms, broadphase, inflate)
+    if broadphase:
+        cb = conf_begin.astype(np.int64)
+        return ([rec["distance"][cb[c]:cb[c + 1]] for c in range(n_conf)],
+                [ids[cb[c]:cb[c + 1]].astype(np.int64) - c * len(pr) for c in range(n_conf)], summ)
     return rec["distance"].reshape(n_conf, len(pr)), rec, summ
 
 

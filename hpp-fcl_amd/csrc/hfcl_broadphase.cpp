@@ -21,83 +21,14 @@
 #include <vector>
 
 #include "../../include/hppfcl_amd.h"
+#include "hfcl_cull.hpp"
 
 namespace {
 
-struct Box3 {
-  double lo[3], hi[3];
-};
+using hfcl::Box3;
+using hfcl::shape_local_box;  // hfcl_cull.hpp: shared with the device cull (hfcl_scene_cull*)
 
-inline bool boxes_touch(const double* a, const double* b) {  // AABB::overlap: closed intervals
-  return !(a[0] > b[3] || a[1] > b[4] || a[2] > b[5] || a[3] < b[0] || a[4] < b[1] || a[5] < b[2]);
-}
-
-Box3 shape_local_box(const hfcl_shape& s, const double* verts) {
-  Box3 b;
-  auto symmetric = [&b](double hx, double hy, double hz) {
-    const double h[3] = {hx, hy, hz};
-    for (int k = 0; k < 3; ++k) {
-      b.lo[k] = -h[k];
-      b.hi[k] = h[k];
-    }
-  };
-  switch (s.type) {
-    case HFCL_GEOM_HALFSPACE:
-    case HFCL_GEOM_PLANE: {
-      // computeBV<AABB, Halfspace|Plane> in the shape's own frame (geometric_shapes_utility.cpp:391-455): the volume
-      // is unbounded (+-DBL_MAX) except along a coordinate axis the normal is aligned with
-      const double big = std::numeric_limits<double>::max();
-      for (int k = 0; k < 3; ++k) {
-        b.lo[k] = -big;
-        b.hi[k] = big;
-      }
-      const double* n = s.params;
-      const int axis = (n[1] == 0.0 && n[2] == 0.0) ? 0 : (n[0] == 0.0 && n[2] == 0.0) ? 1 : (n[0] == 0.0 && n[1] == 0.0) ? 2 : -1;
-      if (axis >= 0 && n[axis] != 0.0) {
-        const double v = n[axis] < 0 ? -s.params[3] : s.params[3];
-        if (s.type == HFCL_GEOM_PLANE) b.lo[axis] = b.hi[axis] = v;
-        else if (n[axis] < 0) b.lo[axis] = v;
-        else b.hi[axis] = v;
-      }
-      break;
-    }
-    case HFCL_GEOM_BOX:
-    case HFCL_GEOM_ELLIPSOID: symmetric(s.params[0], s.params[1], s.params[2]); break;
-    case HFCL_GEOM_SPHERE: symmetric(s.params[0], s.params[0], s.params[0]); break;
-    case HFCL_GEOM_CAPSULE: symmetric(s.params[0], s.params[0], s.params[1] + s.params[0]); break;
-    case HFCL_GEOM_CONE:
-    case HFCL_GEOM_CYLINDER: symmetric(std::abs(s.params[0]), std::abs(s.params[0]), std::abs(s.params[1])); break;
-    default: {  // point sets: Convex, Triangle
-      const double big = std::numeric_limits<double>::max();
-      for (int k = 0; k < 3; ++k) {
-        b.lo[k] = big;
-        b.hi[k] = -big;
-      }
-      const double* p = verts + 3 * size_t(s.vertex_offset);
-      for (uint32_t i = 0; i < s.num_points; ++i, p += 3)
-        for (int k = 0; k < 3; ++k) {
-          b.lo[k] = std::min(b.lo[k], p[k]);
-          b.hi[k] = std::max(b.hi[k], p[k]);
-        }
-    }
-  }
-  if (s.swept_sphere_radius > 0)
-    for (int k = 0; k < 3; ++k) {
-      b.lo[k] -= s.swept_sphere_radius;
-      b.hi[k] += s.swept_sphere_radius;
-    }
-  return b;
-}
-
-inline bool rotation_is_identity(const double* R) {  // Eigen::isIdentity with its default precision
-  const double eps = 1e-12;
-  for (int c = 0; c < 3; ++c)
-    for (int r = 0; r < 3; ++r) {
-      const double x = R[3 * c + r];
-      if (r == c ? !(std::abs(x - 1.0) <= eps * std::min(std::abs(x), 1.0)) : !(std::abs(x) <= eps)) return false;
-    }
-  return true;
-}
+inline bool boxes_touch(const double* a, const double* b) { return hfcl::cull_boxes_touch(a, b); }  // AABB::overlap: closed intervals
 
 template <class F>
 void parallel_ranges(size_t n, int n_threads, F f) {
@@ -242,24 +173,8 @@ int hfcl_world_aabbs(const hfcl_shape* shapes, size_t n_shapes, const double* ve
       const double* R = object_tf + 12 * i;
       const double* T = R + 9;
       double* o = aabbs_out + 6 * i;
-      if (rotation_is_identity(R)) {
-        for (int k = 0; k < 3; ++k) {
-          o[k] = L.lo[k] + T[k];
-          o[3 + k] = L.hi[k] + T[k];
-        }
-        continue;
-      }
-      for (int k = 0; k < 3; ++k) {  // interval arithmetic on row k of R
-        double lo = 0, hi = 0;
-        for (int j = 0; j < 3; ++j) {
-          const double a = R[3 * j + k] * L.lo[j], c = R[3 * j + k] * L.hi[j];
-          const double mn = c < a ? c : a, mx = c > a ? c : a;
-          lo = j ? lo + mn : mn;
-          hi = j ? hi + mx : mx;
-        }
-        o[k] = T[k] + lo;
-        o[3 + k] = T[k] + hi;
-      }
+      const double Lb[6] = {L.lo[0], L.lo[1], L.lo[2], L.hi[0], L.hi[1], L.hi[2]};
+      hfcl::cull_world_box(R, T, Lb, o);  // (the arithmetic k_cull_aabbs runs on the device: hfcl_cull.hpp)
     }
   });
   return HFCL_OK;

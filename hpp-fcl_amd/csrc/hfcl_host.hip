@@ -44,6 +44,7 @@
 #include "hfcl_launch.hpp"
 #include "hfcl_patch.hpp"
 #include "hfcl_scene.hpp"
+#include "hfcl_cull.hpp"
 
 // =======================================================================================
 // Host side: library object + C ABI
@@ -247,7 +248,28 @@ struct hfcl_lib {
     uint32_t* h_counts = nullptr;   // pinned: COUNT_SLOTS x 2 * N_COUNTERS words of the host form (a chunk, its second half when it ran split);
                                     // chunk k uses slot k % COUNT_SLOTS once chunk k - COUNT_SLOTS has been added up (ev_counts: its kernels are done)
     hipEvent_t ev_counts[COUNT_SLOTS] = {};
+    // culling the pair list (hfcl_scene_cull*): world boxes of the configurations a chunk touches (host forms of hfcl_scene_world_aabbs: of
+    // the whole table), ballots / workgroup counts / offsets of a chunk, the running count, and the list of the host forms
+    double* d_boxes = nullptr;
+    size_t boxes_cap = 0;           // boxes (of 6 doubles)
+    uint64_t* d_words = nullptr;
+    size_t words_cap = 0;
+    uint32_t* d_block_counts = nullptr;
+    uint64_t* d_block_offsets = nullptr;
+    size_t blocks_cap = 0;
+    uint64_t* d_running = nullptr;  // [0]: the running count of a cull, [1]: n_listed of the host forms
+    uint64_t* d_ids = nullptr;      // host forms: the surviving queries
+    size_t ids_cap = 0;
+    uint64_t* d_conf_begin = nullptr;
+    size_t conf_begin_cap = 0;
   } scene;
+  // Queries per chunk of the cull (option scene_cull_chunk; 0: automatic -- at most 2^22 queries, 16384 workgroup counts for the one-workgroup scan)
+  size_t scene_cull_chunk = 0;
+  // local AABB of every library shape (hfcl_cull.hpp: shape_local_box; BVH models: the box of their vertices), 6 doubles each, rebuilt when
+  // shapes or meshes were registered since (hfcl_lib_set_shapes, hfcl_lib_add_bvh)
+  double* d_local_boxes = nullptr;
+  bool local_boxes_dirty = true;
+  std::vector<uint32_t> h_mesh_nverts;  // vertices of each registered BVH model
   // Queries per chunk of a scene call (option scene_chunk; 0: automatic -- at most 2^21 queries, the call cut into equal chunks).  The chunks of a
   // call run one after the other, and the solvers' kernels are chains of dependent steps that fill the chip only with a large batch: cfg5's
   // 1.07 M queries in chunks of 262144 (the host pipeline's steady chunk) took 5.9 ms against 2.4 ms for the per-pair call on resident arrays,
@@ -472,6 +494,7 @@ static bool upload_shapes(hfcl_lib* lib, const hfcl_shape* shapes, size_t n_shap
   lib->h_verts.assign(vertices, vertices + (vertices ? 3 * n_vertices : 0));
   lib->h_graphs.clear();  // shape ids / vertex ranges may have changed: adjacency is registered again by the caller
   lib->graph_dirty = true;
+  lib->local_boxes_dirty = true;
   std::vector<DShape<double>> s64(n_shapes);
   std::vector<DShape<float>> s32(n_shapes);
   std::vector<uint8_t> kinds(n_shapes);
@@ -559,7 +582,7 @@ static const char* const* option_keys() {
       "bvh_walk_rounds", "bvh_walk_order", "mesh_beside", "mesh_prio", "shape_walk", "shape_walk_sort", "shape_walk_budget", "shape_walk_min", "gjk_beside_max", "epa_direct_max", "bvh_walk_k", "bvh_walk_budget", "shape_dist_leaf_min", "shape_dist_starve", "bvhd_leaf_min", "bvhd_starve",
       "bvhd_part_min", "shape_dist_budget", "bvh_budget0_coop", "shape_budget0", "shape_budget", "shape_leaf_cost", "shape_levels",
       "climb_min", "bvh_budget", "bvh_budget0", "bvh_levels", "cvx_w", "epa_resume_slots", "bvh_task_slots", "bvh_force_wide",
-      "pipe_trace", "scene_chunk", nullptr};
+      "pipe_trace", "scene_chunk", "scene_cull_chunk", nullptr};
   return keys;
 }
 // "4,16,16": up to `cap` comma-separated unsigned values into out[first...]; returns how many were read
@@ -644,6 +667,10 @@ static int apply_option(hfcl_lib* lib, const std::string& key, const char* v) {
     if (i < 0 || i > 0xFFFFFFF0ll) return HFCL_ERR_INVALID_ARGUMENT;
     lib->scene_chunk = size_t(i);
   }
+  else if (key == "scene_cull_chunk") {
+    if (i < 0 || i > (1ll << 31)) return HFCL_ERR_INVALID_ARGUMENT;  // (one workgroup scans a chunk's counts: 2^23 of them at most)
+    lib->scene_cull_chunk = size_t(i);
+  }
   else return HFCL_ERR_INVALID_ARGUMENT;
   return HFCL_OK;
 }
@@ -722,7 +749,10 @@ void hfcl_lib_destroy(hfcl_lib* lib) {
     if (w.h_counts) hipHostFree(w.h_counts);
     for (hipEvent_t e : w.ev_counts)
       if (e) hipEventDestroy(e);
+    hipFree(w.d_boxes); hipFree(w.d_words); hipFree(w.d_block_counts); hipFree(w.d_block_offsets); hipFree(w.d_running); hipFree(w.d_ids);
+    hipFree(w.d_conf_begin);
   }
+  hipFree(lib->d_local_boxes);
   hipFree(lib->d_lists);
   hipFree(lib->d_epa_queue);
   hipFree(lib->d_epa_queue2);
@@ -904,6 +934,8 @@ int hfcl_lib_add_bvh(hfcl_lib* lib, const hfcl_bvh_node* nodes, size_t n_nodes, 
   lib->h_bvh_verts.insert(lib->h_bvh_verts.end(), vertices, vertices + 3 * n_vertices);
   lib->h_bvh_tris.insert(lib->h_bvh_tris.end(), triangles, triangles + 3 * n_tris);
   lib->h_meshes.push_back(m);
+  lib->h_mesh_nverts.push_back(uint32_t(n_vertices));
+  lib->local_boxes_dirty = true;
   {  // depth of the tree (the traversal stacks are sized from it) -- iterative: degenerate models are as deep as they are big
     std::vector<std::pair<uint32_t, uint32_t>> todo;
     todo.emplace_back(0u, 1u);
@@ -3473,16 +3505,403 @@ static int scene_device(const char* who, hfcl_scene* s, const void* d_table, siz
   return HFCL_OK;
 }
 
+
+// ---------------------------------------------------------------------------------------
+// Culling the pair list per configuration (hfcl_scene_cull*), and the scene calls on the list that is left (hfcl_scene_*_listed*,
+// hfcl_scene_*_culled).  hfcl_k_cull.hip has the kernels, hfcl_cull.hpp the arithmetic.
+// ---------------------------------------------------------------------------------------
+// the library's local boxes on the device, rebuilt when shapes or meshes were registered since
+static int ensure_local_boxes(hfcl_lib* lib) {
+  if (!lib->local_boxes_dirty && lib->d_local_boxes) return HFCL_OK;
+  const double nan = __builtin_nan("");
+  std::vector<double> boxes(6 * lib->n_shapes);
+  for (size_t i = 0; i < lib->n_shapes; ++i) {
+    const hfcl_shape& s = lib->h_shapes[i];
+    Box3 b;
+    if (s.type == HFCL_BV_OBBRSS) {
+      if (s.bvh_index < lib->h_meshes.size())
+        b = mesh_local_box(lib->h_bvh_verts.data() + 3 * size_t(lib->h_meshes[s.bvh_index].vert_off), lib->h_mesh_nverts[s.bvh_index]);
+      else  // (no such model: the narrow phase refuses the pair; a NaN box keeps it in the list)
+        for (int k = 0; k < 3; ++k) b.lo[k] = b.hi[k] = nan;
+    } else {
+      b = shape_local_box(s, lib->h_verts.data());
+    }
+    for (int k = 0; k < 3; ++k) {
+      boxes[6 * i + k] = b.lo[k];
+      boxes[6 * i + 3 + k] = b.hi[k];
+    }
+  }
+  hipFree(lib->d_local_boxes);  // (waits for the device: nothing in flight reads the old table)
+  lib->d_local_boxes = nullptr;
+  HIP_TRY(hipMalloc(&lib->d_local_boxes, std::max<size_t>(boxes.size(), 6) * sizeof(double)));
+  HIP_TRY(hipMemcpy(lib->d_local_boxes, boxes.data(), boxes.size() * sizeof(double), hipMemcpyHostToDevice));
+  lib->local_boxes_dirty = false;
+  return HFCL_OK;
+}
+
+// what the cull calls refuse before any work; total: n_conf * n_pairs (0: no query)
+template <typename T>
+static int cull_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, size_t& total) {
+  total = 0;
+  if (!s) {
+    set_error(std::string(who) + ": null scene");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (s->epoch != s->lib->shapes_epoch) {
+    set_error(std::string(who) + ": the library's shapes were replaced (hfcl_lib_set_shapes) after this scene was created; create a new scene");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (n_conf == 0 || s->n_objects == 0) return HFCL_OK;
+  if (!table) {
+    set_error(std::string(who) + ": null pose table");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if ((s->n_pairs && n_conf > ~size_t(0) / s->n_pairs) || n_conf > ~size_t(0) / (s->n_objects * SceneTypes<T>::WIDTH * sizeof(T))) {
+    set_error(std::string(who) + ": n_conf * n_pairs overflows");
+    return HFCL_ERR_LIMIT;
+  }
+  total = n_conf * s->n_pairs;
+  return HFCL_OK;
+}
+static int cull_check_inflate(const char* who, double inflate) {
+  if (!(inflate >= 0.0)) {
+    set_error(std::string(who) + ": inflate must be >= 0 (and not NaN)");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  return HFCL_OK;
+}
+static size_t cull_chunk_size(const hfcl_lib* lib, size_t total) {
+  if (lib->scene_cull_chunk) return std::min<size_t>(lib->scene_cull_chunk, total);
+  constexpr size_t AUTO = size_t(1) << 22;
+  const size_t n_chunks = (total + AUTO - 1) / AUTO;
+  return (total + n_chunks - 1) / n_chunks;
+}
+
+// world boxes of the whole table -> d_out (n_conf * n_objects * 6 doubles), on st
+template <typename T>
+static int scene_boxes_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, double* d_out, hipStream_t st) {
+  size_t total;
+  int rc = cull_validate<T>(who, s, d_table, n_conf, total);
+  if (rc || n_conf == 0 || s->n_objects == 0) return rc;
+  if (!d_out) {
+    set_error(std::string(who) + ": null output");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  hfcl_lib* lib = s->lib;
+  HIP_TRY(hipSetDevice(lib->device));
+  rc = ensure_local_boxes(lib);
+  if (rc) return rc;
+  launch_cull_aabbs(st, d_table, std::is_same<T, float>::value, s->d_object_shape, lib->d_local_boxes, s->n_objects, n_conf * s->n_objects, d_out);
+  HIP_TRY(hipGetLastError());
+  return HFCL_OK;
+}
+
+// The cull of the whole flat range on st: the list (ids below `capacity`), conf_begin, the count.  Nothing is read back.
+template <typename T>
+static int cull_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, double inflate, uint64_t* d_ids, size_t capacity,
+                       uint64_t* d_conf_begin, uint64_t* d_n_listed, hipStream_t st) {
+  size_t total;
+  int rc = cull_validate<T>(who, s, d_table, n_conf, total);
+  if (rc) return rc;
+  rc = cull_check_inflate(who, inflate);
+  if (rc) return rc;
+  if (!d_n_listed) {
+    set_error(std::string(who) + ": null count");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  hfcl_lib* lib = s->lib;
+  HIP_TRY(hipSetDevice(lib->device));
+  if (!total) {  // no query: an empty list
+    HIP_TRY(hipMemsetAsync(d_n_listed, 0, sizeof(uint64_t), st));
+    if (d_conf_begin) HIP_TRY(hipMemsetAsync(d_conf_begin, 0, (n_conf + 1) * sizeof(uint64_t), st));
+    return HFCL_OK;
+  }
+  rc = ensure_local_boxes(lib);
+  if (rc) return rc;
+  hfcl_lib::SceneWs& w = lib->scene;
+  const size_t chunk = cull_chunk_size(lib, total);
+  const size_t conf_per_chunk = std::min<size_t>(n_conf, chunk / s->n_pairs + 2);
+  const size_t n_blocks = (chunk + CULL_BLOCK - 1) / CULL_BLOCK;
+  rc = scene_grow(&w.d_boxes, w.boxes_cap, conf_per_chunk * s->n_objects, 6 * sizeof(double));
+  if (!rc) rc = scene_grow(&w.d_words, w.words_cap, n_blocks * CULL_WAVES, sizeof(uint64_t));
+  if (!rc && n_blocks > w.blocks_cap) {
+    hipFree(w.d_block_counts);
+    hipFree(w.d_block_offsets);
+    w.d_block_counts = nullptr;
+    w.d_block_offsets = nullptr;
+    w.blocks_cap = 0;
+    HIP_TRY(hipMalloc(&w.d_block_counts, n_blocks * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(&w.d_block_offsets, n_blocks * sizeof(uint64_t)));
+    w.blocks_cap = n_blocks;
+  }
+  if (!rc && !w.d_running) HIP_TRY(hipMalloc(&w.d_running, 2 * sizeof(uint64_t)));
+  if (rc) return rc;
+  constexpr bool f32 = std::is_same<T, float>::value;
+  CullArgs a;
+  a.pairs = s->d_pairs;
+  a.boxes = w.d_boxes;
+  a.n_objects = s->n_objects;
+  a.n_pairs = uint32_t(s->n_pairs);
+  a.total = total;
+  a.n_conf = n_conf;
+  a.inflate = inflate;
+  a.words = w.d_words;
+  a.block_counts = w.d_block_counts;
+  a.block_offsets = w.d_block_offsets;
+  a.running = w.d_running;
+  a.ids = d_ids;
+  a.capacity = d_ids ? capacity : 0;
+  a.conf_begin = d_conf_begin;
+  a.n_listed = d_n_listed;
+  for (size_t q0 = 0; q0 < total; q0 += chunk) {
+    const size_t m = std::min(chunk, total - q0);
+    a.q0 = q0;
+    scene_query(q0, a.n_pairs, a.c0, a.p0);
+    a.m = uint32_t(m);
+    a.first = q0 == 0 ? 1 : 0;
+    a.c_box0 = a.c0;
+    const uint64_t c_last = (q0 + m - 1) / s->n_pairs;
+    const char* rows = static_cast<const char*>(d_table) + a.c0 * s->n_objects * SceneTypes<T>::WIDTH * sizeof(T);
+    launch_cull_aabbs(st, rows, f32, s->d_object_shape, lib->d_local_boxes, s->n_objects, (c_last - a.c0 + 1) * s->n_objects, w.d_boxes);
+    launch_cull_chunk(st, a);
+  }
+  HIP_TRY(hipGetLastError());
+  return HFCL_OK;
+}
+
+// the host forms' stream
+static int scene_host_stream(hfcl_lib::SceneWs& w) {
+  if (!w.s_cmp) HIP_TRY(hipStreamCreateWithFlags(&w.s_cmp, hipStreamNonBlocking));
+  return HFCL_OK;
+}
+// the table of a host form onto the device (w.d_table), on w.s_cmp
+static int scene_table_in(hfcl_lib::SceneWs& w, const void* table, size_t bytes) {
+  char* t = static_cast<char*>(w.d_table);
+  const int rc = scene_grow(&t, w.table_bytes, bytes, 1);
+  w.d_table = t;
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(w.d_table, table, bytes, hipMemcpyHostToDevice, w.s_cmp));
+  return HFCL_OK;
+}
+// The cull of a table that is on the device into the library's own list (w.d_ids, w.d_conf_begin), and the one read-back: the count.
+// A list that outgrows the buffer is culled again into a larger one.
+template <typename T>
+static int cull_into_workspace(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, size_t total, double inflate, bool want_ids,
+                               uint64_t& n_listed) {
+  hfcl_lib* lib = s->lib;
+  hfcl_lib::SceneWs& w = lib->scene;
+  int rc = scene_grow(&w.d_conf_begin, w.conf_begin_cap, n_conf + 1, sizeof(uint64_t));
+  if (rc) return rc;
+  if (!w.d_running) HIP_TRY(hipMalloc(&w.d_running, 2 * sizeof(uint64_t)));
+  if (want_ids) {
+    rc = scene_grow(&w.d_ids, w.ids_cap, std::min<size_t>(total, std::max<size_t>(total / 8, 4096)), sizeof(uint64_t));
+    if (rc) return rc;
+  }
+  for (int pass = 0; pass < 2; ++pass) {
+    rc = cull_device<T>(who, s, d_table, n_conf, inflate, want_ids ? w.d_ids : nullptr, w.ids_cap, w.d_conf_begin, w.d_running + 1, w.s_cmp);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(&n_listed, w.d_running + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
+    HIP_TRY(hipStreamSynchronize(w.s_cmp));
+    if (!want_ids || n_listed <= w.ids_cap) break;
+    rc = scene_grow(&w.d_ids, w.ids_cap, size_t(n_listed), sizeof(uint64_t));
+    if (rc) return rc;
+  }
+  return HFCL_OK;
+}
+
+template <typename T>
+static int scene_cull_host(const char* who, hfcl_scene* s, const void* table, size_t n_conf, double inflate, uint64_t* query_ids, size_t capacity,
+                           uint64_t* conf_begin, size_t* n_listed) {
+  size_t total;
+  int rc = cull_validate<T>(who, s, table, n_conf, total);
+  if (!rc) rc = cull_check_inflate(who, inflate);
+  if (!rc && !n_listed) {
+    set_error(std::string(who) + ": null count");
+    rc = HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (rc) return rc;
+  *n_listed = 0;
+  if (!total) {
+    if (conf_begin) memset(conf_begin, 0, (n_conf + 1) * sizeof(uint64_t));
+    return HFCL_OK;
+  }
+  hfcl_lib* lib = s->lib;
+  hfcl_lib::SceneWs& w = lib->scene;
+  HIP_TRY(hipSetDevice(lib->device));
+  rc = scene_host_stream(w);
+  if (!rc) rc = scene_table_in(w, table, n_conf * s->n_objects * SceneTypes<T>::WIDTH * sizeof(T));
+  uint64_t n = 0;
+  if (!rc) rc = cull_into_workspace<T>(who, s, w.d_table, n_conf, total, inflate, query_ids != nullptr, n);
+  if (rc) {
+    hipStreamSynchronize(w.s_cmp);
+    return rc;
+  }
+  *n_listed = size_t(n);
+  if (query_ids && capacity < n) {
+    set_error(std::string(who) + ": " + std::to_string(n) + " queries survive, the list holds " + std::to_string(capacity));
+    return HFCL_ERR_LIMIT;
+  }
+  if (query_ids && n) HIP_TRY(hipMemcpyAsync(query_ids, w.d_ids, n * sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
+  if (conf_begin) HIP_TRY(hipMemcpyAsync(conf_begin, w.d_conf_begin, (n_conf + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
+  HIP_TRY(hipStreamSynchronize(w.s_cmp));
+  return HFCL_OK;
+}
+
+template <typename T>
+static int scene_boxes_host(const char* who, hfcl_scene* s, const void* table, size_t n_conf, double* aabbs_out) {
+  size_t total;
+  int rc = cull_validate<T>(who, s, table, n_conf, total);
+  if (rc || n_conf == 0 || s->n_objects == 0) return rc;
+  if (!aabbs_out) {
+    set_error(std::string(who) + ": null output");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  hfcl_lib* lib = s->lib;
+  hfcl_lib::SceneWs& w = lib->scene;
+  HIP_TRY(hipSetDevice(lib->device));
+  const size_t rows = n_conf * s->n_objects;
+  rc = scene_host_stream(w);
+  if (!rc) rc = scene_grow(&w.d_boxes, w.boxes_cap, rows, 6 * sizeof(double));
+  if (!rc) rc = scene_table_in(w, table, rows * SceneTypes<T>::WIDTH * sizeof(T));
+  if (!rc) rc = scene_boxes_device<T>(who, s, w.d_table, n_conf, w.d_boxes, w.s_cmp);
+  if (rc) {
+    hipStreamSynchronize(w.s_cmp);
+    return rc;
+  }
+  HIP_TRY(hipMemcpyAsync(aabbs_out, w.d_boxes, rows * 6 * sizeof(double), hipMemcpyDeviceToHost, w.s_cmp));
+  HIP_TRY(hipStreamSynchronize(w.s_cmp));
+  return HFCL_OK;
+}
+
+// fold partials a chunk of the list can need: a slot per piece of every configuration it can span -- any number of them, whatever its
+// length, since configurations without an entry lie in between (none when a pair list is one piece)
+static size_t scene_listed_pieces_bound(size_t n_pairs, size_t n_conf) {
+  const uint32_t shares = scene_shares(uint32_t(n_pairs));
+  return shares <= 1u ? 0 : n_conf * shares;
+}
+// expansion of the chunk [k0, k0 + m) of the list, the batch, the fold: all on st
+template <typename T>
+static int scene_listed_chunk_run(hfcl_scene* s, const void* d_table, size_t n_conf, const uint64_t* d_ids, const uint64_t* d_conf_begin, size_t k0,
+                                  size_t m, const hfcl_collision_request* creq, const hfcl_distance_request* dreq,
+                                  typename SceneTypes<T>::R* d_rec, hfcl_scene_summary* d_summary, const hfcl_guess* d_gin, hfcl_guess* d_gout,
+                                  hipStream_t st) {
+  hfcl_lib* lib = s->lib;
+  hfcl_lib::SceneWs& w = lib->scene;
+  constexpr bool f32 = std::is_same<T, float>::value;
+  const int max_blocks = lib->n_cus * 16;
+  SceneExpandArgs ea;
+  ea.pairs = s->d_pairs;
+  ea.object_shape = s->d_object_shape;
+  ea.object_tf = d_table;
+  ea.n_objects = s->n_objects;
+  ea.n_pairs = uint32_t(s->n_pairs);
+  ea.q0 = 0;
+  ea.c0 = 0;
+  ea.p0 = 0;
+  ea.m = uint32_t(m);
+  ea.s1 = w.d_s1;
+  ea.s2 = w.d_s2;
+  ea.tf1 = w.d_tf1;
+  ea.tf2 = w.d_tf2;
+  launch_scene_expand_listed(st, ea, d_ids + k0, f32, max_blocks);
+  const int rc = scene_batch(lib, w.d_s1, w.d_s2, w.d_tf1, w.d_tf2, m, creq, dreq, d_rec, d_gin, d_gout, st);
+  if (rc) return rc;
+  if (d_summary) {
+    SceneFoldListedArgs fa;
+    fa.rec = d_rec;
+    fa.ids = d_ids;
+    fa.conf_begin = d_conf_begin;
+    fa.k0 = k0;
+    fa.k1 = k0 + m;
+    fa.n_pairs = uint32_t(s->n_pairs);
+    fa.margin = creq ? creq->security_margin : 0.0;
+    fa.collide = creq ? 1 : 0;
+    fa.summary = d_summary;
+    fa.partials = scene_shares(fa.n_pairs) > 1u ? w.d_partials : nullptr;
+    fa.n_conf = n_conf;
+    launch_scene_fold_listed(st, fa, f32, max_blocks);
+  }
+  return HFCL_OK;
+}
+
+// The device form on a list.  The ids are not checked: ascending, below n_conf * n_pairs, conf_begin theirs -- as hfcl_scene_cull_device leaves them.
+template <typename T>
+static int scene_listed_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const uint64_t* d_ids, size_t n_listed,
+                               const uint64_t* d_conf_begin, const hfcl_collision_request* creq, const hfcl_distance_request* dreq,
+                               typename SceneTypes<T>::R* d_out, hfcl_scene_summary* d_summary, const hfcl_guess* d_gin, hfcl_guess* d_gout,
+                               hipStream_t st) {
+  size_t total;
+  int rc = scene_validate<T>(who, s, d_table, n_conf, creq, dreq, d_out, d_summary, total);
+  if (rc) return rc;
+  if (d_summary && !d_conf_begin) {
+    set_error(std::string(who) + ": summaries need conf_begin");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (n_listed > total) {
+    set_error(std::string(who) + ": more list entries than queries");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (n_listed && !d_ids) {
+    set_error(std::string(who) + ": null list");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  hfcl_lib* lib = s->lib;
+  HIP_TRY(hipSetDevice(lib->device));
+  if (d_summary) launch_scene_summary_init(st, d_summary, n_conf, lib->n_cus * 16);
+  if (!n_listed) {
+    HIP_TRY(hipGetLastError());
+    return HFCL_OK;
+  }
+  const size_t chunk = scene_chunk_size(lib, n_listed);
+  rc = scene_workspace(lib, chunk, d_out ? 0 : 1, false, 0, d_summary ? scene_listed_pieces_bound(s->n_pairs, n_conf) : 0);
+  if (rc) return rc;
+  for (size_t k0 = 0; k0 < n_listed; k0 += chunk) {
+    const size_t m = std::min(chunk, n_listed - k0);
+    auto* rec = d_out ? d_out + k0 : static_cast<typename SceneTypes<T>::R*>(lib->scene.d_rec[0]);
+    rc = scene_listed_chunk_run<T>(s, d_table, n_conf, d_ids, d_conf_begin, k0, m, creq, dreq, rec, d_summary, d_gin ? d_gin + k0 : nullptr,
+                                   d_gout ? d_gout + k0 : nullptr, st);
+    if (rc) {
+      scene_join_side(lib, st);
+      return rc;
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  return HFCL_OK;
+}
+
+// what the culled host forms (hfcl_scene_*_culled) add to scene_host
+struct SceneCull {
+  double inflate;
+  size_t out_capacity;
+  uint64_t* query_ids_out;   // nullptr or out_capacity
+  uint64_t* conf_begin_out;  // nullptr or n_conf + 1
+  size_t* n_listed;
+};
+
 // Host form.  The object table goes in once; chunk k computes on one stream while chunk k - 1's records leave on another from the other of
 // two record buffers (the copy is issued AFTER chunk k's launches: a copy into pageable memory holds its caller until the data has moved);
 // the summaries come back once at the end.  No feeder threads: nothing per pair goes in.
 template <typename T>
 static int scene_host(const char* who, hfcl_scene* s, const void* table, size_t n_conf, const hfcl_collision_request* creq,
                       const hfcl_distance_request* dreq, typename SceneTypes<T>::R* out, hfcl_scene_summary* summary, const hfcl_guess* gin,
-                      hfcl_guess* gout) {
+                      hfcl_guess* gout, const SceneCull* cull = nullptr) {
   using R = typename SceneTypes<T>::R;
   size_t total;
   int rc = scene_validate<T>(who, s, table, n_conf, creq, dreq, out, summary, total);
+  if (!rc && cull) {
+    rc = cull_check_inflate(who, cull->inflate);
+    if (!rc && !cull->n_listed) {
+      set_error(std::string(who) + ": null count");
+      rc = HFCL_ERR_INVALID_ARGUMENT;
+    }
+    if (!rc) *cull->n_listed = 0;
+  }
+  auto nothing_listed = [&]() {  // no surviving query: an empty list, the summaries of configurations without records
+    if (cull->conf_begin_out) memset(cull->conf_begin_out, 0, (n_conf + 1) * sizeof(uint64_t));
+    for (size_t c = 0; summary && c < n_conf; ++c) scene_summary_init(summary[c]);
+    return HFCL_OK;
+  };
+  if (!rc && !total && cull) return nothing_listed();
   if (rc || !total) return rc;
   hfcl_lib* lib = s->lib;
   hfcl_lib::SceneWs& w = lib->scene;
@@ -3493,13 +3912,34 @@ static int scene_host(const char* who, hfcl_scene* s, const void* table, size_t 
     if (!w.ev_done[k]) HIP_TRY(hipEventCreateWithFlags(&w.ev_done[k], hipEventDisableTiming));
     if (!w.ev_copied[k]) HIP_TRY(hipEventCreateWithFlags(&w.ev_copied[k], hipEventDisableTiming));
   }
-  const size_t chunk = scene_chunk_size(lib, total);
-  const size_t n_chunks = (total + chunk - 1) / chunk;
-  const bool back = out != nullptr || gout != nullptr;  // something per pair goes back: two buffers, the copy stream
-  rc = scene_workspace(lib, chunk, out ? 2 : 1, gin != nullptr, gout ? 2 : 0, summary ? scene_pieces_bound(s->n_pairs, chunk) : 0);
-  if (rc) return rc;
   const size_t table_bytes = n_conf * s->n_objects * SceneTypes<T>::WIDTH * sizeof(T);
-  {
+  size_t work = total;  // records of the call: every query, or (culled form) the surviving ones
+  if (cull) {  // the table goes in, the cull runs, the count comes back: 8 bytes, the one read-back before the narrow phase
+    rc = scene_table_in(w, table, table_bytes);
+    uint64_t n = 0;
+    if (!rc) rc = cull_into_workspace<T>(who, s, w.d_table, n_conf, total, cull->inflate, true, n);
+    if (rc) {
+      hipStreamSynchronize(w.s_cmp);
+      return rc;
+    }
+    *cull->n_listed = size_t(n);
+    if ((out || gout || cull->query_ids_out) && cull->out_capacity < n) {
+      set_error(std::string(who) + ": " + std::to_string(n) + " queries survive, the outputs hold " + std::to_string(cull->out_capacity));
+      return HFCL_ERR_LIMIT;
+    }
+    if (!n) return nothing_listed();
+    if (cull->query_ids_out) HIP_TRY(hipMemcpyAsync(cull->query_ids_out, w.d_ids, n * sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
+    if (cull->conf_begin_out)
+      HIP_TRY(hipMemcpyAsync(cull->conf_begin_out, w.d_conf_begin, (n_conf + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
+    work = size_t(n);
+  }
+  const size_t chunk = scene_chunk_size(lib, work);
+  const size_t n_chunks = (work + chunk - 1) / chunk;
+  const bool back = out != nullptr || gout != nullptr;  // something per pair goes back: two buffers, the copy stream
+  rc = scene_workspace(lib, chunk, out ? 2 : 1, gin != nullptr, gout ? 2 : 0,
+                       !summary ? 0 : cull ? scene_listed_pieces_bound(s->n_pairs, n_conf) : scene_pieces_bound(s->n_pairs, chunk));
+  if (rc) return rc;
+  if (!cull) {
     char* t = static_cast<char*>(w.d_table);
     rc = scene_grow(&t, w.table_bytes, table_bytes, 1);
     w.d_table = t;
@@ -3543,7 +3983,7 @@ static int scene_host(const char* who, hfcl_scene* s, const void* table, size_t 
   } while (0)
   auto copy_back = [&](size_t k) -> hipError_t {  // chunk k's records (and guesses) to the caller's arrays, behind its kernels
     const int b = int(k & 1);
-    const size_t q0 = k * chunk, m = std::min(chunk, total - q0);
+    const size_t q0 = k * chunk, m = std::min(chunk, work - q0);
     hipError_t e = hipStreamWaitEvent(w.s_copy, w.ev_done[b], 0);
     if (e == hipSuccess && out) e = hipMemcpyAsync(out + q0, w.d_rec[b], m * sizeof(R), hipMemcpyDeviceToHost, w.s_copy);
     if (e == hipSuccess && gout) e = hipMemcpyAsync(gout + q0, w.d_gout[b], m * sizeof(hfcl_guess), hipMemcpyDeviceToHost, w.s_copy);
@@ -3551,10 +3991,11 @@ static int scene_host(const char* who, hfcl_scene* s, const void* table, size_t 
     return e;
   };
 
-  SCENE_TRY(hipMemcpyAsync(w.d_table, table, table_bytes, hipMemcpyHostToDevice, w.s_cmp));
+  if (!cull) SCENE_TRY(hipMemcpyAsync(w.d_table, table, table_bytes, hipMemcpyHostToDevice, w.s_cmp));
+  if (cull && summary) launch_scene_summary_init(w.s_cmp, w.d_summary, n_conf, lib->n_cus * 16);
   for (size_t k = 0; k < n_chunks; ++k) {
     const int b = back ? int(k & 1) : 0;
-    const size_t q0 = k * chunk, m = std::min(chunk, total - q0);
+    const size_t q0 = k * chunk, m = std::min(chunk, work - q0);
     if (back && k >= 2) SCENE_TRY(hipStreamWaitEvent(w.s_cmp, w.ev_copied[b], 0));  // chunk k - 2 has left the buffers
     if (gin) SCENE_TRY(hipMemcpyAsync(w.d_gin, gin + q0, m * sizeof(hfcl_guess), hipMemcpyHostToDevice, w.s_cmp));
     const int slot = int(k % CS);
@@ -3568,8 +4009,10 @@ static int scene_host(const char* who, hfcl_scene* s, const void* table, size_t 
       if (rc) return finish(rc);
       lib->helper->counts_dst = lib->counts_dst + N_COUNTERS;
     }
-    rc = scene_chunk_run<T>(s, w.d_table, q0, m, creq, dreq, static_cast<R*>(w.d_rec[out ? b : 0]), summary ? w.d_summary : nullptr,
-                            gin ? w.d_gin : nullptr, gout ? w.d_gout[b] : nullptr, w.s_cmp);
+    rc = cull ? scene_listed_chunk_run<T>(s, w.d_table, n_conf, w.d_ids, w.d_conf_begin, q0, m, creq, dreq, static_cast<R*>(w.d_rec[out ? b : 0]),
+                                          summary ? w.d_summary : nullptr, gin ? w.d_gin : nullptr, gout ? w.d_gout[b] : nullptr, w.s_cmp)
+              : scene_chunk_run<T>(s, w.d_table, q0, m, creq, dreq, static_cast<R*>(w.d_rec[out ? b : 0]), summary ? w.d_summary : nullptr,
+                                   gin ? w.d_gin : nullptr, gout ? w.d_gout[b] : nullptr, w.s_cmp);
     if (rc) return finish(rc);
     slot_split[slot] = lib->last_split;
     SCENE_TRY(hipEventRecord(w.ev_counts[slot], w.s_cmp));
@@ -3709,5 +4152,95 @@ int hfcl_scene_distance_device_f32(hfcl_scene* s, const float* d_object_pose, si
   return scene_device<float>("hfcl_scene_distance_device_f32", s, d_object_pose, n_conf, nullptr, req, d_out, d_summary, nullptr, nullptr,
                              (hipStream_t)stream);
 }
+
+// ---- culling the pair list per configuration ---------------------------------------------------------------------------------------
+int hfcl_scene_world_aabbs(hfcl_scene* s, const double* object_tf, size_t n_conf, double* aabbs_out) {
+  return scene_boxes_host<double>("hfcl_scene_world_aabbs", s, object_tf, n_conf, aabbs_out);
+}
+int hfcl_scene_world_aabbs_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, double* aabbs_out) {
+  return scene_boxes_host<float>("hfcl_scene_world_aabbs_f32", s, object_pose, n_conf, aabbs_out);
+}
+int hfcl_scene_world_aabbs_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, double* d_aabbs_out, void* stream) {
+  return scene_boxes_device<double>("hfcl_scene_world_aabbs_device", s, d_object_tf, n_conf, d_aabbs_out, (hipStream_t)stream);
+}
+int hfcl_scene_world_aabbs_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, double* d_aabbs_out, void* stream) {
+  return scene_boxes_device<float>("hfcl_scene_world_aabbs_device_f32", s, d_object_pose, n_conf, d_aabbs_out, (hipStream_t)stream);
+}
+int hfcl_scene_cull(hfcl_scene* s, const double* object_tf, size_t n_conf, double inflate, uint64_t* query_ids, size_t capacity,
+                    uint64_t* conf_begin, size_t* n_listed) {
+  return scene_cull_host<double>("hfcl_scene_cull", s, object_tf, n_conf, inflate, query_ids, capacity, conf_begin, n_listed);
+}
+int hfcl_scene_cull_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, double inflate, uint64_t* query_ids, size_t capacity,
+                        uint64_t* conf_begin, size_t* n_listed) {
+  return scene_cull_host<float>("hfcl_scene_cull_f32", s, object_pose, n_conf, inflate, query_ids, capacity, conf_begin, n_listed);
+}
+int hfcl_scene_cull_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, double inflate, uint64_t* d_query_ids, size_t capacity,
+                           uint64_t* d_conf_begin, uint64_t* d_n_listed, void* stream) {
+  return cull_device<double>("hfcl_scene_cull_device", s, d_object_tf, n_conf, inflate, d_query_ids, capacity, d_conf_begin, d_n_listed,
+                             (hipStream_t)stream);
+}
+int hfcl_scene_cull_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, double inflate, uint64_t* d_query_ids, size_t capacity,
+                               uint64_t* d_conf_begin, uint64_t* d_n_listed, void* stream) {
+  return cull_device<float>("hfcl_scene_cull_device_f32", s, d_object_pose, n_conf, inflate, d_query_ids, capacity, d_conf_begin, d_n_listed,
+                            (hipStream_t)stream);
+}
+#define HFCL_NEED_DREQ()                        \
+  if (s && !req) {                              \
+    set_error("null request");                  \
+    return HFCL_ERR_INVALID_ARGUMENT;           \
+  }
+int hfcl_scene_collide_listed_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const uint64_t* d_query_ids, size_t n_listed,
+                                     const uint64_t* d_conf_begin, const hfcl_collision_request* req, hfcl_result* d_out,
+                                     hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in, hfcl_guess* d_guess_out, void* stream) {
+  return scene_listed_device<double>("hfcl_scene_collide_listed_device", s, d_object_tf, n_conf, d_query_ids, n_listed, d_conf_begin, req, nullptr,
+                                     d_out, d_summary, d_guess_in, d_guess_out, (hipStream_t)stream);
+}
+int hfcl_scene_distance_listed_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const uint64_t* d_query_ids, size_t n_listed,
+                                      const uint64_t* d_conf_begin, const hfcl_distance_request* req, hfcl_result* d_out,
+                                      hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in, hfcl_guess* d_guess_out, void* stream) {
+  HFCL_NEED_DREQ()
+  return scene_listed_device<double>("hfcl_scene_distance_listed_device", s, d_object_tf, n_conf, d_query_ids, n_listed, d_conf_begin, nullptr, req,
+                                     d_out, d_summary, d_guess_in, d_guess_out, (hipStream_t)stream);
+}
+int hfcl_scene_collide_listed_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, const uint64_t* d_query_ids, size_t n_listed,
+                                         const uint64_t* d_conf_begin, const hfcl_collision_request* req, hfcl_result_f32* d_out,
+                                         hfcl_scene_summary* d_summary, void* stream) {
+  return scene_listed_device<float>("hfcl_scene_collide_listed_device_f32", s, d_object_pose, n_conf, d_query_ids, n_listed, d_conf_begin, req,
+                                    nullptr, d_out, d_summary, nullptr, nullptr, (hipStream_t)stream);
+}
+int hfcl_scene_distance_listed_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, const uint64_t* d_query_ids, size_t n_listed,
+                                          const uint64_t* d_conf_begin, const hfcl_distance_request* req, hfcl_result_f32* d_out,
+                                          hfcl_scene_summary* d_summary, void* stream) {
+  HFCL_NEED_DREQ()
+  return scene_listed_device<float>("hfcl_scene_distance_listed_device_f32", s, d_object_pose, n_conf, d_query_ids, n_listed, d_conf_begin, nullptr,
+                                    req, d_out, d_summary, nullptr, nullptr, (hipStream_t)stream);
+}
+int hfcl_scene_collide_culled(hfcl_scene* s, const double* object_tf, size_t n_conf, double inflate, const hfcl_collision_request* req,
+                              hfcl_result* out, size_t out_capacity, uint64_t* query_ids_out, uint64_t* conf_begin_out,
+                              hfcl_scene_summary* summary, const hfcl_guess* guess_in, hfcl_guess* guess_out, size_t* n_listed) {
+  const SceneCull cull{inflate, out_capacity, query_ids_out, conf_begin_out, n_listed};
+  return scene_host<double>("hfcl_scene_collide_culled", s, object_tf, n_conf, req, nullptr, out, summary, guess_in, guess_out, &cull);
+}
+int hfcl_scene_distance_culled(hfcl_scene* s, const double* object_tf, size_t n_conf, double inflate, const hfcl_distance_request* req,
+                               hfcl_result* out, size_t out_capacity, uint64_t* query_ids_out, uint64_t* conf_begin_out,
+                               hfcl_scene_summary* summary, const hfcl_guess* guess_in, hfcl_guess* guess_out, size_t* n_listed) {
+  HFCL_NEED_DREQ()
+  const SceneCull cull{inflate, out_capacity, query_ids_out, conf_begin_out, n_listed};
+  return scene_host<double>("hfcl_scene_distance_culled", s, object_tf, n_conf, nullptr, req, out, summary, guess_in, guess_out, &cull);
+}
+int hfcl_scene_collide_culled_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, double inflate, const hfcl_collision_request* req,
+                                  hfcl_result_f32* out, size_t out_capacity, uint64_t* query_ids_out, uint64_t* conf_begin_out,
+                                  hfcl_scene_summary* summary, size_t* n_listed) {
+  const SceneCull cull{inflate, out_capacity, query_ids_out, conf_begin_out, n_listed};
+  return scene_host<float>("hfcl_scene_collide_culled_f32", s, object_pose, n_conf, req, nullptr, out, summary, nullptr, nullptr, &cull);
+}
+int hfcl_scene_distance_culled_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, double inflate, const hfcl_distance_request* req,
+                                   hfcl_result_f32* out, size_t out_capacity, uint64_t* query_ids_out, uint64_t* conf_begin_out,
+                                   hfcl_scene_summary* summary, size_t* n_listed) {
+  HFCL_NEED_DREQ()
+  const SceneCull cull{inflate, out_capacity, query_ids_out, conf_begin_out, n_listed};
+  return scene_host<float>("hfcl_scene_distance_culled_f32", s, object_pose, n_conf, nullptr, req, out, summary, nullptr, nullptr, &cull);
+}
+#undef HFCL_NEED_DREQ
 
 }  // extern "C"

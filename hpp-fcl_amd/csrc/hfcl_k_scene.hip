@@ -79,18 +79,6 @@ void launch_scene_expand(hipStream_t st, const SceneExpandArgs& a, bool f32, int
     hipLaunchKernelGGL(k_scene_expand64<false>, dim3(grid), dim3(256), 0, st, a);
 }
 
-// the wave's lanes' partial summaries -> the same summary in every lane
-static __device__ __forceinline__ void scene_wave_reduce(hfcl_scene_summary& s) {
-  for (int off = 32; off > 0; off >>= 1) {
-    hfcl_scene_summary o;
-    o.min_distance = __shfl_xor(s.min_distance, off, 64);
-    o.min_pair = __shfl_xor(s.min_pair, off, 64);
-    o.first_contact = __shfl_xor(s.first_contact, off, 64);
-    o.n_contacts = __shfl_xor(s.n_contacts, off, 64);
-    o.n_skipped = __shfl_xor(s.n_skipped, off, 64);
-    scene_fold_merge(s, o);
-  }
-}
 // lane 0: the chunk's part of configuration c into its summary
 static __device__ __forceinline__ void scene_store(const SceneFoldArgs& a, uint64_t c, const hfcl_scene_summary& part) {
   hfcl_scene_summary s = part;

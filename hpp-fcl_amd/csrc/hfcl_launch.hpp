@@ -144,3 +144,51 @@ struct SceneFoldArgs {
 };
 // ... -> the summaries of the configurations it touches (one launch, or two when a pair list has several pieces)
 void launch_scene_fold(hipStream_t st, const SceneFoldArgs& a, bool f32, int max_blocks);
+
+// hfcl_k_cull.hip: culling a scene's pair list per configuration (hfcl_scene_cull*) and the scene calls on the list that is left
+// (hfcl_scene_*_listed*).  World boxes of n_rows = configurations x objects pose rows (row r: object r % n_objects), 48 B each
+void launch_cull_aabbs(hipStream_t st, const void* object_tf, bool f32, const uint32_t* object_shape, const double* local_boxes,
+                       uint64_t n_objects, uint64_t n_rows, double* boxes);
+// A chunk [q0, q0 + m) of the flat query range: mark (a lane per query: a ballot per wave, a count per workgroup), scan (the counts, on
+// top of the survivors of the chunks before: *running), emit (the surviving q at their ranks, conf_begin of the configurations that start in
+// the chunk).  Three ordered launches; no kernel waits for another workgroup.
+struct CullArgs {
+  const uint32_t* pairs;     // 2 x n_pairs object indices
+  const double* boxes;       // world boxes of the configurations [c_box0, ...) the chunk touches
+  uint64_t c_box0;
+  uint64_t n_objects;
+  uint32_t n_pairs;
+  uint64_t q0;
+  uint64_t c0;               // (c0, p0) = scene_query(q0)
+  uint32_t p0;
+  uint32_t m;
+  uint64_t total;            // n_conf * n_pairs: the chunk that holds the last query writes conf_begin[n_conf] and *n_listed
+  uint64_t n_conf;
+  double inflate;
+  uint64_t* words;           // ceil(m / 64) ballots
+  uint32_t* block_counts;    // ceil(m / CULL_BLOCK)
+  uint64_t* block_offsets;   // ... survivors before the workgroup, over all chunks
+  uint64_t* running;         // survivors of the chunks before this one (first: taken as 0), then of this one too
+  int first;
+  uint64_t* ids;             // nullptr / capacity 0: count only
+  uint64_t capacity;
+  uint64_t* conf_begin;      // nullptr or n_conf + 1
+  uint64_t* n_listed;        // nullptr or one word
+};
+void launch_cull_chunk(hipStream_t st, const CullArgs& a);
+// the expansion of a chunk of the list: a.m queries, query of row r = ids[r]; a.q0 / c0 / p0 unused
+void launch_scene_expand_listed(hipStream_t st, const SceneExpandArgs& a, const uint64_t* ids, bool f32, int max_blocks);
+void launch_scene_summary_init(hipStream_t st, hfcl_scene_summary* summary, uint64_t n_conf, int max_blocks);
+struct SceneFoldListedArgs {
+  const void* rec;               // the chunk's records: rec[0] is list entry k0's
+  const uint64_t* ids;           // the whole list
+  const uint64_t* conf_begin;
+  uint64_t k0, k1;
+  uint32_t n_pairs;
+  double margin;
+  int collide;
+  hfcl_scene_summary* summary;   // by configuration, initialised (launch_scene_summary_init) before the first chunk
+  hfcl_scene_summary* partials;  // nullptr (pair lists of one piece) or n_conf * scene_shares(n_pairs) slots
+  uint64_t n_conf;               // configurations of the call: the bound on those a chunk spans (it may span empty ones: not bounded by k1 - k0)
+};
+void launch_scene_fold_listed(hipStream_t st, const SceneFoldListedArgs& a, bool f32, int max_blocks);

@@ -102,4 +102,19 @@ HFCL_HD void scene_fold_merge(hfcl_scene_summary& a, const hfcl_scene_summary& b
   a.n_skipped += b.n_skipped;
 }
 
+#if defined(__HIPCC__)
+// the wave's lanes' partial summaries -> the same summary in every lane
+HFCL_D void scene_wave_reduce(hfcl_scene_summary& s) {
+  for (int off = 32; off > 0; off >>= 1) {
+    hfcl_scene_summary o;
+    o.min_distance = __shfl_xor(s.min_distance, off, 64);
+    o.min_pair = __shfl_xor(s.min_pair, off, 64);
+    o.first_contact = __shfl_xor(s.first_contact, off, 64);
+    o.n_contacts = __shfl_xor(s.n_contacts, off, 64);
+    o.n_skipped = __shfl_xor(s.n_skipped, off, 64);
+    scene_fold_merge(s, o);
+  }
+}
+#endif
+
 }  // namespace hfcl

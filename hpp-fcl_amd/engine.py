@@ -34,6 +34,14 @@ EXPORTED_SYMBOLS = [
     "hfcl_scene_collide", "hfcl_scene_distance", "hfcl_scene_collide_device", "hfcl_scene_distance_device",
     "hfcl_scene_collide_f32", "hfcl_scene_distance_f32", "hfcl_scene_collide_device_f32", "hfcl_scene_distance_device_f32",
 ]
+# include/hppfcl_amd_cull.h (included by hppfcl_amd.h): the pair list culled per configuration on the device
+CULL_SYMBOLS = [
+    "hfcl_scene_world_aabbs", "hfcl_scene_world_aabbs_f32", "hfcl_scene_world_aabbs_device", "hfcl_scene_world_aabbs_device_f32",
+    "hfcl_scene_cull", "hfcl_scene_cull_f32", "hfcl_scene_cull_device", "hfcl_scene_cull_device_f32",
+    "hfcl_scene_collide_listed_device", "hfcl_scene_distance_listed_device", "hfcl_scene_collide_listed_device_f32",
+    "hfcl_scene_distance_listed_device_f32", "hfcl_scene_collide_culled", "hfcl_scene_distance_culled", "hfcl_scene_collide_culled_f32",
+    "hfcl_scene_distance_culled_f32",
+]
 
 
 class EngineError(RuntimeError):
@@ -554,6 +562,126 @@ class Scene:
     def distance_device_f32(self, d_object_pose, n_conf, req, d_out=None, d_summary=None, stream=0):
         _check(dll().hfcl_scene_distance_device_f32(self._h, _dptr(d_object_pose), C.c_size_t(int(n_conf)), C.byref(req), _dptr(d_out),
                                                     _dptr(d_summary), C.c_void_p(stream)))
+
+    # ---- the pair list culled per configuration on the device (include/hppfcl_amd_cull.h) ----
+    def _any_table(self, object_tf):
+        """The pose table and whether it is the fp32 form: by dtype (float32) or by its last dimension (7)."""
+        a = np.asarray(object_tf)
+        f32 = a.dtype == np.float32 or (a.ndim >= 2 and a.shape[-1] == 7)
+        return self._table(a, np.float32 if f32 else np.float64, 7 if f32 else 12), f32
+
+    def world_aabbs(self, object_tf):
+        """hfcl_scene_world_aabbs{,_f32}: (n_conf, n_objects, 6) world boxes (min xyz, max xyz), computed on the device."""
+        tf, f32 = self._any_table(object_tf)
+        out = np.zeros((len(tf), self.n_objects, 6), dtype=np.float64)
+        fn = dll().hfcl_scene_world_aabbs_f32 if f32 else dll().hfcl_scene_world_aabbs
+        _check(fn(self._h, abi.ptr(tf), C.c_size_t(len(tf)), abi.ptr(out)))
+        return out
+
+    def cull(self, object_tf, inflate=0.0):
+        """hfcl_scene_cull{,_f32}: (query_ids uint64 ascending, conf_begin uint64[n_conf + 1]) of the queries q = c * n_pairs + p whose two
+        world boxes, each grown by `inflate`, touch."""
+        tf, f32 = self._any_table(object_tf)
+        fn = dll().hfcl_scene_cull_f32 if f32 else dll().hfcl_scene_cull
+        n = C.c_size_t(0)
+        conf_begin = np.zeros(len(tf) + 1, dtype=np.uint64)
+        capacity = self._list_guess(len(tf))
+        while True:  # (at most twice: a list longer than the guess is refused with its length, and the call repeated with that)
+            ids = np.zeros(capacity, dtype=np.uint64)
+            rc = fn(self._h, abi.ptr(tf), C.c_size_t(len(tf)), C.c_double(inflate), abi.ptr(ids), C.c_size_t(capacity), abi.ptr(conf_begin),
+                    C.byref(n))
+            if rc != abi.ERR_LIMIT or n.value <= capacity:
+                break
+            capacity = n.value
+        _check(rc)
+        return ids[:n.value], conf_begin
+
+    def _list_guess(self, n_conf):
+        """Size of the outputs of a culled call when the caller names none: an eighth of the queries (at least 1024, at most all)."""
+        total = n_conf * self.n_pairs
+        return min(total, max(total // 8, 1024))
+
+    def _culled(self, kind, object_tf, inflate, req, records, summary, guess_in, want_guess, capacity, want_ids):
+        tf, f32 = self._any_table(object_tf)
+        d = dll()
+        n_conf = len(tf)
+        fn = getattr(d, "hfcl_scene_%s_culled%s" % (kind, "_f32" if f32 else ""))
+        if not (records or want_ids or want_guess):
+            capacity = 0  # (summaries only: nothing is sized by the list)
+        # no capacity named: a guess; a list that outgrows it is refused after the cull, before any narrow-phase work, with its length,
+        # and the call is made once more with that
+        retry = capacity is None
+        if retry:
+            capacity = self._list_guess(n_conf)
+        out = np.zeros(capacity, dtype=abi.RESULT_F32_DTYPE if f32 else abi.RESULT_DTYPE) if records else None
+        ids = np.zeros(capacity, dtype=np.uint64) if records or want_ids or want_guess else None
+        conf_begin = np.zeros(n_conf + 1, dtype=np.uint64)
+        summ = np.zeros(n_conf, dtype=abi.SCENE_SUMMARY_DTYPE) if summary else None
+        n = C.c_size_t(0)
+        args = [self._h, abi.ptr(tf), C.c_size_t(n_conf), C.c_double(inflate), C.byref(req), abi.ptr(out), C.c_size_t(capacity), abi.ptr(ids),
+                abi.ptr(conf_begin), abi.ptr(summ)]
+        gout = None
+        if not f32:
+            if guess_in is not None:
+                guess_in = np.ascontiguousarray(guess_in, dtype=abi.GUESS_DTYPE)
+            gout = np.zeros(capacity, dtype=abi.GUESS_DTYPE) if want_guess else None
+            args += [abi.ptr(guess_in), abi.ptr(gout)]
+        rc = fn(*args, C.byref(n))
+        if rc == abi.ERR_LIMIT and retry and n.value > capacity:
+            return self._culled(kind, tf, inflate, req, records, summary, guess_in, want_guess, n.value, want_ids)
+        _check(rc)
+        k = n.value
+        res = (out[:k] if records else None, ids[:k] if ids is not None else None, conf_begin, summ)
+        return res + (gout[:k],) if want_guess and not f32 else res
+
+    def collide_culled(self, object_tf, inflate=0.0, req=None, records=True, summary=True, guess_in=None, want_guess=False, capacity=None,
+                       want_ids=True):
+        """hfcl_scene_collide_culled{,_f32}: (records, query_ids, conf_begin, summaries[, guesses]); record k is for query_ids[k] and equals
+        the unculled call's record of that query.  records / summary False: None in its place.  capacity: size of the outputs; a smaller one
+        than the list raises ERR_LIMIT.  Default: an eighth of the queries -- one call, the table crosses the link once; a list longer
+        than that costs a second call (the first is refused after the cull, before any narrow-phase work).  records=False, want_ids=False: the summaries (and conf_begin) alone, one call, no record
+        or id leaves the device."""
+        return self._culled("collide", object_tf, inflate, req or abi.default_collision_request(), records, summary, guess_in, want_guess, capacity,
+                            want_ids)
+
+    def distance_culled(self, object_tf, inflate=0.0, req=None, records=True, summary=True, guess_in=None, want_guess=False, capacity=None,
+                        want_ids=True):
+        return self._culled("distance", object_tf, inflate, req or abi.default_distance_request(), records, summary, guess_in, want_guess, capacity,
+                            want_ids)
+
+    # device forms: torch tensors or raw device pointers, asynchronous on `stream`
+    def world_aabbs_device(self, d_object_tf, n_conf, d_aabbs, f32=False, stream=0):
+        fn = dll().hfcl_scene_world_aabbs_device_f32 if f32 else dll().hfcl_scene_world_aabbs_device
+        _check(fn(self._h, _dptr(d_object_tf), C.c_size_t(int(n_conf)), _dptr(d_aabbs), C.c_void_p(stream)))
+
+    def cull_device(self, d_object_tf, n_conf, inflate, d_query_ids, capacity, d_conf_begin, d_n_listed, f32=False, stream=0):
+        """hfcl_scene_cull_device{,_f32}: *d_n_listed is the true count, ids past `capacity` are not written; nothing is read back."""
+        fn = dll().hfcl_scene_cull_device_f32 if f32 else dll().hfcl_scene_cull_device
+        _check(fn(self._h, _dptr(d_object_tf), C.c_size_t(int(n_conf)), C.c_double(inflate), _dptr(d_query_ids), C.c_size_t(int(capacity)),
+                  _dptr(d_conf_begin), _dptr(d_n_listed), C.c_void_p(stream)))
+
+    def collide_listed_device(self, d_object_tf, n_conf, d_query_ids, n_listed, d_conf_begin, req, d_out=None, d_summary=None, d_gin=None,
+                              d_gout=None, stream=0):
+        """hfcl_scene_collide_listed_device: the ids (ascending, below n_conf * n_pairs) are not checked."""
+        _check(dll().hfcl_scene_collide_listed_device(self._h, _dptr(d_object_tf), C.c_size_t(int(n_conf)), _dptr(d_query_ids),
+                                                      C.c_size_t(int(n_listed)), _dptr(d_conf_begin), C.byref(req), _dptr(d_out),
+                                                      _dptr(d_summary), _dptr(d_gin), _dptr(d_gout), C.c_void_p(stream)))
+
+    def distance_listed_device(self, d_object_tf, n_conf, d_query_ids, n_listed, d_conf_begin, req, d_out=None, d_summary=None, d_gin=None,
+                               d_gout=None, stream=0):
+        _check(dll().hfcl_scene_distance_listed_device(self._h, _dptr(d_object_tf), C.c_size_t(int(n_conf)), _dptr(d_query_ids),
+                                                       C.c_size_t(int(n_listed)), _dptr(d_conf_begin), C.byref(req), _dptr(d_out),
+                                                       _dptr(d_summary), _dptr(d_gin), _dptr(d_gout), C.c_void_p(stream)))
+
+    def collide_listed_device_f32(self, d_object_pose, n_conf, d_query_ids, n_listed, d_conf_begin, req, d_out=None, d_summary=None, stream=0):
+        _check(dll().hfcl_scene_collide_listed_device_f32(self._h, _dptr(d_object_pose), C.c_size_t(int(n_conf)), _dptr(d_query_ids),
+                                                          C.c_size_t(int(n_listed)), _dptr(d_conf_begin), C.byref(req), _dptr(d_out),
+                                                          _dptr(d_summary), C.c_void_p(stream)))
+
+    def distance_listed_device_f32(self, d_object_pose, n_conf, d_query_ids, n_listed, d_conf_begin, req, d_out=None, d_summary=None, stream=0):
+        _check(dll().hfcl_scene_distance_listed_device_f32(self._h, _dptr(d_object_pose), C.c_size_t(int(n_conf)), _dptr(d_query_ids),
+                                                           C.c_size_t(int(n_listed)), _dptr(d_conf_begin), C.byref(req), _dptr(d_out),
+                                                           _dptr(d_summary), C.c_void_p(stream)))
 
 
 def shard_range(n, rank, world):

@@ -598,6 +598,12 @@ typedef struct hfcl_scene_summary {
   uint32_t n_contacts;       /* records with the contact flag */
   uint32_t n_skipped;        /* records with status bit 31 */
 } hfcl_scene_summary;        /* 24 bytes */
+/* The summary of a culled call (hppfcl_amd_cull.h: the _culled and _listed forms) is the same fold over the surviving records only.
+ * With inflate = 0 that is a fold over exactly the pairs the reference's manager passes to the callback: n_contacts and first_contact equal
+ * the unculled values (a contact needs touching boxes), min_distance is over the survivors -- what CollisionCallBackDefault could have
+ * seen; a configuration without survivors reports +inf.  For distance queries inflate = D / 2 keeps every pair whose boxes are within D
+ * along each axis: a box-shaped filter, NOT the manager's traversal with its shrinking bound (a pair farther than the current minimum
+ * is still evaluated here, and a pair outside the filter is not, however close the others are). */
 
 typedef struct hfcl_scene hfcl_scene;   /* opaque: belongs to one library */
 /* object_shape: n_objects shape ids of `lib`; pairs: 2 * n_pairs object indices (i, j) as hfcl_pairlist_data gives them (i == j
@@ -653,4 +659,6 @@ int hfcl_scene_distance_device_f32(hfcl_scene* s, const float* d_object_pose, si
 #ifdef __cplusplus
 }
 #endif
+/* scene queries with the pair list culled per configuration on the device: the cull, the calls on its list, the host forms */
+#include "hppfcl_amd_cull.h"
 #endif /* HPPFCL_AMD_H */

@@ -1427,7 +1427,94 @@ class Scene {
   }
   const std::vector<hfcl_result>& records() const { return rec_; }
 
+  /// The pair list culled per configuration on the device (hfcl_scene_cull, include/hppfcl_amd_cull.h): the queries
+  /// q = c * numPairs() + p whose two world AABBs, each grown by `inflate` >= 0 on every side, overlap -- with inflate = 0 the pairs
+  /// DynamicAABBTreeCollisionManager::collide passes to its callback under configuration c.  query_ids: ascending;
+  /// conf_begin (n_conf + 1 entries): configuration c owns query_ids[conf_begin[c] .. conf_begin[c + 1]).
+  /// The outputs of the culled calls are sized by a guess (an eighth of the queries): one call, the tables cross the link once; a
+  /// longer list is refused with its length before any narrow-phase work, and the call is made once more with that.
+  void cull(const Transform3f* tables, size_t n_conf, double inflate, std::vector<uint64_t>& query_ids, std::vector<uint64_t>& conf_begin) {
+    ensure();
+    conf_begin.assign(n_conf + 1, 0);
+    size_t n = 0, capacity = list_guess(n_conf);
+    for (int attempt = 0;; ++attempt) {
+      query_ids.assign(capacity, 0);
+      const int rc = hfcl_scene_cull(scene_, reinterpret_cast<const double*>(tables), n_conf, inflate, query_ids.data(), capacity, conf_begin.data(), &n);
+      if (rc == HFCL_ERR_LIMIT && attempt == 0 && n > capacity) {
+        capacity = n;
+        continue;
+      }
+      if (rc) throw_for(rc);
+      break;
+    }
+    query_ids.resize(n);
+  }
+  /// collide() on the culled list: results[k] (nullptr: summaries only) is what hpp::fcl::collide gives for query query_ids[k];
+  /// summaries[c] folds configuration c's surviving pairs (n_contacts and first_contact as without the cull when inflate = 0).
+  void collideCulled(const Transform3f* tables, size_t n_conf, double inflate, const CollisionRequest& request,
+                     std::vector<CollisionResult>* results, std::vector<uint64_t>& query_ids, std::vector<uint64_t>& conf_begin,
+                     std::vector<hfcl_scene_summary>* summaries) {
+    ensure();
+    const hfcl_collision_request a = to_abi(request);
+    const size_t n = culled(tables, n_conf, results != nullptr, query_ids, conf_begin, summaries, [&](size_t capacity, size_t* listed) {
+      return hfcl_scene_collide_culled(scene_, reinterpret_cast<const double*>(tables), n_conf, inflate, &a, results ? rec_.data() : nullptr,
+                                       capacity, query_ids.data(), conf_begin.data(), summaries ? summaries->data() : nullptr, nullptr,
+                                       results ? guess_.data() : nullptr, listed);
+    });
+    if (!results) return;
+    results->assign(n, CollisionResult());
+    for (size_t k = 0; k < n; ++k) {
+      hfcl_result r = rec_[k];
+      if (r.num_contacts > 1) r.num_contacts = 1;
+      ctx_.fill((*results)[k], shape_pair(query_ids[k] % numPairs()), request, r, guess_[k]);
+    }
+  }
+  /// distance() on the culled list.  inflate = D / 2 keeps every pair whose boxes are within D along each axis: a box-shaped filter,
+  /// not the manager's distance traversal with its shrinking bound.
+  void distanceCulled(const Transform3f* tables, size_t n_conf, double inflate, const DistanceRequest& request,
+                      std::vector<DistanceResult>* results, std::vector<uint64_t>& query_ids, std::vector<uint64_t>& conf_begin,
+                      std::vector<hfcl_scene_summary>* summaries) {
+    ensure();
+    const hfcl_distance_request a = to_abi(request);
+    const size_t n = culled(tables, n_conf, results != nullptr, query_ids, conf_begin, summaries, [&](size_t capacity, size_t* listed) {
+      return hfcl_scene_distance_culled(scene_, reinterpret_cast<const double*>(tables), n_conf, inflate, &a, results ? rec_.data() : nullptr,
+                                        capacity, query_ids.data(), conf_begin.data(), summaries ? summaries->data() : nullptr, nullptr,
+                                        results ? guess_.data() : nullptr, listed);
+    });
+    if (!results) return;
+    results->assign(n, DistanceResult());
+    for (size_t k = 0; k < n; ++k) ctx_.fill((*results)[k], shape_pair(query_ids[k] % numPairs()), rec_[k], guess_[k]);
+  }
+
  private:
+  size_t list_guess(size_t n_conf) const {
+    const size_t total = n_conf * numPairs();
+    return std::min(total, std::max<size_t>(total / 8, 1024));
+  }
+  // a culled call with outputs sized by the guess, repeated once with the list's length if that was too small; returns the length
+  template <class Call>
+  size_t culled(const Transform3f*, size_t n_conf, bool records, std::vector<uint64_t>& query_ids, std::vector<uint64_t>& conf_begin,
+                std::vector<hfcl_scene_summary>* summaries, Call call) {
+    conf_begin.assign(n_conf + 1, 0);
+    if (summaries) summaries->resize(n_conf);
+    size_t n = 0, capacity = list_guess(n_conf);
+    for (int attempt = 0;; ++attempt) {
+      query_ids.assign(capacity, 0);
+      if (records) {
+        rec_.resize(capacity);
+        guess_.resize(capacity);
+      }
+      const int rc = call(capacity, &n);
+      if (rc == HFCL_ERR_LIMIT && attempt == 0 && n > capacity) {
+        capacity = n;
+        continue;
+      }
+      if (rc) throw_for(rc);
+      break;
+    }
+    query_ids.resize(n);
+    return n;
+  }
   void init() {
     shape_.resize(objects_.size());
     for (size_t i = 0; i < objects_.size(); ++i) shape_[i] = ctx_.add(objects_[i]->collisionGeometryPtr());

@@ -6,6 +6,11 @@ configuration) and on workloads.scene_planner at ~1 M queries.
   B  hfcl_scene_collide, records and summaries (host clock)        C  ... summaries only
   D  hfcl_collide_batch_device on pre-expanded resident arrays (device events)
   E  hfcl_scene_collide_device, records and summaries (device events)   F  ... summaries only
+  G  hfcl_scene_cull_device alone: boxes, mark, scan, emit (device events)
+  H  hfcl_scene_collide_culled, summaries only (host clock; against C)
+  I  hfcl_scene_cull_device, the count read back, hfcl_scene_collide_listed_device with records and summaries (device events; against E)
+  J  the same through the fp32 path (against K)          K  hfcl_scene_collide_device_f32, records and summaries (device events)
+The culled forms run at --inflate (default 0: the reference's manager).  planner2048: scene_planner(2048, 16), 215 040 queries.
 
 Every measurement runs in a child process; A and D also run on a library built from the parent commit's sources (--parent-lib, selected
 with HFCL_LIB_PATH in the child), alternating with the build under test.  Warm-up calls first, then --calls timed calls: median, min, max.
@@ -31,7 +36,7 @@ def _workload(pkg, name):
         b = wl.cfg5_broadphase_scene()
         sc = b.scene
         return b.lib, sc["obj_shape"], sc["pairs"], sc["obj_tf"].reshape(1, -1, 12)
-    ps = wl.scene_planner(n_conf=9984, n_objects=16)
+    ps = wl.scene_planner(n_conf=2048 if name == "planner2048" else 9984, n_objects=16)
     return ps.lib, ps.obj_shape, ps.pairs, ps.obj_tf
 
 
@@ -53,7 +58,7 @@ def worker(args):
     req = abi.default_collision_request()
     dev = torch.device("cuda:0")
     st = torch.cuda.current_stream().cuda_stream
-    out = {"workload": args.workload, "lib": os.environ.get("HFCL_LIB_PATH", "in-tree"), "n_conf": n_conf, "n_objects": G, "n_pairs": P, "queries": n,
+    out = {"workload": args.workload, "lib": os.path.relpath(os.environ["HFCL_LIB_PATH"], ROOT) if "HFCL_LIB_PATH" in os.environ else "in-tree", "n_conf": n_conf, "n_objects": G, "n_pairs": P, "queries": n,
            "forms": {}}
 
     def expand():
@@ -85,7 +90,7 @@ def worker(args):
         return _stats(ms)
 
     forms = args.forms.split(",")
-    scene = lib.scene(obj_shape, pairs) if set(forms) & set("BCEF") else None
+    scene = lib.scene(obj_shape, pairs) if set(forms) & set("BCEFGHIJK") else None
     if "A" in forms or "D" in forms:
         t0 = time.perf_counter()
         s1, s2, tf1, tf2 = expand()
@@ -108,6 +113,46 @@ def worker(args):
         out["forms"]["E"] = device_clock(lambda: scene.collide_device(d_tab, n_conf, req, d_rec, d_sum, stream=st))
     if "F" in forms:
         out["forms"]["F"] = device_clock(lambda: scene.collide_device(d_tab, n_conf, req, None, d_sum, stream=st))
+    if set(forms) & set("GHIJK"):
+        ids, _ = scene.cull(table, args.inflate)
+        out["inflate"] = args.inflate
+        out["n_listed"] = int(len(ids))
+        # the cull's byte model: the pose table in, 8 B of pair list per query, 8 B per survivor out (boxes and pair rows: cached)
+        out["cull_model_bytes"] = 96.0 * n_conf * G + 8.0 * n + 8.0 * len(ids)
+        d_tab64 = torch.from_numpy(np.ascontiguousarray(table)).to(dev)
+        d_ids = torch.zeros(max(len(ids), 1), dtype=torch.int64, device=dev)
+        d_cb = torch.zeros(n_conf + 1, dtype=torch.int64, device=dev)
+        d_n = torch.zeros(1, dtype=torch.int64, device=dev)
+        d_sum2 = torch.zeros(n_conf * 6, dtype=torch.int32, device=dev)
+
+        def culled_device(d_table, d_records, f32):
+            scene.cull_device(d_table, n_conf, args.inflate, d_ids, len(d_ids), d_cb, d_n, f32=f32, stream=st)
+            k = int(d_n.item())  # the one read-back: 8 bytes
+            fn = scene.collide_listed_device_f32 if f32 else scene.collide_listed_device
+            fn(d_table, n_conf, d_ids, min(k, len(d_ids)), d_cb, req, d_records, d_sum2, stream=st)
+    if "G" in forms:
+        out["forms"]["G"] = device_clock(lambda: scene.cull_device(d_tab64, n_conf, args.inflate, d_ids, len(d_ids), d_cb, d_n, stream=st))
+    if "H" in forms:
+        out["forms"]["H"] = host_clock(lambda: scene.collide_culled(table, args.inflate, req, records=False, want_ids=False))
+    if "I" in forms:
+        d_rec2 = torch.zeros(max(len(ids), 1) * 24, dtype=torch.int32, device=dev)
+        out["forms"]["I"] = device_clock(lambda: culled_device(d_tab64, d_rec2, False))
+    if "J" in forms or "K" in forms:
+        # 7-float poses of the same table: quaternions from the rotation matrices (w from the trace; the planner's and cfg5's rotations are
+        # generic, no w near 0)
+        R = pkg.geometry.pose_R(table.reshape(-1, 12))
+        w4 = np.sqrt(np.maximum(1.0 + R[:, 0, 0] + R[:, 1, 1] + R[:, 2, 2], 1e-12)) * 2.0
+        quat = np.stack([0.25 * w4, (R[:, 2, 1] - R[:, 1, 2]) / w4, (R[:, 0, 2] - R[:, 2, 0]) / w4, (R[:, 1, 0] - R[:, 0, 1]) / w4], axis=1)
+        pose = pkg.geometry.pose_f32_from_quat(quat / np.linalg.norm(quat, axis=1, keepdims=True), table.reshape(-1, 12)[:, 9:]).reshape(n_conf, G, 7)
+        d_pose = torch.from_numpy(np.ascontiguousarray(pose)).to(dev)
+    if "K" in forms:
+        d_rec32 = torch.zeros(n * 11, dtype=torch.int32, device=dev)
+        out["forms"]["K"] = device_clock(lambda: scene.collide_device_f32(d_pose, n_conf, req, d_rec32, d_sum2, stream=st))
+    if "J" in forms:
+        ids32, _ = scene.cull(pose, args.inflate)
+        d_ids = torch.zeros(max(len(ids32), len(ids), 1), dtype=torch.int64, device=dev)
+        d_rec32c = torch.zeros(len(d_ids) * 11, dtype=torch.int32, device=dev)
+        out["forms"]["J"] = device_clock(lambda: culled_device(d_pose, d_rec32c, True))
     torch.cuda.synchronize()
     if scene is not None:
         scene.close()
@@ -132,7 +177,9 @@ def bytes_moved(n_conf, G, P):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--worker", action="store_true")
-    ap.add_argument("--workload", default="cfg5", choices=["cfg5", "planner"])
+    ap.add_argument("--workload", default="cfg5", choices=["cfg5", "planner", "planner2048"])
+    ap.add_argument("--workloads", default="cfg5,planner", help="the workloads of a full run, comma-separated")
+    ap.add_argument("--inflate", type=float, default=0.0)
     ap.add_argument("--forms", default="A,B,C,D,E,F")
     ap.add_argument("--calls", type=int, default=12)
     ap.add_argument("--warmup", type=int, default=3)
@@ -144,7 +191,7 @@ def main():
         return worker(args)
     have_parent = os.path.exists(args.parent_lib)
     results = []
-    for workload in ("cfg5", "planner"):
+    for workload in args.workloads.split(","):
         for _ in range(args.rounds):
             for which in (["parent"] if have_parent else []) + ["new"]:
                 env = dict(os.environ)
@@ -152,7 +199,7 @@ def main():
                 if which == "parent":
                     env["HFCL_LIB_PATH"] = args.parent_lib
                 cmd = [sys.executable, os.path.abspath(__file__), "--worker", "--workload", workload, "--calls", str(args.calls), "--warmup",
-                       str(args.warmup), "--forms", "A,D" if which == "parent" else args.forms]
+                       str(args.warmup), "--inflate", str(args.inflate), "--forms", "A,D" if which == "parent" else args.forms]
                 r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
                 line = [x for x in r.stdout.splitlines() if x.startswith("SCENE_BENCH ")]
                 if r.returncode != 0 or not line:  # a child that failed ends the run: nothing more is started on the device
@@ -162,7 +209,7 @@ def main():
                 res["build"] = which
                 results.append(res)
                 print(json.dumps(res), flush=True)
-    for workload in ("cfg5", "planner"):
+    for workload in args.workloads.split(","):
         rs = [r for r in results if r["workload"] == workload]
         if not rs:
             continue
@@ -171,13 +218,16 @@ def main():
         print("| form | build | median ms | min .. max ms (over the runs) |")
         print("|---|---|---|---|")
         for which in ("parent", "new"):
-            for f in "ABCDEF":
+            for f in "ABCDEFGHIJK":
                 runs = [r["forms"][f] for r in rs if r["build"] == which and f in r["forms"]]
                 if runs:
                     print("| %s | %s | %s | %.3f .. %.3f |" % (f, which, " / ".join("%.3f" % x["median_ms"] for x in runs),
                                                           min(x["min_ms"] for x in runs), max(x["max_ms"] for x in runs)))
         print("host expansion for A: %s ms" % " / ".join("%.1f" % r["host_expansion_ms"] for r in rs if "host_expansion_ms" in r))
         print("bytes per query: " + json.dumps(bytes_moved(r0["n_conf"], r0["n_objects"], r0["n_pairs"])))
+        if "n_listed" in r0:
+            print("cull at inflate %g: %d of %d queries survive (%.2f %%); byte model of the cull alone: %.0f bytes" % (
+                r0["inflate"], r0["n_listed"], r0["queries"], 100.0 * r0["n_listed"] / r0["queries"], r0["cull_model_bytes"]))
     if args.out:
         with open(args.out, "w") as f:
             json.dump(results, f, indent=1)
