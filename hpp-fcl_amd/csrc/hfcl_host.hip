@@ -1,6 +1,7 @@
-// hfcl_host.hip -- host side: library object, batch pipeline and the C-ABI implementation of
-// include/hppfcl_amd.h (the kernels live in hfcl_k_gjk.hip / hfcl_k_epa.hip / hfcl_k_bvh.hip, see hfcl_launch.hpp).  No CPU fallback anywhere in this file: every compute entry point
-// needs a HIP device and fails loudly without one.
+// hfcl_host.hip -- host side: library object, options, uploads, batch pipeline, host pipeline and their part of the C-ABI implementation of
+// include/hppfcl_amd.h (contact patches: hfcl_host_patch.hip; scene queries and the cull: hfcl_host_scene.hip; the library object itself and
+// what the three units share: hfcl_host.hpp; the kernels live in hfcl_k_gjk.hip / hfcl_k_epa.hip / hfcl_k_bvh.hip, see hfcl_launch.hpp).
+// No CPU fallback anywhere in these files: every compute entry point needs a HIP device and fails loudly without one.
 //
 // Kernel map (pair buckets follow the reference's dispatch table,
 // include/hpp/fcl/internal/shape_shape_func.h:185-211 and src/collision_func_matrix.cpp:279-733):
@@ -28,345 +29,14 @@
 //   k_bvh_shape<T> / k_bvh_shape_distance<T>   ... one query per 16-lane group, sequential traversal, leaves =
 //                    TriangleP-vs-solid GJK + EPA in LDS: requests that keep walking after a contact
 //   k_unsupported<T> flags the pairs of a bucket the engine cannot evaluate (never computed elsewhere)
-#include <algorithm>
-#include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <condition_variable>
-#include <map>
-#include <mutex>
-#include <thread>
-#include <string>
-#include <vector>
-
-#include "hfcl_dev.hpp"
-#include "hfcl_launch.hpp"
-#include "hfcl_patch.hpp"
-#include "hfcl_scene.hpp"
-#include "hfcl_cull.hpp"
+#include "hfcl_host.hpp"
 
 // =======================================================================================
 // Host side: library object + C ABI
 // =======================================================================================
 static thread_local std::string g_last_error;
-static void set_error(const std::string& s) { g_last_error = s; }
+void set_error(const std::string& s) { g_last_error = s; }
 void hfcl_internal_set_error(const char* msg) { g_last_error = msg ? msg : ""; }  // hfcl_multi.hip: a worker thread's message handed to the caller's
-
-#define HIP_TRY(expr)                                                                         \
-  do {                                                                                        \
-    hipError_t _e = (expr);                                                                   \
-    if (_e != hipSuccess) {                                                                   \
-      set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                           \
-      return HFCL_ERR_HIP;                                                                    \
-    }                                                                                         \
-  } while (0)
-
-struct KernelTime {
-  const char* name;
-  hipEvent_t e0, e1;
-  bool used;
-};
-
-struct hfcl_lib {
-  int device = 0;
-  size_t n_shapes = 0;
-  std::vector<hfcl_shape> h_shapes;
-  std::vector<uint8_t> h_kinds;  // host copy of d_kinds: small host batches are classified on the host (host_batch)
-  DShape<double>* d_shapes64 = nullptr;
-  DShape<float>* d_shapes32 = nullptr;
-  double* d_verts64 = nullptr;
-  float* d_verts32 = nullptr;
-  uint8_t* d_kinds = nullptr;
-  // vertex adjacency of convex shapes (hfcl_lib_set_convex_neighbors): host copies per shape, device image built lazily
-  std::vector<double> h_verts;
-  struct HostGraph { std::vector<uint32_t> off, ids; };
-  std::map<uint32_t, HostGraph> h_graphs;
-  bool graph_dirty = false;
-  uint32_t* d_graph_base = nullptr;
-  std::vector<void*> graph_retired;   // adjacency images replaced by a later registration: batches in flight on other streams may still read
-                                      // them, so they are freed where the library waits for the device anyway (set_shapes, destroy)
-  hipStream_t upload_stream = nullptr;  // non-blocking stream of the adjacency upload (the host waits for it alone)
-  uint32_t* d_graph_off = nullptr;
-  NbrEntry<float>* d_graph_ent32 = nullptr;
-  NbrEntry<double>* d_graph_ent64 = nullptr;
-  uint32_t climb_min = HFCL_CLIMB_MIN;  // HFCL_CLIMB_MIN: hulls of at least this many vertices with a graph hill-climb
-  // workspace (grown on demand)
-  size_t ws_capacity = 0;  // pairs
-  size_t epa_capacity = 0;  // pairs the EPA queues / hand-over area are sized for (0: not allocated yet)
-  uint32_t* d_lists = nullptr;
-  uint32_t* d_counts = nullptr;
-  void* d_epa_queue = nullptr;
-  void* d_epa_queue2 = nullptr;
-  uint32_t* d_epa_cc_over = nullptr;  // Work::epa_cc_over (resume_cap entries)
-  hipStream_t aux = nullptr;     // k_epa_records runs here, beside the tiers that continue the handed-over polytopes
-  hipStream_t mesh_st = nullptr;  // the mesh walks of a mixed library's batch run here, beside the solids' kernels (option mesh_beside)
-  hipEvent_t ev_mesh_fork = nullptr, ev_mesh_join = nullptr;
-  // ... the mesh x mesh walks of such a batch beside its mesh x solid walks (tables of their own: d_bvh2_*), and the helper stream the
-  // mesh x solid walks use instead of `aux` (which the solids' EPA section, now beside them, uses)
-  hipStream_t mesh_st2 = nullptr, mesh_aux = nullptr;
-  bool ran_batch = false;  // h_counts holds the bucket counts of this library's last batch (once its copy has landed)
-  hipEvent_t ev_mesh_fork2 = nullptr, ev_mesh_join2 = nullptr;
-  BvhTask* d_bvh2_tasks = nullptr;
-  void* d_bvh2_sums = nullptr;
-  uint32_t* d_bvh2_susp = nullptr;
-  uint32_t* d_bvh2_ctr = nullptr;
-  size_t bvh2_split_n = 0, bvh2_split_cap = 0;
-  // 0 in line; 1 the mesh walks beside the solids' GJK kernels; 2 also mesh x mesh beside mesh x solid, the solids' EPA section beside both
-  // (1, 2: when the library's last batch held meshes and solids); 4: as 2 whatever the last batch held
-  uint32_t mesh_beside = 2;
-  bool mesh_prio = false;  // option mesh_prio = 1: the streams of the mesh x solid walks at the device's highest priority (read when they are created)
-  // the solids' GJK kernels of a small batch run beside each other on these (option gjk_beside_max): one bucket's kernel does not fill the chip
-  hipStream_t gjk_st[3] = {nullptr, nullptr, nullptr};
-  hipEvent_t gjk_fork = nullptr, gjk_join[3] = {nullptr, nullptr, nullptr};
-  uint32_t epa_direct_max = 4096;    // largest batch whose EPA seeds all go to the full-capacity tier, the fast tiers not launched (0: never)
-  uint32_t gjk_beside_max = 120000;  // largest batch whose GJK kernels fan out (0: never; below the size from which batches run as two halves)
-  hipStream_t walk_st[WALK_ROUNDS - 1] = {};  // mesh x mesh collide(): the continuation of what round r of the walk hands over runs on walk_st[r]
-  hipEvent_t walk_fork[WALK_ROUNDS - 1] = {}, walk_join[WALK_ROUNDS - 1] = {};
-  hipEvent_t ev_aux0 = nullptr, ev_aux1 = nullptr, ev_aux2 = nullptr, ev_aux3 = nullptr;  // fork / join of the EPA tail; of k_bvh_shape_finish's first half
-  void* d_epa_ready = nullptr;   // EpaReady<float>[epa_ready_capacity]: the staged convex x convex fast tier (k_epa_prepare / k_epa_loop / k_epa_records)
-  size_t epa_ready_capacity = 0;
-  void* d_epa_ready_g = nullptr; // EpaReadyG<T>[ws_capacity]: the staged fast tier of the general queues (both precisions)
-  size_t epa_ready_g_bytes = 0;
-  bool epa_general_staged = false;       // HFCL_EPA_GENERAL_STAGED=1: prepare / loop / records for the general queues too.  Byte-identical
-                                         // records; measured slower in wall-clock on cfg2 (0.416 -> 0.479 ms) and cfg5 unsplit (4.77 -> 5.30 ms
-                                         // per 1M mixed pairs), faster only on cfg5 split (5.34 -> 5.13): profiles/r05_e_general_staged.md
-  size_t epa_general_staged_min = 32768; // HFCL_EPA_GENERAL_STAGED_MIN
-  bool records_aside = true;     // HFCL_EPA_RECORDS_ASIDE=0: k_epa_records on the batch's stream
-  bool epa64_two_streams = true; // HFCL_EPA64_TWO_STREAMS=0: the two fp64 fast-tier kernels one after the other
-  bool epa_cc_staged = true;     // HFCL_EPA_CC_STAGED=0: the one-kernel form (k_epa_stream<.., CC>)
-  size_t epa_cc_staged_min = 32768;  // ... which batches below this many pairs keep (two launches less); HFCL_EPA_CC_STAGED_MIN
-  void* d_epa_resume = nullptr;
-  void* d_epa_v0 = nullptr;
-  size_t resume_cap = 0;
-  bool shape_finish_tiers = true;  // HFCL_SHAPE_FINISH_TIERS=0: k_bvh_shape_finish in one launch at full capacity
-  bool shape_finish_aside = true;  // HFCL_SHAPE_FINISH_ASIDE=0: all of k_bvh_shape_finish behind the last launch of k_bvh_shape_coop
-  void* d_shape_defer = nullptr;  // ShapeDeferItem<double>[shape_defer_capacity]: EPA queue of the one-query-per-lane mesh x solid form
-  void* d_shape_oq = nullptr;     // ObbQuery<double>[shape_oq_capacity]: the solids' OBBs against the mesh poses, by pair
-  size_t shape_defer_capacity = 0, shape_oq_capacity = 0;
-  bool bvh_shape_lane = true;     // HFCL_BVH_SHAPE_LANE=0: the group kernels for every request (A/B switch)
-  // step budgets of the one-query-per-lane mesh x solid walk (a unit suspends into tasks when it has taken that many BV-test
-  // equivalents; a GJK leaf counts shape_leaf_cost): the queries themselves / their tasks.  The steps per query have a heavy
-  // tail whatever the batch size (median 1, mean ~60, maximum > 3000 steps with > 1000 leaves), so the walk is always split.
-  uint32_t shape_budget0 = 128, shape_budget = 96, shape_leaf_cost = 32, shape_levels = BVH_MAX_LEVELS;
-  // Suspended queries are continued by k_bvh_shape_coop (a wave per query, 64 stack entries per trip) instead of task levels
-  // (HFCL_SHAPE_COOP=0: the levels); the queries' own budget is then 16 steps (100k queries per kind, budgets 8 / 16 / 32 / 128:
-  // sphere 2.0 / 2.0 / 2.4 / 2.6 ms, ellipsoid 7.5 / 8.1 / 8.4 / 8.3, box 1.4 / 1.3 / 1.2 / 1.1; profiles/r03_i)
-  bool shape_coop = true;
-  // ... and a walk such a kernel has worked on for this many clock ticks is cut into chunk tasks for its next launch (BvhSplit::cut_ticks;
-  // HFCL_BVH_CUT_TICKS / HFCL_SHAPE_CUT_TICKS; 0: never).  The records equal the uncut walks' in every field wherever the cuts fall
-  // (tools/cut_check.py).  mesh x solid, 600 000 ticks (~2.3x the mean walk): 100k mixed queries 4.4 -> 3.7 ms on one box, the single
-  // kinds within +-5 %; shorter budgets lose (200 000: 3.5 against 3.3 at 400 000, 100 000: 6.8 ms -- every cut walks the chunks
-  // behind a contact for nothing and pays three launches).  mesh x mesh: off -- its waves are busy 79 % of the kernel's time already
-  // and cfg4 went 2.97 -> 3.18 ms (profiles/r04_j)
-  uint32_t bvh_cut_ticks = 0, shape_cut_ticks = 350000;  // (600 000 until the queries' own phase became three kernels: profiles/r06_g section 5)
-  uint32_t shape_budget0_coop = 16;
-  // Mesh x mesh queries past their step budget are continued by k_bvh_coop (a wave per query, 64 stack entries per trip)
-  // instead of task levels (HFCL_BVH_COOP=0: the levels).  cfg4, budgets 160 / 192 / 256 / 320 / 384: 100k queries 3.82 / 3.53 /
-  // 3.28 / 3.39 / 3.57 ms (levels: 5.03); 1M queries, 256 / 512 / 640 / 1024: 15.1 / 10.95 / 10.86 / 11.9 ms (unsplit stream:
-  // 14.7); 250k: 5.03 ms (8.78); 10k: 2.63 (3.74) -- profiles/r03_k.  HFCL_BVH_BUDGET0_COOP overrides both.
-  bool bvh_coop = true;
-  uint32_t bvh_budget0_coop = 0;  // 0: 256 steps up to 500k queries, 640 beyond
-  // distance(): a mesh x mesh walk that has taken this many steps is continued by a wave (k_bvh_distance_coop); 0: never
-  uint32_t bvhd_budget = 64;      // HFCL_BVHD_BUDGET: steps a lane walks before its walk goes to k_bvh_distance_pool (cfg4d 100k queries, budgets 16 / 64 / 256: 34.4 / 33.2 / 34.1 ms, profiles/r04_c; with the wave-per-walk form of round 3, HFCL_BVHD_POOL=0, 1024 was best: 55.7 ms)
-  uint32_t bvhd_pool = 1;         // HFCL_BVHD_POOL: the walks past the budget are continued by k_bvh_distance_pool (0: k_bvh_distance_coop)
-  uint32_t bvhd_pool_leaf_min = 24, bvhd_pool_starve = 32, bvhd_pool_part_min = 48;  // HFCL_BVHD_LEAF_MIN / HFCL_BVHD_STARVE / HFCL_BVHD_PART_MIN
-  void* d_dist_susp = nullptr;    // DistSusp<double>[dist_susp_capacity]
-  size_t dist_susp_capacity = 0;
-  uint32_t pool_rerun = 1;          // HFCL_POOL_RERUN: pooled distance() walks whose result could hang on a rounding error are walked again in order (0: never -- the round-5 behaviour; 2: every walk, a test of the ordered mode)
-  uint32_t shape_dist_pool = 1;     // HFCL_SHAPE_DIST_POOL: mesh x solid distance() walks past the budget continue in k_bvh_shape_distance_pool (0: k_bvh_shape_distance_coop)
-  uint32_t shape_dist_leaf_min = 48, shape_dist_starve = 16;  // HFCL_SHAPE_DIST_LEAF_MIN / HFCL_SHAPE_DIST_STARVE (a GJK pass is worth waiting for: profiles/r04_i)
-  uint32_t shape_dist_budget = 64;  // HFCL_SHAPE_DIST_BUDGET: the same for mesh x solid (a GJK leaf counts 16 steps; k_bvh_shape_distance_coop)
-  void* d_shape_dist_susp = nullptr;
-  size_t shape_dist_susp_capacity = 0;
-  // host-call staging: PIPE_SLOTS device buffer sets of `st_capacity` pairs each (a chunk of a host batch), three streams
-  // (H2D | kernels | D2H) and per-slot events / pinned counter blocks (host_batch)
-  static constexpr int PIPE_SLOTS = 6;  // (three left the feeder waiting for records to leave: profiles/r03_c)
-  struct Staging {
-    uint32_t *d_s1 = nullptr, *d_s2 = nullptr;
-    double *d_tf1 = nullptr, *d_tf2 = nullptr;
-    double *d_qt1 = nullptr, *d_qt2 = nullptr;  // compact host poses (7 doubles), expanded into d_tf1/2 on the device
-    hfcl_result* d_out = nullptr;
-    hfcl_guess *d_gin = nullptr, *d_gout = nullptr;
-    hipEvent_t ev_in = nullptr, ev_in2 = nullptr, ev_done = nullptr;  // inputs of object 1 / object 2 arrived, kernels done
-    uint32_t* h_counts = nullptr;  // pinned: bucket populations of the chunk that last ran in this slot
-    uint32_t* h_counts2 = nullptr; // ... of its second half when the chunk ran split
-    bool split = false;
-  };
-  Staging stage[PIPE_SLOTS];
-  size_t st_capacity = 0;
-  // small host batches (<= SMALL_MAX pairs): every input array packed into one pinned block and one device block (one
-  // copy in, one copy out, one stream) instead of five copies and the pipeline's threads
-  static constexpr size_t SMALL_MAX = 4096;
-  char* h_pack = nullptr;  // pinned
-  char* d_pack = nullptr;
-  uint32_t* h_pack_counts = nullptr;  // pinned: bucket populations of a small batch (and of its second half: never split)
-  hipStream_t s_h2d = nullptr, s_h2d2 = nullptr, s_cmp = nullptr, s_d2h = nullptr;
-  uint32_t acc_counts[N_COUNTERS] = {0};  // host batches: bucket populations summed over the chunks
-  bool last_host = false;                 // the last call was a host batch: acc_counts are its populations
-  bool in_host_batch = false;
-  size_t pipe_chunk = 0;                  // pairs per chunk (0 = automatic); HFCL_PIPE_CHUNK / hfcl_lib_set_host_chunk
-  uint32_t* counts_dst = nullptr;         // where run_batch_one sends the bucket populations (default: h_counts)
-  // instrumentation
-  std::vector<KernelTime> timers;
-  // A batch can run as two halves on two streams (hfcl_lib_set_split): the second half goes to `helper`, a shallow
-  // clone (same device shape tables, own workspace / counters / timers) on the internal stream `side`, whose kernels
-  // fill the drain phases of the first half's GJK / EPA launches (profiles/r01_k_two_stream_overlap.txt).
-  int split = 0;  // 0 = automatic (auto_split), 1 = never, 2 = always (large batches without meshes)
-  hfcl_lib* helper = nullptr;
-  bool is_helper = false;   // does not own the shape tables
-  bool last_split = false;  // the last batch ran split: counters / timers of the helper belong to it
-  hipStream_t side = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  bool kernel_timing = true;         // HIP events around every kernel (hfcl_lib_set_kernel_timing)
-  // contact patches (hfcl_contact_patch_batch*): workspace slots, class lists, their counters; staging of the host form
-  void* d_patch_ws = nullptr;
-  size_t patch_ws_bytes = 0;
-  uint32_t* d_patch_lists = nullptr;
-  size_t patch_list_cap = 0;
-  uint32_t* d_patch_counts = nullptr;
-  hipStream_t patch_st = nullptr;
-  // scene queries (hfcl_scene_*): the workspace of a chunk of queries -- expanded ids and poses, two record / guess buffers (summary-only
-  // calls and the host form), the fold's partials --, the host form's object table and summaries, its two streams and per-chunk counters
-  struct SceneWs {
-    uint32_t *d_s1 = nullptr, *d_s2 = nullptr;
-    void *d_tf1 = nullptr, *d_tf2 = nullptr;
-    size_t cap = 0;                 // queries the four arrays above hold
-    void* d_rec[2] = {nullptr, nullptr};
-    size_t rec_cap[2] = {0, 0};     // records (of 96 B) each holds
-    hfcl_guess *d_gin = nullptr, *d_gout[2] = {nullptr, nullptr};
-    size_t gin_cap = 0, gout_cap[2] = {0, 0};
-    hfcl_scene_summary* d_partials = nullptr;
-    size_t partials_cap = 0;
-    void* d_table = nullptr;        // host form: the object pose table
-    size_t table_bytes = 0;
-    hfcl_scene_summary* d_summary = nullptr;
-    size_t summary_cap = 0;
-    hipStream_t s_cmp = nullptr, s_copy = nullptr;
-    hipEvent_t ev_done[2] = {nullptr, nullptr}, ev_copied[2] = {nullptr, nullptr};
-    static constexpr int COUNT_SLOTS = 8;
-    uint32_t* h_counts = nullptr;   // pinned: COUNT_SLOTS x 2 * N_COUNTERS words of the host form (a chunk, its second half when it ran split);
-                                    // chunk k uses slot k % COUNT_SLOTS once chunk k - COUNT_SLOTS has been added up (ev_counts: its kernels are done)
-    hipEvent_t ev_counts[COUNT_SLOTS] = {};
-    // culling the pair list (hfcl_scene_cull*): world boxes of the configurations a chunk touches (host forms of hfcl_scene_world_aabbs: of
-    // the whole table), ballots / workgroup counts / offsets of a chunk, the running count, and the list of the host forms
-    double* d_boxes = nullptr;
-    size_t boxes_cap = 0;           // boxes (of 6 doubles)
-    uint64_t* d_words = nullptr;
-    size_t words_cap = 0;
-    uint32_t* d_block_counts = nullptr;
-    uint64_t* d_block_offsets = nullptr;
-    size_t blocks_cap = 0;
-    uint64_t* d_running = nullptr;  // [0]: the running count of a cull, [1]: n_listed of the host forms
-    uint64_t* d_ids = nullptr;      // host forms: the surviving queries
-    size_t ids_cap = 0;
-    uint64_t* d_conf_begin = nullptr;
-    size_t conf_begin_cap = 0;
-  } scene;
-  // Queries per chunk of the cull (option scene_cull_chunk; 0: automatic -- at most 2^22 queries, 16384 workgroup counts for the one-workgroup scan)
-  size_t scene_cull_chunk = 0;
-  // local AABB of every library shape (hfcl_cull.hpp: shape_local_box; BVH models: the box of their vertices), 6 doubles each, rebuilt when
-  // shapes or meshes were registered since (hfcl_lib_set_shapes, hfcl_lib_add_bvh)
-  double* d_local_boxes = nullptr;
-  bool local_boxes_dirty = true;
-  std::vector<uint32_t> h_mesh_nverts;  // vertices of each registered BVH model
-  // Queries per chunk of a scene call (option scene_chunk; 0: automatic -- at most 2^21 queries, the call cut into equal chunks).  The chunks of a
-  // call run one after the other, and the solvers' kernels are chains of dependent steps that fill the chip only with a large batch: cfg5's
-  // 1.07 M queries in chunks of 262144 (the host pipeline's steady chunk) took 5.9 ms against 2.4 ms for the per-pair call on resident arrays,
-  // 9.0 ms of kernel time against 5.5 (profiles/r08_a_scene.md).  2^21 queries are 0.8 GB of workspace, allocated only by calls that large.
-  size_t scene_chunk = 0;
-  uint64_t shapes_epoch = 0;        // hfcl_lib_set_shapes counts: a scene made before the last one is stale
-  uint32_t possible_buckets = ~0u;   // bit b: some pair of this library's shape kinds classifies into bucket b
-  bool has_flats = true;             // some shape is a Plane / Halfspace: their "very rough" volumes are no lower bounds, so what a mesh walk
-                                     // against them reports depends on the ORDER of its visits -- the ordered continuation, not the pool
-  bool has_curved = true;            // some shape is an Ellipsoid / Cone / Cylinder: the curved class of the fp64 EPA tiers can occur
-  int cvx_w = 0;  // 0 = per kernel (auto_cvx_w); HFCL_CVX_W forces one width for all
-  bool closed_staged = true;  // HFCL_CLOSED_STAGED=0: A/B switch back to the direct-access k_closed<double>
-  int n_cus = 256;
-  std::string dominant;
-  // bucket populations of the last call; PINNED host memory so that the device-to-host copy at the end of a batch is
-  // asynchronous (a pageable destination makes hipMemcpyAsync block the host until the whole batch has run)
-  uint32_t* h_counts = nullptr;
-  // BVH models (host staging + device images in both precisions; uploaded lazily)
-  std::vector<hfcl_bvh_node> h_bvh_nodes;
-  std::vector<double> h_bvh_verts;
-  std::vector<uint32_t> h_bvh_tris;
-  std::vector<DMesh> h_meshes;
-  bool bvh_dirty = false;
-  DNode<double>* d_nodes64 = nullptr;
-  DNode<float>* d_nodes32 = nullptr;
-  DNodeF* d_fnodes = nullptr;  // 64-byte records of the fp32 separating-axis filter (fp64 collide)
-  bool bvh_filter = false;     // HFCL_BVH_FILTER=1: the fp32 filter form of k_bvh_collide (exact, measured slower: profiles/r03_b)
-  DRss<double>* d_rss64 = nullptr;
-  DRss<float>* d_rss32 = nullptr;
-  DNodeD<double>* d_dnodes64 = nullptr;  // the distance() walk's packed node records
-  DNodeD<float>* d_dnodes32 = nullptr;
-  double* d_bverts64 = nullptr;
-  float* d_bverts32 = nullptr;
-  uint32_t* d_btris = nullptr;
-  DMesh* d_meshes = nullptr;
-  // models too large (> 65535 nodes) or too deep for the LDS stacks: 32-bit node ids + per-lane global slabs (BvhSpill)
-  uint32_t bvh_max_depth = 0;
-  size_t bvh_max_nodes = 0;
-  void* d_bvh_slab = nullptr;
-  size_t bvh_slab_bytes = 0;
-  // split mesh x mesh traversals (BvhSplit): task table, unit summaries, suspended-query list, counters
-  BvhTask* d_bvh_tasks = nullptr;
-  uint32_t* d_bvh_cut_words = nullptr;  // BvhSplit::cut_words / cut_vals (bvh_split_cap entries each)
-  double* d_bvh_cut_vals = nullptr;
-  void* d_bvh_sums = nullptr;
-  uint32_t* d_bvh_susp = nullptr;
-  uint32_t* d_bvh_ctr = nullptr;
-  // mesh x mesh collide() in walk / leaves / resolve rounds (hfcl_dev.hpp: WalkRec): records, item list, leaf results, the two query lists, counters
-  void* d_walk_recs = nullptr;
-  uint32_t* d_walk_items = nullptr;
-  void* d_walk_res = nullptr;
-  uint32_t* d_walk_lists = nullptr;
-  uint32_t* d_walk_order = nullptr;  // BvhSplit::order (one entry per suspended slot)
-  bool walk_order = true;            // option bvh_walk_order: the continuation launches draw the queries with the most stack entries first
-  uint32_t* d_walk_ctr = nullptr;
-  size_t walk_n = 0;
-  // ... of the mesh x solid walks (their own: the two kinds of walks of a mixed batch run beside each other); lists: [2 n] + the redo list [n]
-  void* d_swalk_recs = nullptr;
-  uint32_t* d_swalk_items = nullptr;
-  void* d_swalk_res = nullptr;
-  uint32_t* d_swalk_lists = nullptr;
-  uint32_t* d_swalk_ctr = nullptr;   // 8 words per round, then the 64 words of WalkArgs::hist
-  uint32_t* d_swalk_perm = nullptr;  // WalkArgs::perm
-  size_t swalk_n = 0;
-  bool shape_walk_sort = true;       // option shape_walk_sort = 0: the listed leaves evaluated in the order the walks listed them
-  bool shape_walk = true;            // option shape_walk = 0: the queries' own phase of mesh x solid collide() by k_bvh_collide's SOLID form (walk and leaves in one kernel)
-  uint32_t shape_walk_budget = 256;  // box tests a query's walk may take before k_bvh_shape_coop continues it
-  uint32_t shape_walk_min = 65536;   // batch size from which that phase is used (its eight launches are 0.2 ms of latency: 20k queries 1.63 against 1.42 ms,
-                                     // 50k 1.96 / 1.82, 100k 2.43 / 2.70, 200k 3.55 / 4.16)
-  size_t epa_resume_slots = 0, bvh_task_slots = 0;  // options epa_resume_slots / bvh_task_slots (0: sized by the batch)
-  bool bvh_force_wide = false, pipe_trace = false;   // options bvh_force_wide / pipe_trace
-  bool walk_early_coop = true;                               // HFCL_BVH_WALK_EARLY_COOP: the queries round 0 hands over are continued beside the later rounds
-  // Rounds of walk / leaves / resolve (option bvh_walk_rounds; 0: k_bvh_collide walks the queries, leaves inline).  Not set: chosen per
-  // batch -- ONE round of up to 16 listed leaves and 256 box tests (320 from 120k queries), then the continuation, up to 220k queries
-  // (100k: 1.86 against 1.94 ms with two rounds, 20k: 1.20 against 1.78, 50k: 1.46 against 1.74: a round is as long as its longest lane,
-  // and with the node records kept the lanes carry the walks far enough in one); TWO rounds (6 then 16 leaves; 320 / 640 then 256 box tests)
-  // with the first round's hand-overs continued beside the second above that (250k: 3.32 against 3.36-3.58 ms, 400k: 4.78 against 4.92,
-  // 1M: 9.2 against 10.0 with one round).  profiles/r06_a section 6
-  bool walk_auto = true;
-  uint32_t walk_rounds = 2;
-  uint32_t walk_k[WALK_ROUNDS] = {6, 16, 16, 16};           // option bvh_walk_k: leaves a walk lists per round (setting it switches the automatic choice off)
-  uint32_t walk_budget[WALK_ROUNDS] = {224, 256, 512, 512};  // option bvh_walk_budget: box tests per round from round 1 on before the walk goes to k_bvh_coop
-  size_t bvh_split_n = 0, bvh_split_cap = 0;
-  uint32_t bvh_budget0 = HFCL_BVH_BUDGET0;  // HFCL_BVH_BUDGET0: step budget of the queries (level 0); bvh_budget: of the tasks
-  // No budget given by the environment: chosen per batch.  A batch that does not fill the chip's lanes more than ~1.5
-  // times is a walk with one query per lane whose waves run on with most lanes finished; there the queries are cut at
-  // 512 steps and their remainders spread over levels of small tasks (profiles/r02_w: 100k queries 6.4 -> 5.1 ms,
-  // 10k 4.7 -> 3.4 ms).  A larger batch keeps its lanes busy by refilling and loses with the split (1M: 68 -> 51 M q/s).
-  bool bvh_auto = true;
-  uint32_t bvh_budget = HFCL_BVH_BUDGET, bvh_levels = HFCL_BVH_LEVELS;  // HFCL_BVH_BUDGET / HFCL_BVH_LEVELS (1: unsplit)
-  // contact list of the last hfcl_collide_batch_contacts call
-  hfcl_contact* d_contacts = nullptr;
-  size_t contacts_cap = 0;
-  uint32_t* d_contacts_count = nullptr;
-  BvhParams bvh_params = {1u, nullptr, 0u, nullptr};
-  double break_distance = 1e-3;
-};
 
 static void share_tables(hfcl_lib* h, const hfcl_lib* lib);
 static void free_retired_graphs(hfcl_lib* lib);
@@ -548,23 +218,24 @@ static bool upload_shapes(hfcl_lib* lib, const hfcl_shape* shapes, size_t n_shap
   lib->h_kinds = kinds;
   std::vector<float> v32(3 * n_vertices + 3);
   for (size_t i = 0; i < 3 * n_vertices; ++i) v32[i] = float(vertices[i]);
-  hipFree(lib->d_shapes64); hipFree(lib->d_shapes32); hipFree(lib->d_kinds); hipFree(lib->d_verts64); hipFree(lib->d_verts32);
-  lib->d_shapes64 = nullptr; lib->d_shapes32 = nullptr; lib->d_kinds = nullptr; lib->d_verts64 = nullptr; lib->d_verts32 = nullptr;
+  hfcl_lib::Tables& t = lib->own;
+  reset_all(t.shapes64, t.shapes32, t.kinds, t.verts64, t.verts32);
   bool ok = true;
-  ok = ok && hipMalloc(&lib->d_shapes64, n_shapes * sizeof(DShape<double>)) == hipSuccess;
-  ok = ok && hipMalloc(&lib->d_shapes32, n_shapes * sizeof(DShape<float>)) == hipSuccess;
-  ok = ok && hipMalloc(&lib->d_kinds, n_shapes) == hipSuccess;
-  ok = ok && hipMalloc(&lib->d_verts64, (3 * n_vertices + 3) * sizeof(double)) == hipSuccess;
-  ok = ok && hipMalloc(&lib->d_verts32, (3 * n_vertices + 3) * sizeof(float)) == hipSuccess;
+  ok = ok && t.shapes64.grow(n_shapes) == hipSuccess;
+  ok = ok && t.shapes32.grow(n_shapes) == hipSuccess;
+  ok = ok && t.kinds.grow(n_shapes) == hipSuccess;
+  ok = ok && t.verts64.grow(3 * n_vertices + 3) == hipSuccess;
+  ok = ok && t.verts32.grow(3 * n_vertices + 3) == hipSuccess;
   if (ok) {
-    ok = ok && hipMemcpy(lib->d_shapes64, s64.data(), n_shapes * sizeof(DShape<double>), hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && hipMemcpy(lib->d_shapes32, s32.data(), n_shapes * sizeof(DShape<float>), hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && hipMemcpy(lib->d_kinds, kinds.data(), n_shapes, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(t.shapes64, s64.data(), n_shapes * sizeof(DShape<double>), hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(t.shapes32, s32.data(), n_shapes * sizeof(DShape<float>), hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(t.kinds, kinds.data(), n_shapes, hipMemcpyHostToDevice) == hipSuccess;
     if (n_vertices) {
-      ok = ok && hipMemcpy(lib->d_verts64, vertices, 3 * n_vertices * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-      ok = ok && hipMemcpy(lib->d_verts32, v32.data(), 3 * n_vertices * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+      ok = ok && hipMemcpy(t.verts64, vertices, 3 * n_vertices * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+      ok = ok && hipMemcpy(t.verts32, v32.data(), 3 * n_vertices * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
     }
   }
+  share_tables(lib, lib);  // the library's own view of them
   return ok;
 }
 
@@ -682,8 +353,8 @@ hfcl_lib* hfcl_lib_create(const hfcl_shape* shapes, size_t n_shapes, const doubl
   hfcl_lib* lib = new hfcl_lib();
   lib->device = device;
   bool ok = upload_shapes(lib, shapes, n_shapes, vertices, n_vertices);
-  ok = ok && hipMalloc(&lib->d_counts, N_COUNTERS * sizeof(uint32_t)) == hipSuccess;
-  ok = ok && hipHostMalloc((void**)&lib->h_counts, N_COUNTERS * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess;
+  ok = ok && lib->d_counts.grow(N_COUNTERS) == hipSuccess;
+  ok = ok && lib->h_counts.alloc(N_COUNTERS) == hipSuccess;
   if (ok) memset(lib->h_counts, 0, N_COUNTERS * sizeof(uint32_t));
   if (!ok) {
     set_error("hfcl_lib_create: HIP allocation/copy failed");
@@ -693,7 +364,7 @@ hfcl_lib* hfcl_lib_create(const hfcl_shape* shapes, size_t n_shapes, const doubl
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) lib->n_cus = prop.multiProcessorCount;
   // one slot per lane group of the largest full-capacity EPA grid (run_batch caps grids at n_cus * 16 blocks)
-  if (hipMalloc(&lib->d_epa_v0, size_t(lib->n_cus) * 16 * (64 / EPA_WE2) * EPA_MAX_VERTS * sizeof(Quad<double>)) != hipSuccess) {
+  if (lib->d_epa_v0.grow(size_t(lib->n_cus) * 16 * (64 / EPA_WE2) * EPA_MAX_VERTS * sizeof(Quad<double>)) != hipSuccess) {
     set_error("hfcl_lib_create: HIP allocation failed");
     hfcl_lib_destroy(lib);
     return nullptr;
@@ -708,133 +379,12 @@ hfcl_lib* hfcl_lib_create(const hfcl_shape* shapes, size_t n_shapes, const doubl
   return lib;
 }
 
+// (every buffer, stream and event of the library is a handle that frees itself: hfcl_own.hpp)
 void hfcl_lib_destroy(hfcl_lib* lib) {
   if (!lib) return;
   hipSetDevice(lib->device);
   hipDeviceSynchronize();
   if (lib->helper) hfcl_lib_destroy(lib->helper);
-  if (!lib->is_helper) free_retired_graphs(lib);
-  if (lib->upload_stream) hipStreamDestroy(lib->upload_stream);
-  if (lib->side) hipStreamDestroy(lib->side);
-  if (lib->ev_fork) hipEventDestroy(lib->ev_fork);
-  if (lib->ev_join) hipEventDestroy(lib->ev_join);
-  if (!lib->is_helper) {
-    hipFree(lib->d_shapes64);
-    hipFree(lib->d_shapes32);
-    hipFree(lib->d_kinds);
-    hipFree(lib->d_verts64);
-    hipFree(lib->d_verts32);
-    hipFree(lib->d_graph_base);
-    hipFree(lib->d_graph_off);
-    hipFree(lib->d_graph_ent32);
-    hipFree(lib->d_graph_ent64);
-  }
-  hipFree(lib->d_counts);
-  if (lib->h_counts) hipHostFree(lib->h_counts);
-  hipFree(lib->d_patch_ws);
-  hipFree(lib->d_patch_lists);
-  hipFree(lib->d_patch_counts);
-  if (lib->patch_st) hipStreamDestroy(lib->patch_st);
-  {
-    hfcl_lib::SceneWs& w = lib->scene;
-    hipFree(w.d_s1); hipFree(w.d_s2); hipFree(w.d_tf1); hipFree(w.d_tf2); hipFree(w.d_gin); hipFree(w.d_partials); hipFree(w.d_table); hipFree(w.d_summary);
-    for (int k = 0; k < 2; ++k) {
-      hipFree(w.d_rec[k]);
-      hipFree(w.d_gout[k]);
-      if (w.ev_done[k]) hipEventDestroy(w.ev_done[k]);
-      if (w.ev_copied[k]) hipEventDestroy(w.ev_copied[k]);
-    }
-    if (w.s_cmp) hipStreamDestroy(w.s_cmp);
-    if (w.s_copy) hipStreamDestroy(w.s_copy);
-    if (w.h_counts) hipHostFree(w.h_counts);
-    for (hipEvent_t e : w.ev_counts)
-      if (e) hipEventDestroy(e);
-    hipFree(w.d_boxes); hipFree(w.d_words); hipFree(w.d_block_counts); hipFree(w.d_block_offsets); hipFree(w.d_running); hipFree(w.d_ids);
-    hipFree(w.d_conf_begin);
-  }
-  hipFree(lib->d_local_boxes);
-  hipFree(lib->d_lists);
-  hipFree(lib->d_epa_queue);
-  hipFree(lib->d_epa_queue2);
-  hipFree(lib->d_epa_ready);
-  hipFree(lib->d_epa_ready_g);
-  hipFree(lib->d_epa_cc_over);
-  if (lib->mesh_st) hipStreamDestroy(lib->mesh_st);
-  if (lib->mesh_st2) hipStreamDestroy(lib->mesh_st2);
-  if (lib->mesh_aux) hipStreamDestroy(lib->mesh_aux);
-  for (hipEvent_t e : {lib->ev_mesh_fork, lib->ev_mesh_join, lib->ev_mesh_fork2, lib->ev_mesh_join2})
-    if (e) hipEventDestroy(e);
-  hipFree(lib->d_bvh2_tasks); hipFree(lib->d_bvh2_sums); hipFree(lib->d_bvh2_susp); hipFree(lib->d_bvh2_ctr);
-  for (int k = 0; k < 3; ++k) {
-    if (lib->gjk_st[k]) hipStreamDestroy(lib->gjk_st[k]);
-    if (lib->gjk_join[k]) hipEventDestroy(lib->gjk_join[k]);
-  }
-  if (lib->gjk_fork) hipEventDestroy(lib->gjk_fork);
-  for (int k = 0; k < WALK_ROUNDS - 1; ++k) {
-    if (lib->walk_st[k]) hipStreamDestroy(lib->walk_st[k]);
-    if (lib->walk_fork[k]) hipEventDestroy(lib->walk_fork[k]);
-    if (lib->walk_join[k]) hipEventDestroy(lib->walk_join[k]);
-  }
-  if (lib->aux) hipStreamDestroy(lib->aux);
-  if (lib->ev_aux0) hipEventDestroy(lib->ev_aux0);
-  if (lib->ev_aux1) hipEventDestroy(lib->ev_aux1);
-  if (lib->ev_aux2) hipEventDestroy(lib->ev_aux2);
-  if (lib->ev_aux3) hipEventDestroy(lib->ev_aux3);
-  hipFree(lib->d_epa_resume);
-  hipFree(lib->d_epa_v0);
-  hipFree(lib->d_shape_defer);
-  hipFree(lib->d_shape_oq);
-  hipFree(lib->d_dist_susp);
-  hipFree(lib->d_shape_dist_susp);
-  if (lib->h_pack) hipHostFree(lib->h_pack);
-  if (lib->h_pack_counts) hipHostFree(lib->h_pack_counts);
-  hipFree(lib->d_pack);
-  for (auto& sg : lib->stage) {
-    hipFree(sg.d_s1);
-    hipFree(sg.d_s2);
-    hipFree(sg.d_tf1);
-    hipFree(sg.d_tf2);
-    hipFree(sg.d_qt1);
-    hipFree(sg.d_qt2);
-    hipFree(sg.d_out);
-    hipFree(sg.d_gin);
-    hipFree(sg.d_gout);
-    if (sg.ev_in) hipEventDestroy(sg.ev_in);
-    if (sg.ev_done) hipEventDestroy(sg.ev_done);
-    if (sg.ev_in2) hipEventDestroy(sg.ev_in2);
-    if (sg.h_counts) hipHostFree(sg.h_counts);
-    if (sg.h_counts2) hipHostFree(sg.h_counts2);
-  }
-  if (lib->s_h2d) hipStreamDestroy(lib->s_h2d);
-  if (lib->s_h2d2) hipStreamDestroy(lib->s_h2d2);
-  if (lib->s_cmp) hipStreamDestroy(lib->s_cmp);
-  if (lib->s_d2h) hipStreamDestroy(lib->s_d2h);
-  hipFree(lib->d_nodes64);
-  hipFree(lib->d_nodes32);
-  hipFree(lib->d_fnodes);
-  hipFree(lib->d_rss64);
-  hipFree(lib->d_rss32);
-  hipFree(lib->d_dnodes64);
-  hipFree(lib->d_dnodes32);
-  hipFree(lib->d_bverts64);
-  hipFree(lib->d_bverts32);
-  hipFree(lib->d_btris);
-  hipFree(lib->d_meshes);
-  hipFree(lib->d_contacts);
-  hipFree(lib->d_contacts_count);
-  hipFree(lib->d_bvh_tasks);
-  hipFree(lib->d_bvh_cut_words);
-  hipFree(lib->d_bvh_cut_vals);
-  hipFree(lib->d_bvh_slab);
-  hipFree(lib->d_bvh_sums);
-  hipFree(lib->d_bvh_susp);
-  hipFree(lib->d_bvh_ctr);
-  hipFree(lib->d_walk_recs); hipFree(lib->d_walk_items); hipFree(lib->d_walk_res); hipFree(lib->d_walk_lists); hipFree(lib->d_walk_ctr); hipFree(lib->d_walk_order);
-  hipFree(lib->d_swalk_recs); hipFree(lib->d_swalk_items); hipFree(lib->d_swalk_res); hipFree(lib->d_swalk_lists); hipFree(lib->d_swalk_ctr); hipFree(lib->d_swalk_perm);
-  for (auto& t : lib->timers) {
-    hipEventDestroy(t.e0);
-    hipEventDestroy(t.e1);
-  }
   delete lib;
 }
 // Replace the shape table of a library in place: registered BVH models, workspaces, staging buffers and streams stay
@@ -965,33 +515,24 @@ int hfcl_lib_add_bvh(hfcl_lib* lib, const hfcl_bvh_node* nodes, size_t n_nodes, 
 // for them.  ~0.05 KB per pair without EPA, ~1 KB with (it was 1.8 KB for every library).
 static int ensure_workspace(hfcl_lib* lib, size_t n, bool need_epa) {
   if (n > lib->ws_capacity) {
-    hipFree(lib->d_lists);
-    lib->d_lists = nullptr;
     lib->ws_capacity = 0;
     const size_t cap = n + n / 8 + 1024;
-    HIP_TRY(hipMalloc(&lib->d_lists, size_t(B_COUNT) * cap * sizeof(uint32_t)));
+    HIP_TRY(lib->d_lists.grow(size_t(B_COUNT) * cap));
     lib->ws_capacity = cap;
   }
   if (need_epa && lib->ws_capacity > lib->epa_capacity) {
-    hipFree(lib->d_epa_queue);
-    hipFree(lib->d_epa_queue2);
-    hipFree(lib->d_epa_resume);
-    hipFree(lib->d_epa_cc_over);
-    lib->d_epa_queue = nullptr;
-    lib->d_epa_queue2 = nullptr;
-    lib->d_epa_resume = nullptr;
-    lib->d_epa_cc_over = nullptr;
+    reset_all(lib->d_epa_queue, lib->d_epa_queue2, lib->d_epa_resume, lib->d_epa_cc_over);
     lib->resume_cap = 0;
     lib->epa_capacity = 0;
     const size_t cap = lib->ws_capacity;
-    HIP_TRY(hipMalloc(&lib->d_epa_queue, cap * sizeof(EpaItem<double>)));
-    HIP_TRY(hipMalloc(&lib->d_epa_queue2, cap * sizeof(EpaItem<double>)));
+    HIP_TRY(lib->d_epa_queue.grow(cap * sizeof(EpaItem<double>)));
+    HIP_TRY(lib->d_epa_queue2.grow(cap * sizeof(EpaItem<double>)));
     // saved polytopes for the tier hand-over: room for an eighth of the batch (cfg5: 4 % of the pairs outgrow the fast
     // tier; beyond the area the full tier simply redoes the pair from its seed)
     size_t rcap = std::min(cap, std::max<size_t>(65536, cap / 8));
     if (lib->epa_resume_slots) rcap = std::max<size_t>(1, std::min<size_t>(cap, lib->epa_resume_slots));  // test knob (option epa_resume_slots)
-    HIP_TRY(hipMalloc(&lib->d_epa_resume, rcap * std::max(epa_resume_stride<double>, epa_resume_stride<float>)));
-    HIP_TRY(hipMalloc((void**)&lib->d_epa_cc_over, rcap * sizeof(uint32_t)));
+    HIP_TRY(lib->d_epa_resume.grow(rcap * std::max(epa_resume_stride<double>, epa_resume_stride<float>)));
+    HIP_TRY(lib->d_epa_cc_over.grow(rcap));
     lib->resume_cap = rcap;
     lib->epa_capacity = cap;
   }
@@ -1002,18 +543,17 @@ static int ensure_workspace(hfcl_lib* lib, size_t n, bool need_epa) {
 // with a stack of ~20 entries, one query in five is long; mesh x solid walks are cut finer) -- ~2.4 KB of device memory per query in fp64.
 static int ensure_bvh_split(hfcl_lib* lib, size_t n) {
   if (n <= lib->bvh_split_n) return HFCL_OK;
-  hipFree(lib->d_bvh_tasks); hipFree(lib->d_bvh_sums); hipFree(lib->d_bvh_susp); hipFree(lib->d_bvh_cut_words); hipFree(lib->d_bvh_cut_vals);
-  lib->d_bvh_tasks = nullptr; lib->d_bvh_sums = nullptr; lib->d_bvh_susp = nullptr; lib->d_bvh_cut_words = nullptr; lib->d_bvh_cut_vals = nullptr;
+  reset_all(lib->d_bvh_tasks, lib->d_bvh_sums, lib->d_bvh_susp, lib->d_bvh_cut_words, lib->d_bvh_cut_vals);
   lib->bvh_split_n = 0;
   size_t per_query = 16;
   if (lib->bvh_task_slots) per_query = std::max<size_t>(1, lib->bvh_task_slots);  // test / tuning knob (option bvh_task_slots)
   const size_t nq = n + n / 8 + 1024, cap = per_query * nq + 65536;
-  HIP_TRY(hipMalloc(&lib->d_bvh_tasks, cap * sizeof(BvhTask)));
-  HIP_TRY(hipMalloc(&lib->d_bvh_sums, (nq + cap) * sizeof(BvhSum<double>)));
-  HIP_TRY(hipMalloc(&lib->d_bvh_cut_words, cap * sizeof(uint32_t)));
-  HIP_TRY(hipMalloc(&lib->d_bvh_cut_vals, cap * sizeof(double)));
-  HIP_TRY(hipMalloc(&lib->d_bvh_susp, nq * sizeof(uint32_t)));
-  if (!lib->d_bvh_ctr) HIP_TRY(hipMalloc(&lib->d_bvh_ctr, BVH_CTR_WORDS * sizeof(uint32_t)));
+  HIP_TRY(lib->d_bvh_tasks.grow(cap));
+  HIP_TRY(lib->d_bvh_sums.grow((nq + cap) * sizeof(BvhSum<double>)));
+  HIP_TRY(lib->d_bvh_cut_words.grow(cap));
+  HIP_TRY(lib->d_bvh_cut_vals.grow(cap));
+  HIP_TRY(lib->d_bvh_susp.grow(nq));
+  HIP_TRY(lib->d_bvh_ctr.grow(BVH_CTR_WORDS));
   lib->bvh_split_n = nq;
   lib->bvh_split_cap = cap;
   return HFCL_OK;
@@ -1021,33 +561,30 @@ static int ensure_bvh_split(hfcl_lib* lib, size_t n) {
 
 static int ensure_walk(hfcl_lib* lib, size_t n) {
   if (n <= lib->walk_n) return HFCL_OK;
-  hipFree(lib->d_walk_recs); hipFree(lib->d_walk_items); hipFree(lib->d_walk_res); hipFree(lib->d_walk_lists); hipFree(lib->d_walk_order);
-  lib->d_walk_order = nullptr;
-  lib->d_walk_recs = nullptr; lib->d_walk_items = nullptr; lib->d_walk_res = nullptr; lib->d_walk_lists = nullptr;
+  reset_all(lib->d_walk_recs, lib->d_walk_items, lib->d_walk_res, lib->d_walk_lists, lib->d_walk_order);
   lib->walk_n = 0;
   const size_t nq = n + n / 8 + 1024;
-  HIP_TRY(hipMalloc(&lib->d_walk_recs, nq * sizeof(WalkRec<double>)));
-  HIP_TRY(hipMalloc(&lib->d_walk_items, nq * WALK_K * sizeof(uint32_t)));
-  HIP_TRY(hipMalloc(&lib->d_walk_res, nq * WALK_K * 10 * sizeof(double)));  // TriLeafOut<double>: distance, p1, p2, n
-  HIP_TRY(hipMalloc(&lib->d_walk_lists, 2 * nq * sizeof(uint32_t)));
-  HIP_TRY(hipMalloc(&lib->d_walk_order, nq * sizeof(uint32_t)));
-  if (!lib->d_walk_ctr) HIP_TRY(hipMalloc(&lib->d_walk_ctr, 8 * WALK_ROUNDS * sizeof(uint32_t)));
+  HIP_TRY(lib->d_walk_recs.grow(nq * sizeof(WalkRec<double>)));
+  HIP_TRY(lib->d_walk_items.grow(nq * WALK_K));
+  HIP_TRY(lib->d_walk_res.grow(nq * WALK_K * 10 * sizeof(double)));  // TriLeafOut<double>: distance, p1, p2, n
+  HIP_TRY(lib->d_walk_lists.grow(2 * nq));
+  HIP_TRY(lib->d_walk_order.grow(nq));
+  HIP_TRY(lib->d_walk_ctr.grow(8 * WALK_ROUNDS));
   lib->walk_n = nq;
   return HFCL_OK;
 }
 
 static int ensure_swalk(hfcl_lib* lib, size_t n) {
   if (n <= lib->swalk_n) return HFCL_OK;
-  hipFree(lib->d_swalk_recs); hipFree(lib->d_swalk_items); hipFree(lib->d_swalk_res); hipFree(lib->d_swalk_lists); hipFree(lib->d_swalk_perm);
-  lib->d_swalk_recs = nullptr; lib->d_swalk_items = nullptr; lib->d_swalk_res = nullptr; lib->d_swalk_lists = nullptr; lib->d_swalk_perm = nullptr;
+  reset_all(lib->d_swalk_recs, lib->d_swalk_items, lib->d_swalk_res, lib->d_swalk_lists, lib->d_swalk_perm);
   lib->swalk_n = 0;
   const size_t nq = n + n / 8 + 1024;
-  HIP_TRY(hipMalloc(&lib->d_swalk_recs, nq * sizeof(WalkRec<double>)));
-  HIP_TRY(hipMalloc(&lib->d_swalk_items, nq * WALK_K * sizeof(uint32_t)));
-  HIP_TRY(hipMalloc(&lib->d_swalk_res, nq * WALK_K * 10 * sizeof(double)));  // TriLeafOut<double>: distance, p1, p2, n
-  HIP_TRY(hipMalloc(&lib->d_swalk_lists, 3 * nq * sizeof(uint32_t)));
-  HIP_TRY(hipMalloc(&lib->d_swalk_perm, (nq * WALK_K + nq) * sizeof(uint32_t)));
-  if (!lib->d_swalk_ctr) HIP_TRY(hipMalloc(&lib->d_swalk_ctr, (8 * WALK_ROUNDS + 64) * sizeof(uint32_t)));
+  HIP_TRY(lib->d_swalk_recs.grow(nq * sizeof(WalkRec<double>)));
+  HIP_TRY(lib->d_swalk_items.grow(nq * WALK_K));
+  HIP_TRY(lib->d_swalk_res.grow(nq * WALK_K * 10 * sizeof(double)));  // TriLeafOut<double>: distance, p1, p2, n
+  HIP_TRY(lib->d_swalk_lists.grow(3 * nq));
+  HIP_TRY(lib->d_swalk_perm.grow(nq * WALK_K + nq));
+  HIP_TRY(lib->d_swalk_ctr.grow(8 * WALK_ROUNDS + 64));
   lib->swalk_n = nq;
   return HFCL_OK;
 }
@@ -1067,13 +604,7 @@ static int make_bvh_spill(hfcl_lib* lib, BvhSpill& sp, bool distance) {
   const size_t per_block = size_t(BVH_BLOCK) * cap * 2 * sizeof(uint64_t);  // (entry, bound) records: k_bvh_distance
   size_t blocks = std::min<size_t>(size_t(lib->n_cus) * 16, std::max<size_t>(1, (size_t(2) << 30) / per_block));
   const size_t bytes = blocks * per_block;
-  if (bytes > lib->bvh_slab_bytes) {
-    hipFree(lib->d_bvh_slab);
-    lib->d_bvh_slab = nullptr;
-    lib->bvh_slab_bytes = 0;
-    HIP_TRY(hipMalloc(&lib->d_bvh_slab, bytes));
-    lib->bvh_slab_bytes = bytes;
-  }
+  HIP_TRY(lib->d_bvh_slab.grow(bytes));
   sp.slab = lib->d_bvh_slab;
   sp.cap = uint32_t(cap);
   sp.max_blocks = uint32_t(blocks);
@@ -1098,27 +629,24 @@ static DNode<T> pack_node(const hfcl_bvh_node& n) {
 // d_graph_off, the neighbours with their coordinates inline in d_graph_ent32/64 (one fetch per hop instead of two).
 // The warm-start vertices are the support vertices along the 14 directions of ConvexBase::buildSupportWarmStart
 // (src/shape/geometric_shapes.cpp: the six axis directions and the eight cube diagonals).
-static void free_retired_graphs(hfcl_lib* lib) {  // (the caller has waited for the device)
-  for (void* p : lib->graph_retired) hipFree(p);
-  lib->graph_retired.clear();
-}
+static void free_retired_graphs(hfcl_lib* lib) { lib->graph_retired.clear(); }  // (the caller has waited for the device)
 // No device-wide wait (round 4): the previous image is retired, not freed, the new one is copied on a non-blocking stream
-// of its own and the host waits for that stream only -- hipFree and the null-stream hipMemcpy the first version used both
+// of its own and the host waits for that stream only -- freeing it and the null-stream hipMemcpy the first version used both
 // stall every stream of the device, inside an entry point documented as asynchronous.
-static int upload_graph(hfcl_lib* lib) {
+int upload_graph(hfcl_lib* lib) {
   if (!lib->graph_dirty) return HFCL_OK;
   HIP_TRY(hipSetDevice(lib->device));
   // (an application that re-registers neighbours between batches must not grow device memory without bound: after four retired
   // images the device is waited for once and they are freed)
-  if (lib->graph_retired.size() >= 16) {
+  if (lib->graph_retired.size() >= 4) {
     HIP_TRY(hipDeviceSynchronize());
     free_retired_graphs(lib);
   }
-  for (void* p : {(void*)lib->d_graph_base, (void*)lib->d_graph_off, (void*)lib->d_graph_ent32, (void*)lib->d_graph_ent64})
-    if (p) lib->graph_retired.push_back(p);
-  lib->d_graph_base = nullptr; lib->d_graph_off = nullptr; lib->d_graph_ent32 = nullptr; lib->d_graph_ent64 = nullptr;
+  hfcl_lib::GraphImage& img = lib->own.graph;
+  if (img.base) lib->graph_retired.push_back(std::move(img));  // (an image is whole or not there at all; moved from, it is empty)
   lib->graph_dirty = false;
   if (lib->h_graphs.empty()) {
+    share_tables(lib, lib);
     if (lib->helper) share_tables(lib->helper, lib);
     return HFCL_OK;
   }
@@ -1161,38 +689,34 @@ static int upload_graph(hfcl_lib* lib) {
       e32.push_back(b);
     }
   }
-  bool ok = hipMalloc(&lib->d_graph_base, base.size() * sizeof(uint32_t)) == hipSuccess;
-  ok = ok && hipMalloc(&lib->d_graph_off, off.size() * sizeof(uint32_t)) == hipSuccess;
-  ok = ok && hipMalloc(&lib->d_graph_ent32, (e32.size() + 1) * sizeof(NbrEntry<float>)) == hipSuccess;
-  ok = ok && hipMalloc(&lib->d_graph_ent64, (e64.size() + 1) * sizeof(NbrEntry<double>)) == hipSuccess;
-  if (!lib->upload_stream) ok = ok && hipStreamCreateWithFlags(&lib->upload_stream, hipStreamNonBlocking) == hipSuccess;
+  bool ok = img.base.grow(base.size()) == hipSuccess;
+  ok = ok && img.off.grow(off.size()) == hipSuccess;
+  ok = ok && img.ent32.grow(e32.size() + 1) == hipSuccess;
+  ok = ok && img.ent64.grow(e64.size() + 1) == hipSuccess;
+  if (!lib->upload_stream) ok = ok && lib->upload_stream.create() == hipSuccess;
   hipStream_t us = lib->upload_stream;
-  ok = ok && hipMemcpyAsync(lib->d_graph_base, base.data(), base.size() * sizeof(uint32_t), hipMemcpyHostToDevice, us) == hipSuccess;
-  ok = ok && hipMemcpyAsync(lib->d_graph_off, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, us) == hipSuccess;
-  ok = ok && (e32.empty() || hipMemcpyAsync(lib->d_graph_ent32, e32.data(), e32.size() * sizeof(NbrEntry<float>), hipMemcpyHostToDevice, us) == hipSuccess);
-  ok = ok && (e64.empty() || hipMemcpyAsync(lib->d_graph_ent64, e64.data(), e64.size() * sizeof(NbrEntry<double>), hipMemcpyHostToDevice, us) == hipSuccess);
+  ok = ok && hipMemcpyAsync(img.base, base.data(), base.size() * sizeof(uint32_t), hipMemcpyHostToDevice, us) == hipSuccess;
+  ok = ok && hipMemcpyAsync(img.off, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, us) == hipSuccess;
+  ok = ok && (e32.empty() || hipMemcpyAsync(img.ent32, e32.data(), e32.size() * sizeof(NbrEntry<float>), hipMemcpyHostToDevice, us) == hipSuccess);
+  ok = ok && (e64.empty() || hipMemcpyAsync(img.ent64, e64.data(), e64.size() * sizeof(NbrEntry<double>), hipMemcpyHostToDevice, us) == hipSuccess);
   ok = ok && hipStreamSynchronize(us) == hipSuccess;  // the host vectors go out of scope; kernels launched after this see the image
   if (!ok) {  // nothing half-built stays behind: the next batch retries the upload from the host copies
-    hipFree(lib->d_graph_base); hipFree(lib->d_graph_off); hipFree(lib->d_graph_ent32); hipFree(lib->d_graph_ent64);
-    lib->d_graph_base = nullptr; lib->d_graph_off = nullptr; lib->d_graph_ent32 = nullptr; lib->d_graph_ent64 = nullptr;
+    img = hfcl_lib::GraphImage();
     lib->graph_dirty = true;
+    share_tables(lib, lib);
     if (lib->helper) share_tables(lib->helper, lib);
     set_error("vertex adjacency: HIP allocation/copy failed");
     return HFCL_ERR_HIP;
   }
+  share_tables(lib, lib);
   if (lib->helper) share_tables(lib->helper, lib);
   return HFCL_OK;
 }
 
 static int upload_bvh(hfcl_lib* lib) {
   if (!lib->bvh_dirty) return HFCL_OK;
-  hipFree(lib->d_nodes64); hipFree(lib->d_nodes32); hipFree(lib->d_bverts64); hipFree(lib->d_bverts32);
-  hipFree(lib->d_btris); hipFree(lib->d_meshes); hipFree(lib->d_rss64); hipFree(lib->d_rss32); hipFree(lib->d_fnodes);
-  hipFree(lib->d_dnodes64); hipFree(lib->d_dnodes32);
-  lib->d_dnodes64 = nullptr; lib->d_dnodes32 = nullptr;
-  lib->d_rss64 = nullptr; lib->d_rss32 = nullptr; lib->d_fnodes = nullptr;
-  lib->d_nodes64 = nullptr; lib->d_nodes32 = nullptr; lib->d_bverts64 = nullptr; lib->d_bverts32 = nullptr;
-  lib->d_btris = nullptr; lib->d_meshes = nullptr;
+  reset_all(lib->d_nodes64, lib->d_nodes32, lib->d_bverts64, lib->d_bverts32, lib->d_btris, lib->d_meshes, lib->d_rss64, lib->d_rss32,
+            lib->d_fnodes, lib->d_dnodes64, lib->d_dnodes32);
   const size_t nn = lib->h_bvh_nodes.size(), nv = lib->h_bvh_verts.size(), nt = lib->h_bvh_tris.size();
   std::vector<DNode<double>> n64(nn);
   std::vector<DNode<float>> n32(nn);
@@ -1219,7 +743,7 @@ static int upload_bvh(hfcl_lib* lib) {
     obbf_size_ranks(lib->h_bvh_nodes.data(), nn, rank.data());
     std::vector<DNodeF> fn(nn);
     for (size_t i = 0; i < nn; ++i) fn[i] = pack_fnode(lib->h_bvh_nodes[i], rank[i]);
-    HIP_TRY(hipMalloc(&lib->d_fnodes, nn * sizeof(DNodeF)));
+    HIP_TRY(lib->d_fnodes.grow(nn));
     HIP_TRY(hipMemcpy(lib->d_fnodes, fn.data(), nn * sizeof(DNodeF), hipMemcpyHostToDevice));
     // the distance() walk's records: axes + RSS + child link + the same ranks
     std::vector<DNodeD<double>> d64(nn);
@@ -1230,21 +754,21 @@ static int upload_bvh(hfcl_lib* lib) {
       d32[i].axes = n32[i].axes; d32[i].Tr = r32[i].Tr; d32[i].l0 = r32[i].l0; d32[i].l1 = r32[i].l1; d32[i].r = r32[i].r;
       d32[i].first_child = n32[i].first_child; d32[i].rank = rank[i];
     }
-    HIP_TRY(hipMalloc(&lib->d_dnodes64, nn * sizeof(DNodeD<double>)));
-    HIP_TRY(hipMalloc(&lib->d_dnodes32, nn * sizeof(DNodeD<float>)));
+    HIP_TRY(lib->d_dnodes64.grow(nn));
+    HIP_TRY(lib->d_dnodes32.grow(nn));
     HIP_TRY(hipMemcpy(lib->d_dnodes64, d64.data(), nn * sizeof(DNodeD<double>), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(lib->d_dnodes32, d32.data(), nn * sizeof(DNodeD<float>), hipMemcpyHostToDevice));
   }
-  HIP_TRY(hipMalloc(&lib->d_nodes64, nn * sizeof(DNode<double>)));
-  HIP_TRY(hipMalloc(&lib->d_nodes32, nn * sizeof(DNode<float>)));
-  HIP_TRY(hipMalloc(&lib->d_bverts64, nv * sizeof(double)));
-  HIP_TRY(hipMalloc(&lib->d_bverts32, nv * sizeof(float)));
-  HIP_TRY(hipMalloc(&lib->d_btris, nt * sizeof(uint32_t)));
-  HIP_TRY(hipMalloc(&lib->d_meshes, lib->h_meshes.size() * sizeof(DMesh)));
+  HIP_TRY(lib->d_nodes64.grow(nn));
+  HIP_TRY(lib->d_nodes32.grow(nn));
+  HIP_TRY(lib->d_bverts64.grow(nv));
+  HIP_TRY(lib->d_bverts32.grow(nv));
+  HIP_TRY(lib->d_btris.grow(nt));
+  HIP_TRY(lib->d_meshes.grow(lib->h_meshes.size()));
   HIP_TRY(hipMemcpy(lib->d_nodes64, n64.data(), nn * sizeof(DNode<double>), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(lib->d_nodes32, n32.data(), nn * sizeof(DNode<float>), hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&lib->d_rss64, nn * sizeof(DRss<double>)));
-  HIP_TRY(hipMalloc(&lib->d_rss32, nn * sizeof(DRss<float>)));
+  HIP_TRY(lib->d_rss64.grow(nn));
+  HIP_TRY(lib->d_rss32.grow(nn));
   HIP_TRY(hipMemcpy(lib->d_rss64, r64.data(), nn * sizeof(DRss<double>), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(lib->d_rss32, r32.data(), nn * sizeof(DRss<float>), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(lib->d_bverts64, lib->h_bvh_verts.data(), nv * sizeof(double), hipMemcpyHostToDevice));
@@ -1255,14 +779,14 @@ static int upload_bvh(hfcl_lib* lib) {
   return HFCL_OK;
 }
 
-static KernelTime* timer_slot(hfcl_lib* lib, size_t i, const char* name) {
+KernelTime* timer_slot(hfcl_lib* lib, size_t i, const char* name) {
   while (lib->timers.size() <= i) {
     KernelTime t;
     t.name = "";
     t.used = false;
-    hipEventCreate(&t.e0);
-    hipEventCreate(&t.e1);
-    lib->timers.push_back(t);
+    (void)t.e0.create(hipEventDefault);
+    (void)t.e1.create(hipEventDefault);
+    lib->timers.push_back(std::move(t));
   }
   lib->timers[i].name = name;
   lib->timers[i].used = true;
@@ -1313,107 +837,76 @@ static int validate_query(const hfcl_query_request& q) {
 static int ensure_aux(hfcl_lib* lib) {
   if (lib->aux) return HFCL_OK;
   // created into locals and committed together: a failure half way leaves the library without a helper stream, not with null events
-  hipStream_t s = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-  for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&ev[k], hipEventDisableTiming);
-  if (e != hipSuccess) {
-    for (int k = 0; k < 4; ++k)
-      if (ev[k]) hipEventDestroy(ev[k]);
-    if (s) hipStreamDestroy(s);
-    HIP_TRY(e);
-  }
-  lib->ev_aux0 = ev[0];
-  lib->ev_aux1 = ev[1];
-  lib->ev_aux2 = ev[2];
-  lib->ev_aux3 = ev[3];
-  lib->aux = s;
+  Stream s;
+  Event ev[4];
+  HIP_TRY(s.create());
+  for (Event& e : ev) HIP_TRY(e.create());
+  lib->ev_aux0 = std::move(ev[0]);
+  lib->ev_aux1 = std::move(ev[1]);
+  lib->ev_aux2 = std::move(ev[2]);
+  lib->ev_aux3 = std::move(ev[3]);
+  lib->aux = std::move(s);
   return HFCL_OK;
 }
 static int ensure_mesh_stream(hfcl_lib* lib) {
   if (lib->mesh_st) return HFCL_OK;  // (committed last)
-  hipStream_t st[3] = {nullptr, nullptr, nullptr};
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipError_t e = hipSuccess;
+  Stream st[3];
+  Event ev[4];
   // option mesh_prio: [0] the mesh x solid walks and [2] their helper at the device's highest priority -- hardware queues of their own (the runtime
   // maps the streams of one priority onto four queues; two chains that share one run one after the other): cfgmix 2.90 -> 2.72 ms, but a process
   // that has created them runs cfg4s's in-line batches 1 ms slower (3.7 against 2.65 ms; profiles/r06_g).  Off.
   int prio_lo = 0, prio_hi = 0;
   if (lib->mesh_prio) (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-  for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipStreamCreateWithPriority(&st[k], hipStreamNonBlocking, k == 1 ? 0 : prio_hi);
-  for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&ev[k], hipEventDisableTiming);
-  if (e != hipSuccess) {
-    for (hipEvent_t x : ev)
-      if (x) hipEventDestroy(x);
-    for (hipStream_t x : st)
-      if (x) hipStreamDestroy(x);
-    HIP_TRY(e);
-  }
-  lib->ev_mesh_fork = ev[0];
-  lib->ev_mesh_join = ev[1];
-  lib->ev_mesh_fork2 = ev[2];
-  lib->ev_mesh_join2 = ev[3];
-  lib->mesh_st2 = st[1];
-  lib->mesh_aux = st[2];
-  lib->mesh_st = st[0];
+  for (int k = 0; k < 3; ++k) HIP_TRY(st[k].create_with_priority(k == 1 ? 0 : prio_hi));
+  for (Event& e : ev) HIP_TRY(e.create());
+  lib->ev_mesh_fork = std::move(ev[0]);
+  lib->ev_mesh_join = std::move(ev[1]);
+  lib->ev_mesh_fork2 = std::move(ev[2]);
+  lib->ev_mesh_join2 = std::move(ev[3]);
+  lib->mesh_st2 = std::move(st[1]);
+  lib->mesh_aux = std::move(st[2]);
+  lib->mesh_st = std::move(st[0]);
   return HFCL_OK;
 }
 // the second set of split-traversal tables (what k_bvh_walk / k_bvh_resolve / k_bvh_coop use of them: tasks, summaries, suspended list,
 // counters): the mesh x mesh walks of a batch that also holds mesh x solid pairs run beside those on these
 static int ensure_bvh_split2(hfcl_lib* lib, size_t n) {
   if (n <= lib->bvh2_split_n) return HFCL_OK;
-  hipFree(lib->d_bvh2_tasks); hipFree(lib->d_bvh2_sums); hipFree(lib->d_bvh2_susp);
-  lib->d_bvh2_tasks = nullptr; lib->d_bvh2_sums = nullptr; lib->d_bvh2_susp = nullptr;
+  reset_all(lib->d_bvh2_tasks, lib->d_bvh2_sums, lib->d_bvh2_susp);
   lib->bvh2_split_n = 0;
   const size_t nq = n + n / 8 + 1024, cap = 16 * nq + 65536;
-  HIP_TRY(hipMalloc(&lib->d_bvh2_tasks, cap * sizeof(BvhTask)));
-  HIP_TRY(hipMalloc(&lib->d_bvh2_sums, (nq + cap) * sizeof(BvhSum<double>)));
-  HIP_TRY(hipMalloc(&lib->d_bvh2_susp, nq * sizeof(uint32_t)));
-  if (!lib->d_bvh2_ctr) HIP_TRY(hipMalloc(&lib->d_bvh2_ctr, BVH_CTR_WORDS * sizeof(uint32_t)));
+  HIP_TRY(lib->d_bvh2_tasks.grow(cap));
+  HIP_TRY(lib->d_bvh2_sums.grow((nq + cap) * sizeof(BvhSum<double>)));
+  HIP_TRY(lib->d_bvh2_susp.grow(nq));
+  HIP_TRY(lib->d_bvh2_ctr.grow(BVH_CTR_WORDS));
   lib->bvh2_split_n = nq;
   lib->bvh2_split_cap = cap;
   return HFCL_OK;
 }
 static int ensure_walk_streams(hfcl_lib* lib) {
   if (lib->walk_st[WALK_ROUNDS - 2]) return HFCL_OK;  // (committed last)
-  hipStream_t s[WALK_ROUNDS - 1] = {};
-  hipEvent_t ev[2 * (WALK_ROUNDS - 1)] = {};
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < WALK_ROUNDS - 1 && e == hipSuccess; ++k) e = hipStreamCreateWithFlags(&s[k], hipStreamNonBlocking);
-  for (int k = 0; k < 2 * (WALK_ROUNDS - 1) && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&ev[k], hipEventDisableTiming);
-  if (e != hipSuccess) {
-    for (auto x : ev)
-      if (x) hipEventDestroy(x);
-    for (auto x : s)
-      if (x) hipStreamDestroy(x);
-    HIP_TRY(e);
-  }
+  Stream s[WALK_ROUNDS - 1];
+  Event ev[2 * (WALK_ROUNDS - 1)];
+  for (Stream& x : s) HIP_TRY(x.create());
+  for (Event& e : ev) HIP_TRY(e.create());
   for (int k = 0; k < WALK_ROUNDS - 1; ++k) {
-    lib->walk_fork[k] = ev[2 * k];
-    lib->walk_join[k] = ev[2 * k + 1];
+    lib->walk_fork[k] = std::move(ev[2 * k]);
+    lib->walk_join[k] = std::move(ev[2 * k + 1]);
   }
-  for (int k = 0; k < WALK_ROUNDS - 1; ++k) lib->walk_st[k] = s[k];
+  for (int k = 0; k < WALK_ROUNDS - 1; ++k) lib->walk_st[k] = std::move(s[k]);
   return HFCL_OK;
 }
 static int ensure_gjk_streams(hfcl_lib* lib) {
   if (lib->gjk_fork) return HFCL_OK;  // (committed last)
-  hipStream_t s[3] = {nullptr, nullptr, nullptr};
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipStreamCreateWithFlags(&s[k], hipStreamNonBlocking);
-  for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&ev[k], hipEventDisableTiming);
-  if (e != hipSuccess) {
-    for (auto x : ev)
-      if (x) hipEventDestroy(x);
-    for (auto x : s)
-      if (x) hipStreamDestroy(x);
-    HIP_TRY(e);
-  }
+  Stream s[3];
+  Event ev[4];
+  for (Stream& x : s) HIP_TRY(x.create());
+  for (Event& e : ev) HIP_TRY(e.create());
   for (int k = 0; k < 3; ++k) {
-    lib->gjk_st[k] = s[k];
-    lib->gjk_join[k] = ev[k];
+    lib->gjk_st[k] = std::move(s[k]);
+    lib->gjk_join[k] = std::move(ev[k]);
   }
-  lib->gjk_fork = ev[3];
+  lib->gjk_fork = std::move(ev[3]);
   return HFCL_OK;
 }
 template <typename T, int M>
@@ -1615,11 +1108,11 @@ static int run_batch_one(hfcl_lib* lib, const uint32_t* d_s1, const uint32_t* d_
       rc = upload_bvh(lib);
       if (rc) return rc;
       BvhView<T> bv;
-      bv.nodes = std::is_same<T, double>::value ? (const DNode<T>*)lib->d_nodes64 : (const DNode<T>*)lib->d_nodes32;
+      bv.nodes = std::is_same<T, double>::value ? (const DNode<T>*)lib->d_nodes64.get() : (const DNode<T>*)lib->d_nodes32.get();
       bv.fnodes = (std::is_same<T, double>::value && lib->bvh_filter) ? lib->d_fnodes : nullptr;
-      bv.rss = std::is_same<T, double>::value ? (const DRss<T>*)lib->d_rss64 : (const DRss<T>*)lib->d_rss32;
-      bv.dnodes = std::is_same<T, double>::value ? (const DNodeD<T>*)lib->d_dnodes64 : (const DNodeD<T>*)lib->d_dnodes32;
-      bv.verts = std::is_same<T, double>::value ? (const T*)lib->d_bverts64 : (const T*)lib->d_bverts32;
+      bv.rss = std::is_same<T, double>::value ? (const DRss<T>*)lib->d_rss64.get() : (const DRss<T>*)lib->d_rss32.get();
+      bv.dnodes = std::is_same<T, double>::value ? (const DNodeD<T>*)lib->d_dnodes64.get() : (const DNodeD<T>*)lib->d_dnodes32.get();
+      bv.verts = std::is_same<T, double>::value ? (const T*)lib->d_bverts64.get() : (const T*)lib->d_bverts32.get();
       bv.tris = lib->d_btris;
       bv.meshes = lib->d_meshes;
       bv.n_meshes = uint32_t(lib->h_meshes.size());
@@ -1731,24 +1224,14 @@ static int run_batch_one(hfcl_lib* lib, const uint32_t* d_s1, const uint32_t* d_
           if (rc) return rc;
           need = std::max(need, n + lib->bvh_split_cap);
         }
-        if (need > lib->shape_defer_capacity) {
-          hipFree(lib->d_shape_defer);
-          lib->d_shape_defer = nullptr;
-          lib->shape_defer_capacity = 0;
-          HIP_TRY(hipMalloc(&lib->d_shape_defer, need * (sizeof(ShapeDeferItem<double>) + 2 * sizeof(uint32_t))));  // (+ the two lists of k_bvh_shape_finish's second tier)
-          lib->shape_defer_capacity = need;
-        }
+        constexpr size_t DEFER_ITEM = sizeof(ShapeDeferItem<double>) + 2 * sizeof(uint32_t);  // (+ the two lists of k_bvh_shape_finish's second tier)
+        HIP_TRY(lib->d_shape_defer.grow(need * DEFER_ITEM));
+        const size_t defer_cap = lib->d_shape_defer.capacity() / DEFER_ITEM;
         // (the solids' boxes are indexed by pair: one per pair of the workspace, not one per EPA item -- 1M pairs: 0.14 GB instead of 0.7)
-        if (lib->ws_capacity > lib->shape_oq_capacity) {
-          hipFree(lib->d_shape_oq);
-          lib->d_shape_oq = nullptr;
-          lib->shape_oq_capacity = 0;
-          HIP_TRY(hipMalloc(&lib->d_shape_oq, lib->ws_capacity * std::max(sizeof(ObbQuery<double>), sizeof(RssQuery<double>))));
-          lib->shape_oq_capacity = lib->ws_capacity;
-        }
+        HIP_TRY(lib->d_shape_oq.grow(lib->ws_capacity * std::max(sizeof(ObbQuery<double>), sizeof(RssQuery<double>))));
         wk.shape_defer = lib->d_shape_defer;
-        wk.shape_defer_cap = uint32_t(std::min<size_t>(lib->shape_defer_capacity, 0xFFFFFFFFu));
-        wk.shape_finish_over = lib->shape_finish_tiers ? reinterpret_cast<uint32_t*>(static_cast<char*>(lib->d_shape_defer) + lib->shape_defer_capacity * sizeof(ShapeDeferItem<double>)) : nullptr;
+        wk.shape_defer_cap = uint32_t(std::min<size_t>(defer_cap, 0xFFFFFFFFu));
+        wk.shape_finish_over = lib->shape_finish_tiers ? reinterpret_cast<uint32_t*>(static_cast<char*>(lib->d_shape_defer.get()) + defer_cap * sizeof(ShapeDeferItem<double>)) : nullptr;
         wk.shape_oq = lib->d_shape_oq;
       }
       if (q.mode == 1) {
@@ -1820,13 +1303,7 @@ static int run_batch_one(hfcl_lib* lib, const uint32_t* d_s1, const uint32_t* d_
           BvhSpill ss;
           memset(&ss, 0, sizeof(ss));
           if (lib->shape_dist_budget && q.guess_mode != HFCL_GUESS_CACHED && !io.gout) {
-            if (lib->ws_capacity > lib->shape_dist_susp_capacity) {
-              hipFree(lib->d_shape_dist_susp);
-              lib->d_shape_dist_susp = nullptr;
-              lib->shape_dist_susp_capacity = 0;
-              HIP_TRY(hipMalloc(&lib->d_shape_dist_susp, lib->ws_capacity * sizeof(ShapeDistSusp<double>)));
-              lib->shape_dist_susp_capacity = lib->ws_capacity;
-            }
+            HIP_TRY(lib->d_shape_dist_susp.grow(lib->ws_capacity * sizeof(ShapeDistSusp<double>)));
             ss.susp = lib->d_shape_dist_susp;
             ss.rerun_count = lib->pool_rerun ? lib->d_counts + CTR_SHAPE_DIST_RERUN : nullptr;
             ss.rerun_all = lib->pool_rerun >= 2 ? 1u : 0u;
@@ -1845,13 +1322,7 @@ static int run_batch_one(hfcl_lib* lib, const uint32_t* d_s1, const uint32_t* d_
         tend();
         tbeg("k_bvh_distance");
         if (may(B_BVH) && !spill.wide && lib->bvhd_budget) {
-          if (lib->ws_capacity > lib->dist_susp_capacity) {
-            hipFree(lib->d_dist_susp);
-            lib->d_dist_susp = nullptr;
-            lib->dist_susp_capacity = 0;
-            HIP_TRY(hipMalloc(&lib->d_dist_susp, lib->ws_capacity * sizeof(DistSusp<double>)));
-            lib->dist_susp_capacity = lib->ws_capacity;
-          }
+          HIP_TRY(lib->d_dist_susp.grow(lib->ws_capacity * sizeof(DistSusp<double>)));
           spill.susp = lib->d_dist_susp;
           spill.rerun_count = lib->pool_rerun ? lib->d_counts + CTR_DIST_RERUN : nullptr;
           spill.rerun_all = lib->pool_rerun >= 2 ? 1u : 0u;
@@ -1937,23 +1408,11 @@ static int run_batch_one(hfcl_lib* lib, const uint32_t* d_s1, const uint32_t* d_
     };
     if (direct) cc_staged = gen_staged = false;
     if (cc_staged) {
-      if (lib->ws_capacity > lib->epa_ready_capacity) {
-        hipFree(lib->d_epa_ready);
-        lib->d_epa_ready = nullptr;
-        lib->epa_ready_capacity = 0;
-        HIP_TRY(hipMalloc(&lib->d_epa_ready, lib->ws_capacity * sizeof(EpaReady<float>)));
-        lib->epa_ready_capacity = lib->ws_capacity;
-      }
+      HIP_TRY(lib->d_epa_ready.grow(lib->ws_capacity * sizeof(EpaReady<float>)));
       wk.epa_ready = lib->d_epa_ready;
     }
     if (gen_staged) {
-      if (lib->ws_capacity * sizeof(EpaReadyG<T>) > lib->epa_ready_g_bytes) {
-        hipFree(lib->d_epa_ready_g);
-        lib->d_epa_ready_g = nullptr;
-        lib->epa_ready_g_bytes = 0;
-        HIP_TRY(hipMalloc(&lib->d_epa_ready_g, lib->ws_capacity * sizeof(EpaReadyG<T>)));
-        lib->epa_ready_g_bytes = lib->ws_capacity * sizeof(EpaReadyG<T>);
-      }
+      HIP_TRY(lib->d_epa_ready_g.grow(lib->ws_capacity * sizeof(EpaReadyG<T>)));
       wk.epa_ready_g = lib->d_epa_ready_g;
     }
     if constexpr (F32) {
@@ -2053,27 +1512,27 @@ static int run_batch_one(hfcl_lib* lib, const uint32_t* d_s1, const uint32_t* d_
   return HFCL_OK;
 }
 
-// shallow clone for the second half of a split batch: shares the device shape tables, owns everything else
-// the device tables a split batch's second half shares with its owner
+// shallow clone for the second half of a split batch: a view of its owner's device shape tables (`own` of a helper stays empty), everything
+// else its own.  The view of `h` onto the tables `lib` owns (h == lib: the library's own):
 static void share_tables(hfcl_lib* h, const hfcl_lib* lib) {
+  const hfcl_lib::Tables& t = lib->own;
   h->n_shapes = lib->n_shapes;
-  h->d_shapes64 = lib->d_shapes64;
-  h->d_shapes32 = lib->d_shapes32;
-  h->d_verts64 = lib->d_verts64;
-  h->d_verts32 = lib->d_verts32;
-  h->d_kinds = lib->d_kinds;
+  h->d_shapes64 = t.shapes64;
+  h->d_shapes32 = t.shapes32;
+  h->d_verts64 = t.verts64;
+  h->d_verts32 = t.verts32;
+  h->d_kinds = t.kinds;
   h->possible_buckets = lib->possible_buckets;
   h->has_curved = lib->has_curved;
   h->has_flats = lib->has_flats;
-  h->d_graph_base = lib->d_graph_base;
-  h->d_graph_off = lib->d_graph_off;
-  h->d_graph_ent32 = lib->d_graph_ent32;
-  h->d_graph_ent64 = lib->d_graph_ent64;
+  h->d_graph_base = t.graph.base;
+  h->d_graph_off = t.graph.off;
+  h->d_graph_ent32 = t.graph.ent32;
+  h->d_graph_ent64 = t.graph.ent64;
   h->climb_min = lib->climb_min;
 }
 static hfcl_lib* make_helper(hfcl_lib* lib) {
   hfcl_lib* h = new hfcl_lib;
-  h->is_helper = true;
   h->device = lib->device;
   share_tables(h, lib);
   h->cvx_w = lib->cvx_w;
@@ -2089,9 +1548,9 @@ static hfcl_lib* make_helper(hfcl_lib* lib) {
   h->epa64_two_streams = lib->epa64_two_streams;
   h->epa_cc_staged_min = lib->epa_cc_staged_min;
   h->n_cus = lib->n_cus;
-  bool ok = hipMalloc(&h->d_counts, N_COUNTERS * sizeof(uint32_t)) == hipSuccess;
-  ok = ok && hipHostMalloc((void**)&h->h_counts, N_COUNTERS * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess;
-  ok = ok && hipMalloc(&h->d_epa_v0, size_t(h->n_cus) * 16 * (64 / EPA_WE2) * EPA_MAX_VERTS * sizeof(Quad<double>)) == hipSuccess;
+  bool ok = h->d_counts.grow(N_COUNTERS) == hipSuccess;
+  ok = ok && h->h_counts.alloc(N_COUNTERS) == hipSuccess;
+  ok = ok && h->d_epa_v0.grow(size_t(h->n_cus) * 16 * (64 / EPA_WE2) * EPA_MAX_VERTS * sizeof(Quad<double>)) == hipSuccess;
   if (!ok) {
     hfcl_lib_destroy(h);
     return nullptr;
@@ -2112,7 +1571,7 @@ template <> IO<float> io_at(const IO<float>& io, size_t lo) {
 // spread over three or more of the iterative buckets (mixed scenes: cfg5 4.05 -> 3.80 ms) -- the halves then run different
 // kernels side by side; with one or two kernels in the batch the halves only share the machine phase by phase and the
 // doubled fixed costs lose 3 % (cfg2, cfg3).  A/B in profiles/r01_k_two_stream_overlap.txt.
-static bool batch_splits(const hfcl_lib* lib, size_t n) {
+bool batch_splits(const hfcl_lib* lib, size_t n) {
   constexpr size_t MIN_SPLIT = 1u << 17;
   int parts = lib->split;
   if (parts == 0) {
@@ -2123,20 +1582,21 @@ static bool batch_splits(const hfcl_lib* lib, size_t n) {
   // meshes keep query-wide side state (contact lists, pair ids in them): they run unsplit
   return parts >= 2 && n >= MIN_SPLIT && lib->h_meshes.empty();
 }
-static int ensure_helper(hfcl_lib* lib) {
+int ensure_helper(hfcl_lib* lib) {
   if (lib->helper) return HFCL_OK;
   HIP_TRY(hipSetDevice(lib->device));
-  lib->helper = make_helper(lib);
-  bool ok = lib->helper != nullptr;
-  ok = ok && (lib->side || hipStreamCreateWithFlags(&lib->side, hipStreamNonBlocking) == hipSuccess);
-  ok = ok && (lib->ev_fork || hipEventCreateWithFlags(&lib->ev_fork, hipEventDisableTiming) == hipSuccess);
-  ok = ok && (lib->ev_join || hipEventCreateWithFlags(&lib->ev_join, hipEventDisableTiming) == hipSuccess);
-  if (!ok) {  // leave nothing half-made behind: the next call retries cleanly
-    if (lib->helper) hfcl_lib_destroy(lib->helper);
-    lib->helper = nullptr;
+  hfcl_lib* h = make_helper(lib);
+  Stream side;
+  Event fork, join;
+  if (!h || side.create() != hipSuccess || fork.create() != hipSuccess || join.create() != hipSuccess) {
+    if (h) hfcl_lib_destroy(h);  // nothing half-made stays behind: the next call retries cleanly
     set_error("split batches: HIP allocation failed");
     return HFCL_ERR_HIP;
   }
+  lib->side = std::move(side);
+  lib->ev_fork = std::move(fork);
+  lib->ev_join = std::move(join);
+  lib->helper = h;
   return HFCL_OK;
 }
 
@@ -2170,7 +1630,7 @@ static int run_batch(hfcl_lib* lib, const uint32_t* d_s1, const uint32_t* d_s2, 
 }
 
 template <typename T>
-static int setup_collide(const hfcl_collision_request* req, QParams<T>& q, bool& skip_all) {
+int setup_collide(const hfcl_collision_request* req, QParams<T>& q, bool& skip_all) {
   skip_all = false;
   if (!req) {
     set_error("null request");
@@ -2194,7 +1654,7 @@ static int setup_collide(const hfcl_collision_request* req, QParams<T>& q, bool&
   return HFCL_OK;
 }
 template <typename T>
-static int setup_distance(const hfcl_distance_request* req, QParams<T>& q) {
+int setup_distance(const hfcl_distance_request* req, QParams<T>& q) {
   if (!req) {
     set_error("null request");
     return HFCL_ERR_INVALID_ARGUMENT;
@@ -2208,6 +1668,11 @@ static int setup_distance(const hfcl_distance_request* req, QParams<T>& q) {
   q.gjk.distance_upper_bound = Lim<T>::max();  // narrowphase.h:175
   return HFCL_OK;
 }
+
+template int setup_collide<double>(const hfcl_collision_request*, QParams<double>&, bool&);  // (hfcl_host_scene.hip)
+template int setup_collide<float>(const hfcl_collision_request*, QParams<float>&, bool&);
+template int setup_distance<double>(const hfcl_distance_request*, QParams<double>&);
+template int setup_distance<float>(const hfcl_distance_request*, QParams<float>&);
 
 // full records -> compact records (hfcl_result_compact), for the multi-GPU exchange of results
 template <typename R, typename C>
@@ -2315,51 +1780,54 @@ int hfcl_compact_results_device_f32(hfcl_lib* lib, const hfcl_result_f32* d_reco
 }
 
 static int ensure_staging(hfcl_lib* lib, size_t n, bool gin, bool gout, bool compact) {
-  if (!lib->s_cmp) {
-    HIP_TRY(hipStreamCreateWithFlags(&lib->s_h2d, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&lib->s_h2d2, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&lib->s_cmp, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&lib->s_d2h, hipStreamNonBlocking));
-    for (auto& sg : lib->stage) {
-      HIP_TRY(hipEventCreateWithFlags(&sg.ev_in, hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&sg.ev_done, hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&sg.ev_in2, hipEventDisableTiming));
-      HIP_TRY(hipHostMalloc((void**)&sg.h_counts, N_COUNTERS * sizeof(uint32_t), hipHostMallocDefault));
-      HIP_TRY(hipHostMalloc((void**)&sg.h_counts2, N_COUNTERS * sizeof(uint32_t), hipHostMallocDefault));
+  if (!lib->s_cmp) {  // the streams, the slots' events and counter blocks: made into locals and committed together
+    Stream st[4];
+    Event ev[hfcl_lib::PIPE_SLOTS][3];
+    PinnedBuf<uint32_t> hc[hfcl_lib::PIPE_SLOTS][2];
+    for (Stream& x : st) HIP_TRY(x.create());
+    for (int k = 0; k < hfcl_lib::PIPE_SLOTS; ++k) {
+      for (Event& e : ev[k]) HIP_TRY(e.create());
+      for (PinnedBuf<uint32_t>& h : hc[k]) HIP_TRY(h.alloc(N_COUNTERS));
     }
+    for (int k = 0; k < hfcl_lib::PIPE_SLOTS; ++k) {
+      hfcl_lib::Staging& sg = lib->stage[k];
+      sg.ev_in = std::move(ev[k][0]);
+      sg.ev_done = std::move(ev[k][1]);
+      sg.ev_in2 = std::move(ev[k][2]);
+      sg.h_counts = std::move(hc[k][0]);
+      sg.h_counts2 = std::move(hc[k][1]);
+    }
+    lib->s_h2d = std::move(st[0]);
+    lib->s_h2d2 = std::move(st[1]);
+    lib->s_d2h = std::move(st[3]);
+    lib->s_cmp = std::move(st[2]);
   }
   if (n > lib->st_capacity) {
     lib->st_capacity = 0;
     const size_t cap = n + n / 8 + 256;
     for (auto& sg : lib->stage) {
-      hipFree(sg.d_s1); hipFree(sg.d_s2); hipFree(sg.d_tf1); hipFree(sg.d_tf2); hipFree(sg.d_out);
-      hipFree(sg.d_gin); hipFree(sg.d_gout); hipFree(sg.d_qt1); hipFree(sg.d_qt2);
-      sg.d_qt1 = sg.d_qt2 = nullptr;
-      sg.d_s1 = sg.d_s2 = nullptr;
-      sg.d_tf1 = sg.d_tf2 = nullptr;
-      sg.d_out = nullptr;
-      sg.d_gin = sg.d_gout = nullptr;
-      HIP_TRY(hipMalloc(&sg.d_s1, cap * sizeof(uint32_t)));
-      HIP_TRY(hipMalloc(&sg.d_s2, cap * sizeof(uint32_t)));
-      HIP_TRY(hipMalloc(&sg.d_tf1, cap * 12 * sizeof(double)));
-      HIP_TRY(hipMalloc(&sg.d_tf2, cap * 12 * sizeof(double)));
-      HIP_TRY(hipMalloc(&sg.d_out, cap * sizeof(hfcl_result)));
+      reset_all(sg.d_s1, sg.d_s2, sg.d_tf1, sg.d_tf2, sg.d_out, sg.d_gin, sg.d_gout, sg.d_qt1, sg.d_qt2);
+      HIP_TRY(sg.d_s1.grow(cap));
+      HIP_TRY(sg.d_s2.grow(cap));
+      HIP_TRY(sg.d_tf1.grow(cap * 12));
+      HIP_TRY(sg.d_tf2.grow(cap * 12));
+      HIP_TRY(sg.d_out.grow(cap));
     }
     lib->st_capacity = cap;
   }
   for (auto& sg : lib->stage) {
-    if (gin && !sg.d_gin) HIP_TRY(hipMalloc(&sg.d_gin, lib->st_capacity * sizeof(hfcl_guess)));
-    if (gout && !sg.d_gout) HIP_TRY(hipMalloc(&sg.d_gout, lib->st_capacity * sizeof(hfcl_guess)));
-    if (compact && !sg.d_qt1) {
-      HIP_TRY(hipMalloc(&sg.d_qt1, lib->st_capacity * 7 * sizeof(double)));
-      HIP_TRY(hipMalloc(&sg.d_qt2, lib->st_capacity * 7 * sizeof(double)));
+    if (gin) HIP_TRY(sg.d_gin.grow(lib->st_capacity));
+    if (gout) HIP_TRY(sg.d_gout.grow(lib->st_capacity));
+    if (compact) {
+      HIP_TRY(sg.d_qt1.grow(lib->st_capacity * 7));
+      HIP_TRY(sg.d_qt2.grow(lib->st_capacity * 7));
     }
   }
   return HFCL_OK;
 }
 
 // what a host batch reports after its records are back: pairs without an evaluator, requests the reference rejects
-static int host_batch_checks(hfcl_lib* lib, const hfcl_collision_request* creq, const hfcl_distance_request* dreq) {
+int host_batch_checks(hfcl_lib* lib, const hfcl_collision_request* creq, const hfcl_distance_request* dreq) {
   const bool skipped = creq && creq->security_margin == -__builtin_inf();
   if (!skipped && total_count(lib, B_UNSUPPORTED) > 0) {
     set_error("Collision/distance function between some node types of the batch is not yet supported (" +
@@ -2426,9 +1894,9 @@ static int host_batch_small(hfcl_lib* lib, const uint32_t* s1, const uint32_t* s
   const size_t o_tf1 = up(o_out + out_bytes), o_tf2 = o_tf1 + n * 96;
   if (!lib->d_pack) {
     const size_t cap = up(C * (2 * 96 + sizeof(hfcl_guess)) + 2 * up(C * 4)) + up(C * (sizeof(hfcl_result) + sizeof(hfcl_guess))) + 2 * C * 96 + 1024;
-    HIP_TRY(hipHostMalloc((void**)&lib->h_pack, cap, hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc((void**)&lib->h_pack_counts, 2 * N_COUNTERS * sizeof(uint32_t), hipHostMallocDefault));
-    HIP_TRY(hipMalloc(&lib->d_pack, cap));
+    HIP_TRY(lib->h_pack.alloc(cap));
+    HIP_TRY(lib->h_pack_counts.alloc(2 * N_COUNTERS));
+    HIP_TRY(lib->d_pack.grow(cap));
   }
   if (!lib->s_cmp) {  // (the pipeline's streams; this path uses the compute stream only)
     const int rc0 = ensure_staging(lib, 256, false, false, false);
@@ -2716,11 +2184,11 @@ static int host_batch(hfcl_lib* lib, const uint32_t* s1, const uint32_t* s2, con
       lib->helper->counts_dst = sg.h_counts2;
     }
     if (f32 && creq)
-      rc = hfcl_collide_batch_device_f32(lib, sg.d_s1, sg.d_s2, reinterpret_cast<const float*>(sg.d_tf1), reinterpret_cast<const float*>(sg.d_tf2), m, creq,
-                                         reinterpret_cast<hfcl_result_f32*>(sg.d_out), lib->s_cmp);
+      rc = hfcl_collide_batch_device_f32(lib, sg.d_s1, sg.d_s2, reinterpret_cast<const float*>(sg.d_tf1.get()), reinterpret_cast<const float*>(sg.d_tf2.get()), m, creq,
+                                         reinterpret_cast<hfcl_result_f32*>(sg.d_out.get()), lib->s_cmp);
     else if (f32)
-      rc = hfcl_distance_batch_device_f32(lib, sg.d_s1, sg.d_s2, reinterpret_cast<const float*>(sg.d_tf1), reinterpret_cast<const float*>(sg.d_tf2), m, dreq,
-                                          reinterpret_cast<hfcl_result_f32*>(sg.d_out), lib->s_cmp);
+      rc = hfcl_distance_batch_device_f32(lib, sg.d_s1, sg.d_s2, reinterpret_cast<const float*>(sg.d_tf1.get()), reinterpret_cast<const float*>(sg.d_tf2.get()), m, dreq,
+                                          reinterpret_cast<hfcl_result_f32*>(sg.d_out.get()), lib->s_cmp);
     else if (creq)
       rc = hfcl_collide_batch_device(lib, sg.d_s1, sg.d_s2, sg.d_tf1, sg.d_tf2, m, creq, sg.d_out, gin ? sg.d_gin : nullptr,
                                      gout ? sg.d_gout : nullptr, lib->s_cmp);
@@ -2826,14 +2294,8 @@ int hfcl_collide_batch_contacts(hfcl_lib* lib, const uint32_t* shape1, const uin
     return HFCL_ERR_INVALID_ARGUMENT;
   }
   HIP_TRY(hipSetDevice(lib->device));
-  if (max_contacts_total > lib->contacts_cap) {
-    hipFree(lib->d_contacts);
-    lib->d_contacts = nullptr;
-    lib->contacts_cap = 0;
-    HIP_TRY(hipMalloc(&lib->d_contacts, max_contacts_total * sizeof(hfcl_contact)));
-    lib->contacts_cap = max_contacts_total;
-  }
-  if (!lib->d_contacts_count) HIP_TRY(hipMalloc(&lib->d_contacts_count, sizeof(uint32_t)));
+  HIP_TRY(lib->d_contacts.grow(max_contacts_total));
+  HIP_TRY(lib->d_contacts_count.grow(1));
   HIP_TRY(hipMemset(lib->d_contacts_count, 0, sizeof(uint32_t)));
   lib->bvh_params.contacts = lib->d_contacts;
   lib->bvh_params.contacts_cap = uint32_t(max_contacts_total > 0xFFFFFFFFull ? 0xFFFFFFFFull : max_contacts_total);
@@ -2922,6 +2384,11 @@ extern "C" int hfcl_debug_walk_counters(hfcl_lib* lib, int solid, uint32_t* out3
   out34[33] = ctr[BVH_CTR_SUSPENDED];
   return HFCL_OK;
 }
+// (diagnostic, not part of the ABI: the owning handles alive in this process -- device buffers, pinned buffers, streams, events; hfcl_own.hpp.
+// What a library, a scene or a multi-device set took is given back when it is destroyed: tests/test_gpu_ownership.py)
+extern "C" void hfcl_debug_live_handles(int64_t* out4) {
+  for (int k = 0; k < 4; ++k) out4[k] = g_hfcl_live[k].load(std::memory_order_relaxed);
+}
 // pairs per chunk of the host-buffer pipeline (0 = automatic: n/8 clamped to 32k .. 256k)
 void hfcl_lib_set_host_chunk(hfcl_lib* lib, size_t pairs) {
   if (lib) lib->pipe_chunk = pairs;
@@ -3001,1246 +2468,5 @@ uint32_t hfcl_last_epa_handed_over(hfcl_lib* lib) {
   if (lib->last_split && lib->helper && lib->helper->h_counts) c += lib->helper->h_counts[CTR_EPA_CC_OVER];
   return c;
 }
-
-// ---- contact patches (hfcl_k_patch.hip) ------------------------------------------------------------------------------
-void hfcl_contact_patch_request_init(hfcl_patch_request* r) {
-  if (!r) return;
-  r->max_num_patch = 1;
-  r->num_samples_curved_shapes = 12;
-  r->patch_tolerance = 1e-3;
-}
-
-int hfcl_patch_supported(int32_t t1, int32_t t2) {
-  auto known = [](int32_t t) {
-    return t == HFCL_GEOM_BOX || t == HFCL_GEOM_SPHERE || t == HFCL_GEOM_CAPSULE || t == HFCL_GEOM_CONE || t == HFCL_GEOM_CYLINDER ||
-           t == HFCL_GEOM_CONVEX || t == HFCL_GEOM_PLANE || t == HFCL_GEOM_HALFSPACE || t == HFCL_GEOM_TRIANGLE ||
-           t == HFCL_GEOM_ELLIPSOID || t == HFCL_BV_OBBRSS;
-  };
-  return known(t1) && known(t2);
-}
-
-}  // extern "C"
-
-// the request with the reference's setter clamps (collision_data.h:782-808)
-static void patch_request_values(const hfcl_patch_request* r, uint32_t& ns, double& tol) {
-  ns = r->num_samples_curved_shapes < 3u ? 3u : r->num_samples_curved_shapes;
-  tol = r->patch_tolerance < 0 ? 1e-12 : r->patch_tolerance;
-}
-static uint32_t patch_shape_bound(const hfcl_shape& s, uint32_t ns) { return patch_set_bound(s.type, s.num_points, ns); }
-static uint32_t patch_table_bound(const hfcl_shape* shapes, size_t n_shapes, uint32_t ns) {
-  uint32_t m = 1;
-  for (size_t k = 0; k < n_shapes; ++k) m = std::max(m, patch_shape_bound(shapes[k], ns));
-  return 2 * m;
-}
-static uint32_t patch_lib_bound(const hfcl_lib* lib, uint32_t ns) { return patch_table_bound(lib->h_shapes.data(), lib->h_shapes.size(), ns); }
-
-// workspace: slots of the polygons of one record each; at most 64k slots, no more than 256 MiB unless 256 slots need it
-static int ensure_patch_ws(hfcl_lib* lib, size_t n, uint32_t cap, uint32_t cloud_cap, uint32_t vis_cap, PatchArgs& a) {
-  size_t slot = 3 * size_t(cap) * 16 + size_t(cloud_cap) * 16 + size_t(cloud_cap / 2 + 1) * 16 + 8 * size_t(vis_cap) + vis_cap;
-  slot = (slot + 255) & ~size_t(255);
-  size_t nslots = std::max<size_t>(256, std::min<size_t>(65536, (size_t(256) << 20) / slot));
-  nslots = std::min(nslots, std::max<size_t>(n, 1));
-  const size_t bytes = nslots * slot;
-  if (bytes > lib->patch_ws_bytes) {
-    hipFree(lib->d_patch_ws);
-    lib->d_patch_ws = nullptr;
-    lib->patch_ws_bytes = 0;
-    HIP_TRY(hipMalloc(&lib->d_patch_ws, bytes));
-    lib->patch_ws_bytes = bytes;
-  }
-  if (n > lib->patch_list_cap) {
-    hipFree(lib->d_patch_lists);
-    lib->d_patch_lists = nullptr;
-    lib->patch_list_cap = 0;
-    HIP_TRY(hipMalloc(&lib->d_patch_lists, 2 * n * sizeof(uint32_t)));
-    lib->patch_list_cap = n;
-  }
-  if (!lib->d_patch_counts) HIP_TRY(hipMalloc(&lib->d_patch_counts, 2 * sizeof(uint32_t)));
-  a.ws = (char*)lib->d_patch_ws;
-  a.slot_bytes = slot;
-  a.nslots = uint32_t(nslots);
-  a.cap = cap;
-  a.cloud_cap = cloud_cap;
-  a.vis_cap = vis_cap;
-  a.lists = lib->d_patch_lists;
-  a.counts = lib->d_patch_counts;
-  return HFCL_OK;
-}
-
-static int patch_run(hfcl_lib* lib, const uint32_t* d_s1, const uint32_t* d_s2, const double* d_tf1, const double* d_tf2,
-                     const hfcl_result* d_rec, const hfcl_guess* d_guess, size_t n, const hfcl_patch_request* req, uint32_t pcap,
-                     hfcl_contact_patch* d_out, double* d_pts, hipStream_t st, uint32_t plim) {
-  uint32_t ns;
-  double tol;
-  patch_request_values(req, ns, tol);
-  if (lib->graph_dirty) {
-    const int rcg = upload_graph(lib);
-    if (rcg) return rcg;
-  }
-  uint32_t cloud_cap = 8, vis_cap = 0;
-  for (size_t k = 0; k < lib->h_shapes.size(); ++k) {
-    const hfcl_shape& s = lib->h_shapes[k];
-    if (s.type != HFCL_GEOM_CONVEX) continue;
-    cloud_cap = std::max(cloud_cap, s.num_points);
-    if (s.num_points > 32u && lib->h_graphs.count(uint32_t(k))) vis_cap = std::max(vis_cap, s.num_points);
-  }
-  PatchArgs a;
-  a.s1 = d_s1; a.s2 = d_s2; a.tf1 = d_tf1; a.tf2 = d_tf2; a.rec = d_rec; a.guess = d_guess;
-  a.n = uint32_t(n);
-  a.n_shapes = uint32_t(lib->n_shapes);
-  a.shapes = lib->d_shapes64;
-  a.verts = lib->d_verts64;
-  a.graph_base = lib->d_graph_base;
-  a.graph_off = lib->d_graph_off;
-  a.graph_ent = reinterpret_cast<const uint32_t*>(lib->d_graph_ent64);
-  a.max_num_patch = req->max_num_patch;
-  a.num_samples = ns;
-  a.tol = tol;
-  a.pcap = pcap;
-  a.plim = plim;
-  a.out = d_out;
-  a.out_pts = d_pts;
-  int rc = ensure_patch_ws(lib, n, patch_lib_bound(lib, ns), cloud_cap, vis_cap, a);
-  if (rc) return rc;
-  HIP_TRY(hipMemsetAsync(a.counts, 0, 2 * sizeof(uint32_t), st));
-  for (auto& t : lib->timers) t.used = false;
-  const char* names[3];
-  hipEvent_t e0[3], e1[3];
-  bool timed = lib->kernel_timing;
-  if (timed) {
-    for (int k = 0; k < 3; ++k) {
-      KernelTime* t = timer_slot(lib, size_t(k), "");
-      e0[k] = t->e0;
-      e1[k] = t->e1;
-    }
-  }
-  launch_patch(st, a, lib->n_cus * 16, names, timed ? e0 : nullptr, timed ? e1 : nullptr);
-  if (timed)
-    for (int k = 0; k < 3; ++k) lib->timers[size_t(k)].name = names[k];
-  HIP_TRY(hipGetLastError());
-  return HFCL_OK;
-}
-
-extern "C" {
-
-int hfcl_contact_patch_max_points(const hfcl_lib* lib, const hfcl_patch_request* req, uint32_t* cap) {
-  if (!lib || !req || !cap) {
-    set_error("hfcl_contact_patch_max_points: null argument");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  uint32_t ns;
-  double tol;
-  patch_request_values(req, ns, tol);
-  *cap = patch_lib_bound(lib, ns);
-  return HFCL_OK;
-}
-
-int hfcl_contact_patch_max_points_shapes(const hfcl_shape* shapes, size_t n_shapes, const hfcl_patch_request* req, uint32_t* cap) {
-  if ((!shapes && n_shapes) || !req || !cap) {
-    set_error("hfcl_contact_patch_max_points_shapes: null argument");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  uint32_t ns;
-  double tol;
-  patch_request_values(req, ns, tol);
-  *cap = patch_table_bound(shapes, n_shapes, ns);
-  return HFCL_OK;
-}
-
-int hfcl_contact_patch_batch_device(hfcl_lib* lib, const uint32_t* d_shape1, const uint32_t* d_shape2, const double* d_tf1,
-                                    const double* d_tf2, const hfcl_result* d_records, const hfcl_guess* d_guesses, size_t n,
-                                    const hfcl_patch_request* req, uint32_t points_capacity, hfcl_contact_patch* d_out,
-                                    double* d_out_points, void* stream) {
-  int nd = 0;
-  if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) {
-    set_error("no HIP device available (hipGetDeviceCount): the engine has no CPU fallback");
-    return HFCL_ERR_NO_DEVICE;
-  }
-  if (!lib || !req) {
-    set_error("hfcl_contact_patch_batch_device: null library / request");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  if (n == 0) return HFCL_OK;
-  if (!d_shape1 || !d_shape2 || !d_tf1 || !d_tf2 || !d_records || !d_out || !d_out_points) {
-    set_error("hfcl_contact_patch_batch_device: null buffer");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  if (n > 0xFFFFFFF0ull) {
-    set_error("batch too large (max 2^32-16 pairs per call)");
-    return HFCL_ERR_LIMIT;
-  }
-  uint32_t ns;
-  double tol;
-  patch_request_values(req, ns, tol);
-  const uint32_t need = patch_lib_bound(lib, ns);
-  if (points_capacity < need) {
-    set_error("hfcl_contact_patch_batch_device: points_capacity " + std::to_string(points_capacity) + " is below the library's bound " +
-              std::to_string(need) + " (hfcl_contact_patch_max_points)");
-    return HFCL_ERR_LIMIT;
-  }
-  HIP_TRY(hipSetDevice(lib->device));
-  return patch_run(lib, d_shape1, d_shape2, d_tf1, d_tf2, d_records, d_guesses, n, req, points_capacity, d_out, d_out_points,
-                   (hipStream_t)stream, points_capacity);
-}
-
-int hfcl_contact_patch_batch(hfcl_lib* lib, const uint32_t* shape1, const uint32_t* shape2, const double* tf1, const double* tf2,
-                             const hfcl_result* records, const hfcl_guess* guesses, size_t n, const hfcl_patch_request* req,
-                             uint32_t points_capacity, hfcl_contact_patch* out, double* out_points) {
-  int nd = 0;
-  if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) {
-    set_error("no HIP device available (hipGetDeviceCount): the engine has no CPU fallback");
-    return HFCL_ERR_NO_DEVICE;
-  }
-  if (!lib || !req) {
-    set_error("hfcl_contact_patch_batch: null library / request");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  if (n == 0) return HFCL_OK;
-  if (!shape1 || !shape2 || !tf1 || !tf2 || !records || !out || !out_points) {
-    set_error("hfcl_contact_patch_batch: null buffer");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  if (n > 0xFFFFFFF0ull) {
-    set_error("batch too large (max 2^32-16 pairs per call)");
-    return HFCL_ERR_LIMIT;
-  }
-  uint32_t ns;
-  double tol;
-  patch_request_values(req, ns, tol);
-  uint32_t need = 0;
-  for (size_t i = 0; i < n; ++i) {
-    if (shape1[i] >= lib->n_shapes || shape2[i] >= lib->n_shapes) {
-      set_error("hfcl_contact_patch_batch: shape id outside the library at record " + std::to_string(i));
-      return HFCL_ERR_INVALID_ARGUMENT;
-    }
-    const hfcl_shape& a = lib->h_shapes[shape1[i]];
-    const hfcl_shape& b = lib->h_shapes[shape2[i]];
-    if (!hfcl_patch_supported(a.type, b.type)) {
-      set_error("Contact patch computation between node types " + std::to_string(a.type) + " and " + std::to_string(b.type) +
-                " is not yet supported.");
-      return HFCL_ERR_UNSUPPORTED_PAIR;
-    }
-    need = std::max(need, patch_shape_bound(a, ns) + patch_shape_bound(b, ns));
-  }
-  if (points_capacity < need) {
-    set_error("hfcl_contact_patch_batch: points_capacity " + std::to_string(points_capacity) + " is below the batch's need " +
-              std::to_string(need));
-    return HFCL_ERR_LIMIT;
-  }
-  HIP_TRY(hipSetDevice(lib->device));
-  if (!lib->patch_st) HIP_TRY(hipStreamCreateWithFlags(&lib->patch_st, hipStreamNonBlocking));
-  hipStream_t st = lib->patch_st;
-  // the workspace slots are sized by the library's bound: records go through a device copy of that width
-  const uint32_t dcap = std::max(points_capacity, patch_lib_bound(lib, ns));
-  const size_t b_ids = n * sizeof(uint32_t), b_tf = n * 12 * sizeof(double), b_rec = n * sizeof(hfcl_result);
-  const size_t b_g = guesses ? n * sizeof(hfcl_guess) : 0, b_out = n * sizeof(hfcl_contact_patch);
-  const size_t b_pts = n * size_t(dcap) * 2 * sizeof(double);
-  char* d = nullptr;
-  const size_t total = 2 * b_ids + 2 * b_tf + b_rec + b_g + b_out + b_pts + 8 * 256;
-  HIP_TRY(hipMalloc(&d, total));
-  size_t off = 0;
-  auto carve = [&](size_t b) {
-    char* p = d + off;
-    off += (b + 255) & ~size_t(255);
-    return p;
-  };
-  uint32_t* d_s1 = (uint32_t*)carve(b_ids);
-  uint32_t* d_s2 = (uint32_t*)carve(b_ids);
-  double* d_tf1 = (double*)carve(b_tf);
-  double* d_tf2 = (double*)carve(b_tf);
-  hfcl_result* d_rec = (hfcl_result*)carve(b_rec);
-  hfcl_guess* d_g = guesses ? (hfcl_guess*)carve(b_g) : nullptr;
-  hfcl_contact_patch* d_out = (hfcl_contact_patch*)carve(b_out);
-  double* d_pts = (double*)carve(b_pts);
-  int rc = HFCL_OK;
-  bool ok = hipMemcpyAsync(d_s1, shape1, b_ids, hipMemcpyHostToDevice, st) == hipSuccess;
-  ok = ok && hipMemcpyAsync(d_s2, shape2, b_ids, hipMemcpyHostToDevice, st) == hipSuccess;
-  ok = ok && hipMemcpyAsync(d_tf1, tf1, b_tf, hipMemcpyHostToDevice, st) == hipSuccess;
-  ok = ok && hipMemcpyAsync(d_tf2, tf2, b_tf, hipMemcpyHostToDevice, st) == hipSuccess;
-  ok = ok && hipMemcpyAsync(d_rec, records, b_rec, hipMemcpyHostToDevice, st) == hipSuccess;
-  ok = ok && (!guesses || hipMemcpyAsync(d_g, guesses, b_g, hipMemcpyHostToDevice, st) == hipSuccess);
-  // rows are copied back whole: the points past a record's num_points are zeros, not whatever the allocation held
-  ok = ok && hipMemsetAsync(d_pts, 0, b_pts, st) == hipSuccess;
-  if (!ok) rc = HFCL_ERR_HIP;
-  if (!rc) rc = patch_run(lib, d_s1, d_s2, d_tf1, d_tf2, d_rec, d_g, n, req, dcap, d_out, d_pts, st, points_capacity);
-  if (!rc) {
-    ok = hipMemcpyAsync(out, d_out, b_out, hipMemcpyDeviceToHost, st) == hipSuccess;
-    // rows of dcap points on the device, of points_capacity in the caller's buffer
-    ok = ok && hipMemcpy2DAsync(out_points, size_t(points_capacity) * 2 * sizeof(double), d_pts, size_t(dcap) * 2 * sizeof(double),
-                                size_t(points_capacity) * 2 * sizeof(double), n, hipMemcpyDeviceToHost, st) == hipSuccess;
-    ok = ok && hipStreamSynchronize(st) == hipSuccess;
-    if (!ok) rc = HFCL_ERR_HIP;
-  }
-  if (rc == HFCL_ERR_HIP) set_error("hfcl_contact_patch_batch: HIP copy / launch failed");
-  hipStreamSynchronize(st);
-  hipFree(d);
-  return rc;
-}
-
-}  // extern "C"
-
-// =======================================================================================
-// Scene queries (include/hppfcl_amd.h: hfcl_scene_*): an object -> shape table and a pair list resident on the library's device; a call
-// evaluates the pair list for n_conf pose tables.  The flat query range q = c * n_pairs + p is cut into chunks; a chunk is expanded into the
-// per-pair arrays of the batch entry points (k_scene_expand*), goes through hfcl_*_batch_device* exactly as a caller's batch of that size
-// would, and its records are folded into the summaries of the configurations it touches (k_scene_fold).  No record changes on the way.
-// =======================================================================================
-struct hfcl_scene {
-  hfcl_lib* lib = nullptr;
-  size_t n_objects = 0, n_pairs = 0;
-  uint32_t* d_object_shape = nullptr;
-  uint32_t* d_pairs = nullptr;
-  uint64_t epoch = 0;  // hfcl_lib::shapes_epoch when the scene was made
-};
-
-static int scene_check_pairs(const char* who, const uint32_t* pairs, size_t n_pairs, size_t n_objects) {
-  if (n_pairs > 0xFFFFFFF0ull) {
-    set_error(std::string(who) + ": pair list too long (max 2^32-16 pairs)");
-    return HFCL_ERR_LIMIT;
-  }
-  if (n_pairs && !pairs) {
-    set_error(std::string(who) + ": null pair list");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  for (size_t k = 0; k < 2 * n_pairs; ++k)
-    if (pairs[k] >= n_objects) {
-      set_error(std::string(who) + ": object index " + std::to_string(pairs[k]) + " of pair " + std::to_string(k / 2) + " is outside the " +
-                std::to_string(n_objects) + " objects");
-      return HFCL_ERR_INVALID_ARGUMENT;
-    }
-  return HFCL_OK;
-}
-static int scene_upload(uint32_t** dst, const uint32_t* src, size_t words) {
-  *dst = nullptr;
-  if (!words) return HFCL_OK;
-  HIP_TRY(hipMalloc(dst, words * sizeof(uint32_t)));
-  if (hipMemcpy(*dst, src, words * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
-    hipFree(*dst);
-    *dst = nullptr;
-    set_error("scene: copy to the device failed");
-    return HFCL_ERR_HIP;
-  }
-  return HFCL_OK;
-}
-
-template <typename T> struct SceneTypes;
-template <> struct SceneTypes<double> {
-  using R = hfcl_result;
-  static constexpr size_t WIDTH = 12;
-};
-template <> struct SceneTypes<float> {
-  using R = hfcl_result_f32;
-  static constexpr size_t WIDTH = 7;
-};
-
-// a chunk through the batch entry point of its precision
-static int scene_batch(hfcl_lib* lib, const uint32_t* s1, const uint32_t* s2, const void* tf1, const void* tf2, size_t m,
-                       const hfcl_collision_request* creq, const hfcl_distance_request* dreq, hfcl_result* rec, const hfcl_guess* gin,
-                       hfcl_guess* gout, hipStream_t st) {
-  return creq ? hfcl_collide_batch_device(lib, s1, s2, static_cast<const double*>(tf1), static_cast<const double*>(tf2), m, creq, rec, gin, gout, st)
-              : hfcl_distance_batch_device(lib, s1, s2, static_cast<const double*>(tf1), static_cast<const double*>(tf2), m, dreq, rec, gin, gout, st);
-}
-static int scene_batch(hfcl_lib* lib, const uint32_t* s1, const uint32_t* s2, const void* tf1, const void* tf2, size_t m,
-                       const hfcl_collision_request* creq, const hfcl_distance_request* dreq, hfcl_result_f32* rec, const hfcl_guess*, hfcl_guess*,
-                       hipStream_t st) {
-  return creq ? hfcl_collide_batch_device_f32(lib, s1, s2, static_cast<const float*>(tf1), static_cast<const float*>(tf2), m, creq, rec, st)
-              : hfcl_distance_batch_device_f32(lib, s1, s2, static_cast<const float*>(tf1), static_cast<const float*>(tf2), m, dreq, rec, st);
-}
-
-// everything a scene call refuses before any work; total: n_conf * n_pairs (0: nothing to do)
-template <typename T>
-static int scene_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, const hfcl_collision_request* creq,
-                          const hfcl_distance_request* dreq, const void* out, const void* summary, size_t& total) {
-  total = 0;
-  if (!s) {
-    set_error(std::string(who) + ": null scene");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  QParams<T> q;
-  bool skip;
-  const int rc = creq ? setup_collide<T>(creq, q, skip) : setup_distance<T>(dreq, q);
-  if (rc) return rc;
-  if (!out && !summary) {
-    set_error(std::string(who) + ": records and summaries both NULL");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  if (s->epoch != s->lib->shapes_epoch) {
-    set_error(std::string(who) + ": the library's shapes were replaced (hfcl_lib_set_shapes) after this scene was created; create a new scene");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  if (n_conf == 0 || s->n_pairs == 0) return HFCL_OK;
-  if (!table) {
-    set_error(std::string(who) + ": null pose table");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  if (n_conf > ~size_t(0) / s->n_pairs || n_conf > ~size_t(0) / (s->n_objects * SceneTypes<T>::WIDTH * sizeof(T))) {
-    set_error(std::string(who) + ": n_conf * n_pairs overflows");
-    return HFCL_ERR_LIMIT;
-  }
-  total = n_conf * s->n_pairs;
-  return HFCL_OK;
-}
-// queries per chunk of a call of `total` queries: the option as given, or equal chunks of at most 2^21
-static size_t scene_chunk_size(const hfcl_lib* lib, size_t total) {
-  if (lib->scene_chunk) return std::min<size_t>(std::min<size_t>(lib->scene_chunk, total), 0xFFFFFFF0ull);
-  constexpr size_t AUTO = size_t(1) << 21;
-  const size_t n_chunks = (total + AUTO - 1) / AUTO;
-  return (total + n_chunks - 1) / n_chunks;
-}
-
-template <typename P>
-static int scene_grow(P** p, size_t& cap, size_t need, size_t elem) {
-  if (need <= cap) return HFCL_OK;
-  hipFree(*p);  // (waits for the device: nothing in flight reads the old buffer)
-  *p = nullptr;
-  cap = 0;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), need * elem));
-  cap = need;
-  return HFCL_OK;
-}
-// workspace of chunks of up to m queries; recs: how many of the two record buffers; pieces: fold partials (0: none)
-static int scene_workspace(hfcl_lib* lib, size_t m, int recs, bool gin, int gouts, size_t pieces) {
-  hfcl_lib::SceneWs& w = lib->scene;
-  if (m > w.cap) {
-    hipFree(w.d_s1); hipFree(w.d_s2); hipFree(w.d_tf1); hipFree(w.d_tf2);
-    w.d_s1 = w.d_s2 = nullptr;
-    w.d_tf1 = w.d_tf2 = nullptr;
-    w.cap = 0;
-    HIP_TRY(hipMalloc(&w.d_s1, m * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&w.d_s2, m * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&w.d_tf1, m * 12 * sizeof(double)));  // (rows of either precision)
-    HIP_TRY(hipMalloc(&w.d_tf2, m * 12 * sizeof(double)));
-    w.cap = m;
-  }
-  for (int k = 0; k < recs; ++k) {
-    const int rc = scene_grow(&w.d_rec[k], w.rec_cap[k], m, sizeof(hfcl_result));
-    if (rc) return rc;
-  }
-  if (gin) {
-    const int rc = scene_grow(&w.d_gin, w.gin_cap, m, sizeof(hfcl_guess));
-    if (rc) return rc;
-  }
-  for (int k = 0; k < gouts; ++k) {
-    const int rc = scene_grow(&w.d_gout[k], w.gout_cap[k], m, sizeof(hfcl_guess));
-    if (rc) return rc;
-  }
-  return scene_grow(&w.d_partials, w.partials_cap, pieces, sizeof(hfcl_scene_summary));
-}
-// fold partials a chunk of m queries can need: none when a pair list is one piece
-static size_t scene_pieces_bound(size_t n_pairs, size_t m) {
-  if (scene_shares(uint32_t(n_pairs)) <= 1u) return 0;
-  // whole pieces inside the chunk, a cut one at either end, and one more cut per configuration boundary inside it
-  return m / SCENE_FOLD_SHARE + 2 + 2 * (m / n_pairs + 2);
-}
-
-// expansion of chunk [q0, q0 + m), the batch, the fold: all on st
-template <typename T>
-static int scene_chunk_run(hfcl_scene* s, const void* d_table, size_t q0, size_t m, const hfcl_collision_request* creq,
-                           const hfcl_distance_request* dreq, typename SceneTypes<T>::R* d_rec, hfcl_scene_summary* d_summary,
-                           const hfcl_guess* d_gin, hfcl_guess* d_gout, hipStream_t st) {
-  hfcl_lib* lib = s->lib;
-  hfcl_lib::SceneWs& w = lib->scene;
-  constexpr bool f32 = std::is_same<T, float>::value;
-  const int max_blocks = lib->n_cus * 16;
-  SceneExpandArgs ea;
-  ea.pairs = s->d_pairs;
-  ea.object_shape = s->d_object_shape;
-  ea.object_tf = d_table;
-  ea.n_objects = s->n_objects;
-  ea.n_pairs = uint32_t(s->n_pairs);
-  ea.q0 = q0;
-  scene_query(q0, ea.n_pairs, ea.c0, ea.p0);
-  ea.m = uint32_t(m);
-  ea.s1 = w.d_s1;
-  ea.s2 = w.d_s2;
-  ea.tf1 = w.d_tf1;
-  ea.tf2 = w.d_tf2;
-  launch_scene_expand(st, ea, f32, max_blocks);
-  const int rc = scene_batch(lib, w.d_s1, w.d_s2, w.d_tf1, w.d_tf2, m, creq, dreq, d_rec, d_gin, d_gout, st);
-  if (rc) return rc;
-  if (d_summary) {
-    SceneFoldArgs fa;
-    fa.rec = d_rec;
-    fa.q0 = q0;
-    fa.q1 = q0 + m;
-    fa.n_pairs = uint32_t(s->n_pairs);
-    fa.g0 = scene_piece_of(q0, fa.n_pairs);
-    fa.n_pieces = scene_piece_of(q0 + m - 1, fa.n_pairs) - fa.g0 + 1;
-    fa.margin = creq ? creq->security_margin : 0.0;
-    fa.collide = creq ? 1 : 0;
-    fa.summary = d_summary;
-    fa.partials = scene_shares(fa.n_pairs) > 1u ? w.d_partials : nullptr;
-    launch_scene_fold(st, fa, f32, max_blocks);
-  }
-  return HFCL_OK;
-}
-// An error after work was enqueued: the second half of a split batch may be running on the library's side stream -- the caller's stream
-// waits for it, so that "everything this call started is ordered before what the caller enqueues next" holds on the error path too
-static void scene_join_side(hfcl_lib* lib, hipStream_t st) {
-  if (lib->side && lib->ev_join && hipEventRecord(lib->ev_join, lib->side) == hipSuccess) (void)hipStreamWaitEvent(st, lib->ev_join, 0);
-}
-
-template <typename T>
-static int scene_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const hfcl_collision_request* creq,
-                        const hfcl_distance_request* dreq, typename SceneTypes<T>::R* d_out, hfcl_scene_summary* d_summary,
-                        const hfcl_guess* d_gin, hfcl_guess* d_gout, hipStream_t st) {
-  size_t total;
-  int rc = scene_validate<T>(who, s, d_table, n_conf, creq, dreq, d_out, d_summary, total);
-  if (rc || !total) return rc;
-  hfcl_lib* lib = s->lib;
-  HIP_TRY(hipSetDevice(lib->device));
-  const size_t chunk = scene_chunk_size(lib, total);
-  rc = scene_workspace(lib, chunk, d_out ? 0 : 1, false, 0, d_summary ? scene_pieces_bound(s->n_pairs, chunk) : 0);
-  if (rc) return rc;
-  for (size_t q0 = 0; q0 < total; q0 += chunk) {
-    const size_t m = std::min(chunk, total - q0);
-    auto* rec = d_out ? d_out + q0 : static_cast<typename SceneTypes<T>::R*>(lib->scene.d_rec[0]);
-    rc = scene_chunk_run<T>(s, d_table, q0, m, creq, dreq, rec, d_summary, d_gin ? d_gin + q0 : nullptr, d_gout ? d_gout + q0 : nullptr, st);
-    if (rc) {
-      scene_join_side(lib, st);
-      return rc;
-    }
-  }
-  HIP_TRY(hipGetLastError());
-  return HFCL_OK;
-}
-
-
-// ---------------------------------------------------------------------------------------
-// Culling the pair list per configuration (hfcl_scene_cull*), and the scene calls on the list that is left (hfcl_scene_*_listed*,
-// hfcl_scene_*_culled).  hfcl_k_cull.hip has the kernels, hfcl_cull.hpp the arithmetic.
-// ---------------------------------------------------------------------------------------
-// the library's local boxes on the device, rebuilt when shapes or meshes were registered since
-static int ensure_local_boxes(hfcl_lib* lib) {
-  if (!lib->local_boxes_dirty && lib->d_local_boxes) return HFCL_OK;
-  const double nan = __builtin_nan("");
-  std::vector<double> boxes(6 * lib->n_shapes);
-  for (size_t i = 0; i < lib->n_shapes; ++i) {
-    const hfcl_shape& s = lib->h_shapes[i];
-    Box3 b;
-    if (s.type == HFCL_BV_OBBRSS) {
-      if (s.bvh_index < lib->h_meshes.size())
-        b = mesh_local_box(lib->h_bvh_verts.data() + 3 * size_t(lib->h_meshes[s.bvh_index].vert_off), lib->h_mesh_nverts[s.bvh_index]);
-      else  // (no such model: the narrow phase refuses the pair; a NaN box keeps it in the list)
-        for (int k = 0; k < 3; ++k) b.lo[k] = b.hi[k] = nan;
-    } else {
-      b = shape_local_box(s, lib->h_verts.data());
-    }
-    for (int k = 0; k < 3; ++k) {
-      boxes[6 * i + k] = b.lo[k];
-      boxes[6 * i + 3 + k] = b.hi[k];
-    }
-  }
-  hipFree(lib->d_local_boxes);  // (waits for the device: nothing in flight reads the old table)
-  lib->d_local_boxes = nullptr;
-  HIP_TRY(hipMalloc(&lib->d_local_boxes, std::max<size_t>(boxes.size(), 6) * sizeof(double)));
-  HIP_TRY(hipMemcpy(lib->d_local_boxes, boxes.data(), boxes.size() * sizeof(double), hipMemcpyHostToDevice));
-  lib->local_boxes_dirty = false;
-  return HFCL_OK;
-}
-
-// what the cull calls refuse before any work; total: n_conf * n_pairs (0: no query)
-template <typename T>
-static int cull_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, size_t& total) {
-  total = 0;
-  if (!s) {
-    set_error(std::string(who) + ": null scene");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  if (s->epoch != s->lib->shapes_epoch) {
-    set_error(std::string(who) + ": the library's shapes were replaced (hfcl_lib_set_shapes) after this scene was created; create a new scene");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  if (n_conf == 0 || s->n_objects == 0) return HFCL_OK;
-  if (!table) {
-    set_error(std::string(who) + ": null pose table");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  if ((s->n_pairs && n_conf > ~size_t(0) / s->n_pairs) || n_conf > ~size_t(0) / (s->n_objects * SceneTypes<T>::WIDTH * sizeof(T))) {
-    set_error(std::string(who) + ": n_conf * n_pairs overflows");
-    return HFCL_ERR_LIMIT;
-  }
-  total = n_conf * s->n_pairs;
-  return HFCL_OK;
-}
-static int cull_check_inflate(const char* who, double inflate) {
-  if (!(inflate >= 0.0)) {
-    set_error(std::string(who) + ": inflate must be >= 0 (and not NaN)");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  return HFCL_OK;
-}
-static size_t cull_chunk_size(const hfcl_lib* lib, size_t total) {
-  if (lib->scene_cull_chunk) return std::min<size_t>(lib->scene_cull_chunk, total);
-  constexpr size_t AUTO = size_t(1) << 22;
-  const size_t n_chunks = (total + AUTO - 1) / AUTO;
-  return (total + n_chunks - 1) / n_chunks;
-}
-
-// world boxes of the whole table -> d_out (n_conf * n_objects * 6 doubles), on st
-template <typename T>
-static int scene_boxes_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, double* d_out, hipStream_t st) {
-  size_t total;
-  int rc = cull_validate<T>(who, s, d_table, n_conf, total);
-  if (rc || n_conf == 0 || s->n_objects == 0) return rc;
-  if (!d_out) {
-    set_error(std::string(who) + ": null output");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  hfcl_lib* lib = s->lib;
-  HIP_TRY(hipSetDevice(lib->device));
-  rc = ensure_local_boxes(lib);
-  if (rc) return rc;
-  launch_cull_aabbs(st, d_table, std::is_same<T, float>::value, s->d_object_shape, lib->d_local_boxes, s->n_objects, n_conf * s->n_objects, d_out);
-  HIP_TRY(hipGetLastError());
-  return HFCL_OK;
-}
-
-// The cull of the whole flat range on st: the list (ids below `capacity`), conf_begin, the count.  Nothing is read back.
-template <typename T>
-static int cull_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, double inflate, uint64_t* d_ids, size_t capacity,
-                       uint64_t* d_conf_begin, uint64_t* d_n_listed, hipStream_t st) {
-  size_t total;
-  int rc = cull_validate<T>(who, s, d_table, n_conf, total);
-  if (rc) return rc;
-  rc = cull_check_inflate(who, inflate);
-  if (rc) return rc;
-  if (!d_n_listed) {
-    set_error(std::string(who) + ": null count");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  hfcl_lib* lib = s->lib;
-  HIP_TRY(hipSetDevice(lib->device));
-  if (!total) {  // no query: an empty list
-    HIP_TRY(hipMemsetAsync(d_n_listed, 0, sizeof(uint64_t), st));
-    if (d_conf_begin) HIP_TRY(hipMemsetAsync(d_conf_begin, 0, (n_conf + 1) * sizeof(uint64_t), st));
-    return HFCL_OK;
-  }
-  rc = ensure_local_boxes(lib);
-  if (rc) return rc;
-  hfcl_lib::SceneWs& w = lib->scene;
-  const size_t chunk = cull_chunk_size(lib, total);
-  const size_t conf_per_chunk = std::min<size_t>(n_conf, chunk / s->n_pairs + 2);
-  const size_t n_blocks = (chunk + CULL_BLOCK - 1) / CULL_BLOCK;
-  rc = scene_grow(&w.d_boxes, w.boxes_cap, conf_per_chunk * s->n_objects, 6 * sizeof(double));
-  if (!rc) rc = scene_grow(&w.d_words, w.words_cap, n_blocks * CULL_WAVES, sizeof(uint64_t));
-  if (!rc && n_blocks > w.blocks_cap) {
-    hipFree(w.d_block_counts);
-    hipFree(w.d_block_offsets);
-    w.d_block_counts = nullptr;
-    w.d_block_offsets = nullptr;
-    w.blocks_cap = 0;
-    HIP_TRY(hipMalloc(&w.d_block_counts, n_blocks * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&w.d_block_offsets, n_blocks * sizeof(uint64_t)));
-    w.blocks_cap = n_blocks;
-  }
-  if (!rc && !w.d_running) HIP_TRY(hipMalloc(&w.d_running, 2 * sizeof(uint64_t)));
-  if (rc) return rc;
-  constexpr bool f32 = std::is_same<T, float>::value;
-  CullArgs a;
-  a.pairs = s->d_pairs;
-  a.boxes = w.d_boxes;
-  a.n_objects = s->n_objects;
-  a.n_pairs = uint32_t(s->n_pairs);
-  a.total = total;
-  a.n_conf = n_conf;
-  a.inflate = inflate;
-  a.words = w.d_words;
-  a.block_counts = w.d_block_counts;
-  a.block_offsets = w.d_block_offsets;
-  a.running = w.d_running;
-  a.ids = d_ids;
-  a.capacity = d_ids ? capacity : 0;
-  a.conf_begin = d_conf_begin;
-  a.n_listed = d_n_listed;
-  for (size_t q0 = 0; q0 < total; q0 += chunk) {
-    const size_t m = std::min(chunk, total - q0);
-    a.q0 = q0;
-    scene_query(q0, a.n_pairs, a.c0, a.p0);
-    a.m = uint32_t(m);
-    a.first = q0 == 0 ? 1 : 0;
-    a.c_box0 = a.c0;
-    const uint64_t c_last = (q0 + m - 1) / s->n_pairs;
-    const char* rows = static_cast<const char*>(d_table) + a.c0 * s->n_objects * SceneTypes<T>::WIDTH * sizeof(T);
-    launch_cull_aabbs(st, rows, f32, s->d_object_shape, lib->d_local_boxes, s->n_objects, (c_last - a.c0 + 1) * s->n_objects, w.d_boxes);
-    launch_cull_chunk(st, a);
-  }
-  HIP_TRY(hipGetLastError());
-  return HFCL_OK;
-}
-
-// the host forms' stream
-static int scene_host_stream(hfcl_lib::SceneWs& w) {
-  if (!w.s_cmp) HIP_TRY(hipStreamCreateWithFlags(&w.s_cmp, hipStreamNonBlocking));
-  return HFCL_OK;
-}
-// the table of a host form onto the device (w.d_table), on w.s_cmp
-static int scene_table_in(hfcl_lib::SceneWs& w, const void* table, size_t bytes) {
-  char* t = static_cast<char*>(w.d_table);
-  const int rc = scene_grow(&t, w.table_bytes, bytes, 1);
-  w.d_table = t;
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(w.d_table, table, bytes, hipMemcpyHostToDevice, w.s_cmp));
-  return HFCL_OK;
-}
-// The cull of a table that is on the device into the library's own list (w.d_ids, w.d_conf_begin), and the one read-back: the count.
-// A list that outgrows the buffer is culled again into a larger one.
-template <typename T>
-static int cull_into_workspace(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, size_t total, double inflate, bool want_ids,
-                               uint64_t& n_listed) {
-  hfcl_lib* lib = s->lib;
-  hfcl_lib::SceneWs& w = lib->scene;
-  int rc = scene_grow(&w.d_conf_begin, w.conf_begin_cap, n_conf + 1, sizeof(uint64_t));
-  if (rc) return rc;
-  if (!w.d_running) HIP_TRY(hipMalloc(&w.d_running, 2 * sizeof(uint64_t)));
-  if (want_ids) {
-    rc = scene_grow(&w.d_ids, w.ids_cap, std::min<size_t>(total, std::max<size_t>(total / 8, 4096)), sizeof(uint64_t));
-    if (rc) return rc;
-  }
-  for (int pass = 0; pass < 2; ++pass) {
-    rc = cull_device<T>(who, s, d_table, n_conf, inflate, want_ids ? w.d_ids : nullptr, w.ids_cap, w.d_conf_begin, w.d_running + 1, w.s_cmp);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(&n_listed, w.d_running + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
-    HIP_TRY(hipStreamSynchronize(w.s_cmp));
-    if (!want_ids || n_listed <= w.ids_cap) break;
-    rc = scene_grow(&w.d_ids, w.ids_cap, size_t(n_listed), sizeof(uint64_t));
-    if (rc) return rc;
-  }
-  return HFCL_OK;
-}
-
-template <typename T>
-static int scene_cull_host(const char* who, hfcl_scene* s, const void* table, size_t n_conf, double inflate, uint64_t* query_ids, size_t capacity,
-                           uint64_t* conf_begin, size_t* n_listed) {
-  size_t total;
-  int rc = cull_validate<T>(who, s, table, n_conf, total);
-  if (!rc) rc = cull_check_inflate(who, inflate);
-  if (!rc && !n_listed) {
-    set_error(std::string(who) + ": null count");
-    rc = HFCL_ERR_INVALID_ARGUMENT;
-  }
-  if (rc) return rc;
-  *n_listed = 0;
-  if (!total) {
-    if (conf_begin) memset(conf_begin, 0, (n_conf + 1) * sizeof(uint64_t));
-    return HFCL_OK;
-  }
-  hfcl_lib* lib = s->lib;
-  hfcl_lib::SceneWs& w = lib->scene;
-  HIP_TRY(hipSetDevice(lib->device));
-  rc = scene_host_stream(w);
-  if (!rc) rc = scene_table_in(w, table, n_conf * s->n_objects * SceneTypes<T>::WIDTH * sizeof(T));
-  uint64_t n = 0;
-  if (!rc) rc = cull_into_workspace<T>(who, s, w.d_table, n_conf, total, inflate, query_ids != nullptr, n);
-  if (rc) {
-    hipStreamSynchronize(w.s_cmp);
-    return rc;
-  }
-  *n_listed = size_t(n);
-  if (query_ids && capacity < n) {
-    set_error(std::string(who) + ": " + std::to_string(n) + " queries survive, the list holds " + std::to_string(capacity));
-    return HFCL_ERR_LIMIT;
-  }
-  if (query_ids && n) HIP_TRY(hipMemcpyAsync(query_ids, w.d_ids, n * sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
-  if (conf_begin) HIP_TRY(hipMemcpyAsync(conf_begin, w.d_conf_begin, (n_conf + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
-  HIP_TRY(hipStreamSynchronize(w.s_cmp));
-  return HFCL_OK;
-}
-
-template <typename T>
-static int scene_boxes_host(const char* who, hfcl_scene* s, const void* table, size_t n_conf, double* aabbs_out) {
-  size_t total;
-  int rc = cull_validate<T>(who, s, table, n_conf, total);
-  if (rc || n_conf == 0 || s->n_objects == 0) return rc;
-  if (!aabbs_out) {
-    set_error(std::string(who) + ": null output");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  hfcl_lib* lib = s->lib;
-  hfcl_lib::SceneWs& w = lib->scene;
-  HIP_TRY(hipSetDevice(lib->device));
-  const size_t rows = n_conf * s->n_objects;
-  rc = scene_host_stream(w);
-  if (!rc) rc = scene_grow(&w.d_boxes, w.boxes_cap, rows, 6 * sizeof(double));
-  if (!rc) rc = scene_table_in(w, table, rows * SceneTypes<T>::WIDTH * sizeof(T));
-  if (!rc) rc = scene_boxes_device<T>(who, s, w.d_table, n_conf, w.d_boxes, w.s_cmp);
-  if (rc) {
-    hipStreamSynchronize(w.s_cmp);
-    return rc;
-  }
-  HIP_TRY(hipMemcpyAsync(aabbs_out, w.d_boxes, rows * 6 * sizeof(double), hipMemcpyDeviceToHost, w.s_cmp));
-  HIP_TRY(hipStreamSynchronize(w.s_cmp));
-  return HFCL_OK;
-}
-
-// fold partials a chunk of the list can need: a slot per piece of every configuration it can span -- any number of them, whatever its
-// length, since configurations without an entry lie in between (none when a pair list is one piece)
-static size_t scene_listed_pieces_bound(size_t n_pairs, size_t n_conf) {
-  const uint32_t shares = scene_shares(uint32_t(n_pairs));
-  return shares <= 1u ? 0 : n_conf * shares;
-}
-// expansion of the chunk [k0, k0 + m) of the list, the batch, the fold: all on st
-template <typename T>
-static int scene_listed_chunk_run(hfcl_scene* s, const void* d_table, size_t n_conf, const uint64_t* d_ids, const uint64_t* d_conf_begin, size_t k0,
-                                  size_t m, const hfcl_collision_request* creq, const hfcl_distance_request* dreq,
-                                  typename SceneTypes<T>::R* d_rec, hfcl_scene_summary* d_summary, const hfcl_guess* d_gin, hfcl_guess* d_gout,
-                                  hipStream_t st) {
-  hfcl_lib* lib = s->lib;
-  hfcl_lib::SceneWs& w = lib->scene;
-  constexpr bool f32 = std::is_same<T, float>::value;
-  const int max_blocks = lib->n_cus * 16;
-  SceneExpandArgs ea;
-  ea.pairs = s->d_pairs;
-  ea.object_shape = s->d_object_shape;
-  ea.object_tf = d_table;
-  ea.n_objects = s->n_objects;
-  ea.n_pairs = uint32_t(s->n_pairs);
-  ea.q0 = 0;
-  ea.c0 = 0;
-  ea.p0 = 0;
-  ea.m = uint32_t(m);
-  ea.s1 = w.d_s1;
-  ea.s2 = w.d_s2;
-  ea.tf1 = w.d_tf1;
-  ea.tf2 = w.d_tf2;
-  launch_scene_expand_listed(st, ea, d_ids + k0, f32, max_blocks);
-  const int rc = scene_batch(lib, w.d_s1, w.d_s2, w.d_tf1, w.d_tf2, m, creq, dreq, d_rec, d_gin, d_gout, st);
-  if (rc) return rc;
-  if (d_summary) {
-    SceneFoldListedArgs fa;
-    fa.rec = d_rec;
-    fa.ids = d_ids;
-    fa.conf_begin = d_conf_begin;
-    fa.k0 = k0;
-    fa.k1 = k0 + m;
-    fa.n_pairs = uint32_t(s->n_pairs);
-    fa.margin = creq ? creq->security_margin : 0.0;
-    fa.collide = creq ? 1 : 0;
-    fa.summary = d_summary;
-    fa.partials = scene_shares(fa.n_pairs) > 1u ? w.d_partials : nullptr;
-    fa.n_conf = n_conf;
-    launch_scene_fold_listed(st, fa, f32, max_blocks);
-  }
-  return HFCL_OK;
-}
-
-// The device form on a list.  The ids are not checked: ascending, below n_conf * n_pairs, conf_begin theirs -- as hfcl_scene_cull_device leaves them.
-template <typename T>
-static int scene_listed_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const uint64_t* d_ids, size_t n_listed,
-                               const uint64_t* d_conf_begin, const hfcl_collision_request* creq, const hfcl_distance_request* dreq,
-                               typename SceneTypes<T>::R* d_out, hfcl_scene_summary* d_summary, const hfcl_guess* d_gin, hfcl_guess* d_gout,
-                               hipStream_t st) {
-  size_t total;
-  int rc = scene_validate<T>(who, s, d_table, n_conf, creq, dreq, d_out, d_summary, total);
-  if (rc) return rc;
-  if (d_summary && !d_conf_begin) {
-    set_error(std::string(who) + ": summaries need conf_begin");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  if (n_listed > total) {
-    set_error(std::string(who) + ": more list entries than queries");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  if (n_listed && !d_ids) {
-    set_error(std::string(who) + ": null list");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  hfcl_lib* lib = s->lib;
-  HIP_TRY(hipSetDevice(lib->device));
-  if (d_summary) launch_scene_summary_init(st, d_summary, n_conf, lib->n_cus * 16);
-  if (!n_listed) {
-    HIP_TRY(hipGetLastError());
-    return HFCL_OK;
-  }
-  const size_t chunk = scene_chunk_size(lib, n_listed);
-  rc = scene_workspace(lib, chunk, d_out ? 0 : 1, false, 0, d_summary ? scene_listed_pieces_bound(s->n_pairs, n_conf) : 0);
-  if (rc) return rc;
-  for (size_t k0 = 0; k0 < n_listed; k0 += chunk) {
-    const size_t m = std::min(chunk, n_listed - k0);
-    auto* rec = d_out ? d_out + k0 : static_cast<typename SceneTypes<T>::R*>(lib->scene.d_rec[0]);
-    rc = scene_listed_chunk_run<T>(s, d_table, n_conf, d_ids, d_conf_begin, k0, m, creq, dreq, rec, d_summary, d_gin ? d_gin + k0 : nullptr,
-                                   d_gout ? d_gout + k0 : nullptr, st);
-    if (rc) {
-      scene_join_side(lib, st);
-      return rc;
-    }
-  }
-  HIP_TRY(hipGetLastError());
-  return HFCL_OK;
-}
-
-// what the culled host forms (hfcl_scene_*_culled) add to scene_host
-struct SceneCull {
-  double inflate;
-  size_t out_capacity;
-  uint64_t* query_ids_out;   // nullptr or out_capacity
-  uint64_t* conf_begin_out;  // nullptr or n_conf + 1
-  size_t* n_listed;
-};
-
-// Host form.  The object table goes in once; chunk k computes on one stream while chunk k - 1's records leave on another from the other of
-// two record buffers (the copy is issued AFTER chunk k's launches: a copy into pageable memory holds its caller until the data has moved);
-// the summaries come back once at the end.  No feeder threads: nothing per pair goes in.
-template <typename T>
-static int scene_host(const char* who, hfcl_scene* s, const void* table, size_t n_conf, const hfcl_collision_request* creq,
-                      const hfcl_distance_request* dreq, typename SceneTypes<T>::R* out, hfcl_scene_summary* summary, const hfcl_guess* gin,
-                      hfcl_guess* gout, const SceneCull* cull = nullptr) {
-  using R = typename SceneTypes<T>::R;
-  size_t total;
-  int rc = scene_validate<T>(who, s, table, n_conf, creq, dreq, out, summary, total);
-  if (!rc && cull) {
-    rc = cull_check_inflate(who, cull->inflate);
-    if (!rc && !cull->n_listed) {
-      set_error(std::string(who) + ": null count");
-      rc = HFCL_ERR_INVALID_ARGUMENT;
-    }
-    if (!rc) *cull->n_listed = 0;
-  }
-  auto nothing_listed = [&]() {  // no surviving query: an empty list, the summaries of configurations without records
-    if (cull->conf_begin_out) memset(cull->conf_begin_out, 0, (n_conf + 1) * sizeof(uint64_t));
-    for (size_t c = 0; summary && c < n_conf; ++c) scene_summary_init(summary[c]);
-    return HFCL_OK;
-  };
-  if (!rc && !total && cull) return nothing_listed();
-  if (rc || !total) return rc;
-  hfcl_lib* lib = s->lib;
-  hfcl_lib::SceneWs& w = lib->scene;
-  HIP_TRY(hipSetDevice(lib->device));
-  if (!w.s_cmp) HIP_TRY(hipStreamCreateWithFlags(&w.s_cmp, hipStreamNonBlocking));
-  if (!w.s_copy) HIP_TRY(hipStreamCreateWithFlags(&w.s_copy, hipStreamNonBlocking));
-  for (int k = 0; k < 2; ++k) {
-    if (!w.ev_done[k]) HIP_TRY(hipEventCreateWithFlags(&w.ev_done[k], hipEventDisableTiming));
-    if (!w.ev_copied[k]) HIP_TRY(hipEventCreateWithFlags(&w.ev_copied[k], hipEventDisableTiming));
-  }
-  const size_t table_bytes = n_conf * s->n_objects * SceneTypes<T>::WIDTH * sizeof(T);
-  size_t work = total;  // records of the call: every query, or (culled form) the surviving ones
-  if (cull) {  // the table goes in, the cull runs, the count comes back: 8 bytes, the one read-back before the narrow phase
-    rc = scene_table_in(w, table, table_bytes);
-    uint64_t n = 0;
-    if (!rc) rc = cull_into_workspace<T>(who, s, w.d_table, n_conf, total, cull->inflate, true, n);
-    if (rc) {
-      hipStreamSynchronize(w.s_cmp);
-      return rc;
-    }
-    *cull->n_listed = size_t(n);
-    if ((out || gout || cull->query_ids_out) && cull->out_capacity < n) {
-      set_error(std::string(who) + ": " + std::to_string(n) + " queries survive, the outputs hold " + std::to_string(cull->out_capacity));
-      return HFCL_ERR_LIMIT;
-    }
-    if (!n) return nothing_listed();
-    if (cull->query_ids_out) HIP_TRY(hipMemcpyAsync(cull->query_ids_out, w.d_ids, n * sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
-    if (cull->conf_begin_out)
-      HIP_TRY(hipMemcpyAsync(cull->conf_begin_out, w.d_conf_begin, (n_conf + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
-    work = size_t(n);
-  }
-  const size_t chunk = scene_chunk_size(lib, work);
-  const size_t n_chunks = (work + chunk - 1) / chunk;
-  const bool back = out != nullptr || gout != nullptr;  // something per pair goes back: two buffers, the copy stream
-  rc = scene_workspace(lib, chunk, out ? 2 : 1, gin != nullptr, gout ? 2 : 0,
-                       !summary ? 0 : cull ? scene_listed_pieces_bound(s->n_pairs, n_conf) : scene_pieces_bound(s->n_pairs, chunk));
-  if (rc) return rc;
-  if (!cull) {
-    char* t = static_cast<char*>(w.d_table);
-    rc = scene_grow(&t, w.table_bytes, table_bytes, 1);
-    w.d_table = t;
-    if (rc) return rc;
-  }
-  if (summary) {
-    rc = scene_grow(&w.d_summary, w.summary_cap, n_conf, sizeof(hfcl_scene_summary));
-    if (rc) return rc;
-  }
-  constexpr int CS = hfcl_lib::SceneWs::COUNT_SLOTS;
-  constexpr size_t SLOT_WORDS = 2 * size_t(N_COUNTERS);
-  if (!w.h_counts) HIP_TRY(hipHostMalloc((void**)&w.h_counts, CS * SLOT_WORDS * sizeof(uint32_t), hipHostMallocDefault));
-  for (hipEvent_t& e : w.ev_counts)
-    if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  memset(w.h_counts, 0, CS * SLOT_WORDS * sizeof(uint32_t));  // (a skipped batch -- -inf margin -- copies no counters)
-  bool slot_split[CS] = {};
-  memset(lib->acc_counts, 0, sizeof(lib->acc_counts));
-  auto harvest = [&](int slot) {  // a finished chunk's bucket populations into the call's sums; the slot is free again
-    uint32_t* c = w.h_counts + size_t(slot) * SLOT_WORDS;
-    for (int i = 0; i < N_COUNTERS; ++i) lib->acc_counts[i] += c[i] + (slot_split[slot] ? c[N_COUNTERS + i] : 0u);
-    memset(c, 0, SLOT_WORDS * sizeof(uint32_t));
-  };
-  lib->in_host_batch = true;
-
-  auto finish = [&](int code) {  // nothing of this call stays in flight, whatever happened
-    hipStreamSynchronize(w.s_cmp);
-    hipStreamSynchronize(w.s_copy);
-    if (lib->side) hipStreamSynchronize(lib->side);
-    lib->in_host_batch = false;
-    lib->counts_dst = nullptr;
-    if (lib->helper) lib->helper->counts_dst = nullptr;
-    return code;
-  };
-#define SCENE_TRY(expr)                                                      \
-  do {                                                                       \
-    hipError_t _e = (expr);                                                  \
-    if (_e != hipSuccess) {                                                  \
-      set_error(std::string(#expr) + ": " + hipGetErrorString(_e));          \
-      return finish(HFCL_ERR_HIP);                                           \
-    }                                                                        \
-  } while (0)
-  auto copy_back = [&](size_t k) -> hipError_t {  // chunk k's records (and guesses) to the caller's arrays, behind its kernels
-    const int b = int(k & 1);
-    const size_t q0 = k * chunk, m = std::min(chunk, work - q0);
-    hipError_t e = hipStreamWaitEvent(w.s_copy, w.ev_done[b], 0);
-    if (e == hipSuccess && out) e = hipMemcpyAsync(out + q0, w.d_rec[b], m * sizeof(R), hipMemcpyDeviceToHost, w.s_copy);
-    if (e == hipSuccess && gout) e = hipMemcpyAsync(gout + q0, w.d_gout[b], m * sizeof(hfcl_guess), hipMemcpyDeviceToHost, w.s_copy);
-    if (e == hipSuccess) e = hipEventRecord(w.ev_copied[b], w.s_copy);
-    return e;
-  };
-
-  if (!cull) SCENE_TRY(hipMemcpyAsync(w.d_table, table, table_bytes, hipMemcpyHostToDevice, w.s_cmp));
-  if (cull && summary) launch_scene_summary_init(w.s_cmp, w.d_summary, n_conf, lib->n_cus * 16);
-  for (size_t k = 0; k < n_chunks; ++k) {
-    const int b = back ? int(k & 1) : 0;
-    const size_t q0 = k * chunk, m = std::min(chunk, work - q0);
-    if (back && k >= 2) SCENE_TRY(hipStreamWaitEvent(w.s_cmp, w.ev_copied[b], 0));  // chunk k - 2 has left the buffers
-    if (gin) SCENE_TRY(hipMemcpyAsync(w.d_gin, gin + q0, m * sizeof(hfcl_guess), hipMemcpyHostToDevice, w.s_cmp));
-    const int slot = int(k % CS);
-    if (k >= size_t(CS)) {  // the chunk that used this slot has run: its counters are on the host
-      SCENE_TRY(hipEventSynchronize(w.ev_counts[slot]));
-      harvest(slot);
-    }
-    lib->counts_dst = w.h_counts + size_t(slot) * SLOT_WORDS;
-    if (batch_splits(lib, m)) {
-      rc = ensure_helper(lib);
-      if (rc) return finish(rc);
-      lib->helper->counts_dst = lib->counts_dst + N_COUNTERS;
-    }
-    rc = cull ? scene_listed_chunk_run<T>(s, w.d_table, n_conf, w.d_ids, w.d_conf_begin, q0, m, creq, dreq, static_cast<R*>(w.d_rec[out ? b : 0]),
-                                          summary ? w.d_summary : nullptr, gin ? w.d_gin : nullptr, gout ? w.d_gout[b] : nullptr, w.s_cmp)
-              : scene_chunk_run<T>(s, w.d_table, q0, m, creq, dreq, static_cast<R*>(w.d_rec[out ? b : 0]), summary ? w.d_summary : nullptr,
-                                   gin ? w.d_gin : nullptr, gout ? w.d_gout[b] : nullptr, w.s_cmp);
-    if (rc) return finish(rc);
-    slot_split[slot] = lib->last_split;
-    SCENE_TRY(hipEventRecord(w.ev_counts[slot], w.s_cmp));
-    if (back) {
-      SCENE_TRY(hipEventRecord(w.ev_done[b], w.s_cmp));
-      if (k >= 1) SCENE_TRY(copy_back(k - 1));
-    }
-  }
-  if (back) SCENE_TRY(copy_back(n_chunks - 1));
-  if (summary) SCENE_TRY(hipMemcpyAsync(summary, w.d_summary, n_conf * sizeof(hfcl_scene_summary), hipMemcpyDeviceToHost, w.s_cmp));
-  SCENE_TRY(hipStreamSynchronize(w.s_cmp));
-  SCENE_TRY(hipStreamSynchronize(w.s_copy));
-  SCENE_TRY(hipGetLastError());
-#undef SCENE_TRY
-  for (int slot = 0; slot < CS && size_t(slot) < n_chunks; ++slot) harvest(slot);
-  lib->in_host_batch = false;
-  lib->counts_dst = nullptr;
-  if (lib->helper) lib->helper->counts_dst = nullptr;
-  lib->last_host = true;
-  return host_batch_checks(lib, creq, dreq);
-}
-
-extern "C" {
-
-hfcl_scene* hfcl_scene_create(hfcl_lib* lib, const uint32_t* object_shape, size_t n_objects, const uint32_t* pairs, size_t n_pairs) {
-  if (!lib) {
-    set_error("hfcl_scene_create: null library");
-    return nullptr;
-  }
-  if (n_objects && !object_shape) {
-    set_error("hfcl_scene_create: null object table");
-    return nullptr;
-  }
-  for (size_t o = 0; o < n_objects; ++o)
-    if (object_shape[o] >= lib->n_shapes) {
-      set_error("hfcl_scene_create: shape id " + std::to_string(object_shape[o]) + " of object " + std::to_string(o) + " is outside the library");
-      return nullptr;
-    }
-  // (no return code here: the two causes that are not HFCL_ERR_INVALID_ARGUMENT name theirs at the head of the message)
-  if (const int rc = scene_check_pairs("hfcl_scene_create", pairs, n_pairs, n_objects)) {
-    if (rc == HFCL_ERR_LIMIT) set_error("HFCL_ERR_LIMIT: " + g_last_error);
-    return nullptr;
-  }
-  if (hipSetDevice(lib->device) != hipSuccess) {
-    set_error("HFCL_ERR_HIP: hfcl_scene_create: hipSetDevice failed");
-    return nullptr;
-  }
-  hfcl_scene* s = new hfcl_scene();
-  s->lib = lib;
-  s->n_objects = n_objects;
-  s->n_pairs = n_pairs;
-  s->epoch = lib->shapes_epoch;
-  if (scene_upload(&s->d_object_shape, object_shape, n_objects) != HFCL_OK || scene_upload(&s->d_pairs, pairs, 2 * n_pairs) != HFCL_OK) {
-    set_error("HFCL_ERR_HIP: hfcl_scene_create: " + g_last_error);
-    hfcl_scene_destroy(s);
-    return nullptr;
-  }
-  return s;
-}
-
-int hfcl_scene_set_pairs(hfcl_scene* s, const uint32_t* pairs, size_t n_pairs) {
-  if (!s) {
-    set_error("hfcl_scene_set_pairs: null scene");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  int rc = scene_check_pairs("hfcl_scene_set_pairs", pairs, n_pairs, s->n_objects);
-  if (rc) return rc;
-  HIP_TRY(hipSetDevice(s->lib->device));
-  uint32_t* d = nullptr;
-  rc = scene_upload(&d, pairs, 2 * n_pairs);
-  if (rc) return rc;
-  hipFree(s->d_pairs);  // (waits for the device: a query in flight on some stream may still be reading the old list)
-  s->d_pairs = d;
-  s->n_pairs = n_pairs;
-  return HFCL_OK;
-}
-
-void hfcl_scene_destroy(hfcl_scene* s) {
-  if (!s) return;
-  hipSetDevice(s->lib->device);
-  hipFree(s->d_object_shape);
-  hipFree(s->d_pairs);
-  delete s;
-}
-size_t hfcl_scene_num_objects(const hfcl_scene* s) { return s ? s->n_objects : 0; }
-size_t hfcl_scene_num_pairs(const hfcl_scene* s) { return s ? s->n_pairs : 0; }
-
-int hfcl_scene_collide(hfcl_scene* s, const double* object_tf, size_t n_conf, const hfcl_collision_request* req, hfcl_result* out,
-                       hfcl_scene_summary* summary, const hfcl_guess* guess_in, hfcl_guess* guess_out) {
-  return scene_host<double>("hfcl_scene_collide", s, object_tf, n_conf, req, nullptr, out, summary, guess_in, guess_out);
-}
-int hfcl_scene_distance(hfcl_scene* s, const double* object_tf, size_t n_conf, const hfcl_distance_request* req, hfcl_result* out,
-                        hfcl_scene_summary* summary, const hfcl_guess* guess_in, hfcl_guess* guess_out) {
-  if (s && !req) {
-    set_error("null request");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  return scene_host<double>("hfcl_scene_distance", s, object_tf, n_conf, nullptr, req, out, summary, guess_in, guess_out);
-}
-int hfcl_scene_collide_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const hfcl_collision_request* req, hfcl_result* d_out,
-                              hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in, hfcl_guess* d_guess_out, void* stream) {
-  return scene_device<double>("hfcl_scene_collide_device", s, d_object_tf, n_conf, req, nullptr, d_out, d_summary, d_guess_in, d_guess_out,
-                              (hipStream_t)stream);
-}
-int hfcl_scene_distance_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const hfcl_distance_request* req, hfcl_result* d_out,
-                               hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in, hfcl_guess* d_guess_out, void* stream) {
-  if (s && !req) {
-    set_error("null request");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  return scene_device<double>("hfcl_scene_distance_device", s, d_object_tf, n_conf, nullptr, req, d_out, d_summary, d_guess_in, d_guess_out,
-                              (hipStream_t)stream);
-}
-int hfcl_scene_collide_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, const hfcl_collision_request* req, hfcl_result_f32* out,
-                           hfcl_scene_summary* summary) {
-  return scene_host<float>("hfcl_scene_collide_f32", s, object_pose, n_conf, req, nullptr, out, summary, nullptr, nullptr);
-}
-int hfcl_scene_distance_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, const hfcl_distance_request* req, hfcl_result_f32* out,
-                            hfcl_scene_summary* summary) {
-  if (s && !req) {
-    set_error("null request");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  return scene_host<float>("hfcl_scene_distance_f32", s, object_pose, n_conf, nullptr, req, out, summary, nullptr, nullptr);
-}
-int hfcl_scene_collide_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, const hfcl_collision_request* req,
-                                  hfcl_result_f32* d_out, hfcl_scene_summary* d_summary, void* stream) {
-  return scene_device<float>("hfcl_scene_collide_device_f32", s, d_object_pose, n_conf, req, nullptr, d_out, d_summary, nullptr, nullptr,
-                             (hipStream_t)stream);
-}
-int hfcl_scene_distance_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, const hfcl_distance_request* req,
-                                   hfcl_result_f32* d_out, hfcl_scene_summary* d_summary, void* stream) {
-  if (s && !req) {
-    set_error("null request");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  return scene_device<float>("hfcl_scene_distance_device_f32", s, d_object_pose, n_conf, nullptr, req, d_out, d_summary, nullptr, nullptr,
-                             (hipStream_t)stream);
-}
-
-// ---- culling the pair list per configuration ---------------------------------------------------------------------------------------
-int hfcl_scene_world_aabbs(hfcl_scene* s, const double* object_tf, size_t n_conf, double* aabbs_out) {
-  return scene_boxes_host<double>("hfcl_scene_world_aabbs", s, object_tf, n_conf, aabbs_out);
-}
-int hfcl_scene_world_aabbs_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, double* aabbs_out) {
-  return scene_boxes_host<float>("hfcl_scene_world_aabbs_f32", s, object_pose, n_conf, aabbs_out);
-}
-int hfcl_scene_world_aabbs_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, double* d_aabbs_out, void* stream) {
-  return scene_boxes_device<double>("hfcl_scene_world_aabbs_device", s, d_object_tf, n_conf, d_aabbs_out, (hipStream_t)stream);
-}
-int hfcl_scene_world_aabbs_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, double* d_aabbs_out, void* stream) {
-  return scene_boxes_device<float>("hfcl_scene_world_aabbs_device_f32", s, d_object_pose, n_conf, d_aabbs_out, (hipStream_t)stream);
-}
-int hfcl_scene_cull(hfcl_scene* s, const double* object_tf, size_t n_conf, double inflate, uint64_t* query_ids, size_t capacity,
-                    uint64_t* conf_begin, size_t* n_listed) {
-  return scene_cull_host<double>("hfcl_scene_cull", s, object_tf, n_conf, inflate, query_ids, capacity, conf_begin, n_listed);
-}
-int hfcl_scene_cull_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, double inflate, uint64_t* query_ids, size_t capacity,
-                        uint64_t* conf_begin, size_t* n_listed) {
-  return scene_cull_host<float>("hfcl_scene_cull_f32", s, object_pose, n_conf, inflate, query_ids, capacity, conf_begin, n_listed);
-}
-int hfcl_scene_cull_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, double inflate, uint64_t* d_query_ids, size_t capacity,
-                           uint64_t* d_conf_begin, uint64_t* d_n_listed, void* stream) {
-  return cull_device<double>("hfcl_scene_cull_device", s, d_object_tf, n_conf, inflate, d_query_ids, capacity, d_conf_begin, d_n_listed,
-                             (hipStream_t)stream);
-}
-int hfcl_scene_cull_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, double inflate, uint64_t* d_query_ids, size_t capacity,
-                               uint64_t* d_conf_begin, uint64_t* d_n_listed, void* stream) {
-  return cull_device<float>("hfcl_scene_cull_device_f32", s, d_object_pose, n_conf, inflate, d_query_ids, capacity, d_conf_begin, d_n_listed,
-                            (hipStream_t)stream);
-}
-#define HFCL_NEED_DREQ()                        \
-  if (s && !req) {                              \
-    set_error("null request");                  \
-    return HFCL_ERR_INVALID_ARGUMENT;           \
-  }
-int hfcl_scene_collide_listed_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const uint64_t* d_query_ids, size_t n_listed,
-                                     const uint64_t* d_conf_begin, const hfcl_collision_request* req, hfcl_result* d_out,
-                                     hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in, hfcl_guess* d_guess_out, void* stream) {
-  return scene_listed_device<double>("hfcl_scene_collide_listed_device", s, d_object_tf, n_conf, d_query_ids, n_listed, d_conf_begin, req, nullptr,
-                                     d_out, d_summary, d_guess_in, d_guess_out, (hipStream_t)stream);
-}
-int hfcl_scene_distance_listed_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const uint64_t* d_query_ids, size_t n_listed,
-                                      const uint64_t* d_conf_begin, const hfcl_distance_request* req, hfcl_result* d_out,
-                                      hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in, hfcl_guess* d_guess_out, void* stream) {
-  HFCL_NEED_DREQ()
-  return scene_listed_device<double>("hfcl_scene_distance_listed_device", s, d_object_tf, n_conf, d_query_ids, n_listed, d_conf_begin, nullptr, req,
-                                     d_out, d_summary, d_guess_in, d_guess_out, (hipStream_t)stream);
-}
-int hfcl_scene_collide_listed_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, const uint64_t* d_query_ids, size_t n_listed,
-                                         const uint64_t* d_conf_begin, const hfcl_collision_request* req, hfcl_result_f32* d_out,
-                                         hfcl_scene_summary* d_summary, void* stream) {
-  return scene_listed_device<float>("hfcl_scene_collide_listed_device_f32", s, d_object_pose, n_conf, d_query_ids, n_listed, d_conf_begin, req,
-                                    nullptr, d_out, d_summary, nullptr, nullptr, (hipStream_t)stream);
-}
-int hfcl_scene_distance_listed_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, const uint64_t* d_query_ids, size_t n_listed,
-                                          const uint64_t* d_conf_begin, const hfcl_distance_request* req, hfcl_result_f32* d_out,
-                                          hfcl_scene_summary* d_summary, void* stream) {
-  HFCL_NEED_DREQ()
-  return scene_listed_device<float>("hfcl_scene_distance_listed_device_f32", s, d_object_pose, n_conf, d_query_ids, n_listed, d_conf_begin, nullptr,
-                                    req, d_out, d_summary, nullptr, nullptr, (hipStream_t)stream);
-}
-int hfcl_scene_collide_culled(hfcl_scene* s, const double* object_tf, size_t n_conf, double inflate, const hfcl_collision_request* req,
-                              hfcl_result* out, size_t out_capacity, uint64_t* query_ids_out, uint64_t* conf_begin_out,
-                              hfcl_scene_summary* summary, const hfcl_guess* guess_in, hfcl_guess* guess_out, size_t* n_listed) {
-  const SceneCull cull{inflate, out_capacity, query_ids_out, conf_begin_out, n_listed};
-  return scene_host<double>("hfcl_scene_collide_culled", s, object_tf, n_conf, req, nullptr, out, summary, guess_in, guess_out, &cull);
-}
-int hfcl_scene_distance_culled(hfcl_scene* s, const double* object_tf, size_t n_conf, double inflate, const hfcl_distance_request* req,
-                               hfcl_result* out, size_t out_capacity, uint64_t* query_ids_out, uint64_t* conf_begin_out,
-                               hfcl_scene_summary* summary, const hfcl_guess* guess_in, hfcl_guess* guess_out, size_t* n_listed) {
-  HFCL_NEED_DREQ()
-  const SceneCull cull{inflate, out_capacity, query_ids_out, conf_begin_out, n_listed};
-  return scene_host<double>("hfcl_scene_distance_culled", s, object_tf, n_conf, nullptr, req, out, summary, guess_in, guess_out, &cull);
-}
-int hfcl_scene_collide_culled_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, double inflate, const hfcl_collision_request* req,
-                                  hfcl_result_f32* out, size_t out_capacity, uint64_t* query_ids_out, uint64_t* conf_begin_out,
-                                  hfcl_scene_summary* summary, size_t* n_listed) {
-  const SceneCull cull{inflate, out_capacity, query_ids_out, conf_begin_out, n_listed};
-  return scene_host<float>("hfcl_scene_collide_culled_f32", s, object_pose, n_conf, req, nullptr, out, summary, nullptr, nullptr, &cull);
-}
-int hfcl_scene_distance_culled_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, double inflate, const hfcl_distance_request* req,
-                                   hfcl_result_f32* out, size_t out_capacity, uint64_t* query_ids_out, uint64_t* conf_begin_out,
-                                   hfcl_scene_summary* summary, size_t* n_listed) {
-  HFCL_NEED_DREQ()
-  const SceneCull cull{inflate, out_capacity, query_ids_out, conf_begin_out, n_listed};
-  return scene_host<float>("hfcl_scene_distance_culled_f32", s, object_pose, n_conf, nullptr, req, out, summary, nullptr, nullptr, &cull);
-}
-#undef HFCL_NEED_DREQ
 
 }  // extern "C"

@@ -1,0 +1,923 @@
+// hfcl_host_scene.hip -- host side of the scene queries (hfcl_scene_*) and of the cull of their pair lists (the kernels: hfcl_k_scene.hip,
+// hfcl_k_cull.hip).  The library object and what this unit calls of hfcl_host.hip: hfcl_host.hpp.
+#include "hfcl_host.hpp"
+
+// =======================================================================================
+// Scene queries (include/hppfcl_amd.h: hfcl_scene_*): an object -> shape table and a pair list resident on the library's device; a call
+// evaluates the pair list for n_conf pose tables.  The flat query range q = c * n_pairs + p is cut into chunks; a chunk is expanded into the
+// per-pair arrays of the batch entry points (k_scene_expand*), goes through hfcl_*_batch_device* exactly as a caller's batch of that size
+// would, and its records are folded into the summaries of the configurations it touches (k_scene_fold).  No record changes on the way.
+// =======================================================================================
+struct hfcl_scene {
+  hfcl_lib* lib = nullptr;
+  size_t n_objects = 0, n_pairs = 0;
+  DevBuf<uint32_t> d_object_shape, d_pairs;
+  uint64_t epoch = 0;  // hfcl_lib::shapes_epoch when the scene was made
+};
+
+static int scene_check_pairs(const char* who, const uint32_t* pairs, size_t n_pairs, size_t n_objects) {
+  if (n_pairs > 0xFFFFFFF0ull) {
+    set_error(std::string(who) + ": pair list too long (max 2^32-16 pairs)");
+    return HFCL_ERR_LIMIT;
+  }
+  if (n_pairs && !pairs) {
+    set_error(std::string(who) + ": null pair list");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  for (size_t k = 0; k < 2 * n_pairs; ++k)
+    if (pairs[k] >= n_objects) {
+      set_error(std::string(who) + ": object index " + std::to_string(pairs[k]) + " of pair " + std::to_string(k / 2) + " is outside the " +
+                std::to_string(n_objects) + " objects");
+      return HFCL_ERR_INVALID_ARGUMENT;
+    }
+  return HFCL_OK;
+}
+static int scene_upload(DevBuf<uint32_t>& dst, const uint32_t* src, size_t words) {  // (dst: empty)
+  if (!words) return HFCL_OK;
+  HIP_TRY(dst.grow(words));
+  if (hipMemcpy(dst, src, words * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+    dst.reset();
+    set_error("scene: copy to the device failed");
+    return HFCL_ERR_HIP;
+  }
+  return HFCL_OK;
+}
+
+template <typename T> struct SceneTypes;
+template <> struct SceneTypes<double> {
+  using R = hfcl_result;
+  static constexpr size_t WIDTH = 12;
+};
+template <> struct SceneTypes<float> {
+  using R = hfcl_result_f32;
+  static constexpr size_t WIDTH = 7;
+};
+
+// a chunk through the batch entry point of its precision
+static int scene_batch(hfcl_lib* lib, const uint32_t* s1, const uint32_t* s2, const void* tf1, const void* tf2, size_t m,
+                       const hfcl_collision_request* creq, const hfcl_distance_request* dreq, hfcl_result* rec, const hfcl_guess* gin,
+                       hfcl_guess* gout, hipStream_t st) {
+  return creq ? hfcl_collide_batch_device(lib, s1, s2, static_cast<const double*>(tf1), static_cast<const double*>(tf2), m, creq, rec, gin, gout, st)
+              : hfcl_distance_batch_device(lib, s1, s2, static_cast<const double*>(tf1), static_cast<const double*>(tf2), m, dreq, rec, gin, gout, st);
+}
+static int scene_batch(hfcl_lib* lib, const uint32_t* s1, const uint32_t* s2, const void* tf1, const void* tf2, size_t m,
+                       const hfcl_collision_request* creq, const hfcl_distance_request* dreq, hfcl_result_f32* rec, const hfcl_guess*, hfcl_guess*,
+                       hipStream_t st) {
+  return creq ? hfcl_collide_batch_device_f32(lib, s1, s2, static_cast<const float*>(tf1), static_cast<const float*>(tf2), m, creq, rec, st)
+              : hfcl_distance_batch_device_f32(lib, s1, s2, static_cast<const float*>(tf1), static_cast<const float*>(tf2), m, dreq, rec, st);
+}
+
+// everything a scene call refuses before any work; total: n_conf * n_pairs (0: nothing to do)
+template <typename T>
+static int scene_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, const hfcl_collision_request* creq,
+                          const hfcl_distance_request* dreq, const void* out, const void* summary, size_t& total) {
+  total = 0;
+  if (!s) {
+    set_error(std::string(who) + ": null scene");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  QParams<T> q;
+  bool skip;
+  const int rc = creq ? setup_collide<T>(creq, q, skip) : setup_distance<T>(dreq, q);
+  if (rc) return rc;
+  if (!out && !summary) {
+    set_error(std::string(who) + ": records and summaries both NULL");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (s->epoch != s->lib->shapes_epoch) {
+    set_error(std::string(who) + ": the library's shapes were replaced (hfcl_lib_set_shapes) after this scene was created; create a new scene");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (n_conf == 0 || s->n_pairs == 0) return HFCL_OK;
+  if (!table) {
+    set_error(std::string(who) + ": null pose table");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (n_conf > ~size_t(0) / s->n_pairs || n_conf > ~size_t(0) / (s->n_objects * SceneTypes<T>::WIDTH * sizeof(T))) {
+    set_error(std::string(who) + ": n_conf * n_pairs overflows");
+    return HFCL_ERR_LIMIT;
+  }
+  total = n_conf * s->n_pairs;
+  return HFCL_OK;
+}
+// queries per chunk of a call of `total` queries: the option as given, or equal chunks of at most 2^21
+static size_t scene_chunk_size(const hfcl_lib* lib, size_t total) {
+  if (lib->scene_chunk) return std::min<size_t>(std::min<size_t>(lib->scene_chunk, total), 0xFFFFFFF0ull);
+  constexpr size_t AUTO = size_t(1) << 21;
+  const size_t n_chunks = (total + AUTO - 1) / AUTO;
+  return (total + n_chunks - 1) / n_chunks;
+}
+
+// workspace of chunks of up to m queries; recs: how many of the two record buffers; pieces: fold partials (0: none)
+static int scene_workspace(hfcl_lib* lib, size_t m, int recs, bool gin, int gouts, size_t pieces) {
+  hfcl_lib::SceneWs& w = lib->scene;
+  if (m > w.cap) {
+    reset_all(w.d_s1, w.d_s2, w.d_tf1, w.d_tf2);
+    w.cap = 0;
+    HIP_TRY(w.d_s1.grow(m));
+    HIP_TRY(w.d_s2.grow(m));
+    HIP_TRY(w.d_tf1.grow(m * 12 * sizeof(double)));  // (rows of either precision)
+    HIP_TRY(w.d_tf2.grow(m * 12 * sizeof(double)));
+    w.cap = m;
+  }
+  // (a buffer that grows is freed first, which waits for the device: nothing in flight reads the old one)
+  for (int k = 0; k < recs; ++k) HIP_TRY(w.d_rec[k].grow(m * sizeof(hfcl_result)));
+  if (gin) HIP_TRY(w.d_gin.grow(m));
+  for (int k = 0; k < gouts; ++k) HIP_TRY(w.d_gout[k].grow(m));
+  HIP_TRY(w.d_partials.grow(pieces));
+  return HFCL_OK;
+}
+// fold partials a chunk of m queries can need: none when a pair list is one piece
+static size_t scene_pieces_bound(size_t n_pairs, size_t m) {
+  if (scene_shares(uint32_t(n_pairs)) <= 1u) return 0;
+  // whole pieces inside the chunk, a cut one at either end, and one more cut per configuration boundary inside it
+  return m / SCENE_FOLD_SHARE + 2 + 2 * (m / n_pairs + 2);
+}
+
+// expansion of chunk [q0, q0 + m), the batch, the fold: all on st
+template <typename T>
+static int scene_chunk_run(hfcl_scene* s, const void* d_table, size_t q0, size_t m, const hfcl_collision_request* creq,
+                           const hfcl_distance_request* dreq, typename SceneTypes<T>::R* d_rec, hfcl_scene_summary* d_summary,
+                           const hfcl_guess* d_gin, hfcl_guess* d_gout, hipStream_t st) {
+  hfcl_lib* lib = s->lib;
+  hfcl_lib::SceneWs& w = lib->scene;
+  constexpr bool f32 = std::is_same<T, float>::value;
+  const int max_blocks = lib->n_cus * 16;
+  SceneExpandArgs ea;
+  ea.pairs = s->d_pairs;
+  ea.object_shape = s->d_object_shape;
+  ea.object_tf = d_table;
+  ea.n_objects = s->n_objects;
+  ea.n_pairs = uint32_t(s->n_pairs);
+  ea.q0 = q0;
+  scene_query(q0, ea.n_pairs, ea.c0, ea.p0);
+  ea.m = uint32_t(m);
+  ea.s1 = w.d_s1;
+  ea.s2 = w.d_s2;
+  ea.tf1 = w.d_tf1;
+  ea.tf2 = w.d_tf2;
+  launch_scene_expand(st, ea, f32, max_blocks);
+  const int rc = scene_batch(lib, w.d_s1, w.d_s2, w.d_tf1, w.d_tf2, m, creq, dreq, d_rec, d_gin, d_gout, st);
+  if (rc) return rc;
+  if (d_summary) {
+    SceneFoldArgs fa;
+    fa.rec = d_rec;
+    fa.q0 = q0;
+    fa.q1 = q0 + m;
+    fa.n_pairs = uint32_t(s->n_pairs);
+    fa.g0 = scene_piece_of(q0, fa.n_pairs);
+    fa.n_pieces = scene_piece_of(q0 + m - 1, fa.n_pairs) - fa.g0 + 1;
+    fa.margin = creq ? creq->security_margin : 0.0;
+    fa.collide = creq ? 1 : 0;
+    fa.summary = d_summary;
+    fa.partials = scene_shares(fa.n_pairs) > 1u ? w.d_partials : nullptr;
+    launch_scene_fold(st, fa, f32, max_blocks);
+  }
+  return HFCL_OK;
+}
+// An error after work was enqueued: the second half of a split batch may be running on the library's side stream -- the caller's stream
+// waits for it, so that "everything this call started is ordered before what the caller enqueues next" holds on the error path too
+static void scene_join_side(hfcl_lib* lib, hipStream_t st) {
+  if (lib->side && lib->ev_join && hipEventRecord(lib->ev_join, lib->side) == hipSuccess) (void)hipStreamWaitEvent(st, lib->ev_join, 0);
+}
+
+template <typename T>
+static int scene_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const hfcl_collision_request* creq,
+                        const hfcl_distance_request* dreq, typename SceneTypes<T>::R* d_out, hfcl_scene_summary* d_summary,
+                        const hfcl_guess* d_gin, hfcl_guess* d_gout, hipStream_t st) {
+  size_t total;
+  int rc = scene_validate<T>(who, s, d_table, n_conf, creq, dreq, d_out, d_summary, total);
+  if (rc || !total) return rc;
+  hfcl_lib* lib = s->lib;
+  HIP_TRY(hipSetDevice(lib->device));
+  const size_t chunk = scene_chunk_size(lib, total);
+  rc = scene_workspace(lib, chunk, d_out ? 0 : 1, false, 0, d_summary ? scene_pieces_bound(s->n_pairs, chunk) : 0);
+  if (rc) return rc;
+  for (size_t q0 = 0; q0 < total; q0 += chunk) {
+    const size_t m = std::min(chunk, total - q0);
+    auto* rec = d_out ? d_out + q0 : static_cast<typename SceneTypes<T>::R*>(lib->scene.d_rec[0].get());
+    rc = scene_chunk_run<T>(s, d_table, q0, m, creq, dreq, rec, d_summary, d_gin ? d_gin + q0 : nullptr, d_gout ? d_gout + q0 : nullptr, st);
+    if (rc) {
+      scene_join_side(lib, st);
+      return rc;
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  return HFCL_OK;
+}
+
+
+// ---------------------------------------------------------------------------------------
+// Culling the pair list per configuration (hfcl_scene_cull*), and the scene calls on the list that is left (hfcl_scene_*_listed*,
+// hfcl_scene_*_culled).  hfcl_k_cull.hip has the kernels, hfcl_cull.hpp the arithmetic.
+// ---------------------------------------------------------------------------------------
+// the library's local boxes on the device, rebuilt when shapes or meshes were registered since
+static int ensure_local_boxes(hfcl_lib* lib) {
+  if (!lib->local_boxes_dirty && lib->d_local_boxes) return HFCL_OK;
+  const double nan = __builtin_nan("");
+  std::vector<double> boxes(6 * lib->n_shapes);
+  for (size_t i = 0; i < lib->n_shapes; ++i) {
+    const hfcl_shape& s = lib->h_shapes[i];
+    Box3 b;
+    if (s.type == HFCL_BV_OBBRSS) {
+      if (s.bvh_index < lib->h_meshes.size())
+        b = mesh_local_box(lib->h_bvh_verts.data() + 3 * size_t(lib->h_meshes[s.bvh_index].vert_off), lib->h_mesh_nverts[s.bvh_index]);
+      else  // (no such model: the narrow phase refuses the pair; a NaN box keeps it in the list)
+        for (int k = 0; k < 3; ++k) b.lo[k] = b.hi[k] = nan;
+    } else {
+      b = shape_local_box(s, lib->h_verts.data());
+    }
+    for (int k = 0; k < 3; ++k) {
+      boxes[6 * i + k] = b.lo[k];
+      boxes[6 * i + 3 + k] = b.hi[k];
+    }
+  }
+  lib->d_local_boxes.reset();  // (waits for the device: nothing in flight reads the old table)
+  HIP_TRY(lib->d_local_boxes.grow(std::max<size_t>(boxes.size(), 6)));
+  HIP_TRY(hipMemcpy(lib->d_local_boxes, boxes.data(), boxes.size() * sizeof(double), hipMemcpyHostToDevice));
+  lib->local_boxes_dirty = false;
+  return HFCL_OK;
+}
+
+// what the cull calls refuse before any work; total: n_conf * n_pairs (0: no query)
+template <typename T>
+static int cull_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, size_t& total) {
+  total = 0;
+  if (!s) {
+    set_error(std::string(who) + ": null scene");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (s->epoch != s->lib->shapes_epoch) {
+    set_error(std::string(who) + ": the library's shapes were replaced (hfcl_lib_set_shapes) after this scene was created; create a new scene");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (n_conf == 0 || s->n_objects == 0) return HFCL_OK;
+  if (!table) {
+    set_error(std::string(who) + ": null pose table");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if ((s->n_pairs && n_conf > ~size_t(0) / s->n_pairs) || n_conf > ~size_t(0) / (s->n_objects * SceneTypes<T>::WIDTH * sizeof(T))) {
+    set_error(std::string(who) + ": n_conf * n_pairs overflows");
+    return HFCL_ERR_LIMIT;
+  }
+  total = n_conf * s->n_pairs;
+  return HFCL_OK;
+}
+static int cull_check_inflate(const char* who, double inflate) {
+  if (!(inflate >= 0.0)) {
+    set_error(std::string(who) + ": inflate must be >= 0 (and not NaN)");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  return HFCL_OK;
+}
+static size_t cull_chunk_size(const hfcl_lib* lib, size_t total) {
+  if (lib->scene_cull_chunk) return std::min<size_t>(lib->scene_cull_chunk, total);
+  constexpr size_t AUTO = size_t(1) << 22;
+  const size_t n_chunks = (total + AUTO - 1) / AUTO;
+  return (total + n_chunks - 1) / n_chunks;
+}
+
+// world boxes of the whole table -> d_out (n_conf * n_objects * 6 doubles), on st
+template <typename T>
+static int scene_boxes_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, double* d_out, hipStream_t st) {
+  size_t total;
+  int rc = cull_validate<T>(who, s, d_table, n_conf, total);
+  if (rc || n_conf == 0 || s->n_objects == 0) return rc;
+  if (!d_out) {
+    set_error(std::string(who) + ": null output");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  hfcl_lib* lib = s->lib;
+  HIP_TRY(hipSetDevice(lib->device));
+  rc = ensure_local_boxes(lib);
+  if (rc) return rc;
+  launch_cull_aabbs(st, d_table, std::is_same<T, float>::value, s->d_object_shape, lib->d_local_boxes, s->n_objects, n_conf * s->n_objects, d_out);
+  HIP_TRY(hipGetLastError());
+  return HFCL_OK;
+}
+
+// The cull of the whole flat range on st: the list (ids below `capacity`), conf_begin, the count.  Nothing is read back.
+template <typename T>
+static int cull_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, double inflate, uint64_t* d_ids, size_t capacity,
+                       uint64_t* d_conf_begin, uint64_t* d_n_listed, hipStream_t st) {
+  size_t total;
+  int rc = cull_validate<T>(who, s, d_table, n_conf, total);
+  if (rc) return rc;
+  rc = cull_check_inflate(who, inflate);
+  if (rc) return rc;
+  if (!d_n_listed) {
+    set_error(std::string(who) + ": null count");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  hfcl_lib* lib = s->lib;
+  HIP_TRY(hipSetDevice(lib->device));
+  if (!total) {  // no query: an empty list
+    HIP_TRY(hipMemsetAsync(d_n_listed, 0, sizeof(uint64_t), st));
+    if (d_conf_begin) HIP_TRY(hipMemsetAsync(d_conf_begin, 0, (n_conf + 1) * sizeof(uint64_t), st));
+    return HFCL_OK;
+  }
+  rc = ensure_local_boxes(lib);
+  if (rc) return rc;
+  hfcl_lib::SceneWs& w = lib->scene;
+  const size_t chunk = cull_chunk_size(lib, total);
+  const size_t conf_per_chunk = std::min<size_t>(n_conf, chunk / s->n_pairs + 2);
+  const size_t n_blocks = (chunk + CULL_BLOCK - 1) / CULL_BLOCK;
+  HIP_TRY(w.d_boxes.grow(conf_per_chunk * s->n_objects * 6));
+  HIP_TRY(w.d_words.grow(n_blocks * CULL_WAVES));
+  if (n_blocks > w.blocks_cap) {
+    reset_all(w.d_block_counts, w.d_block_offsets);
+    w.blocks_cap = 0;
+    HIP_TRY(w.d_block_counts.grow(n_blocks));
+    HIP_TRY(w.d_block_offsets.grow(n_blocks));
+    w.blocks_cap = n_blocks;
+  }
+  HIP_TRY(w.d_running.grow(2));
+  constexpr bool f32 = std::is_same<T, float>::value;
+  CullArgs a;
+  a.pairs = s->d_pairs;
+  a.boxes = w.d_boxes;
+  a.n_objects = s->n_objects;
+  a.n_pairs = uint32_t(s->n_pairs);
+  a.total = total;
+  a.n_conf = n_conf;
+  a.inflate = inflate;
+  a.words = w.d_words;
+  a.block_counts = w.d_block_counts;
+  a.block_offsets = w.d_block_offsets;
+  a.running = w.d_running;
+  a.ids = d_ids;
+  a.capacity = d_ids ? capacity : 0;
+  a.conf_begin = d_conf_begin;
+  a.n_listed = d_n_listed;
+  for (size_t q0 = 0; q0 < total; q0 += chunk) {
+    const size_t m = std::min(chunk, total - q0);
+    a.q0 = q0;
+    scene_query(q0, a.n_pairs, a.c0, a.p0);
+    a.m = uint32_t(m);
+    a.first = q0 == 0 ? 1 : 0;
+    a.c_box0 = a.c0;
+    const uint64_t c_last = (q0 + m - 1) / s->n_pairs;
+    const char* rows = static_cast<const char*>(d_table) + a.c0 * s->n_objects * SceneTypes<T>::WIDTH * sizeof(T);
+    launch_cull_aabbs(st, rows, f32, s->d_object_shape, lib->d_local_boxes, s->n_objects, (c_last - a.c0 + 1) * s->n_objects, w.d_boxes);
+    launch_cull_chunk(st, a);
+  }
+  HIP_TRY(hipGetLastError());
+  return HFCL_OK;
+}
+
+// the host forms' stream
+static int scene_host_stream(hfcl_lib::SceneWs& w) {
+  if (!w.s_cmp) HIP_TRY(w.s_cmp.create());
+  return HFCL_OK;
+}
+// the table of a host form onto the device (w.d_table), on w.s_cmp
+static int scene_table_in(hfcl_lib::SceneWs& w, const void* table, size_t bytes) {
+  HIP_TRY(w.d_table.grow(bytes));
+  HIP_TRY(hipMemcpyAsync(w.d_table, table, bytes, hipMemcpyHostToDevice, w.s_cmp));
+  return HFCL_OK;
+}
+// The cull of a table that is on the device into the library's own list (w.d_ids, w.d_conf_begin), and the one read-back: the count.
+// A list that outgrows the buffer is culled again into a larger one.
+template <typename T>
+static int cull_into_workspace(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, size_t total, double inflate, bool want_ids,
+                               uint64_t& n_listed) {
+  hfcl_lib* lib = s->lib;
+  hfcl_lib::SceneWs& w = lib->scene;
+  HIP_TRY(w.d_conf_begin.grow(n_conf + 1));
+  HIP_TRY(w.d_running.grow(2));
+  if (want_ids) HIP_TRY(w.d_ids.grow(std::min<size_t>(total, std::max<size_t>(total / 8, 4096))));
+  for (int pass = 0; pass < 2; ++pass) {
+    const int rc = cull_device<T>(who, s, d_table, n_conf, inflate, want_ids ? w.d_ids.get() : nullptr, w.d_ids.capacity(), w.d_conf_begin, w.d_running + 1, w.s_cmp);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(&n_listed, w.d_running + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
+    HIP_TRY(hipStreamSynchronize(w.s_cmp));
+    if (!want_ids || n_listed <= w.d_ids.capacity()) break;
+    HIP_TRY(w.d_ids.grow(size_t(n_listed)));
+  }
+  return HFCL_OK;
+}
+
+template <typename T>
+static int scene_cull_host(const char* who, hfcl_scene* s, const void* table, size_t n_conf, double inflate, uint64_t* query_ids, size_t capacity,
+                           uint64_t* conf_begin, size_t* n_listed) {
+  size_t total;
+  int rc = cull_validate<T>(who, s, table, n_conf, total);
+  if (!rc) rc = cull_check_inflate(who, inflate);
+  if (!rc && !n_listed) {
+    set_error(std::string(who) + ": null count");
+    rc = HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (rc) return rc;
+  *n_listed = 0;
+  if (!total) {
+    if (conf_begin) memset(conf_begin, 0, (n_conf + 1) * sizeof(uint64_t));
+    return HFCL_OK;
+  }
+  hfcl_lib* lib = s->lib;
+  hfcl_lib::SceneWs& w = lib->scene;
+  HIP_TRY(hipSetDevice(lib->device));
+  rc = scene_host_stream(w);
+  if (!rc) rc = scene_table_in(w, table, n_conf * s->n_objects * SceneTypes<T>::WIDTH * sizeof(T));
+  uint64_t n = 0;
+  if (!rc) rc = cull_into_workspace<T>(who, s, w.d_table, n_conf, total, inflate, query_ids != nullptr, n);
+  if (rc) {
+    hipStreamSynchronize(w.s_cmp);
+    return rc;
+  }
+  *n_listed = size_t(n);
+  if (query_ids && capacity < n) {
+    set_error(std::string(who) + ": " + std::to_string(n) + " queries survive, the list holds " + std::to_string(capacity));
+    return HFCL_ERR_LIMIT;
+  }
+  if (query_ids && n) HIP_TRY(hipMemcpyAsync(query_ids, w.d_ids, n * sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
+  if (conf_begin) HIP_TRY(hipMemcpyAsync(conf_begin, w.d_conf_begin, (n_conf + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
+  HIP_TRY(hipStreamSynchronize(w.s_cmp));
+  return HFCL_OK;
+}
+
+template <typename T>
+static int scene_boxes_host(const char* who, hfcl_scene* s, const void* table, size_t n_conf, double* aabbs_out) {
+  size_t total;
+  int rc = cull_validate<T>(who, s, table, n_conf, total);
+  if (rc || n_conf == 0 || s->n_objects == 0) return rc;
+  if (!aabbs_out) {
+    set_error(std::string(who) + ": null output");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  hfcl_lib* lib = s->lib;
+  hfcl_lib::SceneWs& w = lib->scene;
+  HIP_TRY(hipSetDevice(lib->device));
+  const size_t rows = n_conf * s->n_objects;
+  rc = scene_host_stream(w);
+  if (!rc) rc = [&]() -> int { HIP_TRY(w.d_boxes.grow(rows * 6)); return HFCL_OK; }();
+  if (!rc) rc = scene_table_in(w, table, rows * SceneTypes<T>::WIDTH * sizeof(T));
+  if (!rc) rc = scene_boxes_device<T>(who, s, w.d_table, n_conf, w.d_boxes, w.s_cmp);
+  if (rc) {
+    hipStreamSynchronize(w.s_cmp);
+    return rc;
+  }
+  HIP_TRY(hipMemcpyAsync(aabbs_out, w.d_boxes, rows * 6 * sizeof(double), hipMemcpyDeviceToHost, w.s_cmp));
+  HIP_TRY(hipStreamSynchronize(w.s_cmp));
+  return HFCL_OK;
+}
+
+// fold partials a chunk of the list can need: a slot per piece of every configuration it can span -- any number of them, whatever its
+// length, since configurations without an entry lie in between (none when a pair list is one piece)
+static size_t scene_listed_pieces_bound(size_t n_pairs, size_t n_conf) {
+  const uint32_t shares = scene_shares(uint32_t(n_pairs));
+  return shares <= 1u ? 0 : n_conf * shares;
+}
+// expansion of the chunk [k0, k0 + m) of the list, the batch, the fold: all on st
+template <typename T>
+static int scene_listed_chunk_run(hfcl_scene* s, const void* d_table, size_t n_conf, const uint64_t* d_ids, const uint64_t* d_conf_begin, size_t k0,
+                                  size_t m, const hfcl_collision_request* creq, const hfcl_distance_request* dreq,
+                                  typename SceneTypes<T>::R* d_rec, hfcl_scene_summary* d_summary, const hfcl_guess* d_gin, hfcl_guess* d_gout,
+                                  hipStream_t st) {
+  hfcl_lib* lib = s->lib;
+  hfcl_lib::SceneWs& w = lib->scene;
+  constexpr bool f32 = std::is_same<T, float>::value;
+  const int max_blocks = lib->n_cus * 16;
+  SceneExpandArgs ea;
+  ea.pairs = s->d_pairs;
+  ea.object_shape = s->d_object_shape;
+  ea.object_tf = d_table;
+  ea.n_objects = s->n_objects;
+  ea.n_pairs = uint32_t(s->n_pairs);
+  ea.q0 = 0;
+  ea.c0 = 0;
+  ea.p0 = 0;
+  ea.m = uint32_t(m);
+  ea.s1 = w.d_s1;
+  ea.s2 = w.d_s2;
+  ea.tf1 = w.d_tf1;
+  ea.tf2 = w.d_tf2;
+  launch_scene_expand_listed(st, ea, d_ids + k0, f32, max_blocks);
+  const int rc = scene_batch(lib, w.d_s1, w.d_s2, w.d_tf1, w.d_tf2, m, creq, dreq, d_rec, d_gin, d_gout, st);
+  if (rc) return rc;
+  if (d_summary) {
+    SceneFoldListedArgs fa;
+    fa.rec = d_rec;
+    fa.ids = d_ids;
+    fa.conf_begin = d_conf_begin;
+    fa.k0 = k0;
+    fa.k1 = k0 + m;
+    fa.n_pairs = uint32_t(s->n_pairs);
+    fa.margin = creq ? creq->security_margin : 0.0;
+    fa.collide = creq ? 1 : 0;
+    fa.summary = d_summary;
+    fa.partials = scene_shares(fa.n_pairs) > 1u ? w.d_partials : nullptr;
+    fa.n_conf = n_conf;
+    launch_scene_fold_listed(st, fa, f32, max_blocks);
+  }
+  return HFCL_OK;
+}
+
+// The device form on a list.  The ids are not checked: ascending, below n_conf * n_pairs, conf_begin theirs -- as hfcl_scene_cull_device leaves them.
+template <typename T>
+static int scene_listed_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const uint64_t* d_ids, size_t n_listed,
+                               const uint64_t* d_conf_begin, const hfcl_collision_request* creq, const hfcl_distance_request* dreq,
+                               typename SceneTypes<T>::R* d_out, hfcl_scene_summary* d_summary, const hfcl_guess* d_gin, hfcl_guess* d_gout,
+                               hipStream_t st) {
+  size_t total;
+  int rc = scene_validate<T>(who, s, d_table, n_conf, creq, dreq, d_out, d_summary, total);
+  if (rc) return rc;
+  if (d_summary && !d_conf_begin) {
+    set_error(std::string(who) + ": summaries need conf_begin");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (n_listed > total) {
+    set_error(std::string(who) + ": more list entries than queries");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (n_listed && !d_ids) {
+    set_error(std::string(who) + ": null list");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  hfcl_lib* lib = s->lib;
+  HIP_TRY(hipSetDevice(lib->device));
+  if (d_summary) launch_scene_summary_init(st, d_summary, n_conf, lib->n_cus * 16);
+  if (!n_listed) {
+    HIP_TRY(hipGetLastError());
+    return HFCL_OK;
+  }
+  const size_t chunk = scene_chunk_size(lib, n_listed);
+  rc = scene_workspace(lib, chunk, d_out ? 0 : 1, false, 0, d_summary ? scene_listed_pieces_bound(s->n_pairs, n_conf) : 0);
+  if (rc) return rc;
+  for (size_t k0 = 0; k0 < n_listed; k0 += chunk) {
+    const size_t m = std::min(chunk, n_listed - k0);
+    auto* rec = d_out ? d_out + k0 : static_cast<typename SceneTypes<T>::R*>(lib->scene.d_rec[0].get());
+    rc = scene_listed_chunk_run<T>(s, d_table, n_conf, d_ids, d_conf_begin, k0, m, creq, dreq, rec, d_summary, d_gin ? d_gin + k0 : nullptr,
+                                   d_gout ? d_gout + k0 : nullptr, st);
+    if (rc) {
+      scene_join_side(lib, st);
+      return rc;
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  return HFCL_OK;
+}
+
+// what the culled host forms (hfcl_scene_*_culled) add to scene_host
+struct SceneCull {
+  double inflate;
+  size_t out_capacity;
+  uint64_t* query_ids_out;   // nullptr or out_capacity
+  uint64_t* conf_begin_out;  // nullptr or n_conf + 1
+  size_t* n_listed;
+};
+
+// Host form.  The object table goes in once; chunk k computes on one stream while chunk k - 1's records leave on another from the other of
+// two record buffers (the copy is issued AFTER chunk k's launches: a copy into pageable memory holds its caller until the data has moved);
+// the summaries come back once at the end.  No feeder threads: nothing per pair goes in.
+template <typename T>
+static int scene_host(const char* who, hfcl_scene* s, const void* table, size_t n_conf, const hfcl_collision_request* creq,
+                      const hfcl_distance_request* dreq, typename SceneTypes<T>::R* out, hfcl_scene_summary* summary, const hfcl_guess* gin,
+                      hfcl_guess* gout, const SceneCull* cull = nullptr) {
+  using R = typename SceneTypes<T>::R;
+  size_t total;
+  int rc = scene_validate<T>(who, s, table, n_conf, creq, dreq, out, summary, total);
+  if (!rc && cull) {
+    rc = cull_check_inflate(who, cull->inflate);
+    if (!rc && !cull->n_listed) {
+      set_error(std::string(who) + ": null count");
+      rc = HFCL_ERR_INVALID_ARGUMENT;
+    }
+    if (!rc) *cull->n_listed = 0;
+  }
+  auto nothing_listed = [&]() {  // no surviving query: an empty list, the summaries of configurations without records
+    if (cull->conf_begin_out) memset(cull->conf_begin_out, 0, (n_conf + 1) * sizeof(uint64_t));
+    for (size_t c = 0; summary && c < n_conf; ++c) scene_summary_init(summary[c]);
+    return HFCL_OK;
+  };
+  if (!rc && !total && cull) return nothing_listed();
+  if (rc || !total) return rc;
+  hfcl_lib* lib = s->lib;
+  hfcl_lib::SceneWs& w = lib->scene;
+  HIP_TRY(hipSetDevice(lib->device));
+  if (!w.s_cmp) HIP_TRY(w.s_cmp.create());
+  if (!w.s_copy) HIP_TRY(w.s_copy.create());
+  for (int k = 0; k < 2; ++k) {
+    if (!w.ev_done[k]) HIP_TRY(w.ev_done[k].create());
+    if (!w.ev_copied[k]) HIP_TRY(w.ev_copied[k].create());
+  }
+  const size_t table_bytes = n_conf * s->n_objects * SceneTypes<T>::WIDTH * sizeof(T);
+  size_t work = total;  // records of the call: every query, or (culled form) the surviving ones
+  if (cull) {  // the table goes in, the cull runs, the count comes back: 8 bytes, the one read-back before the narrow phase
+    rc = scene_table_in(w, table, table_bytes);
+    uint64_t n = 0;
+    if (!rc) rc = cull_into_workspace<T>(who, s, w.d_table, n_conf, total, cull->inflate, true, n);
+    if (rc) {
+      hipStreamSynchronize(w.s_cmp);
+      return rc;
+    }
+    *cull->n_listed = size_t(n);
+    if ((out || gout || cull->query_ids_out) && cull->out_capacity < n) {
+      set_error(std::string(who) + ": " + std::to_string(n) + " queries survive, the outputs hold " + std::to_string(cull->out_capacity));
+      return HFCL_ERR_LIMIT;
+    }
+    if (!n) return nothing_listed();
+    if (cull->query_ids_out) HIP_TRY(hipMemcpyAsync(cull->query_ids_out, w.d_ids, n * sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
+    if (cull->conf_begin_out)
+      HIP_TRY(hipMemcpyAsync(cull->conf_begin_out, w.d_conf_begin, (n_conf + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
+    work = size_t(n);
+  }
+  const size_t chunk = scene_chunk_size(lib, work);
+  const size_t n_chunks = (work + chunk - 1) / chunk;
+  const bool back = out != nullptr || gout != nullptr;  // something per pair goes back: two buffers, the copy stream
+  rc = scene_workspace(lib, chunk, out ? 2 : 1, gin != nullptr, gout ? 2 : 0,
+                       !summary ? 0 : cull ? scene_listed_pieces_bound(s->n_pairs, n_conf) : scene_pieces_bound(s->n_pairs, chunk));
+  if (rc) return rc;
+  if (!cull) HIP_TRY(w.d_table.grow(table_bytes));
+  if (summary) HIP_TRY(w.d_summary.grow(n_conf));
+  constexpr int CS = hfcl_lib::SceneWs::COUNT_SLOTS;
+  constexpr size_t SLOT_WORDS = 2 * size_t(N_COUNTERS);
+  if (!w.h_counts) HIP_TRY(w.h_counts.alloc(CS * SLOT_WORDS));
+  for (Event& e : w.ev_counts)
+    if (!e) HIP_TRY(e.create());
+  memset(w.h_counts, 0, CS * SLOT_WORDS * sizeof(uint32_t));  // (a skipped batch -- -inf margin -- copies no counters)
+  bool slot_split[CS] = {};
+  memset(lib->acc_counts, 0, sizeof(lib->acc_counts));
+  auto harvest = [&](int slot) {  // a finished chunk's bucket populations into the call's sums; the slot is free again
+    uint32_t* c = w.h_counts + size_t(slot) * SLOT_WORDS;
+    for (int i = 0; i < N_COUNTERS; ++i) lib->acc_counts[i] += c[i] + (slot_split[slot] ? c[N_COUNTERS + i] : 0u);
+    memset(c, 0, SLOT_WORDS * sizeof(uint32_t));
+  };
+  lib->in_host_batch = true;
+
+  auto finish = [&](int code) {  // nothing of this call stays in flight, whatever happened
+    hipStreamSynchronize(w.s_cmp);
+    hipStreamSynchronize(w.s_copy);
+    if (lib->side) hipStreamSynchronize(lib->side);
+    lib->in_host_batch = false;
+    lib->counts_dst = nullptr;
+    if (lib->helper) lib->helper->counts_dst = nullptr;
+    return code;
+  };
+#define SCENE_TRY(expr)                                                      \
+  do {                                                                       \
+    hipError_t _e = (expr);                                                  \
+    if (_e != hipSuccess) {                                                  \
+      set_error(std::string(#expr) + ": " + hipGetErrorString(_e));          \
+      return finish(HFCL_ERR_HIP);                                           \
+    }                                                                        \
+  } while (0)
+  auto copy_back = [&](size_t k) -> hipError_t {  // chunk k's records (and guesses) to the caller's arrays, behind its kernels
+    const int b = int(k & 1);
+    const size_t q0 = k * chunk, m = std::min(chunk, work - q0);
+    hipError_t e = hipStreamWaitEvent(w.s_copy, w.ev_done[b], 0);
+    if (e == hipSuccess && out) e = hipMemcpyAsync(out + q0, w.d_rec[b], m * sizeof(R), hipMemcpyDeviceToHost, w.s_copy);
+    if (e == hipSuccess && gout) e = hipMemcpyAsync(gout + q0, w.d_gout[b], m * sizeof(hfcl_guess), hipMemcpyDeviceToHost, w.s_copy);
+    if (e == hipSuccess) e = hipEventRecord(w.ev_copied[b], w.s_copy);
+    return e;
+  };
+
+  if (!cull) SCENE_TRY(hipMemcpyAsync(w.d_table, table, table_bytes, hipMemcpyHostToDevice, w.s_cmp));
+  if (cull && summary) launch_scene_summary_init(w.s_cmp, w.d_summary, n_conf, lib->n_cus * 16);
+  for (size_t k = 0; k < n_chunks; ++k) {
+    const int b = back ? int(k & 1) : 0;
+    const size_t q0 = k * chunk, m = std::min(chunk, work - q0);
+    if (back && k >= 2) SCENE_TRY(hipStreamWaitEvent(w.s_cmp, w.ev_copied[b], 0));  // chunk k - 2 has left the buffers
+    if (gin) SCENE_TRY(hipMemcpyAsync(w.d_gin, gin + q0, m * sizeof(hfcl_guess), hipMemcpyHostToDevice, w.s_cmp));
+    const int slot = int(k % CS);
+    if (k >= size_t(CS)) {  // the chunk that used this slot has run: its counters are on the host
+      SCENE_TRY(hipEventSynchronize(w.ev_counts[slot]));
+      harvest(slot);
+    }
+    lib->counts_dst = w.h_counts + size_t(slot) * SLOT_WORDS;
+    if (batch_splits(lib, m)) {
+      rc = ensure_helper(lib);
+      if (rc) return finish(rc);
+      lib->helper->counts_dst = lib->counts_dst + N_COUNTERS;
+    }
+    rc = cull ? scene_listed_chunk_run<T>(s, w.d_table, n_conf, w.d_ids, w.d_conf_begin, q0, m, creq, dreq, static_cast<R*>(w.d_rec[out ? b : 0].get()),
+                                          summary ? w.d_summary : nullptr, gin ? w.d_gin : nullptr, gout ? w.d_gout[b] : nullptr, w.s_cmp)
+              : scene_chunk_run<T>(s, w.d_table, q0, m, creq, dreq, static_cast<R*>(w.d_rec[out ? b : 0].get()), summary ? w.d_summary : nullptr,
+                                   gin ? w.d_gin : nullptr, gout ? w.d_gout[b] : nullptr, w.s_cmp);
+    if (rc) return finish(rc);
+    slot_split[slot] = lib->last_split;
+    SCENE_TRY(hipEventRecord(w.ev_counts[slot], w.s_cmp));
+    if (back) {
+      SCENE_TRY(hipEventRecord(w.ev_done[b], w.s_cmp));
+      if (k >= 1) SCENE_TRY(copy_back(k - 1));
+    }
+  }
+  if (back) SCENE_TRY(copy_back(n_chunks - 1));
+  if (summary) SCENE_TRY(hipMemcpyAsync(summary, w.d_summary, n_conf * sizeof(hfcl_scene_summary), hipMemcpyDeviceToHost, w.s_cmp));
+  SCENE_TRY(hipStreamSynchronize(w.s_cmp));
+  SCENE_TRY(hipStreamSynchronize(w.s_copy));
+  SCENE_TRY(hipGetLastError());
+#undef SCENE_TRY
+  for (int slot = 0; slot < CS && size_t(slot) < n_chunks; ++slot) harvest(slot);
+  lib->in_host_batch = false;
+  lib->counts_dst = nullptr;
+  if (lib->helper) lib->helper->counts_dst = nullptr;
+  lib->last_host = true;
+  return host_batch_checks(lib, creq, dreq);
+}
+
+extern "C" {
+
+hfcl_scene* hfcl_scene_create(hfcl_lib* lib, const uint32_t* object_shape, size_t n_objects, const uint32_t* pairs, size_t n_pairs) {
+  if (!lib) {
+    set_error("hfcl_scene_create: null library");
+    return nullptr;
+  }
+  if (n_objects && !object_shape) {
+    set_error("hfcl_scene_create: null object table");
+    return nullptr;
+  }
+  for (size_t o = 0; o < n_objects; ++o)
+    if (object_shape[o] >= lib->n_shapes) {
+      set_error("hfcl_scene_create: shape id " + std::to_string(object_shape[o]) + " of object " + std::to_string(o) + " is outside the library");
+      return nullptr;
+    }
+  // (no return code here: the two causes that are not HFCL_ERR_INVALID_ARGUMENT name theirs at the head of the message)
+  if (const int rc = scene_check_pairs("hfcl_scene_create", pairs, n_pairs, n_objects)) {
+    if (rc == HFCL_ERR_LIMIT) set_error("HFCL_ERR_LIMIT: " + std::string(hfcl_last_error()));
+    return nullptr;
+  }
+  if (hipSetDevice(lib->device) != hipSuccess) {
+    set_error("HFCL_ERR_HIP: hfcl_scene_create: hipSetDevice failed");
+    return nullptr;
+  }
+  hfcl_scene* s = new hfcl_scene();
+  s->lib = lib;
+  s->n_objects = n_objects;
+  s->n_pairs = n_pairs;
+  s->epoch = lib->shapes_epoch;
+  if (scene_upload(s->d_object_shape, object_shape, n_objects) != HFCL_OK || scene_upload(s->d_pairs, pairs, 2 * n_pairs) != HFCL_OK) {
+    set_error("HFCL_ERR_HIP: hfcl_scene_create: " + std::string(hfcl_last_error()));
+    hfcl_scene_destroy(s);
+    return nullptr;
+  }
+  return s;
+}
+
+int hfcl_scene_set_pairs(hfcl_scene* s, const uint32_t* pairs, size_t n_pairs) {
+  if (!s) {
+    set_error("hfcl_scene_set_pairs: null scene");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  int rc = scene_check_pairs("hfcl_scene_set_pairs", pairs, n_pairs, s->n_objects);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(s->lib->device));
+  DevBuf<uint32_t> d;
+  rc = scene_upload(d, pairs, 2 * n_pairs);
+  if (rc) return rc;
+  s->d_pairs = std::move(d);  // (freeing the old list waits for the device: a query in flight on some stream may still be reading it)
+  s->n_pairs = n_pairs;
+  return HFCL_OK;
+}
+
+void hfcl_scene_destroy(hfcl_scene* s) {
+  if (!s) return;
+  hipSetDevice(s->lib->device);
+  delete s;
+}
+size_t hfcl_scene_num_objects(const hfcl_scene* s) { return s ? s->n_objects : 0; }
+size_t hfcl_scene_num_pairs(const hfcl_scene* s) { return s ? s->n_pairs : 0; }
+
+int hfcl_scene_collide(hfcl_scene* s, const double* object_tf, size_t n_conf, const hfcl_collision_request* req, hfcl_result* out,
+                       hfcl_scene_summary* summary, const hfcl_guess* guess_in, hfcl_guess* guess_out) {
+  return scene_host<double>("hfcl_scene_collide", s, object_tf, n_conf, req, nullptr, out, summary, guess_in, guess_out);
+}
+int hfcl_scene_distance(hfcl_scene* s, const double* object_tf, size_t n_conf, const hfcl_distance_request* req, hfcl_result* out,
+                        hfcl_scene_summary* summary, const hfcl_guess* guess_in, hfcl_guess* guess_out) {
+  if (s && !req) {
+    set_error("null request");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  return scene_host<double>("hfcl_scene_distance", s, object_tf, n_conf, nullptr, req, out, summary, guess_in, guess_out);
+}
+int hfcl_scene_collide_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const hfcl_collision_request* req, hfcl_result* d_out,
+                              hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in, hfcl_guess* d_guess_out, void* stream) {
+  return scene_device<double>("hfcl_scene_collide_device", s, d_object_tf, n_conf, req, nullptr, d_out, d_summary, d_guess_in, d_guess_out,
+                              (hipStream_t)stream);
+}
+int hfcl_scene_distance_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const hfcl_distance_request* req, hfcl_result* d_out,
+                               hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in, hfcl_guess* d_guess_out, void* stream) {
+  if (s && !req) {
+    set_error("null request");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  return scene_device<double>("hfcl_scene_distance_device", s, d_object_tf, n_conf, nullptr, req, d_out, d_summary, d_guess_in, d_guess_out,
+                              (hipStream_t)stream);
+}
+int hfcl_scene_collide_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, const hfcl_collision_request* req, hfcl_result_f32* out,
+                           hfcl_scene_summary* summary) {
+  return scene_host<float>("hfcl_scene_collide_f32", s, object_pose, n_conf, req, nullptr, out, summary, nullptr, nullptr);
+}
+int hfcl_scene_distance_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, const hfcl_distance_request* req, hfcl_result_f32* out,
+                            hfcl_scene_summary* summary) {
+  if (s && !req) {
+    set_error("null request");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  return scene_host<float>("hfcl_scene_distance_f32", s, object_pose, n_conf, nullptr, req, out, summary, nullptr, nullptr);
+}
+int hfcl_scene_collide_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, const hfcl_collision_request* req,
+                                  hfcl_result_f32* d_out, hfcl_scene_summary* d_summary, void* stream) {
+  return scene_device<float>("hfcl_scene_collide_device_f32", s, d_object_pose, n_conf, req, nullptr, d_out, d_summary, nullptr, nullptr,
+                             (hipStream_t)stream);
+}
+int hfcl_scene_distance_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, const hfcl_distance_request* req,
+                                   hfcl_result_f32* d_out, hfcl_scene_summary* d_summary, void* stream) {
+  if (s && !req) {
+    set_error("null request");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  return scene_device<float>("hfcl_scene_distance_device_f32", s, d_object_pose, n_conf, nullptr, req, d_out, d_summary, nullptr, nullptr,
+                             (hipStream_t)stream);
+}
+
+// ---- culling the pair list per configuration ---------------------------------------------------------------------------------------
+int hfcl_scene_world_aabbs(hfcl_scene* s, const double* object_tf, size_t n_conf, double* aabbs_out) {
+  return scene_boxes_host<double>("hfcl_scene_world_aabbs", s, object_tf, n_conf, aabbs_out);
+}
+int hfcl_scene_world_aabbs_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, double* aabbs_out) {
+  return scene_boxes_host<float>("hfcl_scene_world_aabbs_f32", s, object_pose, n_conf, aabbs_out);
+}
+int hfcl_scene_world_aabbs_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, double* d_aabbs_out, void* stream) {
+  return scene_boxes_device<double>("hfcl_scene_world_aabbs_device", s, d_object_tf, n_conf, d_aabbs_out, (hipStream_t)stream);
+}
+int hfcl_scene_world_aabbs_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, double* d_aabbs_out, void* stream) {
+  return scene_boxes_device<float>("hfcl_scene_world_aabbs_device_f32", s, d_object_pose, n_conf, d_aabbs_out, (hipStream_t)stream);
+}
+int hfcl_scene_cull(hfcl_scene* s, const double* object_tf, size_t n_conf, double inflate, uint64_t* query_ids, size_t capacity,
+                    uint64_t* conf_begin, size_t* n_listed) {
+  return scene_cull_host<double>("hfcl_scene_cull", s, object_tf, n_conf, inflate, query_ids, capacity, conf_begin, n_listed);
+}
+int hfcl_scene_cull_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, double inflate, uint64_t* query_ids, size_t capacity,
+                        uint64_t* conf_begin, size_t* n_listed) {
+  return scene_cull_host<float>("hfcl_scene_cull_f32", s, object_pose, n_conf, inflate, query_ids, capacity, conf_begin, n_listed);
+}
+int hfcl_scene_cull_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, double inflate, uint64_t* d_query_ids, size_t capacity,
+                           uint64_t* d_conf_begin, uint64_t* d_n_listed, void* stream) {
+  return cull_device<double>("hfcl_scene_cull_device", s, d_object_tf, n_conf, inflate, d_query_ids, capacity, d_conf_begin, d_n_listed,
+                             (hipStream_t)stream);
+}
+int hfcl_scene_cull_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, double inflate, uint64_t* d_query_ids, size_t capacity,
+                               uint64_t* d_conf_begin, uint64_t* d_n_listed, void* stream) {
+  return cull_device<float>("hfcl_scene_cull_device_f32", s, d_object_pose, n_conf, inflate, d_query_ids, capacity, d_conf_begin, d_n_listed,
+                            (hipStream_t)stream);
+}
+#define HFCL_NEED_DREQ()                        \
+  if (s && !req) {                              \
+    set_error("null request");                  \
+    return HFCL_ERR_INVALID_ARGUMENT;           \
+  }
+int hfcl_scene_collide_listed_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const uint64_t* d_query_ids, size_t n_listed,
+                                     const uint64_t* d_conf_begin, const hfcl_collision_request* req, hfcl_result* d_out,
+                                     hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in, hfcl_guess* d_guess_out, void* stream) {
+  return scene_listed_device<double>("hfcl_scene_collide_listed_device", s, d_object_tf, n_conf, d_query_ids, n_listed, d_conf_begin, req, nullptr,
+                                     d_out, d_summary, d_guess_in, d_guess_out, (hipStream_t)stream);
+}
+int hfcl_scene_distance_listed_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const uint64_t* d_query_ids, size_t n_listed,
+                                      const uint64_t* d_conf_begin, const hfcl_distance_request* req, hfcl_result* d_out,
+                                      hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in, hfcl_guess* d_guess_out, void* stream) {
+  HFCL_NEED_DREQ()
+  return scene_listed_device<double>("hfcl_scene_distance_listed_device", s, d_object_tf, n_conf, d_query_ids, n_listed, d_conf_begin, nullptr, req,
+                                     d_out, d_summary, d_guess_in, d_guess_out, (hipStream_t)stream);
+}
+int hfcl_scene_collide_listed_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, const uint64_t* d_query_ids, size_t n_listed,
+                                         const uint64_t* d_conf_begin, const hfcl_collision_request* req, hfcl_result_f32* d_out,
+                                         hfcl_scene_summary* d_summary, void* stream) {
+  return scene_listed_device<float>("hfcl_scene_collide_listed_device_f32", s, d_object_pose, n_conf, d_query_ids, n_listed, d_conf_begin, req,
+                                    nullptr, d_out, d_summary, nullptr, nullptr, (hipStream_t)stream);
+}
+int hfcl_scene_distance_listed_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, const uint64_t* d_query_ids, size_t n_listed,
+                                          const uint64_t* d_conf_begin, const hfcl_distance_request* req, hfcl_result_f32* d_out,
+                                          hfcl_scene_summary* d_summary, void* stream) {
+  HFCL_NEED_DREQ()
+  return scene_listed_device<float>("hfcl_scene_distance_listed_device_f32", s, d_object_pose, n_conf, d_query_ids, n_listed, d_conf_begin, nullptr,
+                                    req, d_out, d_summary, nullptr, nullptr, (hipStream_t)stream);
+}
+int hfcl_scene_collide_culled(hfcl_scene* s, const double* object_tf, size_t n_conf, double inflate, const hfcl_collision_request* req,
+                              hfcl_result* out, size_t out_capacity, uint64_t* query_ids_out, uint64_t* conf_begin_out,
+                              hfcl_scene_summary* summary, const hfcl_guess* guess_in, hfcl_guess* guess_out, size_t* n_listed) {
+  const SceneCull cull{inflate, out_capacity, query_ids_out, conf_begin_out, n_listed};
+  return scene_host<double>("hfcl_scene_collide_culled", s, object_tf, n_conf, req, nullptr, out, summary, guess_in, guess_out, &cull);
+}
+int hfcl_scene_distance_culled(hfcl_scene* s, const double* object_tf, size_t n_conf, double inflate, const hfcl_distance_request* req,
+                               hfcl_result* out, size_t out_capacity, uint64_t* query_ids_out, uint64_t* conf_begin_out,
+                               hfcl_scene_summary* summary, const hfcl_guess* guess_in, hfcl_guess* guess_out, size_t* n_listed) {
+  HFCL_NEED_DREQ()
+  const SceneCull cull{inflate, out_capacity, query_ids_out, conf_begin_out, n_listed};
+  return scene_host<double>("hfcl_scene_distance_culled", s, object_tf, n_conf, nullptr, req, out, summary, guess_in, guess_out, &cull);
+}
+int hfcl_scene_collide_culled_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, double inflate, const hfcl_collision_request* req,
+                                  hfcl_result_f32* out, size_t out_capacity, uint64_t* query_ids_out, uint64_t* conf_begin_out,
+                                  hfcl_scene_summary* summary, size_t* n_listed) {
+  const SceneCull cull{inflate, out_capacity, query_ids_out, conf_begin_out, n_listed};
+  return scene_host<float>("hfcl_scene_collide_culled_f32", s, object_pose, n_conf, req, nullptr, out, summary, nullptr, nullptr, &cull);
+}
+int hfcl_scene_distance_culled_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, double inflate, const hfcl_distance_request* req,
+                                   hfcl_result_f32* out, size_t out_capacity, uint64_t* query_ids_out, uint64_t* conf_begin_out,
+                                   hfcl_scene_summary* summary, size_t* n_listed) {
+  HFCL_NEED_DREQ()
+  const SceneCull cull{inflate, out_capacity, query_ids_out, conf_begin_out, n_listed};
+  return scene_host<float>("hfcl_scene_distance_culled_f32", s, object_pose, n_conf, nullptr, req, out, summary, nullptr, nullptr, &cull);
+}
+#undef HFCL_NEED_DREQ
+
+}  // extern "C"

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/hppfcl_amd.h"
+#include "hfcl_own.hpp"
 
 void hfcl_internal_set_error(const char* msg);  // hfcl_host.hip: the calling thread's hfcl_last_error()
 
@@ -67,7 +68,7 @@ struct hfcl_multi {
   std::string poisoned;
   // the last device-resident batch: ranks the communicator reports (ncclCommCount; 1 without a collective), the all-gather's duration on
   // replica 0's stream (events around the grouped call) and the bytes each rank contributed
-  hipEvent_t ev_g0 = nullptr, ev_g1 = nullptr;
+  Event ev_g0, ev_g1;
   int gather_ranks = 0;
   bool gather_timed = false;
   size_t gather_bytes_per_rank = 0;
@@ -131,12 +132,8 @@ void hfcl_multi_destroy(hfcl_multi* m) {
   DeviceGuard guard;
   for (size_t g = 0; g < m->comms.size(); ++g)
     if (m->comms[g]) m->rccl.CommDestroy(m->comms[g]);
-  if (m->ev_g0 || m->ev_g1) {
-    if (!m->devices.empty()) hipSetDevice(m->devices[0]);
-    if (m->ev_g0) hipEventDestroy(m->ev_g0);
-    if (m->ev_g1) hipEventDestroy(m->ev_g1);
-  }
   for (hfcl_lib* lib : m->libs) hfcl_lib_destroy(lib);
+  if (!m->devices.empty()) hipSetDevice(m->devices[0]);  // (the gather events' device)
   delete m;
 }
 
@@ -291,8 +288,8 @@ static int run_gathered(hfcl_multi* m, size_t n, const char* who, hfcl_result* c
     if (m->rccl.CommCount && m->rccl.CommCount(m->comms[0], &count) == 0) m->gather_ranks = count;
     else m->gather_ranks = G;
     if (!m->ev_g0 && hipSetDevice(m->devices[0]) == hipSuccess) {
-      if (hipEventCreate(&m->ev_g0) != hipSuccess) m->ev_g0 = nullptr;
-      if (hipEventCreate(&m->ev_g1) != hipSuccess) m->ev_g1 = nullptr;
+      (void)m->ev_g0.create(hipEventDefault);  // (timed; one that could not be made stays empty)
+      (void)m->ev_g1.create(hipEventDefault);
     }
   }
   // every shard into its slot; a shard that cannot be launched ends the call AFTER the shards in front of it have run (nothing of this

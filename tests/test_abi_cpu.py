@@ -51,8 +51,11 @@ def test_options_are_an_api_not_an_environment(pkg):
     assert d.hfcl_lib_set_option(None, b"bvh_coop", b"1") == pkg.abi.ERR_INVALID_ARGUMENT
     assert d.hfcl_multi_set_option(None, b"bvh_coop", b"1") == pkg.abi.ERR_INVALID_ARGUMENT
     n_getenv = 0
-    for f in ("hfcl_host.hip", "hfcl_multi.hip"):
-        txt = open(os.path.join(ROOT, "hpp-fcl_amd", "csrc", f)).read()
+    csrc = os.path.join(ROOT, "hpp-fcl_amd", "csrc")
+    units = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".cpp")))
+    assert {"hfcl_host.hip", "hfcl_host_patch.hip", "hfcl_host_scene.hip", "hfcl_multi.hip"} <= set(units)
+    for f in units:
+        txt = open(os.path.join(csrc, f)).read()
         txt = re.sub(r"//[^\n]*", "", txt)
         n_getenv += len(re.findall(r"\bgetenv\s*\(", txt))
     assert n_getenv <= 1, n_getenv
