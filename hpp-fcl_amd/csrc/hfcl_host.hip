@@ -1,6 +1,7 @@
-// hfcl_host.hip -- host side: library object, options, uploads, batch pipeline, host pipeline and their part of the C-ABI implementation of
-// include/hppfcl_amd.h (contact patches: hfcl_host_patch.hip; scene queries and the cull: hfcl_host_scene.hip; the library object itself and
-// what the three units share: hfcl_host.hpp; the kernels live in hfcl_k_gjk.hip / hfcl_k_epa.hip / hfcl_k_bvh.hip, see hfcl_launch.hpp).
+// hfcl_host.hip -- host side: library object, options, uploads, request set-up, host pipeline and their part of the C-ABI implementation of
+// include/hppfcl_amd.h (one device-resident batch, the dispatcher run_batch: hfcl_host_batch.hip; contact patches: hfcl_host_patch.hip; scene
+// queries and the cull: hfcl_host_scene.hip; the library object itself and what the four units share: hfcl_host.hpp; the host pipeline's chunk
+// plan: hfcl_plan.hpp; the kernels live in hfcl_k_gjk.hip / hfcl_k_epa.hip / hfcl_k_bvh.hip, see hfcl_launch.hpp).
 // No CPU fallback anywhere in these files: every compute entry point needs a HIP device and fails loudly without one.
 //
 // Kernel map (pair buckets follow the reference's dispatch table,
@@ -30,6 +31,7 @@
 //                    TriangleP-vs-solid GJK + EPA in LDS: requests that keep walking after a contact
 //   k_unsupported<T> flags the pairs of a bucket the engine cannot evaluate (never computed elsewhere)
 #include "hfcl_host.hpp"
+#include "hfcl_plan.hpp"
 
 // =======================================================================================
 // Host side: library object + C ABI
@@ -38,15 +40,9 @@ static thread_local std::string g_last_error;
 void set_error(const std::string& s) { g_last_error = s; }
 void hfcl_internal_set_error(const char* msg) { g_last_error = msg ? msg : ""; }  // hfcl_multi.hip: a worker thread's message handed to the caller's
 
-static void share_tables(hfcl_lib* h, const hfcl_lib* lib);
 static void free_retired_graphs(hfcl_lib* lib);
 
 // bucket population i of the last batch (both halves of a split batch)
-static uint32_t one_count(const uint32_t* c, int i) {
-  // the EPA queue of a batch = the general queue + the fp32 convex x convex queue
-  // a bucket = its bottom part + its curved part; the EPA queue of a batch = the general queue + the second queue
-  return c[i] + (i < B_COUNT ? c[B_CURVED0 + i] : 0u) + (i == B_COUNT ? c[B_COUNT + 3] : 0u);
-}
 static uint32_t total_count(const hfcl_lib* lib, int i) {
   if (lib->last_host) return one_count(lib->acc_counts, i);
   uint32_t c = lib->h_counts ? one_count(lib->h_counts, i) : 0u;
@@ -239,7 +235,6 @@ static bool upload_shapes(hfcl_lib* lib, const hfcl_shape* shapes, size_t n_shap
   return ok;
 }
 
-
 // ---------------------------------------------------------------------------------------
 // Tuning options (include/hppfcl_amd.h: hfcl_lib_set_option).  One table: the keys, and what each sets.  Every option is a field of
 // the library read when a batch is set up, so an option holds from the next call on; none changes a record (tests/ hold the forms
@@ -271,76 +266,76 @@ static int apply_option(hfcl_lib* lib, const std::string& key, const char* v) {
   const long long i = atoll(v);
   const bool on = i != 0;
   auto u32 = [&](long long lo) { return uint32_t(std::min<long long>(std::max(i, lo), 0xFFFFFFFFll)); };
-  if (key == "closed_staged") lib->closed_staged = on;
-  else if (key == "split") lib->split = i >= 2 ? 2 : (i == 1 ? 1 : 0);
-  else if (key == "epa_cc_staged") lib->epa_cc_staged = on;
-  else if (key == "epa_records_aside") lib->records_aside = on;
+  if (key == "closed_staged") lib->opt.closed_staged = on;
+  else if (key == "split") lib->opt.split = i >= 2 ? 2 : (i == 1 ? 1 : 0);
+  else if (key == "epa_cc_staged") lib->opt.epa_cc_staged = on;
+  else if (key == "epa_records_aside") lib->opt.records_aside = on;
   else if (key == "epa_general_staged") {
     if (on && !HFCL_KEEP_AB_FORMS) return HFCL_ERR_INVALID_ARGUMENT;  // (not in the product build: hfcl_dev.hpp)
-    lib->epa_general_staged = on;
+    lib->opt.epa_general_staged = on;
   }
-  else if (key == "shape_finish_tiers") lib->shape_finish_tiers = on;
-  else if (key == "shape_finish_aside") lib->shape_finish_aside = on;
-  else if (key == "epa_general_staged_min") lib->epa_general_staged_min = size_t(std::max(0ll, i));
-  else if (key == "epa64_two_streams") lib->epa64_two_streams = on;
-  else if (key == "epa_cc_staged_min") lib->epa_cc_staged_min = size_t(std::max(0ll, i));
-  else if (key == "pipe_chunk") lib->pipe_chunk = strtoull(v, nullptr, 10);
+  else if (key == "shape_finish_tiers") lib->opt.shape_finish_tiers = on;
+  else if (key == "shape_finish_aside") lib->opt.shape_finish_aside = on;
+  else if (key == "epa_general_staged_min") lib->opt.epa_general_staged_min = size_t(std::max(0ll, i));
+  else if (key == "epa64_two_streams") lib->opt.epa64_two_streams = on;
+  else if (key == "epa_cc_staged_min") lib->opt.epa_cc_staged_min = size_t(std::max(0ll, i));
+  else if (key == "pipe_chunk") lib->opt.pipe_chunk = strtoull(v, nullptr, 10);
   else if (key == "bvh_filter") {
     if (on && !HFCL_KEEP_AB_FORMS) return HFCL_ERR_INVALID_ARGUMENT;
-    lib->bvh_filter = on;
+    lib->opt.bvh_filter = on;
   }
-  else if (key == "bvh_shape_lane") lib->bvh_shape_lane = on;
-  else if (key == "shape_coop") lib->shape_coop = on;
-  else if (key == "bvh_cut_ticks") lib->bvh_cut_ticks = uint32_t(strtoul(v, nullptr, 10));
-  else if (key == "shape_cut_ticks") lib->shape_cut_ticks = uint32_t(strtoul(v, nullptr, 10));
-  else if (key == "bvh_coop") lib->bvh_coop = on;
-  else if (key == "bvhd_budget") lib->bvhd_budget = u32(0);
-  else if (key == "bvhd_pool") lib->bvhd_pool = u32(0);
-  else if (key == "shape_dist_pool") lib->shape_dist_pool = u32(0);
-  else if (key == "pool_rerun") lib->pool_rerun = u32(0);
-  else if (key == "bvh_walk_early_coop") lib->walk_early_coop = on;
-  else if (key == "bvh_walk_order") lib->walk_order = on;
-  else if (key == "mesh_beside") lib->mesh_beside = u32(0);
-  else if (key == "shape_walk") lib->shape_walk = on;
-  else if (key == "mesh_prio") lib->mesh_prio = on;
-  else if (key == "shape_walk_sort") lib->shape_walk_sort = on;
-  else if (key == "shape_walk_budget") lib->shape_walk_budget = u32(0);
-  else if (key == "shape_walk_min") lib->shape_walk_min = u32(0);
-  else if (key == "gjk_beside_max") lib->gjk_beside_max = u32(0);
-  else if (key == "epa_direct_max") lib->epa_direct_max = u32(0);
-  else if (key == "bvh_walk_rounds") { lib->walk_rounds = uint32_t(std::min<long long>(std::max(0ll, i), WALK_ROUNDS)); lib->walk_auto = false; }
-  else if (key == "bvh_walk_k") { parse_list(v, lib->walk_k, 0, WALK_ROUNDS, 1u, uint32_t(WALK_K)); lib->walk_auto = false; }  // "6,16": per round
-  else if (key == "bvh_walk_budget") parse_list(v, lib->walk_budget, 1, WALK_ROUNDS, 0u, 0xFFFFFFFFu);  // rounds 1 ...: box tests (round 0 takes bvh_budget0_coop's)
-  else if (key == "shape_dist_leaf_min") lib->shape_dist_leaf_min = u32(1);
-  else if (key == "shape_dist_starve") lib->shape_dist_starve = u32(1);  // (>= 1: a window of triangles alone must always run)
-  else if (key == "bvhd_leaf_min") lib->bvhd_pool_leaf_min = u32(1);
-  else if (key == "bvhd_starve") lib->bvhd_pool_starve = u32(1);
-  else if (key == "bvhd_part_min") lib->bvhd_pool_part_min = u32(0);
-  else if (key == "shape_dist_budget") lib->shape_dist_budget = u32(0);
-  else if (key == "bvh_budget0_coop") lib->bvh_budget0_coop = u32(1);
-  else if (key == "shape_budget0") lib->shape_budget0 = lib->shape_budget0_coop = uint32_t(i);
-  else if (key == "shape_budget") lib->shape_budget = uint32_t(i);
-  else if (key == "shape_leaf_cost") lib->shape_leaf_cost = u32(1);
-  else if (key == "shape_levels") lib->shape_levels = uint32_t(std::min<long long>(std::max(1ll, i), BVH_MAX_LEVELS));
-  else if (key == "climb_min") lib->climb_min = u32(0);
-  else if (key == "bvh_budget") { lib->bvh_budget = lib->bvh_budget0 = u32(0); lib->bvh_auto = false; }
-  else if (key == "bvh_budget0") { lib->bvh_budget0 = u32(0); lib->bvh_auto = false; }
-  else if (key == "bvh_levels") { lib->bvh_levels = uint32_t(std::min<long long>(BVH_MAX_LEVELS, std::max(1ll, i))); lib->bvh_auto = false; }
+  else if (key == "bvh_shape_lane") lib->opt.bvh_shape_lane = on;
+  else if (key == "shape_coop") lib->opt.shape_coop = on;
+  else if (key == "bvh_cut_ticks") lib->opt.bvh_cut_ticks = uint32_t(strtoul(v, nullptr, 10));
+  else if (key == "shape_cut_ticks") lib->opt.shape_cut_ticks = uint32_t(strtoul(v, nullptr, 10));
+  else if (key == "bvh_coop") lib->opt.bvh_coop = on;
+  else if (key == "bvhd_budget") lib->opt.bvhd_budget = u32(0);
+  else if (key == "bvhd_pool") lib->opt.bvhd_pool = u32(0);
+  else if (key == "shape_dist_pool") lib->opt.shape_dist_pool = u32(0);
+  else if (key == "pool_rerun") lib->opt.pool_rerun = u32(0);
+  else if (key == "bvh_walk_early_coop") lib->opt.walk_early_coop = on;
+  else if (key == "bvh_walk_order") lib->opt.walk_order = on;
+  else if (key == "mesh_beside") lib->opt.mesh_beside = u32(0);
+  else if (key == "shape_walk") lib->opt.shape_walk = on;
+  else if (key == "mesh_prio") lib->opt.mesh_prio = on;
+  else if (key == "shape_walk_sort") lib->opt.shape_walk_sort = on;
+  else if (key == "shape_walk_budget") lib->opt.shape_walk_budget = u32(0);
+  else if (key == "shape_walk_min") lib->opt.shape_walk_min = u32(0);
+  else if (key == "gjk_beside_max") lib->opt.gjk_beside_max = u32(0);
+  else if (key == "epa_direct_max") lib->opt.epa_direct_max = u32(0);
+  else if (key == "bvh_walk_rounds") { lib->opt.walk_rounds = uint32_t(std::min<long long>(std::max(0ll, i), WALK_ROUNDS)); lib->opt.walk_auto = false; }
+  else if (key == "bvh_walk_k") { parse_list(v, lib->opt.walk_k, 0, WALK_ROUNDS, 1u, uint32_t(WALK_K)); lib->opt.walk_auto = false; }  // "6,16": per round
+  else if (key == "bvh_walk_budget") parse_list(v, lib->opt.walk_budget, 1, WALK_ROUNDS, 0u, 0xFFFFFFFFu);  // rounds 1 ...: box tests (round 0 takes bvh_budget0_coop's)
+  else if (key == "shape_dist_leaf_min") lib->opt.shape_dist_leaf_min = u32(1);
+  else if (key == "shape_dist_starve") lib->opt.shape_dist_starve = u32(1);  // (>= 1: a window of triangles alone must always run)
+  else if (key == "bvhd_leaf_min") lib->opt.bvhd_pool_leaf_min = u32(1);
+  else if (key == "bvhd_starve") lib->opt.bvhd_pool_starve = u32(1);
+  else if (key == "bvhd_part_min") lib->opt.bvhd_pool_part_min = u32(0);
+  else if (key == "shape_dist_budget") lib->opt.shape_dist_budget = u32(0);
+  else if (key == "bvh_budget0_coop") lib->opt.bvh_budget0_coop = u32(1);
+  else if (key == "shape_budget0") lib->opt.shape_budget0 = lib->opt.shape_budget0_coop = uint32_t(i);
+  else if (key == "shape_budget") lib->opt.shape_budget = uint32_t(i);
+  else if (key == "shape_leaf_cost") lib->opt.shape_leaf_cost = u32(1);
+  else if (key == "shape_levels") lib->opt.shape_levels = uint32_t(std::min<long long>(std::max(1ll, i), BVH_MAX_LEVELS));
+  else if (key == "climb_min") lib->opt.climb_min = u32(0);
+  else if (key == "bvh_budget") { lib->opt.bvh_budget = lib->opt.bvh_budget0 = u32(0); lib->opt.bvh_auto = false; }
+  else if (key == "bvh_budget0") { lib->opt.bvh_budget0 = u32(0); lib->opt.bvh_auto = false; }
+  else if (key == "bvh_levels") { lib->opt.bvh_levels = uint32_t(std::min<long long>(BVH_MAX_LEVELS, std::max(1ll, i))); lib->opt.bvh_auto = false; }
   else if (key == "cvx_w") {
-    if (i == 0 || i == 2 || i == 4 || i == 8 || i == 16 || i == 32 || i == 64) lib->cvx_w = int(i);
+    if (i == 0 || i == 2 || i == 4 || i == 8 || i == 16 || i == 32 || i == 64) lib->opt.cvx_w = int(i);
     else return HFCL_ERR_INVALID_ARGUMENT;
   }
-  else if (key == "epa_resume_slots") lib->epa_resume_slots = size_t(std::max(0ll, i));
-  else if (key == "bvh_task_slots") lib->bvh_task_slots = size_t(std::max(0ll, i));
-  else if (key == "bvh_force_wide") lib->bvh_force_wide = on;
-  else if (key == "pipe_trace") lib->pipe_trace = on;
+  else if (key == "epa_resume_slots") lib->opt.epa_resume_slots = size_t(std::max(0ll, i));
+  else if (key == "bvh_task_slots") lib->opt.bvh_task_slots = size_t(std::max(0ll, i));
+  else if (key == "bvh_force_wide") lib->opt.bvh_force_wide = on;
+  else if (key == "pipe_trace") lib->opt.pipe_trace = on;
   else if (key == "scene_chunk") {
     if (i < 0 || i > 0xFFFFFFF0ll) return HFCL_ERR_INVALID_ARGUMENT;
-    lib->scene_chunk = size_t(i);
+    lib->opt.scene_chunk = size_t(i);
   }
   else if (key == "scene_cull_chunk") {
     if (i < 0 || i > (1ll << 31)) return HFCL_ERR_INVALID_ARGUMENT;  // (one workgroup scans a chunk's counts: 2^23 of them at most)
-    lib->scene_cull_chunk = size_t(i);
+    lib->opt.scene_cull_chunk = size_t(i);
   }
   else return HFCL_ERR_INVALID_ARGUMENT;
   return HFCL_OK;
@@ -447,7 +442,7 @@ int hfcl_lib_set_convex_neighbors(hfcl_lib* lib, uint32_t shape_id, const uint32
 }
 size_t hfcl_lib_num_shapes(const hfcl_lib* lib) { return lib ? lib->n_shapes : 0; }
 int hfcl_lib_device(const hfcl_lib* lib) { return lib ? lib->device : -1; }
-uint32_t hfcl_lib_climb_min(const hfcl_lib* lib) { return lib ? lib->climb_min : 0u; }
+uint32_t hfcl_lib_climb_min(const hfcl_lib* lib) { return lib ? lib->opt.climb_min : 0u; }
 
 int hfcl_lib_add_bvh(hfcl_lib* lib, const hfcl_bvh_node* nodes, size_t n_nodes, const double* vertices,
                      size_t n_vertices, const uint32_t* triangles, size_t n_tris) {
@@ -508,108 +503,6 @@ int hfcl_lib_add_bvh(hfcl_lib* lib, const hfcl_bvh_node* nodes, size_t n_nodes, 
 }
 
 }  // extern "C"
-
-// Device workspace of a batch of n pairs.  The bucket lists (4 B per pair and bucket the library's shape kinds can reach)
-// are always needed; the EPA queues (two seeds of ~230 B per pair) and the hand-over area (one slot of ~4 KB per 8 pairs)
-// only when the batch has a GJK bucket and asks for penetration data -- a closed-form or mesh-only library never pays
-// for them.  ~0.05 KB per pair without EPA, ~1 KB with (it was 1.8 KB for every library).
-static int ensure_workspace(hfcl_lib* lib, size_t n, bool need_epa) {
-  if (n > lib->ws_capacity) {
-    lib->ws_capacity = 0;
-    const size_t cap = n + n / 8 + 1024;
-    HIP_TRY(lib->d_lists.grow(size_t(B_COUNT) * cap));
-    lib->ws_capacity = cap;
-  }
-  if (need_epa && lib->ws_capacity > lib->epa_capacity) {
-    reset_all(lib->d_epa_queue, lib->d_epa_queue2, lib->d_epa_resume, lib->d_epa_cc_over);
-    lib->resume_cap = 0;
-    lib->epa_capacity = 0;
-    const size_t cap = lib->ws_capacity;
-    HIP_TRY(lib->d_epa_queue.grow(cap * sizeof(EpaItem<double>)));
-    HIP_TRY(lib->d_epa_queue2.grow(cap * sizeof(EpaItem<double>)));
-    // saved polytopes for the tier hand-over: room for an eighth of the batch (cfg5: 4 % of the pairs outgrow the fast
-    // tier; beyond the area the full tier simply redoes the pair from its seed)
-    size_t rcap = std::min(cap, std::max<size_t>(65536, cap / 8));
-    if (lib->epa_resume_slots) rcap = std::max<size_t>(1, std::min<size_t>(cap, lib->epa_resume_slots));  // test knob (option epa_resume_slots)
-    HIP_TRY(lib->d_epa_resume.grow(rcap * std::max(epa_resume_stride<double>, epa_resume_stride<float>)));
-    HIP_TRY(lib->d_epa_cc_over.grow(rcap));
-    lib->resume_cap = rcap;
-    lib->epa_capacity = cap;
-  }
-  return HFCL_OK;
-}
-
-// Tables of a split traversal (mesh x mesh, mesh x solid) for a batch of n queries: room for 16 tasks per query (a long query suspends
-// with a stack of ~20 entries, one query in five is long; mesh x solid walks are cut finer) -- ~2.4 KB of device memory per query in fp64.
-static int ensure_bvh_split(hfcl_lib* lib, size_t n) {
-  if (n <= lib->bvh_split_n) return HFCL_OK;
-  reset_all(lib->d_bvh_tasks, lib->d_bvh_sums, lib->d_bvh_susp, lib->d_bvh_cut_words, lib->d_bvh_cut_vals);
-  lib->bvh_split_n = 0;
-  size_t per_query = 16;
-  if (lib->bvh_task_slots) per_query = std::max<size_t>(1, lib->bvh_task_slots);  // test / tuning knob (option bvh_task_slots)
-  const size_t nq = n + n / 8 + 1024, cap = per_query * nq + 65536;
-  HIP_TRY(lib->d_bvh_tasks.grow(cap));
-  HIP_TRY(lib->d_bvh_sums.grow((nq + cap) * sizeof(BvhSum<double>)));
-  HIP_TRY(lib->d_bvh_cut_words.grow(cap));
-  HIP_TRY(lib->d_bvh_cut_vals.grow(cap));
-  HIP_TRY(lib->d_bvh_susp.grow(nq));
-  HIP_TRY(lib->d_bvh_ctr.grow(BVH_CTR_WORDS));
-  lib->bvh_split_n = nq;
-  lib->bvh_split_cap = cap;
-  return HFCL_OK;
-}
-
-static int ensure_walk(hfcl_lib* lib, size_t n) {
-  if (n <= lib->walk_n) return HFCL_OK;
-  reset_all(lib->d_walk_recs, lib->d_walk_items, lib->d_walk_res, lib->d_walk_lists, lib->d_walk_order);
-  lib->walk_n = 0;
-  const size_t nq = n + n / 8 + 1024;
-  HIP_TRY(lib->d_walk_recs.grow(nq * sizeof(WalkRec<double>)));
-  HIP_TRY(lib->d_walk_items.grow(nq * WALK_K));
-  HIP_TRY(lib->d_walk_res.grow(nq * WALK_K * 10 * sizeof(double)));  // TriLeafOut<double>: distance, p1, p2, n
-  HIP_TRY(lib->d_walk_lists.grow(2 * nq));
-  HIP_TRY(lib->d_walk_order.grow(nq));
-  HIP_TRY(lib->d_walk_ctr.grow(8 * WALK_ROUNDS));
-  lib->walk_n = nq;
-  return HFCL_OK;
-}
-
-static int ensure_swalk(hfcl_lib* lib, size_t n) {
-  if (n <= lib->swalk_n) return HFCL_OK;
-  reset_all(lib->d_swalk_recs, lib->d_swalk_items, lib->d_swalk_res, lib->d_swalk_lists, lib->d_swalk_perm);
-  lib->swalk_n = 0;
-  const size_t nq = n + n / 8 + 1024;
-  HIP_TRY(lib->d_swalk_recs.grow(nq * sizeof(WalkRec<double>)));
-  HIP_TRY(lib->d_swalk_items.grow(nq * WALK_K));
-  HIP_TRY(lib->d_swalk_res.grow(nq * WALK_K * 10 * sizeof(double)));  // TriLeafOut<double>: distance, p1, p2, n
-  HIP_TRY(lib->d_swalk_lists.grow(3 * nq));
-  HIP_TRY(lib->d_swalk_perm.grow(nq * WALK_K + nq));
-  HIP_TRY(lib->d_swalk_ctr.grow(8 * WALK_ROUNDS + 64));
-  lib->swalk_n = nq;
-  return HFCL_OK;
-}
-
-// How the mesh x mesh traversals of this library keep their stacks.  A stack never holds more than depth1 + depth2 + 2
-// entries (every step pops one entry and pushes at most two, one level deeper in one of the trees).
-static int make_bvh_spill(hfcl_lib* lib, BvhSpill& sp, bool distance) {
-  memset(&sp, 0, sizeof(sp));
-  const size_t need = 2 * size_t(lib->bvh_max_depth) + 4;
-  // collide(): a full LDS stack first suspends into tasks (HFCL_BVH_LEVELS levels of BVH_STACK entries); distance() has
-  // no task form: anything deeper than its LDS stack takes the wide form with slabs
-  const size_t narrow_holds = distance ? size_t(BVHD_STACK) : size_t(std::min(BVH_STACK, BVH_STACK_FILT)) * HFCL_BVH_LEVELS;
-  sp.wide = (lib->bvh_max_nodes > 65535 || need > narrow_holds) ? 1u : 0u;
-  if (lib->bvh_force_wide) sp.wide = 1u;  // test knob (option bvh_force_wide): the wide form (and its slabs) on small models
-  if (!sp.wide || need <= size_t(std::min(BVH_STACK, BVH_STACK_FILT)) / 2) return HFCL_OK;  // the LDS stack of the wide form suffices
-  const size_t cap = ((need + 63) / 64) * 64;                     // entries per lane
-  const size_t per_block = size_t(BVH_BLOCK) * cap * 2 * sizeof(uint64_t);  // (entry, bound) records: k_bvh_distance
-  size_t blocks = std::min<size_t>(size_t(lib->n_cus) * 16, std::max<size_t>(1, (size_t(2) << 30) / per_block));
-  const size_t bytes = blocks * per_block;
-  HIP_TRY(lib->d_bvh_slab.grow(bytes));
-  sp.slab = lib->d_bvh_slab;
-  sp.cap = uint32_t(cap);
-  sp.max_blocks = uint32_t(blocks);
-  return HFCL_OK;
-}
 
 template <typename T>
 static DNode<T> pack_node(const hfcl_bvh_node& n) {
@@ -713,7 +606,7 @@ int upload_graph(hfcl_lib* lib) {
   return HFCL_OK;
 }
 
-static int upload_bvh(hfcl_lib* lib) {
+int upload_bvh(hfcl_lib* lib) {
   if (!lib->bvh_dirty) return HFCL_OK;
   reset_all(lib->d_nodes64, lib->d_nodes32, lib->d_bverts64, lib->d_bverts32, lib->d_btris, lib->d_meshes, lib->d_rss64, lib->d_rss32,
             lib->d_fnodes, lib->d_dnodes64, lib->d_dnodes32);
@@ -827,805 +720,6 @@ static int validate_query(const hfcl_query_request& q) {
     set_error("Wrong initial guess for GJK.");  // narrowphase.h:379-380
     return HFCL_ERR_INVALID_ARGUMENT;
   }
-  return HFCL_OK;
-}
-
-// Lane-group width of the convex GJK kernels.  A/B on cfg3 / cfg5 (profiles/r01_k_gjk_lane_group_w2.txt): 2-lane
-// groups (16 vertices of each hull per lane, 32 pairs per wave: half the redundancy of the serial simplex code)
-// beat 4-lane groups wherever their 96 / 192 vertex registers fit -- everywhere but fp64 convex x convex.
-// the helper stream of a library (tail kernels beside the main ones) and its fork / join events, made on first use
-static int ensure_aux(hfcl_lib* lib) {
-  if (lib->aux) return HFCL_OK;
-  // created into locals and committed together: a failure half way leaves the library without a helper stream, not with null events
-  Stream s;
-  Event ev[4];
-  HIP_TRY(s.create());
-  for (Event& e : ev) HIP_TRY(e.create());
-  lib->ev_aux0 = std::move(ev[0]);
-  lib->ev_aux1 = std::move(ev[1]);
-  lib->ev_aux2 = std::move(ev[2]);
-  lib->ev_aux3 = std::move(ev[3]);
-  lib->aux = std::move(s);
-  return HFCL_OK;
-}
-static int ensure_mesh_stream(hfcl_lib* lib) {
-  if (lib->mesh_st) return HFCL_OK;  // (committed last)
-  Stream st[3];
-  Event ev[4];
-  // option mesh_prio: [0] the mesh x solid walks and [2] their helper at the device's highest priority -- hardware queues of their own (the runtime
-  // maps the streams of one priority onto four queues; two chains that share one run one after the other): cfgmix 2.90 -> 2.72 ms, but a process
-  // that has created them runs cfg4s's in-line batches 1 ms slower (3.7 against 2.65 ms; profiles/r06_g).  Off.
-  int prio_lo = 0, prio_hi = 0;
-  if (lib->mesh_prio) (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-  for (int k = 0; k < 3; ++k) HIP_TRY(st[k].create_with_priority(k == 1 ? 0 : prio_hi));
-  for (Event& e : ev) HIP_TRY(e.create());
-  lib->ev_mesh_fork = std::move(ev[0]);
-  lib->ev_mesh_join = std::move(ev[1]);
-  lib->ev_mesh_fork2 = std::move(ev[2]);
-  lib->ev_mesh_join2 = std::move(ev[3]);
-  lib->mesh_st2 = std::move(st[1]);
-  lib->mesh_aux = std::move(st[2]);
-  lib->mesh_st = std::move(st[0]);
-  return HFCL_OK;
-}
-// the second set of split-traversal tables (what k_bvh_walk / k_bvh_resolve / k_bvh_coop use of them: tasks, summaries, suspended list,
-// counters): the mesh x mesh walks of a batch that also holds mesh x solid pairs run beside those on these
-static int ensure_bvh_split2(hfcl_lib* lib, size_t n) {
-  if (n <= lib->bvh2_split_n) return HFCL_OK;
-  reset_all(lib->d_bvh2_tasks, lib->d_bvh2_sums, lib->d_bvh2_susp);
-  lib->bvh2_split_n = 0;
-  const size_t nq = n + n / 8 + 1024, cap = 16 * nq + 65536;
-  HIP_TRY(lib->d_bvh2_tasks.grow(cap));
-  HIP_TRY(lib->d_bvh2_sums.grow((nq + cap) * sizeof(BvhSum<double>)));
-  HIP_TRY(lib->d_bvh2_susp.grow(nq));
-  HIP_TRY(lib->d_bvh2_ctr.grow(BVH_CTR_WORDS));
-  lib->bvh2_split_n = nq;
-  lib->bvh2_split_cap = cap;
-  return HFCL_OK;
-}
-static int ensure_walk_streams(hfcl_lib* lib) {
-  if (lib->walk_st[WALK_ROUNDS - 2]) return HFCL_OK;  // (committed last)
-  Stream s[WALK_ROUNDS - 1];
-  Event ev[2 * (WALK_ROUNDS - 1)];
-  for (Stream& x : s) HIP_TRY(x.create());
-  for (Event& e : ev) HIP_TRY(e.create());
-  for (int k = 0; k < WALK_ROUNDS - 1; ++k) {
-    lib->walk_fork[k] = std::move(ev[2 * k]);
-    lib->walk_join[k] = std::move(ev[2 * k + 1]);
-  }
-  for (int k = 0; k < WALK_ROUNDS - 1; ++k) lib->walk_st[k] = std::move(s[k]);
-  return HFCL_OK;
-}
-static int ensure_gjk_streams(hfcl_lib* lib) {
-  if (lib->gjk_fork) return HFCL_OK;  // (committed last)
-  Stream s[3];
-  Event ev[4];
-  for (Stream& x : s) HIP_TRY(x.create());
-  for (Event& e : ev) HIP_TRY(e.create());
-  for (int k = 0; k < 3; ++k) {
-    lib->gjk_st[k] = std::move(s[k]);
-    lib->gjk_join[k] = std::move(ev[k]);
-  }
-  lib->gjk_fork = std::move(ev[3]);
-  return HFCL_OK;
-}
-template <typename T, int M>
-static int auto_cvx_w() {
-  return (sizeof(T) == 8 && M == 0) ? 4 : 2;
-}
-template <typename T, int M>
-static void launch_cvx_m(hfcl_lib* lib, const Work& wk, const LibView<T>& lv, const IO<T>& io, const QParams<T>& q,
-                         hipStream_t st, size_t n) {
-  const int w = lib->cvx_w ? lib->cvx_w : auto_cvx_w<T, M>();
-  const size_t nt = size_t(gjk_cvx_threads<T>(w, M));
-  size_t b = (n + nt / w - 1) / (nt / w);
-  if (b < 1) b = 1;
-  // single-wave workgroups: one per round of pairs, handed out by the dispatcher as waves end (the kernel's grid-stride loop serves what is beyond 2^20 rounds)
-  const size_t cap = nt == 64 ? size_t(1) << 20 : size_t(lib->n_cus) * 16;
-  if (b > cap) b = cap;
-  launch_gjk_cvx<T>(M, w, q.guess_mode == HFCL_GUESS_BOUNDING_VOLUME, int(b), st, wk, lv, io, q);
-}
-// (next_stream, optional: called in front of every kernel, returns the stream it goes on -- the solids' kernels of a small batch fan out)
-template <typename T, class Next>
-static void launch_cvx(hfcl_lib* lib, const Work& wk, const LibView<T>& lv, const IO<T>& io, const QParams<T>& q,
-                       hipStream_t st, size_t& ti, size_t n, Next&& next_stream) {
-  KernelTime* t = nullptr;
-  auto tbeg = [&](const char* name) {
-    if (!lib->kernel_timing) return;
-    t = timer_slot(lib, ti++, name);
-    hipEventRecord(t->e0, st);
-  };
-  auto tend = [&]() {
-    if (lib->kernel_timing) hipEventRecord(t->e1, st);
-  };
-  if ((lib->possible_buckets >> B_CC) & 1u) {
-    st = next_stream();
-    tbeg("k_gjk_cvx<cc>");
-    launch_cvx_m<T, 0>(lib, wk, lv, io, q, st, n);
-    tend();
-  }
-  if ((lib->possible_buckets >> B_PC) & 1u) {
-    st = next_stream();
-    tbeg("k_gjk_cvx<pc>");
-    launch_cvx_m<T, 1>(lib, wk, lv, io, q, st, n);
-    tend();
-  }
-  if ((lib->possible_buckets >> B_CP) & 1u) {
-    st = next_stream();
-    tbeg("k_gjk_cvx<cp>");
-    launch_cvx_m<T, 2>(lib, wk, lv, io, q, st, n);
-    tend();
-  }
-}
-
-// The whole pipeline for one batch, asynchronous on `st`.
-template <typename T>
-static int run_batch_one(hfcl_lib* lib, const uint32_t* d_s1, const uint32_t* d_s2, IO<T> io, size_t n, QParams<T> q,
-                         hipStream_t st) {
-  if (n == 0) return HFCL_OK;
-  if (n > 0xFFFFFFF0ull) {
-    set_error("batch too large (max 2^32-16 pairs per call)");
-    return HFCL_ERR_LIMIT;
-  }
-  HIP_TRY(hipSetDevice(lib->device));
-  const bool any_gjk_bucket = ((lib->possible_buckets >> B_PRIM) | (lib->possible_buckets >> B_CC) | (lib->possible_buckets >> B_PC) |
-                               (lib->possible_buckets >> B_CP) | (lib->possible_buckets >> B_LARGE)) & 1u;
-  int rc = ensure_workspace(lib, n, any_gjk_bucket && q.compute_penetration);
-  if (rc) return rc;
-  Work wk;
-  wk.shape1 = d_s1;
-  wk.shape2 = d_s2;
-  wk.n = uint32_t(n);
-  wk.lists = lib->d_lists;
-  wk.counts = lib->d_counts;
-  wk.epa_queue = lib->d_epa_queue;
-  wk.epa_queue2 = lib->d_epa_queue2;
-  wk.epa_resume = lib->d_epa_resume;
-  wk.epa_v0 = lib->d_epa_v0;
-  wk.resume_cap = uint32_t(std::min<size_t>(lib->resume_cap, 0xFFFFFFFFu));
-  wk.shape_defer = nullptr;
-  wk.shape_defer_cap = 0;
-  wk.shape_finish_over = nullptr;
-  wk.shape_oq = nullptr;
-  wk.epa_ready = nullptr;
-  wk.epa_ready_g = nullptr;
-  wk.epa_cc_over = lib->d_epa_cc_over;
-  // fp32 slots are shorter than the area's stride (the fp64 slot): the slots past resume_cap are the convex x convex tier's own
-  wk.cc_resume_base = wk.resume_cap;
-  {
-    const size_t fslots = lib->resume_cap * std::max(epa_resume_stride<double>, epa_resume_stride<float>) / epa_resume_stride<float>;
-    wk.cc_resume_cap = std::is_same<T, float>::value && fslots > lib->resume_cap ? uint32_t(std::min<size_t>(fslots - lib->resume_cap, lib->resume_cap)) : 0u;
-  }
-  LibView<T> lv;
-  lv.shapes = std::is_same<T, double>::value ? (const DShape<T>*)lib->d_shapes64 : (const DShape<T>*)lib->d_shapes32;
-  lv.verts = std::is_same<T, double>::value ? (const T*)lib->d_verts64 : (const T*)lib->d_verts32;
-  lv.kinds = lib->d_kinds;
-  lv.n_shapes = uint32_t(lib->n_shapes);
-  lv.graph_base = lib->d_graph_base;
-  lv.graph_off = lib->d_graph_off;
-  lv.graph_ent = std::is_same<T, double>::value ? (const NbrEntry<T>*)lib->d_graph_ent64 : (const NbrEntry<T>*)lib->d_graph_ent32;
-  lv.climb_min = lib->climb_min;
-
-  for (auto& t : lib->timers) t.used = false;
-  size_t ti = 0;
-  const int max_blocks = lib->n_cus * 16;
-  auto blocks_for = [&](size_t items, size_t per_block) {
-    size_t b = (items + per_block - 1) / per_block;
-    if (b < 1) b = 1;
-    if (b > (size_t)max_blocks) b = max_blocks;
-    return int(b);
-  };
-  KernelTime* t = nullptr;
-  auto tbeg = [&](const char* name) {
-    if (!lib->kernel_timing) return;
-    t = timer_slot(lib, ti++, name);
-    hipEventRecord(t->e0, st);
-  };
-  auto tend = [&]() {
-    if (lib->kernel_timing) hipEventRecord(t->e1, st);
-  };
-  // buckets no pair of this library's shape kinds can fall into are not launched at all
-  auto may = [&](int b) { return (lib->possible_buckets >> b) & 1u; };
-  const bool any_gjk = may(B_PRIM) || may(B_CC) || may(B_PC) || may(B_CP) || may(B_LARGE);
-  const bool bvg = q.guess_mode == HFCL_GUESS_BOUNDING_VOLUME;
-  HIP_TRY(hipMemsetAsync(lib->d_counts, 0, N_COUNTERS * sizeof(uint32_t), st));
-  tbeg("k_classify");
-  launch_classify(blocks_for(n, CLS_BLOCK * 8), st, wk, lib->d_kinds, uint32_t(lib->n_shapes), q.mode != 1);
-  tend();
-
-  // the solids' kernels of the batch (closed forms, GJK; their EPA follows below, behind the mesh walks: a mesh x solid leaf can queue for it)
-  auto launch_solids = [&]() -> int {
-    // A small batch (option gjk_beside_max) of a library without meshes: its buckets' kernels -- independent of each other, each a chain of
-    // GJK trips on a chip it does not fill -- fan out over the caller's stream and three helpers, joined in front of the EPA section
-    // (cfg5 at 20 000 pairs: four GJK kernels of 40-116 us in a row).
-    // From three iterative kernels on: a fork and a join cost ~0.08 ms themselves (cfg2, closed forms + one GJK kernel: 0.10 -> 0.20 ms with them).
-    int kernels = 0;
-    for (int b : {int(B_PRIM), int(B_CC), int(B_PC), int(B_CP), int(B_LARGE), int(B_TRI)}) kernels += may(b) ? 1 : 0;
-    bool fan = lib->gjk_beside_max && n <= lib->gjk_beside_max && lib->h_meshes.empty() && kernels >= 3;
-    if (fan && ensure_gjk_streams(lib) != HFCL_OK) fan = false;
-    hipStream_t const caller = st;
-    int fan_i = 0;
-    uint32_t used = 0;
-    if (fan) HIP_TRY(hipEventRecord(lib->gjk_fork, caller));
-    auto next_stream = [&]() -> hipStream_t {
-      if (!fan) return caller;
-      const int k = fan_i;
-      fan_i = (fan_i + 1) % 4;
-      if (k && !(used & (1u << (k - 1)))) {
-        used |= 1u << (k - 1);
-        (void)hipStreamWaitEvent(lib->gjk_st[k - 1], lib->gjk_fork, 0);
-      }
-      return k ? lib->gjk_st[k - 1] : caller;
-    };
-    if (may(B_CLOSED)) {
-      st = next_stream();
-      tbeg("k_closed");
-      launch_closed<T>(blocks_for(n, 256), st, wk, lv, io, q, lib->closed_staged);
-      tend();
-    }
-    if (may(B_PRIM)) {
-      st = next_stream();
-      tbeg("k_gjk_prim");
-      launch_gjk_prim<T>(blocks_for(n, 256), st, wk, lv, io, q, bvg);
-      tend();
-    }
-
-    launch_cvx<T>(lib, wk, lv, io, q, caller, ti, n, next_stream);
-
-    if (may(B_LARGE)) {
-      st = next_stream();
-      tbeg("k_gjk_large");
-      launch_gjk_large<T>(blocks_for(n, 256 / LARGE_W), st, wk, lv, io, q, bvg);
-      tend();
-    }
-
-    if (may(B_TRI)) {
-      st = next_stream();
-      tbeg("k_triangle");
-      launch_triangle<T>(blocks_for(n / 8 + 1, 64 / BS_W), st, wk, lv, io, q);
-      tend();
-    }
-    st = caller;
-    for (int k = 0; k < 3; ++k)
-      if (used & (1u << k)) {
-        HIP_TRY(hipEventRecord(lib->gjk_join[k], lib->gjk_st[k]));
-        HIP_TRY(hipStreamWaitEvent(caller, lib->gjk_join[k], 0));
-      }
-    return HFCL_OK;
-  };
-  // the mesh walks of the batch
-  bool meshes_on_own_stream = false;
-  auto launch_meshes = [&]() -> int {
-    if (!lib->h_meshes.empty() && (may(B_BVH) || may(B_BVHSHAPE))) {
-      // every BVH shape must name a registered model: checked on the host, the kernels index the mesh table with it
-      const hfcl_lib* owner = lib;  // (helpers never run mesh batches)
-      for (const hfcl_shape& sh : owner->h_shapes)
-        if (sh.type == HFCL_BV_OBBRSS && (sh.bvh_index < 0 || size_t(sh.bvh_index) >= owner->h_meshes.size())) {
-          set_error("BVH shape with bvh_index " + std::to_string(sh.bvh_index) + " but only " + std::to_string(owner->h_meshes.size()) +
-                    " BVHModel(s) registered (hfcl_lib_add_bvh)");
-          return HFCL_ERR_INVALID_ARGUMENT;
-        }
-      rc = upload_bvh(lib);
-      if (rc) return rc;
-      BvhView<T> bv;
-      bv.nodes = std::is_same<T, double>::value ? (const DNode<T>*)lib->d_nodes64.get() : (const DNode<T>*)lib->d_nodes32.get();
-      bv.fnodes = (std::is_same<T, double>::value && lib->bvh_filter) ? lib->d_fnodes : nullptr;
-      bv.rss = std::is_same<T, double>::value ? (const DRss<T>*)lib->d_rss64.get() : (const DRss<T>*)lib->d_rss32.get();
-      bv.dnodes = std::is_same<T, double>::value ? (const DNodeD<T>*)lib->d_dnodes64.get() : (const DNodeD<T>*)lib->d_dnodes32.get();
-      bv.verts = std::is_same<T, double>::value ? (const T*)lib->d_bverts64.get() : (const T*)lib->d_bverts32.get();
-      bv.tris = lib->d_btris;
-      bv.meshes = lib->d_meshes;
-      bv.n_meshes = uint32_t(lib->h_meshes.size());
-      BvhSpill spill;
-      rc = make_bvh_spill(lib, spill, q.mode != 1);
-      if (rc) return rc;
-      // long traversals are cut into tasks when the batch is large enough for the tail to matter and the request keeps no
-      // query-wide contact count (mesh x mesh and the one-query-per-lane form of mesh x solid alike)
-      auto make_split = [&](BvhSplit& split, bool want, bool solid, bool own_tables = false) -> int {
-        memset(&split, 0, sizeof(split));
-        split.leaf_cost = lib->shape_leaf_cost;
-        if (!(want && (solid ? lib->shape_levels : lib->bvh_levels) > 1 && lib->bvh_params.num_max_contacts == 1 && !lib->bvh_params.contacts)) return HFCL_OK;
-        int r = own_tables ? ensure_bvh_split2(lib, n) : ensure_bvh_split(lib, n);
-        if (r) return r;
-        HIP_TRY(hipMemsetAsync(own_tables ? lib->d_bvh2_ctr : lib->d_bvh_ctr, 0, BVH_CTR_WORDS * sizeof(uint32_t), st));
-        split.tasks = own_tables ? lib->d_bvh2_tasks : lib->d_bvh_tasks;
-        split.sums = own_tables ? lib->d_bvh2_sums : lib->d_bvh_sums;
-        split.suspended = own_tables ? lib->d_bvh2_susp : lib->d_bvh_susp;
-        split.ctr = own_tables ? lib->d_bvh2_ctr : lib->d_bvh_ctr;
-        split.cap = uint32_t(std::min<size_t>(own_tables ? lib->bvh2_split_cap : lib->bvh_split_cap, 0x7FFFFFFFu));
-        split.n_queries = uint32_t(own_tables ? lib->bvh2_split_n : lib->bvh_split_n);
-        split.budget = lib->bvh_budget;
-        split.budget0 = lib->bvh_budget0;
-        split.n_levels = lib->bvh_levels;
-        if (lib->bvh_auto && 2 * n <= 3 * size_t(lib->n_cus) * 512) {  // (8 waves of 64 lanes per CU are resident)
-          split.budget0 = 512;
-          split.budget = 16;
-          split.n_levels = BVH_MAX_LEVELS;
-        }
-        split.coop_grid = uint32_t(lib->n_cus) * 8u;
-        split.cut_ticks = solid ? lib->shape_cut_ticks : (own_tables ? 0u : lib->bvh_cut_ticks);  // (the second set has no chunk tables)
-        split.cut_cap = split.cap;
-        // (mesh x solid: the EPA queue has room for one item per query and per chunk -- shape_defer_cap entries, sized before the walk)
-        split.cut_task_cap = solid ? (wk.shape_defer_cap > n ? uint32_t(std::min<size_t>(wk.shape_defer_cap - n, split.cap)) : 0u) : split.cap;
-        split.cut_words = lib->d_bvh_cut_words;
-        split.cut_vals = lib->d_bvh_cut_vals;
-        if (!solid && lib->bvh_coop) {
-          split.coop = 1u;
-          const bool one_round = lib->walk_auto && n <= 220000;
-          const uint32_t rounds = lib->walk_auto ? (one_round ? 1u : 2u) : lib->walk_rounds;
-          split.budget0 = lib->bvh_budget0_coop ? lib->bvh_budget0_coop
-                                                : (n > 500000 ? 640u : (one_round ? (n > 120000 ? 320u : 256u) : (rounds ? (n > 150000 ? std::max(320u, lib->walk_budget[0]) : lib->walk_budget[0]) : 256u)));
-          // the queries' own phase as walk / leaves / resolve rounds (narrow node ids; rec indices travel in 28 bits)
-          if (rounds && n < (size_t(1) << 28)) {
-            r = ensure_walk(lib, n);
-            if (r) return r;
-            HIP_TRY(hipMemsetAsync(lib->d_walk_ctr, 0, 8 * WALK_ROUNDS * sizeof(uint32_t), st));
-            split.walk.recs = lib->d_walk_recs;
-            split.walk.items = lib->d_walk_items;
-            split.walk.res = lib->d_walk_res;
-            split.walk.ctr = lib->d_walk_ctr;
-            split.walk.list_in = lib->d_walk_lists;
-            split.walk.list_out = lib->d_walk_lists;
-            split.walk.item_cap = uint32_t(std::min<size_t>(lib->walk_n * WALK_K, 0xFFFFFFFFu));
-            split.walk.list_stride = uint32_t(lib->walk_n);
-            split.order = lib->walk_order ? lib->d_walk_order : nullptr;
-            split.walk_rounds = std::min<uint32_t>(rounds, WALK_ROUNDS);
-            for (int k = 0; k < WALK_ROUNDS; ++k) {
-              split.walk_k[k] = (one_round && k == 0) ? uint32_t(WALK_K) : lib->walk_k[k];
-              split.walk_budget[k] = k == 0 ? split.budget0 : lib->walk_budget[k];
-            }
-          }
-        }
-        if (solid) {
-          split.coop = lib->shape_coop ? 1u : 0u;
-          split.budget0 = lib->shape_coop ? lib->shape_budget0_coop : lib->shape_budget0;
-          split.budget = lib->shape_budget;
-          split.n_levels = lib->shape_levels;
-          // the queries' own phase as walk / leaves / resolve (one round; what is left of a walk is k_bvh_shape_coop's)
-          if (split.coop && lib->shape_walk && n >= lib->shape_walk_min && n < (size_t(1) << 28)) {
-            r = ensure_swalk(lib, n);
-            if (r) return r;
-            HIP_TRY(hipMemsetAsync(lib->d_swalk_ctr, 0, (8 * WALK_ROUNDS + 64) * sizeof(uint32_t), st));
-            split.walk.hist = lib->d_swalk_ctr + 8 * WALK_ROUNDS;
-            split.walk.perm = lib->shape_walk_sort ? lib->d_swalk_perm : nullptr;
-            split.walk.recs = lib->d_swalk_recs;
-            split.walk.items = lib->d_swalk_items;
-            split.walk.res = lib->d_swalk_res;
-            split.walk.ctr = lib->d_swalk_ctr;
-            split.walk.list_in = lib->d_swalk_lists;
-            split.walk.list_out = lib->d_swalk_lists;
-            split.walk.redo = lib->d_swalk_lists + 2 * lib->swalk_n;
-            split.walk.item_cap = uint32_t(std::min<size_t>(lib->swalk_n * WALK_K, 0xFFFFFFFFu));
-            split.walk.list_stride = uint32_t(lib->swalk_n);
-            split.walk_rounds = 1u;
-            split.walk_k[0] = uint32_t(WALK_K);
-            split.walk_budget[0] = lib->shape_walk_budget;
-          }
-        }
-        return HFCL_OK;
-      };
-      // mesh x solid: one query per lane (k_bvh_collide's SOLID form) where the request lets a leaf that needs EPA end the
-      // walk (hfcl_bvh_shape.hpp: mesh_shape_lane_request) and the lanes' stacks hold the models; the 16-lane group kernel
-      // otherwise
-      const bool shape_fast = q.mode == 1 && may(B_BVHSHAPE) && lib->bvh_shape_lane && size_t(lib->bvh_max_depth) + 1 <= size_t(BVH_STACK) &&
-                              mesh_shape_lane_request(q, lib->bvh_params.num_max_contacts);
-      // distance(): a leaf that needs EPA always ends the walk; models deeper than the lanes' stacks take the group kernel
-      const bool shape_fast_d = q.mode != 1 && may(B_BVHSHAPE) && lib->bvh_shape_lane && size_t(lib->bvh_max_depth) + 1 <= size_t(BVHD_STACK);
-      if (shape_fast || shape_fast_d) {
-        // one EPA item per unit at most (a contact ends the unit): a query, or -- when suspended walks are cut into task levels
-        // instead of being continued by a wave (HFCL_SHAPE_COOP=0) -- every task of the split's table as well
-        size_t need = lib->ws_capacity;
-        // (the chunks of a cut walk are units too, and every unit can queue one item: room for four chunks per query -- 336 B each --; a walk
-        // whose chunks would not fit is not cut, BvhSplit::cut_task_cap.  cfg4s makes ~0.6 chunks per query; n / 2 was too tight: cuts refused,
-        // 3.5 -> 4.4 ms)
-        if (shape_fast && lib->shape_coop && lib->shape_cut_ticks) need = std::max(need, n + 4 * n + 4096);
-        if (shape_fast && !lib->shape_coop && n >= 256) {
-          rc = ensure_bvh_split(lib, n);
-          if (rc) return rc;
-          need = std::max(need, n + lib->bvh_split_cap);
-        }
-        constexpr size_t DEFER_ITEM = sizeof(ShapeDeferItem<double>) + 2 * sizeof(uint32_t);  // (+ the two lists of k_bvh_shape_finish's second tier)
-        HIP_TRY(lib->d_shape_defer.grow(need * DEFER_ITEM));
-        const size_t defer_cap = lib->d_shape_defer.capacity() / DEFER_ITEM;
-        // (the solids' boxes are indexed by pair: one per pair of the workspace, not one per EPA item -- 1M pairs: 0.14 GB instead of 0.7)
-        HIP_TRY(lib->d_shape_oq.grow(lib->ws_capacity * std::max(sizeof(ObbQuery<double>), sizeof(RssQuery<double>))));
-        wk.shape_defer = lib->d_shape_defer;
-        wk.shape_defer_cap = uint32_t(std::min<size_t>(defer_cap, 0xFFFFFFFFu));
-        wk.shape_finish_over = lib->shape_finish_tiers ? reinterpret_cast<uint32_t*>(static_cast<char*>(lib->d_shape_defer.get()) + defer_cap * sizeof(ShapeDeferItem<double>)) : nullptr;
-        wk.shape_oq = lib->d_shape_oq;
-      }
-      if (q.mode == 1) {
-        // Both kinds of mesh pairs in the batch's library, and the mesh walks on streams of their own: the mesh x mesh walks (tables of
-        // their own) on a second one, beside the mesh x solid walks -- the two share nothing else, and each is a chain that leaves the chip
-        // half empty (cfgmix: 1.45 ms of mesh x mesh behind 2.3 ms of mesh x solid)
-        const bool mm_beside = meshes_on_own_stream && lib->mesh_beside >= 2 && may(B_BVH) && may(B_BVHSHAPE) && !spill.wide && !lib->bvh_cut_ticks && lib->bvh_coop && (lib->walk_auto || lib->walk_rounds != 0);
-        auto mesh_mesh = [&](bool own_tables) -> int {
-          tbeg("k_bvh_collide");
-          BvhSplit split;
-          rc = make_split(split, may(B_BVH) && !spill.wide && (n >= 256 || 2 * size_t(lib->bvh_max_depth) + 4 > size_t(std::min(BVH_STACK, BVH_STACK_FILT))), false, own_tables);
-          if (rc) return rc;
-          AsideStream beside[WALK_ROUNDS - 1];
-          memset(beside, 0, sizeof(beside));
-          const bool early = split.walk.recs && split.walk_rounds > 1 && lib->walk_early_coop;
-          if (early) {
-            rc = ensure_walk_streams(lib);
-            if (rc) return rc;
-            for (int k = 0; k < WALK_ROUNDS - 1; ++k) beside[k] = AsideStream{lib->walk_st[k], lib->walk_fork[k], lib->walk_join[k]};
-          }
-          launch_bvh_collide<T>(blocks_for(n, BVH_BLOCK), st, wk, lv, bv, io, q, lib->bvh_params, T(lib->break_distance * lib->break_distance), split, spill, early ? beside : nullptr);
-          tend();
-          return HFCL_OK;
-        };
-        auto mesh_mesh_beside = [&]() -> int {
-          hipStream_t const ms = st;
-          st = lib->mesh_st2;
-          rc = mesh_mesh(true);
-          st = ms;
-          if (rc) return rc;
-          HIP_TRY(hipEventRecord(lib->ev_mesh_join2, lib->mesh_st2));
-          return HFCL_OK;
-        };
-        if (mm_beside) {
-          HIP_TRY(hipEventRecord(lib->ev_mesh_fork2, st));
-          HIP_TRY(hipStreamWaitEvent(lib->mesh_st2, lib->ev_mesh_fork2, 0));
-          rc = mesh_mesh_beside();
-          if (rc) return rc;
-        }
-        tbeg("k_bvh_shape");
-        if (shape_fast) {
-          // tasks re-start the leaf solver from the request's guess: a walk whose leaves hand the cached guess on, or whose
-          // final guess is read, stays in one piece
-          BvhSplit split;
-          rc = make_split(split, n >= 256 && q.guess_mode != HFCL_GUESS_CACHED && !io.gout, true);
-          if (rc) return rc;
-          AsideStream aside = {nullptr, nullptr, nullptr};
-          if (lib->shape_finish_aside && wk.shape_finish_over && split.tasks && split.coop && split.cut_ticks) {
-            rc = ensure_aux(lib);
-            if (rc) return rc;
-            aside = AsideStream{meshes_on_own_stream ? lib->mesh_aux : lib->aux, lib->ev_aux2, lib->ev_aux3};  // (`aux` is the solids' EPA section's, beside)
-          }
-          launch_bvh_shape_fast<T>(blocks_for(n, BVH_BLOCK), blocks_for(n / 8 + 1, 64 / BS_W), int(std::min<size_t>(n / 4 + 1, size_t(lib->n_cus) * 8)), st, wk, lv, bv, io, q, lib->bvh_params,
-                                   T(lib->break_distance * lib->break_distance), split, spill, aside.stream ? &aside : nullptr);
-        } else {
-          launch_bvh_shape<T>(blocks_for(n / 8 + 1, 64 / BS_W), st, wk, lv, bv, io, q, lib->bvh_params, T(lib->break_distance * lib->break_distance));
-        }
-        tend();
-        if (mm_beside) {
-          HIP_TRY(hipStreamWaitEvent(st, lib->ev_mesh_join2, 0));
-        } else {
-          rc = mesh_mesh(false);
-          if (rc) return rc;
-        }
-      } else {
-        tbeg("k_bvh_shape_distance");
-        if (shape_fast_d) {
-          // long walks are handed to waves -- unless their leaves hand a cached guess on, or the final guess is read
-          BvhSpill ss;
-          memset(&ss, 0, sizeof(ss));
-          if (lib->shape_dist_budget && q.guess_mode != HFCL_GUESS_CACHED && !io.gout) {
-            HIP_TRY(lib->d_shape_dist_susp.grow(lib->ws_capacity * sizeof(ShapeDistSusp<double>)));
-            ss.susp = lib->d_shape_dist_susp;
-            ss.rerun_count = lib->pool_rerun ? lib->d_counts + CTR_SHAPE_DIST_RERUN : nullptr;
-            ss.rerun_all = lib->pool_rerun >= 2 ? 1u : 0u;
-            ss.susp_count = lib->d_counts + CTR_SHAPE_DIST_SUSP;
-            ss.budget = lib->shape_dist_budget;
-            ss.max_blocks = uint32_t(lib->n_cus) * 8u;
-            ss.pool = lib->has_flats ? 0u : lib->shape_dist_pool;
-            ss.pool_ticket = lib->d_counts + CTR_SHAPE_DIST_TICKET;
-            ss.pool_leaf_min = lib->shape_dist_leaf_min;
-            ss.pool_starve = lib->shape_dist_starve;
-          }
-          launch_bvh_shape_distance_fast<T>(blocks_for(n, BVHD_BLOCK), blocks_for(n / 8 + 1, 64 / BS_W), st, wk, lv, bv, io, q, ss);
-        }
-        else
-          launch_bvh_shape_distance<T>(blocks_for(n / 8 + 1, 64 / BS_W), st, wk, lv, bv, io, q);
-        tend();
-        tbeg("k_bvh_distance");
-        if (may(B_BVH) && !spill.wide && lib->bvhd_budget) {
-          HIP_TRY(lib->d_dist_susp.grow(lib->ws_capacity * sizeof(DistSusp<double>)));
-          spill.susp = lib->d_dist_susp;
-          spill.rerun_count = lib->pool_rerun ? lib->d_counts + CTR_DIST_RERUN : nullptr;
-          spill.rerun_all = lib->pool_rerun >= 2 ? 1u : 0u;
-          spill.susp_count = lib->d_counts + CTR_DIST_SUSP;
-          spill.budget = lib->bvhd_budget;
-          spill.max_blocks = uint32_t(lib->n_cus) * 8u;
-          spill.pool = lib->bvhd_pool;
-          spill.pool_ticket = lib->d_counts + CTR_DIST_TICKET;
-          spill.pool_leaf_min = lib->bvhd_pool_leaf_min;
-          spill.pool_starve = lib->bvhd_pool_starve;
-          spill.pool_part_min = lib->bvhd_pool_part_min;
-          if (lib->bvh_max_nodes > 32767) spill.pool = 0;  // 15-bit node ids in the pool's entry word (POOL_MAX_NODES)
-        }
-        launch_bvh_distance<T>(blocks_for(n, BVHD_BLOCK), st, wk, lv, bv, io, q, spill);
-        tend();
-      }
-    }
-    return HFCL_OK;
-  };
-  bool mesh_join_pending = false;
-  // A library with meshes AND solids: the mesh walks on a stream of their own BESIDE the solids' kernels -- the walks are chains of dependent
-  // steps that leave the chip half empty (section 3 item 6f), and every kernel of a bucket the library COULD fill is launched whether or not
-  // this batch fills it (a mesh-only batch of a mixed library used to wait for ~0.08 ms of empty GJK launches in front of its walks).
-  {
-    const bool any_mesh = !lib->h_meshes.empty() && (may(B_BVH) || may(B_BVHSHAPE));
-    const bool any_solid = may(B_CLOSED) || any_gjk || may(B_TRI);
-    bool beside = any_mesh && any_solid && lib->mesh_beside;
-    // ... when the batch holds both: a batch of mesh pairs alone pays for the solids' empty launches when they stand BESIDE its walks (grids sized
-    // for the batch, every block waiting for a wave slot of a full chip: cfg4s 2.67 -> 2.80 ms) and nothing when they stand in front of them
-    // (4 us each on an empty chip).  The witness is the library's batch before this one (its bucket counts, read without waiting for them:
-    // they only choose between two orders of the same launches); the first batch runs beside.
-    if (beside && lib->mesh_beside < 4 && lib->ran_batch && lib->h_counts) {
-      uint32_t solids_before = 0, meshes_before = one_count(lib->h_counts, int(B_BVH)) + one_count(lib->h_counts, int(B_BVHSHAPE));
-      for (int b : {int(B_CLOSED), int(B_PRIM), int(B_CC), int(B_PC), int(B_CP), int(B_LARGE), int(B_TRI)}) solids_before += one_count(lib->h_counts, b);
-      if (!solids_before || !meshes_before) beside = false;
-    }
-    if (beside && ensure_mesh_stream(lib) != HFCL_OK) beside = false;  // (no helper stream: one after the other, as before)
-    if (beside) {
-      hipStream_t const caller = st;
-      HIP_TRY(hipEventRecord(lib->ev_mesh_fork, caller));
-      HIP_TRY(hipStreamWaitEvent(lib->mesh_st, lib->ev_mesh_fork, 0));
-      st = lib->mesh_st;  // (the lambdas above launch on `st`)
-      meshes_on_own_stream = true;
-      rc = launch_meshes();
-      st = caller;
-      if (rc) return rc;
-      HIP_TRY(hipEventRecord(lib->ev_mesh_join, lib->mesh_st));
-      rc = launch_solids();
-      if (rc) return rc;
-      if (lib->mesh_beside < 2) HIP_TRY(hipStreamWaitEvent(caller, lib->ev_mesh_join, 0));
-      else mesh_join_pending = true;  // (the solids' EPA section first: no mesh kernel feeds its queues; joined in front of the batch's last launches)
-    } else {
-      rc = launch_solids();
-      if (rc) return rc;
-      rc = launch_meshes();
-      if (rc) return rc;
-    }
-  }
-
-  if (q.compute_penetration && any_gjk) {
-    // ---- EPA.  Fast tiers in three stages (hfcl_k_epa.hip) for batches large enough to pay for the extra launches: one lane per polytope
-    // prepares it (encloseOrigin, first tetrahedron) and writes its record; the loop kernels between them do nothing but expand.
-    //   fp32 convex x convex (the top queue): k_epa_prepare / k_epa_loop / k_epa_records, k_epa_resume_cc for the polytopes that outgrow the block
-    //   every other queue, both precisions:    k_epa_prepare_general / k_epa_loop_general / k_epa_records_general, the full-capacity tier behind them
-    // Otherwise the one-kernel forms (launch_epa_fast: fp32 streams, fp64 lockstep kernels).
-    constexpr bool F32 = std::is_same<T, float>::value;
-    const bool general_q = may(B_PRIM) || may(B_PC) || may(B_CP) || (!F32 && may(B_CC));
-    bool cc_staged = false;
-    if constexpr (F32) cc_staged = may(B_CC) && lib->epa_cc_staged && n >= lib->epa_cc_staged_min;
-    bool gen_staged = general_q && lib->epa_general_staged && n >= lib->epa_general_staged_min;
-    // A very small batch: the full-capacity tier alone, over every seed (k_epa_requeue) -- the batch is as long as its longest polytope either way, and
-    // the fast tier in front of the full one is a second such chain (cfg5's mix at 2 000 pairs: 0.18 + 0.22 ms)
-    // (fp64 only: its tiers are compiled without contraction and agree bit for bit; the fp32 tiers are different instantiations of contracted code)
-    const bool direct = sizeof(T) == 8 && lib->epa_direct_max && n <= lib->epa_direct_max;
-    auto need_aux = [&]() -> int { return ensure_aux(lib); };
-    auto tbeg_on = [&](const char* name, hipStream_t s) {
-      if (!lib->kernel_timing) return;
-      t = timer_slot(lib, ti++, name);
-      hipEventRecord(t->e0, s);
-    };
-    auto tend_on = [&](hipStream_t s) {
-      if (lib->kernel_timing) hipEventRecord(t->e1, s);
-    };
-    if (direct) cc_staged = gen_staged = false;
-    if (cc_staged) {
-      HIP_TRY(lib->d_epa_ready.grow(lib->ws_capacity * sizeof(EpaReady<float>)));
-      wk.epa_ready = lib->d_epa_ready;
-    }
-    if (gen_staged) {
-      HIP_TRY(lib->d_epa_ready_g.grow(lib->ws_capacity * sizeof(EpaReadyG<T>)));
-      wk.epa_ready_g = lib->d_epa_ready_g;
-    }
-    if constexpr (F32) {
-      if (cc_staged) {
-        tbeg("k_epa_prepare");
-        launch_epa_prepare(blocks_for(n / 4 + 1, 256), st, wk, lv, io, q);
-        tend();
-      }
-    }
-    if (gen_staged) {
-      tbeg("k_epa_prepare_general");
-      launch_epa_prepare_general<T>(blocks_for(n / 4 + 1, 256), st, wk, lv, io, q, F32);
-      tend();
-    }
-    if (direct) {
-      tbeg("k_epa<full>");
-      launch_epa_requeue<T>(st, wk);
-      // (the grid: a lane group per seed, up to what k_epa's shape-0 support point area holds -- n_cus * 16 blocks)
-      launch_epa_full<T>(int(std::min<size_t>(blocks_for(n / 2 + 1, 64 / epa_we2<T>), size_t(lib->n_cus) * 16)), st, wk, lv, io, q);
-      tend();
-    } else {
-    const int epa_batches = int(std::min<size_t>((n + 64 / EPA_WE - 1) / (64 / EPA_WE), size_t(1) << 22));
-    tbeg("k_epa<fast>");
-    // fp64 with both classes of pairs: their fast-tier kernels on two streams (each one's tail under the other's body)
-    hipStream_t st2 = nullptr;
-    if constexpr (!F32) {
-      if (lib->epa64_two_streams && lib->has_curved && general_q) {
-        if (int rc2 = need_aux()) return rc2;
-        st2 = lib->aux;
-        HIP_TRY(hipEventRecord(lib->ev_aux0, st));
-        HIP_TRY(hipStreamWaitEvent(st2, lib->ev_aux0, 0));
-      }
-    }
-    // (the launchers size the grids of the persistent forms themselves: here only the number of wave-sized batches)
-    if constexpr (F32) {
-      if (cc_staged) launch_epa_loop(epa_batches, st, wk, lv, q, lib->n_cus);
-    }
-    if (gen_staged) launch_epa_loop_general<T>(epa_batches, st, st2, wk, lv, q, lib->n_cus, lib->has_curved);
-    if ((F32 && may(B_CC) && !cc_staged) || (general_q && !gen_staged))
-      launch_epa_fast<T>(epa_batches, st, wk, lv, io, q, may(B_CC) && !cc_staged, general_q && !gen_staged, lib->n_cus, lib->has_curved, st2);
-    if (st2) {
-      HIP_TRY(hipEventRecord(lib->ev_aux1, st2));
-      HIP_TRY(hipStreamWaitEvent(st, lib->ev_aux1, 0));
-    }
-    tend();
-    if (cc_staged || gen_staged) {
-      // What ends the batch: the records of the finished polytopes (bound by memory), the continuation of the handed-over ones
-      // (k_epa_resume_cc; as long as its longest chain of iterations) and the full-capacity tier (likewise).  The records run on a stream of
-      // their own beside the latter two (with a convex x convex tier the full-capacity tier joins them there, beside the continuation).
-      const bool aside = lib->records_aside;
-      if (aside) {
-        if (int rc2 = need_aux()) return rc2;
-        HIP_TRY(hipEventRecord(lib->ev_aux0, st));
-        HIP_TRY(hipStreamWaitEvent(lib->aux, lib->ev_aux0, 0));
-      }
-      hipStream_t rs = aside ? lib->aux : st;
-      tbeg_on("k_epa_records", rs);
-      if constexpr (F32) {
-        if (cc_staged) launch_epa_records(blocks_for(n / 4 + 1, 256), rs, wk, lv, io, q);
-      }
-      if (gen_staged) launch_epa_records_general<T>(blocks_for(n / 4 + 1, 256), rs, wk, lv, io, q, F32);
-      tend_on(rs);
-      // (without a continuation kernel of its own the batch's stream takes the full-capacity tier)
-      hipStream_t fs = cc_staged ? rs : st;
-      tbeg_on("k_epa<full>", fs);
-      launch_epa_full<T>(blocks_for(n / 16 + 1, 64 / epa_we2<T>), fs, wk, lv, io, q);
-      tend_on(fs);
-      if (aside) HIP_TRY(hipEventRecord(lib->ev_aux1, rs));
-      if constexpr (F32) {
-        if (cc_staged) {
-          tbeg("k_epa_resume_cc");
-          launch_epa_resume_cc(blocks_for(n / 16 + 1, 64 / HFCL_EPA_CC_RESUME_WE), st, wk, lv, io, q);
-          tend();
-        }
-      }
-      if (aside) HIP_TRY(hipStreamWaitEvent(st, lib->ev_aux1, 0));
-    } else {
-      tbeg("k_epa<full>");
-      launch_epa_full<T>(blocks_for(n / 16 + 1, 64 / epa_we2<T>), st, wk, lv, io, q);
-      tend();
-    }
-    }
-  }
-  // last: a launch of a few waves that, between the GJK and the EPA kernels, only waited for a free CU while the other
-  // half of a split batch had the chip (0.2 ms of this stream's timeline on cfg5)
-  if (mesh_join_pending) HIP_TRY(hipStreamWaitEvent(st, lib->ev_mesh_join, 0));
-  tbeg("k_unsupported");
-  if (may(B_UNSUPPORTED)) launch_unsupported<T>(blocks_for(n, 256 * 64), st, wk, io, int(B_UNSUPPORTED));
-  if (lib->h_meshes.empty()) {  // BVH shapes without any registered mesh: flagged, never left unwritten
-    if (may(B_BVHSHAPE)) launch_unsupported<T>(blocks_for(n, 256 * 64), st, wk, io, int(B_BVHSHAPE));
-    if (may(B_BVH)) launch_unsupported<T>(blocks_for(n, 256 * 64), st, wk, io, int(B_BVH));
-  }
-  tend();
-  HIP_TRY(hipMemcpyAsync(lib->counts_dst ? lib->counts_dst : lib->h_counts, lib->d_counts, N_COUNTERS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  lib->ran_batch = lib->counts_dst == nullptr;
-  HIP_TRY(hipGetLastError());
-  return HFCL_OK;
-}
-
-// shallow clone for the second half of a split batch: a view of its owner's device shape tables (`own` of a helper stays empty), everything
-// else its own.  The view of `h` onto the tables `lib` owns (h == lib: the library's own):
-static void share_tables(hfcl_lib* h, const hfcl_lib* lib) {
-  const hfcl_lib::Tables& t = lib->own;
-  h->n_shapes = lib->n_shapes;
-  h->d_shapes64 = t.shapes64;
-  h->d_shapes32 = t.shapes32;
-  h->d_verts64 = t.verts64;
-  h->d_verts32 = t.verts32;
-  h->d_kinds = t.kinds;
-  h->possible_buckets = lib->possible_buckets;
-  h->has_curved = lib->has_curved;
-  h->has_flats = lib->has_flats;
-  h->d_graph_base = t.graph.base;
-  h->d_graph_off = t.graph.off;
-  h->d_graph_ent32 = t.graph.ent32;
-  h->d_graph_ent64 = t.graph.ent64;
-  h->climb_min = lib->climb_min;
-}
-static hfcl_lib* make_helper(hfcl_lib* lib) {
-  hfcl_lib* h = new hfcl_lib;
-  h->device = lib->device;
-  share_tables(h, lib);
-  h->cvx_w = lib->cvx_w;
-  h->epa_resume_slots = lib->epa_resume_slots;
-  h->closed_staged = lib->closed_staged;
-  h->epa_cc_staged = lib->epa_cc_staged;
-  h->records_aside = lib->records_aside;
-  h->epa_general_staged = lib->epa_general_staged;
-  h->shape_finish_tiers = lib->shape_finish_tiers;
-  h->shape_finish_aside = lib->shape_finish_aside;
-  h->shape_cut_ticks = lib->shape_cut_ticks;
-  h->epa_general_staged_min = lib->epa_general_staged_min;
-  h->epa64_two_streams = lib->epa64_two_streams;
-  h->epa_cc_staged_min = lib->epa_cc_staged_min;
-  h->n_cus = lib->n_cus;
-  bool ok = h->d_counts.grow(N_COUNTERS) == hipSuccess;
-  ok = ok && h->h_counts.alloc(N_COUNTERS) == hipSuccess;
-  ok = ok && h->d_epa_v0.grow(size_t(h->n_cus) * 16 * (64 / EPA_WE2) * EPA_MAX_VERTS * sizeof(Quad<double>)) == hipSuccess;
-  if (!ok) {
-    hfcl_lib_destroy(h);
-    return nullptr;
-  }
-  memset(h->h_counts, 0, N_COUNTERS * sizeof(uint32_t));
-  return h;
-}
-
-template <typename T> static IO<T> io_at(const IO<T>& io, size_t lo);
-template <> IO<double> io_at(const IO<double>& io, size_t lo) {
-  return IO<double>{io.tf1 + 12 * lo, io.tf2 + 12 * lo, io.out + lo, io.gin ? io.gin + lo : nullptr, io.gout ? io.gout + lo : nullptr};
-}
-template <> IO<float> io_at(const IO<float>& io, size_t lo) {
-  return IO<float>{io.tf1 + 7 * lo, io.tf2 + 7 * lo, io.out + lo, nullptr, nullptr};
-}
-
-// Does a batch of n pairs of this library run as two halves on two streams?  Automatic choice: a library whose pairs
-// spread over three or more of the iterative buckets (mixed scenes: cfg5 4.05 -> 3.80 ms) -- the halves then run different
-// kernels side by side; with one or two kernels in the batch the halves only share the machine phase by phase and the
-// doubled fixed costs lose 3 % (cfg2, cfg3).  A/B in profiles/r01_k_two_stream_overlap.txt.
-bool batch_splits(const hfcl_lib* lib, size_t n) {
-  constexpr size_t MIN_SPLIT = 1u << 17;
-  int parts = lib->split;
-  if (parts == 0) {
-    int kinds = 0;
-    for (int b : {int(B_PRIM), int(B_CC), int(B_PC), int(B_CP), int(B_LARGE)}) kinds += (lib->possible_buckets >> b) & 1u;
-    parts = kinds >= 3 ? 2 : 1;
-  }
-  // meshes keep query-wide side state (contact lists, pair ids in them): they run unsplit
-  return parts >= 2 && n >= MIN_SPLIT && lib->h_meshes.empty();
-}
-int ensure_helper(hfcl_lib* lib) {
-  if (lib->helper) return HFCL_OK;
-  HIP_TRY(hipSetDevice(lib->device));
-  hfcl_lib* h = make_helper(lib);
-  Stream side;
-  Event fork, join;
-  if (!h || side.create() != hipSuccess || fork.create() != hipSuccess || join.create() != hipSuccess) {
-    if (h) hfcl_lib_destroy(h);  // nothing half-made stays behind: the next call retries cleanly
-    set_error("split batches: HIP allocation failed");
-    return HFCL_ERR_HIP;
-  }
-  lib->side = std::move(side);
-  lib->ev_fork = std::move(fork);
-  lib->ev_join = std::move(join);
-  lib->helper = h;
-  return HFCL_OK;
-}
-
-template <typename T>
-static int run_batch(hfcl_lib* lib, const uint32_t* d_s1, const uint32_t* d_s2, IO<T> io, size_t n, QParams<T> q,
-                     hipStream_t st) {
-  lib->last_split = false;
-  if (!lib->in_host_batch) lib->last_host = false;
-  if (lib->graph_dirty) {
-    const int rcg = upload_graph(lib);
-    if (rcg) return rcg;
-  }
-  if (!batch_splits(lib, n)) return run_batch_one<T>(lib, d_s1, d_s2, io, n, q, st);
-  int rc0 = ensure_helper(lib);
-  if (rc0) return rc0;
-  hfcl_lib* h2 = lib->helper;
-  h2->kernel_timing = lib->kernel_timing;
-  h2->break_distance = lib->break_distance;
-  h2->bvh_params = lib->bvh_params;
-  const size_t h = n / 2;  // unequal parts (0.35 / 0.6 / 0.7 of the batch first) measured slower on cfg3 and cfg5
-  HIP_TRY(hipEventRecord(lib->ev_fork, st));  // the inputs are ready where the caller's stream stands now
-  HIP_TRY(hipStreamWaitEvent(lib->side, lib->ev_fork, 0));
-  int rc = run_batch_one<T>(lib, d_s1, d_s2, io, h, q, st);
-  if (rc) return rc;
-  rc = run_batch_one<T>(h2, d_s1 + h, d_s2 + h, io_at<T>(io, h), n - h, q, lib->side);
-  if (rc) return rc;
-  HIP_TRY(hipEventRecord(lib->ev_join, lib->side));
-  HIP_TRY(hipStreamWaitEvent(st, lib->ev_join, 0));  // results are complete in the caller's stream order
-  lib->last_split = true;
   return HFCL_OK;
 }
 
@@ -1976,44 +1070,10 @@ static int host_batch(hfcl_lib* lib, const uint32_t* s1, const uint32_t* s2, con
     return HFCL_ERR_INVALID_ARGUMENT;
   }
   HIP_TRY(hipSetDevice(lib->device));
-  if (pipelined && n <= hfcl_lib::SMALL_MAX && !lib->pipe_chunk && !f32) return host_batch_small(lib, s1, s2, tf1, tf2, n, creq, dreq, out, gin, gout, compact);
-  // Chunks: large enough that a chunk's fixed costs (a dozen launches, ~0.1 ms) vanish, small enough that the pipeline
-  // has several chunks to overlap.  The link is busy from the first byte to the last only if the first chunk is small
-  // (nothing computes until it has arrived) and the last one too (nothing overlaps its way back): the sizes ramp up
-  // geometrically from 16k pairs to the steady size and down again (1M pairs: 6.4 -> see profiles/r03_c).
-  std::vector<size_t> bounds;  // chunk k = [bounds[k], bounds[k + 1])
-  bounds.push_back(0);
-  size_t max_chunk = n;
-  if (pipelined && lib->pipe_chunk) {
-    for (size_t lo = 0; lo < n; lo += lib->pipe_chunk) bounds.push_back(std::min(n, lo + lib->pipe_chunk));
-    max_chunk = std::min(n, lib->pipe_chunk);
-  } else if (pipelined && f32 && n > (size_t(1) << 16)) {
-    // fp32: 108 B per pair cross the link -- a quarter of the time the kernels take -- and those kernels live on latency, so a chunk a quarter the
-    // size takes 0.44 of the time, not 0.25: few, large chunks (1M convex32 pairs: three chunks 3.7 ms, the fp64 policy's ten 6.4 ms, one chunk 4.1 ms)
-    const size_t c = std::min<size_t>(std::max<size_t>((n + 2) / 3, size_t(1) << 16), size_t(1) << 19);
-    for (size_t lo = 0; lo < n; lo += c) bounds.push_back(std::min(n, lo + c));
-    max_chunk = std::min(n, c);
-  } else if (pipelined && n > (size_t(1) << 16)) {
-    const size_t steady = std::min<size_t>(std::max<size_t>(n / 6, size_t(1) << 16), size_t(1) << 18);
-    std::vector<size_t> up;    // 16k, 32k, ... below the steady size
-    for (size_t c = size_t(1) << 14; c < steady; c *= 2) up.push_back(c);
-    size_t ramp = 0;
-    for (size_t c : up) ramp += c;
-    while (!up.empty() && 2 * ramp + steady > n) {  // a batch too small for the whole ramp: shorten it from the top
-      ramp -= up.back();
-      up.pop_back();
-    }
-    size_t lo = 0;
-    for (size_t c : up) bounds.push_back(lo += c);
-    const size_t mid_end = n - ramp;
-    while (mid_end - lo > steady + steady / 2) bounds.push_back(lo += steady);
-    if (mid_end > lo) bounds.push_back(lo = mid_end);
-    for (size_t k = up.size(); k-- > 0;) bounds.push_back(lo += up[k]);
-    max_chunk = 0;
-    for (size_t k = 0; k + 1 < bounds.size(); ++k) max_chunk = std::max(max_chunk, bounds[k + 1] - bounds[k]);
-  } else {
-    bounds.push_back(n);
-  }
+  if (pipelined && n <= hfcl_lib::SMALL_MAX && !lib->opt.pipe_chunk && !f32) return host_batch_small(lib, s1, s2, tf1, tf2, n, creq, dreq, out, gin, gout, compact);
+  const std::vector<size_t> bounds = plan_chunks(n, lib->opt.pipe_chunk, pipelined, f32);  // chunk k = [bounds[k], bounds[k + 1]): hfcl_plan.hpp
+  size_t max_chunk = 0;
+  for (size_t k = 0; k + 1 < bounds.size(); ++k) max_chunk = std::max(max_chunk, bounds[k + 1] - bounds[k]);
   const size_t n_chunks = bounds.size() - 1;
   int rc = ensure_staging(lib, max_chunk, gin != nullptr, gout != nullptr, compact);
   if (rc) return rc;
@@ -2045,7 +1105,7 @@ static int host_batch(hfcl_lib* lib, const uint32_t* s1, const uint32_t* s2, con
   };
 
   // option pipe_trace: per-chunk time line of the three threads on stderr (ms since the call started)
-  const bool trace = lib->pipe_trace;
+  const bool trace = lib->opt.pipe_trace;
   const auto t_call = std::chrono::steady_clock::now();
   auto ms_now = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count(); };
   std::vector<double> tr(trace ? 6 * n_chunks : 0);
@@ -2365,20 +1425,20 @@ int hfcl_last_kernel_breakdown(hfcl_lib* lib, const char** names, double* ms, in
 
 // parts = 2: batches of at least 128k pairs (libraries without meshes) run as two halves on two streams; 1: one stream
 void hfcl_lib_set_split(hfcl_lib* lib, int parts) {
-  if (lib) lib->split = parts >= 2 ? 2 : (parts == 1 ? 1 : 0);
+  if (lib) lib->opt.split = parts >= 2 ? 2 : (parts == 1 ? 1 : 0);
 }
-int hfcl_lib_get_split(const hfcl_lib* lib) { return lib ? lib->split : 0; }
+int hfcl_lib_get_split(const hfcl_lib* lib) { return lib ? lib->opt.split : 0; }
 // (diagnostic, not part of the ABI: the counters of the last batch's walk rounds -- WalkArgs::ctr, 8 words per round -- of the mesh x mesh (solid = 0) or the
 // mesh x solid walks, and BVH_CTR_TASKS / BVH_CTR_SUSPENDED of their split tables behind them: tools/dbg/walk_counters.py)
 extern "C" int hfcl_debug_walk_counters(hfcl_lib* lib, int solid, uint32_t* out34) {
   if (!lib || !out34) return HFCL_ERR_INVALID_ARGUMENT;
   if (hipSetDevice(lib->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return HFCL_ERR_HIP;
   memset(out34, 0, 34 * sizeof(uint32_t));
-  const uint32_t* src = solid ? lib->d_swalk_ctr : lib->d_walk_ctr;
+  const uint32_t* src = solid ? lib->walk_ms.ctr : lib->walk_mm.ctr;
   if (src && hipMemcpy(out34, src, 8 * WALK_ROUNDS * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return HFCL_ERR_HIP;
   uint32_t ctr[BVH_CTR_WORDS] = {0};
   // (a mixed batch run beside walks its mesh x mesh pairs on the second set of tables; otherwise the kind walked last owns the first)
-  const uint32_t* bsrc = (!solid && lib->d_bvh2_ctr) ? lib->d_bvh2_ctr : lib->d_bvh_ctr;
+  const uint32_t* bsrc = (!solid && lib->split_beside.ctr) ? lib->split_beside.ctr : lib->split_main.ctr;
   if (bsrc && hipMemcpy(ctr, bsrc, sizeof(ctr), hipMemcpyDeviceToHost) != hipSuccess) return HFCL_ERR_HIP;
   out34[32] = ctr[BVH_CTR_TASKS];
   out34[33] = ctr[BVH_CTR_SUSPENDED];
@@ -2391,7 +1451,7 @@ extern "C" void hfcl_debug_live_handles(int64_t* out4) {
 }
 // pairs per chunk of the host-buffer pipeline (0 = automatic: n/8 clamped to 32k .. 256k)
 void hfcl_lib_set_host_chunk(hfcl_lib* lib, size_t pairs) {
-  if (lib) lib->pipe_chunk = pairs;
+  if (lib) lib->opt.pipe_chunk = pairs;
 }
 // Options by name (the list: option_keys above; INTEGRATION.md describes them).  Keys are case-insensitive, an "HFCL_" prefix -- the
 // spelling of the environment fallback -- is accepted.  Holds from the next batch on; the caller does not call it while a batch of this
@@ -2411,8 +1471,7 @@ int hfcl_lib_set_option(hfcl_lib* lib, const char* key, const char* value) {
   }
   // buffers sized by an option are sized again by the next batch
   if (k == "epa_resume_slots") lib->epa_capacity = 0;
-  if (k == "bvh_task_slots") lib->bvh_split_n = 0;
-  if (lib->helper) apply_option(lib->helper, k, value);
+  if (k == "bvh_task_slots") lib->split_main.n = 0;
   return HFCL_OK;
 }
 // The option names, one per call: index 0, 1, ... until nullptr.

@@ -1,4 +1,5 @@
-// hfcl_host.hpp -- internal header of the host units (hfcl_host.hip: the library object, options, uploads, the batch and host pipelines;
+// hfcl_host.hpp -- internal header of the host units (hfcl_host.hip: the library object, options, uploads, request set-up, the entry points
+// and the host pipeline; hfcl_host_batch.hip: one device-resident batch -- workspace, stream sets, the dispatcher run_batch;
 // hfcl_host_patch.hip: contact patches; hfcl_host_scene.hip: scene queries and the cull): the library object and what the units call of
 // each other.  Not included by the kernel units.
 #pragma once
@@ -38,7 +39,123 @@ struct KernelTime {
   bool used;
 };
 
+// Tables of a split traversal (BvhSplit): task table, unit summaries, suspended-query list, counters; the main set also the stack entries of
+// cut walks (BvhSplit::cut_words / cut_vals, `cap` entries each).  n / cap: queries / tasks they are sized for (0: not allocated)
+struct SplitTables {
+  DevBuf<BvhTask> tasks;
+  DevBuf<void> sums;
+  DevBuf<uint32_t> susp, ctr, cut_words;
+  DevBuf<double> cut_vals;
+  size_t n = 0, cap = 0;
+};
+// Tables of a collide() walk in walk / leaves / resolve rounds (hfcl_dev.hpp: WalkRec): records, item list, leaf results, the query lists,
+// counters (8 words per round; mesh x solid: then the 64 words of WalkArgs::hist), and `order`: BvhSplit::order of mesh x mesh (one entry
+// per suspended slot), WalkArgs::perm of mesh x solid
+struct WalkTables {
+  DevBuf<void> recs;
+  DevBuf<uint32_t> items;
+  DevBuf<void> res;
+  DevBuf<uint32_t> lists, ctr, order;
+  size_t n = 0;
+};
+
+// Everything hfcl_lib_set_option sets (hfcl_host.hip: apply_option): plain values, read when a batch is set up.  A split batch's helper takes
+// its owner's block as it is (run_batch).
+struct hfcl_options {
+  uint32_t climb_min = HFCL_CLIMB_MIN;  // HFCL_CLIMB_MIN: hulls of at least this many vertices with a graph hill-climb
+  // 0 in line; 1 the mesh walks beside the solids' GJK kernels; 2 also mesh x mesh beside mesh x solid, the solids' EPA section beside both
+  // (1, 2: when the library's last batch held meshes and solids); 4: as 2 whatever the last batch held
+  uint32_t mesh_beside = 2;
+  bool mesh_prio = false;  // option mesh_prio = 1: the streams of the mesh x solid walks at the device's highest priority (read when they are created)
+  uint32_t epa_direct_max = 4096;    // largest batch whose EPA seeds all go to the full-capacity tier, the fast tiers not launched (0: never)
+  uint32_t gjk_beside_max = 120000;  // largest batch whose GJK kernels fan out (0: never; below the size from which batches run as two halves)
+  bool epa_general_staged = false;       // HFCL_EPA_GENERAL_STAGED=1: prepare / loop / records for the general queues too.  Byte-identical
+                                         // records; measured slower in wall-clock on cfg2 (0.416 -> 0.479 ms) and cfg5 unsplit (4.77 -> 5.30 ms
+                                         // per 1M mixed pairs), faster only on cfg5 split (5.34 -> 5.13): profiles/r05_e_general_staged.md
+  size_t epa_general_staged_min = 32768; // HFCL_EPA_GENERAL_STAGED_MIN
+  bool records_aside = true;     // HFCL_EPA_RECORDS_ASIDE=0: k_epa_records on the batch's stream
+  bool epa64_two_streams = true; // HFCL_EPA64_TWO_STREAMS=0: the two fp64 fast-tier kernels one after the other
+  bool epa_cc_staged = true;     // HFCL_EPA_CC_STAGED=0: the one-kernel form (k_epa_stream<.., CC>)
+  size_t epa_cc_staged_min = 32768;  // ... which batches below this many pairs keep (two launches less); HFCL_EPA_CC_STAGED_MIN
+  bool shape_finish_tiers = true;  // HFCL_SHAPE_FINISH_TIERS=0: k_bvh_shape_finish in one launch at full capacity
+  bool shape_finish_aside = true;  // HFCL_SHAPE_FINISH_ASIDE=0: all of k_bvh_shape_finish behind the last launch of k_bvh_shape_coop
+  bool bvh_shape_lane = true;     // HFCL_BVH_SHAPE_LANE=0: the group kernels for every request (A/B switch)
+  // step budgets of the one-query-per-lane mesh x solid walk (a unit suspends into tasks when it has taken that many BV-test
+  // equivalents; a GJK leaf counts shape_leaf_cost): the queries themselves / their tasks.  The steps per query have a heavy
+  // tail whatever the batch size (median 1, mean ~60, maximum > 3000 steps with > 1000 leaves), so the walk is always split.
+  uint32_t shape_budget0 = 128, shape_budget = 96, shape_leaf_cost = 32, shape_levels = BVH_MAX_LEVELS;
+  // Suspended queries are continued by k_bvh_shape_coop (a wave per query, 64 stack entries per trip) instead of task levels
+  // (HFCL_SHAPE_COOP=0: the levels); the queries' own budget is then 16 steps (100k queries per kind, budgets 8 / 16 / 32 / 128:
+  // sphere 2.0 / 2.0 / 2.4 / 2.6 ms, ellipsoid 7.5 / 8.1 / 8.4 / 8.3, box 1.4 / 1.3 / 1.2 / 1.1; profiles/r03_i)
+  bool shape_coop = true;
+  // ... and a walk such a kernel has worked on for this many clock ticks is cut into chunk tasks for its next launch (BvhSplit::cut_ticks;
+  // HFCL_BVH_CUT_TICKS / HFCL_SHAPE_CUT_TICKS; 0: never).  The records equal the uncut walks' in every field wherever the cuts fall
+  // (tools/cut_check.py).  mesh x solid, 600 000 ticks (~2.3x the mean walk): 100k mixed queries 4.4 -> 3.7 ms on one box, the single
+  // kinds within +-5 %; shorter budgets lose (200 000: 3.5 against 3.3 at 400 000, 100 000: 6.8 ms -- every cut walks the chunks
+  // behind a contact for nothing and pays three launches).  mesh x mesh: off -- its waves are busy 79 % of the kernel's time already
+  // and cfg4 went 2.97 -> 3.18 ms (profiles/r04_j)
+  uint32_t bvh_cut_ticks = 0, shape_cut_ticks = 350000;  // (600 000 until the queries' own phase became three kernels: profiles/r06_g section 5)
+  uint32_t shape_budget0_coop = 16;
+  // Mesh x mesh queries past their step budget are continued by k_bvh_coop (a wave per query, 64 stack entries per trip)
+  // instead of task levels (HFCL_BVH_COOP=0: the levels).  cfg4, budgets 160 / 192 / 256 / 320 / 384: 100k queries 3.82 / 3.53 /
+  // 3.28 / 3.39 / 3.57 ms (levels: 5.03); 1M queries, 256 / 512 / 640 / 1024: 15.1 / 10.95 / 10.86 / 11.9 ms (unsplit stream:
+  // 14.7); 250k: 5.03 ms (8.78); 10k: 2.63 (3.74) -- profiles/r03_k.  HFCL_BVH_BUDGET0_COOP overrides both.
+  bool bvh_coop = true;
+  uint32_t bvh_budget0_coop = 0;  // 0: 256 steps up to 500k queries, 640 beyond
+  // distance(): a mesh x mesh walk that has taken this many steps is continued by a wave (k_bvh_distance_coop); 0: never
+  uint32_t bvhd_budget = 64;      // HFCL_BVHD_BUDGET: steps a lane walks before its walk goes to k_bvh_distance_pool (cfg4d 100k queries, budgets 16 / 64 / 256: 34.4 / 33.2 / 34.1 ms, profiles/r04_c; with the wave-per-walk form of round 3, HFCL_BVHD_POOL=0, 1024 was best: 55.7 ms)
+  uint32_t bvhd_pool = 1;         // HFCL_BVHD_POOL: the walks past the budget are continued by k_bvh_distance_pool (0: k_bvh_distance_coop)
+  uint32_t bvhd_pool_leaf_min = 24, bvhd_pool_starve = 32, bvhd_pool_part_min = 48;  // HFCL_BVHD_LEAF_MIN / HFCL_BVHD_STARVE / HFCL_BVHD_PART_MIN
+  uint32_t pool_rerun = 1;          // HFCL_POOL_RERUN: pooled distance() walks whose result could hang on a rounding error are walked again in order (0: never -- the round-5 behaviour; 2: every walk, a test of the ordered mode)
+  uint32_t shape_dist_pool = 1;     // HFCL_SHAPE_DIST_POOL: mesh x solid distance() walks past the budget continue in k_bvh_shape_distance_pool (0: k_bvh_shape_distance_coop)
+  uint32_t shape_dist_leaf_min = 48, shape_dist_starve = 16;  // HFCL_SHAPE_DIST_LEAF_MIN / HFCL_SHAPE_DIST_STARVE (a GJK pass is worth waiting for: profiles/r04_i)
+  uint32_t shape_dist_budget = 64;  // HFCL_SHAPE_DIST_BUDGET: the same for mesh x solid (a GJK leaf counts 16 steps; k_bvh_shape_distance_coop)
+  size_t pipe_chunk = 0;                  // pairs per chunk (0 = automatic); HFCL_PIPE_CHUNK / hfcl_lib_set_host_chunk
+  int split = 0;  // 0 = automatic (auto_split), 1 = never, 2 = always (large batches without meshes)
+  // Queries per chunk of the cull (option scene_cull_chunk; 0: automatic -- at most 2^22 queries, 16384 workgroup counts for the one-workgroup scan)
+  size_t scene_cull_chunk = 0;
+  // Queries per chunk of a scene call (option scene_chunk; 0: automatic -- at most 2^21 queries, the call cut into equal chunks).  The chunks of a
+  // call run one after the other, and the solvers' kernels are chains of dependent steps that fill the chip only with a large batch: cfg5's
+  // 1.07 M queries in chunks of 262144 (the host pipeline's steady chunk) took 5.9 ms against 2.4 ms for the per-pair call on resident arrays,
+  // 9.0 ms of kernel time against 5.5 (profiles/r08_a_scene.md).  2^21 queries are 0.8 GB of workspace, allocated only by calls that large.
+  size_t scene_chunk = 0;
+  int cvx_w = 0;  // 0 = per kernel (auto_cvx_w); HFCL_CVX_W forces one width for all
+  bool closed_staged = true;  // HFCL_CLOSED_STAGED=0: A/B switch back to the direct-access k_closed<double>
+  bool bvh_filter = false;     // HFCL_BVH_FILTER=1: the fp32 filter form of k_bvh_collide (exact, measured slower: profiles/r03_b)
+  bool walk_order = true;            // option bvh_walk_order: the continuation launches draw the queries with the most stack entries first
+  bool shape_walk_sort = true;       // option shape_walk_sort = 0: the listed leaves evaluated in the order the walks listed them
+  bool shape_walk = true;            // option shape_walk = 0: the queries' own phase of mesh x solid collide() by k_bvh_collide's SOLID form (walk and leaves in one kernel)
+  uint32_t shape_walk_budget = 256;  // box tests a query's walk may take before k_bvh_shape_coop continues it
+  uint32_t shape_walk_min = 65536;   // batch size from which that phase is used (its eight launches are 0.2 ms of latency: 20k queries 1.63 against 1.42 ms,
+                                     // 50k 1.96 / 1.82, 100k 2.43 / 2.70, 200k 3.55 / 4.16)
+  size_t epa_resume_slots = 0, bvh_task_slots = 0;  // options epa_resume_slots / bvh_task_slots (0: sized by the batch)
+  bool bvh_force_wide = false, pipe_trace = false;   // options bvh_force_wide / pipe_trace
+  bool walk_early_coop = true;                               // HFCL_BVH_WALK_EARLY_COOP: the queries round 0 hands over are continued beside the later rounds
+  // Rounds of walk / leaves / resolve (option bvh_walk_rounds; 0: k_bvh_collide walks the queries, leaves inline).  Not set: chosen per
+  // batch -- ONE round of up to 16 listed leaves and 256 box tests (320 from 120k queries), then the continuation, up to 220k queries
+  // (100k: 1.86 against 1.94 ms with two rounds, 20k: 1.20 against 1.78, 50k: 1.46 against 1.74: a round is as long as its longest lane,
+  // and with the node records kept the lanes carry the walks far enough in one); TWO rounds (6 then 16 leaves; 320 / 640 then 256 box tests)
+  // with the first round's hand-overs continued beside the second above that (250k: 3.32 against 3.36-3.58 ms, 400k: 4.78 against 4.92,
+  // 1M: 9.2 against 10.0 with one round).  profiles/r06_a section 6
+  bool walk_auto = true;
+  uint32_t walk_rounds = 2;
+  uint32_t walk_k[WALK_ROUNDS] = {6, 16, 16, 16};           // option bvh_walk_k: leaves a walk lists per round (setting it switches the automatic choice off)
+  uint32_t walk_budget[WALK_ROUNDS] = {224, 256, 512, 512};  // option bvh_walk_budget: box tests per round from round 1 on before the walk goes to k_bvh_coop
+  uint32_t bvh_budget0 = HFCL_BVH_BUDGET0;  // HFCL_BVH_BUDGET0: step budget of the queries (level 0); bvh_budget: of the tasks
+  // No budget given by the environment: chosen per batch.  A batch that does not fill the chip's lanes more than ~1.5
+  // times is a walk with one query per lane whose waves run on with most lanes finished; there the queries are cut at
+  // 512 steps and their remainders spread over levels of small tasks (profiles/r02_w: 100k queries 6.4 -> 5.1 ms,
+  // 10k 4.7 -> 3.4 ms).  A larger batch keeps its lanes busy by refilling and loses with the split (1M: 68 -> 51 M q/s).
+  bool bvh_auto = true;
+  uint32_t bvh_budget = HFCL_BVH_BUDGET, bvh_levels = HFCL_BVH_LEVELS;  // HFCL_BVH_BUDGET / HFCL_BVH_LEVELS (1: unsplit)
+};
+
 struct hfcl_lib {
+  hfcl_options opt;
+  // split traversals: the main set, and the set of the mesh x mesh walks of a batch that run beside its mesh x solid walks (no cut tables)
+  SplitTables split_main, split_beside;
+  // collide() walks in rounds: mesh x mesh; mesh x solid (their own: the two kinds of walks of a mixed batch run beside each other; lists: [2 n] + the redo list [n])
+  WalkTables walk_mm, walk_ms;
   int device = 0;
   size_t n_shapes = 0;
   std::vector<hfcl_shape> h_shapes;
@@ -75,7 +192,6 @@ struct hfcl_lib {
   const uint32_t* d_graph_off = nullptr;
   const NbrEntry<float>* d_graph_ent32 = nullptr;
   const NbrEntry<double>* d_graph_ent64 = nullptr;
-  uint32_t climb_min = HFCL_CLIMB_MIN;  // HFCL_CLIMB_MIN: hulls of at least this many vertices with a graph hill-climb
   // workspace (grown on demand)
   size_t ws_capacity = 0;  // pairs
   size_t epa_capacity = 0;  // pairs the EPA queues / hand-over area are sized for (0: not allocated yet)
@@ -92,72 +208,20 @@ struct hfcl_lib {
   Stream mesh_st2, mesh_aux;
   bool ran_batch = false;  // h_counts holds the bucket counts of this library's last batch (once its copy has landed)
   Event ev_mesh_fork2, ev_mesh_join2;
-  DevBuf<BvhTask> d_bvh2_tasks;
-  DevBuf<void> d_bvh2_sums;
-  DevBuf<uint32_t> d_bvh2_susp;
-  DevBuf<uint32_t> d_bvh2_ctr;
-  size_t bvh2_split_n = 0, bvh2_split_cap = 0;
-  // 0 in line; 1 the mesh walks beside the solids' GJK kernels; 2 also mesh x mesh beside mesh x solid, the solids' EPA section beside both
-  // (1, 2: when the library's last batch held meshes and solids); 4: as 2 whatever the last batch held
-  uint32_t mesh_beside = 2;
-  bool mesh_prio = false;  // option mesh_prio = 1: the streams of the mesh x solid walks at the device's highest priority (read when they are created)
   // the solids' GJK kernels of a small batch run beside each other on these (option gjk_beside_max): one bucket's kernel does not fill the chip
   Stream gjk_st[3];
   Event gjk_fork, gjk_join[3];
-  uint32_t epa_direct_max = 4096;    // largest batch whose EPA seeds all go to the full-capacity tier, the fast tiers not launched (0: never)
-  uint32_t gjk_beside_max = 120000;  // largest batch whose GJK kernels fan out (0: never; below the size from which batches run as two halves)
   Stream walk_st[WALK_ROUNDS - 1];  // mesh x mesh collide(): the continuation of what round r of the walk hands over runs on walk_st[r]
   Event walk_fork[WALK_ROUNDS - 1], walk_join[WALK_ROUNDS - 1];
   Event ev_aux0, ev_aux1, ev_aux2, ev_aux3;  // fork / join of the EPA tail; of k_bvh_shape_finish's first half
   DevBuf<void> d_epa_ready;   // EpaReady<float>[ws_capacity]: the staged convex x convex fast tier (k_epa_prepare / k_epa_loop / k_epa_records)
   DevBuf<void> d_epa_ready_g; // EpaReadyG<T>[ws_capacity]: the staged fast tier of the general queues (both precisions)
-  bool epa_general_staged = false;       // HFCL_EPA_GENERAL_STAGED=1: prepare / loop / records for the general queues too.  Byte-identical
-                                         // records; measured slower in wall-clock on cfg2 (0.416 -> 0.479 ms) and cfg5 unsplit (4.77 -> 5.30 ms
-                                         // per 1M mixed pairs), faster only on cfg5 split (5.34 -> 5.13): profiles/r05_e_general_staged.md
-  size_t epa_general_staged_min = 32768; // HFCL_EPA_GENERAL_STAGED_MIN
-  bool records_aside = true;     // HFCL_EPA_RECORDS_ASIDE=0: k_epa_records on the batch's stream
-  bool epa64_two_streams = true; // HFCL_EPA64_TWO_STREAMS=0: the two fp64 fast-tier kernels one after the other
-  bool epa_cc_staged = true;     // HFCL_EPA_CC_STAGED=0: the one-kernel form (k_epa_stream<.., CC>)
-  size_t epa_cc_staged_min = 32768;  // ... which batches below this many pairs keep (two launches less); HFCL_EPA_CC_STAGED_MIN
   DevBuf<void> d_epa_resume;
   DevBuf<void> d_epa_v0;
   size_t resume_cap = 0;
-  bool shape_finish_tiers = true;  // HFCL_SHAPE_FINISH_TIERS=0: k_bvh_shape_finish in one launch at full capacity
-  bool shape_finish_aside = true;  // HFCL_SHAPE_FINISH_ASIDE=0: all of k_bvh_shape_finish behind the last launch of k_bvh_shape_coop
   DevBuf<void> d_shape_defer;  // ShapeDeferItem<double>[], two words more each: EPA queue of the one-query-per-lane mesh x solid form
   DevBuf<void> d_shape_oq;     // ObbQuery<double>[ws_capacity]: the solids' OBBs against the mesh poses, by pair
-  bool bvh_shape_lane = true;     // HFCL_BVH_SHAPE_LANE=0: the group kernels for every request (A/B switch)
-  // step budgets of the one-query-per-lane mesh x solid walk (a unit suspends into tasks when it has taken that many BV-test
-  // equivalents; a GJK leaf counts shape_leaf_cost): the queries themselves / their tasks.  The steps per query have a heavy
-  // tail whatever the batch size (median 1, mean ~60, maximum > 3000 steps with > 1000 leaves), so the walk is always split.
-  uint32_t shape_budget0 = 128, shape_budget = 96, shape_leaf_cost = 32, shape_levels = BVH_MAX_LEVELS;
-  // Suspended queries are continued by k_bvh_shape_coop (a wave per query, 64 stack entries per trip) instead of task levels
-  // (HFCL_SHAPE_COOP=0: the levels); the queries' own budget is then 16 steps (100k queries per kind, budgets 8 / 16 / 32 / 128:
-  // sphere 2.0 / 2.0 / 2.4 / 2.6 ms, ellipsoid 7.5 / 8.1 / 8.4 / 8.3, box 1.4 / 1.3 / 1.2 / 1.1; profiles/r03_i)
-  bool shape_coop = true;
-  // ... and a walk such a kernel has worked on for this many clock ticks is cut into chunk tasks for its next launch (BvhSplit::cut_ticks;
-  // HFCL_BVH_CUT_TICKS / HFCL_SHAPE_CUT_TICKS; 0: never).  The records equal the uncut walks' in every field wherever the cuts fall
-  // (tools/cut_check.py).  mesh x solid, 600 000 ticks (~2.3x the mean walk): 100k mixed queries 4.4 -> 3.7 ms on one box, the single
-  // kinds within +-5 %; shorter budgets lose (200 000: 3.5 against 3.3 at 400 000, 100 000: 6.8 ms -- every cut walks the chunks
-  // behind a contact for nothing and pays three launches).  mesh x mesh: off -- its waves are busy 79 % of the kernel's time already
-  // and cfg4 went 2.97 -> 3.18 ms (profiles/r04_j)
-  uint32_t bvh_cut_ticks = 0, shape_cut_ticks = 350000;  // (600 000 until the queries' own phase became three kernels: profiles/r06_g section 5)
-  uint32_t shape_budget0_coop = 16;
-  // Mesh x mesh queries past their step budget are continued by k_bvh_coop (a wave per query, 64 stack entries per trip)
-  // instead of task levels (HFCL_BVH_COOP=0: the levels).  cfg4, budgets 160 / 192 / 256 / 320 / 384: 100k queries 3.82 / 3.53 /
-  // 3.28 / 3.39 / 3.57 ms (levels: 5.03); 1M queries, 256 / 512 / 640 / 1024: 15.1 / 10.95 / 10.86 / 11.9 ms (unsplit stream:
-  // 14.7); 250k: 5.03 ms (8.78); 10k: 2.63 (3.74) -- profiles/r03_k.  HFCL_BVH_BUDGET0_COOP overrides both.
-  bool bvh_coop = true;
-  uint32_t bvh_budget0_coop = 0;  // 0: 256 steps up to 500k queries, 640 beyond
-  // distance(): a mesh x mesh walk that has taken this many steps is continued by a wave (k_bvh_distance_coop); 0: never
-  uint32_t bvhd_budget = 64;      // HFCL_BVHD_BUDGET: steps a lane walks before its walk goes to k_bvh_distance_pool (cfg4d 100k queries, budgets 16 / 64 / 256: 34.4 / 33.2 / 34.1 ms, profiles/r04_c; with the wave-per-walk form of round 3, HFCL_BVHD_POOL=0, 1024 was best: 55.7 ms)
-  uint32_t bvhd_pool = 1;         // HFCL_BVHD_POOL: the walks past the budget are continued by k_bvh_distance_pool (0: k_bvh_distance_coop)
-  uint32_t bvhd_pool_leaf_min = 24, bvhd_pool_starve = 32, bvhd_pool_part_min = 48;  // HFCL_BVHD_LEAF_MIN / HFCL_BVHD_STARVE / HFCL_BVHD_PART_MIN
   DevBuf<void> d_dist_susp;    // DistSusp<double>[ws_capacity]
-  uint32_t pool_rerun = 1;          // HFCL_POOL_RERUN: pooled distance() walks whose result could hang on a rounding error are walked again in order (0: never -- the round-5 behaviour; 2: every walk, a test of the ordered mode)
-  uint32_t shape_dist_pool = 1;     // HFCL_SHAPE_DIST_POOL: mesh x solid distance() walks past the budget continue in k_bvh_shape_distance_pool (0: k_bvh_shape_distance_coop)
-  uint32_t shape_dist_leaf_min = 48, shape_dist_starve = 16;  // HFCL_SHAPE_DIST_LEAF_MIN / HFCL_SHAPE_DIST_STARVE (a GJK pass is worth waiting for: profiles/r04_i)
-  uint32_t shape_dist_budget = 64;  // HFCL_SHAPE_DIST_BUDGET: the same for mesh x solid (a GJK leaf counts 16 steps; k_bvh_shape_distance_coop)
   DevBuf<void> d_shape_dist_susp;
   // host-call staging: PIPE_SLOTS device buffer sets of `st_capacity` pairs each (a chunk of a host batch), three streams
   // (H2D | kernels | D2H) and per-slot events / pinned counter blocks (host_batch)
@@ -185,14 +249,12 @@ struct hfcl_lib {
   uint32_t acc_counts[N_COUNTERS] = {0};  // host batches: bucket populations summed over the chunks
   bool last_host = false;                 // the last call was a host batch: acc_counts are its populations
   bool in_host_batch = false;
-  size_t pipe_chunk = 0;                  // pairs per chunk (0 = automatic); HFCL_PIPE_CHUNK / hfcl_lib_set_host_chunk
   uint32_t* counts_dst = nullptr;         // where run_batch_one sends the bucket populations (default: h_counts)
   // instrumentation
   std::vector<KernelTime> timers;
   // A batch can run as two halves on two streams (hfcl_lib_set_split): the second half goes to `helper`, a shallow
   // clone (same device shape tables, own workspace / counters / timers) on the internal stream `side`, whose kernels
   // fill the drain phases of the first half's GJK / EPA launches (profiles/r01_k_two_stream_overlap.txt).
-  int split = 0;  // 0 = automatic (auto_split), 1 = never, 2 = always (large batches without meshes)
   hfcl_lib* helper = nullptr;
   bool last_split = false;  // the last batch ran split: counters / timers of the helper belong to it
   Stream side;
@@ -231,25 +293,16 @@ struct hfcl_lib {
     DevBuf<uint64_t> d_ids;      // host forms: the surviving queries
     DevBuf<uint64_t> d_conf_begin;
   } scene;
-  // Queries per chunk of the cull (option scene_cull_chunk; 0: automatic -- at most 2^22 queries, 16384 workgroup counts for the one-workgroup scan)
-  size_t scene_cull_chunk = 0;
   // local AABB of every library shape (hfcl_cull.hpp: shape_local_box; BVH models: the box of their vertices), 6 doubles each, rebuilt when
   // shapes or meshes were registered since (hfcl_lib_set_shapes, hfcl_lib_add_bvh)
   DevBuf<double> d_local_boxes;
   bool local_boxes_dirty = true;
   std::vector<uint32_t> h_mesh_nverts;  // vertices of each registered BVH model
-  // Queries per chunk of a scene call (option scene_chunk; 0: automatic -- at most 2^21 queries, the call cut into equal chunks).  The chunks of a
-  // call run one after the other, and the solvers' kernels are chains of dependent steps that fill the chip only with a large batch: cfg5's
-  // 1.07 M queries in chunks of 262144 (the host pipeline's steady chunk) took 5.9 ms against 2.4 ms for the per-pair call on resident arrays,
-  // 9.0 ms of kernel time against 5.5 (profiles/r08_a_scene.md).  2^21 queries are 0.8 GB of workspace, allocated only by calls that large.
-  size_t scene_chunk = 0;
   uint64_t shapes_epoch = 0;        // hfcl_lib_set_shapes counts: a scene made before the last one is stale
   uint32_t possible_buckets = ~0u;   // bit b: some pair of this library's shape kinds classifies into bucket b
   bool has_flats = true;             // some shape is a Plane / Halfspace: their "very rough" volumes are no lower bounds, so what a mesh walk
                                      // against them reports depends on the ORDER of its visits -- the ordered continuation, not the pool
   bool has_curved = true;            // some shape is an Ellipsoid / Cone / Cylinder: the curved class of the fp64 EPA tiers can occur
-  int cvx_w = 0;  // 0 = per kernel (auto_cvx_w); HFCL_CVX_W forces one width for all
-  bool closed_staged = true;  // HFCL_CLOSED_STAGED=0: A/B switch back to the direct-access k_closed<double>
   int n_cus = 256;
   std::string dominant;
   // bucket populations of the last call; PINNED host memory so that the device-to-host copy at the end of a batch is
@@ -264,7 +317,6 @@ struct hfcl_lib {
   DevBuf<DNode<double>> d_nodes64;
   DevBuf<DNode<float>> d_nodes32;
   DevBuf<DNodeF> d_fnodes;  // 64-byte records of the fp32 separating-axis filter (fp64 collide)
-  bool bvh_filter = false;     // HFCL_BVH_FILTER=1: the fp32 filter form of k_bvh_collide (exact, measured slower: profiles/r03_b)
   DevBuf<DRss<double>> d_rss64;
   DevBuf<DRss<float>> d_rss32;
   DevBuf<DNodeD<double>> d_dnodes64;  // the distance() walk's packed node records
@@ -277,56 +329,6 @@ struct hfcl_lib {
   uint32_t bvh_max_depth = 0;
   size_t bvh_max_nodes = 0;
   DevBuf<void> d_bvh_slab;
-  // split mesh x mesh traversals (BvhSplit): task table, unit summaries, suspended-query list, counters
-  DevBuf<BvhTask> d_bvh_tasks;
-  DevBuf<uint32_t> d_bvh_cut_words;  // BvhSplit::cut_words / cut_vals (bvh_split_cap entries each)
-  DevBuf<double> d_bvh_cut_vals;
-  DevBuf<void> d_bvh_sums;
-  DevBuf<uint32_t> d_bvh_susp;
-  DevBuf<uint32_t> d_bvh_ctr;
-  // mesh x mesh collide() in walk / leaves / resolve rounds (hfcl_dev.hpp: WalkRec): records, item list, leaf results, the two query lists, counters
-  DevBuf<void> d_walk_recs;
-  DevBuf<uint32_t> d_walk_items;
-  DevBuf<void> d_walk_res;
-  DevBuf<uint32_t> d_walk_lists;
-  DevBuf<uint32_t> d_walk_order;  // BvhSplit::order (one entry per suspended slot)
-  bool walk_order = true;            // option bvh_walk_order: the continuation launches draw the queries with the most stack entries first
-  DevBuf<uint32_t> d_walk_ctr;
-  size_t walk_n = 0;
-  // ... of the mesh x solid walks (their own: the two kinds of walks of a mixed batch run beside each other); lists: [2 n] + the redo list [n]
-  DevBuf<void> d_swalk_recs;
-  DevBuf<uint32_t> d_swalk_items;
-  DevBuf<void> d_swalk_res;
-  DevBuf<uint32_t> d_swalk_lists;
-  DevBuf<uint32_t> d_swalk_ctr;   // 8 words per round, then the 64 words of WalkArgs::hist
-  DevBuf<uint32_t> d_swalk_perm;  // WalkArgs::perm
-  size_t swalk_n = 0;
-  bool shape_walk_sort = true;       // option shape_walk_sort = 0: the listed leaves evaluated in the order the walks listed them
-  bool shape_walk = true;            // option shape_walk = 0: the queries' own phase of mesh x solid collide() by k_bvh_collide's SOLID form (walk and leaves in one kernel)
-  uint32_t shape_walk_budget = 256;  // box tests a query's walk may take before k_bvh_shape_coop continues it
-  uint32_t shape_walk_min = 65536;   // batch size from which that phase is used (its eight launches are 0.2 ms of latency: 20k queries 1.63 against 1.42 ms,
-                                     // 50k 1.96 / 1.82, 100k 2.43 / 2.70, 200k 3.55 / 4.16)
-  size_t epa_resume_slots = 0, bvh_task_slots = 0;  // options epa_resume_slots / bvh_task_slots (0: sized by the batch)
-  bool bvh_force_wide = false, pipe_trace = false;   // options bvh_force_wide / pipe_trace
-  bool walk_early_coop = true;                               // HFCL_BVH_WALK_EARLY_COOP: the queries round 0 hands over are continued beside the later rounds
-  // Rounds of walk / leaves / resolve (option bvh_walk_rounds; 0: k_bvh_collide walks the queries, leaves inline).  Not set: chosen per
-  // batch -- ONE round of up to 16 listed leaves and 256 box tests (320 from 120k queries), then the continuation, up to 220k queries
-  // (100k: 1.86 against 1.94 ms with two rounds, 20k: 1.20 against 1.78, 50k: 1.46 against 1.74: a round is as long as its longest lane,
-  // and with the node records kept the lanes carry the walks far enough in one); TWO rounds (6 then 16 leaves; 320 / 640 then 256 box tests)
-  // with the first round's hand-overs continued beside the second above that (250k: 3.32 against 3.36-3.58 ms, 400k: 4.78 against 4.92,
-  // 1M: 9.2 against 10.0 with one round).  profiles/r06_a section 6
-  bool walk_auto = true;
-  uint32_t walk_rounds = 2;
-  uint32_t walk_k[WALK_ROUNDS] = {6, 16, 16, 16};           // option bvh_walk_k: leaves a walk lists per round (setting it switches the automatic choice off)
-  uint32_t walk_budget[WALK_ROUNDS] = {224, 256, 512, 512};  // option bvh_walk_budget: box tests per round from round 1 on before the walk goes to k_bvh_coop
-  size_t bvh_split_n = 0, bvh_split_cap = 0;
-  uint32_t bvh_budget0 = HFCL_BVH_BUDGET0;  // HFCL_BVH_BUDGET0: step budget of the queries (level 0); bvh_budget: of the tasks
-  // No budget given by the environment: chosen per batch.  A batch that does not fill the chip's lanes more than ~1.5
-  // times is a walk with one query per lane whose waves run on with most lanes finished; there the queries are cut at
-  // 512 steps and their remainders spread over levels of small tasks (profiles/r02_w: 100k queries 6.4 -> 5.1 ms,
-  // 10k 4.7 -> 3.4 ms).  A larger batch keeps its lanes busy by refilling and loses with the split (1M: 68 -> 51 M q/s).
-  bool bvh_auto = true;
-  uint32_t bvh_budget = HFCL_BVH_BUDGET, bvh_levels = HFCL_BVH_LEVELS;  // HFCL_BVH_BUDGET / HFCL_BVH_LEVELS (1: unsplit)
   // contact list of the last hfcl_collide_batch_contacts call
   DevBuf<hfcl_contact> d_contacts;
   DevBuf<uint32_t> d_contacts_count;
@@ -334,13 +336,23 @@ struct hfcl_lib {
   double break_distance = 1e-3;
 };
 
-// hfcl_host.hip, for the other two units (internal to the shared library: hidden)
+// bucket population i of a batch's counter block: a bucket = its bottom + its curved part; the EPA queue = the general + the second queue
+inline uint32_t one_count(const uint32_t* c, int i) {
+  return c[i] + (i < B_COUNT ? c[B_CURVED0 + i] : 0u) + (i == B_COUNT ? c[B_COUNT + 3] : 0u);
+}
+
+// what the units call of each other (internal to the shared library: hidden)
 #pragma GCC visibility push(hidden)
+// hfcl_host_batch.hip
+template <typename T> int run_batch(hfcl_lib* lib, const uint32_t* d_s1, const uint32_t* d_s2, IO<T> io, size_t n, QParams<T> q, hipStream_t st);
+void share_tables(hfcl_lib* h, const hfcl_lib* lib);  // the view of `h` onto the device tables `lib` owns (h == lib: the library's own)
 bool batch_splits(const hfcl_lib* lib, size_t n);
 int ensure_helper(hfcl_lib* lib);
+// hfcl_host.hip
 extern "C" int host_batch_checks(hfcl_lib* lib, const hfcl_collision_request* creq, const hfcl_distance_request* dreq);  // (defined among hfcl_host.hip's extern "C" entry points)
 template <typename T> int setup_collide(const hfcl_collision_request* req, QParams<T>& q, bool& skip_all);
 template <typename T> int setup_distance(const hfcl_distance_request* req, QParams<T>& q);
 KernelTime* timer_slot(hfcl_lib* lib, size_t i, const char* name);
 int upload_graph(hfcl_lib* lib);
+int upload_bvh(hfcl_lib* lib);
 #pragma GCC visibility pop

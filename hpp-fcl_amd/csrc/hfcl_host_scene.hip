@@ -102,7 +102,7 @@ static int scene_validate(const char* who, const hfcl_scene* s, const void* tabl
 }
 // queries per chunk of a call of `total` queries: the option as given, or equal chunks of at most 2^21
 static size_t scene_chunk_size(const hfcl_lib* lib, size_t total) {
-  if (lib->scene_chunk) return std::min<size_t>(std::min<size_t>(lib->scene_chunk, total), 0xFFFFFFF0ull);
+  if (lib->opt.scene_chunk) return std::min<size_t>(std::min<size_t>(lib->opt.scene_chunk, total), 0xFFFFFFF0ull);
   constexpr size_t AUTO = size_t(1) << 21;
   const size_t n_chunks = (total + AUTO - 1) / AUTO;
   return (total + n_chunks - 1) / n_chunks;
@@ -271,7 +271,7 @@ static int cull_check_inflate(const char* who, double inflate) {
   return HFCL_OK;
 }
 static size_t cull_chunk_size(const hfcl_lib* lib, size_t total) {
-  if (lib->scene_cull_chunk) return std::min<size_t>(lib->scene_cull_chunk, total);
+  if (lib->opt.scene_cull_chunk) return std::min<size_t>(lib->opt.scene_cull_chunk, total);
   constexpr size_t AUTO = size_t(1) << 22;
   const size_t n_chunks = (total + AUTO - 1) / AUTO;
   return (total + n_chunks - 1) / n_chunks;

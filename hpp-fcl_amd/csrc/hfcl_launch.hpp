@@ -29,7 +29,7 @@
 //                                     keep walking after a contact, models deeper than the lanes' stacks
 //                    k_triangle<T>    top-level TriangleP pairs
 //
-// Every launcher is asynchronous on `st` and does no error checking of its own (run_batch_one checks hipGetLastError once).
+// Every launcher is asynchronous on `st` and does no error checking of its own (hfcl_host_batch.hip: run_batch_one checks hipGetLastError once, in its last stage).
 #pragma once
 #include "hfcl_dev.hpp"
 

@@ -53,7 +53,7 @@ def test_options_are_an_api_not_an_environment(pkg):
     n_getenv = 0
     csrc = os.path.join(ROOT, "hpp-fcl_amd", "csrc")
     units = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".cpp")))
-    assert {"hfcl_host.hip", "hfcl_host_patch.hip", "hfcl_host_scene.hip", "hfcl_multi.hip"} <= set(units)
+    assert {"hfcl_host.hip", "hfcl_host_batch.hip", "hfcl_host_patch.hip", "hfcl_host_scene.hip", "hfcl_multi.hip"} <= set(units)
     for f in units:
         txt = open(os.path.join(csrc, f)).read()
         txt = re.sub(r"//[^\n]*", "", txt)
