@@ -674,10 +674,11 @@ def collide_pairs(pairs, request):
     return out
 
 
-def _scene_run(kind, objects, pair_indices, request, transforms, broadphase=False, inflate=0.0):
+def _scene_run(kind, objects, pair_indices, request, transforms, broadphase=False, inflate=0.0, nearest_bound=None):
     """The pair list `pair_indices` ((n_pairs, 2) indices into `objects`) for every configuration: ONE scene call.  broadphase: the
     list is culled per configuration on the device first (boxes grown by `inflate`); rec / g then hold the surviving queries only and
-    the last two items are their ids q = c * n_pairs + p and conf_begin (None without broadphase)."""
+    the last two items are their ids q = c * n_pairs + p and conf_begin (None without broadphase).  nearest_bound (distance only): the
+    pruned minimum (engine.Scene.nearest) with that upper bound; rec then holds one min record per configuration and g is None."""
     ctx = _context()
     geoms = [o.collisionGeometry() for o in objects]
     ids = np.array([ctx.add(g) for g in geoms], dtype=np.uint32)
@@ -699,7 +700,10 @@ def _scene_run(kind, objects, pair_indices, request, transforms, broadphase=Fals
     sc = lib.scene(ids, pr)
     try:
         ids = conf_begin = None
-        if broadphase:
+        if nearest_bound is not None:
+            summ, rec, _ = sc.nearest(table, request._abi(), float(nearest_bound))
+            g = None
+        elif broadphase:
             fn = sc.distance_culled if kind == "distance" else sc.collide_culled
             rec, ids, conf_begin, summ, g = fn(table, float(inflate), request._abi(), records=True, summary=True, want_guess=True)
         else:
@@ -751,12 +755,29 @@ def collide_scene(objects, pair_indices, request, transforms=None, broadphase=Fa
     return (out[0] if transforms is None and out else out), summ
 
 
-def distance_scene(objects, pair_indices, request, transforms=None, broadphase=False, inflate=0.0):
+def distance_scene(objects, pair_indices, request, transforms=None, broadphase=False, inflate=0.0, nearest=False, upper_bound=float("inf")):
     """distance() on the listed pairs of `objects`: (min_distance array (n_conf, n_pairs), records, summaries); the
     summaries' min_distance is DistanceCallBackDefault's answer per configuration.
     broadphase=True: only the pairs whose world AABBs, each grown by `inflate`, overlap are evaluated (inflate = D / 2 keeps every pair
     whose boxes are within D along each axis: a box-shaped filter, not the manager's traversal with its shrinking bound).  Returns
-    (distances, pair indices, summaries): per configuration the array of the surviving pairs' distances and the array of their p."""
+    (distances, pair indices, summaries): per configuration the array of the surviving pairs' distances and the array of their p.
+    nearest=True: the clearance alone -- one DistanceResult per configuration, what DistanceCallBackDefault leaves behind after
+    DynamicAABBTreeCollisionManager::distance: the closest listed pair's min_distance, o1 / o2, nearest points, normal, b1 / b2.  The pairs
+    are pruned on the device by a bound from their world boxes (engine.Scene.nearest); a configuration whose closest pair is farther than
+    `upper_bound` keeps a default DistanceResult."""
+    if nearest:
+        geoms, pr, n_conf, rec, summ, _, _, _ = _scene_run("distance", objects, pair_indices, request, transforms, nearest_bound=upper_bound)
+        out = []
+        for c in range(n_conf):
+            res = DistanceResult()
+            p, r = int(summ["min_pair"][c]), rec[c]
+            if p != abi.SCENE_NONE and float(summ["min_distance"][c]) <= upper_bound:
+                res.min_distance, res.o1, res.o2 = float(r["distance"]), geoms[pr[p][0]], geoms[pr[p][1]]
+                res.b1, res.b2 = int(r["b1"]), int(r["b2"])
+                res.normal = np.array(r["normal"])
+                res.nearest_points = [np.array(r["p1"]), np.array(r["p2"])]
+            out.append(res)
+        return out
     geoms, pr, n_conf, rec, summ, g, ids, conf_begin = _scene_run("distance", objects, pair_indices, request, transforms, broadphase, inflate)
     if broadphase:
         cb = conf_begin.astype(np.int64)

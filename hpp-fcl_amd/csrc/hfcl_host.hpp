@@ -292,6 +292,14 @@ struct hfcl_lib {
     DevBuf<uint64_t> d_running;  // [0]: the running count of a cull, [1]: n_listed of the host forms
     DevBuf<uint64_t> d_ids;      // host forms: the surviving queries
     DevBuf<uint64_t> d_conf_begin;
+    // the pruned minimum distance (hfcl_scene_nearest*): the second pass's list, the seeds and thresholds by configuration, both passes'
+    // records when min records are asked for, and the host forms' min records
+    DevBuf<uint64_t> d_ids2, d_conf_begin2;
+    DevBuf<uint32_t> d_seed;
+    DevBuf<void> d_seed_partials;
+    DevBuf<double> d_thr;
+    DevBuf<void> d_nrec[2];
+    DevBuf<void> d_minrec;
   } scene;
   // local AABB of every library shape (hfcl_cull.hpp: shape_local_box; BVH models: the box of their vertices), 6 doubles each, rebuilt when
   // shapes or meshes were registered since (hfcl_lib_set_shapes, hfcl_lib_add_bvh)

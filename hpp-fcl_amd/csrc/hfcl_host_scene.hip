@@ -1,6 +1,8 @@
 // hfcl_host_scene.hip -- host side of the scene queries (hfcl_scene_*) and of the cull of their pair lists (the kernels: hfcl_k_scene.hip,
 // hfcl_k_cull.hip).  The library object and what this unit calls of hfcl_host.hip: hfcl_host.hpp.
 #include "hfcl_host.hpp"
+#include "hfcl_nearest.hpp"
+#include "../../include/hppfcl_amd_nearest.h"
 
 // =======================================================================================
 // Scene queries (include/hppfcl_amd.h: hfcl_scene_*): an object -> shape table and a pair list resident on the library's device; a call
@@ -296,6 +298,22 @@ static int scene_boxes_device(const char* who, hfcl_scene* s, const void* d_tabl
   return HFCL_OK;
 }
 
+// ballots, workgroup counts and offsets of a chunk of `chunk` queries, the running count
+static int cull_chunk_buffers(hfcl_lib* lib, size_t chunk) {
+  hfcl_lib::SceneWs& w = lib->scene;
+  const size_t n_blocks = (chunk + CULL_BLOCK - 1) / CULL_BLOCK;
+  HIP_TRY(w.d_words.grow(n_blocks * CULL_WAVES));
+  if (n_blocks > w.blocks_cap) {
+    reset_all(w.d_block_counts, w.d_block_offsets);
+    w.blocks_cap = 0;
+    HIP_TRY(w.d_block_counts.grow(n_blocks));
+    HIP_TRY(w.d_block_offsets.grow(n_blocks));
+    w.blocks_cap = n_blocks;
+  }
+  HIP_TRY(w.d_running.grow(2));
+  return HFCL_OK;
+}
+
 // The cull of the whole flat range on st: the list (ids below `capacity`), conf_begin, the count.  Nothing is read back.
 template <typename T>
 static int cull_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, double inflate, uint64_t* d_ids, size_t capacity,
@@ -321,17 +339,9 @@ static int cull_device(const char* who, hfcl_scene* s, const void* d_table, size
   hfcl_lib::SceneWs& w = lib->scene;
   const size_t chunk = cull_chunk_size(lib, total);
   const size_t conf_per_chunk = std::min<size_t>(n_conf, chunk / s->n_pairs + 2);
-  const size_t n_blocks = (chunk + CULL_BLOCK - 1) / CULL_BLOCK;
   HIP_TRY(w.d_boxes.grow(conf_per_chunk * s->n_objects * 6));
-  HIP_TRY(w.d_words.grow(n_blocks * CULL_WAVES));
-  if (n_blocks > w.blocks_cap) {
-    reset_all(w.d_block_counts, w.d_block_offsets);
-    w.blocks_cap = 0;
-    HIP_TRY(w.d_block_counts.grow(n_blocks));
-    HIP_TRY(w.d_block_offsets.grow(n_blocks));
-    w.blocks_cap = n_blocks;
-  }
-  HIP_TRY(w.d_running.grow(2));
+  rc = cull_chunk_buffers(lib, chunk);
+  if (rc) return rc;
   constexpr bool f32 = std::is_same<T, float>::value;
   CullArgs a;
   a.pairs = s->d_pairs;
@@ -512,12 +522,72 @@ static int scene_listed_chunk_run(hfcl_scene* s, const void* d_table, size_t n_c
   return HFCL_OK;
 }
 
+// The bucket populations of a host form whose chunks run through scene_listed_device (hfcl_scene_nearest*): a pinned slot per chunk, as
+// scene_host keeps them -- chunk k uses slot k % COUNT_SLOTS once chunk k - COUNT_SLOTS has been added up.
+struct SceneCountSlots {
+  static constexpr int CS = hfcl_lib::SceneWs::COUNT_SLOTS;
+  static constexpr size_t SLOT_WORDS = 2 * size_t(N_COUNTERS);
+  hfcl_lib* lib;
+  bool slot_split[CS] = {};
+  size_t k = 0;  // chunks so far
+  explicit SceneCountSlots(hfcl_lib* l) : lib(l) {}
+  int begin() {
+    hfcl_lib::SceneWs& w = lib->scene;
+    if (!w.h_counts) HIP_TRY(w.h_counts.alloc(CS * SLOT_WORDS));
+    for (Event& e : w.ev_counts)
+      if (!e) HIP_TRY(e.create());
+    memset(w.h_counts, 0, CS * SLOT_WORDS * sizeof(uint32_t));
+    memset(lib->acc_counts, 0, sizeof(lib->acc_counts));
+    lib->in_host_batch = true;
+    return HFCL_OK;
+  }
+  void harvest(int slot) {
+    uint32_t* c = lib->scene.h_counts + size_t(slot) * SLOT_WORDS;
+    for (int i = 0; i < N_COUNTERS; ++i) lib->acc_counts[i] += c[i] + (slot_split[slot] ? c[N_COUNTERS + i] : 0u);
+    memset(c, 0, SLOT_WORDS * sizeof(uint32_t));
+  }
+  int before_chunk(size_t m) {
+    hfcl_lib::SceneWs& w = lib->scene;
+    const int slot = int(k % CS);
+    if (k >= size_t(CS)) {
+      HIP_TRY(hipEventSynchronize(w.ev_counts[slot]));
+      harvest(slot);
+    }
+    lib->counts_dst = w.h_counts + size_t(slot) * SLOT_WORDS;
+    if (batch_splits(lib, m)) {
+      const int rc = ensure_helper(lib);
+      if (rc) return rc;
+      lib->helper->counts_dst = lib->counts_dst + N_COUNTERS;
+    }
+    return HFCL_OK;
+  }
+  int after_chunk(hipStream_t st) {
+    const int slot = int(k % CS);
+    slot_split[slot] = lib->last_split;
+    HIP_TRY(hipEventRecord(lib->scene.ev_counts[slot], st));
+    ++k;
+    return HFCL_OK;
+  }
+  // the call's streams have been waited for (ok: and nothing failed -- the populations are complete)
+  void end(bool ok) {
+    for (int slot = 0; ok && slot < CS && size_t(slot) < k; ++slot) harvest(slot);
+    lib->in_host_batch = false;
+    lib->counts_dst = nullptr;
+    if (lib->helper) lib->helper->counts_dst = nullptr;
+  }
+};
+// what hfcl_scene_nearest* adds to a run on a list
+struct SceneListedExtra {
+  bool merge;               // the summaries are not re-initialised: the list's records are merged into what is stored
+  SceneCountSlots* counts;  // nullptr, or the host form's slots
+};
+
 // The device form on a list.  The ids are not checked: ascending, below n_conf * n_pairs, conf_begin theirs -- as hfcl_scene_cull_device leaves them.
 template <typename T>
 static int scene_listed_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const uint64_t* d_ids, size_t n_listed,
                                const uint64_t* d_conf_begin, const hfcl_collision_request* creq, const hfcl_distance_request* dreq,
                                typename SceneTypes<T>::R* d_out, hfcl_scene_summary* d_summary, const hfcl_guess* d_gin, hfcl_guess* d_gout,
-                               hipStream_t st) {
+                               hipStream_t st, const SceneListedExtra* extra = nullptr) {
   size_t total;
   int rc = scene_validate<T>(who, s, d_table, n_conf, creq, dreq, d_out, d_summary, total);
   if (rc) return rc;
@@ -535,7 +605,7 @@ static int scene_listed_device(const char* who, hfcl_scene* s, const void* d_tab
   }
   hfcl_lib* lib = s->lib;
   HIP_TRY(hipSetDevice(lib->device));
-  if (d_summary) launch_scene_summary_init(st, d_summary, n_conf, lib->n_cus * 16);
+  if (d_summary && !(extra && extra->merge)) launch_scene_summary_init(st, d_summary, n_conf, lib->n_cus * 16);
   if (!n_listed) {
     HIP_TRY(hipGetLastError());
     return HFCL_OK;
@@ -546,8 +616,12 @@ static int scene_listed_device(const char* who, hfcl_scene* s, const void* d_tab
   for (size_t k0 = 0; k0 < n_listed; k0 += chunk) {
     const size_t m = std::min(chunk, n_listed - k0);
     auto* rec = d_out ? d_out + k0 : static_cast<typename SceneTypes<T>::R*>(lib->scene.d_rec[0].get());
-    rc = scene_listed_chunk_run<T>(s, d_table, n_conf, d_ids, d_conf_begin, k0, m, creq, dreq, rec, d_summary, d_gin ? d_gin + k0 : nullptr,
-                                   d_gout ? d_gout + k0 : nullptr, st);
+    SceneCountSlots* counts = extra ? extra->counts : nullptr;
+    rc = counts ? counts->before_chunk(m) : HFCL_OK;
+    if (!rc)
+      rc = scene_listed_chunk_run<T>(s, d_table, n_conf, d_ids, d_conf_begin, k0, m, creq, dreq, rec, d_summary, d_gin ? d_gin + k0 : nullptr,
+                                     d_gout ? d_gout + k0 : nullptr, st);
+    if (!rc && counts) rc = counts->after_chunk(st);
     if (rc) {
       scene_join_side(lib, st);
       return rc;
@@ -713,6 +787,209 @@ static int scene_host(const char* who, hfcl_scene* s, const void* table, size_t 
   if (lib->helper) lib->helper->counts_dst = nullptr;
   lib->last_host = true;
   return host_batch_checks(lib, creq, dreq);
+}
+
+// ---------------------------------------------------------------------------------------
+// The per-configuration minimum distance with box-bound pruning (include/hppfcl_amd_nearest.h: hfcl_scene_nearest*).  hfcl_k_nearest.hip has
+// the kernels, hfcl_nearest.hpp the arithmetic.  The boxes of the whole table once; the seeds; the list of pass 1 (mark / scan / emit), its
+// count read back, its narrow phase through scene_listed_device; the thresholds; the same for pass 2, merged into the same summaries; the
+// min records gathered.  Two read-backs of 8 bytes.
+// ---------------------------------------------------------------------------------------
+template <typename T>
+static int nearest_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, const hfcl_distance_request* req, double upper,
+                            const void* summary, size_t& total) {
+  total = 0;
+  if (upper != upper) {
+    set_error(std::string(who) + ": upper_bound is NaN");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (s && !req) {
+    set_error("null request");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (s && !summary) {
+    set_error(std::string(who) + ": null summaries");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  return scene_validate<T>(who, s, table, n_conf, nullptr, req, nullptr, summary, total);
+}
+
+// table on the device, total > 0, everything on st (which is waited for twice)
+template <typename T>
+static int nearest_run(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, size_t total, const hfcl_distance_request* req,
+                       double upper, hfcl_scene_summary* d_summary, typename SceneTypes<T>::R* d_min, size_t* n_evaluated, SceneCountSlots* counts,
+                       hipStream_t st) {
+  using R = typename SceneTypes<T>::R;
+  constexpr bool f32 = std::is_same<T, float>::value;
+  hfcl_lib* lib = s->lib;
+  hfcl_lib::SceneWs& w = lib->scene;
+  const int max_blocks = lib->n_cus * 16;
+  int rc = ensure_local_boxes(lib);
+  if (rc) return rc;
+  const size_t chunk = cull_chunk_size(lib, total);
+  const uint32_t shares = scene_shares(uint32_t(s->n_pairs));
+  rc = cull_chunk_buffers(lib, chunk);
+  if (rc) return rc;
+  HIP_TRY(w.d_boxes.grow(n_conf * s->n_objects * 6));
+  HIP_TRY(w.d_conf_begin.grow(n_conf + 1));
+  HIP_TRY(w.d_conf_begin2.grow(n_conf + 1));
+  HIP_TRY(w.d_seed.grow(n_conf));
+  HIP_TRY(w.d_thr.grow(n_conf));
+  if (shares > 1u) HIP_TRY(w.d_seed_partials.grow(n_conf * shares * sizeof(NearestSeed)));
+  const size_t guess = std::min<size_t>(total, std::max<size_t>(total / 8, 4096));
+  HIP_TRY(w.d_ids.grow(guess));
+  HIP_TRY(w.d_ids2.grow(guess));
+
+  launch_cull_aabbs(st, d_table, f32, s->d_object_shape, lib->d_local_boxes, s->n_objects, n_conf * s->n_objects, w.d_boxes);
+  NearestArgs a{};
+  a.c.pairs = s->d_pairs;
+  a.c.boxes = w.d_boxes;
+  a.c.c_box0 = 0;
+  a.c.n_objects = s->n_objects;
+  a.c.n_pairs = uint32_t(s->n_pairs);
+  a.c.total = total;
+  a.c.n_conf = n_conf;
+  a.c.inflate = 0.0;
+  a.c.words = w.d_words;
+  a.c.block_counts = w.d_block_counts;
+  a.c.block_offsets = w.d_block_offsets;
+  a.c.running = w.d_running;
+  a.c.n_listed = w.d_running + 1;
+  a.r = f32 ? NEAREST_R32 : NEAREST_R64;
+  a.upper = upper;
+  a.seed = w.d_seed;
+  a.seed_partials = shares > 1u ? w.d_seed_partials.get() : nullptr;
+  a.thr = w.d_thr;
+  launch_nearest_seed(st, a, max_blocks);
+
+  // the list of a pass into ids / conf_begin, and the one read-back: its count.  A list that outgrows the buffer is made again in a larger one.
+  auto compact = [&](int pass, DevBuf<uint64_t>& ids, uint64_t* conf_begin, uint64_t& n) -> int {
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      a.c.ids = ids;
+      a.c.capacity = ids.capacity();
+      a.c.conf_begin = conf_begin;
+      for (size_t q0 = 0; q0 < total; q0 += chunk) {
+        a.c.q0 = q0;
+        scene_query(q0, a.c.n_pairs, a.c.c0, a.c.p0);
+        a.c.m = uint32_t(std::min(chunk, total - q0));
+        a.c.first = q0 == 0 ? 1 : 0;
+        launch_nearest_chunk(st, a, pass);
+      }
+      HIP_TRY(hipMemcpyAsync(&n, w.d_running + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      if (n <= ids.capacity()) break;
+      HIP_TRY(ids.grow(size_t(n)));
+    }
+    return HFCL_OK;
+  };
+  uint64_t n_list[2] = {0, 0};
+  DevBuf<uint64_t>* ids[2] = {&w.d_ids, &w.d_ids2};
+  uint64_t* conf_begin[2] = {w.d_conf_begin, w.d_conf_begin2};
+  for (int pass = 1; pass <= 2; ++pass) {
+    const int l = pass - 1;
+    if (pass == 2) launch_nearest_threshold(st, a, d_summary);
+    rc = compact(pass, *ids[l], conf_begin[l], n_list[l]);
+    if (rc) return rc;
+    if (d_min) HIP_TRY(w.d_nrec[l].grow(size_t(n_list[l]) * sizeof(R)));
+    const SceneListedExtra extra{pass == 2, counts};
+    rc = scene_listed_device<T>(who, s, d_table, n_conf, ids[l]->get(), size_t(n_list[l]), conf_begin[l], nullptr, req,
+                                d_min ? static_cast<R*>(w.d_nrec[l].get()) : nullptr, d_summary, nullptr, nullptr, st, &extra);
+    if (rc) return rc;
+  }
+  if (d_min) {
+    NearestGatherArgs g;
+    g.summary = d_summary;
+    g.n_conf = n_conf;
+    g.n_pairs = uint32_t(s->n_pairs);
+    for (int l = 0; l < 2; ++l) {
+      g.ids[l] = ids[l]->get();
+      g.conf_begin[l] = conf_begin[l];
+      g.rec[l] = w.d_nrec[l].get();
+    }
+    g.out = d_min;
+    launch_nearest_gather(st, g, f32);
+  }
+  if (n_evaluated) {
+    n_evaluated[0] = size_t(n_list[0]);
+    n_evaluated[1] = size_t(n_list[1]);
+  }
+  HIP_TRY(hipGetLastError());
+  return HFCL_OK;
+}
+
+template <typename T>
+static int nearest_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const hfcl_distance_request* req, double upper,
+                          hfcl_scene_summary* d_summary, typename SceneTypes<T>::R* d_min, size_t* n_evaluated, hipStream_t st) {
+  size_t total;
+  const int rc = nearest_validate<T>(who, s, d_table, n_conf, req, upper, d_summary, total);
+  if (rc) return rc;
+  if (n_evaluated) n_evaluated[0] = n_evaluated[1] = 0;
+  if (!n_conf) return HFCL_OK;
+  hfcl_lib* lib = s->lib;
+  HIP_TRY(hipSetDevice(lib->device));
+  if (!total) {  // no query: every configuration is one without records
+    launch_scene_summary_init(st, d_summary, n_conf, lib->n_cus * 16);
+    if (d_min) {
+      NearestGatherArgs g = {};
+      g.summary = d_summary;
+      g.n_conf = n_conf;
+      g.out = d_min;
+      launch_nearest_gather(st, g, std::is_same<T, float>::value);
+    }
+    HIP_TRY(hipGetLastError());
+    return HFCL_OK;
+  }
+  return nearest_run<T>(who, s, d_table, n_conf, total, req, upper, d_summary, d_min, n_evaluated, nullptr, st);
+}
+
+template <typename T>
+static int nearest_host(const char* who, hfcl_scene* s, const void* table, size_t n_conf, const hfcl_distance_request* req, double upper,
+                        hfcl_scene_summary* summary, typename SceneTypes<T>::R* min_records, size_t* n_evaluated) {
+  using R = typename SceneTypes<T>::R;
+  size_t total;
+  int rc = nearest_validate<T>(who, s, table, n_conf, req, upper, summary, total);
+  if (rc) return rc;
+  if (n_evaluated) n_evaluated[0] = n_evaluated[1] = 0;
+  if (!total) {
+    for (size_t c = 0; c < n_conf; ++c) {
+      scene_summary_init(summary[c]);
+      if (min_records) {
+        memset(&min_records[c], 0, sizeof(R));
+        nearest_no_record(min_records[c]);
+      }
+    }
+    return HFCL_OK;
+  }
+  hfcl_lib* lib = s->lib;
+  hfcl_lib::SceneWs& w = lib->scene;
+  HIP_TRY(hipSetDevice(lib->device));
+  rc = scene_host_stream(w);
+  if (rc) return rc;
+  HIP_TRY(w.d_summary.grow(n_conf));
+  if (min_records) HIP_TRY(w.d_minrec.grow(n_conf * sizeof(R)));
+  SceneCountSlots counts(lib);
+  rc = counts.begin();
+  if (rc) return rc;
+  auto finish = [&](int code) {  // nothing of this call stays in flight, whatever happened
+    const bool synced = hipStreamSynchronize(w.s_cmp) == hipSuccess;
+    if (lib->side) hipStreamSynchronize(lib->side);
+    counts.end(code == HFCL_OK && synced);
+    if (code == HFCL_OK && !synced) {
+      set_error(std::string(who) + ": the device reported an error");
+      return int(HFCL_ERR_HIP);
+    }
+    return code;
+  };
+  rc = scene_table_in(w, table, n_conf * s->n_objects * SceneTypes<T>::WIDTH * sizeof(T));
+  if (!rc) rc = nearest_run<T>(who, s, w.d_table, n_conf, total, req, upper, w.d_summary, min_records ? static_cast<R*>(w.d_minrec.get()) : nullptr,
+                               n_evaluated, &counts, w.s_cmp);
+  if (!rc && hipMemcpyAsync(summary, w.d_summary, n_conf * sizeof(hfcl_scene_summary), hipMemcpyDeviceToHost, w.s_cmp) != hipSuccess) rc = HFCL_ERR_HIP;
+  if (!rc && min_records && hipMemcpyAsync(min_records, w.d_minrec, n_conf * sizeof(R), hipMemcpyDeviceToHost, w.s_cmp) != hipSuccess)
+    rc = HFCL_ERR_HIP;
+  rc = finish(rc);
+  if (rc) return rc;
+  lib->last_host = true;
+  return host_batch_checks(lib, nullptr, req);
 }
 
 extern "C" {
@@ -919,5 +1196,25 @@ int hfcl_scene_distance_culled_f32(hfcl_scene* s, const float* object_pose, size
   return scene_host<float>("hfcl_scene_distance_culled_f32", s, object_pose, n_conf, nullptr, req, out, summary, nullptr, nullptr, &cull);
 }
 #undef HFCL_NEED_DREQ
+
+// ---- the per-configuration minimum distance with box-bound pruning -----------------------------------------------------------------
+int hfcl_scene_nearest(hfcl_scene* s, const double* object_tf, size_t n_conf, const hfcl_distance_request* req, double upper_bound,
+                       hfcl_scene_summary* summary, hfcl_result* min_records, size_t* n_evaluated) {
+  return nearest_host<double>("hfcl_scene_nearest", s, object_tf, n_conf, req, upper_bound, summary, min_records, n_evaluated);
+}
+int hfcl_scene_nearest_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, const hfcl_distance_request* req, double upper_bound,
+                           hfcl_scene_summary* summary, hfcl_result_f32* min_records, size_t* n_evaluated) {
+  return nearest_host<float>("hfcl_scene_nearest_f32", s, object_pose, n_conf, req, upper_bound, summary, min_records, n_evaluated);
+}
+int hfcl_scene_nearest_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const hfcl_distance_request* req, double upper_bound,
+                              hfcl_scene_summary* d_summary, hfcl_result* d_min_records, size_t* n_evaluated, void* stream) {
+  return nearest_device<double>("hfcl_scene_nearest_device", s, d_object_tf, n_conf, req, upper_bound, d_summary, d_min_records, n_evaluated,
+                                (hipStream_t)stream);
+}
+int hfcl_scene_nearest_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, const hfcl_distance_request* req, double upper_bound,
+                                  hfcl_scene_summary* d_summary, hfcl_result_f32* d_min_records, size_t* n_evaluated, void* stream) {
+  return nearest_device<float>("hfcl_scene_nearest_device_f32", s, d_object_pose, n_conf, req, upper_bound, d_summary, d_min_records, n_evaluated,
+                               (hipStream_t)stream);
+}
 
 }  // extern "C"

@@ -142,6 +142,11 @@ __global__ void __launch_bounds__(CULL_BLOCK) k_cull_emit(CullArgs a) {
 void launch_cull_chunk(hipStream_t st, const CullArgs& a) {
   const uint32_t n_blocks = uint32_t((uint64_t(a.m) + CULL_BLOCK - 1u) / CULL_BLOCK);
   hipLaunchKernelGGL(k_cull_mark, dim3(n_blocks), dim3(CULL_BLOCK), 0, st, a);
+  launch_cull_scan_emit(st, a);
+}
+
+void launch_cull_scan_emit(hipStream_t st, const CullArgs& a) {
+  const uint32_t n_blocks = uint32_t((uint64_t(a.m) + CULL_BLOCK - 1u) / CULL_BLOCK);
   hipLaunchKernelGGL(k_cull_scan, dim3(1), dim3(256), 0, st, a, n_blocks);
   hipLaunchKernelGGL(k_cull_emit, dim3(n_blocks), dim3(CULL_BLOCK), 0, st, a);
 }

@@ -192,3 +192,34 @@ struct SceneFoldListedArgs {
   uint64_t n_conf;               // configurations of the call: the bound on those a chunk spans (it may span empty ones: not bounded by k1 - k0)
 };
 void launch_scene_fold_listed(hipStream_t st, const SceneFoldListedArgs& a, bool f32, int max_blocks);
+// (hfcl_k_cull.hip) the scan and the emit of launch_cull_chunk alone, behind a mark kernel of another unit that left a.words / a.block_counts
+void launch_cull_scan_emit(hipStream_t st, const CullArgs& a);
+
+// hfcl_k_nearest.hip: the per-configuration minimum distance with box-bound pruning (hfcl_scene_nearest*; hfcl_nearest.hpp has the arithmetic).
+// c.boxes: the world boxes of the WHOLE table (c.c_box0 = 0); c.inflate unused
+struct NearestArgs {
+  CullArgs c;
+  double r;                  // the bound's rounding term: NEAREST_R64 / NEAREST_R32
+  double upper;              // the caller's upper bound D
+  uint32_t* seed;            // n_conf: written by launch_nearest_seed, read by the marks
+  void* seed_partials;       // nullptr (pair lists of one piece) or n_conf * scene_shares(n_pairs) NearestSeed
+  double* thr;               // n_conf: written by launch_nearest_threshold, read by the mark of pass 2
+};
+// seed[c] of every configuration: a wave per (configuration, piece of SCENE_FOLD_SHARE pairs), then a wave per configuration
+void launch_nearest_seed(hipStream_t st, const NearestArgs& a, int max_blocks);
+// a chunk [q0, q0 + m) of the flat range: the mark of pass 1 / pass 2, then launch_cull_scan_emit
+void launch_nearest_chunk(hipStream_t st, const NearestArgs& a, int pass);
+// thr[c] = min(D, summary[c].min_distance)
+void launch_nearest_threshold(hipStream_t st, const NearestArgs& a, const hfcl_scene_summary* summary);
+// min record of every configuration: the record of c * n_pairs + min_pair out of the two lists' records (rec[k] is for ids[k]); a
+// configuration without a min_pair gets distance = +inf, status bit 31
+struct NearestGatherArgs {
+  const hfcl_scene_summary* summary;
+  uint64_t n_conf;
+  uint32_t n_pairs;
+  const uint64_t* ids[2];
+  const uint64_t* conf_begin[2];
+  const void* rec[2];
+  void* out;
+};
+void launch_nearest_gather(hipStream_t st, const NearestGatherArgs& a, bool f32);

@@ -42,6 +42,10 @@ CULL_SYMBOLS = [
     "hfcl_scene_distance_listed_device_f32", "hfcl_scene_collide_culled", "hfcl_scene_distance_culled", "hfcl_scene_collide_culled_f32",
     "hfcl_scene_distance_culled_f32",
 ]
+# include/hppfcl_amd_nearest.h (included by hppfcl_amd.h): the per-configuration minimum distance with box-bound pruning
+NEAREST_SYMBOLS = [
+    "hfcl_scene_nearest", "hfcl_scene_nearest_f32", "hfcl_scene_nearest_device", "hfcl_scene_nearest_device_f32",
+]
 
 
 class EngineError(RuntimeError):
@@ -682,6 +686,42 @@ class Scene:
         _check(dll().hfcl_scene_distance_listed_device_f32(self._h, _dptr(d_object_pose), C.c_size_t(int(n_conf)), _dptr(d_query_ids),
                                                            C.c_size_t(int(n_listed)), _dptr(d_conf_begin), C.byref(req), _dptr(d_out),
                                                            _dptr(d_summary), C.c_void_p(stream)))
+
+    # ---- the per-configuration minimum distance with box-bound pruning (include/hppfcl_amd_nearest.h) ----
+    def _nearest(self, object_tf, req, upper_bound, records, f32):
+        tf = self._table(object_tf, np.float32 if f32 else np.float64, 7 if f32 else 12)
+        n_conf = len(tf)
+        summ = np.zeros(n_conf, dtype=abi.SCENE_SUMMARY_DTYPE)
+        rec = np.zeros(n_conf, dtype=abi.RESULT_F32_DTYPE if f32 else abi.RESULT_DTYPE) if records else None
+        n = (C.c_size_t * 2)()
+        fn = dll().hfcl_scene_nearest_f32 if f32 else dll().hfcl_scene_nearest
+        _check(fn(self._h, abi.ptr(tf), C.c_size_t(n_conf), C.byref(req or abi.default_distance_request()), C.c_double(upper_bound),
+                  abi.ptr(summ), abi.ptr(rec), n))
+        return summ, rec, (int(n[0]), int(n[1]))
+
+    def nearest(self, object_tf, req=None, upper_bound=float("inf"), records=True):
+        """hfcl_scene_nearest: (summaries, min_records, n_evaluated).  min_distance / min_pair of a summary equal those of distance()
+        wherever that minimum is <= upper_bound (elsewhere: some value above it, or +inf); min record c is the record of query
+        c * n_pairs + min_pair (records=False: None); n_evaluated: the queries the two narrow-phase passes evaluated."""
+        return self._nearest(object_tf, req, upper_bound, records, False)
+
+    def nearest_f32(self, object_pose, req=None, upper_bound=float("inf"), records=True):
+        """(n_conf, n_objects, 7) float32 poses, hfcl_result_f32 min records."""
+        return self._nearest(object_pose, req, upper_bound, records, True)
+
+    def nearest_device(self, d_object_tf, n_conf, req, d_summary, d_min_records=None, upper_bound=float("inf"), stream=0):
+        """hfcl_scene_nearest_device: device tensors or pointers, enqueued on `stream`, which the call waits on twice (the two list
+        counts).  Returns n_evaluated."""
+        n = (C.c_size_t * 2)()
+        _check(dll().hfcl_scene_nearest_device(self._h, _dptr(d_object_tf), C.c_size_t(int(n_conf)), C.byref(req), C.c_double(upper_bound),
+                                               _dptr(d_summary), _dptr(d_min_records), n, C.c_void_p(stream)))
+        return int(n[0]), int(n[1])
+
+    def nearest_device_f32(self, d_object_pose, n_conf, req, d_summary, d_min_records=None, upper_bound=float("inf"), stream=0):
+        n = (C.c_size_t * 2)()
+        _check(dll().hfcl_scene_nearest_device_f32(self._h, _dptr(d_object_pose), C.c_size_t(int(n_conf)), C.byref(req),
+                                                   C.c_double(upper_bound), _dptr(d_summary), _dptr(d_min_records), n, C.c_void_p(stream)))
+        return int(n[0]), int(n[1])
 
 
 def shard_range(n, rank, world):

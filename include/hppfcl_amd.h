@@ -661,4 +661,6 @@ int hfcl_scene_distance_device_f32(hfcl_scene* s, const float* d_object_pose, si
 #endif
 /* scene queries with the pair list culled per configuration on the device: the cull, the calls on its list, the host forms */
 #include "hppfcl_amd_cull.h"
+/* the per-configuration minimum distance with the pairs pruned by a bound from their boxes */
+#include "hppfcl_amd_nearest.h"
 #endif /* HPPFCL_AMD_H */

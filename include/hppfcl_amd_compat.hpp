@@ -1486,6 +1486,30 @@ class Scene {
     for (size_t k = 0; k < n; ++k) ctx_.fill((*results)[k], shape_pair(query_ids[k] % numPairs()), rec_[k], guess_[k]);
   }
 
+  /// The clearance per configuration (hfcl_scene_nearest, include/hppfcl_amd_nearest.h): what DistanceCallBackDefault leaves behind
+  /// after DynamicAABBTreeCollisionManager::distance -- the smallest distance over the listed pairs and the pair that has it --, with
+  /// the pairs pruned by a bound from their world boxes instead of evaluated one by one.  summaries[c].min_distance / min_pair equal
+  /// those of distance() wherever that minimum is <= upper_bound (+inf: always); elsewhere min_distance is some value above
+  /// upper_bound, or +inf.  results: nullptr or one DistanceResult per configuration, filled from the closest pair's record (o1, o2,
+  /// nearest points, normal, b1, b2); a configuration without an evaluated pair keeps a default DistanceResult.
+  void nearest(const Transform3f* tables, size_t n_conf, const DistanceRequest& request, double upper_bound,
+               std::vector<hfcl_scene_summary>& summaries, std::vector<DistanceResult>* results, size_t* n_evaluated = nullptr) {
+    ensure();
+    const hfcl_distance_request a = to_abi(request);
+    summaries.resize(n_conf);
+    if (results) rec_.resize(n_conf);
+    const int rc = hfcl_scene_nearest(scene_, reinterpret_cast<const double*>(tables), n_conf, &a, upper_bound, summaries.data(),
+                                      results ? rec_.data() : nullptr, n_evaluated);
+    if (rc) throw_for(rc);
+    if (!results) return;
+    results->assign(n_conf, DistanceResult());
+    hfcl_guess g;
+    std::memset(&g, 0, sizeof(g));
+    g.gjk_guess[0] = 1.0;  // (DistanceResult's own default: no guess comes back from this call)
+    for (size_t c = 0; c < n_conf; ++c)
+      if (summaries[c].min_pair != 0xFFFFFFFFu) ctx_.fill((*results)[c], shape_pair(summaries[c].min_pair), rec_[c], g);
+  }
+
  private:
   size_t list_guess(size_t n_conf) const {
     const size_t total = n_conf * numPairs();

@@ -10,13 +10,22 @@ configuration) and on workloads.scene_planner at ~1 M queries.
   H  hfcl_scene_collide_culled, summaries only (host clock; against C)
   I  hfcl_scene_cull_device, the count read back, hfcl_scene_collide_listed_device with records and summaries (device events; against E)
   J  the same through the fp32 path (against K)          K  hfcl_scene_collide_device_f32, records and summaries (device events)
-The culled forms run at --inflate (default 0: the reference's manager).  planner2048: scene_planner(2048, 16), 215 040 queries.
+  L  hfcl_scene_distance, summaries only (host clock)               M  hfcl_scene_nearest, summaries only (host clock; against L)
+  N  hfcl_scene_distance_device, summaries only (device events)     O  hfcl_scene_nearest_device, summaries only (device events; against N)
+  P, Q, R, S  the same four through the fp32 path
+  T  the narrow phase of nearest's pass 1 alone: hfcl_scene_distance_listed_device on that list, summaries only (device events)
+  U  ... of pass 2          V, W  the same two through the fp32 path
+The culled forms run at --inflate (default 0: the reference's manager).  planner2048: scene_planner(2048, 16), 215 040 queries;
+planner2048x32: scene_planner(2048, 32), 952 320 queries.  L .. W report the share of the queries each pass of nearest evaluates.
+Rows L .. W import the numpy model of the selection from tests/nearest_model.py: the lists of T .. W (the library keeps its own in its
+workspace) and the fp32 (lb - d_f32) / M come from it; no other row depends on tests/.
 
 Every measurement runs in a child process; A and D also run on a library built from the parent commit's sources (--parent-lib, selected
 with HFCL_LIB_PATH in the child), alternating with the build under test.  Warm-up calls first, then --calls timed calls: median, min, max.
 
   python tools/scene_bench.py [--parent-lib build/ab/lib_parent.so] [--calls 12] [--rounds 2] [--out profiles/x.json]
-  python tools/scene_bench.py --worker --workload cfg5 --forms A,D     (one child; prints one JSON line)"""
+  python tools/scene_bench.py --worker --workload cfg5 --forms A,D     (one child; prints one JSON line)
+  python tools/scene_bench.py --workloads planner2048,planner2048x32 --forms L,M,N,O,P,Q,R,S,T,U,V,W     (the pruned minimum distance)"""
 import argparse
 import json
 import os
@@ -36,7 +45,10 @@ def _workload(pkg, name):
         b = wl.cfg5_broadphase_scene()
         sc = b.scene
         return b.lib, sc["obj_shape"], sc["pairs"], sc["obj_tf"].reshape(1, -1, 12)
-    ps = wl.scene_planner(n_conf=2048 if name == "planner2048" else 9984, n_objects=16)
+    if name == "planner2048x32":
+        ps = wl.scene_planner(n_conf=2048, n_objects=32)
+    else:
+        ps = wl.scene_planner(n_conf=2048 if name == "planner2048" else 9984, n_objects=16)
     return ps.lib, ps.obj_shape, ps.pairs, ps.obj_tf
 
 
@@ -90,7 +102,7 @@ def worker(args):
         return _stats(ms)
 
     forms = args.forms.split(",")
-    scene = lib.scene(obj_shape, pairs) if set(forms) & set("BCEFGHIJK") else None
+    scene = lib.scene(obj_shape, pairs) if set(forms) & set("BCEFGHIJKLMNOPQRSTUVW") else None
     if "A" in forms or "D" in forms:
         t0 = time.perf_counter()
         s1, s2, tf1, tf2 = expand()
@@ -137,7 +149,7 @@ def worker(args):
     if "I" in forms:
         d_rec2 = torch.zeros(max(len(ids), 1) * 24, dtype=torch.int32, device=dev)
         out["forms"]["I"] = device_clock(lambda: culled_device(d_tab64, d_rec2, False))
-    if "J" in forms or "K" in forms:
+    if set(forms) & set("JKPQRSVW"):
         # 7-float poses of the same table: quaternions from the rotation matrices (w from the trace; the planner's and cfg5's rotations are
         # generic, no w near 0)
         R = pkg.geometry.pose_R(table.reshape(-1, 12))
@@ -153,6 +165,51 @@ def worker(args):
         d_ids = torch.zeros(max(len(ids32), len(ids), 1), dtype=torch.int64, device=dev)
         d_rec32c = torch.zeros(len(d_ids) * 11, dtype=torch.int32, device=dev)
         out["forms"]["J"] = device_clock(lambda: culled_device(d_pose, d_rec32c, True))
+    if set(forms) & set("LMNOPQRSTUVW"):  # the pruned minimum distance against the unculled summaries-only call
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import nearest_model
+        dreq = abi.default_distance_request()
+        d_sum3 = torch.zeros(n_conf * 6, dtype=torch.int32, device=dev)
+        for f32, letters in ((False, "LMNOTU"), (True, "PQRSVW")):
+            if not set(forms) & set(letters):
+                continue
+            tab = pose if f32 else table
+            d_t = d_pose if f32 else torch.from_numpy(np.ascontiguousarray(table)).to(dev)
+            host_full = scene.distance_f32 if f32 else scene.distance
+            host_near = scene.nearest_f32 if f32 else scene.nearest
+            dev_full = scene.distance_device_f32 if f32 else scene.distance_device
+            dev_near = scene.nearest_device_f32 if f32 else scene.nearest_device
+            listed = scene.distance_listed_device_f32 if f32 else scene.distance_listed_device
+            summ, _, n_eval = host_near(tab, dreq, records=False)
+            rec, full = host_full(tab, dreq)
+            key = "nearest_f32" if f32 else "nearest"
+            out[key] = {"evaluated": list(n_eval), "share_pct": [100.0 * k / n for k in n_eval],
+                        "equal_to_unculled": bool(summ["min_distance"].tobytes() == full["min_distance"].tobytes() and
+                                                  summ["min_pair"].tobytes() == full["min_pair"].tobytes())}
+            if f32:  # what the fp32 rounding term of the bound has to cover
+                boxes = scene.world_aabbs(tab)
+                lb, _, M = nearest_model.raw_bound(boxes[:, pairs[:, 0]], boxes[:, pairs[:, 1]])
+                ok = (np.isfinite(lb) & (lb > 0)).reshape(-1)
+                out[key]["max_lb_minus_d_over_M"] = float(((lb.reshape(-1) - rec["distance"].astype(np.float64)) / M.reshape(-1))[ok].max())
+            if letters[0] in forms:
+                out["forms"][letters[0]] = host_clock(lambda: host_full(tab, dreq, records=False))
+            if letters[1] in forms:
+                out["forms"][letters[1]] = host_clock(lambda: host_near(tab, dreq, records=False))
+            if letters[2] in forms:
+                out["forms"][letters[2]] = device_clock(lambda: dev_full(d_t, n_conf, dreq, None, d_sum3, stream=st))
+            if letters[3] in forms:
+                out["forms"][letters[3]] = device_clock(lambda: dev_near(d_t, n_conf, dreq, d_sum3, None, stream=st))
+            if letters[4] in forms or letters[5] in forms:
+                L_ = nearest_model.query_bounds(scene.world_aabbs(tab), pairs, nearest_model.R32 if f32 else nearest_model.R64)
+                sel = nearest_model.select(abi, L_, rec, np.inf)
+                assert (len(sel["ids1"]), len(sel["ids2"])) == tuple(n_eval)
+                for letter, k in ((letters[4], "1"), (letters[5], "2")):
+                    if letter not in forms:
+                        continue
+                    d_l = torch.from_numpy(sel["ids" + k].view(np.int64)).to(dev)
+                    d_c = torch.from_numpy(sel["conf_begin" + k].view(np.int64)).to(dev)
+                    m = len(sel["ids" + k])
+                    out["forms"][letter] = device_clock(lambda: listed(d_t, n_conf, d_l, m, d_c, dreq, None, d_sum3, stream=st))
     torch.cuda.synchronize()
     if scene is not None:
         scene.close()
@@ -177,7 +234,7 @@ def bytes_moved(n_conf, G, P):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--worker", action="store_true")
-    ap.add_argument("--workload", default="cfg5", choices=["cfg5", "planner", "planner2048"])
+    ap.add_argument("--workload", default="cfg5", choices=["cfg5", "planner", "planner2048", "planner2048x32"])
     ap.add_argument("--workloads", default="cfg5,planner", help="the workloads of a full run, comma-separated")
     ap.add_argument("--inflate", type=float, default=0.0)
     ap.add_argument("--forms", default="A,B,C,D,E,F")
@@ -218,13 +275,19 @@ def main():
         print("| form | build | median ms | min .. max ms (over the runs) |")
         print("|---|---|---|---|")
         for which in ("parent", "new"):
-            for f in "ABCDEFGHIJK":
+            for f in "ABCDEFGHIJKLMNOPQRSTUVW":
                 runs = [r["forms"][f] for r in rs if r["build"] == which and f in r["forms"]]
                 if runs:
                     print("| %s | %s | %s | %.3f .. %.3f |" % (f, which, " / ".join("%.3f" % x["median_ms"] for x in runs),
                                                           min(x["min_ms"] for x in runs), max(x["max_ms"] for x in runs)))
         print("host expansion for A: %s ms" % " / ".join("%.1f" % r["host_expansion_ms"] for r in rs if "host_expansion_ms" in r))
         print("bytes per query: " + json.dumps(bytes_moved(r0["n_conf"], r0["n_objects"], r0["n_pairs"])))
+        for key in ("nearest", "nearest_f32"):
+            if key in r0:
+                k = r0[key]
+                print("%s: %d + %d queries evaluated (%.2f %% + %.2f %%), min_distance / min_pair equal to the unculled call: %s%s" % (
+                    key, k["evaluated"][0], k["evaluated"][1], k["share_pct"][0], k["share_pct"][1], k["equal_to_unculled"],
+                    "; largest (lb - d_f32) / M = %.3g" % k["max_lb_minus_d_over_M"] if "max_lb_minus_d_over_M" in k else ""))
         if "n_listed" in r0:
             print("cull at inflate %g: %d of %d queries survive (%.2f %%); byte model of the cull alone: %.0f bytes" % (
                 r0["inflate"], r0["n_listed"], r0["queries"], 100.0 * r0["n_listed"] / r0["queries"], r0["cull_model_bytes"]))
