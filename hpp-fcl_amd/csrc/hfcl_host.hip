@@ -1012,9 +1012,8 @@ static int host_batch_small(hfcl_lib* lib, const uint32_t* s1, const uint32_t* s
     d_tf1 = reinterpret_cast<const double*>(d + o_tf1);
     d_tf2 = reinterpret_cast<const double*>(d + o_tf2);
   }
-  memset(lib->acc_counts, 0, sizeof(lib->acc_counts));
+  HostBatchScope scope(lib);
   memset(lib->h_pack_counts, 0, 2 * N_COUNTERS * sizeof(uint32_t));
-  lib->in_host_batch = true;
   lib->counts_dst = lib->h_pack_counts;
   if (lib->helper) lib->helper->counts_dst = lib->h_pack_counts + N_COUNTERS;  // (a batch this small is never split)
   int rc;
@@ -1032,9 +1031,6 @@ static int host_batch_small(hfcl_lib* lib, const uint32_t* s1, const uint32_t* s
   hipError_t e = hipSuccess;
   if (rc == HFCL_OK) e = hipMemcpyAsync(h + o_out, d + o_out, out_bytes, hipMemcpyDeviceToHost, st);
   const hipError_t e2 = hipStreamSynchronize(st);  // (also after a failed launch sequence: nothing of this call stays in flight)
-  lib->in_host_batch = false;
-  lib->counts_dst = nullptr;
-  if (lib->helper) lib->helper->counts_dst = nullptr;
   if (rc) return rc;
   if (e != hipSuccess || e2 != hipSuccess) {
     set_error(std::string("host batch (small): ") + hipGetErrorString(e != hipSuccess ? e : e2));
@@ -1079,8 +1075,7 @@ static int host_batch(hfcl_lib* lib, const uint32_t* s1, const uint32_t* s2, con
   if (rc) return rc;
   SmallBatchBuckets batch_buckets(lib, s1, s2, n, dreq != nullptr);
   constexpr int S = hfcl_lib::PIPE_SLOTS;
-  memset(lib->acc_counts, 0, sizeof(lib->acc_counts));
-  lib->in_host_batch = true;
+  HostBatchScope scope(lib);  // (before the threads: they are joined on every way out)
 
   // Host threads keep the streams busy.  A copy between pageable memory and the device holds its caller until the data
   // has moved (above a few MB; the first time a range of host memory is used it is also pinned, several times slower),
@@ -1198,9 +1193,6 @@ static int host_batch(hfcl_lib* lib, const uint32_t* s1, const uint32_t* s2, con
     hipStreamSynchronize(lib->s_h2d2);
     hipStreamSynchronize(lib->s_cmp);
     hipStreamSynchronize(lib->s_d2h);
-    lib->in_host_batch = false;
-    lib->counts_dst = nullptr;
-    if (lib->helper) lib->helper->counts_dst = nullptr;
     return code;
   };
 #define PIPE_TRY(expr)                                                       \
@@ -1278,9 +1270,6 @@ static int host_batch(hfcl_lib* lib, const uint32_t* s1, const uint32_t* s2, con
       fprintf(stderr, "[hfcl pipe] chunk %2zu %7zu pairs: copy-in issued %.3f..%.3f  launches %.3f..%.3f  kernels done %.3f  records out %.3f\n", k,
               bounds[k + 1] - bounds[k], tr[6 * k], tr[6 * k + 1], tr[6 * k + 2], tr[6 * k + 3], tr[6 * k + 4], tr[6 * k + 5]);
   }
-  lib->in_host_batch = false;
-  lib->counts_dst = nullptr;
-  if (lib->helper) lib->helper->counts_dst = nullptr;
   lib->last_host = true;
   if (side_rc) {
     set_error(side_err);

@@ -349,6 +349,24 @@ inline uint32_t one_count(const uint32_t* c, int i) {
   return c[i] + (i < B_COUNT ? c[B_CURVED0 + i] : 0u) + (i == B_COUNT ? c[B_COUNT + 3] : 0u);
 }
 
+// A host call whose chunks go through the device batch entry points, for its duration: the populations of the chunks are summed into
+// acc_counts, run_batch_one sends a chunk's where counts_dst points.  Declared before the call enqueues anything, so that it ends after
+// the call's streams have been waited for and its threads joined.
+struct HostBatchScope {
+  hfcl_lib* lib;
+  explicit HostBatchScope(hfcl_lib* l) : lib(l) {
+    memset(lib->acc_counts, 0, sizeof(lib->acc_counts));
+    lib->in_host_batch = true;
+  }
+  ~HostBatchScope() {
+    lib->in_host_batch = false;
+    lib->counts_dst = nullptr;
+    if (lib->helper) lib->helper->counts_dst = nullptr;
+  }
+  HostBatchScope(const HostBatchScope&) = delete;
+  HostBatchScope& operator=(const HostBatchScope&) = delete;
+};
+
 // what the units call of each other (internal to the shared library: hidden)
 #pragma GCC visibility push(hidden)
 // hfcl_host_batch.hip

@@ -1,6 +1,7 @@
 // hfcl_host_scene.hip -- host side of the scene queries (hfcl_scene_*) and of the cull of their pair lists (the kernels: hfcl_k_scene.hip,
 // hfcl_k_cull.hip).  The library object and what this unit calls of hfcl_host.hip: hfcl_host.hpp.
 #include "hfcl_host.hpp"
+#include "hfcl_plan.hpp"
 #include "hfcl_nearest.hpp"
 #include "../../include/hppfcl_amd_nearest.h"
 
@@ -69,45 +70,56 @@ static int scene_batch(hfcl_lib* lib, const uint32_t* s1, const uint32_t* s2, co
               : hfcl_distance_batch_device_f32(lib, s1, s2, static_cast<const float*>(tf1), static_cast<const float*>(tf2), m, dreq, rec, st);
 }
 
-// everything a scene call refuses before any work; total: n_conf * n_pairs (0: nothing to do)
+// What every scene and cull call refuses before any work, in this order: a null scene, a stale one, a null table, an overflow; total:
+// n_conf * n_pairs.  nothing_if_zero: the member (n_pairs: the scene calls, n_objects: the cull calls) that, like n_conf, leaves a call with
+// nothing to do when it is 0 -- HFCL_OK before the table is looked at.  (The overflow test skips n_pairs == 0, which only the cull calls'
+// rule lets through.)
 template <typename T>
-static int scene_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, const hfcl_collision_request* creq,
-                          const hfcl_distance_request* dreq, const void* out, const void* summary, size_t& total) {
+static int scene_validate_core(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, size_t hfcl_scene::*nothing_if_zero,
+                               size_t& total) {
   total = 0;
   if (!s) {
     set_error(std::string(who) + ": null scene");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  QParams<T> q;
-  bool skip;
-  const int rc = creq ? setup_collide<T>(creq, q, skip) : setup_distance<T>(dreq, q);
-  if (rc) return rc;
-  if (!out && !summary) {
-    set_error(std::string(who) + ": records and summaries both NULL");
     return HFCL_ERR_INVALID_ARGUMENT;
   }
   if (s->epoch != s->lib->shapes_epoch) {
     set_error(std::string(who) + ": the library's shapes were replaced (hfcl_lib_set_shapes) after this scene was created; create a new scene");
     return HFCL_ERR_INVALID_ARGUMENT;
   }
-  if (n_conf == 0 || s->n_pairs == 0) return HFCL_OK;
+  if (n_conf == 0 || s->*nothing_if_zero == 0) return HFCL_OK;
   if (!table) {
     set_error(std::string(who) + ": null pose table");
     return HFCL_ERR_INVALID_ARGUMENT;
   }
-  if (n_conf > ~size_t(0) / s->n_pairs || n_conf > ~size_t(0) / (s->n_objects * SceneTypes<T>::WIDTH * sizeof(T))) {
+  if ((s->n_pairs && n_conf > ~size_t(0) / s->n_pairs) || n_conf > ~size_t(0) / (s->n_objects * SceneTypes<T>::WIDTH * sizeof(T))) {
     set_error(std::string(who) + ": n_conf * n_pairs overflows");
     return HFCL_ERR_LIMIT;
   }
   total = n_conf * s->n_pairs;
   return HFCL_OK;
 }
-// queries per chunk of a call of `total` queries: the option as given, or equal chunks of at most 2^21
-static size_t scene_chunk_size(const hfcl_lib* lib, size_t total) {
-  if (lib->opt.scene_chunk) return std::min<size_t>(std::min<size_t>(lib->opt.scene_chunk, total), 0xFFFFFFF0ull);
-  constexpr size_t AUTO = size_t(1) << 21;
-  const size_t n_chunks = (total + AUTO - 1) / AUTO;
-  return (total + n_chunks - 1) / n_chunks;
+// everything a scene call refuses before any work; total: n_conf * n_pairs (0: nothing to do).  Of a scene that is there, the request (a
+// null one: "null request", setup_collide / setup_distance) and the outputs are looked at before the scene's state
+template <typename T>
+static int scene_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, const hfcl_collision_request* creq,
+                          const hfcl_distance_request* dreq, const void* out, const void* summary, size_t& total) {
+  total = 0;
+  if (s) {
+    QParams<T> q;
+    bool skip;
+    const int rc = creq ? setup_collide<T>(creq, q, skip) : setup_distance<T>(dreq, q);
+    if (rc) return rc;
+    if (!out && !summary) {
+      set_error(std::string(who) + ": records and summaries both NULL");
+      return HFCL_ERR_INVALID_ARGUMENT;
+    }
+  }
+  return scene_validate_core<T>(who, s, table, n_conf, &hfcl_scene::n_pairs, total);
+}
+// what the cull calls refuse before any work; total: n_conf * n_pairs (0: no query)
+template <typename T>
+static int cull_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, size_t& total) {
+  return scene_validate_core<T>(who, s, table, n_conf, &hfcl_scene::n_objects, total);
 }
 
 // workspace of chunks of up to m queries; recs: how many of the two record buffers; pieces: fold partials (0: none)
@@ -129,16 +141,21 @@ static int scene_workspace(hfcl_lib* lib, size_t m, int recs, bool gin, int gout
   HIP_TRY(w.d_partials.grow(pieces));
   return HFCL_OK;
 }
-// fold partials a chunk of m queries can need: none when a pair list is one piece
-static size_t scene_pieces_bound(size_t n_pairs, size_t m) {
-  if (scene_shares(uint32_t(n_pairs)) <= 1u) return 0;
-  // whole pieces inside the chunk, a cut one at either end, and one more cut per configuration boundary inside it
-  return m / SCENE_FOLD_SHARE + 2 + 2 * (m / n_pairs + 2);
+// A list of flat queries on the device, as hfcl_scene_cull_device leaves it: ascending ids, conf_begin theirs.  Where a function takes a
+// pointer to one, nullptr is the flat range itself.
+struct SceneList {
+  const uint64_t* d_ids;
+  const uint64_t* d_conf_begin;
+  size_t n_conf;
+};
+// fold partials of a call in chunks of `chunk`
+static size_t scene_pieces(const hfcl_scene* s, const SceneList* list, size_t chunk) {
+  return list ? scene_listed_pieces_bound(s->n_pairs, list->n_conf) : scene_pieces_bound(s->n_pairs, chunk);
 }
 
-// expansion of chunk [q0, q0 + m), the batch, the fold: all on st
+// expansion of the chunk [k0, k0 + m) of the flat range or of the list, the batch, the fold: all on st
 template <typename T>
-static int scene_chunk_run(hfcl_scene* s, const void* d_table, size_t q0, size_t m, const hfcl_collision_request* creq,
+static int scene_chunk_run(hfcl_scene* s, const void* d_table, const SceneList* list, size_t k0, size_t m, const hfcl_collision_request* creq,
                            const hfcl_distance_request* dreq, typename SceneTypes<T>::R* d_rec, hfcl_scene_summary* d_summary,
                            const hfcl_guess* d_gin, hfcl_guess* d_gout, hipStream_t st) {
   hfcl_lib* lib = s->lib;
@@ -151,28 +168,47 @@ static int scene_chunk_run(hfcl_scene* s, const void* d_table, size_t q0, size_t
   ea.object_tf = d_table;
   ea.n_objects = s->n_objects;
   ea.n_pairs = uint32_t(s->n_pairs);
-  ea.q0 = q0;
-  scene_query(q0, ea.n_pairs, ea.c0, ea.p0);
+  ea.q0 = list ? 0 : k0;  // (a list's rows name their queries)
+  scene_query(ea.q0, ea.n_pairs, ea.c0, ea.p0);
   ea.m = uint32_t(m);
   ea.s1 = w.d_s1;
   ea.s2 = w.d_s2;
   ea.tf1 = w.d_tf1;
   ea.tf2 = w.d_tf2;
-  launch_scene_expand(st, ea, f32, max_blocks);
+  if (list)
+    launch_scene_expand_listed(st, ea, list->d_ids + k0, f32, max_blocks);
+  else
+    launch_scene_expand(st, ea, f32, max_blocks);
   const int rc = scene_batch(lib, w.d_s1, w.d_s2, w.d_tf1, w.d_tf2, m, creq, dreq, d_rec, d_gin, d_gout, st);
-  if (rc) return rc;
-  if (d_summary) {
-    SceneFoldArgs fa;
+  if (rc || !d_summary) return rc;
+  const double margin = creq ? creq->security_margin : 0.0;
+  hfcl_scene_summary* partials = scene_shares(ea.n_pairs) > 1u ? w.d_partials.get() : nullptr;
+  if (list) {
+    SceneFoldListedArgs fa;
     fa.rec = d_rec;
-    fa.q0 = q0;
-    fa.q1 = q0 + m;
-    fa.n_pairs = uint32_t(s->n_pairs);
-    fa.g0 = scene_piece_of(q0, fa.n_pairs);
-    fa.n_pieces = scene_piece_of(q0 + m - 1, fa.n_pairs) - fa.g0 + 1;
-    fa.margin = creq ? creq->security_margin : 0.0;
+    fa.ids = list->d_ids;
+    fa.conf_begin = list->d_conf_begin;
+    fa.k0 = k0;
+    fa.k1 = k0 + m;
+    fa.n_pairs = ea.n_pairs;
+    fa.margin = margin;
     fa.collide = creq ? 1 : 0;
     fa.summary = d_summary;
-    fa.partials = scene_shares(fa.n_pairs) > 1u ? w.d_partials : nullptr;
+    fa.partials = partials;
+    fa.n_conf = list->n_conf;
+    launch_scene_fold_listed(st, fa, f32, max_blocks);
+  } else {
+    SceneFoldArgs fa;
+    fa.rec = d_rec;
+    fa.q0 = k0;
+    fa.q1 = k0 + m;
+    fa.n_pairs = ea.n_pairs;
+    fa.g0 = scene_piece_of(k0, fa.n_pairs);
+    fa.n_pieces = scene_piece_of(k0 + m - 1, fa.n_pairs) - fa.g0 + 1;
+    fa.margin = margin;
+    fa.collide = creq ? 1 : 0;
+    fa.summary = d_summary;
+    fa.partials = partials;
     launch_scene_fold(st, fa, f32, max_blocks);
   }
   return HFCL_OK;
@@ -183,22 +219,75 @@ static void scene_join_side(hfcl_lib* lib, hipStream_t st) {
   if (lib->side && lib->ev_join && hipEventRecord(lib->ev_join, lib->side) == hipSuccess) (void)hipStreamWaitEvent(st, lib->ev_join, 0);
 }
 
+// The bucket populations of a host form (one at a time: HostBatchScope): COUNT_SLOTS pinned slots, a chunk's populations in the first half
+// of its slot, its second half's -- when it ran split -- in the other.  Chunk k uses slot k % COUNT_SLOTS once chunk k - COUNT_SLOTS has
+// been added up.
+struct SceneCountSlots {
+  static constexpr int CS = hfcl_lib::SceneWs::COUNT_SLOTS;
+  static constexpr size_t SLOT_WORDS = 2 * size_t(N_COUNTERS);
+  // the pinned block and the events, once per library: before the first SceneCountSlots
+  static int ready(hfcl_lib::SceneWs& w) {
+    if (!w.h_counts) HIP_TRY(w.h_counts.alloc(CS * SLOT_WORDS));
+    for (Event& e : w.ev_counts)
+      if (!e) HIP_TRY(e.create());
+    return HFCL_OK;
+  }
+  hfcl_lib* lib;
+  HostBatchScope scope;
+  bool slot_split[CS] = {};
+  size_t k = 0;  // chunks so far
+  explicit SceneCountSlots(hfcl_lib* l) : lib(l), scope(l) {
+    memset(lib->scene.h_counts, 0, CS * SLOT_WORDS * sizeof(uint32_t));  // (a skipped batch -- -inf margin -- copies no counters)
+  }
+  void harvest(int slot) {  // a finished chunk's bucket populations into the call's sums; the slot is free again
+    uint32_t* c = lib->scene.h_counts + size_t(slot) * SLOT_WORDS;
+    for (int i = 0; i < N_COUNTERS; ++i) lib->acc_counts[i] += c[i] + (slot_split[slot] ? c[N_COUNTERS + i] : 0u);
+    memset(c, 0, SLOT_WORDS * sizeof(uint32_t));
+  }
+  int before_chunk(size_t m) {
+    hfcl_lib::SceneWs& w = lib->scene;
+    const int slot = int(k % CS);
+    if (k >= size_t(CS)) {  // the chunk that used this slot has run: its counters are on the host
+      HIP_TRY(hipEventSynchronize(w.ev_counts[slot]));
+      harvest(slot);
+    }
+    lib->counts_dst = w.h_counts + size_t(slot) * SLOT_WORDS;
+    if (batch_splits(lib, m)) {
+      const int rc = ensure_helper(lib);
+      if (rc) return rc;
+      lib->helper->counts_dst = lib->counts_dst + N_COUNTERS;
+    }
+    return HFCL_OK;
+  }
+  int after_chunk(hipStream_t st) {
+    const int slot = int(k % CS);
+    slot_split[slot] = lib->last_split;
+    HIP_TRY(hipEventRecord(lib->scene.ev_counts[slot], st));
+    ++k;
+    return HFCL_OK;
+  }
+  // the call's streams have been waited for and nothing failed: the populations are complete
+  void harvest_rest() {
+    for (int slot = 0; slot < CS && size_t(slot) < k; ++slot) harvest(slot);
+  }
+};
+
+// `work` queries of the flat range (list: entries of the list) in chunks, one after the other on st: the workspace, then per chunk its
+// records to d_out (nullptr: the workspace's buffer), a host form's count slots (counts; nullptr: none) around it.
 template <typename T>
-static int scene_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const hfcl_collision_request* creq,
-                        const hfcl_distance_request* dreq, typename SceneTypes<T>::R* d_out, hfcl_scene_summary* d_summary,
-                        const hfcl_guess* d_gin, hfcl_guess* d_gout, hipStream_t st) {
-  size_t total;
-  int rc = scene_validate<T>(who, s, d_table, n_conf, creq, dreq, d_out, d_summary, total);
-  if (rc || !total) return rc;
+static int scene_chunks_device(hfcl_scene* s, const void* d_table, const SceneList* list, size_t work, const hfcl_collision_request* creq,
+                               const hfcl_distance_request* dreq, typename SceneTypes<T>::R* d_out, hfcl_scene_summary* d_summary,
+                               const hfcl_guess* d_gin, hfcl_guess* d_gout, hipStream_t st, SceneCountSlots* counts = nullptr) {
   hfcl_lib* lib = s->lib;
-  HIP_TRY(hipSetDevice(lib->device));
-  const size_t chunk = scene_chunk_size(lib, total);
-  rc = scene_workspace(lib, chunk, d_out ? 0 : 1, false, 0, d_summary ? scene_pieces_bound(s->n_pairs, chunk) : 0);
+  const size_t chunk = scene_chunk_size(work, lib->opt.scene_chunk);
+  int rc = scene_workspace(lib, chunk, d_out ? 0 : 1, false, 0, d_summary ? scene_pieces(s, list, chunk) : 0);
   if (rc) return rc;
-  for (size_t q0 = 0; q0 < total; q0 += chunk) {
-    const size_t m = std::min(chunk, total - q0);
-    auto* rec = d_out ? d_out + q0 : static_cast<typename SceneTypes<T>::R*>(lib->scene.d_rec[0].get());
-    rc = scene_chunk_run<T>(s, d_table, q0, m, creq, dreq, rec, d_summary, d_gin ? d_gin + q0 : nullptr, d_gout ? d_gout + q0 : nullptr, st);
+  for (size_t k0 = 0; k0 < work; k0 += chunk) {
+    const size_t m = std::min(chunk, work - k0);
+    auto* rec = d_out ? d_out + k0 : static_cast<typename SceneTypes<T>::R*>(lib->scene.d_rec[0].get());
+    rc = counts ? counts->before_chunk(m) : HFCL_OK;
+    if (!rc) rc = scene_chunk_run<T>(s, d_table, list, k0, m, creq, dreq, rec, d_summary, d_gin ? d_gin + k0 : nullptr, d_gout ? d_gout + k0 : nullptr, st);
+    if (!rc && counts) rc = counts->after_chunk(st);
     if (rc) {
       scene_join_side(lib, st);
       return rc;
@@ -206,6 +295,17 @@ static int scene_device(const char* who, hfcl_scene* s, const void* d_table, siz
   }
   HIP_TRY(hipGetLastError());
   return HFCL_OK;
+}
+
+template <typename T>
+static int scene_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const hfcl_collision_request* creq,
+                        const hfcl_distance_request* dreq, typename SceneTypes<T>::R* d_out, hfcl_scene_summary* d_summary,
+                        const hfcl_guess* d_gin, hfcl_guess* d_gout, hipStream_t st) {
+  size_t total;
+  const int rc = scene_validate<T>(who, s, d_table, n_conf, creq, dreq, d_out, d_summary, total);
+  if (rc || !total) return rc;
+  HIP_TRY(hipSetDevice(s->lib->device));
+  return scene_chunks_device<T>(s, d_table, nullptr, total, creq, dreq, d_out, d_summary, d_gin, d_gout, st);
 }
 
 
@@ -241,42 +341,12 @@ static int ensure_local_boxes(hfcl_lib* lib) {
   return HFCL_OK;
 }
 
-// what the cull calls refuse before any work; total: n_conf * n_pairs (0: no query)
-template <typename T>
-static int cull_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, size_t& total) {
-  total = 0;
-  if (!s) {
-    set_error(std::string(who) + ": null scene");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  if (s->epoch != s->lib->shapes_epoch) {
-    set_error(std::string(who) + ": the library's shapes were replaced (hfcl_lib_set_shapes) after this scene was created; create a new scene");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  if (n_conf == 0 || s->n_objects == 0) return HFCL_OK;
-  if (!table) {
-    set_error(std::string(who) + ": null pose table");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  if ((s->n_pairs && n_conf > ~size_t(0) / s->n_pairs) || n_conf > ~size_t(0) / (s->n_objects * SceneTypes<T>::WIDTH * sizeof(T))) {
-    set_error(std::string(who) + ": n_conf * n_pairs overflows");
-    return HFCL_ERR_LIMIT;
-  }
-  total = n_conf * s->n_pairs;
-  return HFCL_OK;
-}
 static int cull_check_inflate(const char* who, double inflate) {
   if (!(inflate >= 0.0)) {
     set_error(std::string(who) + ": inflate must be >= 0 (and not NaN)");
     return HFCL_ERR_INVALID_ARGUMENT;
   }
   return HFCL_OK;
-}
-static size_t cull_chunk_size(const hfcl_lib* lib, size_t total) {
-  if (lib->opt.scene_cull_chunk) return std::min<size_t>(lib->opt.scene_cull_chunk, total);
-  constexpr size_t AUTO = size_t(1) << 22;
-  const size_t n_chunks = (total + AUTO - 1) / AUTO;
-  return (total + n_chunks - 1) / n_chunks;
 }
 
 // world boxes of the whole table -> d_out (n_conf * n_objects * 6 doubles), on st
@@ -314,6 +384,49 @@ static int cull_chunk_buffers(hfcl_lib* lib, size_t chunk) {
   return HFCL_OK;
 }
 
+// what every cull of a scene's flat range gives its kernels, whatever marks the queries
+static void cull_args(CullArgs& a, const hfcl_scene* s, size_t total, size_t n_conf, double inflate, uint64_t* d_n_listed) {
+  hfcl_lib::SceneWs& w = s->lib->scene;
+  a.pairs = s->d_pairs;
+  a.boxes = w.d_boxes;
+  a.n_objects = s->n_objects;
+  a.n_pairs = uint32_t(s->n_pairs);
+  a.total = total;
+  a.n_conf = n_conf;
+  a.inflate = inflate;
+  a.words = w.d_words;
+  a.block_counts = w.d_block_counts;
+  a.block_offsets = w.d_block_offsets;
+  a.running = w.d_running;
+  a.n_listed = d_n_listed;
+}
+// the chunks of the flat range [0, a.total) in turn: a's q0, c0, p0, m and first are the chunk's when per_chunk() is called
+template <typename F>
+static void cull_chunks(CullArgs& a, size_t chunk, F&& per_chunk) {
+  for (size_t q0 = 0; q0 < a.total; q0 += chunk) {
+    a.q0 = q0;
+    scene_query(q0, a.n_pairs, a.c0, a.p0);
+    a.m = uint32_t(std::min<size_t>(chunk, a.total - q0));
+    a.first = q0 == 0 ? 1 : 0;
+    per_chunk();
+  }
+}
+// A list whose length is known only afterwards: make() enqueues its making into `ids` (as large as it is then) on st, the count at d_count
+// is read back -- 8 bytes, st waited for --, and a list that outgrew the buffer is made once more in one of its size.  want_ids = false:
+// the count alone.
+template <typename Make>
+static int list_and_count(DevBuf<uint64_t>& ids, bool want_ids, const uint64_t* d_count, hipStream_t st, uint64_t& n, Make&& make) {
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    const int rc = make();
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(&n, d_count, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (!want_ids || n <= ids.capacity()) break;
+    HIP_TRY(ids.grow(size_t(n)));
+  }
+  return HFCL_OK;
+}
+
 // The cull of the whole flat range on st: the list (ids below `capacity`), conf_begin, the count.  Nothing is read back.
 template <typename T>
 static int cull_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, double inflate, uint64_t* d_ids, size_t capacity,
@@ -337,40 +450,24 @@ static int cull_device(const char* who, hfcl_scene* s, const void* d_table, size
   rc = ensure_local_boxes(lib);
   if (rc) return rc;
   hfcl_lib::SceneWs& w = lib->scene;
-  const size_t chunk = cull_chunk_size(lib, total);
+  const size_t chunk = cull_chunk_size(total, lib->opt.scene_cull_chunk);
   const size_t conf_per_chunk = std::min<size_t>(n_conf, chunk / s->n_pairs + 2);
   HIP_TRY(w.d_boxes.grow(conf_per_chunk * s->n_objects * 6));
   rc = cull_chunk_buffers(lib, chunk);
   if (rc) return rc;
   constexpr bool f32 = std::is_same<T, float>::value;
   CullArgs a;
-  a.pairs = s->d_pairs;
-  a.boxes = w.d_boxes;
-  a.n_objects = s->n_objects;
-  a.n_pairs = uint32_t(s->n_pairs);
-  a.total = total;
-  a.n_conf = n_conf;
-  a.inflate = inflate;
-  a.words = w.d_words;
-  a.block_counts = w.d_block_counts;
-  a.block_offsets = w.d_block_offsets;
-  a.running = w.d_running;
+  cull_args(a, s, total, n_conf, inflate, d_n_listed);
   a.ids = d_ids;
   a.capacity = d_ids ? capacity : 0;
   a.conf_begin = d_conf_begin;
-  a.n_listed = d_n_listed;
-  for (size_t q0 = 0; q0 < total; q0 += chunk) {
-    const size_t m = std::min(chunk, total - q0);
-    a.q0 = q0;
-    scene_query(q0, a.n_pairs, a.c0, a.p0);
-    a.m = uint32_t(m);
-    a.first = q0 == 0 ? 1 : 0;
+  cull_chunks(a, chunk, [&]() {  // the boxes of the configurations the chunk touches, then the chunk
     a.c_box0 = a.c0;
-    const uint64_t c_last = (q0 + m - 1) / s->n_pairs;
+    const uint64_t c_last = (a.q0 + a.m - 1) / s->n_pairs;
     const char* rows = static_cast<const char*>(d_table) + a.c0 * s->n_objects * SceneTypes<T>::WIDTH * sizeof(T);
     launch_cull_aabbs(st, rows, f32, s->d_object_shape, lib->d_local_boxes, s->n_objects, (c_last - a.c0 + 1) * s->n_objects, w.d_boxes);
     launch_cull_chunk(st, a);
-  }
+  });
   HIP_TRY(hipGetLastError());
   return HFCL_OK;
 }
@@ -395,16 +492,10 @@ static int cull_into_workspace(const char* who, hfcl_scene* s, const void* d_tab
   hfcl_lib::SceneWs& w = lib->scene;
   HIP_TRY(w.d_conf_begin.grow(n_conf + 1));
   HIP_TRY(w.d_running.grow(2));
-  if (want_ids) HIP_TRY(w.d_ids.grow(std::min<size_t>(total, std::max<size_t>(total / 8, 4096))));
-  for (int pass = 0; pass < 2; ++pass) {
-    const int rc = cull_device<T>(who, s, d_table, n_conf, inflate, want_ids ? w.d_ids.get() : nullptr, w.d_ids.capacity(), w.d_conf_begin, w.d_running + 1, w.s_cmp);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(&n_listed, w.d_running + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
-    HIP_TRY(hipStreamSynchronize(w.s_cmp));
-    if (!want_ids || n_listed <= w.d_ids.capacity()) break;
-    HIP_TRY(w.d_ids.grow(size_t(n_listed)));
-  }
-  return HFCL_OK;
+  if (want_ids) HIP_TRY(w.d_ids.grow(list_capacity_guess(total)));
+  return list_and_count(w.d_ids, want_ids, w.d_running + 1, w.s_cmp, n_listed, [&]() {
+    return cull_device<T>(who, s, d_table, n_conf, inflate, want_ids ? w.d_ids.get() : nullptr, w.d_ids.capacity(), w.d_conf_begin, w.d_running + 1, w.s_cmp);
+  });
 }
 
 template <typename T>
@@ -471,125 +562,16 @@ static int scene_boxes_host(const char* who, hfcl_scene* s, const void* table, s
   return HFCL_OK;
 }
 
-// fold partials a chunk of the list can need: a slot per piece of every configuration it can span -- any number of them, whatever its
-// length, since configurations without an entry lie in between (none when a pair list is one piece)
-static size_t scene_listed_pieces_bound(size_t n_pairs, size_t n_conf) {
-  const uint32_t shares = scene_shares(uint32_t(n_pairs));
-  return shares <= 1u ? 0 : n_conf * shares;
-}
-// expansion of the chunk [k0, k0 + m) of the list, the batch, the fold: all on st
-template <typename T>
-static int scene_listed_chunk_run(hfcl_scene* s, const void* d_table, size_t n_conf, const uint64_t* d_ids, const uint64_t* d_conf_begin, size_t k0,
-                                  size_t m, const hfcl_collision_request* creq, const hfcl_distance_request* dreq,
-                                  typename SceneTypes<T>::R* d_rec, hfcl_scene_summary* d_summary, const hfcl_guess* d_gin, hfcl_guess* d_gout,
-                                  hipStream_t st) {
-  hfcl_lib* lib = s->lib;
-  hfcl_lib::SceneWs& w = lib->scene;
-  constexpr bool f32 = std::is_same<T, float>::value;
-  const int max_blocks = lib->n_cus * 16;
-  SceneExpandArgs ea;
-  ea.pairs = s->d_pairs;
-  ea.object_shape = s->d_object_shape;
-  ea.object_tf = d_table;
-  ea.n_objects = s->n_objects;
-  ea.n_pairs = uint32_t(s->n_pairs);
-  ea.q0 = 0;
-  ea.c0 = 0;
-  ea.p0 = 0;
-  ea.m = uint32_t(m);
-  ea.s1 = w.d_s1;
-  ea.s2 = w.d_s2;
-  ea.tf1 = w.d_tf1;
-  ea.tf2 = w.d_tf2;
-  launch_scene_expand_listed(st, ea, d_ids + k0, f32, max_blocks);
-  const int rc = scene_batch(lib, w.d_s1, w.d_s2, w.d_tf1, w.d_tf2, m, creq, dreq, d_rec, d_gin, d_gout, st);
-  if (rc) return rc;
-  if (d_summary) {
-    SceneFoldListedArgs fa;
-    fa.rec = d_rec;
-    fa.ids = d_ids;
-    fa.conf_begin = d_conf_begin;
-    fa.k0 = k0;
-    fa.k1 = k0 + m;
-    fa.n_pairs = uint32_t(s->n_pairs);
-    fa.margin = creq ? creq->security_margin : 0.0;
-    fa.collide = creq ? 1 : 0;
-    fa.summary = d_summary;
-    fa.partials = scene_shares(fa.n_pairs) > 1u ? w.d_partials : nullptr;
-    fa.n_conf = n_conf;
-    launch_scene_fold_listed(st, fa, f32, max_blocks);
-  }
-  return HFCL_OK;
-}
-
-// The bucket populations of a host form whose chunks run through scene_listed_device (hfcl_scene_nearest*): a pinned slot per chunk, as
-// scene_host keeps them -- chunk k uses slot k % COUNT_SLOTS once chunk k - COUNT_SLOTS has been added up.
-struct SceneCountSlots {
-  static constexpr int CS = hfcl_lib::SceneWs::COUNT_SLOTS;
-  static constexpr size_t SLOT_WORDS = 2 * size_t(N_COUNTERS);
-  hfcl_lib* lib;
-  bool slot_split[CS] = {};
-  size_t k = 0;  // chunks so far
-  explicit SceneCountSlots(hfcl_lib* l) : lib(l) {}
-  int begin() {
-    hfcl_lib::SceneWs& w = lib->scene;
-    if (!w.h_counts) HIP_TRY(w.h_counts.alloc(CS * SLOT_WORDS));
-    for (Event& e : w.ev_counts)
-      if (!e) HIP_TRY(e.create());
-    memset(w.h_counts, 0, CS * SLOT_WORDS * sizeof(uint32_t));
-    memset(lib->acc_counts, 0, sizeof(lib->acc_counts));
-    lib->in_host_batch = true;
-    return HFCL_OK;
-  }
-  void harvest(int slot) {
-    uint32_t* c = lib->scene.h_counts + size_t(slot) * SLOT_WORDS;
-    for (int i = 0; i < N_COUNTERS; ++i) lib->acc_counts[i] += c[i] + (slot_split[slot] ? c[N_COUNTERS + i] : 0u);
-    memset(c, 0, SLOT_WORDS * sizeof(uint32_t));
-  }
-  int before_chunk(size_t m) {
-    hfcl_lib::SceneWs& w = lib->scene;
-    const int slot = int(k % CS);
-    if (k >= size_t(CS)) {
-      HIP_TRY(hipEventSynchronize(w.ev_counts[slot]));
-      harvest(slot);
-    }
-    lib->counts_dst = w.h_counts + size_t(slot) * SLOT_WORDS;
-    if (batch_splits(lib, m)) {
-      const int rc = ensure_helper(lib);
-      if (rc) return rc;
-      lib->helper->counts_dst = lib->counts_dst + N_COUNTERS;
-    }
-    return HFCL_OK;
-  }
-  int after_chunk(hipStream_t st) {
-    const int slot = int(k % CS);
-    slot_split[slot] = lib->last_split;
-    HIP_TRY(hipEventRecord(lib->scene.ev_counts[slot], st));
-    ++k;
-    return HFCL_OK;
-  }
-  // the call's streams have been waited for (ok: and nothing failed -- the populations are complete)
-  void end(bool ok) {
-    for (int slot = 0; ok && slot < CS && size_t(slot) < k; ++slot) harvest(slot);
-    lib->in_host_batch = false;
-    lib->counts_dst = nullptr;
-    if (lib->helper) lib->helper->counts_dst = nullptr;
-  }
-};
-// what hfcl_scene_nearest* adds to a run on a list
-struct SceneListedExtra {
-  bool merge;               // the summaries are not re-initialised: the list's records are merged into what is stored
-  SceneCountSlots* counts;  // nullptr, or the host form's slots
-};
-
 // The device form on a list.  The ids are not checked: ascending, below n_conf * n_pairs, conf_begin theirs -- as hfcl_scene_cull_device leaves them.
+// merge (hfcl_scene_nearest*): the summaries are not re-initialised, the list's records are merged into what is stored; counts: as
+// scene_chunks_device takes them.
 template <typename T>
 static int scene_listed_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const uint64_t* d_ids, size_t n_listed,
                                const uint64_t* d_conf_begin, const hfcl_collision_request* creq, const hfcl_distance_request* dreq,
                                typename SceneTypes<T>::R* d_out, hfcl_scene_summary* d_summary, const hfcl_guess* d_gin, hfcl_guess* d_gout,
-                               hipStream_t st, const SceneListedExtra* extra = nullptr) {
+                               hipStream_t st, bool merge = false, SceneCountSlots* counts = nullptr) {
   size_t total;
-  int rc = scene_validate<T>(who, s, d_table, n_conf, creq, dreq, d_out, d_summary, total);
+  const int rc = scene_validate<T>(who, s, d_table, n_conf, creq, dreq, d_out, d_summary, total);
   if (rc) return rc;
   if (d_summary && !d_conf_begin) {
     set_error(std::string(who) + ": summaries need conf_begin");
@@ -605,30 +587,13 @@ static int scene_listed_device(const char* who, hfcl_scene* s, const void* d_tab
   }
   hfcl_lib* lib = s->lib;
   HIP_TRY(hipSetDevice(lib->device));
-  if (d_summary && !(extra && extra->merge)) launch_scene_summary_init(st, d_summary, n_conf, lib->n_cus * 16);
+  if (d_summary && !merge) launch_scene_summary_init(st, d_summary, n_conf, lib->n_cus * 16);
   if (!n_listed) {
     HIP_TRY(hipGetLastError());
     return HFCL_OK;
   }
-  const size_t chunk = scene_chunk_size(lib, n_listed);
-  rc = scene_workspace(lib, chunk, d_out ? 0 : 1, false, 0, d_summary ? scene_listed_pieces_bound(s->n_pairs, n_conf) : 0);
-  if (rc) return rc;
-  for (size_t k0 = 0; k0 < n_listed; k0 += chunk) {
-    const size_t m = std::min(chunk, n_listed - k0);
-    auto* rec = d_out ? d_out + k0 : static_cast<typename SceneTypes<T>::R*>(lib->scene.d_rec[0].get());
-    SceneCountSlots* counts = extra ? extra->counts : nullptr;
-    rc = counts ? counts->before_chunk(m) : HFCL_OK;
-    if (!rc)
-      rc = scene_listed_chunk_run<T>(s, d_table, n_conf, d_ids, d_conf_begin, k0, m, creq, dreq, rec, d_summary, d_gin ? d_gin + k0 : nullptr,
-                                     d_gout ? d_gout + k0 : nullptr, st);
-    if (!rc && counts) rc = counts->after_chunk(st);
-    if (rc) {
-      scene_join_side(lib, st);
-      return rc;
-    }
-  }
-  HIP_TRY(hipGetLastError());
-  return HFCL_OK;
+  const SceneList list{d_ids, d_conf_begin, n_conf};
+  return scene_chunks_device<T>(s, d_table, &list, n_listed, creq, dreq, d_out, d_summary, d_gin, d_gout, st, counts);
 }
 
 // what the culled host forms (hfcl_scene_*_culled) add to scene_host
@@ -695,36 +660,23 @@ static int scene_host(const char* who, hfcl_scene* s, const void* table, size_t 
       HIP_TRY(hipMemcpyAsync(cull->conf_begin_out, w.d_conf_begin, (n_conf + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
     work = size_t(n);
   }
-  const size_t chunk = scene_chunk_size(lib, work);
+  const SceneList listed{w.d_ids, w.d_conf_begin, n_conf};
+  const SceneList* list = cull ? &listed : nullptr;
+  const size_t chunk = scene_chunk_size(work, lib->opt.scene_chunk);
   const size_t n_chunks = (work + chunk - 1) / chunk;
   const bool back = out != nullptr || gout != nullptr;  // something per pair goes back: two buffers, the copy stream
-  rc = scene_workspace(lib, chunk, out ? 2 : 1, gin != nullptr, gout ? 2 : 0,
-                       !summary ? 0 : cull ? scene_listed_pieces_bound(s->n_pairs, n_conf) : scene_pieces_bound(s->n_pairs, chunk));
+  rc = scene_workspace(lib, chunk, out ? 2 : 1, gin != nullptr, gout ? 2 : 0, summary ? scene_pieces(s, list, chunk) : 0);
   if (rc) return rc;
   if (!cull) HIP_TRY(w.d_table.grow(table_bytes));
   if (summary) HIP_TRY(w.d_summary.grow(n_conf));
-  constexpr int CS = hfcl_lib::SceneWs::COUNT_SLOTS;
-  constexpr size_t SLOT_WORDS = 2 * size_t(N_COUNTERS);
-  if (!w.h_counts) HIP_TRY(w.h_counts.alloc(CS * SLOT_WORDS));
-  for (Event& e : w.ev_counts)
-    if (!e) HIP_TRY(e.create());
-  memset(w.h_counts, 0, CS * SLOT_WORDS * sizeof(uint32_t));  // (a skipped batch -- -inf margin -- copies no counters)
-  bool slot_split[CS] = {};
-  memset(lib->acc_counts, 0, sizeof(lib->acc_counts));
-  auto harvest = [&](int slot) {  // a finished chunk's bucket populations into the call's sums; the slot is free again
-    uint32_t* c = w.h_counts + size_t(slot) * SLOT_WORDS;
-    for (int i = 0; i < N_COUNTERS; ++i) lib->acc_counts[i] += c[i] + (slot_split[slot] ? c[N_COUNTERS + i] : 0u);
-    memset(c, 0, SLOT_WORDS * sizeof(uint32_t));
-  };
-  lib->in_host_batch = true;
+  rc = SceneCountSlots::ready(w);
+  if (rc) return rc;
+  SceneCountSlots counts(lib);  // (ends after finish, or the tail, has waited for the streams)
 
   auto finish = [&](int code) {  // nothing of this call stays in flight, whatever happened
     hipStreamSynchronize(w.s_cmp);
     hipStreamSynchronize(w.s_copy);
     if (lib->side) hipStreamSynchronize(lib->side);
-    lib->in_host_batch = false;
-    lib->counts_dst = nullptr;
-    if (lib->helper) lib->helper->counts_dst = nullptr;
     return code;
   };
 #define SCENE_TRY(expr)                                                      \
@@ -735,8 +687,10 @@ static int scene_host(const char* who, hfcl_scene* s, const void* table, size_t 
       return finish(HFCL_ERR_HIP);                                           \
     }                                                                        \
   } while (0)
+  // which of the two record / guess buffers chunk k computes into while chunk k - 1's leave from the other (one buffer: nothing goes back)
+  auto buffer_of = [&](size_t k) { return back ? int(k & 1) : 0; };
   auto copy_back = [&](size_t k) -> hipError_t {  // chunk k's records (and guesses) to the caller's arrays, behind its kernels
-    const int b = int(k & 1);
+    const int b = buffer_of(k);
     const size_t q0 = k * chunk, m = std::min(chunk, work - q0);
     hipError_t e = hipStreamWaitEvent(w.s_copy, w.ev_done[b], 0);
     if (e == hipSuccess && out) e = hipMemcpyAsync(out + q0, w.d_rec[b], m * sizeof(R), hipMemcpyDeviceToHost, w.s_copy);
@@ -748,28 +702,16 @@ static int scene_host(const char* who, hfcl_scene* s, const void* table, size_t 
   if (!cull) SCENE_TRY(hipMemcpyAsync(w.d_table, table, table_bytes, hipMemcpyHostToDevice, w.s_cmp));
   if (cull && summary) launch_scene_summary_init(w.s_cmp, w.d_summary, n_conf, lib->n_cus * 16);
   for (size_t k = 0; k < n_chunks; ++k) {
-    const int b = back ? int(k & 1) : 0;
+    const int b = buffer_of(k);
     const size_t q0 = k * chunk, m = std::min(chunk, work - q0);
     if (back && k >= 2) SCENE_TRY(hipStreamWaitEvent(w.s_cmp, w.ev_copied[b], 0));  // chunk k - 2 has left the buffers
     if (gin) SCENE_TRY(hipMemcpyAsync(w.d_gin, gin + q0, m * sizeof(hfcl_guess), hipMemcpyHostToDevice, w.s_cmp));
-    const int slot = int(k % CS);
-    if (k >= size_t(CS)) {  // the chunk that used this slot has run: its counters are on the host
-      SCENE_TRY(hipEventSynchronize(w.ev_counts[slot]));
-      harvest(slot);
-    }
-    lib->counts_dst = w.h_counts + size_t(slot) * SLOT_WORDS;
-    if (batch_splits(lib, m)) {
-      rc = ensure_helper(lib);
-      if (rc) return finish(rc);
-      lib->helper->counts_dst = lib->counts_dst + N_COUNTERS;
-    }
-    rc = cull ? scene_listed_chunk_run<T>(s, w.d_table, n_conf, w.d_ids, w.d_conf_begin, q0, m, creq, dreq, static_cast<R*>(w.d_rec[out ? b : 0].get()),
-                                          summary ? w.d_summary : nullptr, gin ? w.d_gin : nullptr, gout ? w.d_gout[b] : nullptr, w.s_cmp)
-              : scene_chunk_run<T>(s, w.d_table, q0, m, creq, dreq, static_cast<R*>(w.d_rec[out ? b : 0].get()), summary ? w.d_summary : nullptr,
-                                   gin ? w.d_gin : nullptr, gout ? w.d_gout[b] : nullptr, w.s_cmp);
+    rc = counts.before_chunk(m);
+    if (!rc)
+      rc = scene_chunk_run<T>(s, w.d_table, list, q0, m, creq, dreq, static_cast<R*>(w.d_rec[out ? b : 0].get()), summary ? w.d_summary : nullptr,
+                              gin ? w.d_gin : nullptr, gout ? w.d_gout[b] : nullptr, w.s_cmp);
+    if (!rc) rc = counts.after_chunk(w.s_cmp);
     if (rc) return finish(rc);
-    slot_split[slot] = lib->last_split;
-    SCENE_TRY(hipEventRecord(w.ev_counts[slot], w.s_cmp));
     if (back) {
       SCENE_TRY(hipEventRecord(w.ev_done[b], w.s_cmp));
       if (k >= 1) SCENE_TRY(copy_back(k - 1));
@@ -781,10 +723,7 @@ static int scene_host(const char* who, hfcl_scene* s, const void* table, size_t 
   SCENE_TRY(hipStreamSynchronize(w.s_copy));
   SCENE_TRY(hipGetLastError());
 #undef SCENE_TRY
-  for (int slot = 0; slot < CS && size_t(slot) < n_chunks; ++slot) harvest(slot);
-  lib->in_host_batch = false;
-  lib->counts_dst = nullptr;
-  if (lib->helper) lib->helper->counts_dst = nullptr;
+  counts.harvest_rest();
   lib->last_host = true;
   return host_batch_checks(lib, creq, dreq);
 }
@@ -826,7 +765,7 @@ static int nearest_run(const char* who, hfcl_scene* s, const void* d_table, size
   const int max_blocks = lib->n_cus * 16;
   int rc = ensure_local_boxes(lib);
   if (rc) return rc;
-  const size_t chunk = cull_chunk_size(lib, total);
+  const size_t chunk = cull_chunk_size(total, lib->opt.scene_cull_chunk);
   const uint32_t shares = scene_shares(uint32_t(s->n_pairs));
   rc = cull_chunk_buffers(lib, chunk);
   if (rc) return rc;
@@ -836,25 +775,13 @@ static int nearest_run(const char* who, hfcl_scene* s, const void* d_table, size
   HIP_TRY(w.d_seed.grow(n_conf));
   HIP_TRY(w.d_thr.grow(n_conf));
   if (shares > 1u) HIP_TRY(w.d_seed_partials.grow(n_conf * shares * sizeof(NearestSeed)));
-  const size_t guess = std::min<size_t>(total, std::max<size_t>(total / 8, 4096));
-  HIP_TRY(w.d_ids.grow(guess));
-  HIP_TRY(w.d_ids2.grow(guess));
+  HIP_TRY(w.d_ids.grow(list_capacity_guess(total)));
+  HIP_TRY(w.d_ids2.grow(list_capacity_guess(total)));
 
   launch_cull_aabbs(st, d_table, f32, s->d_object_shape, lib->d_local_boxes, s->n_objects, n_conf * s->n_objects, w.d_boxes);
   NearestArgs a{};
-  a.c.pairs = s->d_pairs;
-  a.c.boxes = w.d_boxes;
+  cull_args(a.c, s, total, n_conf, 0.0, w.d_running + 1);
   a.c.c_box0 = 0;
-  a.c.n_objects = s->n_objects;
-  a.c.n_pairs = uint32_t(s->n_pairs);
-  a.c.total = total;
-  a.c.n_conf = n_conf;
-  a.c.inflate = 0.0;
-  a.c.words = w.d_words;
-  a.c.block_counts = w.d_block_counts;
-  a.c.block_offsets = w.d_block_offsets;
-  a.c.running = w.d_running;
-  a.c.n_listed = w.d_running + 1;
   a.r = f32 ? NEAREST_R32 : NEAREST_R64;
   a.upper = upper;
   a.seed = w.d_seed;
@@ -862,25 +789,15 @@ static int nearest_run(const char* who, hfcl_scene* s, const void* d_table, size
   a.thr = w.d_thr;
   launch_nearest_seed(st, a, max_blocks);
 
-  // the list of a pass into ids / conf_begin, and the one read-back: its count.  A list that outgrows the buffer is made again in a larger one.
+  // the list of a pass into ids / conf_begin, and the one read-back: its count
   auto compact = [&](int pass, DevBuf<uint64_t>& ids, uint64_t* conf_begin, uint64_t& n) -> int {
-    for (int attempt = 0; attempt < 2; ++attempt) {
+    return list_and_count(ids, true, w.d_running + 1, st, n, [&]() {
       a.c.ids = ids;
       a.c.capacity = ids.capacity();
       a.c.conf_begin = conf_begin;
-      for (size_t q0 = 0; q0 < total; q0 += chunk) {
-        a.c.q0 = q0;
-        scene_query(q0, a.c.n_pairs, a.c.c0, a.c.p0);
-        a.c.m = uint32_t(std::min(chunk, total - q0));
-        a.c.first = q0 == 0 ? 1 : 0;
-        launch_nearest_chunk(st, a, pass);
-      }
-      HIP_TRY(hipMemcpyAsync(&n, w.d_running + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      if (n <= ids.capacity()) break;
-      HIP_TRY(ids.grow(size_t(n)));
-    }
-    return HFCL_OK;
+      cull_chunks(a.c, chunk, [&]() { launch_nearest_chunk(st, a, pass); });
+      return int(HFCL_OK);
+    });
   };
   uint64_t n_list[2] = {0, 0};
   DevBuf<uint64_t>* ids[2] = {&w.d_ids, &w.d_ids2};
@@ -891,9 +808,8 @@ static int nearest_run(const char* who, hfcl_scene* s, const void* d_table, size
     rc = compact(pass, *ids[l], conf_begin[l], n_list[l]);
     if (rc) return rc;
     if (d_min) HIP_TRY(w.d_nrec[l].grow(size_t(n_list[l]) * sizeof(R)));
-    const SceneListedExtra extra{pass == 2, counts};
     rc = scene_listed_device<T>(who, s, d_table, n_conf, ids[l]->get(), size_t(n_list[l]), conf_begin[l], nullptr, req,
-                                d_min ? static_cast<R*>(w.d_nrec[l].get()) : nullptr, d_summary, nullptr, nullptr, st, &extra);
+                                d_min ? static_cast<R*>(w.d_nrec[l].get()) : nullptr, d_summary, nullptr, nullptr, st, pass == 2, counts);
     if (rc) return rc;
   }
   if (d_min) {
@@ -967,13 +883,13 @@ static int nearest_host(const char* who, hfcl_scene* s, const void* table, size_
   if (rc) return rc;
   HIP_TRY(w.d_summary.grow(n_conf));
   if (min_records) HIP_TRY(w.d_minrec.grow(n_conf * sizeof(R)));
-  SceneCountSlots counts(lib);
-  rc = counts.begin();
+  rc = SceneCountSlots::ready(w);
   if (rc) return rc;
+  SceneCountSlots counts(lib);  // (ends after finish has waited for the streams)
   auto finish = [&](int code) {  // nothing of this call stays in flight, whatever happened
     const bool synced = hipStreamSynchronize(w.s_cmp) == hipSuccess;
     if (lib->side) hipStreamSynchronize(lib->side);
-    counts.end(code == HFCL_OK && synced);
+    if (code == HFCL_OK && synced) counts.harvest_rest();
     if (code == HFCL_OK && !synced) {
       set_error(std::string(who) + ": the device reported an error");
       return int(HFCL_ERR_HIP);
@@ -1060,10 +976,6 @@ int hfcl_scene_collide(hfcl_scene* s, const double* object_tf, size_t n_conf, co
 }
 int hfcl_scene_distance(hfcl_scene* s, const double* object_tf, size_t n_conf, const hfcl_distance_request* req, hfcl_result* out,
                         hfcl_scene_summary* summary, const hfcl_guess* guess_in, hfcl_guess* guess_out) {
-  if (s && !req) {
-    set_error("null request");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
   return scene_host<double>("hfcl_scene_distance", s, object_tf, n_conf, nullptr, req, out, summary, guess_in, guess_out);
 }
 int hfcl_scene_collide_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const hfcl_collision_request* req, hfcl_result* d_out,
@@ -1073,10 +985,6 @@ int hfcl_scene_collide_device(hfcl_scene* s, const double* d_object_tf, size_t n
 }
 int hfcl_scene_distance_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const hfcl_distance_request* req, hfcl_result* d_out,
                                hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in, hfcl_guess* d_guess_out, void* stream) {
-  if (s && !req) {
-    set_error("null request");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
   return scene_device<double>("hfcl_scene_distance_device", s, d_object_tf, n_conf, nullptr, req, d_out, d_summary, d_guess_in, d_guess_out,
                               (hipStream_t)stream);
 }
@@ -1086,10 +994,6 @@ int hfcl_scene_collide_f32(hfcl_scene* s, const float* object_pose, size_t n_con
 }
 int hfcl_scene_distance_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, const hfcl_distance_request* req, hfcl_result_f32* out,
                             hfcl_scene_summary* summary) {
-  if (s && !req) {
-    set_error("null request");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
   return scene_host<float>("hfcl_scene_distance_f32", s, object_pose, n_conf, nullptr, req, out, summary, nullptr, nullptr);
 }
 int hfcl_scene_collide_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, const hfcl_collision_request* req,
@@ -1099,10 +1003,6 @@ int hfcl_scene_collide_device_f32(hfcl_scene* s, const float* d_object_pose, siz
 }
 int hfcl_scene_distance_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, const hfcl_distance_request* req,
                                    hfcl_result_f32* d_out, hfcl_scene_summary* d_summary, void* stream) {
-  if (s && !req) {
-    set_error("null request");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
   return scene_device<float>("hfcl_scene_distance_device_f32", s, d_object_pose, n_conf, nullptr, req, d_out, d_summary, nullptr, nullptr,
                              (hipStream_t)stream);
 }
@@ -1138,11 +1038,6 @@ int hfcl_scene_cull_device_f32(hfcl_scene* s, const float* d_object_pose, size_t
   return cull_device<float>("hfcl_scene_cull_device_f32", s, d_object_pose, n_conf, inflate, d_query_ids, capacity, d_conf_begin, d_n_listed,
                             (hipStream_t)stream);
 }
-#define HFCL_NEED_DREQ()                        \
-  if (s && !req) {                              \
-    set_error("null request");                  \
-    return HFCL_ERR_INVALID_ARGUMENT;           \
-  }
 int hfcl_scene_collide_listed_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const uint64_t* d_query_ids, size_t n_listed,
                                      const uint64_t* d_conf_begin, const hfcl_collision_request* req, hfcl_result* d_out,
                                      hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in, hfcl_guess* d_guess_out, void* stream) {
@@ -1152,7 +1047,6 @@ int hfcl_scene_collide_listed_device(hfcl_scene* s, const double* d_object_tf, s
 int hfcl_scene_distance_listed_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const uint64_t* d_query_ids, size_t n_listed,
                                       const uint64_t* d_conf_begin, const hfcl_distance_request* req, hfcl_result* d_out,
                                       hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in, hfcl_guess* d_guess_out, void* stream) {
-  HFCL_NEED_DREQ()
   return scene_listed_device<double>("hfcl_scene_distance_listed_device", s, d_object_tf, n_conf, d_query_ids, n_listed, d_conf_begin, nullptr, req,
                                      d_out, d_summary, d_guess_in, d_guess_out, (hipStream_t)stream);
 }
@@ -1165,7 +1059,6 @@ int hfcl_scene_collide_listed_device_f32(hfcl_scene* s, const float* d_object_po
 int hfcl_scene_distance_listed_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, const uint64_t* d_query_ids, size_t n_listed,
                                           const uint64_t* d_conf_begin, const hfcl_distance_request* req, hfcl_result_f32* d_out,
                                           hfcl_scene_summary* d_summary, void* stream) {
-  HFCL_NEED_DREQ()
   return scene_listed_device<float>("hfcl_scene_distance_listed_device_f32", s, d_object_pose, n_conf, d_query_ids, n_listed, d_conf_begin, nullptr,
                                     req, d_out, d_summary, nullptr, nullptr, (hipStream_t)stream);
 }
@@ -1178,7 +1071,6 @@ int hfcl_scene_collide_culled(hfcl_scene* s, const double* object_tf, size_t n_c
 int hfcl_scene_distance_culled(hfcl_scene* s, const double* object_tf, size_t n_conf, double inflate, const hfcl_distance_request* req,
                                hfcl_result* out, size_t out_capacity, uint64_t* query_ids_out, uint64_t* conf_begin_out,
                                hfcl_scene_summary* summary, const hfcl_guess* guess_in, hfcl_guess* guess_out, size_t* n_listed) {
-  HFCL_NEED_DREQ()
   const SceneCull cull{inflate, out_capacity, query_ids_out, conf_begin_out, n_listed};
   return scene_host<double>("hfcl_scene_distance_culled", s, object_tf, n_conf, nullptr, req, out, summary, guess_in, guess_out, &cull);
 }
@@ -1191,11 +1083,9 @@ int hfcl_scene_collide_culled_f32(hfcl_scene* s, const float* object_pose, size_
 int hfcl_scene_distance_culled_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, double inflate, const hfcl_distance_request* req,
                                    hfcl_result_f32* out, size_t out_capacity, uint64_t* query_ids_out, uint64_t* conf_begin_out,
                                    hfcl_scene_summary* summary, size_t* n_listed) {
-  HFCL_NEED_DREQ()
   const SceneCull cull{inflate, out_capacity, query_ids_out, conf_begin_out, n_listed};
   return scene_host<float>("hfcl_scene_distance_culled_f32", s, object_pose, n_conf, nullptr, req, out, summary, nullptr, nullptr, &cull);
 }
-#undef HFCL_NEED_DREQ
 
 // ---- the per-configuration minimum distance with box-bound pruning -----------------------------------------------------------------
 int hfcl_scene_nearest(hfcl_scene* s, const double* object_tf, size_t n_conf, const hfcl_distance_request* req, double upper_bound,

@@ -1,9 +1,12 @@
-// hfcl_plan.hpp -- the chunk plan of the host pipeline (hfcl_host.hip: host_batch).  Plain C++, no HIP header: tests/plan_harness builds it
-// with the host compiler.
+// hfcl_plan.hpp -- the planning arithmetic of the host units: the chunk plan of the host pipeline (hfcl_host.hip: host_batch), and the chunk
+// sizes, fold-partial bounds and list capacities of the scene calls (hfcl_host_scene.hip).  Plain C++, no HIP header: tests/plan_harness
+// builds it with the host compiler.
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <vector>
+
+#include "hfcl_scene.hpp"
 
 // Chunk bounds of a host batch of n > 0 pairs: chunk k = [bounds[k], bounds[k + 1]), bounds[0] = 0, bounds.back() = n.
 // Chunks: large enough that a chunk's fixed costs (a dozen launches, ~0.1 ms) vanish, small enough that the pipeline
@@ -42,3 +45,29 @@ inline std::vector<size_t> plan_chunks(size_t n, size_t pipe_chunk, bool pipelin
   }
   return bounds;
 }
+
+// ---- scene calls (hfcl_host_scene.hip) ------------------------------------------------------------------------------------
+// queries per chunk of a call of `total` > 0 queries: the option as given, or (0) equal chunks of at most auto_max
+inline size_t equal_chunks(size_t total, size_t option, size_t auto_max) {
+  if (option) return std::min(option, total);
+  const size_t n_chunks = (total + auto_max - 1) / auto_max;
+  return (total + n_chunks - 1) / n_chunks;
+}
+// ... of a scene call (option scene_chunk; a chunk's size goes to the kernels in 32 bits), of the cull (option scene_cull_chunk)
+inline size_t scene_chunk_size(size_t total, size_t option) { return std::min<size_t>(equal_chunks(total, option, size_t(1) << 21), 0xFFFFFFF0ull); }
+inline size_t cull_chunk_size(size_t total, size_t option) { return equal_chunks(total, option, size_t(1) << 22); }
+
+// fold partials a chunk of m queries of the flat range can need: none when a pair list is one piece
+inline size_t scene_pieces_bound(size_t n_pairs, size_t m) {
+  if (hfcl::scene_shares(uint32_t(n_pairs)) <= 1u) return 0;
+  // whole pieces inside the chunk, a cut one at either end, and one more cut per configuration boundary inside it
+  return m / hfcl::SCENE_FOLD_SHARE + 2 + 2 * (m / n_pairs + 2);
+}
+// ... a chunk of a list can need: a slot per piece of every configuration it can span -- any number of them, whatever its length, since
+// configurations without an entry lie in between (none when a pair list is one piece)
+inline size_t scene_listed_pieces_bound(size_t n_pairs, size_t n_conf) {
+  const uint32_t shares = hfcl::scene_shares(uint32_t(n_pairs));
+  return shares <= 1u ? 0 : n_conf * shares;
+}
+// entries a list of the survivors of `total` queries is first given room for (a longer one is made again in a buffer of its size)
+inline size_t list_capacity_guess(size_t total) { return std::min<size_t>(total, std::max<size_t>(total / 8, 4096)); }

@@ -1,8 +1,8 @@
 #!/bin/bash
 # Build a variant of libhppfcl_amd.so with one or more kernel units recompiled under extra flags (A/B runs on the GPU box select it
 # with HFCL_LIB_PATH).  Usage: tools/build_variant.sh <name> <units, comma-separated> <flags...>
-#   units: host host_batch host_patch host_scene k_gjk32 k_gjk64 k_epa32 k_epa64 k_bvh k_bvhc k_bvhs k_bvhd k_util k_patch k_scene k_cull   (k_gjk / k_epa: both precisions of the unit; k_bvhc / k_bvhs:
-#   the mesh x solid collide() / distance() parts of hfcl_k_bvh.hip)
+#   units: the Makefile's DEVOBJS without "hfcl_" and ".o" -- host, host_scene, k_gjk32, k_cull, k_nearest, ...  (k_gjk / k_epa: both
+#   precisions of the unit; k_bvhc / k_bvhs: the mesh x solid collide() / distance() parts of hfcl_k_bvh.hip)
 # Output: build/ab/lib_<name>.so (git-ignored; travels with gpurun).  The other objects are the in-tree ones (run make first).
 set -e
 name=$1; units=$2; shift 2
@@ -12,7 +12,9 @@ csrc=$root/hpp-fcl_amd/csrc
 mkdir -p $root/build/ab
 objs=""
 pids=""
-for u in host host_batch host_patch host_scene multi k_gjk32 k_gjk64 k_epa32 k_epa64 k_bvh k_bvhc k_bvhs k_bvhd k_util k_patch k_scene k_cull; do
+all_units=$(make -s -C $csrc -pn 2>/dev/null | sed -n 's/^DEVOBJS = //p' | head -1 | sed 's/hfcl_//g; s/\.o//g')
+[ -n "$all_units" ] || { echo "no DEVOBJS in $csrc/Makefile" >&2; exit 1; }
+for u in $all_units; do
   o=hfcl_$u
   if [[ "$units" == *",$u,"* ]]; then
     unitflags=$(make -s -C $csrc -pn 2>/dev/null | sed -n "s/^FLAGS_$u = //p" | head -1)

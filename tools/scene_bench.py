@@ -20,10 +20,12 @@ planner2048x32: scene_planner(2048, 32), 952 320 queries.  L .. W report the sha
 Rows L .. W import the numpy model of the selection from tests/nearest_model.py: the lists of T .. W (the library keeps its own in its
 workspace) and the fp32 (lb - d_f32) / M come from it; no other row depends on tests/.
 
-Every measurement runs in a child process; A and D also run on a library built from the parent commit's sources (--parent-lib, selected
-with HFCL_LIB_PATH in the child), alternating with the build under test.  Warm-up calls first, then --calls timed calls: median, min, max.
+Every measurement runs in a child process.  Up to three arms, each a library selected with HFCL_LIB_PATH in the child, run every row that
+--forms names, in an order that rotates from round to round: "parent", a library built from the parent commit's sources (--parent-lib,
+when the file is there); "new", the build under test; "control", a copy of the build under test (--control-lib) -- the same code loaded
+from another file, so what it loses against "new" is the noise of the run.  Warm-up calls first, then --calls timed calls: median, min, max.
 
-  python tools/scene_bench.py [--parent-lib build/ab/lib_parent.so] [--calls 12] [--rounds 2] [--out profiles/x.json]
+  python tools/scene_bench.py [--parent-lib build/ab/lib_parent.so] [--control-lib build/ab/lib_control.so] [--calls 12] [--rounds 2] [--out profiles/x.json]
   python tools/scene_bench.py --worker --workload cfg5 --forms A,D     (one child; prints one JSON line)
   python tools/scene_bench.py --workloads planner2048,planner2048x32 --forms L,M,N,O,P,Q,R,S,T,U,V,W     (the pruned minimum distance)"""
 import argparse
@@ -242,21 +244,28 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--parent-lib", default=os.path.join(ROOT, "build", "ab", "lib_parent.so"))
+    ap.add_argument("--control-lib", default=None, help="a copy of the library under test: the control arm")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.worker:
         return worker(args)
-    have_parent = os.path.exists(args.parent_lib)
+    arms = [("new", None)]
+    if os.path.exists(args.parent_lib):
+        arms.insert(0, ("parent", os.path.abspath(args.parent_lib)))
+    if args.control_lib:
+        if not os.path.exists(args.control_lib):
+            sys.exit("--control-lib %s: no such file" % args.control_lib)
+        arms.append(("control", os.path.abspath(args.control_lib)))
     results = []
     for workload in args.workloads.split(","):
-        for _ in range(args.rounds):
-            for which in (["parent"] if have_parent else []) + ["new"]:
+        for rnd in range(args.rounds):
+            for which, lib_path in arms[rnd % len(arms):] + arms[:rnd % len(arms)]:
                 env = dict(os.environ)
                 env.pop("HFCL_LIB_PATH", None)
-                if which == "parent":
-                    env["HFCL_LIB_PATH"] = args.parent_lib
+                if lib_path:
+                    env["HFCL_LIB_PATH"] = lib_path
                 cmd = [sys.executable, os.path.abspath(__file__), "--worker", "--workload", workload, "--calls", str(args.calls), "--warmup",
-                       str(args.warmup), "--inflate", str(args.inflate), "--forms", "A,D" if which == "parent" else args.forms]
+                       str(args.warmup), "--inflate", str(args.inflate), "--forms", args.forms]
                 r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
                 line = [x for x in r.stdout.splitlines() if x.startswith("SCENE_BENCH ")]
                 if r.returncode != 0 or not line:  # a child that failed ends the run: nothing more is started on the device
@@ -274,7 +283,7 @@ def main():
         print("\n%s: %d configurations x %d pairs = %d queries, %d objects" % (workload, r0["n_conf"], r0["n_pairs"], r0["queries"], r0["n_objects"]))
         print("| form | build | median ms | min .. max ms (over the runs) |")
         print("|---|---|---|---|")
-        for which in ("parent", "new"):
+        for which in ("parent", "new", "control"):
             for f in "ABCDEFGHIJKLMNOPQRSTUVW":
                 runs = [r["forms"][f] for r in rs if r["build"] == which and f in r["forms"]]
                 if runs:

@@ -1,0 +1,166 @@
+#!/usr/bin/env python3
+"""What the scene entry points launch and compute, for comparing two builds of the library (HFCL_LIB_PATH selects one): every family of
+hfcl_scene_* once -- scene (host and device), boxes, cull, listed, culled, nearest (host and device) --, fp64 then fp32, on
+workloads.scene_planner(64, 16): 6720 queries, far below the size at which a chunk runs split.  scene_chunk and scene_cull_chunk are set
+so that every call runs in three chunks (the listed, culled and nearest forms: a third of their list, read from a call before).
+
+  python tools/scene_launches.py --out DIR        every output of every call as DIR/<nn>_<name>.npy: records, summaries, boxes, lists,
+      conf_begin, counts, min records, n_evaluated, and last_bucket_counts() after every host form
+  rocprofv3 --kernel-trace --output-format csv -d TRACE -- python tools/scene_launches.py --out DIR      (one fresh process per build)
+  python tools/scene_launches.py --compare DIR_A TRACE_A DIR_B TRACE_B
+      the .npy files byte for byte, and the kernel traces: per queue, in dispatch order, (kernel name, grid size, workgroup size)"""
+import argparse
+import csv
+import glob
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def run(out_dir):
+    import torch
+    import __graft_entry__ as ge
+    pkg = ge.load_pkg()
+    abi = pkg.abi
+    os.makedirs(out_dir, exist_ok=True)
+    ps = pkg.workloads.scene_planner(n_conf=64, n_objects=16)
+    table = np.ascontiguousarray(ps.obj_tf)
+    n_conf, G, P = table.shape[0], table.shape[1], len(ps.pairs)
+    total = n_conf * P
+    # 7-float poses of the same table: quaternions from the rotation matrices (generic rotations, no w near 0)
+    R = pkg.geometry.pose_R(table.reshape(-1, 12))
+    w4 = np.sqrt(np.maximum(1.0 + R[:, 0, 0] + R[:, 1, 1] + R[:, 2, 2], 1e-12)) * 2.0
+    quat = np.stack([0.25 * w4, (R[:, 2, 1] - R[:, 1, 2]) / w4, (R[:, 0, 2] - R[:, 2, 0]) / w4, (R[:, 1, 0] - R[:, 0, 1]) / w4], axis=1)
+    pose = np.ascontiguousarray(pkg.geometry.pose_f32_from_quat(quat / np.linalg.norm(quat, axis=1, keepdims=True),
+                                                                table.reshape(-1, 12)[:, 9:]).reshape(n_conf, G, 7))
+    lib = pkg.Library(ps.lib)
+    scene = lib.scene(ps.obj_shape, ps.pairs)
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    creq, dreq = abi.default_collision_request(), abi.default_distance_request()
+    seq = [0]
+
+    def dump(name, *arrays, host=False):
+        for k, a in enumerate(arrays):
+            if a is None:
+                continue
+            if hasattr(a, "cpu"):
+                torch.cuda.synchronize()
+                a = a.cpu().numpy()
+            np.save(os.path.join(out_dir, "%02d_%s_%d.npy" % (seq[0], name, k)), np.ascontiguousarray(a))
+        if host:
+            np.save(os.path.join(out_dir, "%02d_%s_buckets.npy" % (seq[0], name)), np.array(list(lib.last_bucket_counts().values()), dtype=np.int64))
+        seq[0] += 1
+
+    def d_zeros(n, dtype=torch.int32):
+        return torch.zeros(max(int(n), 1), dtype=dtype, device=dev)
+
+    def thirds(work):
+        lib.set_option("scene_chunk", max(1, -(-work // 3)))
+
+    lib.set_option("scene_cull_chunk", -(-total // 3))
+    for f32 in (False, True):
+        p = "f32_" if f32 else "f64_"
+        tab = pose if f32 else table
+        d_tab = torch.from_numpy(tab).to(dev)
+        words = 11 if f32 else 24  # 32-bit words of a record
+        sfx = "_f32" if f32 else ""
+
+        thirds(total)
+        # scene: host, device
+        for kind, req in (("collide", creq), ("distance", dreq)):
+            dump(p + kind, *getattr(scene, kind + sfx)(tab, req), host=True)
+            d_rec, d_sum = d_zeros(total * words), d_zeros(n_conf * 6)
+            getattr(scene, kind + "_device" + sfx)(d_tab, n_conf, req, d_rec, d_sum, stream=st)
+            dump(p + kind + "_device", d_rec, d_sum)
+        if not f32:  # guesses in and out
+            rec, summ, g = scene.collide(tab, creq, want_guess=True)
+            dump(p + "collide_guess_out", rec, summ, g, host=True)
+            dump(p + "collide_guess_in", *scene.collide(tab, creq, guess_in=g), host=True)
+        # boxes
+        dump(p + "boxes", scene.world_aabbs(tab))
+        d_box = d_zeros(n_conf * G * 6, torch.float64)
+        scene.world_aabbs_device(d_tab, n_conf, d_box, f32=f32, stream=st)
+        dump(p + "boxes_device", d_box)
+        # cull: host, device
+        ids, conf_begin = scene.cull(tab, 0.0)
+        dump(p + "cull", ids, conf_begin)
+        d_ids, d_cb, d_n = d_zeros(total, torch.int64), d_zeros(n_conf + 1, torch.int64), d_zeros(1, torch.int64)
+        scene.cull_device(d_tab, n_conf, 0.0, d_ids, total, d_cb, d_n, f32=f32, stream=st)
+        dump(p + "cull_device", d_ids, d_cb, d_n)
+        n_listed = len(ids)
+        thirds(n_listed)
+        # listed (device), culled (host)
+        for kind, req in (("collide", creq), ("distance", dreq)):
+            d_rec, d_sum = d_zeros(n_listed * words), d_zeros(n_conf * 6)
+            getattr(scene, kind + "_listed_device" + sfx)(d_tab, n_conf, d_ids, n_listed, d_cb, req, d_rec, d_sum, stream=st)
+            dump(p + kind + "_listed_device", d_rec, d_sum)
+            dump(p + kind + "_culled", *getattr(scene, kind + "_culled")(tab, 0.0, req, capacity=total), host=True)
+        # nearest: host, device
+        near = scene.nearest_f32 if f32 else scene.nearest
+        _, _, n_eval = near(tab, dreq)
+        thirds(max(n_eval))
+        summ, rec, n_eval = near(tab, dreq)
+        dump(p + "nearest", summ, rec, np.array(n_eval, dtype=np.int64), host=True)
+        d_sum, d_min = d_zeros(n_conf * 6), d_zeros(n_conf * words)
+        n_eval = (scene.nearest_device_f32 if f32 else scene.nearest_device)(d_tab, n_conf, dreq, d_sum, d_min, stream=st)
+        dump(p + "nearest_device", d_sum, d_min, np.array(n_eval, dtype=np.int64))
+    torch.cuda.synchronize()
+    scene.close()
+    lib.close()
+    print("scene_launches: %d calls dumped to %s (%d queries; lists: %d entries)" % (seq[0], out_dir, total, n_listed))
+
+
+def _launches(trace_dir):
+    """[(kernel name, grid, workgroup), ...] per queue in dispatch order; the queues in the order of their first dispatch."""
+    files = glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True)
+    if len(files) != 1:
+        sys.exit("%s: %d kernel traces" % (trace_dir, len(files)))
+    queues = {}
+    with open(files[0]) as f:
+        rows = sorted(csv.DictReader(f), key=lambda r: int(r["Dispatch_Id"]))
+    for r in rows:
+        q = (r.get("Agent_Id"), r.get("Queue_Id"))
+        queues.setdefault(q, []).append((r["Kernel_Name"], tuple(int(r["Grid_Size_" + a]) for a in "XYZ"), tuple(int(r["Workgroup_Size_" + a]) for a in "XYZ")))
+    return list(queues.values())
+
+
+def compare(dir_a, trace_a, dir_b, trace_b):
+    names_a, names_b = (sorted(os.path.basename(x) for x in glob.glob(os.path.join(d, "*.npy"))) for d in (dir_a, dir_b))
+    bad = 0
+    if names_a != names_b or not names_a:
+        print("DIFFERENT file lists: %d against %d files" % (len(names_a), len(names_b)))
+        bad += 1
+    for name in names_a:
+        if name in names_b and open(os.path.join(dir_a, name), "rb").read() != open(os.path.join(dir_b, name), "rb").read():
+            print("DIFFERENT bytes: " + name)
+            bad += 1
+    print("outputs: %d files, %s" % (len(names_a), "byte-identical" if not bad else "%d differences" % bad))
+    la, lb = _launches(trace_a), _launches(trace_b)
+    print("launches: %s against %s per queue" % ([len(q) for q in la], [len(q) for q in lb]))
+    if la != lb:
+        bad += 1
+        for k, (qa, qb) in enumerate(zip(la, lb)):
+            for i, (a, b) in enumerate(zip(qa, qb)):
+                if a != b:
+                    print("queue %d, launch %d: %s against %s" % (k, i, a, b))
+                    break
+    print("launches: " + ("identical (kernel name, grid size, workgroup size; in order within each queue)" if la == lb else "DIFFERENT"))
+    sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--compare", nargs=4, metavar=("DIR_A", "TRACE_A", "DIR_B", "TRACE_B"))
+    a = ap.parse_args()
+    if a.compare:
+        compare(*a.compare)
+    elif a.out:
+        run(a.out)
+    else:
+        ap.error("--out DIR or --compare ...")
