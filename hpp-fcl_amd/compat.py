@@ -682,11 +682,20 @@ def _scene_run(kind, objects, pair_indices, request, transforms, broadphase=Fals
     ctx = _context()
     geoms = [o.collisionGeometry() for o in objects]
     ids = np.array([ctx.add(g) for g in geoms], dtype=np.uint32)
-    pr = np.ascontiguousarray(pair_indices, dtype=np.uint32).reshape(-1, 2)
+    self_pairs = isinstance(broadphase, str) and broadphase == "self"
+    if isinstance(broadphase, str) and not self_pairs:
+        raise ValueError('broadphase: False, True or "self"')
+    pr = np.ascontiguousarray([] if self_pairs or pair_indices is None else pair_indices, dtype=np.uint32).reshape(-1, 2)
     if len(pr) and int(pr.max()) >= len(objects):
         raise ValueError("pair index outside the objects")
     types = np.array([g.getNodeType() for g in geoms], dtype=np.int64)
-    for t1, t2 in (np.unique(types[pr], axis=0) if len(pr) else ()):  # (the distinct kind pairs: a few, whatever the list's length)
+    if self_pairs:  # (any two objects can meet: kinds (a, b) with an object of kind a in front of one of kind b)
+        first = {int(t): int(np.flatnonzero(types == t)[0]) for t in np.unique(types)}
+        last = {int(t): int(np.flatnonzero(types == t)[-1]) for t in np.unique(types)}
+        kinds = [(a, b) for a in first for b in first if first[a] < last[b]]
+    else:
+        kinds = np.unique(types[pr], axis=0) if len(pr) else ()
+    for t1, t2 in kinds:  # (the distinct kind pairs: a few, whatever the list's length)
         if not engine.dll().hfcl_pair_supported(int(t1), int(t2), int(kind == "distance")):
             raise ValueError("%s function between node type %d and node type %d is not yet supported." %
                              ("Distance" if kind == "distance" else "Collision", t1, t2))
@@ -703,6 +712,9 @@ def _scene_run(kind, objects, pair_indices, request, transforms, broadphase=Fals
         if nearest_bound is not None:
             summ, rec, _ = sc.nearest(table, request._abi(), float(nearest_bound))
             g = None
+        elif self_pairs:  # (ids: the listed pairs (i, j) themselves)
+            fn = sc.distance_self if kind == "distance" else sc.collide_self
+            rec, ids, conf_begin, summ, g = fn(table, request._abi(), float(inflate), records=True, want_guess=True)
         elif broadphase:
             fn = sc.distance_culled if kind == "distance" else sc.collide_culled
             rec, ids, conf_begin, summ, g = fn(table, float(inflate), request._abi(), records=True, summary=True, want_guess=True)
@@ -730,7 +742,10 @@ def collide_scene(objects, pair_indices, request, transforms=None, broadphase=Fa
     broadphase=True: per configuration only the listed pairs whose world AABBs (each grown by `inflate` >= 0 on every side) overlap
     are evaluated -- with inflate = 0 the pairs DynamicAABBTreeCollisionManager::collide passes to its callback; the test runs on the
     device (engine.Scene.collide_culled).  results[c] is then a list of (p, CollisionResult) for the surviving pairs, p ascending, and
-    the summaries are folds over those (n_contacts and first_contact as without the broadphase)."""
+    the summaries are folds over those (n_contacts and first_contact as without the broadphase).
+    broadphase="self": no list at all -- `pair_indices` is ignored (None will do): per configuration the device finds every pair (i < j)
+    of `objects` whose grown world AABBs overlap (engine.Scene.collide_self) and evaluates those.  results[c] is a list of
+    ((i, j), CollisionResult), i then j ascending; min_pair / first_contact of a summary are positions in that list."""
     if request.num_max_contacts == 0:
         raise ValueError("Invalid number of max contacts (current value is 0).")
     if request.num_max_contacts > 1 and any(isinstance(o.collisionGeometry(), BVHModelOBBRSS) for o in objects):
@@ -739,7 +754,13 @@ def collide_scene(objects, pair_indices, request, transforms=None, broadphase=Fa
     out = []
     for c in range(n_conf):
         row = []
-        if broadphase:  # (p, result) of configuration c's surviving pairs
+        if broadphase == "self":  # ((i, j), result) of configuration c's touching pairs
+            for k in range(int(conf_begin[c]), int(conf_begin[c + 1])):
+                i, j = int(ids[k][0]), int(ids[k][1])
+                r = CollisionResult()
+                _fill_collision(r, geoms[i], geoms[j], request, rec[k], g[k], None, k - int(conf_begin[c]))
+                row.append(((i, j), r))
+        elif broadphase:  # (p, result) of configuration c's surviving pairs
             for k in range(int(conf_begin[c]), int(conf_begin[c + 1])):
                 p = int(ids[k]) - c * len(pr)
                 r = CollisionResult()
@@ -761,6 +782,8 @@ def distance_scene(objects, pair_indices, request, transforms=None, broadphase=F
     broadphase=True: only the pairs whose world AABBs, each grown by `inflate`, overlap are evaluated (inflate = D / 2 keeps every pair
     whose boxes are within D along each axis: a box-shaped filter, not the manager's traversal with its shrinking bound).  Returns
     (distances, pair indices, summaries): per configuration the array of the surviving pairs' distances and the array of their p.
+    broadphase="self": `pair_indices` is ignored; the device finds every pair (i < j) whose grown boxes overlap (engine.Scene.distance_self);
+    the second item is then per configuration the (k, 2) array of those pairs.
     nearest=True: the clearance alone -- one DistanceResult per configuration, what DistanceCallBackDefault leaves behind after
     DynamicAABBTreeCollisionManager::distance: the closest listed pair's min_distance, o1 / o2, nearest points, normal, b1 / b2.  The pairs
     are pruned on the device by a bound from their world boxes (engine.Scene.nearest); a configuration whose closest pair is farther than
@@ -779,6 +802,9 @@ def distance_scene(objects, pair_indices, request, transforms=None, broadphase=F
             out.append(res)
         return out
     geoms, pr, n_conf, rec, summ, g, ids, conf_begin = _scene_run("distance", objects, pair_indices, request, transforms, broadphase, inflate)
+    if broadphase == "self":  # (distances, (i, j) arrays, summaries): no list; the device finds the pairs whose grown boxes overlap
+        cb = conf_begin.astype(np.int64)
+        return [rec["distance"][cb[c]:cb[c + 1]] for c in range(n_conf)], [ids[cb[c]:cb[c + 1]] for c in range(n_conf)], summ
     if broadphase:
         cb = conf_begin.astype(np.int64)
         return ([rec["distance"][cb[c]:cb[c + 1]] for c in range(n_conf)],

@@ -20,6 +20,7 @@
 #include "hfcl_patch.hpp"
 #include "hfcl_scene.hpp"
 #include "hfcl_cull.hpp"
+#include "hfcl_pairs.hpp"
 #include "hfcl_own.hpp"
 
 __attribute__((visibility("hidden"))) void set_error(const std::string& s);  // the calling thread's hfcl_last_error()
@@ -114,6 +115,12 @@ struct hfcl_options {
   int split = 0;  // 0 = automatic (auto_split), 1 = never, 2 = always (large batches without meshes)
   // Queries per chunk of the cull (option scene_cull_chunk; 0: automatic -- at most 2^22 queries, 16384 workgroup counts for the one-workgroup scan)
   size_t scene_cull_chunk = 0;
+  // hfcl_scene_self_pairs*: scenes of at most this many objects (option scene_pairs_small_max, at most PAIRS_SMALL_MAX) take the
+  // wave-per-configuration form of the all-pairs test, larger ones the tiled form; both write the same bytes.  Measured: 16 objects x 2048
+  // configurations 0.029 against 0.033 ms, 32 x 2048 0.040 against 0.047 - 0.050 ms, 64 x 256 0.051 against 0.027 ms -- a wave walks a
+  // configuration's rows one after the other (profiles/r14_a_scene_pairs.md).  scene_cull_chunk is, for these calls, the rows
+  // (configuration, object) per chunk, in whole row blocks
+  uint32_t scene_pairs_small_max = 32;
   // Queries per chunk of a scene call (option scene_chunk; 0: automatic -- at most 2^21 queries, the call cut into equal chunks).  The chunks of a
   // call run one after the other, and the solvers' kernels are chains of dependent steps that fill the chip only with a large batch: cfg5's
   // 1.07 M queries in chunks of 262144 (the host pipeline's steady chunk) took 5.9 ms against 2.4 ms for the per-pair call on resident arrays,
@@ -300,6 +307,12 @@ struct hfcl_lib {
     DevBuf<double> d_thr;
     DevBuf<void> d_nrec[2];
     DevBuf<void> d_minrec;
+    // the self-collision pairs (hfcl_scene_self_pairs*): counts and offsets of a chunk's rows, the sums of its scan workgroups and the
+    // entries before them, and the list of the host forms
+    DevBuf<uint32_t> d_row_counts, d_row_sums;
+    DevBuf<uint64_t> d_row_offsets, d_row_sum_offsets;
+    size_t rows_cap = 0;
+    DevBuf<uint32_t> d_pair_list;  // (two words an entry)
   } scene;
   // local AABB of every library shape (hfcl_cull.hpp: shape_local_box; BVH models: the box of their vertices), 6 doubles each, rebuilt when
   // shapes or meshes were registered since (hfcl_lib_set_shapes, hfcl_lib_add_bvh)

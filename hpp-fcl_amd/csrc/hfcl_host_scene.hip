@@ -4,6 +4,7 @@
 #include "hfcl_plan.hpp"
 #include "hfcl_nearest.hpp"
 #include "../../include/hppfcl_amd_nearest.h"
+#include "../../include/hppfcl_amd_pairs.h"
 
 // =======================================================================================
 // Scene queries (include/hppfcl_amd.h: hfcl_scene_*): an object -> shape table and a pair list resident on the library's device; a call
@@ -76,7 +77,7 @@ static int scene_batch(hfcl_lib* lib, const uint32_t* s1, const uint32_t* s2, co
 // rule lets through.)
 template <typename T>
 static int scene_validate_core(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, size_t hfcl_scene::*nothing_if_zero,
-                               size_t& total) {
+                               size_t& total, bool own_list = true) {
   total = 0;
   if (!s) {
     set_error(std::string(who) + ": null scene");
@@ -91,7 +92,12 @@ static int scene_validate_core(const char* who, const hfcl_scene* s, const void*
     set_error(std::string(who) + ": null pose table");
     return HFCL_ERR_INVALID_ARGUMENT;
   }
-  if ((s->n_pairs && n_conf > ~size_t(0) / s->n_pairs) || n_conf > ~size_t(0) / (s->n_objects * SceneTypes<T>::WIDTH * sizeof(T))) {
+  if (n_conf > ~size_t(0) / (s->n_objects * SceneTypes<T>::WIDTH * sizeof(T))) {
+    set_error(std::string(who) + ": the pose table's size overflows");
+    return HFCL_ERR_LIMIT;
+  }
+  if (!own_list) return HFCL_OK;  // (the calls that make or take a list of pairs: the scene's own plays no part, total stays 0)
+  if (s->n_pairs && n_conf > ~size_t(0) / s->n_pairs) {
     set_error(std::string(who) + ": n_conf * n_pairs overflows");
     return HFCL_ERR_LIMIT;
   }
@@ -102,7 +108,8 @@ static int scene_validate_core(const char* who, const hfcl_scene* s, const void*
 // null one: "null request", setup_collide / setup_distance) and the outputs are looked at before the scene's state
 template <typename T>
 static int scene_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, const hfcl_collision_request* creq,
-                          const hfcl_distance_request* dreq, const void* out, const void* summary, size_t& total) {
+                          const hfcl_distance_request* dreq, const void* out, const void* summary, size_t& total,
+                          size_t hfcl_scene::*nothing_if_zero = &hfcl_scene::n_pairs) {
   total = 0;
   if (s) {
     QParams<T> q;
@@ -114,12 +121,18 @@ static int scene_validate(const char* who, const hfcl_scene* s, const void* tabl
       return HFCL_ERR_INVALID_ARGUMENT;
     }
   }
-  return scene_validate_core<T>(who, s, table, n_conf, &hfcl_scene::n_pairs, total);
+  return scene_validate_core<T>(who, s, table, n_conf, nothing_if_zero, total, nothing_if_zero == &hfcl_scene::n_pairs);
 }
 // what the cull calls refuse before any work; total: n_conf * n_pairs (0: no query)
 template <typename T>
 static int cull_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, size_t& total) {
   return scene_validate_core<T>(who, s, table, n_conf, &hfcl_scene::n_objects, total);
+}
+// ... the calls that make the list of pairs themselves (hfcl_scene_self_pairs*): the scene's own list is not looked at
+template <typename T>
+static int self_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf) {
+  size_t total;
+  return scene_validate_core<T>(who, s, table, n_conf, &hfcl_scene::n_objects, total, false);
 }
 
 // workspace of chunks of up to m queries; recs: how many of the two record buffers; pieces: fold partials (0: none)
@@ -143,13 +156,24 @@ static int scene_workspace(hfcl_lib* lib, size_t m, int recs, bool gin, int gout
 }
 // A list of flat queries on the device, as hfcl_scene_cull_device leaves it: ascending ids, conf_begin theirs.  Where a function takes a
 // pointer to one, nullptr is the flat range itself.
+// The other flavour (hfcl_scene_self_pairs_device leaves it): d_ids == nullptr, the entries are the pairs (i, j) themselves (d_pairs, two
+// words an entry), the scene's own pair list plays no part, an entry's pair index in the summaries is its rank in its configuration, and a
+// configuration has at most `shares` fold pieces (hfcl_pairs.hpp: pairs_shares).
 struct SceneList {
   const uint64_t* d_ids;
   const uint64_t* d_conf_begin;
   size_t n_conf;
+  const uint32_t* d_pairs = nullptr;
+  uint32_t shares = 0;
+  bool ranked() const { return d_pairs != nullptr; }
 };
+// fold pieces of a configuration of a call
+static uint32_t scene_list_shares(const hfcl_scene* s, const SceneList* list) {
+  return list && list->ranked() ? list->shares : scene_shares(uint32_t(s->n_pairs));
+}
 // fold partials of a call in chunks of `chunk`
 static size_t scene_pieces(const hfcl_scene* s, const SceneList* list, size_t chunk) {
+  if (list && list->ranked()) return list->shares <= 1u ? 0 : list->n_conf * size_t(list->shares);
   return list ? scene_listed_pieces_bound(s->n_pairs, list->n_conf) : scene_pieces_bound(s->n_pairs, chunk);
 }
 
@@ -169,20 +193,24 @@ static int scene_chunk_run(hfcl_scene* s, const void* d_table, const SceneList* 
   ea.n_objects = s->n_objects;
   ea.n_pairs = uint32_t(s->n_pairs);
   ea.q0 = list ? 0 : k0;  // (a list's rows name their queries)
-  scene_query(ea.q0, ea.n_pairs, ea.c0, ea.p0);
+  ea.c0 = 0;
+  ea.p0 = 0;
+  if (!list || !list->ranked()) scene_query(ea.q0, ea.n_pairs, ea.c0, ea.p0);
   ea.m = uint32_t(m);
   ea.s1 = w.d_s1;
   ea.s2 = w.d_s2;
   ea.tf1 = w.d_tf1;
   ea.tf2 = w.d_tf2;
-  if (list)
+  if (list && list->ranked())
+    launch_scene_expand_pairs(st, ea, list->d_pairs, list->d_conf_begin, list->n_conf, k0, f32, max_blocks);
+  else if (list)
     launch_scene_expand_listed(st, ea, list->d_ids + k0, f32, max_blocks);
   else
     launch_scene_expand(st, ea, f32, max_blocks);
   const int rc = scene_batch(lib, w.d_s1, w.d_s2, w.d_tf1, w.d_tf2, m, creq, dreq, d_rec, d_gin, d_gout, st);
   if (rc || !d_summary) return rc;
   const double margin = creq ? creq->security_margin : 0.0;
-  hfcl_scene_summary* partials = scene_shares(ea.n_pairs) > 1u ? w.d_partials.get() : nullptr;
+  hfcl_scene_summary* partials = scene_list_shares(s, list) > 1u ? w.d_partials.get() : nullptr;
   if (list) {
     SceneFoldListedArgs fa;
     fa.rec = d_rec;
@@ -196,7 +224,11 @@ static int scene_chunk_run(hfcl_scene* s, const void* d_table, const SceneList* 
     fa.summary = d_summary;
     fa.partials = partials;
     fa.n_conf = list->n_conf;
-    launch_scene_fold_listed(st, fa, f32, max_blocks);
+    fa.shares = scene_list_shares(s, list);
+    if (list->ranked())
+      launch_scene_fold_ranked(st, fa, list->shares, f32, max_blocks);
+    else
+      launch_scene_fold_listed(st, fa, f32, max_blocks);
   } else {
     SceneFoldArgs fa;
     fa.rec = d_rec;
@@ -414,15 +446,16 @@ static void cull_chunks(CullArgs& a, size_t chunk, F&& per_chunk) {
 // A list whose length is known only afterwards: make() enqueues its making into `ids` (as large as it is then) on st, the count at d_count
 // is read back -- 8 bytes, st waited for --, and a list that outgrew the buffer is made once more in one of its size.  want_ids = false:
 // the count alone.
-template <typename Make>
-static int list_and_count(DevBuf<uint64_t>& ids, bool want_ids, const uint64_t* d_count, hipStream_t st, uint64_t& n, Make&& make) {
+// (words: the buffer's elements per list entry -- 1 for a list of queries, 2 for a list of pairs)
+template <typename W, typename Make>
+static int list_and_count(DevBuf<W>& ids, bool want_ids, const uint64_t* d_count, hipStream_t st, uint64_t& n, Make&& make, size_t words = 1) {
   for (int attempt = 0; attempt < 2; ++attempt) {
     const int rc = make();
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(&n, d_count, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (!want_ids || n <= ids.capacity()) break;
-    HIP_TRY(ids.grow(size_t(n)));
+    if (!want_ids || n <= ids.capacity() / words) break;
+    HIP_TRY(ids.grow(size_t(n) * words));
   }
   return HFCL_OK;
 }
@@ -596,6 +629,211 @@ static int scene_listed_device(const char* who, hfcl_scene* s, const void* d_tab
   return scene_chunks_device<T>(s, d_table, &list, n_listed, creq, dreq, d_out, d_summary, d_gin, d_gout, st, counts);
 }
 
+// ---------------------------------------------------------------------------------------
+// The self-collision pairs per configuration (include/hppfcl_amd_pairs.h: hfcl_scene_self_pairs*), and the scene calls on such a list
+// (hfcl_scene_*_pairs_device*, hfcl_scene_*_self).  hfcl_k_pairs.hip has the kernels, hfcl_pairs.hpp the arithmetic.
+// ---------------------------------------------------------------------------------------
+// every entry point of hppfcl_amd_pairs.h, before anything else
+static int pairs_need_device() {
+  int nd = 0;
+  if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) {
+    set_error("no HIP device available (hipGetDeviceCount): the engine has no CPU fallback");
+    return HFCL_ERR_NO_DEVICE;
+  }
+  return HFCL_OK;
+}
+// a scan workgroup adds the counts of PAIRS_SCAN_BLOCK rows in 32 bits: a row has fewer than n_objects entries
+constexpr size_t PAIRS_MAX_OBJECTS = (size_t(1) << 32) / PAIRS_SCAN_BLOCK;
+static int self_pairs_limits(const char* who, const hfcl_scene* s) {
+  if (s->n_objects > PAIRS_MAX_OBJECTS) {
+    set_error(std::string(who) + ": the all-pairs test takes scenes of at most " + std::to_string(PAIRS_MAX_OBJECTS) + " objects");
+    return HFCL_ERR_LIMIT;
+  }
+  return HFCL_OK;
+}
+// summaries name a pair by its rank in its configuration, in 32 bits
+static int pairs_rank_limit(const char* who, uint64_t n_listed, size_t n_objects) {
+  if (pairs_shares(n_listed, n_objects) > 0xFFFFFFFFull / SCENE_FOLD_SHARE) {
+    set_error(std::string(who) + ": a configuration could hold 2^32 entries or more; summaries rank an entry in 32 bits");
+    return HFCL_ERR_LIMIT;
+  }
+  return HFCL_OK;
+}
+// counts, offsets and scan sums of a chunk of `rows` rows, the running count
+static int pairs_chunk_buffers(hfcl_lib* lib, size_t rows) {
+  hfcl_lib::SceneWs& w = lib->scene;
+  if (rows > w.rows_cap) {
+    reset_all(w.d_row_counts, w.d_row_offsets, w.d_row_sums, w.d_row_sum_offsets);
+    w.rows_cap = 0;
+    const size_t n_sums = (rows + PAIRS_SCAN_BLOCK - 1) / PAIRS_SCAN_BLOCK;
+    HIP_TRY(w.d_row_counts.grow(rows));
+    HIP_TRY(w.d_row_offsets.grow(rows));
+    HIP_TRY(w.d_row_sums.grow(n_sums));
+    HIP_TRY(w.d_row_sum_offsets.grow(n_sums));
+    w.rows_cap = rows;
+  }
+  HIP_TRY(w.d_running.grow(2));
+  return HFCL_OK;
+}
+
+// The list of the whole table on st: the pairs (below `capacity`), conf_begin, the count.  Nothing is read back.
+template <typename T>
+static int self_pairs_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, double inflate, uint32_t* d_pairs, size_t capacity,
+                             uint64_t* d_conf_begin, uint64_t* d_n_listed, hipStream_t st) {
+  int rc = self_validate<T>(who, s, d_table, n_conf);
+  if (rc) return rc;
+  rc = cull_check_inflate(who, inflate);
+  if (rc) return rc;
+  if (!d_n_listed) {
+    set_error(std::string(who) + ": null count");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  rc = self_pairs_limits(who, s);
+  if (rc) return rc;
+  hfcl_lib* lib = s->lib;
+  HIP_TRY(hipSetDevice(lib->device));
+  if (n_conf == 0 || s->n_objects < 2) {  // no pair: an empty list
+    HIP_TRY(hipMemsetAsync(d_n_listed, 0, sizeof(uint64_t), st));
+    if (d_conf_begin) HIP_TRY(hipMemsetAsync(d_conf_begin, 0, (n_conf + 1) * sizeof(uint64_t), st));
+    return HFCL_OK;
+  }
+  rc = ensure_local_boxes(lib);
+  if (rc) return rc;
+  hfcl_lib::SceneWs& w = lib->scene;
+  const uint32_t n = uint32_t(s->n_objects);
+  const bool small = n <= std::min(lib->opt.scene_pairs_small_max, PAIRS_SMALL_MAX);
+  const PairsGeometry geo = pairs_geometry(n, small);
+  const uint64_t n_blocks = uint64_t(n_conf) * geo.blocks_per_conf;
+  const uint64_t per = pairs_chunk_blocks(geo, n_blocks, lib->opt.scene_cull_chunk);
+  const size_t conf_per_chunk = std::min<size_t>(n_conf, size_t(per / geo.blocks_per_conf) + 2);
+  HIP_TRY(w.d_boxes.grow(conf_per_chunk * n * 6));
+  rc = pairs_chunk_buffers(lib, size_t(std::min<uint64_t>(per * geo.rows_per_block, uint64_t(n_conf) * n)));
+  if (rc) return rc;
+  constexpr bool f32 = std::is_same<T, float>::value;
+  PairsArgs a;
+  a.boxes = w.d_boxes;
+  a.n_objects = n;
+  a.rows_per_block = geo.rows_per_block;
+  a.blocks_per_conf = geo.blocks_per_conf;
+  a.small = small ? 1 : 0;
+  a.total_rows = uint64_t(n_conf) * n;
+  a.n_conf = n_conf;
+  a.inflate = inflate;
+  a.row_counts = w.d_row_counts;
+  a.row_offsets = w.d_row_offsets;
+  a.sums = w.d_row_sums;
+  a.sum_offsets = w.d_row_sum_offsets;
+  a.running = w.d_running;
+  a.pairs = d_pairs;
+  a.capacity = d_pairs ? capacity : 0;
+  a.conf_begin = d_conf_begin;
+  a.n_listed = d_n_listed;
+  for (uint64_t g0 = 0; g0 < n_blocks; g0 += per) {  // the boxes of the configurations the chunk touches, then the chunk
+    a.g0 = g0;
+    a.n_blocks = uint32_t(std::min<uint64_t>(per, n_blocks - g0));
+    a.row0 = pairs_block_row(geo, g0);
+    a.n_rows = uint32_t(pairs_block_row(geo, g0 + a.n_blocks) - a.row0);
+    a.first = g0 == 0 ? 1 : 0;
+    a.c_box0 = g0 / geo.blocks_per_conf;
+    const uint64_t c_last = (g0 + a.n_blocks - 1) / geo.blocks_per_conf;
+    const char* rows = static_cast<const char*>(d_table) + a.c_box0 * n * SceneTypes<T>::WIDTH * sizeof(T);
+    launch_cull_aabbs(st, rows, f32, s->d_object_shape, lib->d_local_boxes, n, (c_last - a.c_box0 + 1) * n, w.d_boxes);
+    launch_pairs_chunk(st, a);
+  }
+  HIP_TRY(hipGetLastError());
+  return HFCL_OK;
+}
+
+// entries a list of self pairs of `rows` rows is first given room for (a longer one is made again in a buffer of its size)
+static size_t pairs_capacity_guess(size_t rows) { return std::max<size_t>(16 * rows, 4096); }
+// The list of a table that is on the device into the library's own (w.d_pair_list, w.d_conf_begin), and the one read-back: the count.
+template <typename T>
+static int self_pairs_into_workspace(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, double inflate, bool want_pairs,
+                                     uint64_t& n_listed) {
+  hfcl_lib* lib = s->lib;
+  hfcl_lib::SceneWs& w = lib->scene;
+  HIP_TRY(w.d_conf_begin.grow(n_conf + 1));
+  HIP_TRY(w.d_running.grow(2));
+  if (want_pairs) HIP_TRY(w.d_pair_list.grow(2 * pairs_capacity_guess(n_conf * s->n_objects)));
+  return list_and_count(w.d_pair_list, want_pairs, w.d_running + 1, w.s_cmp, n_listed, [&]() {
+    return self_pairs_device<T>(who, s, d_table, n_conf, inflate, want_pairs ? w.d_pair_list.get() : nullptr, w.d_pair_list.capacity() / 2,
+                                w.d_conf_begin, w.d_running + 1, w.s_cmp);
+  }, 2);
+}
+
+template <typename T>
+static int self_pairs_host(const char* who, hfcl_scene* s, const void* table, size_t n_conf, double inflate, uint32_t* pairs, size_t capacity,
+                           uint64_t* conf_begin, size_t* n_listed) {
+  int rc = self_validate<T>(who, s, table, n_conf);
+  if (!rc) rc = cull_check_inflate(who, inflate);
+  if (!rc && !n_listed) {
+    set_error(std::string(who) + ": null count");
+    rc = HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (!rc) rc = self_pairs_limits(who, s);
+  if (rc) return rc;
+  *n_listed = 0;
+  if (n_conf == 0 || s->n_objects < 2) {
+    if (conf_begin) memset(conf_begin, 0, (n_conf + 1) * sizeof(uint64_t));
+    return HFCL_OK;
+  }
+  hfcl_lib* lib = s->lib;
+  hfcl_lib::SceneWs& w = lib->scene;
+  HIP_TRY(hipSetDevice(lib->device));
+  rc = scene_host_stream(w);
+  if (!rc) rc = scene_table_in(w, table, n_conf * s->n_objects * SceneTypes<T>::WIDTH * sizeof(T));
+  uint64_t n = 0;
+  if (!rc) rc = self_pairs_into_workspace<T>(who, s, w.d_table, n_conf, inflate, pairs != nullptr, n);
+  if (rc) {
+    hipStreamSynchronize(w.s_cmp);
+    return rc;
+  }
+  *n_listed = size_t(n);
+  if (pairs && capacity < n) {
+    set_error(std::string(who) + ": " + std::to_string(n) + " pairs are listed, the list holds " + std::to_string(capacity));
+    return HFCL_ERR_LIMIT;
+  }
+  if (pairs && n) HIP_TRY(hipMemcpyAsync(pairs, w.d_pair_list, n * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, w.s_cmp));
+  if (conf_begin) HIP_TRY(hipMemcpyAsync(conf_begin, w.d_conf_begin, (n_conf + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
+  HIP_TRY(hipStreamSynchronize(w.s_cmp));
+  return HFCL_OK;
+}
+
+// The device form on a list of pairs.  The list is not checked: i < j < n_objects, conf_begin its spans -- as hfcl_scene_self_pairs_device
+// leaves them.
+template <typename T>
+static int scene_pairs_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const uint32_t* d_pairs, size_t n_listed,
+                              const uint64_t* d_conf_begin, const hfcl_collision_request* creq, const hfcl_distance_request* dreq,
+                              typename SceneTypes<T>::R* d_out, hfcl_scene_summary* d_summary, const hfcl_guess* d_gin, hfcl_guess* d_gout,
+                              hipStream_t st) {
+  size_t total;
+  int rc = scene_validate<T>(who, s, d_table, n_conf, creq, dreq, d_out, d_summary, total, &hfcl_scene::n_objects);
+  if (rc) return rc;
+  if (n_conf == 0 || s->n_objects == 0) {
+    if (n_listed) {
+      set_error(std::string(who) + ": list entries without a configuration or an object");
+      return HFCL_ERR_INVALID_ARGUMENT;
+    }
+    return HFCL_OK;
+  }
+  if (n_listed && (!d_pairs || !d_conf_begin)) {
+    set_error(std::string(who) + ": null list / conf_begin");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (d_summary && (rc = pairs_rank_limit(who, n_listed, s->n_objects))) return rc;
+  hfcl_lib* lib = s->lib;
+  HIP_TRY(hipSetDevice(lib->device));
+  if (d_summary) launch_scene_summary_init(st, d_summary, n_conf, lib->n_cus * 16);
+  if (!n_listed) {
+    HIP_TRY(hipGetLastError());
+    return HFCL_OK;
+  }
+  SceneList list{nullptr, d_conf_begin, n_conf};
+  list.d_pairs = d_pairs;
+  list.shares = uint32_t(pairs_shares(n_listed, s->n_objects));
+  return scene_chunks_device<T>(s, d_table, &list, n_listed, creq, dreq, d_out, d_summary, d_gin, d_gout, st);
+}
+
 // what the culled host forms (hfcl_scene_*_culled) add to scene_host
 struct SceneCull {
   double inflate;
@@ -603,6 +841,9 @@ struct SceneCull {
   uint64_t* query_ids_out;   // nullptr or out_capacity
   uint64_t* conf_begin_out;  // nullptr or n_conf + 1
   size_t* n_listed;
+  // the self forms (hfcl_scene_*_self): the list is made by hfcl_scene_self_pairs_device, not culled from the scene's own; query_ids_out unused
+  bool self = false;
+  uint32_t* pairs_out = nullptr;  // nullptr or 2 x out_capacity
 };
 
 // Host form.  The object table goes in once; chunk k computes on one stream while chunk k - 1's records leave on another from the other of
@@ -614,7 +855,10 @@ static int scene_host(const char* who, hfcl_scene* s, const void* table, size_t 
                       hfcl_guess* gout, const SceneCull* cull = nullptr) {
   using R = typename SceneTypes<T>::R;
   size_t total;
-  int rc = scene_validate<T>(who, s, table, n_conf, creq, dreq, out, summary, total);
+  const bool self = cull && cull->self;
+  int rc = scene_validate<T>(who, s, table, n_conf, creq, dreq, out, summary, total, self ? &hfcl_scene::n_objects : &hfcl_scene::n_pairs);
+  if (!rc && self) rc = self_pairs_limits(who, s);
+  if (!rc && self) total = n_conf && s->n_objects >= 2 ? n_conf * s->n_objects : 0;  // (rows: what the list is made from)
   if (!rc && cull) {
     rc = cull_check_inflate(who, cull->inflate);
     if (!rc && !cull->n_listed) {
@@ -644,23 +888,32 @@ static int scene_host(const char* who, hfcl_scene* s, const void* table, size_t 
   if (cull) {  // the table goes in, the cull runs, the count comes back: 8 bytes, the one read-back before the narrow phase
     rc = scene_table_in(w, table, table_bytes);
     uint64_t n = 0;
-    if (!rc) rc = cull_into_workspace<T>(who, s, w.d_table, n_conf, total, cull->inflate, true, n);
+    if (!rc)
+      rc = self ? self_pairs_into_workspace<T>(who, s, w.d_table, n_conf, cull->inflate, true, n)
+                : cull_into_workspace<T>(who, s, w.d_table, n_conf, total, cull->inflate, true, n);
     if (rc) {
       hipStreamSynchronize(w.s_cmp);
       return rc;
     }
     *cull->n_listed = size_t(n);
-    if ((out || gout || cull->query_ids_out) && cull->out_capacity < n) {
+    if ((out || gout || cull->query_ids_out || cull->pairs_out) && cull->out_capacity < n) {
       set_error(std::string(who) + ": " + std::to_string(n) + " queries survive, the outputs hold " + std::to_string(cull->out_capacity));
       return HFCL_ERR_LIMIT;
     }
     if (!n) return nothing_listed();
+    if (self && summary && (rc = pairs_rank_limit(who, n, s->n_objects))) return rc;
     if (cull->query_ids_out) HIP_TRY(hipMemcpyAsync(cull->query_ids_out, w.d_ids, n * sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
+    if (cull->pairs_out) HIP_TRY(hipMemcpyAsync(cull->pairs_out, w.d_pair_list, n * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, w.s_cmp));
     if (cull->conf_begin_out)
       HIP_TRY(hipMemcpyAsync(cull->conf_begin_out, w.d_conf_begin, (n_conf + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
     work = size_t(n);
   }
-  const SceneList listed{w.d_ids, w.d_conf_begin, n_conf};
+  SceneList listed{w.d_ids, w.d_conf_begin, n_conf};
+  if (self) {
+    listed.d_ids = nullptr;
+    listed.d_pairs = w.d_pair_list;
+    listed.shares = uint32_t(pairs_shares(work, s->n_objects));
+  }
   const SceneList* list = cull ? &listed : nullptr;
   const size_t chunk = scene_chunk_size(work, lib->opt.scene_chunk);
   const size_t n_chunks = (work + chunk - 1) / chunk;
@@ -1086,6 +1339,95 @@ int hfcl_scene_distance_culled_f32(hfcl_scene* s, const float* object_pose, size
   const SceneCull cull{inflate, out_capacity, query_ids_out, conf_begin_out, n_listed};
   return scene_host<float>("hfcl_scene_distance_culled_f32", s, object_pose, n_conf, nullptr, req, out, summary, nullptr, nullptr, &cull);
 }
+
+// ---- the self-collision pairs per configuration (include/hppfcl_amd_pairs.h) ---------------------------------------------------------
+#define PAIRS_ENTRY                                     \
+  if (const int no_device = pairs_need_device()) return no_device
+int hfcl_scene_self_pairs(hfcl_scene* s, const double* object_tf, size_t n_conf, double inflate, uint32_t* pairs, size_t capacity,
+                          uint64_t* conf_begin, size_t* n_listed) {
+  PAIRS_ENTRY;
+  return self_pairs_host<double>("hfcl_scene_self_pairs", s, object_tf, n_conf, inflate, pairs, capacity, conf_begin, n_listed);
+}
+int hfcl_scene_self_pairs_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, double inflate, uint32_t* pairs, size_t capacity,
+                              uint64_t* conf_begin, size_t* n_listed) {
+  PAIRS_ENTRY;
+  return self_pairs_host<float>("hfcl_scene_self_pairs_f32", s, object_pose, n_conf, inflate, pairs, capacity, conf_begin, n_listed);
+}
+int hfcl_scene_self_pairs_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, double inflate, uint32_t* d_pairs, size_t capacity,
+                                 uint64_t* d_conf_begin, uint64_t* d_n_listed, void* stream) {
+  PAIRS_ENTRY;
+  return self_pairs_device<double>("hfcl_scene_self_pairs_device", s, d_object_tf, n_conf, inflate, d_pairs, capacity, d_conf_begin, d_n_listed,
+                                   (hipStream_t)stream);
+}
+int hfcl_scene_self_pairs_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, double inflate, uint32_t* d_pairs, size_t capacity,
+                                     uint64_t* d_conf_begin, uint64_t* d_n_listed, void* stream) {
+  PAIRS_ENTRY;
+  return self_pairs_device<float>("hfcl_scene_self_pairs_device_f32", s, d_object_pose, n_conf, inflate, d_pairs, capacity, d_conf_begin,
+                                  d_n_listed, (hipStream_t)stream);
+}
+int hfcl_scene_collide_pairs_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const uint32_t* d_pairs, size_t n_listed,
+                                    const uint64_t* d_conf_begin, const hfcl_collision_request* req, hfcl_result* d_out,
+                                    hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in, hfcl_guess* d_guess_out, void* stream) {
+  PAIRS_ENTRY;
+  return scene_pairs_device<double>("hfcl_scene_collide_pairs_device", s, d_object_tf, n_conf, d_pairs, n_listed, d_conf_begin, req, nullptr, d_out,
+                                    d_summary, d_guess_in, d_guess_out, (hipStream_t)stream);
+}
+int hfcl_scene_distance_pairs_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const uint32_t* d_pairs, size_t n_listed,
+                                     const uint64_t* d_conf_begin, const hfcl_distance_request* req, hfcl_result* d_out,
+                                     hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in, hfcl_guess* d_guess_out, void* stream) {
+  PAIRS_ENTRY;
+  return scene_pairs_device<double>("hfcl_scene_distance_pairs_device", s, d_object_tf, n_conf, d_pairs, n_listed, d_conf_begin, nullptr, req, d_out,
+                                    d_summary, d_guess_in, d_guess_out, (hipStream_t)stream);
+}
+int hfcl_scene_collide_pairs_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, const uint32_t* d_pairs, size_t n_listed,
+                                        const uint64_t* d_conf_begin, const hfcl_collision_request* req, hfcl_result_f32* d_out,
+                                        hfcl_scene_summary* d_summary, void* stream) {
+  PAIRS_ENTRY;
+  return scene_pairs_device<float>("hfcl_scene_collide_pairs_device_f32", s, d_object_pose, n_conf, d_pairs, n_listed, d_conf_begin, req, nullptr,
+                                   d_out, d_summary, nullptr, nullptr, (hipStream_t)stream);
+}
+int hfcl_scene_distance_pairs_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, const uint32_t* d_pairs, size_t n_listed,
+                                         const uint64_t* d_conf_begin, const hfcl_distance_request* req, hfcl_result_f32* d_out,
+                                         hfcl_scene_summary* d_summary, void* stream) {
+  PAIRS_ENTRY;
+  return scene_pairs_device<float>("hfcl_scene_distance_pairs_device_f32", s, d_object_pose, n_conf, d_pairs, n_listed, d_conf_begin, nullptr, req,
+                                   d_out, d_summary, nullptr, nullptr, (hipStream_t)stream);
+}
+static SceneCull self_form(double inflate, size_t out_capacity, uint32_t* pairs_out, uint64_t* conf_begin_out, size_t* n_listed) {
+  SceneCull cull{inflate, out_capacity, nullptr, conf_begin_out, n_listed};
+  cull.self = true;
+  cull.pairs_out = pairs_out;
+  return cull;
+}
+int hfcl_scene_collide_self(hfcl_scene* s, const double* object_tf, size_t n_conf, double inflate, const hfcl_collision_request* req,
+                            hfcl_result* out, size_t out_capacity, uint32_t* pairs_out, uint64_t* conf_begin_out, hfcl_scene_summary* summary,
+                            const hfcl_guess* guess_in, hfcl_guess* guess_out, size_t* n_listed) {
+  PAIRS_ENTRY;
+  const SceneCull cull = self_form(inflate, out_capacity, pairs_out, conf_begin_out, n_listed);
+  return scene_host<double>("hfcl_scene_collide_self", s, object_tf, n_conf, req, nullptr, out, summary, guess_in, guess_out, &cull);
+}
+int hfcl_scene_distance_self(hfcl_scene* s, const double* object_tf, size_t n_conf, double inflate, const hfcl_distance_request* req,
+                             hfcl_result* out, size_t out_capacity, uint32_t* pairs_out, uint64_t* conf_begin_out, hfcl_scene_summary* summary,
+                             const hfcl_guess* guess_in, hfcl_guess* guess_out, size_t* n_listed) {
+  PAIRS_ENTRY;
+  const SceneCull cull = self_form(inflate, out_capacity, pairs_out, conf_begin_out, n_listed);
+  return scene_host<double>("hfcl_scene_distance_self", s, object_tf, n_conf, nullptr, req, out, summary, guess_in, guess_out, &cull);
+}
+int hfcl_scene_collide_self_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, double inflate, const hfcl_collision_request* req,
+                                hfcl_result_f32* out, size_t out_capacity, uint32_t* pairs_out, uint64_t* conf_begin_out,
+                                hfcl_scene_summary* summary, size_t* n_listed) {
+  PAIRS_ENTRY;
+  const SceneCull cull = self_form(inflate, out_capacity, pairs_out, conf_begin_out, n_listed);
+  return scene_host<float>("hfcl_scene_collide_self_f32", s, object_pose, n_conf, req, nullptr, out, summary, nullptr, nullptr, &cull);
+}
+int hfcl_scene_distance_self_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, double inflate, const hfcl_distance_request* req,
+                                 hfcl_result_f32* out, size_t out_capacity, uint32_t* pairs_out, uint64_t* conf_begin_out,
+                                 hfcl_scene_summary* summary, size_t* n_listed) {
+  PAIRS_ENTRY;
+  const SceneCull cull = self_form(inflate, out_capacity, pairs_out, conf_begin_out, n_listed);
+  return scene_host<float>("hfcl_scene_distance_self_f32", s, object_pose, n_conf, nullptr, req, out, summary, nullptr, nullptr, &cull);
+}
+#undef PAIRS_ENTRY
 
 // ---- the per-configuration minimum distance with box-bound pruning -----------------------------------------------------------------
 int hfcl_scene_nearest(hfcl_scene* s, const double* object_tf, size_t n_conf, const hfcl_distance_request* req, double upper_bound,

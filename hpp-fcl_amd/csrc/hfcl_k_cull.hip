@@ -12,15 +12,19 @@
 //                         Three launches in stream order; no atomics, no kernel waits for another workgroup, the list is ascending
 //                         and the same bytes however the range is cut.
 //   k_scene_expand_listed64<ALIGNED> / 32   k_scene_expand64 / 32 (hfcl_k_scene.hip) with q read from the list: same lanes, same vectors
+//   k_scene_expand_pairs64<ALIGNED> / 32    the same with (i, j) read from a list of explicit pairs (hfcl_scene_*_pairs_device*); the
+//                         configuration of an entry is the span of conf_begin that holds it: found once per wave for its first row, a few
+//                         steps forward per lane, the search again for a lane whose entry lies further on (hfcl_pairs.hpp)
 //   k_scene_summary_init  every configuration's summary to the value of a configuration without records
-//   k_scene_fold_listed<R>  a wave per (configuration the chunk touches, piece of SCENE_FOLD_SHARE of its records), lanes stride the
+//   k_scene_fold_listed<R, RANKED>  a wave per (configuration the chunk touches, piece of SCENE_FOLD_SHARE of its records), lanes stride the
 //                         piece, butterfly, then lane 0 merges into the stored summary (lists of at most one piece per configuration)
-//                         or writes a partial for
+//                         or writes a partial for.  RANKED (lists of explicit pairs): a record's pair index is its rank in its configuration
 //   k_scene_fold_listed_combine   a wave per configuration folds its pieces' partials and merges into the stored summary.
 //                         The merge is commutative and associative on disjoint sets of pairs: the summaries do not depend on the chunks.
 #include "hfcl_dev.hpp"
 #include "hfcl_launch.hpp"
 #include "hfcl_cull.hpp"
+#include "hfcl_pairs.hpp"
 
 template <bool F32>
 __global__ void __launch_bounds__(256) k_cull_aabbs(const void* __restrict__ object_tf, const uint32_t* __restrict__ object_shape,
@@ -214,6 +218,84 @@ __global__ void __launch_bounds__(256) k_scene_expand_listed32(SceneExpandArgs a
   }
 }
 
+// the configuration of list entry k0 + row; c_wave: that of the wave's first row (the same in every lane)
+static __device__ __forceinline__ uint64_t pairs_entry_conf(const uint64_t* __restrict__ conf_begin, uint64_t n_conf, uint64_t c_wave, uint64_t k) {
+  return pairs_conf_from(conf_begin, n_conf, c_wave, k);
+}
+// ... of the first row any lane of this wave has in this trip: lane 0's row (the rows ascend with the lanes)
+// (HFCL_PAIRS_LANE_SEARCH: a variant build in which every lane searches for itself -- the form this one was measured against,
+// profiles/r14_a_scene_pairs.md)
+static __device__ __forceinline__ uint64_t pairs_wave_conf(const uint64_t* __restrict__ conf_begin, uint64_t n_conf, uint64_t k_lane) {
+#ifdef HFCL_PAIRS_LANE_SEARCH
+  return pairs_conf_of(conf_begin, n_conf, k_lane);
+#endif
+  const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(k_lane)), hi = __builtin_amdgcn_readfirstlane(uint32_t(k_lane >> 32));
+  return pairs_conf_of(conf_begin, n_conf, (uint64_t(hi) << 32) | lo);
+}
+
+template <bool ALIGNED>
+__global__ void __launch_bounds__(256) k_scene_expand_pairs64(SceneExpandArgs a, const uint32_t* __restrict__ pairs,
+                                                              const uint64_t* __restrict__ conf_begin, uint64_t n_conf, uint64_t k0) {
+  const uint64_t total = uint64_t(a.m) * 6u;
+  const double* __restrict__ table = static_cast<const double*>(a.object_tf);
+  double2* __restrict__ o1 = static_cast<double2*>(a.tf1);
+  double2* __restrict__ o2 = static_cast<double2*>(a.tf2);
+  for (uint64_t t = uint64_t(blockIdx.x) * 256u + threadIdx.x; t < total; t += uint64_t(gridDim.x) * 256u) {
+    const uint32_t row = uint32_t(t / 6u), part = uint32_t(t - uint64_t(row) * 6u);
+    const uint64_t k = k0 + row;
+    const uint64_t c = pairs_entry_conf(conf_begin, n_conf, pairs_wave_conf(conf_begin, n_conf, k), k);
+    const uint2 ij = reinterpret_cast<const uint2*>(pairs)[k];
+    const double* r1 = table + scene_pose_row(c, a.n_objects, ij.x, 12u) + 2u * part;
+    const double* r2 = table + scene_pose_row(c, a.n_objects, ij.y, 12u) + 2u * part;
+    double2 v1, v2;
+    if (ALIGNED) {
+      v1 = *reinterpret_cast<const double2*>(r1);
+      v2 = *reinterpret_cast<const double2*>(r2);
+    } else {
+      v1.x = r1[0]; v1.y = r1[1];
+      v2.x = r2[0]; v2.y = r2[1];
+    }
+    o1[t] = v1;
+    o2[t] = v2;
+    if (part == 0u) {
+      a.s1[row] = a.object_shape[ij.x];
+      a.s2[row] = a.object_shape[ij.y];
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) k_scene_expand_pairs32(SceneExpandArgs a, const uint32_t* __restrict__ pairs,
+                                                              const uint64_t* __restrict__ conf_begin, uint64_t n_conf, uint64_t k0) {
+  const uint64_t total = uint64_t(a.m) * 7u;
+  const float* __restrict__ table = static_cast<const float*>(a.object_tf);
+  float* __restrict__ o1 = static_cast<float*>(a.tf1);
+  float* __restrict__ o2 = static_cast<float*>(a.tf2);
+  for (uint64_t t = uint64_t(blockIdx.x) * 256u + threadIdx.x; t < total; t += uint64_t(gridDim.x) * 256u) {
+    const uint32_t row = uint32_t(t / 7u), part = uint32_t(t - uint64_t(row) * 7u);
+    const uint64_t k = k0 + row;
+    const uint64_t c = pairs_entry_conf(conf_begin, n_conf, pairs_wave_conf(conf_begin, n_conf, k), k);
+    const uint2 ij = reinterpret_cast<const uint2*>(pairs)[k];
+    o1[t] = table[scene_pose_row(c, a.n_objects, ij.x, 7u) + part];
+    o2[t] = table[scene_pose_row(c, a.n_objects, ij.y, 7u) + part];
+    if (part == 0u) {
+      a.s1[row] = a.object_shape[ij.x];
+      a.s2[row] = a.object_shape[ij.y];
+    }
+  }
+}
+
+void launch_scene_expand_pairs(hipStream_t st, const SceneExpandArgs& a, const uint32_t* pairs, const uint64_t* conf_begin, uint64_t n_conf,
+                               uint64_t k0, bool f32, int max_blocks) {
+  const uint64_t lanes = uint64_t(a.m) * (f32 ? 7u : 6u);
+  const uint32_t grid = uint32_t(std::max<uint64_t>(1u, std::min<uint64_t>((lanes + 255u) / 256u, uint64_t(max_blocks))));
+  if (f32)
+    hipLaunchKernelGGL(k_scene_expand_pairs32, dim3(grid), dim3(256), 0, st, a, pairs, conf_begin, n_conf, k0);
+  else if ((reinterpret_cast<uintptr_t>(a.object_tf) & 15u) == 0)
+    hipLaunchKernelGGL(k_scene_expand_pairs64<true>, dim3(grid), dim3(256), 0, st, a, pairs, conf_begin, n_conf, k0);
+  else
+    hipLaunchKernelGGL(k_scene_expand_pairs64<false>, dim3(grid), dim3(256), 0, st, a, pairs, conf_begin, n_conf, k0);
+}
+
 void launch_scene_expand_listed(hipStream_t st, const SceneExpandArgs& a, const uint64_t* ids, bool f32, int max_blocks) {
   const uint64_t lanes = uint64_t(a.m) * (f32 ? 7u : 6u);
   const uint32_t grid = uint32_t(std::max<uint64_t>(1u, std::min<uint64_t>((lanes + 255u) / 256u, uint64_t(max_blocks))));
@@ -250,17 +332,23 @@ static __device__ __forceinline__ void listed_store(const SceneFoldListedArgs& a
   a.summary[c] = s;
 }
 // the configurations the chunk [k0, k1) of the list spans (hfcl_cull.hpp: scene_listed_span)
+template <bool RANKED>
 static __device__ __forceinline__ void listed_conf_range(const SceneFoldListedArgs& a, uint64_t& c_lo, uint64_t& n_conf) {
-  scene_listed_span(a.ids[a.k0], a.ids[a.k1 - 1u], a.n_pairs, a.n_conf, c_lo, n_conf);
+  if (RANKED) {  // (the spans of conf_begin that hold the chunk's first and last entry)
+    c_lo = pairs_conf_of(a.conf_begin, a.n_conf, a.k0);
+    n_conf = pairs_conf_of(a.conf_begin, a.n_conf, a.k1 - 1u) - c_lo + 1u;
+  } else {
+    scene_listed_span(a.ids[a.k0], a.ids[a.k1 - 1u], a.n_pairs, a.n_conf, c_lo, n_conf);
+  }
 }
 
-template <typename R>
+template <typename R, bool RANKED>
 __global__ void __launch_bounds__(256) k_scene_fold_listed(SceneFoldListedArgs a) {
   const R* __restrict__ rec = static_cast<const R*>(a.rec);
   const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t shares = scene_shares(a.n_pairs);
+  const uint32_t shares = RANKED ? a.shares : scene_shares(a.n_pairs);
   uint64_t c_lo, n_conf;
-  listed_conf_range(a, c_lo, n_conf);
+  listed_conf_range<RANKED>(a, c_lo, n_conf);
   const uint64_t n_items = n_conf * shares;
   for (uint64_t w = uint64_t(blockIdx.x) * 4u + (threadIdx.x >> 6); w < n_items; w += uint64_t(gridDim.x) * 4u) {
     const uint64_t c = c_lo + w / shares;
@@ -271,7 +359,7 @@ __global__ void __launch_bounds__(256) k_scene_fold_listed(SceneFoldListedArgs a
     scene_summary_init(s);
     for (uint64_t k = lo + lane; k < hi; k += 64u) {
       const R& r = rec[k - a.k0];
-      scene_fold_record(s, listed_record_value(r, a), r.status, uint32_t(a.ids[k] - c * a.n_pairs));
+      scene_fold_record(s, listed_record_value(r, a), r.status, RANKED ? uint32_t(k - a.conf_begin[c]) : uint32_t(a.ids[k] - c * a.n_pairs));
     }
     scene_wave_reduce(s);
     if (lane == 0u) {
@@ -283,11 +371,12 @@ __global__ void __launch_bounds__(256) k_scene_fold_listed(SceneFoldListedArgs a
   }
 }
 
+template <bool RANKED>
 __global__ void __launch_bounds__(256) k_scene_fold_listed_combine(SceneFoldListedArgs a) {
   const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t shares = scene_shares(a.n_pairs);
+  const uint32_t shares = RANKED ? a.shares : scene_shares(a.n_pairs);
   uint64_t c_lo, n_conf;
-  listed_conf_range(a, c_lo, n_conf);
+  listed_conf_range<RANKED>(a, c_lo, n_conf);
   for (uint64_t w = uint64_t(blockIdx.x) * 4u + (threadIdx.x >> 6); w < n_conf; w += uint64_t(gridDim.x) * 4u) {
     hfcl_scene_summary s;
     scene_summary_init(s);
@@ -297,15 +386,23 @@ __global__ void __launch_bounds__(256) k_scene_fold_listed_combine(SceneFoldList
   }
 }
 
-void launch_scene_fold_listed(hipStream_t st, const SceneFoldListedArgs& a, bool f32, int max_blocks) {
-  const uint32_t shares = scene_shares(a.n_pairs);
+template <bool RANKED>
+static void launch_fold_listed(hipStream_t st, const SceneFoldListedArgs& a, uint32_t shares, bool f32, int max_blocks) {
   const uint64_t items = a.n_conf * shares;  // (a bound: the span of the chunk is known on the device only; the waves stride it)
   const uint32_t grid = uint32_t(std::max<uint64_t>(1u, std::min<uint64_t>((items + 3u) / 4u, uint64_t(max_blocks))));
   if (f32)
-    hipLaunchKernelGGL(k_scene_fold_listed<hfcl_result_f32>, dim3(grid), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((k_scene_fold_listed<hfcl_result_f32, RANKED>), dim3(grid), dim3(256), 0, st, a);
   else
-    hipLaunchKernelGGL(k_scene_fold_listed<hfcl_result>, dim3(grid), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((k_scene_fold_listed<hfcl_result, RANKED>), dim3(grid), dim3(256), 0, st, a);
   if (!a.partials) return;
   const uint32_t grid2 = uint32_t(std::max<uint64_t>(1u, std::min<uint64_t>((a.n_conf + 3u) / 4u, uint64_t(max_blocks))));
-  hipLaunchKernelGGL(k_scene_fold_listed_combine, dim3(grid2), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_scene_fold_listed_combine<RANKED>, dim3(grid2), dim3(256), 0, st, a);
+}
+void launch_scene_fold_listed(hipStream_t st, const SceneFoldListedArgs& a, bool f32, int max_blocks) {
+  launch_fold_listed<false>(st, a, scene_shares(a.n_pairs), f32, max_blocks);
+}
+void launch_scene_fold_ranked(hipStream_t st, const SceneFoldListedArgs& a, uint32_t shares, bool f32, int max_blocks) {
+  SceneFoldListedArgs r = a;
+  r.shares = shares;
+  launch_fold_listed<true>(st, r, shares, f32, max_blocks);
 }

@@ -190,8 +190,16 @@ struct SceneFoldListedArgs {
   hfcl_scene_summary* summary;   // by configuration, initialised (launch_scene_summary_init) before the first chunk
   hfcl_scene_summary* partials;  // nullptr (pair lists of one piece) or n_conf * scene_shares(n_pairs) slots
   uint64_t n_conf;               // configurations of the call: the bound on those a chunk spans (it may span empty ones: not bounded by k1 - k0)
+  uint32_t shares;               // launch_scene_fold_ranked: pieces per configuration (launch_scene_fold_listed: scene_shares(n_pairs), not read)
 };
 void launch_scene_fold_listed(hipStream_t st, const SceneFoldListedArgs& a, bool f32, int max_blocks);
+// (hfcl_k_cull.hip) the expansion of a chunk of a list of explicit pairs: a.m entries from entry k0 on; pairs: the whole list, 2 x uint32 an
+// entry; the configuration of an entry: the span of conf_begin that holds it; a.pairs / n_pairs / q0 / c0 / p0 unused
+void launch_scene_expand_pairs(hipStream_t st, const SceneExpandArgs& a, const uint32_t* pairs, const uint64_t* conf_begin, uint64_t n_conf,
+                               uint64_t k0, bool f32, int max_blocks);
+// (hfcl_k_cull.hip) the fold of a chunk of a list of explicit pairs (hfcl_scene_*_pairs_device*): a.ids unused, a.n_pairs unused; an entry's
+// pair index is its rank k - conf_begin[c], the configurations of the chunk are found in conf_begin, a configuration has at most `shares` pieces
+void launch_scene_fold_ranked(hipStream_t st, const SceneFoldListedArgs& a, uint32_t shares, bool f32, int max_blocks);
 // (hfcl_k_cull.hip) the scan and the emit of launch_cull_chunk alone, behind a mark kernel of another unit that left a.words / a.block_counts
 void launch_cull_scan_emit(hipStream_t st, const CullArgs& a);
 
@@ -223,3 +231,34 @@ struct NearestGatherArgs {
   void* out;
 };
 void launch_nearest_gather(hipStream_t st, const NearestGatherArgs& a, bool f32);
+
+// hfcl_k_pairs.hip: the self-collision pairs of a scene per configuration (hfcl_scene_self_pairs*; hfcl_pairs.hpp has the arithmetic).
+// A chunk of consecutive row blocks [g0, g0 + n_blocks): count (a uint32 per row), scan (row offsets on top of the
+// entries of the chunks before: *running; conf_begin of the configurations that start in the chunk; the total with the last row), emit (the
+// pairs at their positions, below the capacity).  Launches in stream order; no atomics, no kernel waits for another workgroup.
+struct PairsArgs {
+  const double* boxes;       // world boxes of the configurations [c_box0, ...) the chunk touches, n_objects each
+  uint64_t c_box0;
+  uint32_t n_objects;
+  uint32_t rows_per_block;   // hfcl_pairs.hpp: PairsGeometry
+  uint32_t blocks_per_conf;
+  int small;                 // the wave-per-configuration form (n_objects <= PAIRS_SMALL_MAX)
+  uint64_t g0;               // first row block of the chunk
+  uint32_t n_blocks;         // row blocks of the chunk
+  uint64_t row0;             // first row of the chunk in the table
+  uint32_t n_rows;           // rows of the chunk
+  uint64_t total_rows;       // n_conf * n_objects
+  uint64_t n_conf;
+  double inflate;
+  uint32_t* row_counts;      // n_rows
+  uint64_t* row_offsets;     // n_rows
+  uint32_t* sums;            // ceil(n_rows / PAIRS_SCAN_BLOCK): entries of a scan workgroup's rows
+  uint64_t* sum_offsets;     // ... entries before them, over all chunks
+  uint64_t* running;         // entries of the chunks before this one (first: taken as 0), then of this one too
+  int first;
+  uint32_t* pairs;           // nullptr / capacity 0: count only
+  uint64_t capacity;
+  uint64_t* conf_begin;      // nullptr or n_conf + 1
+  uint64_t* n_listed;        // nullptr or one word
+};
+void launch_pairs_chunk(hipStream_t st, const PairsArgs& a);

@@ -46,6 +46,13 @@ CULL_SYMBOLS = [
 NEAREST_SYMBOLS = [
     "hfcl_scene_nearest", "hfcl_scene_nearest_f32", "hfcl_scene_nearest_device", "hfcl_scene_nearest_device_f32",
 ]
+# include/hppfcl_amd_pairs.h (included by hppfcl_amd.h): the self-collision pairs per configuration made on the device, the calls on such a list
+PAIRS_SYMBOLS = [
+    "hfcl_scene_self_pairs", "hfcl_scene_self_pairs_f32", "hfcl_scene_self_pairs_device", "hfcl_scene_self_pairs_device_f32",
+    "hfcl_scene_collide_pairs_device", "hfcl_scene_distance_pairs_device", "hfcl_scene_collide_pairs_device_f32",
+    "hfcl_scene_distance_pairs_device_f32", "hfcl_scene_collide_self", "hfcl_scene_distance_self", "hfcl_scene_collide_self_f32",
+    "hfcl_scene_distance_self_f32",
+]
 
 
 class EngineError(RuntimeError):
@@ -686,6 +693,96 @@ class Scene:
         _check(dll().hfcl_scene_distance_listed_device_f32(self._h, _dptr(d_object_pose), C.c_size_t(int(n_conf)), _dptr(d_query_ids),
                                                            C.c_size_t(int(n_listed)), _dptr(d_conf_begin), C.byref(req), _dptr(d_out),
                                                            _dptr(d_summary), C.c_void_p(stream)))
+
+    # ---- the self-collision pairs per configuration, made on the device (include/hppfcl_amd_pairs.h) ----
+    def _pairs_guess(self, n_conf):
+        """Size of the outputs of a self-pairs call when the caller names none: 16 entries per (configuration, object), at most all pairs."""
+        n = self.n_objects
+        return min(n_conf * (n * (n - 1) // 2), max(16 * n_conf * n, 1024))
+
+    def self_pairs(self, object_tf, inflate=0.0):
+        """hfcl_scene_self_pairs{,_f32}: (pairs uint32 (n_listed, 2), conf_begin uint64[n_conf + 1]) -- for configuration c, then i, then j
+        ascending, every (i < j) whose two world boxes, each grown by `inflate`, touch.  The scene's own pair list plays no part."""
+        tf, f32 = self._any_table(object_tf)
+        fn = dll().hfcl_scene_self_pairs_f32 if f32 else dll().hfcl_scene_self_pairs
+        n = C.c_size_t(0)
+        conf_begin = np.zeros(len(tf) + 1, dtype=np.uint64)
+        capacity = self._pairs_guess(len(tf))
+        while True:  # (at most twice: a list longer than the guess is refused with its length, and the call repeated with that)
+            pairs = np.zeros((capacity, 2), dtype=np.uint32)
+            rc = fn(self._h, abi.ptr(tf), C.c_size_t(len(tf)), C.c_double(inflate), abi.ptr(pairs), C.c_size_t(capacity), abi.ptr(conf_begin),
+                    C.byref(n))
+            if rc != abi.ERR_LIMIT or n.value <= capacity:
+                break
+            capacity = n.value
+        _check(rc)
+        return pairs[:n.value], conf_begin
+
+    def _self(self, kind, object_tf, inflate, req, records, capacity=None, want_guess=False):
+        tf, f32 = self._any_table(object_tf)
+        n_conf = len(tf)
+        fn = getattr(dll(), "hfcl_scene_%s_self%s" % (kind, "_f32" if f32 else ""))
+        retry = capacity is None
+        if retry:
+            capacity = self._pairs_guess(n_conf)
+        out = np.zeros(capacity, dtype=abi.RESULT_F32_DTYPE if f32 else abi.RESULT_DTYPE) if records else None
+        pairs = np.zeros((capacity, 2), dtype=np.uint32)
+        conf_begin = np.zeros(n_conf + 1, dtype=np.uint64)
+        summ = np.zeros(n_conf, dtype=abi.SCENE_SUMMARY_DTYPE)
+        n = C.c_size_t(0)
+        args = [self._h, abi.ptr(tf), C.c_size_t(n_conf), C.c_double(inflate), C.byref(req), abi.ptr(out), C.c_size_t(capacity), abi.ptr(pairs),
+                abi.ptr(conf_begin), abi.ptr(summ)]
+        gout = None
+        if not f32:
+            gout = np.zeros(capacity, dtype=abi.GUESS_DTYPE) if want_guess else None
+            args += [None, abi.ptr(gout)]  # (no guesses in)
+        rc = fn(*args, C.byref(n))
+        if rc == abi.ERR_LIMIT and retry and n.value > capacity:
+            return self._self(kind, tf, inflate, req, records, n.value, want_guess)
+        _check(rc)
+        k = n.value
+        res = (out[:k] if records else None), pairs[:k], conf_begin, summ
+        return res + (gout[:k],) if gout is not None else res
+
+    def collide_self(self, object_tf, req=None, inflate=0.0, records=True, want_guess=False):
+        """hfcl_scene_collide_self{,_f32}: (records, pairs, conf_begin, summaries) of collide() on the self-collision pairs of every
+        configuration; record k is for pairs[k] in the configuration whose conf_begin span holds k, min_pair / first_contact of a summary
+        are ranks inside the configuration (pairs[conf_begin[c] + rank]).  records=False: None in their place, no record leaves the device.
+        want_guess (fp64 poses): the guesses the records hand out, as a fifth item."""
+        return self._self("collide", object_tf, inflate, req or abi.default_collision_request(), records, want_guess=want_guess)
+
+    def distance_self(self, object_tf, req=None, inflate=0.0, records=True, want_guess=False):
+        return self._self("distance", object_tf, inflate, req or abi.default_distance_request(), records, want_guess=want_guess)
+
+    # device forms: torch tensors or raw device pointers, asynchronous on `stream`
+    def self_pairs_device(self, d_object_tf, n_conf, inflate, d_pairs, capacity, d_conf_begin, d_n_listed, f32=False, stream=0):
+        """hfcl_scene_self_pairs_device{,_f32}: *d_n_listed is the true count, entries past `capacity` are not written; nothing is read back."""
+        fn = dll().hfcl_scene_self_pairs_device_f32 if f32 else dll().hfcl_scene_self_pairs_device
+        _check(fn(self._h, _dptr(d_object_tf), C.c_size_t(int(n_conf)), C.c_double(inflate), _dptr(d_pairs), C.c_size_t(int(capacity)),
+                  _dptr(d_conf_begin), _dptr(d_n_listed), C.c_void_p(stream)))
+
+    def _pairs_device(self, kind, f32, d_object_tf, n_conf, d_pairs, n_listed, d_conf_begin, req, d_out, d_summary, d_gin, d_gout, stream):
+        fn = getattr(dll(), "hfcl_scene_%s_pairs_device%s" % (kind, "_f32" if f32 else ""))
+        args = [self._h, _dptr(d_object_tf), C.c_size_t(int(n_conf)), _dptr(d_pairs), C.c_size_t(int(n_listed)), _dptr(d_conf_begin),
+                C.byref(req), _dptr(d_out), _dptr(d_summary)]
+        if not f32:
+            args += [_dptr(d_gin), _dptr(d_gout)]
+        _check(fn(*args, C.c_void_p(stream)))
+
+    def collide_pairs_device(self, d_object_tf, n_conf, d_pairs, n_listed, d_conf_begin, req, d_out=None, d_summary=None, d_gin=None,
+                             d_gout=None, stream=0):
+        """hfcl_scene_collide_pairs_device: the list (i < j < n_objects, conf_begin its spans) is not checked."""
+        self._pairs_device("collide", False, d_object_tf, n_conf, d_pairs, n_listed, d_conf_begin, req, d_out, d_summary, d_gin, d_gout, stream)
+
+    def distance_pairs_device(self, d_object_tf, n_conf, d_pairs, n_listed, d_conf_begin, req, d_out=None, d_summary=None, d_gin=None,
+                              d_gout=None, stream=0):
+        self._pairs_device("distance", False, d_object_tf, n_conf, d_pairs, n_listed, d_conf_begin, req, d_out, d_summary, d_gin, d_gout, stream)
+
+    def collide_pairs_device_f32(self, d_object_pose, n_conf, d_pairs, n_listed, d_conf_begin, req, d_out=None, d_summary=None, stream=0):
+        self._pairs_device("collide", True, d_object_pose, n_conf, d_pairs, n_listed, d_conf_begin, req, d_out, d_summary, None, None, stream)
+
+    def distance_pairs_device_f32(self, d_object_pose, n_conf, d_pairs, n_listed, d_conf_begin, req, d_out=None, d_summary=None, stream=0):
+        self._pairs_device("distance", True, d_object_pose, n_conf, d_pairs, n_listed, d_conf_begin, req, d_out, d_summary, None, None, stream)
 
     # ---- the per-configuration minimum distance with box-bound pruning (include/hppfcl_amd_nearest.h) ----
     def _nearest(self, object_tf, req, upper_bound, records, f32):

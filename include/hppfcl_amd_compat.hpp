@@ -1486,6 +1486,50 @@ class Scene {
     for (size_t k = 0; k < n; ++k) ctx_.fill((*results)[k], shape_pair(query_ids[k] % numPairs()), rec_[k], guess_[k]);
   }
 
+  /// The self-collision pairs per configuration, made on the device without a list (hfcl_scene_self_pairs, include/hppfcl_amd_pairs.h):
+  /// for configuration c, then i, then j ascending, every (i < j) whose two world AABBs, each grown by `inflate` >= 0, overlap -- with
+  /// inflate = 0 the pairs DynamicAABBTreeCollisionManager::collide passes to its callback.  pairs: two object indices per entry;
+  /// conf_begin (n_conf + 1 entries): configuration c owns the entries conf_begin[c] .. conf_begin[c + 1].  The scene's own pair list
+  /// plays no part (a Scene made with an empty list serves).
+  void selfPairs(const Transform3f* tables, size_t n_conf, double inflate, std::vector<uint32_t>& pairs, std::vector<uint64_t>& conf_begin) {
+    ensure();
+    listed(n_conf, false, pairs, conf_begin, nullptr, [&](size_t capacity, size_t* n) {
+      return hfcl_scene_self_pairs(scene_, reinterpret_cast<const double*>(tables), n_conf, inflate, pairs.data(), capacity, conf_begin.data(), n);
+    });
+  }
+  /// collide() on that list: results[k] (nullptr: summaries only) is what hpp::fcl::collide gives for entry k; summaries[c] folds
+  /// configuration c's entries, min_pair and first_contact being RANKS inside the configuration: entry conf_begin[c] + rank.
+  void collideSelf(const Transform3f* tables, size_t n_conf, double inflate, const CollisionRequest& request, std::vector<CollisionResult>* results,
+                   std::vector<uint32_t>& pairs, std::vector<uint64_t>& conf_begin, std::vector<hfcl_scene_summary>* summaries) {
+    ensure();
+    const hfcl_collision_request a = to_abi(request);
+    const size_t n = listed(n_conf, results != nullptr, pairs, conf_begin, summaries, [&](size_t capacity, size_t* count) {
+      return hfcl_scene_collide_self(scene_, reinterpret_cast<const double*>(tables), n_conf, inflate, &a, results ? rec_.data() : nullptr, capacity,
+                                     pairs.data(), conf_begin.data(), summaries ? summaries->data() : nullptr, nullptr,
+                                     results ? guess_.data() : nullptr, count);
+    });
+    if (!results) return;
+    results->assign(n, CollisionResult());
+    for (size_t k = 0; k < n; ++k) {
+      hfcl_result r = rec_[k];
+      if (r.num_contacts > 1) r.num_contacts = 1;
+      ctx_.fill((*results)[k], {shape_[pairs[2 * k]], shape_[pairs[2 * k + 1]]}, request, r, guess_[k]);
+    }
+  }
+  void distanceSelf(const Transform3f* tables, size_t n_conf, double inflate, const DistanceRequest& request, std::vector<DistanceResult>* results,
+                    std::vector<uint32_t>& pairs, std::vector<uint64_t>& conf_begin, std::vector<hfcl_scene_summary>* summaries) {
+    ensure();
+    const hfcl_distance_request a = to_abi(request);
+    const size_t n = listed(n_conf, results != nullptr, pairs, conf_begin, summaries, [&](size_t capacity, size_t* count) {
+      return hfcl_scene_distance_self(scene_, reinterpret_cast<const double*>(tables), n_conf, inflate, &a, results ? rec_.data() : nullptr, capacity,
+                                      pairs.data(), conf_begin.data(), summaries ? summaries->data() : nullptr, nullptr,
+                                      results ? guess_.data() : nullptr, count);
+    });
+    if (!results) return;
+    results->assign(n, DistanceResult());
+    for (size_t k = 0; k < n; ++k) ctx_.fill((*results)[k], {shape_[pairs[2 * k]], shape_[pairs[2 * k + 1]]}, rec_[k], guess_[k]);
+  }
+
   /// The clearance per configuration (hfcl_scene_nearest, include/hppfcl_amd_nearest.h): what DistanceCallBackDefault leaves behind
   /// after DynamicAABBTreeCollisionManager::distance -- the smallest distance over the listed pairs and the pair that has it --, with
   /// the pairs pruned by a bound from their world boxes instead of evaluated one by one.  summaries[c].min_distance / min_pair equal
@@ -1537,6 +1581,30 @@ class Scene {
       break;
     }
     query_ids.resize(n);
+    return n;
+  }
+  // a self-pairs call with outputs sized by a guess (16 entries per configuration and object), repeated once with the list's length
+  template <class Call>
+  size_t listed(size_t n_conf, bool records, std::vector<uint32_t>& pairs, std::vector<uint64_t>& conf_begin,
+                std::vector<hfcl_scene_summary>* summaries, Call call) {
+    conf_begin.assign(n_conf + 1, 0);
+    if (summaries) summaries->resize(n_conf);
+    size_t n = 0, capacity = std::max<size_t>(16 * n_conf * numObjects(), 1024);
+    for (int attempt = 0;; ++attempt) {
+      pairs.assign(2 * capacity, 0);
+      if (records) {
+        rec_.resize(capacity);
+        guess_.resize(capacity);
+      }
+      const int rc = call(capacity, &n);
+      if (rc == HFCL_ERR_LIMIT && attempt == 0 && n > capacity) {
+        capacity = n;
+        continue;
+      }
+      if (rc) throw_for(rc);
+      break;
+    }
+    pairs.resize(2 * n);
     return n;
   }
   void init() {

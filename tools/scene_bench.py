@@ -15,6 +15,14 @@ configuration) and on workloads.scene_planner at ~1 M queries.
   P, Q, R, S  the same four through the fp32 path
   T  the narrow phase of nearest's pass 1 alone: hfcl_scene_distance_listed_device on that list, summaries only (device events)
   U  ... of pass 2          V, W  the same two through the fp32 path
+  X  hfcl_scene_self_pairs_device alone: boxes, count, scan, emit of ALL pairs of every configuration, no list (device events)
+  Y  hfcl_scene_collide_self, summaries only (host clock)
+  Z  what a caller had before X: per configuration engine.world_aabbs + engine.broadphase_self_pairs on the host, hfcl_scene_set_pairs,
+     hfcl_scene_collide summaries only, all timed together (host clock; one-configuration workloads only; against Y)
+  a  hfcl_scene_self_pairs_device, the count read back, hfcl_scene_collide_pairs_device with records and summaries (device events)
+  b  the same list by the route that existed: a scene whose own list is all n (n - 1) / 2 pairs, hfcl_scene_cull_device, the count read
+     back, hfcl_scene_collide_listed_device with records and summaries (device events; against a; scenes of at most 256 objects)
+X .. b ignore the workload's pair list.  --options key=value,... sets library options in the worker (scene_pairs_small_max=0: the tiled form).
 The culled forms run at --inflate (default 0: the reference's manager).  planner2048: scene_planner(2048, 16), 215 040 queries;
 planner2048x32: scene_planner(2048, 32), 952 320 queries.  L .. W report the share of the queries each pass of nearest evaluates.
 Rows L .. W import the numpy model of the selection from tests/nearest_model.py: the lists of T .. W (the library keeps its own in its
@@ -49,6 +57,8 @@ def _workload(pkg, name):
         return b.lib, sc["obj_shape"], sc["pairs"], sc["obj_tf"].reshape(1, -1, 12)
     if name == "planner2048x32":
         ps = wl.scene_planner(n_conf=2048, n_objects=32)
+    elif name == "planner256x64":
+        ps = wl.scene_planner(n_conf=256, n_objects=64)
     else:
         ps = wl.scene_planner(n_conf=2048 if name == "planner2048" else 9984, n_objects=16)
     return ps.lib, ps.obj_shape, ps.pairs, ps.obj_tf
@@ -68,7 +78,7 @@ def worker(args):
     n_conf, G, P = table.shape[0], table.shape[1], len(pairs)
     n = n_conf * P
     i, j = pairs[:, 0], pairs[:, 1]
-    lib = pkg.Library(L)
+    lib = pkg.Library(L, options=dict(kv.split("=") for kv in args.options.split(",") if kv))
     req = abi.default_collision_request()
     dev = torch.device("cuda:0")
     st = torch.cuda.current_stream().cuda_stream
@@ -104,7 +114,7 @@ def worker(args):
         return _stats(ms)
 
     forms = args.forms.split(",")
-    scene = lib.scene(obj_shape, pairs) if set(forms) & set("BCEFGHIJKLMNOPQRSTUVW") else None
+    scene = lib.scene(obj_shape, pairs) if set(forms) & set("BCEFGHIJKLMNOPQRSTUVWXYZab") else None
     if "A" in forms or "D" in forms:
         t0 = time.perf_counter()
         s1, s2, tf1, tf2 = expand()
@@ -212,6 +222,49 @@ def worker(args):
                     d_c = torch.from_numpy(sel["conf_begin" + k].view(np.int64)).to(dev)
                     m = len(sel["ids" + k])
                     out["forms"][letter] = device_clock(lambda: listed(d_t, n_conf, d_l, m, d_c, dreq, None, d_sum3, stream=st))
+    if set(forms) & set("XYZab"):  # the pairs made on the device, no list
+        d_tab_p = torch.from_numpy(np.ascontiguousarray(table)).to(dev)
+        sp, sp_cb = scene.self_pairs(table, args.inflate)
+        out["self_pairs"] = {"n_listed": int(len(sp)), "box_tests": n_conf * G * (G - 1) // 2, "options": args.options}
+        cap = max(len(sp), 1)
+        d_sp = torch.zeros(2 * cap, dtype=torch.int32, device=dev)
+        d_spcb = torch.zeros(n_conf + 1, dtype=torch.int64, device=dev)
+        d_spn = torch.zeros(1, dtype=torch.int64, device=dev)
+        d_sum4 = torch.zeros(n_conf * 6, dtype=torch.int32, device=dev)
+    if "X" in forms:
+        out["forms"]["X"] = device_clock(lambda: scene.self_pairs_device(d_tab_p, n_conf, args.inflate, d_sp, cap, d_spcb, d_spn, stream=st))
+    if "Y" in forms:
+        out["forms"]["Y"] = host_clock(lambda: scene.collide_self(table, req, args.inflate, records=False))
+    if "Z" in forms and n_conf == 1:
+        def host_route():
+            boxes = pkg.engine.world_aabbs(L, obj_shape, table[0])
+            scene.set_pairs(pkg.engine.broadphase_self_pairs(boxes))
+            return scene.collide(table, req, records=False)
+        summ_host = host_route()
+        out["self_pairs"]["host_route_equal"] = bool(summ_host.tobytes() == scene.collide_self(table, req, 0.0, records=False)[3].tobytes()) if args.inflate == 0.0 else None
+        out["forms"]["Z"] = host_clock(host_route)
+        scene.set_pairs(pairs)
+    if "a" in forms:
+        d_rec_p = torch.zeros(cap * 24, dtype=torch.int32, device=dev)
+
+        def self_device():
+            scene.self_pairs_device(d_tab_p, n_conf, args.inflate, d_sp, cap, d_spcb, d_spn, stream=st)
+            k = int(d_spn.item())  # the one read-back: 8 bytes
+            scene.collide_pairs_device(d_tab_p, n_conf, d_sp, min(k, cap), d_spcb, req, d_rec_p, d_sum4, stream=st)
+        out["forms"]["a"] = device_clock(self_device)
+    if "b" in forms and G <= 256:
+        ti, tj = np.triu_indices(G, 1)
+        every = lib.scene(obj_shape, np.stack([ti, tj], axis=1).astype(np.uint32))
+        d_ids_b = torch.zeros(cap, dtype=torch.int64, device=dev)
+        d_rec_b = torch.zeros(cap * 24, dtype=torch.int32, device=dev)
+
+        def culled_all_pairs():
+            every.cull_device(d_tab_p, n_conf, args.inflate, d_ids_b, cap, d_spcb, d_spn, stream=st)
+            k = int(d_spn.item())
+            every.collide_listed_device(d_tab_p, n_conf, d_ids_b, min(k, cap), d_spcb, req, d_rec_b, d_sum4, stream=st)
+        out["forms"]["b"] = device_clock(culled_all_pairs)
+        torch.cuda.synchronize()
+        every.close()
     torch.cuda.synchronize()
     if scene is not None:
         scene.close()
@@ -236,9 +289,10 @@ def bytes_moved(n_conf, G, P):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--worker", action="store_true")
-    ap.add_argument("--workload", default="cfg5", choices=["cfg5", "planner", "planner2048", "planner2048x32"])
+    ap.add_argument("--workload", default="cfg5", choices=["cfg5", "planner", "planner2048", "planner2048x32", "planner256x64"])
     ap.add_argument("--workloads", default="cfg5,planner", help="the workloads of a full run, comma-separated")
     ap.add_argument("--inflate", type=float, default=0.0)
+    ap.add_argument("--options", default="", help="library options of the worker: key=value,...")
     ap.add_argument("--forms", default="A,B,C,D,E,F")
     ap.add_argument("--calls", type=int, default=12)
     ap.add_argument("--warmup", type=int, default=3)
@@ -265,7 +319,7 @@ def main():
                 if lib_path:
                     env["HFCL_LIB_PATH"] = lib_path
                 cmd = [sys.executable, os.path.abspath(__file__), "--worker", "--workload", workload, "--calls", str(args.calls), "--warmup",
-                       str(args.warmup), "--inflate", str(args.inflate), "--forms", args.forms]
+                       str(args.warmup), "--inflate", str(args.inflate), "--forms", args.forms, "--options", args.options]
                 r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
                 line = [x for x in r.stdout.splitlines() if x.startswith("SCENE_BENCH ")]
                 if r.returncode != 0 or not line:  # a child that failed ends the run: nothing more is started on the device
@@ -284,7 +338,7 @@ def main():
         print("| form | build | median ms | min .. max ms (over the runs) |")
         print("|---|---|---|---|")
         for which in ("parent", "new", "control"):
-            for f in "ABCDEFGHIJKLMNOPQRSTUVW":
+            for f in "ABCDEFGHIJKLMNOPQRSTUVWXYZab":
                 runs = [r["forms"][f] for r in rs if r["build"] == which and f in r["forms"]]
                 if runs:
                     print("| %s | %s | %s | %.3f .. %.3f |" % (f, which, " / ".join("%.3f" % x["median_ms"] for x in runs),
@@ -297,6 +351,10 @@ def main():
                 print("%s: %d + %d queries evaluated (%.2f %% + %.2f %%), min_distance / min_pair equal to the unculled call: %s%s" % (
                     key, k["evaluated"][0], k["evaluated"][1], k["share_pct"][0], k["share_pct"][1], k["equal_to_unculled"],
                     "; largest (lb - d_f32) / M = %.3g" % k["max_lb_minus_d_over_M"] if "max_lb_minus_d_over_M" in k else ""))
+        if "self_pairs" in r0:
+            k = r0["self_pairs"]
+            print("self pairs at inflate %g: %d pairs listed of %d box tests (%.3f %%)" % (args.inflate, k["n_listed"], k["box_tests"],
+                                                                                          100.0 * k["n_listed"] / max(k["box_tests"], 1)))
         if "n_listed" in r0:
             print("cull at inflate %g: %d of %d queries survive (%.2f %%); byte model of the cull alone: %.0f bytes" % (
                 r0["inflate"], r0["n_listed"], r0["queries"], 100.0 * r0["n_listed"] / r0["queries"], r0["cull_model_bytes"]))
