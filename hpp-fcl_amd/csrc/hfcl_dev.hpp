@@ -11,6 +11,7 @@
 #include "../../include/hppfcl_amd.h"
 #include "hfcl_bvh.hpp"
 #include "hfcl_bvh_shape.hpp"
+#include "hfcl_epa_pool.hpp"
 #include "hfcl_pair.hpp"
 
 using namespace hfcl;
@@ -64,6 +65,11 @@ constexpr int CTR_SHAPE_DEFER_MARK = 2 * B_COUNT + 13;   // CTR_SHAPE_DEFER as t
 // walks the pooled distance() continuations walked again in the reference's order (BvhSpill::rerun_count): mesh x mesh, mesh x solid
 constexpr int CTR_DIST_RERUN = 2 * B_COUNT + 14, CTR_SHAPE_DIST_RERUN = 2 * B_COUNT + 15;
 constexpr int N_COUNTERS = 2 * B_COUNT + 16;  // bucket populations + the four counters of Work::counts + curved populations + those
+// Behind them, in the same allocation and under the same memset: the ticket counters of k_epa_loop's pool (hfcl_epa_pool.hpp), each alone in
+// a 128-byte line -- none shares a line with a counter above or with another (atomics on one line queue up whatever their addresses:
+// profiles/r07_a section 5).  The host reads back the first N_COUNTERS words only.
+constexpr int EPA_POOL_CTR0 = (N_COUNTERS + EPA_POOL_STRIDE_WORDS - 1) / EPA_POOL_STRIDE_WORDS * EPA_POOL_STRIDE_WORDS;
+constexpr int N_COUNTER_WORDS = EPA_POOL_CTR0 + EPA_POOL_K * EPA_POOL_STRIDE_WORDS;  // what d_counts holds
 
 // Classification-only kind code of a ConvexBase with more than 32 vertices (the reference switches
 // support algorithm there, minkowski_difference.cpp:136-151): GJK pairs with such a hull go to

@@ -248,7 +248,7 @@ static const char* const* option_keys() {
       "bvh_walk_rounds", "bvh_walk_order", "mesh_beside", "mesh_prio", "shape_walk", "shape_walk_sort", "shape_walk_budget", "shape_walk_min", "gjk_beside_max", "epa_direct_max", "bvh_walk_k", "bvh_walk_budget", "shape_dist_leaf_min", "shape_dist_starve", "bvhd_leaf_min", "bvhd_starve",
       "bvhd_part_min", "shape_dist_budget", "bvh_budget0_coop", "shape_budget0", "shape_budget", "shape_leaf_cost", "shape_levels",
       "climb_min", "bvh_budget", "bvh_budget0", "bvh_levels", "cvx_w", "epa_resume_slots", "bvh_task_slots", "bvh_force_wide",
-      "pipe_trace", "scene_chunk", "scene_cull_chunk", "scene_pairs_small_max", nullptr};
+      "pipe_trace", "scene_chunk", "scene_cull_chunk", "scene_pairs_small_max", "epa_pool_share", "epa_pool_min_refills", nullptr};
   return keys;
 }
 // "4,16,16": up to `cap` comma-separated unsigned values into out[first...]; returns how many were read
@@ -303,6 +303,11 @@ static int apply_option(hfcl_lib* lib, const std::string& key, const char* v) {
   else if (key == "shape_walk_min") lib->opt.shape_walk_min = u32(0);
   else if (key == "gjk_beside_max") lib->opt.gjk_beside_max = u32(0);
   else if (key == "epa_direct_max") lib->opt.epa_direct_max = u32(0);
+  else if (key == "epa_pool_share") {
+    if (i < 0 || i > 50) return HFCL_ERR_INVALID_ARGUMENT;
+    lib->opt.epa_pool_share = uint32_t(i);
+  }
+  else if (key == "epa_pool_min_refills") lib->opt.epa_pool_min_refills = u32(0);
   else if (key == "bvh_walk_rounds") { lib->opt.walk_rounds = uint32_t(std::min<long long>(std::max(0ll, i), WALK_ROUNDS)); lib->opt.walk_auto = false; }
   else if (key == "bvh_walk_k") { parse_list(v, lib->opt.walk_k, 0, WALK_ROUNDS, 1u, uint32_t(WALK_K)); lib->opt.walk_auto = false; }  // "6,16": per round
   else if (key == "bvh_walk_budget") parse_list(v, lib->opt.walk_budget, 1, WALK_ROUNDS, 0u, 0xFFFFFFFFu);  // rounds 1 ...: box tests (round 0 takes bvh_budget0_coop's)
@@ -352,7 +357,7 @@ hfcl_lib* hfcl_lib_create(const hfcl_shape* shapes, size_t n_shapes, const doubl
   hfcl_lib* lib = new hfcl_lib();
   lib->device = device;
   bool ok = upload_shapes(lib, shapes, n_shapes, vertices, n_vertices);
-  ok = ok && lib->d_counts.grow(N_COUNTERS) == hipSuccess;
+  ok = ok && lib->d_counts.grow(N_COUNTER_WORDS) == hipSuccess;
   ok = ok && lib->h_counts.alloc(N_COUNTERS) == hipSuccess;
   if (ok) memset(lib->h_counts, 0, N_COUNTERS * sizeof(uint32_t));
   if (!ok) {

@@ -78,6 +78,9 @@ struct hfcl_options {
   bool epa64_two_streams = true; // HFCL_EPA64_TWO_STREAMS=0: the two fp64 fast-tier kernels one after the other
   bool epa_cc_staged = true;     // HFCL_EPA_CC_STAGED=0: the one-kernel form (k_epa_stream<.., CC>)
   size_t epa_cc_staged_min = 32768;  // ... which batches below this many pairs keep (two launches less); HFCL_EPA_CC_STAGED_MIN
+  // k_epa_loop's end-game pool (hfcl_epa_pool.hpp): percent of a batch's polytopes drawn by ticket instead of strided (0 - 50; 0: the static
+  // schedule), in batches that give every wave at least epa_pool_min_refills full refills (tests: 0, so that a small batch draws too)
+  uint32_t epa_pool_share = 20, epa_pool_min_refills = 2;
   bool shape_finish_tiers = true;  // HFCL_SHAPE_FINISH_TIERS=0: k_bvh_shape_finish in one launch at full capacity
   bool shape_finish_aside = true;  // HFCL_SHAPE_FINISH_ASIDE=0: all of k_bvh_shape_finish behind the last launch of k_bvh_shape_coop
   bool bvh_shape_lane = true;     // HFCL_BVH_SHAPE_LANE=0: the group kernels for every request (A/B switch)

@@ -661,7 +661,7 @@ static int launch_epa(Batch<T>& b, hipStream_t st) {
     }
     // (the launchers size the grids of the persistent forms themselves: here only the number of wave-sized batches)
     if constexpr (F32)
-      if (cc_staged) launch_epa_loop(epa_batches, st, wk, b.lv, b.q, lib->n_cus);
+      if (cc_staged) launch_epa_loop(epa_batches, st, wk, b.lv, b.q, lib->n_cus, o.epa_pool_share, o.epa_pool_min_refills);
     if (gen_staged) launch_epa_loop_general<T>(epa_batches, st, st2, wk, b.lv, b.q, lib->n_cus, lib->has_curved);
     if ((F32 && b.may(B_CC) && !cc_staged) || (general_q && !gen_staged))
       launch_epa_fast<T>(epa_batches, st, wk, b.lv, b.io, b.q, b.may(B_CC) && !cc_staged, general_q && !gen_staged, lib->n_cus, lib->has_curved, st2);
@@ -742,7 +742,7 @@ static int run_batch_one(hfcl_lib* lib, const uint32_t* d_s1, const uint32_t* d_
   if (rc) return rc;
   make_views(b, d_s1, d_s2);
   for (auto& t : lib->timers) t.used = false;
-  HIP_TRY(hipMemsetAsync(lib->d_counts, 0, N_COUNTERS * sizeof(uint32_t), st));
+  HIP_TRY(hipMemsetAsync(lib->d_counts, 0, N_COUNTER_WORDS * sizeof(uint32_t), st));
   {
     Timed t(b, "k_classify", st);
     launch_classify(b.blocks_for(n, CLS_BLOCK * 8), st, b.wk, lib->d_kinds, uint32_t(lib->n_shapes), q.mode != 1);
@@ -795,7 +795,7 @@ static hfcl_lib* make_helper(hfcl_lib* lib) {
   h->device = lib->device;
   share_tables(h, lib);
   h->n_cus = lib->n_cus;
-  bool ok = h->d_counts.grow(N_COUNTERS) == hipSuccess;
+  bool ok = h->d_counts.grow(N_COUNTER_WORDS) == hipSuccess;
   ok = ok && h->h_counts.alloc(N_COUNTERS) == hipSuccess;
   ok = ok && h->d_epa_v0.grow(size_t(h->n_cus) * 16 * (64 / EPA_WE2) * EPA_MAX_VERTS * sizeof(Quad<double>)) == hipSuccess;
   if (!ok) {

@@ -415,12 +415,20 @@ __device__ __forceinline__ EpaSaved<T, EPA_FAST_CAP>* cc_resume_slot(const Work&
 }
 template <typename T, int WE, int CAP>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HFCL_WPE_EPA32_CC, 8)))
-k_epa_loop(Work wk, LibView<T> lib, QParams<T> q) {
+k_epa_loop(Work wk, LibView<T> lib, QParams<T> q, uint32_t pool_share, uint32_t pool_min_refills) {
   constexpr int G = 64 / WE;
   static_assert(WE >= 8, "a group's lanes copy the eight records of a block");
   typedef LaneGroup<WE> Grp;
   __shared__ EpaScratch<T, CAP, V0_TAG> scratch[G];
   const uint32_t cnt = wk.counts[B_COUNT + 3];  // one block per item of the convex x convex queue
+  // Blocks [0, S) are strided over the waves; the rest is drawn by ticket from EPA_POOL_K ranges as waves run out of their own
+  // (hfcl_epa_pool.hpp; S == cnt: no pool, the static schedule).  All of it wave-uniform.
+  constexpr uint32_t K = EPA_POOL_K, POOL_FULL = (1u << K) - 1u;
+  const EpaPoolPlan pool = epa_pool_plan(cnt, gridDim.x, G, pool_share, pool_min_refills, K);
+  const uint32_t S = pool.S;
+  uint32_t* const tickets = wk.counts + EPA_POOL_CTR0;
+  uint32_t dry = pool.len ? 0u : POOL_FULL;  // ranges this wave knows to be empty (counters only grow: for good)
+  uint32_t at = blockIdx.x % K;              // the range it draws from next
   const int lane = threadIdx.x & 63, grp = lane / WE, lig = lane & (WE - 1);
   EpaReady<T>* const ready = reinterpret_cast<EpaReady<T>*>(wk.epa_ready);
   const EpaItem<T>* const queue = reinterpret_cast<const EpaItem<T>*>(wk.epa_queue);
@@ -435,9 +443,30 @@ k_epa_loop(Work wk, LibView<T> lib, QParams<T> q) {
   while (true) {
     const uint64_t live = __ballot(state == LIVE);
     const int n_live = __popcll(live) / WE;
-    const bool more = next < cnt;
+    const bool strided = next < S;
+    const bool more = strided || dry != POOL_FULL;
     if (n_live == 0 || (more && G - n_live >= HFCL_EPA_LOOP_REFILL_MIN)) {
       // ---- refill phase (uniform decision; groups with a live polytope sit it out) ----
+      uint32_t drawn = 0, n_drawn = 0;  // the blocks [drawn, drawn + n_drawn) of the pool, for the idle groups in rank order
+      if (!strided && dry != POOL_FULL) {
+        const uint32_t want = uint32_t(G - n_live);
+        // One atomic by lane 0, nothing read beforehand: a look at the counters first -- lane j at counter j, to skip ranges that others
+        // have drained -- is a second round trip in front of every refill, on lines the atomics are queued on, and cost more than the
+        // pool gains (profiles/r15_a).  A pass without blocks marks its range dry: at most K of them in a wave's life, all at its end.
+        while (dry != POOL_FULL) {
+          at = epa_pool_pick(dry, at, K);
+          uint32_t t = 0u;
+          if (lane == 0) t = __hip_atomic_fetch_add(tickets + at * EPA_POOL_STRIDE_WORDS, want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          t = __builtin_amdgcn_readfirstlane(t);
+          const uint32_t len_at = epa_pool_range_len(pool, cnt, at);
+          n_drawn = epa_pool_take(t, want, len_at);
+          if (epa_pool_drained(t, want, len_at)) dry |= 1u << at;
+          if (n_drawn) {
+            drawn = epa_pool_range_base(pool, at) + t;
+            break;
+          }
+        }
+      }
       if (state != LIVE) {
         if (state != IDLE) {
           EpaReady<T>* rb = ready + it;
@@ -474,8 +503,8 @@ k_epa_loop(Work wk, LibView<T> lib, QParams<T> q) {
         // rank of this group among the groups taking part, in lane order
         const uint64_t lower = live | ~((uint64_t(1) << (grp * WE)) - 1);  // live lanes and lanes >= mine do not count
         const uint32_t rank = uint32_t(__popcll(~lower)) / WE;
-        it = next + rank * gridDim.x;
-        if (it < cnt) {
+        it = strided ? next + rank * gridDim.x : drawn + rank;
+        if (strided ? it < S : rank < n_drawn) {
           const EpaReady<T>* rb = ready + it;
           const uint32_t packed = rb->packed;
           if ((packed & 63u) != 0u) {  // (0 vertices: EPA_READY_NONE, k_epa_prepare wrote the record or queued the seed elsewhere)
@@ -492,7 +521,7 @@ k_epa_loop(Work wk, LibView<T> lib, QParams<T> q) {
           }
         }
       }
-      next += uint32_t(G - n_live) * gridDim.x;
+      if (strided) next += uint32_t(G - n_live) * gridDim.x;
       if (n_live == 0 && !more) {
         if (__ballot(state == LIVE) == 0) break;
       }
@@ -841,9 +870,9 @@ template void launch_epa_fast<double>(int, hipStream_t, const Work&, const LibVi
 void launch_epa_prepare(int grid, hipStream_t st, const Work& wk, const LibView<float>& lv, const IO<float>& io, const QParams<float>& q) {
   hipLaunchKernelGGL((k_epa_prepare<float>), dim3(grid), dim3(256), 0, st, wk, lv, io, q);
 }
-void launch_epa_loop(int grid, hipStream_t st, const Work& wk, const LibView<float>& lv, const QParams<float>& q, int n_cus) {
+void launch_epa_loop(int grid, hipStream_t st, const Work& wk, const LibView<float>& lv, const QParams<float>& q, int n_cus, uint32_t pool_share, uint32_t pool_min_refills) {
   static const int per_cu = resident_blocks_per_cu(k_epa_loop<float, EPA_WE, EPA_FAST_CAP>);
-  hipLaunchKernelGGL((k_epa_loop<float, EPA_WE, EPA_FAST_CAP>), dim3(std::min(grid, n_cus * per_cu * HFCL_EPA_LOOP_ROUNDS)), dim3(64), 0, st, wk, lv, q);
+  hipLaunchKernelGGL((k_epa_loop<float, EPA_WE, EPA_FAST_CAP>), dim3(std::min(grid, n_cus * per_cu * HFCL_EPA_LOOP_ROUNDS)), dim3(64), 0, st, wk, lv, q, pool_share, pool_min_refills);
 }
 void launch_epa_resume_cc(int grid, hipStream_t st, const Work& wk, const LibView<float>& lv, const IO<float>& io, const QParams<float>& q) {
   hipLaunchKernelGGL((k_epa_resume_cc<float, HFCL_EPA_CC_RESUME_WE>), dim3(grid), dim3(64), 0, st, wk, lv, io, q);

@@ -5,12 +5,15 @@
                     iterations + 1).  256-thread form: block b owns the rounds of its four waves (it += groups) and frees its slots when
                     the slowest of the four has ended; single-wave form: every round is a workgroup, placed as slots fall free.
   k_epa_loop        a wave steps 8 polytopes in lockstep and refills when two groups are idle (a refill = 0.25 trip); blocks strided
-                    over one round of resident waves (the tree), or the last share of them drawn by ticket from a pool of counters:
-                    a design that was built, lost its measurement and is NOT in the tree (profiles/r07_a_wave_scheduling.md, HISTORY.md);
-                    its model stays so that the figures quoted there can be reproduced.
+                    over one round of resident waves, and the last share of them (option epa_pool_share, SHIPPED_SHARE percent by
+                    default) drawn by ticket from a pool of 16 counters: csrc/hfcl_epa_pool.hpp is the arithmetic the kernel runs,
+                    model_epa the same on the oracle's iteration counts -- keep the two in step.  The model looks at every counter
+                    in front of a draw, as the form of round 7 did; the kernel in the tree does not (profiles/r15_a_epa_pool.md: the
+                    look cost more than the pool gained), which changes the model's count of atomics at a wave's end, not its trips.
 
 Times are in trips (one lockstep iteration of a wave) and say nothing about waves that share a SIMD speeding up when a partner leaves:
-the device shows less than the model (profiles/r07_a_wave_scheduling.md has both).
+for k_gjk_cvx the device shows less than the model (profiles/r07_a_wave_scheduling.md has both); for k_epa_loop's pool it shows as much
+or more, levelling off at 20 % as here (profiles/r15_a_epa_pool.md).
 
 usage: tools/sched_model.py [--pairs 1000000] [--seed 1] [--cus 256] [--threads 16]"""
 import argparse
@@ -27,6 +30,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 EPA_BLOCK_CAP = 17   # EPA_FAST_CAP: a polytope that needs more iterations leaves k_epa_loop (hand-over)
 REFILL = 0.25        # trips per refill (reproduces HFCL_EPA_LOOP_REFILL_MIN 1 ~ 2, 3 = +4 %; profiles/r05_a)
 REFILL_MIN = 2
+SHIPPED_SHARE = 20   # percent: the default of option epa_pool_share (csrc/hfcl_host.hpp)
 
 
 def oracle_counts(n, seed, threads):
@@ -75,7 +79,7 @@ def model_gjk(iters, cus, setup):
 
 
 def model_epa(lengths, grid, pool_share, k, min_refills, groups=8):
-    """Event-driven: every wave at its next refill, in time order.  pool_share = 0: the static form of the tree; > 0: the dropped pool."""
+    """Event-driven: every wave at its next refill, in time order.  pool_share = 0: every block strided; > 0: that share drawn by ticket."""
     cnt = len(lengths)
     L = np.minimum(lengths, EPA_BLOCK_CAP)
     S = cnt
@@ -158,7 +162,8 @@ def main():
     grid = a.cus * 12
     base = model_epa(epa_len, grid, 0.0, 16, 2)
     print("k_epa_loop  static: waves end at %.0f trips on average, the last at %.0f" % (base["mean_end"], base["last_end"]))
-    for share, k in ((0.1, 1), (0.1, 16), (0.1, 32), (0.2, 16), (0.05, 16)):
+    print("k_epa_loop  the tree draws the last %d %% by ticket (option epa_pool_share)" % SHIPPED_SHARE)
+    for share, k in ((0.1, 1), (0.1, 16), (0.1, 32), (SHIPPED_SHARE / 100.0, 16), (0.05, 16)):
         m = model_epa(epa_len, grid, share, k, 2)
         print("k_epa_loop  pool = last %.0f %% (S = %d), %2d counters: mean %.0f, last %.0f (%+.1f %%), %d atomics (%.0f per counter)" % (
             100 * share, m["S"], k, m["mean_end"], m["last_end"], 100 * (m["last_end"] / base["last_end"] - 1), m["atomics"], m["atomics"] / k))
