@@ -674,17 +674,20 @@ def collide_pairs(pairs, request):
     return out
 
 
-def _scene_run(kind, objects, pair_indices, request, transforms, broadphase=False, inflate=0.0, nearest_bound=None):
+def _scene_run(kind, objects, pair_indices, request, transforms, broadphase=False, inflate=0.0, nearest_bound=None, groups=None):
     """The pair list `pair_indices` ((n_pairs, 2) indices into `objects`) for every configuration: ONE scene call.  broadphase: the
     list is culled per configuration on the device first (boxes grown by `inflate`); rec / g then hold the surviving queries only and
     the last two items are their ids q = c * n_pairs + p and conf_begin (None without broadphase).  nearest_bound (distance only): the
-    pruned minimum (engine.Scene.nearest) with that upper bound; rec then holds one min record per configuration and g is None."""
+    pruned minimum (engine.Scene.nearest) with that upper bound; rec then holds one min record per configuration and g is None.
+    groups (broadphase="self" only): (object_group, collides) for engine.Scene.set_groups."""
     ctx = _context()
     geoms = [o.collisionGeometry() for o in objects]
     ids = np.array([ctx.add(g) for g in geoms], dtype=np.uint32)
     self_pairs = isinstance(broadphase, str) and broadphase == "self"
     if isinstance(broadphase, str) and not self_pairs:
         raise ValueError('broadphase: False, True or "self"')
+    if groups is not None and not self_pairs:
+        raise ValueError('groups filter the pairs the device finds itself: they need broadphase="self" (a pair list already says which pairs)')
     pr = np.ascontiguousarray([] if self_pairs or pair_indices is None else pair_indices, dtype=np.uint32).reshape(-1, 2)
     if len(pr) and int(pr.max()) >= len(objects):
         raise ValueError("pair index outside the objects")
@@ -709,6 +712,8 @@ def _scene_run(kind, objects, pair_indices, request, transforms, broadphase=Fals
     sc = lib.scene(ids, pr)
     try:
         ids = conf_begin = None
+        if groups is not None:
+            sc.set_groups(*groups)
         if nearest_bound is not None:
             summ, rec, _ = sc.nearest(table, request._abi(), float(nearest_bound))
             g = None
@@ -730,7 +735,7 @@ def _scene_run(kind, objects, pair_indices, request, transforms, broadphase=Fals
     return geoms, pr, len(table), rec, summ, g, ids, conf_begin
 
 
-def collide_scene(objects, pair_indices, request, transforms=None, broadphase=False, inflate=0.0):
+def collide_scene(objects, pair_indices, request, transforms=None, broadphase=False, inflate=0.0, groups=None):
     """collide() on the listed pairs of `objects` (CollisionObjects) through a scene: each object's pose goes to the device
     once per configuration, not once per pair.  transforms: None -- one configuration, the objects' own transforms --, an
     array (n_conf, n_objects, 12) of Transform3f images, or n_conf lists of Transform3f.  Returns (results, summaries):
@@ -745,12 +750,16 @@ def collide_scene(objects, pair_indices, request, transforms=None, broadphase=Fa
     the summaries are folds over those (n_contacts and first_contact as without the broadphase).
     broadphase="self": no list at all -- `pair_indices` is ignored (None will do): per configuration the device finds every pair (i < j)
     of `objects` whose grown world AABBs overlap (engine.Scene.collide_self) and evaluates those.  results[c] is a list of
-    ((i, j), CollisionResult), i then j ascending; min_pair / first_contact of a summary are positions in that list."""
+    ((i, j), CollisionResult), i then j ascending; min_pair / first_contact of a summary are positions in that list.
+    groups=(object_group, collides), with broadphase="self" only: a group per object and the symmetric group matrix ((G, G) bools or G
+    uint64 words, G <= 64) -- only pairs whose groups may pair are found (engine.Scene.set_groups; engine.groups_between gives
+    collide(otherManager, callback), engine.groups_excluding an allowed-collision matrix)."""
     if request.num_max_contacts == 0:
         raise ValueError("Invalid number of max contacts (current value is 0).")
     if request.num_max_contacts > 1 and any(isinstance(o.collisionGeometry(), BVHModelOBBRSS) for o in objects):
         raise ValueError("collide_scene: contact lists of mesh pairs (num_max_contacts > 1) go through collide_pairs")
-    geoms, pr, n_conf, rec, summ, g, ids, conf_begin = _scene_run("collide", objects, pair_indices, request, transforms, broadphase, inflate)
+    geoms, pr, n_conf, rec, summ, g, ids, conf_begin = _scene_run("collide", objects, pair_indices, request, transforms, broadphase, inflate,
+                                                                    groups=groups)
     out = []
     for c in range(n_conf):
         row = []
@@ -776,18 +785,22 @@ def collide_scene(objects, pair_indices, request, transforms=None, broadphase=Fa
     return (out[0] if transforms is None and out else out), summ
 
 
-def distance_scene(objects, pair_indices, request, transforms=None, broadphase=False, inflate=0.0, nearest=False, upper_bound=float("inf")):
+def distance_scene(objects, pair_indices, request, transforms=None, broadphase=False, inflate=0.0, nearest=False, upper_bound=float("inf"),
+                   groups=None):
     """distance() on the listed pairs of `objects`: (min_distance array (n_conf, n_pairs), records, summaries); the
     summaries' min_distance is DistanceCallBackDefault's answer per configuration.
     broadphase=True: only the pairs whose world AABBs, each grown by `inflate`, overlap are evaluated (inflate = D / 2 keeps every pair
     whose boxes are within D along each axis: a box-shaped filter, not the manager's traversal with its shrinking bound).  Returns
     (distances, pair indices, summaries): per configuration the array of the surviving pairs' distances and the array of their p.
     broadphase="self": `pair_indices` is ignored; the device finds every pair (i < j) whose grown boxes overlap (engine.Scene.distance_self);
-    the second item is then per configuration the (k, 2) array of those pairs.
+    the second item is then per configuration the (k, 2) array of those pairs.  groups=(object_group, collides), with broadphase="self"
+    only: as in collide_scene.
     nearest=True: the clearance alone -- one DistanceResult per configuration, what DistanceCallBackDefault leaves behind after
     DynamicAABBTreeCollisionManager::distance: the closest listed pair's min_distance, o1 / o2, nearest points, normal, b1 / b2.  The pairs
     are pruned on the device by a bound from their world boxes (engine.Scene.nearest); a configuration whose closest pair is farther than
     `upper_bound` keeps a default DistanceResult."""
+    if nearest and groups is not None:
+        raise ValueError('groups need broadphase="self": the pruned minimum (nearest=True) runs on the pair list')
     if nearest:
         geoms, pr, n_conf, rec, summ, _, _, _ = _scene_run("distance", objects, pair_indices, request, transforms, nearest_bound=upper_bound)
         out = []
@@ -801,7 +814,8 @@ def distance_scene(objects, pair_indices, request, transforms=None, broadphase=F
                 res.nearest_points = [np.array(r["p1"]), np.array(r["p2"])]
             out.append(res)
         return out
-    geoms, pr, n_conf, rec, summ, g, ids, conf_begin = _scene_run("distance", objects, pair_indices, request, transforms, broadphase, inflate)
+    geoms, pr, n_conf, rec, summ, g, ids, conf_begin = _scene_run("distance", objects, pair_indices, request, transforms, broadphase, inflate,
+                                                                    groups=groups)
     if broadphase == "self":  # (distances, (i, j) arrays, summaries): no list; the device finds the pairs whose grown boxes overlap
         cb = conf_begin.astype(np.int64)
         return [rec["distance"][cb[c]:cb[c + 1]] for c in range(n_conf)], [ids[cb[c]:cb[c + 1]] for c in range(n_conf)], summ

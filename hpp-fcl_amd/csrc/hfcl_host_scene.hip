@@ -4,6 +4,7 @@
 #include "hfcl_plan.hpp"
 #include "hfcl_nearest.hpp"
 #include "../../include/hppfcl_amd_nearest.h"
+#include "../../include/hppfcl_amd_groups.h"
 #include "../../include/hppfcl_amd_pairs.h"
 
 // =======================================================================================
@@ -17,6 +18,10 @@ struct hfcl_scene {
   size_t n_objects = 0, n_pairs = 0;
   DevBuf<uint32_t> d_object_shape, d_pairs;
   uint64_t epoch = 0;  // hfcl_lib::shapes_epoch when the scene was made
+  // object groups (hfcl_scene_set_groups; 0: none): an object's group, the groups' row masks, the groups present per column tile
+  size_t n_groups = 0;
+  DevBuf<uint8_t> d_group;
+  DevBuf<uint64_t> d_collides, d_tile_groups;
 };
 
 static int scene_check_pairs(const char* who, const uint32_t* pairs, size_t n_pairs, size_t n_objects) {
@@ -642,6 +647,24 @@ static int pairs_need_device() {
   }
   return HFCL_OK;
 }
+// the entry points of hppfcl_amd_groups.h: a null scene, then a stale one; a table to the device
+static int groups_scene(const char* who, const hfcl_scene* s) {
+  if (!s) {
+    set_error(std::string(who) + ": null scene");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (s->epoch != s->lib->shapes_epoch) {
+    set_error(std::string(who) + ": the library's shapes were replaced (hfcl_lib_set_shapes) after this scene was created; create a new scene");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  return HFCL_OK;
+}
+template <typename W>
+static int groups_upload(DevBuf<W>& dst, const W* src, size_t n) {  // (dst: empty)
+  HIP_TRY(dst.grow(n));
+  HIP_TRY(hipMemcpy(dst, src, n * sizeof(W), hipMemcpyHostToDevice));
+  return HFCL_OK;
+}
 // a scan workgroup adds the counts of PAIRS_SCAN_BLOCK rows in 32 bits: a row has fewer than n_objects entries
 constexpr size_t PAIRS_MAX_OBJECTS = (size_t(1) << 32) / PAIRS_SCAN_BLOCK;
 static int self_pairs_limits(const char* who, const hfcl_scene* s) {
@@ -728,6 +751,9 @@ static int self_pairs_device(const char* who, hfcl_scene* s, const void* d_table
   a.capacity = d_pairs ? capacity : 0;
   a.conf_begin = d_conf_begin;
   a.n_listed = d_n_listed;
+  a.group = s->n_groups ? s->d_group.get() : nullptr;
+  a.collides = s->n_groups ? s->d_collides.get() : nullptr;
+  a.tile_groups = s->n_groups ? s->d_tile_groups.get() : nullptr;
   for (uint64_t g0 = 0; g0 < n_blocks; g0 += per) {  // the boxes of the configurations the chunk touches, then the chunk
     a.g0 = g0;
     a.n_blocks = uint32_t(std::min<uint64_t>(per, n_blocks - g0));
@@ -1427,6 +1453,60 @@ int hfcl_scene_distance_self_f32(hfcl_scene* s, const float* object_pose, size_t
   const SceneCull cull = self_form(inflate, out_capacity, pairs_out, conf_begin_out, n_listed);
   return scene_host<float>("hfcl_scene_distance_self_f32", s, object_pose, n_conf, nullptr, req, out, summary, nullptr, nullptr, &cull);
 }
+
+// ---- object groups of the lists made above (include/hppfcl_amd_groups.h) ---------------------------------------------------------------
+int hfcl_scene_set_groups(hfcl_scene* s, const uint8_t* object_group, size_t n_groups, const uint64_t* collides) {
+  PAIRS_ENTRY;
+  const char* who = "hfcl_scene_set_groups";
+  int rc = groups_scene(who, s);
+  if (rc) return rc;
+  auto refuse = [&](const std::string& why) {
+    set_error(std::string(who) + ": " + why);
+    return HFCL_ERR_INVALID_ARGUMENT;
+  };
+  if (n_groups < 1 || n_groups > PAIRS_MAX_GROUPS) return refuse(std::to_string(n_groups) + " groups (1 to " + std::to_string(PAIRS_MAX_GROUPS) + ")");
+  if (!collides) return refuse("null group matrix");
+  if (s->n_objects && !object_group) return refuse("null group table");
+  for (size_t o = 0; o < s->n_objects; ++o)
+    if (object_group[o] >= n_groups)
+      return refuse("group " + std::to_string(object_group[o]) + " of object " + std::to_string(o) + " is outside the " + std::to_string(n_groups) + " groups");
+  for (size_t g = 0; g < n_groups; ++g) {
+    if (n_groups < 64 && (collides[g] >> n_groups) != 0u)
+      return refuse("word " + std::to_string(g) + " of the group matrix has a bit set at or above the " + std::to_string(n_groups) + " groups");
+    for (size_t h = 0; h < g; ++h)
+      if (((collides[g] >> h) & 1u) != ((collides[h] >> g) & 1u))
+        return refuse("the group matrix is not symmetric: groups " + std::to_string(h) + " and " + std::to_string(g));
+  }
+  // the tables: the masks padded to PAIRS_MAX_GROUPS words, the groups present per column tile (hfcl_pairs.hpp: the sweep skips by them)
+  uint64_t masks[PAIRS_MAX_GROUPS] = {};
+  std::copy(collides, collides + n_groups, masks);
+  const uint32_t n = uint32_t(std::min<size_t>(s->n_objects, 0xFFFFFFFFu));  // (scenes beyond the self forms' limit are refused there)
+  std::vector<uint64_t> tiles(std::max<uint32_t>(pairs_tiles(n), 1u), 0u);
+  for (uint32_t t = 0; t < pairs_tiles(n); ++t) tiles[t] = pairs_tile_word(object_group, n, t);
+  const uint8_t none = 0;
+  HIP_TRY(hipSetDevice(s->lib->device));
+  DevBuf<uint8_t> d_group;
+  DevBuf<uint64_t> d_collides, d_tile_groups;
+  rc = groups_upload(d_group, s->n_objects ? object_group : &none, std::max<size_t>(s->n_objects, 1));
+  if (!rc) rc = groups_upload(d_collides, masks, size_t(PAIRS_MAX_GROUPS));
+  if (!rc) rc = groups_upload(d_tile_groups, tiles.data(), tiles.size());
+  if (rc) return rc;  // (the scene as it was)
+  // (freeing the old tables waits for the device: a query in flight on some stream may still be reading them)
+  s->d_group = std::move(d_group);
+  s->d_collides = std::move(d_collides);
+  s->d_tile_groups = std::move(d_tile_groups);
+  s->n_groups = n_groups;
+  return HFCL_OK;
+}
+int hfcl_scene_clear_groups(hfcl_scene* s) {
+  PAIRS_ENTRY;
+  if (const int rc = groups_scene("hfcl_scene_clear_groups", s)) return rc;
+  HIP_TRY(hipSetDevice(s->lib->device));
+  reset_all(s->d_group, s->d_collides, s->d_tile_groups);  // (waits for the device, as above)
+  s->n_groups = 0;
+  return HFCL_OK;
+}
+size_t hfcl_scene_num_groups(const hfcl_scene* s) { return s ? s->n_groups : 0; }
 #undef PAIRS_ENTRY
 
 // ---- the per-configuration minimum distance with box-bound pruning -----------------------------------------------------------------

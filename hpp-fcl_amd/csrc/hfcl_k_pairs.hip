@@ -10,6 +10,13 @@
 //                         count so far + the ballot's bits below the lane -- ascending by construction --, written below the capacity.
 //   k_pairs_small<EMIT>   scenes of at most 64 objects: a wave per configuration, lane = column j with its grown box in registers, a loop over
 //                         the rows i whose box comes from lane i (readlane); the same counts, the same positions.
+//   k_pairs_sweep_groups<EMIT> / k_pairs_small_groups<EMIT>   the same two forms for a scene with object groups (hppfcl_amd_groups.h):
+//                         a pair is kept iff its boxes touch and bit group[j] of collides[group[i]] is set.  The tiled form -- the second
+//                         instantiation of the body k_pairs_sweep shares with it -- stages a tile's
+//                         group bytes next to its boxes (256 B of LDS), keeps a row's mask wave-uniform, and skips -- in front of the
+//                         barriers, by a decision the whole workgroup shares (pairs_block_mask) -- every column tile none of whose groups
+//                         (tile_groups, built on the host) may pair with any row of the block; a block that may pair with nothing writes
+//                         its rows' zero counts and leaves.  The emit pass takes the same decisions.
 //   k_pairs_scan_sums     a workgroup per PAIRS_SCAN_BLOCK rows of the chunk: their entries
 //   k_pairs_scan_top      one workgroup (the structure of k_cull_scan): exclusive scan of those sums on top of the chunks before
 //   k_pairs_scan_rows     a workgroup per PAIRS_SCAN_BLOCK rows: the rows' offsets, conf_begin of the configurations whose first row is in the
@@ -27,9 +34,11 @@ static __device__ __forceinline__ PairsGeometry pairs_geometry_of(const PairsArg
   return g;
 }
 
-template <bool EMIT>
-__global__ void __launch_bounds__(256) k_pairs_sweep(PairsArgs a) {
+// the body of k_pairs_sweep<EMIT> (GROUPS = false: the code of the kernel as it was) and of k_pairs_sweep_groups<EMIT>
+template <bool EMIT, bool GROUPS>
+static __device__ __forceinline__ void pairs_sweep_body(PairsArgs a) {
   __shared__ double tile[6][PAIRS_TILE];
+  __shared__ uint8_t tile_group[GROUPS ? PAIRS_TILE : 1u];  // (GROUPS: the tile's groups next to its boxes)
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
   const uint32_t n = a.n_objects;
   uint64_t c;
@@ -38,15 +47,32 @@ __global__ void __launch_bounds__(256) k_pairs_sweep(PairsArgs a) {
   const double* __restrict__ boxes = a.boxes + 6u * ((c - a.c_box0) * n);
   const uint64_t chunk_row = c * n + i0 - a.row0;  // the block's first row in the chunk's row arrays
 
+  // GROUPS: the block's mask, from ALL rows of the block -- the same value in the four waves, so that what is skipped in front of the
+  // barriers below is skipped by the whole workgroup.  A block that may pair with nothing leaves; the scan still reads its rows' counts
+  uint64_t block_mask = 0;
+  if (GROUPS) {
+    block_mask = pairs_block_mask(a.group, a.collides, i0, i1);
+    if (block_mask == 0u) {
+      if (!EMIT && threadIdx.x < i1 - i0) a.row_counts[chunk_row + threadIdx.x] = 0u;
+      return;
+    }
+  }
+
   // the wave's rows: i0 + wave * PAIRS_WAVE_ROWS + r (past i1: no row -- its tests fail on j < n with a row index of n)
   double row_box[PAIRS_WAVE_ROWS][6];
   uint32_t row_i[PAIRS_WAVE_ROWS], count[PAIRS_WAVE_ROWS];
   uint64_t pos[PAIRS_WAVE_ROWS];
+  uint64_t row_mask[GROUPS ? PAIRS_WAVE_ROWS : 1u];  // collides[group of the row]: wave-uniform; 0 for a row past i1
   for (uint32_t r = 0; r < PAIRS_WAVE_ROWS; ++r) {
     const uint32_t i = i0 + wave * PAIRS_WAVE_ROWS + r;
     const bool there = i < i1;
     row_i[r] = there ? i : n;
     count[r] = 0u;
+    if (GROUPS) {  // (uniform in the wave, which the compiler cannot see of threadIdx.x >> 6: held in scalar registers, 22 VGPRs fewer)
+      const uint64_t m = there ? a.collides[a.group[i] & 63u] : 0u;
+      const uint32_t lo = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(m)))), hi = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(m >> 32))));
+      row_mask[r] = (uint64_t(hi) << 32) | lo;  // (the builtin returns an int: widened as it is, a low word with its top bit set would fill the high one)
+    }
     double raw[6];
     for (int k = 0; k < 6; ++k) raw[k] = boxes[6u * size_t(there ? i : i0) + k];
     pairs_grow(raw, a.inflate, row_box[r]);
@@ -55,6 +81,7 @@ __global__ void __launch_bounds__(256) k_pairs_sweep(PairsArgs a) {
 
   const double2* __restrict__ vec = reinterpret_cast<const double2*>(boxes);  // (a box: 48 B, three vectors; the table is 16-byte aligned)
   for (uint32_t base = pairs_first_tile(i0); base < n; base += PAIRS_TILE) {
+    if (GROUPS && pairs_tile_skipped(a.tile_groups[base / PAIRS_TILE], block_mask)) continue;  // (workgroup-uniform: no loads, no barrier)
     __syncthreads();  // (the tile before has been read)
     for (uint32_t v = threadIdx.x; v < 3u * PAIRS_TILE; v += 256u) {
       const uint32_t col = v / 3u, part = v - 3u * col;
@@ -65,13 +92,17 @@ __global__ void __launch_bounds__(256) k_pairs_sweep(PairsArgs a) {
         tile[2u * part + 1u][col] = part < 1u ? x.y - a.inflate : x.y + a.inflate;
       }
     }
+    if (GROUPS)
+      for (uint32_t col = threadIdx.x; col < PAIRS_TILE; col += 256u)
+        if (base + col < n) tile_group[col] = a.group[base + col];
     __syncthreads();
     for (uint32_t step = 0; step < PAIRS_TILE; step += 64u) {
       const uint32_t j = base + step + lane;
       double col_box[6];
       for (int k = 0; k < 6; ++k) col_box[k] = tile[k][step + lane];  // (columns past n: stale values, refused by j < n)
+      const uint32_t col_group = GROUPS ? tile_group[step + lane] : 0u;  // (consecutive lanes, consecutive bytes: no bank conflict)
       for (uint32_t r = 0; r < PAIRS_WAVE_ROWS; ++r) {
-        const bool keep = pairs_keep(row_i[r], j, n, row_box[r], col_box);
+        const bool keep = pairs_keep(row_i[r], j, n, row_box[r], col_box) && (!GROUPS || pairs_allowed(row_mask[r], col_group));
         const uint64_t ballot = __ballot(keep);
         if (EMIT && ballot != 0u) {  // (most steps list nothing: cfg5's scene keeps one test in 4 700)
           const uint64_t p = pos[r] + count[r] + cull_rank(ballot, lane);
@@ -84,6 +115,14 @@ __global__ void __launch_bounds__(256) k_pairs_sweep(PairsArgs a) {
   if (!EMIT && lane == 0u)
     for (uint32_t r = 0; r < PAIRS_WAVE_ROWS; ++r)
       if (row_i[r] < n) a.row_counts[chunk_row + wave * PAIRS_WAVE_ROWS + r] = count[r];
+}
+template <bool EMIT>
+__global__ void __launch_bounds__(256) k_pairs_sweep(PairsArgs a) {
+  pairs_sweep_body<EMIT, false>(a);
+}
+template <bool EMIT>
+__global__ void __launch_bounds__(256) k_pairs_sweep_groups(PairsArgs a) {
+  pairs_sweep_body<EMIT, true>(a);
 }
 
 // a wave per configuration (a row block is the configuration: rows_per_block = n_objects <= 64, blocks_per_conf = 1)
@@ -103,6 +142,36 @@ __global__ void __launch_bounds__(256) k_pairs_small(PairsArgs a) {
     double row_box[6];
     for (int k = 0; k < 6; ++k) row_box[k] = __shfl(col_box[k], int(i), 64);
     const bool keep = pairs_keep(i, lane, n, row_box, col_box);
+    const uint64_t ballot = __ballot(keep);
+    if (EMIT) {
+      const uint64_t p = a.row_offsets[chunk_row + i] + cull_rank(ballot, lane);
+      if (keep && p < a.capacity) reinterpret_cast<uint2*>(a.pairs)[p] = make_uint2(i, lane);
+    } else if (lane == 0u) {
+      a.row_counts[chunk_row + i] = cull_popcount(ballot);
+    }
+  }
+}
+// ... with object groups: the lane keeps its column's group, the row's mask is the one of lane i's group (wave-uniform); no tiles.
+// (A kernel of its own, not a second instantiation of a shared body as the tiled form is: with its body moved into an inlined function
+// k_pairs_small<true> allocates 36 registers instead of 34 -- the compiler's handling of the argument block, not the code -- and the
+// kernels without groups are to stay the kernels they were.)
+template <bool EMIT>
+__global__ void __launch_bounds__(256) k_pairs_small_groups(PairsArgs a) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t b = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (b >= a.n_blocks) return;
+  const uint32_t n = a.n_objects;
+  const uint64_t c = a.g0 + b;
+  const double* __restrict__ boxes = a.boxes + 6u * ((c - a.c_box0) * n);
+  const uint64_t chunk_row = c * n - a.row0;
+  double raw[6], col_box[6];
+  for (int k = 0; k < 6; ++k) raw[k] = boxes[6u * size_t(lane < n ? lane : 0u) + k];
+  pairs_grow(raw, a.inflate, col_box);
+  const uint32_t col_group = a.group[lane < n ? lane : 0u];
+  for (uint32_t i = 0; i < n; ++i) {
+    double row_box[6];
+    for (int k = 0; k < 6; ++k) row_box[k] = __shfl(col_box[k], int(i), 64);
+    const bool keep = pairs_keep(i, lane, n, row_box, col_box) && pairs_allowed(a.collides[a.group[i] & 63u], col_group);
     const uint64_t ballot = __ballot(keep);
     if (EMIT) {
       const uint64_t p = a.row_offsets[chunk_row + i] + cull_rank(ballot, lane);
@@ -193,16 +262,17 @@ __global__ void __launch_bounds__(256) k_pairs_scan_rows(PairsArgs a) {
 void launch_pairs_chunk(hipStream_t st, const PairsArgs& a) {
   const uint32_t small_grid = (a.n_blocks + 3u) / 4u;
   const uint32_t n_sums = (a.n_rows + PAIRS_SCAN_BLOCK - 1u) / PAIRS_SCAN_BLOCK;
-  if (a.small)
-    hipLaunchKernelGGL(k_pairs_small<false>, dim3(small_grid), dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL(k_pairs_sweep<false>, dim3(a.n_blocks), dim3(256), 0, st, a);
+  // with object groups (hfcl_scene_set_groups: the three tables come together) the kernels that read them
+  const bool groups = a.group != nullptr;
+  void (*const count)(PairsArgs) = a.small ? (groups ? k_pairs_small_groups<false> : k_pairs_small<false>)
+                                           : (groups ? k_pairs_sweep_groups<false> : k_pairs_sweep<false>);
+  void (*const emit)(PairsArgs) = a.small ? (groups ? k_pairs_small_groups<true> : k_pairs_small<true>)
+                                          : (groups ? k_pairs_sweep_groups<true> : k_pairs_sweep<true>);
+  const dim3 grid(a.small ? small_grid : a.n_blocks);
+  hipLaunchKernelGGL(count, grid, dim3(256), 0, st, a);
   hipLaunchKernelGGL(k_pairs_scan_sums, dim3(n_sums), dim3(256), 0, st, a);
   hipLaunchKernelGGL(k_pairs_scan_top, dim3(1), dim3(256), 0, st, a, n_sums);
   hipLaunchKernelGGL(k_pairs_scan_rows, dim3(n_sums), dim3(256), 0, st, a);
   if (!a.pairs || !a.capacity) return;  // count only
-  if (a.small)
-    hipLaunchKernelGGL(k_pairs_small<true>, dim3(small_grid), dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL(k_pairs_sweep<true>, dim3(a.n_blocks), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(emit, grid, dim3(256), 0, st, a);
 }

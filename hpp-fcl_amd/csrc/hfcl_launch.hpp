@@ -260,5 +260,9 @@ struct PairsArgs {
   uint64_t capacity;
   uint64_t* conf_begin;      // nullptr or n_conf + 1
   uint64_t* n_listed;        // nullptr or one word
+  // object groups (hppfcl_amd_groups.h; hfcl_pairs.hpp has the rule): all three nullptr without groups, which picks the kernels
+  const uint8_t* group;          // n_objects: an object's group
+  const uint64_t* collides;      // PAIRS_MAX_GROUPS words: the row mask of a group
+  const uint64_t* tile_groups;   // a word per column tile of PAIRS_TILE objects: the groups present
 };
 void launch_pairs_chunk(hipStream_t st, const PairsArgs& a);

@@ -85,6 +85,28 @@ HFCL_HD uint64_t pairs_chunk_blocks(const PairsGeometry& geo, uint64_t n_blocks,
   return (n_blocks + n_chunks - 1u) / n_chunks;
 }
 
+// ---- object groups (include/hppfcl_amd_groups.h) -------------------------------------------------------------------------------
+// Every object has a group below PAIRS_MAX_GROUPS; collides[g] is the row mask of an object of group g: bit h set = it may pair with an
+// object of group h.  (i, j) is listed iff pairs_keep and pairs_allowed(collides[group[i]], group[j]).
+constexpr uint32_t PAIRS_MAX_GROUPS = 64u;
+HFCL_HD bool pairs_allowed(uint64_t row_mask, uint32_t col_group) { return ((row_mask >> (col_group & 63u)) & 1u) != 0u; }
+// column tiles of a scene, and the word of tile t: the groups its objects [t PAIRS_TILE, (t + 1) PAIRS_TILE) have, a bit each
+HFCL_HD uint32_t pairs_tiles(uint32_t n_objects) { return (n_objects + PAIRS_TILE - 1u) / PAIRS_TILE; }
+HFCL_HD uint64_t pairs_tile_word(const uint8_t* group, uint32_t n_objects, uint32_t t) {
+  uint64_t word = 0;
+  for (uint32_t j = t * PAIRS_TILE; j < n_objects && j - t * PAIRS_TILE < PAIRS_TILE; ++j) word |= uint64_t(1) << (group[j] & 63u);
+  return word;
+}
+// the mask of a row block: the OR of its rows' masks -- every group some row [i0, i1) of the block may pair with.  One value for the
+// whole block: what it skips is decided in front of a workgroup barrier, so every wave must decide the same
+HFCL_HD uint64_t pairs_block_mask(const uint8_t* group, const uint64_t* collides, uint32_t i0, uint32_t i1) {
+  uint64_t mask = 0;
+  for (uint32_t i = i0; i < i1; ++i) mask |= collides[group[i] & 63u];
+  return mask;
+}
+// a block skips a column tile none of whose groups any of its rows may pair with (a block whose mask is 0 skips them all: it leaves)
+HFCL_HD bool pairs_tile_skipped(uint64_t tile_word, uint64_t block_mask) { return (tile_word & block_mask) == 0u; }
+
 // ---- the scan ----------------------------------------------------------------------------------------------------------------
 // row `row` of the table starts at `offset` with `count` entries: what it says about conf_begin and the total
 HFCL_HD void pairs_row_marks(uint64_t row, uint64_t offset, uint32_t count, uint32_t n_objects, uint64_t total_rows, uint64_t n_conf,

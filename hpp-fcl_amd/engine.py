@@ -53,6 +53,10 @@ PAIRS_SYMBOLS = [
     "hfcl_scene_distance_pairs_device_f32", "hfcl_scene_collide_self", "hfcl_scene_distance_self", "hfcl_scene_collide_self_f32",
     "hfcl_scene_distance_self_f32",
 ]
+# include/hppfcl_amd_groups.h (included by hppfcl_amd.h): object groups and a group matrix for the device-made pair lists
+GROUPS_SYMBOLS = [
+    "hfcl_scene_set_groups", "hfcl_scene_clear_groups", "hfcl_scene_num_groups",
+]
 
 
 class EngineError(RuntimeError):
@@ -104,6 +108,8 @@ def dll():
             d.hfcl_scene_create.restype = C.c_void_p
             d.hfcl_scene_num_objects.restype = C.c_size_t
             d.hfcl_scene_num_pairs.restype = C.c_size_t
+        if hasattr(d, "hfcl_scene_num_groups"):
+            d.hfcl_scene_num_groups.restype = C.c_size_t
         _DLL = d
     return _DLL
 
@@ -206,6 +212,39 @@ def broadphase_pairs_between(aabbs_a, aabbs_b, n_threads=0):
 def _check(rc):
     if rc != 0:
         raise EngineError(rc, last_error())
+
+
+def group_words(collides):
+    """A group matrix as hfcl_scene_set_groups takes it: uint64[G] from a (G, G) bool matrix (bit h of word g = collides[g][h]) or from
+    G words, which pass through."""
+    c = np.asarray(collides)
+    if c.ndim == 2:
+        if c.shape[0] != c.shape[1] or not 1 <= c.shape[0] <= 64:
+            raise ValueError("a group matrix is (G, G) with 1 <= G <= 64")
+        bits = np.uint64(1) << np.arange(c.shape[0], dtype=np.uint64)
+        return np.array([bits[row].sum(dtype=np.uint64) for row in c.astype(bool)], dtype=np.uint64)
+    if c.ndim != 1:
+        raise ValueError("collides: a (G, G) bool matrix or G uint64 words")
+    return np.ascontiguousarray(c, dtype=np.uint64)
+
+
+def groups_between(n_a, n_b):
+    """(object_group, collides) of two managers in one scene: objects [0, n_a) are group 0, [n_a, n_a + n_b) group 1, and only pairs
+    of one object of each are listed -- DynamicAABBTreeCollisionManager::collide(otherManager, callback)."""
+    group = np.zeros(n_a + n_b, dtype=np.uint8)
+    group[n_a:] = 1
+    return group, np.array([2, 1], dtype=np.uint64)
+
+
+def groups_excluding(n_objects, excluded_pairs):
+    """(object_group, collides) with one group per object (n_objects <= 64): every pair of distinct objects is allowed but the
+    excluded ones -- a robot's allowed-collision matrix."""
+    if not 1 <= n_objects <= 64:
+        raise ValueError("one group per object takes scenes of 1 to 64 objects")
+    m = ~np.eye(n_objects, dtype=bool)
+    for i, j in np.asarray(excluded_pairs, dtype=np.int64).reshape(-1, 2):
+        m[i, j] = m[j, i] = False
+    return np.arange(n_objects, dtype=np.uint8), group_words(m)
 
 
 def _dptr(x):
@@ -508,6 +547,26 @@ class Scene:
     @property
     def n_pairs(self):
         return int(dll().hfcl_scene_num_pairs(self._h))
+
+    @property
+    def n_groups(self):
+        """hfcl_scene_num_groups: 0 without groups."""
+        return int(dll().hfcl_scene_num_groups(self._h))
+
+    def set_groups(self, object_group, collides):
+        """hfcl_scene_set_groups: a group per object (uint8[n_objects]) and the symmetric group matrix -- a (G, G) bool matrix or G
+        uint64 words, bit h of word g set = objects of groups g and h may be listed as a pair.  The lists of self_pairs* / collide_self /
+        distance_self then hold the pairs that touch AND whose groups may pair."""
+        g = np.asarray(object_group)
+        if g.shape != (self.n_objects,) or g.size and (g.min() < 0 or g.max() > 255):
+            raise ValueError("object_group: one group in 0..255 per object")
+        g = np.ascontiguousarray(g, dtype=np.uint8)
+        w = group_words(collides)
+        _check(dll().hfcl_scene_set_groups(self._h, abi.ptr(g), C.c_size_t(len(w)), abi.ptr(w)))
+
+    def clear_groups(self):
+        """hfcl_scene_clear_groups: back to every touching pair."""
+        _check(dll().hfcl_scene_clear_groups(self._h))
 
     def set_pairs(self, pairs):
         """hfcl_scene_set_pairs: a new pair list over the same objects (a new broadphase pass)."""

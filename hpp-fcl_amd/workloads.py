@@ -527,6 +527,43 @@ def scene_planner(n_conf=2048, n_objects=16, seed=1, nper=64, link=1.6, bend=0.8
     return PlannerScene(lib, obj_shape, pairs, quat, T)
 
 
+def scene_robot_env(n_conf, n_links, n_obstacles, seed=1, nper=64, link=1.6, bend=0.8, spread=1.0):
+    """A robot in a static environment, for the device-made pair lists with object groups (engine.Scene.set_groups): scene_planner's
+    bent chain of n_links <= 63 bodies per configuration, then n_obstacles bodies of the same shape mix whose pose is the same in
+    every configuration, scattered uniformly through the box the chains sweep over all configurations -- their centres' box grown by
+    the bodies' reach, 1.8, and scaled about its centre by `spread`.  Object order: links first.  Returns (scene, groups, pairs):
+      scene   a PlannerScene (lib, obj_shape, quat, T; obj_tf / obj_pose_f32 are the pose tables) whose pair list is `pairs`;
+      groups  (object_group uint8, collides uint64[n_links + 1]): link k is group k, every obstacle group n_links; allowed are
+              link-link but the chain's neighbours and link-obstacle, not obstacle-obstacle;
+      pairs   the equivalent explicit list: the allowed pairs (i < j) in lexicographic order, uint32 (P, 2)."""
+    if not 1 <= n_links <= 63:
+        raise ValueError("scene_robot_env: 1 to 63 links (a group each, one more for the obstacles)")
+    chain = scene_planner(n_conf, n_links, seed, nper, link, bend)
+    rng = _rng(seed, 78)
+    n = n_links + n_obstacles
+    obj_shape = np.concatenate([chain.obj_shape, rng.integers(0, 5 * nper, n_obstacles).astype(np.uint32)])
+    lo, hi = chain.T.reshape(-1, 3).min(axis=0), chain.T.reshape(-1, 3).max(axis=0)
+    mid, half = (lo + hi) / 2, ((hi - lo) / 2 + 1.8) * spread
+    T_obs = rng.uniform(mid - half, mid + half, (n_obstacles, 3))
+    q_obs = uniform_quaternions(rng, n_obstacles)
+    quat = np.concatenate([chain.quat, np.broadcast_to(q_obs, (n_conf, n_obstacles, 4))], axis=1)
+    T = np.concatenate([chain.T, np.broadcast_to(T_obs, (n_conf, n_obstacles, 3))], axis=1)
+    object_group = np.minimum(np.arange(n), n_links).astype(np.uint8)
+    m = np.ones((n_links + 1, n_links + 1), dtype=bool)
+    k = np.arange(n_links)
+    m[k, k] = False
+    m[k[:-1], k[1:]] = m[k[1:], k[:-1]] = False
+    m[n_links, n_links] = False
+    collides = np.array([(np.uint64(1) << np.flatnonzero(row).astype(np.uint64)).sum(dtype=np.uint64) for row in m], dtype=np.uint64)
+    li, lj = np.triu_indices(n_links, 2)
+    rows = [np.stack([li, lj], axis=1)] + [np.stack([np.full(n_obstacles, i), np.arange(n_links, n)], axis=1) for i in range(n_links)]
+    pairs = np.concatenate(rows).astype(np.int64)
+    pairs = pairs[np.lexsort((pairs[:, 1], pairs[:, 0]))].astype(np.uint32)
+    scene = PlannerScene(chain.lib, obj_shape, np.ascontiguousarray(pairs), np.ascontiguousarray(quat), np.ascontiguousarray(T))
+    scene.name = "scene_robot_env_%dx%d+%d" % (n_conf, n_links, n_obstacles)
+    return scene, (object_group, collides), scene.pairs
+
+
 _MESH_CACHE = {}
 
 

@@ -1530,6 +1530,28 @@ class Scene {
     for (size_t k = 0; k < n; ++k) ctx_.fill((*results)[k], {shape_[pairs[2 * k]], shape_[pairs[2 * k + 1]]}, rec_[k], guess_[k]);
   }
 
+  /// Object groups and a group matrix for the lists of selfPairs / collideSelf / distanceSelf (hfcl_scene_set_groups,
+  /// include/hppfcl_amd_groups.h): object_group[i] < collides.size() <= 64 for every object; bit h of collides[g] set = an object of
+  /// group g and one of group h may be listed; the matrix must be symmetric.  Groups {0 .. 0, 1 .. 1} with collides {2, 1} give what
+  /// DynamicAABBTreeCollisionManager::collide(otherManager, callback) collects; one group per link with the neighbours' bits cleared a
+  /// robot's allowed-collision matrix.  The groups stay until clearGroups(), also when the scene is re-created.
+  void setGroups(const std::vector<uint8_t>& object_group, const std::vector<uint64_t>& collides) {
+    ensure();
+    if (object_group.size() != objects_.size()) throw std::invalid_argument("Scene::setGroups: one group per object");
+    const int rc = hfcl_scene_set_groups(scene_, object_group.data(), collides.size(), collides.data());
+    if (rc) throw_for(rc);
+    group_ = object_group;
+    collides_ = collides;
+  }
+  void clearGroups() {
+    ensure();
+    const int rc = hfcl_scene_clear_groups(scene_);
+    if (rc) throw_for(rc);
+    group_.clear();
+    collides_.clear();
+  }
+  size_t numGroups() const { return hfcl_scene_num_groups(scene_); }
+
   /// The clearance per configuration (hfcl_scene_nearest, include/hppfcl_amd_nearest.h): what DistanceCallBackDefault leaves behind
   /// after DynamicAABBTreeCollisionManager::distance -- the smallest distance over the listed pairs and the pair that has it --, with
   /// the pairs pruned by a bound from their world boxes instead of evaluated one by one.  summaries[c].min_distance / min_pair equal
@@ -1620,6 +1642,10 @@ class Scene {
     if (!scene_) throw_for(HFCL_ERR_INVALID_ARGUMENT);
     lib_ = lib;
     geometries_ = ctx_.numGeometries();
+    if (!collides_.empty()) {  // (the groups of the scene before)
+      const int rc = hfcl_scene_set_groups(scene_, group_.data(), collides_.size(), collides_.data());
+      if (rc) throw_for(rc);
+    }
   }
   std::vector<Transform3f> current() const {
     std::vector<Transform3f> t(objects_.size());
@@ -1630,6 +1656,8 @@ class Scene {
   BatchQueries& ctx_;
   std::vector<CollisionObject*> objects_;
   std::vector<uint32_t> shape_, pairs_;
+  std::vector<uint8_t> group_;      // setGroups: kept for a scene made again
+  std::vector<uint64_t> collides_;
   hfcl_scene* scene_ = nullptr;
   hfcl_lib* lib_ = nullptr;
   size_t geometries_ = 0;

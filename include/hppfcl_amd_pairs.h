@@ -17,6 +17,8 @@
  * option `scene_cull_chunk` is, for these calls, the rows (configuration, object) per chunk (0: automatic, 2^20), and scenes of at most
  * `scene_pairs_small_max` objects (default 32, at most 64) take a wave-per-configuration form of the same test.
  * Limits: n_objects <= 2^22 (HFCL_ERR_LIMIT beyond).  n_conf == 0 or n_objects < 2: HFCL_OK, count 0, conf_begin all zero.
+ * Object groups and a group matrix (hppfcl_amd_groups.h: hfcl_scene_set_groups) leave of this list the pairs whose groups may pair --
+ * a robot's links without their neighbours, a robot against an environment without environment x environment; none set: every pair.
  *
  * Without a HIP device every call below returns HFCL_ERR_NO_DEVICE.  inflate < 0 or NaN: HFCL_ERR_INVALID_ARGUMENT before any work.
  * Invalidation by hfcl_lib_set_shapes, the workspace (the library's, grown on demand: a call that grows it waits for the device) and

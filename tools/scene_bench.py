@@ -22,9 +22,16 @@ configuration) and on workloads.scene_planner at ~1 M queries.
   a  hfcl_scene_self_pairs_device, the count read back, hfcl_scene_collide_pairs_device with records and summaries (device events)
   b  the same list by the route that existed: a scene whose own list is all n (n - 1) / 2 pairs, hfcl_scene_cull_device, the count read
      back, hfcl_scene_collide_listed_device with records and summaries (device events; against a; scenes of at most 256 objects)
+  c  hfcl_scene_self_pairs_device with the workload's object groups set (device events; robot workloads)
+  d  hfcl_scene_collide_self with the groups set, summaries only (host clock)
+  e  the same pairs as an explicit list: hfcl_scene_collide_culled on the workload's pair list, summaries only (host clock; against d;
+     where the call is refused -- the list's workspace does not fit -- the row holds the refusal instead of a time)
+  f  X on the same table without groups (device events; against c: what the skipping saves)
 X .. b ignore the workload's pair list.  --options key=value,... sets library options in the worker (scene_pairs_small_max=0: the tiled form).
 The culled forms run at --inflate (default 0: the reference's manager).  planner2048: scene_planner(2048, 16), 215 040 queries;
-planner2048x32: scene_planner(2048, 32), 952 320 queries.  L .. W report the share of the queries each pass of nearest evaluates.
+planner2048x32: scene_planner(2048, 32), 952 320 queries.  robot16x4096 / robot32x65536: workloads.scene_robot_env, 16 links and 4 096
+obstacles in 256 configurations / 32 links and 65 536 obstacles in 8; rows c .. f run on these alone, and c .. e only in a library that
+has object groups.  They report, from tests/groups_model.py, the share of column tiles the sweep skips and of row blocks that leave at once.  L .. W report the share of the queries each pass of nearest evaluates.
 Rows L .. W import the numpy model of the selection from tests/nearest_model.py: the lists of T .. W (the library keeps its own in its
 workspace) and the fp32 (lb - d_f32) / M come from it; no other row depends on tests/.
 
@@ -49,19 +56,25 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+ROBOTS = {"robot16x4096": (256, 16, 4096), "robot32x65536": (8, 32, 65536)}  # (configurations, links, obstacles)
+
+
 def _workload(pkg, name):
     wl = pkg.workloads
+    if name in ROBOTS:
+        sc, groups, pairs = wl.scene_robot_env(*ROBOTS[name])
+        return sc.lib, sc.obj_shape, pairs, sc.obj_tf, groups
     if name == "cfg5":
         b = wl.cfg5_broadphase_scene()
         sc = b.scene
-        return b.lib, sc["obj_shape"], sc["pairs"], sc["obj_tf"].reshape(1, -1, 12)
+        return b.lib, sc["obj_shape"], sc["pairs"], sc["obj_tf"].reshape(1, -1, 12), None
     if name == "planner2048x32":
         ps = wl.scene_planner(n_conf=2048, n_objects=32)
     elif name == "planner256x64":
         ps = wl.scene_planner(n_conf=256, n_objects=64)
     else:
         ps = wl.scene_planner(n_conf=2048 if name == "planner2048" else 9984, n_objects=16)
-    return ps.lib, ps.obj_shape, ps.pairs, ps.obj_tf
+    return ps.lib, ps.obj_shape, ps.pairs, ps.obj_tf, None
 
 
 def _stats(ms):
@@ -74,7 +87,7 @@ def worker(args):
     import __graft_entry__ as ge
     pkg = ge.load_pkg()
     abi = pkg.abi
-    L, obj_shape, pairs, table = _workload(pkg, args.workload)
+    L, obj_shape, pairs, table, groups = _workload(pkg, args.workload)
     n_conf, G, P = table.shape[0], table.shape[1], len(pairs)
     n = n_conf * P
     i, j = pairs[:, 0], pairs[:, 1]
@@ -114,7 +127,7 @@ def worker(args):
         return _stats(ms)
 
     forms = args.forms.split(",")
-    scene = lib.scene(obj_shape, pairs) if set(forms) & set("BCEFGHIJKLMNOPQRSTUVWXYZab") else None
+    scene = lib.scene(obj_shape, pairs) if set(forms) & set("BCEFGHIJKLMNOPQRSTUVWXYZabcdef") else None
     if "A" in forms or "D" in forms:
         t0 = time.perf_counter()
         s1, s2, tf1, tf2 = expand()
@@ -265,6 +278,45 @@ def worker(args):
         out["forms"]["b"] = device_clock(culled_all_pairs)
         torch.cuda.synchronize()
         every.close()
+    if set(forms) & set("cdef") and groups is not None:  # object groups on the device-made lists, against the explicit list and no groups
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import groups_model
+        d_tab_g = torch.from_numpy(np.ascontiguousarray(table)).to(dev)
+        d_gcb = torch.zeros(n_conf + 1, dtype=torch.int64, device=dev)
+        d_gn = torch.zeros(1, dtype=torch.int64, device=dev)
+        has_groups = hasattr(pkg.engine.dll(), "hfcl_scene_set_groups") and hasattr(scene, "set_groups")
+        skips, tiles, early, blocks = groups_model.skipped(*groups)
+        out["groups"] = {"n_groups": int(len(groups[1])), "tiles_skipped_pct": 100.0 * skips / max(tiles, 1), "blocks_left_early_pct": 100.0 * early / blocks,
+                         "box_tests": n_conf * G * (G - 1) // 2, "allowed_pairs": n_conf * P}
+
+        def count_only():
+            scene.self_pairs_device(d_tab_g, n_conf, args.inflate, None, 0, d_gcb, d_gn, stream=st)
+            return int(d_gn.item())
+        if has_groups and set(forms) & set("cde"):
+            scene.set_groups(*groups)
+            cap_g = max(count_only(), 1)
+            out["groups"]["n_listed"] = cap_g
+            d_gp = torch.zeros(2 * cap_g, dtype=torch.int32, device=dev)
+            if "c" in forms:
+                out["forms"]["c"] = device_clock(lambda: scene.self_pairs_device(d_tab_g, n_conf, args.inflate, d_gp, cap_g, d_gcb, d_gn, stream=st))
+            if "d" in forms:
+                summ_d = scene.collide_self(table, req, args.inflate, records=False)[3]
+                out["forms"]["d"] = host_clock(lambda: scene.collide_self(table, req, args.inflate, records=False))
+            del d_gp
+            scene.clear_groups()
+            if "e" in forms:
+                try:
+                    summ_e = scene.collide_culled(table, args.inflate, req, records=False, want_ids=False)[3]
+                    out["forms"]["e"] = host_clock(lambda: scene.collide_culled(table, args.inflate, req, records=False, want_ids=False))
+                    if "d" in forms:
+                        out["groups"]["d_equals_e"] = bool(all(summ_d[k].tobytes() == summ_e[k].tobytes() for k in ("min_distance", "n_contacts", "n_skipped")))
+                except pkg.EngineError as err:
+                    out["groups"]["e_refused"] = str(err)
+        if "f" in forms:
+            cap_f = max(count_only(), 1)
+            out["groups"]["n_listed_without_groups"] = cap_f
+            d_fp = torch.zeros(2 * cap_f, dtype=torch.int32, device=dev)
+            out["forms"]["f"] = device_clock(lambda: scene.self_pairs_device(d_tab_g, n_conf, args.inflate, d_fp, cap_f, d_gcb, d_gn, stream=st))
     torch.cuda.synchronize()
     if scene is not None:
         scene.close()
@@ -289,7 +341,7 @@ def bytes_moved(n_conf, G, P):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--worker", action="store_true")
-    ap.add_argument("--workload", default="cfg5", choices=["cfg5", "planner", "planner2048", "planner2048x32", "planner256x64"])
+    ap.add_argument("--workload", default="cfg5", choices=["cfg5", "planner", "planner2048", "planner2048x32", "planner256x64"] + sorted(ROBOTS))
     ap.add_argument("--workloads", default="cfg5,planner", help="the workloads of a full run, comma-separated")
     ap.add_argument("--inflate", type=float, default=0.0)
     ap.add_argument("--options", default="", help="library options of the worker: key=value,...")
@@ -338,7 +390,7 @@ def main():
         print("| form | build | median ms | min .. max ms (over the runs) |")
         print("|---|---|---|---|")
         for which in ("parent", "new", "control"):
-            for f in "ABCDEFGHIJKLMNOPQRSTUVWXYZab":
+            for f in "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdef":
                 runs = [r["forms"][f] for r in rs if r["build"] == which and f in r["forms"]]
                 if runs:
                     print("| %s | %s | %s | %.3f .. %.3f |" % (f, which, " / ".join("%.3f" % x["median_ms"] for x in runs),
@@ -355,6 +407,13 @@ def main():
             k = r0["self_pairs"]
             print("self pairs at inflate %g: %d pairs listed of %d box tests (%.3f %%)" % (args.inflate, k["n_listed"], k["box_tests"],
                                                                                           100.0 * k["n_listed"] / max(k["box_tests"], 1)))
+        gs = [r["groups"] for r in rs if "n_listed" in r.get("groups", {})] or [r["groups"] for r in rs if "groups" in r]
+        if gs:
+            k = gs[0]
+            print("object groups: %d groups; %.1f %% of the column tiles skipped, %.1f %% of the row blocks leave at once; %s listed with groups, %s without, of "
+                  "%d box tests; %d allowed pairs in the explicit list; summaries of d equal those of e: %s%s" % (
+                      k["n_groups"], k["tiles_skipped_pct"], k["blocks_left_early_pct"], k.get("n_listed", "-"), k.get("n_listed_without_groups", "-"),
+                      k["box_tests"], k["allowed_pairs"], k.get("d_equals_e", "-"), "; e refused: " + k["e_refused"] if "e_refused" in k else ""))
         if "n_listed" in r0:
             print("cull at inflate %g: %d of %d queries survive (%.2f %%); byte model of the cull alone: %.0f bytes" % (
                 r0["inflate"], r0["n_listed"], r0["queries"], 100.0 * r0["n_listed"] / r0["queries"], r0["cull_model_bytes"]))

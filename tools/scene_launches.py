@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """What the scene entry points launch and compute, for comparing two builds of the library (HFCL_LIB_PATH selects one): every family of
-hfcl_scene_* once -- scene (host and device), boxes, cull, listed, culled, nearest (host and device) --, fp64 then fp32, on
+hfcl_scene_* once -- scene (host and device), boxes, cull, listed, culled, nearest (host and device), the self pairs without groups
+(host, device, collide_self / distance_self) --, fp64 then fp32, on
 workloads.scene_planner(64, 16): 6720 queries, far below the size at which a chunk runs split.  scene_chunk and scene_cull_chunk are set
 so that every call runs in three chunks (the listed, culled and nearest forms: a third of their list, read from a call before).
 
@@ -109,6 +110,17 @@ def run(out_dir):
         d_sum, d_min = d_zeros(n_conf * 6), d_zeros(n_conf * words)
         n_eval = (scene.nearest_device_f32 if f32 else scene.nearest_device)(d_tab, n_conf, dreq, d_sum, d_min, stream=st)
         dump(p + "nearest_device", d_sum, d_min, np.array(n_eval, dtype=np.int64))
+        # the pairs made on the device, no list and no groups: host, device, and the narrow phase on them (rows in three chunks)
+        lib.set_option("scene_cull_chunk", -(-n_conf * G // 3))
+        sp, sp_cb = scene.self_pairs(tab, 0.25)
+        dump(p + "self_pairs", sp, sp_cb)
+        d_sp, d_cb, d_n = d_zeros(2 * len(sp)), d_zeros(n_conf + 1, torch.int64), d_zeros(1, torch.int64)
+        scene.self_pairs_device(d_tab, n_conf, 0.25, d_sp, len(sp), d_cb, d_n, f32=f32, stream=st)
+        dump(p + "self_pairs_device", d_sp, d_cb, d_n)
+        thirds(len(sp))
+        for kind, req in (("collide", creq), ("distance", dreq)):
+            dump(p + kind + "_self", *getattr(scene, kind + "_self")(tab, req, 0.25), host=True)
+        lib.set_option("scene_cull_chunk", -(-total // 3))
     torch.cuda.synchronize()
     scene.close()
     lib.close()
