@@ -115,6 +115,9 @@ SCENE_SUMMARY_DTYPE = np.dtype([("min_distance", "<f8"), ("min_pair", "<u4"), ("
                                 ("n_skipped", "<u4")])
 assert SCENE_SUMMARY_DTYPE.itemsize == 24
 SCENE_NONE = 0xFFFFFFFF
+# hfcl_scene_clearance (include/hppfcl_amd_nearest_self.h)
+SCENE_CLEARANCE_DTYPE = np.dtype([("min_distance", "<f8"), ("min_i", "<u4"), ("min_j", "<u4"), ("n_evaluated", "<u4"), ("n_skipped", "<u4")])
+assert SCENE_CLEARANCE_DTYPE.itemsize == 24
 
 
 def fold_records(records, n_pairs, security_margin=None):

@@ -678,7 +678,8 @@ def _scene_run(kind, objects, pair_indices, request, transforms, broadphase=Fals
     """The pair list `pair_indices` ((n_pairs, 2) indices into `objects`) for every configuration: ONE scene call.  broadphase: the
     list is culled per configuration on the device first (boxes grown by `inflate`); rec / g then hold the surviving queries only and
     the last two items are their ids q = c * n_pairs + p and conf_begin (None without broadphase).  nearest_bound (distance only): the
-    pruned minimum (engine.Scene.nearest) with that upper bound; rec then holds one min record per configuration and g is None.
+    pruned minimum (engine.Scene.nearest; with broadphase="self" engine.Scene.nearest_self, the summaries then being its clearances) with
+    that upper bound; rec then holds one min record per configuration and g is None.
     groups (broadphase="self" only): (object_group, collides) for engine.Scene.set_groups."""
     ctx = _context()
     geoms = [o.collisionGeometry() for o in objects]
@@ -714,7 +715,10 @@ def _scene_run(kind, objects, pair_indices, request, transforms, broadphase=Fals
         ids = conf_begin = None
         if groups is not None:
             sc.set_groups(*groups)
-        if nearest_bound is not None:
+        if nearest_bound is not None and self_pairs:  # (summ: the clearances, hfcl_scene_clearance)
+            summ, rec, _ = sc.nearest_self(table, request._abi(), float(nearest_bound))
+            g = None
+        elif nearest_bound is not None:
             summ, rec, _ = sc.nearest(table, request._abi(), float(nearest_bound))
             g = None
         elif self_pairs:  # (ids: the listed pairs (i, j) themselves)
@@ -798,17 +802,26 @@ def distance_scene(objects, pair_indices, request, transforms=None, broadphase=F
     nearest=True: the clearance alone -- one DistanceResult per configuration, what DistanceCallBackDefault leaves behind after
     DynamicAABBTreeCollisionManager::distance: the closest listed pair's min_distance, o1 / o2, nearest points, normal, b1 / b2.  The pairs
     are pruned on the device by a bound from their world boxes (engine.Scene.nearest); a configuration whose closest pair is farther than
-    `upper_bound` keeps a default DistanceResult."""
-    if nearest and groups is not None:
+    `upper_bound` keeps a default DistanceResult.  With broadphase="self" there is no list and no inflate: the clearance over every
+    pair (i < j) the `groups` allow, the pairs made and pruned on the device (engine.Scene.nearest_self) --
+    DynamicAABBTreeCollisionManager::distance(otherManager, DistanceCallBackDefault) with two groups."""
+    self_pairs = isinstance(broadphase, str) and broadphase == "self"
+    if nearest and groups is not None and not self_pairs:
         raise ValueError('groups need broadphase="self": the pruned minimum (nearest=True) runs on the pair list')
     if nearest:
-        geoms, pr, n_conf, rec, summ, _, _, _ = _scene_run("distance", objects, pair_indices, request, transforms, nearest_bound=upper_bound)
+        geoms, pr, n_conf, rec, summ, _, _, _ = _scene_run("distance", objects, pair_indices, request, transforms, "self" if self_pairs else False,
+                                                           nearest_bound=upper_bound, groups=groups)
         out = []
         for c in range(n_conf):
             res = DistanceResult()
-            p, r = int(summ["min_pair"][c]), rec[c]
-            if p != abi.SCENE_NONE and float(summ["min_distance"][c]) <= upper_bound:
-                res.min_distance, res.o1, res.o2 = float(r["distance"]), geoms[pr[p][0]], geoms[pr[p][1]]
+            r = rec[c]
+            if self_pairs:
+                i, j = int(summ["min_i"][c]), int(summ["min_j"][c])
+            else:
+                p = int(summ["min_pair"][c])
+                i, j = (int(pr[p][0]), int(pr[p][1])) if p != abi.SCENE_NONE else (abi.SCENE_NONE, abi.SCENE_NONE)
+            if i != abi.SCENE_NONE and float(summ["min_distance"][c]) <= upper_bound:
+                res.min_distance, res.o1, res.o2 = float(r["distance"]), geoms[i], geoms[j]
                 res.b1, res.b2 = int(r["b1"]), int(r["b2"])
                 res.normal = np.array(r["normal"])
                 res.nearest_points = [np.array(r["p1"]), np.array(r["p2"])]

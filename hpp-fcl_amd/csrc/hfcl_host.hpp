@@ -316,6 +316,17 @@ struct hfcl_lib {
     DevBuf<uint64_t> d_row_offsets, d_row_sum_offsets;
     size_t rows_cap = 0;
     DevBuf<uint32_t> d_pair_list;  // (two words an entry)
+    // the clearance on device-made pairs (hfcl_scene_nearest_self*): a row seed per row of the table, seed and threshold by
+    // configuration, per pass the list of pairs with its conf_begin, its summaries and -- when min records are asked for -- its records,
+    // and the host forms' clearances
+    DevBuf<void> d_ns_row_seeds;
+    DevBuf<uint64_t> d_ns_seed;
+    DevBuf<double> d_ns_thr;
+    DevBuf<uint32_t> d_ns_list[2];  // (two words an entry)
+    DevBuf<uint64_t> d_ns_conf_begin[2];
+    DevBuf<hfcl_scene_summary> d_ns_summary[2];
+    DevBuf<void> d_ns_rec[2];
+    DevBuf<hfcl_scene_clearance> d_ns_out;
   } scene;
   // local AABB of every library shape (hfcl_cull.hpp: shape_local_box; BVH models: the box of their vertices), 6 doubles each, rebuilt when
   // shapes or meshes were registered since (hfcl_lib_set_shapes, hfcl_lib_add_bvh)

@@ -3,8 +3,10 @@
 #include "hfcl_host.hpp"
 #include "hfcl_plan.hpp"
 #include "hfcl_nearest.hpp"
+#include "hfcl_nearest_self.hpp"
 #include "../../include/hppfcl_amd_nearest.h"
 #include "../../include/hppfcl_amd_groups.h"
+#include "../../include/hppfcl_amd_nearest_self.h"
 #include "../../include/hppfcl_amd_pairs.h"
 
 // =======================================================================================
@@ -699,6 +701,51 @@ static int pairs_chunk_buffers(hfcl_lib* lib, size_t rows) {
   return HFCL_OK;
 }
 
+// what every sweep over a scene's row blocks gives its kernels, whatever it lists: the geometry, the chunk's row arrays, the groups
+static void pairs_args(PairsArgs& a, const hfcl_scene* s, const PairsGeometry& geo, bool small, size_t n_conf) {
+  hfcl_lib::SceneWs& w = s->lib->scene;
+  a.boxes = w.d_boxes;
+  a.n_objects = geo.n_objects;
+  a.rows_per_block = geo.rows_per_block;
+  a.blocks_per_conf = geo.blocks_per_conf;
+  a.small = small ? 1 : 0;
+  a.total_rows = uint64_t(n_conf) * geo.n_objects;
+  a.n_conf = n_conf;
+  a.inflate = 0.0;
+  a.row_counts = w.d_row_counts;
+  a.row_offsets = w.d_row_offsets;
+  a.sums = w.d_row_sums;
+  a.sum_offsets = w.d_row_sum_offsets;
+  a.running = w.d_running;
+  a.pairs = nullptr;
+  a.capacity = 0;
+  a.conf_begin = nullptr;
+  a.n_listed = nullptr;
+  a.group = s->n_groups ? s->d_group.get() : nullptr;
+  a.collides = s->n_groups ? s->d_collides.get() : nullptr;
+  a.tile_groups = s->n_groups ? s->d_tile_groups.get() : nullptr;
+}
+// the chunks of n_blocks row blocks, `per` a chunk, in turn: the boxes of the configurations a chunk touches (w.d_boxes), then
+// per_chunk() with a's chunk members set
+template <typename T, typename F>
+static void pairs_chunks(PairsArgs& a, const hfcl_scene* s, const void* d_table, const PairsGeometry& geo, uint64_t n_blocks, uint64_t per,
+                         hipStream_t st, F&& per_chunk) {
+  hfcl_lib* lib = s->lib;
+  const uint32_t n = geo.n_objects;
+  for (uint64_t g0 = 0; g0 < n_blocks; g0 += per) {
+    a.g0 = g0;
+    a.n_blocks = uint32_t(std::min<uint64_t>(per, n_blocks - g0));
+    a.row0 = pairs_block_row(geo, g0);
+    a.n_rows = uint32_t(pairs_block_row(geo, g0 + a.n_blocks) - a.row0);
+    a.first = g0 == 0 ? 1 : 0;
+    a.c_box0 = g0 / geo.blocks_per_conf;
+    const uint64_t c_last = (g0 + a.n_blocks - 1) / geo.blocks_per_conf;
+    const char* rows = static_cast<const char*>(d_table) + a.c_box0 * n * SceneTypes<T>::WIDTH * sizeof(T);
+    launch_cull_aabbs(st, rows, std::is_same<T, float>::value, s->d_object_shape, lib->d_local_boxes, n, (c_last - a.c_box0 + 1) * n, lib->scene.d_boxes);
+    per_chunk();
+  }
+}
+
 // The list of the whole table on st: the pairs (below `capacity`), conf_begin, the count.  Nothing is read back.
 template <typename T>
 static int self_pairs_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, double inflate, uint32_t* d_pairs, size_t capacity,
@@ -732,40 +779,14 @@ static int self_pairs_device(const char* who, hfcl_scene* s, const void* d_table
   HIP_TRY(w.d_boxes.grow(conf_per_chunk * n * 6));
   rc = pairs_chunk_buffers(lib, size_t(std::min<uint64_t>(per * geo.rows_per_block, uint64_t(n_conf) * n)));
   if (rc) return rc;
-  constexpr bool f32 = std::is_same<T, float>::value;
   PairsArgs a;
-  a.boxes = w.d_boxes;
-  a.n_objects = n;
-  a.rows_per_block = geo.rows_per_block;
-  a.blocks_per_conf = geo.blocks_per_conf;
-  a.small = small ? 1 : 0;
-  a.total_rows = uint64_t(n_conf) * n;
-  a.n_conf = n_conf;
+  pairs_args(a, s, geo, small, n_conf);
   a.inflate = inflate;
-  a.row_counts = w.d_row_counts;
-  a.row_offsets = w.d_row_offsets;
-  a.sums = w.d_row_sums;
-  a.sum_offsets = w.d_row_sum_offsets;
-  a.running = w.d_running;
   a.pairs = d_pairs;
   a.capacity = d_pairs ? capacity : 0;
   a.conf_begin = d_conf_begin;
   a.n_listed = d_n_listed;
-  a.group = s->n_groups ? s->d_group.get() : nullptr;
-  a.collides = s->n_groups ? s->d_collides.get() : nullptr;
-  a.tile_groups = s->n_groups ? s->d_tile_groups.get() : nullptr;
-  for (uint64_t g0 = 0; g0 < n_blocks; g0 += per) {  // the boxes of the configurations the chunk touches, then the chunk
-    a.g0 = g0;
-    a.n_blocks = uint32_t(std::min<uint64_t>(per, n_blocks - g0));
-    a.row0 = pairs_block_row(geo, g0);
-    a.n_rows = uint32_t(pairs_block_row(geo, g0 + a.n_blocks) - a.row0);
-    a.first = g0 == 0 ? 1 : 0;
-    a.c_box0 = g0 / geo.blocks_per_conf;
-    const uint64_t c_last = (g0 + a.n_blocks - 1) / geo.blocks_per_conf;
-    const char* rows = static_cast<const char*>(d_table) + a.c_box0 * n * SceneTypes<T>::WIDTH * sizeof(T);
-    launch_cull_aabbs(st, rows, f32, s->d_object_shape, lib->d_local_boxes, n, (c_last - a.c_box0 + 1) * n, w.d_boxes);
-    launch_pairs_chunk(st, a);
-  }
+  pairs_chunks<T>(a, s, d_table, geo, n_blocks, per, st, [&]() { launch_pairs_chunk(st, a); });
   HIP_TRY(hipGetLastError());
   return HFCL_OK;
 }
@@ -826,12 +847,12 @@ static int self_pairs_host(const char* who, hfcl_scene* s, const void* table, si
 }
 
 // The device form on a list of pairs.  The list is not checked: i < j < n_objects, conf_begin its spans -- as hfcl_scene_self_pairs_device
-// leaves them.
+// leaves them.  counts: as scene_chunks_device takes them.
 template <typename T>
 static int scene_pairs_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const uint32_t* d_pairs, size_t n_listed,
                               const uint64_t* d_conf_begin, const hfcl_collision_request* creq, const hfcl_distance_request* dreq,
                               typename SceneTypes<T>::R* d_out, hfcl_scene_summary* d_summary, const hfcl_guess* d_gin, hfcl_guess* d_gout,
-                              hipStream_t st) {
+                              hipStream_t st, SceneCountSlots* counts = nullptr) {
   size_t total;
   int rc = scene_validate<T>(who, s, d_table, n_conf, creq, dreq, d_out, d_summary, total, &hfcl_scene::n_objects);
   if (rc) return rc;
@@ -857,7 +878,7 @@ static int scene_pairs_device(const char* who, hfcl_scene* s, const void* d_tabl
   SceneList list{nullptr, d_conf_begin, n_conf};
   list.d_pairs = d_pairs;
   list.shares = uint32_t(pairs_shares(n_listed, s->n_objects));
-  return scene_chunks_device<T>(s, d_table, &list, n_listed, creq, dreq, d_out, d_summary, d_gin, d_gout, st);
+  return scene_chunks_device<T>(s, d_table, &list, n_listed, creq, dreq, d_out, d_summary, d_gin, d_gout, st, counts);
 }
 
 // what the culled host forms (hfcl_scene_*_culled) add to scene_host
@@ -1187,6 +1208,189 @@ static int nearest_host(const char* who, hfcl_scene* s, const void* table, size_
   return host_batch_checks(lib, nullptr, req);
 }
 
+// ---------------------------------------------------------------------------------------
+// The clearance per configuration on device-made pairs (include/hppfcl_amd_nearest_self.h: hfcl_scene_nearest_self*).
+// hfcl_k_nearest_self.hip has the kernels, hfcl_nearest_self.hpp the arithmetic.  Five walks of the all-pairs sweep, each in the chunks of
+// self_pairs_device with the boxes made per chunk: the seeds; count and emit of pass 1, its count read back, its narrow phase through
+// scene_pairs_device into summaries of its own; the thresholds; the same for pass 2; the two combined.  Two read-backs of 8 bytes.
+// ---------------------------------------------------------------------------------------
+template <typename T>
+static int nearest_self_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, const hfcl_distance_request* req,
+                                 double upper, const void* out) {
+  if (upper != upper) {
+    set_error(std::string(who) + ": upper_bound is NaN");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (s && !req) {
+    set_error("null request");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (s && !out) {
+    set_error(std::string(who) + ": null output");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (s) {
+    QParams<T> q;
+    if (const int rc = setup_distance<T>(req, q)) return rc;
+  }
+  const int rc = self_validate<T>(who, s, table, n_conf);
+  return rc ? rc : self_pairs_limits(who, s);
+}
+
+// table on the device, n_conf > 0, at least two objects, everything on st (which is waited for twice)
+template <typename T>
+static int nearest_self_run(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const hfcl_distance_request* req, double upper,
+                            hfcl_scene_clearance* d_out, typename SceneTypes<T>::R* d_min, size_t* n_evaluated, SceneCountSlots* counts,
+                            hipStream_t st) {
+  using R = typename SceneTypes<T>::R;
+  constexpr bool f32 = std::is_same<T, float>::value;
+  hfcl_lib* lib = s->lib;
+  hfcl_lib::SceneWs& w = lib->scene;
+  int rc = ensure_local_boxes(lib);
+  if (rc) return rc;
+  const uint32_t n = uint32_t(s->n_objects);
+  const bool small = n <= std::min(lib->opt.scene_pairs_small_max, PAIRS_SMALL_MAX);
+  const PairsGeometry geo = pairs_geometry(n, small);
+  const uint64_t n_blocks = uint64_t(n_conf) * geo.blocks_per_conf;
+  const uint64_t per = pairs_chunk_blocks(geo, n_blocks, lib->opt.scene_cull_chunk);
+  const size_t conf_per_chunk = std::min<size_t>(n_conf, size_t(per / geo.blocks_per_conf) + 2);
+  const size_t rows = n_conf * size_t(n);
+  HIP_TRY(w.d_boxes.grow(conf_per_chunk * n * 6));
+  rc = pairs_chunk_buffers(lib, size_t(std::min<uint64_t>(per * geo.rows_per_block, rows)));
+  if (rc) return rc;
+  if (!small) HIP_TRY(w.d_ns_row_seeds.grow(rows * sizeof(NselfRowSeed)));
+  HIP_TRY(w.d_ns_seed.grow(n_conf));
+  HIP_TRY(w.d_ns_thr.grow(n_conf));
+  for (int l = 0; l < 2; ++l) {
+    HIP_TRY(w.d_ns_conf_begin[l].grow(n_conf + 1));
+    HIP_TRY(w.d_ns_summary[l].grow(n_conf));
+    HIP_TRY(w.d_ns_list[l].grow(2 * pairs_capacity_guess(rows)));
+  }
+
+  NselfArgs a{};
+  pairs_args(a.p, s, geo, small, n_conf);
+  a.r = f32 ? NEAREST_R32 : NEAREST_R64;
+  a.upper = upper;
+  a.row_seeds = small ? nullptr : w.d_ns_row_seeds.get();
+  a.seed = w.d_ns_seed;
+  a.thr = w.d_ns_thr;
+  pairs_chunks<T>(a.p, s, d_table, geo, n_blocks, per, st, [&]() { launch_nself_seed(st, a); });
+  if (!small) launch_nself_seed_combine(st, a, lib->n_cus * 16);
+
+  uint64_t n_list[2] = {0, 0};
+  for (int pass = 1; pass <= 2; ++pass) {
+    const int l = pass - 1;
+    if (pass == 2) {  // thr[c] = min(D, min_distance of pass 1)
+      NearestArgs t{};
+      t.c.n_conf = n_conf;
+      t.upper = upper;
+      t.thr = w.d_ns_thr;
+      launch_nearest_threshold(st, t, w.d_ns_summary[0]);
+    }
+    a.pass = pass;
+    a.p.conf_begin = w.d_ns_conf_begin[l];
+    a.p.n_listed = w.d_running + 1;
+    rc = list_and_count(w.d_ns_list[l], true, w.d_running + 1, st, n_list[l], [&]() {  // the pass's list, and the one read-back: its count
+      a.p.pairs = w.d_ns_list[l];
+      a.p.capacity = w.d_ns_list[l].capacity() / 2;
+      pairs_chunks<T>(a.p, s, d_table, geo, n_blocks, per, st, [&]() { launch_nself_chunk(st, a); });
+      return int(HFCL_OK);
+    }, 2);
+    if (!rc) rc = pairs_rank_limit(who, n_list[l], n);
+    if (rc) return rc;
+    if (d_min) HIP_TRY(w.d_ns_rec[l].grow(size_t(n_list[l]) * sizeof(R)));
+    rc = scene_pairs_device<T>(who, s, d_table, n_conf, w.d_ns_list[l], size_t(n_list[l]), w.d_ns_conf_begin[l], nullptr, req,
+                               d_min ? static_cast<R*>(w.d_ns_rec[l].get()) : nullptr, w.d_ns_summary[l], nullptr, nullptr, st, counts);
+    if (rc) return rc;
+  }
+  NselfCombineArgs g{};
+  g.n_conf = n_conf;
+  for (int l = 0; l < 2; ++l) {
+    g.summary[l] = w.d_ns_summary[l];
+    g.pairs[l] = w.d_ns_list[l];
+    g.conf_begin[l] = w.d_ns_conf_begin[l];
+    g.rec[l] = d_min ? w.d_ns_rec[l].get() : nullptr;
+  }
+  g.out = d_out;
+  g.min_out = d_min;
+  launch_nself_combine(st, g, f32);
+  if (n_evaluated) {
+    n_evaluated[0] = size_t(n_list[0]);
+    n_evaluated[1] = size_t(n_list[1]);
+  }
+  HIP_TRY(hipGetLastError());
+  return HFCL_OK;
+}
+
+template <typename T>
+static int nearest_self_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const hfcl_distance_request* req, double upper,
+                               hfcl_scene_clearance* d_out, typename SceneTypes<T>::R* d_min, size_t* n_evaluated, hipStream_t st) {
+  const int rc = nearest_self_validate<T>(who, s, d_table, n_conf, req, upper, d_out);
+  if (rc) return rc;
+  if (n_evaluated) n_evaluated[0] = n_evaluated[1] = 0;
+  if (!n_conf) return HFCL_OK;
+  hfcl_lib* lib = s->lib;
+  HIP_TRY(hipSetDevice(lib->device));
+  if (s->n_objects < 2) {  // no pair: every configuration is one without records
+    NselfCombineArgs g{};
+    g.n_conf = n_conf;
+    g.out = d_out;
+    g.min_out = d_min;
+    launch_nself_combine(st, g, std::is_same<T, float>::value);
+    HIP_TRY(hipGetLastError());
+    return HFCL_OK;
+  }
+  return nearest_self_run<T>(who, s, d_table, n_conf, req, upper, d_out, d_min, n_evaluated, nullptr, st);
+}
+
+template <typename T>
+static int nearest_self_host(const char* who, hfcl_scene* s, const void* table, size_t n_conf, const hfcl_distance_request* req, double upper,
+                             hfcl_scene_clearance* out, typename SceneTypes<T>::R* min_records, size_t* n_evaluated) {
+  using R = typename SceneTypes<T>::R;
+  int rc = nearest_self_validate<T>(who, s, table, n_conf, req, upper, out);
+  if (rc) return rc;
+  if (n_evaluated) n_evaluated[0] = n_evaluated[1] = 0;
+  if (!n_conf) return HFCL_OK;
+  if (s->n_objects < 2) {
+    const hfcl_scene_summary* no_summary[2] = {nullptr, nullptr};
+    const uint32_t* no_pairs[2] = {nullptr, nullptr};
+    const uint64_t* no_begin[2] = {nullptr, nullptr};
+    const R* no_rec[2] = {nullptr, nullptr};
+    for (size_t c = 0; c < n_conf; ++c) nself_combine<R>(c, no_summary, no_pairs, no_begin, no_rec, out[c], min_records ? &min_records[c] : nullptr);
+    return HFCL_OK;
+  }
+  hfcl_lib* lib = s->lib;
+  hfcl_lib::SceneWs& w = lib->scene;
+  HIP_TRY(hipSetDevice(lib->device));
+  rc = scene_host_stream(w);
+  if (rc) return rc;
+  HIP_TRY(w.d_ns_out.grow(n_conf));
+  if (min_records) HIP_TRY(w.d_minrec.grow(n_conf * sizeof(R)));
+  rc = SceneCountSlots::ready(w);
+  if (rc) return rc;
+  SceneCountSlots counts(lib);  // (ends after finish has waited for the streams)
+  auto finish = [&](int code) {  // nothing of this call stays in flight, whatever happened
+    const bool synced = hipStreamSynchronize(w.s_cmp) == hipSuccess;
+    if (lib->side) hipStreamSynchronize(lib->side);
+    if (code == HFCL_OK && synced) counts.harvest_rest();
+    if (code == HFCL_OK && !synced) {
+      set_error(std::string(who) + ": the device reported an error");
+      return int(HFCL_ERR_HIP);
+    }
+    return code;
+  };
+  rc = scene_table_in(w, table, n_conf * s->n_objects * SceneTypes<T>::WIDTH * sizeof(T));
+  if (!rc) rc = nearest_self_run<T>(who, s, w.d_table, n_conf, req, upper, w.d_ns_out, min_records ? static_cast<R*>(w.d_minrec.get()) : nullptr,
+                                    n_evaluated, &counts, w.s_cmp);
+  if (!rc && hipMemcpyAsync(out, w.d_ns_out, n_conf * sizeof(hfcl_scene_clearance), hipMemcpyDeviceToHost, w.s_cmp) != hipSuccess) rc = HFCL_ERR_HIP;
+  if (!rc && min_records && hipMemcpyAsync(min_records, w.d_minrec, n_conf * sizeof(R), hipMemcpyDeviceToHost, w.s_cmp) != hipSuccess)
+    rc = HFCL_ERR_HIP;
+  rc = finish(rc);
+  if (rc) return rc;
+  lib->last_host = true;
+  return host_batch_checks(lib, nullptr, req);
+}
+
 extern "C" {
 
 hfcl_scene* hfcl_scene_create(hfcl_lib* lib, const uint32_t* object_shape, size_t n_objects, const uint32_t* pairs, size_t n_pairs) {
@@ -1507,6 +1711,31 @@ int hfcl_scene_clear_groups(hfcl_scene* s) {
   return HFCL_OK;
 }
 size_t hfcl_scene_num_groups(const hfcl_scene* s) { return s ? s->n_groups : 0; }
+
+// ---- the clearance per configuration on device-made pairs (include/hppfcl_amd_nearest_self.h) -------------------------------------------
+int hfcl_scene_nearest_self(hfcl_scene* s, const double* object_tf, size_t n_conf, const hfcl_distance_request* req, double upper_bound,
+                            hfcl_scene_clearance* out, hfcl_result* min_records, size_t* n_evaluated) {
+  PAIRS_ENTRY;
+  return nearest_self_host<double>("hfcl_scene_nearest_self", s, object_tf, n_conf, req, upper_bound, out, min_records, n_evaluated);
+}
+int hfcl_scene_nearest_self_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, const hfcl_distance_request* req, double upper_bound,
+                                hfcl_scene_clearance* out, hfcl_result_f32* min_records, size_t* n_evaluated) {
+  PAIRS_ENTRY;
+  return nearest_self_host<float>("hfcl_scene_nearest_self_f32", s, object_pose, n_conf, req, upper_bound, out, min_records, n_evaluated);
+}
+int hfcl_scene_nearest_self_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const hfcl_distance_request* req, double upper_bound,
+                                   hfcl_scene_clearance* d_out, hfcl_result* d_min_records, size_t* n_evaluated, void* stream) {
+  PAIRS_ENTRY;
+  return nearest_self_device<double>("hfcl_scene_nearest_self_device", s, d_object_tf, n_conf, req, upper_bound, d_out, d_min_records, n_evaluated,
+                                     (hipStream_t)stream);
+}
+int hfcl_scene_nearest_self_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, const hfcl_distance_request* req,
+                                       double upper_bound, hfcl_scene_clearance* d_out, hfcl_result_f32* d_min_records, size_t* n_evaluated,
+                                       void* stream) {
+  PAIRS_ENTRY;
+  return nearest_self_device<float>("hfcl_scene_nearest_self_device_f32", s, d_object_pose, n_conf, req, upper_bound, d_out, d_min_records,
+                                    n_evaluated, (hipStream_t)stream);
+}
 #undef PAIRS_ENTRY
 
 // ---- the per-configuration minimum distance with box-bound pruning -----------------------------------------------------------------

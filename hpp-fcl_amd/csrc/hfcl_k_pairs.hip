@@ -259,9 +259,16 @@ __global__ void __launch_bounds__(256) k_pairs_scan_rows(PairsArgs a) {
   }
 }
 
+// the scan of a chunk's row counts (also behind the counts of hfcl_k_nearest_self.hip)
+void launch_pairs_scan(hipStream_t st, const PairsArgs& a) {
+  const uint32_t n_sums = (a.n_rows + PAIRS_SCAN_BLOCK - 1u) / PAIRS_SCAN_BLOCK;
+  hipLaunchKernelGGL(k_pairs_scan_sums, dim3(n_sums), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_pairs_scan_top, dim3(1), dim3(256), 0, st, a, n_sums);
+  hipLaunchKernelGGL(k_pairs_scan_rows, dim3(n_sums), dim3(256), 0, st, a);
+}
+
 void launch_pairs_chunk(hipStream_t st, const PairsArgs& a) {
   const uint32_t small_grid = (a.n_blocks + 3u) / 4u;
-  const uint32_t n_sums = (a.n_rows + PAIRS_SCAN_BLOCK - 1u) / PAIRS_SCAN_BLOCK;
   // with object groups (hfcl_scene_set_groups: the three tables come together) the kernels that read them
   const bool groups = a.group != nullptr;
   void (*const count)(PairsArgs) = a.small ? (groups ? k_pairs_small_groups<false> : k_pairs_small<false>)
@@ -270,9 +277,7 @@ void launch_pairs_chunk(hipStream_t st, const PairsArgs& a) {
                                           : (groups ? k_pairs_sweep_groups<true> : k_pairs_sweep<true>);
   const dim3 grid(a.small ? small_grid : a.n_blocks);
   hipLaunchKernelGGL(count, grid, dim3(256), 0, st, a);
-  hipLaunchKernelGGL(k_pairs_scan_sums, dim3(n_sums), dim3(256), 0, st, a);
-  hipLaunchKernelGGL(k_pairs_scan_top, dim3(1), dim3(256), 0, st, a, n_sums);
-  hipLaunchKernelGGL(k_pairs_scan_rows, dim3(n_sums), dim3(256), 0, st, a);
+  launch_pairs_scan(st, a);
   if (!a.pairs || !a.capacity) return;  // count only
   hipLaunchKernelGGL(emit, grid, dim3(256), 0, st, a);
 }

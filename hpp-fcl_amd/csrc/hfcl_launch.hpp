@@ -266,3 +266,34 @@ struct PairsArgs {
   const uint64_t* tile_groups;   // a word per column tile of PAIRS_TILE objects: the groups present
 };
 void launch_pairs_chunk(hipStream_t st, const PairsArgs& a);
+// (hfcl_k_pairs.hip) the three scan launches of launch_pairs_chunk alone, behind a count kernel of another unit that left a.row_counts
+void launch_pairs_scan(hipStream_t st, const PairsArgs& a);
+
+// hfcl_k_nearest_self.hip: the clearance per configuration on device-made pairs (hfcl_scene_nearest_self*; hfcl_nearest_self.hpp has the
+// arithmetic).  The row blocks, chunks and row arrays are those of PairsArgs (p.inflate unused: nothing is inflated).
+struct NselfArgs {
+  PairsArgs p;
+  double r;                  // the bound's rounding term: NEAREST_R64 / NEAREST_R32
+  double upper;              // the caller's upper bound D
+  int pass;                  // launch_nself_chunk: 1 / 2
+  void* row_seeds;           // tiled form: a NselfRowSeed per row of the WHOLE table (a configuration may straddle chunks)
+  uint64_t* seed;            // n_conf pairs as words (nself_key; NSELF_NO_PAIR: no candidate)
+  const double* thr;         // n_conf: read by pass 2
+};
+// a chunk's part of the seeds: the tiled form writes its rows' row_seeds, the small form seed[c] of its configurations
+void launch_nself_seed(hipStream_t st, const NselfArgs& a);
+// tiled form, after the last chunk: seed[c] from the rows' partials, a wave per configuration
+void launch_nself_seed_combine(hipStream_t st, const NselfArgs& a, int max_blocks);
+// a chunk of pass a.pass: count, launch_pairs_scan, emit (p.pairs == nullptr / capacity 0: count only)
+void launch_nself_chunk(hipStream_t st, const NselfArgs& a);
+// the two passes' summaries, lists and records into the clearance and the min record of every configuration (null conf_begin: no list)
+struct NselfCombineArgs {
+  uint64_t n_conf;
+  const hfcl_scene_summary* summary[2];
+  const uint32_t* pairs[2];
+  const uint64_t* conf_begin[2];
+  const void* rec[2];        // nullptr: no min records
+  hfcl_scene_clearance* out;
+  void* min_out;             // nullptr or n_conf records
+};
+void launch_nself_combine(hipStream_t st, const NselfCombineArgs& a, bool f32);

@@ -57,6 +57,10 @@ PAIRS_SYMBOLS = [
 GROUPS_SYMBOLS = [
     "hfcl_scene_set_groups", "hfcl_scene_clear_groups", "hfcl_scene_num_groups",
 ]
+# include/hppfcl_amd_nearest_self.h (included by hppfcl_amd.h): the clearance per configuration on device-made pairs
+NEAREST_SELF_SYMBOLS = [
+    "hfcl_scene_nearest_self", "hfcl_scene_nearest_self_f32", "hfcl_scene_nearest_self_device", "hfcl_scene_nearest_self_device_f32",
+]
 
 
 class EngineError(RuntimeError):
@@ -877,6 +881,37 @@ class Scene:
         n = (C.c_size_t * 2)()
         _check(dll().hfcl_scene_nearest_device_f32(self._h, _dptr(d_object_pose), C.c_size_t(int(n_conf)), C.byref(req),
                                                    C.c_double(upper_bound), _dptr(d_summary), _dptr(d_min_records), n, C.c_void_p(stream)))
+        return int(n[0]), int(n[1])
+
+    # ---- the clearance per configuration on device-made pairs (include/hppfcl_amd_nearest_self.h) ----
+    def nearest_self(self, object_tf, req=None, upper_bound=float("inf"), records=True):
+        """hfcl_scene_nearest_self{,_f32}: (clearance SCENE_CLEARANCE_DTYPE[n_conf], min_records, n_evaluated) from the pose table and the
+        scene's groups alone -- no pair list, no inflate.  min_distance / (min_i, min_j) are those of distance() on the explicit list of
+        every allowed pair wherever that minimum is <= upper_bound (elsewhere: some value above it, or +inf); min record c is that
+        pair's record (records=False: None); n_evaluated: the pairs the two narrow-phase passes evaluated.  (n_conf, n_objects, 7)
+        float32 poses take the fp32 path."""
+        tf, f32 = self._any_table(object_tf)
+        n_conf = len(tf)
+        out = np.zeros(n_conf, dtype=abi.SCENE_CLEARANCE_DTYPE)
+        rec = np.zeros(n_conf, dtype=abi.RESULT_F32_DTYPE if f32 else abi.RESULT_DTYPE) if records else None
+        n = (C.c_size_t * 2)()
+        fn = dll().hfcl_scene_nearest_self_f32 if f32 else dll().hfcl_scene_nearest_self
+        _check(fn(self._h, abi.ptr(tf), C.c_size_t(n_conf), C.byref(req or abi.default_distance_request()), C.c_double(upper_bound),
+                  abi.ptr(out), abi.ptr(rec), n))
+        return out, rec, (int(n[0]), int(n[1]))
+
+    def nearest_self_device(self, d_object_tf, n_conf, req, d_out, d_min_records=None, upper_bound=float("inf"), stream=0):
+        """hfcl_scene_nearest_self_device: device tensors or pointers, enqueued on `stream`, which the call waits on twice (the two list
+        counts).  Returns n_evaluated."""
+        n = (C.c_size_t * 2)()
+        _check(dll().hfcl_scene_nearest_self_device(self._h, _dptr(d_object_tf), C.c_size_t(int(n_conf)), C.byref(req), C.c_double(upper_bound),
+                                                    _dptr(d_out), _dptr(d_min_records), n, C.c_void_p(stream)))
+        return int(n[0]), int(n[1])
+
+    def nearest_self_device_f32(self, d_object_pose, n_conf, req, d_out, d_min_records=None, upper_bound=float("inf"), stream=0):
+        n = (C.c_size_t * 2)()
+        _check(dll().hfcl_scene_nearest_self_device_f32(self._h, _dptr(d_object_pose), C.c_size_t(int(n_conf)), C.byref(req),
+                                                        C.c_double(upper_bound), _dptr(d_out), _dptr(d_min_records), n, C.c_void_p(stream)))
         return int(n[0]), int(n[1])
 
 

@@ -665,6 +665,8 @@ int hfcl_scene_distance_device_f32(hfcl_scene* s, const float* d_object_pose, si
 #include "hppfcl_amd_nearest.h"
 /* object groups and a group matrix for the pair lists a scene makes on the device (below) */
 #include "hppfcl_amd_groups.h"
+/* the clearance per configuration over every allowed pair of objects: the pairs made and pruned on the device, no list, no inflate */
+#include "hppfcl_amd_nearest_self.h"
 /* the self-collision pairs of a scene per configuration, made on the device, and the scene calls on such a list */
 #include "hppfcl_amd_pairs.h"
 #endif /* HPPFCL_AMD_H */

@@ -1576,6 +1576,31 @@ class Scene {
       if (summaries[c].min_pair != 0xFFFFFFFFu) ctx_.fill((*results)[c], shape_pair(summaries[c].min_pair), rec_[c], g);
   }
 
+  /// The clearance per configuration from the poses and the groups alone (hfcl_scene_nearest_self, include/hppfcl_amd_nearest_self.h):
+  /// DynamicAABBTreeCollisionManager::distance(otherManager, DistanceCallBackDefault) -- the smallest distance over every pair of objects
+  /// the groups allow (setGroups; none: all pairs) and the pair that has it, the pairs made and pruned on the device: no pair list, no
+  /// inflate.  clearances[c].min_distance / min_i / min_j equal what distance() on the explicit list of all allowed pairs gives wherever
+  /// that minimum is <= upper_bound (+inf: always); elsewhere min_distance is some value above upper_bound, or +inf.  results: nullptr or
+  /// one DistanceResult per configuration, filled from the closest pair's record; a configuration without one keeps a default
+  /// DistanceResult.
+  void nearestSelf(const Transform3f* tables, size_t n_conf, const DistanceRequest& request, double upper_bound,
+                   std::vector<hfcl_scene_clearance>& clearances, std::vector<DistanceResult>* results = nullptr, size_t* n_evaluated = nullptr) {
+    ensure();
+    const hfcl_distance_request a = to_abi(request);
+    clearances.resize(n_conf);
+    if (results) rec_.resize(n_conf);
+    const int rc = hfcl_scene_nearest_self(scene_, reinterpret_cast<const double*>(tables), n_conf, &a, upper_bound, clearances.data(),
+                                           results ? rec_.data() : nullptr, n_evaluated);
+    if (rc) throw_for(rc);
+    if (!results) return;
+    results->assign(n_conf, DistanceResult());
+    hfcl_guess g;
+    std::memset(&g, 0, sizeof(g));
+    g.gjk_guess[0] = 1.0;  // (DistanceResult's own default: no guess comes back from this call)
+    for (size_t c = 0; c < n_conf; ++c)
+      if (clearances[c].min_i != 0xFFFFFFFFu) ctx_.fill((*results)[c], {shape_[clearances[c].min_i], shape_[clearances[c].min_j]}, rec_[c], g);
+  }
+
  private:
   size_t list_guess(size_t n_conf) const {
     const size_t total = n_conf * numPairs();

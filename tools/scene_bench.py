@@ -27,11 +27,20 @@ configuration) and on workloads.scene_planner at ~1 M queries.
   e  the same pairs as an explicit list: hfcl_scene_collide_culled on the workload's pair list, summaries only (host clock; against d;
      where the call is refused -- the list's workspace does not fit -- the row holds the refusal instead of a time)
   f  X on the same table without groups (device events; against c: what the skipping saves)
+  g  hfcl_scene_nearest_self with the groups set, summaries only: the clearance from the poses and the groups alone (host clock)
+  h  hfcl_scene_nearest_self_device, summaries only (device events)            i, j  the same two through the fp32 path
+  k  the same answer from the explicit list: hfcl_scene_nearest on the workload's pair list, summaries only (host clock; against g; a
+     refusal is kept in the place of a time, as in e)        l  hfcl_scene_nearest_device (device events; against h)
+  m, n  the same two through the fp32 path
+  o  the same answer from a guessed box filter: hfcl_scene_distance_self with the groups set, summaries only, `inflate` = the scene's true
+     clearance taken from g -- the best possible guess (host clock; against g)        p  the same through the fp32 path
+  q  o on the device: hfcl_scene_self_pairs_device at that inflate, the count read back, hfcl_scene_distance_pairs_device, summaries only
+     (device events; against h)        r  the same through the fp32 path
 X .. b ignore the workload's pair list.  --options key=value,... sets library options in the worker (scene_pairs_small_max=0: the tiled form).
 The culled forms run at --inflate (default 0: the reference's manager).  planner2048: scene_planner(2048, 16), 215 040 queries;
 planner2048x32: scene_planner(2048, 32), 952 320 queries.  robot16x4096 / robot32x65536: workloads.scene_robot_env, 16 links and 4 096
-obstacles in 256 configurations / 32 links and 65 536 obstacles in 8; rows c .. f run on these alone, and c .. e only in a library that
-has object groups.  They report, from tests/groups_model.py, the share of column tiles the sweep skips and of row blocks that leave at once.  L .. W report the share of the queries each pass of nearest evaluates.
+obstacles in 256 configurations / 32 links and 65 536 obstacles in 8; rows c .. r run on these alone, and c .. e only in a library that
+has object groups, g .. r only in one that has hfcl_scene_nearest_self.  They report, from tests/groups_model.py, the share of column tiles the sweep skips and of row blocks that leave at once.  L .. W report the share of the queries each pass of nearest evaluates.
 Rows L .. W import the numpy model of the selection from tests/nearest_model.py: the lists of T .. W (the library keeps its own in its
 workspace) and the fp32 (lb - d_f32) / M come from it; no other row depends on tests/.
 
@@ -127,7 +136,7 @@ def worker(args):
         return _stats(ms)
 
     forms = args.forms.split(",")
-    scene = lib.scene(obj_shape, pairs) if set(forms) & set("BCEFGHIJKLMNOPQRSTUVWXYZabcdef") else None
+    scene = lib.scene(obj_shape, pairs) if set(forms) & set("BCEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqr") else None
     if "A" in forms or "D" in forms:
         t0 = time.perf_counter()
         s1, s2, tf1, tf2 = expand()
@@ -174,7 +183,7 @@ def worker(args):
     if "I" in forms:
         d_rec2 = torch.zeros(max(len(ids), 1) * 24, dtype=torch.int32, device=dev)
         out["forms"]["I"] = device_clock(lambda: culled_device(d_tab64, d_rec2, False))
-    if set(forms) & set("JKPQRSVW"):
+    if set(forms) & set("JKPQRSVWijmnpr"):
         # 7-float poses of the same table: quaternions from the rotation matrices (w from the trace; the planner's and cfg5's rotations are
         # generic, no w near 0)
         R = pkg.geometry.pose_R(table.reshape(-1, 12))
@@ -317,6 +326,60 @@ def worker(args):
             out["groups"]["n_listed_without_groups"] = cap_f
             d_fp = torch.zeros(2 * cap_f, dtype=torch.int32, device=dev)
             out["forms"]["f"] = device_clock(lambda: scene.self_pairs_device(d_tab_g, n_conf, args.inflate, d_fp, cap_f, d_gcb, d_gn, stream=st))
+    if set(forms) & set("ghijklmnopqr") and groups is not None and hasattr(scene, "nearest_self"):  # the clearance on device-made pairs
+        dreq = abi.default_distance_request()
+        d_clear = torch.zeros(n_conf * 6, dtype=torch.int32, device=dev)
+        d_sum5 = torch.zeros(n_conf * 6, dtype=torch.int32, device=dev)
+        d_ncb = torch.zeros(n_conf + 1, dtype=torch.int64, device=dev)
+        d_nn = torch.zeros(1, dtype=torch.int64, device=dev)
+        info = out["nearest_self"] = {"candidates": n_conf * P}
+        for f32, letters in ((False, "ghkloq"), (True, "ijmnpr")):
+            if not set(forms) & set(letters):
+                continue
+            tab = pose if f32 else table
+            d_t = d_pose if f32 else torch.from_numpy(np.ascontiguousarray(table)).to(dev)
+            tag = "f32" if f32 else "f64"
+            scene.set_groups(*groups)
+            clear, _, n_eval = scene.nearest_self(tab, dreq, records=False)
+            info["evaluated_" + tag] = list(n_eval)
+            true_clearance = float(max(clear["min_distance"].max(), 0.0))
+            info["inflate_" + tag] = true_clearance
+            if letters[0] in forms:
+                out["forms"][letters[0]] = host_clock(lambda: scene.nearest_self(tab, dreq, records=False))
+            if letters[1] in forms:
+                fn = scene.nearest_self_device_f32 if f32 else scene.nearest_self_device
+                out["forms"][letters[1]] = device_clock(lambda: fn(d_t, n_conf, dreq, d_clear, None, stream=st))
+            if letters[4] in forms:
+                summ_o = scene.distance_self(tab, dreq, true_clearance, records=False)[3]
+                info["o_equal_" + tag] = bool(summ_o["min_distance"].tobytes() == clear["min_distance"].tobytes())
+                out["forms"][letters[4]] = host_clock(lambda: scene.distance_self(tab, dreq, true_clearance, records=False))
+            if letters[5] in forms:
+                def count_at():
+                    scene.self_pairs_device(d_t, n_conf, true_clearance, None, 0, d_ncb, d_nn, f32=f32, stream=st)
+                    return int(d_nn.item())
+                cap_q = max(count_at(), 1)
+                info["listed_at_inflate_" + tag] = cap_q
+                d_qp = torch.zeros(2 * cap_q, dtype=torch.int32, device=dev)
+                pairs_fn = scene.distance_pairs_device_f32 if f32 else scene.distance_pairs_device
+
+                def filtered_device():
+                    scene.self_pairs_device(d_t, n_conf, true_clearance, d_qp, cap_q, d_ncb, d_nn, f32=f32, stream=st)
+                    k = int(d_nn.item())  # the one read-back: 8 bytes
+                    pairs_fn(d_t, n_conf, d_qp, min(k, cap_q), d_ncb, dreq, None, d_sum5, stream=st)
+                out["forms"][letters[5]] = device_clock(filtered_device)
+                del d_qp
+            scene.clear_groups()
+            try:  # the explicit list
+                summ_k, _, n_k = (scene.nearest_f32 if f32 else scene.nearest)(tab, dreq, records=False)
+                info["k_equal_" + tag] = bool(summ_k["min_distance"].tobytes() == clear["min_distance"].tobytes() and tuple(n_k) == tuple(n_eval))
+                if letters[2] in forms:
+                    near = scene.nearest_f32 if f32 else scene.nearest
+                    out["forms"][letters[2]] = host_clock(lambda: near(tab, dreq, records=False))
+                if letters[3] in forms:
+                    near_d = scene.nearest_device_f32 if f32 else scene.nearest_device
+                    out["forms"][letters[3]] = device_clock(lambda: near_d(d_t, n_conf, dreq, d_sum5, None, stream=st))
+            except pkg.EngineError as err:
+                info["k_refused_" + tag] = str(err)
     torch.cuda.synchronize()
     if scene is not None:
         scene.close()
@@ -390,7 +453,7 @@ def main():
         print("| form | build | median ms | min .. max ms (over the runs) |")
         print("|---|---|---|---|")
         for which in ("parent", "new", "control"):
-            for f in "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdef":
+            for f in "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqr":
                 runs = [r["forms"][f] for r in rs if r["build"] == which and f in r["forms"]]
                 if runs:
                     print("| %s | %s | %s | %.3f .. %.3f |" % (f, which, " / ".join("%.3f" % x["median_ms"] for x in runs),
@@ -414,6 +477,9 @@ def main():
                   "%d box tests; %d allowed pairs in the explicit list; summaries of d equal those of e: %s%s" % (
                       k["n_groups"], k["tiles_skipped_pct"], k["blocks_left_early_pct"], k.get("n_listed", "-"), k.get("n_listed_without_groups", "-"),
                       k["box_tests"], k["allowed_pairs"], k.get("d_equals_e", "-"), "; e refused: " + k["e_refused"] if "e_refused" in k else ""))
+        ns = [r["nearest_self"] for r in rs if "nearest_self" in r]
+        if ns:
+            print("clearance on device-made pairs: " + json.dumps(ns[-1]))
         if "n_listed" in r0:
             print("cull at inflate %g: %d of %d queries survive (%.2f %%); byte model of the cull alone: %.0f bytes" % (
                 r0["inflate"], r0["n_listed"], r0["queries"], 100.0 * r0["n_listed"] / r0["queries"], r0["cull_model_bytes"]))
