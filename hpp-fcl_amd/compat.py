@@ -674,21 +674,31 @@ def collide_pairs(pairs, request):
     return out
 
 
-def _scene_run(kind, objects, pair_indices, request, transforms, broadphase=False, inflate=0.0, nearest_bound=None, groups=None):
+def _scene_run(kind, objects, pair_indices, request, transforms, broadphase=False, inflate=0.0, nearest_bound=None, groups=None, n_moving=None):
     """The pair list `pair_indices` ((n_pairs, 2) indices into `objects`) for every configuration: ONE scene call.  broadphase: the
     list is culled per configuration on the device first (boxes grown by `inflate`); rec / g then hold the surviving queries only and
     the last two items are their ids q = c * n_pairs + p and conf_begin (None without broadphase).  nearest_bound (distance only): the
     pruned minimum (engine.Scene.nearest; with broadphase="self" engine.Scene.nearest_self, the summaries then being its clearances) with
     that upper bound; rec then holds one min record per configuration and g is None.
-    groups (broadphase="self" only): (object_group, collides) for engine.Scene.set_groups."""
+    groups (broadphase="self" or "env"): (object_group, collides) for engine.Scene.set_groups.
+    broadphase="env", n_moving=K: as "self" for a scene whose objects[K:] stand still at their own transforms (engine.Scene.set_environment);
+    `transforms` then holds the K moving objects' alone, and no pair of two environment objects is listed."""
     ctx = _context()
     geoms = [o.collisionGeometry() for o in objects]
     ids = np.array([ctx.add(g) for g in geoms], dtype=np.uint32)
-    self_pairs = isinstance(broadphase, str) and broadphase == "self"
+    env = isinstance(broadphase, str) and broadphase == "env"
+    self_pairs = isinstance(broadphase, str) and broadphase == "self" or env
     if isinstance(broadphase, str) and not self_pairs:
-        raise ValueError('broadphase: False, True or "self"')
+        raise ValueError('broadphase: False, True, "self" or "env"')
     if groups is not None and not self_pairs:
-        raise ValueError('groups filter the pairs the device finds itself: they need broadphase="self" (a pair list already says which pairs)')
+        raise ValueError('groups filter the pairs the device finds itself: they need broadphase="self" or "env" (a pair list already says which pairs)')
+    if env != (n_moving is not None):
+        raise ValueError('broadphase="env" and n_moving go together')
+    if env and not 0 <= int(n_moving) <= len(objects):
+        raise ValueError("n_moving outside the objects")
+    if env and nearest_bound is not None:
+        raise ValueError('the pruned minimum (nearest=True) takes full tables: broadphase="self"')
+    n_table = int(n_moving) if env else len(objects)  # objects a configuration of `transforms` holds
     pr = np.ascontiguousarray([] if self_pairs or pair_indices is None else pair_indices, dtype=np.uint32).reshape(-1, 2)
     if len(pr) and int(pr.max()) >= len(objects):
         raise ValueError("pair index outside the objects")
@@ -703,10 +713,12 @@ def _scene_run(kind, objects, pair_indices, request, transforms, broadphase=Fals
         if not engine.dll().hfcl_pair_supported(int(t1), int(t2), int(kind == "distance")):
             raise ValueError("%s function between node type %d and node type %d is not yet supported." %
                              ("Distance" if kind == "distance" else "Collision", t1, t2))
+    own = lambda objs: np.concatenate([o.getTransform()._abi().reshape(1, 12) for o in objs] + [np.zeros((0, 12))])  # noqa: E731
     if transforms is None:
-        table = np.concatenate([o.getTransform()._abi().reshape(1, 12) for o in objects]).reshape(1, len(objects), 12)
+        table = own(objects[:n_table]).reshape(1, n_table, 12)
     elif isinstance(transforms, np.ndarray):
-        table = np.ascontiguousarray(transforms, dtype=np.float64).reshape(-1, len(objects), 12)
+        table = np.ascontiguousarray(transforms, dtype=np.float64)
+        table = table.reshape(-1, n_table, 12) if n_table else table.reshape(len(table) if table.ndim == 3 else 0, 0, 12)
     else:
         table = np.stack([np.concatenate([t._abi().reshape(1, 12) for t in conf]) for conf in transforms])
     lib = ctx.library()
@@ -715,7 +727,11 @@ def _scene_run(kind, objects, pair_indices, request, transforms, broadphase=Fals
         ids = conf_begin = None
         if groups is not None:
             sc.set_groups(*groups)
-        if nearest_bound is not None and self_pairs:  # (summ: the clearances, hfcl_scene_clearance)
+        if env:
+            sc.set_environment(n_table, own(objects[n_table:]))
+            fn = sc.distance_env if kind == "distance" else sc.collide_env
+            rec, ids, conf_begin, summ, g = fn(table, request._abi(), float(inflate), records=True, want_guess=True)
+        elif nearest_bound is not None and self_pairs:  # (summ: the clearances, hfcl_scene_clearance)
             summ, rec, _ = sc.nearest_self(table, request._abi(), float(nearest_bound))
             g = None
         elif nearest_bound is not None:
@@ -739,7 +755,7 @@ def _scene_run(kind, objects, pair_indices, request, transforms, broadphase=Fals
     return geoms, pr, len(table), rec, summ, g, ids, conf_begin
 
 
-def collide_scene(objects, pair_indices, request, transforms=None, broadphase=False, inflate=0.0, groups=None):
+def collide_scene(objects, pair_indices, request, transforms=None, broadphase=False, inflate=0.0, groups=None, n_moving=None):
     """collide() on the listed pairs of `objects` (CollisionObjects) through a scene: each object's pose goes to the device
     once per configuration, not once per pair.  transforms: None -- one configuration, the objects' own transforms --, an
     array (n_conf, n_objects, 12) of Transform3f images, or n_conf lists of Transform3f.  Returns (results, summaries):
@@ -757,17 +773,21 @@ def collide_scene(objects, pair_indices, request, transforms=None, broadphase=Fa
     ((i, j), CollisionResult), i then j ascending; min_pair / first_contact of a summary are positions in that list.
     groups=(object_group, collides), with broadphase="self" only: a group per object and the symmetric group matrix ((G, G) bools or G
     uint64 words, G <= 64) -- only pairs whose groups may pair are found (engine.Scene.set_groups; engine.groups_between gives
-    collide(otherManager, callback), engine.groups_excluding an allowed-collision matrix)."""
+    collide(otherManager, callback), engine.groups_excluding an allowed-collision matrix).
+    broadphase="env", n_moving=K: a robot among a static environment.  objects[K:] keep their own transforms as the environment, which goes
+    to the device once with its boxes (engine.Scene.set_environment; put the robot first and the obstacles in engine.spatial_order);
+    `transforms` is (n_conf, K, 12) -- the moving objects' poses alone (None: their own).  The results are those of broadphase="self"
+    on the full transforms less every pair of two environment objects; `groups` works as with "self"."""
     if request.num_max_contacts == 0:
         raise ValueError("Invalid number of max contacts (current value is 0).")
     if request.num_max_contacts > 1 and any(isinstance(o.collisionGeometry(), BVHModelOBBRSS) for o in objects):
         raise ValueError("collide_scene: contact lists of mesh pairs (num_max_contacts > 1) go through collide_pairs")
     geoms, pr, n_conf, rec, summ, g, ids, conf_begin = _scene_run("collide", objects, pair_indices, request, transforms, broadphase, inflate,
-                                                                    groups=groups)
+                                                                    groups=groups, n_moving=n_moving)
     out = []
     for c in range(n_conf):
         row = []
-        if broadphase == "self":  # ((i, j), result) of configuration c's touching pairs
+        if broadphase in ("self", "env"):  # ((i, j), result) of configuration c's touching pairs
             for k in range(int(conf_begin[c]), int(conf_begin[c + 1])):
                 i, j = int(ids[k][0]), int(ids[k][1])
                 r = CollisionResult()
@@ -790,7 +810,7 @@ def collide_scene(objects, pair_indices, request, transforms=None, broadphase=Fa
 
 
 def distance_scene(objects, pair_indices, request, transforms=None, broadphase=False, inflate=0.0, nearest=False, upper_bound=float("inf"),
-                   groups=None):
+                   groups=None, n_moving=None):
     """distance() on the listed pairs of `objects`: (min_distance array (n_conf, n_pairs), records, summaries); the
     summaries' min_distance is DistanceCallBackDefault's answer per configuration.
     broadphase=True: only the pairs whose world AABBs, each grown by `inflate`, overlap are evaluated (inflate = D / 2 keeps every pair
@@ -804,7 +824,11 @@ def distance_scene(objects, pair_indices, request, transforms=None, broadphase=F
     are pruned on the device by a bound from their world boxes (engine.Scene.nearest); a configuration whose closest pair is farther than
     `upper_bound` keeps a default DistanceResult.  With broadphase="self" there is no list and no inflate: the clearance over every
     pair (i < j) the `groups` allow, the pairs made and pruned on the device (engine.Scene.nearest_self) --
-    DynamicAABBTreeCollisionManager::distance(otherManager, DistanceCallBackDefault) with two groups."""
+    DynamicAABBTreeCollisionManager::distance(otherManager, DistanceCallBackDefault) with two groups.
+    broadphase="env", n_moving=K: as in collide_scene -- objects[K:] are the environment, `transforms` is (n_conf, K, 12); the items are
+    those of "self"."""
+    if nearest and broadphase == "env":
+        raise ValueError('the pruned minimum (nearest=True) takes full tables: broadphase="self"')
     self_pairs = isinstance(broadphase, str) and broadphase == "self"
     if nearest and groups is not None and not self_pairs:
         raise ValueError('groups need broadphase="self": the pruned minimum (nearest=True) runs on the pair list')
@@ -828,8 +852,8 @@ def distance_scene(objects, pair_indices, request, transforms=None, broadphase=F
             out.append(res)
         return out
     geoms, pr, n_conf, rec, summ, g, ids, conf_begin = _scene_run("distance", objects, pair_indices, request, transforms, broadphase, inflate,
-                                                                    groups=groups)
-    if broadphase == "self":  # (distances, (i, j) arrays, summaries): no list; the device finds the pairs whose grown boxes overlap
+                                                                    groups=groups, n_moving=n_moving)
+    if broadphase in ("self", "env"):  # (distances, (i, j) arrays, summaries): no list; the device finds the pairs whose grown boxes overlap
         cb = conf_begin.astype(np.int64)
         return [rec["distance"][cb[c]:cb[c + 1]] for c in range(n_conf)], [ids[cb[c]:cb[c + 1]] for c in range(n_conf)], summ
     if broadphase:

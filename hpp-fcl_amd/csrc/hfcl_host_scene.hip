@@ -4,10 +4,12 @@
 #include "hfcl_plan.hpp"
 #include "hfcl_nearest.hpp"
 #include "hfcl_nearest_self.hpp"
+#include "hfcl_env.hpp"
 #include "../../include/hppfcl_amd_nearest.h"
 #include "../../include/hppfcl_amd_groups.h"
 #include "../../include/hppfcl_amd_nearest_self.h"
 #include "../../include/hppfcl_amd_pairs.h"
+#include "../../include/hppfcl_amd_env.h"
 
 // =======================================================================================
 // Scene queries (include/hppfcl_amd.h: hfcl_scene_*): an object -> shape table and a pair list resident on the library's device; a call
@@ -24,6 +26,16 @@ struct hfcl_scene {
   size_t n_groups = 0;
   DevBuf<uint8_t> d_group;
   DevBuf<uint64_t> d_collides, d_tile_groups;
+  std::vector<uint8_t> h_group;  // (the groups again, for the tiling of a scene with an environment)
+  // a static environment (hfcl_scene_set_environment*; has_env false: none): objects [n_moving, n_objects) with their poses in the
+  // precision of the setter, their world boxes, a box per tile of PAIRS_TILE of them, and -- with groups -- the groups present per column
+  // tile of hfcl_env.hpp's tiling (moving tiles, then environment tiles)
+  bool has_env = false, env_f32 = false;
+  size_t n_moving = 0;
+  DevBuf<void> d_env_table;
+  DevBuf<double> d_env_boxes, d_env_tile_boxes;
+  DevBuf<uint64_t> d_env_tile_groups;
+  size_t n_env() const { return n_objects - n_moving; }
 };
 
 static int scene_check_pairs(const char* who, const uint32_t* pairs, size_t n_pairs, size_t n_objects) {
@@ -173,6 +185,11 @@ struct SceneList {
   const uint32_t* d_pairs = nullptr;
   uint32_t shares = 0;
   bool ranked() const { return d_pairs != nullptr; }
+  // ... of a scene with an environment (hfcl_scene_env_pairs_device leaves it): the call's table holds n_moving rows a configuration,
+  // the rows of j >= n_moving come from d_env_table
+  bool env = false;
+  const void* d_env_table = nullptr;
+  size_t n_moving = 0;
 };
 // fold pieces of a configuration of a call
 static uint32_t scene_list_shares(const hfcl_scene* s, const SceneList* list) {
@@ -208,7 +225,10 @@ static int scene_chunk_run(hfcl_scene* s, const void* d_table, const SceneList* 
   ea.s2 = w.d_s2;
   ea.tf1 = w.d_tf1;
   ea.tf2 = w.d_tf2;
-  if (list && list->ranked())
+  if (list && list->ranked() && list->env) {
+    ea.n_objects = list->n_moving;
+    launch_scene_expand_env(st, ea, list->d_pairs, list->d_conf_begin, list->n_conf, k0, list->d_env_table, f32, max_blocks);
+  } else if (list && list->ranked())
     launch_scene_expand_pairs(st, ea, list->d_pairs, list->d_conf_begin, list->n_conf, k0, f32, max_blocks);
   else if (list)
     launch_scene_expand_listed(st, ea, list->d_ids + k0, f32, max_blocks);
@@ -881,6 +901,289 @@ static int scene_pairs_device(const char* who, hfcl_scene* s, const void* d_tabl
   return scene_chunks_device<T>(s, d_table, &list, n_listed, creq, dreq, d_out, d_summary, d_gin, d_gout, st, counts);
 }
 
+// ---------------------------------------------------------------------------------------
+// A static environment kept on the device (include/hppfcl_amd_env.h): the pairs of the moving objects among themselves and against the
+// environment per configuration (hfcl_scene_env_pairs*), and the scene calls on such a list (hfcl_scene_*_env_pairs_device*,
+// hfcl_scene_*_env).  hfcl_k_env.hip has the kernels, hfcl_env.hpp the arithmetic.
+// ---------------------------------------------------------------------------------------
+// What every _env call refuses before any work, in this order: a null scene, a stale one, no environment, one of the other precision, a
+// null table (with something to do), an overflow.  nothing: n_conf == 0 or no moving object -- HFCL_OK before the table is looked at.
+template <typename T>
+static int env_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, bool& nothing) {
+  nothing = true;
+  if (const int rc = groups_scene(who, s)) return rc;
+  if (!s->has_env) {
+    set_error(std::string(who) + ": the scene has no environment (hfcl_scene_set_environment)");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (s->env_f32 != std::is_same<T, float>::value) {
+    set_error(std::string(who) + ": the environment was set in " + (s->env_f32 ? "fp32 (hfcl_scene_set_environment_f32)" : "fp64 (hfcl_scene_set_environment)") +
+              ", this call is of the other precision; the two pose formats are not converted into each other");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (n_conf == 0 || s->n_moving == 0) return HFCL_OK;
+  if (!table) {
+    set_error(std::string(who) + ": null pose table");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (n_conf > ~size_t(0) / (s->n_moving * SceneTypes<T>::WIDTH * sizeof(T))) {
+    set_error(std::string(who) + ": the pose table's size overflows");
+    return HFCL_ERR_LIMIT;
+  }
+  nothing = false;
+  return HFCL_OK;
+}
+// ... of a narrow-phase call: of a scene that is there, the request and the outputs first (scene_validate)
+template <typename T>
+static int env_scene_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, const hfcl_collision_request* creq,
+                              const hfcl_distance_request* dreq, const void* out, const void* summary, bool& nothing) {
+  nothing = true;
+  if (s) {
+    QParams<T> q;
+    bool skip;
+    const int rc = creq ? setup_collide<T>(creq, q, skip) : setup_distance<T>(dreq, q);
+    if (rc) return rc;
+    if (!out && !summary) {
+      set_error(std::string(who) + ": records and summaries both NULL");
+      return HFCL_ERR_INVALID_ARGUMENT;
+    }
+  }
+  return env_validate<T>(who, s, table, n_conf, nothing);
+}
+static int env_limits(const char* who, const hfcl_scene* s) {
+  if (s->n_moving > ENV_MAX_OBJECTS || s->n_env() > ENV_MAX_OBJECTS) {
+    set_error(std::string(who) + ": at most " + std::to_string(ENV_MAX_OBJECTS) + " moving objects and as many in the environment");
+    return HFCL_ERR_LIMIT;
+  }
+  return HFCL_OK;
+}
+static int env_rank_limit(const char* who, uint64_t n_listed, const hfcl_scene* s) {
+  if (env_shares(n_listed, s->n_moving, s->n_env()) > 0xFFFFFFFFull / SCENE_FOLD_SHARE) {
+    set_error(std::string(who) + ": a configuration could hold 2^32 entries or more; summaries rank an entry in 32 bits");
+    return HFCL_ERR_LIMIT;
+  }
+  return HFCL_OK;
+}
+// the groups present per column tile of a scene that has both groups and an environment (either may have been set last)
+static int env_tile_groups(hfcl_scene* s) {
+  s->d_env_tile_groups.reset();
+  if (!s->has_env || !s->n_groups || s->n_moving > ENV_MAX_OBJECTS || s->n_env() > ENV_MAX_OBJECTS) return HFCL_OK;
+  const EnvGeometry geo = env_geometry(uint32_t(s->n_moving), uint32_t(s->n_env()), 0u);
+  std::vector<uint64_t> words(std::max<uint32_t>(geo.tiles, 1u), 0u);
+  for (uint32_t u = 0; u < geo.tiles; ++u) words[u] = env_tile_word(geo, s->h_group.data(), u);
+  return groups_upload(s->d_env_tile_groups, words.data(), words.size());
+}
+
+template <typename T>
+static int env_set(const char* who, hfcl_scene* s, size_t n_moving, const T* env_rows) {
+  int rc = groups_scene(who, s);
+  if (rc) return rc;
+  if (n_moving > s->n_objects) {
+    set_error(std::string(who) + ": " + std::to_string(n_moving) + " moving objects in a scene of " + std::to_string(s->n_objects));
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  const size_t n_env = s->n_objects - n_moving;
+  if (n_env && !env_rows) {
+    set_error(std::string(who) + ": null environment poses");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (n_env > 0xFFFFFFFFull - PAIRS_TILE) {
+    set_error(std::string(who) + ": too many environment objects");
+    return HFCL_ERR_LIMIT;
+  }
+  hfcl_lib* lib = s->lib;
+  HIP_TRY(hipSetDevice(lib->device));
+  rc = ensure_local_boxes(lib);
+  if (rc) return rc;
+  DevBuf<void> d_table;
+  DevBuf<double> d_boxes, d_tile_boxes;
+  if (n_env) {
+    const size_t bytes = n_env * SceneTypes<T>::WIDTH * sizeof(T);
+    HIP_TRY(d_table.grow(bytes));
+    HIP_TRY(d_boxes.grow(n_env * 6));
+    HIP_TRY(d_tile_boxes.grow(size_t(env_tiles(uint32_t(n_env))) * 6));
+    HIP_TRY(hipMemcpy(d_table, env_rows, bytes, hipMemcpyHostToDevice));
+    // the boxes with the kernel of hfcl_scene_world_aabbs*: row r of this table is object n_moving + r
+    launch_cull_aabbs(nullptr, d_table, std::is_same<T, float>::value, s->d_object_shape.get() + n_moving, lib->d_local_boxes, n_env, n_env, d_boxes);
+    launch_env_tile_boxes(nullptr, d_boxes, uint32_t(n_env), d_tile_boxes);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(nullptr));
+  }
+  // (freeing the old tables waits for the device: a query in flight on some stream may still be reading them)
+  s->d_env_table = std::move(d_table);
+  s->d_env_boxes = std::move(d_boxes);
+  s->d_env_tile_boxes = std::move(d_tile_boxes);
+  s->has_env = true;
+  s->env_f32 = std::is_same<T, float>::value;
+  s->n_moving = n_moving;
+  return env_tile_groups(s);
+}
+
+// The env list of the whole moving table on st: the pairs (below `capacity`), conf_begin, the count.  Nothing is read back.
+template <typename T>
+static int env_pairs_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, double inflate, uint32_t* d_pairs, size_t capacity,
+                            uint64_t* d_conf_begin, uint64_t* d_n_listed, hipStream_t st) {
+  bool nothing;
+  int rc = env_validate<T>(who, s, d_table, n_conf, nothing);
+  if (rc) return rc;
+  rc = cull_check_inflate(who, inflate);
+  if (rc) return rc;
+  if (!d_n_listed) {
+    set_error(std::string(who) + ": null count");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  rc = env_limits(who, s);
+  if (rc) return rc;
+  hfcl_lib* lib = s->lib;
+  HIP_TRY(hipSetDevice(lib->device));
+  if (nothing) {  // no pair: an empty list
+    HIP_TRY(hipMemsetAsync(d_n_listed, 0, sizeof(uint64_t), st));
+    if (d_conf_begin) HIP_TRY(hipMemsetAsync(d_conf_begin, 0, (n_conf + 1) * sizeof(uint64_t), st));
+    return HFCL_OK;
+  }
+  rc = ensure_local_boxes(lib);
+  if (rc) return rc;
+  hfcl_lib::SceneWs& w = lib->scene;
+  const uint32_t nm = uint32_t(s->n_moving), ne = uint32_t(s->n_env());
+  const PairsGeometry rows = pairs_geometry(nm, false);
+  const uint64_t n_blocks = uint64_t(n_conf) * rows.blocks_per_conf;
+  const uint32_t tiles = env_geometry(nm, ne, 0u).tiles;
+  const uint32_t span = lib->opt.scene_env_span ? lib->opt.scene_env_span : env_auto_span(tiles, n_blocks, uint32_t(std::max(lib->n_cus, 1)), ENV_AUTO_PER_CU);
+  const EnvGeometry geo = env_geometry(nm, ne, span);
+  const uint64_t per = env_chunk_blocks(geo, n_blocks, lib->opt.scene_cull_chunk);
+  const size_t conf_per_chunk = std::min<size_t>(n_conf, size_t(per / rows.blocks_per_conf) + 2);
+  HIP_TRY(w.d_boxes.grow(conf_per_chunk * nm * 6));
+  const uint64_t chunk_rows = std::min<uint64_t>(per * rows.rows_per_block, uint64_t(n_conf) * nm);
+  rc = pairs_chunk_buffers(lib, size_t(chunk_rows * geo.n_spans));
+  if (rc) return rc;
+  EnvArgs a;
+  pairs_args(a.p, s, rows, false, n_conf);
+  a.p.tile_groups = nullptr;
+  a.p.n_objects = nm * geo.n_spans;  // (the scan's rows: (row, span) counts, row-major)
+  a.p.total_rows = uint64_t(n_conf) * nm * geo.n_spans;
+  a.p.inflate = inflate;
+  a.p.pairs = d_pairs;
+  a.p.capacity = d_pairs ? capacity : 0;
+  a.p.conf_begin = d_conf_begin;
+  a.p.n_listed = d_n_listed;
+  a.n_moving = nm;
+  a.n_env = ne;
+  a.tiles_moving = geo.tiles_moving;
+  a.tiles = geo.tiles;
+  a.span_len = geo.span_len;
+  a.n_spans = geo.n_spans;
+  a.blocks_per_conf = rows.blocks_per_conf;
+  a.env_boxes = s->d_env_boxes;
+  a.env_tile_boxes = s->d_env_tile_boxes;
+  a.col_tile_groups = s->n_groups ? s->d_env_tile_groups.get() : nullptr;
+  // the chunks in turn: the boxes of the moving rows of the configurations a chunk touches (the first n_moving objects' shapes), then the chunk
+  pairs_chunks<T>(a.p, s, d_table, rows, n_blocks, per, st, [&]() {
+    a.row0 = a.p.row0;
+    a.p.row0 = a.row0 * geo.n_spans;
+    a.p.n_rows = uint32_t(uint64_t(a.p.n_rows) * geo.n_spans);
+    launch_env_chunk(st, a);
+  });
+  HIP_TRY(hipGetLastError());
+  return HFCL_OK;
+}
+
+// The env list of a moving table that is on the device into the library's own (w.d_pair_list, w.d_conf_begin), and the one read-back: the count.
+template <typename T>
+static int env_pairs_into_workspace(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, double inflate, bool want_pairs,
+                                    uint64_t& n_listed) {
+  hfcl_lib* lib = s->lib;
+  hfcl_lib::SceneWs& w = lib->scene;
+  HIP_TRY(w.d_conf_begin.grow(n_conf + 1));
+  HIP_TRY(w.d_running.grow(2));
+  if (want_pairs) HIP_TRY(w.d_pair_list.grow(2 * pairs_capacity_guess(n_conf * s->n_moving)));
+  return list_and_count(w.d_pair_list, want_pairs, w.d_running + 1, w.s_cmp, n_listed, [&]() {
+    return env_pairs_device<T>(who, s, d_table, n_conf, inflate, want_pairs ? w.d_pair_list.get() : nullptr, w.d_pair_list.capacity() / 2,
+                               w.d_conf_begin, w.d_running + 1, w.s_cmp);
+  }, 2);
+}
+
+template <typename T>
+static int env_pairs_host(const char* who, hfcl_scene* s, const void* table, size_t n_conf, double inflate, uint32_t* pairs, size_t capacity,
+                          uint64_t* conf_begin, size_t* n_listed) {
+  bool nothing;
+  int rc = env_validate<T>(who, s, table, n_conf, nothing);
+  if (!rc) rc = cull_check_inflate(who, inflate);
+  if (!rc && !n_listed) {
+    set_error(std::string(who) + ": null count");
+    rc = HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (!rc) rc = env_limits(who, s);
+  if (rc) return rc;
+  *n_listed = 0;
+  if (nothing) {
+    if (conf_begin) memset(conf_begin, 0, (n_conf + 1) * sizeof(uint64_t));
+    return HFCL_OK;
+  }
+  hfcl_lib* lib = s->lib;
+  hfcl_lib::SceneWs& w = lib->scene;
+  HIP_TRY(hipSetDevice(lib->device));
+  rc = scene_host_stream(w);
+  if (!rc) rc = scene_table_in(w, table, n_conf * s->n_moving * SceneTypes<T>::WIDTH * sizeof(T));
+  uint64_t n = 0;
+  if (!rc) rc = env_pairs_into_workspace<T>(who, s, w.d_table, n_conf, inflate, pairs != nullptr, n);
+  if (rc) {
+    hipStreamSynchronize(w.s_cmp);
+    return rc;
+  }
+  *n_listed = size_t(n);
+  if (pairs && capacity < n) {
+    set_error(std::string(who) + ": " + std::to_string(n) + " pairs are listed, the list holds " + std::to_string(capacity));
+    return HFCL_ERR_LIMIT;
+  }
+  if (pairs && n) HIP_TRY(hipMemcpyAsync(pairs, w.d_pair_list, n * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, w.s_cmp));
+  if (conf_begin) HIP_TRY(hipMemcpyAsync(conf_begin, w.d_conf_begin, (n_conf + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
+  HIP_TRY(hipStreamSynchronize(w.s_cmp));
+  return HFCL_OK;
+}
+
+// the list flavour of a scene with an environment
+static SceneList env_list(const hfcl_scene* s, const uint32_t* d_pairs, const uint64_t* d_conf_begin, size_t n_conf, size_t n_listed) {
+  SceneList list{nullptr, d_conf_begin, n_conf};
+  list.d_pairs = d_pairs;
+  list.shares = uint32_t(env_shares(n_listed, s->n_moving, s->n_env()));
+  list.env = true;
+  list.d_env_table = s->d_env_table;
+  list.n_moving = s->n_moving;
+  return list;
+}
+// The device form on an env list.  The list is not checked: i < n_moving, i < j < n_objects, conf_begin its spans -- as
+// hfcl_scene_env_pairs_device leaves them.
+template <typename T>
+static int scene_env_pairs_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const uint32_t* d_pairs, size_t n_listed,
+                                  const uint64_t* d_conf_begin, const hfcl_collision_request* creq, const hfcl_distance_request* dreq,
+                                  typename SceneTypes<T>::R* d_out, hfcl_scene_summary* d_summary, const hfcl_guess* d_gin, hfcl_guess* d_gout,
+                                  hipStream_t st) {
+  bool nothing;
+  int rc = env_scene_validate<T>(who, s, d_table, n_conf, creq, dreq, d_out, d_summary, nothing);
+  if (rc) return rc;
+  if (n_conf == 0 || s->n_moving == 0) {
+    if (n_listed) {
+      set_error(std::string(who) + ": list entries without a configuration or a moving object");
+      return HFCL_ERR_INVALID_ARGUMENT;
+    }
+    if (n_conf == 0) return HFCL_OK;
+  }
+  if (n_listed && (!d_pairs || !d_conf_begin)) {
+    set_error(std::string(who) + ": null list / conf_begin");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (d_summary && (rc = env_rank_limit(who, n_listed, s))) return rc;
+  hfcl_lib* lib = s->lib;
+  HIP_TRY(hipSetDevice(lib->device));
+  if (d_summary) launch_scene_summary_init(st, d_summary, n_conf, lib->n_cus * 16);
+  if (!n_listed) {
+    HIP_TRY(hipGetLastError());
+    return HFCL_OK;
+  }
+  const SceneList list = env_list(s, d_pairs, d_conf_begin, n_conf, n_listed);
+  return scene_chunks_device<T>(s, d_table, &list, n_listed, creq, dreq, d_out, d_summary, d_gin, d_gout, st);
+}
+
 // what the culled host forms (hfcl_scene_*_culled) add to scene_host
 struct SceneCull {
   double inflate;
@@ -891,6 +1194,8 @@ struct SceneCull {
   // the self forms (hfcl_scene_*_self): the list is made by hfcl_scene_self_pairs_device, not culled from the scene's own; query_ids_out unused
   bool self = false;
   uint32_t* pairs_out = nullptr;  // nullptr or 2 x out_capacity
+  // the env forms (hfcl_scene_*_env): self, with the list made by hfcl_scene_env_pairs_device from a table of the moving objects alone
+  bool env = false;
 };
 
 // Host form.  The object table goes in once; chunk k computes on one stream while chunk k - 1's records leave on another from the other of
@@ -902,10 +1207,14 @@ static int scene_host(const char* who, hfcl_scene* s, const void* table, size_t 
                       hfcl_guess* gout, const SceneCull* cull = nullptr) {
   using R = typename SceneTypes<T>::R;
   size_t total;
-  const bool self = cull && cull->self;
-  int rc = scene_validate<T>(who, s, table, n_conf, creq, dreq, out, summary, total, self ? &hfcl_scene::n_objects : &hfcl_scene::n_pairs);
-  if (!rc && self) rc = self_pairs_limits(who, s);
-  if (!rc && self) total = n_conf && s->n_objects >= 2 ? n_conf * s->n_objects : 0;  // (rows: what the list is made from)
+  const bool self = cull && cull->self, env = cull && cull->env;
+  bool env_nothing = true;
+  int rc = env ? env_scene_validate<T>(who, s, table, n_conf, creq, dreq, out, summary, env_nothing)
+               : scene_validate<T>(who, s, table, n_conf, creq, dreq, out, summary, total, self ? &hfcl_scene::n_objects : &hfcl_scene::n_pairs);
+  if (!rc && self && !env) rc = self_pairs_limits(who, s);
+  if (!rc && self && !env) total = n_conf && s->n_objects >= 2 ? n_conf * s->n_objects : 0;  // (rows: what the list is made from)
+  if (!rc && env) rc = env_limits(who, s);
+  if (!rc && env) total = env_nothing ? 0 : n_conf * s->n_moving;
   if (!rc && cull) {
     rc = cull_check_inflate(who, cull->inflate);
     if (!rc && !cull->n_listed) {
@@ -930,14 +1239,15 @@ static int scene_host(const char* who, hfcl_scene* s, const void* table, size_t 
     if (!w.ev_done[k]) HIP_TRY(w.ev_done[k].create());
     if (!w.ev_copied[k]) HIP_TRY(w.ev_copied[k].create());
   }
-  const size_t table_bytes = n_conf * s->n_objects * SceneTypes<T>::WIDTH * sizeof(T);
+  const size_t table_bytes = n_conf * (env ? s->n_moving : s->n_objects) * SceneTypes<T>::WIDTH * sizeof(T);
   size_t work = total;  // records of the call: every query, or (culled form) the surviving ones
   if (cull) {  // the table goes in, the cull runs, the count comes back: 8 bytes, the one read-back before the narrow phase
     rc = scene_table_in(w, table, table_bytes);
     uint64_t n = 0;
     if (!rc)
-      rc = self ? self_pairs_into_workspace<T>(who, s, w.d_table, n_conf, cull->inflate, true, n)
-                : cull_into_workspace<T>(who, s, w.d_table, n_conf, total, cull->inflate, true, n);
+      rc = env    ? env_pairs_into_workspace<T>(who, s, w.d_table, n_conf, cull->inflate, true, n)
+           : self ? self_pairs_into_workspace<T>(who, s, w.d_table, n_conf, cull->inflate, true, n)
+                  : cull_into_workspace<T>(who, s, w.d_table, n_conf, total, cull->inflate, true, n);
     if (rc) {
       hipStreamSynchronize(w.s_cmp);
       return rc;
@@ -948,7 +1258,7 @@ static int scene_host(const char* who, hfcl_scene* s, const void* table, size_t 
       return HFCL_ERR_LIMIT;
     }
     if (!n) return nothing_listed();
-    if (self && summary && (rc = pairs_rank_limit(who, n, s->n_objects))) return rc;
+    if (self && summary && (rc = env ? env_rank_limit(who, n, s) : pairs_rank_limit(who, n, s->n_objects))) return rc;
     if (cull->query_ids_out) HIP_TRY(hipMemcpyAsync(cull->query_ids_out, w.d_ids, n * sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
     if (cull->pairs_out) HIP_TRY(hipMemcpyAsync(cull->pairs_out, w.d_pair_list, n * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, w.s_cmp));
     if (cull->conf_begin_out)
@@ -961,6 +1271,7 @@ static int scene_host(const char* who, hfcl_scene* s, const void* table, size_t 
     listed.d_pairs = w.d_pair_list;
     listed.shares = uint32_t(pairs_shares(work, s->n_objects));
   }
+  if (env) listed = env_list(s, w.d_pair_list, w.d_conf_begin, n_conf, work);
   const SceneList* list = cull ? &listed : nullptr;
   const size_t chunk = scene_chunk_size(work, lib->opt.scene_chunk);
   const size_t n_chunks = (work + chunk - 1) / chunk;
@@ -1700,13 +2011,14 @@ int hfcl_scene_set_groups(hfcl_scene* s, const uint8_t* object_group, size_t n_g
   s->d_collides = std::move(d_collides);
   s->d_tile_groups = std::move(d_tile_groups);
   s->n_groups = n_groups;
-  return HFCL_OK;
+  s->h_group.assign(object_group, object_group + s->n_objects);
+  return env_tile_groups(s);  // (a scene with an environment: the groups per tile of its tiling)
 }
 int hfcl_scene_clear_groups(hfcl_scene* s) {
   PAIRS_ENTRY;
   if (const int rc = groups_scene("hfcl_scene_clear_groups", s)) return rc;
   HIP_TRY(hipSetDevice(s->lib->device));
-  reset_all(s->d_group, s->d_collides, s->d_tile_groups);  // (waits for the device, as above)
+  reset_all(s->d_group, s->d_collides, s->d_tile_groups, s->d_env_tile_groups);  // (waits for the device, as above)
   s->n_groups = 0;
   return HFCL_OK;
 }
@@ -1735,6 +2047,127 @@ int hfcl_scene_nearest_self_device_f32(hfcl_scene* s, const float* d_object_pose
   PAIRS_ENTRY;
   return nearest_self_device<float>("hfcl_scene_nearest_self_device_f32", s, d_object_pose, n_conf, req, upper_bound, d_out, d_min_records,
                                     n_evaluated, (hipStream_t)stream);
+}
+
+// ---- a static environment kept on the device (include/hppfcl_amd_env.h) ----------------------------------------------------------------
+int hfcl_scene_set_environment(hfcl_scene* s, size_t n_moving, const double* env_tf) {
+  PAIRS_ENTRY;
+  return env_set<double>("hfcl_scene_set_environment", s, n_moving, env_tf);
+}
+int hfcl_scene_set_environment_f32(hfcl_scene* s, size_t n_moving, const float* env_pose) {
+  PAIRS_ENTRY;
+  return env_set<float>("hfcl_scene_set_environment_f32", s, n_moving, env_pose);
+}
+int hfcl_scene_clear_environment(hfcl_scene* s) {
+  PAIRS_ENTRY;
+  if (const int rc = groups_scene("hfcl_scene_clear_environment", s)) return rc;
+  HIP_TRY(hipSetDevice(s->lib->device));
+  s->d_env_table.reset();  // (waits for the device: a query in flight on some stream may still be reading the tables)
+  reset_all(s->d_env_boxes, s->d_env_tile_boxes);
+  s->d_env_tile_groups.reset();
+  s->has_env = false;
+  s->n_moving = 0;
+  return HFCL_OK;
+}
+size_t hfcl_scene_n_moving(const hfcl_scene* s) { return s ? (s->has_env ? s->n_moving : s->n_objects) : 0; }
+int hfcl_scene_environment_aabbs(hfcl_scene* s, double* aabbs_out, double* tile_aabbs_out) {
+  PAIRS_ENTRY;
+  const char* who = "hfcl_scene_environment_aabbs";
+  if (const int rc = groups_scene(who, s)) return rc;
+  if (!s->has_env) {
+    set_error(std::string(who) + ": the scene has no environment (hfcl_scene_set_environment)");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  const size_t n_env = s->n_env();
+  if (!n_env) return HFCL_OK;
+  HIP_TRY(hipSetDevice(s->lib->device));
+  if (aabbs_out) HIP_TRY(hipMemcpy(aabbs_out, s->d_env_boxes, n_env * 6 * sizeof(double), hipMemcpyDeviceToHost));
+  if (tile_aabbs_out)
+    HIP_TRY(hipMemcpy(tile_aabbs_out, s->d_env_tile_boxes, size_t(env_tiles(uint32_t(n_env))) * 6 * sizeof(double), hipMemcpyDeviceToHost));
+  return HFCL_OK;
+}
+int hfcl_scene_env_pairs(hfcl_scene* s, const double* moving_tf, size_t n_conf, double inflate, uint32_t* pairs, size_t capacity,
+                         uint64_t* conf_begin, size_t* n_listed) {
+  PAIRS_ENTRY;
+  return env_pairs_host<double>("hfcl_scene_env_pairs", s, moving_tf, n_conf, inflate, pairs, capacity, conf_begin, n_listed);
+}
+int hfcl_scene_env_pairs_f32(hfcl_scene* s, const float* moving_pose, size_t n_conf, double inflate, uint32_t* pairs, size_t capacity,
+                             uint64_t* conf_begin, size_t* n_listed) {
+  PAIRS_ENTRY;
+  return env_pairs_host<float>("hfcl_scene_env_pairs_f32", s, moving_pose, n_conf, inflate, pairs, capacity, conf_begin, n_listed);
+}
+int hfcl_scene_env_pairs_device(hfcl_scene* s, const double* d_moving_tf, size_t n_conf, double inflate, uint32_t* d_pairs, size_t capacity,
+                                uint64_t* d_conf_begin, uint64_t* d_n_listed, void* stream) {
+  PAIRS_ENTRY;
+  return env_pairs_device<double>("hfcl_scene_env_pairs_device", s, d_moving_tf, n_conf, inflate, d_pairs, capacity, d_conf_begin, d_n_listed,
+                                  (hipStream_t)stream);
+}
+int hfcl_scene_env_pairs_device_f32(hfcl_scene* s, const float* d_moving_pose, size_t n_conf, double inflate, uint32_t* d_pairs,
+                                    size_t capacity, uint64_t* d_conf_begin, uint64_t* d_n_listed, void* stream) {
+  PAIRS_ENTRY;
+  return env_pairs_device<float>("hfcl_scene_env_pairs_device_f32", s, d_moving_pose, n_conf, inflate, d_pairs, capacity, d_conf_begin,
+                                 d_n_listed, (hipStream_t)stream);
+}
+int hfcl_scene_collide_env_pairs_device(hfcl_scene* s, const double* d_moving_tf, size_t n_conf, const uint32_t* d_pairs, size_t n_listed,
+                                        const uint64_t* d_conf_begin, const hfcl_collision_request* req, hfcl_result* d_out,
+                                        hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in, hfcl_guess* d_guess_out, void* stream) {
+  PAIRS_ENTRY;
+  return scene_env_pairs_device<double>("hfcl_scene_collide_env_pairs_device", s, d_moving_tf, n_conf, d_pairs, n_listed, d_conf_begin, req, nullptr,
+                                        d_out, d_summary, d_guess_in, d_guess_out, (hipStream_t)stream);
+}
+int hfcl_scene_distance_env_pairs_device(hfcl_scene* s, const double* d_moving_tf, size_t n_conf, const uint32_t* d_pairs, size_t n_listed,
+                                         const uint64_t* d_conf_begin, const hfcl_distance_request* req, hfcl_result* d_out,
+                                         hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in, hfcl_guess* d_guess_out, void* stream) {
+  PAIRS_ENTRY;
+  return scene_env_pairs_device<double>("hfcl_scene_distance_env_pairs_device", s, d_moving_tf, n_conf, d_pairs, n_listed, d_conf_begin, nullptr, req,
+                                        d_out, d_summary, d_guess_in, d_guess_out, (hipStream_t)stream);
+}
+int hfcl_scene_collide_env_pairs_device_f32(hfcl_scene* s, const float* d_moving_pose, size_t n_conf, const uint32_t* d_pairs,
+                                            size_t n_listed, const uint64_t* d_conf_begin, const hfcl_collision_request* req,
+                                            hfcl_result_f32* d_out, hfcl_scene_summary* d_summary, void* stream) {
+  PAIRS_ENTRY;
+  return scene_env_pairs_device<float>("hfcl_scene_collide_env_pairs_device_f32", s, d_moving_pose, n_conf, d_pairs, n_listed, d_conf_begin, req,
+                                       nullptr, d_out, d_summary, nullptr, nullptr, (hipStream_t)stream);
+}
+int hfcl_scene_distance_env_pairs_device_f32(hfcl_scene* s, const float* d_moving_pose, size_t n_conf, const uint32_t* d_pairs,
+                                             size_t n_listed, const uint64_t* d_conf_begin, const hfcl_distance_request* req,
+                                             hfcl_result_f32* d_out, hfcl_scene_summary* d_summary, void* stream) {
+  PAIRS_ENTRY;
+  return scene_env_pairs_device<float>("hfcl_scene_distance_env_pairs_device_f32", s, d_moving_pose, n_conf, d_pairs, n_listed, d_conf_begin,
+                                       nullptr, req, d_out, d_summary, nullptr, nullptr, (hipStream_t)stream);
+}
+static SceneCull env_form(double inflate, size_t out_capacity, uint32_t* pairs_out, uint64_t* conf_begin_out, size_t* n_listed) {
+  SceneCull cull = self_form(inflate, out_capacity, pairs_out, conf_begin_out, n_listed);
+  cull.env = true;
+  return cull;
+}
+int hfcl_scene_collide_env(hfcl_scene* s, const double* moving_tf, size_t n_conf, double inflate, const hfcl_collision_request* req,
+                           hfcl_result* out, size_t out_capacity, uint32_t* pairs_out, uint64_t* conf_begin_out, hfcl_scene_summary* summary,
+                           const hfcl_guess* guess_in, hfcl_guess* guess_out, size_t* n_listed) {
+  PAIRS_ENTRY;
+  const SceneCull cull = env_form(inflate, out_capacity, pairs_out, conf_begin_out, n_listed);
+  return scene_host<double>("hfcl_scene_collide_env", s, moving_tf, n_conf, req, nullptr, out, summary, guess_in, guess_out, &cull);
+}
+int hfcl_scene_distance_env(hfcl_scene* s, const double* moving_tf, size_t n_conf, double inflate, const hfcl_distance_request* req,
+                            hfcl_result* out, size_t out_capacity, uint32_t* pairs_out, uint64_t* conf_begin_out, hfcl_scene_summary* summary,
+                            const hfcl_guess* guess_in, hfcl_guess* guess_out, size_t* n_listed) {
+  PAIRS_ENTRY;
+  const SceneCull cull = env_form(inflate, out_capacity, pairs_out, conf_begin_out, n_listed);
+  return scene_host<double>("hfcl_scene_distance_env", s, moving_tf, n_conf, nullptr, req, out, summary, guess_in, guess_out, &cull);
+}
+int hfcl_scene_collide_env_f32(hfcl_scene* s, const float* moving_pose, size_t n_conf, double inflate, const hfcl_collision_request* req,
+                               hfcl_result_f32* out, size_t out_capacity, uint32_t* pairs_out, uint64_t* conf_begin_out,
+                               hfcl_scene_summary* summary, size_t* n_listed) {
+  PAIRS_ENTRY;
+  const SceneCull cull = env_form(inflate, out_capacity, pairs_out, conf_begin_out, n_listed);
+  return scene_host<float>("hfcl_scene_collide_env_f32", s, moving_pose, n_conf, req, nullptr, out, summary, nullptr, nullptr, &cull);
+}
+int hfcl_scene_distance_env_f32(hfcl_scene* s, const float* moving_pose, size_t n_conf, double inflate, const hfcl_distance_request* req,
+                                hfcl_result_f32* out, size_t out_capacity, uint32_t* pairs_out, uint64_t* conf_begin_out,
+                                hfcl_scene_summary* summary, size_t* n_listed) {
+  PAIRS_ENTRY;
+  const SceneCull cull = env_form(inflate, out_capacity, pairs_out, conf_begin_out, n_listed);
+  return scene_host<float>("hfcl_scene_distance_env_f32", s, moving_pose, n_conf, nullptr, req, out, summary, nullptr, nullptr, &cull);
 }
 #undef PAIRS_ENTRY
 

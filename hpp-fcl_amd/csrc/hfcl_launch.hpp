@@ -269,6 +269,30 @@ void launch_pairs_chunk(hipStream_t st, const PairsArgs& a);
 // (hfcl_k_pairs.hip) the three scan launches of launch_pairs_chunk alone, behind a count kernel of another unit that left a.row_counts
 void launch_pairs_scan(hipStream_t st, const PairsArgs& a);
 
+// hfcl_k_env.hip: a static environment kept on the device (hfcl_scene_set_environment*, hfcl_scene_env_pairs*; hfcl_env.hpp has the
+// arithmetic).  The boxes of one tile of PAIRS_TILE environment boxes each (set time)
+void launch_env_tile_boxes(hipStream_t st, const double* env_boxes, uint32_t n_env, double* tile_boxes);
+// A chunk of consecutive row blocks of the moving rows, times the spans of column tiles: count (a uint32 per (row, span)), launch_pairs_scan
+// with rows x spans as its rows, emit.  p: the chunk's blocks (g0, n_blocks, c_box0, boxes: of the MOVING rows, n_moving a configuration),
+// inflate, the list, the groups (tile_groups unused), and -- for the scan -- n_objects = n_moving * n_spans, row0, n_rows, total_rows in
+// (row, span) counts.
+struct EnvArgs {
+  PairsArgs p;
+  uint32_t n_moving, n_env;
+  uint32_t tiles_moving, tiles;      // hfcl_env.hpp: EnvGeometry
+  uint32_t span_len, n_spans;
+  uint32_t blocks_per_conf;
+  uint64_t row0;                     // first moving row of the chunk, c * n_moving + i
+  const double* env_boxes;           // n_env world boxes
+  const double* env_tile_boxes;      // ceil(n_env / PAIRS_TILE)
+  const uint64_t* col_tile_groups;   // a word per column tile (moving tiles, then environment tiles): the groups present; nullptr without groups
+};
+void launch_env_chunk(hipStream_t st, const EnvArgs& a);
+// the expansion of a chunk of an env list: launch_scene_expand_pairs with two tables -- a.object_tf: n_conf x n_moving rows, a.n_objects =
+// n_moving; rows of j >= n_moving from env_tf[j - n_moving]
+void launch_scene_expand_env(hipStream_t st, const SceneExpandArgs& a, const uint32_t* pairs, const uint64_t* conf_begin, uint64_t n_conf,
+                             uint64_t k0, const void* env_tf, bool f32, int max_blocks);
+
 // hfcl_k_nearest_self.hip: the clearance per configuration on device-made pairs (hfcl_scene_nearest_self*; hfcl_nearest_self.hpp has the
 // arithmetic).  The row blocks, chunks and row arrays are those of PairsArgs (p.inflate unused: nothing is inflated).
 struct NselfArgs {

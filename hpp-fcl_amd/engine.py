@@ -61,6 +61,14 @@ GROUPS_SYMBOLS = [
 NEAREST_SELF_SYMBOLS = [
     "hfcl_scene_nearest_self", "hfcl_scene_nearest_self_f32", "hfcl_scene_nearest_self_device", "hfcl_scene_nearest_self_device_f32",
 ]
+# include/hppfcl_amd_env.h (included by hppfcl_amd.h): a static environment kept on the device, the calls on the moving objects' poses alone
+ENV_SYMBOLS = [
+    "hfcl_scene_set_environment", "hfcl_scene_set_environment_f32", "hfcl_scene_clear_environment", "hfcl_scene_n_moving",
+    "hfcl_scene_environment_aabbs", "hfcl_scene_env_pairs", "hfcl_scene_env_pairs_f32", "hfcl_scene_env_pairs_device",
+    "hfcl_scene_env_pairs_device_f32", "hfcl_scene_collide_env_pairs_device", "hfcl_scene_distance_env_pairs_device",
+    "hfcl_scene_collide_env_pairs_device_f32", "hfcl_scene_distance_env_pairs_device_f32", "hfcl_scene_collide_env",
+    "hfcl_scene_distance_env", "hfcl_scene_collide_env_f32", "hfcl_scene_distance_env_f32",
+]
 
 
 class EngineError(RuntimeError):
@@ -114,6 +122,8 @@ def dll():
             d.hfcl_scene_num_pairs.restype = C.c_size_t
         if hasattr(d, "hfcl_scene_num_groups"):
             d.hfcl_scene_num_groups.restype = C.c_size_t
+        if hasattr(d, "hfcl_scene_n_moving"):
+            d.hfcl_scene_n_moving.restype = C.c_size_t
         _DLL = d
     return _DLL
 
@@ -516,6 +526,27 @@ class Library:
         return dict(zip(["mesh_continued", "mesh_rerun", "solid_continued", "solid_rerun"], [int(v) for v in out]))
 
 
+def spatial_order(centres):
+    """A permutation of points (n, 3) by Morton code: 21 bits a coordinate over the points' bounding box, ties by index.  Consecutive
+    objects of centres[spatial_order(centres)] are neighbours in space, which is what the tile boxes of Scene.set_environment need."""
+    p = np.asarray(centres, dtype=np.float64).reshape(-1, 3)
+    if len(p) == 0:
+        return np.zeros(0, dtype=np.int64)
+    lo, hi = p.min(axis=0), p.max(axis=0)
+    scale = np.where(hi > lo, (2 ** 21 - 1) / np.where(hi > lo, hi - lo, 1.0), 0.0)
+    q = np.clip(np.nan_to_num((p - lo) * scale), 0, 2 ** 21 - 1).astype(np.uint64)
+
+    def spread(x):  # 21 bits -> every third bit of 63
+        x = (x | (x << np.uint64(32))) & np.uint64(0x1F00000000FFFF)
+        x = (x | (x << np.uint64(16))) & np.uint64(0x1F0000FF0000FF)
+        x = (x | (x << np.uint64(8))) & np.uint64(0x100F00F00F00F00F)
+        x = (x | (x << np.uint64(4))) & np.uint64(0x10C30C30C30C30C3)
+        x = (x | (x << np.uint64(2))) & np.uint64(0x1249249249249249)
+        return x
+    code = spread(q[:, 0]) | (spread(q[:, 1]) << np.uint64(1)) | (spread(q[:, 2]) << np.uint64(2))
+    return np.argsort(code, kind="stable")
+
+
 class Scene:
     """hfcl_scene: objects (a shape each), a list of object pairs, and queries that evaluate the list for n_conf pose
     tables.  Query c * n_pairs + p is pair p of configuration c; its record is the per-pair call's record."""
@@ -846,6 +877,133 @@ class Scene:
 
     def distance_pairs_device_f32(self, d_object_pose, n_conf, d_pairs, n_listed, d_conf_begin, req, d_out=None, d_summary=None, stream=0):
         self._pairs_device("distance", True, d_object_pose, n_conf, d_pairs, n_listed, d_conf_begin, req, d_out, d_summary, None, None, stream)
+
+    # ---- a static environment kept on the device (include/hppfcl_amd_env.h) ----
+    @property
+    def n_moving(self):
+        """hfcl_scene_n_moving: the objects in front of the environment; n_objects when none is set."""
+        return int(dll().hfcl_scene_n_moving(self._h))
+
+    def set_environment(self, n_moving, env_tf):
+        """hfcl_scene_set_environment{,_f32}: objects [n_moving, n_objects) stand still at the poses env_tf -- (n_env, 12) float64 or
+        (n_env, 7) float32, the dtype choosing the precision of the _env calls that may follow.  Copied to the device once, with the world
+        boxes and a box per tile of 256 consecutive environment objects: put the moving objects first and the environment in a spatial
+        order (spatial_order), or the tile boxes skip nothing."""
+        a = np.asarray(env_tf)
+        f32 = a.dtype == np.float32 or (a.ndim >= 2 and a.shape[-1] == 7)
+        width = 7 if f32 else 12
+        a = np.ascontiguousarray(a, dtype=np.float32 if f32 else np.float64).reshape(-1, width)
+        if len(a) != max(self.n_objects - int(n_moving), 0) and 0 <= int(n_moving) <= self.n_objects:
+            raise ValueError("env_tf: one pose row per environment object (n_objects - n_moving)")
+        fn = dll().hfcl_scene_set_environment_f32 if f32 else dll().hfcl_scene_set_environment
+        _check(fn(self._h, C.c_size_t(int(n_moving)), abi.ptr(a) if len(a) else None))
+
+    def clear_environment(self):
+        _check(dll().hfcl_scene_clear_environment(self._h))
+
+    def environment_aabbs(self):
+        """hfcl_scene_environment_aabbs: (boxes (n_env, 6), tile boxes (ceil(n_env / 256), 6))."""
+        n_env = self.n_objects - self.n_moving
+        boxes = np.zeros((n_env, 6), dtype=np.float64)
+        tiles = np.zeros(((n_env + 255) // 256, 6), dtype=np.float64)
+        _check(dll().hfcl_scene_environment_aabbs(self._h, abi.ptr(boxes), abi.ptr(tiles)))
+        return boxes, tiles
+
+    def _moving_table(self, moving_tf):
+        """The (n_conf, n_moving, W) table of an _env call and whether it is the fp32 form."""
+        a = np.asarray(moving_tf)
+        f32 = a.dtype == np.float32 or (a.ndim >= 2 and a.shape[-1] == 7)
+        width, k = (7 if f32 else 12), self.n_moving
+        a = np.ascontiguousarray(a, dtype=np.float32 if f32 else np.float64)
+        if a.ndim < 2 or a.shape[-1] != width:
+            raise ValueError("pose table must have shape (n_conf, n_moving, %d)" % width)
+        if k == 0:
+            return a.reshape(a.shape[0] if a.ndim == 3 else 0, 0, width), f32
+        return a.reshape(-1, k, width), f32
+
+    def _env_guess(self, n_conf):
+        k = self.n_moving
+        return min(n_conf * (k * (k - 1) // 2 + k * (self.n_objects - k)), max(16 * n_conf * k, 1024))
+
+    def env_pairs(self, moving_tf, inflate=0.0):
+        """hfcl_scene_env_pairs{,_f32}: (pairs, conf_begin) as self_pairs gives them for the full tables -- moving_tf[c] followed by the
+        environment's rows --, less every entry with i >= n_moving."""
+        tf, f32 = self._moving_table(moving_tf)
+        fn = dll().hfcl_scene_env_pairs_f32 if f32 else dll().hfcl_scene_env_pairs
+        n = C.c_size_t(0)
+        conf_begin = np.zeros(len(tf) + 1, dtype=np.uint64)
+        capacity = self._env_guess(len(tf))
+        while True:  # (at most twice, as self_pairs)
+            pairs = np.zeros((capacity, 2), dtype=np.uint32)
+            rc = fn(self._h, abi.ptr(tf), C.c_size_t(len(tf)), C.c_double(inflate), abi.ptr(pairs), C.c_size_t(capacity), abi.ptr(conf_begin),
+                    C.byref(n))
+            if rc != abi.ERR_LIMIT or n.value <= capacity:
+                break
+            capacity = n.value
+        _check(rc)
+        return pairs[:n.value], conf_begin
+
+    def env_pairs_device(self, d_moving_tf, n_conf, inflate, d_pairs, capacity, d_conf_begin, d_n_listed, f32=False, stream=0):
+        """hfcl_scene_env_pairs_device{,_f32}: *d_n_listed is the true count, entries past `capacity` are not written; nothing is read back."""
+        fn = dll().hfcl_scene_env_pairs_device_f32 if f32 else dll().hfcl_scene_env_pairs_device
+        _check(fn(self._h, _dptr(d_moving_tf), C.c_size_t(int(n_conf)), C.c_double(inflate), _dptr(d_pairs), C.c_size_t(int(capacity)),
+                  _dptr(d_conf_begin), _dptr(d_n_listed), C.c_void_p(stream)))
+
+    def _env(self, kind, moving_tf, inflate, req, records, capacity=None, want_guess=False):
+        tf, f32 = self._moving_table(moving_tf)
+        n_conf = len(tf)
+        fn = getattr(dll(), "hfcl_scene_%s_env%s" % (kind, "_f32" if f32 else ""))
+        retry = capacity is None
+        if retry:
+            capacity = self._env_guess(n_conf)
+        out = np.zeros(capacity, dtype=abi.RESULT_F32_DTYPE if f32 else abi.RESULT_DTYPE) if records else None
+        pairs = np.zeros((capacity, 2), dtype=np.uint32)
+        conf_begin = np.zeros(n_conf + 1, dtype=np.uint64)
+        summ = np.zeros(n_conf, dtype=abi.SCENE_SUMMARY_DTYPE)
+        n = C.c_size_t(0)
+        args = [self._h, abi.ptr(tf), C.c_size_t(n_conf), C.c_double(inflate), C.byref(req), abi.ptr(out), C.c_size_t(capacity), abi.ptr(pairs),
+                abi.ptr(conf_begin), abi.ptr(summ)]
+        gout = None
+        if not f32:
+            gout = np.zeros(capacity, dtype=abi.GUESS_DTYPE) if want_guess else None
+            args += [None, abi.ptr(gout)]  # (no guesses in)
+        rc = fn(*args, C.byref(n))
+        if rc == abi.ERR_LIMIT and retry and n.value > capacity:
+            return self._env(kind, tf, inflate, req, records, n.value, want_guess)
+        _check(rc)
+        k = n.value
+        res = (out[:k] if records else None), pairs[:k], conf_begin, summ
+        return res + (gout[:k],) if gout is not None else res
+
+    def collide_env(self, moving_tf, req=None, inflate=0.0, records=True, want_guess=False):
+        """hfcl_scene_collide_env{,_f32}: collide_self on the env list of a (n_conf, n_moving, W) table."""
+        return self._env("collide", moving_tf, inflate, req or abi.default_collision_request(), records, want_guess=want_guess)
+
+    def distance_env(self, moving_tf, req=None, inflate=0.0, records=True, want_guess=False):
+        return self._env("distance", moving_tf, inflate, req or abi.default_distance_request(), records, want_guess=want_guess)
+
+    def _env_pairs_device(self, kind, f32, d_moving_tf, n_conf, d_pairs, n_listed, d_conf_begin, req, d_out, d_summary, d_gin, d_gout, stream):
+        fn = getattr(dll(), "hfcl_scene_%s_env_pairs_device%s" % (kind, "_f32" if f32 else ""))
+        args = [self._h, _dptr(d_moving_tf), C.c_size_t(int(n_conf)), _dptr(d_pairs), C.c_size_t(int(n_listed)), _dptr(d_conf_begin),
+                C.byref(req), _dptr(d_out), _dptr(d_summary)]
+        if not f32:
+            args += [_dptr(d_gin), _dptr(d_gout)]
+        _check(fn(*args, C.c_void_p(stream)))
+
+    def collide_env_pairs_device(self, d_moving_tf, n_conf, d_pairs, n_listed, d_conf_begin, req, d_out=None, d_summary=None, d_gin=None,
+                                 d_gout=None, stream=0):
+        """hfcl_scene_collide_env_pairs_device: the list (i < n_moving, i < j < n_objects, conf_begin its spans) is not checked."""
+        self._env_pairs_device("collide", False, d_moving_tf, n_conf, d_pairs, n_listed, d_conf_begin, req, d_out, d_summary, d_gin, d_gout, stream)
+
+    def distance_env_pairs_device(self, d_moving_tf, n_conf, d_pairs, n_listed, d_conf_begin, req, d_out=None, d_summary=None, d_gin=None,
+                                  d_gout=None, stream=0):
+        self._env_pairs_device("distance", False, d_moving_tf, n_conf, d_pairs, n_listed, d_conf_begin, req, d_out, d_summary, d_gin, d_gout, stream)
+
+    def collide_env_pairs_device_f32(self, d_moving_pose, n_conf, d_pairs, n_listed, d_conf_begin, req, d_out=None, d_summary=None, stream=0):
+        self._env_pairs_device("collide", True, d_moving_pose, n_conf, d_pairs, n_listed, d_conf_begin, req, d_out, d_summary, None, None, stream)
+
+    def distance_env_pairs_device_f32(self, d_moving_pose, n_conf, d_pairs, n_listed, d_conf_begin, req, d_out=None, d_summary=None, stream=0):
+        self._env_pairs_device("distance", True, d_moving_pose, n_conf, d_pairs, n_listed, d_conf_begin, req, d_out, d_summary, None, None, stream)
 
     # ---- the per-configuration minimum distance with box-bound pruning (include/hppfcl_amd_nearest.h) ----
     def _nearest(self, object_tf, req, upper_bound, records, f32):

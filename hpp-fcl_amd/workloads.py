@@ -527,7 +527,7 @@ def scene_planner(n_conf=2048, n_objects=16, seed=1, nper=64, link=1.6, bend=0.8
     return PlannerScene(lib, obj_shape, pairs, quat, T)
 
 
-def scene_robot_env(n_conf, n_links, n_obstacles, seed=1, nper=64, link=1.6, bend=0.8, spread=1.0):
+def scene_robot_env(n_conf, n_links, n_obstacles, seed=1, nper=64, link=1.6, bend=0.8, spread=1.0, split=False, spatial=False, full=True):
     """A robot in a static environment, for the device-made pair lists with object groups (engine.Scene.set_groups): scene_planner's
     bent chain of n_links <= 63 bodies per configuration, then n_obstacles bodies of the same shape mix whose pose is the same in
     every configuration, scattered uniformly through the box the chains sweep over all configurations -- their centres' box grown by
@@ -535,7 +535,12 @@ def scene_robot_env(n_conf, n_links, n_obstacles, seed=1, nper=64, link=1.6, ben
       scene   a PlannerScene (lib, obj_shape, quat, T; obj_tf / obj_pose_f32 are the pose tables) whose pair list is `pairs`;
       groups  (object_group uint8, collides uint64[n_links + 1]): link k is group k, every obstacle group n_links; allowed are
               link-link but the chain's neighbours and link-obstacle, not obstacle-obstacle;
-      pairs   the equivalent explicit list: the allowed pairs (i < j) in lexicographic order, uint32 (P, 2)."""
+      pairs   the equivalent explicit list: the allowed pairs (i < j) in lexicographic order, uint32 (P, 2).
+    spatial: the obstacles in engine.spatial_order of their centres (the same obstacles, permuted), which is what the tile boxes of a
+    scene with an environment (engine.Scene.set_environment) need.  split: two more items, for the calls that take the moving objects'
+    poses alone -- (moving table (n_conf, n_links, 12), environment poses (n_obstacles, 12)) and the same as 7-float poses.
+    full=False (with split): the returned scene holds configuration 0 alone -- a table of n_conf x n_objects rows is what the split
+    forms exist to avoid (4 096 configurations of 65 536 obstacles: 25.8 GB)."""
     if not 1 <= n_links <= 63:
         raise ValueError("scene_robot_env: 1 to 63 links (a group each, one more for the obstacles)")
     chain = scene_planner(n_conf, n_links, seed, nper, link, bend)
@@ -546,8 +551,14 @@ def scene_robot_env(n_conf, n_links, n_obstacles, seed=1, nper=64, link=1.6, ben
     mid, half = (lo + hi) / 2, ((hi - lo) / 2 + 1.8) * spread
     T_obs = rng.uniform(mid - half, mid + half, (n_obstacles, 3))
     q_obs = uniform_quaternions(rng, n_obstacles)
-    quat = np.concatenate([chain.quat, np.broadcast_to(q_obs, (n_conf, n_obstacles, 4))], axis=1)
-    T = np.concatenate([chain.T, np.broadcast_to(T_obs, (n_conf, n_obstacles, 3))], axis=1)
+    if spatial:
+        from . import engine
+        order = engine.spatial_order(T_obs)
+        T_obs, q_obs = T_obs[order], q_obs[order]
+        obj_shape[n_links:] = obj_shape[n_links:][order]
+    n_full = n_conf if full or not split else 1
+    quat = np.concatenate([chain.quat[:n_full], np.broadcast_to(q_obs, (n_full, n_obstacles, 4))], axis=1)
+    T = np.concatenate([chain.T[:n_full], np.broadcast_to(T_obs, (n_full, n_obstacles, 3))], axis=1)
     object_group = np.minimum(np.arange(n), n_links).astype(np.uint8)
     m = np.ones((n_links + 1, n_links + 1), dtype=bool)
     k = np.arange(n_links)
@@ -561,6 +572,12 @@ def scene_robot_env(n_conf, n_links, n_obstacles, seed=1, nper=64, link=1.6, ben
     pairs = pairs[np.lexsort((pairs[:, 1], pairs[:, 0]))].astype(np.uint32)
     scene = PlannerScene(chain.lib, obj_shape, np.ascontiguousarray(pairs), np.ascontiguousarray(quat), np.ascontiguousarray(T))
     scene.name = "scene_robot_env_%dx%d+%d" % (n_conf, n_links, n_obstacles)
+    if split:
+        env_tf, env_pose = scene.obj_tf[0, n_links:], scene.obj_pose_f32[0, n_links:]
+        moving_tf = geometry.make_pose(quat=chain.quat.reshape(-1, 4), T=chain.T.reshape(-1, 3)).reshape(n_conf, n_links, 12)
+        moving_pose = geometry.pose_f32_from_quat(chain.quat.reshape(-1, 4), chain.T.reshape(-1, 3)).reshape(n_conf, n_links, 7)
+        return (scene, (object_group, collides), scene.pairs, (np.ascontiguousarray(moving_tf), np.ascontiguousarray(env_tf)),
+                (np.ascontiguousarray(moving_pose), np.ascontiguousarray(env_pose)))
     return scene, (object_group, collides), scene.pairs
 
 

@@ -1552,6 +1552,70 @@ class Scene {
   }
   size_t numGroups() const { return hfcl_scene_num_groups(scene_); }
 
+  /// A static environment kept on the device (hfcl_scene_set_environment, include/hppfcl_amd_env.h): objects [n_moving, numObjects())
+  /// stand still at env_transforms (one per environment object); the calls below take tables of n_moving transforms a configuration.
+  /// Put the moving objects first and the environment in a spatial order: a box per 256 consecutive environment objects decides what a
+  /// sweep may skip.  The environment stays until clearEnvironment(), also when the scene is re-created.
+  void setEnvironment(size_t n_moving, const std::vector<Transform3f>& env_transforms) {
+    ensure();
+    if (n_moving > objects_.size() || env_transforms.size() != objects_.size() - n_moving)
+      throw std::invalid_argument("Scene::setEnvironment: one transform per object from n_moving on");
+    const int rc = hfcl_scene_set_environment(scene_, n_moving, reinterpret_cast<const double*>(env_transforms.data()));
+    if (rc) throw_for(rc);
+    env_ = env_transforms;
+    n_moving_ = n_moving;
+    has_env_ = true;
+  }
+  void clearEnvironment() {
+    ensure();
+    const int rc = hfcl_scene_clear_environment(scene_);
+    if (rc) throw_for(rc);
+    env_.clear();
+    has_env_ = false;
+  }
+  size_t numMoving() const { return hfcl_scene_n_moving(scene_); }
+  /// selfPairs / collideSelf / distanceSelf for a scene with an environment: the list of the full tables -- moving_tables[c] followed
+  /// by the environment -- less every entry whose first object is not a moving one (no environment x environment pair), from tables of
+  /// numMoving() transforms a configuration.  j of an entry (i, j) is an index into the whole scene.
+  void envPairs(const Transform3f* moving_tables, size_t n_conf, double inflate, std::vector<uint32_t>& pairs, std::vector<uint64_t>& conf_begin) {
+    ensure();
+    listed(n_conf, false, pairs, conf_begin, nullptr, [&](size_t capacity, size_t* n) {
+      return hfcl_scene_env_pairs(scene_, reinterpret_cast<const double*>(moving_tables), n_conf, inflate, pairs.data(), capacity, conf_begin.data(), n);
+    });
+  }
+  void collideEnv(const Transform3f* moving_tables, size_t n_conf, double inflate, const CollisionRequest& request,
+                  std::vector<CollisionResult>* results, std::vector<uint32_t>& pairs, std::vector<uint64_t>& conf_begin,
+                  std::vector<hfcl_scene_summary>* summaries) {
+    ensure();
+    const hfcl_collision_request a = to_abi(request);
+    const size_t n = listed(n_conf, results != nullptr, pairs, conf_begin, summaries, [&](size_t capacity, size_t* count) {
+      return hfcl_scene_collide_env(scene_, reinterpret_cast<const double*>(moving_tables), n_conf, inflate, &a, results ? rec_.data() : nullptr,
+                                    capacity, pairs.data(), conf_begin.data(), summaries ? summaries->data() : nullptr, nullptr,
+                                    results ? guess_.data() : nullptr, count);
+    });
+    if (!results) return;
+    results->assign(n, CollisionResult());
+    for (size_t k = 0; k < n; ++k) {
+      hfcl_result r = rec_[k];
+      if (r.num_contacts > 1) r.num_contacts = 1;
+      ctx_.fill((*results)[k], {shape_[pairs[2 * k]], shape_[pairs[2 * k + 1]]}, request, r, guess_[k]);
+    }
+  }
+  void distanceEnv(const Transform3f* moving_tables, size_t n_conf, double inflate, const DistanceRequest& request,
+                   std::vector<DistanceResult>* results, std::vector<uint32_t>& pairs, std::vector<uint64_t>& conf_begin,
+                   std::vector<hfcl_scene_summary>* summaries) {
+    ensure();
+    const hfcl_distance_request a = to_abi(request);
+    const size_t n = listed(n_conf, results != nullptr, pairs, conf_begin, summaries, [&](size_t capacity, size_t* count) {
+      return hfcl_scene_distance_env(scene_, reinterpret_cast<const double*>(moving_tables), n_conf, inflate, &a, results ? rec_.data() : nullptr,
+                                     capacity, pairs.data(), conf_begin.data(), summaries ? summaries->data() : nullptr, nullptr,
+                                     results ? guess_.data() : nullptr, count);
+    });
+    if (!results) return;
+    results->assign(n, DistanceResult());
+    for (size_t k = 0; k < n; ++k) ctx_.fill((*results)[k], {shape_[pairs[2 * k]], shape_[pairs[2 * k + 1]]}, rec_[k], guess_[k]);
+  }
+
   /// The clearance per configuration (hfcl_scene_nearest, include/hppfcl_amd_nearest.h): what DistanceCallBackDefault leaves behind
   /// after DynamicAABBTreeCollisionManager::distance -- the smallest distance over the listed pairs and the pair that has it --, with
   /// the pairs pruned by a bound from their world boxes instead of evaluated one by one.  summaries[c].min_distance / min_pair equal
@@ -1671,6 +1735,10 @@ class Scene {
       const int rc = hfcl_scene_set_groups(scene_, group_.data(), collides_.size(), collides_.data());
       if (rc) throw_for(rc);
     }
+    if (has_env_) {  // (the environment of the scene before)
+      const int rc = hfcl_scene_set_environment(scene_, n_moving_, reinterpret_cast<const double*>(env_.data()));
+      if (rc) throw_for(rc);
+    }
   }
   std::vector<Transform3f> current() const {
     std::vector<Transform3f> t(objects_.size());
@@ -1683,6 +1751,9 @@ class Scene {
   std::vector<uint32_t> shape_, pairs_;
   std::vector<uint8_t> group_;      // setGroups: kept for a scene made again
   std::vector<uint64_t> collides_;
+  std::vector<Transform3f> env_;    // setEnvironment: kept for a scene made again
+  size_t n_moving_ = 0;
+  bool has_env_ = false;
   hfcl_scene* scene_ = nullptr;
   hfcl_lib* lib_ = nullptr;
   size_t geometries_ = 0;

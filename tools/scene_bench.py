@@ -36,6 +36,14 @@ configuration) and on workloads.scene_planner at ~1 M queries.
      clearance taken from g -- the best possible guess (host clock; against g)        p  the same through the fp32 path
   q  o on the device: hfcl_scene_self_pairs_device at that inflate, the count read back, hfcl_scene_distance_pairs_device, summaries only
      (device events; against h)        r  the same through the fp32 path
+  s  hfcl_scene_env_pairs_device with the groups set: the list from the links' poses alone, the obstacles an environment set once (device
+     events; against c)
+  t  hfcl_scene_collide_env, summaries only (host clock; against d)        u  hfcl_scene_distance_env, summaries only (host clock)
+  v  t on the device: hfcl_scene_env_pairs_device, the count read back, hfcl_scene_collide_env_pairs_device, summaries only (device events)
+  w  the same with hfcl_scene_distance_env_pairs_device
+     s .. w report the bytes of the table a call takes against those of the full table, and whether the list is that of c.  Workloads
+     whose name ends in "s" have the obstacles in engine.spatial_order; robot32x65536x4096 (4 096 configurations: a full table of 25.8 GB)
+     runs s .. w alone.
 X .. b ignore the workload's pair list.  --options key=value,... sets library options in the worker (scene_pairs_small_max=0: the tiled form).
 The culled forms run at --inflate (default 0: the reference's manager).  planner2048: scene_planner(2048, 16), 215 040 queries;
 planner2048x32: scene_planner(2048, 32), 952 320 queries.  robot16x4096 / robot32x65536: workloads.scene_robot_env, 16 links and 4 096
@@ -66,24 +74,31 @@ sys.path.insert(0, ROOT)
 
 
 ROBOTS = {"robot16x4096": (256, 16, 4096), "robot32x65536": (8, 32, 65536)}  # (configurations, links, obstacles)
+ROBOTS.update({k + "s": v for k, v in list(ROBOTS.items())})  # ... the obstacles in spatial order
+ENV_ONLY = {"robot32x65536x4096": (4096, 32, 65536), "robot32x65536x4096s": (4096, 32, 65536)}  # (no full table: the env forms alone)
+ENV_FORMS = "stuvw"
 
 
 def _workload(pkg, name):
     wl = pkg.workloads
-    if name in ROBOTS:
-        sc, groups, pairs = wl.scene_robot_env(*ROBOTS[name])
-        return sc.lib, sc.obj_shape, pairs, sc.obj_tf, groups
+    if name in ROBOTS or name in ENV_ONLY:
+        if "split" not in wl.scene_robot_env.__code__.co_varnames:  # (a parent build's package: the rows that exist there)
+            sc, groups, pairs = wl.scene_robot_env(*ROBOTS[name])
+            return sc.lib, sc.obj_shape, pairs, sc.obj_tf, groups, None
+        sc, groups, pairs, split, _ = wl.scene_robot_env(*(ROBOTS.get(name) or ENV_ONLY[name]), split=True, spatial=name.endswith("s"),
+                                                         full=name in ROBOTS)
+        return sc.lib, sc.obj_shape, pairs, sc.obj_tf, groups, split
     if name == "cfg5":
         b = wl.cfg5_broadphase_scene()
         sc = b.scene
-        return b.lib, sc["obj_shape"], sc["pairs"], sc["obj_tf"].reshape(1, -1, 12), None
+        return b.lib, sc["obj_shape"], sc["pairs"], sc["obj_tf"].reshape(1, -1, 12), None, None
     if name == "planner2048x32":
         ps = wl.scene_planner(n_conf=2048, n_objects=32)
     elif name == "planner256x64":
         ps = wl.scene_planner(n_conf=256, n_objects=64)
     else:
         ps = wl.scene_planner(n_conf=2048 if name == "planner2048" else 9984, n_objects=16)
-    return ps.lib, ps.obj_shape, ps.pairs, ps.obj_tf, None
+    return ps.lib, ps.obj_shape, ps.pairs, ps.obj_tf, None, None
 
 
 def _stats(ms):
@@ -96,7 +111,7 @@ def worker(args):
     import __graft_entry__ as ge
     pkg = ge.load_pkg()
     abi = pkg.abi
-    L, obj_shape, pairs, table, groups = _workload(pkg, args.workload)
+    L, obj_shape, pairs, table, groups, split = _workload(pkg, args.workload)
     n_conf, G, P = table.shape[0], table.shape[1], len(pairs)
     n = n_conf * P
     i, j = pairs[:, 0], pairs[:, 1]
@@ -136,7 +151,9 @@ def worker(args):
         return _stats(ms)
 
     forms = args.forms.split(",")
-    scene = lib.scene(obj_shape, pairs) if set(forms) & set("BCEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqr") else None
+    if args.workload in ENV_ONLY:  # (the table holds configuration 0 alone)
+        forms = [f for f in forms if f in ENV_FORMS]
+    scene = lib.scene(obj_shape, pairs if args.workload not in ENV_ONLY else pairs[:0]) if set(forms) & set("BCEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvw") else None
     if "A" in forms or "D" in forms:
         t0 = time.perf_counter()
         s1, s2, tf1, tf2 = expand()
@@ -380,6 +397,48 @@ def worker(args):
                     out["forms"][letters[3]] = device_clock(lambda: near_d(d_t, n_conf, dreq, d_sum5, None, stream=st))
             except pkg.EngineError as err:
                 info["k_refused_" + tag] = str(err)
+    if set(forms) & set(ENV_FORMS) and split is not None and hasattr(scene, "set_environment"):  # a static environment kept on the device
+        moving_tf, env_tf = split
+        m_conf, n_links = moving_tf.shape[:2]
+        dreq = abi.default_distance_request()
+        scene.set_groups(*groups)
+        t0 = time.perf_counter()
+        scene.set_environment(n_links, env_tf)
+        info = out["env"] = {"n_conf": m_conf, "n_moving": n_links, "n_env": int(len(env_tf)), "set_environment_ms": 1e3 * (time.perf_counter() - t0),
+                             "table_bytes": int(moving_tf.nbytes), "full_table_bytes": 96 * m_conf * (n_links + len(env_tf)), "options": args.options}
+        d_mov = torch.from_numpy(np.ascontiguousarray(moving_tf)).to(dev)
+        d_ecb = torch.zeros(m_conf + 1, dtype=torch.int64, device=dev)
+        d_en = torch.zeros(1, dtype=torch.int64, device=dev)
+        d_esum = torch.zeros(m_conf * 6, dtype=torch.int32, device=dev)
+        scene.env_pairs_device(d_mov, m_conf, args.inflate, None, 0, d_ecb, d_en, stream=st)
+        cap_e = max(int(d_en.item()), 1)
+        info["n_listed"] = cap_e
+        d_ep = torch.zeros(2 * cap_e, dtype=torch.int32, device=dev)
+        if args.workload in ROBOTS:  # the list is the groups sweep's
+            ep, ecb = scene.env_pairs(moving_tf, args.inflate)
+            gp, gcb = scene.self_pairs(table, args.inflate)
+            info["equal_to_groups_list"] = bool(ep.tobytes() == gp.tobytes() and ecb.tobytes() == gcb.tobytes())
+            sys.path.insert(0, os.path.join(ROOT, "tests"))
+            import env_model
+            skipped, cells, _ = env_model.skipped_by_box(scene.world_aabbs(table), n_links, args.inflate)
+            info["cells_skipped_by_box_pct"] = 100.0 * float(skipped.sum()) / max(m_conf * cells, 1)
+
+        def env_device(fn, req_):
+            scene.env_pairs_device(d_mov, m_conf, args.inflate, d_ep, cap_e, d_ecb, d_en, stream=st)
+            k = int(d_en.item())  # the one read-back: 8 bytes
+            fn(d_mov, m_conf, d_ep, min(k, cap_e), d_ecb, req_, None, d_esum, stream=st)
+        if "s" in forms:
+            out["forms"]["s"] = device_clock(lambda: scene.env_pairs_device(d_mov, m_conf, args.inflate, d_ep, cap_e, d_ecb, d_en, stream=st))
+        if "t" in forms:
+            out["forms"]["t"] = host_clock(lambda: scene.collide_env(moving_tf, req, args.inflate, records=False))
+        if "u" in forms:
+            out["forms"]["u"] = host_clock(lambda: scene.distance_env(moving_tf, dreq, args.inflate, records=False))
+        if "v" in forms:
+            out["forms"]["v"] = device_clock(lambda: env_device(scene.collide_env_pairs_device, req))
+        if "w" in forms:
+            out["forms"]["w"] = device_clock(lambda: env_device(scene.distance_env_pairs_device, dreq))
+        scene.clear_groups()
+        scene.clear_environment()
     torch.cuda.synchronize()
     if scene is not None:
         scene.close()
@@ -404,7 +463,7 @@ def bytes_moved(n_conf, G, P):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--worker", action="store_true")
-    ap.add_argument("--workload", default="cfg5", choices=["cfg5", "planner", "planner2048", "planner2048x32", "planner256x64"] + sorted(ROBOTS))
+    ap.add_argument("--workload", default="cfg5", choices=["cfg5", "planner", "planner2048", "planner2048x32", "planner256x64"] + sorted(ROBOTS) + sorted(ENV_ONLY))
     ap.add_argument("--workloads", default="cfg5,planner", help="the workloads of a full run, comma-separated")
     ap.add_argument("--inflate", type=float, default=0.0)
     ap.add_argument("--options", default="", help="library options of the worker: key=value,...")
@@ -453,7 +512,7 @@ def main():
         print("| form | build | median ms | min .. max ms (over the runs) |")
         print("|---|---|---|---|")
         for which in ("parent", "new", "control"):
-            for f in "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqr":
+            for f in "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvw":
                 runs = [r["forms"][f] for r in rs if r["build"] == which and f in r["forms"]]
                 if runs:
                     print("| %s | %s | %s | %.3f .. %.3f |" % (f, which, " / ".join("%.3f" % x["median_ms"] for x in runs),
@@ -480,6 +539,9 @@ def main():
         ns = [r["nearest_self"] for r in rs if "nearest_self" in r]
         if ns:
             print("clearance on device-made pairs: " + json.dumps(ns[-1]))
+        es = [r["env"] for r in rs if "env" in r]
+        if es:
+            print("environment: " + json.dumps(es[-1]))
         if "n_listed" in r0:
             print("cull at inflate %g: %d of %d queries survive (%.2f %%); byte model of the cull alone: %.0f bytes" % (
                 r0["inflate"], r0["n_listed"], r0["queries"], 100.0 * r0["n_listed"] / r0["queries"], r0["cull_model_bytes"]))
