@@ -678,7 +678,8 @@ def _scene_run(kind, objects, pair_indices, request, transforms, broadphase=Fals
     """The pair list `pair_indices` ((n_pairs, 2) indices into `objects`) for every configuration: ONE scene call.  broadphase: the
     list is culled per configuration on the device first (boxes grown by `inflate`); rec / g then hold the surviving queries only and
     the last two items are their ids q = c * n_pairs + p and conf_begin (None without broadphase).  nearest_bound (distance only): the
-    pruned minimum (engine.Scene.nearest; with broadphase="self" engine.Scene.nearest_self, the summaries then being its clearances) with
+    pruned minimum (engine.Scene.nearest; with broadphase="self" engine.Scene.nearest_self, with broadphase="env" engine.Scene.nearest_env,
+    the summaries then being its clearances) with
     that upper bound; rec then holds one min record per configuration and g is None.
     groups (broadphase="self" or "env"): (object_group, collides) for engine.Scene.set_groups.
     broadphase="env", n_moving=K: as "self" for a scene whose objects[K:] stand still at their own transforms (engine.Scene.set_environment);
@@ -696,8 +697,6 @@ def _scene_run(kind, objects, pair_indices, request, transforms, broadphase=Fals
         raise ValueError('broadphase="env" and n_moving go together')
     if env and not 0 <= int(n_moving) <= len(objects):
         raise ValueError("n_moving outside the objects")
-    if env and nearest_bound is not None:
-        raise ValueError('the pruned minimum (nearest=True) takes full tables: broadphase="self"')
     n_table = int(n_moving) if env else len(objects)  # objects a configuration of `transforms` holds
     pr = np.ascontiguousarray([] if self_pairs or pair_indices is None else pair_indices, dtype=np.uint32).reshape(-1, 2)
     if len(pr) and int(pr.max()) >= len(objects):
@@ -729,6 +728,10 @@ def _scene_run(kind, objects, pair_indices, request, transforms, broadphase=Fals
             sc.set_groups(*groups)
         if env:
             sc.set_environment(n_table, own(objects[n_table:]))
+        if env and nearest_bound is not None:  # (summ: the clearances, hfcl_scene_clearance)
+            summ, rec, _ = sc.nearest_env(table, request._abi(), float(nearest_bound))
+            g = None
+        elif env:
             fn = sc.distance_env if kind == "distance" else sc.collide_env
             rec, ids, conf_begin, summ, g = fn(table, request._abi(), float(inflate), records=True, want_guess=True)
         elif nearest_bound is not None and self_pairs:  # (summ: the clearances, hfcl_scene_clearance)
@@ -826,15 +829,14 @@ def distance_scene(objects, pair_indices, request, transforms=None, broadphase=F
     pair (i < j) the `groups` allow, the pairs made and pruned on the device (engine.Scene.nearest_self) --
     DynamicAABBTreeCollisionManager::distance(otherManager, DistanceCallBackDefault) with two groups.
     broadphase="env", n_moving=K: as in collide_scene -- objects[K:] are the environment, `transforms` is (n_conf, K, 12); the items are
-    those of "self"."""
-    if nearest and broadphase == "env":
-        raise ValueError('the pruned minimum (nearest=True) takes full tables: broadphase="self"')
-    self_pairs = isinstance(broadphase, str) and broadphase == "self"
+    those of "self".  With nearest=True: the clearance of the K moving objects among themselves and against the environment
+    (engine.Scene.nearest_env), never a pair of two environment objects."""
+    self_pairs = isinstance(broadphase, str) and broadphase in ("self", "env")
     if nearest and groups is not None and not self_pairs:
-        raise ValueError('groups need broadphase="self": the pruned minimum (nearest=True) runs on the pair list')
+        raise ValueError('groups need broadphase="self" or "env": the pruned minimum (nearest=True) runs on the pair list')
     if nearest:
-        geoms, pr, n_conf, rec, summ, _, _, _ = _scene_run("distance", objects, pair_indices, request, transforms, "self" if self_pairs else False,
-                                                           nearest_bound=upper_bound, groups=groups)
+        geoms, pr, n_conf, rec, summ, _, _, _ = _scene_run("distance", objects, pair_indices, request, transforms, broadphase if self_pairs else False,
+                                                           nearest_bound=upper_bound, groups=groups, n_moving=n_moving)
         out = []
         for c in range(n_conf):
             res = DistanceResult()

@@ -126,6 +126,9 @@ struct hfcl_options {
   uint32_t scene_pairs_small_max = 32;
   // hfcl_scene_env_pairs*: column tiles per workgroup of the sweep (option scene_env_span; 0: automatic, hfcl_env.hpp: env_auto_span)
   uint32_t scene_env_span = 0;
+  // hfcl_scene_nearest_env*: drop whole (row block, environment tile) cells of a pass by a bound of their distance (option
+  // scene_nearest_env_prune; hfcl_nearest_env.hpp: nenv_tile_bound).  0: no cell is dropped by distance; the same bytes either way
+  bool scene_nearest_env_prune = true;
   // Queries per chunk of a scene call (option scene_chunk; 0: automatic -- at most 2^21 queries, the call cut into equal chunks).  The chunks of a
   // call run one after the other, and the solvers' kernels are chains of dependent steps that fill the chip only with a large batch: cfg5's
   // 1.07 M queries in chunks of 262144 (the host pipeline's steady chunk) took 5.9 ms against 2.4 ms for the per-pair call on resident arrays,

@@ -5,9 +5,11 @@
 #include "hfcl_nearest.hpp"
 #include "hfcl_nearest_self.hpp"
 #include "hfcl_env.hpp"
+#include "hfcl_nearest_env.hpp"
 #include "../../include/hppfcl_amd_nearest.h"
 #include "../../include/hppfcl_amd_groups.h"
 #include "../../include/hppfcl_amd_nearest_self.h"
+#include "../../include/hppfcl_amd_nearest_env.h"
 #include "../../include/hppfcl_amd_pairs.h"
 #include "../../include/hppfcl_amd_env.h"
 
@@ -35,6 +37,8 @@ struct hfcl_scene {
   DevBuf<void> d_env_table;
   DevBuf<double> d_env_boxes, d_env_tile_boxes;
   DevBuf<uint64_t> d_env_tile_groups;
+  // ... and the terms of the clearance bound (hfcl_nearest_env.hpp): two doubles per environment box, two per tile
+  DevBuf<double> d_env_terms, d_env_tile_terms;
   size_t n_env() const { return n_objects - n_moving; }
 };
 
@@ -996,16 +1000,19 @@ static int env_set(const char* who, hfcl_scene* s, size_t n_moving, const T* env
   rc = ensure_local_boxes(lib);
   if (rc) return rc;
   DevBuf<void> d_table;
-  DevBuf<double> d_boxes, d_tile_boxes;
+  DevBuf<double> d_boxes, d_tile_boxes, d_terms, d_tile_terms;
   if (n_env) {
     const size_t bytes = n_env * SceneTypes<T>::WIDTH * sizeof(T);
     HIP_TRY(d_table.grow(bytes));
     HIP_TRY(d_boxes.grow(n_env * 6));
     HIP_TRY(d_tile_boxes.grow(size_t(env_tiles(uint32_t(n_env))) * 6));
+    HIP_TRY(d_terms.grow(n_env * 2));
+    HIP_TRY(d_tile_terms.grow(size_t(env_tiles(uint32_t(n_env))) * 2));
     HIP_TRY(hipMemcpy(d_table, env_rows, bytes, hipMemcpyHostToDevice));
     // the boxes with the kernel of hfcl_scene_world_aabbs*: row r of this table is object n_moving + r
     launch_cull_aabbs(nullptr, d_table, std::is_same<T, float>::value, s->d_object_shape.get() + n_moving, lib->d_local_boxes, n_env, n_env, d_boxes);
     launch_env_tile_boxes(nullptr, d_boxes, uint32_t(n_env), d_tile_boxes);
+    launch_nenv_terms(nullptr, d_boxes, uint32_t(n_env), d_terms, d_tile_terms);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(nullptr));
   }
@@ -1013,6 +1020,8 @@ static int env_set(const char* who, hfcl_scene* s, size_t n_moving, const T* env
   s->d_env_table = std::move(d_table);
   s->d_env_boxes = std::move(d_boxes);
   s->d_env_tile_boxes = std::move(d_tile_boxes);
+  s->d_env_terms = std::move(d_terms);
+  s->d_env_tile_terms = std::move(d_tile_terms);
   s->has_env = true;
   s->env_f32 = std::is_same<T, float>::value;
   s->n_moving = n_moving;
@@ -1157,7 +1166,7 @@ template <typename T>
 static int scene_env_pairs_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const uint32_t* d_pairs, size_t n_listed,
                                   const uint64_t* d_conf_begin, const hfcl_collision_request* creq, const hfcl_distance_request* dreq,
                                   typename SceneTypes<T>::R* d_out, hfcl_scene_summary* d_summary, const hfcl_guess* d_gin, hfcl_guess* d_gout,
-                                  hipStream_t st) {
+                                  hipStream_t st, SceneCountSlots* counts = nullptr) {
   bool nothing;
   int rc = env_scene_validate<T>(who, s, d_table, n_conf, creq, dreq, d_out, d_summary, nothing);
   if (rc) return rc;
@@ -1181,7 +1190,7 @@ static int scene_env_pairs_device(const char* who, hfcl_scene* s, const void* d_
     return HFCL_OK;
   }
   const SceneList list = env_list(s, d_pairs, d_conf_begin, n_conf, n_listed);
-  return scene_chunks_device<T>(s, d_table, &list, n_listed, creq, dreq, d_out, d_summary, d_gin, d_gout, st);
+  return scene_chunks_device<T>(s, d_table, &list, n_listed, creq, dreq, d_out, d_summary, d_gin, d_gout, st, counts);
 }
 
 // what the culled host forms (hfcl_scene_*_culled) add to scene_host
@@ -1702,6 +1711,222 @@ static int nearest_self_host(const char* who, hfcl_scene* s, const void* table, 
   return host_batch_checks(lib, nullptr, req);
 }
 
+// ---------------------------------------------------------------------------------------
+// The clearance of the moving objects among an environment kept on the device (include/hppfcl_amd_nearest_env.h: hfcl_scene_nearest_env*).
+// hfcl_k_nearest_env.hip has the kernels, hfcl_nearest_env.hpp the arithmetic.  nearest_self_run over the cells, chunks and spans of
+// env_pairs_device: the seeds (a partial per (row, span), then a wave per configuration); count and emit of pass 1, its count read back,
+// its narrow phase through scene_env_pairs_device into summaries of its own; the thresholds; the same for pass 2; the two combined.
+// Two read-backs of 8 bytes.
+// ---------------------------------------------------------------------------------------
+// nothing: n_conf == 0 or no moving object
+template <typename T>
+static int nearest_env_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, const hfcl_distance_request* req,
+                                double upper, const void* out, bool& nothing) {
+  nothing = true;
+  if (upper != upper) {
+    set_error(std::string(who) + ": upper_bound is NaN");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (s && !req) {
+    set_error("null request");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (s && !out) {
+    set_error(std::string(who) + ": null output");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (s) {
+    QParams<T> q;
+    if (const int rc = setup_distance<T>(req, q)) return rc;
+  }
+  const int rc = env_validate<T>(who, s, table, n_conf, nothing);
+  return rc ? rc : env_limits(who, s);
+}
+
+// moving table on the device, n_conf > 0, at least one moving object, everything on st (which is waited for twice)
+template <typename T>
+static int nearest_env_run(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const hfcl_distance_request* req, double upper,
+                           hfcl_scene_clearance* d_out, typename SceneTypes<T>::R* d_min, size_t* n_evaluated, SceneCountSlots* counts,
+                           hipStream_t st) {
+  using R = typename SceneTypes<T>::R;
+  constexpr bool f32 = std::is_same<T, float>::value;
+  hfcl_lib* lib = s->lib;
+  hfcl_lib::SceneWs& w = lib->scene;
+  int rc = ensure_local_boxes(lib);
+  if (rc) return rc;
+  const uint32_t nm = uint32_t(s->n_moving), ne = uint32_t(s->n_env());
+  const PairsGeometry rows = pairs_geometry(nm, false);
+  const uint64_t n_blocks = uint64_t(n_conf) * rows.blocks_per_conf;
+  const uint32_t tiles = env_geometry(nm, ne, 0u).tiles;
+  const uint32_t span = lib->opt.scene_env_span ? lib->opt.scene_env_span : env_auto_span(tiles, n_blocks, uint32_t(std::max(lib->n_cus, 1)), ENV_AUTO_PER_CU);
+  const EnvGeometry geo = env_geometry(nm, ne, span);
+  const uint64_t per = env_chunk_blocks(geo, n_blocks, lib->opt.scene_cull_chunk);
+  const size_t conf_per_chunk = std::min<size_t>(n_conf, size_t(per / rows.blocks_per_conf) + 2);
+  const size_t moving_rows = n_conf * size_t(nm);
+  HIP_TRY(w.d_boxes.grow(conf_per_chunk * nm * 6));
+  const uint64_t chunk_rows = std::min<uint64_t>(per * rows.rows_per_block, uint64_t(moving_rows));
+  rc = pairs_chunk_buffers(lib, size_t(chunk_rows * geo.n_spans));
+  if (rc) return rc;
+  HIP_TRY(w.d_ns_row_seeds.grow(moving_rows * geo.n_spans * sizeof(NselfRowSeed)));
+  HIP_TRY(w.d_ns_seed.grow(n_conf));
+  HIP_TRY(w.d_ns_thr.grow(n_conf));
+  for (int l = 0; l < 2; ++l) {
+    HIP_TRY(w.d_ns_conf_begin[l].grow(n_conf + 1));
+    HIP_TRY(w.d_ns_summary[l].grow(n_conf));
+    HIP_TRY(w.d_ns_list[l].grow(2 * pairs_capacity_guess(moving_rows)));
+  }
+
+  NenvArgs a{};
+  pairs_args(a.e.p, s, rows, false, n_conf);
+  a.e.p.tile_groups = nullptr;
+  a.e.p.n_objects = nm * geo.n_spans;  // (the scan's rows: (row, span) counts, row-major)
+  a.e.p.total_rows = uint64_t(n_conf) * nm * geo.n_spans;
+  a.e.n_moving = nm;
+  a.e.n_env = ne;
+  a.e.tiles_moving = geo.tiles_moving;
+  a.e.tiles = geo.tiles;
+  a.e.span_len = geo.span_len;
+  a.e.n_spans = geo.n_spans;
+  a.e.blocks_per_conf = rows.blocks_per_conf;
+  a.e.env_boxes = s->d_env_boxes;
+  a.e.env_tile_boxes = s->d_env_tile_boxes;
+  a.e.col_tile_groups = s->n_groups ? s->d_env_tile_groups.get() : nullptr;
+  a.r = f32 ? NEAREST_R32 : NEAREST_R64;
+  a.upper = upper;
+  a.prune = lib->opt.scene_nearest_env_prune ? 1 : 0;
+  a.row_seeds = w.d_ns_row_seeds.get();
+  a.seed = w.d_ns_seed;
+  a.thr = w.d_ns_thr;
+  a.env_terms = s->d_env_terms;
+  a.env_tile_terms = s->d_env_tile_terms;
+  // the chunks in turn: the boxes of the moving rows of the configurations a chunk touches, then the chunk's cells
+  auto walk = [&](auto&& launch) {
+    pairs_chunks<T>(a.e.p, s, d_table, rows, n_blocks, per, st, [&]() {
+      a.e.row0 = a.e.p.row0;
+      a.e.p.row0 = a.e.row0 * geo.n_spans;
+      a.e.p.n_rows = uint32_t(uint64_t(a.e.p.n_rows) * geo.n_spans);
+      launch();
+    });
+  };
+  walk([&]() { launch_nenv_seed(st, a); });
+  launch_nenv_seed_combine(st, a, lib->n_cus * 16);
+
+  uint64_t n_list[2] = {0, 0};
+  for (int pass = 1; pass <= 2; ++pass) {
+    const int l = pass - 1;
+    if (pass == 2) {  // thr[c] = min(D, min_distance of pass 1)
+      NearestArgs t{};
+      t.c.n_conf = n_conf;
+      t.upper = upper;
+      t.thr = w.d_ns_thr;
+      launch_nearest_threshold(st, t, w.d_ns_summary[0]);
+    }
+    a.pass = pass;
+    a.e.p.conf_begin = w.d_ns_conf_begin[l];
+    a.e.p.n_listed = w.d_running + 1;
+    rc = list_and_count(w.d_ns_list[l], true, w.d_running + 1, st, n_list[l], [&]() {  // the pass's list, and the one read-back: its count
+      a.e.p.pairs = w.d_ns_list[l];
+      a.e.p.capacity = w.d_ns_list[l].capacity() / 2;
+      walk([&]() { launch_nenv_chunk(st, a); });
+      return int(HFCL_OK);
+    }, 2);
+    if (!rc) rc = env_rank_limit(who, n_list[l], s);
+    if (rc) return rc;
+    if (d_min) HIP_TRY(w.d_ns_rec[l].grow(size_t(n_list[l]) * sizeof(R)));
+    rc = scene_env_pairs_device<T>(who, s, d_table, n_conf, w.d_ns_list[l], size_t(n_list[l]), w.d_ns_conf_begin[l], nullptr, req,
+                                   d_min ? static_cast<R*>(w.d_ns_rec[l].get()) : nullptr, w.d_ns_summary[l], nullptr, nullptr, st, counts);
+    if (rc) return rc;
+  }
+  NselfCombineArgs g{};
+  g.n_conf = n_conf;
+  for (int l = 0; l < 2; ++l) {
+    g.summary[l] = w.d_ns_summary[l];
+    g.pairs[l] = w.d_ns_list[l];
+    g.conf_begin[l] = w.d_ns_conf_begin[l];
+    g.rec[l] = d_min ? w.d_ns_rec[l].get() : nullptr;
+  }
+  g.out = d_out;
+  g.min_out = d_min;
+  launch_nself_combine(st, g, f32);
+  if (n_evaluated) {
+    n_evaluated[0] = size_t(n_list[0]);
+    n_evaluated[1] = size_t(n_list[1]);
+  }
+  HIP_TRY(hipGetLastError());
+  return HFCL_OK;
+}
+
+template <typename T>
+static int nearest_env_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const hfcl_distance_request* req, double upper,
+                              hfcl_scene_clearance* d_out, typename SceneTypes<T>::R* d_min, size_t* n_evaluated, hipStream_t st) {
+  bool nothing;
+  const int rc = nearest_env_validate<T>(who, s, d_table, n_conf, req, upper, d_out, nothing);
+  if (rc) return rc;
+  if (n_evaluated) n_evaluated[0] = n_evaluated[1] = 0;
+  if (!n_conf) return HFCL_OK;
+  hfcl_lib* lib = s->lib;
+  HIP_TRY(hipSetDevice(lib->device));
+  if (nothing) {  // no moving object: every configuration is one without records
+    NselfCombineArgs g{};
+    g.n_conf = n_conf;
+    g.out = d_out;
+    g.min_out = d_min;
+    launch_nself_combine(st, g, std::is_same<T, float>::value);
+    HIP_TRY(hipGetLastError());
+    return HFCL_OK;
+  }
+  return nearest_env_run<T>(who, s, d_table, n_conf, req, upper, d_out, d_min, n_evaluated, nullptr, st);
+}
+
+template <typename T>
+static int nearest_env_host(const char* who, hfcl_scene* s, const void* table, size_t n_conf, const hfcl_distance_request* req, double upper,
+                            hfcl_scene_clearance* out, typename SceneTypes<T>::R* min_records, size_t* n_evaluated) {
+  using R = typename SceneTypes<T>::R;
+  bool nothing;
+  int rc = nearest_env_validate<T>(who, s, table, n_conf, req, upper, out, nothing);
+  if (rc) return rc;
+  if (n_evaluated) n_evaluated[0] = n_evaluated[1] = 0;
+  if (!n_conf) return HFCL_OK;
+  if (nothing) {
+    const hfcl_scene_summary* no_summary[2] = {nullptr, nullptr};
+    const uint32_t* no_pairs[2] = {nullptr, nullptr};
+    const uint64_t* no_begin[2] = {nullptr, nullptr};
+    const R* no_rec[2] = {nullptr, nullptr};
+    for (size_t c = 0; c < n_conf; ++c) nself_combine<R>(c, no_summary, no_pairs, no_begin, no_rec, out[c], min_records ? &min_records[c] : nullptr);
+    return HFCL_OK;
+  }
+  hfcl_lib* lib = s->lib;
+  hfcl_lib::SceneWs& w = lib->scene;
+  HIP_TRY(hipSetDevice(lib->device));
+  rc = scene_host_stream(w);
+  if (rc) return rc;
+  HIP_TRY(w.d_ns_out.grow(n_conf));
+  if (min_records) HIP_TRY(w.d_minrec.grow(n_conf * sizeof(R)));
+  rc = SceneCountSlots::ready(w);
+  if (rc) return rc;
+  SceneCountSlots counts(lib);  // (ends after finish has waited for the streams)
+  auto finish = [&](int code) {  // nothing of this call stays in flight, whatever happened
+    const bool synced = hipStreamSynchronize(w.s_cmp) == hipSuccess;
+    if (lib->side) hipStreamSynchronize(lib->side);
+    if (code == HFCL_OK && synced) counts.harvest_rest();
+    if (code == HFCL_OK && !synced) {
+      set_error(std::string(who) + ": the device reported an error");
+      return int(HFCL_ERR_HIP);
+    }
+    return code;
+  };
+  rc = scene_table_in(w, table, n_conf * s->n_moving * SceneTypes<T>::WIDTH * sizeof(T));
+  if (!rc) rc = nearest_env_run<T>(who, s, w.d_table, n_conf, req, upper, w.d_ns_out, min_records ? static_cast<R*>(w.d_minrec.get()) : nullptr,
+                                   n_evaluated, &counts, w.s_cmp);
+  if (!rc && hipMemcpyAsync(out, w.d_ns_out, n_conf * sizeof(hfcl_scene_clearance), hipMemcpyDeviceToHost, w.s_cmp) != hipSuccess) rc = HFCL_ERR_HIP;
+  if (!rc && min_records && hipMemcpyAsync(min_records, w.d_minrec, n_conf * sizeof(R), hipMemcpyDeviceToHost, w.s_cmp) != hipSuccess)
+    rc = HFCL_ERR_HIP;
+  rc = finish(rc);
+  if (rc) return rc;
+  lib->last_host = true;
+  return host_batch_checks(lib, nullptr, req);
+}
+
 extern "C" {
 
 hfcl_scene* hfcl_scene_create(hfcl_lib* lib, const uint32_t* object_shape, size_t n_objects, const uint32_t* pairs, size_t n_pairs) {
@@ -2063,7 +2288,7 @@ int hfcl_scene_clear_environment(hfcl_scene* s) {
   if (const int rc = groups_scene("hfcl_scene_clear_environment", s)) return rc;
   HIP_TRY(hipSetDevice(s->lib->device));
   s->d_env_table.reset();  // (waits for the device: a query in flight on some stream may still be reading the tables)
-  reset_all(s->d_env_boxes, s->d_env_tile_boxes);
+  reset_all(s->d_env_boxes, s->d_env_tile_boxes, s->d_env_terms, s->d_env_tile_terms);
   s->d_env_tile_groups.reset();
   s->has_env = false;
   s->n_moving = 0;
@@ -2168,6 +2393,31 @@ int hfcl_scene_distance_env_f32(hfcl_scene* s, const float* moving_pose, size_t 
   PAIRS_ENTRY;
   const SceneCull cull = env_form(inflate, out_capacity, pairs_out, conf_begin_out, n_listed);
   return scene_host<float>("hfcl_scene_distance_env_f32", s, moving_pose, n_conf, nullptr, req, out, summary, nullptr, nullptr, &cull);
+}
+
+// ---- the clearance of the moving objects among the environment (include/hppfcl_amd_nearest_env.h) ---------------------------------------
+int hfcl_scene_nearest_env(hfcl_scene* s, const double* moving_tf, size_t n_conf, const hfcl_distance_request* req, double upper_bound,
+                           hfcl_scene_clearance* out, hfcl_result* min_records, size_t* n_evaluated) {
+  PAIRS_ENTRY;
+  return nearest_env_host<double>("hfcl_scene_nearest_env", s, moving_tf, n_conf, req, upper_bound, out, min_records, n_evaluated);
+}
+int hfcl_scene_nearest_env_f32(hfcl_scene* s, const float* moving_pose, size_t n_conf, const hfcl_distance_request* req, double upper_bound,
+                               hfcl_scene_clearance* out, hfcl_result_f32* min_records, size_t* n_evaluated) {
+  PAIRS_ENTRY;
+  return nearest_env_host<float>("hfcl_scene_nearest_env_f32", s, moving_pose, n_conf, req, upper_bound, out, min_records, n_evaluated);
+}
+int hfcl_scene_nearest_env_device(hfcl_scene* s, const double* d_moving_tf, size_t n_conf, const hfcl_distance_request* req, double upper_bound,
+                                  hfcl_scene_clearance* d_out, hfcl_result* d_min_records, size_t* n_evaluated, void* stream) {
+  PAIRS_ENTRY;
+  return nearest_env_device<double>("hfcl_scene_nearest_env_device", s, d_moving_tf, n_conf, req, upper_bound, d_out, d_min_records, n_evaluated,
+                                    (hipStream_t)stream);
+}
+int hfcl_scene_nearest_env_device_f32(hfcl_scene* s, const float* d_moving_pose, size_t n_conf, const hfcl_distance_request* req,
+                                      double upper_bound, hfcl_scene_clearance* d_out, hfcl_result_f32* d_min_records, size_t* n_evaluated,
+                                      void* stream) {
+  PAIRS_ENTRY;
+  return nearest_env_device<float>("hfcl_scene_nearest_env_device_f32", s, d_moving_pose, n_conf, req, upper_bound, d_out, d_min_records,
+                                   n_evaluated, (hipStream_t)stream);
 }
 #undef PAIRS_ENTRY
 

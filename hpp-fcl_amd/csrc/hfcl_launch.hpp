@@ -321,3 +321,26 @@ struct NselfCombineArgs {
   void* min_out;             // nullptr or n_conf records
 };
 void launch_nself_combine(hipStream_t st, const NselfCombineArgs& a, bool f32);
+
+// hfcl_k_nearest_env.hip: the clearance of the moving objects among an environment kept on the device (hfcl_scene_nearest_env*;
+// hfcl_nearest_env.hpp has the arithmetic).  Set time: two doubles per environment box (nenv_box_terms) and per tile (nenv_tile_terms)
+void launch_nenv_terms(hipStream_t st, const double* env_boxes, uint32_t n_env, double* env_terms, double* tile_terms);
+// The cells, chunks and (row, span) arrays are those of EnvArgs (e.p.inflate unused: nothing is inflated).
+struct NenvArgs {
+  EnvArgs e;
+  double r;                      // the bound's rounding term: NEAREST_R64 / NEAREST_R32
+  double upper;                  // the caller's upper bound D
+  int pass;                      // launch_nenv_chunk: 1 / 2
+  int prune;                     // 0: no environment tile is dropped by its distance (option scene_nearest_env_prune)
+  void* row_seeds;               // a NselfRowSeed per (row, span) of the WHOLE table, row-major (a configuration may straddle chunks)
+  uint64_t* seed;                // n_conf pairs as words (nself_key; NSELF_NO_PAIR: no candidate)
+  const double* thr;             // n_conf: read by pass 2
+  const double* env_terms;       // 2 x n_env
+  const double* env_tile_terms;  // 2 x ceil(n_env / PAIRS_TILE)
+};
+// a chunk's part of the seeds: its cells' partials
+void launch_nenv_seed(hipStream_t st, const NenvArgs& a);
+// after the last chunk: seed[c] from the partials, a wave per configuration
+void launch_nenv_seed_combine(hipStream_t st, const NenvArgs& a, int max_blocks);
+// a chunk of pass a.pass: count, launch_pairs_scan, emit (e.p.pairs == nullptr / capacity 0: count only)
+void launch_nenv_chunk(hipStream_t st, const NenvArgs& a);

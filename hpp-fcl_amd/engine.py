@@ -69,6 +69,10 @@ ENV_SYMBOLS = [
     "hfcl_scene_collide_env_pairs_device_f32", "hfcl_scene_distance_env_pairs_device_f32", "hfcl_scene_collide_env",
     "hfcl_scene_distance_env", "hfcl_scene_collide_env_f32", "hfcl_scene_distance_env_f32",
 ]
+# include/hppfcl_amd_nearest_env.h (included by hppfcl_amd.h): the clearance of the moving objects among the environment kept on the device
+NEAREST_ENV_SYMBOLS = [
+    "hfcl_scene_nearest_env", "hfcl_scene_nearest_env_f32", "hfcl_scene_nearest_env_device", "hfcl_scene_nearest_env_device_f32",
+]
 
 
 class EngineError(RuntimeError):
@@ -1070,6 +1074,36 @@ class Scene:
         n = (C.c_size_t * 2)()
         _check(dll().hfcl_scene_nearest_self_device_f32(self._h, _dptr(d_object_pose), C.c_size_t(int(n_conf)), C.byref(req),
                                                         C.c_double(upper_bound), _dptr(d_out), _dptr(d_min_records), n, C.c_void_p(stream)))
+        return int(n[0]), int(n[1])
+
+    # ---- the clearance of the moving objects among the environment (include/hppfcl_amd_nearest_env.h) ----
+    def nearest_env(self, moving_tf, req=None, upper_bound=float("inf"), records=True):
+        """hfcl_scene_nearest_env{,_f32}: nearest_self for a scene with an environment set, from a (n_conf, n_moving, W) table of the moving
+        objects alone -- (clearance SCENE_CLEARANCE_DTYPE[n_conf], min_records, n_evaluated).  The candidates are the allowed pairs (i, j),
+        i < n_moving, i < j < n_objects: never two environment objects; min_i / min_j index the full scene.  Whole tiles of 256 environment
+        objects are dropped by a bound of their distance (option scene_nearest_env_prune, default 1): time, never a byte."""
+        tf, f32 = self._moving_table(moving_tf)
+        n_conf = len(tf)
+        out = np.zeros(n_conf, dtype=abi.SCENE_CLEARANCE_DTYPE)
+        rec = np.zeros(n_conf, dtype=abi.RESULT_F32_DTYPE if f32 else abi.RESULT_DTYPE) if records else None
+        n = (C.c_size_t * 2)()
+        fn = dll().hfcl_scene_nearest_env_f32 if f32 else dll().hfcl_scene_nearest_env
+        _check(fn(self._h, abi.ptr(tf), C.c_size_t(n_conf), C.byref(req or abi.default_distance_request()), C.c_double(upper_bound),
+                  abi.ptr(out), abi.ptr(rec), n))
+        return out, rec, (int(n[0]), int(n[1]))
+
+    def nearest_env_device(self, d_moving_tf, n_conf, req, d_out, d_min_records=None, upper_bound=float("inf"), stream=0):
+        """hfcl_scene_nearest_env_device: device tensors or pointers, enqueued on `stream`, which the call waits on twice (the two list
+        counts).  Returns n_evaluated."""
+        n = (C.c_size_t * 2)()
+        _check(dll().hfcl_scene_nearest_env_device(self._h, _dptr(d_moving_tf), C.c_size_t(int(n_conf)), C.byref(req), C.c_double(upper_bound),
+                                                   _dptr(d_out), _dptr(d_min_records), n, C.c_void_p(stream)))
+        return int(n[0]), int(n[1])
+
+    def nearest_env_device_f32(self, d_moving_pose, n_conf, req, d_out, d_min_records=None, upper_bound=float("inf"), stream=0):
+        n = (C.c_size_t * 2)()
+        _check(dll().hfcl_scene_nearest_env_device_f32(self._h, _dptr(d_moving_pose), C.c_size_t(int(n_conf)), C.byref(req),
+                                                       C.c_double(upper_bound), _dptr(d_out), _dptr(d_min_records), n, C.c_void_p(stream)))
         return int(n[0]), int(n[1])
 
 

@@ -1665,6 +1665,27 @@ class Scene {
       if (clearances[c].min_i != 0xFFFFFFFFu) ctx_.fill((*results)[c], {shape_[clearances[c].min_i], shape_[clearances[c].min_j]}, rec_[c], g);
   }
 
+  /// nearestSelf for a scene with an environment set (hfcl_scene_nearest_env, include/hppfcl_amd_nearest_env.h): `moving` holds n_conf
+  /// tables of the moving objects alone (hfcl_scene_n_moving rows each); the candidates are the allowed pairs with a moving object in
+  /// them, never environment x environment; min_i / min_j index the full scene.  Outputs as nearestSelf.
+  void nearestEnv(const Transform3f* moving, size_t n_conf, const DistanceRequest& request, double upper_bound,
+                  std::vector<hfcl_scene_clearance>& clearances, std::vector<DistanceResult>* results = nullptr, size_t* n_evaluated = nullptr) {
+    ensure();
+    const hfcl_distance_request a = to_abi(request);
+    clearances.resize(n_conf);
+    if (results) rec_.resize(n_conf);
+    const int rc = hfcl_scene_nearest_env(scene_, reinterpret_cast<const double*>(moving), n_conf, &a, upper_bound, clearances.data(),
+                                          results ? rec_.data() : nullptr, n_evaluated);
+    if (rc) throw_for(rc);
+    if (!results) return;
+    results->assign(n_conf, DistanceResult());
+    hfcl_guess g;
+    std::memset(&g, 0, sizeof(g));
+    g.gjk_guess[0] = 1.0;  // (DistanceResult's own default: no guess comes back from this call)
+    for (size_t c = 0; c < n_conf; ++c)
+      if (clearances[c].min_i != 0xFFFFFFFFu) ctx_.fill((*results)[c], {shape_[clearances[c].min_i], shape_[clearances[c].min_j]}, rec_[c], g);
+  }
+
  private:
   size_t list_guess(size_t n_conf) const {
     const size_t total = n_conf * numPairs();

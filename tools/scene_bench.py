@@ -44,11 +44,16 @@ configuration) and on workloads.scene_planner at ~1 M queries.
      s .. w report the bytes of the table a call takes against those of the full table, and whether the list is that of c.  Workloads
      whose name ends in "s" have the obstacles in engine.spatial_order; robot32x65536x4096 (4 096 configurations: a full table of 25.8 GB)
      runs s .. w alone.
+  x  hfcl_scene_nearest_env with the groups set, clearances only: g from the links' poses alone (host clock; against g and k)
+  y  hfcl_scene_nearest_env_device, clearances only (device events; against h and l)        z, 1  the same two through the fp32 path
+  2, 3, 4, 5  x, y, z, 1 with scene_nearest_env_prune=0: no environment tile dropped by its distance
+     x .. 5 report the pairs each pass evaluates, whether the clearances are those of g and -- from tests/nearest_env_model.py, with
+     the thresholds recomputed on the host -- the (16 rows, tile) cells each pass drops by distance.  robot32x65536x4096 runs them too.
 X .. b ignore the workload's pair list.  --options key=value,... sets library options in the worker (scene_pairs_small_max=0: the tiled form).
 The culled forms run at --inflate (default 0: the reference's manager).  planner2048: scene_planner(2048, 16), 215 040 queries;
 planner2048x32: scene_planner(2048, 32), 952 320 queries.  robot16x4096 / robot32x65536: workloads.scene_robot_env, 16 links and 4 096
-obstacles in 256 configurations / 32 links and 65 536 obstacles in 8; rows c .. r run on these alone, and c .. e only in a library that
-has object groups, g .. r only in one that has hfcl_scene_nearest_self.  They report, from tests/groups_model.py, the share of column tiles the sweep skips and of row blocks that leave at once.  L .. W report the share of the queries each pass of nearest evaluates.
+obstacles in 256 configurations / 32 links and 65 536 obstacles in 8; rows c .. 5 run on these alone, and c .. e only in a library that
+has object groups, g .. r only in one that has hfcl_scene_nearest_self, x .. 5 only in one that has hfcl_scene_nearest_env.  They report, from tests/groups_model.py, the share of column tiles the sweep skips and of row blocks that leave at once.  L .. W report the share of the queries each pass of nearest evaluates.
 Rows L .. W import the numpy model of the selection from tests/nearest_model.py: the lists of T .. W (the library keeps its own in its
 workspace) and the fp32 (lb - d_f32) / M come from it; no other row depends on tests/.
 
@@ -76,7 +81,8 @@ sys.path.insert(0, ROOT)
 ROBOTS = {"robot16x4096": (256, 16, 4096), "robot32x65536": (8, 32, 65536)}  # (configurations, links, obstacles)
 ROBOTS.update({k + "s": v for k, v in list(ROBOTS.items())})  # ... the obstacles in spatial order
 ENV_ONLY = {"robot32x65536x4096": (4096, 32, 65536), "robot32x65536x4096s": (4096, 32, 65536)}  # (no full table: the env forms alone)
-ENV_FORMS = "stuvw"
+ENV_FORMS = "stuvwxyz12345"
+NENV_FORMS = "xyz12345"
 
 
 def _workload(pkg, name):
@@ -85,9 +91,9 @@ def _workload(pkg, name):
         if "split" not in wl.scene_robot_env.__code__.co_varnames:  # (a parent build's package: the rows that exist there)
             sc, groups, pairs = wl.scene_robot_env(*ROBOTS[name])
             return sc.lib, sc.obj_shape, pairs, sc.obj_tf, groups, None
-        sc, groups, pairs, split, _ = wl.scene_robot_env(*(ROBOTS.get(name) or ENV_ONLY[name]), split=True, spatial=name.endswith("s"),
+        sc, groups, pairs, split, split32 = wl.scene_robot_env(*(ROBOTS.get(name) or ENV_ONLY[name]), split=True, spatial=name.endswith("s"),
                                                          full=name in ROBOTS)
-        return sc.lib, sc.obj_shape, pairs, sc.obj_tf, groups, split
+        return sc.lib, sc.obj_shape, pairs, sc.obj_tf, groups, split + split32
     if name == "cfg5":
         b = wl.cfg5_broadphase_scene()
         sc = b.scene
@@ -99,6 +105,32 @@ def _workload(pkg, name):
     else:
         ps = wl.scene_planner(n_conf=2048 if name == "planner2048" else 9984, n_objects=16)
     return ps.lib, ps.obj_shape, ps.pairs, ps.obj_tf, None, None
+
+
+def _dropped_cells(pkg, lib, obj_shape, groups, boxes, table, n_moving, f32):
+    """The (16 rows, environment tile) cells each pass of nearest_env drops by distance at upper_bound = inf, from the boxes: the seed and
+    pass 1 by the numpy model's bound, the thresholds from the per-pair distance call on pass 1's pairs."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import nearest_env_model as nem
+    import nearest_model
+    r = nearest_model.R32 if f32 else nearest_model.R64
+    n_conf, n = boxes.shape[:2]
+    cand = nem.candidates(n_moving, n, groups)
+    seed, thr = np.zeros(n_conf, dtype=np.uint64), np.zeros(n_conf)
+    dreq = pkg.abi.default_distance_request()
+    for c in range(n_conf):
+        L = nearest_model.bound(boxes[c, :n_moving, None, :], boxes[c, None, :, :], r)
+        first = int(np.where(cand, L, np.inf).argmin())
+        seed[c] = (first // n) << 32 | (first % n)
+        in1 = cand & np.isneginf(L)
+        in1[first // n, first % n] = True
+        i, j = np.nonzero(in1)
+        fn = lib.distance_f32 if f32 else lib.distance
+        rec = fn(obj_shape[i], obj_shape[j], np.ascontiguousarray(table[c, i]), np.ascontiguousarray(table[c, j]), dreq)
+        d = rec["distance"].astype(np.float64)
+        thr[c] = d[~np.isnan(d)].min() if len(d) else np.inf
+    drop1, drop2, _ = nem.dropped_cells({"seed": seed, "thr": thr}, boxes, n_moving, r)
+    return {"cells": int(drop1.size), "dropped_pass1": int(drop1.sum()), "dropped_pass2": int(drop2.sum())}
 
 
 def _stats(ms):
@@ -153,7 +185,7 @@ def worker(args):
     forms = args.forms.split(",")
     if args.workload in ENV_ONLY:  # (the table holds configuration 0 alone)
         forms = [f for f in forms if f in ENV_FORMS]
-    scene = lib.scene(obj_shape, pairs if args.workload not in ENV_ONLY else pairs[:0]) if set(forms) & set("BCEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvw") else None
+    scene = lib.scene(obj_shape, pairs if args.workload not in ENV_ONLY else pairs[:0]) if set(forms) & set("BCEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz12345") else None
     if "A" in forms or "D" in forms:
         t0 = time.perf_counter()
         s1, s2, tf1, tf2 = expand()
@@ -398,7 +430,7 @@ def worker(args):
             except pkg.EngineError as err:
                 info["k_refused_" + tag] = str(err)
     if set(forms) & set(ENV_FORMS) and split is not None and hasattr(scene, "set_environment"):  # a static environment kept on the device
-        moving_tf, env_tf = split
+        moving_tf, env_tf = split[:2]
         m_conf, n_links = moving_tf.shape[:2]
         dreq = abi.default_distance_request()
         scene.set_groups(*groups)
@@ -437,6 +469,35 @@ def worker(args):
             out["forms"]["v"] = device_clock(lambda: env_device(scene.collide_env_pairs_device, req))
         if "w" in forms:
             out["forms"]["w"] = device_clock(lambda: env_device(scene.distance_env_pairs_device, dreq))
+        if set(forms) & set(NENV_FORMS) and hasattr(scene, "nearest_env") and hasattr(pkg.engine.dll(), "hfcl_scene_nearest_env"):  # the clearance from the links' poses alone
+            ninfo = out["nearest_env"] = {"candidates": m_conf * P}
+            d_nclear = torch.zeros(m_conf * 6, dtype=torch.int32, device=dev)
+            for f32, letters in ((False, "xy23"), (True, "z145")):
+                if not set(forms) & set(letters):
+                    continue
+                tag = "f32" if f32 else "f64"
+                mov = split[2] if f32 else moving_tf
+                scene.set_environment(n_links, split[3] if f32 else env_tf)
+                d_m = torch.from_numpy(np.ascontiguousarray(mov)).to(dev)
+                fn_d = scene.nearest_env_device_f32 if f32 else scene.nearest_env_device
+                clear = {}
+                for prune, (host_letter, dev_letter) in ((1, letters[:2]), (0, letters[2:])):
+                    lib.set_option("scene_nearest_env_prune", prune)
+                    clear[prune], _, n_eval = scene.nearest_env(mov, dreq, records=False)
+                    ninfo["evaluated_" + tag] = list(n_eval)
+                    if host_letter in forms:
+                        out["forms"][host_letter] = host_clock(lambda: scene.nearest_env(mov, dreq, records=False))
+                    if dev_letter in forms:
+                        out["forms"][dev_letter] = device_clock(lambda: fn_d(d_m, m_conf, dreq, d_nclear, None, stream=st))
+                lib.set_option("scene_nearest_env_prune", 1)
+                ninfo["prune_off_equal_" + tag] = bool(clear[0].tobytes() == clear[1].tobytes())
+                if args.workload in ROBOTS:  # the same answer from the full table; the cells each pass drops
+                    tab = table
+                    if f32:
+                        tab = np.ascontiguousarray(np.concatenate([mov, np.broadcast_to(split[3][None], (m_conf,) + split[3].shape)], axis=1))
+                    want, _, n_want = scene.nearest_self(tab, dreq, records=False)
+                    ninfo["equal_to_nearest_self_" + tag] = bool(want.tobytes() == clear[1].tobytes() and tuple(n_want) == tuple(n_eval))
+                    ninfo["cells_" + tag] = _dropped_cells(pkg, lib, obj_shape, groups, scene.world_aabbs(tab), tab, n_links, f32)
         scene.clear_groups()
         scene.clear_environment()
     torch.cuda.synchronize()
@@ -512,7 +573,7 @@ def main():
         print("| form | build | median ms | min .. max ms (over the runs) |")
         print("|---|---|---|---|")
         for which in ("parent", "new", "control"):
-            for f in "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvw":
+            for f in "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz12345":
                 runs = [r["forms"][f] for r in rs if r["build"] == which and f in r["forms"]]
                 if runs:
                     print("| %s | %s | %s | %.3f .. %.3f |" % (f, which, " / ".join("%.3f" % x["median_ms"] for x in runs),
@@ -542,6 +603,9 @@ def main():
         es = [r["env"] for r in rs if "env" in r]
         if es:
             print("environment: " + json.dumps(es[-1]))
+        ne = [r["nearest_env"] for r in rs if "nearest_env" in r]
+        if ne:
+            print("clearance among the environment: " + json.dumps(ne[-1]))
         if "n_listed" in r0:
             print("cull at inflate %g: %d of %d queries survive (%.2f %%); byte model of the cull alone: %.0f bytes" % (
                 r0["inflate"], r0["n_listed"], r0["queries"], 100.0 * r0["n_listed"] / r0["queries"], r0["cull_model_bytes"]))

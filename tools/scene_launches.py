@@ -5,8 +5,10 @@ hfcl_scene_* once -- scene (host and device), boxes, cull, listed, culled, neare
 workloads.scene_planner(64, 16): 6720 queries, far below the size at which a chunk runs split.  scene_chunk and scene_cull_chunk are set
 so that every call runs in three chunks (the listed, culled and nearest forms: a third of their list, read from a call before).
 
-  python tools/scene_launches.py --out DIR        every output of every call as DIR/<nn>_<name>.npy: records, summaries, boxes, lists,
-      conf_begin, counts, min records, n_evaluated, and last_bucket_counts() after every host form
+  python tools/scene_launches.py --out DIR [--nearest-env]       every output of every call as DIR/<nn>_<name>.npy: records, summaries, boxes, lists,
+      conf_begin, counts, min records, n_evaluated, and last_bucket_counts() after every host form.  --nearest-env adds, behind all of
+      these, the clearance among a kept environment (hfcl_scene_set_environment* with the first 6 bodies moving, hfcl_scene_nearest_env*
+      host and device, moving rows in three chunks and spans of one tile): a run without it is what a build without those calls runs
   rocprofv3 --kernel-trace --output-format csv -d TRACE -- python tools/scene_launches.py --out DIR      (one fresh process per build)
   python tools/scene_launches.py --compare DIR_A TRACE_A DIR_B TRACE_B
       the .npy files byte for byte, and the kernel traces: per queue, in dispatch order, (kernel name, grid size, workgroup size)"""
@@ -22,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def run(out_dir):
+def run(out_dir, nearest_env=False):
     import torch
     import __graft_entry__ as ge
     pkg = ge.load_pkg()
@@ -121,6 +123,26 @@ def run(out_dir):
         for kind, req in (("collide", creq), ("distance", dreq)):
             dump(p + kind + "_self", *getattr(scene, kind + "_self")(tab, req, 0.25), host=True)
         lib.set_option("scene_cull_chunk", -(-total // 3))
+    if nearest_env:  # behind every call a build without it has: the clearance among a kept environment
+        K = 6
+        lib.set_option("scene_cull_chunk", -(-n_conf * K // 3))
+        lib.set_option("scene_env_span", 1)
+        for f32 in (False, True):
+            p = "f32_" if f32 else "f64_"
+            tab = pose if f32 else table
+            words = 11 if f32 else 24
+            moving = np.ascontiguousarray(tab[:, :K])
+            scene.set_environment(K, np.ascontiguousarray(tab[0, K:]))
+            boxes, tiles = scene.environment_aabbs()
+            dump(p + "environment", boxes, tiles)
+            _, _, n_eval = scene.nearest_env(moving, dreq)
+            thirds(max(max(n_eval), 1))
+            clear, rec, n_eval = scene.nearest_env(moving, dreq)
+            dump(p + "nearest_env", clear, rec, np.array(n_eval, dtype=np.int64), host=True)
+            d_clear, d_min = d_zeros(n_conf * 6), d_zeros(n_conf * words)
+            n_eval = (scene.nearest_env_device_f32 if f32 else scene.nearest_env_device)(torch.from_numpy(moving).to(dev), n_conf, dreq, d_clear, d_min, stream=st)
+            dump(p + "nearest_env_device", d_clear, d_min, np.array(n_eval, dtype=np.int64))
+        scene.clear_environment()
     torch.cuda.synchronize()
     scene.close()
     lib.close()
@@ -168,11 +190,12 @@ def compare(dir_a, trace_a, dir_b, trace_b):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--nearest-env", action="store_true", help="add the hfcl_scene_nearest_env* calls behind the others")
     ap.add_argument("--compare", nargs=4, metavar=("DIR_A", "TRACE_A", "DIR_B", "TRACE_B"))
     a = ap.parse_args()
     if a.compare:
         compare(*a.compare)
     elif a.out:
-        run(a.out)
+        run(a.out, a.nearest_env)
     else:
         ap.error("--out DIR or --compare ...")
