@@ -90,6 +90,14 @@ BVH_NODE_DTYPE = np.dtype([("first_child", "<i4"), ("first_primitive", "<i4"), (
 assert BVH_NODE_DTYPE.itemsize == C.sizeof(BvhNode) == 256
 
 
+# hfcl_hfield_node = HFNode<AABB> (include/hppfcl_amd_hfield.h)
+HFIELD_NODE_DTYPE = np.dtype([("first_child", "<u4"), ("x_id", "<i4"), ("x_size", "<i4"), ("y_id", "<i4"), ("y_size", "<i4"),
+                              ("contact_active_faces", "<i4"), ("max_height", "<f8"), ("aabb_min", "<f8", 3), ("aabb_max", "<f8", 3)])
+assert HFIELD_NODE_DTYPE.itemsize == 80
+HF_GEOM_AABB, HF_GEOM_OBBRSS = 20, 21  # NODE_TYPE HF_AABB / HF_OBBRSS (collision_object.h:65-89)
+STATUS_SWAPPED = 1 << 23
+
+
 class PatchRequest(C.Structure):
     """hfcl_patch_request = ContactPatchRequest (collision_data.h:726-823)."""
     _fields_ = [("max_num_patch", C.c_uint32), ("num_samples_curved_shapes", C.c_uint32), ("patch_tolerance", C.c_double)]

@@ -17,6 +17,7 @@ class NODE_TYPE:  # include/hpp/fcl/collision_object.h:65-89
     GEOM_BOX, GEOM_SPHERE, GEOM_CAPSULE, GEOM_CONE = abi.GEOM_BOX, abi.GEOM_SPHERE, abi.GEOM_CAPSULE, abi.GEOM_CONE
     GEOM_CYLINDER, GEOM_CONVEX, GEOM_PLANE = abi.GEOM_CYLINDER, abi.GEOM_CONVEX, abi.GEOM_PLANE
     GEOM_HALFSPACE, GEOM_TRIANGLE, GEOM_ELLIPSOID = abi.GEOM_HALFSPACE, abi.GEOM_TRIANGLE, abi.GEOM_ELLIPSOID
+    HF_AABB, HF_OBBRSS = abi.HF_GEOM_AABB, abi.HF_GEOM_OBBRSS
 
 
 class GJKInitialGuess:
@@ -285,6 +286,66 @@ class BVHModelOBBRSS(CollisionGeometry):  # BVHModel<OBBRSS>, src/BVH/BVH_model.
         return len(self._t)
 
 
+class HeightFieldAABB(CollisionGeometry):  # HeightField<AABB>, include/hpp/fcl/hfield.h:202-520
+    """heights: (ny, nx), row 0 = the north edge (+y_dim/2).  The tree is built by the library's host builder (hfcl_hfield_build);
+    collide() against a convex solid, in either operand order, goes to hfcl_hfield_collide_batch."""
+    _node_type = NODE_TYPE.HF_AABB
+
+    def __init__(self, x_dim, y_dim, heights, min_height=0.0):
+        self._x_dim, self._y_dim, self._min = float(x_dim), float(y_dim), float(min_height)
+        self._version = 0
+        self.aabb_local = None
+        self._set(np.array(heights, dtype=np.float64))
+
+    def _set(self, heights):
+        if heights.ndim != 2:
+            raise ValueError("heights: a (ny, nx) matrix")
+        try:
+            self._nodes, self._xg, self._yg = engine.hfield_build(self._x_dim, self._y_dim, heights, self._min)
+        except engine.EngineError as e:
+            raise ValueError(str(e))
+        self._heights = np.maximum(heights, self._min)
+        self._max = float(self._nodes[0]["max_height"])
+        self._version += 1  # (the next collide() registers the field again)
+
+    def getXDim(self):
+        return self._x_dim
+
+    def getYDim(self):
+        return self._y_dim
+
+    def getXGrid(self):
+        return self._xg
+
+    def getYGrid(self):
+        return self._yg
+
+    def getHeights(self):
+        return self._heights
+
+    def getMinHeight(self):
+        return self._min
+
+    def getMaxHeight(self):
+        return self._max
+
+    def getNodes(self):
+        return self._nodes
+
+    def computeLocalAABB(self):  # hfield.h:278-287
+        a = np.array([self._xg[0], self._yg[0], self._min])
+        b = np.array([self._xg[-1], self._yg[-1], self._max])
+        self.aabb_local = np.concatenate([np.minimum(a, b), np.maximum(a, b)])
+        self.aabb_radius = float(np.sqrt(((a - b) ** 2).sum())) / 2.0
+        self.aabb_center = (self.aabb_local[:3] + self.aabb_local[3:]) * 0.5
+
+    def updateHeights(self, new_heights):  # hfield.h:290-305: same size; the tree is rebuilt and uploaded again by the next call
+        h = np.array(new_heights, dtype=np.float64)
+        if h.shape != self._heights.shape:
+            raise ValueError("The matrix containing the new heights values does not have the same matrix size as the original one.")
+        self._set(h)
+
+
 class _Query:
     def __init__(self):
         self.gjk_initial_guess = GJKInitialGuess.DefaultGuess
@@ -429,6 +490,7 @@ class _Context:
         self.device, self.L, self.lib = device, geometry.ShapeLibrary(), None
         self.ids, self.keep, self.meshes = {}, [], []
         self.built = 0
+        self.hfields, self.hfield_ids = [], {}  # registered (field, heights, ...) in index order; (id(field), version) -> index
 
     @staticmethod
     def _signature(g):
@@ -458,7 +520,28 @@ class _Context:
         self.keep.append(g)  # ids stay valid while the context lives
         return sid
 
+    HFIELDS_MAX = 16  # registered (field, version) entries the context keeps before it clears them and the library's tables
+
+    def add_hfield(self, g):
+        """the index of a HeightFieldAABB on the library (a field whose heights were updated is registered again; at most HFIELDS_MAX
+        registrations are kept, so a caller that updates heights every step does not grow host or device memory)"""
+        key = (id(g), g._version)
+        if key not in self.hfield_ids:
+            if len(self.hfields) >= self.HFIELDS_MAX:  # versions of updated fields, fields that came and went: start over, here and on the library
+                self.hfields, self.hfield_ids = [], {}
+                if self.lib is not None:
+                    self.lib.clear_hfields()
+            self.hfield_ids[key] = len(self.hfields)
+            self.hfields.append((g, g._x_dim, g._y_dim, g._heights.copy(), g._min))  # (g is kept: its id stays its own while it is listed)
+        return self.hfield_ids[key]
+
     def library(self):
+        lib = self._library()
+        for _, x_dim, y_dim, h, mh in self.hfields[lib.hfield_count():]:  # (all of them on a library that was just rebuilt)
+            lib.add_hfield(x_dim, y_dim, h, mh)
+        return lib
+
+    def _library(self):
         if self.lib is None or self.built != len(self.L):
             if self.lib is not None:
                 self.lib.close()
@@ -488,6 +571,11 @@ def _context():
 
 
 def _check_pair(o1, o2, for_distance):
+    h1, h2 = isinstance(o1, HeightFieldAABB), isinstance(o2, HeightFieldAABB)
+    if (h1 or h2) and not for_distance:
+        if h1 != h2 and engine.hfield_pair_supported(int((o2 if h1 else o1).getNodeType())):
+            return
+        raise ValueError("Collision function between node type %d and node type %d is not yet supported." % (o1.getNodeType(), o2.getNodeType()))
     if not engine.dll().hfcl_pair_supported(int(o1.getNodeType()), int(o2.getNodeType()), int(for_distance)):
         raise ValueError("%s function between node type %d and node type %d is not yet supported." %
                          ("Distance" if for_distance else "Collision", o1.getNodeType(), o2.getNodeType()))
@@ -540,6 +628,34 @@ def _fill_collision(result, o1, o2, request, rec, guess, contacts, pair_index=0)
         request.updateGuess(result)
 
 
+def _collide_hfield(o1, tf1, o2, tf2, request, result):
+    """(HeightFieldAABB, solid) or (solid, HeightFieldAABB) through hfcl_hfield_collide_batch.  The result gets every contact and the
+    call's distance_lower_bound; its nearest_points / normal are the record's: the first contact's when there is one."""
+    swapped = not isinstance(o1, HeightFieldAABB)
+    field, tfh, solid, tfs = (o2, tf2, o1, tf1) if swapped else (o1, tf1, o2, tf2)
+    ctx = _context()
+    sid, hid = ctx.add(solid), ctx.add_hfield(field)
+    lib = ctx.library()
+    cap = int(min(request.num_max_contacts, 1 << 16))
+    try:
+        rec, dlb, contacts, _ = lib.hfield_collide([hid], [sid], tfh._abi().reshape(1, 12), tfs._abi().reshape(1, 12), request._abi(),
+                                                   swapped=[1 if swapped else 0], max_contacts=cap)
+    except engine.EngineError as e:
+        if e.code in (abi.ERR_INVALID_ARGUMENT, abi.ERR_UNSUPPORTED_PAIR, abi.ERR_LIMIT):
+            raise ValueError(str(e))
+        raise
+    if abi.status_skipped(rec[0]["status"]):
+        return result.numContacts()
+    if dlb[0] < result.distance_lower_bound:
+        result.distance_lower_bound = float(dlb[0])
+        result.normal = np.array(rec[0]["normal"])
+        result.nearest_points = [np.array(rec[0]["p1"]), np.array(rec[0]["p2"])]
+    for c in contacts:
+        if result.numContacts() < request.num_max_contacts:
+            result.addContact(Contact(o1, o2, c["b1"], c["b2"], c["p1"], c["p2"], c["normal"], c["penetration_depth"]))
+    return result.numContacts()
+
+
 def collide(*args):
     """collide(o1, tf1, o2, tf2, request, result) or collide(obj1, obj2, request, result)  (python/collision.cc:257-266)"""
     if len(args) == 4:
@@ -555,6 +671,8 @@ def collide(*args):
     _check_pair(o1, o2, False)
     if result.isCollision() and request.num_max_contacts <= result.numContacts():
         return result.numContacts()
+    if isinstance(o1, HeightFieldAABB) or isinstance(o2, HeightFieldAABB):
+        return _collide_hfield(o1, tf1, o2, tf2, request, result)
     rec, g, contacts = _run("collide", [(o1, tf1, o2, tf2)], request)
     _fill_collision(result, o1, o2, request, rec[0], g[0] if g is not None else None, contacts)
     return result.numContacts()

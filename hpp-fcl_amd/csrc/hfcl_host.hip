@@ -71,6 +71,8 @@ int hfcl_abi_version(void) { return HFCL_ABI_VERSION; }
 int hfcl_has_ab_forms(void) { return HFCL_KEEP_AB_FORMS ? 1 : 0; }
 int hfcl_pair_supported(int32_t t1, int32_t t2, int for_distance) {
   if (t1 < 0 || t1 > 255 || t2 < 0 || t2 > 255) return 0;
+  // 21 is NODE_TYPE HF_OBBRSS to a caller (no row here: height fields have hfcl_hfield_pair_supported); inside, the kernels' class of large hulls
+  if (t1 == K_CONVEX_LARGE || t2 == K_CONVEX_LARGE) return 0;
   return bucket_of(t1, t2, for_distance != 0) != B_UNSUPPORTED;
 }
 int hfcl_device_count(void) {
@@ -248,7 +250,7 @@ static const char* const* option_keys() {
       "bvh_walk_rounds", "bvh_walk_order", "mesh_beside", "mesh_prio", "shape_walk", "shape_walk_sort", "shape_walk_budget", "shape_walk_min", "gjk_beside_max", "epa_direct_max", "bvh_walk_k", "bvh_walk_budget", "shape_dist_leaf_min", "shape_dist_starve", "bvhd_leaf_min", "bvhd_starve",
       "bvhd_part_min", "shape_dist_budget", "bvh_budget0_coop", "shape_budget0", "shape_budget", "shape_leaf_cost", "shape_levels",
       "climb_min", "bvh_budget", "bvh_budget0", "bvh_levels", "cvx_w", "epa_resume_slots", "bvh_task_slots", "bvh_force_wide",
-      "pipe_trace", "scene_chunk", "scene_cull_chunk", "scene_pairs_small_max", "scene_env_span", "scene_nearest_env_prune", "epa_pool_share", "epa_pool_min_refills", nullptr};
+      "pipe_trace", "scene_chunk", "scene_cull_chunk", "scene_pairs_small_max", "scene_env_span", "scene_nearest_env_prune", "epa_pool_share", "epa_pool_min_refills", "hfield_chunk", "hfield_items", nullptr};
   return keys;
 }
 // "4,16,16": up to `cap` comma-separated unsigned values into out[first...]; returns how many were read
@@ -351,6 +353,14 @@ static int apply_option(hfcl_lib* lib, const std::string& key, const char* v) {
     lib->opt.scene_env_span = uint32_t(i);
   }
   else if (key == "scene_nearest_env_prune") lib->opt.scene_nearest_env_prune = on;
+  else if (key == "hfield_chunk") {
+    if (i < 0 || i > 0xFFFFFFF0ll) return HFCL_ERR_INVALID_ARGUMENT;
+    lib->opt.hfield_chunk = size_t(i);
+  }
+  else if (key == "hfield_items") {
+    if (i < 0 || i > (1ll << 26)) return HFCL_ERR_INVALID_ARGUMENT;  // (the item workspace of one query's limit)
+    lib->opt.hfield_items = size_t(i);
+  }
   else return HFCL_ERR_INVALID_ARGUMENT;
   return HFCL_OK;
 }

@@ -21,6 +21,7 @@
 #include "hfcl_scene.hpp"
 #include "hfcl_cull.hpp"
 #include "hfcl_pairs.hpp"
+#include "hfcl_hfield.hpp"
 #include "hfcl_own.hpp"
 
 __attribute__((visibility("hidden"))) void set_error(const std::string& s);  // the calling thread's hfcl_last_error()
@@ -134,6 +135,10 @@ struct hfcl_options {
   // 1.07 M queries in chunks of 262144 (the host pipeline's steady chunk) took 5.9 ms against 2.4 ms for the per-pair call on resident arrays,
   // 9.0 ms of kernel time against 5.5 (profiles/r08_a_scene.md).  2^21 queries are 0.8 GB of workspace, allocated only by calls that large.
   size_t scene_chunk = 0;
+  // Queries per chunk of hfcl_hfield_collide_batch* (option hfield_chunk; 0: automatic -- 65536): bounds the per-query workspace; a chunk that
+  // lists more than 2^20 (query, leaf) items is cut down further.  The records do not depend on it
+  size_t hfield_chunk = 0;
+  size_t hfield_items = 0;  // option hfield_items: the items a chunk may list before it is cut down (0: automatic -- 2^20); a chunk of one query is never cut
   int cvx_w = 0;  // 0 = per kernel (auto_cvx_w); HFCL_CVX_W forces one width for all
   bool closed_staged = true;  // HFCL_CLOSED_STAGED=0: A/B switch back to the direct-access k_closed<double>
   bool bvh_filter = false;     // HFCL_BVH_FILTER=1: the fp32 filter form of k_bvh_collide (exact, measured slower: profiles/r03_b)
@@ -333,6 +338,30 @@ struct hfcl_lib {
     DevBuf<void> d_ns_rec[2];
     DevBuf<hfcl_scene_clearance> d_ns_out;
   } scene;
+  // height fields (hfcl_lib_add_hfield; hfcl_host_hfield.hip): the host tables of every registered field one after the other, their device
+  // images (uploaded by the next call when a field was added since), the workspace of a chunk of queries and its items, the host
+  // form's stream and staging, and the call's contact list
+  struct Hfields {
+    std::vector<DHfield> h_fields;
+    std::vector<hfcl_hfield_node> h_nodes;
+    std::vector<double> h_heights, h_xgrid, h_ygrid;
+    bool dirty = false;
+    DevBuf<DHfield> d_fields;
+    DevBuf<hfcl_hfield_node> d_nodes;
+    DevBuf<double> d_heights, d_xgrid, d_ygrid;
+    DevBuf<uint32_t> d_counts, d_ccounts;
+    DevBuf<uint64_t> d_offsets, d_coffsets, d_running;
+    DevBuf<double> d_box_total;
+    DevBuf<HfItem<double>> d_items;
+    DevBuf<HfLeafOut<double>> d_leaves;
+    PinnedBuf<uint64_t> h_words;  // pinned: [0] a chunk's item count, [1] the call's contact count
+    Stream st;
+    DevBuf<uint32_t> s_hfield, s_shape;
+    DevBuf<double> s_tfh, s_tfs, s_dlb;
+    DevBuf<uint8_t> s_swapped;
+    DevBuf<hfcl_result> s_out;
+    DevBuf<hfcl_contact> s_contacts;
+  } hf;
   // local AABB of every library shape (hfcl_cull.hpp: shape_local_box; BVH models: the box of their vertices), 6 doubles each, rebuilt when
   // shapes or meshes were registered since (hfcl_lib_set_shapes, hfcl_lib_add_bvh)
   DevBuf<double> d_local_boxes;

@@ -73,6 +73,11 @@ ENV_SYMBOLS = [
 NEAREST_ENV_SYMBOLS = [
     "hfcl_scene_nearest_env", "hfcl_scene_nearest_env_f32", "hfcl_scene_nearest_env_device", "hfcl_scene_nearest_env_device_f32",
 ]
+# include/hppfcl_amd_hfield.h (included by hppfcl_amd.h): HeightField<AABB> against convex solids
+HFIELD_SYMBOLS = [
+    "hfcl_hfield_build", "hfcl_lib_add_hfield", "hfcl_lib_hfield_count", "hfcl_lib_clear_hfields", "hfcl_hfield_local_aabb", "hfcl_hfield_pair_supported",
+    "hfcl_hfield_collide_batch", "hfcl_hfield_collide_batch_device",
+]
 
 
 class EngineError(RuntimeError):
@@ -128,6 +133,8 @@ def dll():
             d.hfcl_scene_num_groups.restype = C.c_size_t
         if hasattr(d, "hfcl_scene_n_moving"):
             d.hfcl_scene_n_moving.restype = C.c_size_t
+        if hasattr(d, "hfcl_lib_hfield_count"):
+            d.hfcl_lib_hfield_count.restype = C.c_size_t
         _DLL = d
     return _DLL
 
@@ -159,6 +166,28 @@ def contact_patch_max_points_shapes(shapes, req=None):
     _check(dll().hfcl_contact_patch_max_points_shapes(abi.ptr(shapes), C.c_size_t(len(shapes)),
                                                       C.byref(req or abi.default_patch_request()), C.byref(cap)))
     return int(cap.value)
+
+
+def hfield_pair_supported(node_type):
+    """hfcl_hfield_pair_supported: does collide() have a height-field row for a solid of this node type?"""
+    return bool(dll().hfcl_hfield_pair_supported(C.c_int32(int(node_type))))
+
+
+def hfield_build(x_dim, y_dim, heights, min_height=0.0):
+    """hfcl_hfield_build: (nodes[HFIELD_NODE_DTYPE], x_grid, y_grid) of HeightField<AABB>(x_dim, y_dim, heights, min_height) (host, no
+    GPU needed).  heights: (ny, nx), row 0 = the north edge."""
+    h = np.ascontiguousarray(heights, dtype=np.float64)
+    if h.ndim != 2:
+        raise ValueError("heights: a (ny, nx) matrix")
+    ny, nx = h.shape
+    n = C.c_size_t(0)
+    _check(dll().hfcl_hfield_build(C.c_double(x_dim), C.c_double(y_dim), abi.ptr(h), C.c_size_t(ny), C.c_size_t(nx), C.c_double(min_height),
+                                   None, C.byref(n), None, None))
+    nodes = np.zeros(n.value, dtype=abi.HFIELD_NODE_DTYPE)
+    xg, yg = np.zeros(nx), np.zeros(ny)
+    _check(dll().hfcl_hfield_build(C.c_double(x_dim), C.c_double(y_dim), abi.ptr(h), C.c_size_t(ny), C.c_size_t(nx), C.c_double(min_height),
+                                   abi.ptr(nodes), C.byref(n), abi.ptr(xg), abi.ptr(yg)))
+    return nodes, xg, yg
 
 
 def has_ab_forms():
@@ -320,6 +349,66 @@ class Library:
         if idx < 0:
             raise EngineError(abi.ERR_INVALID_ARGUMENT, last_error())
         return idx
+
+    # ---- height fields (hfcl_lib_add_hfield, hfcl_hfield_collide_batch*) ----
+    def add_hfield(self, x_dim, y_dim, heights, min_height=0.0):
+        """Register a HeightField<AABB>; heights: (ny, nx), row 0 = the north edge.  Returns its index on this library."""
+        h = np.ascontiguousarray(heights, dtype=np.float64)
+        if h.ndim != 2:
+            raise ValueError("heights: a (ny, nx) matrix")
+        idx = dll().hfcl_lib_add_hfield(self._h, C.c_double(x_dim), C.c_double(y_dim), abi.ptr(h), C.c_size_t(h.shape[0]),
+                                        C.c_size_t(h.shape[1]), C.c_double(min_height))
+        if idx < 0:
+            raise EngineError(abi.ERR_INVALID_ARGUMENT, last_error())
+        return idx
+
+    def hfield_count(self):
+        return int(dll().hfcl_lib_hfield_count(self._h))
+
+    def clear_hfields(self):
+        """Forget every registered height field (indices start at 0 again): hfcl_lib_clear_hfields."""
+        _check(dll().hfcl_lib_clear_hfields(self._h))
+
+    def hfield_local_aabb(self, hfield):
+        """computeLocalAABB of a registered height field: (min xyz, max xyz)."""
+        out = np.zeros(6)
+        _check(dll().hfcl_hfield_local_aabb(self._h, C.c_int(int(hfield)), abi.ptr(out)))
+        return out
+
+    def hfield_collide(self, hfield, shape, tf_hfield, tf_shape, req=None, swapped=None, max_contacts=0, want_bound=True):
+        """Batched collide(HeightField<AABB>, solid) -- swapped[i] = 1: collide(solid, HeightField) -- from host arrays.  Returns
+        (records, distance_lower_bound or None, contacts[CONTACT_DTYPE], n_produced)."""
+        req = req or abi.default_collision_request()
+        hfield = np.ascontiguousarray(hfield, dtype=np.uint32)
+        shape = np.ascontiguousarray(shape, dtype=np.uint32)
+        tfh = np.ascontiguousarray(tf_hfield, dtype=np.float64).reshape(-1, 12)
+        tfs = np.ascontiguousarray(tf_shape, dtype=np.float64).reshape(-1, 12)
+        n = len(hfield)
+        if not (len(shape) == len(tfh) == len(tfs) == n):
+            raise ValueError("batch arrays must have equal length")
+        if swapped is not None:
+            swapped = np.ascontiguousarray(swapped, dtype=np.uint8)
+            if len(swapped) != n:
+                raise ValueError("swapped: one byte per query")
+        out = np.zeros(n, dtype=abi.RESULT_DTYPE)
+        dlb = np.zeros(n) if want_bound else None
+        contacts = np.zeros(int(max_contacts), dtype=abi.CONTACT_DTYPE)
+        nc = C.c_size_t(0)
+        _check(dll().hfcl_hfield_collide_batch(self._h, abi.ptr(hfield), abi.ptr(shape), abi.ptr(tfh), abi.ptr(tfs), C.c_size_t(n),
+                                               abi.ptr(swapped), C.byref(req), abi.ptr(out), abi.ptr(dlb),
+                                               abi.ptr(contacts) if max_contacts else None, C.c_size_t(int(max_contacts)), C.byref(nc)))
+        return out, dlb, contacts[:min(nc.value, int(max_contacts))], int(nc.value)
+
+    def hfield_collide_device(self, d_hfield, d_shape, d_tf_hfield, d_tf_shape, n, req, d_out, d_swapped=None, d_bound=None, d_contacts=None,
+                              max_contacts=0, want_count=False, stream=0):
+        """The same call on device pointers (torch tensors or raw pointers).  Returns the number of contacts produced when want_count
+        (the call then waits for the stream), else None."""
+        nc = C.c_size_t(0)
+        _check(dll().hfcl_hfield_collide_batch_device(self._h, _dptr(d_hfield), _dptr(d_shape), _dptr(d_tf_hfield), _dptr(d_tf_shape),
+                                                      C.c_size_t(n), _dptr(d_swapped), C.byref(req), _dptr(d_out), _dptr(d_bound),
+                                                      _dptr(d_contacts), C.c_size_t(int(max_contacts)), C.byref(nc) if want_count else None,
+                                                      C.c_void_p(stream)))
+        return int(nc.value) if want_count else None
 
     def collide_contacts(self, s1, s2, tf1, tf2, req, max_contacts):
         """Batched collide() returning (records, contacts[CONTACT_DTYPE], n_produced)."""

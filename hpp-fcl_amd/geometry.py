@@ -111,6 +111,15 @@ class ShapeLibrary:
     def __len__(self):
         return self._count
 
+    def copy(self):
+        """A library with the same shapes and vertices (same ids), to which more can be added."""
+        c = ShapeLibrary()
+        if self._count:
+            c._chunks, c._count = [self.shapes_array().copy()], self._count
+        if self._nverts:
+            c._verts, c._nverts = [self.vertices_array().copy()], self._nverts
+        return c
+
     def shapes_array(self):
         self._flush()
         if not self._chunks:

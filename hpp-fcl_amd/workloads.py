@@ -619,6 +619,82 @@ def cfg4_mesh_mesh_distance(n=100_000, seed=1, n_variants=8, seg=50, ring=50, ha
     return b
 
 
+class HfieldTerrain:
+    """A height field and queries of solids against it (hfield_terrain): the field (x_dim, y_dim, heights (ny, nx), min_height), the
+    solids' ShapeLibrary, per query the solid's id, the two poses and the operand order."""
+
+    def __init__(self, x_dim, y_dim, heights, min_height, lib, shape, tf_hfield, tf_shape, swapped):
+        self.x_dim, self.y_dim, self.heights, self.min_height, self.lib = x_dim, y_dim, heights, min_height, lib
+        self.shape, self.tf_hfield, self.tf_shape, self.swapped = shape, tf_hfield, tf_shape, swapped
+        self.hfield = np.zeros(len(shape), dtype=np.uint32)
+
+    def __len__(self):
+        return len(self.shape)
+
+    def triangulation(self):
+        """(vertices, triangles) of the field's top surface, the two triangles of a cell cut along the prisms' diagonal: what a caller
+        without height fields hands to BVHModel<OBBRSS>.  A surface, not the solid down to min_height: it answers another question."""
+        ny, nx = self.heights.shape
+        xg = np.linspace(-0.5 * self.x_dim, 0.5 * self.x_dim, nx)
+        yg = np.linspace(0.5 * self.y_dim, -0.5 * self.y_dim, ny)
+        X, Y = np.meshgrid(xg, yg)
+        verts = np.stack([X.ravel(), Y.ravel(), np.maximum(self.heights, self.min_height).ravel()], axis=1)
+        r, c = np.meshgrid(np.arange(ny - 1), np.arange(nx - 1), indexing="ij")
+        v00, v01, v10, v11 = (r * nx + c).ravel(), (r * nx + c + 1).ravel(), ((r + 1) * nx + c).ravel(), ((r + 1) * nx + c + 1).ravel()
+        tris = np.concatenate([np.stack([v00, v10, v01], axis=1), np.stack([v10, v11, v01], axis=1)]).astype(np.uint32)
+        return verts, tris
+
+
+def hfield_terrain(n_queries=100_000, nx=256, ny=256, seed=1, cell=0.25, nper=16):
+    """A smooth random terrain of nx x ny samples, `cell` apart (a sum of a few sine products, heights around 1.3 +- 0.6 over
+    min_height = 0), and n_queries solids of the seven kinds a height field collides with, 0.2 to 0.6 across, resting near the
+    surface under random rotations: about half of them in contact.  Both operand orders; the field at the identity."""
+    rng = _rng(seed, 131)
+    x_dim, y_dim = cell * (nx - 1), cell * (ny - 1)
+    xg = np.linspace(-0.5 * x_dim, 0.5 * x_dim, nx)
+    yg = np.linspace(0.5 * y_dim, -0.5 * y_dim, ny)
+    X, Y = np.meshgrid(xg, yg)
+    h = np.full((ny, nx), 1.3)
+    for _ in range(6):
+        lx, ly = rng.uniform(3.0, 12.0, 2)
+        h += rng.uniform(0.08, 0.22) * np.sin(2 * np.pi * X / lx + rng.uniform(0, 6.3)) * np.sin(2 * np.pi * Y / ly + rng.uniform(0, 6.3))
+    lib = geometry.ShapeLibrary()
+    reach = []  # a radius that bounds the solid
+    for _ in range(nper):
+        s = rng.uniform(0.2, 0.6, 3)
+        lib.add_box(*map(float, s))
+        reach.append(0.5 * float(np.linalg.norm(s)))
+    for r in rng.uniform(0.1, 0.3, nper):
+        lib.add_sphere(float(r))
+        reach.append(float(r))
+    for r, lz in zip(rng.uniform(0.08, 0.2, nper), rng.uniform(0.1, 0.4, nper)):
+        lib.add_capsule(float(r), float(lz))
+        reach.append(float(r + lz / 2))
+    for r, lz in zip(rng.uniform(0.1, 0.3, nper), rng.uniform(0.2, 0.6, nper)):
+        lib.add_cone(float(r), float(lz))
+        reach.append(float(np.hypot(r, lz / 2)))
+    for r, lz in zip(rng.uniform(0.1, 0.3, nper), rng.uniform(0.2, 0.6, nper)):
+        lib.add_cylinder(float(r), float(lz))
+        reach.append(float(np.hypot(r, lz / 2)))
+    for r in rng.uniform(0.1, 0.3, (nper, 3)):
+        lib.add_ellipsoid(*map(float, r))
+        reach.append(float(r.max()))
+    base = fibonacci_sphere(24)
+    for r in rng.uniform(0.1, 0.3, (nper, 3)):
+        lib.add_convex(base * r)
+        reach.append(float(r.max()))
+    reach = np.array(reach)
+    shape = rng.integers(0, len(lib), n_queries).astype(np.uint32)
+    u, v = rng.uniform(0.01, 0.99, n_queries), rng.uniform(0.01, 0.99, n_queries)
+    ci, ri = np.minimum((u * (nx - 1)).astype(int), nx - 2), np.minimum((v * (ny - 1)).astype(int), ny - 2)
+    ground = np.maximum.reduce([h[ri, ci], h[ri + 1, ci], h[ri, ci + 1], h[ri + 1, ci + 1]])
+    T = np.stack([(u - 0.5) * x_dim, (0.5 - v) * y_dim, ground + reach[shape] * rng.uniform(0.0, 1.2, n_queries)], axis=1)
+    tf_shape = geometry.make_pose(quat=uniform_quaternions(rng, n_queries), T=T)
+    tf_hfield = np.repeat(geometry.make_pose().reshape(1, 12), n_queries, axis=0)
+    swapped = (rng.random(n_queries) < 0.5).astype(np.uint8)
+    return HfieldTerrain(x_dim, y_dim, h, 0.0, lib, shape, tf_hfield, tf_shape, swapped)
+
+
 def make_library(pkg, batch, device=0, options=None):
     """engine.Library for a batch (registers the batch's meshes, if any); options: {key: value} for hfcl_lib_set_option."""
     lib = pkg.Library(batch.lib, device=device, options=options)

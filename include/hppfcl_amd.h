@@ -671,6 +671,8 @@ int hfcl_scene_distance_device_f32(hfcl_scene* s, const float* d_object_pose, si
 #include "./hppfcl_amd_env.h"
 /* the clearance of the moving objects among such an environment per configuration: the pairs made and pruned on the device */
 #include "hppfcl_amd_nearest_env.h"
+/* HeightField<AABB> against convex solids: the builder, the registration and the batched collide() */
+#include "./hppfcl_amd_hfield.h"
 /* the self-collision pairs of a scene per configuration, made on the device, and the scene calls on such a list */
 #include "hppfcl_amd_pairs.h"
 #endif /* HPPFCL_AMD_H */

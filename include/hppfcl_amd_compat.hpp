@@ -26,6 +26,7 @@
 #include <string>
 #include <utility>
 #include <typeinfo>
+#include <type_traits>
 #include <vector>
 
 #include <algorithm>
@@ -118,7 +119,8 @@ enum NODE_TYPE {  // include/hpp/fcl/collision_object.h:65-89 (subset in scope)
   BV_OBBRSS = HFCL_BV_OBBRSS, GEOM_BOX = HFCL_GEOM_BOX, GEOM_SPHERE = HFCL_GEOM_SPHERE, GEOM_CAPSULE = HFCL_GEOM_CAPSULE,
   GEOM_CONE = HFCL_GEOM_CONE, GEOM_CYLINDER = HFCL_GEOM_CYLINDER, GEOM_PLANE = HFCL_GEOM_PLANE,
   GEOM_HALFSPACE = HFCL_GEOM_HALFSPACE,
-  GEOM_CONVEX = HFCL_GEOM_CONVEX, GEOM_TRIANGLE = HFCL_GEOM_TRIANGLE, GEOM_ELLIPSOID = HFCL_GEOM_ELLIPSOID
+  GEOM_CONVEX = HFCL_GEOM_CONVEX, GEOM_TRIANGLE = HFCL_GEOM_TRIANGLE, GEOM_ELLIPSOID = HFCL_GEOM_ELLIPSOID,
+  HF_AABB = 20, HF_OBBRSS = 21  // height fields: HF_AABB has collide() against the convex solids (hppfcl_amd_hfield.h)
 };
 enum GJKInitialGuess { DefaultGuess, CachedGuess, BoundingVolumeGuess };
 enum GJKVariant { DefaultGJK, PolyakAcceleration, NesterovAcceleration };
@@ -352,6 +354,109 @@ class BVHModel : public CollisionGeometry {
   std::vector<uint32_t> flat_tris_, primitive_indices_;
 };
 
+struct AABB {
+  Vec3f min_, max_;
+  bool overlap(const AABB& o) const {  // BV/AABB.h:112-122
+    for (int k = 0; k < 3; ++k)
+      if (min_[k] > o.max_[k] || max_[k] < o.min_[k]) return false;
+    return true;
+  }
+};
+
+/// The two Eigen types HeightField's interface names, as far as it uses them: a dense matrix of heights (rows = y, north edge first)
+/// and a vector.
+struct MatrixXf {
+  MatrixXf() {}
+  MatrixXf(std::size_t rows, std::size_t cols) : rows_(rows), cols_(cols), v_(rows * cols, 0.0) {}
+  static MatrixXf Constant(std::size_t rows, std::size_t cols, FCL_REAL c) {
+    MatrixXf m(rows, cols);
+    m.fill(c);
+    return m;
+  }
+  static MatrixXf Ones(std::size_t rows, std::size_t cols) { return Constant(rows, cols, 1.0); }
+  void fill(FCL_REAL c) { std::fill(v_.begin(), v_.end(), c); }
+  std::size_t rows() const { return rows_; }
+  std::size_t cols() const { return cols_; }
+  FCL_REAL& operator()(std::size_t r, std::size_t c) { return v_[r * cols_ + c]; }
+  const FCL_REAL& operator()(std::size_t r, std::size_t c) const { return v_[r * cols_ + c]; }
+  FCL_REAL maxCoeff() const { return *std::max_element(v_.begin(), v_.end()); }
+  const FCL_REAL* data() const { return v_.data(); }  // row-major
+
+ private:
+  std::size_t rows_ = 0, cols_ = 0;
+  std::vector<FCL_REAL> v_;
+};
+typedef std::vector<FCL_REAL> VecXf;
+
+/// HeightField<AABB> (include/hpp/fcl/hfield.h:202-520): x_dim by y_dim, centred at the origin, heights(row, col) over
+/// x_grid = LinSpaced(cols, -x_dim/2, x_dim/2) and y_grid = LinSpaced(rows, y_dim/2, -y_dim/2), solid down to min_height.  The tree is
+/// built on the host (hfcl_hfield_build, the reference's numbering); collide() against a convex solid, in either operand order, goes to
+/// hfcl_hfield_collide_batch.  Only BV = AABB has collide() here.
+template <typename BV>
+class HeightField : public CollisionGeometry {
+  static_assert(std::is_same<BV, AABB>::value, "only HeightField<AABB> is built (HeightField<OBBRSS>: not done)");
+
+ public:
+  typedef hfcl_hfield_node Node;
+  typedef std::vector<Node> BVS;
+  HeightField(FCL_REAL x_dim, FCL_REAL y_dim, const MatrixXf& heights, FCL_REAL min_height = 0) : x_dim_(x_dim), y_dim_(y_dim), min_height_(min_height) {
+    init(heights);
+  }
+  NODE_TYPE getNodeType() const override { return HF_AABB; }
+  const VecXf& getXGrid() const { return x_grid_; }
+  const VecXf& getYGrid() const { return y_grid_; }
+  const MatrixXf& getHeights() const { return heights_; }
+  FCL_REAL getXDim() const { return x_dim_; }
+  FCL_REAL getYDim() const { return y_dim_; }
+  FCL_REAL getMinHeight() const { return min_height_; }
+  FCL_REAL getMaxHeight() const { return max_height_; }
+  const BVS& getNodes() const { return bvs_; }
+  const Node& getBV(unsigned int i) const {
+    if (i >= bvs_.size()) throw std::invalid_argument("Index out of bounds");
+    return bvs_[i];
+  }
+  void computeLocalAABB() {  // hfield.h:278-287
+    const Vec3f A(x_grid_.front(), y_grid_.front(), min_height_), B(x_grid_.back(), y_grid_.back(), max_height_);
+    for (int k = 0; k < 3; ++k) {
+      aabb_local.min_[k] = std::min(A[k], B[k]);
+      aabb_local.max_[k] = std::max(A[k], B[k]);
+    }
+    aabb_radius = (A - B).norm() / 2.;
+    aabb_center = (aabb_local.min_ + aabb_local.max_) * 0.5;
+  }
+  void updateHeights(const MatrixXf& new_heights) {  // hfield.h:290-305: the tree is rebuilt, the next collide() uploads it again
+    if (new_heights.rows() != heights_.rows() || new_heights.cols() != heights_.cols())
+      throw std::invalid_argument("The matrix containing the new heights values does not have the same matrix size as the original one.");
+    init(new_heights);
+  }
+  unsigned int version() const { return version_; }  // counts init / updateHeights: what a context has registered is this version
+  AABB aabb_local;
+  FCL_REAL aabb_radius = 0;
+  Vec3f aabb_center;
+
+ private:
+  void init(const MatrixXf& heights) {
+    std::size_t n = 0;
+    int rc = hfcl_hfield_build(x_dim_, y_dim_, heights.data(), heights.rows(), heights.cols(), min_height_, nullptr, &n, nullptr, nullptr);
+    if (rc) throw std::invalid_argument(hfcl_last_error());
+    bvs_.resize(n);
+    x_grid_.resize(heights.cols());
+    y_grid_.resize(heights.rows());
+    rc = hfcl_hfield_build(x_dim_, y_dim_, heights.data(), heights.rows(), heights.cols(), min_height_, bvs_.data(), &n, x_grid_.data(), y_grid_.data());
+    if (rc) throw std::invalid_argument(hfcl_last_error());
+    heights_ = heights;
+    for (std::size_t r = 0; r < heights_.rows(); ++r)
+      for (std::size_t c = 0; c < heights_.cols(); ++c) heights_(r, c) = std::max(heights_(r, c), min_height_);  // cwiseMax(min_height)
+    max_height_ = bvs_[0].max_height;
+    ++version_;
+  }
+  FCL_REAL x_dim_, y_dim_, min_height_, max_height_ = 0;
+  MatrixXf heights_;
+  VecXf x_grid_, y_grid_;
+  BVS bvs_;
+  unsigned int version_ = 0;
+};
+
 struct QueryRequest {
   GJKInitialGuess gjk_initial_guess = DefaultGuess;
   mutable Vec3f cached_gjk_guess = Vec3f(1, 0, 0);
@@ -486,6 +591,7 @@ class BatchQueries {
   void reset() {
     hfcl_multi_destroy(lib_);
     lib_ = nullptr;
+    ++generation_;
     shapes_.clear();
     verts_.clear();
     geoms_.clear();
@@ -500,6 +606,10 @@ class BatchQueries {
     adjacency_pending_ = false;
   }
   size_t numGeometries() const { return shapes_.size(); }
+  const CollisionGeometry* geometry(uint32_t id) const { return geoms_.at(id); }
+  /// Counts the device libraries this context has had (a new one after the first query and after every reset()): what was registered on
+  /// an earlier library directly -- height fields -- is gone when this number has changed, whatever address the new library has.
+  uint64_t libraryGeneration() const { return generation_; }
 
   uint32_t add(const CollisionGeometry* g) {
     hfcl_shape s{};
@@ -660,6 +770,7 @@ class BatchQueries {
     if (!lib_) {
       lib_ = hfcl_multi_create(devices_.data(), static_cast<int>(devices_.size()), shapes_.data(), shapes_.size(), verts_.data(), verts_.size() / 3);
       if (!lib_) throw std::runtime_error(hfcl_last_error());
+      ++generation_;
       meshes_uploaded_ = 0;
     } else if (shapes_dirty_) {  // geometries were added since the last query: new shape tables, everything else stays
       const int rc = hfcl_multi_set_shapes(lib_, shapes_.data(), shapes_.size(), verts_.data(), verts_.size() / 3);
@@ -731,6 +842,7 @@ class BatchQueries {
 
  private:
   std::vector<int> devices_;
+  uint64_t generation_ = 0;
   hfcl_multi* lib_ = nullptr;  // one replica of the library per device (one device: a single library behind the same calls)
   std::vector<hfcl_shape> shapes_;
   std::vector<double> verts_;
@@ -764,6 +876,151 @@ inline BatchQueries& default_context() {
   return ctx;
 }
 
+/// Batched collide() of HeightField<AABB> against convex solids (hfcl_hfield_collide_batch) on the library of a BatchQueries context:
+/// the solids are that context's geometries, the fields are registered here (a field whose heights were updated, and every field after
+/// the context was reset, is registered again).  One HeightFieldBatch per context.  The batch keeps a copy of every field it was given
+/// and the library a set of tables for each: reset() drops both (the indices addField returned are void then).
+class HeightFieldBatch {
+ public:
+  explicit HeightFieldBatch(BatchQueries& ctx) : ctx_(ctx) {}
+  uint32_t addSolid(const CollisionGeometry* g) { return ctx_.add(g); }
+  size_t numFields() const { return fields_.size(); }
+  /// Forget every field (and clear the library's height-field tables, if the library this batch registered on is still the context's).
+  void reset() {
+    if (lib_ && generation_ == ctx_.libraryGeneration()) hfcl_lib_clear_hfields(lib_);
+    fields_.clear();
+  }
+  uint32_t addField(const HeightField<AABB>* f) {
+    // The cache is keyed by address; a hit is only trusted if the field's CONTENT is still what was copied (addresses get reused once a
+    // field is destroyed: a stack object in a loop, a freed and reallocated one -- and every new field starts at version 1).
+    for (size_t k = 0; k < fields_.size(); ++k) {
+      const Entry& o = fields_[k];
+      if (o.field != f || o.version != f->version()) continue;
+      const MatrixXf& h = f->getHeights();
+      if (o.x_dim == f->getXDim() && o.y_dim == f->getYDim() && o.min_height == f->getMinHeight() && o.rows == h.rows() && o.cols == h.cols() &&
+          std::equal(o.heights.begin(), o.heights.end(), h.data()))
+        return static_cast<uint32_t>(k);
+    }
+    Entry e;
+    e.field = f;
+    e.version = f->version();
+    e.x_dim = f->getXDim();
+    e.y_dim = f->getYDim();
+    e.min_height = f->getMinHeight();
+    e.rows = f->getHeights().rows();
+    e.cols = f->getHeights().cols();
+    e.heights.assign(f->getHeights().data(), f->getHeights().data() + e.rows * e.cols);  // a copy: the field may be gone by the next query
+    fields_.push_back(e);
+    return static_cast<uint32_t>(fields_.size() - 1);
+  }
+  /// Query i: collide(field, solid), or collide(solid, field) where swapped[i] (swapped: empty, or one flag per query).  tf_field /
+  /// tf_solid are the field's and the solid's pose either way.  Results are fresh objects.
+  void collide(const std::vector<std::pair<uint32_t, uint32_t>>& field_solid, const std::vector<Transform3f>& tf_field,
+               const std::vector<Transform3f>& tf_solid, const std::vector<uint8_t>& swapped, const CollisionRequest& request,
+               std::vector<CollisionResult>& results) {
+    const size_t n = field_solid.size();
+    if (tf_field.size() != n || tf_solid.size() != n || (!swapped.empty() && swapped.size() != n))
+      throw std::invalid_argument("pairs/poses size mismatch");
+    hfcl_lib* lib = ctx_.library();
+    if (lib != lib_ || generation_ != ctx_.libraryGeneration()) {  // a new library (the first query, or the context was reset -- the new one
+      lib_ = lib;                                                 // may sit at the old address): nothing of ours is on it
+      generation_ = ctx_.libraryGeneration();
+      for (Entry& e : fields_) e.index = -1;
+    }
+    std::vector<uint32_t> hf(n), sh(n);
+    for (size_t i = 0; i < n; ++i) {
+      Entry& e = fields_.at(field_solid[i].first);
+      if (e.index < 0) {
+        e.index = hfcl_lib_add_hfield(lib, e.x_dim, e.y_dim, e.heights.data(), e.rows, e.cols, e.min_height);
+        if (e.index < 0) throw std::invalid_argument(hfcl_last_error());
+      }
+      hf[i] = static_cast<uint32_t>(e.index);
+      sh[i] = field_solid[i].second;
+    }
+    const hfcl_collision_request a = to_abi(request);
+    rec_.resize(n);
+    bound_.resize(n);
+    size_t cap = std::max<size_t>(64, 4 * n), produced = 0;
+    int rc = HFCL_OK;
+    for (int attempt = 0; attempt < 2; ++attempt) {  // (a list that outgrew the guess: once more with the count)
+      contacts_.resize(cap);
+      rc = hfcl_hfield_collide_batch(lib, hf.data(), sh.data(), reinterpret_cast<const double*>(tf_field.data()),
+                                     reinterpret_cast<const double*>(tf_solid.data()), n, swapped.empty() ? nullptr : swapped.data(), &a,
+                                     rec_.data(), bound_.data(), contacts_.data(), cap, &produced);
+      if (rc || produced <= cap) break;
+      cap = produced;
+    }
+    if (rc == HFCL_ERR_LIMIT) throw std::invalid_argument(hfcl_last_error());
+    if (rc) throw_for(rc);
+    contacts_.resize(std::min(produced, cap));
+    results.assign(n, CollisionResult());
+    size_t k = 0;
+    for (size_t i = 0; i < n; ++i) {
+      const bool sw = !swapped.empty() && swapped[i];
+      const CollisionGeometry* field = fields_[field_solid[i].first].field;
+      const CollisionGeometry* solid = ctx_.geometry(sh[i]);
+      fill(results[i], rec_[i], bound_[i], sw ? solid : field, sw ? field : solid, static_cast<uint32_t>(i), k, request);
+    }
+  }
+  /// One record into a result that may hold earlier ones: every contact, the call's bound; nearest_points / normal are the record's
+  /// (the first contact's when there is one).
+  void fill(CollisionResult& res, const hfcl_result& r, double bound, const CollisionGeometry* o1, const CollisionGeometry* o2, uint32_t query,
+            size_t& k, const CollisionRequest& request) const {
+    while (k < contacts_.size() && contacts_[k].pair < query) ++k;
+    if (HFCL_STATUS_SKIPPED(r.status)) return;
+    if (bound < res.distance_lower_bound) {
+      res.distance_lower_bound = bound;
+      res.normal = Vec3f(r.normal[0], r.normal[1], r.normal[2]);
+      res.nearest_points = {{Vec3f(r.p1[0], r.p1[1], r.p1[2]), Vec3f(r.p2[0], r.p2[1], r.p2[2])}};
+    }
+    for (; k < contacts_.size() && contacts_[k].pair == query; ++k) {
+      if (res.numContacts() >= request.num_max_contacts) continue;
+      const hfcl_contact& h = contacts_[k];
+      Contact c;
+      c.o1 = o1;
+      c.o2 = o2;
+      c.b1 = h.b1;
+      c.b2 = h.b2;
+      c.normal = Vec3f(h.normal[0], h.normal[1], h.normal[2]);
+      c.nearest_points = {{Vec3f(h.p1[0], h.p1[1], h.p1[2]), Vec3f(h.p2[0], h.p2[1], h.p2[2])}};
+      c.pos = (c.nearest_points[0] + c.nearest_points[1]) / 2;
+      c.penetration_depth = h.penetration_depth;
+      res.addContact(c);
+    }
+  }
+  const std::vector<hfcl_result>& records() const { return rec_; }
+  const std::vector<double>& bounds() const { return bound_; }
+  const std::vector<hfcl_contact>& contacts() const { return contacts_; }
+
+ private:
+  struct Entry {
+    const HeightField<AABB>* field;
+    unsigned int version;
+    FCL_REAL x_dim, y_dim, min_height;
+    size_t rows, cols;
+    std::vector<double> heights;
+    int index = -1;  // on lib_
+  };
+  BatchQueries& ctx_;
+  hfcl_lib* lib_ = nullptr;
+  uint64_t generation_ = 0;  // ctx_.libraryGeneration() when lib_ was taken
+  std::vector<Entry> fields_;
+  std::vector<hfcl_result> rec_;
+  std::vector<double> bound_;
+  std::vector<hfcl_contact> contacts_;
+};
+constexpr size_t DEFAULT_HFIELD_BATCH_MAX = 16;  // fields (and versions of fields) the thread's default batch keeps before it starts over
+inline HeightFieldBatch& default_hfield_batch() {
+  static thread_local HeightFieldBatch b(default_context());
+  return b;
+}
+/// does collide() have a function for this pair with a height field in it?
+inline bool hfield_pair_supported(const CollisionGeometry* o1, const CollisionGeometry* o2) {
+  const bool h1 = o1->getNodeType() == HF_AABB, h2 = o2->getNodeType() == HF_AABB;
+  return h1 != h2 && hfcl_hfield_pair_supported((h1 ? o2 : o1)->getNodeType()) != 0;
+}
+inline bool is_hfield(const CollisionGeometry* g) { return g->getNodeType() == HF_AABB || g->getNodeType() == HF_OBBRSS; }
+
 }  // namespace amd
 
 /// hpp::fcl::collide (src/collision.cpp:69-130) as a batch of one.  Results accumulate in
@@ -777,6 +1034,18 @@ inline std::size_t collide(const CollisionGeometry* o1, const Transform3f& tf1, 
   if (request.num_max_contacts == 0)
     throw std::invalid_argument("Invalid number of max contacts (current value is 0).");
   if (result.isCollision() && request.num_max_contacts <= result.numContacts()) return result.numContacts();
+  if (amd::is_hfield(o1) || amd::is_hfield(o2)) {  // a height field against a solid, either order (hppfcl_amd_hfield.h)
+    if (!amd::hfield_pair_supported(o1, o2)) throw std::invalid_argument("Collision function between the two node types is not yet supported.");
+    const bool swapped = !amd::is_hfield(o1);
+    amd::HeightFieldBatch& hb = amd::default_hfield_batch();
+    if (hb.numFields() >= amd::DEFAULT_HFIELD_BATCH_MAX) hb.reset();  // (fields that came and went, versions of updated ones: not kept for ever)
+    const std::pair<uint32_t, uint32_t> fs(hb.addField(static_cast<const HeightField<AABB>*>(swapped ? o2 : o1)), hb.addSolid(swapped ? o1 : o2));
+    std::vector<CollisionResult> one;
+    hb.collide({fs}, {swapped ? tf2 : tf1}, {swapped ? tf1 : tf2}, {static_cast<uint8_t>(swapped ? 1 : 0)}, request, one);
+    size_t k = 0;
+    hb.fill(result, hb.records()[0], hb.bounds()[0], o1, o2, 0, k, request);
+    return result.numContacts();
+  }
   amd::BatchQueries& ctx = amd::default_context();
   const std::pair<uint32_t, uint32_t> p(ctx.add(o1), ctx.add(o2));
   ctx.run({p}, {tf1}, {tf2}, &request, nullptr);
@@ -809,7 +1078,7 @@ inline FCL_REAL distance(const CollisionGeometry* o1, const Transform3f& tf1, co
 class ComputeCollision {
  public:
   ComputeCollision(const CollisionGeometry* o1_, const CollisionGeometry* o2_) : o1(o1_), o2(o2_) {
-    if (!hfcl_pair_supported(o1->getNodeType(), o2->getNodeType(), 0))
+    if (amd::is_hfield(o1) || amd::is_hfield(o2) ? !amd::hfield_pair_supported(o1, o2) : !hfcl_pair_supported(o1->getNodeType(), o2->getNodeType(), 0))
       throw std::invalid_argument("Collision function between the two node types is not yet supported.");
   }
   virtual ~ComputeCollision() {}
@@ -992,15 +1261,6 @@ class ComputeContactPatch {
 // Broadphase hand-off (include/hpp/fcl/collision_object.h:215-357, broadphase/broadphase_callbacks.h,
 // broadphase/default_broadphase_callbacks.h:200-230, broadphase/broadphase_dynamic_AABB_tree.h).
 // ---------------------------------------------------------------------------------------------
-struct AABB {
-  Vec3f min_, max_;
-  bool overlap(const AABB& o) const {  // BV/AABB.h:112-122
-    for (int k = 0; k < 3; ++k)
-      if (min_[k] > o.max_[k] || max_[k] < o.min_[k]) return false;
-    return true;
-  }
-};
-
 class CollisionObject {
  public:
   CollisionObject(const std::shared_ptr<CollisionGeometry>& g, const Transform3f& tf = Transform3f()) : cgeom(g), t(tf) {}
