@@ -18,7 +18,12 @@ using namespace hfcl;
 
 // minimum waves per SIMD the register allocator must allow for (A/B-tuned, see profiles/)
 #ifndef HFCL_WPE_GJK_W2
-#define HFCL_WPE_GJK_W2 2  // 2-lane groups hold 16 vertices of each hull per lane (96 VGPRs)
+#define HFCL_WPE_GJK_W2 2  // 2-lane groups, prim x convex and convex x prim: one hull of 16 vertices per lane in registers (48 VGPRs)
+#endif
+// ... convex x convex: hull 0 in registers (48 VGPRs), hull 1 in an LDS slab (hfcl_k_gjk.hip: HullLds).  Allowed 256 registers
+// the allocator takes 240; held to 168 it emits the same instructions with no scratch, and three waves fit a SIMD.
+#ifndef HFCL_WPE_GJK_CC2
+#define HFCL_WPE_GJK_CC2 3
 #endif
 #ifndef HFCL_WPE_GJK
 #define HFCL_WPE_GJK 3

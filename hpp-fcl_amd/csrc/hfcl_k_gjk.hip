@@ -211,17 +211,42 @@ __device__ __forceinline__ void finish_gjk(const Gjk<T, P>& g, const Work& wk, c
   }
 }
 
-// The simplex payload policy of a GJK kernel with NT threads per block (HFCL_GJK_W0_LDS=0: A/B switch back to
-// register payloads).
-#if HFCL_GJK_W0_LDS
-template <typename T, int NT> using GjkW0 = W0Lds<T, NT>;
-#define HFCL_GJK_W0_SLAB(T, NT, name)          \
-  __shared__ T name##_slab[W0Lds<T, NT>::WORDS]; \
-  const W0Lds<T, NT> name{name##_slab + threadIdx.x}
-#else
-template <typename T, int NT> using GjkW0 = W0Regs<T>;
-#define HFCL_GJK_W0_SLAB(T, NT, name) const W0Regs<T> name = W0Regs<T>()
-#endif
+// Where a GJK kernel with NT threads per block keeps the payload of its simplex vertices (the support point on shape 0, read only
+// after the loop) is a property of the instantiation (MODE):
+//   W0_REGS  in registers with the vertex (W0Regs, hfcl_pair.hpp): 12 VGPRs that every simplex shift drags along
+//   W0_LANE  in an LDS slab of four points per lane (W0Lds<T, NT>, hfcl_dev.hpp)
+//   W0_GROUP in an LDS slab of four points per lane group of G lanes (W0Lds<T, NT / G> at threadIdx.x / G): the lanes of a group step one
+//            pair and hold the same simplex, so they store the same points to the same words and read them back as a broadcast
+//   W0_INDEX nowhere: the support point of a register-resident hull is one of its vertices, so a simplex vertex carries the index the
+//            support scan ended on (W0Index) and the finish reads the three floats back from the library -- one register per vertex, no LDS
+// HFCL_GJK_W0_LDS=0 is the A/B switch of every kernel but k_gjk_cvx<2, 0> back to W0_REGS; that kernel has HFCL_GJK_CC2_W0 (below).
+enum { W0_REGS = 0, W0_LANE = 1, W0_GROUP = 2, W0_INDEX = 3 };
+constexpr int GJK_W0_DEFAULT = HFCL_GJK_W0_LDS ? W0_LANE : W0_REGS;
+template <typename T, int NT, int MODE, int G = 1>
+__device__ __forceinline__ auto gjk_w0() {
+  static_assert(MODE == W0_REGS || MODE == W0_LANE || MODE == W0_GROUP, "W0_INDEX is made per pair (gjk_cvx_body)");
+  if constexpr (MODE == W0_REGS) {
+    return W0Regs<T>();
+  } else {
+    constexpr int SLOTS = MODE == W0_GROUP ? NT / G : NT;
+    __shared__ T slab[W0Lds<T, SLOTS>::WORDS];
+    return W0Lds<T, SLOTS>{slab + (MODE == W0_GROUP ? threadIdx.x / G : threadIdx.x)};
+  }
+}
+// put() follows the support call of its vertex (gjk_run, hfcl_pair.hpp), which left the vertex's index in *last; the lanes of a group
+// agree on it (HullRegs::support).  get() clamps as the hull's loader does, so a read stays inside the hull whatever the index.
+template <typename T>
+struct W0Index {
+  typedef PSlot P;
+  const int* last;  // index of the vertex the last support call on shape 0 returned
+  const T* verts;   // the hull of shape 0
+  uint32_t n;
+  template <class G> __device__ __forceinline__ P put(const G&, const V3<T>&) const { return P{uint32_t(*last)}; }
+  __device__ __forceinline__ V3<T> get(const P& p) const {
+    const T* q = verts + 3 * size_t(p.s < n ? p.s : 0u);
+    return mk<T>(q[0], q[1], q[2]);
+  }
+};
 
 // ---------------------------------------------------------------------------------------
 // k_gjk_prim: primitive x primitive GJK, one pair per lane.
@@ -231,7 +256,7 @@ template <typename T, int NT> using GjkW0 = W0Regs<T>;
 // 0.96 -> 1.51 ms), so the default-guess kernels are compiled without it.
 template <typename T, bool BVG>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HFCL_WPE_PRIM, 8))) k_gjk_prim(Work wk, LibView<T> lib, IO<T> io, QParams<T> q) {
-  HFCL_GJK_W0_SLAB(T, 256, ps);
+  const auto ps = gjk_w0<T, 256, GJK_W0_DEFAULT>();
   const BucketList list = bucket_list(wk, B_PRIM);
   for (uint32_t it = blockIdx.x * blockDim.x + threadIdx.x; it < list.cnt; it += gridDim.x * blockDim.x) {
     const uint32_t pair = list[it];
@@ -244,7 +269,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HFCL_W
     sup.md = make_mdiff(tf1, tf2);
     const T r0 = swept_radius(a), r1 = swept_radius(b);
     const V3<T> guess0 = initial_guess<T>(io, q, pair);
-    Gjk<T, typename GjkW0<T, 256>::P> g;
+    Gjk<T, typename decltype(ps)::P> g;
     if constexpr (BVG)
       gjk_run(g, q.gjk, start_guess(q, a, b, sup.md, guess0), r0 + r1, false, sup, ps);
     else
@@ -340,8 +365,10 @@ template <typename T, int W, int M> constexpr bool hull_b_in_lds = HFCL_GJK_HULL
 
 // M: 0 = convex-convex, 1 = prim-convex, 2 = convex-prim
 // NT: threads per workgroup (the stride of the LDS slabs)
-template <typename T, int W, int M, int NT>
+// IDX: keep the index of the vertex the last support call on shape 0 returned (i0: W0Index)
+template <typename T, int W, int M, int NT, bool IDX = false>
 struct CvxSupport {
+  mutable int i0;
   DShape<T> a, b;
   HullRegs<T, W> h0;
   typename std::conditional<hull_b_in_lds<T, W, M>, HullLds<T, W, NT>, HullRegs<T, W>>::type h1;
@@ -351,7 +378,7 @@ struct CvxSupport {
     if (M == 1)
       w0 = prim_support(a, dir);
     else
-      w0 = h0.support(dir, lig);
+      w0 = h0.support(dir, lig, IDX ? &i0 : nullptr);
     const V3<T> d1 = md.identity ? -dir : -tmul(md.oR1, dir);
     V3<T> s1;
     if (M == 2)
@@ -364,17 +391,33 @@ struct CvxSupport {
   __device__ __forceinline__ void operator()(const V3<T>& dir, V3<T>& w, V3<T>& w0) const { eval(dir, w, w0); }
 };
 
+// Simplex payloads of the fp32 convex x convex kernel of 2-lane groups (HFCL_GJK_CC2_W0: a W0_* value; A/B switch).  Its workgroup is one
+// wave whose LDS is the hull slab (12 288 B) plus the payload slab, and a CU's LDS is 128 units of 1 280 B: with a slab per lane
+// (3 072 B more) a workgroup is 12 units and ten fit a CU, per group 11 units and eleven, without one 10 units and twelve -- three
+// waves on every SIMD, which is what the kernel's register budget (HFCL_WPE_GJK_CC2, hfcl_dev.hpp) allows.  Headline step on one MI355X:
+// 1.562 ms at eight per CU (two waves per SIMD by registers), 1.540 at ten, 1.518 at eleven, 1.417 at twelve with W0_INDEX
+// (profiles/r21_a_gjk_occupancy.md).  W0_REGS also gives twelve (1.430 ms) but not the same records: with the points in registers the
+// compiler fuses the multiply-adds of gjk_finish's witness sums differently, and a fifth of the separated pairs' points differ in their last bits.
+// Every other instantiation keeps the policy of the unit.
+#ifndef HFCL_GJK_CC2_W0
+#define HFCL_GJK_CC2_W0 3
+#endif
+template <typename T, int W, int M> constexpr int gjk_cvx_w0 = (sizeof(T) == 4 && W == 2 && M == 0) ? HFCL_GJK_CC2_W0 : GJK_W0_DEFAULT;
+static_assert(HFCL_GJK_CC2_W0 >= W0_REGS && HFCL_GJK_CC2_W0 <= W0_INDEX, "HFCL_GJK_CC2_W0: one of W0_REGS, W0_LANE, W0_GROUP, W0_INDEX");
+
 template <typename T, int W, int M, bool BVG, int NT>
 __device__ __forceinline__ void gjk_cvx_body(const Work& wk, const LibView<T>& lib, const IO<T>& io, const QParams<T>& q) {
   constexpr int BUCKET = (M == 0) ? B_CC : (M == 1 ? B_PC : B_CP);
-  HFCL_GJK_W0_SLAB(T, NT, ps);
+  constexpr bool IDX = gjk_cvx_w0<T, W, M> == W0_INDEX;
+  static_assert(!IDX || M != 1, "W0_INDEX: shape 0 is a register-resident hull");
+  const auto ps0 = gjk_w0<T, NT, IDX ? W0_REGS : gjk_cvx_w0<T, W, M>, W>();  // (IDX: unused)
   __shared__ T hull_slab[hull_b_in_lds<T, W, M> ? HullLds<T, W, NT>::WORDS : 1];
   const BucketList list = bucket_list(wk, BUCKET);
   const int lig = threadIdx.x & (W - 1);
   const uint32_t groups = (gridDim.x * blockDim.x) / W;
   for (uint32_t it = (blockIdx.x * blockDim.x + threadIdx.x) / W; it < list.cnt; it += groups) {
     const uint32_t pair = list[it];
-    CvxSupport<T, W, M, NT> sup;
+    CvxSupport<T, W, M, NT, IDX> sup;
     if constexpr (hull_b_in_lds<T, W, M>) sup.h1.lane = hull_slab + threadIdx.x;
     sup.a = lib.shapes[wk.shape1[pair]];
     sup.b = lib.shapes[wk.shape2[pair]];
@@ -385,7 +428,13 @@ __device__ __forceinline__ void gjk_cvx_body(const Work& wk, const LibView<T>& l
     sup.md = make_mdiff(tf1, tf2);
     const T r0 = swept_radius(sup.a), r1 = swept_radius(sup.b);
     const V3<T> guess0 = initial_guess<T>(io, q, pair);
-    Gjk<T, typename GjkW0<T, NT>::P> g;
+    const auto ps = [&] {
+      if constexpr (IDX)
+        return W0Index<T>{&sup.i0, lib.verts + 3 * size_t(sup.a.vertex_offset), sup.a.num_points};
+      else
+        return ps0;
+    }();
+    Gjk<T, typename decltype(ps)::P> g;
     // normalize_support_direction only when both are ConvexBase (minkowski_difference.cpp:261-266)
     if constexpr (BVG)
       gjk_run(g, q.gjk, start_guess(q, sup.a, sup.b, sup.md, guess0), r0 + r1, M == 0, sup, ps);
@@ -401,9 +450,11 @@ __device__ __forceinline__ void gjk_cvx_body(const Work& wk, const LibView<T>& l
 // instantiation spills heavily at the fp32 setting (A/B in profiles/).
 // The fp32 convex x convex kernel of 2-lane groups runs in workgroups of one wave (gjk_cvx_threads, hfcl_launch.hpp): a wave's
 // round of 32 pairs lasts as long as its slowest pair, and a 256-thread block holds its four wave slots and its 60 KB of LDS until the
-// slowest of four such rounds has ended.  A wave that is a workgroup of its own (15 KB) is replaced the moment it ends.
+// slowest of four such rounds has ended.  A wave that is a workgroup of its own (12 KB: gjk_cvx_w0) is replaced the moment it ends, and
+// twelve of them are resident on a CU: the kernel runs at about half of the VALU issue peak with its waves waiting a third of their time,
+// so a third wave on every SIMD fills slots the other two leave (headline step 1.562 -> 1.417 ms, profiles/r21_a_gjk_occupancy.md).
 template <int W, int M, bool BVG>
-__global__ void __launch_bounds__(gjk_cvx_threads<float>(W, M)) __attribute__((amdgpu_waves_per_eu(W == 2 ? HFCL_WPE_GJK_W2 : HFCL_WPE_GJK, 8)))
+__global__ void __launch_bounds__(gjk_cvx_threads<float>(W, M)) __attribute__((amdgpu_waves_per_eu(W == 2 ? (M == 0 ? HFCL_WPE_GJK_CC2 : HFCL_WPE_GJK_W2) : HFCL_WPE_GJK, 8)))
 k_gjk_cvx(Work wk, LibView<float> lib, IO<float> io, QParams<float> q) {
   gjk_cvx_body<float, W, M, BVG, gjk_cvx_threads<float>(W, M)>(wk, lib, io, q);
 }
@@ -445,7 +496,7 @@ template <typename T, bool BVG>
 // (two waves per SIMD: the compiler's own fp64 allocation is 260 registers -- one wave -- for 20 B of scratch less;
 // k_gjk_large<double> 1.05 -> 0.60 ms per 100k 64-vertex pairs, 6.0 -> 3.4 ms at 1024 vertices)
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) k_gjk_large(Work wk, LibView<T> lib, IO<T> io, QParams<T> q) {
-  HFCL_GJK_W0_SLAB(T, 256, ps);
+  const auto ps = gjk_w0<T, 256, GJK_W0_DEFAULT>();
   const uint32_t cnt = wk.counts[B_LARGE];
   const int lig = threadIdx.x & (LARGE_W - 1);
   const uint32_t groups = (gridDim.x * blockDim.x) / LARGE_W;
@@ -465,7 +516,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))
     sup.md = make_mdiff(tf1, tf2);
     const T r0 = swept_radius(sup.a), r1 = swept_radius(sup.b);
     const V3<T> guess0 = initial_guess<T>(io, q, pair);
-    Gjk<T, typename GjkW0<T, 256>::P> g;
+    Gjk<T, typename decltype(ps)::P> g;
     if constexpr (BVG)
       gjk_run(g, q.gjk, start_guess(q, sup.a, sup.b, sup.md, guess0), r0 + r1, sup.a.kind == K_CONVEX && sup.b.kind == K_CONVEX, sup, ps);
     else

@@ -13,9 +13,11 @@
 
 Times are in trips (one lockstep iteration of a wave) and say nothing about waves that share a SIMD speeding up when a partner leaves:
 for k_gjk_cvx the device shows less than the model (profiles/r07_a_wave_scheduling.md has both); for k_epa_loop's pool it shows as much
-or more, levelling off at 20 % as here (profiles/r15_a_epa_pool.md).
+or more, levelling off at 20 % as here (profiles/r15_a_epa_pool.md).  model_gjk's number of resident waves per CU is an argument (8 until
+round 20, 12 since); gjk_forecast turns its ends at two residencies into a time, pricing a trip by how many independent waves share a
+SIMD's issue slots: 0.531 ms forecast for 0.457 measured (profiles/r21_a_gjk_occupancy.md section 5).
 
-usage: tools/sched_model.py [--pairs 1000000] [--seed 1] [--cus 256] [--threads 16]"""
+usage: tools/sched_model.py [--pairs 1000000] [--seed 1] [--cus 256] [--threads 16] [--gjk-waves-per-cu 12]"""
 import argparse
 import heapq
 import os
@@ -59,11 +61,14 @@ def greedy(durations, slots):
     return end, float(np.sum(durations)) / (slots * end) if end > 0 else 0.0
 
 
-def model_gjk(iters, cus, setup):
+def model_gjk(iters, cus, setup, waves_per_cu=8):
+    """waves_per_cu: resident waves of the kernel per CU (8 = two per SIMD, the form of rounds 2 to 20; 12 = three per SIMD).  The ends are in
+    trips of a wave, and a trip lasts longer the more waves share a SIMD's issue slots: compare ends of different residencies through
+    gjk_forecast, not directly."""
     trips = iters + 1
     pad = (-len(trips)) % 32
     rounds = np.concatenate([trips, np.zeros(pad, dtype=trips.dtype)]).reshape(-1, 32).max(axis=1) + setup
-    wave_slots = cus * 8  # two waves per SIMD
+    wave_slots = cus * waves_per_cu
     # 256-thread blocks, grid = 16 per CU: wave w of block b owns the rounds (4 b + w) + k * (4 * grid)
     grid = min(cus * 16, (len(rounds) + 3) // 4)
     waves = np.zeros(grid * 4)
@@ -76,6 +81,17 @@ def model_gjk(iters, cus, setup):
     end_wave, _ = greedy(rounds, wave_slots)
     return {"trips_per_pair": float(trips.mean()), "round_mean": float(rounds.mean() - setup), "round_sd": float(rounds.std()),
             "rounds_per_wave": len(rounds) / (grid * 4.0), "held": held, "used": used, "end_256": end_block, "end_64": end_wave}
+
+
+def gjk_forecast(ms_ref, end_ref, end_new, waves_ref, waves_new, issue_ref):
+    """k_gjk_cvx<2, 0> at another residency, from a measured time.  A wave issues a VALU instruction in the share issue_ref / waves_ref of its
+    SIMD's cycles when waves_ref waves share the SIMD (issue_ref: measured SQ_INSTS_VALU over the issue peak) and waits for the rest; with
+    more waves the waits overlap and the issue slots are shared, so the SIMD's issue share rises to at most 1 - (1 - issue_ref / waves_ref) ** waves_new
+    (independent waves) and a trip takes waves_new / waves_ref * issue_ref / that as long.  Returns (ms, issue share)."""
+    p = issue_ref / waves_ref
+    issue_new = 1.0 - (1.0 - p) ** waves_new
+    trip = (waves_new / waves_ref) * (issue_ref / issue_new)
+    return ms_ref * (end_new / end_ref) * trip, issue_new
 
 
 def model_epa(lengths, grid, pool_share, k, min_refills, groups=8):
@@ -149,6 +165,9 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--cus", type=int, default=256)
     ap.add_argument("--threads", type=int, default=min(16, os.cpu_count() or 1))
+    ap.add_argument("--gjk-waves-per-cu", type=int, default=12, help="resident waves of k_gjk_cvx<2, 0> per CU (registers and LDS: DESIGN.md section 3)")
+    ap.add_argument("--gjk-ref-ms", type=float, default=0.596, help="measured k_gjk_cvx<2, 0> time at 8 waves per CU (profiles/r15_a section 5)")
+    ap.add_argument("--gjk-ref-issue", type=float, default=0.50, help="its SQ_INSTS_VALU over the issue peak (profiles/traffic_cfg3.json of that build)")
     a = ap.parse_args()
     gjk_iters, epa_len = oracle_counts(a.pairs, a.seed, a.threads)
     print("oracle: %d pairs, %.2f GJK iterations per pair, %d polytopes, %.2f EPA iterations each (%d past the block's %d)" % (
@@ -159,6 +178,12 @@ def main():
               "wave-trips per slot for %.0f used and end at %.0f; single-wave workgroups end at %.0f (-%.1f %%)" % (
                   setup, g["round_mean"], g["round_sd"], g["trips_per_pair"], g["rounds_per_wave"], g["held"], g["used"], g["end_256"],
                   g["end_64"], 100 * (1 - g["end_64"] / g["end_256"])))
+    if a.gjk_waves_per_cu != 8:
+        g8, gn = model_gjk(gjk_iters, a.cus, 3, 8), model_gjk(gjk_iters, a.cus, 3, a.gjk_waves_per_cu)
+        ms, issue = gjk_forecast(a.gjk_ref_ms, g8["end_64"], gn["end_64"], 2.0, a.gjk_waves_per_cu / 4.0, a.gjk_ref_issue)
+        print("k_gjk_cvx<2,0>  %d waves per CU against 8: single-wave workgroups end at %.0f trips against %.0f; issue share %.2f -> %.2f, "
+              "a trip %.2f times as long: %.3f ms -> forecast %.3f ms" % (a.gjk_waves_per_cu, gn["end_64"], g8["end_64"], a.gjk_ref_issue, issue,
+                                                                        ms / a.gjk_ref_ms * g8["end_64"] / gn["end_64"], a.gjk_ref_ms, ms))
     grid = a.cus * 12
     base = model_epa(epa_len, grid, 0.0, 16, 2)
     print("k_epa_loop  static: waves end at %.0f trips on average, the last at %.0f" % (base["mean_end"], base["last_end"]))
