@@ -983,6 +983,69 @@ def distance_scene(objects, pair_indices, request, transforms=None, broadphase=F
     return rec["distance"].reshape(n_conf, len(pr)), rec, summ
 
 
+def collide_terrain(objects, field, field_tf, request, transforms=None, object_indices=None):
+    """A HeightFieldAABB under `objects` (CollisionObjects): DynamicAABBTreeCollisionManager::collide(terrain, CollisionCallBackDefault), or
+    the loop of collide(field, field_tf, o, tf_o) over a robot's links, for every configuration in ONE scene call
+    (engine.Scene.collide_terrain).  object_indices: the strictly ascending indices of the objects tested against the ground; None: every
+    object whose geometry has an evaluator against a height field.  transforms: as collide_scene -- None (one configuration, the objects'
+    own), an array (n_conf, n_objects, 12), or n_conf lists of Transform3f.  Returns (results, summaries): results[c][k] is the
+    CollisionResult collide(field, field_tf, objects[object_indices[k]], ...) gives under configuration c (a flat list when transforms
+    is None); summaries the abi.SCENE_SUMMARY_DTYPE record of every configuration -- min_distance the smallest
+    distance_lower_bound, min_pair / first_contact indices into `objects`, n_contacts > 0: isCollision() of the default callback."""
+    if request.num_max_contacts == 0:
+        raise ValueError("Invalid number of max contacts (current value is 0).")
+    if not isinstance(field, HeightFieldAABB):
+        raise ValueError("collide_terrain: the terrain is a HeightFieldAABB")
+    ctx = _context()
+    geoms = [o.collisionGeometry() for o in objects]
+    if object_indices is None:
+        listed = [i for i, g in enumerate(geoms) if engine.hfield_pair_supported(int(g.getNodeType()))]
+    else:
+        listed = [int(i) for i in object_indices]
+        if any(i < 0 or i >= len(objects) for i in listed):
+            raise ValueError("object index outside the objects")
+    ids = np.array([ctx.add(g) for g in geoms], dtype=np.uint32)
+    hid = ctx.add_hfield(field)
+    n = len(objects)
+    if transforms is None:
+        table = np.concatenate([o.getTransform()._abi().reshape(1, 12) for o in objects] + [np.zeros((0, 12))]).reshape(1, n, 12)
+    elif isinstance(transforms, np.ndarray):
+        table = np.ascontiguousarray(transforms, dtype=np.float64)
+        table = table.reshape(-1, n, 12) if n else table.reshape(len(table) if table.ndim == 3 else 0, 0, 12)
+    else:
+        table = np.stack([np.concatenate([t._abi().reshape(1, 12) for t in conf]) for conf in transforms])
+    lib = ctx.library()
+    sc = lib.scene(ids, np.zeros((0, 2), dtype=np.uint32))
+    try:
+        sc.set_terrain(hid, field_tf._abi().reshape(12), np.array(listed, dtype=np.uint32))
+        cap = int(min(request.num_max_contacts, 1 << 16)) * len(table) * len(listed)
+        rec, dlb, summ, contacts, _ = sc.collide_terrain(table, request._abi(), max_contacts=cap)
+    except engine.EngineError as e:
+        if e.code in (abi.ERR_INVALID_ARGUMENT, abi.ERR_UNSUPPORTED_PAIR, abi.ERR_LIMIT):
+            raise ValueError(str(e))  # std::invalid_argument in the reference
+        raise
+    finally:
+        sc.close()
+    starts = np.searchsorted(contacts["pair"], np.arange(len(rec) + 1))  # (the contacts come in query order)
+    out = []
+    for c in range(len(table)):
+        row = []
+        for k, i in enumerate(listed):
+            q = c * len(listed) + k
+            r = CollisionResult()
+            if not abi.status_skipped(rec[q]["status"]):
+                if dlb[q] < r.distance_lower_bound:
+                    r.distance_lower_bound = float(dlb[q])
+                    r.normal = np.array(rec[q]["normal"])
+                    r.nearest_points = [np.array(rec[q]["p1"]), np.array(rec[q]["p2"])]
+                for h in contacts[starts[q]:starts[q + 1]]:
+                    if r.numContacts() < request.num_max_contacts:
+                        r.addContact(Contact(field, geoms[i], h["b1"], h["b2"], h["p1"], h["p2"], h["normal"], h["penetration_depth"]))
+            row.append(r)
+        out.append(row)
+    return (out[0] if transforms is None else out), summ
+
+
 class DynamicAABBTreeCollisionManager:  # broadphase_dynamic_AABB_tree.h (candidate set = all AABB-overlapping pairs)
     def __init__(self):
         self._objs, self._aabbs = [], None

@@ -442,4 +442,15 @@ template <typename T> int setup_distance(const hfcl_distance_request* req, QPara
 KernelTime* timer_slot(hfcl_lib* lib, size_t i, const char* name);
 int upload_graph(hfcl_lib* lib);
 int upload_bvh(hfcl_lib* lib);
+// hfcl_host_hfield.hip: the height-field call's own pieces, which the terrain calls of the scene unit run their chunks through.
+// hf_request: what every form checks of a request before any work (q: hf_leaf_params of it); hf_chunk: queries per chunk (option
+// hfield_chunk); hf_run: queries [0, n) on device pointers in chunks -- pair0: the index of query 0 in the caller's batch, first: this
+// is the first part of that batch (the running contact count, lib->hf.d_running, starts at 0); hf_no_device: HFCL_ERR_NO_DEVICE or 0
+constexpr uint64_t HF_ITEM_HARD_CAP = 1u << 26;  // leaves one query may list (7 GB of item workspace); no query yields more contacts
+int hf_request(const char* who, const hfcl_collision_request* req, QParams<double>& q, bool& skip_all);
+size_t hf_chunk(const hfcl_lib* lib);
+int hf_run(hfcl_lib* lib, const uint32_t* d_hfield, const uint32_t* d_shape, const double* d_tfh, const double* d_tfs, size_t n,
+           const uint8_t* d_swapped, const hfcl_collision_request* req, const QParams<double>& q, bool skip_all, hfcl_result* d_out, double* d_dlb,
+           hfcl_contact* d_contacts, size_t contacts_cap, bool want_contacts, uint32_t pair0, bool first, hipStream_t st);
+int hf_no_device();
 #pragma GCC visibility pop

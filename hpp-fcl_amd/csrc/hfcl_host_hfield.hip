@@ -9,7 +9,7 @@ namespace {
 
 constexpr size_t HF_AUTO_CHUNK = 65536;         // queries per chunk when the option is 0
 constexpr uint64_t HF_ITEM_SOFT_CAP = 1u << 20;  // a chunk is cut down (to one query at the least) while it lists more items than this (option hfield_items)
-constexpr uint64_t HF_ITEM_HARD_CAP = 1u << 26;  // ... and a single query that lists more is refused (7 GB of item workspace)
+// (HF_ITEM_HARD_CAP, hfcl_host.hpp: ... and a single query that lists more is refused)
 
 int hf_build(double x_dim, double y_dim, const double* heights, size_t ny, size_t nx, double min_height, hfcl_hfield_node* nodes_out,
              size_t* n_nodes_out, double* xg_out, double* yg_out, std::vector<double>* clamped_out) {
@@ -92,6 +92,9 @@ int upload_hfields(hfcl_lib* lib) {
   return HFCL_OK;
 }
 
+}  // namespace
+
+// (hf_request, hf_chunk, hf_run, hf_no_device: declared in hfcl_host.hpp -- the scene unit's terrain calls run their chunks through them)
 // what every form checks before any work
 int hf_request(const char* who, const hfcl_collision_request* req, QParams<double>& q, bool& skip_all) {
   const int rc = setup_collide<double>(req, q, skip_all);  // num_max_contacts == 0, epa_max_iterations > 64, tolerances, variants
@@ -110,7 +113,7 @@ int hf_request(const char* who, const hfcl_collision_request* req, QParams<doubl
 }
 
 size_t hf_chunk(const hfcl_lib* lib) { return lib->opt.hfield_chunk ? lib->opt.hfield_chunk : HF_AUTO_CHUNK; }
-uint64_t hf_item_cap(const hfcl_lib* lib) { return lib->opt.hfield_items ? lib->opt.hfield_items : HF_ITEM_SOFT_CAP; }
+static uint64_t hf_item_cap(const hfcl_lib* lib) { return lib->opt.hfield_items ? lib->opt.hfield_items : HF_ITEM_SOFT_CAP; }
 
 // The call on device pointers: queries [0, n) in chunks; pair0: the index of query 0 in the caller's batch; first: this is the first
 // part of that batch (the running contact count starts at 0)
@@ -215,8 +218,6 @@ int hf_no_device() {
   }
   return HFCL_OK;
 }
-
-}  // namespace
 
 extern "C" {
 

@@ -1,11 +1,13 @@
 // hfcl_host_scene.hip -- host side of the scene queries (hfcl_scene_*) and of the cull of their pair lists (the kernels: hfcl_k_scene.hip,
-// hfcl_k_cull.hip).  The library object and what this unit calls of hfcl_host.hip: hfcl_host.hpp.
+// hfcl_k_cull.hip, ...; the terrain calls: hfcl_k_terrain.hip around hfcl_host_hfield.hip's hf_run).  The library object and what this
+// unit calls of the other host units: hfcl_host.hpp.
 #include "hfcl_host.hpp"
 #include "hfcl_plan.hpp"
 #include "hfcl_nearest.hpp"
 #include "hfcl_nearest_self.hpp"
 #include "hfcl_env.hpp"
 #include "hfcl_nearest_env.hpp"
+#include "hfcl_terrain.hpp"
 #include "../../include/hppfcl_amd_nearest.h"
 #include "../../include/hppfcl_amd_groups.h"
 #include "../../include/hppfcl_amd_nearest_self.h"
@@ -40,6 +42,23 @@ struct hfcl_scene {
   // ... and the terms of the clearance bound (hfcl_nearest_env.hpp): two doubles per environment box, two per tile
   DevBuf<double> d_env_terms, d_env_tile_terms;
   size_t n_env() const { return n_objects - n_moving; }
+  size_t rows() const { return has_env ? n_moving : n_objects; }  // hfcl_scene_n_moving: pose rows a configuration of an _env / terrain table
+  // a height-field terrain (hfcl_scene_set_terrain; has_terrain false: none): a field of the library at one pose and the ascending list
+  // of the objects tested against it; the objects' shapes on the host, for the setter's checks; the workspace of a chunk of terrain
+  // queries -- the four arrays of the height-field call, and its records when the caller takes none --, what a call keeps per query for
+  // the fold (bounds when the caller gives no buffer for them, status words), and the host form's summaries
+  std::vector<uint32_t> h_object_shape;
+  bool has_terrain = false;
+  uint32_t terrain_hfield = 0;
+  std::vector<uint32_t> h_terrain_objects;
+  DevBuf<uint32_t> d_terrain_objects;
+  DevBuf<double> d_terrain_tf;
+  struct TerrainWs {
+    DevBuf<uint32_t> d_hfield, d_shape, d_status;
+    DevBuf<double> d_tfh, d_tfs, d_bounds;
+    DevBuf<hfcl_result> d_rec;
+    DevBuf<hfcl_scene_summary> d_summary;
+  } tw;
 };
 
 static int scene_check_pairs(const char* who, const uint32_t* pairs, size_t n_pairs, size_t n_objects) {
@@ -1927,6 +1946,129 @@ static int nearest_env_host(const char* who, hfcl_scene* s, const void* table, s
   return host_batch_checks(lib, nullptr, req);
 }
 
+// ---------------------------------------------------------------------------------------
+// A height-field terrain under the moving objects (include/hppfcl_amd_terrain.h): query q = c * n_t + k is the terrain against listed
+// object k under configuration c.  The flat range goes in chunks of hfield_chunk queries: k_terrain_expand writes the chunk's four
+// per-query arrays into the scene's workspace, hf_run (hfcl_host_hfield.hip) runs them exactly as a caller's batch of that size -- with
+// the chunk's place in the call for hfcl_contact::pair and the running contact count --, k_terrain_status keeps the status words; after
+// the last chunk k_terrain_fold folds the kept bounds and status words.  hfcl_k_terrain.hip has the kernels, hfcl_terrain.hpp the arithmetic.
+// ---------------------------------------------------------------------------------------
+// What a terrain call refuses before any work, in this order: a null scene, a null request, the request checks of the height-field
+// calls, a stale scene, no terrain, a field that left the library, a listed object that is no pose row of the table any more, then
+// (n_conf > 0) an overflow, nothing asked for, a null table.  nothing: n_conf == 0.  total: n_conf * n_t
+static int terrain_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, const hfcl_collision_request* req,
+                            bool any_output, size_t* n_contacts_out, QParams<double>& q, bool& skip_all, bool& nothing, size_t& total) {
+  nothing = true;
+  total = 0;
+  if (!s) {
+    set_error(std::string(who) + ": null scene");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (!req) {
+    set_error(std::string(who) + ": null request");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (const int rc = hf_request(who, req, q, skip_all)) return rc;
+  if (const int rc = groups_scene(who, s)) return rc;
+  if (n_contacts_out) *n_contacts_out = 0;
+  if (!s->has_terrain) {
+    set_error(std::string(who) + ": the scene has no terrain (hfcl_scene_set_terrain)");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (s->terrain_hfield >= s->lib->hf.h_fields.size()) {
+    set_error(std::string(who) + ": height field " + std::to_string(s->terrain_hfield) + " is no longer on the library (hfcl_lib_clear_hfields); set the terrain again");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  const size_t n_t = s->h_terrain_objects.size();
+  if (n_t && s->h_terrain_objects.back() >= s->rows()) {
+    set_error(std::string(who) + ": listed object " + std::to_string(s->h_terrain_objects.back()) + " is none of the " + std::to_string(s->rows()) +
+              " moving objects (an environment was set after the terrain)");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (n_conf == 0) return HFCL_OK;
+  if (n_t && n_conf > 0xFFFFFFF0ull / n_t) {
+    set_error(std::string(who) + ": batch too large (max 2^32-16 queries per call)");
+    return HFCL_ERR_LIMIT;
+  }
+  if (!any_output) {
+    set_error(std::string(who) + ": records, bounds, summaries, contacts and the contact count all NULL");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (n_t && !table) {
+    set_error(std::string(who) + ": null pose table");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  nothing = false;
+  total = n_conf * n_t;
+  return HFCL_OK;
+}
+
+// The call on a table that is on the device, on st.  d_out / d_bounds / d_summary / d_contacts: device destinations (nullptr each: not
+// asked for); h_out / h_bounds: the host form's, filled chunk by chunk (the stream is waited for after every chunk then: the record
+// buffer is the next chunk's)
+static int terrain_run(hfcl_scene* s, const double* d_table, size_t n_conf, const hfcl_collision_request* req, const QParams<double>& q, bool skip_all,
+                       hfcl_result* d_out, double* d_bounds, hfcl_scene_summary* d_summary, hfcl_contact* d_contacts, size_t contacts_cap,
+                       bool want_contacts, hfcl_result* h_out, double* h_bounds, hipStream_t st) {
+  hfcl_lib* lib = s->lib;
+  hfcl_scene::TerrainWs& w = s->tw;
+  const size_t n_t = s->h_terrain_objects.size(), total = n_conf * n_t;
+  const size_t chunk = std::min(hf_chunk(lib), total);
+  const bool fold = d_summary != nullptr;
+  if (total) {  // (a buffer that grows is freed first, which waits for the device: nothing in flight reads the old one)
+    HIP_TRY(w.d_hfield.grow(chunk));
+    HIP_TRY(w.d_shape.grow(chunk));
+    HIP_TRY(w.d_tfh.grow(12 * chunk));
+    HIP_TRY(w.d_tfs.grow(12 * chunk));
+    if (!d_out) HIP_TRY(w.d_rec.grow(chunk));
+    if (!d_bounds && (fold || h_bounds)) {
+      HIP_TRY(w.d_bounds.grow(total));
+      d_bounds = w.d_bounds;
+    }
+    if (fold) HIP_TRY(w.d_status.grow(total));
+  }
+  const int max_blocks = lib->n_cus * 16;
+  TerrainExpandArgs e;
+  e.table = d_table;
+  e.tf_terrain = s->d_terrain_tf;
+  e.objects = s->d_terrain_objects;
+  e.object_shape = s->d_object_shape;
+  e.n_rows = s->rows();
+  e.n_t = uint32_t(n_t);
+  e.hfield = s->terrain_hfield;
+  e.out_hfield = w.d_hfield;
+  e.out_shape = w.d_shape;
+  e.out_tfh = w.d_tfh;
+  e.out_tfs = w.d_tfs;
+  for (size_t q0 = 0; q0 < total; q0 += chunk) {
+    const size_t m = std::min(chunk, total - q0);
+    e.q0 = q0;
+    e.m = uint32_t(m);
+    launch_terrain_expand(st, e, max_blocks);
+    hfcl_result* rec = d_out ? d_out + q0 : w.d_rec.get();
+    const int rc = hf_run(lib, w.d_hfield, w.d_shape, w.d_tfh, w.d_tfs, m, nullptr, req, q, skip_all, rec, d_bounds ? d_bounds + q0 : nullptr, d_contacts,
+                          contacts_cap, want_contacts, uint32_t(q0), q0 == 0, st);
+    if (rc) return rc;
+    if (fold) launch_terrain_status(st, rec, w.d_status.get() + q0, uint32_t(m), max_blocks);
+    if (h_out || h_bounds) {
+      if (h_out) HIP_TRY(hipMemcpyAsync(h_out + q0, rec, m * sizeof(hfcl_result), hipMemcpyDeviceToHost, st));
+      if (h_bounds) HIP_TRY(hipMemcpyAsync(h_bounds + q0, d_bounds + q0, m * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+    }
+  }
+  if (fold) {
+    TerrainFoldArgs f;
+    f.bounds = d_bounds;
+    f.status = w.d_status;
+    f.objects = s->d_terrain_objects;
+    f.n_conf = n_conf;
+    f.n_t = uint32_t(n_t);
+    f.summary = d_summary;
+    launch_terrain_fold(st, f, max_blocks);
+  }
+  HIP_TRY(hipGetLastError());
+  return HFCL_OK;
+}
+
 extern "C" {
 
 hfcl_scene* hfcl_scene_create(hfcl_lib* lib, const uint32_t* object_shape, size_t n_objects, const uint32_t* pairs, size_t n_pairs) {
@@ -1957,6 +2099,7 @@ hfcl_scene* hfcl_scene_create(hfcl_lib* lib, const uint32_t* object_shape, size_
   s->n_objects = n_objects;
   s->n_pairs = n_pairs;
   s->epoch = lib->shapes_epoch;
+  s->h_object_shape.assign(object_shape, object_shape + n_objects);
   if (scene_upload(s->d_object_shape, object_shape, n_objects) != HFCL_OK || scene_upload(s->d_pairs, pairs, 2 * n_pairs) != HFCL_OK) {
     set_error("HFCL_ERR_HIP: hfcl_scene_create: " + std::string(hfcl_last_error()));
     hfcl_scene_destroy(s);
@@ -2439,6 +2582,148 @@ int hfcl_scene_nearest_device_f32(hfcl_scene* s, const float* d_object_pose, siz
                                   hfcl_scene_summary* d_summary, hfcl_result_f32* d_min_records, size_t* n_evaluated, void* stream) {
   return nearest_device<float>("hfcl_scene_nearest_device_f32", s, d_object_pose, n_conf, req, upper_bound, d_summary, d_min_records, n_evaluated,
                                (hipStream_t)stream);
+}
+
+// ---- a height-field terrain under the moving objects (include/hppfcl_amd_terrain.h) ----------------------------------------------------
+int hfcl_scene_set_terrain(hfcl_scene* s, uint32_t hfield, const double* tf_terrain, const uint32_t* objects, size_t n_terrain_objects) {
+  if (const int no_device = hf_no_device()) return no_device;
+  const char* who = "hfcl_scene_set_terrain";
+  if (const int rc = groups_scene(who, s)) return rc;
+  hfcl_lib* lib = s->lib;
+  if (hfield >= lib->hf.h_fields.size()) {
+    set_error(std::string(who) + ": not a height field of the scene's library (hfcl_lib_add_hfield)");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (!tf_terrain) {
+    set_error(std::string(who) + ": null terrain pose");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  std::vector<uint32_t> list;
+  if (!objects) {
+    list.resize(s->rows());
+    for (size_t o = 0; o < list.size(); ++o) list[o] = uint32_t(o);
+  } else {
+    for (size_t k = 0; k < n_terrain_objects; ++k) {
+      if (objects[k] >= s->n_objects) {
+        set_error(std::string(who) + ": object index " + std::to_string(objects[k]) + " is outside the " + std::to_string(s->n_objects) + " objects");
+        return HFCL_ERR_INVALID_ARGUMENT;
+      }
+      if (k && objects[k] <= objects[k - 1]) {
+        set_error(std::string(who) + ": the object list must ascend strictly (entry " + std::to_string(k) + ")");
+        return HFCL_ERR_INVALID_ARGUMENT;
+      }
+    }
+    list.assign(objects, objects + n_terrain_objects);
+  }
+  for (const uint32_t o : list) {
+    const int32_t type = lib->h_shapes[s->h_object_shape[o]].type;
+    if (!hfcl_hfield_pair_supported(type)) {
+      set_error("Collision function between a height field and node type " + std::to_string(type) + " (object " + std::to_string(o) +
+                ") is not yet supported.");
+      return HFCL_ERR_UNSUPPORTED_PAIR;
+    }
+  }
+  HIP_TRY(hipSetDevice(lib->device));
+  DevBuf<uint32_t> d_list;
+  DevBuf<double> d_tf;
+  if (!list.empty())
+    if (const int rc = groups_upload(d_list, list.data(), list.size())) return rc;
+  if (const int rc = groups_upload(d_tf, tf_terrain, size_t(12))) return rc;
+  // (freeing the old list waits for the device: a query in flight on some stream may still be reading it)
+  s->d_terrain_objects = std::move(d_list);
+  s->d_terrain_tf = std::move(d_tf);
+  s->h_terrain_objects.swap(list);
+  s->terrain_hfield = hfield;
+  s->has_terrain = true;
+  return HFCL_OK;
+}
+int hfcl_scene_clear_terrain(hfcl_scene* s) {
+  if (const int no_device = hf_no_device()) return no_device;
+  if (const int rc = groups_scene("hfcl_scene_clear_terrain", s)) return rc;
+  HIP_TRY(hipSetDevice(s->lib->device));
+  s->d_terrain_objects.reset();  // (waits for the device)
+  s->d_terrain_tf.reset();
+  s->h_terrain_objects.clear();
+  s->has_terrain = false;
+  return HFCL_OK;
+}
+size_t hfcl_scene_n_terrain_objects(const hfcl_scene* s) { return s && s->has_terrain ? s->h_terrain_objects.size() : 0; }
+
+int hfcl_scene_collide_terrain_device(hfcl_scene* s, const double* d_moving_tf, size_t n_conf, const hfcl_collision_request* req, hfcl_result* d_out,
+                                      double* d_bounds, hfcl_scene_summary* d_summary, hfcl_contact* d_contacts, size_t max_contacts_total,
+                                      size_t* n_contacts_out, void* stream) {
+  if (const int no_device = hf_no_device()) return no_device;
+  QParams<double> q;
+  bool skip_all = false, nothing = true;
+  size_t total = 0;
+  if (const int rc = terrain_validate("hfcl_scene_collide_terrain_device", s, d_moving_tf, n_conf, req,
+                                      d_out || d_bounds || d_summary || d_contacts || n_contacts_out, n_contacts_out, q, skip_all, nothing, total))
+    return rc;
+  if (nothing) return HFCL_OK;
+  hfcl_lib* lib = s->lib;
+  HIP_TRY(hipSetDevice(lib->device));
+  hipStream_t st = (hipStream_t)stream;
+  const bool want_contacts = d_contacts || n_contacts_out;
+  if (const int rc = terrain_run(s, d_moving_tf, n_conf, req, q, skip_all, d_out, d_bounds, d_summary, d_contacts, max_contacts_total, want_contacts,
+                                 nullptr, nullptr, st))
+    return rc;
+  if (n_contacts_out && total) {
+    HIP_TRY(hipMemcpyAsync(lib->hf.h_words.get() + 1, lib->hf.d_running, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *n_contacts_out = size_t(lib->hf.h_words[1]);
+  }
+  return HFCL_OK;
+}
+
+int hfcl_scene_collide_terrain(hfcl_scene* s, const double* moving_tf, size_t n_conf, const hfcl_collision_request* req, hfcl_result* out,
+                               double* bounds, hfcl_scene_summary* summary, hfcl_contact* contacts, size_t max_contacts_total,
+                               size_t* n_contacts_out) {
+  if (const int no_device = hf_no_device()) return no_device;
+  const char* who = "hfcl_scene_collide_terrain";
+  QParams<double> q;
+  bool skip_all = false, nothing = true;
+  size_t total = 0;
+  if (const int rc = terrain_validate(who, s, moving_tf, n_conf, req, out || bounds || summary || contacts || n_contacts_out, n_contacts_out, q,
+                                      skip_all, nothing, total))
+    return rc;
+  if (nothing) return HFCL_OK;
+  hfcl_lib* lib = s->lib;
+  auto& hf = lib->hf;
+  HIP_TRY(hipSetDevice(lib->device));
+  if (!hf.st) HIP_TRY(hf.st.create());
+  hipStream_t st = hf.st;
+  if (total) {  // the table crosses the link once
+    const size_t bytes = n_conf * s->rows() * 12 * sizeof(double);
+    HIP_TRY(lib->scene.d_table.grow(bytes));
+    HIP_TRY(hipMemcpyAsync(lib->scene.d_table, moving_tf, bytes, hipMemcpyHostToDevice, st));
+  }
+  const bool want_contacts = contacts || n_contacts_out;
+  // the contact list of the whole call stays on the device until the last chunk has run (hfcl_hfield_collide_batch: at most what the queries can produce)
+  const size_t ccap = contacts ? std::min(max_contacts_total, total * size_t(std::min<uint64_t>(req->num_max_contacts, HF_ITEM_HARD_CAP))) : 0;
+  if (ccap) HIP_TRY(hf.s_contacts.grow(ccap));
+  if (summary) HIP_TRY(s->tw.d_summary.grow(n_conf));
+  int rc = terrain_run(s, static_cast<const double*>(lib->scene.d_table.get()), n_conf, req, q, skip_all, nullptr, nullptr,
+                       summary ? s->tw.d_summary.get() : nullptr, ccap ? hf.s_contacts.get() : nullptr, ccap, want_contacts, out, bounds, st);
+  if (!rc) {
+    bool ok = !summary || hipMemcpyAsync(summary, s->tw.d_summary, n_conf * sizeof(hfcl_scene_summary), hipMemcpyDeviceToHost, st) == hipSuccess;
+    if (ok && want_contacts && total) {
+      ok = hipMemcpyAsync(hf.h_words.get() + 1, hf.d_running, sizeof(uint64_t), hipMemcpyDeviceToHost, st) == hipSuccess;
+      ok = ok && hipStreamSynchronize(st) == hipSuccess;
+      if (ok) {
+        const size_t produced = size_t(hf.h_words[1]);
+        if (n_contacts_out) *n_contacts_out = produced;
+        const size_t stored = std::min(produced, ccap);
+        if (stored) ok = hipMemcpy(contacts, hf.s_contacts, stored * sizeof(hfcl_contact), hipMemcpyDeviceToHost) == hipSuccess;
+      }
+    }
+    ok = ok && hipStreamSynchronize(st) == hipSuccess;
+    if (!ok) {
+      set_error(std::string(who) + ": HIP copy failed");
+      rc = HFCL_ERR_HIP;
+    }
+  }
+  hipStreamSynchronize(st);
+  return rc;
 }
 
 }  // extern "C"

@@ -78,6 +78,11 @@ HFIELD_SYMBOLS = [
     "hfcl_hfield_build", "hfcl_lib_add_hfield", "hfcl_lib_hfield_count", "hfcl_lib_clear_hfields", "hfcl_hfield_local_aabb", "hfcl_hfield_pair_supported",
     "hfcl_hfield_collide_batch", "hfcl_hfield_collide_batch_device",
 ]
+# include/hppfcl_amd_terrain.h (included by hppfcl_amd.h): a height-field terrain under a scene's moving objects
+TERRAIN_SYMBOLS = [
+    "hfcl_scene_set_terrain", "hfcl_scene_clear_terrain", "hfcl_scene_n_terrain_objects", "hfcl_scene_collide_terrain",
+    "hfcl_scene_collide_terrain_device",
+]
 
 
 class EngineError(RuntimeError):
@@ -135,6 +140,8 @@ def dll():
             d.hfcl_scene_n_moving.restype = C.c_size_t
         if hasattr(d, "hfcl_lib_hfield_count"):
             d.hfcl_lib_hfield_count.restype = C.c_size_t
+        if hasattr(d, "hfcl_scene_n_terrain_objects"):
+            d.hfcl_scene_n_terrain_objects.restype = C.c_size_t
         _DLL = d
     return _DLL
 
@@ -1097,6 +1104,60 @@ class Scene:
 
     def distance_env_pairs_device_f32(self, d_moving_pose, n_conf, d_pairs, n_listed, d_conf_begin, req, d_out=None, d_summary=None, stream=0):
         self._env_pairs_device("distance", True, d_moving_pose, n_conf, d_pairs, n_listed, d_conf_begin, req, d_out, d_summary, None, None, stream)
+
+    # ---- a height-field terrain under the moving objects (include/hppfcl_amd_terrain.h) ----
+    @property
+    def n_terrain_objects(self):
+        """hfcl_scene_n_terrain_objects: the objects tested against the terrain; 0 when none is set."""
+        return int(dll().hfcl_scene_n_terrain_objects(self._h))
+
+    def set_terrain(self, hfield, tf, objects=None):
+        """hfcl_scene_set_terrain: height field `hfield` of the library (Library.add_hfield) at pose tf (12 doubles) is the ground under
+        the objects listed in `objects` -- strictly ascending object indices; None: every moving object.  Replaces a terrain set before."""
+        tf = np.ascontiguousarray(tf, dtype=np.float64).reshape(-1)
+        if tf.shape != (12,):
+            raise ValueError("tf: one pose row of 12 doubles")
+        if objects is None:
+            ids, n = None, 0
+        else:
+            ids = np.ascontiguousarray(objects, dtype=np.uint32).reshape(-1)
+            n = len(ids)
+            if n == 0:
+                ids = np.zeros(1, dtype=np.uint32)  # (an empty list, not "every object": the pointer must not be NULL)
+        _check(dll().hfcl_scene_set_terrain(self._h, C.c_uint32(int(hfield)), abi.ptr(tf), abi.ptr(ids), C.c_size_t(n)))
+
+    def clear_terrain(self):
+        _check(dll().hfcl_scene_clear_terrain(self._h))
+
+    def collide_terrain(self, moving_tf, req=None, records=True, bounds=True, max_contacts=0):
+        """hfcl_scene_collide_terrain on a (n_conf, n_moving, 12) table: query c * n_terrain_objects + k is the terrain against listed
+        object k under configuration c.  Returns (records or None, bounds or None, summaries, contacts[CONTACT_DTYPE], n_produced);
+        summaries[c]: min_distance the smallest bound of the configuration, min_pair / first_contact OBJECT indices."""
+        req = req or abi.default_collision_request()
+        tf = np.ascontiguousarray(moving_tf, dtype=np.float64)
+        k = self.n_moving
+        if tf.ndim < 2 or tf.shape[-1] != 12:
+            raise ValueError("pose table must have shape (n_conf, n_moving, 12)")
+        tf = tf.reshape(-1, k, 12) if k else tf.reshape(tf.shape[0] if tf.ndim == 3 else 0, 0, 12)
+        n_conf, n = len(tf), len(tf) * self.n_terrain_objects
+        out = np.zeros(n, dtype=abi.RESULT_DTYPE) if records else None
+        dlb = np.zeros(n) if bounds else None
+        summ = np.zeros(n_conf, dtype=abi.SCENE_SUMMARY_DTYPE)
+        contacts = np.zeros(int(max_contacts), dtype=abi.CONTACT_DTYPE)
+        nc = C.c_size_t(0)
+        _check(dll().hfcl_scene_collide_terrain(self._h, abi.ptr(tf), C.c_size_t(n_conf), C.byref(req), abi.ptr(out), abi.ptr(dlb), abi.ptr(summ),
+                                                abi.ptr(contacts) if max_contacts else None, C.c_size_t(int(max_contacts)), C.byref(nc)))
+        return out, dlb, summ, contacts[:min(nc.value, int(max_contacts))], int(nc.value)
+
+    def collide_terrain_device(self, d_moving_tf, n_conf, req, d_out=None, d_bounds=None, d_summary=None, d_contacts=None, max_contacts=0,
+                               want_count=False, stream=0):
+        """hfcl_scene_collide_terrain_device: torch tensors or raw device pointers, each output may be None.  Returns the number of
+        contacts produced when want_count (the call then waits for the stream once more), else None."""
+        nc = C.c_size_t(0)
+        _check(dll().hfcl_scene_collide_terrain_device(self._h, _dptr(d_moving_tf), C.c_size_t(int(n_conf)), C.byref(req), _dptr(d_out),
+                                                       _dptr(d_bounds), _dptr(d_summary), _dptr(d_contacts), C.c_size_t(int(max_contacts)),
+                                                       C.byref(nc) if want_count else None, C.c_void_p(stream)))
+        return int(nc.value) if want_count else None
 
     # ---- the per-configuration minimum distance with box-bound pruning (include/hppfcl_amd_nearest.h) ----
     def _nearest(self, object_tf, req, upper_bound, records, f32):

@@ -695,6 +695,46 @@ def hfield_terrain(n_queries=100_000, nx=256, ny=256, seed=1, cell=0.25, nper=16
     return HfieldTerrain(x_dim, y_dim, h, 0.0, lib, shape, tf_hfield, tf_shape, swapped)
 
 
+class SceneRobotTerrain:
+    """Chains of solids over a terrain (scene_robot_terrain): the terrain (an HfieldTerrain: field and ShapeLibrary), its pose (12
+    doubles), the shape of every link and the pose table (n_conf, n_links, 12)."""
+
+    def __init__(self, terrain, tf_terrain, object_shape, moving_tf):
+        self.terrain, self.tf_terrain, self.object_shape, self.moving_tf = terrain, tf_terrain, object_shape, moving_tf
+
+    def explicit(self):
+        """the same queries as the per-query arrays of Library.hfield_collide: (hfield, shape, tf_hfield, tf_shape), query c * n_links + k"""
+        n_conf, n_links = self.moving_tf.shape[:2]
+        n = n_conf * n_links
+        return (np.zeros(n, dtype=np.uint32), np.tile(self.object_shape, n_conf), np.repeat(self.tf_terrain.reshape(1, 12), n, axis=0),
+                np.ascontiguousarray(self.moving_tf.reshape(n, 12)))
+
+
+def scene_robot_terrain(n_conf=4096, n_links=24, side=256, seed=1, spacing=0.3):
+    """n_conf configurations of a chain of n_links solids (the kinds and sizes of hfield_terrain, `spacing` apart along a random heading)
+    laid over hfield_terrain's surface of side x side samples: every link sits above the ground under it by the configuration's own
+    clearance (0 to 0.5) plus a little of its own, under a random rotation, so that a share of the configurations touch the ground with
+    some of their links and the others clear it.  The terrain at the identity."""
+    t = hfield_terrain(n_queries=1, nx=side, ny=side, seed=seed)
+    rng = _rng(seed, 137)
+    ny, nx = t.heights.shape
+    object_shape = rng.integers(0, len(t.lib), n_links).astype(np.uint32)
+    heading = rng.uniform(0.0, 2 * np.pi, n_conf)
+    base = np.stack([rng.uniform(-0.4, 0.4, n_conf) * t.x_dim, rng.uniform(-0.4, 0.4, n_conf) * t.y_dim], axis=1)
+    along = (np.arange(n_links) - 0.5 * (n_links - 1)) * spacing
+    x = base[:, :1] + np.cos(heading)[:, None] * along[None, :]
+    y = base[:, 1:] + np.sin(heading)[:, None] * along[None, :]
+    u = np.clip(x / t.x_dim + 0.5, 0.01, 0.99)
+    v = np.clip(0.5 - y / t.y_dim, 0.01, 0.99)
+    ci, ri = np.minimum((u * (nx - 1)).astype(int), nx - 2), np.minimum((v * (ny - 1)).astype(int), ny - 2)
+    h = t.heights
+    ground = np.maximum.reduce([h[ri, ci], h[ri + 1, ci], h[ri, ci + 1], h[ri + 1, ci + 1]])
+    z = ground + rng.uniform(0.0, 0.5, (n_conf, 1)) + rng.uniform(0.05, 0.2, (n_conf, n_links))
+    T = np.stack([(u - 0.5) * t.x_dim, (0.5 - v) * t.y_dim, z], axis=2).reshape(-1, 3)
+    moving_tf = geometry.make_pose(quat=uniform_quaternions(rng, n_conf * n_links), T=T).reshape(n_conf, n_links, 12)
+    return SceneRobotTerrain(t, geometry.make_pose().reshape(12), object_shape, np.ascontiguousarray(moving_tf))
+
+
 def make_library(pkg, batch, device=0, options=None):
     """engine.Library for a batch (registers the batch's meshes, if any); options: {key: value} for hfcl_lib_set_option."""
     lib = pkg.Library(batch.lib, device=device, options=options)

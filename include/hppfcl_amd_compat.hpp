@@ -889,6 +889,24 @@ class HeightFieldBatch {
   void reset() {
     if (lib_ && generation_ == ctx_.libraryGeneration()) hfcl_lib_clear_hfields(lib_);
     fields_.clear();
+    ++epoch_;
+  }
+  /// counts the reset() calls: an index addField or libraryIndex returned before the last one is void
+  uint64_t epoch() const { return epoch_; }
+  /// The index of field k (addField) on the context's library as it is now; the field is registered there if it is not yet.
+  uint32_t libraryIndex(uint32_t k) {
+    hfcl_lib* lib = ctx_.library();
+    if (lib != lib_ || generation_ != ctx_.libraryGeneration()) {  // a new library (the first query, or the context was reset -- the new one
+      lib_ = lib;                                                 // may sit at the old address): nothing of ours is on it
+      generation_ = ctx_.libraryGeneration();
+      for (Entry& e : fields_) e.index = -1;
+    }
+    Entry& e = fields_.at(k);
+    if (e.index < 0) {
+      e.index = hfcl_lib_add_hfield(lib, e.x_dim, e.y_dim, e.heights.data(), e.rows, e.cols, e.min_height);
+      if (e.index < 0) throw std::invalid_argument(hfcl_last_error());
+    }
+    return static_cast<uint32_t>(e.index);
   }
   uint32_t addField(const HeightField<AABB>* f) {
     // The cache is keyed by address; a hit is only trusted if the field's CONTENT is still what was copied (addresses get reused once a
@@ -922,19 +940,9 @@ class HeightFieldBatch {
     if (tf_field.size() != n || tf_solid.size() != n || (!swapped.empty() && swapped.size() != n))
       throw std::invalid_argument("pairs/poses size mismatch");
     hfcl_lib* lib = ctx_.library();
-    if (lib != lib_ || generation_ != ctx_.libraryGeneration()) {  // a new library (the first query, or the context was reset -- the new one
-      lib_ = lib;                                                 // may sit at the old address): nothing of ours is on it
-      generation_ = ctx_.libraryGeneration();
-      for (Entry& e : fields_) e.index = -1;
-    }
     std::vector<uint32_t> hf(n), sh(n);
     for (size_t i = 0; i < n; ++i) {
-      Entry& e = fields_.at(field_solid[i].first);
-      if (e.index < 0) {
-        e.index = hfcl_lib_add_hfield(lib, e.x_dim, e.y_dim, e.heights.data(), e.rows, e.cols, e.min_height);
-        if (e.index < 0) throw std::invalid_argument(hfcl_last_error());
-      }
-      hf[i] = static_cast<uint32_t>(e.index);
+      hf[i] = libraryIndex(field_solid[i].first);
       sh[i] = field_solid[i].second;
     }
     const hfcl_collision_request a = to_abi(request);
@@ -966,6 +974,11 @@ class HeightFieldBatch {
   /// (the first contact's when there is one).
   void fill(CollisionResult& res, const hfcl_result& r, double bound, const CollisionGeometry* o1, const CollisionGeometry* o2, uint32_t query,
             size_t& k, const CollisionRequest& request) const {
+    fill(contacts_, res, r, bound, o1, o2, query, k, request);
+  }
+  /// ... with the contacts of a call made elsewhere (Scene::collideTerrain)
+  static void fill(const std::vector<hfcl_contact>& contacts_, CollisionResult& res, const hfcl_result& r, double bound, const CollisionGeometry* o1,
+                   const CollisionGeometry* o2, uint32_t query, size_t& k, const CollisionRequest& request) {
     while (k < contacts_.size() && contacts_[k].pair < query) ++k;
     if (HFCL_STATUS_SKIPPED(r.status)) return;
     if (bound < res.distance_lower_bound) {
@@ -1004,6 +1017,7 @@ class HeightFieldBatch {
   BatchQueries& ctx_;
   hfcl_lib* lib_ = nullptr;
   uint64_t generation_ = 0;  // ctx_.libraryGeneration() when lib_ was taken
+  uint64_t epoch_ = 0;
   std::vector<Entry> fields_;
   std::vector<hfcl_result> rec_;
   std::vector<double> bound_;
@@ -1946,7 +1960,106 @@ class Scene {
       if (clearances[c].min_i != 0xFFFFFFFFu) ctx_.fill((*results)[c], {shape_[clearances[c].min_i], shape_[clearances[c].min_j]}, rec_[c], g);
   }
 
+  /// A height-field terrain under the moving objects (hfcl_scene_set_terrain, include/hppfcl_amd_terrain.h): `field` at `tf` is the ground
+  /// under the objects listed in `objects` (strictly ascending indices), or under every moving object.  The field's heights are copied
+  /// now and again after updateHeights(); the field must stay alive while it is the terrain.  A scene of the default context registers the
+  /// field through the thread's default HeightFieldBatch, a scene of another context through a batch of its own.
+  void setTerrain(const HeightField<AABB>* field, const Transform3f& tf, const std::vector<uint32_t>& objects) { set_terrain(field, tf, objects, false); }
+  void setTerrain(const HeightField<AABB>* field, const Transform3f& tf) { set_terrain(field, tf, std::vector<uint32_t>(), true); }
+  void clearTerrain() {
+    ensure();
+    const int rc = hfcl_scene_clear_terrain(scene_);
+    if (rc) throw_for(rc);
+    has_terrain_ = false;
+    terrain_field_ = nullptr;
+  }
+  size_t numTerrainObjects() const { return hfcl_scene_n_terrain_objects(scene_); }
+  /// The terrain against its listed objects for n_conf tables of numMoving() transforms each: query c * numTerrainObjects() + k is
+  /// hpp::fcl::collide(field, tf, object o_k, moving_tables[c][o_k]).  results: nullptr or one fresh CollisionResult per query (every
+  /// contact up to num_max_contacts, distance_lower_bound); summaries: nullptr or one record per configuration -- min_distance the
+  /// smallest distance_lower_bound, min_pair / first_contact OBJECT indices, n_contacts > 0: isCollision() of the default callback.
+  void collideTerrain(const Transform3f* moving_tables, size_t n_conf, const CollisionRequest& request, std::vector<CollisionResult>* results,
+                      std::vector<hfcl_scene_summary>* summaries) {
+    ensure();
+    if (!has_terrain_) throw std::invalid_argument("Scene::collideTerrain: no terrain set");
+    if (terrain_epoch_ != terrain_batch().epoch() || terrain_version_ != terrain_field_->version()) apply_terrain();
+    const hfcl_collision_request a = to_abi(request);
+    const size_t n_t = numTerrainObjects(), n = n_conf * n_t;
+    if (summaries) summaries->resize(n_conf);
+    if (!results) {
+      const int rc = hfcl_scene_collide_terrain(scene_, reinterpret_cast<const double*>(moving_tables), n_conf, &a, nullptr, nullptr,
+                                                summaries ? summaries->data() : nullptr, nullptr, 0, nullptr);
+      if (rc == HFCL_ERR_LIMIT) throw std::invalid_argument(hfcl_last_error());
+      if (rc) throw_for(rc);
+      return;
+    }
+    rec_.resize(n);
+    terrain_bound_.resize(n);
+    size_t cap = std::max<size_t>(64, 4 * n), produced = 0;
+    int rc = HFCL_OK;
+    for (int attempt = 0; attempt < 2; ++attempt) {  // (a list that outgrew the guess: once more with the count)
+      terrain_contacts_.resize(cap);
+      rc = hfcl_scene_collide_terrain(scene_, reinterpret_cast<const double*>(moving_tables), n_conf, &a, rec_.data(), terrain_bound_.data(),
+                                      summaries ? summaries->data() : nullptr, terrain_contacts_.data(), cap, &produced);
+      if (rc || produced <= cap) break;
+      cap = produced;
+    }
+    if (rc == HFCL_ERR_LIMIT) throw std::invalid_argument(hfcl_last_error());
+    if (rc) throw_for(rc);
+    terrain_contacts_.resize(std::min(produced, cap));
+    results->assign(n, CollisionResult());
+    std::vector<uint32_t> listed(terrain_objects_);
+    if (terrain_all_) {
+      listed.resize(n_t);
+      for (size_t k = 0; k < n_t; ++k) listed[k] = static_cast<uint32_t>(k);
+    }
+    size_t k = 0;
+    for (size_t q = 0; q < n; ++q)
+      HeightFieldBatch::fill(terrain_contacts_, (*results)[q], rec_[q], terrain_bound_[q], terrain_field_,
+                             objects_[listed[q % n_t]]->collisionGeometryPtr(), static_cast<uint32_t>(q), k, request);
+  }
+  const std::vector<double>& terrainBounds() const { return terrain_bound_; }
+  const std::vector<hfcl_contact>& terrainContacts() const { return terrain_contacts_; }
+
  private:
+  HeightFieldBatch& terrain_batch() {
+    if (&ctx_ == &default_context()) return default_hfield_batch();
+    if (!own_hfields_) own_hfields_.reset(new HeightFieldBatch(ctx_));
+    return *own_hfields_;
+  }
+  void set_terrain(const HeightField<AABB>* field, const Transform3f& tf, const std::vector<uint32_t>& objects, bool all) {
+    ensure();
+    const HeightField<AABB>* old_field = terrain_field_;
+    const Transform3f old_tf = terrain_tf_;
+    std::vector<uint32_t> old_objects = objects;
+    old_objects.swap(terrain_objects_);
+    const bool old_all = terrain_all_, old_has = has_terrain_;
+    terrain_field_ = field;
+    terrain_tf_ = tf;
+    terrain_all_ = all;
+    try {
+      apply_terrain();
+    } catch (...) {  // (a refused terrain sets nothing: the one before stays)
+      terrain_field_ = old_field;
+      terrain_tf_ = old_tf;
+      terrain_objects_.swap(old_objects);
+      terrain_all_ = old_all;
+      has_terrain_ = old_has;
+      throw;
+    }
+    has_terrain_ = true;
+  }
+  void apply_terrain() {  // the device scene is there (ensure)
+    HeightFieldBatch& hb = terrain_batch();
+    const uint32_t index = hb.libraryIndex(hb.addField(terrain_field_));
+    static const uint32_t none = 0;  // (an empty list is a non-null pointer and a count of 0)
+    const int rc = hfcl_scene_set_terrain(scene_, index, reinterpret_cast<const double*>(&terrain_tf_),
+                                          terrain_all_ ? nullptr : (terrain_objects_.empty() ? &none : terrain_objects_.data()), terrain_objects_.size());
+    if (rc == HFCL_ERR_UNSUPPORTED_PAIR) throw std::invalid_argument(hfcl_last_error());
+    if (rc) throw_for(rc);
+    terrain_epoch_ = hb.epoch();
+    terrain_version_ = terrain_field_->version();
+  }
   size_t list_guess(size_t n_conf) const {
     const size_t total = n_conf * numPairs();
     return std::min(total, std::max<size_t>(total / 8, 1024));
@@ -2020,6 +2133,7 @@ class Scene {
       const int rc = hfcl_scene_set_environment(scene_, n_moving_, reinterpret_cast<const double*>(env_.data()));
       if (rc) throw_for(rc);
     }
+    if (has_terrain_) apply_terrain();  // (the terrain of the scene before)
   }
   std::vector<Transform3f> current() const {
     std::vector<Transform3f> t(objects_.size());
@@ -2040,6 +2154,15 @@ class Scene {
   size_t geometries_ = 0;
   std::vector<hfcl_result> rec_;
   std::vector<hfcl_guess> guess_;
+  const HeightField<AABB>* terrain_field_ = nullptr;  // setTerrain: kept for a scene made again, and for updated heights
+  Transform3f terrain_tf_;
+  std::vector<uint32_t> terrain_objects_;
+  bool terrain_all_ = false, has_terrain_ = false;
+  uint64_t terrain_epoch_ = 0;
+  unsigned int terrain_version_ = 0;
+  std::unique_ptr<HeightFieldBatch> own_hfields_;
+  std::vector<double> terrain_bound_;
+  std::vector<hfcl_contact> terrain_contacts_;
 };
 }  // namespace amd
 
