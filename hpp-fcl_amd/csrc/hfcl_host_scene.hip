@@ -146,24 +146,30 @@ static int scene_validate_core(const char* who, const hfcl_scene* s, const void*
   total = n_conf * s->n_pairs;
   return HFCL_OK;
 }
-// everything a scene call refuses before any work; total: n_conf * n_pairs (0: nothing to do).  Of a scene that is there, the request (a
-// null one: "null request", setup_collide / setup_distance) and the outputs are looked at before the scene's state
+// Of a scene that is there, a narrow-phase call looks at the request (a null one: "null request", setup_collide / setup_distance) and at
+// the outputs before the scene's state; a null scene is refused after this
+template <typename T>
+static int scene_request_and_outputs(const char* who, const hfcl_scene* s, const hfcl_collision_request* creq, const hfcl_distance_request* dreq,
+                                     const void* out, const void* summary) {
+  if (!s) return HFCL_OK;
+  QParams<T> q;
+  bool skip;
+  const int rc = creq ? setup_collide<T>(creq, q, skip) : setup_distance<T>(dreq, q);
+  if (rc) return rc;
+  if (!out && !summary) {
+    set_error(std::string(who) + ": records and summaries both NULL");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  return HFCL_OK;
+}
+// everything a scene call refuses before any work; total: n_conf * n_pairs (0: nothing to do)
 template <typename T>
 static int scene_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, const hfcl_collision_request* creq,
                           const hfcl_distance_request* dreq, const void* out, const void* summary, size_t& total,
                           size_t hfcl_scene::*nothing_if_zero = &hfcl_scene::n_pairs) {
   total = 0;
-  if (s) {
-    QParams<T> q;
-    bool skip;
-    const int rc = creq ? setup_collide<T>(creq, q, skip) : setup_distance<T>(dreq, q);
-    if (rc) return rc;
-    if (!out && !summary) {
-      set_error(std::string(who) + ": records and summaries both NULL");
-      return HFCL_ERR_INVALID_ARGUMENT;
-    }
-  }
-  return scene_validate_core<T>(who, s, table, n_conf, nothing_if_zero, total, nothing_if_zero == &hfcl_scene::n_pairs);
+  const int rc = scene_request_and_outputs<T>(who, s, creq, dreq, out, summary);
+  return rc ? rc : scene_validate_core<T>(who, s, table, n_conf, nothing_if_zero, total, nothing_if_zero == &hfcl_scene::n_pairs);
 }
 // what the cull calls refuse before any work; total: n_conf * n_pairs (0: no query)
 template <typename T>
@@ -196,24 +202,38 @@ static int scene_workspace(hfcl_lib* lib, size_t m, int recs, bool gin, int gout
   HIP_TRY(w.d_partials.grow(pieces));
   return HFCL_OK;
 }
-// A list of flat queries on the device, as hfcl_scene_cull_device leaves it: ascending ids, conf_begin theirs.  Where a function takes a
-// pointer to one, nullptr is the flat range itself.
-// The other flavour (hfcl_scene_self_pairs_device leaves it): d_ids == nullptr, the entries are the pairs (i, j) themselves (d_pairs, two
-// words an entry), the scene's own pair list plays no part, an entry's pair index in the summaries is its rank in its configuration, and a
-// configuration has at most `shares` fold pieces (hfcl_pairs.hpp: pairs_shares).
+// How the list a call works on comes about -- named once, here, wherever a flavour is meant (SceneList, SceneCull, the functions on a
+// list of pairs): culled from the scene's own pair list (hfcl_scene_cull*), made by the all-pairs sweep (hfcl_scene_self_pairs*), made by
+// the sweep of the moving objects against a kept environment (hfcl_scene_env_pairs*)
+enum class ListKind { Culled, Self, Env };
+// A list of flat queries on the device, as hfcl_scene_cull_device leaves it (Culled): ascending ids, conf_begin theirs.  Where a function
+// takes a pointer to one, nullptr is the flat range itself.
+// The other flavour (Self: hfcl_scene_self_pairs_device leaves it): d_ids == nullptr, the entries are the pairs (i, j) themselves (d_pairs,
+// two words an entry), the scene's own pair list plays no part, an entry's pair index in the summaries is its rank in its configuration,
+// and a configuration has at most `shares` fold pieces (hfcl_pairs.hpp: pairs_shares).
+// ... of a scene with an environment (Env: hfcl_scene_env_pairs_device leaves it): the call's table holds n_moving rows a configuration,
+// the rows of j >= n_moving come from d_env_table.
+// Made by query_list / pair_list below, nowhere else.
 struct SceneList {
+  ListKind kind;
   const uint64_t* d_ids;
   const uint64_t* d_conf_begin;
   size_t n_conf;
-  const uint32_t* d_pairs = nullptr;
-  uint32_t shares = 0;
-  bool ranked() const { return d_pairs != nullptr; }
-  // ... of a scene with an environment (hfcl_scene_env_pairs_device leaves it): the call's table holds n_moving rows a configuration,
-  // the rows of j >= n_moving come from d_env_table
-  bool env = false;
-  const void* d_env_table = nullptr;
-  size_t n_moving = 0;
+  const uint32_t* d_pairs;
+  uint32_t shares;
+  const void* d_env_table;
+  size_t n_moving;
+  bool ranked() const { return kind != ListKind::Culled; }
 };
+static SceneList query_list(const uint64_t* d_ids, const uint64_t* d_conf_begin, size_t n_conf) {
+  return SceneList{ListKind::Culled, d_ids, d_conf_begin, n_conf, nullptr, 0u, nullptr, 0};
+}
+// kind: Self or Env; n_listed > 0 entries at d_pairs
+static SceneList pair_list(const hfcl_scene* s, ListKind kind, const uint32_t* d_pairs, const uint64_t* d_conf_begin, size_t n_conf, size_t n_listed) {
+  if (kind == ListKind::Env)
+    return SceneList{kind, nullptr, d_conf_begin, n_conf, d_pairs, uint32_t(env_shares(n_listed, s->n_moving, s->n_env())), s->d_env_table.get(), s->n_moving};
+  return SceneList{kind, nullptr, d_conf_begin, n_conf, d_pairs, uint32_t(pairs_shares(n_listed, s->n_objects)), nullptr, 0};
+}
 // fold pieces of a configuration of a call
 static uint32_t scene_list_shares(const hfcl_scene* s, const SceneList* list) {
   return list && list->ranked() ? list->shares : scene_shares(uint32_t(s->n_pairs));
@@ -248,7 +268,7 @@ static int scene_chunk_run(hfcl_scene* s, const void* d_table, const SceneList* 
   ea.s2 = w.d_s2;
   ea.tf1 = w.d_tf1;
   ea.tf2 = w.d_tf2;
-  if (list && list->ranked() && list->env) {
+  if (list && list->kind == ListKind::Env) {
     ea.n_objects = list->n_moving;
     launch_scene_expand_env(st, ea, list->d_pairs, list->d_conf_begin, list->n_conf, k0, list->d_env_table, f32, max_blocks);
   } else if (list && list->ranked())
@@ -675,13 +695,14 @@ static int scene_listed_device(const char* who, hfcl_scene* s, const void* d_tab
     HIP_TRY(hipGetLastError());
     return HFCL_OK;
   }
-  const SceneList list{d_ids, d_conf_begin, n_conf};
+  const SceneList list = query_list(d_ids, d_conf_begin, n_conf);
   return scene_chunks_device<T>(s, d_table, &list, n_listed, creq, dreq, d_out, d_summary, d_gin, d_gout, st, counts);
 }
 
 // ---------------------------------------------------------------------------------------
-// The self-collision pairs per configuration (include/hppfcl_amd_pairs.h: hfcl_scene_self_pairs*), and the scene calls on such a list
-// (hfcl_scene_*_pairs_device*, hfcl_scene_*_self).  hfcl_k_pairs.hip has the kernels, hfcl_pairs.hpp the arithmetic.
+// The self-collision pairs per configuration (include/hppfcl_amd_pairs.h: hfcl_scene_self_pairs*): what is the all-pairs sweep's own.  The
+// list maker and the scene calls on such a list (hfcl_scene_*_pairs_device*, hfcl_scene_*_self) are one with the environment's: further
+// down, "A list of pairs made on the device, of either kind".  hfcl_k_pairs.hip has the kernels, hfcl_pairs.hpp the arithmetic.
 // ---------------------------------------------------------------------------------------
 // every entry point of hppfcl_amd_pairs.h, before anything else
 static int pairs_need_device() {
@@ -789,145 +810,33 @@ static void pairs_chunks(PairsArgs& a, const hfcl_scene* s, const void* d_table,
   }
 }
 
-// The list of the whole table on st: the pairs (below `capacity`), conf_begin, the count.  Nothing is read back.
-template <typename T>
-static int self_pairs_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, double inflate, uint32_t* d_pairs, size_t capacity,
-                             uint64_t* d_conf_begin, uint64_t* d_n_listed, hipStream_t st) {
-  int rc = self_validate<T>(who, s, d_table, n_conf);
-  if (rc) return rc;
-  rc = cull_check_inflate(who, inflate);
-  if (rc) return rc;
-  if (!d_n_listed) {
-    set_error(std::string(who) + ": null count");
-    return HFCL_ERR_INVALID_ARGUMENT;
+// The all-pairs sweep of a call over n_conf configurations, planned once (hfcl_plan.hpp: self_sweep_plan): the list maker and the
+// clearance walk the same chunks with the same buffers
+struct SelfSweep {
+  hfcl_scene* s = nullptr;
+  SelfSweepPlan p;
+  // the plan; the boxes of the configurations a chunk touches, a chunk's row arrays
+  int ready(hfcl_scene* scene, size_t n_conf) {
+    s = scene;
+    hfcl_lib* lib = s->lib;
+    const uint32_t n = uint32_t(s->n_objects);
+    p = self_sweep_plan(n, n_conf, lib->opt.scene_pairs_small_max, lib->opt.scene_cull_chunk);
+    HIP_TRY(lib->scene.d_boxes.grow(p.conf_per_chunk * n * 6));
+    return pairs_chunk_buffers(lib, size_t(p.chunk_rows));
   }
-  rc = self_pairs_limits(who, s);
-  if (rc) return rc;
-  hfcl_lib* lib = s->lib;
-  HIP_TRY(hipSetDevice(lib->device));
-  if (n_conf == 0 || s->n_objects < 2) {  // no pair: an empty list
-    HIP_TRY(hipMemsetAsync(d_n_listed, 0, sizeof(uint64_t), st));
-    if (d_conf_begin) HIP_TRY(hipMemsetAsync(d_conf_begin, 0, (n_conf + 1) * sizeof(uint64_t), st));
-    return HFCL_OK;
+  // what does not depend on the caller: inflate 0, no list
+  void args(PairsArgs& a, size_t n_conf) const { pairs_args(a, s, p.geo, p.small, n_conf); }
+  // the chunks in turn on st: a chunk's boxes, then launch() with a's chunk members set
+  template <typename T, typename F>
+  void walk(PairsArgs& a, const void* d_table, hipStream_t st, F&& launch) const {
+    pairs_chunks<T>(a, s, d_table, p.geo, p.n_blocks, p.per, st, launch);
   }
-  rc = ensure_local_boxes(lib);
-  if (rc) return rc;
-  hfcl_lib::SceneWs& w = lib->scene;
-  const uint32_t n = uint32_t(s->n_objects);
-  const bool small = n <= std::min(lib->opt.scene_pairs_small_max, PAIRS_SMALL_MAX);
-  const PairsGeometry geo = pairs_geometry(n, small);
-  const uint64_t n_blocks = uint64_t(n_conf) * geo.blocks_per_conf;
-  const uint64_t per = pairs_chunk_blocks(geo, n_blocks, lib->opt.scene_cull_chunk);
-  const size_t conf_per_chunk = std::min<size_t>(n_conf, size_t(per / geo.blocks_per_conf) + 2);
-  HIP_TRY(w.d_boxes.grow(conf_per_chunk * n * 6));
-  rc = pairs_chunk_buffers(lib, size_t(std::min<uint64_t>(per * geo.rows_per_block, uint64_t(n_conf) * n)));
-  if (rc) return rc;
-  PairsArgs a;
-  pairs_args(a, s, geo, small, n_conf);
-  a.inflate = inflate;
-  a.pairs = d_pairs;
-  a.capacity = d_pairs ? capacity : 0;
-  a.conf_begin = d_conf_begin;
-  a.n_listed = d_n_listed;
-  pairs_chunks<T>(a, s, d_table, geo, n_blocks, per, st, [&]() { launch_pairs_chunk(st, a); });
-  HIP_TRY(hipGetLastError());
-  return HFCL_OK;
-}
-
-// entries a list of self pairs of `rows` rows is first given room for (a longer one is made again in a buffer of its size)
-static size_t pairs_capacity_guess(size_t rows) { return std::max<size_t>(16 * rows, 4096); }
-// The list of a table that is on the device into the library's own (w.d_pair_list, w.d_conf_begin), and the one read-back: the count.
-template <typename T>
-static int self_pairs_into_workspace(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, double inflate, bool want_pairs,
-                                     uint64_t& n_listed) {
-  hfcl_lib* lib = s->lib;
-  hfcl_lib::SceneWs& w = lib->scene;
-  HIP_TRY(w.d_conf_begin.grow(n_conf + 1));
-  HIP_TRY(w.d_running.grow(2));
-  if (want_pairs) HIP_TRY(w.d_pair_list.grow(2 * pairs_capacity_guess(n_conf * s->n_objects)));
-  return list_and_count(w.d_pair_list, want_pairs, w.d_running + 1, w.s_cmp, n_listed, [&]() {
-    return self_pairs_device<T>(who, s, d_table, n_conf, inflate, want_pairs ? w.d_pair_list.get() : nullptr, w.d_pair_list.capacity() / 2,
-                                w.d_conf_begin, w.d_running + 1, w.s_cmp);
-  }, 2);
-}
-
-template <typename T>
-static int self_pairs_host(const char* who, hfcl_scene* s, const void* table, size_t n_conf, double inflate, uint32_t* pairs, size_t capacity,
-                           uint64_t* conf_begin, size_t* n_listed) {
-  int rc = self_validate<T>(who, s, table, n_conf);
-  if (!rc) rc = cull_check_inflate(who, inflate);
-  if (!rc && !n_listed) {
-    set_error(std::string(who) + ": null count");
-    rc = HFCL_ERR_INVALID_ARGUMENT;
-  }
-  if (!rc) rc = self_pairs_limits(who, s);
-  if (rc) return rc;
-  *n_listed = 0;
-  if (n_conf == 0 || s->n_objects < 2) {
-    if (conf_begin) memset(conf_begin, 0, (n_conf + 1) * sizeof(uint64_t));
-    return HFCL_OK;
-  }
-  hfcl_lib* lib = s->lib;
-  hfcl_lib::SceneWs& w = lib->scene;
-  HIP_TRY(hipSetDevice(lib->device));
-  rc = scene_host_stream(w);
-  if (!rc) rc = scene_table_in(w, table, n_conf * s->n_objects * SceneTypes<T>::WIDTH * sizeof(T));
-  uint64_t n = 0;
-  if (!rc) rc = self_pairs_into_workspace<T>(who, s, w.d_table, n_conf, inflate, pairs != nullptr, n);
-  if (rc) {
-    hipStreamSynchronize(w.s_cmp);
-    return rc;
-  }
-  *n_listed = size_t(n);
-  if (pairs && capacity < n) {
-    set_error(std::string(who) + ": " + std::to_string(n) + " pairs are listed, the list holds " + std::to_string(capacity));
-    return HFCL_ERR_LIMIT;
-  }
-  if (pairs && n) HIP_TRY(hipMemcpyAsync(pairs, w.d_pair_list, n * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, w.s_cmp));
-  if (conf_begin) HIP_TRY(hipMemcpyAsync(conf_begin, w.d_conf_begin, (n_conf + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
-  HIP_TRY(hipStreamSynchronize(w.s_cmp));
-  return HFCL_OK;
-}
-
-// The device form on a list of pairs.  The list is not checked: i < j < n_objects, conf_begin its spans -- as hfcl_scene_self_pairs_device
-// leaves them.  counts: as scene_chunks_device takes them.
-template <typename T>
-static int scene_pairs_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const uint32_t* d_pairs, size_t n_listed,
-                              const uint64_t* d_conf_begin, const hfcl_collision_request* creq, const hfcl_distance_request* dreq,
-                              typename SceneTypes<T>::R* d_out, hfcl_scene_summary* d_summary, const hfcl_guess* d_gin, hfcl_guess* d_gout,
-                              hipStream_t st, SceneCountSlots* counts = nullptr) {
-  size_t total;
-  int rc = scene_validate<T>(who, s, d_table, n_conf, creq, dreq, d_out, d_summary, total, &hfcl_scene::n_objects);
-  if (rc) return rc;
-  if (n_conf == 0 || s->n_objects == 0) {
-    if (n_listed) {
-      set_error(std::string(who) + ": list entries without a configuration or an object");
-      return HFCL_ERR_INVALID_ARGUMENT;
-    }
-    return HFCL_OK;
-  }
-  if (n_listed && (!d_pairs || !d_conf_begin)) {
-    set_error(std::string(who) + ": null list / conf_begin");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  if (d_summary && (rc = pairs_rank_limit(who, n_listed, s->n_objects))) return rc;
-  hfcl_lib* lib = s->lib;
-  HIP_TRY(hipSetDevice(lib->device));
-  if (d_summary) launch_scene_summary_init(st, d_summary, n_conf, lib->n_cus * 16);
-  if (!n_listed) {
-    HIP_TRY(hipGetLastError());
-    return HFCL_OK;
-  }
-  SceneList list{nullptr, d_conf_begin, n_conf};
-  list.d_pairs = d_pairs;
-  list.shares = uint32_t(pairs_shares(n_listed, s->n_objects));
-  return scene_chunks_device<T>(s, d_table, &list, n_listed, creq, dreq, d_out, d_summary, d_gin, d_gout, st, counts);
-}
+};
 
 // ---------------------------------------------------------------------------------------
-// A static environment kept on the device (include/hppfcl_amd_env.h): the pairs of the moving objects among themselves and against the
-// environment per configuration (hfcl_scene_env_pairs*), and the scene calls on such a list (hfcl_scene_*_env_pairs_device*,
-// hfcl_scene_*_env).  hfcl_k_env.hip has the kernels, hfcl_env.hpp the arithmetic.
+// A static environment kept on the device (include/hppfcl_amd_env.h): what is its own of the pairs of the moving objects among themselves
+// and against the environment per configuration (hfcl_scene_env_pairs*) -- the validator, the limits, the setter, the sweep.
+// hfcl_k_env.hip has the kernels, hfcl_env.hpp the arithmetic.
 // ---------------------------------------------------------------------------------------
 // What every _env call refuses before any work, in this order: a null scene, a stale one, no environment, one of the other precision, a
 // null table (with something to do), an overflow.  nothing: n_conf == 0 or no moving object -- HFCL_OK before the table is looked at.
@@ -961,17 +870,8 @@ template <typename T>
 static int env_scene_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, const hfcl_collision_request* creq,
                               const hfcl_distance_request* dreq, const void* out, const void* summary, bool& nothing) {
   nothing = true;
-  if (s) {
-    QParams<T> q;
-    bool skip;
-    const int rc = creq ? setup_collide<T>(creq, q, skip) : setup_distance<T>(dreq, q);
-    if (rc) return rc;
-    if (!out && !summary) {
-      set_error(std::string(who) + ": records and summaries both NULL");
-      return HFCL_ERR_INVALID_ARGUMENT;
-    }
-  }
-  return env_validate<T>(who, s, table, n_conf, nothing);
+  const int rc = scene_request_and_outputs<T>(who, s, creq, dreq, out, summary);
+  return rc ? rc : env_validate<T>(who, s, table, n_conf, nothing);
 }
 static int env_limits(const char* who, const hfcl_scene* s) {
   if (s->n_moving > ENV_MAX_OBJECTS || s->n_env() > ENV_MAX_OBJECTS) {
@@ -1047,12 +947,89 @@ static int env_set(const char* who, hfcl_scene* s, size_t n_moving, const T* env
   return env_tile_groups(s);
 }
 
-// The env list of the whole moving table on st: the pairs (below `capacity`), conf_begin, the count.  Nothing is read back.
+// The sweep of the moving rows of n_conf configurations against their own and the environment's columns, planned once (hfcl_plan.hpp:
+// env_sweep_plan): the list maker and the clearance walk the same cells with the same buffers
+struct EnvSweep {
+  hfcl_scene* s = nullptr;
+  EnvSweepPlan p;
+  // the plan; the boxes of the moving rows of the configurations a chunk touches, a chunk's (row, span) arrays
+  int ready(hfcl_scene* scene, size_t n_conf) {
+    s = scene;
+    hfcl_lib* lib = s->lib;
+    const uint32_t nm = uint32_t(s->n_moving);
+    p = env_sweep_plan(nm, uint32_t(s->n_env()), n_conf, lib->opt.scene_env_span, lib->n_cus, lib->opt.scene_cull_chunk);
+    HIP_TRY(lib->scene.d_boxes.grow(p.conf_per_chunk * nm * 6));
+    return pairs_chunk_buffers(lib, size_t(p.scan_rows));
+  }
+  // what does not depend on the caller: inflate 0, no list
+  void args(EnvArgs& a, size_t n_conf) const {
+    const uint32_t nm = p.geo.n_moving;
+    pairs_args(a.p, s, p.rows, false, n_conf);
+    a.p.tile_groups = nullptr;
+    a.p.n_objects = nm * p.geo.n_spans;  // (the scan's rows: (row, span) counts, row-major)
+    a.p.total_rows = uint64_t(n_conf) * nm * p.geo.n_spans;
+    a.n_moving = nm;
+    a.n_env = p.geo.n_env;
+    a.tiles_moving = p.geo.tiles_moving;
+    a.tiles = p.geo.tiles;
+    a.span_len = p.geo.span_len;
+    a.n_spans = p.geo.n_spans;
+    a.blocks_per_conf = p.rows.blocks_per_conf;
+    a.env_boxes = s->d_env_boxes;
+    a.env_tile_boxes = s->d_env_tile_boxes;
+    a.col_tile_groups = s->n_groups ? s->d_env_tile_groups.get() : nullptr;
+  }
+  // the chunks in turn on st: the boxes of a chunk's moving rows (the first n_moving objects' shapes), then launch() with a's chunk
+  // members set -- the scan's rows are the chunk's rows times the spans
+  template <typename T, typename F>
+  void walk(EnvArgs& a, const void* d_table, hipStream_t st, F&& launch) const {
+    pairs_chunks<T>(a.p, s, d_table, p.rows, p.n_blocks, p.per, st, [&]() {
+      a.row0 = a.p.row0;
+      a.p.row0 = a.row0 * p.geo.n_spans;
+      a.p.n_rows = uint32_t(uint64_t(a.p.n_rows) * p.geo.n_spans);
+      launch();
+    });
+  }
+};
+
+// ---------------------------------------------------------------------------------------
+// A list of pairs made on the device, of either kind (ListKind::Self / ListKind::Env): what differs between the two, then the forms that
+// are one for both -- the list into the library's workspace, the host form, the narrow phase on such a list.
+// ---------------------------------------------------------------------------------------
+// pose rows a configuration of the call's table has
+static size_t pair_rows(const hfcl_scene* s, ListKind kind) { return kind == ListKind::Env ? s->n_moving : s->n_objects; }
+static int pair_limits(const char* who, const hfcl_scene* s, ListKind kind) {
+  return kind == ListKind::Env ? env_limits(who, s) : self_pairs_limits(who, s);
+}
+static int pair_rank_limit(const char* who, uint64_t n_listed, const hfcl_scene* s, ListKind kind) {
+  return kind == ListKind::Env ? env_rank_limit(who, n_listed, s) : pairs_rank_limit(who, n_listed, s->n_objects);
+}
+// What a maker of such a list refuses of the scene and the table; nothing: the list is empty whatever the table holds -- n_conf == 0, or
+// fewer than two objects (Self; a scene of ONE object still has its table refused when it is null) / no moving object (Env)
 template <typename T>
-static int env_pairs_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, double inflate, uint32_t* d_pairs, size_t capacity,
-                            uint64_t* d_conf_begin, uint64_t* d_n_listed, hipStream_t st) {
+static int pair_validate(ListKind kind, const char* who, const hfcl_scene* s, const void* table, size_t n_conf, bool& nothing) {
+  if (kind == ListKind::Env) return env_validate<T>(who, s, table, n_conf, nothing);
+  const int rc = self_validate<T>(who, s, table, n_conf);
+  nothing = rc || n_conf == 0 || s->n_objects < 2;
+  return rc;
+}
+// ... and a narrow-phase call on one: of a scene that is there, the request and the outputs first
+template <typename T>
+static int pair_scene_validate(ListKind kind, const char* who, const hfcl_scene* s, const void* table, size_t n_conf, const hfcl_collision_request* creq,
+                               const hfcl_distance_request* dreq, const void* out, const void* summary, bool& nothing) {
+  if (kind == ListKind::Env) return env_scene_validate<T>(who, s, table, n_conf, creq, dreq, out, summary, nothing);
+  size_t total;
+  const int rc = scene_validate<T>(who, s, table, n_conf, creq, dreq, out, summary, total, &hfcl_scene::n_objects);
+  nothing = rc || n_conf == 0 || s->n_objects < 2;
+  return rc;
+}
+// The list of the whole table on st (hfcl_scene_self_pairs_device*, hfcl_scene_env_pairs_device*): the pairs (below `capacity`),
+// conf_begin, the count.  Nothing is read back.
+template <typename T>
+static int pairs_device(ListKind kind, const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, double inflate, uint32_t* d_pairs,
+                        size_t capacity, uint64_t* d_conf_begin, uint64_t* d_n_listed, hipStream_t st) {
   bool nothing;
-  int rc = env_validate<T>(who, s, d_table, n_conf, nothing);
+  int rc = pair_validate<T>(kind, who, s, d_table, n_conf, nothing);
   if (rc) return rc;
   rc = cull_check_inflate(who, inflate);
   if (rc) return rc;
@@ -1060,7 +1037,7 @@ static int env_pairs_device(const char* who, hfcl_scene* s, const void* d_table,
     set_error(std::string(who) + ": null count");
     return HFCL_ERR_INVALID_ARGUMENT;
   }
-  rc = env_limits(who, s);
+  rc = pair_limits(who, s, kind);
   if (rc) return rc;
   hfcl_lib* lib = s->lib;
   HIP_TRY(hipSetDevice(lib->device));
@@ -1071,76 +1048,62 @@ static int env_pairs_device(const char* who, hfcl_scene* s, const void* d_table,
   }
   rc = ensure_local_boxes(lib);
   if (rc) return rc;
-  hfcl_lib::SceneWs& w = lib->scene;
-  const uint32_t nm = uint32_t(s->n_moving), ne = uint32_t(s->n_env());
-  const PairsGeometry rows = pairs_geometry(nm, false);
-  const uint64_t n_blocks = uint64_t(n_conf) * rows.blocks_per_conf;
-  const uint32_t tiles = env_geometry(nm, ne, 0u).tiles;
-  const uint32_t span = lib->opt.scene_env_span ? lib->opt.scene_env_span : env_auto_span(tiles, n_blocks, uint32_t(std::max(lib->n_cus, 1)), ENV_AUTO_PER_CU);
-  const EnvGeometry geo = env_geometry(nm, ne, span);
-  const uint64_t per = env_chunk_blocks(geo, n_blocks, lib->opt.scene_cull_chunk);
-  const size_t conf_per_chunk = std::min<size_t>(n_conf, size_t(per / rows.blocks_per_conf) + 2);
-  HIP_TRY(w.d_boxes.grow(conf_per_chunk * nm * 6));
-  const uint64_t chunk_rows = std::min<uint64_t>(per * rows.rows_per_block, uint64_t(n_conf) * nm);
-  rc = pairs_chunk_buffers(lib, size_t(chunk_rows * geo.n_spans));
-  if (rc) return rc;
-  EnvArgs a;
-  pairs_args(a.p, s, rows, false, n_conf);
-  a.p.tile_groups = nullptr;
-  a.p.n_objects = nm * geo.n_spans;  // (the scan's rows: (row, span) counts, row-major)
-  a.p.total_rows = uint64_t(n_conf) * nm * geo.n_spans;
-  a.p.inflate = inflate;
-  a.p.pairs = d_pairs;
-  a.p.capacity = d_pairs ? capacity : 0;
-  a.p.conf_begin = d_conf_begin;
-  a.p.n_listed = d_n_listed;
-  a.n_moving = nm;
-  a.n_env = ne;
-  a.tiles_moving = geo.tiles_moving;
-  a.tiles = geo.tiles;
-  a.span_len = geo.span_len;
-  a.n_spans = geo.n_spans;
-  a.blocks_per_conf = rows.blocks_per_conf;
-  a.env_boxes = s->d_env_boxes;
-  a.env_tile_boxes = s->d_env_tile_boxes;
-  a.col_tile_groups = s->n_groups ? s->d_env_tile_groups.get() : nullptr;
-  // the chunks in turn: the boxes of the moving rows of the configurations a chunk touches (the first n_moving objects' shapes), then the chunk
-  pairs_chunks<T>(a.p, s, d_table, rows, n_blocks, per, st, [&]() {
-    a.row0 = a.p.row0;
-    a.p.row0 = a.row0 * geo.n_spans;
-    a.p.n_rows = uint32_t(uint64_t(a.p.n_rows) * geo.n_spans);
-    launch_env_chunk(st, a);
-  });
+  auto the_list = [&](PairsArgs& p) {  // the caller's part of a sweep's arguments
+    p.inflate = inflate;
+    p.pairs = d_pairs;
+    p.capacity = d_pairs ? capacity : 0;
+    p.conf_begin = d_conf_begin;
+    p.n_listed = d_n_listed;
+  };
+  if (kind == ListKind::Env) {
+    EnvSweep sweep;
+    rc = sweep.ready(s, n_conf);
+    if (rc) return rc;
+    EnvArgs a;
+    sweep.args(a, n_conf);
+    the_list(a.p);
+    sweep.walk<T>(a, d_table, st, [&]() { launch_env_chunk(st, a); });
+  } else {
+    SelfSweep sweep;
+    rc = sweep.ready(s, n_conf);
+    if (rc) return rc;
+    PairsArgs a;
+    sweep.args(a, n_conf);
+    the_list(a);
+    sweep.walk<T>(a, d_table, st, [&]() { launch_pairs_chunk(st, a); });
+  }
   HIP_TRY(hipGetLastError());
   return HFCL_OK;
 }
 
-// The env list of a moving table that is on the device into the library's own (w.d_pair_list, w.d_conf_begin), and the one read-back: the count.
+// entries a list of pairs of `rows` rows is first given room for (a longer one is made again in a buffer of its size)
+static size_t pairs_capacity_guess(size_t rows) { return std::max<size_t>(16 * rows, 4096); }
+// The list of a table that is on the device into the library's own (w.d_pair_list, w.d_conf_begin), and the one read-back: the count.
 template <typename T>
-static int env_pairs_into_workspace(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, double inflate, bool want_pairs,
-                                    uint64_t& n_listed) {
+static int pairs_into_workspace(ListKind kind, const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, double inflate, bool want_pairs,
+                                uint64_t& n_listed) {
   hfcl_lib* lib = s->lib;
   hfcl_lib::SceneWs& w = lib->scene;
   HIP_TRY(w.d_conf_begin.grow(n_conf + 1));
   HIP_TRY(w.d_running.grow(2));
-  if (want_pairs) HIP_TRY(w.d_pair_list.grow(2 * pairs_capacity_guess(n_conf * s->n_moving)));
+  if (want_pairs) HIP_TRY(w.d_pair_list.grow(2 * pairs_capacity_guess(n_conf * pair_rows(s, kind))));
   return list_and_count(w.d_pair_list, want_pairs, w.d_running + 1, w.s_cmp, n_listed, [&]() {
-    return env_pairs_device<T>(who, s, d_table, n_conf, inflate, want_pairs ? w.d_pair_list.get() : nullptr, w.d_pair_list.capacity() / 2,
-                               w.d_conf_begin, w.d_running + 1, w.s_cmp);
+    return pairs_device<T>(kind, who, s, d_table, n_conf, inflate, want_pairs ? w.d_pair_list.get() : nullptr, w.d_pair_list.capacity() / 2,
+                           w.d_conf_begin, w.d_running + 1, w.s_cmp);
   }, 2);
 }
 
 template <typename T>
-static int env_pairs_host(const char* who, hfcl_scene* s, const void* table, size_t n_conf, double inflate, uint32_t* pairs, size_t capacity,
-                          uint64_t* conf_begin, size_t* n_listed) {
+static int pairs_host(ListKind kind, const char* who, hfcl_scene* s, const void* table, size_t n_conf, double inflate, uint32_t* pairs,
+                      size_t capacity, uint64_t* conf_begin, size_t* n_listed) {
   bool nothing;
-  int rc = env_validate<T>(who, s, table, n_conf, nothing);
+  int rc = pair_validate<T>(kind, who, s, table, n_conf, nothing);
   if (!rc) rc = cull_check_inflate(who, inflate);
   if (!rc && !n_listed) {
     set_error(std::string(who) + ": null count");
     rc = HFCL_ERR_INVALID_ARGUMENT;
   }
-  if (!rc) rc = env_limits(who, s);
+  if (!rc) rc = pair_limits(who, s, kind);
   if (rc) return rc;
   *n_listed = 0;
   if (nothing) {
@@ -1151,9 +1114,9 @@ static int env_pairs_host(const char* who, hfcl_scene* s, const void* table, siz
   hfcl_lib::SceneWs& w = lib->scene;
   HIP_TRY(hipSetDevice(lib->device));
   rc = scene_host_stream(w);
-  if (!rc) rc = scene_table_in(w, table, n_conf * s->n_moving * SceneTypes<T>::WIDTH * sizeof(T));
+  if (!rc) rc = scene_table_in(w, table, n_conf * pair_rows(s, kind) * SceneTypes<T>::WIDTH * sizeof(T));
   uint64_t n = 0;
-  if (!rc) rc = env_pairs_into_workspace<T>(who, s, w.d_table, n_conf, inflate, pairs != nullptr, n);
+  if (!rc) rc = pairs_into_workspace<T>(kind, who, s, w.d_table, n_conf, inflate, pairs != nullptr, n);
   if (rc) {
     hipStreamSynchronize(w.s_cmp);
     return rc;
@@ -1169,38 +1132,29 @@ static int env_pairs_host(const char* who, hfcl_scene* s, const void* table, siz
   return HFCL_OK;
 }
 
-// the list flavour of a scene with an environment
-static SceneList env_list(const hfcl_scene* s, const uint32_t* d_pairs, const uint64_t* d_conf_begin, size_t n_conf, size_t n_listed) {
-  SceneList list{nullptr, d_conf_begin, n_conf};
-  list.d_pairs = d_pairs;
-  list.shares = uint32_t(env_shares(n_listed, s->n_moving, s->n_env()));
-  list.env = true;
-  list.d_env_table = s->d_env_table;
-  list.n_moving = s->n_moving;
-  return list;
-}
-// The device form on an env list.  The list is not checked: i < n_moving, i < j < n_objects, conf_begin its spans -- as
-// hfcl_scene_env_pairs_device leaves them.
+// The device form on a list of pairs.  The list is not checked: i < j < n_objects (Env: i < n_moving), conf_begin its spans -- as
+// hfcl_scene_self_pairs_device / hfcl_scene_env_pairs_device leave them.  counts: as scene_chunks_device takes them.
+// Kept as the two were: with configurations but no pose row, a Self call returns here, an Env call goes on to the summary init.
 template <typename T>
-static int scene_env_pairs_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const uint32_t* d_pairs, size_t n_listed,
-                                  const uint64_t* d_conf_begin, const hfcl_collision_request* creq, const hfcl_distance_request* dreq,
-                                  typename SceneTypes<T>::R* d_out, hfcl_scene_summary* d_summary, const hfcl_guess* d_gin, hfcl_guess* d_gout,
-                                  hipStream_t st, SceneCountSlots* counts = nullptr) {
+static int scene_pairs_device(ListKind kind, const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const uint32_t* d_pairs,
+                              size_t n_listed, const uint64_t* d_conf_begin, const hfcl_collision_request* creq, const hfcl_distance_request* dreq,
+                              typename SceneTypes<T>::R* d_out, hfcl_scene_summary* d_summary, const hfcl_guess* d_gin, hfcl_guess* d_gout,
+                              hipStream_t st, SceneCountSlots* counts = nullptr) {
   bool nothing;
-  int rc = env_scene_validate<T>(who, s, d_table, n_conf, creq, dreq, d_out, d_summary, nothing);
+  int rc = pair_scene_validate<T>(kind, who, s, d_table, n_conf, creq, dreq, d_out, d_summary, nothing);
   if (rc) return rc;
-  if (n_conf == 0 || s->n_moving == 0) {
+  if (n_conf == 0 || pair_rows(s, kind) == 0) {
     if (n_listed) {
-      set_error(std::string(who) + ": list entries without a configuration or a moving object");
+      set_error(std::string(who) + ": list entries without a configuration or " + (kind == ListKind::Env ? "a moving object" : "an object"));
       return HFCL_ERR_INVALID_ARGUMENT;
     }
-    if (n_conf == 0) return HFCL_OK;
+    if (n_conf == 0 || kind == ListKind::Self) return HFCL_OK;
   }
   if (n_listed && (!d_pairs || !d_conf_begin)) {
     set_error(std::string(who) + ": null list / conf_begin");
     return HFCL_ERR_INVALID_ARGUMENT;
   }
-  if (d_summary && (rc = env_rank_limit(who, n_listed, s))) return rc;
+  if (d_summary && (rc = pair_rank_limit(who, n_listed, s, kind))) return rc;
   hfcl_lib* lib = s->lib;
   HIP_TRY(hipSetDevice(lib->device));
   if (d_summary) launch_scene_summary_init(st, d_summary, n_conf, lib->n_cus * 16);
@@ -1208,22 +1162,21 @@ static int scene_env_pairs_device(const char* who, hfcl_scene* s, const void* d_
     HIP_TRY(hipGetLastError());
     return HFCL_OK;
   }
-  const SceneList list = env_list(s, d_pairs, d_conf_begin, n_conf, n_listed);
+  const SceneList list = pair_list(s, kind, d_pairs, d_conf_begin, n_conf, n_listed);
   return scene_chunks_device<T>(s, d_table, &list, n_listed, creq, dreq, d_out, d_summary, d_gin, d_gout, st, counts);
 }
 
-// what the culled host forms (hfcl_scene_*_culled) add to scene_host
+// What the culled host forms add to scene_host.  kind: Culled (hfcl_scene_*_culled): the list is culled from the scene's own, its ids to
+// query_ids_out; Self / Env (hfcl_scene_*_self / _env): the list is made by pairs_into_workspace, its pairs to pairs_out -- Env from a
+// table of the moving objects alone
 struct SceneCull {
+  ListKind kind;
   double inflate;
   size_t out_capacity;
-  uint64_t* query_ids_out;   // nullptr or out_capacity
+  uint64_t* query_ids_out;   // Culled: nullptr or out_capacity
+  uint32_t* pairs_out;       // Self, Env: nullptr or 2 x out_capacity
   uint64_t* conf_begin_out;  // nullptr or n_conf + 1
   size_t* n_listed;
-  // the self forms (hfcl_scene_*_self): the list is made by hfcl_scene_self_pairs_device, not culled from the scene's own; query_ids_out unused
-  bool self = false;
-  uint32_t* pairs_out = nullptr;  // nullptr or 2 x out_capacity
-  // the env forms (hfcl_scene_*_env): self, with the list made by hfcl_scene_env_pairs_device from a table of the moving objects alone
-  bool env = false;
 };
 
 // Host form.  The object table goes in once; chunk k computes on one stream while chunk k - 1's records leave on another from the other of
@@ -1234,15 +1187,17 @@ static int scene_host(const char* who, hfcl_scene* s, const void* table, size_t 
                       const hfcl_distance_request* dreq, typename SceneTypes<T>::R* out, hfcl_scene_summary* summary, const hfcl_guess* gin,
                       hfcl_guess* gout, const SceneCull* cull = nullptr) {
   using R = typename SceneTypes<T>::R;
-  size_t total;
-  const bool self = cull && cull->self, env = cull && cull->env;
-  bool env_nothing = true;
-  int rc = env ? env_scene_validate<T>(who, s, table, n_conf, creq, dreq, out, summary, env_nothing)
-               : scene_validate<T>(who, s, table, n_conf, creq, dreq, out, summary, total, self ? &hfcl_scene::n_objects : &hfcl_scene::n_pairs);
-  if (!rc && self && !env) rc = self_pairs_limits(who, s);
-  if (!rc && self && !env) total = n_conf && s->n_objects >= 2 ? n_conf * s->n_objects : 0;  // (rows: what the list is made from)
-  if (!rc && env) rc = env_limits(who, s);
-  if (!rc && env) total = env_nothing ? 0 : n_conf * s->n_moving;
+  size_t total = 0;
+  const bool made = cull && cull->kind != ListKind::Culled;  // the list is made from the table's rows, not culled from the scene's own
+  int rc;
+  if (made) {
+    bool nothing;
+    rc = pair_scene_validate<T>(cull->kind, who, s, table, n_conf, creq, dreq, out, summary, nothing);
+    if (!rc) rc = pair_limits(who, s, cull->kind);
+    if (!rc) total = nothing ? 0 : n_conf * pair_rows(s, cull->kind);  // (rows: what the list is made from)
+  } else {
+    rc = scene_validate<T>(who, s, table, n_conf, creq, dreq, out, summary, total);
+  }
   if (!rc && cull) {
     rc = cull_check_inflate(who, cull->inflate);
     if (!rc && !cull->n_listed) {
@@ -1267,15 +1222,14 @@ static int scene_host(const char* who, hfcl_scene* s, const void* table, size_t 
     if (!w.ev_done[k]) HIP_TRY(w.ev_done[k].create());
     if (!w.ev_copied[k]) HIP_TRY(w.ev_copied[k].create());
   }
-  const size_t table_bytes = n_conf * (env ? s->n_moving : s->n_objects) * SceneTypes<T>::WIDTH * sizeof(T);
+  const size_t table_bytes = n_conf * (made ? pair_rows(s, cull->kind) : s->n_objects) * SceneTypes<T>::WIDTH * sizeof(T);
   size_t work = total;  // records of the call: every query, or (culled form) the surviving ones
   if (cull) {  // the table goes in, the cull runs, the count comes back: 8 bytes, the one read-back before the narrow phase
     rc = scene_table_in(w, table, table_bytes);
     uint64_t n = 0;
     if (!rc)
-      rc = env    ? env_pairs_into_workspace<T>(who, s, w.d_table, n_conf, cull->inflate, true, n)
-           : self ? self_pairs_into_workspace<T>(who, s, w.d_table, n_conf, cull->inflate, true, n)
-                  : cull_into_workspace<T>(who, s, w.d_table, n_conf, total, cull->inflate, true, n);
+      rc = made ? pairs_into_workspace<T>(cull->kind, who, s, w.d_table, n_conf, cull->inflate, true, n)
+                : cull_into_workspace<T>(who, s, w.d_table, n_conf, total, cull->inflate, true, n);
     if (rc) {
       hipStreamSynchronize(w.s_cmp);
       return rc;
@@ -1286,20 +1240,14 @@ static int scene_host(const char* who, hfcl_scene* s, const void* table, size_t 
       return HFCL_ERR_LIMIT;
     }
     if (!n) return nothing_listed();
-    if (self && summary && (rc = env ? env_rank_limit(who, n, s) : pairs_rank_limit(who, n, s->n_objects))) return rc;
+    if (made && summary && (rc = pair_rank_limit(who, n, s, cull->kind))) return rc;
     if (cull->query_ids_out) HIP_TRY(hipMemcpyAsync(cull->query_ids_out, w.d_ids, n * sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
     if (cull->pairs_out) HIP_TRY(hipMemcpyAsync(cull->pairs_out, w.d_pair_list, n * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, w.s_cmp));
     if (cull->conf_begin_out)
       HIP_TRY(hipMemcpyAsync(cull->conf_begin_out, w.d_conf_begin, (n_conf + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, w.s_cmp));
     work = size_t(n);
   }
-  SceneList listed{w.d_ids, w.d_conf_begin, n_conf};
-  if (self) {
-    listed.d_ids = nullptr;
-    listed.d_pairs = w.d_pair_list;
-    listed.shares = uint32_t(pairs_shares(work, s->n_objects));
-  }
-  if (env) listed = env_list(s, w.d_pair_list, w.d_conf_begin, n_conf, work);
+  const SceneList listed = made ? pair_list(s, cull->kind, w.d_pair_list, w.d_conf_begin, n_conf, work) : query_list(w.d_ids, w.d_conf_begin, n_conf);
   const SceneList* list = cull ? &listed : nullptr;
   const size_t chunk = scene_chunk_size(work, lib->opt.scene_chunk);
   const size_t n_chunks = (work + chunk - 1) / chunk;
@@ -1373,23 +1321,72 @@ static int scene_host(const char* who, hfcl_scene* s, const void* table, size_t 
 // count read back, its narrow phase through scene_listed_device; the thresholds; the same for pass 2, merged into the same summaries; the
 // min records gathered.  Two read-backs of 8 bytes.
 // ---------------------------------------------------------------------------------------
+// What the three families of pruned-clearance calls (nearest, nearest_self, nearest_env) refuse first, in this order: a NaN bound; of a
+// scene that is there a null request, a null output -- in the family's words, no_out -- and the request's own checks.  A null scene is
+// the family's validator's to refuse, after this.
 template <typename T>
-static int nearest_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, const hfcl_distance_request* req, double upper,
-                            const void* summary, size_t& total) {
-  total = 0;
+static int nearest_head(const char* who, const hfcl_scene* s, const hfcl_distance_request* req, double upper, const void* out, const char* no_out) {
   if (upper != upper) {
     set_error(std::string(who) + ": upper_bound is NaN");
     return HFCL_ERR_INVALID_ARGUMENT;
   }
-  if (s && !req) {
+  if (!s) return HFCL_OK;
+  if (!req) {
     set_error("null request");
     return HFCL_ERR_INVALID_ARGUMENT;
   }
-  if (s && !summary) {
-    set_error(std::string(who) + ": null summaries");
+  if (!out) {
+    set_error(std::string(who) + ": " + no_out);
     return HFCL_ERR_INVALID_ARGUMENT;
   }
-  return scene_validate<T>(who, s, table, n_conf, nullptr, req, nullptr, summary, total);
+  QParams<T> q;
+  return setup_distance<T>(req, q);
+}
+template <typename T>
+static int nearest_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, const hfcl_distance_request* req, double upper,
+                            const void* summary, size_t& total) {
+  total = 0;
+  const int rc = nearest_head<T>(who, s, req, upper, summary, "null summaries");
+  return rc ? rc : scene_validate<T>(who, s, table, n_conf, nullptr, req, nullptr, summary, total);  // (the request's checks once more: they passed)
+}
+
+// The host shell of the three families once there is something to do: the stream, the output (d_out: the library's buffer of the family's
+// per-configuration output) and min-record buffers, the count slots, the table of n_conf x rows pose rows in, run(d_table, d_out, d_min,
+// counts, st) -- the family's *_run --, the outputs back, nothing left in flight, the tail of a host form.
+// (scene_host has a shell of its own: two streams, and a finish that waits for both and does not harvest.)
+template <typename T, typename Out, typename Run>
+static int nearest_host_shell(const char* who, hfcl_scene* s, const void* table, size_t rows, size_t n_conf, const hfcl_distance_request* req,
+                              DevBuf<Out>& d_out, Out* out, typename SceneTypes<T>::R* min_records, Run&& run) {
+  using R = typename SceneTypes<T>::R;
+  hfcl_lib* lib = s->lib;
+  hfcl_lib::SceneWs& w = lib->scene;
+  HIP_TRY(hipSetDevice(lib->device));
+  int rc = scene_host_stream(w);
+  if (rc) return rc;
+  HIP_TRY(d_out.grow(n_conf));
+  if (min_records) HIP_TRY(w.d_minrec.grow(n_conf * sizeof(R)));
+  rc = SceneCountSlots::ready(w);
+  if (rc) return rc;
+  SceneCountSlots counts(lib);  // (ends after finish has waited for the streams)
+  auto finish = [&](int code) {  // nothing of this call stays in flight, whatever happened
+    const bool synced = hipStreamSynchronize(w.s_cmp) == hipSuccess;
+    if (lib->side) hipStreamSynchronize(lib->side);
+    if (code == HFCL_OK && synced) counts.harvest_rest();
+    if (code == HFCL_OK && !synced) {
+      set_error(std::string(who) + ": the device reported an error");
+      return int(HFCL_ERR_HIP);
+    }
+    return code;
+  };
+  rc = scene_table_in(w, table, n_conf * rows * SceneTypes<T>::WIDTH * sizeof(T));
+  if (!rc) rc = run(w.d_table.get(), d_out.get(), min_records ? static_cast<R*>(w.d_minrec.get()) : nullptr, &counts, w.s_cmp.get());
+  if (!rc && hipMemcpyAsync(out, d_out, n_conf * sizeof(Out), hipMemcpyDeviceToHost, w.s_cmp) != hipSuccess) rc = HFCL_ERR_HIP;
+  if (!rc && min_records && hipMemcpyAsync(min_records, w.d_minrec, n_conf * sizeof(R), hipMemcpyDeviceToHost, w.s_cmp) != hipSuccess)
+    rc = HFCL_ERR_HIP;
+  rc = finish(rc);
+  if (rc) return rc;
+  lib->last_host = true;
+  return host_batch_checks(lib, nullptr, req);
 }
 
 // table on the device, total > 0, everything on st (which is waited for twice)
@@ -1515,89 +1512,23 @@ static int nearest_host(const char* who, hfcl_scene* s, const void* table, size_
     }
     return HFCL_OK;
   }
-  hfcl_lib* lib = s->lib;
-  hfcl_lib::SceneWs& w = lib->scene;
-  HIP_TRY(hipSetDevice(lib->device));
-  rc = scene_host_stream(w);
-  if (rc) return rc;
-  HIP_TRY(w.d_summary.grow(n_conf));
-  if (min_records) HIP_TRY(w.d_minrec.grow(n_conf * sizeof(R)));
-  rc = SceneCountSlots::ready(w);
-  if (rc) return rc;
-  SceneCountSlots counts(lib);  // (ends after finish has waited for the streams)
-  auto finish = [&](int code) {  // nothing of this call stays in flight, whatever happened
-    const bool synced = hipStreamSynchronize(w.s_cmp) == hipSuccess;
-    if (lib->side) hipStreamSynchronize(lib->side);
-    if (code == HFCL_OK && synced) counts.harvest_rest();
-    if (code == HFCL_OK && !synced) {
-      set_error(std::string(who) + ": the device reported an error");
-      return int(HFCL_ERR_HIP);
-    }
-    return code;
-  };
-  rc = scene_table_in(w, table, n_conf * s->n_objects * SceneTypes<T>::WIDTH * sizeof(T));
-  if (!rc) rc = nearest_run<T>(who, s, w.d_table, n_conf, total, req, upper, w.d_summary, min_records ? static_cast<R*>(w.d_minrec.get()) : nullptr,
-                               n_evaluated, &counts, w.s_cmp);
-  if (!rc && hipMemcpyAsync(summary, w.d_summary, n_conf * sizeof(hfcl_scene_summary), hipMemcpyDeviceToHost, w.s_cmp) != hipSuccess) rc = HFCL_ERR_HIP;
-  if (!rc && min_records && hipMemcpyAsync(min_records, w.d_minrec, n_conf * sizeof(R), hipMemcpyDeviceToHost, w.s_cmp) != hipSuccess)
-    rc = HFCL_ERR_HIP;
-  rc = finish(rc);
-  if (rc) return rc;
-  lib->last_host = true;
-  return host_batch_checks(lib, nullptr, req);
+  return nearest_host_shell<T>(who, s, table, s->n_objects, n_conf, req, s->lib->scene.d_summary, summary, min_records,
+                               [&](const void* d_table, hfcl_scene_summary* d_summary, R* d_min, SceneCountSlots* counts, hipStream_t st) {
+                                 return nearest_run<T>(who, s, d_table, n_conf, total, req, upper, d_summary, d_min, n_evaluated, counts, st);
+                               });
 }
 
 // ---------------------------------------------------------------------------------------
 // The clearance per configuration on device-made pairs (include/hppfcl_amd_nearest_self.h: hfcl_scene_nearest_self*).
-// hfcl_k_nearest_self.hip has the kernels, hfcl_nearest_self.hpp the arithmetic.  Five walks of the all-pairs sweep, each in the chunks of
-// self_pairs_device with the boxes made per chunk: the seeds; count and emit of pass 1, its count read back, its narrow phase through
-// scene_pairs_device into summaries of its own; the thresholds; the same for pass 2; the two combined.  Two read-backs of 8 bytes.
+// hfcl_k_nearest_self.hip has the kernels, hfcl_nearest_self.hpp the arithmetic.  Five walks of the all-pairs sweep (SelfSweep: the chunks
+// of the list maker, the boxes made per chunk): the seeds; count and emit of pass 1, its count read back, its narrow phase through
+// scene_pairs_device into summaries of its own; the thresholds; the same for pass 2; the two combined (clearance_passes).  Two read-backs
+// of 8 bytes.  The clearance among a kept environment (hfcl_scene_nearest_env*) is the same over EnvSweep; the validator, the device form
+// and the host form are one for both (clearance_validate / _device / _host).
 // ---------------------------------------------------------------------------------------
-template <typename T>
-static int nearest_self_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, const hfcl_distance_request* req,
-                                 double upper, const void* out) {
-  if (upper != upper) {
-    set_error(std::string(who) + ": upper_bound is NaN");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  if (s && !req) {
-    set_error("null request");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  if (s && !out) {
-    set_error(std::string(who) + ": null output");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  if (s) {
-    QParams<T> q;
-    if (const int rc = setup_distance<T>(req, q)) return rc;
-  }
-  const int rc = self_validate<T>(who, s, table, n_conf);
-  return rc ? rc : self_pairs_limits(who, s);
-}
-
-// table on the device, n_conf > 0, at least two objects, everything on st (which is waited for twice)
-template <typename T>
-static int nearest_self_run(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const hfcl_distance_request* req, double upper,
-                            hfcl_scene_clearance* d_out, typename SceneTypes<T>::R* d_min, size_t* n_evaluated, SceneCountSlots* counts,
-                            hipStream_t st) {
-  using R = typename SceneTypes<T>::R;
-  constexpr bool f32 = std::is_same<T, float>::value;
-  hfcl_lib* lib = s->lib;
-  hfcl_lib::SceneWs& w = lib->scene;
-  int rc = ensure_local_boxes(lib);
-  if (rc) return rc;
-  const uint32_t n = uint32_t(s->n_objects);
-  const bool small = n <= std::min(lib->opt.scene_pairs_small_max, PAIRS_SMALL_MAX);
-  const PairsGeometry geo = pairs_geometry(n, small);
-  const uint64_t n_blocks = uint64_t(n_conf) * geo.blocks_per_conf;
-  const uint64_t per = pairs_chunk_blocks(geo, n_blocks, lib->opt.scene_cull_chunk);
-  const size_t conf_per_chunk = std::min<size_t>(n_conf, size_t(per / geo.blocks_per_conf) + 2);
-  const size_t rows = n_conf * size_t(n);
-  HIP_TRY(w.d_boxes.grow(conf_per_chunk * n * 6));
-  rc = pairs_chunk_buffers(lib, size_t(std::min<uint64_t>(per * geo.rows_per_block, rows)));
-  if (rc) return rc;
-  if (!small) HIP_TRY(w.d_ns_row_seeds.grow(rows * sizeof(NselfRowSeed)));
+// What the two passes keep per configuration, whatever sweeps: seeds and thresholds, and per pass conf_begin, summaries and a list with
+// first room for the entries of `rows` rows
+static int clearance_buffers(hfcl_lib::SceneWs& w, size_t n_conf, size_t rows) {
   HIP_TRY(w.d_ns_seed.grow(n_conf));
   HIP_TRY(w.d_ns_thr.grow(n_conf));
   for (int l = 0; l < 2; ++l) {
@@ -1605,54 +1536,60 @@ static int nearest_self_run(const char* who, hfcl_scene* s, const void* d_table,
     HIP_TRY(w.d_ns_summary[l].grow(n_conf));
     HIP_TRY(w.d_ns_list[l].grow(2 * pairs_capacity_guess(rows)));
   }
-
-  NselfArgs a{};
-  pairs_args(a.p, s, geo, small, n_conf);
-  a.r = f32 ? NEAREST_R32 : NEAREST_R64;
-  a.upper = upper;
-  a.row_seeds = small ? nullptr : w.d_ns_row_seeds.get();
-  a.seed = w.d_ns_seed;
-  a.thr = w.d_ns_thr;
-  pairs_chunks<T>(a.p, s, d_table, geo, n_blocks, per, st, [&]() { launch_nself_seed(st, a); });
-  if (!small) launch_nself_seed_combine(st, a, lib->n_cus * 16);
-
+  return HFCL_OK;
+}
+// the clearance and the min record of n_conf configurations from the two passes' lists (nullptr: every configuration is one without records)
+static void clearance_combine(hfcl_lib::SceneWs* w, size_t n_conf, hfcl_scene_clearance* d_out, void* d_min, bool f32, hipStream_t st) {
+  NselfCombineArgs g{};
+  g.n_conf = n_conf;
+  for (int l = 0; w && l < 2; ++l) {
+    g.summary[l] = w->d_ns_summary[l];
+    g.pairs[l] = w->d_ns_list[l];
+    g.conf_begin[l] = w->d_ns_conf_begin[l];
+    g.rec[l] = d_min ? w->d_ns_rec[l].get() : nullptr;
+  }
+  g.out = d_out;
+  g.min_out = d_min;
+  launch_nself_combine(st, g, f32);
+}
+// The two passes of a clearance call on st, the seeds made: per pass the thresholds (pass 2: thr[c] = min(D, min_distance of pass 1)), the
+// pass's list -- list_chunks() walks the family's sweep with `pass`, and `p`'s list members, set --, its count read back, the rank limit,
+// its narrow phase through scene_pairs_device into summaries of its own; then the two combined.  Two read-backs of 8 bytes.
+// (hfcl_scene_nearest's nearest_run is the same skeleton on ids: its lists go through scene_listed_device, pass 2 merged into the
+// summaries of pass 1, and a gather ends it.)
+template <typename T, typename Walk>
+static int clearance_passes(ListKind kind, const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const hfcl_distance_request* req,
+                            double upper, PairsArgs& p, int& pass_of_args, Walk&& list_chunks, hfcl_scene_clearance* d_out,
+                            typename SceneTypes<T>::R* d_min, size_t* n_evaluated, SceneCountSlots* counts, hipStream_t st) {
+  using R = typename SceneTypes<T>::R;
+  hfcl_lib::SceneWs& w = s->lib->scene;
   uint64_t n_list[2] = {0, 0};
   for (int pass = 1; pass <= 2; ++pass) {
     const int l = pass - 1;
-    if (pass == 2) {  // thr[c] = min(D, min_distance of pass 1)
+    if (pass == 2) {
       NearestArgs t{};
       t.c.n_conf = n_conf;
       t.upper = upper;
       t.thr = w.d_ns_thr;
       launch_nearest_threshold(st, t, w.d_ns_summary[0]);
     }
-    a.pass = pass;
-    a.p.conf_begin = w.d_ns_conf_begin[l];
-    a.p.n_listed = w.d_running + 1;
-    rc = list_and_count(w.d_ns_list[l], true, w.d_running + 1, st, n_list[l], [&]() {  // the pass's list, and the one read-back: its count
-      a.p.pairs = w.d_ns_list[l];
-      a.p.capacity = w.d_ns_list[l].capacity() / 2;
-      pairs_chunks<T>(a.p, s, d_table, geo, n_blocks, per, st, [&]() { launch_nself_chunk(st, a); });
+    pass_of_args = pass;
+    p.conf_begin = w.d_ns_conf_begin[l];
+    p.n_listed = w.d_running + 1;
+    int rc = list_and_count(w.d_ns_list[l], true, w.d_running + 1, st, n_list[l], [&]() {
+      p.pairs = w.d_ns_list[l];
+      p.capacity = w.d_ns_list[l].capacity() / 2;
+      list_chunks();
       return int(HFCL_OK);
     }, 2);
-    if (!rc) rc = pairs_rank_limit(who, n_list[l], n);
+    if (!rc) rc = pair_rank_limit(who, n_list[l], s, kind);
     if (rc) return rc;
     if (d_min) HIP_TRY(w.d_ns_rec[l].grow(size_t(n_list[l]) * sizeof(R)));
-    rc = scene_pairs_device<T>(who, s, d_table, n_conf, w.d_ns_list[l], size_t(n_list[l]), w.d_ns_conf_begin[l], nullptr, req,
+    rc = scene_pairs_device<T>(kind, who, s, d_table, n_conf, w.d_ns_list[l], size_t(n_list[l]), w.d_ns_conf_begin[l], nullptr, req,
                                d_min ? static_cast<R*>(w.d_ns_rec[l].get()) : nullptr, w.d_ns_summary[l], nullptr, nullptr, st, counts);
     if (rc) return rc;
   }
-  NselfCombineArgs g{};
-  g.n_conf = n_conf;
-  for (int l = 0; l < 2; ++l) {
-    g.summary[l] = w.d_ns_summary[l];
-    g.pairs[l] = w.d_ns_list[l];
-    g.conf_begin[l] = w.d_ns_conf_begin[l];
-    g.rec[l] = d_min ? w.d_ns_rec[l].get() : nullptr;
-  }
-  g.out = d_out;
-  g.min_out = d_min;
-  launch_nself_combine(st, g, f32);
+  clearance_combine(&w, n_conf, d_out, d_min, std::is_same<T, float>::value, st);
   if (n_evaluated) {
     n_evaluated[0] = size_t(n_list[0]);
     n_evaluated[1] = size_t(n_list[1]);
@@ -1661,156 +1598,58 @@ static int nearest_self_run(const char* who, hfcl_scene* s, const void* d_table,
   return HFCL_OK;
 }
 
+// table on the device, n_conf > 0, at least two objects, everything on st (which is waited for twice)
 template <typename T>
-static int nearest_self_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const hfcl_distance_request* req, double upper,
-                               hfcl_scene_clearance* d_out, typename SceneTypes<T>::R* d_min, size_t* n_evaluated, hipStream_t st) {
-  const int rc = nearest_self_validate<T>(who, s, d_table, n_conf, req, upper, d_out);
-  if (rc) return rc;
-  if (n_evaluated) n_evaluated[0] = n_evaluated[1] = 0;
-  if (!n_conf) return HFCL_OK;
-  hfcl_lib* lib = s->lib;
-  HIP_TRY(hipSetDevice(lib->device));
-  if (s->n_objects < 2) {  // no pair: every configuration is one without records
-    NselfCombineArgs g{};
-    g.n_conf = n_conf;
-    g.out = d_out;
-    g.min_out = d_min;
-    launch_nself_combine(st, g, std::is_same<T, float>::value);
-    HIP_TRY(hipGetLastError());
-    return HFCL_OK;
-  }
-  return nearest_self_run<T>(who, s, d_table, n_conf, req, upper, d_out, d_min, n_evaluated, nullptr, st);
-}
-
-template <typename T>
-static int nearest_self_host(const char* who, hfcl_scene* s, const void* table, size_t n_conf, const hfcl_distance_request* req, double upper,
-                             hfcl_scene_clearance* out, typename SceneTypes<T>::R* min_records, size_t* n_evaluated) {
-  using R = typename SceneTypes<T>::R;
-  int rc = nearest_self_validate<T>(who, s, table, n_conf, req, upper, out);
-  if (rc) return rc;
-  if (n_evaluated) n_evaluated[0] = n_evaluated[1] = 0;
-  if (!n_conf) return HFCL_OK;
-  if (s->n_objects < 2) {
-    const hfcl_scene_summary* no_summary[2] = {nullptr, nullptr};
-    const uint32_t* no_pairs[2] = {nullptr, nullptr};
-    const uint64_t* no_begin[2] = {nullptr, nullptr};
-    const R* no_rec[2] = {nullptr, nullptr};
-    for (size_t c = 0; c < n_conf; ++c) nself_combine<R>(c, no_summary, no_pairs, no_begin, no_rec, out[c], min_records ? &min_records[c] : nullptr);
-    return HFCL_OK;
-  }
+static int nearest_self_run(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const hfcl_distance_request* req, double upper,
+                            hfcl_scene_clearance* d_out, typename SceneTypes<T>::R* d_min, size_t* n_evaluated, SceneCountSlots* counts,
+                            hipStream_t st) {
   hfcl_lib* lib = s->lib;
   hfcl_lib::SceneWs& w = lib->scene;
-  HIP_TRY(hipSetDevice(lib->device));
-  rc = scene_host_stream(w);
+  int rc = ensure_local_boxes(lib);
   if (rc) return rc;
-  HIP_TRY(w.d_ns_out.grow(n_conf));
-  if (min_records) HIP_TRY(w.d_minrec.grow(n_conf * sizeof(R)));
-  rc = SceneCountSlots::ready(w);
+  SelfSweep sweep;
+  rc = sweep.ready(s, n_conf);
   if (rc) return rc;
-  SceneCountSlots counts(lib);  // (ends after finish has waited for the streams)
-  auto finish = [&](int code) {  // nothing of this call stays in flight, whatever happened
-    const bool synced = hipStreamSynchronize(w.s_cmp) == hipSuccess;
-    if (lib->side) hipStreamSynchronize(lib->side);
-    if (code == HFCL_OK && synced) counts.harvest_rest();
-    if (code == HFCL_OK && !synced) {
-      set_error(std::string(who) + ": the device reported an error");
-      return int(HFCL_ERR_HIP);
-    }
-    return code;
-  };
-  rc = scene_table_in(w, table, n_conf * s->n_objects * SceneTypes<T>::WIDTH * sizeof(T));
-  if (!rc) rc = nearest_self_run<T>(who, s, w.d_table, n_conf, req, upper, w.d_ns_out, min_records ? static_cast<R*>(w.d_minrec.get()) : nullptr,
-                                    n_evaluated, &counts, w.s_cmp);
-  if (!rc && hipMemcpyAsync(out, w.d_ns_out, n_conf * sizeof(hfcl_scene_clearance), hipMemcpyDeviceToHost, w.s_cmp) != hipSuccess) rc = HFCL_ERR_HIP;
-  if (!rc && min_records && hipMemcpyAsync(min_records, w.d_minrec, n_conf * sizeof(R), hipMemcpyDeviceToHost, w.s_cmp) != hipSuccess)
-    rc = HFCL_ERR_HIP;
-  rc = finish(rc);
+  const bool small = sweep.p.small;
+  const size_t rows = n_conf * s->n_objects;
+  if (!small) HIP_TRY(w.d_ns_row_seeds.grow(rows * sizeof(NselfRowSeed)));
+  rc = clearance_buffers(w, n_conf, rows);
   if (rc) return rc;
-  lib->last_host = true;
-  return host_batch_checks(lib, nullptr, req);
+  NselfArgs a{};
+  sweep.args(a.p, n_conf);
+  a.r = std::is_same<T, float>::value ? NEAREST_R32 : NEAREST_R64;
+  a.upper = upper;
+  a.row_seeds = small ? nullptr : w.d_ns_row_seeds.get();
+  a.seed = w.d_ns_seed;
+  a.thr = w.d_ns_thr;
+  sweep.walk<T>(a.p, d_table, st, [&]() { launch_nself_seed(st, a); });
+  if (!small) launch_nself_seed_combine(st, a, lib->n_cus * 16);
+  return clearance_passes<T>(ListKind::Self, who, s, d_table, n_conf, req, upper, a.p, a.pass,
+                             [&]() { sweep.walk<T>(a.p, d_table, st, [&]() { launch_nself_chunk(st, a); }); }, d_out, d_min, n_evaluated, counts, st);
 }
 
-// ---------------------------------------------------------------------------------------
-// The clearance of the moving objects among an environment kept on the device (include/hppfcl_amd_nearest_env.h: hfcl_scene_nearest_env*).
-// hfcl_k_nearest_env.hip has the kernels, hfcl_nearest_env.hpp the arithmetic.  nearest_self_run over the cells, chunks and spans of
-// env_pairs_device: the seeds (a partial per (row, span), then a wave per configuration); count and emit of pass 1, its count read back,
-// its narrow phase through scene_env_pairs_device into summaries of its own; the thresholds; the same for pass 2; the two combined.
-// Two read-backs of 8 bytes.
-// ---------------------------------------------------------------------------------------
-// nothing: n_conf == 0 or no moving object
-template <typename T>
-static int nearest_env_validate(const char* who, const hfcl_scene* s, const void* table, size_t n_conf, const hfcl_distance_request* req,
-                                double upper, const void* out, bool& nothing) {
-  nothing = true;
-  if (upper != upper) {
-    set_error(std::string(who) + ": upper_bound is NaN");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  if (s && !req) {
-    set_error("null request");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  if (s && !out) {
-    set_error(std::string(who) + ": null output");
-    return HFCL_ERR_INVALID_ARGUMENT;
-  }
-  if (s) {
-    QParams<T> q;
-    if (const int rc = setup_distance<T>(req, q)) return rc;
-  }
-  const int rc = env_validate<T>(who, s, table, n_conf, nothing);
-  return rc ? rc : env_limits(who, s);
-}
-
+// ... of the moving objects among an environment kept on the device (include/hppfcl_amd_nearest_env.h: hfcl_scene_nearest_env*;
+// hfcl_k_nearest_env.hip has the kernels, hfcl_nearest_env.hpp the arithmetic): nearest_self_run over the cells, chunks and spans of
+// the env list maker (EnvSweep); the seeds are a partial per (row, span), then a wave per configuration.
 // moving table on the device, n_conf > 0, at least one moving object, everything on st (which is waited for twice)
 template <typename T>
 static int nearest_env_run(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const hfcl_distance_request* req, double upper,
                            hfcl_scene_clearance* d_out, typename SceneTypes<T>::R* d_min, size_t* n_evaluated, SceneCountSlots* counts,
                            hipStream_t st) {
-  using R = typename SceneTypes<T>::R;
-  constexpr bool f32 = std::is_same<T, float>::value;
   hfcl_lib* lib = s->lib;
   hfcl_lib::SceneWs& w = lib->scene;
   int rc = ensure_local_boxes(lib);
   if (rc) return rc;
-  const uint32_t nm = uint32_t(s->n_moving), ne = uint32_t(s->n_env());
-  const PairsGeometry rows = pairs_geometry(nm, false);
-  const uint64_t n_blocks = uint64_t(n_conf) * rows.blocks_per_conf;
-  const uint32_t tiles = env_geometry(nm, ne, 0u).tiles;
-  const uint32_t span = lib->opt.scene_env_span ? lib->opt.scene_env_span : env_auto_span(tiles, n_blocks, uint32_t(std::max(lib->n_cus, 1)), ENV_AUTO_PER_CU);
-  const EnvGeometry geo = env_geometry(nm, ne, span);
-  const uint64_t per = env_chunk_blocks(geo, n_blocks, lib->opt.scene_cull_chunk);
-  const size_t conf_per_chunk = std::min<size_t>(n_conf, size_t(per / rows.blocks_per_conf) + 2);
-  const size_t moving_rows = n_conf * size_t(nm);
-  HIP_TRY(w.d_boxes.grow(conf_per_chunk * nm * 6));
-  const uint64_t chunk_rows = std::min<uint64_t>(per * rows.rows_per_block, uint64_t(moving_rows));
-  rc = pairs_chunk_buffers(lib, size_t(chunk_rows * geo.n_spans));
+  EnvSweep sweep;
+  rc = sweep.ready(s, n_conf);
   if (rc) return rc;
-  HIP_TRY(w.d_ns_row_seeds.grow(moving_rows * geo.n_spans * sizeof(NselfRowSeed)));
-  HIP_TRY(w.d_ns_seed.grow(n_conf));
-  HIP_TRY(w.d_ns_thr.grow(n_conf));
-  for (int l = 0; l < 2; ++l) {
-    HIP_TRY(w.d_ns_conf_begin[l].grow(n_conf + 1));
-    HIP_TRY(w.d_ns_summary[l].grow(n_conf));
-    HIP_TRY(w.d_ns_list[l].grow(2 * pairs_capacity_guess(moving_rows)));
-  }
-
+  const size_t moving_rows = n_conf * s->n_moving;
+  HIP_TRY(w.d_ns_row_seeds.grow(moving_rows * sweep.p.geo.n_spans * sizeof(NselfRowSeed)));
+  rc = clearance_buffers(w, n_conf, moving_rows);
+  if (rc) return rc;
   NenvArgs a{};
-  pairs_args(a.e.p, s, rows, false, n_conf);
-  a.e.p.tile_groups = nullptr;
-  a.e.p.n_objects = nm * geo.n_spans;  // (the scan's rows: (row, span) counts, row-major)
-  a.e.p.total_rows = uint64_t(n_conf) * nm * geo.n_spans;
-  a.e.n_moving = nm;
-  a.e.n_env = ne;
-  a.e.tiles_moving = geo.tiles_moving;
-  a.e.tiles = geo.tiles;
-  a.e.span_len = geo.span_len;
-  a.e.n_spans = geo.n_spans;
-  a.e.blocks_per_conf = rows.blocks_per_conf;
-  a.e.env_boxes = s->d_env_boxes;
-  a.e.env_tile_boxes = s->d_env_tile_boxes;
-  a.e.col_tile_groups = s->n_groups ? s->d_env_tile_groups.get() : nullptr;
-  a.r = f32 ? NEAREST_R32 : NEAREST_R64;
+  sweep.args(a.e, n_conf);
+  a.r = std::is_same<T, float>::value ? NEAREST_R32 : NEAREST_R64;
   a.upper = upper;
   a.prune = lib->opt.scene_nearest_env_prune ? 1 : 0;
   a.row_seeds = w.d_ns_row_seeds.get();
@@ -1818,95 +1657,55 @@ static int nearest_env_run(const char* who, hfcl_scene* s, const void* d_table, 
   a.thr = w.d_ns_thr;
   a.env_terms = s->d_env_terms;
   a.env_tile_terms = s->d_env_tile_terms;
-  // the chunks in turn: the boxes of the moving rows of the configurations a chunk touches, then the chunk's cells
-  auto walk = [&](auto&& launch) {
-    pairs_chunks<T>(a.e.p, s, d_table, rows, n_blocks, per, st, [&]() {
-      a.e.row0 = a.e.p.row0;
-      a.e.p.row0 = a.e.row0 * geo.n_spans;
-      a.e.p.n_rows = uint32_t(uint64_t(a.e.p.n_rows) * geo.n_spans);
-      launch();
-    });
-  };
-  walk([&]() { launch_nenv_seed(st, a); });
+  sweep.walk<T>(a.e, d_table, st, [&]() { launch_nenv_seed(st, a); });
   launch_nenv_seed_combine(st, a, lib->n_cus * 16);
-
-  uint64_t n_list[2] = {0, 0};
-  for (int pass = 1; pass <= 2; ++pass) {
-    const int l = pass - 1;
-    if (pass == 2) {  // thr[c] = min(D, min_distance of pass 1)
-      NearestArgs t{};
-      t.c.n_conf = n_conf;
-      t.upper = upper;
-      t.thr = w.d_ns_thr;
-      launch_nearest_threshold(st, t, w.d_ns_summary[0]);
-    }
-    a.pass = pass;
-    a.e.p.conf_begin = w.d_ns_conf_begin[l];
-    a.e.p.n_listed = w.d_running + 1;
-    rc = list_and_count(w.d_ns_list[l], true, w.d_running + 1, st, n_list[l], [&]() {  // the pass's list, and the one read-back: its count
-      a.e.p.pairs = w.d_ns_list[l];
-      a.e.p.capacity = w.d_ns_list[l].capacity() / 2;
-      walk([&]() { launch_nenv_chunk(st, a); });
-      return int(HFCL_OK);
-    }, 2);
-    if (!rc) rc = env_rank_limit(who, n_list[l], s);
-    if (rc) return rc;
-    if (d_min) HIP_TRY(w.d_ns_rec[l].grow(size_t(n_list[l]) * sizeof(R)));
-    rc = scene_env_pairs_device<T>(who, s, d_table, n_conf, w.d_ns_list[l], size_t(n_list[l]), w.d_ns_conf_begin[l], nullptr, req,
-                                   d_min ? static_cast<R*>(w.d_ns_rec[l].get()) : nullptr, w.d_ns_summary[l], nullptr, nullptr, st, counts);
-    if (rc) return rc;
-  }
-  NselfCombineArgs g{};
-  g.n_conf = n_conf;
-  for (int l = 0; l < 2; ++l) {
-    g.summary[l] = w.d_ns_summary[l];
-    g.pairs[l] = w.d_ns_list[l];
-    g.conf_begin[l] = w.d_ns_conf_begin[l];
-    g.rec[l] = d_min ? w.d_ns_rec[l].get() : nullptr;
-  }
-  g.out = d_out;
-  g.min_out = d_min;
-  launch_nself_combine(st, g, f32);
-  if (n_evaluated) {
-    n_evaluated[0] = size_t(n_list[0]);
-    n_evaluated[1] = size_t(n_list[1]);
-  }
-  HIP_TRY(hipGetLastError());
-  return HFCL_OK;
+  return clearance_passes<T>(ListKind::Env, who, s, d_table, n_conf, req, upper, a.e.p, a.pass,
+                             [&]() { sweep.walk<T>(a.e, d_table, st, [&]() { launch_nenv_chunk(st, a); }); }, d_out, d_min, n_evaluated, counts, st);
 }
 
+// ---- the three forms of either family (kind: Self / Env) ----
+// head, then what the family's list maker refuses, then its limits.  nothing: n_conf == 0, or no pair whatever the table holds
 template <typename T>
-static int nearest_env_device(const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const hfcl_distance_request* req, double upper,
-                              hfcl_scene_clearance* d_out, typename SceneTypes<T>::R* d_min, size_t* n_evaluated, hipStream_t st) {
+static int clearance_validate(ListKind kind, const char* who, const hfcl_scene* s, const void* table, size_t n_conf, const hfcl_distance_request* req,
+                              double upper, const void* out, bool& nothing) {
+  nothing = true;
+  int rc = nearest_head<T>(who, s, req, upper, out, "null output");
+  if (!rc) rc = pair_validate<T>(kind, who, s, table, n_conf, nothing);
+  return rc ? rc : pair_limits(who, s, kind);
+}
+template <typename T>
+static int clearance_run(ListKind kind, const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const hfcl_distance_request* req,
+                         double upper, hfcl_scene_clearance* d_out, typename SceneTypes<T>::R* d_min, size_t* n_evaluated, SceneCountSlots* counts,
+                         hipStream_t st) {
+  return kind == ListKind::Env ? nearest_env_run<T>(who, s, d_table, n_conf, req, upper, d_out, d_min, n_evaluated, counts, st)
+                               : nearest_self_run<T>(who, s, d_table, n_conf, req, upper, d_out, d_min, n_evaluated, counts, st);
+}
+template <typename T>
+static int clearance_device(ListKind kind, const char* who, hfcl_scene* s, const void* d_table, size_t n_conf, const hfcl_distance_request* req,
+                            double upper, hfcl_scene_clearance* d_out, typename SceneTypes<T>::R* d_min, size_t* n_evaluated, hipStream_t st) {
   bool nothing;
-  const int rc = nearest_env_validate<T>(who, s, d_table, n_conf, req, upper, d_out, nothing);
+  const int rc = clearance_validate<T>(kind, who, s, d_table, n_conf, req, upper, d_out, nothing);
   if (rc) return rc;
   if (n_evaluated) n_evaluated[0] = n_evaluated[1] = 0;
   if (!n_conf) return HFCL_OK;
-  hfcl_lib* lib = s->lib;
-  HIP_TRY(hipSetDevice(lib->device));
-  if (nothing) {  // no moving object: every configuration is one without records
-    NselfCombineArgs g{};
-    g.n_conf = n_conf;
-    g.out = d_out;
-    g.min_out = d_min;
-    launch_nself_combine(st, g, std::is_same<T, float>::value);
+  HIP_TRY(hipSetDevice(s->lib->device));
+  if (nothing) {  // no pair: every configuration is one without records
+    clearance_combine(nullptr, n_conf, d_out, d_min, std::is_same<T, float>::value, st);
     HIP_TRY(hipGetLastError());
     return HFCL_OK;
   }
-  return nearest_env_run<T>(who, s, d_table, n_conf, req, upper, d_out, d_min, n_evaluated, nullptr, st);
+  return clearance_run<T>(kind, who, s, d_table, n_conf, req, upper, d_out, d_min, n_evaluated, nullptr, st);
 }
-
 template <typename T>
-static int nearest_env_host(const char* who, hfcl_scene* s, const void* table, size_t n_conf, const hfcl_distance_request* req, double upper,
-                            hfcl_scene_clearance* out, typename SceneTypes<T>::R* min_records, size_t* n_evaluated) {
+static int clearance_host(ListKind kind, const char* who, hfcl_scene* s, const void* table, size_t n_conf, const hfcl_distance_request* req,
+                          double upper, hfcl_scene_clearance* out, typename SceneTypes<T>::R* min_records, size_t* n_evaluated) {
   using R = typename SceneTypes<T>::R;
   bool nothing;
-  int rc = nearest_env_validate<T>(who, s, table, n_conf, req, upper, out, nothing);
+  const int rc = clearance_validate<T>(kind, who, s, table, n_conf, req, upper, out, nothing);
   if (rc) return rc;
   if (n_evaluated) n_evaluated[0] = n_evaluated[1] = 0;
   if (!n_conf) return HFCL_OK;
-  if (nothing) {
+  if (nothing) {  // no pair: the combine of no list, on the host
     const hfcl_scene_summary* no_summary[2] = {nullptr, nullptr};
     const uint32_t* no_pairs[2] = {nullptr, nullptr};
     const uint64_t* no_begin[2] = {nullptr, nullptr};
@@ -1914,36 +1713,10 @@ static int nearest_env_host(const char* who, hfcl_scene* s, const void* table, s
     for (size_t c = 0; c < n_conf; ++c) nself_combine<R>(c, no_summary, no_pairs, no_begin, no_rec, out[c], min_records ? &min_records[c] : nullptr);
     return HFCL_OK;
   }
-  hfcl_lib* lib = s->lib;
-  hfcl_lib::SceneWs& w = lib->scene;
-  HIP_TRY(hipSetDevice(lib->device));
-  rc = scene_host_stream(w);
-  if (rc) return rc;
-  HIP_TRY(w.d_ns_out.grow(n_conf));
-  if (min_records) HIP_TRY(w.d_minrec.grow(n_conf * sizeof(R)));
-  rc = SceneCountSlots::ready(w);
-  if (rc) return rc;
-  SceneCountSlots counts(lib);  // (ends after finish has waited for the streams)
-  auto finish = [&](int code) {  // nothing of this call stays in flight, whatever happened
-    const bool synced = hipStreamSynchronize(w.s_cmp) == hipSuccess;
-    if (lib->side) hipStreamSynchronize(lib->side);
-    if (code == HFCL_OK && synced) counts.harvest_rest();
-    if (code == HFCL_OK && !synced) {
-      set_error(std::string(who) + ": the device reported an error");
-      return int(HFCL_ERR_HIP);
-    }
-    return code;
-  };
-  rc = scene_table_in(w, table, n_conf * s->n_moving * SceneTypes<T>::WIDTH * sizeof(T));
-  if (!rc) rc = nearest_env_run<T>(who, s, w.d_table, n_conf, req, upper, w.d_ns_out, min_records ? static_cast<R*>(w.d_minrec.get()) : nullptr,
-                                   n_evaluated, &counts, w.s_cmp);
-  if (!rc && hipMemcpyAsync(out, w.d_ns_out, n_conf * sizeof(hfcl_scene_clearance), hipMemcpyDeviceToHost, w.s_cmp) != hipSuccess) rc = HFCL_ERR_HIP;
-  if (!rc && min_records && hipMemcpyAsync(min_records, w.d_minrec, n_conf * sizeof(R), hipMemcpyDeviceToHost, w.s_cmp) != hipSuccess)
-    rc = HFCL_ERR_HIP;
-  rc = finish(rc);
-  if (rc) return rc;
-  lib->last_host = true;
-  return host_batch_checks(lib, nullptr, req);
+  return nearest_host_shell<T>(who, s, table, pair_rows(s, kind), n_conf, req, s->lib->scene.d_ns_out, out, min_records,
+                               [&](const void* d_table, hfcl_scene_clearance* d_out, R* d_min, SceneCountSlots* counts, hipStream_t st) {
+                                 return clearance_run<T>(kind, who, s, d_table, n_conf, req, upper, d_out, d_min, n_evaluated, counts, st);
+                               });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2227,25 +2000,25 @@ int hfcl_scene_distance_listed_device_f32(hfcl_scene* s, const float* d_object_p
 int hfcl_scene_collide_culled(hfcl_scene* s, const double* object_tf, size_t n_conf, double inflate, const hfcl_collision_request* req,
                               hfcl_result* out, size_t out_capacity, uint64_t* query_ids_out, uint64_t* conf_begin_out,
                               hfcl_scene_summary* summary, const hfcl_guess* guess_in, hfcl_guess* guess_out, size_t* n_listed) {
-  const SceneCull cull{inflate, out_capacity, query_ids_out, conf_begin_out, n_listed};
+  const SceneCull cull{ListKind::Culled, inflate, out_capacity, query_ids_out, nullptr, conf_begin_out, n_listed};
   return scene_host<double>("hfcl_scene_collide_culled", s, object_tf, n_conf, req, nullptr, out, summary, guess_in, guess_out, &cull);
 }
 int hfcl_scene_distance_culled(hfcl_scene* s, const double* object_tf, size_t n_conf, double inflate, const hfcl_distance_request* req,
                                hfcl_result* out, size_t out_capacity, uint64_t* query_ids_out, uint64_t* conf_begin_out,
                                hfcl_scene_summary* summary, const hfcl_guess* guess_in, hfcl_guess* guess_out, size_t* n_listed) {
-  const SceneCull cull{inflate, out_capacity, query_ids_out, conf_begin_out, n_listed};
+  const SceneCull cull{ListKind::Culled, inflate, out_capacity, query_ids_out, nullptr, conf_begin_out, n_listed};
   return scene_host<double>("hfcl_scene_distance_culled", s, object_tf, n_conf, nullptr, req, out, summary, guess_in, guess_out, &cull);
 }
 int hfcl_scene_collide_culled_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, double inflate, const hfcl_collision_request* req,
                                   hfcl_result_f32* out, size_t out_capacity, uint64_t* query_ids_out, uint64_t* conf_begin_out,
                                   hfcl_scene_summary* summary, size_t* n_listed) {
-  const SceneCull cull{inflate, out_capacity, query_ids_out, conf_begin_out, n_listed};
+  const SceneCull cull{ListKind::Culled, inflate, out_capacity, query_ids_out, nullptr, conf_begin_out, n_listed};
   return scene_host<float>("hfcl_scene_collide_culled_f32", s, object_pose, n_conf, req, nullptr, out, summary, nullptr, nullptr, &cull);
 }
 int hfcl_scene_distance_culled_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, double inflate, const hfcl_distance_request* req,
                                    hfcl_result_f32* out, size_t out_capacity, uint64_t* query_ids_out, uint64_t* conf_begin_out,
                                    hfcl_scene_summary* summary, size_t* n_listed) {
-  const SceneCull cull{inflate, out_capacity, query_ids_out, conf_begin_out, n_listed};
+  const SceneCull cull{ListKind::Culled, inflate, out_capacity, query_ids_out, nullptr, conf_begin_out, n_listed};
   return scene_host<float>("hfcl_scene_distance_culled_f32", s, object_pose, n_conf, nullptr, req, out, summary, nullptr, nullptr, &cull);
 }
 
@@ -2255,85 +2028,79 @@ int hfcl_scene_distance_culled_f32(hfcl_scene* s, const float* object_pose, size
 int hfcl_scene_self_pairs(hfcl_scene* s, const double* object_tf, size_t n_conf, double inflate, uint32_t* pairs, size_t capacity,
                           uint64_t* conf_begin, size_t* n_listed) {
   PAIRS_ENTRY;
-  return self_pairs_host<double>("hfcl_scene_self_pairs", s, object_tf, n_conf, inflate, pairs, capacity, conf_begin, n_listed);
+  return pairs_host<double>(ListKind::Self, "hfcl_scene_self_pairs", s, object_tf, n_conf, inflate, pairs, capacity, conf_begin, n_listed);
 }
 int hfcl_scene_self_pairs_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, double inflate, uint32_t* pairs, size_t capacity,
                               uint64_t* conf_begin, size_t* n_listed) {
   PAIRS_ENTRY;
-  return self_pairs_host<float>("hfcl_scene_self_pairs_f32", s, object_pose, n_conf, inflate, pairs, capacity, conf_begin, n_listed);
+  return pairs_host<float>(ListKind::Self, "hfcl_scene_self_pairs_f32", s, object_pose, n_conf, inflate, pairs, capacity, conf_begin, n_listed);
 }
 int hfcl_scene_self_pairs_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, double inflate, uint32_t* d_pairs, size_t capacity,
                                  uint64_t* d_conf_begin, uint64_t* d_n_listed, void* stream) {
   PAIRS_ENTRY;
-  return self_pairs_device<double>("hfcl_scene_self_pairs_device", s, d_object_tf, n_conf, inflate, d_pairs, capacity, d_conf_begin, d_n_listed,
+  return pairs_device<double>(ListKind::Self, "hfcl_scene_self_pairs_device", s, d_object_tf, n_conf, inflate, d_pairs, capacity, d_conf_begin, d_n_listed,
                                    (hipStream_t)stream);
 }
 int hfcl_scene_self_pairs_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, double inflate, uint32_t* d_pairs, size_t capacity,
                                      uint64_t* d_conf_begin, uint64_t* d_n_listed, void* stream) {
   PAIRS_ENTRY;
-  return self_pairs_device<float>("hfcl_scene_self_pairs_device_f32", s, d_object_pose, n_conf, inflate, d_pairs, capacity, d_conf_begin,
+  return pairs_device<float>(ListKind::Self, "hfcl_scene_self_pairs_device_f32", s, d_object_pose, n_conf, inflate, d_pairs, capacity, d_conf_begin,
                                   d_n_listed, (hipStream_t)stream);
 }
 int hfcl_scene_collide_pairs_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const uint32_t* d_pairs, size_t n_listed,
                                     const uint64_t* d_conf_begin, const hfcl_collision_request* req, hfcl_result* d_out,
                                     hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in, hfcl_guess* d_guess_out, void* stream) {
   PAIRS_ENTRY;
-  return scene_pairs_device<double>("hfcl_scene_collide_pairs_device", s, d_object_tf, n_conf, d_pairs, n_listed, d_conf_begin, req, nullptr, d_out,
+  return scene_pairs_device<double>(ListKind::Self, "hfcl_scene_collide_pairs_device", s, d_object_tf, n_conf, d_pairs, n_listed, d_conf_begin, req, nullptr, d_out,
                                     d_summary, d_guess_in, d_guess_out, (hipStream_t)stream);
 }
 int hfcl_scene_distance_pairs_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const uint32_t* d_pairs, size_t n_listed,
                                      const uint64_t* d_conf_begin, const hfcl_distance_request* req, hfcl_result* d_out,
                                      hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in, hfcl_guess* d_guess_out, void* stream) {
   PAIRS_ENTRY;
-  return scene_pairs_device<double>("hfcl_scene_distance_pairs_device", s, d_object_tf, n_conf, d_pairs, n_listed, d_conf_begin, nullptr, req, d_out,
+  return scene_pairs_device<double>(ListKind::Self, "hfcl_scene_distance_pairs_device", s, d_object_tf, n_conf, d_pairs, n_listed, d_conf_begin, nullptr, req, d_out,
                                     d_summary, d_guess_in, d_guess_out, (hipStream_t)stream);
 }
 int hfcl_scene_collide_pairs_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, const uint32_t* d_pairs, size_t n_listed,
                                         const uint64_t* d_conf_begin, const hfcl_collision_request* req, hfcl_result_f32* d_out,
                                         hfcl_scene_summary* d_summary, void* stream) {
   PAIRS_ENTRY;
-  return scene_pairs_device<float>("hfcl_scene_collide_pairs_device_f32", s, d_object_pose, n_conf, d_pairs, n_listed, d_conf_begin, req, nullptr,
+  return scene_pairs_device<float>(ListKind::Self, "hfcl_scene_collide_pairs_device_f32", s, d_object_pose, n_conf, d_pairs, n_listed, d_conf_begin, req, nullptr,
                                    d_out, d_summary, nullptr, nullptr, (hipStream_t)stream);
 }
 int hfcl_scene_distance_pairs_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, const uint32_t* d_pairs, size_t n_listed,
                                          const uint64_t* d_conf_begin, const hfcl_distance_request* req, hfcl_result_f32* d_out,
                                          hfcl_scene_summary* d_summary, void* stream) {
   PAIRS_ENTRY;
-  return scene_pairs_device<float>("hfcl_scene_distance_pairs_device_f32", s, d_object_pose, n_conf, d_pairs, n_listed, d_conf_begin, nullptr, req,
+  return scene_pairs_device<float>(ListKind::Self, "hfcl_scene_distance_pairs_device_f32", s, d_object_pose, n_conf, d_pairs, n_listed, d_conf_begin, nullptr, req,
                                    d_out, d_summary, nullptr, nullptr, (hipStream_t)stream);
-}
-static SceneCull self_form(double inflate, size_t out_capacity, uint32_t* pairs_out, uint64_t* conf_begin_out, size_t* n_listed) {
-  SceneCull cull{inflate, out_capacity, nullptr, conf_begin_out, n_listed};
-  cull.self = true;
-  cull.pairs_out = pairs_out;
-  return cull;
 }
 int hfcl_scene_collide_self(hfcl_scene* s, const double* object_tf, size_t n_conf, double inflate, const hfcl_collision_request* req,
                             hfcl_result* out, size_t out_capacity, uint32_t* pairs_out, uint64_t* conf_begin_out, hfcl_scene_summary* summary,
                             const hfcl_guess* guess_in, hfcl_guess* guess_out, size_t* n_listed) {
   PAIRS_ENTRY;
-  const SceneCull cull = self_form(inflate, out_capacity, pairs_out, conf_begin_out, n_listed);
+  const SceneCull cull{ListKind::Self, inflate, out_capacity, nullptr, pairs_out, conf_begin_out, n_listed};
   return scene_host<double>("hfcl_scene_collide_self", s, object_tf, n_conf, req, nullptr, out, summary, guess_in, guess_out, &cull);
 }
 int hfcl_scene_distance_self(hfcl_scene* s, const double* object_tf, size_t n_conf, double inflate, const hfcl_distance_request* req,
                              hfcl_result* out, size_t out_capacity, uint32_t* pairs_out, uint64_t* conf_begin_out, hfcl_scene_summary* summary,
                              const hfcl_guess* guess_in, hfcl_guess* guess_out, size_t* n_listed) {
   PAIRS_ENTRY;
-  const SceneCull cull = self_form(inflate, out_capacity, pairs_out, conf_begin_out, n_listed);
+  const SceneCull cull{ListKind::Self, inflate, out_capacity, nullptr, pairs_out, conf_begin_out, n_listed};
   return scene_host<double>("hfcl_scene_distance_self", s, object_tf, n_conf, nullptr, req, out, summary, guess_in, guess_out, &cull);
 }
 int hfcl_scene_collide_self_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, double inflate, const hfcl_collision_request* req,
                                 hfcl_result_f32* out, size_t out_capacity, uint32_t* pairs_out, uint64_t* conf_begin_out,
                                 hfcl_scene_summary* summary, size_t* n_listed) {
   PAIRS_ENTRY;
-  const SceneCull cull = self_form(inflate, out_capacity, pairs_out, conf_begin_out, n_listed);
+  const SceneCull cull{ListKind::Self, inflate, out_capacity, nullptr, pairs_out, conf_begin_out, n_listed};
   return scene_host<float>("hfcl_scene_collide_self_f32", s, object_pose, n_conf, req, nullptr, out, summary, nullptr, nullptr, &cull);
 }
 int hfcl_scene_distance_self_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, double inflate, const hfcl_distance_request* req,
                                  hfcl_result_f32* out, size_t out_capacity, uint32_t* pairs_out, uint64_t* conf_begin_out,
                                  hfcl_scene_summary* summary, size_t* n_listed) {
   PAIRS_ENTRY;
-  const SceneCull cull = self_form(inflate, out_capacity, pairs_out, conf_begin_out, n_listed);
+  const SceneCull cull{ListKind::Self, inflate, out_capacity, nullptr, pairs_out, conf_begin_out, n_listed};
   return scene_host<float>("hfcl_scene_distance_self_f32", s, object_pose, n_conf, nullptr, req, out, summary, nullptr, nullptr, &cull);
 }
 
@@ -2396,24 +2163,24 @@ size_t hfcl_scene_num_groups(const hfcl_scene* s) { return s ? s->n_groups : 0; 
 int hfcl_scene_nearest_self(hfcl_scene* s, const double* object_tf, size_t n_conf, const hfcl_distance_request* req, double upper_bound,
                             hfcl_scene_clearance* out, hfcl_result* min_records, size_t* n_evaluated) {
   PAIRS_ENTRY;
-  return nearest_self_host<double>("hfcl_scene_nearest_self", s, object_tf, n_conf, req, upper_bound, out, min_records, n_evaluated);
+  return clearance_host<double>(ListKind::Self, "hfcl_scene_nearest_self", s, object_tf, n_conf, req, upper_bound, out, min_records, n_evaluated);
 }
 int hfcl_scene_nearest_self_f32(hfcl_scene* s, const float* object_pose, size_t n_conf, const hfcl_distance_request* req, double upper_bound,
                                 hfcl_scene_clearance* out, hfcl_result_f32* min_records, size_t* n_evaluated) {
   PAIRS_ENTRY;
-  return nearest_self_host<float>("hfcl_scene_nearest_self_f32", s, object_pose, n_conf, req, upper_bound, out, min_records, n_evaluated);
+  return clearance_host<float>(ListKind::Self, "hfcl_scene_nearest_self_f32", s, object_pose, n_conf, req, upper_bound, out, min_records, n_evaluated);
 }
 int hfcl_scene_nearest_self_device(hfcl_scene* s, const double* d_object_tf, size_t n_conf, const hfcl_distance_request* req, double upper_bound,
                                    hfcl_scene_clearance* d_out, hfcl_result* d_min_records, size_t* n_evaluated, void* stream) {
   PAIRS_ENTRY;
-  return nearest_self_device<double>("hfcl_scene_nearest_self_device", s, d_object_tf, n_conf, req, upper_bound, d_out, d_min_records, n_evaluated,
+  return clearance_device<double>(ListKind::Self, "hfcl_scene_nearest_self_device", s, d_object_tf, n_conf, req, upper_bound, d_out, d_min_records, n_evaluated,
                                      (hipStream_t)stream);
 }
 int hfcl_scene_nearest_self_device_f32(hfcl_scene* s, const float* d_object_pose, size_t n_conf, const hfcl_distance_request* req,
                                        double upper_bound, hfcl_scene_clearance* d_out, hfcl_result_f32* d_min_records, size_t* n_evaluated,
                                        void* stream) {
   PAIRS_ENTRY;
-  return nearest_self_device<float>("hfcl_scene_nearest_self_device_f32", s, d_object_pose, n_conf, req, upper_bound, d_out, d_min_records,
+  return clearance_device<float>(ListKind::Self, "hfcl_scene_nearest_self_device_f32", s, d_object_pose, n_conf, req, upper_bound, d_out, d_min_records,
                                     n_evaluated, (hipStream_t)stream);
 }
 
@@ -2457,84 +2224,79 @@ int hfcl_scene_environment_aabbs(hfcl_scene* s, double* aabbs_out, double* tile_
 int hfcl_scene_env_pairs(hfcl_scene* s, const double* moving_tf, size_t n_conf, double inflate, uint32_t* pairs, size_t capacity,
                          uint64_t* conf_begin, size_t* n_listed) {
   PAIRS_ENTRY;
-  return env_pairs_host<double>("hfcl_scene_env_pairs", s, moving_tf, n_conf, inflate, pairs, capacity, conf_begin, n_listed);
+  return pairs_host<double>(ListKind::Env, "hfcl_scene_env_pairs", s, moving_tf, n_conf, inflate, pairs, capacity, conf_begin, n_listed);
 }
 int hfcl_scene_env_pairs_f32(hfcl_scene* s, const float* moving_pose, size_t n_conf, double inflate, uint32_t* pairs, size_t capacity,
                              uint64_t* conf_begin, size_t* n_listed) {
   PAIRS_ENTRY;
-  return env_pairs_host<float>("hfcl_scene_env_pairs_f32", s, moving_pose, n_conf, inflate, pairs, capacity, conf_begin, n_listed);
+  return pairs_host<float>(ListKind::Env, "hfcl_scene_env_pairs_f32", s, moving_pose, n_conf, inflate, pairs, capacity, conf_begin, n_listed);
 }
 int hfcl_scene_env_pairs_device(hfcl_scene* s, const double* d_moving_tf, size_t n_conf, double inflate, uint32_t* d_pairs, size_t capacity,
                                 uint64_t* d_conf_begin, uint64_t* d_n_listed, void* stream) {
   PAIRS_ENTRY;
-  return env_pairs_device<double>("hfcl_scene_env_pairs_device", s, d_moving_tf, n_conf, inflate, d_pairs, capacity, d_conf_begin, d_n_listed,
+  return pairs_device<double>(ListKind::Env, "hfcl_scene_env_pairs_device", s, d_moving_tf, n_conf, inflate, d_pairs, capacity, d_conf_begin, d_n_listed,
                                   (hipStream_t)stream);
 }
 int hfcl_scene_env_pairs_device_f32(hfcl_scene* s, const float* d_moving_pose, size_t n_conf, double inflate, uint32_t* d_pairs,
                                     size_t capacity, uint64_t* d_conf_begin, uint64_t* d_n_listed, void* stream) {
   PAIRS_ENTRY;
-  return env_pairs_device<float>("hfcl_scene_env_pairs_device_f32", s, d_moving_pose, n_conf, inflate, d_pairs, capacity, d_conf_begin,
+  return pairs_device<float>(ListKind::Env, "hfcl_scene_env_pairs_device_f32", s, d_moving_pose, n_conf, inflate, d_pairs, capacity, d_conf_begin,
                                  d_n_listed, (hipStream_t)stream);
 }
 int hfcl_scene_collide_env_pairs_device(hfcl_scene* s, const double* d_moving_tf, size_t n_conf, const uint32_t* d_pairs, size_t n_listed,
                                         const uint64_t* d_conf_begin, const hfcl_collision_request* req, hfcl_result* d_out,
                                         hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in, hfcl_guess* d_guess_out, void* stream) {
   PAIRS_ENTRY;
-  return scene_env_pairs_device<double>("hfcl_scene_collide_env_pairs_device", s, d_moving_tf, n_conf, d_pairs, n_listed, d_conf_begin, req, nullptr,
+  return scene_pairs_device<double>(ListKind::Env, "hfcl_scene_collide_env_pairs_device", s, d_moving_tf, n_conf, d_pairs, n_listed, d_conf_begin, req, nullptr,
                                         d_out, d_summary, d_guess_in, d_guess_out, (hipStream_t)stream);
 }
 int hfcl_scene_distance_env_pairs_device(hfcl_scene* s, const double* d_moving_tf, size_t n_conf, const uint32_t* d_pairs, size_t n_listed,
                                          const uint64_t* d_conf_begin, const hfcl_distance_request* req, hfcl_result* d_out,
                                          hfcl_scene_summary* d_summary, const hfcl_guess* d_guess_in, hfcl_guess* d_guess_out, void* stream) {
   PAIRS_ENTRY;
-  return scene_env_pairs_device<double>("hfcl_scene_distance_env_pairs_device", s, d_moving_tf, n_conf, d_pairs, n_listed, d_conf_begin, nullptr, req,
+  return scene_pairs_device<double>(ListKind::Env, "hfcl_scene_distance_env_pairs_device", s, d_moving_tf, n_conf, d_pairs, n_listed, d_conf_begin, nullptr, req,
                                         d_out, d_summary, d_guess_in, d_guess_out, (hipStream_t)stream);
 }
 int hfcl_scene_collide_env_pairs_device_f32(hfcl_scene* s, const float* d_moving_pose, size_t n_conf, const uint32_t* d_pairs,
                                             size_t n_listed, const uint64_t* d_conf_begin, const hfcl_collision_request* req,
                                             hfcl_result_f32* d_out, hfcl_scene_summary* d_summary, void* stream) {
   PAIRS_ENTRY;
-  return scene_env_pairs_device<float>("hfcl_scene_collide_env_pairs_device_f32", s, d_moving_pose, n_conf, d_pairs, n_listed, d_conf_begin, req,
+  return scene_pairs_device<float>(ListKind::Env, "hfcl_scene_collide_env_pairs_device_f32", s, d_moving_pose, n_conf, d_pairs, n_listed, d_conf_begin, req,
                                        nullptr, d_out, d_summary, nullptr, nullptr, (hipStream_t)stream);
 }
 int hfcl_scene_distance_env_pairs_device_f32(hfcl_scene* s, const float* d_moving_pose, size_t n_conf, const uint32_t* d_pairs,
                                              size_t n_listed, const uint64_t* d_conf_begin, const hfcl_distance_request* req,
                                              hfcl_result_f32* d_out, hfcl_scene_summary* d_summary, void* stream) {
   PAIRS_ENTRY;
-  return scene_env_pairs_device<float>("hfcl_scene_distance_env_pairs_device_f32", s, d_moving_pose, n_conf, d_pairs, n_listed, d_conf_begin,
+  return scene_pairs_device<float>(ListKind::Env, "hfcl_scene_distance_env_pairs_device_f32", s, d_moving_pose, n_conf, d_pairs, n_listed, d_conf_begin,
                                        nullptr, req, d_out, d_summary, nullptr, nullptr, (hipStream_t)stream);
-}
-static SceneCull env_form(double inflate, size_t out_capacity, uint32_t* pairs_out, uint64_t* conf_begin_out, size_t* n_listed) {
-  SceneCull cull = self_form(inflate, out_capacity, pairs_out, conf_begin_out, n_listed);
-  cull.env = true;
-  return cull;
 }
 int hfcl_scene_collide_env(hfcl_scene* s, const double* moving_tf, size_t n_conf, double inflate, const hfcl_collision_request* req,
                            hfcl_result* out, size_t out_capacity, uint32_t* pairs_out, uint64_t* conf_begin_out, hfcl_scene_summary* summary,
                            const hfcl_guess* guess_in, hfcl_guess* guess_out, size_t* n_listed) {
   PAIRS_ENTRY;
-  const SceneCull cull = env_form(inflate, out_capacity, pairs_out, conf_begin_out, n_listed);
+  const SceneCull cull{ListKind::Env, inflate, out_capacity, nullptr, pairs_out, conf_begin_out, n_listed};
   return scene_host<double>("hfcl_scene_collide_env", s, moving_tf, n_conf, req, nullptr, out, summary, guess_in, guess_out, &cull);
 }
 int hfcl_scene_distance_env(hfcl_scene* s, const double* moving_tf, size_t n_conf, double inflate, const hfcl_distance_request* req,
                             hfcl_result* out, size_t out_capacity, uint32_t* pairs_out, uint64_t* conf_begin_out, hfcl_scene_summary* summary,
                             const hfcl_guess* guess_in, hfcl_guess* guess_out, size_t* n_listed) {
   PAIRS_ENTRY;
-  const SceneCull cull = env_form(inflate, out_capacity, pairs_out, conf_begin_out, n_listed);
+  const SceneCull cull{ListKind::Env, inflate, out_capacity, nullptr, pairs_out, conf_begin_out, n_listed};
   return scene_host<double>("hfcl_scene_distance_env", s, moving_tf, n_conf, nullptr, req, out, summary, guess_in, guess_out, &cull);
 }
 int hfcl_scene_collide_env_f32(hfcl_scene* s, const float* moving_pose, size_t n_conf, double inflate, const hfcl_collision_request* req,
                                hfcl_result_f32* out, size_t out_capacity, uint32_t* pairs_out, uint64_t* conf_begin_out,
                                hfcl_scene_summary* summary, size_t* n_listed) {
   PAIRS_ENTRY;
-  const SceneCull cull = env_form(inflate, out_capacity, pairs_out, conf_begin_out, n_listed);
+  const SceneCull cull{ListKind::Env, inflate, out_capacity, nullptr, pairs_out, conf_begin_out, n_listed};
   return scene_host<float>("hfcl_scene_collide_env_f32", s, moving_pose, n_conf, req, nullptr, out, summary, nullptr, nullptr, &cull);
 }
 int hfcl_scene_distance_env_f32(hfcl_scene* s, const float* moving_pose, size_t n_conf, double inflate, const hfcl_distance_request* req,
                                 hfcl_result_f32* out, size_t out_capacity, uint32_t* pairs_out, uint64_t* conf_begin_out,
                                 hfcl_scene_summary* summary, size_t* n_listed) {
   PAIRS_ENTRY;
-  const SceneCull cull = env_form(inflate, out_capacity, pairs_out, conf_begin_out, n_listed);
+  const SceneCull cull{ListKind::Env, inflate, out_capacity, nullptr, pairs_out, conf_begin_out, n_listed};
   return scene_host<float>("hfcl_scene_distance_env_f32", s, moving_pose, n_conf, nullptr, req, out, summary, nullptr, nullptr, &cull);
 }
 
@@ -2542,24 +2304,24 @@ int hfcl_scene_distance_env_f32(hfcl_scene* s, const float* moving_pose, size_t 
 int hfcl_scene_nearest_env(hfcl_scene* s, const double* moving_tf, size_t n_conf, const hfcl_distance_request* req, double upper_bound,
                            hfcl_scene_clearance* out, hfcl_result* min_records, size_t* n_evaluated) {
   PAIRS_ENTRY;
-  return nearest_env_host<double>("hfcl_scene_nearest_env", s, moving_tf, n_conf, req, upper_bound, out, min_records, n_evaluated);
+  return clearance_host<double>(ListKind::Env, "hfcl_scene_nearest_env", s, moving_tf, n_conf, req, upper_bound, out, min_records, n_evaluated);
 }
 int hfcl_scene_nearest_env_f32(hfcl_scene* s, const float* moving_pose, size_t n_conf, const hfcl_distance_request* req, double upper_bound,
                                hfcl_scene_clearance* out, hfcl_result_f32* min_records, size_t* n_evaluated) {
   PAIRS_ENTRY;
-  return nearest_env_host<float>("hfcl_scene_nearest_env_f32", s, moving_pose, n_conf, req, upper_bound, out, min_records, n_evaluated);
+  return clearance_host<float>(ListKind::Env, "hfcl_scene_nearest_env_f32", s, moving_pose, n_conf, req, upper_bound, out, min_records, n_evaluated);
 }
 int hfcl_scene_nearest_env_device(hfcl_scene* s, const double* d_moving_tf, size_t n_conf, const hfcl_distance_request* req, double upper_bound,
                                   hfcl_scene_clearance* d_out, hfcl_result* d_min_records, size_t* n_evaluated, void* stream) {
   PAIRS_ENTRY;
-  return nearest_env_device<double>("hfcl_scene_nearest_env_device", s, d_moving_tf, n_conf, req, upper_bound, d_out, d_min_records, n_evaluated,
+  return clearance_device<double>(ListKind::Env, "hfcl_scene_nearest_env_device", s, d_moving_tf, n_conf, req, upper_bound, d_out, d_min_records, n_evaluated,
                                     (hipStream_t)stream);
 }
 int hfcl_scene_nearest_env_device_f32(hfcl_scene* s, const float* d_moving_pose, size_t n_conf, const hfcl_distance_request* req,
                                       double upper_bound, hfcl_scene_clearance* d_out, hfcl_result_f32* d_min_records, size_t* n_evaluated,
                                       void* stream) {
   PAIRS_ENTRY;
-  return nearest_env_device<float>("hfcl_scene_nearest_env_device_f32", s, d_moving_pose, n_conf, req, upper_bound, d_out, d_min_records,
+  return clearance_device<float>(ListKind::Env, "hfcl_scene_nearest_env_device_f32", s, d_moving_pose, n_conf, req, upper_bound, d_out, d_min_records,
                                    n_evaluated, (hipStream_t)stream);
 }
 #undef PAIRS_ENTRY

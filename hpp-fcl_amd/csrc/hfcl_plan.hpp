@@ -1,11 +1,12 @@
 // hfcl_plan.hpp -- the planning arithmetic of the host units: the chunk plan of the host pipeline (hfcl_host.hip: host_batch), and the chunk
-// sizes, fold-partial bounds and list capacities of the scene calls (hfcl_host_scene.hip).  Plain C++, no HIP header: tests/plan_harness
-// builds it with the host compiler.
+// sizes, fold-partial bounds, list capacities and sweep plans of the scene calls (hfcl_host_scene.hip).  Plain C++, no HIP header:
+// tests/plan_harness builds it with the host compiler.
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <vector>
 
+#include "hfcl_env.hpp"
 #include "hfcl_scene.hpp"
 
 // Chunk bounds of a host batch of n > 0 pairs: chunk k = [bounds[k], bounds[k + 1]), bounds[0] = 0, bounds.back() = n.
@@ -71,3 +72,54 @@ inline size_t scene_listed_pieces_bound(size_t n_pairs, size_t n_conf) {
 }
 // entries a list of the survivors of `total` queries is first given room for (a longer one is made again in a buffer of its size)
 inline size_t list_capacity_guess(size_t total) { return std::min<size_t>(total, std::max<size_t>(total / 8, 4096)); }
+
+// ---- the sweeps that make a list of pairs (hfcl_host_scene.hip: SelfSweep, EnvSweep) ---------------------------------------------
+// (a sweep has rows: n_conf > 0 and n > 0 / nm > 0 -- the callers answer an empty table before they plan)
+// configurations whose boxes a chunk of `per` row blocks can touch: the whole ones inside it and a cut one at either end
+inline size_t sweep_conf_per_chunk(size_t n_conf, uint64_t per, uint32_t blocks_per_conf) {
+  return std::min<size_t>(n_conf, size_t(per / blocks_per_conf) + 2);
+}
+// The all-pairs sweep over n_conf configurations of n objects (hfcl_pairs.hpp): small -- a wave per configuration -- up to the option
+// scene_pairs_small_max (at most PAIRS_SMALL_MAX); `per` row blocks a chunk (chunk_option: option scene_cull_chunk, rows); chunk_rows:
+// table rows a chunk's row arrays hold
+struct SelfSweepPlan {
+  bool small;
+  hfcl::PairsGeometry geo;
+  uint64_t n_blocks, per;
+  size_t conf_per_chunk;
+  uint64_t chunk_rows;
+};
+inline SelfSweepPlan self_sweep_plan(uint32_t n, size_t n_conf, uint32_t small_max_option, uint64_t chunk_option) {
+  SelfSweepPlan p;
+  p.small = n <= std::min(small_max_option, hfcl::PAIRS_SMALL_MAX);
+  p.geo = hfcl::pairs_geometry(n, p.small);
+  p.n_blocks = uint64_t(n_conf) * p.geo.blocks_per_conf;
+  p.per = hfcl::pairs_chunk_blocks(p.geo, p.n_blocks, chunk_option);
+  p.conf_per_chunk = sweep_conf_per_chunk(n_conf, p.per, p.geo.blocks_per_conf);
+  p.chunk_rows = std::min<uint64_t>(p.per * p.geo.rows_per_block, uint64_t(n_conf) * n);
+  return p;
+}
+// tiles per span of the environment sweep: the option scene_env_span as given, or (0) env_auto_span for the call's row blocks
+inline uint32_t env_sweep_span(uint32_t span_option, uint32_t tiles, uint64_t n_blocks, int n_cus) {
+  return span_option ? span_option : hfcl::env_auto_span(tiles, n_blocks, uint32_t(std::max(n_cus, 1)), hfcl::ENV_AUTO_PER_CU);
+}
+// The sweep of nm moving rows against their own and ne environment columns (hfcl_env.hpp): rows -- the row blocks, never small --, geo --
+// the column tiles in spans --, `per` row blocks a chunk; chunk_rows: moving rows of a chunk, scan_rows: its (row, span) counts
+struct EnvSweepPlan {
+  hfcl::PairsGeometry rows;
+  hfcl::EnvGeometry geo;
+  uint64_t n_blocks, per;
+  size_t conf_per_chunk;
+  uint64_t chunk_rows, scan_rows;
+};
+inline EnvSweepPlan env_sweep_plan(uint32_t nm, uint32_t ne, size_t n_conf, uint32_t span_option, int n_cus, uint64_t chunk_option) {
+  EnvSweepPlan p;
+  p.rows = hfcl::pairs_geometry(nm, false);
+  p.n_blocks = uint64_t(n_conf) * p.rows.blocks_per_conf;
+  p.geo = hfcl::env_geometry(nm, ne, env_sweep_span(span_option, hfcl::env_geometry(nm, ne, 0u).tiles, p.n_blocks, n_cus));
+  p.per = hfcl::env_chunk_blocks(p.geo, p.n_blocks, chunk_option);
+  p.conf_per_chunk = sweep_conf_per_chunk(n_conf, p.per, p.rows.blocks_per_conf);
+  p.chunk_rows = std::min<uint64_t>(p.per * p.rows.rows_per_block, uint64_t(n_conf) * nm);
+  p.scan_rows = p.chunk_rows * p.geo.n_spans;
+  return p;
+}

@@ -18,3 +18,19 @@ extern "C" uint64_t ph_scene_pieces_bound(uint64_t n_pairs, uint64_t m) { return
 extern "C" uint64_t ph_scene_listed_pieces_bound(uint64_t n_pairs, uint64_t n_conf) { return scene_listed_pieces_bound(size_t(n_pairs), size_t(n_conf)); }
 extern "C" uint64_t ph_list_capacity_guess(uint64_t total) { return list_capacity_guess(size_t(total)); }
 extern "C" uint64_t ph_scene_piece_of(uint64_t q, uint32_t n_pairs) { return hfcl::scene_piece_of(q, n_pairs); }
+
+// the sweep plans: the members in the order of the header's structs, `small` / the geometry flattened
+extern "C" uint64_t ph_sweep_conf_per_chunk(uint64_t n_conf, uint64_t per, uint32_t blocks_per_conf) { return sweep_conf_per_chunk(size_t(n_conf), per, blocks_per_conf); }
+extern "C" uint64_t ph_env_sweep_span(uint32_t span_option, uint32_t tiles, uint64_t n_blocks, int n_cus) { return env_sweep_span(span_option, tiles, n_blocks, n_cus); }
+// out: small, rows_per_block, blocks_per_conf, n_blocks, per, conf_per_chunk, chunk_rows
+extern "C" void ph_self_sweep_plan(uint32_t n, uint64_t n_conf, uint32_t small_max_option, uint64_t chunk_option, uint64_t* out) {
+  const SelfSweepPlan p = self_sweep_plan(n, size_t(n_conf), small_max_option, chunk_option);
+  const uint64_t v[7] = {p.small, p.geo.rows_per_block, p.geo.blocks_per_conf, p.n_blocks, p.per, p.conf_per_chunk, p.chunk_rows};
+  for (int k = 0; k < 7; ++k) out[k] = v[k];
+}
+// out: blocks_per_conf, tiles_moving, tiles, span_len, n_spans, n_blocks, per, conf_per_chunk, chunk_rows, scan_rows
+extern "C" void ph_env_sweep_plan(uint32_t nm, uint32_t ne, uint64_t n_conf, uint32_t span_option, int n_cus, uint64_t chunk_option, uint64_t* out) {
+  const EnvSweepPlan p = env_sweep_plan(nm, ne, size_t(n_conf), span_option, n_cus, chunk_option);
+  const uint64_t v[10] = {p.rows.blocks_per_conf, p.geo.tiles_moving, p.geo.tiles, p.geo.span_len, p.geo.n_spans, p.n_blocks, p.per, p.conf_per_chunk, p.chunk_rows, p.scan_rows};
+  for (int k = 0; k < 10; ++k) out[k] = v[k];
+}

@@ -3,7 +3,8 @@ call keeps COUNT_SLOTS = 8 pinned slots; chunk k uses slot k % 8 once chunk k - 
 test_scene_gpu.py::test_unsupported_pair_kind -- three shapes, seven objects, 21 pairs, 2 configurations: 42 queries -- in chunks of
 0 (one chunk), 6, 5 and 2 queries is 1, 7, 9 and 21 chunks: fewer than eight, one more than eight, more than twice eight.  The yardsticks:
 the per-pair host call on the expanded arrays (hfcl_scene_distance, hfcl_scene_collide), the same call in one chunk (the culled form,
-hfcl_scene_nearest).  Chunks that run split are covered by the cfg5 scene tests at their size."""
+hfcl_scene_nearest, and the host forms on lists of pairs made on the device: hfcl_scene_collide_self, hfcl_scene_collide_env,
+hfcl_scene_nearest_self, hfcl_scene_nearest_env).  Chunks that run split are covered by the cfg5 scene tests at their size."""
 import ctypes as C
 
 import numpy as np
@@ -125,6 +126,80 @@ def test_listed_counts_equal_the_one_chunk_call(pkg, small, one_chunk, form, chu
     if form == "culled":
         assert n_listed == N_CONF * small.n_pairs
         assert counts["unsupported"] == N_CONF * small.n_tri
+    assert rc == ref_rc, (form, chunk, rc, ref_rc)
+    assert rc == (abi.ERR_UNSUPPORTED_PAIR if counts["unsupported"] else abi.OK)
+    assert counts == ref_counts, (form, chunk)
+
+
+# ---- the host forms on a list of pairs made on the device, and the clearance calls on such lists -------------------------------------
+# collide_self / collide_env at inflate 10 list every pair -- 21 a configuration of the seven objects; 6 + 12 = 18 with the first four
+# moving and the other three the environment --: 42 and 36 entries, in chunks of 0, 6, 5, 2 entries 1 / 7 / 9 / 21 and 1 / 6 / 8 / 18 chunks.
+# nearest_self / nearest_env (no upper bound): scene_chunk cuts each pass's narrow phase.  The yardstick: the same call in one chunk.
+N_MOVING = 4
+
+
+def _made(pkg, small, chunk, env):
+    abi, d = pkg.abi, pkg.engine.dll()
+    table = np.ascontiguousarray(small.table[:, :N_MOVING]) if env else small.table
+    cap = N_CONF * small.n_pairs
+    small.lib.set_option("scene_chunk", chunk)
+    req = abi.default_collision_request()
+    out = np.zeros(cap, dtype=abi.RESULT_DTYPE)
+    pairs = np.zeros((cap, 2), dtype=np.uint32)
+    summ = np.zeros(N_CONF, dtype=abi.SCENE_SUMMARY_DTYPE)
+    k = C.c_size_t(0)
+    fn = d.hfcl_scene_collide_env if env else d.hfcl_scene_collide_self
+    rc = fn(small.scene._h, abi.ptr(table), C.c_size_t(N_CONF), C.c_double(10.0), C.byref(req), abi.ptr(out), C.c_size_t(cap), abi.ptr(pairs),
+            None, abi.ptr(summ), None, None, C.byref(k))
+    return rc, int(k.value), small.lib.last_bucket_counts()
+
+
+def _clearance(pkg, small, chunk, env):
+    abi, d = pkg.abi, pkg.engine.dll()
+    table = np.ascontiguousarray(small.table[:, :N_MOVING]) if env else small.table
+    small.lib.set_option("scene_chunk", chunk)
+    req = abi.default_distance_request()
+    out = np.zeros(N_CONF, dtype=abi.SCENE_CLEARANCE_DTYPE)
+    rec = np.zeros(N_CONF, dtype=abi.RESULT_DTYPE)
+    k = (C.c_size_t * 2)(0, 0)
+    fn = d.hfcl_scene_nearest_env if env else d.hfcl_scene_nearest_self
+    rc = fn(small.scene._h, abi.ptr(table), C.c_size_t(N_CONF), C.byref(req), C.c_double(np.inf), abi.ptr(out), abi.ptr(rec), k)
+    return rc, (int(k[0]), int(k[1])), small.lib.last_bucket_counts()
+
+
+MADE_FORMS = {"collide_self": (_made, False), "collide_env": (_made, True), "nearest_self": (_clearance, False), "nearest_env": (_clearance, True)}
+
+
+def _call(pkg, small, form, chunk):
+    """the form's call; for the env forms the first N_MOVING objects move and the others stand where configuration 0 has them"""
+    call, env = MADE_FORMS[form]
+    if env:
+        small.scene.set_environment(N_MOVING, np.ascontiguousarray(small.table[0, N_MOVING:]))
+    try:
+        return call(pkg, small, chunk, env)
+    finally:
+        if env:
+            small.scene.clear_environment()
+
+
+@pytest.fixture(scope="module")
+def made_one_chunk(pkg, small):
+    return {form: _call(pkg, small, form, 0) for form in MADE_FORMS}
+
+
+@pytest.mark.parametrize("chunk", CHUNKS)
+@pytest.mark.parametrize("form", list(MADE_FORMS))
+def test_made_list_counts_equal_the_one_chunk_call(pkg, small, made_one_chunk, form, chunk):
+    abi = pkg.abi
+    rc, n_listed, counts = _call(pkg, small, form, chunk)
+    ref_rc, ref_listed, ref_counts = made_one_chunk[form]
+    print(form, chunk, rc, n_listed, counts)
+    assert n_listed == ref_listed
+    if form == "collide_self":
+        assert n_listed == N_CONF * small.n_pairs
+    if form == "collide_env":
+        assert n_listed == N_CONF * (N_MOVING * (N_MOVING - 1) // 2 + N_MOVING * (7 - N_MOVING))
+    assert sum(counts.values()) > 0
     assert rc == ref_rc, (form, chunk, rc, ref_rc)
     assert rc == (abi.ERR_UNSUPPORTED_PAIR if counts["unsupported"] else abi.OK)
     assert counts == ref_counts, (form, chunk)

@@ -5,11 +5,17 @@ hfcl_scene_* once -- scene (host and device), boxes, cull, listed, culled, neare
 workloads.scene_planner(64, 16): 6720 queries, far below the size at which a chunk runs split.  scene_chunk and scene_cull_chunk are set
 so that every call runs in three chunks (the listed, culled and nearest forms: a third of their list, read from a call before).
 
-  python tools/scene_launches.py --out DIR [--nearest-env]       every output of every call as DIR/<nn>_<name>.npy: records, summaries, boxes, lists,
-      conf_begin, counts, min records, n_evaluated, and last_bucket_counts() after every host form.  --nearest-env adds, behind all of
-      these, the clearance among a kept environment (hfcl_scene_set_environment* with the first 6 bodies moving, hfcl_scene_nearest_env*
-      host and device, moving rows in three chunks and spans of one tile): a run without it is what a build without those calls runs
-  rocprofv3 --kernel-trace --output-format csv -d TRACE -- python tools/scene_launches.py --out DIR      (one fresh process per build)
+  python tools/scene_launches.py --out DIR [--nearest-env] [--made-lists]
+      every output of every call as DIR/<nn>_<name>.npy: records, summaries, boxes, lists, conf_begin, counts, min records, n_evaluated,
+      and last_bucket_counts() after every host form.  --nearest-env adds, behind all of these, the clearance among a kept environment
+      (hfcl_scene_set_environment* with the first 6 bodies moving, hfcl_scene_nearest_env* host and device, moving rows in three chunks
+      and spans of one tile): a run without it is what a build without those calls runs.  --made-lists adds, behind those, the other
+      calls on lists made on the device, fp64 then fp32, each in three chunks: under hfcl_scene_set_groups with a matrix that forbids some
+      pairs the self pairs and hfcl_scene_nearest_self* (host and device), then hfcl_scene_clear_groups; with the environment set
+      hfcl_scene_env_pairs* (host and device), hfcl_scene_{collide,distance}_env_pairs_device* on that list and
+      hfcl_scene_{collide,distance}_env*; and hfcl_scene_set_terrain on the smallest field workloads.scene_robot_terrain makes, then
+      hfcl_scene_collide_terrain (host and device, with summaries and contacts; fp64: the call has no other form)
+  rocprofv3 --kernel-trace --output-format csv -d TRACE -- python tools/scene_launches.py --out DIR [switches]     (one fresh process per build)
   python tools/scene_launches.py --compare DIR_A TRACE_A DIR_B TRACE_B
       the .npy files byte for byte, and the kernel traces: per queue, in dispatch order, (kernel name, grid size, workgroup size)"""
 import argparse
@@ -24,7 +30,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def run(out_dir, nearest_env=False):
+def run(out_dir, nearest_env=False, made_lists=False):
     import torch
     import __graft_entry__ as ge
     pkg = ge.load_pkg()
@@ -143,10 +149,90 @@ def run(out_dir, nearest_env=False):
             n_eval = (scene.nearest_env_device_f32 if f32 else scene.nearest_env_device)(torch.from_numpy(moving).to(dev), n_conf, dreq, d_clear, d_min, stream=st)
             dump(p + "nearest_env_device", d_clear, d_min, np.array(n_eval, dtype=np.int64))
         scene.clear_environment()
+        lib.set_option("scene_env_span", 0)
+    if made_lists:
+        _made_lists(pkg, lib, scene, table, pose, dump, d_zeros, thirds, dev, st)
     torch.cuda.synchronize()
     scene.close()
     lib.close()
     print("scene_launches: %d calls dumped to %s (%d queries; lists: %d entries)" % (seq[0], out_dir, total, n_listed))
+
+
+def _made_lists(pkg, lib, scene, table, pose, dump, d_zeros, thirds, dev, st):
+    """--made-lists: groups over the self pairs and nearest_self, the env lists and their narrow phases, the terrain"""
+    import torch
+    abi = pkg.abi
+    creq, dreq = abi.default_collision_request(), abi.default_distance_request()
+    n_conf, G = table.shape[:2]
+    third = lambda n: max(1, -(-n // 3))
+    # groups: three, by object index; objects of group 0 never pair with each other, nor group 1 with group 2
+    scene.set_groups(np.arange(G) % 3, np.array([[0, 1, 1], [1, 1, 0], [1, 0, 1]], dtype=bool))
+    for f32 in (False, True):
+        p = "groups_f32_" if f32 else "groups_f64_"
+        tab = pose if f32 else table
+        d_tab = torch.from_numpy(tab).to(dev)
+        words = 11 if f32 else 24
+        lib.set_option("scene_cull_chunk", third(n_conf * G))
+        sp, sp_cb = scene.self_pairs(tab, 0.25)
+        dump(p + "self_pairs", sp, sp_cb)
+        d_sp, d_cb, d_n = d_zeros(2 * len(sp)), d_zeros(n_conf + 1, torch.int64), d_zeros(1, torch.int64)
+        scene.self_pairs_device(d_tab, n_conf, 0.25, d_sp, len(sp), d_cb, d_n, f32=f32, stream=st)
+        dump(p + "self_pairs_device", d_sp, d_cb, d_n)
+        _, _, n_eval = scene.nearest_self(tab, dreq)
+        thirds(max(max(n_eval), 1))
+        clear, rec, n_eval = scene.nearest_self(tab, dreq)
+        dump(p + "nearest_self", clear, rec, np.array(n_eval, dtype=np.int64), host=True)
+        d_clear, d_min = d_zeros(n_conf * 6), d_zeros(n_conf * words)
+        n_eval = (scene.nearest_self_device_f32 if f32 else scene.nearest_self_device)(d_tab, n_conf, dreq, d_clear, d_min, stream=st)
+        dump(p + "nearest_self_device", d_clear, d_min, np.array(n_eval, dtype=np.int64))
+    scene.clear_groups()
+    # the environment: the first K bodies move, the others stand where configuration 0 has them
+    K = 6
+    lib.set_option("scene_cull_chunk", third(n_conf * K))
+    lib.set_option("scene_env_span", 1)
+    for f32 in (False, True):
+        p = "env_f32_" if f32 else "env_f64_"
+        tab = pose if f32 else table
+        sfx = "_f32" if f32 else ""
+        words = 11 if f32 else 24
+        moving = np.ascontiguousarray(tab[:, :K])
+        d_moving = torch.from_numpy(moving).to(dev)
+        scene.set_environment(K, np.ascontiguousarray(tab[0, K:]))
+        ep, ep_cb = scene.env_pairs(moving, 0.25)
+        dump(p + "env_pairs", ep, ep_cb)
+        d_ep, d_cb, d_n = d_zeros(2 * len(ep)), d_zeros(n_conf + 1, torch.int64), d_zeros(1, torch.int64)
+        scene.env_pairs_device(d_moving, n_conf, 0.25, d_ep, len(ep), d_cb, d_n, f32=f32, stream=st)
+        dump(p + "env_pairs_device", d_ep, d_cb, d_n)
+        thirds(max(len(ep), 1))
+        for kind, req in (("collide", creq), ("distance", dreq)):
+            d_rec, d_sum = d_zeros(len(ep) * words), d_zeros(n_conf * 6)
+            getattr(scene, kind + "_env_pairs_device" + sfx)(d_moving, n_conf, d_ep, len(ep), d_cb, req, d_rec, d_sum, stream=st)
+            dump(p + kind + "_env_pairs_device", d_rec, d_sum)
+            dump(p + kind + "_env", *getattr(scene, kind + "_env")(moving, req, 0.25), host=True)
+    scene.clear_environment()
+    lib.set_option("scene_env_span", 0)
+    # the terrain: a library and a scene of its own (the workload's solids), every link listed, queries in three chunks
+    w = pkg.workloads.scene_robot_terrain(n_conf=16, n_links=6, side=2)
+    t = w.terrain
+    tlib = pkg.Library(t.lib)
+    field = tlib.add_hfield(t.x_dim, t.y_dim, t.heights, t.min_height)
+    tscene = tlib.scene(w.object_shape, np.zeros((0, 2), dtype=np.uint32))
+    tscene.set_terrain(field, w.tf_terrain)
+    n_conf_t, n_links = w.moving_tf.shape[:2]
+    n_q = n_conf_t * n_links
+    tlib.set_option("hfield_chunk", third(n_q))
+    treq = abi.default_collision_request()
+    treq.num_max_contacts = 4
+    cap = 4 * n_q
+    rec, dlb, summ, con, n_con = tscene.collide_terrain(w.moving_tf, treq, max_contacts=cap)
+    dump("terrain", rec, dlb, summ, con, np.array([n_con], dtype=np.int64))
+    d_rec, d_dlb, d_sum = d_zeros(n_q * 24), d_zeros(n_q, torch.float64), d_zeros(n_conf_t * 6)
+    d_con = torch.zeros(cap * abi.CONTACT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    n_con = tscene.collide_terrain_device(torch.from_numpy(w.moving_tf).to(dev), n_conf_t, treq, d_rec, d_dlb, d_sum, d_con, cap, want_count=True, stream=st)
+    dump("terrain_device", d_rec, d_dlb, d_sum, d_con[:n_con * abi.CONTACT_DTYPE.itemsize], np.array([n_con], dtype=np.int64))
+    torch.cuda.synchronize()
+    tscene.close()
+    tlib.close()
 
 
 def _launches(trace_dir):
@@ -191,11 +277,13 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--nearest-env", action="store_true", help="add the hfcl_scene_nearest_env* calls behind the others")
+    ap.add_argument("--made-lists", action="store_true",
+                    help="add, behind the others, the calls under groups, on env lists and on a terrain (see the text above)")
     ap.add_argument("--compare", nargs=4, metavar=("DIR_A", "TRACE_A", "DIR_B", "TRACE_B"))
     a = ap.parse_args()
     if a.compare:
         compare(*a.compare)
     elif a.out:
-        run(a.out, a.nearest_env)
+        run(a.out, a.nearest_env, a.made_lists)
     else:
         ap.error("--out DIR or --compare ...")
