@@ -125,6 +125,12 @@ struct hfcl_options {
   // configuration's rows one after the other (profiles/r14_a_scene_pairs.md).  scene_cull_chunk is, for these calls, the rows
   // (configuration, object) per chunk, in whole row blocks
   uint32_t scene_pairs_small_max = 32;
+  // hfcl_scene_self_pairs* and the _self host forms: option scene_pairs_sorted = 1 makes the same list by sort and sweep along one axis
+  // (hfcl_pairs_sorted.hpp) for every scene of two objects or more, 0 (the default) never; option scene_pairs_sorted_axis: the sweep axis
+  // 0 / 1 / 2, or 3 -- per configuration the axis on which the boxes' centres spread widest.  The list's bytes depend on neither.  With the
+  // option set the device forms wait on their stream once per chunk (the count of the chunk's entries sizes the second sort)
+  bool scene_pairs_sorted = false;
+  uint32_t scene_pairs_sorted_axis = 3;
   // hfcl_scene_env_pairs*: column tiles per workgroup of the sweep (option scene_env_span; 0: automatic, hfcl_env.hpp: env_auto_span)
   uint32_t scene_env_span = 0;
   // hfcl_scene_nearest_env*: drop whole (row block, environment tile) cells of a pass by a bound of their distance (option
@@ -326,6 +332,14 @@ struct hfcl_lib {
     DevBuf<uint64_t> d_row_offsets, d_row_sum_offsets;
     size_t rows_cap = 0;
     DevBuf<uint32_t> d_pair_list;  // (two words an entry)
+    // ... by sort and sweep (option scene_pairs_sorted): of a chunk of whole configurations the words as made and sorted with their
+    // objects, the grown boxes, groups and window ends in sorted order, the axis of a configuration and the centre ranges behind it, the
+    // entries' words as emitted and sorted, and the sorts' temporary storage
+    DevBuf<uint64_t> d_ps_keys[2], d_ps_emit[2];
+    DevBuf<uint32_t> d_ps_vals[2], d_ps_ends, d_ps_axis;
+    DevBuf<double> d_ps_boxes, d_ps_spread;
+    DevBuf<uint8_t> d_ps_group;
+    DevBuf<void> d_ps_temp;
     // the clearance on device-made pairs (hfcl_scene_nearest_self*): a row seed per row of the table, seed and threshold by
     // configuration, per pass the list of pairs with its conf_begin, its summaries and -- when min records are asked for -- its records,
     // and the host forms' clearances

@@ -26,6 +26,7 @@ struct hfcl_scene {
   size_t n_objects = 0, n_pairs = 0;
   DevBuf<uint32_t> d_object_shape, d_pairs;
   uint64_t epoch = 0;  // hfcl_lib::shapes_epoch when the scene was made
+  int last_pairs_form = -1;  // hfcl_scene_last_pairs_form: how the last list of self pairs was made (-1: none yet)
   // object groups (hfcl_scene_set_groups; 0: none): an object's group, the groups' row masks, the groups present per column tile
   size_t n_groups = 0;
   DevBuf<uint8_t> d_group;
@@ -833,6 +834,88 @@ struct SelfSweep {
   }
 };
 
+// The same list by sort and sweep along one axis (option scene_pairs_sorted; hfcl_plan.hpp: sorted_sweep_plan, hfcl_k_pairs_sorted.hip):
+// chunks of whole configurations on st.  Per chunk its boxes, the count half -- keys, sort, windows, count, scan --, the ONE wait: the
+// entries so far (8 bytes) size the chunk's emitted words and their sort; then the emit half, unless the list is not asked for or the
+// chunk lies behind its capacity.  the_list: the caller's part of the arguments, as the all-pairs sweep takes it.
+template <typename T, typename F>
+static int pairs_sorted_chunks(hfcl_scene* s, const void* d_table, size_t n_conf, hipStream_t st, F&& the_list) {
+  hfcl_lib* lib = s->lib;
+  hfcl_lib::SceneWs& w = lib->scene;
+  const uint32_t n = uint32_t(s->n_objects);
+  const SortedSweepPlan plan = sorted_sweep_plan(n, n_conf, lib->opt.scene_cull_chunk);
+  const size_t rows = size_t(plan.chunk_rows);
+  HIP_TRY(w.d_boxes.grow(rows * 6));
+  int rc = pairs_chunk_buffers(lib, rows);
+  if (rc) return rc;
+  PairsSortedArgs a;
+  pairs_args(a.p, s, pairs_geometry(n, false), false, n_conf);
+  the_list(a.p);
+  a.p.tile_groups = nullptr;
+  a.p.g0 = 0;
+  a.axis = lib->opt.scene_pairs_sorted_axis;
+  a.blocks_per_conf = plan.blocks_per_conf;
+  a.conf_bits = plan.conf_bits;
+  a.obj_bits = plan.obj_bits;
+  a.spread_blocks = (n + PSORT_SPREAD_BLOCK - 1u) / PSORT_SPREAD_BLOCK;
+  for (int k = 0; k < 2; ++k) {
+    HIP_TRY(w.d_ps_keys[k].grow(rows));
+    HIP_TRY(w.d_ps_vals[k].grow(rows));
+    a.keys[k] = w.d_ps_keys[k];
+    a.vals[k] = w.d_ps_vals[k];
+  }
+  HIP_TRY(w.d_ps_boxes.grow(rows * 6));
+  HIP_TRY(w.d_ps_ends.grow(rows));
+  if (a.p.group) HIP_TRY(w.d_ps_group.grow(rows));
+  if (a.axis >= PSORT_AXIS_AUTO) {
+    HIP_TRY(w.d_ps_axis.grow(plan.conf_per_chunk));
+    HIP_TRY(w.d_ps_spread.grow(plan.conf_per_chunk * a.spread_blocks * 6));
+  }
+  a.sorted_boxes = w.d_ps_boxes;
+  a.ends = w.d_ps_ends;
+  a.sorted_group = a.p.group ? w.d_ps_group.get() : nullptr;
+  a.conf_axis = w.d_ps_axis;
+  a.spread = w.d_ps_spread;
+  a.emit[0] = a.emit[1] = nullptr;
+  a.n_emit = a.emit_base = 0;
+  uint64_t before = 0;
+  for (size_t c0 = 0; c0 < n_conf; c0 += plan.conf_per_chunk) {
+    const size_t confs = std::min(plan.conf_per_chunk, n_conf - c0);
+    a.n_conf_chunk = uint32_t(confs);
+    a.p.c_box0 = c0;
+    a.p.n_blocks = uint32_t(confs * plan.blocks_per_conf);
+    a.p.row0 = uint64_t(c0) * n;
+    a.p.n_rows = uint32_t(confs * n);
+    a.p.first = c0 == 0 ? 1 : 0;
+    a.n_emit = 0;
+    size_t bytes;
+    HIP_TRY(pairs_sorted_temp_bytes(a, false, bytes));
+    HIP_TRY(w.d_ps_temp.grow(std::max<size_t>(bytes, 16)));  // (never a null pointer: that would be the size query again)
+    a.temp = w.d_ps_temp;
+    a.temp_bytes = w.d_ps_temp.capacity();
+    const char* table_rows = static_cast<const char*>(d_table) + c0 * n * SceneTypes<T>::WIDTH * sizeof(T);
+    launch_cull_aabbs(st, table_rows, std::is_same<T, float>::value, s->d_object_shape, lib->d_local_boxes, n, confs * n, w.d_boxes);
+    HIP_TRY(launch_pairs_sorted_count(st, a));
+    uint64_t upto = 0;
+    HIP_TRY(hipMemcpyAsync(&upto, w.d_running, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    a.n_emit = upto - before;
+    a.emit_base = before;
+    before = upto;
+    if (!a.p.pairs || !a.n_emit || a.emit_base >= a.p.capacity) continue;
+    for (int k = 0; k < 2; ++k) {
+      HIP_TRY(w.d_ps_emit[k].grow(size_t(a.n_emit)));
+      a.emit[k] = w.d_ps_emit[k];
+    }
+    HIP_TRY(pairs_sorted_temp_bytes(a, true, bytes));
+    HIP_TRY(w.d_ps_temp.grow(std::max<size_t>(bytes, 16)));  // (never a null pointer: that would be the size query again)
+    a.temp = w.d_ps_temp;
+    a.temp_bytes = w.d_ps_temp.capacity();
+    HIP_TRY(launch_pairs_sorted_emit(st, a));
+  }
+  return HFCL_OK;
+}
+
 // ---------------------------------------------------------------------------------------
 // A static environment kept on the device (include/hppfcl_amd_env.h): what is its own of the pairs of the moving objects among themselves
 // and against the environment per configuration (hfcl_scene_env_pairs*) -- the validator, the limits, the setter, the sweep.
@@ -1063,6 +1146,10 @@ static int pairs_device(ListKind kind, const char* who, hfcl_scene* s, const voi
     sweep.args(a, n_conf);
     the_list(a.p);
     sweep.walk<T>(a, d_table, st, [&]() { launch_env_chunk(st, a); });
+  } else if (lib->opt.scene_pairs_sorted) {  // the same list by sort and sweep: waits on st once per chunk
+    rc = pairs_sorted_chunks<T>(s, d_table, n_conf, st, the_list);
+    if (rc) return rc;
+    s->last_pairs_form = 2;
   } else {
     SelfSweep sweep;
     rc = sweep.ready(s, n_conf);
@@ -1071,6 +1158,7 @@ static int pairs_device(ListKind kind, const char* who, hfcl_scene* s, const voi
     sweep.args(a, n_conf);
     the_list(a);
     sweep.walk<T>(a, d_table, st, [&]() { launch_pairs_chunk(st, a); });
+    s->last_pairs_form = sweep.p.small ? 1 : 0;
   }
   HIP_TRY(hipGetLastError());
   return HFCL_OK;
@@ -1903,6 +1991,7 @@ void hfcl_scene_destroy(hfcl_scene* s) {
   delete s;
 }
 size_t hfcl_scene_num_objects(const hfcl_scene* s) { return s ? s->n_objects : 0; }
+int hfcl_scene_last_pairs_form(const hfcl_scene* s) { return s ? s->last_pairs_form : -1; }
 size_t hfcl_scene_num_pairs(const hfcl_scene* s) { return s ? s->n_pairs : 0; }
 
 int hfcl_scene_collide(hfcl_scene* s, const double* object_tf, size_t n_conf, const hfcl_collision_request* req, hfcl_result* out,

@@ -269,6 +269,34 @@ void launch_pairs_chunk(hipStream_t st, const PairsArgs& a);
 // (hfcl_k_pairs.hip) the three scan launches of launch_pairs_chunk alone, behind a count kernel of another unit that left a.row_counts
 void launch_pairs_scan(hipStream_t st, const PairsArgs& a);
 
+// hfcl_k_pairs_sorted.hip: the same list by sort and sweep along one axis (option scene_pairs_sorted; hfcl_pairs_sorted.hpp has the
+// arithmetic).  A chunk of n_conf_chunk WHOLE configurations.  p: the chunk's boxes (c_box0 = the chunk's first configuration), n_objects,
+// row0 / n_rows / total_rows / n_conf, inflate, the row arrays and the scan's (a row is a SORTED position of the chunk), running / first,
+// the list, the groups (tile_groups unused).  Two halves around the one read-back of a chunk: ..._count leaves the rows' counts, their
+// offsets, conf_begin and the count (p.running[0]: the entries up to and with this chunk); the host sizes emit[] and temp by the chunk's
+// entries; ..._emit writes the entries [emit_base, emit_base + n_emit) of the list below p.capacity.
+struct PairsSortedArgs {
+  PairsArgs p;
+  uint32_t axis;             // 0, 1, 2, or PSORT_AXIS_AUTO: per configuration, conf_axis
+  uint32_t n_conf_chunk, blocks_per_conf, conf_bits, obj_bits;
+  uint32_t* conf_axis;       // n_conf_chunk (automatic axis)
+  double* spread;            // n_conf_chunk x spread_blocks x 6: centre min / max per workgroup of the spread kernel (automatic axis)
+  uint32_t spread_blocks;    // ceil(n_objects / PSORT_SPREAD_BLOCK)
+  uint64_t* keys[2];         // n_rows each: the words as made, sorted
+  uint32_t* vals[2];         // n_rows each: the object of a word
+  double* sorted_boxes;      // n_rows x 6: the grown boxes in sorted order
+  uint8_t* sorted_group;     // n_rows (with groups)
+  uint32_t* ends;            // n_rows: a position's window end, a position of its configuration
+  uint64_t* emit[2];         // n_emit each: the entries' words as emitted, sorted
+  uint64_t n_emit, emit_base;
+  void* temp;                // the sorts' temporary storage
+  size_t temp_bytes;
+};
+// temporary storage of the sort of a chunk's p.n_rows keys (emit false) / of its n_emit entries (emit true), over the bits in use
+hipError_t pairs_sorted_temp_bytes(const PairsSortedArgs& a, bool emit, size_t& bytes);
+hipError_t launch_pairs_sorted_count(hipStream_t st, const PairsSortedArgs& a);
+hipError_t launch_pairs_sorted_emit(hipStream_t st, const PairsSortedArgs& a);
+
 // hfcl_k_env.hip: a static environment kept on the device (hfcl_scene_set_environment*, hfcl_scene_env_pairs*; hfcl_env.hpp has the
 // arithmetic).  The boxes of one tile of PAIRS_TILE environment boxes each (set time)
 void launch_env_tile_boxes(hipStream_t st, const double* env_boxes, uint32_t n_env, double* tile_boxes);

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "hfcl_env.hpp"
+#include "hfcl_pairs_sorted.hpp"
 #include "hfcl_scene.hpp"
 
 // Chunk bounds of a host batch of n > 0 pairs: chunk k = [bounds[k], bounds[k + 1]), bounds[0] = 0, bounds.back() = n.
@@ -97,6 +98,27 @@ inline SelfSweepPlan self_sweep_plan(uint32_t n, size_t n_conf, uint32_t small_m
   p.per = hfcl::pairs_chunk_blocks(p.geo, p.n_blocks, chunk_option);
   p.conf_per_chunk = sweep_conf_per_chunk(n_conf, p.per, p.geo.blocks_per_conf);
   p.chunk_rows = std::min<uint64_t>(p.per * p.geo.rows_per_block, uint64_t(n_conf) * n);
+  return p;
+}
+// The sort-and-sweep form of the same list (hfcl_pairs_sorted.hpp; option scene_pairs_sorted) over n_conf configurations of n >= 2 objects:
+// chunks of whole configurations -- chunk_option rows (option scene_cull_chunk; 0: PAIRS_CHUNK_ROWS, the call in equal chunks), at least
+// one configuration.  conf_bits: bits of a configuration's index in its chunk, obj_bits: of an object's index -- the sorted words have
+// 32 + conf_bits and conf_bits + 2 obj_bits bits in use; blocks_per_conf: workgroups of PAIRS_ROWS sorted positions
+struct SortedSweepPlan {
+  size_t conf_per_chunk, n_chunks;
+  uint64_t chunk_rows;
+  uint32_t blocks_per_conf, conf_bits, obj_bits;
+};
+inline SortedSweepPlan sorted_sweep_plan(uint32_t n, size_t n_conf, uint64_t chunk_option) {
+  SortedSweepPlan p;
+  const uint64_t rows = chunk_option ? chunk_option : hfcl::PAIRS_CHUNK_ROWS;
+  p.conf_per_chunk = std::min<size_t>(n_conf, std::max<size_t>(size_t(rows / n), 1));
+  p.n_chunks = (n_conf + p.conf_per_chunk - 1) / p.conf_per_chunk;
+  if (!chunk_option) p.conf_per_chunk = (n_conf + p.n_chunks - 1) / p.n_chunks;
+  p.chunk_rows = uint64_t(p.conf_per_chunk) * n;
+  p.blocks_per_conf = (n + hfcl::PAIRS_ROWS - 1u) / hfcl::PAIRS_ROWS;
+  p.conf_bits = hfcl::psort_bits(p.conf_per_chunk);
+  p.obj_bits = hfcl::psort_bits(n);
   return p;
 }
 // tiles per span of the environment sweep: the option scene_env_span as given, or (0) env_auto_span for the call's row blocks

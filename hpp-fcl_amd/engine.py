@@ -53,6 +53,10 @@ PAIRS_SYMBOLS = [
     "hfcl_scene_distance_pairs_device_f32", "hfcl_scene_collide_self", "hfcl_scene_distance_self", "hfcl_scene_collide_self_f32",
     "hfcl_scene_distance_self_f32",
 ]
+# include/hppfcl_amd_pairs_sorted.h (included by hppfcl_amd_pairs.h): the same list by sort and sweep (option scene_pairs_sorted)
+PAIRS_SORTED_SYMBOLS = [
+    "hfcl_scene_last_pairs_form",
+]
 # include/hppfcl_amd_groups.h (included by hppfcl_amd.h): object groups and a group matrix for the device-made pair lists
 GROUPS_SYMBOLS = [
     "hfcl_scene_set_groups", "hfcl_scene_clear_groups", "hfcl_scene_num_groups",
@@ -948,7 +952,13 @@ class Scene:
     def distance_self(self, object_tf, req=None, inflate=0.0, records=True, want_guess=False):
         return self._self("distance", object_tf, inflate, req or abi.default_distance_request(), records, want_guess=want_guess)
 
-    # device forms: torch tensors or raw device pointers, asynchronous on `stream`
+    def last_pairs_form(self):
+        """hfcl_scene_last_pairs_form: how this scene's last list of self pairs was made -- 0 the tiled all-pairs test, 1 its
+        wave-per-configuration form, 2 sort and sweep (library option scene_pairs_sorted); -1: none yet."""
+        return int(dll().hfcl_scene_last_pairs_form(self._h))
+
+    # device forms: torch tensors or raw device pointers, asynchronous on `stream` (with the library option scene_pairs_sorted set,
+    # self_pairs_device waits on `stream` once per chunk: include/hppfcl_amd_pairs_sorted.h)
     def self_pairs_device(self, d_object_tf, n_conf, inflate, d_pairs, capacity, d_conf_begin, d_n_listed, f32=False, stream=0):
         """hfcl_scene_self_pairs_device{,_f32}: *d_n_listed is the true count, entries past `capacity` are not written; nothing is read back."""
         fn = dll().hfcl_scene_self_pairs_device_f32 if f32 else dll().hfcl_scene_self_pairs_device

@@ -1825,6 +1825,9 @@ class Scene {
     collides_.clear();
   }
   size_t numGroups() const { return hfcl_scene_num_groups(scene_); }
+  /// How the last list of selfPairs / collideSelf / distanceSelf was made (hfcl_scene_last_pairs_form, include/hppfcl_amd_pairs_sorted.h):
+  /// 0 the tiled all-pairs test, 1 its wave-per-configuration form, 2 sort and sweep (library option scene_pairs_sorted); -1: none yet
+  int lastPairsForm() const { return hfcl_scene_last_pairs_form(scene_); }
 
   /// A static environment kept on the device (hfcl_scene_set_environment, include/hppfcl_amd_env.h): objects [n_moving, numObjects())
   /// stand still at env_transforms (one per environment object); the calls below take tables of n_moving transforms a configuration.

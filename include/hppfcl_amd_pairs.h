@@ -5,7 +5,9 @@
  * DynamicAABBTreeCollisionManager::collide(callback) finds the pairs whose world AABBs overlap itself.  hfcl_broadphase_self_pairs does
  * that on the host for one configuration; the calls below do it on the device for every configuration of a pose table that is already
  * there, without a list: a tiled test of all pairs of world boxes -- no tree, no sorting, no atomics --, compacted by count / scan / emit.
- * 5 * 10^9 box tests (100 000 objects) are milliseconds of the device's time; scenes far beyond that want a tree or a grid, which this is not.
+ * 5 * 10^9 box tests (100 000 objects) are milliseconds of the device's time; scenes far beyond that want a tree or a grid, which this is
+ * not -- or the second way to the same list, sort and sweep along one axis, which the option `scene_pairs_sorted` chooses
+ * (hppfcl_amd_pairs_sorted.h, included below: what it costs, and the one wait it adds to the device forms).
  *
  * The list.  Entry k is a pair (i, j), i < j, two uint32 object indices.  The list holds, for configuration c ascending, then i ascending,
  * then j ascending, every pair whose two world boxes touch after each was grown by `inflate` on every side.  The boxes are those of
@@ -93,4 +95,5 @@ int hfcl_scene_distance_self_f32(hfcl_scene* s, const float* object_pose, size_t
 #ifdef __cplusplus
 }
 #endif
+#include "hppfcl_amd_pairs_sorted.h"
 #endif /* HPPFCL_AMD_PAIRS_H */

@@ -49,7 +49,10 @@ configuration) and on workloads.scene_planner at ~1 M queries.
   2, 3, 4, 5  x, y, z, 1 with scene_nearest_env_prune=0: no environment tile dropped by its distance
      x .. 5 report the pairs each pass evaluates, whether the clearances are those of g and -- from tests/nearest_env_model.py, with
      the thresholds recomputed on the host -- the (16 rows, tile) cells each pass drops by distance.  robot32x65536x4096 runs them too.
-X .. b ignore the workload's pair list.  --options key=value,... sets library options in the worker (scene_pairs_small_max=0: the tiled form).
+X .. b ignore the workload's pair list.  --options key=value,... sets library options in the worker (scene_pairs_small_max=0: the tiled form;
+scene_pairs_sorted=1: the list of X, Y, a by sort and sweep -- profiles/r24_a_pairs_sorted.md; the row reports the form that ran).
+cfg5x4 / cfg5x16: cfg5's scene with 4 / 16 times the objects at the same density (400 000 / 1 600 000 objects, 4 M / 16 M pairs);
+cfg5n1000 .. cfg5n50000: with that many objects.
 The culled forms run at --inflate (default 0: the reference's manager).  planner2048: scene_planner(2048, 16), 215 040 queries;
 planner2048x32: scene_planner(2048, 32), 952 320 queries.  robot16x4096 / robot32x65536: workloads.scene_robot_env, 16 links and 4 096
 obstacles in 256 configurations / 32 links and 65 536 obstacles in 8; rows c .. 5 run on these alone, and c .. e only in a library that
@@ -82,6 +85,8 @@ ROBOTS = {"robot16x4096": (256, 16, 4096), "robot32x65536": (8, 32, 65536)}  # (
 ROBOTS.update({k + "s": v for k, v in list(ROBOTS.items())})  # ... the obstacles in spatial order
 ENV_ONLY = {"robot32x65536x4096": (4096, 32, 65536), "robot32x65536x4096s": (4096, 32, 65536)}  # (no full table: the env forms alone)
 ENV_FORMS = "stuvwxyz12345"
+CFG5_SIZES = {"cfg5": 100_000, "cfg5x4": 400_000, "cfg5x16": 1_600_000}
+CFG5_SIZES.update({"cfg5n%d" % n: n for n in (1000, 2000, 5000, 10000, 20000, 50000)})  # (the crossover of the two ways to the self pairs)
 NENV_FORMS = "xyz12345"
 
 
@@ -94,8 +99,8 @@ def _workload(pkg, name):
         sc, groups, pairs, split, split32 = wl.scene_robot_env(*(ROBOTS.get(name) or ENV_ONLY[name]), split=True, spatial=name.endswith("s"),
                                                          full=name in ROBOTS)
         return sc.lib, sc.obj_shape, pairs, sc.obj_tf, groups, split + split32
-    if name == "cfg5":
-        b = wl.cfg5_broadphase_scene()
+    if name in CFG5_SIZES:  # (cfg5's scene with other numbers of objects in a cube of the same density: ten touching pairs an object)
+        b = wl.cfg5_broadphase_scene(n_objects=CFG5_SIZES[name], target_pairs=10 * CFG5_SIZES[name])
         sc = b.scene
         return b.lib, sc["obj_shape"], sc["pairs"], sc["obj_tf"].reshape(1, -1, 12), None, None
     if name == "planner2048x32":
@@ -297,6 +302,10 @@ def worker(args):
         d_tab_p = torch.from_numpy(np.ascontiguousarray(table)).to(dev)
         sp, sp_cb = scene.self_pairs(table, args.inflate)
         out["self_pairs"] = {"n_listed": int(len(sp)), "box_tests": n_conf * G * (G - 1) // 2, "options": args.options}
+        if hasattr(scene, "last_pairs_form"):  # (0 tiled, 1 wave per configuration, 2 sort and sweep: option scene_pairs_sorted)
+            out["self_pairs"]["form"] = scene.last_pairs_form()
+        if args.workload.startswith("cfg5") and args.inflate == 0.0:
+            out["self_pairs"]["equals_host_broadphase"] = bool(sp.tobytes() == np.ascontiguousarray(pairs.astype(np.uint32)).tobytes())
         cap = max(len(sp), 1)
         d_sp = torch.zeros(2 * cap, dtype=torch.int32, device=dev)
         d_spcb = torch.zeros(n_conf + 1, dtype=torch.int64, device=dev)
@@ -524,7 +533,7 @@ def bytes_moved(n_conf, G, P):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--worker", action="store_true")
-    ap.add_argument("--workload", default="cfg5", choices=["cfg5", "planner", "planner2048", "planner2048x32", "planner256x64"] + sorted(ROBOTS) + sorted(ENV_ONLY))
+    ap.add_argument("--workload", default="cfg5", choices=sorted(CFG5_SIZES) + ["planner", "planner2048", "planner2048x32", "planner256x64"] + sorted(ROBOTS) + sorted(ENV_ONLY))
     ap.add_argument("--workloads", default="cfg5,planner", help="the workloads of a full run, comma-separated")
     ap.add_argument("--inflate", type=float, default=0.0)
     ap.add_argument("--options", default="", help="library options of the worker: key=value,...")
