@@ -96,6 +96,11 @@ HFIELD_NODE_DTYPE = np.dtype([("first_child", "<u4"), ("x_id", "<i4"), ("x_size"
 assert HFIELD_NODE_DTYPE.itemsize == 80
 HF_GEOM_AABB, HF_GEOM_OBBRSS = 20, 21  # NODE_TYPE HF_AABB / HF_OBBRSS (collision_object.h:65-89)
 STATUS_SWAPPED = 1 << 23
+# hfcl_octree_node (include/hppfcl_amd_octree.h): child[i] = index of child i in the array, 0 = none (node 0 is the root)
+OCTREE_NODE_DTYPE = np.dtype([("child", "<u4", (8,)), ("occupancy", "<f8")])
+assert OCTREE_NODE_DTYPE.itemsize == 40
+GEOM_OCTREE = 18  # NODE_TYPE GEOM_OCTREE (collision_object.h:65-89)
+OCTREE_MAX_DEPTH = 16
 
 
 class PatchRequest(C.Structure):

@@ -18,6 +18,7 @@ class NODE_TYPE:  # include/hpp/fcl/collision_object.h:65-89
     GEOM_CYLINDER, GEOM_CONVEX, GEOM_PLANE = abi.GEOM_CYLINDER, abi.GEOM_CONVEX, abi.GEOM_PLANE
     GEOM_HALFSPACE, GEOM_TRIANGLE, GEOM_ELLIPSOID = abi.GEOM_HALFSPACE, abi.GEOM_TRIANGLE, abi.GEOM_ELLIPSOID
     HF_AABB, HF_OBBRSS = abi.HF_GEOM_AABB, abi.HF_GEOM_OBBRSS
+    GEOM_OCTREE = abi.GEOM_OCTREE
 
 
 class GJKInitialGuess:
@@ -346,6 +347,90 @@ class HeightFieldAABB(CollisionGeometry):  # HeightField<AABB>, include/hpp/fcl/
         self._set(h)
 
 
+class OcTree(CollisionGeometry):  # include/hpp/fcl/octree.h:53-296, over a node array instead of an octomap tree
+    """nodes: abi.OCTREE_NODE_DTYPE (node 0 the root, child[i] = index of child i, 0 = none; engine.octree_from_points / makeOctree
+    make one).  Every box is halved down from getRootBV, as the reference computes them.  collide() against a convex solid, in either
+    operand order, goes to hfcl_octree_collide_batch."""
+    _node_type = NODE_TYPE.GEOM_OCTREE
+
+    def __init__(self, nodes, resolution, depth=abi.OCTREE_MAX_DEPTH, occupancy_threshold=0.5, free_threshold=0.0):
+        self._nodes = np.ascontiguousarray(nodes, dtype=abi.OCTREE_NODE_DTYPE).copy()
+        self._resolution, self._depth = float(resolution), int(depth)
+        try:
+            engine.octree_validate(self._nodes, self._depth)
+        except engine.EngineError as e:
+            raise ValueError(str(e))
+        self._occ, self._free = float(occupancy_threshold), float(free_threshold)
+        self._version = 1
+
+    def getTreeDepth(self):
+        return self._depth
+
+    def getResolution(self):
+        return self._resolution
+
+    def size(self):
+        return len(self._nodes)
+
+    def getNodes(self):
+        return self._nodes
+
+    def getRootBV(self):  # octree.h:139-144: (min xyz, max xyz)
+        delta = (1 << self._depth) * self._resolution / 2
+        return np.array([-delta, -delta, -delta, delta, delta, delta])
+
+    def getOccupancyThres(self):
+        return self._occ
+
+    def getFreeThres(self):
+        return self._free
+
+    def setOccupancyThres(self, d):
+        self._occ = float(d)
+        self._version += 1  # (the next collide() sets the thresholds on the library)
+
+    def setFreeThres(self, d):
+        self._free = float(d)
+        self._version += 1
+
+    def _leaves(self):
+        """(node, min, max) of every node without children, depth-first with the children in index order"""
+        out = []
+        if len(self._nodes) == 0:
+            return out
+        child = self._nodes["child"]
+        b = self.getRootBV()
+        stack = [(0, b[:3].copy(), b[3:].copy())]
+        while stack:
+            i, lo, hi = stack.pop()
+            kids = child[i]
+            if not kids.any():
+                out.append((i, lo, hi))
+                continue
+            for k in range(7, -1, -1):  # (popped in index order)
+                if kids[k]:
+                    clo, chi = lo.copy(), hi.copy()
+                    for a in range(3):  # computeChildBV, octree.h:299-324
+                        if k & (1 << a):
+                            clo[a] = (lo[a] + hi[a]) * 0.5
+                        else:
+                            chi[a] = (lo[a] + hi[a]) * 0.5
+                    stack.append((int(kids[k]), clo, chi))
+        return out
+
+    def toBoxes(self):  # octree.h:178-200: (x, y, z, size, occupancy, threshold) of the occupied leaves, from the halved boxes
+        rows = [[(lo[0] + hi[0]) * 0.5, (lo[1] + hi[1]) * 0.5, (lo[2] + hi[2]) * 0.5, hi[0] - lo[0], float(self._nodes[i]["occupancy"]), self._occ]
+                for i, lo, hi in self._leaves() if self._nodes[i]["occupancy"] >= self._occ]
+        return np.array(rows, dtype=np.float64).reshape(-1, 6)
+
+
+def makeOctree(points, resolution):  # src/octree.cpp:188-202 (octomap's tree depth: 16)
+    try:
+        return OcTree(engine.octree_from_points(points, resolution, abi.OCTREE_MAX_DEPTH), resolution, abi.OCTREE_MAX_DEPTH)
+    except engine.EngineError as e:
+        raise ValueError(str(e))
+
+
 class _Query:
     def __init__(self):
         self.gjk_initial_guess = GJKInitialGuess.DefaultGuess
@@ -491,6 +576,7 @@ class _Context:
         self.ids, self.keep, self.meshes = {}, [], []
         self.built = 0
         self.hfields, self.hfield_ids = [], {}  # registered (field, heights, ...) in index order; (id(field), version) -> index
+        self.octrees, self.octree_ids = [], {}  # the same for OcTree objects (a version: the thresholds as they were)
 
     @staticmethod
     def _signature(g):
@@ -535,10 +621,26 @@ class _Context:
             self.hfields.append((g, g._x_dim, g._y_dim, g._heights.copy(), g._min))  # (g is kept: its id stays its own while it is listed)
         return self.hfield_ids[key]
 
+    OCTREES_MAX = 16  # the same for (octree, version) entries
+
+    def add_octree(self, g):
+        """the index of an OcTree on the library (one whose thresholds were set is registered again; at most OCTREES_MAX registrations)"""
+        key = (id(g), g._version)
+        if key not in self.octree_ids:
+            if len(self.octrees) >= self.OCTREES_MAX:
+                self.octrees, self.octree_ids = [], {}
+                if self.lib is not None:
+                    self.lib.clear_octrees()
+            self.octree_ids[key] = len(self.octrees)
+            self.octrees.append((g, g._nodes, g._resolution, g._depth, g._occ, g._free))
+        return self.octree_ids[key]
+
     def library(self):
         lib = self._library()
         for _, x_dim, y_dim, h, mh in self.hfields[lib.hfield_count():]:  # (all of them on a library that was just rebuilt)
             lib.add_hfield(x_dim, y_dim, h, mh)
+        for _, nodes, res, depth, occ, free in self.octrees[lib.octree_count():]:
+            lib.add_octree(nodes, res, depth, occ, free)
         return lib
 
     def _library(self):
@@ -571,6 +673,11 @@ def _context():
 
 
 def _check_pair(o1, o2, for_distance):
+    t1, t2 = isinstance(o1, OcTree), isinstance(o2, OcTree)
+    if (t1 or t2) and not for_distance:
+        if t1 != t2 and engine.octree_pair_supported(int((o2 if t1 else o1).getNodeType())):
+            return
+        raise ValueError("Collision function between node type %d and node type %d is not yet supported." % (o1.getNodeType(), o2.getNodeType()))
     h1, h2 = isinstance(o1, HeightFieldAABB), isinstance(o2, HeightFieldAABB)
     if (h1 or h2) and not for_distance:
         if h1 != h2 and engine.hfield_pair_supported(int((o2 if h1 else o1).getNodeType())):
@@ -656,6 +763,35 @@ def _collide_hfield(o1, tf1, o2, tf2, request, result):
     return result.numContacts()
 
 
+def _collide_octree(o1, tf1, o2, tf2, request, result):
+    """(OcTree, solid) or (solid, OcTree) through hfcl_octree_collide_batch.  Either order gets the octree-first result (the reference
+    does not swap it back: src/collision.cpp:92-108 has no octree branch): the tree is o1 of every contact, its node b1."""
+    swapped = not isinstance(o1, OcTree)
+    tree, tft, solid, tfs = (o2, tf2, o1, tf1) if swapped else (o1, tf1, o2, tf2)
+    ctx = _context()
+    sid, tid = ctx.add(solid), ctx.add_octree(tree)
+    lib = ctx.library()
+    cap = int(min(request.num_max_contacts, 1 << 16))
+    try:
+        rec, dlb, contacts, _ = lib.octree_collide([tid], [sid], tft._abi().reshape(1, 12), tfs._abi().reshape(1, 12), request._abi(),
+                                                   swapped=[1 if swapped else 0], max_contacts=cap)
+    except engine.EngineError as e:
+        if e.code in (abi.ERR_INVALID_ARGUMENT, abi.ERR_UNSUPPORTED_PAIR, abi.ERR_LIMIT):
+            raise ValueError(str(e))
+        raise
+    if abi.status_skipped(rec[0]["status"]):
+        return result.numContacts()
+    if dlb[0] < result.distance_lower_bound:
+        result.distance_lower_bound = float(dlb[0])
+        if rec[0]["num_contacts"] == 0:  # (a record with a contact carries the contact's rebuilt points, not the result's)
+            result.normal = np.array(rec[0]["normal"])
+            result.nearest_points = [np.array(rec[0]["p1"]), np.array(rec[0]["p2"])]
+    for c in contacts:
+        if result.numContacts() < request.num_max_contacts:
+            result.addContact(Contact(tree, solid, c["b1"], c["b2"], c["p1"], c["p2"], c["normal"], c["penetration_depth"]))
+    return result.numContacts()
+
+
 def collide(*args):
     """collide(o1, tf1, o2, tf2, request, result) or collide(obj1, obj2, request, result)  (python/collision.cc:257-266)"""
     if len(args) == 4:
@@ -673,6 +809,8 @@ def collide(*args):
         return result.numContacts()
     if isinstance(o1, HeightFieldAABB) or isinstance(o2, HeightFieldAABB):
         return _collide_hfield(o1, tf1, o2, tf2, request, result)
+    if isinstance(o1, OcTree) or isinstance(o2, OcTree):
+        return _collide_octree(o1, tf1, o2, tf2, request, result)
     rec, g, contacts = _run("collide", [(o1, tf1, o2, tf2)], request)
     _fill_collision(result, o1, o2, request, rec[0], g[0] if g is not None else None, contacts)
     return result.numContacts()

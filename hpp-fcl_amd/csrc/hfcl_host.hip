@@ -250,7 +250,7 @@ static const char* const* option_keys() {
       "bvh_walk_rounds", "bvh_walk_order", "mesh_beside", "mesh_prio", "shape_walk", "shape_walk_sort", "shape_walk_budget", "shape_walk_min", "gjk_beside_max", "epa_direct_max", "bvh_walk_k", "bvh_walk_budget", "shape_dist_leaf_min", "shape_dist_starve", "bvhd_leaf_min", "bvhd_starve",
       "bvhd_part_min", "shape_dist_budget", "bvh_budget0_coop", "shape_budget0", "shape_budget", "shape_leaf_cost", "shape_levels",
       "climb_min", "bvh_budget", "bvh_budget0", "bvh_levels", "cvx_w", "epa_resume_slots", "bvh_task_slots", "bvh_force_wide",
-      "pipe_trace", "scene_chunk", "scene_cull_chunk", "scene_pairs_small_max", "scene_pairs_sorted", "scene_pairs_sorted_axis", "scene_env_span", "scene_nearest_env_prune", "epa_pool_share", "epa_pool_min_refills", "hfield_chunk", "hfield_items", nullptr};
+      "pipe_trace", "scene_chunk", "scene_cull_chunk", "scene_pairs_small_max", "scene_pairs_sorted", "scene_pairs_sorted_axis", "scene_env_span", "scene_nearest_env_prune", "epa_pool_share", "epa_pool_min_refills", "hfield_chunk", "hfield_items", "octree_chunk", "octree_items", nullptr};
   return keys;
 }
 // "4,16,16": up to `cap` comma-separated unsigned values into out[first...]; returns how many were read
@@ -365,6 +365,14 @@ static int apply_option(hfcl_lib* lib, const std::string& key, const char* v) {
   else if (key == "hfield_items") {
     if (i < 0 || i > (1ll << 26)) return HFCL_ERR_INVALID_ARGUMENT;  // (the item workspace of one query's limit)
     lib->opt.hfield_items = size_t(i);
+  }
+  else if (key == "octree_chunk") {
+    if (i < 0 || i > 0xFFFFFFF0ll) return HFCL_ERR_INVALID_ARGUMENT;
+    lib->opt.octree_chunk = size_t(i);
+  }
+  else if (key == "octree_items") {
+    if (i < 0 || i > (1ll << 26)) return HFCL_ERR_INVALID_ARGUMENT;  // (the item workspace of one query's limit)
+    lib->opt.octree_items = size_t(i);
   }
   else return HFCL_ERR_INVALID_ARGUMENT;
   return HFCL_OK;

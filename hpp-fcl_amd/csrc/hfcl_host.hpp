@@ -22,6 +22,7 @@
 #include "hfcl_cull.hpp"
 #include "hfcl_pairs.hpp"
 #include "hfcl_hfield.hpp"
+#include "hfcl_octree.hpp"
 #include "hfcl_own.hpp"
 
 __attribute__((visibility("hidden"))) void set_error(const std::string& s);  // the calling thread's hfcl_last_error()
@@ -145,6 +146,10 @@ struct hfcl_options {
   // lists more than 2^20 (query, leaf) items is cut down further.  The records do not depend on it
   size_t hfield_chunk = 0;
   size_t hfield_items = 0;  // option hfield_items: the items a chunk may list before it is cut down (0: automatic -- 2^20); a chunk of one query is never cut
+  // Queries per chunk of hfcl_octree_collide_batch* (option octree_chunk; 0: automatic -- 65536) and the items a chunk may list before it is
+  // cut down (option octree_items; 0: automatic -- 2^20; a chunk of one query is never cut).  The records depend on neither
+  size_t octree_chunk = 0;
+  size_t octree_items = 0;
   int cvx_w = 0;  // 0 = per kernel (auto_cvx_w); HFCL_CVX_W forces one width for all
   bool closed_staged = true;  // HFCL_CLOSED_STAGED=0: A/B switch back to the direct-access k_closed<double>
   bool bvh_filter = false;     // HFCL_BVH_FILTER=1: the fp32 filter form of k_bvh_collide (exact, measured slower: profiles/r03_b)
@@ -376,6 +381,28 @@ struct hfcl_lib {
     DevBuf<hfcl_result> s_out;
     DevBuf<hfcl_contact> s_contacts;
   } hf;
+  // octrees (hfcl_lib_add_octree; hfcl_host_octree.hip): the host tables of every registered tree one after the other, their device
+  // images (uploaded by the next call when a tree was added or its thresholds set since), the workspace of a chunk of queries and its
+  // items, the host form's stream and staging, and the call's contact list
+  struct Octrees {
+    std::vector<DOctree> h_trees;
+    std::vector<hfcl_octree_node> h_nodes;
+    bool dirty = false;
+    DevBuf<DOctree> d_trees;
+    DevBuf<hfcl_octree_node> d_nodes;
+    DevBuf<uint32_t> d_counts, d_ccounts;
+    DevBuf<uint64_t> d_offsets, d_coffsets, d_running;
+    DevBuf<double> d_box_total;
+    DevBuf<OctItem<double>> d_items;
+    DevBuf<OctLeafOut<double>> d_leaves;
+    PinnedBuf<uint64_t> h_words;  // pinned: [0] a chunk's item count, [1] the call's contact count
+    Stream st;
+    DevBuf<uint32_t> s_octree, s_shape;
+    DevBuf<double> s_tft, s_tfs, s_dlb;
+    DevBuf<uint8_t> s_swapped;
+    DevBuf<hfcl_result> s_out;
+    DevBuf<hfcl_contact> s_contacts;
+  } oct;
   // local AABB of every library shape (hfcl_cull.hpp: shape_local_box; BVH models: the box of their vertices), 6 doubles each, rebuilt when
   // shapes or meshes were registered since (hfcl_lib_set_shapes, hfcl_lib_add_bvh)
   DevBuf<double> d_local_boxes;
@@ -467,4 +494,6 @@ int hf_run(hfcl_lib* lib, const uint32_t* d_hfield, const uint32_t* d_shape, con
            const uint8_t* d_swapped, const hfcl_collision_request* req, const QParams<double>& q, bool skip_all, hfcl_result* d_out, double* d_dlb,
            hfcl_contact* d_contacts, size_t contacts_cap, bool want_contacts, uint32_t pair0, bool first, hipStream_t st);
 int hf_no_device();
+// hfcl_host_scene.hip: the library's local boxes on the device (lib->d_local_boxes), rebuilt when shapes or meshes were registered since
+int ensure_local_boxes(hfcl_lib* lib);
 #pragma GCC visibility pop

@@ -417,7 +417,7 @@ static int scene_device(const char* who, hfcl_scene* s, const void* d_table, siz
 // hfcl_scene_*_culled).  hfcl_k_cull.hip has the kernels, hfcl_cull.hpp the arithmetic.
 // ---------------------------------------------------------------------------------------
 // the library's local boxes on the device, rebuilt when shapes or meshes were registered since
-static int ensure_local_boxes(hfcl_lib* lib) {
+int ensure_local_boxes(hfcl_lib* lib) {  // (declared in hfcl_host.hpp: the octree unit builds the solids' OBBs from them)
   if (!lib->local_boxes_dirty && lib->d_local_boxes) return HFCL_OK;
   const double nan = __builtin_nan("");
   std::vector<double> boxes(6 * lib->n_shapes);

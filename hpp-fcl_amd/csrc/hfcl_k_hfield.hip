@@ -163,6 +163,11 @@ void launch_hf_count(hipStream_t st, const HfArgs& a) {
   hipLaunchKernelGGL(k_hf_scan, dim3(1), dim3(256), 0, st, a.counts, a.offsets, a.m, static_cast<uint64_t*>(nullptr));
 }
 
+// the scan on its own, for the units that list items the same way (hfcl_k_octree.hip)
+void launch_hf_scan(hipStream_t st, const uint32_t* counts, uint64_t* offsets, uint32_t m, uint64_t* running) {
+  hipLaunchKernelGGL(k_hf_scan, dim3(1), dim3(256), 0, st, counts, offsets, m, running);
+}
+
 void launch_hf_solve(hipStream_t st, const HfArgs& a, int max_blocks, bool want_contacts, const char** names, hipEvent_t* e0, hipEvent_t* e1) {
   static const char* const kn[HF_TIMED_KERNELS] = {"k_hf_walk<emit>", "k_hf_leaf", "k_hf_fold", "k_hf_scan<contacts>", "k_hf_fold<contacts>"};
   for (int k = 0; k < HF_TIMED_KERNELS; ++k) names[k] = kn[k];

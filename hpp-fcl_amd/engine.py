@@ -87,6 +87,12 @@ TERRAIN_SYMBOLS = [
     "hfcl_scene_set_terrain", "hfcl_scene_clear_terrain", "hfcl_scene_n_terrain_objects", "hfcl_scene_collide_terrain",
     "hfcl_scene_collide_terrain_device",
 ]
+# include/hppfcl_amd_octree.h (included by hppfcl_amd.h): an occupancy OcTree against convex solids
+OCTREE_SYMBOLS = [
+    "hfcl_octree_validate", "hfcl_octree_from_points", "hfcl_lib_add_octree", "hfcl_lib_octree_set_thresholds", "hfcl_lib_octree_count",
+    "hfcl_lib_clear_octrees", "hfcl_octree_root_box", "hfcl_octree_pair_supported", "hfcl_octree_collide_batch",
+    "hfcl_octree_collide_batch_device",
+]
 
 
 class EngineError(RuntimeError):
@@ -144,6 +150,8 @@ def dll():
             d.hfcl_scene_n_moving.restype = C.c_size_t
         if hasattr(d, "hfcl_lib_hfield_count"):
             d.hfcl_lib_hfield_count.restype = C.c_size_t
+        if hasattr(d, "hfcl_lib_octree_count"):
+            d.hfcl_lib_octree_count.restype = C.c_size_t
         if hasattr(d, "hfcl_scene_n_terrain_objects"):
             d.hfcl_scene_n_terrain_objects.restype = C.c_size_t
         _DLL = d
@@ -199,6 +207,38 @@ def hfield_build(x_dim, y_dim, heights, min_height=0.0):
     _check(dll().hfcl_hfield_build(C.c_double(x_dim), C.c_double(y_dim), abi.ptr(h), C.c_size_t(ny), C.c_size_t(nx), C.c_double(min_height),
                                    abi.ptr(nodes), C.byref(n), abi.ptr(xg), abi.ptr(yg)))
     return nodes, xg, yg
+
+
+def octree_pair_supported(node_type):
+    """hfcl_octree_pair_supported: does collide() have an octree row for a solid of this node type?"""
+    return bool(dll().hfcl_octree_pair_supported(C.c_int32(int(node_type))))
+
+
+def _octree_nodes(nodes):
+    nodes = np.ascontiguousarray(nodes, dtype=abi.OCTREE_NODE_DTYPE)
+    if nodes.ndim != 1:
+        raise ValueError("nodes: a 1-d array of OCTREE_NODE_DTYPE")
+    return nodes
+
+
+def octree_validate(nodes, depth):
+    """hfcl_octree_validate: raises EngineError (last_error names the rule) unless the node array is one tree of at most `depth` levels
+    (host, no GPU needed)."""
+    nodes = _octree_nodes(nodes)
+    _check(dll().hfcl_octree_validate(abi.ptr(nodes) if len(nodes) else None, C.c_size_t(len(nodes)), C.c_uint32(int(depth))))
+
+
+def octree_from_points(points, resolution, depth=abi.OCTREE_MAX_DEPTH):
+    """hfcl_octree_from_points: nodes[OCTREE_NODE_DTYPE] of makeOctree(points, resolution) without octomap (host, no GPU needed): one
+    leaf at level `depth` per voxel hit, nodes in depth-first preorder."""
+    xyz = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    n = C.c_size_t(0)
+    args = (abi.ptr(xyz) if len(xyz) else None, C.c_size_t(len(xyz)), C.c_double(resolution), C.c_uint32(int(depth)))
+    _check(dll().hfcl_octree_from_points(*args, None, C.c_size_t(0), C.byref(n)))
+    nodes = np.zeros(n.value, dtype=abi.OCTREE_NODE_DTYPE)
+    if n.value:
+        _check(dll().hfcl_octree_from_points(*args, abi.ptr(nodes), C.c_size_t(n.value), C.byref(n)))
+    return nodes
 
 
 def has_ab_forms():
@@ -416,6 +456,70 @@ class Library:
         (the call then waits for the stream), else None."""
         nc = C.c_size_t(0)
         _check(dll().hfcl_hfield_collide_batch_device(self._h, _dptr(d_hfield), _dptr(d_shape), _dptr(d_tf_hfield), _dptr(d_tf_shape),
+                                                      C.c_size_t(n), _dptr(d_swapped), C.byref(req), _dptr(d_out), _dptr(d_bound),
+                                                      _dptr(d_contacts), C.c_size_t(int(max_contacts)), C.byref(nc) if want_count else None,
+                                                      C.c_void_p(stream)))
+        return int(nc.value) if want_count else None
+
+    # ---- octrees (hfcl_lib_add_octree, hfcl_octree_collide_batch*) ----
+    def add_octree(self, nodes, resolution, depth=abi.OCTREE_MAX_DEPTH, occupancy_threshold=0.5, free_threshold=0.0):
+        """Register an occupancy octree given as a node array (OCTREE_NODE_DTYPE; engine.octree_from_points makes one).  Returns its
+        index on this library."""
+        nodes = _octree_nodes(nodes)
+        idx = dll().hfcl_lib_add_octree(self._h, abi.ptr(nodes) if len(nodes) else None, C.c_size_t(len(nodes)), C.c_double(resolution),
+                                        C.c_uint32(int(depth)), C.c_double(occupancy_threshold), C.c_double(free_threshold))
+        if idx < 0:
+            raise EngineError(abi.ERR_INVALID_ARGUMENT, last_error())
+        return idx
+
+    def octree_set_thresholds(self, octree, occupancy_threshold, free_threshold):
+        """setOccupancyThres / setFreeThres of a registered octree: hfcl_lib_octree_set_thresholds."""
+        _check(dll().hfcl_lib_octree_set_thresholds(self._h, C.c_int(int(octree)), C.c_double(occupancy_threshold), C.c_double(free_threshold)))
+
+    def octree_count(self):
+        return int(dll().hfcl_lib_octree_count(self._h))
+
+    def clear_octrees(self):
+        """Forget every registered octree (indices start at 0 again): hfcl_lib_clear_octrees."""
+        _check(dll().hfcl_lib_clear_octrees(self._h))
+
+    def octree_root_box(self, octree):
+        """getRootBV of a registered octree: (min xyz, max xyz)."""
+        out = np.zeros(6)
+        _check(dll().hfcl_octree_root_box(self._h, C.c_int(int(octree)), abi.ptr(out)))
+        return out
+
+    def octree_collide(self, octree, shape, tf_octree, tf_shape, req=None, swapped=None, max_contacts=0, want_bound=True):
+        """Batched collide(OcTree, solid) -- swapped[i] = 1: the caller's order was collide(solid, OcTree), which the reference answers
+        with the octree-first result (bit 23 of the status alone changes) -- from host arrays.  Returns (records,
+        distance_lower_bound or None, contacts[CONTACT_DTYPE], n_produced)."""
+        req = req or abi.default_collision_request()
+        octree = np.ascontiguousarray(octree, dtype=np.uint32)
+        shape = np.ascontiguousarray(shape, dtype=np.uint32)
+        tft = np.ascontiguousarray(tf_octree, dtype=np.float64).reshape(-1, 12)
+        tfs = np.ascontiguousarray(tf_shape, dtype=np.float64).reshape(-1, 12)
+        n = len(octree)
+        if not (len(shape) == len(tft) == len(tfs) == n):
+            raise ValueError("batch arrays must have equal length")
+        if swapped is not None:
+            swapped = np.ascontiguousarray(swapped, dtype=np.uint8)
+            if len(swapped) != n:
+                raise ValueError("swapped: one byte per query")
+        out = np.zeros(n, dtype=abi.RESULT_DTYPE)
+        dlb = np.zeros(n) if want_bound else None
+        contacts = np.zeros(int(max_contacts), dtype=abi.CONTACT_DTYPE)
+        nc = C.c_size_t(0)
+        _check(dll().hfcl_octree_collide_batch(self._h, abi.ptr(octree), abi.ptr(shape), abi.ptr(tft), abi.ptr(tfs), C.c_size_t(n),
+                                               abi.ptr(swapped), C.byref(req), abi.ptr(out), abi.ptr(dlb),
+                                               abi.ptr(contacts) if max_contacts else None, C.c_size_t(int(max_contacts)), C.byref(nc)))
+        return out, dlb, contacts[:min(nc.value, int(max_contacts))], int(nc.value)
+
+    def octree_collide_device(self, d_octree, d_shape, d_tf_octree, d_tf_shape, n, req, d_out, d_swapped=None, d_bound=None, d_contacts=None,
+                              max_contacts=0, want_count=False, stream=0):
+        """The same call on device pointers (torch tensors or raw pointers).  Returns the number of contacts produced when want_count
+        (the call then waits for the stream), else None."""
+        nc = C.c_size_t(0)
+        _check(dll().hfcl_octree_collide_batch_device(self._h, _dptr(d_octree), _dptr(d_shape), _dptr(d_tf_octree), _dptr(d_tf_shape),
                                                       C.c_size_t(n), _dptr(d_swapped), C.byref(req), _dptr(d_out), _dptr(d_bound),
                                                       _dptr(d_contacts), C.c_size_t(int(max_contacts)), C.byref(nc) if want_count else None,
                                                       C.c_void_p(stream)))

@@ -120,7 +120,8 @@ enum NODE_TYPE {  // include/hpp/fcl/collision_object.h:65-89 (subset in scope)
   GEOM_CONE = HFCL_GEOM_CONE, GEOM_CYLINDER = HFCL_GEOM_CYLINDER, GEOM_PLANE = HFCL_GEOM_PLANE,
   GEOM_HALFSPACE = HFCL_GEOM_HALFSPACE,
   GEOM_CONVEX = HFCL_GEOM_CONVEX, GEOM_TRIANGLE = HFCL_GEOM_TRIANGLE, GEOM_ELLIPSOID = HFCL_GEOM_ELLIPSOID,
-  HF_AABB = 20, HF_OBBRSS = 21  // height fields: HF_AABB has collide() against the convex solids (hppfcl_amd_hfield.h)
+  HF_AABB = 20, HF_OBBRSS = 21,  // height fields: HF_AABB has collide() against the convex solids (hppfcl_amd_hfield.h)
+  GEOM_OCTREE = 18               // an occupancy octree: collide() against the convex solids (hppfcl_amd_octree.h)
 };
 enum GJKInitialGuess { DefaultGuess, CachedGuess, BoundingVolumeGuess };
 enum GJKVariant { DefaultGJK, PolyakAcceleration, NesterovAcceleration };
@@ -456,6 +457,80 @@ class HeightField : public CollisionGeometry {
   BVS bvs_;
   unsigned int version_ = 0;
 };
+
+/// OcTree (include/hpp/fcl/octree.h:53-296) over a node array instead of an octomap tree: node 0 is the root, child[i] the index of
+/// child i (0: none).  Every box is halved down from getRootBV, as the reference computes them.  collide() against a convex solid, in
+/// either operand order, goes to hfcl_octree_collide_batch and returns the octree-first result (the reference does not swap it back).
+class OcTree : public CollisionGeometry {
+ public:
+  typedef hfcl_octree_node OcTreeNode;
+  typedef std::array<FCL_REAL, 6> Vec6f;
+  OcTree(const std::vector<OcTreeNode>& nodes, FCL_REAL resolution, unsigned int depth = HFCL_OCTREE_MAX_DEPTH)
+      : nodes_(nodes), resolution_(resolution), depth_(depth) {
+    if (hfcl_octree_validate(nodes_.data(), nodes_.size(), depth_)) throw std::invalid_argument(hfcl_last_error());
+    if (!(resolution_ > 0)) throw std::invalid_argument("OcTree: the resolution must be positive");
+  }
+  NODE_TYPE getNodeType() const override { return GEOM_OCTREE; }
+  unsigned int getTreeDepth() const { return depth_; }
+  FCL_REAL getResolution() const { return resolution_; }
+  unsigned long size() const { return nodes_.size(); }
+  const std::vector<OcTreeNode>& getNodes() const { return nodes_; }
+  AABB getRootBV() const {  // octree.h:139-144
+    const FCL_REAL delta = (1 << depth_) * resolution_ / 2;
+    AABB bv;
+    bv.min_ = Vec3f(-delta, -delta, -delta);
+    bv.max_ = Vec3f(delta, delta, delta);
+    return bv;
+  }
+  FCL_REAL getOccupancyThres() const { return occupancy_threshold_; }
+  FCL_REAL getFreeThres() const { return free_threshold_; }
+  void setOccupancyThres(FCL_REAL d) { occupancy_threshold_ = d; }
+  void setFreeThres(FCL_REAL d) { free_threshold_ = d; }
+  bool isNodeOccupied(const OcTreeNode* n) const { return n->occupancy >= occupancy_threshold_; }
+  bool isNodeFree(const OcTreeNode* n) const { return n->occupancy <= free_threshold_; }
+  bool isNodeUncertain(const OcTreeNode* n) const { return !isNodeOccupied(n) && !isNodeFree(n); }
+  /// toBoxes (octree.h:178-200): (x, y, z, size, occupancy, threshold) of the occupied leaves, depth-first with the children in index
+  /// order, centre and size from the halved boxes
+  std::vector<Vec6f> toBoxes() const {
+    std::vector<Vec6f> boxes;
+    if (!nodes_.empty()) to_boxes(0, getRootBV(), boxes);
+    return boxes;
+  }
+
+ private:
+  void to_boxes(uint32_t i, const AABB& bv, std::vector<Vec6f>& out) const {  // (at most depth + 1 levels: the validator's)
+    const OcTreeNode& n = nodes_[i];
+    bool leaf = true;
+    for (unsigned int k = 0; k < 8; ++k) {
+      if (!n.child[k]) continue;
+      leaf = false;
+      AABB c = bv;
+      for (int a = 0; a < 3; ++a) {  // computeChildBV, octree.h:299-324
+        if (k & (1u << a)) c.min_[a] = (bv.min_[a] + bv.max_[a]) * 0.5;
+        else c.max_[a] = (bv.min_[a] + bv.max_[a]) * 0.5;
+      }
+      to_boxes(n.child[k], c, out);
+    }
+    if (leaf && isNodeOccupied(&n))
+      out.push_back({{(bv.min_[0] + bv.max_[0]) * 0.5, (bv.min_[1] + bv.max_[1]) * 0.5, (bv.min_[2] + bv.max_[2]) * 0.5, bv.max_[0] - bv.min_[0],
+                      n.occupancy, occupancy_threshold_}});
+  }
+  std::vector<OcTreeNode> nodes_;
+  FCL_REAL resolution_;
+  unsigned int depth_;
+  FCL_REAL occupancy_threshold_ = 0.5, free_threshold_ = 0;
+};
+/// makeOctree (src/octree.cpp:188-202) without octomap: points as x y z triples; hfcl_octree_from_points at octomap's depth of 16
+inline std::shared_ptr<OcTree> makeOctree(const std::vector<Vec3f>& point_cloud, FCL_REAL resolution) {
+  static_assert(sizeof(Vec3f) == 3 * sizeof(double), "Vec3f must be three doubles");
+  std::size_t n = 0;
+  const double* xyz = point_cloud.empty() ? nullptr : reinterpret_cast<const double*>(point_cloud.data());
+  if (hfcl_octree_from_points(xyz, point_cloud.size(), resolution, HFCL_OCTREE_MAX_DEPTH, nullptr, 0, &n)) throw std::invalid_argument(hfcl_last_error());
+  std::vector<hfcl_octree_node> nodes(n);
+  if (n && hfcl_octree_from_points(xyz, point_cloud.size(), resolution, HFCL_OCTREE_MAX_DEPTH, nodes.data(), n, &n))
+    throw std::invalid_argument(hfcl_last_error());
+  return std::make_shared<OcTree>(nodes, resolution, HFCL_OCTREE_MAX_DEPTH);
+}
 
 struct QueryRequest {
   GJKInitialGuess gjk_initial_guess = DefaultGuess;
@@ -1035,6 +1110,150 @@ inline bool hfield_pair_supported(const CollisionGeometry* o1, const CollisionGe
 }
 inline bool is_hfield(const CollisionGeometry* g) { return g->getNodeType() == HF_AABB || g->getNodeType() == HF_OBBRSS; }
 
+/// Batched collide() of OcTree objects against convex solids (hfcl_octree_collide_batch) on the library of a BatchQueries context: the
+/// solids are that context's geometries, the trees are registered here (and again after the context was reset, or when a tree's
+/// thresholds were set since).  One OcTreeBatch per context; reset() forgets the trees, here and on the library.
+class OcTreeBatch {
+ public:
+  explicit OcTreeBatch(BatchQueries& ctx) : ctx_(ctx) {}
+  uint32_t addSolid(const CollisionGeometry* g) { return ctx_.add(g); }
+  size_t numTrees() const { return trees_.size(); }
+  void reset() {
+    if (lib_ && generation_ == ctx_.libraryGeneration()) hfcl_lib_clear_octrees(lib_);
+    trees_.clear();
+  }
+  uint32_t addTree(const OcTree* t) {
+    // keyed by address; a hit is trusted only while the tree's content is what was copied (addresses get reused)
+    for (size_t k = 0; k < trees_.size(); ++k) {
+      const Entry& o = trees_[k];
+      if (o.tree != t || o.resolution != t->getResolution() || o.depth != t->getTreeDepth() || o.nodes.size() != t->getNodes().size()) continue;
+      if (o.nodes.empty() || std::memcmp(o.nodes.data(), t->getNodes().data(), o.nodes.size() * sizeof(hfcl_octree_node)) == 0) return static_cast<uint32_t>(k);
+    }
+    Entry e;
+    e.tree = t;
+    e.resolution = t->getResolution();
+    e.depth = t->getTreeDepth();
+    e.nodes = t->getNodes();  // a copy: the tree may be gone by the next query
+    trees_.push_back(e);
+    return static_cast<uint32_t>(trees_.size() - 1);
+  }
+  /// The index of tree k (addTree) on the context's library as it is now, registered or its thresholds set there as needed.
+  uint32_t libraryIndex(uint32_t k) {
+    hfcl_lib* lib = ctx_.library();
+    if (lib != lib_ || generation_ != ctx_.libraryGeneration()) {
+      lib_ = lib;
+      generation_ = ctx_.libraryGeneration();
+      for (Entry& e : trees_) e.index = -1;
+    }
+    Entry& e = trees_.at(k);
+    const FCL_REAL occ = e.tree->getOccupancyThres(), fr = e.tree->getFreeThres();
+    if (e.index < 0) {
+      e.index = hfcl_lib_add_octree(lib, e.nodes.data(), e.nodes.size(), e.resolution, e.depth, occ, fr);
+      if (e.index < 0) throw std::invalid_argument(hfcl_last_error());
+    } else if (e.occ != occ || e.free != fr) {
+      if (hfcl_lib_octree_set_thresholds(lib, e.index, occ, fr)) throw std::invalid_argument(hfcl_last_error());
+    }
+    e.occ = occ;
+    e.free = fr;
+    return static_cast<uint32_t>(e.index);
+  }
+  /// Query i: collide(tree, solid), or collide(solid, tree) where swapped[i] -- the same result either way but for the order of the
+  /// operands the caller named (the reference does not swap an octree query back).  Results are fresh objects: the tree is o1 of every
+  /// contact and its node b1.
+  void collide(const std::vector<std::pair<uint32_t, uint32_t>>& tree_solid, const std::vector<Transform3f>& tf_tree,
+               const std::vector<Transform3f>& tf_solid, const std::vector<uint8_t>& swapped, const CollisionRequest& request,
+               std::vector<CollisionResult>& results) {
+    const size_t n = tree_solid.size();
+    if (tf_tree.size() != n || tf_solid.size() != n || (!swapped.empty() && swapped.size() != n))
+      throw std::invalid_argument("pairs/poses size mismatch");
+    hfcl_lib* lib = ctx_.library();
+    std::vector<uint32_t> ot(n), sh(n);
+    for (size_t i = 0; i < n; ++i) {
+      ot[i] = libraryIndex(tree_solid[i].first);
+      sh[i] = tree_solid[i].second;
+    }
+    const hfcl_collision_request a = to_abi(request);
+    rec_.resize(n);
+    bound_.resize(n);
+    size_t cap = std::max<size_t>(64, 4 * n), produced = 0;
+    int rc = HFCL_OK;
+    for (int attempt = 0; attempt < 2; ++attempt) {  // (a list that outgrew the guess: once more with the count)
+      contacts_.resize(cap);
+      rc = hfcl_octree_collide_batch(lib, ot.data(), sh.data(), reinterpret_cast<const double*>(tf_tree.data()),
+                                     reinterpret_cast<const double*>(tf_solid.data()), n, swapped.empty() ? nullptr : swapped.data(), &a,
+                                     rec_.data(), bound_.data(), contacts_.data(), cap, &produced);
+      if (rc || produced <= cap) break;
+      cap = produced;
+    }
+    if (rc == HFCL_ERR_LIMIT) throw std::invalid_argument(hfcl_last_error());
+    if (rc) throw_for(rc);
+    contacts_.resize(std::min(produced, cap));
+    results.assign(n, CollisionResult());
+    size_t k = 0;
+    for (size_t i = 0; i < n; ++i)
+      fill(results[i], rec_[i], bound_[i], trees_[tree_solid[i].first].tree, ctx_.geometry(sh[i]), static_cast<uint32_t>(i), k, request);
+  }
+  /// One record into a result that may hold earlier ones: every contact and the call's bound; the result's nearest_points / normal
+  /// are set from a record without a contact (one with a contact carries the contact's rebuilt points instead).
+  void fill(CollisionResult& res, const hfcl_result& r, double bound, const CollisionGeometry* tree, const CollisionGeometry* solid, uint32_t query,
+            size_t& k, const CollisionRequest& request) const {
+    while (k < contacts_.size() && contacts_[k].pair < query) ++k;
+    if (HFCL_STATUS_SKIPPED(r.status)) return;
+    if (bound < res.distance_lower_bound) {
+      res.distance_lower_bound = bound;
+      if (r.num_contacts == 0) {
+        res.normal = Vec3f(r.normal[0], r.normal[1], r.normal[2]);
+        res.nearest_points = {{Vec3f(r.p1[0], r.p1[1], r.p1[2]), Vec3f(r.p2[0], r.p2[1], r.p2[2])}};
+      }
+    }
+    for (; k < contacts_.size() && contacts_[k].pair == query; ++k) {
+      if (res.numContacts() >= request.num_max_contacts) continue;
+      const hfcl_contact& h = contacts_[k];
+      Contact c;
+      c.o1 = tree;
+      c.o2 = solid;
+      c.b1 = h.b1;
+      c.b2 = h.b2;
+      c.normal = Vec3f(h.normal[0], h.normal[1], h.normal[2]);
+      c.nearest_points = {{Vec3f(h.p1[0], h.p1[1], h.p1[2]), Vec3f(h.p2[0], h.p2[1], h.p2[2])}};
+      c.pos = (c.nearest_points[0] + c.nearest_points[1]) / 2;
+      c.penetration_depth = h.penetration_depth;
+      res.addContact(c);
+    }
+  }
+  const std::vector<hfcl_result>& records() const { return rec_; }
+  const std::vector<double>& bounds() const { return bound_; }
+  const std::vector<hfcl_contact>& contacts() const { return contacts_; }
+
+ private:
+  struct Entry {
+    const OcTree* tree;
+    FCL_REAL resolution;
+    unsigned int depth;
+    std::vector<hfcl_octree_node> nodes;
+    FCL_REAL occ = 0, free = 0;  // as set on lib_
+    int index = -1;              // on lib_
+  };
+  BatchQueries& ctx_;
+  hfcl_lib* lib_ = nullptr;
+  uint64_t generation_ = 0;  // ctx_.libraryGeneration() when lib_ was taken
+  std::vector<Entry> trees_;
+  std::vector<hfcl_result> rec_;
+  std::vector<double> bound_;
+  std::vector<hfcl_contact> contacts_;
+};
+constexpr size_t DEFAULT_OCTREE_BATCH_MAX = 16;  // trees the thread's default batch keeps before it starts over
+inline OcTreeBatch& default_octree_batch() {
+  static thread_local OcTreeBatch b(default_context());
+  return b;
+}
+inline bool is_octree(const CollisionGeometry* g) { return g->getNodeType() == GEOM_OCTREE; }
+/// does collide() have a function for this pair with an octree in it?
+inline bool octree_pair_supported(const CollisionGeometry* o1, const CollisionGeometry* o2) {
+  const bool t1 = is_octree(o1), t2 = is_octree(o2);
+  return t1 != t2 && hfcl_octree_pair_supported((t1 ? o2 : o1)->getNodeType()) != 0;
+}
+
 }  // namespace amd
 
 /// hpp::fcl::collide (src/collision.cpp:69-130) as a batch of one.  Results accumulate in
@@ -1058,6 +1277,18 @@ inline std::size_t collide(const CollisionGeometry* o1, const Transform3f& tf1, 
     hb.collide({fs}, {swapped ? tf2 : tf1}, {swapped ? tf1 : tf2}, {static_cast<uint8_t>(swapped ? 1 : 0)}, request, one);
     size_t k = 0;
     hb.fill(result, hb.records()[0], hb.bounds()[0], o1, o2, 0, k, request);
+    return result.numContacts();
+  }
+  if (amd::is_octree(o1) || amd::is_octree(o2)) {  // an octree against a solid, either order (hppfcl_amd_octree.h)
+    if (!amd::octree_pair_supported(o1, o2)) throw std::invalid_argument("Collision function between the two node types is not yet supported.");
+    const bool swapped = !amd::is_octree(o1);
+    amd::OcTreeBatch& ob = amd::default_octree_batch();
+    if (ob.numTrees() >= amd::DEFAULT_OCTREE_BATCH_MAX) ob.reset();
+    const std::pair<uint32_t, uint32_t> ts(ob.addTree(static_cast<const OcTree*>(swapped ? o2 : o1)), ob.addSolid(swapped ? o1 : o2));
+    std::vector<CollisionResult> one;
+    ob.collide({ts}, {swapped ? tf2 : tf1}, {swapped ? tf1 : tf2}, {static_cast<uint8_t>(swapped ? 1 : 0)}, request, one);
+    size_t k = 0;
+    ob.fill(result, ob.records()[0], ob.bounds()[0], swapped ? o2 : o1, swapped ? o1 : o2, 0, k, request);
     return result.numContacts();
   }
   amd::BatchQueries& ctx = amd::default_context();
@@ -1092,7 +1323,9 @@ inline FCL_REAL distance(const CollisionGeometry* o1, const Transform3f& tf1, co
 class ComputeCollision {
  public:
   ComputeCollision(const CollisionGeometry* o1_, const CollisionGeometry* o2_) : o1(o1_), o2(o2_) {
-    if (amd::is_hfield(o1) || amd::is_hfield(o2) ? !amd::hfield_pair_supported(o1, o2) : !hfcl_pair_supported(o1->getNodeType(), o2->getNodeType(), 0))
+    if (amd::is_octree(o1) || amd::is_octree(o2) ? !amd::octree_pair_supported(o1, o2)
+        : amd::is_hfield(o1) || amd::is_hfield(o2) ? !amd::hfield_pair_supported(o1, o2)
+                                                   : !hfcl_pair_supported(o1->getNodeType(), o2->getNodeType(), 0))
       throw std::invalid_argument("Collision function between the two node types is not yet supported.");
   }
   virtual ~ComputeCollision() {}
