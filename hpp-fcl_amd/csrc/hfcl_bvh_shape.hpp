@@ -451,10 +451,13 @@ struct SolidTriSupport {
 // tf_solid.inverseTimes(tf_tri), the relative transform precomputed (identity), and on return the points
 // exchanged and the normal negated.  `o` keeps the statuses / cached guess of that run (solid = shape 0);
 // p_tri / p_solid / n are the world-frame results in (triangle, solid) order.
-template <typename T, class Grp, class Solid>
+// GUARD: the marks of an inconsistent fp32 run (gjk_run<true>, gjk_finish<true>, epa_depth_suspect; o.redo) -- for the top-level pairs
+// of a batch only (triangle_pair), whose record writer lists a marked pair for the fp64 redo.  The leaves of the mesh x solid walks pass
+// nothing: they run the solver as they always did.
+template <typename T, class Grp, bool GUARD = false, class Solid>
 HFCL_HD T triangle_solid_distance(const V3<T>& ta, const V3<T>& tb, const V3<T>& tc, const Pose<T>& tft, const Pose<T>& tfs,
                                   const Solid& solid, T r_solid, const QParams<T>& q, const V3<T>& guess0,
-                                  EpaScratch<T, EPA_MAX_ITER>* scratch, PairOut<T>& o, V3<T>& p_tri, V3<T>& p_solid, V3<T>& n) {
+                                  EpaScratch<T, EPA_MAX_ITER>* scratch, PairOut<T>& o, V3<T>& p_tri, V3<T>& p_solid, V3<T>& n, bool solid_curved = true) {
   const MDiff<T> sMt = make_mdiff(tfs, tft);  // Transform3f::inverseTimes
   SolidTriSupport<T, Solid> sup;
   sup.a = mul(sMt.oR1, ta) + sMt.ot1;
@@ -462,11 +465,12 @@ HFCL_HD T triangle_solid_distance(const V3<T>& ta, const V3<T>& tb, const V3<T>&
   sup.c = mul(sMt.oR1, tc) + sMt.ot1;
   sup.solid = &solid;
   Gjk<T, PW0<T>> g;
-  gjk_run(g, q.gjk, guess0, r_solid, false, sup);
+  gjk_run<GUARD>(g, q.gjk, guess0, r_solid, false, sup);
   EpaSeed<T> seed;
-  if (gjk_finish(g, q, tfs, r_solid, T(0), guess0, o, seed)) {
+  if (gjk_finish<GUARD>(g, q, tfs, r_solid, T(0), guess0, o, seed, solid_curved)) {
     Grp::sync();
     epa_run<T, Grp, EPA_MAX_ITER>(scratch, seed, q, tfs, r_solid, T(0), sup, o);
+    if (GUARD && sizeof(T) == 4) o.redo = epa_depth_suspect(o, tfs, r_solid, T(0), sup, solid_curved);
     Grp::sync();
   }
   p_tri = o.p2;
@@ -511,8 +515,8 @@ HFCL_HD void triangle_pair(const DShape<T>& a, const DShape<T>& b, const T* vert
   } else {
     const V3<T> guess0 = (q.guess_mode == HFCL_GUESS_CACHED) ? guess_in : mk<T>(T(1), T(0), T(0));
     PairOut<T> og;
-    const T d = triangle_solid_distance<T, Grp>(ta, tb, tc, tft, tfs, solid, swept_radius(sol), q, guess0, scratch, og, p_tri,
-                                                p_solid, n);
+    const T d = triangle_solid_distance<T, Grp, true>(ta, tb, tc, tft, tfs, solid, swept_radius(sol), q, guess0, scratch, og, p_tri,
+                                                p_solid, n, kind_is_curved(sol.kind));
     o = og;
     o.distance = d;
   }

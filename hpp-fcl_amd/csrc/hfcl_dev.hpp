@@ -69,7 +69,8 @@ constexpr int CTR_SHAPE_FINISH_OVER = 2 * B_COUNT + 11;  // [+0, +1] mesh x soli
 constexpr int CTR_SHAPE_DEFER_MARK = 2 * B_COUNT + 13;   // CTR_SHAPE_DEFER as the first launch of k_bvh_shape_coop left it: the items of whole walks (k_bvh_level_mark)
 // walks the pooled distance() continuations walked again in the reference's order (BvhSpill::rerun_count): mesh x mesh, mesh x solid
 constexpr int CTR_DIST_RERUN = 2 * B_COUNT + 14, CTR_SHAPE_DIST_RERUN = 2 * B_COUNT + 15;
-constexpr int N_COUNTERS = 2 * B_COUNT + 16;  // bucket populations + the four counters of Work::counts + curved populations + those
+constexpr int CTR_REDO = 2 * B_COUNT + 16;  // pairs of an fp32 batch marked as inconsistent (PairOut::redo): the length of IO<float>::redo_list, k_redo's work
+constexpr int N_COUNTERS = 2 * B_COUNT + 17;  // bucket populations + the four counters of Work::counts + curved populations + those
 // Behind them, in the same allocation and under the same memset: the ticket counters of k_epa_loop's pool (hfcl_epa_pool.hpp), each alone in
 // a 128-byte line -- none shares a line with a counter above or with another (atomics on one line queue up whatever their addresses:
 // profiles/r07_a section 5).  The host reads back the first N_COUNTERS words only.
@@ -168,6 +169,11 @@ template <> struct IO<float> {
   hfcl_result_f32* out;
   const hfcl_guess* gin;  // unused
   hfcl_guess* gout;       // unused
+  // the pairs whose fp32 run was inconsistent, appended by whoever writes their record (write_out) and solved again in fp64 by k_redo
+  // (hfcl_k_redo.hip) at the end of the batch.  nullptr: the batch has no kernel that marks (a library of hulls only).  Room for every pair.
+  uint32_t* redo_list = nullptr;
+  uint32_t* redo_count = nullptr;  // &Work::counts[CTR_REDO]
+  uint32_t redo_cap = 0;           // entries of redo_list (the pairs of the batch)
 };
 
 template <typename T> using EpaItem = EpaSeed<T>;
@@ -245,6 +251,12 @@ __device__ __forceinline__ void write_out(const IO<T>& io, const QParams<T>& q, 
   int nc;
   const bool contact = apply_query_semantics(q, o, nc);
   store_record(io, pair, o, contact, nc);
+  if constexpr (sizeof(T) == 4) {
+    if (o.redo && io.redo_list) {  // (a pair has one record writer: listed once, and the list holds every pair)
+      const uint32_t slot = atomicAdd(io.redo_count, 1u);
+      if (slot < io.redo_cap) io.redo_list[slot] = pair;
+    }
+  }
 }
 
 // BVH pair record: distance = distance_lower_bound + margin (= the first contact's penetration depth
@@ -376,6 +388,7 @@ __device__ __forceinline__ X group_exchange(X v) {
 }
 
 constexpr int HULL_MAX = 32;  // ConvexBase::num_vertices_large_convex_threshold (geometric_shapes.h:709)
+static_assert(uint32_t(HULL_MAX) == REDO_HULL_MAX, "redo_exempt (hfcl_pair.hpp) names the pairs of the convex x convex bucket");
 constexpr int HULL_LARGE_MAX = 1 << 16;  // hulls above HULL_MAX are scanned from memory (k_gjk_large)
 
 template <typename T, int W>

@@ -82,6 +82,7 @@ struct alignas(4 * sizeof(T) > 16 ? 16 : 4 * sizeof(T)) Quad {  // one LDS vecto
 // either tier, so continuing is bit-identical to restarting).
 struct EpaHeader {
   int32_t closest, iterations, pass, status, num_vertices, hull_count, stock_top, stamp, hw;
+  float upper;  // EpaLoop::upper of an fp32 polytope with coordinates: the bound goes on where the saving tier left it
 };
 // Where the shape-0 support point of every polytope vertex lives (needed once, for the witness points):
 //   V0_BLOCK   in the scratch block itself;
@@ -160,12 +161,17 @@ struct EpaLoop {  // state of the expansion loop between two trips
   V3<T> outer_n;
   T outer_d;
   int o0, o1, o2;
+  // fp32, blocks with coordinates (not the convex x convex tier's V0_TAG blocks): the smallest support value n . w the trips of this
+  // tier have seen along a face normal.  Every one of them bounds the penetration depth from above, so the depth of the final face
+  // must not exceed it (Epa::loop_suspect); since the last start or hand-over.
+  T upper;
 };
 
 template <typename T>
 struct EpaResult {
   int status;
   int iterations;
+  bool suspect = false;  // fp32: the final depth exceeds an upper bound the loop itself established (Epa::loop_suspect)
   V3<T> normal;
   T depth;
   // result face (reference order) or single vertex for FallBack: w and w0 of its 3 vertices
@@ -442,6 +448,7 @@ struct __attribute__((may_alias)) EpaLoopOutG {  // overlays EpaReadyG::md .. on
   T nx, ny, nz, depth;       // the last valid `outer` face: normal and distance
   T rw[9];                   // w of its three vertices
   T r0[9];                   // ... and their support points on shape 0
+  int32_t suspect;           // Epa::loop_suspect
 };
 static_assert(sizeof(EpaLoopOutG<float>) <= sizeof(float) * 12 + 2 * sizeof(Quad<float>) * 4 && sizeof(EpaLoopOutG<double>) <= sizeof(double) * 12 + 2 * sizeof(Quad<double>) * 4,
               "the result overlays the pose and vertex area");
@@ -505,6 +512,7 @@ struct Epa {
   T tolerance;
   int max_iterations;  // the request's (reference) limit
   int cap_iterations;  // min(max_iterations, CAP): what this scratch block can hold
+  float resume_upper;  // EpaHeader::upper of the polytope load() continued (run_loop)
   bool overflow;       // the polytope outgrew CAP although the reference's capacity would not be exhausted
   bool resumable;      // ... at an iteration boundary: the scratch block (incl. its hdr) describes it completely
   int status;
@@ -586,6 +594,7 @@ struct Epa {
     cap_iterations = max_it < CAP ? max_it : CAP;
     overflow = false;
     resumable = false;
+    resume_upper = 3.402823466e+38f;
     status = EPA_DID_NOT_RUN;
     num_vertices = 0;
     hull_count = 0;
@@ -1151,6 +1160,7 @@ struct Epa {
     const V3<T> a = vw(L.o0), b = vw(L.o1), c = vw(L.o2), a0 = v0(L.o0), b0 = v0(L.o1), c0 = v0(L.o2);
     o.rw[0] = a.x; o.rw[1] = a.y; o.rw[2] = a.z; o.rw[3] = b.x; o.rw[4] = b.y; o.rw[5] = b.z; o.rw[6] = c.x; o.rw[7] = c.y; o.rw[8] = c.z;
     o.r0[0] = a0.x; o.r0[1] = a0.y; o.r0[2] = a0.z; o.r0[3] = b0.x; o.r0[4] = b0.y; o.r0[5] = b0.z; o.r0[6] = c0.x; o.r0[7] = c0.y; o.r0[8] = c0.z;
+    o.suspect = loop_suspect(L) ? 1 : 0;
   }
   // The loop's result with tags instead of shape-0 support points (V0_TAG blocks; resolved by whoever writes the record).
   HFCL_HD void loop_out(const EpaLoop<T>& L, EpaLoopOut<T>& o) const {
@@ -1242,7 +1252,27 @@ struct Epa {
   // The expansion loop of evaluate() (:1231-1296) as enter / step / result, so that a kernel can interleave
   // the trips of several polytopes with other work (refilling finished lane groups).  `L` is what the
   // reference keeps in locals across trips: the current best face and the last valid `outer` face.
+  // The consistency check of the fp32 loop.  In exact arithmetic the distance of the closest face never exceeds a support value of the
+  // difference along any direction; a final depth above the smallest support value the loop has seen means that an expansion removed
+  // the face the minimum lay on (visibility misjudged on sliver faces of smooth shapes, a polytope that lost the origin).  The batch
+  // then solves the pair again in fp64 (hfcl_k_redo.hip).  Margin: that of epa_depth_suspect (hfcl_pair.hpp).
+  static constexpr bool UPPER = sizeof(T) == 4 && V0M != V0_TAG;
+  HFCL_HD float upper_of(const EpaLoop<T>& L) const {
+    if constexpr (UPPER)
+      return L.upper;
+    else
+      return 3.402823466e+38f;  // (a tier that keeps no bound hands over "no bound")
+  }
+  HFCL_HD bool loop_suspect(const EpaLoop<T>& L) const {
+    if constexpr (UPPER)
+      return L.outer_d > L.upper + T(2e-5) * (T(1) + L.upper);
+    else
+      return false;
+  }
   HFCL_HD void loop_enter(EpaLoop<T>& L, int closest, int iterations, int pass) const {
+    if constexpr (UPPER) {
+      if (iterations == 0) L.upper = Lim<T>::max();
+    }
     L.closest = closest;
     L.iterations = iterations;
     L.pass = pass;
@@ -1267,7 +1297,7 @@ struct Epa {
         if (early == 2) {
           overflow = true;
           resumable = true;
-          if (Grp::lane() == 0) m->hdr = EpaHeader{L.closest, L.iterations, L.pass, status, num_vertices, hull_count, stock_top, stamp, hw};
+          if (Grp::lane() == 0) m->hdr = EpaHeader{L.closest, L.iterations, L.pass, status, num_vertices, hull_count, stock_top, stamp, hw, upper_of(L)};
           Grp::sync();
           return 2;
         }
@@ -1283,7 +1313,7 @@ struct Epa {
         // capacity of this scratch block reached before the reference's limit: hand over
         overflow = true;
         resumable = true;
-        if (Grp::lane() == 0) m->hdr = EpaHeader{L.closest, L.iterations, L.pass, status, num_vertices, hull_count, stock_top, stamp, hw};
+        if (Grp::lane() == 0) m->hdr = EpaHeader{L.closest, L.iterations, L.pass, status, num_vertices, hull_count, stock_top, stamp, hw, upper_of(L)};
         Grp::sync();
         return 2;
       }
@@ -1311,6 +1341,7 @@ struct Epa {
     Grp::sync();
     set_vert(iw, w, w0, tag);
     Grp::sync();
+    if constexpr (UPPER) L.upper = hmin(L.upper, dot(cn, w));
     const FaceTopo tcl = m->ft[closest];
     const V3<T> vf1 = vw(tcl.vid(0)), vf2 = vw(tcl.vid(1)), vf3 = vw(tcl.vid(2));
     const T fdist = dot(cn, w - vf1);
@@ -1337,7 +1368,7 @@ struct Epa {
       if (resumable) {  // hand over as of the start of this iteration (vertex iw is recomputed there)
         --num_vertices;
         --L.pass;
-        if (Grp::lane() == 0) m->hdr = EpaHeader{closest, L.iterations, L.pass, status, num_vertices, hull_count, stock_top, stamp, hw};
+        if (Grp::lane() == 0) m->hdr = EpaHeader{closest, L.iterations, L.pass, status, num_vertices, hull_count, stock_top, stamp, hw, upper_of(L)};
         Grp::sync();
         return 2;
       }
@@ -1360,6 +1391,7 @@ struct Epa {
   HFCL_HD void loop_result(const EpaLoop<T>& L, T ssr_sum, EpaResult<T>& out, const Tags& tags = Tags()) const {
     out.status = status;
     out.iterations = L.iterations;
+    out.suspect = loop_suspect(L);
     out.normal = L.outer_n;
     out.depth = L.outer_d + ssr_sum;
     out.rw0_ = vw(L.o0); out.rw1_ = vw(L.o1); out.rw2_ = vw(L.o2);
@@ -1370,6 +1402,7 @@ struct Epa {
   template <class Sup, class Tags = NoTags>
   HFCL_HD void run_loop(int closest, int iterations, int pass, T ssr_sum, Sup& sup, EpaResult<T>& out, const Tags& tags = Tags()) {
     EpaLoop<T> L;
+    L.upper = iterations == 0 ? Lim<T>::max() : T(resume_upper);  // (a polytope handed over: the bound of the tier that saved it, load())
     loop_enter(L, closest, iterations, pass);
     int r;
     while ((r = step(L, sup)) == 0) {
@@ -1410,6 +1443,7 @@ struct Epa {
     for (int i = Grp::lane(); i < extra; i += Grp::W) m->stock[i] = uint8_t(Src::NF + extra - 1 - i);
     for (int i = Grp::lane(); i < h.stock_top; i += Grp::W) m->stock[extra + i] = src->stock[i];
     status = h.status;
+    resume_upper = h.upper;
     num_vertices = h.num_vertices;
     hull_count = h.hull_count;
     stock_top = h.stock_top + extra;

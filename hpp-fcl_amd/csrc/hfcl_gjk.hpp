@@ -24,6 +24,12 @@ enum {
 enum { VAR_DEFAULT = 0, VAR_POLYAK = 1, VAR_NESTEROV = 2 };
 enum { CRIT_DEFAULT = 0, CRIT_DUALITY_GAP = 1, CRIT_HYBRID = 2 };
 enum { CRIT_RELATIVE = 0, CRIT_ABSOLUTE = 1 };
+// the consistency guard of the fp32 runs (gjk_end): rl < alpha (1 - REL) - ABS.  fp32 round-off of the two norms is ~1e-7 relative;
+// the margins keep honest runs (0 of 200 000 box x capsule, 0 of 200 000 hull x hull records) out.
+constexpr double GJK_GUARD_REL = 1e-5, GJK_GUARD_ABS = 1e-6;
+// why a pair of an fp32 batch is solved again in fp64 (PairOut::redo; 0: it is not)
+enum { REDO_GJK_BOUND = 1, REDO_GJK_GAP = 2, REDO_GJK_WITNESS = 3, REDO_EPA_STATUS = 4, REDO_EPA_BOUND = 5, REDO_EPA_DEPTH = 6, REDO_CLOSED_FORM = 7, REDO_REASONS = 8 };
+constexpr double GJK_SELF_TOL = 2e-5;  // ... and of the final direction's own gap rl - omega: a fifth of the fp32 envelope (1e-4)
 
 // ---------------------------------------------------------------------------------------
 // Tetrahedron Voronoi-region table (gjk.cpp:613-1010).  Predicate k (bit k-1 of the mask)
@@ -124,6 +130,7 @@ struct Gjk {
   T rl, alpha, distance, ssr, upper_bound;
   int iterations, variant, status;
   bool done, normalize;
+  int suspect;  // fp32, gjk_end<true>: a REDO_* reason when the run was inconsistent (0: none); its record is solved again in fp64
 };
 
 // Component-wise select of a simplex vertex.  (A `c ? a : b` on the structs themselves turns
@@ -146,6 +153,7 @@ HFCL_HD void gjk_init(Gjk<T, P>& g, const GjkParams<T>& prm, const V3<T>& guess,
   g.distance = T(0);
   g.rank = 0;
   g.done = false;
+  g.suspect = 0;
   g.normalize = normalize_dir;
   T rl = norm(guess);
   if (rl < prm.tolerance) {
@@ -383,7 +391,12 @@ HFCL_HD bool gjk_project_tetra(Gjk<T, P>& g) {  // :613-1010
 
 // Second half of a trip: the new support vertex `v` (for direction -dir) is appended and
 // checks B, momentum removal, check C and the simplex projection run (gjk.cpp:281-365).
-template <typename T, class P>
+// GUARD (fp32 only): alpha is a lower bound of the distance and rl = |ray| the length of a point of the set, so rl >= alpha in exact
+// arithmetic.  On the sliver simplices that smooth supports (Ellipsoid, Cone, Cylinder) produce, fp32 round-off can pick the interior
+// region of a triangle for a point whose projection lies outside: rl then drops below the distance and below alpha, and check C calls
+// that converged.  Such a run is stopped and marked (Gjk::suspect); the batch solves the pair again in fp64 (hfcl_k_redo.hip).  Kernels
+// that only see pairs of hulls compile it out: it never fires there (vertices are exact supports).
+template <bool GUARD = false, typename T, class P>
 HFCL_HD void gjk_end(Gjk<T, P>& g, const GjkParams<T>& prm, const SimplexV<T, P>& v) {
   g.s3 = g.s2;
   g.s2 = g.s1;
@@ -425,6 +438,11 @@ HFCL_HD void gjk_end(Gjk<T, P>& g, const GjkParams<T>& prm, const SimplexV<T, P>
       g.variant = VAR_DEFAULT;
       return;
     }
+    // (GUARD) check C compares rl with alpha, the best lower bound of ANY trip: the final ray may have converged on the strength of an
+    // earlier direction while its own support value omega (VAR_DEFAULT: dir = ray) lies well below rl.  Exact arithmetic bounds the
+    // distance all the same, but the record's normal then realises it only to first order in the direction's error: the pair is
+    // solved again in fp64 unless the final direction certifies the distance by itself.
+    if (GUARD && sizeof(T) == 4 && g.rl - omega > T(GJK_SELF_TOL) * (T(1) + g.rl)) g.suspect = REDO_GJK_GAP;
     g.distance = g.rl - g.ssr;
     g.status = (g.distance < prm.tolerance) ? GJK_COLLISION_WITH_PEN : GJK_NO_COLLISION;
     g.done = true;
@@ -449,6 +467,13 @@ HFCL_HD void gjk_end(Gjk<T, P>& g, const GjkParams<T>& prm, const SimplexV<T, P>
   if (inside || g.rl == T(0)) {
     g.status = GJK_COLLISION;
     g.distance = g.rl;
+    g.done = true;
+    return;
+  }
+  if (GUARD && sizeof(T) == 4 && g.rank > 1 && g.rl < g.alpha * (T(1) - T(GJK_GUARD_REL)) - T(GJK_GUARD_ABS)) {
+    g.suspect = REDO_GJK_BOUND;
+    g.distance = g.rl - g.ssr;
+    g.status = GJK_FAILED;
     g.done = true;
     return;
   }

@@ -212,6 +212,7 @@ static bool upload_shapes(hfcl_lib* lib, const hfcl_shape* shapes, size_t n_shap
     lib->possible_buckets = mask;
     lib->has_curved = present[K_ELLIPSOID] || present[K_CONE] || present[K_CYLINDER];
     lib->has_flats = present[K_PLANE] || present[K_HALFSPACE];
+    lib->has_capsules = present[K_CAPSULE];
   }
   lib->h_kinds = kinds;
   std::vector<float> v32(3 * n_vertices + 3);
@@ -1518,6 +1519,18 @@ void hfcl_last_bucket_counts(hfcl_lib* lib, uint32_t* out12) {  // B_COUNT bucke
     hipDeviceSynchronize();
   }
   for (int i = 0; i <= B_COUNT + 1; ++i) out12[i] = lib ? total_count(lib, i) : 0;
+}
+
+// Pairs of the last fp32 call whose fp32 run was inconsistent and which the batch solved again in fp64 (CTR_REDO; k_redo).  Waits for the
+// device like hfcl_last_bucket_counts.
+uint32_t hfcl_last_redo_count(hfcl_lib* lib) {
+  if (!lib) return 0;
+  hipSetDevice(lib->device);
+  hipDeviceSynchronize();
+  if (lib->last_host) return lib->acc_counts[CTR_REDO];
+  uint32_t c = lib->h_counts ? lib->h_counts[CTR_REDO] : 0u;
+  if (lib->last_split && lib->helper && lib->helper->h_counts) c += lib->helper->h_counts[CTR_REDO];
+  return c;
 }
 
 // Walks of the last distance() batch that the pooled continuations walked again in the reference's order (BvhSpill::rerun_count): out4 = mesh x mesh

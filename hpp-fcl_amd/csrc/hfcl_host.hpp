@@ -231,6 +231,7 @@ struct hfcl_lib {
   DevBuf<void> d_epa_queue;
   DevBuf<void> d_epa_queue2;
   DevBuf<uint32_t> d_epa_cc_over;  // Work::epa_cc_over (resume_cap entries)
+  DevBuf<uint32_t> d_redo;         // IO<float>::redo_list (ws_capacity entries; fp32 batches of libraries whose kernels mark)
   Stream aux;     // k_epa_records runs here, beside the tiers that continue the handed-over polytopes
   Stream mesh_st;  // the mesh walks of a mixed library's batch run here, beside the solids' kernels (option mesh_beside)
   Event ev_mesh_fork, ev_mesh_join;
@@ -412,6 +413,7 @@ struct hfcl_lib {
   uint32_t possible_buckets = ~0u;   // bit b: some pair of this library's shape kinds classifies into bucket b
   bool has_flats = true;             // some shape is a Plane / Halfspace: their "very rough" volumes are no lower bounds, so what a mesh walk
                                      // against them reports depends on the ORDER of its visits -- the ordered continuation, not the pool
+  bool has_capsules = true;          // some shape is a Capsule: the closed form that marks nearly parallel pairs can occur (closed_form_suspect)
   bool has_curved = true;            // some shape is an Ellipsoid / Cone / Cylinder: the curved class of the fp64 EPA tiers can occur
   int n_cus = 256;
   std::string dominant;

@@ -716,6 +716,13 @@ static int finish_batch(Batch<T>& b, hipStream_t st) {
   hfcl_lib* lib = b.lib;
   {
     Timed t(b, "k_unsupported", st);
+    // fp32: the pairs the batch's kernels marked as inconsistent, solved again in fp64 (hfcl_k_redo.hip) -- every record writer of the
+    // batch is in `st`'s order by now.  Part of the tail's entry in last_kernel_breakdown.  A few percent of the batch at most, and a block
+    // holds four full-capacity polytopes in LDS (three blocks fit a CU): a grid of resident blocks that stride over the list.
+    if constexpr (std::is_same<T, float>::value) {
+      if (b.io.redo_list)
+        launch_redo(int(std::min<size_t>(b.blocks_for(b.n / 64 + 1, 64 / BS_W), size_t(lib->n_cus) * 3)), st, b.wk, lib->d_shapes64, lib->d_verts64, b.io, redo_params(b.q));
+    }
     if (b.may(B_UNSUPPORTED)) launch_unsupported<T>(b.blocks_for(b.n, 256 * 64), st, b.wk, b.io, int(B_UNSUPPORTED));
     if (lib->h_meshes.empty()) {  // BVH shapes without any registered mesh: flagged, never left unwritten
       if (b.may(B_BVHSHAPE)) launch_unsupported<T>(b.blocks_for(b.n, 256 * 64), st, b.wk, b.io, int(B_BVHSHAPE));
@@ -741,6 +748,17 @@ static int run_batch_one(hfcl_lib* lib, const uint32_t* d_s1, const uint32_t* d_
   int rc = ensure_workspace(lib, n, b.any_gjk() && q.compute_penetration);
   if (rc) return rc;
   make_views(b, d_s1, d_s2);
+  if constexpr (std::is_same<T, float>::value) {
+    // The kernels that can mark a pair as inconsistent (hfcl_gjk.hpp: REDO_*) list it for k_redo, the batch's last stage: every GJK kernel
+    // but the one of hull x hull pairs, their EPA tiers, k_triangle, and the Capsule x Capsule closed form.  A library that reaches
+    // none of them (hulls only: the headline) has no list, no launch, and the records it always had.
+    if (b.may(B_PRIM) || b.may(B_PC) || b.may(B_CP) || b.may(B_LARGE) || b.may(B_TRI) || (b.may(B_CLOSED) && lib->has_capsules)) {
+      HIP_TRY(lib->d_redo.grow(lib->ws_capacity));
+      b.io.redo_list = lib->d_redo;
+      b.io.redo_count = lib->d_counts + CTR_REDO;
+      b.io.redo_cap = uint32_t(n);
+    }
+  }
   for (auto& t : lib->timers) t.used = false;
   HIP_TRY(hipMemsetAsync(lib->d_counts, 0, N_COUNTER_WORDS * sizeof(uint32_t), st));
   {
@@ -785,6 +803,7 @@ void share_tables(hfcl_lib* h, const hfcl_lib* lib) {
   h->possible_buckets = lib->possible_buckets;
   h->has_curved = lib->has_curved;
   h->has_flats = lib->has_flats;
+  h->has_capsules = lib->has_capsules;
   h->d_graph_base = t.graph.base;
   h->d_graph_off = t.graph.off;
   h->d_graph_ent32 = t.graph.ent32;

@@ -79,6 +79,28 @@ struct SeedTags {
   }
 };
 
+// fp32: is the EPA record `o` of `pair` to be solved again in fp64 (PairOut::redo)?  The loop's own verdict (Epa::loop_suspect, through
+// epa_finish), a failure status, or -- pairs with a smooth shape -- one support evaluation along the record's normal against its depth
+// (hfcl_pair.hpp: epa_depth_suspect).  ONE function of the record, the shapes and the poses, evaluated by the lane that writes the record
+// with the serial supports, whichever tier and form produced it: the unit contracts a*b+c only inside an expression (FLAGS_k_epa32), so
+// every caller computes the same bits and the same pairs are marked in every form.  Pairs of two register-resident hulls: never.
+template <typename T>
+__device__ __noinline__ int epa_record_redo(const Work& wk, const LibView<T>& lib, const IO<T>& io, uint32_t pair, const PairOut<T>& o) {
+  if constexpr (sizeof(T) == 4) {
+    SerialSupport<T> sup;
+    sup.a = lib.shapes[wk.shape1[pair]];
+    sup.b = lib.shapes[wk.shape2[pair]];
+    if (redo_exempt(sup.a, sup.b)) return 0;
+    sup.va = lib.verts + 3 * size_t(sup.a.vertex_offset);
+    sup.vb = lib.verts + 3 * size_t(sup.b.vertex_offset);
+    const Pose<T> tf1 = load_pose(io.tf1, pair);
+    sup.md = make_mdiff(tf1, load_pose(io.tf2, pair));
+    return epa_depth_suspect(o, tf1, swept_radius(sup.a), swept_radius(sup.b), sup, curved_pair(sup.a.kind, sup.b.kind));
+  } else {
+    return 0;
+  }
+}
+
 template <typename T, int CAP>
 __device__ __forceinline__ EpaSaved<T, CAP>* resume_slot(const Work& wk, uint32_t slot) {
   static_assert(sizeof(EpaSaved<T, CAP>) <= epa_resume_stride<T>, "hand-over slots hold any fast tier's polytope");
@@ -147,6 +169,7 @@ k_epa(Work wk, LibView<T> lib, IO<T> io, QParams<T> q) {
         rc = epa_run<T, LaneGroup<WE>, CAP>(&scratch[grp], item, q, tf1, r0, r1, sup, o, v0_ext);
       }
       if (lig == 0) {
+        o.redo = epa_record_redo<T>(wk, lib, io, pair, o);
         write_out<T>(io, q, pair, o);
         write_guess<T>(io, pair, o.cached_guess, 0, 0);
       }
@@ -154,6 +177,7 @@ k_epa(Work wk, LibView<T> lib, IO<T> io, QParams<T> q) {
       rc = epa_run<T, LaneGroup<WE>, CAP>(&scratch[grp], item, q, tf1, r0, r1, sup, o);
       if (rc == 1) {
         if (lig == 0) {
+          o.redo = epa_record_redo<T>(wk, lib, io, pair, o);
           write_out<T>(io, q, pair, o);
           write_guess<T>(io, pair, o.cached_guess, 0, 0);
         }
@@ -228,6 +252,7 @@ k_epa_stream(Work wk, LibView<T> lib, IO<T> io, QParams<T> q) {
     PairOut<T> o;
     epa_finish(res, ip->gjk_iters, tf1, r0, r1, o);
     if (lig == 0) {
+      if constexpr (!CC) o.redo = epa_record_redo<T>(wk, lib, io, pair, o);
       write_out<T>(io, q, pair, o);
       write_guess<T>(io, pair, o.cached_guess, 0, 0);
     }
@@ -682,6 +707,7 @@ __global__ void __launch_bounds__(256) k_epa_prepare_general(Work wk, LibView<T>
       res.iterations = 0;
       PairOut<T> o;
       epa_finish(res, ip->gjk_iters, load_pose(io.tf1, pair), swept_radius(lib.shapes[wk.shape1[pair]]), swept_radius(lib.shapes[wk.shape2[pair]]), o);
+      o.redo = epa_record_redo<T>(wk, lib, io, pair, o);
       write_out<T>(io, q, pair, o);
       write_guess<T>(io, pair, o.cached_guess, 0, 0);
       rbp->state = EPA_READY_NONE;
@@ -797,8 +823,10 @@ __global__ void __launch_bounds__(256) k_epa_records_general(Work wk, LibView<T>
     res.r00 = mk<T>(lo->r0[0], lo->r0[1], lo->r0[2]);
     res.r01 = mk<T>(lo->r0[3], lo->r0[4], lo->r0[5]);
     res.r02 = mk<T>(lo->r0[6], lo->r0[7], lo->r0[8]);
+    res.suspect = lo->suspect != 0;
     PairOut<T> o;
     epa_finish(res, rb->gjk_iters, load_pose(io.tf1, pair), r0, r1, o);
+    o.redo = epa_record_redo<T>(wk, lib, io, pair, o);
     write_out<T>(io, q, pair, o);
     write_guess<T>(io, pair, o.cached_guess, 0, 0);
   }

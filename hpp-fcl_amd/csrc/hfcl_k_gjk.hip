@@ -111,6 +111,7 @@ __global__ void __launch_bounds__(256) k_closed(Work wk, LibView<T> lib, IO<T> i
     o.gjk_status = GJK_DID_NOT_RUN;
     o.epa_status = EPA_DID_NOT_RUN;
     o.gjk_iters = o.epa_iters = 0;
+    if constexpr (sizeof(T) == 4) o.redo = closed_form_suspect(a, tf1, b, tf2) ? REDO_CLOSED_FORM : 0;
     write_out<T>(io, q, pair, o);
     // the closed forms never touch the solver's cached guess: it stays at its initial value
     write_guess<T>(io, pair, initial_guess<T>(io, q, pair), 0, 0);
@@ -180,13 +181,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HFCL_W
 // sphere / capsule cores (measured on cfg5 with the oracle).  The fp64 fast tier steps the 8 polytopes of a wave in
 // lockstep, so the two classes get a queue each (the second one is the fp32 convex x convex queue, unused in fp64) and
 // a wave's polytopes are of one class: the short ones are not held to the length of the long ones.
-template <typename T, class P, class PS>
+// GUARD / curved: the marks of an inconsistent fp32 run (gjk_run<GUARD>, gjk_finish<GUARD>: hfcl_pair.hpp)
+template <typename T, bool GUARD = false, class P, class PS>
 __device__ __forceinline__ void finish_gjk(const Gjk<T, P>& g, const Work& wk, const IO<T>& io, const QParams<T>& q,
                                            uint32_t pair, const Pose<T>& tf1, T r0, T r1, const V3<T>& guess0,
-                                           bool writer, const PS& ps, bool full_tier = false, bool cc_queue = false) {
+                                           bool writer, const PS& ps, bool full_tier = false, bool cc_queue = false, bool curved = true) {
   PairOut<T> o;
   EpaSeed<T> seed;
-  const bool to_epa = gjk_finish(g, q, tf1, r0, r1, guess0, o, seed, ps);
+  const bool to_epa = gjk_finish<GUARD>(g, q, tf1, r0, r1, guess0, o, seed, ps, curved);
   if (!writer) return;
   if (to_epa) {
     seed.pair = pair;
@@ -271,10 +273,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HFCL_W
     const V3<T> guess0 = initial_guess<T>(io, q, pair);
     Gjk<T, typename decltype(ps)::P> g;
     if constexpr (BVG)
-      gjk_run(g, q.gjk, start_guess(q, a, b, sup.md, guess0), r0 + r1, false, sup, ps);
+      gjk_run<true>(g, q.gjk, start_guess(q, a, b, sup.md, guess0), r0 + r1, false, sup, ps);
     else
-      gjk_run(g, q.gjk, guess0, r0 + r1, false, sup, ps);
-    finish_gjk<T>(g, wk, io, q, pair, tf1, r0, r1, guess0, true, ps, false, sizeof(T) == 8 && curved_pair(a.kind, b.kind));
+      gjk_run<true>(g, q.gjk, guess0, r0 + r1, false, sup, ps);
+    finish_gjk<T, true>(g, wk, io, q, pair, tf1, r0, r1, guess0, true, ps, false, sizeof(T) == 8 && curved_pair(a.kind, b.kind), curved_pair(a.kind, b.kind));
   }
 }
 // Hull of a W-lane group held in LDS instead of registers: element (vertex k, component c) of thread t at
@@ -437,12 +439,13 @@ __device__ __forceinline__ void gjk_cvx_body(const Work& wk, const LibView<T>& l
     Gjk<T, typename decltype(ps)::P> g;
     // normalize_support_direction only when both are ConvexBase (minkowski_difference.cpp:261-266)
     if constexpr (BVG)
-      gjk_run(g, q.gjk, start_guess(q, sup.a, sup.b, sup.md, guess0), r0 + r1, M == 0, sup, ps);
+      gjk_run<M != 0>(g, q.gjk, start_guess(q, sup.a, sup.b, sup.md, guess0), r0 + r1, M == 0, sup, ps);
     else
-      gjk_run(g, q.gjk, guess0, r0 + r1, M == 0, sup, ps);
+      gjk_run<M != 0>(g, q.gjk, guess0, r0 + r1, M == 0, sup, ps);
     // second EPA queue: fp32 -- the convex x convex pairs (their own kernel); fp64 -- the pairs with a curved shape
-    finish_gjk<T>(g, wk, io, q, pair, tf1, r0, r1, guess0, lig == 0, ps, false,
-                  sizeof(T) == 4 ? M == 0 : (M != 0 && curved_pair(sup.a.kind, sup.b.kind)));
+    // (the pairs of two register-resident hulls are not guarded: hfcl_pair.hpp, redo_exempt)
+    finish_gjk<T, M != 0>(g, wk, io, q, pair, tf1, r0, r1, guess0, lig == 0, ps, false,
+                          sizeof(T) == 4 ? M == 0 : (M != 0 && curved_pair(sup.a.kind, sup.b.kind)), M != 0 && curved_pair(sup.a.kind, sup.b.kind));
   }
 }
 
@@ -518,10 +521,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))
     const V3<T> guess0 = initial_guess<T>(io, q, pair);
     Gjk<T, typename decltype(ps)::P> g;
     if constexpr (BVG)
-      gjk_run(g, q.gjk, start_guess(q, sup.a, sup.b, sup.md, guess0), r0 + r1, sup.a.kind == K_CONVEX && sup.b.kind == K_CONVEX, sup, ps);
+      gjk_run<true>(g, q.gjk, start_guess(q, sup.a, sup.b, sup.md, guess0), r0 + r1, sup.a.kind == K_CONVEX && sup.b.kind == K_CONVEX, sup, ps);
     else
-      gjk_run(g, q.gjk, guess0, r0 + r1, sup.a.kind == K_CONVEX && sup.b.kind == K_CONVEX, sup, ps);
-    finish_gjk<T>(g, wk, io, q, pair, tf1, r0, r1, guess0, lig == 0, ps, true);
+      gjk_run<true>(g, q.gjk, guess0, r0 + r1, sup.a.kind == K_CONVEX && sup.b.kind == K_CONVEX, sup, ps);
+    finish_gjk<T, true>(g, wk, io, q, pair, tf1, r0, r1, guess0, lig == 0, ps, true, false, curved_pair(sup.a.kind, sup.b.kind));
   }
 }
 

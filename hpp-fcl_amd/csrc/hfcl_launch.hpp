@@ -82,6 +82,9 @@ template <typename T> void launch_bvh_shape(int grid, hipStream_t st, const Work
 template <typename T> void launch_bvh_shape_distance_fast(int grid, int grid_finish, hipStream_t st, const Work& wk, const LibView<T>& lv, const BvhView<T>& bv, const IO<T>& io, const QParams<T>& q, BvhSpill spill);
 template <typename T> void launch_bvh_shape_fast(int grid, int grid_finish, int coop_grid, hipStream_t st, const Work& wk, const LibView<T>& lv, const BvhView<T>& bv, const IO<T>& io, const QParams<T>& q, const BvhParams& bp, T break_distance2, BvhSplit split, BvhSpill spill, const AsideStream* aside = nullptr);
 template <typename T> void launch_bvh_shape_distance(int grid, hipStream_t st, const Work& wk, const LibView<T>& lv, const BvhView<T>& bv, const IO<T>& io, const QParams<T>& q);
+// hfcl_k_redo.hip: the pairs an fp32 batch marked as inconsistent (IO<float>::redo_list), solved again in fp64 from the fp64 tables and the
+// promoted fp32 poses; the record rounded to the 44-byte form.  The grid strides over the device-side count.
+void launch_redo(int grid, hipStream_t st, const Work& wk, const DShape<double>* shapes64, const double* verts64, const IO<float>& io, const QParams<double>& q);
 template <typename T> void launch_triangle(int grid, hipStream_t st, const Work& wk, const LibView<T>& lv, const IO<T>& io, const QParams<T>& q);
 
 // hfcl_k_patch.hip: contact patches of collide() records (hfcl_contact_patch_batch*).  lists: 2 x n record ids (one-sided,

@@ -66,6 +66,7 @@ struct PairOut {
   V3<T> normal, p1, p2;
   V3<T> cached_guess;
   int gjk_status, epa_status, gjk_iters, epa_iters;
+  int redo = 0;  // fp32: a REDO_* reason (hfcl_gjk.hpp) when the solver's state was inconsistent: the record is to be solved again in fp64
 };
 
 // GJK's final simplex handed to EPA (reference order: oldest vertex first).
@@ -90,7 +91,10 @@ struct W0Regs {
   HFCL_HD V3<T> get(const P& p) const { return p.w0; }
 };
 
-template <typename T, class P, class Sup, class PS>
+// GUARD: gjk_end's consistency guard (fp32 only).  On in the solids' batch kernels, whose marked pairs the batch solves again in fp64
+// (hfcl_k_redo.hip), but for the kernel whose pairs are all hull x hull; off (the default) in the leaves of the mesh, height-field and
+// octree walks, whose records no redo follows.
+template <bool GUARD = false, typename T, class P, class Sup, class PS>
 HFCL_HD void gjk_run(Gjk<T, P>& g, const GjkParams<T>& prm, const V3<T>& guess, T ssr_sum, bool normalize, Sup& sup, const PS& ps) {
   gjk_init(g, prm, guess, ssr_sum, normalize);
   while (!g.done) {
@@ -100,13 +104,13 @@ HFCL_HD void gjk_run(Gjk<T, P>& g, const GjkParams<T>& prm, const V3<T>& guess, 
       V3<T> w0;
       sup(sd, v.w, w0);
       v.p = ps.put(g, w0);
-      gjk_end(g, prm, v);
+      gjk_end<GUARD>(g, prm, v);
     }
   }
 }
-template <typename T, class Sup>
+template <bool GUARD = false, typename T, class Sup>
 HFCL_HD void gjk_run(Gjk<T, PW0<T>>& g, const GjkParams<T>& prm, const V3<T>& guess, T ssr_sum, bool normalize, Sup& sup) {
-  gjk_run(g, prm, guess, ssr_sum, normalize, sup, W0Regs<T>());
+  gjk_run<GUARD>(g, prm, guess, ssr_sum, normalize, sup, W0Regs<T>());
 }
 
 // The pose of shape 1 is needed once, for the record: a caller may pass the pose itself or something that produces it then
@@ -117,9 +121,14 @@ template <typename T, class F>
 HFCL_HD auto pose_now(const F& f) -> decltype(f()) { return f(); }
 
 // Returns true when the pair must go through EPA (seed filled); otherwise `out` is final.
-template <typename T, class P, class PS, class TF>
+// GUARD (fp32, with gjk_run<true>): the witness points are barycentric combinations of the simplex and their difference is the ray in
+// exact arithmetic; on a sliver simplex fp32 gives points whose difference -- the record's normal -- is off the ray.  Marked as well.
+// curved: the pair has a shape with a smooth surface (kind_is_curved).  The two marks that judge the final DIRECTION (REDO_GJK_GAP,
+// REDO_GJK_WITNESS) are kept for these pairs only: between polytopes and sphere-swept polytopes a direction within GJK's own
+// sqrt(tolerance) changes the overlap along it to second order, and their fp32 runs stay inside the envelope as they are.
+template <bool GUARD = false, typename T, class P, class PS, class TF>
 HFCL_HD bool gjk_finish(const Gjk<T, P>& g, const QParams<T>& q, const TF& tf1, T r0, T r1,
-                        const V3<T>& guess0, PairOut<T>& out, EpaSeed<T>& seed, const PS& ps) {
+                        const V3<T>& guess0, PairOut<T>& out, EpaSeed<T>& seed, const PS& ps, bool curved = true) {
   typedef SimplexV<T, P> SV;
   const T nanv = Lim<T>::nan();
   const V3<T> nan3 = mk<T>(nanv, nanv, nanv);
@@ -129,6 +138,7 @@ HFCL_HD bool gjk_finish(const Gjk<T, P>& g, const QParams<T>& q, const TF& tf1, 
   out.epa_status = EPA_DID_NOT_RUN;
   out.gjk_iters = g.iterations;
   out.epa_iters = 0;
+  out.redo = (g.suspect == REDO_GJK_GAP && !curved) ? 0 : g.suspect;
   if (st == GJK_COLLISION && q.compute_penetration) {
     // newest-first registers -> reference order: ref[i] = s[rank-1-i]
     const SV ref0 = svsel(r == 1, g.s0, svsel(r == 2, g.s1, svsel(r == 3, g.s2, g.s3)));
@@ -156,6 +166,7 @@ HFCL_HD bool gjk_finish(const Gjk<T, P>& g, const QParams<T>& q, const TF& tf1, 
   const V3<T> a0 = ps.get(ref0.p), b0 = ps.get(ref1.p), c0 = ps.get(g.s0.p);
   V3<T> p1, p2, n;
   closest_points(r, ref0.w, ref1.w, g.s0.w, a0, b0, c0, a0 - ref0.w, b0 - ref1.w, c0 - g.s0.w, p1, p2);
+  if (GUARD && sizeof(T) == 4 && curved && !out.redo && !(norm((p1 - p2) - g.ray) <= T(GJK_SELF_TOL) * g.rl)) out.redo = REDO_GJK_WITNESS;
   gjk_witness_normal(g.ray, r0, r1, p1, p2, n);
   to_world(pose_now<T>(tf1), g.distance, p1, p2, n);
   out.distance = g.distance;
@@ -165,10 +176,10 @@ HFCL_HD bool gjk_finish(const Gjk<T, P>& g, const QParams<T>& q, const TF& tf1, 
   out.cached_guess = g.ray;
   return false;
 }
-template <typename T>
+template <bool GUARD = false, typename T>
 HFCL_HD bool gjk_finish(const Gjk<T, PW0<T>>& g, const QParams<T>& q, const Pose<T>& tf1, T r0, T r1,
-                        const V3<T>& guess0, PairOut<T>& out, EpaSeed<T>& seed) {
-  return gjk_finish(g, q, tf1, r0, r1, guess0, out, seed, W0Regs<T>());
+                        const V3<T>& guess0, PairOut<T>& out, EpaSeed<T>& seed, bool curved = true) {
+  return gjk_finish<GUARD>(g, q, tf1, r0, r1, guess0, out, seed, W0Regs<T>(), curved);
 }
 
 // EPAExtractWitnessPointsAndNormal / EPAFailedExtractWitnessPointsAndNormal (narrowphase.h:658-723)
@@ -219,6 +230,7 @@ template <typename T>
 HFCL_HD void epa_finish(const EpaResult<T>& res, uint32_t gjk_iters, const Pose<T>& tf1, T r0, T r1, PairOut<T>& out) {
   out.gjk_status = GJK_COLLISION;
   out.gjk_iters = int(gjk_iters);
+  out.redo = res.suspect ? REDO_EPA_BOUND : 0;
   out.epa_status = res.status;
   out.epa_iters = res.iterations;
   if (res.status == EPA_FALLBACK) {  // EPAFailedExtractWitnessPointsAndNormal :713-723
@@ -238,6 +250,36 @@ HFCL_HD void epa_finish(const EpaResult<T>& res, uint32_t gjk_iters, const Pose<
   out.normal = n;
   out.p1 = p1;
   out.p2 = p2;
+}
+
+// fp32: one support evaluation along the final normal of an EPA record against the depth it reports.  n is the record's normal (world
+// frame, from shape 0 to shape 1) and h(n) = h0(n) + h1(-n) the extent of the Minkowski difference along it: the depth of the
+// penetration along n.  EPA's depth is the distance of a face of a polytope inscribed in the difference, so depth <= h(n), with equality
+// up to its tolerance where it converged onto the difference's boundary; the true depth is the minimum of h over all directions.  A
+// record whose depth is off h(n) by more than EPA_DEPTH_TOL (1 + depth) has not found that face (round-off in the face normals of sliver
+// faces; Box x Box: a polytope that lost the origin).  A function of the record, the shapes and the poses alone: every tier that writes
+// the same record marks the same pairs.  A run that ended in a failure status (EPA_FALLBACK, a polytope out of faces or vertices, ...)
+// is marked without a support call.  Pairs of two register-resident hulls are exempt, as they are from GJK's guard (redo_exempt).
+constexpr double EPA_DEPTH_TOL = 2e-5;
+constexpr uint32_t REDO_HULL_MAX = 32;  // (= HULL_MAX, hfcl_dev.hpp: the hulls of the convex x convex bucket)
+template <typename T>
+HFCL_HD bool redo_exempt(const DShape<T>& a, const DShape<T>& b) {
+  return a.kind == K_CONVEX && b.kind == K_CONVEX && a.num_points <= REDO_HULL_MAX && b.num_points <= REDO_HULL_MAX;
+}
+template <typename T, class Sup>
+HFCL_HD int epa_depth_suspect(const PairOut<T>& o, const Pose<T>& tf1, T r0, T r1, Sup& sup, bool curved = true) {
+  if (o.epa_status == EPA_DID_NOT_RUN || o.redo) return o.redo;  // (Epa::loop_suspect, through epa_finish)
+  // (a run that ended at a capacity limit -- iterations, faces, vertices -- reports its last closest face, as the reference does, and
+  // would end there in fp64 as well: judged by its depth like a converged one)
+  const bool limit = o.epa_status == EPA_FAILED || o.epa_status == EPA_OUT_OF_FACES || o.epa_status == EPA_OUT_OF_VERTICES;
+  if (o.epa_status != EPA_VALID && o.epa_status != EPA_ACCURACY_REACHED && !limit) return REDO_EPA_STATUS;
+  if (!(o.distance <= T(0)) || !(o.normal.x == o.normal.x)) return REDO_EPA_STATUS;
+  if (!curved) return 0;  // (the support call: pairs with a smooth shape, as the direction marks of gjk_finish)
+  const V3<T> dir = tmul(tf1.R, o.normal);  // into the frame of shape 0
+  V3<T> w, w0;
+  sup(dir, w, w0);
+  const T h = dot(w, dir) + r0 + r1;
+  return !(habs(h + o.distance) <= T(EPA_DEPTH_TOL) * (T(1) - o.distance)) ? REDO_EPA_DEPTH : 0;
 }
 
 // Record semantics on a fresh result object.  Returns the contact flag; for collide() the
@@ -261,6 +303,40 @@ HFCL_HD bool apply_query_semantics(const QParams<T>& q, PairOut<T>& o, int& num_
 HFCL_HD uint32_t pack_status(int gjk, int epa, bool contact, int gi, int ei) {
   return (uint32_t(gjk) & 7u) | ((uint32_t(epa) & 15u) << 3) | (contact ? 128u : 0u) |
          (uint32_t(gi > 255 ? 255 : gi) << 8) | (uint32_t(ei > 127 ? 127 : ei) << 16);
+}
+
+// The redo of a marked fp32 pair (hfcl_k_redo.hip; tests/hostsim mirrors it): the request in fp64 -- the values the fp32 batch ran with,
+// promoted -- and the fp64 result rounded to the 44-byte record R (hfcl_result_f32).  `contact` is the fp64 run's flag.
+HFCL_HD QParams<double> redo_params(const QParams<float>& q) {
+  QParams<double> r;
+  r.gjk.tolerance = double(q.gjk.tolerance);
+  r.gjk.distance_upper_bound = q.gjk.distance_upper_bound >= Lim<float>::max() ? Lim<double>::max() : double(q.gjk.distance_upper_bound);
+  r.gjk.max_iterations = q.gjk.max_iterations;
+  r.gjk.variant = q.gjk.variant;
+  r.gjk.crit = q.gjk.crit;
+  r.gjk.crit_type = q.gjk.crit_type;
+  r.epa_tolerance = double(q.epa_tolerance);
+  r.epa_max_iterations = q.epa_max_iterations;
+  r.compute_penetration = q.compute_penetration;
+  r.mode = q.mode;
+  r.security_margin = double(q.security_margin);
+  r.collision_distance_threshold = double(q.collision_distance_threshold);
+  r.guess_mode = q.guess_mode;
+  for (int k = 0; k < 3; ++k) r.guess[k] = double(q.guess[k]);
+  return r;
+}
+HFCL_HD float redo_round(double x) {  // (+-DBL_MAX, the "no value" of the fp64 records, is +-FLT_MAX in the fp32 ones)
+  return x >= double(Lim<float>::max()) ? Lim<float>::max() : (x <= -double(Lim<float>::max()) ? -Lim<float>::max() : float(x));
+}
+template <class R>
+HFCL_HD R redo_record(const PairOut<double>& o, bool contact) {
+  R r;
+  r.distance = redo_round(o.distance);
+  r.p1[0] = float(o.p1.x); r.p1[1] = float(o.p1.y); r.p1[2] = float(o.p1.z);
+  r.p2[0] = float(o.p2.x); r.p2[1] = float(o.p2.y); r.p2[2] = float(o.p2.z);
+  r.normal[0] = float(o.normal.x); r.normal[1] = float(o.normal.y); r.normal[2] = float(o.normal.z);
+  r.status = pack_status(o.gjk_status, o.epa_status, contact, o.gjk_iters, o.epa_iters);
+  return r;
 }
 
 // Serial support evaluator over DShape records (any kinds).  Used by the per-lane primitive

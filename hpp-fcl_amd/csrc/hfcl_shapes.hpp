@@ -33,6 +33,8 @@ HFCL_HD bool kind_is_prim(int k) {
   return k == K_BOX || k == K_SPHERE || k == K_CAPSULE || k == K_ELLIPSOID || k == K_CONE || k == K_CYLINDER;
 }
 HFCL_HD bool kind_is_flat(int k) { return k == K_PLANE || k == K_HALFSPACE; }
+// a shape whose support is not a vertex (or a vertex plus a sphere): its GJK simplices and EPA faces are slivers of a smooth surface
+HFCL_HD bool kind_is_curved(int k) { return k == K_ELLIPSOID || k == K_CONE || k == K_CYLINDER; }
 HFCL_HD int pair_class(int k1, int k2) {
   if (k1 == K_BVH && k2 == K_BVH) return CLS_BVH;
   if (kind_is_flat(k1) || kind_is_flat(k2)) {  // every Plane / Halfspace row of the table is a closed form
@@ -524,6 +526,19 @@ HFCL_HD T closed_form_distance(const DShape<T>& s1, const Pose<T>& tf1, const DS
   const T d = box_sphere(s2, tf2, s1, tf1, p2, p1, n);
   n = -n;
   return d;
+}
+
+// fp32: a closed form whose result round-off can move out of the fp32 envelope (the batch solves such a pair again in fp64,
+// hfcl_k_redo.hip).  Capsule x Capsule with nearly parallel axes: denom = a e - b^2 = a e sin^2(angle) is a difference of two products
+// of size a e, each rounded to ~1e-7 a e, so the segment parameter s = num / denom carries a relative error of ~1e-7 / sin^2(angle) and
+// the witness on a segment of length ~1 moves by that much: below 1e-2 the bound passes 1e-5, a tenth of the envelope.
+constexpr double CAPSULE_PARALLEL_SIN2 = 1e-2;
+template <typename T>
+HFCL_HD bool closed_form_suspect(const DShape<T>& s1, const Pose<T>& tf1, const DShape<T>& s2, const Pose<T>& tf2) {
+  if (!(s1.kind == K_CAPSULE && s2.kind == K_CAPSULE)) return false;
+  const V3<T> d1 = (T(2) * s1.p1) * col(tf1.R, 2), d2 = (T(2) * s2.p1) * col(tf2.R, 2);
+  const T a = dot(d1, d1), b = dot(d1, d2), e = dot(d2, d2);
+  return a * e - b * b < T(CAPSULE_PARALLEL_SIN2) * (a * e);
 }
 
 }  // namespace hfcl

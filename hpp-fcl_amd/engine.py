@@ -21,7 +21,7 @@ EXPORTED_SYMBOLS = [
     "hfcl_distance_batch_device", "hfcl_distance_batch_device_f32", "hfcl_collide_batch_device_f32", "hfcl_collide_batch_f32", "hfcl_distance_batch_f32",
     "hfcl_collide_batch_contacts", "hfcl_last_kernel_ms", "hfcl_last_kernel_name", "hfcl_bvh_build",
     "hfcl_world_aabbs", "hfcl_broadphase_self_pairs", "hfcl_broadphase_pairs_between", "hfcl_pairlist_size",
-    "hfcl_pairlist_data", "hfcl_pairlist_free", "hfcl_lib_set_kernel_timing", "hfcl_pair_supported", "hfcl_last_kernel_breakdown", "hfcl_last_bucket_counts", "hfcl_last_ordered_reruns", "hfcl_last_epa_handed_over", "hfcl_lib_set_split", "hfcl_lib_get_split", "hfcl_lib_last_split_parts",
+    "hfcl_pairlist_data", "hfcl_pairlist_free", "hfcl_lib_set_kernel_timing", "hfcl_pair_supported", "hfcl_last_kernel_breakdown", "hfcl_last_bucket_counts", "hfcl_last_ordered_reruns", "hfcl_last_epa_handed_over", "hfcl_last_redo_count", "hfcl_lib_set_split", "hfcl_lib_get_split", "hfcl_lib_last_split_parts",
     "hfcl_collide_batch_qt", "hfcl_distance_batch_qt", "hfcl_lib_set_host_chunk", "hfcl_lib_set_shapes",
     "hfcl_lib_set_convex_neighbors", "hfcl_compact_results_device", "hfcl_compact_results_device_f32",
  "hfcl_shard_range", "hfcl_multi_create", "hfcl_multi_destroy", "hfcl_multi_size", "hfcl_multi_replica",
@@ -140,6 +140,8 @@ def dll():
         d.hfcl_lib_option_key.restype = C.c_char_p
         if hasattr(d, "hfcl_last_epa_handed_over"):
             d.hfcl_last_epa_handed_over.restype = C.c_uint32
+        if hasattr(d, "hfcl_last_redo_count"):
+            d.hfcl_last_redo_count.restype = C.c_uint32
         if hasattr(d, "hfcl_scene_create"):  # (an A/B build of an older source tree behind HFCL_LIB_PATH has no scenes: Library.scene raises there)
             d.hfcl_scene_create.restype = C.c_void_p
             d.hfcl_scene_num_objects.restype = C.c_size_t
@@ -720,7 +722,10 @@ class Library:
         out = (C.c_uint32 * 12)()
         dll().hfcl_last_bucket_counts(self._h, out)
         keys = ["closed", "prim", "cc", "pc", "cp", "bvh", "unsupported", "large", "bvh_shape", "tri", "epa_queue", "epa_overflow"]
-        return dict(zip(keys, [int(v) for v in out]))
+        counts = dict(zip(keys, [int(v) for v in out]))
+        if hasattr(dll(), "hfcl_last_redo_count"):  # fp32 calls: pairs solved again in fp64
+            counts["redo"] = int(dll().hfcl_last_redo_count(self._h))
+        return counts
 
 
     def last_epa_handed_over(self):

@@ -424,6 +424,10 @@ void hfcl_last_bucket_counts(hfcl_lib* lib, uint32_t* out12);
 void hfcl_last_ordered_reruns(hfcl_lib* lib, uint32_t* out4);
 /* fp32 convex x convex polytopes of the last call that outgrew the fast EPA block and were continued by the next tier (waits for the device) */
 uint32_t hfcl_last_epa_handed_over(hfcl_lib* lib);
+/* fp32 entry points: pairs of the last call whose fp32 run was inconsistent -- GJK's ray shorter than its own lower bound, an EPA depth
+ * above a support value the run had seen, a failure status, ... -- and which the batch therefore solved again in fp64 (see "fp32
+ * contract" in INTEGRATION.md).  0 for fp64 calls and for libraries of convex hulls only.  Waits for the device. */
+uint32_t hfcl_last_redo_count(hfcl_lib* lib);
 /* Batches of >= 128k pairs (library without meshes) can run as two halves on two streams -- the caller's and an
  * internal one, forked and joined with events, so the call stays asynchronous and ordered on the caller's stream.
  * Pays when the halves run different kernels side by side (mixed scenes: -6 % per batch) and costs ~3 % when the

@@ -90,6 +90,7 @@ static void one_pair(const DShape<T>& a, const DShape<T>& b, const T* verts, con
     o.epa_status = EPA_DID_NOT_RUN;
     o.gjk_iters = o.epa_iters = 0;
     o.cached_guess = guess0;
+    if (sizeof(T) == 4) o.redo = closed_form_suspect(a, tf1, b, tf2) ? REDO_CLOSED_FORM : 0;
   } else if (cls == CLS_PRIM_GJK || cls == CLS_CONVEX) {
     SerialSupport<T> sup;
     sup.a = a;
@@ -99,9 +100,15 @@ static void one_pair(const DShape<T>& a, const DShape<T>& b, const T* verts, con
     sup.md = make_mdiff(tf1, tf2);
     const T r0 = swept_radius(a), r1 = swept_radius(b);
     Gjk<T, PW0<T>> g;
-    gjk_run(g, q.gjk, start_guess(q, a, b, sup.md, guess0), r0 + r1, a.kind == K_CONVEX && b.kind == K_CONVEX, sup);
+    // as the kernels: the guard and the depth check are compiled out of the ones that only see pairs of register-resident hulls
+    const bool exempt = redo_exempt(a, b);
+    if (exempt)
+      gjk_run<false>(g, q.gjk, start_guess(q, a, b, sup.md, guess0), r0 + r1, a.kind == K_CONVEX && b.kind == K_CONVEX, sup);
+    else
+      gjk_run<true>(g, q.gjk, start_guess(q, a, b, sup.md, guess0), r0 + r1, a.kind == K_CONVEX && b.kind == K_CONVEX, sup);
     EpaSeed<T> seed;
-    if (gjk_finish(g, q, tf1, r0, r1, guess0, o, seed)) {
+    const bool curved = kind_is_curved(a.kind) || kind_is_curved(b.kind);
+    if (exempt ? gjk_finish<false>(g, q, tf1, r0, r1, guess0, o, seed) : gjk_finish<true>(g, q, tf1, r0, r1, guess0, o, seed, curved)) {
       // same two-tier scheme as the kernels: small-capacity block first; on overflow the polytope is saved
       // and continued in the full-capacity block (or redone there when it is not at an iteration boundary)
       static thread_local EpaScratch<T, 20> small;
@@ -114,6 +121,8 @@ static void one_pair(const DShape<T>& a, const DShape<T>& b, const T* verts, con
       } else if (rc == 0) {
         epa_run<T, SerialGroup<1>, EPA_MAX_ITER>(&full, seed, q, tf1, r0, r1, sup, o);
       }
+      // (exempt pairs: never marked, whatever the loop's own verdict -- epa_record_redo, hfcl_k_epa.hip)
+      if (sizeof(T) == 4) o.redo = exempt ? 0 : epa_depth_suspect(o, tf1, r0, r1, sup, curved);
     }
   } else if ((a.kind == K_TRIANGLE || b.kind == K_TRIANGLE) && cls != CLS_BVH) {
     const DShape<T>& other = (a.kind == K_TRIANGLE) ? b : a;
@@ -130,6 +139,9 @@ static void one_pair(const DShape<T>& a, const DShape<T>& b, const T* verts, con
   }
   contact = apply_query_semantics(q, o, nc);
 }
+
+static long g_redo_count = 0, g_redo_reasons[REDO_REASONS] = {};
+static int g_redo_enabled = 1;
 
 extern "C" {
 
@@ -212,6 +224,12 @@ int sim_batch_f32(const hfcl_shape* shapes, size_t n_shapes, const double* verti
     q.security_margin = 0;
     q.gjk.distance_upper_bound = Lim<float>::max();
   }
+  // the redo of the marked pairs (hfcl_k_redo.hip): the fp64 tables of the library, the request in fp64 as redo_params makes it
+  std::vector<DShape<double>> lib64(n_shapes);
+  for (size_t i = 0; i < n_shapes; ++i) lib64[i] = to_dshape<double>(shapes[i], vertices);
+  const QParams<double> q64 = redo_params(q);
+  g_redo_count = 0;
+  for (long& c : g_redo_reasons) c = 0;
   for (size_t i = 0; i < n; ++i) {
     V3<float> g0 = mk<float>(1, 0, 0);
     if (q.guess_mode == HFCL_GUESS_CACHED) g0 = mk<float>(q.guess[0], q.guess[1], q.guess[2]);
@@ -226,6 +244,17 @@ int sim_batch_f32(const hfcl_shape* shapes, size_t n_shapes, const double* verti
       r.status = 0x80000000u;
       continue;
     }
+    if (o.redo) ++g_redo_reasons[o.redo & (REDO_REASONS - 1)];
+    if (o.redo && g_redo_enabled) {
+      ++g_redo_count;
+      V3<double> h0 = mk<double>(1, 0, 0);
+      if (q64.guess_mode == HFCL_GUESS_CACHED) h0 = mk<double>(q64.guess[0], q64.guess[1], q64.guess[2]);
+      PairOut<double> o64;
+      one_pair<double>(lib64[s1[i]], lib64[s2[i]], vertices, pose_from_quat<double>(pose1 + 7 * i), pose_from_quat<double>(pose2 + 7 * i), q64, h0,
+                       o64, contact, nc, skipped);
+      r = redo_record<hfcl_result_f32>(o64, contact);
+      continue;
+    }
     r.distance = o.distance;
     r.p1[0] = o.p1.x; r.p1[1] = o.p1.y; r.p1[2] = o.p1.z;
     r.p2[0] = o.p2.x; r.p2[1] = o.p2.y; r.p2[2] = o.p2.z;
@@ -234,6 +263,11 @@ int sim_batch_f32(const hfcl_shape* shapes, size_t n_shapes, const double* verti
   }
   return 0;
 }
+// records the last sim_batch_f32 marked and solved again in fp64; sim_set_redo(0): marked records are left as the fp32 run wrote them
+// (what the judge of tests/fp32_judge.py is shown to catch)
+long sim_redo_count() { return g_redo_count; }
+const long* sim_redo_reasons() { return g_redo_reasons; }  // marks of the last batch by REDO_* reason (hfcl_gjk.hpp)
+void sim_set_redo(int on) { g_redo_enabled = on; }
 
 // The staged convex x convex fast tier (hfcl_epa.hpp: EpaReady): for every pair whose GJK ends in a seed of rank 4,
 // epa_prepare_tetrahedron + Epa::install must leave the scratch block and the solver fields exactly as Epa::begin does

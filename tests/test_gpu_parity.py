@@ -266,10 +266,11 @@ def test_fp32_device_path(pkg, oracle, torch_cuda, case):
     lib.close()
 
 
-@pytest.mark.parametrize("case,n", [("cfg3_convex_convex", 300001), ("cfg2_box_capsule", 70000), ("cfg5_mixed", 257), ("cfg3_convex_convex", 1)])
+@pytest.mark.parametrize("case,n", [("cfg3_convex_convex", 300001), ("cfg2_box_capsule", 70000), ("cfg5_mixed", 257), ("cfg3_convex_convex", 1), ("all_primitives", 300001)])
 def test_fp32_host_buffers_equal_device_path(pkg, torch_cuda, case, n):
     """hfcl_collide_batch_f32 / hfcl_distance_batch_f32 (host arrays through the chunked pipeline; 300 001 pairs = several chunks of ramping
-    size, 257 and 1 = one chunk) against the device-resident fp32 call on the same batch: every record byte for byte."""
+    size, 257 and 1 = one chunk) against the device-resident fp32 call on the same batch: every record byte for byte.  all_primitives:
+    every pair kind, with the pairs the fp32 kernels mark and the batch solves again in fp64, across chunks and split halves."""
     torch = torch_cuda
     abi, wl = pkg.abi, pkg.workloads
     b = getattr(wl, case)(n=n, seed=11)
