@@ -496,10 +496,12 @@ __device__ __forceinline__ V3<T> scan_support(const T* v, uint32_t n, const V3<T
 // triangulated facet (a subdivided box, the cap centre of a cylinder mesh) has all its neighbours in the facet's plane:
 // along the facet's INWARD normal every neighbour ties and none improves although the facet is the hull's minimum.
 // The reference walks on over equal neighbours until its first strict improvement (loose_check, with a visited set to
-// stay finite, :368-382); here a climb that ends where it started, without any strict improvement and with a neighbour
-// that ties, is that plateau case and is answered by the scan (the only place a tie can hide a better vertex: after a
-// strict improvement a plateau reached is a maximum).  Where several vertices tie at the maximum the result may be
-// another of them than the scan's / the reference's.
+// stay finite, :368-382); here a climb that ends with a neighbour that ties is answered by the scan.  Before any strict
+// improvement that is the plateau case (the only place a tie can hide a better vertex); after one the plateau reached is
+// a maximum, but the scan reports the FIRST index of it, the climb would report whichever vertex it arrived at, and GJK's
+// path -- its iteration counts, the last bits of its record -- follows the vertex: GJK's last directions are normal to a
+// facet of the difference, so ties are what it ends on (2 of 1025 records of 33 - 256-vertex hulls differed between the
+// forms; tests/test_options_gpu.py holds option climb_min by bytes).
 // A hop costs O(degree) instead of O(num_points): measured crossover against scan_support in profiles/r02_p.
 template <typename T, int W>
 __device__ __forceinline__ V3<T> climb_support(const T* v, uint32_t n, const HullGraph<T>& g, const V3<T>& dir, int lig, int& hint) {
@@ -532,7 +534,6 @@ __device__ __forceinline__ V3<T> climb_support(const T* v, uint32_t n, const Hul
     cur = uint32_t(hint);
     best = v[3 * size_t(cur)] * dir.x + v[3 * size_t(cur) + 1] * dir.y + v[3 * size_t(cur) + 2] * dir.z;
   }
-  bool improved = false;
   for (;;) {
     const uint32_t b = g.off[cur], e = g.off[cur + 1];
     T mb = best;
@@ -559,22 +560,22 @@ __device__ __forceinline__ V3<T> climb_support(const T* v, uint32_t n, const Hul
       mpos = take ? ok : mpos;
     });
     if (mi == 0xFFFFFFFFu) {  // no neighbour is strictly better (uniform over the group)
-      if (!improved) {        // ... and none ever was: a neighbour that ties may hide a better vertex behind the plateau
-        uint32_t any = tie ? 1u : 0u;
-        butterfly_stages<W>([&](auto stage) {
-          constexpr int M = decltype(stage)::value;
-          any |= group_exchange<W, M>(any);
-        });
-        if (any) {
-          uint32_t si = 0;
-          const V3<T> r = scan_support<T, W>(v, n, dir, lig, &si);
-          hint = int(si);
-          return r;
-        }
+      // ... but one ties: before any strict improvement it may hide a better vertex behind the plateau; after one the plateau is the
+      // maximum, but which of its vertices the scan reports -- the first index -- is not known here, and GJK's path (its iteration
+      // counts, the last bits of its record) hangs on the vertex.  Either way the scan answers: option climb_min changes no record
+      uint32_t any = tie ? 1u : 0u;
+      butterfly_stages<W>([&](auto stage) {
+        constexpr int M = decltype(stage)::value;
+        any |= group_exchange<W, M>(any);
+      });
+      if (any) {
+        uint32_t si = 0;
+        const V3<T> r = scan_support<T, W>(v, n, dir, lig, &si);
+        hint = int(si);
+        return r;
       }
       break;
     }
-    improved = true;
     cur = mi;
     best = mb;
   }

@@ -240,8 +240,12 @@ static bool upload_shapes(hfcl_lib* lib, const hfcl_shape* shapes, size_t n_shap
 
 // ---------------------------------------------------------------------------------------
 // Tuning options (include/hppfcl_amd.h: hfcl_lib_set_option).  One table: the keys, and what each sets.  Every option is a field of
-// the library read when a batch is set up, so an option holds from the next call on; none changes a record (tests/ hold the forms
-// against each other), they choose between forms of the same computation and size their budgets.
+// the library read when a batch is set up, so an option holds from the next call on; none changes a record (tests/test_options_gpu.py
+// holds every value against the default form byte for byte; a new key needs a row in tests/options_table.py), they choose between forms
+// of the same computation and size their budgets.  The one exception -- the last bits of `distance` in fp64 mesh x mesh collide() under
+// bvh_coop = 0 / bvh_walk_rounds = 0 / bvh_force_wide = 1, every decision the same bytes -- and the triangle named inside a 0-ulp tie
+// class of distance() under pool_rerun = 0, bvhd_pool = 0, shape_dist_pool = 0, bvh_shape_lane = 0 are in the header and in
+// INTEGRATION.md section 4.  A value outside an option's range is refused, never clamped (apply_option).
 // ---------------------------------------------------------------------------------------
 static const char* const* option_keys() {
   static const char* const keys[] = {
@@ -254,129 +258,187 @@ static const char* const* option_keys() {
       "pipe_trace", "scene_chunk", "scene_cull_chunk", "scene_pairs_small_max", "scene_pairs_sorted", "scene_pairs_sorted_axis", "scene_env_span", "scene_nearest_env_prune", "epa_pool_share", "epa_pool_min_refills", "hfield_chunk", "hfield_items", "octree_chunk", "octree_items", nullptr};
   return keys;
 }
-// "4,16,16": up to `cap` comma-separated unsigned values into out[first...]; returns how many were read
-static int parse_list(const char* v, uint32_t* out, int first, int cap, uint32_t lo, uint32_t hi) {
-  int k = first;
-  for (const char* p = v; *p && k < cap; ++k) {
-    const long long x = atoll(p);
-    out[k] = uint32_t(std::min<long long>(std::max<long long>(x, lo), hi));
-    while (*p && *p != ',') ++p;
-    if (*p == ',') ++p;
+// One unsigned decimal number, the whole string: digits only -- no sign, no blank, nothing behind it -- and lo <= value <= hi.
+static bool parse_uint(const char* p, const char* end, unsigned long long lo, unsigned long long hi, unsigned long long* out) {
+  if (p == end || end - p > 20) return false;
+  unsigned long long x = 0;
+  for (; p != end; ++p) {
+    if (*p < '0' || *p > '9') return false;
+    const unsigned long long d = (unsigned long long)(*p - '0');
+    if (x > (~0ull - d) / 10) return false;  // (past 2^64 - 1)
+    x = x * 10 + d;
   }
-  return k - first;
+  if (x < lo || x > hi) return false;
+  *out = x;
+  return true;
 }
+// "4,16,16": one to `cap` comma-separated unsigned values, each in lo .. hi, into out[0 ...]; returns how many there are, 0 when any
+// element is not a number in range, when one is empty or when there are too many (out is then not to be used)
+static int parse_list(const char* v, uint32_t* out, int cap, uint32_t lo, uint32_t hi) {
+  int k = 0;
+  for (const char* p = v;; ++k) {
+    const char* e = p;
+    while (*e && *e != ',') ++e;
+    unsigned long long x;
+    if (k >= cap || !parse_uint(p, e, lo, hi, &x)) return 0;
+    out[k] = uint32_t(x);
+    if (!*e) return k + 1;
+    p = e + 1;
+  }
+}
+// The value is parsed and checked against the option's range first; the library is written only when all of it is valid, so a refused
+// call changes nothing (include/hppfcl_amd.h).  No value is clamped: what is outside an option's range is refused.
 static int apply_option(hfcl_lib* lib, const std::string& key, const char* v) {
-  const long long i = atoll(v);
-  const bool on = i != 0;
-  auto u32 = [&](long long lo) { return uint32_t(std::min<long long>(std::max(i, lo), 0xFFFFFFFFll)); };
-  if (key == "closed_staged") lib->opt.closed_staged = on;
-  else if (key == "split") lib->opt.split = i >= 2 ? 2 : (i == 1 ? 1 : 0);
-  else if (key == "epa_cc_staged") lib->opt.epa_cc_staged = on;
-  else if (key == "epa_records_aside") lib->opt.records_aside = on;
-  else if (key == "epa_general_staged") {
-    if (on && !HFCL_KEEP_AB_FORMS) return HFCL_ERR_INVALID_ARGUMENT;  // (not in the product build: hfcl_dev.hpp)
-    lib->opt.epa_general_staged = on;
+  constexpr unsigned long long U32 = 0xFFFFFFFFull, SIZE = 1ull << 40;
+  hfcl_options& o = lib->opt;
+  unsigned long long x = 0;
+  bool on = false;
+  auto num = [&](unsigned long long lo, unsigned long long hi) { return parse_uint(v, v + strlen(v), lo, hi, &x); };
+  auto flag = [&]() {
+    const bool ok = num(0, 1);
+    on = x != 0;
+    return ok;
+  };
+  auto set_flag = [&](bool& field) {
+    if (!flag()) return int(HFCL_ERR_INVALID_ARGUMENT);
+    field = on;
+    return int(HFCL_OK);
+  };
+  auto set_u32 = [&](uint32_t& field, unsigned long long lo, unsigned long long hi) {
+    if (!num(lo, hi)) return int(HFCL_ERR_INVALID_ARGUMENT);
+    field = uint32_t(x);
+    return int(HFCL_OK);
+  };
+  auto set_size = [&](size_t& field, unsigned long long hi) {
+    if (!num(0, hi)) return int(HFCL_ERR_INVALID_ARGUMENT);
+    field = size_t(x);
+    return int(HFCL_OK);
+  };
+  if (key == "closed_staged") return set_flag(o.closed_staged);
+  if (key == "split") {
+    if (!num(0, 2)) return HFCL_ERR_INVALID_ARGUMENT;
+    o.split = int(x);
+    return HFCL_OK;
   }
-  else if (key == "shape_finish_tiers") lib->opt.shape_finish_tiers = on;
-  else if (key == "shape_finish_aside") lib->opt.shape_finish_aside = on;
-  else if (key == "epa_general_staged_min") lib->opt.epa_general_staged_min = size_t(std::max(0ll, i));
-  else if (key == "epa64_two_streams") lib->opt.epa64_two_streams = on;
-  else if (key == "epa_cc_staged_min") lib->opt.epa_cc_staged_min = size_t(std::max(0ll, i));
-  else if (key == "pipe_chunk") lib->opt.pipe_chunk = strtoull(v, nullptr, 10);
-  else if (key == "bvh_filter") {
-    if (on && !HFCL_KEEP_AB_FORMS) return HFCL_ERR_INVALID_ARGUMENT;
-    lib->opt.bvh_filter = on;
+  if (key == "epa_cc_staged") return set_flag(o.epa_cc_staged);
+  if (key == "epa_records_aside") return set_flag(o.records_aside);
+  if (key == "epa_general_staged") {
+    if (!flag() || (on && !HFCL_KEEP_AB_FORMS)) return HFCL_ERR_INVALID_ARGUMENT;  // (not in the product build: hfcl_dev.hpp)
+    o.epa_general_staged = on;
+    return HFCL_OK;
   }
-  else if (key == "bvh_shape_lane") lib->opt.bvh_shape_lane = on;
-  else if (key == "shape_coop") lib->opt.shape_coop = on;
-  else if (key == "bvh_cut_ticks") lib->opt.bvh_cut_ticks = uint32_t(strtoul(v, nullptr, 10));
-  else if (key == "shape_cut_ticks") lib->opt.shape_cut_ticks = uint32_t(strtoul(v, nullptr, 10));
-  else if (key == "bvh_coop") lib->opt.bvh_coop = on;
-  else if (key == "bvhd_budget") lib->opt.bvhd_budget = u32(0);
-  else if (key == "bvhd_pool") lib->opt.bvhd_pool = u32(0);
-  else if (key == "shape_dist_pool") lib->opt.shape_dist_pool = u32(0);
-  else if (key == "pool_rerun") lib->opt.pool_rerun = u32(0);
-  else if (key == "bvh_walk_early_coop") lib->opt.walk_early_coop = on;
-  else if (key == "bvh_walk_order") lib->opt.walk_order = on;
-  else if (key == "mesh_beside") lib->opt.mesh_beside = u32(0);
-  else if (key == "shape_walk") lib->opt.shape_walk = on;
-  else if (key == "mesh_prio") lib->opt.mesh_prio = on;
-  else if (key == "shape_walk_sort") lib->opt.shape_walk_sort = on;
-  else if (key == "shape_walk_budget") lib->opt.shape_walk_budget = u32(0);
-  else if (key == "shape_walk_min") lib->opt.shape_walk_min = u32(0);
-  else if (key == "gjk_beside_max") lib->opt.gjk_beside_max = u32(0);
-  else if (key == "epa_direct_max") lib->opt.epa_direct_max = u32(0);
-  else if (key == "epa_pool_share") {
-    if (i < 0 || i > 50) return HFCL_ERR_INVALID_ARGUMENT;
-    lib->opt.epa_pool_share = uint32_t(i);
+  if (key == "shape_finish_tiers") return set_flag(o.shape_finish_tiers);
+  if (key == "shape_finish_aside") return set_flag(o.shape_finish_aside);
+  if (key == "epa_general_staged_min") return set_size(o.epa_general_staged_min, SIZE);
+  if (key == "epa64_two_streams") return set_flag(o.epa64_two_streams);
+  if (key == "epa_cc_staged_min") return set_size(o.epa_cc_staged_min, SIZE);
+  if (key == "pipe_chunk") return set_size(o.pipe_chunk, SIZE);
+  if (key == "bvh_filter") {
+    if (!flag() || (on && !HFCL_KEEP_AB_FORMS)) return HFCL_ERR_INVALID_ARGUMENT;
+    o.bvh_filter = on;
+    return HFCL_OK;
   }
-  else if (key == "epa_pool_min_refills") lib->opt.epa_pool_min_refills = u32(0);
-  else if (key == "bvh_walk_rounds") { lib->opt.walk_rounds = uint32_t(std::min<long long>(std::max(0ll, i), WALK_ROUNDS)); lib->opt.walk_auto = false; }
-  else if (key == "bvh_walk_k") { parse_list(v, lib->opt.walk_k, 0, WALK_ROUNDS, 1u, uint32_t(WALK_K)); lib->opt.walk_auto = false; }  // "6,16": per round
-  else if (key == "bvh_walk_budget") parse_list(v, lib->opt.walk_budget, 1, WALK_ROUNDS, 0u, 0xFFFFFFFFu);  // rounds 1 ...: box tests (round 0 takes bvh_budget0_coop's)
-  else if (key == "shape_dist_leaf_min") lib->opt.shape_dist_leaf_min = u32(1);
-  else if (key == "shape_dist_starve") lib->opt.shape_dist_starve = u32(1);  // (>= 1: a window of triangles alone must always run)
-  else if (key == "bvhd_leaf_min") lib->opt.bvhd_pool_leaf_min = u32(1);
-  else if (key == "bvhd_starve") lib->opt.bvhd_pool_starve = u32(1);
-  else if (key == "bvhd_part_min") lib->opt.bvhd_pool_part_min = u32(0);
-  else if (key == "shape_dist_budget") lib->opt.shape_dist_budget = u32(0);
-  else if (key == "bvh_budget0_coop") lib->opt.bvh_budget0_coop = u32(1);
-  else if (key == "shape_budget0") lib->opt.shape_budget0 = lib->opt.shape_budget0_coop = uint32_t(i);
-  else if (key == "shape_budget") lib->opt.shape_budget = uint32_t(i);
-  else if (key == "shape_leaf_cost") lib->opt.shape_leaf_cost = u32(1);
-  else if (key == "shape_levels") lib->opt.shape_levels = uint32_t(std::min<long long>(std::max(1ll, i), BVH_MAX_LEVELS));
-  else if (key == "climb_min") lib->opt.climb_min = u32(0);
-  else if (key == "bvh_budget") { lib->opt.bvh_budget = lib->opt.bvh_budget0 = u32(0); lib->opt.bvh_auto = false; }
-  else if (key == "bvh_budget0") { lib->opt.bvh_budget0 = u32(0); lib->opt.bvh_auto = false; }
-  else if (key == "bvh_levels") { lib->opt.bvh_levels = uint32_t(std::min<long long>(BVH_MAX_LEVELS, std::max(1ll, i))); lib->opt.bvh_auto = false; }
-  else if (key == "cvx_w") {
-    if (i == 0 || i == 2 || i == 4 || i == 8 || i == 16 || i == 32 || i == 64) lib->opt.cvx_w = int(i);
-    else return HFCL_ERR_INVALID_ARGUMENT;
+  if (key == "bvh_shape_lane") return set_flag(o.bvh_shape_lane);
+  if (key == "shape_coop") return set_flag(o.shape_coop);
+  if (key == "bvh_cut_ticks") return set_u32(o.bvh_cut_ticks, 0, U32);
+  if (key == "shape_cut_ticks") return set_u32(o.shape_cut_ticks, 0, U32);
+  if (key == "bvh_coop") return set_flag(o.bvh_coop);
+  if (key == "bvhd_budget") return set_u32(o.bvhd_budget, 0, U32);
+  if (key == "bvhd_pool") return set_u32(o.bvhd_pool, 0, 1);
+  if (key == "shape_dist_pool") return set_u32(o.shape_dist_pool, 0, 1);
+  if (key == "pool_rerun") return set_u32(o.pool_rerun, 0, 2);
+  if (key == "bvh_walk_early_coop") return set_flag(o.walk_early_coop);
+  if (key == "bvh_walk_order") return set_flag(o.walk_order);
+  if (key == "mesh_beside") {
+    if (!num(0, 4) || x == 3) return HFCL_ERR_INVALID_ARGUMENT;
+    o.mesh_beside = uint32_t(x);
+    return HFCL_OK;
   }
-  else if (key == "epa_resume_slots") lib->opt.epa_resume_slots = size_t(std::max(0ll, i));
-  else if (key == "bvh_task_slots") lib->opt.bvh_task_slots = size_t(std::max(0ll, i));
-  else if (key == "bvh_force_wide") lib->opt.bvh_force_wide = on;
-  else if (key == "pipe_trace") lib->opt.pipe_trace = on;
-  else if (key == "scene_chunk") {
-    if (i < 0 || i > 0xFFFFFFF0ll) return HFCL_ERR_INVALID_ARGUMENT;
-    lib->opt.scene_chunk = size_t(i);
+  if (key == "shape_walk") return set_flag(o.shape_walk);
+  if (key == "mesh_prio") return set_flag(o.mesh_prio);
+  if (key == "shape_walk_sort") return set_flag(o.shape_walk_sort);
+  if (key == "shape_walk_budget") return set_u32(o.shape_walk_budget, 0, U32);
+  if (key == "shape_walk_min") return set_u32(o.shape_walk_min, 0, U32);
+  if (key == "gjk_beside_max") return set_u32(o.gjk_beside_max, 0, U32);
+  if (key == "epa_direct_max") return set_u32(o.epa_direct_max, 0, U32);
+  if (key == "epa_pool_share") return set_u32(o.epa_pool_share, 0, 50);
+  if (key == "epa_pool_min_refills") return set_u32(o.epa_pool_min_refills, 0, U32);
+  if (key == "bvh_walk_rounds") {
+    if (!num(0, WALK_ROUNDS)) return HFCL_ERR_INVALID_ARGUMENT;
+    o.walk_rounds = uint32_t(x);
+    o.walk_auto = false;
+    return HFCL_OK;
   }
-  else if (key == "scene_cull_chunk") {
-    if (i < 0 || i > (1ll << 31)) return HFCL_ERR_INVALID_ARGUMENT;  // (one workgroup scans a chunk's counts: 2^23 of them at most)
-    lib->opt.scene_cull_chunk = size_t(i);
+  if (key == "bvh_walk_k") {  // "6,16": per round
+    uint32_t k[WALK_ROUNDS];
+    const int n = parse_list(v, k, WALK_ROUNDS, 1u, uint32_t(WALK_K));
+    if (!n) return HFCL_ERR_INVALID_ARGUMENT;
+    std::copy(k, k + n, o.walk_k);
+    o.walk_auto = false;
+    return HFCL_OK;
   }
-  else if (key == "scene_pairs_small_max") {
-    if (i < 0 || i > (long long)PAIRS_SMALL_MAX) return HFCL_ERR_INVALID_ARGUMENT;  // (a lane per column)
-    lib->opt.scene_pairs_small_max = uint32_t(i);
+  if (key == "bvh_walk_budget") {  // rounds 1 ...: box tests (round 0 takes bvh_budget0_coop's)
+    uint32_t b[WALK_ROUNDS - 1];
+    const int n = parse_list(v, b, WALK_ROUNDS - 1, 0u, 0xFFFFFFFFu);
+    if (!n) return HFCL_ERR_INVALID_ARGUMENT;
+    std::copy(b, b + n, o.walk_budget + 1);
+    return HFCL_OK;
   }
-  else if (key == "scene_pairs_sorted") lib->opt.scene_pairs_sorted = on;
-  else if (key == "scene_pairs_sorted_axis") {
-    if (i < 0 || i > 3) return HFCL_ERR_INVALID_ARGUMENT;  // (3: automatic, per configuration)
-    lib->opt.scene_pairs_sorted_axis = uint32_t(i);
+  if (key == "shape_dist_leaf_min") return set_u32(o.shape_dist_leaf_min, 1, U32);
+  if (key == "shape_dist_starve") return set_u32(o.shape_dist_starve, 1, U32);  // (>= 1: a window of triangles alone must always run)
+  if (key == "bvhd_leaf_min") return set_u32(o.bvhd_pool_leaf_min, 1, U32);
+  if (key == "bvhd_starve") return set_u32(o.bvhd_pool_starve, 1, U32);
+  if (key == "bvhd_part_min") return set_u32(o.bvhd_pool_part_min, 0, U32);
+  if (key == "shape_dist_budget") return set_u32(o.shape_dist_budget, 0, U32);
+  if (key == "bvh_budget0_coop") return set_u32(o.bvh_budget0_coop, 1, U32);
+  if (key == "shape_budget0") {
+    if (!num(0, U32)) return HFCL_ERR_INVALID_ARGUMENT;
+    o.shape_budget0 = o.shape_budget0_coop = uint32_t(x);
+    return HFCL_OK;
   }
-  else if (key == "scene_env_span") {
-    if (i < 0 || i > 0xFFFFFFFFll) return HFCL_ERR_INVALID_ARGUMENT;
-    lib->opt.scene_env_span = uint32_t(i);
+  if (key == "shape_budget") return set_u32(o.shape_budget, 0, U32);
+  if (key == "shape_leaf_cost") return set_u32(o.shape_leaf_cost, 1, U32);
+  if (key == "shape_levels") return set_u32(o.shape_levels, 1, BVH_MAX_LEVELS);
+  if (key == "climb_min") return set_u32(o.climb_min, 0, U32);
+  if (key == "bvh_budget") {
+    if (!num(0, U32)) return HFCL_ERR_INVALID_ARGUMENT;
+    o.bvh_budget = o.bvh_budget0 = uint32_t(x);
+    o.bvh_auto = false;
+    return HFCL_OK;
   }
-  else if (key == "scene_nearest_env_prune") lib->opt.scene_nearest_env_prune = on;
-  else if (key == "hfield_chunk") {
-    if (i < 0 || i > 0xFFFFFFF0ll) return HFCL_ERR_INVALID_ARGUMENT;
-    lib->opt.hfield_chunk = size_t(i);
+  if (key == "bvh_budget0") {
+    if (!num(0, U32)) return HFCL_ERR_INVALID_ARGUMENT;
+    o.bvh_budget0 = uint32_t(x);
+    o.bvh_auto = false;
+    return HFCL_OK;
   }
-  else if (key == "hfield_items") {
-    if (i < 0 || i > (1ll << 26)) return HFCL_ERR_INVALID_ARGUMENT;  // (the item workspace of one query's limit)
-    lib->opt.hfield_items = size_t(i);
+  if (key == "bvh_levels") {
+    if (!num(1, BVH_MAX_LEVELS)) return HFCL_ERR_INVALID_ARGUMENT;
+    o.bvh_levels = uint32_t(x);
+    o.bvh_auto = false;
+    return HFCL_OK;
   }
-  else if (key == "octree_chunk") {
-    if (i < 0 || i > 0xFFFFFFF0ll) return HFCL_ERR_INVALID_ARGUMENT;
-    lib->opt.octree_chunk = size_t(i);
+  if (key == "cvx_w") {
+    if (!num(0, 64) || (x != 0 && (x < 2 || (x & (x - 1)) != 0))) return HFCL_ERR_INVALID_ARGUMENT;  // 0, 2, 4, 8, 16, 32, 64
+    o.cvx_w = int(x);
+    return HFCL_OK;
   }
-  else if (key == "octree_items") {
-    if (i < 0 || i > (1ll << 26)) return HFCL_ERR_INVALID_ARGUMENT;  // (the item workspace of one query's limit)
-    lib->opt.octree_items = size_t(i);
-  }
-  else return HFCL_ERR_INVALID_ARGUMENT;
-  return HFCL_OK;
+  if (key == "epa_resume_slots") return set_size(o.epa_resume_slots, SIZE);
+  if (key == "bvh_task_slots") return set_size(o.bvh_task_slots, 1ull << 16);  // (the table is slots x queries entries)
+  if (key == "bvh_force_wide") return set_flag(o.bvh_force_wide);
+  if (key == "pipe_trace") return set_flag(o.pipe_trace);
+  if (key == "scene_chunk") return set_size(o.scene_chunk, 0xFFFFFFF0ull);
+  if (key == "scene_cull_chunk") return set_size(o.scene_cull_chunk, 1ull << 31);  // (one workgroup scans a chunk's counts: 2^23 of them at most)
+  if (key == "scene_pairs_small_max") return set_u32(o.scene_pairs_small_max, 0, PAIRS_SMALL_MAX);  // (a lane per column)
+  if (key == "scene_pairs_sorted") return set_flag(o.scene_pairs_sorted);
+  if (key == "scene_pairs_sorted_axis") return set_u32(o.scene_pairs_sorted_axis, 0, 3);  // (3: automatic, per configuration)
+  if (key == "scene_env_span") return set_u32(o.scene_env_span, 0, U32);
+  if (key == "scene_nearest_env_prune") return set_flag(o.scene_nearest_env_prune);
+  if (key == "hfield_chunk") return set_size(o.hfield_chunk, 0xFFFFFFF0ull);
+  if (key == "hfield_items") return set_size(o.hfield_items, 1ull << 26);  // (the item workspace of one query's limit)
+  if (key == "octree_chunk") return set_size(o.octree_chunk, 0xFFFFFFF0ull);
+  if (key == "octree_items") return set_size(o.octree_items, 1ull << 26);  // (the item workspace of one query's limit)
+  return HFCL_ERR_INVALID_ARGUMENT;
 }
 
 hfcl_lib* hfcl_lib_create(const hfcl_shape* shapes, size_t n_shapes, const double* vertices, size_t n_vertices,
@@ -407,7 +469,8 @@ hfcl_lib* hfcl_lib_create(const hfcl_shape* shapes, size_t n_shapes, const doubl
   for (const char* const* k = option_keys(); *k; ++k) {
     std::string name = "HFCL_";
     for (const char* c = *k; *c; ++c) name.push_back(char(toupper(static_cast<unsigned char>(*c))));
-    if (const char* v = getenv(name.c_str())) apply_option(lib, *k, v);
+    if (const char* v = getenv(name.c_str()))
+      if (apply_option(lib, *k, v) != HFCL_OK) fprintf(stderr, "[hfcl] %s=%s in the environment is not a value of option %s: ignored\n", name.c_str(), v, *k);
   }
   return lib;
 }
@@ -1051,6 +1114,7 @@ static int host_batch_small(hfcl_lib* lib, const uint32_t* s1, const uint32_t* s
     d_tf2 = reinterpret_cast<const double*>(d + o_tf2);
   }
   HostBatchScope scope(lib);
+  if (lib->note_forms) lib->host_notes = "host_packed=1;";
   memset(lib->h_pack_counts, 0, 2 * N_COUNTERS * sizeof(uint32_t));
   lib->counts_dst = lib->h_pack_counts;
   if (lib->helper) lib->helper->counts_dst = lib->h_pack_counts + N_COUNTERS;  // (a batch this small is never split)
@@ -1109,6 +1173,7 @@ static int host_batch(hfcl_lib* lib, const uint32_t* s1, const uint32_t* s2, con
   size_t max_chunk = 0;
   for (size_t k = 0; k + 1 < bounds.size(); ++k) max_chunk = std::max(max_chunk, bounds[k + 1] - bounds[k]);
   const size_t n_chunks = bounds.size() - 1;
+  if (lib->note_forms) lib->host_notes = "host_chunks=" + std::to_string(n_chunks) + ";host_max_chunk=" + std::to_string(max_chunk) + ";host_trace=" + std::to_string(int(lib->opt.pipe_trace)) + ";";
   int rc = ensure_staging(lib, max_chunk, gin != nullptr, gout != nullptr, compact);
   if (rc) return rc;
   SmallBatchBuckets batch_buckets(lib, s1, s2, n, dreq != nullptr);
@@ -1475,6 +1540,23 @@ extern "C" int hfcl_debug_walk_counters(hfcl_lib* lib, int solid, uint32_t* out3
 // What a library, a scene or a multi-device set took is given back when it is destroyed: tests/test_gpu_ownership.py)
 extern "C" void hfcl_debug_live_handles(int64_t* out4) {
   for (int k = 0; k < 4; ++k) out4[k] = g_hfcl_live[k].load(std::memory_order_relaxed);
+}
+// (diagnostic, not part of the ABI: what the host entry point and the dispatcher chose for the last call -- "name=value;" per decision, note_form;
+// a split batch: the first half's.  Empty unless hfcl_debug_note_forms(lib, 1) was called before the batch.  Valid until the library's next call: tests/test_options_gpu.py takes the forms' witnesses from it)
+extern "C" void hfcl_debug_note_forms(hfcl_lib* lib, int on) {
+  if (lib) lib->note_forms = on != 0;
+  if (lib && lib->helper) lib->helper->note_forms = on != 0;
+}
+extern "C" const char* hfcl_debug_last_forms(hfcl_lib* lib) {
+  if (!lib) return "";
+  lib->notes_out = lib->host_notes + lib->form_notes;
+  return lib->notes_out.c_str();
+}
+// (diagnostic, not part of the ABI: the bytes of the library's options block, hfcl_options, so that a test can show that a refused
+// hfcl_lib_set_option left every option as it was; returns the block's size, copies min(cap, size) bytes: tests/test_options_gpu.py)
+extern "C" size_t hfcl_debug_options_block(const hfcl_lib* lib, void* out, size_t cap) {
+  if (lib && out) memcpy(out, &lib->opt, std::min(cap, sizeof(hfcl_options)));
+  return sizeof(hfcl_options);
 }
 // pairs per chunk of the host-buffer pipeline (0 = automatic: n/8 clamped to 32k .. 256k)
 void hfcl_lib_set_host_chunk(hfcl_lib* lib, size_t pairs) {

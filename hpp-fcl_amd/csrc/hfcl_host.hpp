@@ -417,6 +417,10 @@ struct hfcl_lib {
   bool has_curved = true;            // some shape is an Ellipsoid / Cone / Cylinder: the curved class of the fp64 EPA tiers can occur
   int n_cus = 256;
   std::string dominant;
+  // (diagnostic, off unless hfcl_debug_note_forms switched it on) what the host entry point chose for the last host call (its chunks) and
+  // what the dispatcher chose for the last batch, one "name=value;" per decision (note_form; hfcl_debug_last_forms)
+  bool note_forms = false;
+  std::string form_notes, host_notes, notes_out;
   // bucket populations of the last call; PINNED host memory so that the device-to-host copy at the end of a batch is
   // asynchronous (a pageable destination makes hipMemcpyAsync block the host until the whole batch has run)
   PinnedBuf<uint32_t> h_counts;
@@ -447,6 +451,15 @@ struct hfcl_lib {
   BvhParams bvh_params = {1u, nullptr, 0u, nullptr};
   double break_distance = 1e-3;
 };
+
+// (diagnostic) one decision of the dispatcher about the batch being set up: the form it takes, a budget or a table size as the kernels get it
+inline void note_form(hfcl_lib* lib, const char* name, unsigned long long value) {
+  if (!lib->note_forms) return;
+  lib->form_notes += name;
+  lib->form_notes += '=';
+  lib->form_notes += std::to_string(value);
+  lib->form_notes += ';';
+}
 
 // bucket population i of a batch's counter block: a bucket = its bottom + its curved part; the EPA queue = the general + the second queue
 inline uint32_t one_count(const uint32_t* c, int i) {

@@ -169,6 +169,7 @@ template <typename T, int M>
 static void launch_cvx_m(hfcl_lib* lib, const Work& wk, const LibView<T>& lv, const IO<T>& io, const QParams<T>& q,
                          hipStream_t st, size_t n) {
   const int w = lib->opt.cvx_w ? lib->opt.cvx_w : auto_cvx_w<T, M>();
+  note_form(lib, M == 0 ? "cvx_w_cc" : (M == 1 ? "cvx_w_pc" : "cvx_w_cp"), unsigned(w));
   const size_t nt = size_t(gjk_cvx_threads<T>(w, M));
   size_t b = (n + nt / w - 1) / (nt / w);
   if (b < 1) b = 1;
@@ -252,6 +253,7 @@ static void make_views(Batch<T>& b, const uint32_t* d_s1, const uint32_t* d_s2) 
   lv.graph_off = lib->d_graph_off;
   lv.graph_ent = F64 ? (const NbrEntry<T>*)lib->d_graph_ent64 : (const NbrEntry<T>*)lib->d_graph_ent32;
   lv.climb_min = lib->opt.climb_min;
+  if (b.may(B_LARGE)) note_form(lib, "climb_min", lv.climb_min);
 }
 template <typename T>
 static BvhView<T> make_bvh_view(const hfcl_lib* lib) {
@@ -290,6 +292,8 @@ static int launch_solids(Batch<T>& b, hipStream_t caller) {
   for (int k : {int(B_PRIM), int(B_CC), int(B_PC), int(B_CP), int(B_LARGE), int(B_TRI)}) kernels += b.may(k) ? 1 : 0;
   bool fan = lib->opt.gjk_beside_max && n <= lib->opt.gjk_beside_max && lib->h_meshes.empty() && kernels >= 3;
   if (fan && ensure_gjk_streams(lib) != HFCL_OK) fan = false;
+  note_form(lib, "gjk_fan", fan);
+  if (b.may(B_CLOSED)) note_form(lib, "closed_staged", lib->opt.closed_staged);
   int fan_i = 0;
   uint32_t used = 0;
   if (fan) HIP_TRY(hipEventRecord(lib->gjk_fork, caller));
@@ -337,7 +341,10 @@ static int plan_split(Batch<T>& b, hipStream_t st, BvhSplit& split, bool want, b
   const size_t n = b.n;
   memset(&split, 0, sizeof(split));
   split.leaf_cost = o.shape_leaf_cost;
-  if (!(want && (solid ? o.shape_levels : o.bvh_levels) > 1 && lib->bvh_params.num_max_contacts == 1 && !lib->bvh_params.contacts)) return HFCL_OK;
+  if (!(want && (solid ? o.shape_levels : o.bvh_levels) > 1 && lib->bvh_params.num_max_contacts == 1 && !lib->bvh_params.contacts)) {
+    note_form(lib, solid ? "ms_split" : "mm_split", 0);
+    return HFCL_OK;
+  }
   const bool main_set = &tabs == &lib->split_main;
   int r = main_set ? ensure_split_main(lib, n) : ensure_split(tabs, n, 16, false);
   if (r) return r;
@@ -404,6 +411,24 @@ static int plan_split(Batch<T>& b, hipStream_t st, BvhSplit& split, bool want, b
       split.walk_budget[0] = o.shape_walk_budget;
     }
   }
+  // (the plan as the kernels get it)
+  const char* const names[2][12] = {{"mm_coop", "mm_budget0", "mm_budget", "mm_levels", "mm_cap", "mm_cut_ticks", "mm_rounds", "mm_order", "mm_walk_k", "mm_walk_budget", "mm_leaf_cost", "mm_perm"},
+                                    {"ms_coop", "ms_budget0", "ms_budget", "ms_levels", "ms_cap", "ms_cut_ticks", "ms_rounds", "ms_order", "ms_walk_k", "ms_walk_budget", "ms_leaf_cost", "ms_perm"}};
+  const char* const* nm = names[solid ? 1 : 0];
+  note_form(lib, nm[0], split.coop);
+  note_form(lib, nm[1], split.budget0);
+  note_form(lib, nm[2], split.budget);
+  note_form(lib, nm[3], split.n_levels);
+  note_form(lib, nm[4], split.cap);
+  note_form(lib, nm[5], split.cut_ticks);
+  note_form(lib, nm[6], split.walk.recs ? split.walk_rounds : 0u);
+  note_form(lib, nm[7], split.order != nullptr);
+  for (int k = 0; k < WALK_ROUNDS && split.walk.recs; ++k) {
+    note_form(lib, nm[8], split.walk_k[k]);
+    note_form(lib, nm[9], split.walk_budget[k]);
+  }
+  note_form(lib, nm[10], split.leaf_cost);
+  note_form(lib, nm[11], split.walk.perm != nullptr);
   return HFCL_OK;
 }
 
@@ -418,6 +443,7 @@ static int mesh_mesh_collide(Batch<T>& b, hipStream_t st, const BvhView<T>& bv, 
   if (rc) return rc;
   AsideStream beside[WALK_ROUNDS - 1] = {};
   const bool early = split.walk.recs && split.walk_rounds > 1 && lib->opt.walk_early_coop;
+  note_form(lib, "mm_early_coop", early);
   if (early) {
     rc = ensure_walk_streams(lib);
     if (rc) return rc;
@@ -434,6 +460,7 @@ static int mesh_solid_collide(Batch<T>& b, hipStream_t st, const BvhView<T>& bv,
   hfcl_lib* lib = b.lib;
   const size_t n = b.n;
   Timed t(b, "k_bvh_shape", st);
+  note_form(lib, "ms_lane", lane);
   if (!lane) {
     launch_bvh_shape<T>(b.blocks_for(n / 8 + 1, 64 / BS_W), st, b.wk, b.lv, bv, b.io, b.q, lib->bvh_params, b.break_distance2());
     return HFCL_OK;
@@ -449,13 +476,15 @@ static int mesh_solid_collide(Batch<T>& b, hipStream_t st, const BvhView<T>& bv,
     if (rc) return rc;
     aside = AsideStream{own_stream ? lib->mesh_aux : lib->aux, lib->ev_aux2, lib->ev_aux3};  // (`aux` is the solids' EPA section's, beside)
   }
+  note_form(lib, "ms_finish_aside", aside.stream != nullptr);
+  note_form(lib, "ms_finish_tiers", b.wk.shape_finish_over != nullptr);
   launch_bvh_shape_fast<T>(b.blocks_for(n, BVH_BLOCK), b.blocks_for(n / 8 + 1, 64 / BS_W), int(std::min<size_t>(n / 4 + 1, size_t(lib->n_cus) * 8)), st, b.wk, b.lv, bv, b.io, b.q,
                            lib->bvh_params, b.break_distance2(), split, spill, aside.stream ? &aside : nullptr);
   return HFCL_OK;
 }
 
 // what the two distance() walks hand to their continuation kernels: the suspended records, their counters in the batch's counter block, the pool's knobs
-static void fill_continuation(BvhSpill& sp, const hfcl_lib* lib, void* susp, int ctr_susp, int ctr_rerun, int ctr_ticket, uint32_t budget, uint32_t pool,
+static void fill_continuation(BvhSpill& sp, hfcl_lib* lib, void* susp, int ctr_susp, int ctr_rerun, int ctr_ticket, uint32_t budget, uint32_t pool,
                               uint32_t leaf_min, uint32_t starve) {
   sp.susp = susp;
   sp.rerun_count = lib->opt.pool_rerun ? lib->d_counts + ctr_rerun : nullptr;
@@ -467,6 +496,12 @@ static void fill_continuation(BvhSpill& sp, const hfcl_lib* lib, void* susp, int
   sp.pool_ticket = lib->d_counts + ctr_ticket;
   sp.pool_leaf_min = leaf_min;
   sp.pool_starve = starve;
+  const bool solid = ctr_susp == CTR_SHAPE_DIST_SUSP;
+  note_form(lib, solid ? "msd_budget" : "mmd_budget", budget);
+  note_form(lib, solid ? "msd_pool" : "mmd_pool", pool);
+  note_form(lib, solid ? "msd_leaf_min" : "mmd_leaf_min", leaf_min);
+  note_form(lib, solid ? "msd_starve" : "mmd_starve", starve);
+  note_form(lib, solid ? "msd_rerun" : "mmd_rerun", lib->opt.pool_rerun);
 }
 // ---- stage: the two distance() walks on `st`: mesh x solid (lane: one query per lane), then mesh x mesh
 template <typename T>
@@ -476,6 +511,7 @@ static int mesh_distance(Batch<T>& b, hipStream_t st, const BvhView<T>& bv, BvhS
   const size_t n = b.n;
   {
     Timed t(b, "k_bvh_shape_distance", st);
+    note_form(lib, "msd_lane", lane);
     if (lane) {
       // long walks are handed to waves -- unless their leaves hand a cached guess on, or the final guess is read
       BvhSpill ss;
@@ -497,6 +533,7 @@ static int mesh_distance(Batch<T>& b, hipStream_t st, const BvhView<T>& bv, BvhS
     fill_continuation(spill, lib, lib->d_dist_susp, CTR_DIST_SUSP, CTR_DIST_RERUN, CTR_DIST_TICKET, o.bvhd_budget, lib->bvh_max_nodes > 32767 ? 0u : o.bvhd_pool,
                       o.bvhd_pool_leaf_min, o.bvhd_pool_starve);
     spill.pool_part_min = o.bvhd_pool_part_min;
+    note_form(lib, "mmd_part_min", spill.pool_part_min);
   }
   launch_bvh_distance<T>(b.blocks_for(n, BVHD_BLOCK), st, b.wk, b.lv, bv, b.io, b.q, spill);
   return HFCL_OK;
@@ -557,6 +594,8 @@ static int launch_meshes(Batch<T>& b, hipStream_t st, bool own_stream) {
   const bool lane = b.may(B_BVHSHAPE) && o.bvh_shape_lane &&
                     (collide ? size_t(lib->bvh_max_depth) + 1 <= size_t(BVH_STACK) && mesh_shape_lane_request(b.q, lib->bvh_params.num_max_contacts)
                              : size_t(lib->bvh_max_depth) + 1 <= size_t(BVHD_STACK));
+  note_form(lib, "bvh_wide", spill.wide);
+  note_form(lib, "bvh_filter", bv.fnodes != nullptr);
   if (lane) {
     rc = size_shape_defer(b, collide);
     if (rc) return rc;
@@ -566,6 +605,7 @@ static int launch_meshes(Batch<T>& b, hipStream_t st, bool own_stream) {
   // their own) on a second one, beside the mesh x solid walks -- the two share nothing else, and each is a chain that leaves the chip
   // half empty (cfgmix: 1.45 ms of mesh x mesh behind 2.3 ms of mesh x solid)
   const bool mm_beside = own_stream && o.mesh_beside >= 2 && b.may(B_BVH) && b.may(B_BVHSHAPE) && !spill.wide && !o.bvh_cut_ticks && o.bvh_coop && (o.walk_auto || o.walk_rounds != 0);
+  note_form(lib, "mm_beside", mm_beside);
   if (mm_beside) {
     HIP_TRY(hipEventRecord(lib->ev_mesh_fork2, st));
     HIP_TRY(hipStreamWaitEvent(lib->mesh_st2, lib->ev_mesh_fork2, 0));
@@ -621,7 +661,14 @@ static int launch_epa(Batch<T>& b, hipStream_t st) {
   const bool direct = sizeof(T) == 8 && o.epa_direct_max && n <= o.epa_direct_max;
   const bool cc_staged = F32 && !direct && b.may(B_CC) && o.epa_cc_staged && n >= o.epa_cc_staged_min;
   const bool gen_staged = !direct && general_q && o.epa_general_staged && n >= o.epa_general_staged_min;
+  note_form(lib, "epa_direct", direct);
+  note_form(lib, "epa_cc_staged", cc_staged);
+  note_form(lib, "epa_gen_staged", gen_staged);
+  note_form(lib, "epa_resume_cap", wk.resume_cap);
   if (cc_staged) {
+    note_form(lib, "epa_pool_share", o.epa_pool_share);
+    note_form(lib, "epa_pool_min_refills", o.epa_pool_min_refills);
+    note_form(lib, "epa_records_aside", o.records_aside);
     HIP_TRY(lib->d_epa_ready.grow(lib->ws_capacity * sizeof(EpaReady<float>)));
     wk.epa_ready = lib->d_epa_ready;
   }
@@ -655,6 +702,7 @@ static int launch_epa(Batch<T>& b, hipStream_t st) {
       if (o.epa64_two_streams && lib->has_curved && general_q) {
         if (int rc = ensure_aux(lib)) return rc;
         st2 = lib->aux;
+        note_form(lib, "epa64_two_streams", 1);
         HIP_TRY(hipEventRecord(lib->ev_aux0, st));
         HIP_TRY(hipStreamWaitEvent(st2, lib->ev_aux0, 0));
       }
@@ -745,6 +793,7 @@ static int run_batch_one(hfcl_lib* lib, const uint32_t* d_s1, const uint32_t* d_
   }
   HIP_TRY(hipSetDevice(lib->device));
   Batch<T> b{lib, Work(), LibView<T>(), io, q, n};
+  lib->form_notes.clear();
   int rc = ensure_workspace(lib, n, b.any_gjk() && q.compute_penetration);
   if (rc) return rc;
   make_views(b, d_s1, d_s2);
@@ -766,7 +815,9 @@ static int run_batch_one(hfcl_lib* lib, const uint32_t* d_s1, const uint32_t* d_
     launch_classify(b.blocks_for(n, CLS_BLOCK * 8), st, b.wk, lib->d_kinds, uint32_t(lib->n_shapes), q.mode != 1);
   }
   bool mesh_join_pending = false;
-  if (meshes_run_beside(b)) {
+  const bool meshes_beside = meshes_run_beside(b);
+  if (!lib->h_meshes.empty()) note_form(lib, "mesh_beside", meshes_beside);
+  if (meshes_beside) {
     HIP_TRY(hipEventRecord(lib->ev_mesh_fork, st));
     HIP_TRY(hipStreamWaitEvent(lib->mesh_st, lib->ev_mesh_fork, 0));
     rc = launch_meshes(b, lib->mesh_st.get(), true);
@@ -867,7 +918,10 @@ int ensure_helper(hfcl_lib* lib) {
 template <typename T>
 int run_batch(hfcl_lib* lib, const uint32_t* d_s1, const uint32_t* d_s2, IO<T> io, size_t n, QParams<T> q, hipStream_t st) {
   lib->last_split = false;
-  if (!lib->in_host_batch) lib->last_host = false;
+  if (!lib->in_host_batch) {
+    lib->last_host = false;
+    lib->host_notes.clear();
+  }
   if (lib->graph_dirty) {
     const int rcg = upload_graph(lib);
     if (rcg) return rcg;

@@ -5,9 +5,9 @@
 #include "hfcl_launch.hpp"
 
 // This file is compiled three times (Makefile): hfcl_k_bvh.o, HFCL_BVH_PART = 1 -- mesh x mesh collide(), top-level triangle pairs and their
-// launchers --, hfcl_k_bvhc.o, HFCL_BVH_PART = 3 -- mesh x solid collide(), its leaves' solvers without contraction (HFCL_LEAF_CONTRACT_OFF,
-// hfcl_bvh.hpp: every inlined copy of a leaf is then the same arithmetic; the box tests keep hipcc's default) -- and
-// hfcl_k_bvhs.o, HFCL_BVH_PART = 2 -- mesh x solid distance() -- WITHOUT contraction of a*b+c: the reported triangle hangs on
+// launchers --, hfcl_k_bvhc.o, HFCL_BVH_PART = 3 -- mesh x solid collide(), WITHOUT contraction of a*b+c: every inlined copy of a leaf,
+// of the fit of the solid's box and of the box tests is then the same arithmetic, and the forms of the walk write the same bytes -- and
+// hfcl_k_bvhs.o, HFCL_BVH_PART = 2 -- mesh x solid distance() -- without it either: the reported triangle hangs on
 // comparisons of distances that are equal or an ulp apart (triangles that share the closest vertex or edge), and with the
 // reference's arithmetic the ids, distances and witness points are the oracle's (profiles/r05_c: ids 77-93 % -> 100 % equal,
 // distances 29-71 % -> 100 % bit-equal), as for mesh x mesh (hfcl_k_bvhd.hip).  Kernels both parts launch carry the part as a
@@ -996,7 +996,7 @@ __global__ void __launch_bounds__(64) k_bvh_shape(Work wk, LibView<T> lib, BvhVi
       } else {
         PairOut<T> o;
         o.distance = st.rec_dist;
-        o.normal = swapped ? -st.nn : st.nn;
+        o.normal = (swapped && st.nn.x == st.nn.x) ? -st.nn : st.nn;  // (no witness: the one NaN of every form, not its negative)
         o.p1 = swapped ? st.np2 : st.np1;
         o.p2 = swapped ? st.np1 : st.np2;
         o.gjk_status = GJK_DID_NOT_RUN;
@@ -2134,7 +2134,7 @@ __global__ void __launch_bounds__(64) k_bvh_shape_distance(Work wk, LibView<T> l
       } else {
         PairOut<T> o;
         o.distance = st.min_distance;
-        o.normal = swapped ? -st.nn : st.nn;
+        o.normal = (swapped && st.nn.x == st.nn.x) ? -st.nn : st.nn;  // (no witness: the one NaN of every form, not its negative)
         o.p1 = swapped ? st.np2 : st.np1;
         o.p2 = swapped ? st.np1 : st.np2;
         o.gjk_status = GJK_DID_NOT_RUN;

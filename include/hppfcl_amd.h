@@ -437,11 +437,21 @@ void hfcl_lib_set_split(hfcl_lib* lib, int parts);
 int  hfcl_lib_get_split(const hfcl_lib* lib);
 int  hfcl_lib_last_split_parts(const hfcl_lib* lib);  /* 1 or 2: how the last batch ran */
 /* Tuning options by name.  Every option chooses between forms of the same computation or sizes a budget / a table; none changes a
- * record (the forms are held against each other byte for byte in tests/).  Keys are case-insensitive; hfcl_lib_option_key(0), (1), ...
- * enumerates them (NULL ends the list); INTEGRATION.md describes each.  An option holds from the next batch on.  Returns
- * HFCL_ERR_INVALID_ARGUMENT for an unknown key or a value outside the option's range (nothing is changed then).
+ * record: tests/test_options_gpu.py holds every value of every option against the default form byte for byte (tests/options_table.py
+ * is the list).  One exception, in the last bits and not in a decision (INTEGRATION.md section 4 has the figures): fp64 mesh x mesh
+ * collide() under bvh_coop = 0, bvh_walk_rounds = 0 or bvh_force_wide = 1 -- status, num_contacts, b1, b2 and the NaN pattern are the
+ * same bytes; distance may differ in its last bits (another inlined copy of the contracted triangle-pair leaf).  And one by design:
+ * pool_rerun = 0 switches the ordered re-walk of doubtful distance() walks off, so a record may name another triangle (pair) of exactly
+ * the same distance, as may the ordered continuations (bvhd_pool = 0, shape_dist_pool = 0) and the group kernel (bvh_shape_lane = 0) at
+ * an exact tie; distances never differ.
+ * Keys are case-insensitive, an "HFCL_" prefix is accepted; hfcl_lib_option_key(0), (1), ... enumerates them (NULL ends the list);
+ * INTEGRATION.md describes each.  A value is an unsigned decimal number -- digits only: no sign, no blank, nothing behind it -- or, for
+ * bvh_walk_k and bvh_walk_budget, a comma-separated list of such numbers.  An option holds from the next batch on.  Returns
+ * HFCL_ERR_INVALID_ARGUMENT for an unknown key, for a value that is no such number (or list: an empty or a bad element, too many
+ * elements) and for a value outside the option's range; nothing is changed then, no value is clamped into its range.
  * The environment is a FALLBACK, read once by hfcl_lib_create: HFCL_<KEY IN UPPER CASE>=value sets the same option for a process that
- * cannot be changed to call this function (A/B runs of a built binary); a later hfcl_lib_set_option wins. */
+ * cannot be changed to call this function (A/B runs of a built binary); a value this function would refuse is ignored there; a later
+ * hfcl_lib_set_option wins. */
 int hfcl_lib_set_option(hfcl_lib* lib, const char* key, const char* value);
 /* 1 when this build carries the forms that lost their A/B and are kept as identity references for the tests only (options `bvh_filter`,
  * `epa_general_staged`: compiled with -DHFCL_KEEP_AB_FORMS=1, tools/build_variant.sh); the product build returns 0 and refuses those options. */
