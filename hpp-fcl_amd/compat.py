@@ -678,6 +678,10 @@ def _check_pair(o1, o2, for_distance):
         if t1 != t2 and engine.octree_pair_supported(int((o2 if t1 else o1).getNodeType())):
             return
         raise ValueError("Collision function between node type %d and node type %d is not yet supported." % (o1.getNodeType(), o2.getNodeType()))
+    if t1 or t2:  # distance(): an octree against one of the seven convex solids, either order (hppfcl_amd_octree_distance.h)
+        if t1 != t2 and engine.octree_distance_pair_supported(int((o2 if t1 else o1).getNodeType())):
+            return
+        raise ValueError("Distance function between node type %d and node type %d is not yet supported." % (o1.getNodeType(), o2.getNodeType()))
     h1, h2 = isinstance(o1, HeightFieldAABB), isinstance(o2, HeightFieldAABB)
     if (h1 or h2) and not for_distance:
         if h1 != h2 and engine.hfield_pair_supported(int((o2 if h1 else o1).getNodeType())):
@@ -792,6 +796,32 @@ def _collide_octree(o1, tf1, o2, tf2, request, result):
     return result.numContacts()
 
 
+def _distance_octree(o1, tf1, o2, tf2, request, result):
+    """(OcTree, solid) or (solid, OcTree) through hfcl_octree_distance_batch: the reference's ordered walk.  Either order gets the
+    octree-first result (src/distance.cpp swaps back only for BVH and height fields): result.o1 is the tree, b1 its node.  The walk of
+    the reference runs on the caller's DistanceResult, so a minimum it already holds would prune this walk too; here the walk starts
+    fresh and the result is merged by DistanceResult::update."""
+    swapped = not isinstance(o1, OcTree)
+    tree, tft, solid, tfs = (o2, tf2, o1, tf1) if swapped else (o1, tf1, o2, tf2)
+    ctx = _context()
+    sid, tid = ctx.add(solid), ctx.add_octree(tree)
+    lib = ctx.library()
+    try:
+        rec = lib.octree_distance([tid], [sid], tft._abi().reshape(1, 12), tfs._abi().reshape(1, 12), request._abi(), swapped=[1 if swapped else 0])
+    except engine.EngineError as e:
+        if e.code in (abi.ERR_INVALID_ARGUMENT, abi.ERR_UNSUPPORTED_PAIR, abi.ERR_LIMIT):
+            raise ValueError(str(e))
+        raise
+    r = rec[0]
+    d = float(r["distance"])
+    if result.min_distance > d:  # DistanceResult::update
+        result.min_distance, result.o1, result.o2 = d, tree, solid
+        result.b1, result.b2 = int(r["b1"]), int(r["b2"])
+        result.normal = np.array(r["normal"])
+        result.nearest_points = [np.array(r["p1"]), np.array(r["p2"])]
+    return d
+
+
 def collide(*args):
     """collide(o1, tf1, o2, tf2, request, result) or collide(obj1, obj2, request, result)  (python/collision.cc:257-266)"""
     if len(args) == 4:
@@ -826,6 +856,8 @@ def distance(*args):
     _check_pair(o1, o2, True)
     if result.min_distance <= 0:  # DistanceRequest::isSatisfied
         return result.min_distance
+    if isinstance(o1, OcTree) or isinstance(o2, OcTree):
+        return _distance_octree(o1, tf1, o2, tf2, request, result)
     rec, g, _ = _run("distance", [(o1, tf1, o2, tf2)], request)
     r = rec[0]
     d = float(r["distance"])

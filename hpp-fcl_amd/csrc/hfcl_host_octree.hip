@@ -1,8 +1,10 @@
 // hfcl_host_octree.hip -- host side of the octrees (hppfcl_amd_octree.h; the kernels: hfcl_k_octree.hip, the arithmetic:
 // hfcl_octree.hpp): the validator and the builder from points, the registration on a library, and hfcl_octree_collide_batch* -- the
 // device form in chunks of queries (count, scan, list, solve, fold), the host form a chunked copy / compute / copy around it.  The
-// chunking and workspace rules are those of hfcl_host_hfield.hip.
+// chunking and workspace rules are those of hfcl_host_hfield.hip.  At the end hfcl_octree_distance_batch* (hppfcl_amd_octree_distance.h;
+// the kernel: hfcl_k_octree_distance.hip): one launch per chunk, no workspace, no read-back.
 #include "hfcl_host.hpp"
+#include "hfcl_octree_distance.hpp"
 
 #include <cmath>
 
@@ -369,6 +371,168 @@ int hfcl_octree_collide_batch(hfcl_lib* lib, const uint32_t* octree, const uint3
     }
     if (!ok) {
       set_error("hfcl_octree_collide_batch: HIP copy failed");
+      rc = HFCL_ERR_HIP;
+    }
+  }
+  hipStreamSynchronize(st);
+  return rc;
+}
+
+// ---- distance() (hppfcl_amd_octree_distance.h) ------------------------------------------------------------------------------------
+}  // extern "C"
+
+namespace {
+
+// what both forms check before any work
+int octd_request(const char* who, const hfcl_distance_request* req, QParams<double>& q) {
+  const int rc = setup_distance<double>(req, q);  // a null request, tolerances, epa_max_iterations > 64, variants
+  if (rc) return rc;
+  if (req->q.gjk_initial_guess != HFCL_GUESS_DEFAULT) {
+    set_error(std::string(who) + ": gjk_initial_guess must be DefaultGuess (a cached guess chains from leaf to leaf inside a query, a bounding-volume guess changes the leaf set-up: not done)");
+    return HFCL_ERR_LIMIT;
+  }
+  return HFCL_OK;
+}
+
+// one entry of last_kernel_breakdown() around the launches of a call
+struct Timed {
+  hfcl_lib* lib = nullptr;
+  hipStream_t st;
+  Timed(hfcl_lib* l, const char* name, hipStream_t s) : st(s) {
+    for (auto& t : l->timers) t.used = false;
+    if (!l->kernel_timing) return;
+    lib = l;
+    (void)hipEventRecord(timer_slot(lib, 0, name)->e0, st);
+  }
+  ~Timed() {
+    if (lib) (void)hipEventRecord(lib->timers[0].e1, st);
+  }
+  Timed(const Timed&) = delete;
+};
+
+// The call on device pointers: queries [0, n) in chunks, one launch each; nothing is read back
+int octd_run(hfcl_lib* lib, const uint32_t* d_octree, const uint32_t* d_shape, const double* d_tft, const double* d_tfs, size_t n,
+             const uint8_t* d_swapped, const QParams<double>& q, hfcl_result* d_out, uint32_t* d_visited, hipStream_t st) {
+  auto& oc = lib->oct;
+  const int rc = upload_octrees(lib);
+  if (rc) return rc;
+  hfcl::OctDistArgs a;
+  a.shapes = lib->d_shapes64;
+  a.verts = lib->d_verts64;
+  a.n_shapes = uint32_t(lib->n_shapes);
+  a.n_trees = uint32_t(oc.h_trees.size());
+  a.trees = oc.d_trees;
+  a.nodes = oc.d_nodes;
+  a.q = q;
+  const size_t chunk = std::min(oct_chunk(lib), n);
+  Timed t(lib, "k_oct_distance", st);
+  for (size_t q0 = 0; q0 < n; q0 += chunk) {
+    const size_t m = std::min(chunk, n - q0);
+    a.octree = d_octree + q0;
+    a.shape = d_shape + q0;
+    a.tf_t = d_tft + 12 * q0;
+    a.tf_s = d_tfs + 12 * q0;
+    a.swapped = d_swapped ? d_swapped + q0 : nullptr;
+    a.out = d_out + q0;
+    a.n_visited = d_visited ? d_visited + q0 : nullptr;
+    a.m = uint32_t(m);
+    launch_oct_distance(st, a, 1 << 20);  // (a workgroup per four queries: the hardware hands the long walks out as they come)
+  }
+  HIP_TRY(hipGetLastError());
+  return HFCL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hfcl_octree_distance_pair_supported(int32_t t) { return hfcl::oct_kind_supported(t) ? 1 : 0; }
+
+int hfcl_octree_distance_batch_device(hfcl_lib* lib, const uint32_t* d_octree, const uint32_t* d_shape, const double* d_tf_octree,
+                                      const double* d_tf_shape, size_t n, const uint8_t* d_swapped, const hfcl_distance_request* req,
+                                      hfcl_result* d_out, uint32_t* d_n_visited, void* stream) {
+  if (int rc = hf_no_device()) return rc;
+  if (!lib) {
+    set_error("hfcl_octree_distance_batch_device: null library");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  QParams<double> q;
+  if (int rc = octd_request("hfcl_octree_distance_batch_device", req, q)) return rc;
+  if (n == 0) return HFCL_OK;
+  if (!d_octree || !d_shape || !d_tf_octree || !d_tf_shape || !d_out) {
+    set_error("hfcl_octree_distance_batch_device: null buffer");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (n > 0xFFFFFFF0ull) {
+    set_error("batch too large (max 2^32-16 queries per call)");
+    return HFCL_ERR_LIMIT;
+  }
+  HIP_TRY(hipSetDevice(lib->device));
+  return octd_run(lib, d_octree, d_shape, d_tf_octree, d_tf_shape, n, d_swapped, q, d_out, d_n_visited, (hipStream_t)stream);
+}
+
+int hfcl_octree_distance_batch(hfcl_lib* lib, const uint32_t* octree, const uint32_t* shape, const double* tf_octree, const double* tf_shape,
+                               size_t n, const uint8_t* swapped, const hfcl_distance_request* req, hfcl_result* out, uint32_t* n_visited) {
+  if (int rc = hf_no_device()) return rc;
+  if (!lib) {
+    set_error("hfcl_octree_distance_batch: null library");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  QParams<double> q;
+  if (int rc = octd_request("hfcl_octree_distance_batch", req, q)) return rc;
+  if (n == 0) return HFCL_OK;
+  if (!octree || !shape || !tf_octree || !tf_shape || !out) {
+    set_error("hfcl_octree_distance_batch: null buffer");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  if (n > 0xFFFFFFF0ull) {
+    set_error("batch too large (max 2^32-16 queries per call)");
+    return HFCL_ERR_LIMIT;
+  }
+  auto& oc = lib->oct;
+  for (size_t i = 0; i < n; ++i) {
+    if (octree[i] >= oc.h_trees.size() || shape[i] >= lib->n_shapes) {
+      set_error("hfcl_octree_distance_batch: octree / shape id outside the library at query " + std::to_string(i));
+      return HFCL_ERR_INVALID_ARGUMENT;
+    }
+    if (!hfcl_octree_distance_pair_supported(lib->h_shapes[shape[i]].type)) {
+      set_error("Distance function between an octree and node type " + std::to_string(lib->h_shapes[shape[i]].type) + " is not yet supported.");
+      return HFCL_ERR_UNSUPPORTED_PAIR;
+    }
+  }
+  HIP_TRY(hipSetDevice(lib->device));
+  if (!oc.st) HIP_TRY(oc.st.create());
+  hipStream_t st = oc.st;
+  // staged in pieces of the chunk option: the staging buffers are the collide call's, the visited counts go through its count buffer
+  const size_t chunk = std::min(oct_chunk(lib), n);
+  HIP_TRY(oc.s_octree.grow(chunk));
+  HIP_TRY(oc.s_shape.grow(chunk));
+  HIP_TRY(oc.s_tft.grow(12 * chunk));
+  HIP_TRY(oc.s_tfs.grow(12 * chunk));
+  HIP_TRY(oc.s_swapped.grow(chunk));
+  HIP_TRY(oc.s_out.grow(chunk));
+  HIP_TRY(oc.d_counts.grow(chunk));
+  int rc = HFCL_OK;
+  for (size_t q0 = 0; q0 < n && !rc; q0 += chunk) {
+    const size_t m = std::min(chunk, n - q0);
+    bool ok = hipMemcpyAsync(oc.s_octree, octree + q0, m * sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess;
+    ok = ok && hipMemcpyAsync(oc.s_shape, shape + q0, m * sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess;
+    ok = ok && hipMemcpyAsync(oc.s_tft, tf_octree + 12 * q0, m * 12 * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
+    ok = ok && hipMemcpyAsync(oc.s_tfs, tf_shape + 12 * q0, m * 12 * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
+    ok = ok && (!swapped || hipMemcpyAsync(oc.s_swapped, swapped + q0, m, hipMemcpyHostToDevice, st) == hipSuccess);
+    if (!ok) {
+      set_error("hfcl_octree_distance_batch: HIP copy failed");
+      rc = HFCL_ERR_HIP;
+      break;
+    }
+    rc = octd_run(lib, oc.s_octree, oc.s_shape, oc.s_tft, oc.s_tfs, m, swapped ? oc.s_swapped.get() : nullptr, q, oc.s_out,
+                  n_visited ? oc.d_counts.get() : nullptr, st);
+    if (rc) break;
+    ok = hipMemcpyAsync(out + q0, oc.s_out, m * sizeof(hfcl_result), hipMemcpyDeviceToHost, st) == hipSuccess;
+    ok = ok && (!n_visited || hipMemcpyAsync(n_visited + q0, oc.d_counts, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess);
+    ok = ok && hipStreamSynchronize(st) == hipSuccess;  // (the staging buffers are the next chunk's)
+    if (!ok) {
+      set_error("hfcl_octree_distance_batch: HIP copy failed");
       rc = HFCL_ERR_HIP;
     }
   }

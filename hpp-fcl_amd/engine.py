@@ -93,6 +93,8 @@ OCTREE_SYMBOLS = [
     "hfcl_lib_clear_octrees", "hfcl_octree_root_box", "hfcl_octree_pair_supported", "hfcl_octree_collide_batch",
     "hfcl_octree_collide_batch_device",
 ]
+# include/hppfcl_amd_octree_distance.h (included by hppfcl_amd.h): distance() between a registered OcTree and a convex solid
+OCTREE_DISTANCE_SYMBOLS = ["hfcl_octree_distance_pair_supported", "hfcl_octree_distance_batch", "hfcl_octree_distance_batch_device"]
 
 
 class EngineError(RuntimeError):
@@ -214,6 +216,11 @@ def hfield_build(x_dim, y_dim, heights, min_height=0.0):
 def octree_pair_supported(node_type):
     """hfcl_octree_pair_supported: does collide() have an octree row for a solid of this node type?"""
     return bool(dll().hfcl_octree_pair_supported(C.c_int32(int(node_type))))
+
+
+def octree_distance_pair_supported(node_type):
+    """hfcl_octree_distance_pair_supported: does distance() have an octree row for a solid of this node type?"""
+    return bool(dll().hfcl_octree_distance_pair_supported(C.c_int32(int(node_type))))
 
 
 def _octree_nodes(nodes):
@@ -526,6 +533,35 @@ class Library:
                                                       _dptr(d_contacts), C.c_size_t(int(max_contacts)), C.byref(nc) if want_count else None,
                                                       C.c_void_p(stream)))
         return int(nc.value) if want_count else None
+
+    def octree_distance(self, octree, shape, tf_octree, tf_shape, req=None, swapped=None, want_visited=False):
+        """Batched distance(OcTree, solid) from host arrays: the result of the reference's ordered walk (hppfcl_amd_octree_distance.h).
+        swapped[i] = 1: the caller's order was distance(solid, OcTree), which the reference answers with the octree-first result (bit
+        23 of the status alone changes).  Returns the records, or (records, n_visited) -- the leaves each walk solved -- when
+        want_visited."""
+        req = req or abi.default_distance_request()
+        octree = np.ascontiguousarray(octree, dtype=np.uint32)
+        shape = np.ascontiguousarray(shape, dtype=np.uint32)
+        tft = np.ascontiguousarray(tf_octree, dtype=np.float64).reshape(-1, 12)
+        tfs = np.ascontiguousarray(tf_shape, dtype=np.float64).reshape(-1, 12)
+        n = len(octree)
+        if not (len(shape) == len(tft) == len(tfs) == n):
+            raise ValueError("batch arrays must have equal length")
+        if swapped is not None:
+            swapped = np.ascontiguousarray(swapped, dtype=np.uint8)
+            if len(swapped) != n:
+                raise ValueError("swapped: one byte per query")
+        out = np.zeros(n, dtype=abi.RESULT_DTYPE)
+        visited = np.zeros(n, dtype=np.uint32) if want_visited else None
+        _check(dll().hfcl_octree_distance_batch(self._h, abi.ptr(octree), abi.ptr(shape), abi.ptr(tft), abi.ptr(tfs), C.c_size_t(n),
+                                                abi.ptr(swapped), C.byref(req), abi.ptr(out), abi.ptr(visited)))
+        return (out, visited) if want_visited else out
+
+    def octree_distance_device(self, d_octree, d_shape, d_tf_octree, d_tf_shape, n, req, d_out, d_swapped=None, d_visited=None, stream=0):
+        """The same call on device pointers (torch tensors or raw pointers): asynchronous on `stream`, nothing is read back."""
+        _check(dll().hfcl_octree_distance_batch_device(self._h, _dptr(d_octree), _dptr(d_shape), _dptr(d_tf_octree), _dptr(d_tf_shape),
+                                                       C.c_size_t(n), _dptr(d_swapped), C.byref(req), _dptr(d_out), _dptr(d_visited),
+                                                       C.c_void_p(stream)))
 
     def collide_contacts(self, s1, s2, tf1, tf2, req, max_contacts):
         """Batched collide() returning (records, contacts[CONTACT_DTYPE], n_produced)."""

@@ -65,9 +65,10 @@
  * HFCL_ERR_NO_DEVICE, as every compute entry point.
  *
  * Not done: Plane and Halfspace against an octree (their local boxes are unbounded and the OBB conversion yields NaN centres);
- * distance() (its pruning depends on the running minimum); octree x octree, x mesh, x height field; octrees as scene objects or
- * environments; reading octomap's files; fp32 and hfcl_multi_* forms; cached and bounding-volume GJK guesses; a finite
- * distance_upper_bound.
+ * octree x octree, x mesh, x height field; octrees as scene objects or environments; reading octomap's files; fp32 and hfcl_multi_*
+ * forms; cached and bounding-volume GJK guesses; a finite distance_upper_bound.  (distance() against the same solids is in
+ * hppfcl_amd_octree_distance.h: its pruning depends on the running minimum, so it is the reference's ordered walk, a query per lane
+ * group, and not the route below.)
  *
  * Work on the device: the queries of a call go in chunks (option `octree_chunk`: queries per chunk, 0 = automatic; a chunk that lists
  * more (query, leaf) items than option `octree_items`, 0 = automatic: 2^20, is cut down, to one query at the least; records do not
