@@ -13,6 +13,7 @@
 #pragma once
 #include "../../include/hppfcl_amd_hfield.h"
 #include "hfcl_pair.hpp"
+#include "hfcl_listed.hpp"
 
 namespace hfcl {
 
@@ -556,46 +557,23 @@ struct DHfield {
 };
 
 // ---- the kernels' parameter block (hfcl_k_hfield.hip) ---------------------------------------------------------------------------
-// A chunk of m queries of a call: the per-query arrays point at the chunk's first query.
-struct HfArgs {
-  const DShape<double>* shapes;
-  const double* verts;
-  uint32_t n_shapes, n_fields;
+// What a chunk of height-field queries adds to the pipeline's block (hfcl_listed.hpp; tf_c: the fields' poses)
+struct HfArgs : ListedArgs {
+  uint32_t n_fields;
   const DHfield* fields;
   const hfcl_hfield_node* nodes;
   const double* heights;
   const double* xgrid;
   const double* ygrid;
   const uint32_t* hfield;
-  const uint32_t* shape;
-  const double* tf_h;
-  const double* tf_s;
-  const uint8_t* swapped;  // nullptr: none
-  uint32_t m, pair0;       // queries of the chunk; index of its first query in the call (hfcl_contact::pair)
-  QParams<double> q;       // hf_leaf_params of the request
-  double bd2;              // break_distance^2
-  uint32_t num_max_contacts;
-  int skip_all;            // security_margin == -inf
-  uint32_t* counts;        // m: listed leaves of a query
-  uint64_t* offsets;       // m + 1: where a query's items start
-  double* box_total;       // m: the minimum over all box bounds of a query's walk
   HfItem<double>* items;
   HfLeafOut<double>* leaves;
-  uint64_t n_items;
-  uint32_t* ccounts;       // m: contacts of a query
-  uint64_t* coffsets;      // m + 1: where they go in the call's contact list
-  uint64_t* running;       // contacts of the chunks before this one, then of this one too
-  hfcl_result* out;
-  double* dlb;             // nullptr or m
-  hfcl_contact* contacts;  // nullptr or contacts_cap records
-  uint64_t contacts_cap;
 };
 
 }  // namespace hfcl
 
 #if defined(__HIPCC__)
-// Launches of one chunk, in stream order; no atomics, no kernel waits for another workgroup.  names / e0 / e1: timing slots (e0 == nullptr: none)
-void launch_hf_count(hipStream_t st, const hfcl::HfArgs& a);      // k_hf_walk<count>, k_hf_scan: a.counts, a.offsets (a.offsets[m] = the items)
+// Launches of one chunk (hfcl_k_hfield.hip: launch_listed_count / launch_listed_solve of hfcl_listed.hpp for this kind)
+void launch_hf_count(hipStream_t st, const hfcl::HfArgs& a);
 void launch_hf_solve(hipStream_t st, const hfcl::HfArgs& a, int max_blocks, bool want_contacts, const char** names, hipEvent_t* e0, hipEvent_t* e1);
-constexpr int HF_TIMED_KERNELS = 5;
 #endif

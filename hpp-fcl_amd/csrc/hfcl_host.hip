@@ -787,6 +787,15 @@ KernelTime* timer_slot(hfcl_lib* lib, size_t i, const char* name) {
   return &lib->timers[i];
 }
 
+int no_device() {
+  int nd = 0;
+  if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) {
+    set_error("no HIP device available (hipGetDeviceCount): the engine has no CPU fallback");
+    return HFCL_ERR_NO_DEVICE;
+  }
+  return HFCL_OK;
+}
+
 template <typename T>
 static void fill_qparams(QParams<T>& q, const hfcl_query_request& r) {
   q.gjk.tolerance = T(r.gjk_tolerance);

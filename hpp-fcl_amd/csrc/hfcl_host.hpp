@@ -1,7 +1,8 @@
 // hfcl_host.hpp -- internal header of the host units (hfcl_host.hip: the library object, options, uploads, request set-up, the entry points
 // and the host pipeline; hfcl_host_batch.hip: one device-resident batch -- workspace, stream sets, the dispatcher run_batch;
-// hfcl_host_patch.hip: contact patches; hfcl_host_scene.hip: scene queries and the cull): the library object and what the units call of
-// each other.  Not included by the kernel units.
+// hfcl_host_patch.hip: contact patches; hfcl_host_scene.hip: scene queries and the cull; hfcl_host_hfield.hip / hfcl_host_octree.hip:
+// height fields and octrees, both over hfcl_host_listed.hpp): the library object and what the units call of each other.  Not included
+// by the kernel units.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -60,6 +61,25 @@ struct WalkTables {
   DevBuf<void> res;
   DevBuf<uint32_t> lists, ctr, order;
   size_t n = 0;
+};
+
+// Workspace of a call of the listed-leaf pipeline (hfcl_listed.hpp; the driver: hfcl_host_listed.hpp), one per kind on a library -- a
+// height-field call and an octree call on two streams share nothing: the counts, offsets and box minima of a chunk of queries, its items
+// and their leaf results, the call's running contact count, and of the host form its stream, its staging and the call's contact list
+template <class Item, class Leaf>
+struct ListedWs {
+  DevBuf<uint32_t> d_counts, d_ccounts;
+  DevBuf<uint64_t> d_offsets, d_coffsets, d_running;
+  DevBuf<double> d_box_total;
+  DevBuf<Item> d_items;
+  DevBuf<Leaf> d_leaves;
+  PinnedBuf<uint64_t> h_words;  // pinned: [0] a chunk's item count, [1] the call's contact count
+  Stream st;
+  DevBuf<uint32_t> s_id, s_shape;  // (s_id: the container ids)
+  DevBuf<double> s_tf_a, s_tf_s, s_dlb;  // (s_tf_a: the containers' poses)
+  DevBuf<uint8_t> s_swapped;
+  DevBuf<hfcl_result> s_out;
+  DevBuf<hfcl_contact> s_contacts;
 };
 
 // Everything hfcl_lib_set_option sets (hfcl_host.hip: apply_option): plain values, read when a batch is set up.  A split batch's helper takes
@@ -359,8 +379,7 @@ struct hfcl_lib {
     DevBuf<hfcl_scene_clearance> d_ns_out;
   } scene;
   // height fields (hfcl_lib_add_hfield; hfcl_host_hfield.hip): the host tables of every registered field one after the other, their device
-  // images (uploaded by the next call when a field was added since), the workspace of a chunk of queries and its items, the host
-  // form's stream and staging, and the call's contact list
+  // images (uploaded by the next call when a field was added since), and the workspace of their calls (the terrain calls of a scene use it too)
   struct Hfields {
     std::vector<DHfield> h_fields;
     std::vector<hfcl_hfield_node> h_nodes;
@@ -369,40 +388,17 @@ struct hfcl_lib {
     DevBuf<DHfield> d_fields;
     DevBuf<hfcl_hfield_node> d_nodes;
     DevBuf<double> d_heights, d_xgrid, d_ygrid;
-    DevBuf<uint32_t> d_counts, d_ccounts;
-    DevBuf<uint64_t> d_offsets, d_coffsets, d_running;
-    DevBuf<double> d_box_total;
-    DevBuf<HfItem<double>> d_items;
-    DevBuf<HfLeafOut<double>> d_leaves;
-    PinnedBuf<uint64_t> h_words;  // pinned: [0] a chunk's item count, [1] the call's contact count
-    Stream st;
-    DevBuf<uint32_t> s_hfield, s_shape;
-    DevBuf<double> s_tfh, s_tfs, s_dlb;
-    DevBuf<uint8_t> s_swapped;
-    DevBuf<hfcl_result> s_out;
-    DevBuf<hfcl_contact> s_contacts;
+    ListedWs<HfItem<double>, HfLeafOut<double>> ws;
   } hf;
   // octrees (hfcl_lib_add_octree; hfcl_host_octree.hip): the host tables of every registered tree one after the other, their device
-  // images (uploaded by the next call when a tree was added or its thresholds set since), the workspace of a chunk of queries and its
-  // items, the host form's stream and staging, and the call's contact list
+  // images (uploaded by the next call when a tree was added or its thresholds set since), and the workspace of their calls
   struct Octrees {
     std::vector<DOctree> h_trees;
     std::vector<hfcl_octree_node> h_nodes;
     bool dirty = false;
     DevBuf<DOctree> d_trees;
     DevBuf<hfcl_octree_node> d_nodes;
-    DevBuf<uint32_t> d_counts, d_ccounts;
-    DevBuf<uint64_t> d_offsets, d_coffsets, d_running;
-    DevBuf<double> d_box_total;
-    DevBuf<OctItem<double>> d_items;
-    DevBuf<OctLeafOut<double>> d_leaves;
-    PinnedBuf<uint64_t> h_words;  // pinned: [0] a chunk's item count, [1] the call's contact count
-    Stream st;
-    DevBuf<uint32_t> s_octree, s_shape;
-    DevBuf<double> s_tft, s_tfs, s_dlb;
-    DevBuf<uint8_t> s_swapped;
-    DevBuf<hfcl_result> s_out;
-    DevBuf<hfcl_contact> s_contacts;
+    ListedWs<OctItem<double>, OctLeafOut<double>> ws;
   } oct;
   // local AABB of every library shape (hfcl_cull.hpp: shape_local_box; BVH models: the box of their vertices), 6 doubles each, rebuilt when
   // shapes or meshes were registered since (hfcl_lib_set_shapes, hfcl_lib_add_bvh)
@@ -498,17 +494,36 @@ template <typename T> int setup_distance(const hfcl_distance_request* req, QPara
 KernelTime* timer_slot(hfcl_lib* lib, size_t i, const char* name);
 int upload_graph(hfcl_lib* lib);
 int upload_bvh(hfcl_lib* lib);
+int no_device();  // HFCL_ERR_NO_DEVICE (with its error text) or 0
 // hfcl_host_hfield.hip: the height-field call's own pieces, which the terrain calls of the scene unit run their chunks through.
 // hf_request: what every form checks of a request before any work (q: hf_leaf_params of it); hf_chunk: queries per chunk (option
-// hfield_chunk); hf_run: queries [0, n) on device pointers in chunks -- pair0: the index of query 0 in the caller's batch, first: this
-// is the first part of that batch (the running contact count, lib->hf.d_running, starts at 0); hf_no_device: HFCL_ERR_NO_DEVICE or 0
-constexpr uint64_t HF_ITEM_HARD_CAP = 1u << 26;  // leaves one query may list (7 GB of item workspace); no query yields more contacts
+// hfield_chunk); hf_run: queries [0, n) on device pointers in chunks (hfcl_host_listed.hpp: listed_run) -- pair0: the index of query 0 in
+// the caller's batch, first: this is the first part of that batch (the running contact count, lib->hf.ws.d_running, starts at 0)
 int hf_request(const char* who, const hfcl_collision_request* req, QParams<double>& q, bool& skip_all);
 size_t hf_chunk(const hfcl_lib* lib);
 int hf_run(hfcl_lib* lib, const uint32_t* d_hfield, const uint32_t* d_shape, const double* d_tfh, const double* d_tfs, size_t n,
            const uint8_t* d_swapped, const hfcl_collision_request* req, const QParams<double>& q, bool skip_all, hfcl_result* d_out, double* d_dlb,
            hfcl_contact* d_contacts, size_t contacts_cap, bool want_contacts, uint32_t pair0, bool first, hipStream_t st);
-int hf_no_device();
 // hfcl_host_scene.hip: the library's local boxes on the device (lib->d_local_boxes), rebuilt when shapes or meshes were registered since
 int ensure_local_boxes(hfcl_lib* lib);
 #pragma GCC visibility pop
+
+// ---- the calls of the listed-leaf pipeline: what the height-field, octree and terrain entry points share of their contact lists ----
+constexpr uint64_t LISTED_ITEM_HARD_CAP = 1u << 26;  // leaves one query may list (7 GB of item workspace); no query yields more contacts
+// The contact list of a whole host call stays on the device until the last chunk has run: room for at most what its n queries can
+// produce (a query adds at most num_max_contacts contacts, and no more than the 2^26 leaves it may list).  No list asked for: 0
+inline size_t listed_contact_cap(const hfcl_contact* contacts, size_t max_contacts_total, size_t n, const hfcl_collision_request* req) {
+  return contacts ? std::min(max_contacts_total, n * size_t(std::min<uint64_t>(req->num_max_contacts, LISTED_ITEM_HARD_CAP))) : 0;
+}
+// After the last chunk of a call: its contact count (w.d_running) read through w.h_words[1] -- st is waited for -- into *n_contacts_out
+// where given; contacts: then the stored ones, at most ccap, from w.s_contacts to the host.  The first HIP error, or hipSuccess
+template <class Ws>
+hipError_t listed_contacts_back(Ws& w, hipStream_t st, size_t* n_contacts_out, hfcl_contact* contacts = nullptr, size_t ccap = 0) {
+  hipError_t e = hipMemcpyAsync(w.h_words.get() + 1, w.d_running, sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return e;
+  const size_t total = size_t(w.h_words[1]);
+  if (n_contacts_out) *n_contacts_out = total;
+  const size_t stored = contacts ? std::min(total, ccap) : 0;
+  return stored ? hipMemcpy(contacts, w.s_contacts, stored * sizeof(hfcl_contact), hipMemcpyDeviceToHost) : hipSuccess;
+}

@@ -2437,7 +2437,7 @@ int hfcl_scene_nearest_device_f32(hfcl_scene* s, const float* d_object_pose, siz
 
 // ---- a height-field terrain under the moving objects (include/hppfcl_amd_terrain.h) ----------------------------------------------------
 int hfcl_scene_set_terrain(hfcl_scene* s, uint32_t hfield, const double* tf_terrain, const uint32_t* objects, size_t n_terrain_objects) {
-  if (const int no_device = hf_no_device()) return no_device;
+  if (const int rc = no_device()) return rc;
   const char* who = "hfcl_scene_set_terrain";
   if (const int rc = groups_scene(who, s)) return rc;
   hfcl_lib* lib = s->lib;
@@ -2489,7 +2489,7 @@ int hfcl_scene_set_terrain(hfcl_scene* s, uint32_t hfield, const double* tf_terr
   return HFCL_OK;
 }
 int hfcl_scene_clear_terrain(hfcl_scene* s) {
-  if (const int no_device = hf_no_device()) return no_device;
+  if (const int rc = no_device()) return rc;
   if (const int rc = groups_scene("hfcl_scene_clear_terrain", s)) return rc;
   HIP_TRY(hipSetDevice(s->lib->device));
   s->d_terrain_objects.reset();  // (waits for the device)
@@ -2503,7 +2503,7 @@ size_t hfcl_scene_n_terrain_objects(const hfcl_scene* s) { return s && s->has_te
 int hfcl_scene_collide_terrain_device(hfcl_scene* s, const double* d_moving_tf, size_t n_conf, const hfcl_collision_request* req, hfcl_result* d_out,
                                       double* d_bounds, hfcl_scene_summary* d_summary, hfcl_contact* d_contacts, size_t max_contacts_total,
                                       size_t* n_contacts_out, void* stream) {
-  if (const int no_device = hf_no_device()) return no_device;
+  if (const int rc = no_device()) return rc;
   QParams<double> q;
   bool skip_all = false, nothing = true;
   size_t total = 0;
@@ -2518,18 +2518,14 @@ int hfcl_scene_collide_terrain_device(hfcl_scene* s, const double* d_moving_tf, 
   if (const int rc = terrain_run(s, d_moving_tf, n_conf, req, q, skip_all, d_out, d_bounds, d_summary, d_contacts, max_contacts_total, want_contacts,
                                  nullptr, nullptr, st))
     return rc;
-  if (n_contacts_out && total) {
-    HIP_TRY(hipMemcpyAsync(lib->hf.h_words.get() + 1, lib->hf.d_running, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *n_contacts_out = size_t(lib->hf.h_words[1]);
-  }
+  if (n_contacts_out && total) HIP_TRY(listed_contacts_back(lib->hf.ws, st, n_contacts_out));
   return HFCL_OK;
 }
 
 int hfcl_scene_collide_terrain(hfcl_scene* s, const double* moving_tf, size_t n_conf, const hfcl_collision_request* req, hfcl_result* out,
                                double* bounds, hfcl_scene_summary* summary, hfcl_contact* contacts, size_t max_contacts_total,
                                size_t* n_contacts_out) {
-  if (const int no_device = hf_no_device()) return no_device;
+  if (const int rc = no_device()) return rc;
   const char* who = "hfcl_scene_collide_terrain";
   QParams<double> q;
   bool skip_all = false, nothing = true;
@@ -2539,34 +2535,25 @@ int hfcl_scene_collide_terrain(hfcl_scene* s, const double* moving_tf, size_t n_
     return rc;
   if (nothing) return HFCL_OK;
   hfcl_lib* lib = s->lib;
-  auto& hf = lib->hf;
+  auto& ws = lib->hf.ws;
   HIP_TRY(hipSetDevice(lib->device));
-  if (!hf.st) HIP_TRY(hf.st.create());
-  hipStream_t st = hf.st;
+  if (!ws.st) HIP_TRY(ws.st.create());
+  hipStream_t st = ws.st;
   if (total) {  // the table crosses the link once
     const size_t bytes = n_conf * s->rows() * 12 * sizeof(double);
     HIP_TRY(lib->scene.d_table.grow(bytes));
     HIP_TRY(hipMemcpyAsync(lib->scene.d_table, moving_tf, bytes, hipMemcpyHostToDevice, st));
   }
   const bool want_contacts = contacts || n_contacts_out;
-  // the contact list of the whole call stays on the device until the last chunk has run (hfcl_hfield_collide_batch: at most what the queries can produce)
-  const size_t ccap = contacts ? std::min(max_contacts_total, total * size_t(std::min<uint64_t>(req->num_max_contacts, HF_ITEM_HARD_CAP))) : 0;
-  if (ccap) HIP_TRY(hf.s_contacts.grow(ccap));
+  // the contact list of the whole call stays on the device until the last chunk has run (as hfcl_hfield_collide_batch)
+  const size_t ccap = listed_contact_cap(contacts, max_contacts_total, total, req);
+  if (ccap) HIP_TRY(ws.s_contacts.grow(ccap));
   if (summary) HIP_TRY(s->tw.d_summary.grow(n_conf));
   int rc = terrain_run(s, static_cast<const double*>(lib->scene.d_table.get()), n_conf, req, q, skip_all, nullptr, nullptr,
-                       summary ? s->tw.d_summary.get() : nullptr, ccap ? hf.s_contacts.get() : nullptr, ccap, want_contacts, out, bounds, st);
+                       summary ? s->tw.d_summary.get() : nullptr, ccap ? ws.s_contacts.get() : nullptr, ccap, want_contacts, out, bounds, st);
   if (!rc) {
     bool ok = !summary || hipMemcpyAsync(summary, s->tw.d_summary, n_conf * sizeof(hfcl_scene_summary), hipMemcpyDeviceToHost, st) == hipSuccess;
-    if (ok && want_contacts && total) {
-      ok = hipMemcpyAsync(hf.h_words.get() + 1, hf.d_running, sizeof(uint64_t), hipMemcpyDeviceToHost, st) == hipSuccess;
-      ok = ok && hipStreamSynchronize(st) == hipSuccess;
-      if (ok) {
-        const size_t produced = size_t(hf.h_words[1]);
-        if (n_contacts_out) *n_contacts_out = produced;
-        const size_t stored = std::min(produced, ccap);
-        if (stored) ok = hipMemcpy(contacts, hf.s_contacts, stored * sizeof(hfcl_contact), hipMemcpyDeviceToHost) == hipSuccess;
-      }
-    }
+    if (ok && want_contacts && total) ok = listed_contacts_back(ws, st, n_contacts_out, contacts, ccap) == hipSuccess;
     ok = ok && hipStreamSynchronize(st) == hipSuccess;
     if (!ok) {
       set_error(std::string(who) + ": HIP copy failed");

@@ -5,7 +5,7 @@
 //                    groups to a 64-lane workgroup (the shape of k_bvh_shape_distance).  Per group in LDS: the walk's stack (node, next
 //                    child, box and the eight child-box distances of each level) and a full-capacity EPA polytope.  The loop of a
 //                    group is "advance the walk to the next leaf to solve, or to its end; then solve": the groups of a wave meet at
-//                    the solve, which is the group solver of k_oct_leaf (the group's lanes share a hull's support scan and EPA's face
+//                    the solve, which is the group solver of the octree leaves (hfcl_k_octree.hip) (the group's lanes share a hull's support scan and EPA's face
 //                    work).  When an inner node is pushed, lanes 0..7 compute the box distances of its eight children in one step; the
 //                    comparisons against the minimum are taken serially in index order.  Lane 0 writes the record.  No atomics, no
 //                    workspace, no read-back.
@@ -15,19 +15,6 @@
 #include "hfcl_octree_distance.hpp"
 
 using namespace hfcl;
-
-// support of the solid in its own frame, evaluated by the lane group (NoSweptSphere): as OctGroupSolid of hfcl_k_octree.hip
-struct OctDistGroupSolid {
-  DShape<double> s;
-  HullRegs<double, BS_W> h;
-  const double* v;
-  int lig;
-  __device__ __forceinline__ V3<double> operator()(const V3<double>& d) const {
-    if (s.kind != K_CONVEX) return prim_support(s, d);
-    if (s.num_points > uint32_t(HULL_MAX)) return scan_support<double, BS_W>(v, s.num_points, d, lig);
-    return h.support(d, lig);
-  }
-};
 
 __global__ void __launch_bounds__(64) k_oct_distance(OctDistArgs a) {
   constexpr int G = 64 / BS_W;
@@ -47,11 +34,8 @@ __global__ void __launch_bounds__(64) k_oct_distance(OctDistArgs a) {
       continue;
     }
     const DOctree tr = a.trees[t];
-    OctDistGroupSolid solid;
-    solid.s = a.shapes[sid];
-    solid.v = a.verts + 3 * size_t(solid.s.vertex_offset);
-    solid.lig = lig;
-    if (solid.s.kind == K_CONVEX && solid.s.num_points <= uint32_t(HULL_MAX)) solid.h.load(solid.v, solid.s.num_points, lig);
+    GroupSolid solid;  // (hfcl_listed.hpp: the group's support of the solid, as k_listed_leaf)
+    solid.load(a, uint32_t(i), lig);
     const Pose<double> tft = load_pose(a.tf_t, i), tfs = load_pose(a.tf_s, i);
     OctDistResult<double> r;
     bool overflow;

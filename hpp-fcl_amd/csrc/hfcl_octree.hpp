@@ -20,6 +20,7 @@
 #include "../../include/hppfcl_amd_octree.h"
 #include "hfcl_bvh.hpp"
 #include "hfcl_pair.hpp"
+#include "hfcl_listed.hpp"
 
 namespace hfcl {
 
@@ -433,46 +434,21 @@ HFCL_HD void oct_skipped_record(hfcl_result* rec, double* dlb_out, bool swapped)
 }
 
 // ---- the kernels' parameter block (hfcl_k_octree.hip) ---------------------------------------------------------------------------
-// A chunk of m queries of a call: the per-query arrays point at the chunk's first query.
-struct OctArgs {
-  const DShape<double>* shapes;
-  const double* verts;
+// What a chunk of octree queries adds to the pipeline's block (hfcl_listed.hpp; tf_c: the trees' poses)
+struct OctArgs : ListedArgs {
   const double* local_boxes;  // 6 doubles a shape of the library
-  uint32_t n_shapes, n_trees;
+  uint32_t n_trees;
   const DOctree* trees;
   const hfcl_octree_node* nodes;
   const uint32_t* octree;
-  const uint32_t* shape;
-  const double* tf_t;
-  const double* tf_s;
-  const uint8_t* swapped;  // nullptr: none
-  uint32_t m, pair0;       // queries of the chunk; index of its first query in the call (hfcl_contact::pair)
-  QParams<double> q;
-  double bd2;              // break_distance^2
-  uint32_t num_max_contacts;
-  int skip_all;            // security_margin == -inf
-  uint32_t* counts;        // m: listed leaves of a query
-  uint64_t* offsets;       // m + 1: where a query's items start
-  double* box_total;       // m: the minimum over all box bounds of a query's walk
   OctItem<double>* items;
   OctLeafOut<double>* leaves;
-  uint64_t n_items;
-  uint32_t* ccounts;       // m: contacts of a query
-  uint64_t* coffsets;      // m + 1: where they go in the call's contact list
-  uint64_t* running;       // contacts of the chunks before this one, then of this one too
-  hfcl_result* out;
-  double* dlb;             // nullptr or m
-  hfcl_contact* contacts;  // nullptr or contacts_cap records
-  uint64_t contacts_cap;
 };
 
 }  // namespace hfcl
 
 #if defined(__HIPCC__)
-// Launches of one chunk, in stream order; no atomics, no kernel waits for another workgroup.  names / e0 / e1: timing slots (e0 == nullptr: none)
-void launch_oct_count(hipStream_t st, const hfcl::OctArgs& a);  // k_oct_walk<count>, k_hf_scan: a.counts, a.offsets (a.offsets[m] = the items)
+// Launches of one chunk (hfcl_k_octree.hip: launch_listed_count / launch_listed_solve of hfcl_listed.hpp for this kind)
+void launch_oct_count(hipStream_t st, const hfcl::OctArgs& a);
 void launch_oct_solve(hipStream_t st, const hfcl::OctArgs& a, int max_blocks, bool want_contacts, const char** names, hipEvent_t* e0, hipEvent_t* e1);
-constexpr int OCT_TIMED_KERNELS = 5;
-// hfcl_k_hfield.hip: k_hf_scan on its own -- the exclusive scan of m counts (on top of *running where given), offsets[m] = the total
-void launch_hf_scan(hipStream_t st, const uint32_t* counts, uint64_t* offsets, uint32_t m, uint64_t* running);
 #endif

@@ -363,6 +363,23 @@ def _dptr(x):
     return C.c_void_p(x.data_ptr())
 
 
+def _listed_arrays(ids, shape, tf_container, tf_shape, swapped):
+    """The host arrays of a height-field / octree batch as the library takes them: (ids, shape, container poses, shape poses, swapped or
+    None, n)."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    shape = np.ascontiguousarray(shape, dtype=np.uint32)
+    tfc = np.ascontiguousarray(tf_container, dtype=np.float64).reshape(-1, 12)
+    tfs = np.ascontiguousarray(tf_shape, dtype=np.float64).reshape(-1, 12)
+    n = len(ids)
+    if not (len(shape) == len(tfc) == len(tfs) == n):
+        raise ValueError("batch arrays must have equal length")
+    if swapped is not None:
+        swapped = np.ascontiguousarray(swapped, dtype=np.uint8)
+        if len(swapped) != n:
+            raise ValueError("swapped: one byte per query")
+    return ids, shape, tfc, tfs, swapped, n
+
+
 class Library:
     """hfcl_lib: a shape library resident on one GPU."""
 
@@ -439,17 +456,7 @@ class Library:
         """Batched collide(HeightField<AABB>, solid) -- swapped[i] = 1: collide(solid, HeightField) -- from host arrays.  Returns
         (records, distance_lower_bound or None, contacts[CONTACT_DTYPE], n_produced)."""
         req = req or abi.default_collision_request()
-        hfield = np.ascontiguousarray(hfield, dtype=np.uint32)
-        shape = np.ascontiguousarray(shape, dtype=np.uint32)
-        tfh = np.ascontiguousarray(tf_hfield, dtype=np.float64).reshape(-1, 12)
-        tfs = np.ascontiguousarray(tf_shape, dtype=np.float64).reshape(-1, 12)
-        n = len(hfield)
-        if not (len(shape) == len(tfh) == len(tfs) == n):
-            raise ValueError("batch arrays must have equal length")
-        if swapped is not None:
-            swapped = np.ascontiguousarray(swapped, dtype=np.uint8)
-            if len(swapped) != n:
-                raise ValueError("swapped: one byte per query")
+        hfield, shape, tfh, tfs, swapped, n = _listed_arrays(hfield, shape, tf_hfield, tf_shape, swapped)
         out = np.zeros(n, dtype=abi.RESULT_DTYPE)
         dlb = np.zeros(n) if want_bound else None
         contacts = np.zeros(int(max_contacts), dtype=abi.CONTACT_DTYPE)
@@ -503,17 +510,7 @@ class Library:
         with the octree-first result (bit 23 of the status alone changes) -- from host arrays.  Returns (records,
         distance_lower_bound or None, contacts[CONTACT_DTYPE], n_produced)."""
         req = req or abi.default_collision_request()
-        octree = np.ascontiguousarray(octree, dtype=np.uint32)
-        shape = np.ascontiguousarray(shape, dtype=np.uint32)
-        tft = np.ascontiguousarray(tf_octree, dtype=np.float64).reshape(-1, 12)
-        tfs = np.ascontiguousarray(tf_shape, dtype=np.float64).reshape(-1, 12)
-        n = len(octree)
-        if not (len(shape) == len(tft) == len(tfs) == n):
-            raise ValueError("batch arrays must have equal length")
-        if swapped is not None:
-            swapped = np.ascontiguousarray(swapped, dtype=np.uint8)
-            if len(swapped) != n:
-                raise ValueError("swapped: one byte per query")
+        octree, shape, tft, tfs, swapped, n = _listed_arrays(octree, shape, tf_octree, tf_shape, swapped)
         out = np.zeros(n, dtype=abi.RESULT_DTYPE)
         dlb = np.zeros(n) if want_bound else None
         contacts = np.zeros(int(max_contacts), dtype=abi.CONTACT_DTYPE)
@@ -540,17 +537,7 @@ class Library:
         23 of the status alone changes).  Returns the records, or (records, n_visited) -- the leaves each walk solved -- when
         want_visited."""
         req = req or abi.default_distance_request()
-        octree = np.ascontiguousarray(octree, dtype=np.uint32)
-        shape = np.ascontiguousarray(shape, dtype=np.uint32)
-        tft = np.ascontiguousarray(tf_octree, dtype=np.float64).reshape(-1, 12)
-        tfs = np.ascontiguousarray(tf_shape, dtype=np.float64).reshape(-1, 12)
-        n = len(octree)
-        if not (len(shape) == len(tft) == len(tfs) == n):
-            raise ValueError("batch arrays must have equal length")
-        if swapped is not None:
-            swapped = np.ascontiguousarray(swapped, dtype=np.uint8)
-            if len(swapped) != n:
-                raise ValueError("swapped: one byte per query")
+        octree, shape, tft, tfs, swapped, n = _listed_arrays(octree, shape, tf_octree, tf_shape, swapped)
         out = np.zeros(n, dtype=abi.RESULT_DTYPE)
         visited = np.zeros(n, dtype=np.uint32) if want_visited else None
         _check(dll().hfcl_octree_distance_batch(self._h, abi.ptr(octree), abi.ptr(shape), abi.ptr(tft), abi.ptr(tfs), C.c_size_t(n),
