@@ -1,4 +1,4 @@
-// hfcl_dev.hpp -- what the kernel translation units (hfcl_k_gjk.hip, hfcl_k_epa.hip, hfcl_k_bvh.hip) and the host side
+// hfcl_dev.hpp -- what the kernel translation units (hfcl_k_gjk.hip, hfcl_k_epa.hip, the mesh units hfcl_k_bvh.hip / hfcl_k_bvhs.hip over hfcl_mesh.hpp) and the host side
 // (hfcl_host.hip) share: bucket ids, kernel parameter blocks, result-record writers, lane-group primitives, the
 // register-resident hull, tier constants of the EPA kernels and the BVH views.  gfx950 / wave64 only.
 #pragma once
@@ -688,7 +688,7 @@ struct BvhParams {
   uint32_t* contacts_count;
 };
 
-// ---- long mesh x mesh traversals cut into tasks (k_bvh_collide / k_bvh_combine, hfcl_k_bvh.hip) ----
+// ---- long mesh x mesh traversals cut into tasks (k_bvh_collide / k_bvh_combine, hfcl_k_bvh.hip; bvh_sum / bvh_moot, hfcl_mesh.hpp) ----
 struct BvhTask {
   uint32_t pair;    // the query
   uint32_t parent;  // summary slot of the unit that made the task

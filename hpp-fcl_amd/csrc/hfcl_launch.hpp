@@ -23,7 +23,8 @@
 //                    k_shape_obb<T>, k_bvh_collide<T, ., ., SOLID>, k_bvh_shape_coop<T>, k_bvh_shape_finish<T>
 //                                     BVHModel<OBBRSS> x convex solid, first-contact collide(): the solids' OBBs, the walk
 //                                     (lane, then wave), the leaves that need EPA
-//                    k_shape_obbrss<T>, k_bvh_shape_distance_lane<T>, k_bvh_shape_distance_pool<T>   ... distance()
+//   hfcl_k_bvhs.hip  k_shape_obbrss<T>, k_bvh_shape_distance_lane<T>, k_bvh_shape_distance_pool<T>   ... distance() (a source of its own;
+//                                     hfcl_mesh.hpp: what it shares with hfcl_k_bvh.hip, k_bvh_shape_finish among it)
 //                                     (k_bvh_shape_distance_coop<T>: the ordered form, libraries with a Plane / Halfspace)
 //                    k_bvh_shape<T> / k_bvh_shape_distance<T>   the same rows, one 16-lane group per query: requests that
 //                                     keep walking after a contact, models deeper than the lanes' stacks
