@@ -675,7 +675,8 @@ def _context():
 def _check_pair(o1, o2, for_distance):
     t1, t2 = isinstance(o1, OcTree), isinstance(o2, OcTree)
     if (t1 or t2) and not for_distance:
-        if t1 != t2 and engine.octree_pair_supported(int((o2 if t1 else o1).getNodeType())):
+        other = int((o2 if t1 else o1).getNodeType())
+        if t1 != t2 and (engine.octree_pair_supported(other) or engine.octree_mesh_pair_supported(other)):  # a solid, or a BVHModel<OBBRSS>
             return
         raise ValueError("Collision function between node type %d and node type %d is not yet supported." % (o1.getNodeType(), o2.getNodeType()))
     if t1 or t2:  # distance(): an octree against one of the seven convex solids, either order (hppfcl_amd_octree_distance.h)
@@ -768,7 +769,7 @@ def _collide_hfield(o1, tf1, o2, tf2, request, result):
 
 
 def _collide_octree(o1, tf1, o2, tf2, request, result):
-    """(OcTree, solid) or (solid, OcTree) through hfcl_octree_collide_batch.  Either order gets the octree-first result (the reference
+    """(OcTree, solid or mesh) or (solid or mesh, OcTree) through hfcl_octree_collide_batch / hfcl_octree_mesh_collide_batch.  Either order gets the octree-first result (the reference
     does not swap it back: src/collision.cpp:92-108 has no octree branch): the tree is o1 of every contact, its node b1."""
     swapped = not isinstance(o1, OcTree)
     tree, tft, solid, tfs = (o2, tf2, o1, tf1) if swapped else (o1, tf1, o2, tf2)
@@ -776,9 +777,12 @@ def _collide_octree(o1, tf1, o2, tf2, request, result):
     sid, tid = ctx.add(solid), ctx.add_octree(tree)
     lib = ctx.library()
     cap = int(min(request.num_max_contacts, 1 << 16))
+    # a BVHModel<OBBRSS> goes through hfcl_octree_mesh_collide_batch (hppfcl_amd_octree_mesh.h): the same record conventions, the
+    # triangle in b2, the solver's own points in the contacts
+    call = lib.octree_mesh_collide if isinstance(solid, BVHModelOBBRSS) else lib.octree_collide
     try:
-        rec, dlb, contacts, _ = lib.octree_collide([tid], [sid], tft._abi().reshape(1, 12), tfs._abi().reshape(1, 12), request._abi(),
-                                                   swapped=[1 if swapped else 0], max_contacts=cap)
+        rec, dlb, contacts, _ = call([tid], [sid], tft._abi().reshape(1, 12), tfs._abi().reshape(1, 12), request._abi(),
+                                     swapped=[1 if swapped else 0], max_contacts=cap)
     except engine.EngineError as e:
         if e.code in (abi.ERR_INVALID_ARGUMENT, abi.ERR_UNSUPPORTED_PAIR, abi.ERR_LIMIT):
             raise ValueError(str(e))
@@ -787,7 +791,7 @@ def _collide_octree(o1, tf1, o2, tf2, request, result):
         return result.numContacts()
     if dlb[0] < result.distance_lower_bound:
         result.distance_lower_bound = float(dlb[0])
-        if rec[0]["num_contacts"] == 0:  # (a record with a contact carries the contact's rebuilt points, not the result's)
+        if rec[0]["num_contacts"] == 0:  # (a record with a contact carries the contact's points, not the result's)
             result.normal = np.array(rec[0]["normal"])
             result.nearest_points = [np.array(rec[0]["p1"]), np.array(rec[0]["p2"])]
     for c in contacts:

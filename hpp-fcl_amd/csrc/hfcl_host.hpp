@@ -24,6 +24,7 @@
 #include "hfcl_pairs.hpp"
 #include "hfcl_hfield.hpp"
 #include "hfcl_octree.hpp"
+#include "hfcl_octree_mesh.hpp"
 #include "hfcl_own.hpp"
 
 __attribute__((visibility("hidden"))) void set_error(const std::string& s);  // the calling thread's hfcl_last_error()
@@ -399,6 +400,10 @@ struct hfcl_lib {
     DevBuf<DOctree> d_trees;
     DevBuf<hfcl_octree_node> d_nodes;
     ListedWs<OctItem<double>, OctLeafOut<double>> ws;
+    // ... against meshes (hfcl_octree_mesh_collide_batch*): a workspace of its own kind of items, and the levels of every registered
+    // mesh's BVH (hfcl_octree_mesh.hpp: octm_bvh_depth), computed by the first call that needs them
+    ListedWs<OctMeshItem<double>, OctMeshLeafOut<double>> ws_mesh;
+    std::vector<uint32_t> mesh_depth;
   } oct;
   // local AABB of every library shape (hfcl_cull.hpp: shape_local_box; BVH models: the box of their vertices), 6 doubles each, rebuilt when
   // shapes or meshes were registered since (hfcl_lib_set_shapes, hfcl_lib_add_bvh)

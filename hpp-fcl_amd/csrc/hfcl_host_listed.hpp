@@ -61,8 +61,11 @@ int listed_run(hfcl_lib* lib, const uint32_t* d_id, const uint32_t* d_shape, con
   a.running = w.d_running;
   a.contacts = d_contacts;
   a.contacts_cap = d_contacts ? contacts_cap : 0;
+  // A chunk that was cut leaves the counts of the queries behind the cut in place: `left` of them from w.d_counts + at on.  The next
+  // chunk is those queries and scans their counts again instead of walking them (and every query still to come) once more
+  size_t left = 0, at = 0;
   for (size_t q0 = 0; q0 < n;) {  // (every pass takes at least one query)
-    size_t m = std::min(chunk, n - q0);
+    size_t m = left ? left : std::min(chunk, n - q0);
     K::ids(a, d_id + q0);
     a.shape = d_shape + q0;
     a.tf_c = d_tfc + 12 * q0;
@@ -75,7 +78,15 @@ int listed_run(hfcl_lib* lib, const uint32_t* d_id, const uint32_t* d_shape, con
     a.items = w.d_items;
     a.leaves = w.d_leaves;
     a.n_items = 0;
-    K::count(st, a);
+    if (left) {
+      a.counts = w.d_counts.get() + at;
+      launch_hf_scan(st, a.counts, a.offsets, a.m, nullptr);
+    } else {
+      a.counts = w.d_counts;
+      at = 0;
+      K::count(st, a);
+    }
+    const size_t counted = m;
     // the one read-back of a chunk: its item count (the item workspace is sized by it); a chunk that lists too much is cut at a query
     uint64_t total = 0;
     for (;;) {  // (m at least halves per pass)
@@ -102,6 +113,8 @@ int listed_run(hfcl_lib* lib, const uint32_t* d_id, const uint32_t* d_shape, con
     if (timed)
       for (int k = 0; k < LISTED_TIMED_KERNELS; ++k) lib->timers[size_t(k)].name = names[k];
     q0 += m;
+    left = counted - m;
+    at += m;
   }
   HIP_TRY(hipGetLastError());
   return HFCL_OK;

@@ -3,6 +3,8 @@
 // checks, and hfcl_octree_collide_batch* -- the entry points and the chunk driver of the listed-leaf pipeline (hfcl_host_listed.hpp)
 // for OctHost, the kind defined here.  At the end hfcl_octree_distance_batch* (hppfcl_amd_octree_distance.h; the kernel:
 // hfcl_k_octree_distance.hip): one launch per chunk, no workspace, no read-back; its host form is staged as the collide call's.
+// Last hfcl_octree_mesh_collide_batch* (hppfcl_amd_octree_mesh.h; the kernels: hfcl_k_octree_mesh.hip): the same driver for OctMeshHost, on a
+// workspace of its own, behind a check of the meshes' BVH depths.
 #include "hfcl_host_listed.hpp"
 #include "hfcl_octree_distance.hpp"
 
@@ -306,6 +308,103 @@ int hfcl_octree_distance_batch(hfcl_lib* lib, const uint32_t* octree, const uint
   });
   hipStreamSynchronize(w.st);
   return rc;
+}
+
+}  // extern "C"
+
+// ---- collide() against meshes (hppfcl_amd_octree_mesh.h; the kernels: hfcl_k_octree_mesh.hip) ---------------------------------------
+namespace {
+
+// the levels of every registered mesh's BVH, computed once per mesh
+void octm_depths(hfcl_lib* lib) {
+  auto& depth = lib->oct.mesh_depth;
+  for (size_t k = depth.size(); k < lib->h_meshes.size(); ++k) {
+    const hfcl_bvh_node* nodes = lib->h_bvh_nodes.data() + lib->h_meshes[k].node_off;
+    depth.push_back(hfcl::octm_bvh_depth(lib->h_meshes[k].n_nodes, [&](uint32_t i) { return nodes[i].first_child; }));
+  }
+}
+int octm_too_deep(const char* who, size_t mesh, uint32_t depth) {
+  set_error(std::string(who) + ": the BVH of mesh " + std::to_string(mesh) + " has " + (depth == 0xFFFFFFFFu ? std::string("unbounded") : std::to_string(depth)) +
+            " levels (limit " + std::to_string(HFCL_OCTREE_MESH_MAX_BVH_DEPTH) + ")");
+  return HFCL_ERR_LIMIT;
+}
+
+struct OctMeshHost {
+  using Args = hfcl::OctMeshArgs;
+  static constexpr const char* limit_who = "hfcl_octree_mesh_collide_batch";
+  static constexpr const char* noun = "octree";
+  static constexpr const char* a_noun = "an octree";
+  static auto& ws(hfcl_lib* lib) { return lib->oct.ws_mesh; }
+  static size_t n_containers(const hfcl_lib* lib) { return lib->oct.h_trees.size(); }
+  static int upload(hfcl_lib* lib) {
+    const int rc = upload_octrees(lib);
+    return rc ? rc : upload_bvh(lib);
+  }
+  static void fill(hfcl_lib* lib, Args& a) {
+    a.n_trees = uint32_t(lib->oct.h_trees.size());
+    a.trees = lib->oct.d_trees;
+    a.nodes = lib->oct.d_nodes;
+    a.n_meshes = uint32_t(lib->h_meshes.size());
+    a.mnodes = lib->d_nodes64;
+    a.mverts = lib->d_bverts64;
+    a.mtris = lib->d_btris;
+    a.meshes = lib->d_meshes;
+  }
+  static void ids(Args& a, const uint32_t* p) { a.octree = p; }
+  static constexpr auto chunk = oct_chunk;
+  static uint64_t item_cap(const hfcl_lib* lib) { return lib->opt.octree_items ? lib->opt.octree_items : LISTED_ITEM_SOFT_CAP; }
+  static constexpr auto request = oct_request;
+  static constexpr auto supported = hfcl_octree_mesh_pair_supported;
+  static constexpr auto count = launch_octm_count;
+  static constexpr auto solve = launch_octm_solve;
+};
+
+}  // namespace
+
+extern "C" {
+
+int hfcl_octree_mesh_pair_supported(int32_t t) { return t == HFCL_BV_OBBRSS ? 1 : 0; }
+
+int hfcl_octree_mesh_collide_batch_device(hfcl_lib* lib, const uint32_t* d_octree, const uint32_t* d_shape, const double* d_tf_octree,
+                                          const double* d_tf_mesh, size_t n, const uint8_t* d_swapped, const hfcl_collision_request* req,
+                                          hfcl_result* d_out, double* d_distance_lower_bound, hfcl_contact* d_contacts, size_t max_contacts_total,
+                                          size_t* n_contacts_out, void* stream) {
+  const char* who = "hfcl_octree_mesh_collide_batch_device";
+  if (lib && req && n && no_device() == HFCL_OK) {  // the ids are not visible here: no registered mesh may be deeper than the walk's stack
+    QParams<double> q;
+    bool skip_all = false;
+    if (int rc = oct_request(who, req, q, skip_all)) return rc;
+    octm_depths(lib);
+    for (size_t k = 0; k < lib->oct.mesh_depth.size(); ++k)
+      if (lib->oct.mesh_depth[k] > HFCL_OCTREE_MESH_MAX_BVH_DEPTH) return octm_too_deep(who, k, lib->oct.mesh_depth[k]);
+  }
+  return listed_collide_device<OctMeshHost>(who, lib, d_octree, d_shape, d_tf_octree, d_tf_mesh, n, d_swapped, req, d_out, d_distance_lower_bound,
+                                            d_contacts, max_contacts_total, n_contacts_out, (hipStream_t)stream);
+}
+
+int hfcl_octree_mesh_collide_batch(hfcl_lib* lib, const uint32_t* octree, const uint32_t* shape, const double* tf_octree, const double* tf_mesh, size_t n,
+                                   const uint8_t* swapped, const hfcl_collision_request* req, hfcl_result* out, double* distance_lower_bound,
+                                   hfcl_contact* contacts, size_t max_contacts_total, size_t* n_contacts_out) {
+  const char* who = "hfcl_octree_mesh_collide_batch";
+  if (lib && req && n && shape && no_device() == HFCL_OK) {  // a mesh named by the batch that is deeper than the walk's stack: nothing is written
+    QParams<double> q;
+    bool skip_all = false;
+    if (int rc = oct_request(who, req, q, skip_all)) return rc;
+    octm_depths(lib);
+    for (size_t i = 0; i < n; ++i) {
+      if (shape[i] >= lib->n_shapes || lib->h_shapes[shape[i]].type != HFCL_BV_OBBRSS) continue;  // (refused below, in the order of every host form)
+      const size_t k = lib->h_shapes[shape[i]].bvh_index;
+      if (k < lib->oct.mesh_depth.size() && lib->oct.mesh_depth[k] > HFCL_OCTREE_MESH_MAX_BVH_DEPTH) return octm_too_deep(who, k, lib->oct.mesh_depth[k]);
+    }
+  }
+  if (lib && shape && n && no_device() == HFCL_OK)  // a mesh row that names no registered mesh
+    for (size_t i = 0; i < n; ++i)
+      if (shape[i] < lib->n_shapes && lib->h_shapes[shape[i]].type == HFCL_BV_OBBRSS && size_t(lib->h_shapes[shape[i]].bvh_index) >= lib->h_meshes.size()) {
+        set_error(std::string(who) + ": bvh_index outside the registered meshes at query " + std::to_string(i));
+        return HFCL_ERR_INVALID_ARGUMENT;
+      }
+  return listed_collide_host<OctMeshHost>(who, lib, octree, shape, tf_octree, tf_mesh, n, swapped, req, out, distance_lower_bound, contacts,
+                                          max_contacts_total, n_contacts_out);
 }
 
 }  // extern "C"

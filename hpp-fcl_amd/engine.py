@@ -95,6 +95,9 @@ OCTREE_SYMBOLS = [
 ]
 # include/hppfcl_amd_octree_distance.h (included by hppfcl_amd.h): distance() between a registered OcTree and a convex solid
 OCTREE_DISTANCE_SYMBOLS = ["hfcl_octree_distance_pair_supported", "hfcl_octree_distance_batch", "hfcl_octree_distance_batch_device"]
+# include/hppfcl_amd_octree_mesh.h (included by hppfcl_amd.h): collide() between a registered OcTree and a registered BVHModel<OBBRSS>
+OCTREE_MESH_SYMBOLS = ["hfcl_octree_mesh_pair_supported", "hfcl_octree_mesh_collide_batch", "hfcl_octree_mesh_collide_batch_device"]
+OCTREE_MESH_MAX_BVH_DEPTH = 64  # HFCL_OCTREE_MESH_MAX_BVH_DEPTH
 
 
 class EngineError(RuntimeError):
@@ -221,6 +224,11 @@ def octree_pair_supported(node_type):
 def octree_distance_pair_supported(node_type):
     """hfcl_octree_distance_pair_supported: does distance() have an octree row for a solid of this node type?"""
     return bool(dll().hfcl_octree_distance_pair_supported(C.c_int32(int(node_type))))
+
+
+def octree_mesh_pair_supported(node_type):
+    """hfcl_octree_mesh_pair_supported: does collide() have an octree row for a mesh of this node type?  (BV_OBBRSS alone)"""
+    return bool(dll().hfcl_octree_mesh_pair_supported(C.c_int32(int(node_type))))
 
 
 def _octree_nodes(nodes):
@@ -529,6 +537,33 @@ class Library:
                                                       C.c_size_t(n), _dptr(d_swapped), C.byref(req), _dptr(d_out), _dptr(d_bound),
                                                       _dptr(d_contacts), C.c_size_t(int(max_contacts)), C.byref(nc) if want_count else None,
                                                       C.c_void_p(stream)))
+        return int(nc.value) if want_count else None
+
+    def octree_mesh_collide(self, octree, shape, tf_octree, tf_mesh, req=None, swapped=None, max_contacts=0, want_bound=True):
+        """Batched collide(OcTree, BVHModel<OBBRSS>) from host arrays: shape[i] is a BV_OBBRSS row of the library whose bvh_index names
+        a mesh registered with add_bvh.  swapped[i] = 1: the caller's order was collide(mesh, OcTree), which the reference answers with
+        the octree-first result (bit 23 of the status alone changes).  Returns (records, distance_lower_bound or None,
+        contacts[CONTACT_DTYPE] -- b1 the octree node, b2 the triangle --, n_produced)."""
+        req = req or abi.default_collision_request()
+        octree, shape, tft, tfm, swapped, n = _listed_arrays(octree, shape, tf_octree, tf_mesh, swapped)
+        out = np.zeros(n, dtype=abi.RESULT_DTYPE)
+        dlb = np.zeros(n) if want_bound else None
+        contacts = np.zeros(int(max_contacts), dtype=abi.CONTACT_DTYPE)
+        nc = C.c_size_t(0)
+        _check(dll().hfcl_octree_mesh_collide_batch(self._h, abi.ptr(octree), abi.ptr(shape), abi.ptr(tft), abi.ptr(tfm), C.c_size_t(n),
+                                                    abi.ptr(swapped), C.byref(req), abi.ptr(out), abi.ptr(dlb),
+                                                    abi.ptr(contacts) if max_contacts else None, C.c_size_t(int(max_contacts)), C.byref(nc)))
+        return out, dlb, contacts[:min(nc.value, int(max_contacts))], int(nc.value)
+
+    def octree_mesh_collide_device(self, d_octree, d_shape, d_tf_octree, d_tf_mesh, n, req, d_out, d_swapped=None, d_bound=None, d_contacts=None,
+                                   max_contacts=0, want_count=False, stream=0):
+        """The same call on device pointers (torch tensors or raw pointers).  Returns the number of contacts produced when want_count
+        (the call then waits for the stream), else None."""
+        nc = C.c_size_t(0)
+        _check(dll().hfcl_octree_mesh_collide_batch_device(self._h, _dptr(d_octree), _dptr(d_shape), _dptr(d_tf_octree), _dptr(d_tf_mesh),
+                                                           C.c_size_t(n), _dptr(d_swapped), C.byref(req), _dptr(d_out), _dptr(d_bound),
+                                                           _dptr(d_contacts), C.c_size_t(int(max_contacts)), C.byref(nc) if want_count else None,
+                                                           C.c_void_p(stream)))
         return int(nc.value) if want_count else None
 
     def octree_distance(self, octree, shape, tf_octree, tf_shape, req=None, swapped=None, want_visited=False):

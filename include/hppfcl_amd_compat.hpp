@@ -1163,6 +1163,23 @@ class OcTreeBatch {
   void collide(const std::vector<std::pair<uint32_t, uint32_t>>& tree_solid, const std::vector<Transform3f>& tf_tree,
                const std::vector<Transform3f>& tf_solid, const std::vector<uint8_t>& swapped, const CollisionRequest& request,
                std::vector<CollisionResult>& results) {
+    collideWith(hfcl_octree_collide_batch, tree_solid, tf_tree, tf_solid, swapped, request, results);
+  }
+  /// The same for BVHModel<OBBRSS> meshes of the context in the place of the solids (hfcl_octree_mesh_collide_batch,
+  /// hppfcl_amd_octree_mesh.h): query i is collide(tree, mesh), or collide(mesh, tree) where swapped[i].  The tree is o1 of every contact,
+  /// its node b1, the mesh's triangle b2, and the nearest points are the solver's own.
+  void collideMesh(const std::vector<std::pair<uint32_t, uint32_t>>& tree_mesh, const std::vector<Transform3f>& tf_tree,
+                   const std::vector<Transform3f>& tf_mesh, const std::vector<uint8_t>& swapped, const CollisionRequest& request,
+                   std::vector<CollisionResult>& results) {
+    collideWith(hfcl_octree_mesh_collide_batch, tree_mesh, tf_tree, tf_mesh, swapped, request, results);
+  }
+
+ private:
+  typedef int (*CollideCall)(hfcl_lib*, const uint32_t*, const uint32_t*, const double*, const double*, size_t, const uint8_t*,
+                             const hfcl_collision_request*, hfcl_result*, double*, hfcl_contact*, size_t, size_t*);
+  void collideWith(CollideCall call, const std::vector<std::pair<uint32_t, uint32_t>>& tree_solid, const std::vector<Transform3f>& tf_tree,
+                   const std::vector<Transform3f>& tf_solid, const std::vector<uint8_t>& swapped, const CollisionRequest& request,
+                   std::vector<CollisionResult>& results) {
     const size_t n = tree_solid.size();
     if (tf_tree.size() != n || tf_solid.size() != n || (!swapped.empty() && swapped.size() != n))
       throw std::invalid_argument("pairs/poses size mismatch");
@@ -1179,9 +1196,8 @@ class OcTreeBatch {
     int rc = HFCL_OK;
     for (int attempt = 0; attempt < 2; ++attempt) {  // (a list that outgrew the guess: once more with the count)
       contacts_.resize(cap);
-      rc = hfcl_octree_collide_batch(lib, ot.data(), sh.data(), reinterpret_cast<const double*>(tf_tree.data()),
-                                     reinterpret_cast<const double*>(tf_solid.data()), n, swapped.empty() ? nullptr : swapped.data(), &a,
-                                     rec_.data(), bound_.data(), contacts_.data(), cap, &produced);
+      rc = call(lib, ot.data(), sh.data(), reinterpret_cast<const double*>(tf_tree.data()), reinterpret_cast<const double*>(tf_solid.data()), n,
+                swapped.empty() ? nullptr : swapped.data(), &a, rec_.data(), bound_.data(), contacts_.data(), cap, &produced);
       if (rc || produced <= cap) break;
       cap = produced;
     }
@@ -1193,6 +1209,8 @@ class OcTreeBatch {
     for (size_t i = 0; i < n; ++i)
       fill(results[i], rec_[i], bound_[i], trees_[tree_solid[i].first].tree, ctx_.geometry(sh[i]), static_cast<uint32_t>(i), k, request);
   }
+
+ public:
   /// One record into a result that may hold earlier ones: every contact and the call's bound; the result's nearest_points / normal
   /// are set from a record without a contact (one with a contact carries the contact's rebuilt points instead).
   void fill(CollisionResult& res, const hfcl_result& r, double bound, const CollisionGeometry* tree, const CollisionGeometry* solid, uint32_t query,
@@ -1290,7 +1308,8 @@ inline bool is_octree(const CollisionGeometry* g) { return g->getNodeType() == G
 /// does collide() have a function for this pair with an octree in it?
 inline bool octree_pair_supported(const CollisionGeometry* o1, const CollisionGeometry* o2) {
   const bool t1 = is_octree(o1), t2 = is_octree(o2);
-  return t1 != t2 && hfcl_octree_pair_supported((t1 ? o2 : o1)->getNodeType()) != 0;
+  const int other = (t1 ? o2 : o1)->getNodeType();
+  return t1 != t2 && (hfcl_octree_pair_supported(other) != 0 || hfcl_octree_mesh_pair_supported(other) != 0);
 }
 /// ... and distance()?
 inline bool octree_distance_pair_supported(const CollisionGeometry* o1, const CollisionGeometry* o2) {
@@ -1323,14 +1342,17 @@ inline std::size_t collide(const CollisionGeometry* o1, const Transform3f& tf1, 
     hb.fill(result, hb.records()[0], hb.bounds()[0], o1, o2, 0, k, request);
     return result.numContacts();
   }
-  if (amd::is_octree(o1) || amd::is_octree(o2)) {  // an octree against a solid, either order (hppfcl_amd_octree.h)
+  if (amd::is_octree(o1) || amd::is_octree(o2)) {  // an octree against a solid or a mesh, either order (hppfcl_amd_octree.h, hppfcl_amd_octree_mesh.h)
     if (!amd::octree_pair_supported(o1, o2)) throw std::invalid_argument("Collision function between the two node types is not yet supported.");
     const bool swapped = !amd::is_octree(o1);
     amd::OcTreeBatch& ob = amd::default_octree_batch();
     if (ob.numTrees() >= amd::DEFAULT_OCTREE_BATCH_MAX) ob.reset();
     const std::pair<uint32_t, uint32_t> ts(ob.addTree(static_cast<const OcTree*>(swapped ? o2 : o1)), ob.addSolid(swapped ? o1 : o2));
     std::vector<CollisionResult> one;
-    ob.collide({ts}, {swapped ? tf2 : tf1}, {swapped ? tf1 : tf2}, {static_cast<uint8_t>(swapped ? 1 : 0)}, request, one);
+    if (hfcl_octree_mesh_pair_supported((swapped ? o1 : o2)->getNodeType()))  // a BVHModel<OBBRSS> (hppfcl_amd_octree_mesh.h)
+      ob.collideMesh({ts}, {swapped ? tf2 : tf1}, {swapped ? tf1 : tf2}, {static_cast<uint8_t>(swapped ? 1 : 0)}, request, one);
+    else
+      ob.collide({ts}, {swapped ? tf2 : tf1}, {swapped ? tf1 : tf2}, {static_cast<uint8_t>(swapped ? 1 : 0)}, request, one);
     size_t k = 0;
     ob.fill(result, ob.records()[0], ob.bounds()[0], swapped ? o2 : o1, swapped ? o1 : o2, 0, k, request);
     return result.numContacts();

@@ -65,7 +65,7 @@
  * HFCL_ERR_NO_DEVICE, as every compute entry point.
  *
  * Not done: Plane and Halfspace against an octree (their local boxes are unbounded and the OBB conversion yields NaN centres);
- * octree x octree, x mesh, x height field; octrees as scene objects or environments; reading octomap's files; fp32 and hfcl_multi_*
+ * octree x octree, x height field (x mesh: hppfcl_amd_octree_mesh.h); octrees as scene objects or environments; reading octomap's files; fp32 and hfcl_multi_*
  * forms; cached and bounding-volume GJK guesses; a finite distance_upper_bound.  (distance() against the same solids is in
  * hppfcl_amd_octree_distance.h: its pruning depends on the running minimum, so it is the reference's ordered walk, a query per lane
  * group, and not the route below.)
