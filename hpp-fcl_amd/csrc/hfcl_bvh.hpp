@@ -10,7 +10,7 @@
 // The leaves' solvers -- GJK, EPA, the supports, everything of hfcl_pair.hpp and the leaf functions of hfcl_bvh_shape.hpp -- are called
 // from several kernels (the lanes' walk, the waves' continuation, the task levels, the group kernels), each with its own inlined copy;
 // contracted, two copies may fuse a*b+c differently and a GJK run that stops an iteration apart reports a normal 1e-3 away (cylinder
-// caps; profiles/r06_b).  The mesh x solid objects (hfcl_k_bvh.hip as hfcl_k_bvhc.o, hfcl_k_bvhs.hip) are therefore compiled without contraction (Makefile: FLAGS_k_bvhc,
+// caps; profiles/r06_b).  The mesh x solid objects (hfcl_k_bvhc.hip, hfcl_k_bvhs.hip) are therefore compiled without contraction (Makefile: FLAGS_k_bvhc,
 // FLAGS_k_bvhs): every copy is the same arithmetic, and the oracle's.  The mesh x mesh collide() part keeps hipcc's default.
 #include "hfcl_pair.hpp"
 #if !defined(__HIP_DEVICE_COMPILE__)

@@ -630,7 +630,7 @@ HFCL_HD void mesh_shape_collide(const DNode<T>* nodes, const T* mverts, const ui
 
 
 // ---------------------------------------------------------------------------------------
-// The same traversals with one query per LANE (hfcl_k_bvh.hip: k_bvh_collide<SOLID>, hfcl_k_bvhs.hip: k_bvh_shape_distance_lane, and the
+// The same traversals with one query per LANE (hfcl_mesh_collide.hpp: k_bvh_collide<SOLID>, hfcl_k_bvhs.hip: k_bvh_shape_distance_lane, and the
 // kernels that continue their long walks 64 stack entries at a time).
 //
 // The group form above spends a 16-lane group on a walk whose separating-axis tests and (for every solid but a

@@ -1,4 +1,4 @@
-// hfcl_dev.hpp -- what the kernel translation units (hfcl_k_gjk.hip, hfcl_k_epa.hip, the mesh units hfcl_k_bvh.hip / hfcl_k_bvhs.hip over hfcl_mesh.hpp) and the host side
+// hfcl_dev.hpp -- what the kernel translation units (hfcl_k_gjk.hip, hfcl_k_epa.hip, the mesh units hfcl_k_bvh.hip / hfcl_k_bvhc.hip / hfcl_k_bvhs.hip over hfcl_mesh.hpp) and the host side
 // (hfcl_host.hip) share: bucket ids, kernel parameter blocks, result-record writers, lane-group primitives, the
 // register-resident hull, tier constants of the EPA kernels and the BVH views.  gfx950 / wave64 only.
 #pragma once
@@ -688,7 +688,7 @@ struct BvhParams {
   uint32_t* contacts_count;
 };
 
-// ---- long mesh x mesh traversals cut into tasks (k_bvh_collide / k_bvh_combine, hfcl_k_bvh.hip; bvh_sum / bvh_moot, hfcl_mesh.hpp) ----
+// ---- long mesh x mesh traversals cut into tasks (k_bvh_collide / k_bvh_combine, hfcl_mesh_collide.hpp; bvh_sum / bvh_moot, hfcl_mesh.hpp) ----
 struct BvhTask {
   uint32_t pair;    // the query
   uint32_t parent;  // summary slot of the unit that made the task
@@ -717,8 +717,8 @@ struct BvhSum {  // what a unit (query or task) knows when it ends or suspends
 // counters of a split traversal (device words)
 enum { BVH_CTR_TASKS = 0, BVH_CTR_SUSPENDED = 1, BVH_CTR_LEVEL0 = 2 /* [2 + k] = number of tasks made before level k ended */, BVH_CTR_CUT = 15 /* words of BvhSplit::cut_words in use */, BVH_CTR_WORDS = 16 };
 // ---------------------------------------------------------------------------------------
-// Mesh x mesh collide() with the walk and the leaves in kernels of their own (round 6; hfcl_k_bvh.hip: k_bvh_walk, k_tri_leaves,
-// k_bvh_resolve).  collisionRecurse's box tests do not depend on anything a triangle pair reports -- only WHERE the walk ends does (the
+// Mesh x mesh collide() with the walk and the leaves in kernels of their own (round 6; hfcl_mesh_collide.hpp: k_bvh_walk, k_bvh_resolve;
+// hfcl_k_bvh.hip: k_tri_leaves).  collisionRecurse's box tests do not depend on anything a triangle pair reports -- only WHERE the walk ends does (the
 // first contact) -- so a lane can walk ahead of its triangle pairs: it lists the next `k` leaves it meets (with the smallest box bound
 // seen in front of each: the events between two leaves only ever form a minimum), a dense kernel evaluates every listed pair of the
 // batch, one per lane, and a third replays each query's events in the reference's order: bound, witness, first contact.  A query that

@@ -1,7 +1,7 @@
 // hfcl_host.hip -- host side: library object, options, uploads, request set-up, host pipeline and their part of the C-ABI implementation of
 // include/hppfcl_amd.h (one device-resident batch, the dispatcher run_batch: hfcl_host_batch.hip; contact patches: hfcl_host_patch.hip; scene
 // queries and the cull: hfcl_host_scene.hip; the library object itself and what the four units share: hfcl_host.hpp; the host pipeline's chunk
-// plan: hfcl_plan.hpp; the kernels live in hfcl_k_gjk.hip / hfcl_k_epa.hip / hfcl_k_bvh.hip / hfcl_k_bvhs.hip, see hfcl_launch.hpp).
+// plan: hfcl_plan.hpp; the kernels live in hfcl_k_gjk.hip / hfcl_k_epa.hip / hfcl_k_bvh.hip / hfcl_k_bvhc.hip / hfcl_k_bvhs.hip, see hfcl_launch.hpp).
 // No CPU fallback anywhere in these files: every compute entry point needs a HIP device and fails loudly without one.
 //
 // Kernel map (pair buckets follow the reference's dispatch table,

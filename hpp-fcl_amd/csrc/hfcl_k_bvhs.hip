@@ -6,9 +6,9 @@
 // as for mesh x mesh (hfcl_k_bvhd.hip).
 #include "hfcl_mesh.hpp"
 
-constexpr int MESH_UNIT_PART = 2;  // what this object's copy of a kernel two mesh objects launch carries (hfcl_mesh.hpp; hfcl_k_bvh.hip: parts 1 and 3)
+constexpr int MESH_UNIT_PART = 2;  // what this object's copy of a kernel two mesh objects launch carries (hfcl_mesh.hpp; hfcl_k_bvh.hip: 1, hfcl_k_bvhc.hip: 3)
 
-// k_shape_obbrss: computeBV<OBBRSS, S>(solid, tf) per query, by pair, as k_shape_obb's for collide() (hfcl_k_bvh.hip) -- for
+// k_shape_obbrss: computeBV<OBBRSS, S>(solid, tf) per query, by pair, as k_shape_obb's for collide() (hfcl_k_bvhc.hip) -- for
 // distance() the solid's OBBRSS itself (rss_lower_bound takes the mesh pose as an argument)
 template <typename T>
 __global__ void __launch_bounds__(256) k_shape_obbrss(Work wk, LibView<T> lib, IO<T> io) {

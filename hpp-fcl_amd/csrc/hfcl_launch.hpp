@@ -11,7 +11,8 @@
 //                    k_unsupported<T>, k_fill_skipped
 //   hfcl_k_epa.hip   k_epa<T,WE,CAP,TIER>, k_epa_stream<T,WE,CAP>   EPA on the pairs GJK left in `Collision`
 //                    k_epa_prepare / k_epa_loop / k_epa_records   the fp32 convex x convex fast tier in three stages
-//   hfcl_k_bvh.hip   k_bvh_collide<T>   BVHModel<OBBRSS> x BVHModel<OBBRSS> collide(), one query per lane for a step budget;
+//   hfcl_k_bvh.hip   k_bvh_collide<T>   BVHModel<OBBRSS> x BVHModel<OBBRSS> collide(), one query per lane for a step budget
+//                                     (hfcl_mesh_collide.hpp: what this source shares with hfcl_k_bvhc.hip, this kernel among it);
 //                                     k_bvh_coop<T>: the queries past it, a wave each, 64 stack entries per trip
 //                                     (BvhSplit::cut_ticks: a walk a wave has had for that long is cut into chunk tasks for the kernel's next
 //                                     launch, k_bvh_combine folds them back; on for mesh x solid, k_bvh_shape_coop)
@@ -20,15 +21,15 @@
 //                                     contraction: triangle ids equal to the reference's); k_bvh_distance_pool<T, PQ>: the walks past
 //                                     it, PQ per wave, their box and triangle tests pooled, DFS order kept by a marker
 //                                     (k_bvh_distance_coop<T>: the ordered wave-per-walk form)
-//                    k_shape_obb<T>, k_bvh_collide<T, ., ., SOLID>, k_bvh_shape_coop<T>, k_bvh_shape_finish<T>
+//   hfcl_k_bvhc.hip  k_shape_obb<T>, k_bvh_collide<T, ., ., SOLID>, k_bvh_shape_coop<T>, k_bvh_shape_finish<T>
 //                                     BVHModel<OBBRSS> x convex solid, first-contact collide(): the solids' OBBs, the walk
 //                                     (lane, then wave), the leaves that need EPA
 //   hfcl_k_bvhs.hip  k_shape_obbrss<T>, k_bvh_shape_distance_lane<T>, k_bvh_shape_distance_pool<T>   ... distance() (a source of its own;
-//                                     hfcl_mesh.hpp: what it shares with hfcl_k_bvh.hip, k_bvh_shape_finish among it)
+//                                     hfcl_mesh.hpp: what it shares with the two collide() sources, k_bvh_shape_finish among it)
 //                                     (k_bvh_shape_distance_coop<T>: the ordered form, libraries with a Plane / Halfspace)
-//                    k_bvh_shape<T> / k_bvh_shape_distance<T>   the same rows, one 16-lane group per query: requests that
-//                                     keep walking after a contact, models deeper than the lanes' stacks
-//                    k_triangle<T>    top-level TriangleP pairs
+//                    k_bvh_shape<T> (hfcl_k_bvhc.hip) / k_bvh_shape_distance<T>   the same rows, one 16-lane group per query: requests
+//                                     that keep walking after a contact, models deeper than the lanes' stacks
+//   hfcl_k_bvh.hip   k_triangle<T>    top-level TriangleP pairs
 //
 // Every launcher is asynchronous on `st` and does no error checking of its own (hfcl_host_batch.hip: run_batch_one checks hipGetLastError once, in its last stage).
 #pragma once

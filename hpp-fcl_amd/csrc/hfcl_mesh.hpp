@@ -1,17 +1,12 @@
-// hfcl_mesh.hpp -- what the mesh objects share as templates: hfcl_k_bvh.hip (compiled twice: hfcl_k_bvh.o, mesh x mesh collide() and
-// triangle pairs; hfcl_k_bvhc.o, mesh x solid collide()) and hfcl_k_bvhs.hip (hfcl_k_bvhs.o, mesh x solid distance()).  Only these
-// include it.  Here: the task summaries' accessors, the solid of a lane and of a lane group, the mesh x solid leaf as a call, and the
-// leaves that needed EPA (k_bvh_shape_finish), which both solid objects launch.
+// hfcl_mesh.hpp -- what the three mesh objects share as templates: hfcl_k_bvh.hip (hfcl_k_bvh.o, mesh x mesh collide() and triangle
+// pairs), hfcl_k_bvhc.hip (hfcl_k_bvhc.o, mesh x solid collide()) and hfcl_k_bvhs.hip (hfcl_k_bvhs.o, mesh x solid distance()).  Only
+// these include it, the two collide() sources through hfcl_mesh_collide.hpp, which holds what those two alone share.  Here: the task
+// summaries' accessors, the solid of a lane and of a lane group, the mesh x solid leaf as a call, and the leaves that needed EPA
+// (k_bvh_shape_finish), which both solid objects launch.
 //
-// The three objects are built under two contraction settings (Makefile: hfcl_k_bvh.o with hipcc's default, the two solid objects with
-// -ffp-contract=off), and every template is instantiated by the object that uses it.  A kernel or a non-inlined device function
-// instantiated with the same arguments in two of these objects would therefore be built twice, differently, and the two copies would
-// collide at the kernel's host stub (a template's stub is one weak symbol for the whole library): which arithmetic a launch then runs
-// is the linker's choice.  The forms of a walk write the same bytes (tests/test_options_gpu.py, test_bvh_collide_forms_agree,
-// test_gpu_mesh_solid_*_forms_agree) only because each object runs its own copies.  So whatever two objects launch carries the
-// launching object's part as a template argument (k_bvh_shape_finish here; k_bvh_level_mark and k_bvh_combine in hfcl_k_bvh.hip), and
-// what one object launches is told apart by its own arguments (SOLID of k_bvh_collide / k_bvh_walk / k_bvh_resolve, the W0Lds block
-// size of the leaf calls).  tests/test_mesh_units_cpu.py holds the built objects to it: no kernel's host stub in two of them.
+// The three objects are built under two contraction settings, so no kernel and no non-inlined device function may be instantiated with
+// the same arguments in two of them: hfcl_mesh_collide.hpp's opening comment says why and how that is kept.  What it means here:
+// k_bvh_shape_finish carries the launching object's part (its source's MESH_UNIT_PART) as a template argument.
 #pragma once
 #include <algorithm>
 
@@ -23,7 +18,7 @@ template <typename T>
 __device__ __forceinline__ BvhSum<T>* bvh_sum(const BvhSplit& sp, uint32_t slot) { return reinterpret_cast<BvhSum<T>*>(sp.sums) + slot; }
 
 // ---------------------------------------------------------------------------------------
-// Mesh x solid with one query per LANE: pieces of the SOLID form of k_bvh_collide (hfcl_k_bvh.hip) and of k_bvh_shape_finish (below).
+// Mesh x solid with one query per LANE: pieces of the SOLID form of k_bvh_collide (hfcl_mesh_collide.hpp) and of k_bvh_shape_finish (below).
 // ---------------------------------------------------------------------------------------
 #ifndef HFCL_LANE_SOLID_BATCH
 #define HFCL_LANE_SOLID_BATCH 4

@@ -1,7 +1,9 @@
-"""The three mesh objects (hfcl_k_bvh.o, hfcl_k_bvhc.o, hfcl_k_bvhs.o) share templates (csrc/hfcl_mesh.hpp) and are built under two
+"""The three mesh objects, each from a source of its own (hfcl_k_bvh.hip, hfcl_k_bvhc.hip, hfcl_k_bvhs.hip -> hfcl_k_bvh.o, hfcl_k_bvhc.o,
+hfcl_k_bvhs.o), share templates (csrc/hfcl_mesh.hpp; the two collide() sources also csrc/hfcl_mesh_collide.hpp) and are built under two
 contraction settings: a kernel instantiated with the same arguments in two of them would be built twice, differently, and meet at one
-host stub.  Whatever two of them launch therefore carries the unit's part as a template argument.  Here: the host stubs the built
-objects define are pairwise disjoint, and together they are the 60 kernels of the mesh units.  Symbol names only; no GPU."""
+host stub.  Whatever two of them launch therefore carries the launching source's part (MESH_UNIT_PART) as a template argument.  Here:
+the host stubs the built objects define are pairwise disjoint, each object defines its own number of them, and together they are the
+60 kernels of the mesh units.  Symbol names only; no GPU."""
 import os
 import shutil
 import subprocess
@@ -9,6 +11,7 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "hpp-fcl_amd", "csrc")
 UNITS = ("hfcl_k_bvh.o", "hfcl_k_bvhc.o", "hfcl_k_bvhs.o")
+KERNELS = {"hfcl_k_bvh.o": 19, "hfcl_k_bvhc.o": 27, "hfcl_k_bvhs.o": 14}  # (product build; profiles/r29_a_mesh_units.md section 1)
 
 
 def defined_stubs(obj):
@@ -32,6 +35,8 @@ def test_no_kernel_is_built_in_two_mesh_units():
     for i, a in enumerate(UNITS):
         for b in UNITS[i + 1:]:
             both = stubs[a] & stubs[b]
-            assert not both, "%s and %s both build %s: pass the unit's part to it (hfcl_mesh.hpp)" % (a, b, sorted(both))
-    counts = {u: len(stubs[u]) for u in UNITS}  # 19, 27 and 14 when this was written
+            assert not both, "%s and %s both build %s: pass the unit's part to it (hfcl_mesh_collide.hpp)" % (a, b, sorted(both))
+    counts = {u: len(stubs[u]) for u in UNITS}
     assert len(set().union(*stubs.values())) == 60, "kernels per mesh object: %s (stale objects? rebuild with make)" % counts
+    # a kernel that drifts from one object into another (and so under another contraction setting) leaves the total at 60
+    assert counts == KERNELS, "kernels per mesh object: %s, expected %s (stale objects? rebuild with make)" % (counts, KERNELS)

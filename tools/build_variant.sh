@@ -2,7 +2,7 @@
 # Build a variant of libhppfcl_amd.so with one or more kernel units recompiled under extra flags (A/B runs on the GPU box select it
 # with HFCL_LIB_PATH).  Usage: tools/build_variant.sh <name> <units, comma-separated> <flags...>
 #   units: the Makefile's DEVOBJS without "hfcl_" and ".o" -- host, host_scene, k_gjk32, k_cull, k_nearest, ...  (k_gjk / k_epa: both
-#   precisions of the unit; k_bvhc: the mesh x solid collide() part of hfcl_k_bvh.hip)
+#   precisions of the unit)
 # Output: build/ab/lib_<name>.so (git-ignored; travels with gpurun).  The other objects are the in-tree ones (run make first).
 set -e
 name=$1; units=$2; shift 2
@@ -19,7 +19,7 @@ for u in $all_units; do
   if [[ "$units" == *",$u,"* ]]; then
     unitflags=$(make -s -C $csrc -pn 2>/dev/null | sed -n "s/^FLAGS_$u = //p" | head -1)
     src=$o; def=""
-    case $u in *32) src=${o%32}; def="-DHFCL_UNIT_PRECISION=32";; *64) src=${o%64}; def="-DHFCL_UNIT_PRECISION=64";; k_bvhc) src=hfcl_k_bvh;; esac
+    case $u in *32) src=${o%32}; def="-DHFCL_UNIT_PRECISION=32";; *64) src=${o%64}; def="-DHFCL_UNIT_PRECISION=64";; esac
     (cd $csrc && /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-value $unitflags $def "$@" -Wno-pass-failed -c -o $root/build/ab/${o}_$name.o $src.hip) &
     pids="$pids $!"
     objs="$objs $root/build/ab/${o}_$name.o"
