@@ -826,6 +826,38 @@ def _distance_octree(o1, tf1, o2, tf2, request, result):
     return d
 
 
+def distance_octree_mesh(o1, tf1, o2, tf2, request, result):
+    """distance() between an OcTree and a BVHModel<OBBRSS>, either operand order, through hfcl_octree_mesh_distance_batch
+    (hppfcl_amd_octree_mesh_distance.h): the reference's ordered dual walk.  A call of its own BESIDE the dispatch: distance() and
+    ComputeDistance keep refusing the pair (taking it there is the follow-up; two tests hold the refusal).  Either order gets the
+    octree-first result: result.o1 is the tree and result.o2 the mesh, b1 the node and b2 the triangle, nearest_points and normal the
+    record's.  The walk starts fresh and the result is merged by DistanceResult::update, as distance() does for an octree."""
+    t1, t2 = isinstance(o1, OcTree), isinstance(o2, OcTree)
+    if t1 == t2 or not engine.octree_mesh_distance_pair_supported(int((o2 if t1 else o1).getNodeType())):
+        raise ValueError("Distance function between node type %d and node type %d is not yet supported." % (o1.getNodeType(), o2.getNodeType()))
+    if result.min_distance <= 0:  # DistanceRequest::isSatisfied
+        return result.min_distance
+    swapped = not t1
+    tree, tft, mesh, tfm = (o2, tf2, o1, tf1) if swapped else (o1, tf1, o2, tf2)
+    ctx = _context()
+    sid, tid = ctx.add(mesh), ctx.add_octree(tree)
+    lib = ctx.library()
+    try:
+        rec = lib.octree_mesh_distance([tid], [sid], tft._abi().reshape(1, 12), tfm._abi().reshape(1, 12), request._abi(), swapped=[1 if swapped else 0])
+    except engine.EngineError as e:
+        if e.code in (abi.ERR_INVALID_ARGUMENT, abi.ERR_UNSUPPORTED_PAIR, abi.ERR_LIMIT):
+            raise ValueError(str(e))
+        raise
+    r = rec[0]
+    d = float(r["distance"])
+    if result.min_distance > d:  # DistanceResult::update
+        result.min_distance, result.o1, result.o2 = d, tree, mesh
+        result.b1, result.b2 = int(r["b1"]), int(r["b2"])
+        result.normal = np.array(r["normal"])
+        result.nearest_points = [np.array(r["p1"]), np.array(r["p2"])]
+    return d
+
+
 def collide(*args):
     """collide(o1, tf1, o2, tf2, request, result) or collide(obj1, obj2, request, result)  (python/collision.cc:257-266)"""
     if len(args) == 4:

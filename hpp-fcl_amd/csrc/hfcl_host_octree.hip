@@ -4,9 +4,12 @@
 // for OctHost, the kind defined here.  At the end hfcl_octree_distance_batch* (hppfcl_amd_octree_distance.h; the kernel:
 // hfcl_k_octree_distance.hip): one launch per chunk, no workspace, no read-back; its host form is staged as the collide call's.
 // Last hfcl_octree_mesh_collide_batch* (hppfcl_amd_octree_mesh.h; the kernels: hfcl_k_octree_mesh.hip): the same driver for OctMeshHost, on a
-// workspace of its own, behind a check of the meshes' BVH depths.
+// workspace of its own, behind a check of the meshes' BVH depths.  And hfcl_octree_mesh_distance_batch* (hppfcl_amd_octree_mesh_distance.h; the
+// kernel: hfcl_k_octree_mesh_distance.hip): the request check of the octree distance() call, the mesh checks of the mesh collide() call, one
+// launch per chunk.
 #include "hfcl_host_listed.hpp"
 #include "hfcl_octree_distance.hpp"
+#include "hfcl_octree_mesh_distance.hpp"
 
 #include <cmath>
 
@@ -405,6 +408,113 @@ int hfcl_octree_mesh_collide_batch(hfcl_lib* lib, const uint32_t* octree, const 
       }
   return listed_collide_host<OctMeshHost>(who, lib, octree, shape, tf_octree, tf_mesh, n, swapped, req, out, distance_lower_bound, contacts,
                                           max_contacts_total, n_contacts_out);
+}
+
+}  // extern "C"
+
+// ---- distance() against meshes (hppfcl_amd_octree_mesh_distance.h; the kernel: hfcl_k_octree_mesh_distance.hip) ---------------------
+namespace {
+
+// The call on device pointers: queries [0, n) in chunks, one launch each; nothing is read back
+int octmd_run(hfcl_lib* lib, const uint32_t* d_octree, const uint32_t* d_shape, const double* d_tft, const double* d_tfm, size_t n,
+              const uint8_t* d_swapped, const QParams<double>& q, hfcl_result* d_out, uint32_t* d_visited, hipStream_t st) {
+  auto& oc = lib->oct;
+  if (int rc = upload_octrees(lib)) return rc;
+  if (int rc = upload_bvh(lib)) return rc;
+  hfcl::OctMeshDistArgs a;
+  a.shapes = lib->d_shapes64;
+  a.n_shapes = uint32_t(lib->n_shapes);
+  a.n_trees = uint32_t(oc.h_trees.size());
+  a.n_meshes = uint32_t(lib->h_meshes.size());
+  a.trees = oc.d_trees;
+  a.nodes = oc.d_nodes;
+  a.mnodes = lib->d_nodes64;
+  a.mverts = lib->d_bverts64;
+  a.mtris = lib->d_btris;
+  a.meshes = lib->d_meshes;
+  a.q = q;
+  const size_t chunk = std::min(oct_chunk(lib), n);
+  Timed t(lib, "k_octm_distance", st);
+  for (size_t q0 = 0; q0 < n; q0 += chunk) {
+    const size_t m = std::min(chunk, n - q0);
+    a.octree = d_octree + q0;
+    a.shape = d_shape + q0;
+    a.tf_t = d_tft + 12 * q0;
+    a.tf_m = d_tfm + 12 * q0;
+    a.swapped = d_swapped ? d_swapped + q0 : nullptr;
+    a.out = d_out + q0;
+    a.n_visited = d_visited ? d_visited + q0 : nullptr;
+    a.m = uint32_t(m);
+    launch_octm_distance(st, a, 1 << 20);  // (a workgroup per four queries: the hardware hands the long walks out as they come)
+  }
+  HIP_TRY(hipGetLastError());
+  return HFCL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hfcl_octree_mesh_distance_pair_supported(int32_t t) { return t == HFCL_BV_OBBRSS ? 1 : 0; }
+
+int hfcl_octree_mesh_distance_batch_device(hfcl_lib* lib, const uint32_t* d_octree, const uint32_t* d_shape, const double* d_tf_octree,
+                                           const double* d_tf_mesh, size_t n, const uint8_t* d_swapped, const hfcl_distance_request* req,
+                                           hfcl_result* d_out, uint32_t* d_n_visited, void* stream) {
+  const char* who = "hfcl_octree_mesh_distance_batch_device";
+  if (int rc = no_device()) return rc;
+  if (!lib) {
+    set_error(std::string(who) + ": null library");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  QParams<double> q;
+  if (int rc = octd_request(who, req, q)) return rc;
+  if (n == 0) return HFCL_OK;
+  if (int rc = listed_check_arrays(who, d_octree, d_shape, d_tf_octree, d_tf_mesh, d_out, n)) return rc;
+  octm_depths(lib);  // the ids are not visible here: no registered mesh may be deeper than the walk's stack
+  for (size_t k = 0; k < lib->oct.mesh_depth.size(); ++k)
+    if (lib->oct.mesh_depth[k] > HFCL_OCTREE_MESH_MAX_BVH_DEPTH) return octm_too_deep(who, k, lib->oct.mesh_depth[k]);
+  HIP_TRY(hipSetDevice(lib->device));
+  return octmd_run(lib, d_octree, d_shape, d_tf_octree, d_tf_mesh, n, d_swapped, q, d_out, d_n_visited, (hipStream_t)stream);
+}
+
+int hfcl_octree_mesh_distance_batch(hfcl_lib* lib, const uint32_t* octree, const uint32_t* shape, const double* tf_octree, const double* tf_mesh,
+                                    size_t n, const uint8_t* swapped, const hfcl_distance_request* req, hfcl_result* out, uint32_t* n_visited) {
+  const char* who = "hfcl_octree_mesh_distance_batch";
+  if (int rc = no_device()) return rc;
+  if (!lib) {
+    set_error(std::string(who) + ": null library");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  QParams<double> q;
+  if (int rc = octd_request(who, req, q)) return rc;
+  if (n == 0) return HFCL_OK;
+  if (int rc = listed_check_arrays(who, octree, shape, tf_octree, tf_mesh, out, n)) return rc;
+  octm_depths(lib);
+  for (size_t i = 0; i < n; ++i) {  // a mesh named by the batch that is deeper than the walk's stack, or a mesh row that names no registered mesh
+    if (shape[i] >= lib->n_shapes || lib->h_shapes[shape[i]].type != HFCL_BV_OBBRSS) continue;  // (refused below, in the order of every host form)
+    const size_t k = lib->h_shapes[shape[i]].bvh_index;
+    if (k < lib->oct.mesh_depth.size() && lib->oct.mesh_depth[k] > HFCL_OCTREE_MESH_MAX_BVH_DEPTH) return octm_too_deep(who, k, lib->oct.mesh_depth[k]);
+  }
+  for (size_t i = 0; i < n; ++i)
+    if (shape[i] < lib->n_shapes && lib->h_shapes[shape[i]].type == HFCL_BV_OBBRSS && size_t(lib->h_shapes[shape[i]].bvh_index) >= lib->h_meshes.size()) {
+      set_error(std::string(who) + ": bvh_index outside the registered meshes at query " + std::to_string(i));
+      return HFCL_ERR_INVALID_ARGUMENT;
+    }
+  if (int rc = listed_check_queries(who, lib, octree, lib->oct.h_trees.size(), shape, n, OctHost::noun, OctHost::a_noun, "Distance",
+                                    hfcl_octree_mesh_distance_pair_supported))
+    return rc;
+  HIP_TRY(hipSetDevice(lib->device));
+  auto& w = lib->oct.ws_mesh;
+  if (!w.st) HIP_TRY(w.st.create());
+  // staged in pieces of the chunk option: the staging buffers are the mesh collide call's, the visited counts go through its count buffer
+  const size_t chunk = std::min(oct_chunk(lib), n);
+  HIP_TRY(w.d_counts.grow(chunk));
+  const int rc = listed_staged(who, w, chunk, octree, shape, tf_octree, tf_mesh, n, swapped, out, n_visited, w.d_counts.get(), [&](size_t, size_t m) {
+    return octmd_run(lib, w.s_id, w.s_shape, w.s_tf_a, w.s_tf_s, m, swapped ? w.s_swapped.get() : nullptr, q, w.s_out,
+                     n_visited ? w.d_counts.get() : nullptr, w.st);
+  });
+  hipStreamSynchronize(w.st);
+  return rc;
 }
 
 }  // extern "C"

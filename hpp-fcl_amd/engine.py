@@ -98,6 +98,8 @@ OCTREE_DISTANCE_SYMBOLS = ["hfcl_octree_distance_pair_supported", "hfcl_octree_d
 # include/hppfcl_amd_octree_mesh.h (included by hppfcl_amd.h): collide() between a registered OcTree and a registered BVHModel<OBBRSS>
 OCTREE_MESH_SYMBOLS = ["hfcl_octree_mesh_pair_supported", "hfcl_octree_mesh_collide_batch", "hfcl_octree_mesh_collide_batch_device"]
 OCTREE_MESH_MAX_BVH_DEPTH = 64  # HFCL_OCTREE_MESH_MAX_BVH_DEPTH
+# include/hppfcl_amd_octree_mesh_distance.h (included by hppfcl_amd.h): distance() between a registered OcTree and a registered BVHModel<OBBRSS>
+OCTREE_MESH_DISTANCE_SYMBOLS = ["hfcl_octree_mesh_distance_pair_supported", "hfcl_octree_mesh_distance_batch", "hfcl_octree_mesh_distance_batch_device"]
 
 
 class EngineError(RuntimeError):
@@ -229,6 +231,11 @@ def octree_distance_pair_supported(node_type):
 def octree_mesh_pair_supported(node_type):
     """hfcl_octree_mesh_pair_supported: does collide() have an octree row for a mesh of this node type?  (BV_OBBRSS alone)"""
     return bool(dll().hfcl_octree_mesh_pair_supported(C.c_int32(int(node_type))))
+
+
+def octree_mesh_distance_pair_supported(node_type):
+    """hfcl_octree_mesh_distance_pair_supported: does hfcl_octree_mesh_distance_batch take a mesh of this node type?  (BV_OBBRSS alone)"""
+    return bool(dll().hfcl_octree_mesh_distance_pair_supported(C.c_int32(int(node_type))))
 
 
 def _octree_nodes(nodes):
@@ -584,6 +591,26 @@ class Library:
         _check(dll().hfcl_octree_distance_batch_device(self._h, _dptr(d_octree), _dptr(d_shape), _dptr(d_tf_octree), _dptr(d_tf_shape),
                                                        C.c_size_t(n), _dptr(d_swapped), C.byref(req), _dptr(d_out), _dptr(d_visited),
                                                        C.c_void_p(stream)))
+
+    def octree_mesh_distance(self, octree, shape, tf_octree, tf_mesh, req=None, swapped=None, want_visited=False):
+        """Batched distance(OcTree, BVHModel<OBBRSS>) from host arrays: the result of the reference's ordered dual walk
+        (hppfcl_amd_octree_mesh_distance.h).  shape[i] is a BV_OBBRSS row of the library whose bvh_index names a mesh registered with
+        add_bvh.  swapped[i] = 1: the caller's order was distance(mesh, OcTree), which the reference answers with the octree-first
+        result (bit 23 of the status alone changes).  b1 is the octree node, b2 the triangle.  Returns the records, or (records,
+        n_visited) -- the (leaf, triangle) pairs each walk solved -- when want_visited."""
+        req = req or abi.default_distance_request()
+        octree, shape, tft, tfm, swapped, n = _listed_arrays(octree, shape, tf_octree, tf_mesh, swapped)
+        out = np.zeros(n, dtype=abi.RESULT_DTYPE)
+        visited = np.zeros(n, dtype=np.uint32) if want_visited else None
+        _check(dll().hfcl_octree_mesh_distance_batch(self._h, abi.ptr(octree), abi.ptr(shape), abi.ptr(tft), abi.ptr(tfm), C.c_size_t(n),
+                                                     abi.ptr(swapped), C.byref(req), abi.ptr(out), abi.ptr(visited)))
+        return (out, visited) if want_visited else out
+
+    def octree_mesh_distance_device(self, d_octree, d_shape, d_tf_octree, d_tf_mesh, n, req, d_out, d_swapped=None, d_visited=None, stream=0):
+        """The same call on device pointers (torch tensors or raw pointers): asynchronous on `stream`, nothing is read back."""
+        _check(dll().hfcl_octree_mesh_distance_batch_device(self._h, _dptr(d_octree), _dptr(d_shape), _dptr(d_tf_octree), _dptr(d_tf_mesh),
+                                                            C.c_size_t(n), _dptr(d_swapped), C.byref(req), _dptr(d_out), _dptr(d_visited),
+                                                            C.c_void_p(stream)))
 
     def collide_contacts(self, s1, s2, tf1, tf2, req, max_contacts):
         """Batched collide() returning (records, contacts[CONTACT_DTYPE], n_produced)."""

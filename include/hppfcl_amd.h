@@ -695,6 +695,8 @@ int hfcl_scene_distance_device_f32(hfcl_scene* s, const float* d_object_pose, si
 #include "./hppfcl_amd_octree_distance.h"
 /* ... and the batched collide() of an OcTree against BVHModel<OBBRSS> meshes: the reference's dual walk */
 #include "./hppfcl_amd_octree_mesh.h"
+/* ... and the batched distance() of that pair: the reference's ordered dual walk under the running minimum */
+#include "./hppfcl_amd_octree_mesh_distance.h"
 /* the self-collision pairs of a scene per configuration, made on the device, and the scene calls on such a list */
 #include "hppfcl_amd_pairs.h"
 #endif /* HPPFCL_AMD_H */

@@ -1245,6 +1245,23 @@ class OcTreeBatch {
   void distance(const std::vector<std::pair<uint32_t, uint32_t>>& tree_solid, const std::vector<Transform3f>& tf_tree,
                 const std::vector<Transform3f>& tf_solid, const std::vector<uint8_t>& swapped, const DistanceRequest& request,
                 std::vector<DistanceResult>& results, std::vector<uint32_t>* visited = nullptr) {
+    distanceWith(hfcl_octree_distance_batch, tree_solid, tf_tree, tf_solid, swapped, request, results, visited);
+  }
+  /// The same for BVHModel<OBBRSS> meshes of the context in the place of the solids (hfcl_octree_mesh_distance_batch,
+  /// hppfcl_amd_octree_mesh_distance.h): query i is distance(tree, mesh), or distance(mesh, tree) where swapped[i].  The tree is o1, its
+  /// node b1, the mesh's triangle b2.  visited (optional): the (leaf, triangle) pairs each walk solved.
+  void distanceMesh(const std::vector<std::pair<uint32_t, uint32_t>>& tree_mesh, const std::vector<Transform3f>& tf_tree,
+                    const std::vector<Transform3f>& tf_mesh, const std::vector<uint8_t>& swapped, const DistanceRequest& request,
+                    std::vector<DistanceResult>& results, std::vector<uint32_t>* visited = nullptr) {
+    distanceWith(hfcl_octree_mesh_distance_batch, tree_mesh, tf_tree, tf_mesh, swapped, request, results, visited);
+  }
+
+ private:
+  typedef int (*DistanceCall)(hfcl_lib*, const uint32_t*, const uint32_t*, const double*, const double*, size_t, const uint8_t*,
+                              const hfcl_distance_request*, hfcl_result*, uint32_t*);
+  void distanceWith(DistanceCall call, const std::vector<std::pair<uint32_t, uint32_t>>& tree_solid, const std::vector<Transform3f>& tf_tree,
+                    const std::vector<Transform3f>& tf_solid, const std::vector<uint8_t>& swapped, const DistanceRequest& request,
+                    std::vector<DistanceResult>& results, std::vector<uint32_t>* visited) {
     const size_t n = tree_solid.size();
     if (tf_tree.size() != n || tf_solid.size() != n || (!swapped.empty() && swapped.size() != n))
       throw std::invalid_argument("pairs/poses size mismatch");
@@ -1257,14 +1274,15 @@ class OcTreeBatch {
     const hfcl_distance_request a = to_abi(request);
     rec_.resize(n);
     if (visited) visited->assign(n, 0u);
-    const int rc = hfcl_octree_distance_batch(lib, ot.data(), sh.data(), reinterpret_cast<const double*>(tf_tree.data()),
-                                              reinterpret_cast<const double*>(tf_solid.data()), n, swapped.empty() ? nullptr : swapped.data(), &a,
-                                              rec_.data(), visited ? visited->data() : nullptr);
+    const int rc = call(lib, ot.data(), sh.data(), reinterpret_cast<const double*>(tf_tree.data()), reinterpret_cast<const double*>(tf_solid.data()), n,
+                        swapped.empty() ? nullptr : swapped.data(), &a, rec_.data(), visited ? visited->data() : nullptr);
     if (rc == HFCL_ERR_LIMIT) throw std::invalid_argument(hfcl_last_error());
     if (rc) throw_for(rc);
     results.assign(n, DistanceResult());
     for (size_t i = 0; i < n; ++i) fill(results[i], rec_[i], trees_[tree_solid[i].first].tree, ctx_.geometry(sh[i]));
   }
+
+ public:
   /// DistanceResult::update with one record
   void fill(DistanceResult& res, const hfcl_result& r, const CollisionGeometry* tree, const CollisionGeometry* solid) const {
     if (HFCL_STATUS_SKIPPED(r.status)) return;
@@ -1315,6 +1333,26 @@ inline bool octree_pair_supported(const CollisionGeometry* o1, const CollisionGe
 inline bool octree_distance_pair_supported(const CollisionGeometry* o1, const CollisionGeometry* o2) {
   const bool t1 = is_octree(o1), t2 = is_octree(o2);
   return t1 != t2 && hfcl_octree_distance_pair_supported((t1 ? o2 : o1)->getNodeType()) != 0;
+}
+
+/// distance() between an OcTree and a BVHModel<OBBRSS>, either operand order, as a batch of one through
+/// OcTreeBatch::distanceMesh (hppfcl_amd_octree_mesh_distance.h).  A call of its own BESIDE the dispatch: hpp::fcl::distance() and
+/// ComputeDistance keep refusing the pair (taking it there is the follow-up; two tests hold the refusal).  Either order gets the
+/// octree-first result: the tree is result.o1 and its node b1, the mesh result.o2 and its triangle b2.
+inline FCL_REAL distanceOcTreeMesh(const CollisionGeometry* o1, const Transform3f& tf1, const CollisionGeometry* o2, const Transform3f& tf2,
+                                   const DistanceRequest& request, DistanceResult& result) {
+  const bool t1 = is_octree(o1), t2 = is_octree(o2);
+  if (t1 == t2 || hfcl_octree_mesh_distance_pair_supported((t1 ? o2 : o1)->getNodeType()) == 0)
+    throw std::invalid_argument("Distance function between the two node types is not yet supported.");
+  if (result.min_distance <= 0) return result.min_distance;  // DistanceRequest::isSatisfied
+  const bool swapped = !t1;
+  OcTreeBatch& ob = default_octree_batch();
+  if (ob.numTrees() >= DEFAULT_OCTREE_BATCH_MAX) ob.reset();
+  const std::pair<uint32_t, uint32_t> ts(ob.addTree(static_cast<const OcTree*>(swapped ? o2 : o1)), ob.addSolid(swapped ? o1 : o2));
+  std::vector<DistanceResult> one;
+  ob.distanceMesh({ts}, {swapped ? tf2 : tf1}, {swapped ? tf1 : tf2}, {static_cast<uint8_t>(swapped ? 1 : 0)}, request, one);
+  ob.fill(result, ob.records()[0], swapped ? o2 : o1, swapped ? o1 : o2);
+  return ob.records()[0].distance;
 }
 
 }  // namespace amd

@@ -63,7 +63,7 @@
  * Option `octree_items` has no meaning for this call.  A wave takes as long as its longest walk.
  *
  * Not done: Plane and Halfspace against an octree; fp32 and hfcl_multi_* forms; cached and bounding-volume GJK guesses; a lane-per-query
- * or pooled continuation form for the long walks; octree x octree; octree x mesh; octrees in scenes. */
+ * or pooled continuation form for the long walks; octree x octree; octrees in scenes.  (Octree x mesh: hppfcl_amd_octree_mesh_distance.h.) */
 #ifndef HPPFCL_AMD_OCTREE_DISTANCE_H
 #define HPPFCL_AMD_OCTREE_DISTANCE_H
 #include "hppfcl_amd.h"

@@ -61,7 +61,9 @@
  * reached (leaf, triangle) pairs listed in walk order with their boxes, every item solved by a lane group, and one replay per query
  * folds its items in order.  A query is walked by ONE lane: few queries with long walks are bound by that walk.
  *
- * Not done: distance() for the pair (OcTreeMeshDistanceRecurse); octree x octree and x height field; BV types other than OBBRSS; fp32
+ * distance() for the pair (OcTreeMeshDistanceRecurse) has a header of its own: hppfcl_amd_octree_mesh_distance.h.
+ *
+ * Not done: octree x octree and x height field; BV types other than OBBRSS; fp32
  * and hfcl_multi_* forms; cached and bounding-volume GJK guesses; a finite distance_upper_bound; octrees as scene objects; a pooled or
  * wave-wide form of the walk; a leaf pass in rounds that stops at a query's first contact. */
 #ifndef HPPFCL_AMD_OCTREE_MESH_H

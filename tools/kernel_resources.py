@@ -1,14 +1,14 @@
 #!/usr/bin/env python
 """Compact per-kernel resource table (VGPR / AGPR / scratch / LDS / occupancy) from hipcc's
 -Rpass-analysis=kernel-resource-usage.
-usage: tools/kernel_resources.py [gjk|epa|bvh|bvhd|patch|scene|cull|nearest|pairs|nearest_self|env|nearest_env|hfield|terrain|octree|octree_distance|octree_mesh ...] [extra hipcc flags]   (default: every kernel translation unit)"""
+usage: tools/kernel_resources.py [gjk|epa|bvh|bvhd|patch|scene|cull|nearest|pairs|nearest_self|env|nearest_env|hfield|terrain|octree|octree_distance|octree_mesh|octree_mesh_distance ...] [extra hipcc flags]   (default: every kernel translation unit)"""
 import os
 import re
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-UNITS = ("gjk32", "gjk64", "epa32", "epa64", "bvh", "bvhc", "bvhs", "bvhd", "patch", "scene", "cull", "nearest", "pairs", "nearest_self", "env", "nearest_env", "hfield", "terrain", "octree", "octree_distance", "octree_mesh")  # as the Makefile builds them (gjk / epa: both precisions)
+UNITS = ("gjk32", "gjk64", "epa32", "epa64", "bvh", "bvhc", "bvhs", "bvhd", "patch", "scene", "cull", "nearest", "pairs", "nearest_self", "env", "nearest_env", "hfield", "terrain", "octree", "octree_distance", "octree_mesh", "octree_mesh_distance")  # as the Makefile builds them (gjk / epa: both precisions)
 ALIAS = {"gjk": ["gjk32", "gjk64"], "epa": ["epa32", "epa64"]}
 units = [u for a in sys.argv[1:] for u in ALIAS.get(a, [a] if a in UNITS else [])] or list(UNITS)
 flags = [a for a in sys.argv[1:] if a not in UNITS and a not in ALIAS]
