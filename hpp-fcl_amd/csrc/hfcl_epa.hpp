@@ -498,7 +498,9 @@ HFCL_HD bool epa_prepare_general(EpaRegStore<T>& st, int rank, T tolerance, Sup&
   return true;
 }
 
-template <typename T, class Grp, int CAP = EPA_MAX_ITER, int V0M = V0_BLOCK>
+// LEAN: the instruction-count form of a trip, for the one kernel that lives on the length of a wave's dependent chain (k_epa_loop<float, 8, 17>,
+// hfcl_k_epa.hip; profiles/r33_a).  Same arithmetic, same LDS contents at every Grp::sync(); every other instantiation keeps its code.
+template <typename T, class Grp, int CAP = EPA_MAX_ITER, int V0M = V0_BLOCK, bool LEAN = false>
 struct Epa {
   static constexpr bool TAGGED = V0M == V0_TAG;
   // (blocks of the reference's capacity walk: the tier that continues a handed-over convex x convex polytope does what the general
@@ -913,7 +915,25 @@ struct Epa {
         *(mark ? topo_bytes(m->ft[f < nf ? f : 0], 1) + 3 : start_at + Grp::lane()) = uint8_t(pass);
       }
     }
-    for (int v = Grp::lane(); v < 2 * Block::NV; v += Grp::W) start_at[v] = 255;
+    if constexpr (LEAN) {
+      // The 2 * NV bytes as words, straight-line: a byte per lane and pass is 2 * NV / W stores, each under a mask of its own that the
+      // compiler keeps in (spilled) SGPRs across the kernel.  A lane without a word of its own in a pass writes word 0 once more; the
+      // bytes past the last whole word go out as bytes, to lanes 0 .. 2 (the others repeat byte `lane`, which is 255 by then: LDS
+      // instructions of a wave complete in order).
+      constexpr int WORDS = 2 * Block::NV / 4, REST = 2 * Block::NV % 4;
+      static_assert(REST <= Grp::W && offsetof(Block, stack) % 4 == 0, "the vertex tables start on a word");
+      uint32_t* const words = reinterpret_cast<uint32_t*>(m->stack);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+      for (int j = 0; j * Grp::W < WORDS; ++j) {
+        const int i = Grp::lane() + j * Grp::W;
+        words[i < WORDS ? i : 0] = 0xFFFFFFFFu;
+      }
+      if constexpr (REST != 0) start_at[Grp::lane() < REST ? 4 * WORDS + Grp::lane() : Grp::lane()] = 255;
+    } else {
+      for (int v = Grp::lane(); v < 2 * Block::NV; v += Grp::W) start_at[v] = 255;
+    }
     if (Grp::lane() == 0) m->top = 0u;
     Grp::sync();
     {
@@ -966,7 +986,14 @@ struct Epa {
       const FaceTopo t = m->ft[hz_face(fr)];
       const int e = hz_edge(fr), a = t.vid((e + 1) % 3), b = t.vid(e);
       // the only entry that starts at a / ends at b, and the loop goes on at both ends
-      if (start_at[a] != k || end_at[b] != k || start_at[b] == 255 || end_at[a] == 255) bad = 1;
+      if constexpr (LEAN) {
+        // (the four bytes read side by side: a horizon that is fine -- nearly every one -- fails none of the four tests, and behind ||
+        // that is four LDS round trips one after the other, each under a mask of its own)
+        const int sa = start_at[a], eb = end_at[b], sb = start_at[b], ea = end_at[a];
+        bad |= int((sa != k) | (eb != k) | (sb == 255) | (ea == 255));
+      } else {
+        if (start_at[a] != k || end_at[b] != k || start_at[b] == 255 || end_at[a] == 255) bad = 1;
+      }
     }
     butterfly_stages<Grp::W>([&](auto stage) {
       constexpr int M = decltype(stage)::value;

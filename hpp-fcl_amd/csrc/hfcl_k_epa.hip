@@ -463,14 +463,24 @@ k_epa_loop(Work wk, LibView<T> lib, QParams<T> q, uint32_t pool_share, uint32_t 
   uint32_t next = blockIdx.x;  // wave-uniform: the wave's blocks are next, next + gridDim.x, ...
   EpaSupportCC<T, WE> sup;
   sup.lig = lig;
-  Epa<T, Grp, CAP, V0_TAG> epa;
+  Epa<T, Grp, CAP, V0_TAG, true> epa;
   EpaLoop<T> L;
   while (true) {
-    const uint64_t live = __ballot(state == LIVE);
-    const int n_live = __popcll(live) / WE;
     const bool strided = next < S;
     const bool more = strided || dry != POOL_FULL;
-    if (n_live == 0 || (more && G - n_live >= HFCL_EPA_LOOP_REFILL_MIN)) {
+    // ---- trips: a loop of its own with one back edge, until a refill is due (the same wave-uniform test in front of every trip as
+    // ever; what the refill alone works with -- next, dry, at, it, the plan -- is not part of this loop's state) ----
+    uint64_t live = __ballot(state == LIVE);
+    int n_live = __popcll(live) / WE;
+    while (!(n_live == 0 || (more && G - n_live >= HFCL_EPA_LOOP_REFILL_MIN))) {
+      if (state == LIVE) {
+        const int r = epa.step(L, sup);
+        if (r != 0) state = r == 1 ? DONE : HANDOVER;
+      }
+      live = __ballot(state == LIVE);
+      n_live = __popcll(live) / WE;
+    }
+    {
       // ---- refill phase (uniform decision; groups with a live polytope sit it out) ----
       uint32_t drawn = 0, n_drawn = 0;  // the blocks [drawn, drawn + n_drawn) of the pool, for the idle groups in rank order
       if (!strided && dry != POOL_FULL) {
@@ -550,12 +560,6 @@ k_epa_loop(Work wk, LibView<T> lib, QParams<T> q, uint32_t pool_share, uint32_t 
       if (n_live == 0 && !more) {
         if (__ballot(state == LIVE) == 0) break;
       }
-      continue;
-    }
-    // ---- trip ----
-    if (state == LIVE) {
-      const int r = epa.step(L, sup);
-      if (r != 0) state = r == 1 ? DONE : HANDOVER;
     }
   }
 }
