@@ -184,11 +184,11 @@ struct hfcl_options {
   bool bvh_force_wide = false, pipe_trace = false;   // options bvh_force_wide / pipe_trace
   bool walk_early_coop = true;                               // HFCL_BVH_WALK_EARLY_COOP: the queries round 0 hands over are continued beside the later rounds
   // Rounds of walk / leaves / resolve (option bvh_walk_rounds; 0: k_bvh_collide walks the queries, leaves inline).  Not set: chosen per
-  // batch -- ONE round of up to 16 listed leaves and 256 box tests (320 from 120k queries), then the continuation, up to 220k queries
+  // batch -- ONE round of up to 16 listed leaves and 256 box tests (320 above 120 000 queries), then the continuation, up to 220 000 queries
   // (100k: 1.86 against 1.94 ms with two rounds, 20k: 1.20 against 1.78, 50k: 1.46 against 1.74: a round is as long as its longest lane,
-  // and with the node records kept the lanes carry the walks far enough in one); TWO rounds (6 then 16 leaves; 320 / 640 then 256 box tests)
-  // with the first round's hand-overs continued beside the second above that (250k: 3.32 against 3.36-3.58 ms, 400k: 4.78 against 4.92,
-  // 1M: 9.2 against 10.0 with one round).  profiles/r06_a section 6
+  // and with the node records kept the lanes carry the walks far enough in one); TWO rounds (6 then 16 leaves; 320 -- above 500 000 queries
+  // 640 -- then 256 box tests) with the first round's hand-overs continued beside the second above that (250k: 3.32 against 3.36-3.58 ms,
+  // 400k: 4.78 against 4.92, 1M: 9.2 against 10.0 with one round).  profiles/r06_a section 6.  tests/test_bvh_plan_sizes_gpu.py
   bool walk_auto = true;
   uint32_t walk_rounds = 2;
   uint32_t walk_k[WALK_ROUNDS] = {6, 16, 16, 16};           // option bvh_walk_k: leaves a walk lists per round (setting it switches the automatic choice off)

@@ -58,6 +58,22 @@ def check_parity(abi, got, ref, *, dist_tol, point_tol, flag_band, name="", allo
     return stats
 
 
+def boundary_band(ref, margin, width=1e-9, allowed=0, name=""):
+    """The records of the ORACLE within `width` of the decision boundary of a collide() request, d_ref = security_margin: the only ones
+    a checker may excuse from equal contact counts and triangle ids.  Returns the mask |d_ref - margin| < width and asserts that it holds
+    at most `allowed` records -- a condition on the oracle alone, known before the device runs (tests/test_bvh_boundary_cpu.py recomputes
+    it for every batch a call site names); where it is 0 the excuse is empty and the check strict."""
+    d = np.asarray(ref["distance"], dtype=np.float64)
+    band = np.abs(d - margin) < width
+    idx = np.flatnonzero(band)
+    if len(idx) > allowed:
+        print("    %s: %d records within %g of the boundary d = %g (allowed %d): %s" % (
+            name, len(idx), width, margin, allowed, [(int(i), float(d[i])) for i in idx[:32]]))
+    assert len(idx) <= allowed, "%s: %d oracle records within %g of the decision boundary d = %g, %d allowed (first %s)" % (
+        name, len(idx), width, margin, allowed, idx[:8].tolist())
+    return band
+
+
 def check_properties(abi, res, *, tol, name=""):
     """Size-independent invariants of the reference's own property test
     (test/normal_and_nearest_points.cpp:60-73): p2 = p1 + d*n, |n| = 1, |p2-p1| = |d|."""

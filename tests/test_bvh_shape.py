@@ -4,6 +4,9 @@ traversal_node_bvh_shape.h:98-188) checked against brute force over all triangle
 import numpy as np
 import pytest
 
+import boundary_batches
+from compare import boundary_band
+
 
 def _scene(pkg, n=400, seed=1, **kw):
     return pkg.workloads.mesh_vs_shapes(n=n, seed=seed, **kw)
@@ -161,10 +164,9 @@ def test_lane_form_equals_group_form(pkg, hostsim, margin, cached):
 def test_gpu_mesh_vs_shapes(pkg, oracle, nmax, margin):
     """k_bvh_shape (+ mesh x mesh and shape x shape pairs of the same batch) vs the oracle."""
     abi, wl, bb = pkg.abi, pkg.workloads, pkg.bvh_builder
-    b = _scene(pkg, n=20000, seed=7)
+    b, req, case = boundary_batches.make(pkg, "scene-%d-%s" % (nmax, margin))
+    assert (req.num_max_contacts, req.security_margin) == (nmax, margin)
     ML = bb.MeshLibrary(b.meshes)
-    req = abi.default_collision_request()
-    req.num_max_contacts, req.security_margin = nmax, margin
     ref, cref = oracle.mixed_collide_batch(b.shapes, b.verts, ML, b.s1, b.s2, b.tf1, b.tf2, req, max_contacts=4 * 10 ** 6,
                                            n_threads=16)
     lib = wl.make_library(pkg, b)
@@ -177,7 +179,7 @@ def test_gpu_mesh_vs_shapes(pkg, oracle, nmax, margin):
     assert not ((got["status"] >> 30) & 1).any()
     kinds = b.shapes["type"]
     mixed = (kinds[b.s1] == abi.BV_OBBRSS) != (kinds[b.s2] == abi.BV_OBBRSS)
-    near = np.abs(ref["distance"]) < 1e-9  # decision boundary
+    near = boundary_band(ref, margin, allowed=case.allowed, name="scene")  # decision boundary: d = security_margin
     ok = (got["num_contacts"] == ref["num_contacts"]) | near
     assert ok[mixed].all(), int((~ok[mixed]).sum())
     m = mixed & ~near & (got["num_contacts"] == ref["num_contacts"])
@@ -302,12 +304,9 @@ def test_gpu_mesh_solid_guesses(pkg, oracle, cached):
     leaves hand it on: CachedGuess) keeps its walks in one piece; decisions and first-contact triangles are the oracle's,
     the returned guess is the oracle's where the walk ended on a leaf result that round-off does not move (a contact)."""
     abi, bb = pkg.abi, pkg.bvh_builder
-    b = pkg.workloads.mesh_vs_solid("box,capsule,convex32", n=4000, seed=11)
+    b, req, case = boundary_batches.make(pkg, "guesses-%s" % cached)
+    assert (req.q.gjk_initial_guess == abi.CachedGuess) == cached
     ML = bb.MeshLibrary(b.meshes)
-    req = abi.default_collision_request()
-    if cached:
-        req.q.gjk_initial_guess = abi.CachedGuess
-        req.q.cached_gjk_guess[:] = [0.3, -0.2, 0.9]
     ref, _, gref = oracle.mixed_collide_batch(b.shapes, b.verts, ML, b.s1, b.s2, b.tf1, b.tf2, req, max_contacts=10 ** 5,
                                               n_threads=16, want_guess=True)
     lib = pkg.workloads.make_library(pkg, b)
@@ -315,7 +314,7 @@ def test_gpu_mesh_solid_guesses(pkg, oracle, cached):
         got, ggot = lib.collide(b.s1, b.s2, b.tf1, b.tf2, req, want_guess=True)
     finally:
         lib.close()
-    near = np.abs(ref["distance"]) < 1e-9
+    near = boundary_band(ref, case.margin, allowed=case.allowed, name="guesses")
     assert ((got["num_contacts"] == ref["num_contacts"]) | near).all()
     m = ~near
     assert np.array_equal(got["b1"][m], ref["b1"][m]) and np.array_equal(got["b2"][m], ref["b2"][m])
@@ -333,12 +332,11 @@ def test_gpu_mesh_solid_margin_forms_agree(pkg, oracle, kind):
     """A security margin on the one-query-per-lane path (contacts without penetration: no EPA leaf; bounds shifted by the margin):
     wave continuation (budget 8), task levels and walks in one piece against the oracle."""
     abi, bb = pkg.abi, pkg.bvh_builder
-    b = pkg.workloads.mesh_vs_solid(kind, n=4000, seed=8)
+    b, req, case = boundary_batches.make(pkg, "margin-forms-" + kind)
+    assert req.security_margin == 0.04
     ML = bb.MeshLibrary(b.meshes)
-    req = abi.default_collision_request()
-    req.security_margin = 0.04
     ref, _ = oracle.mixed_collide_batch(b.shapes, b.verts, ML, b.s1, b.s2, b.tf1, b.tf2, req, max_contacts=10 ** 5, n_threads=16)
-    near = np.abs(ref["distance"] - 0.04) < 1e-9
+    near = boundary_band(ref, case.margin, allowed=case.allowed, name="margin-forms-" + kind)
     for env in (dict(HFCL_SHAPE_BUDGET0="8"), dict(HFCL_SHAPE_COOP="0", HFCL_SHAPE_BUDGET0="8", HFCL_SHAPE_BUDGET="8"), dict(HFCL_SHAPE_LEVELS="1")):
         got = _device_collide(pkg, b, req, env=env)
         assert ((got["num_contacts"] == ref["num_contacts"]) | near).all(), env
@@ -360,13 +358,12 @@ def test_gpu_mesh_solid_long_walks(pkg, oracle, kind):
     EPA leaves overtaken by earlier contacts) and no budget at all give the same records.  (3) The 16-lane
     group kernel agrees with both.  (4) The fp32 device path takes the same decisions away from the decision boundary."""
     abi, bb = pkg.abi, pkg.bvh_builder
-    b = pkg.workloads.mesh_vs_solid(kind, n=6000, seed=3)
+    b, req, case = boundary_batches.make(pkg, "long-walks-" + kind)
     ML = bb.MeshLibrary(b.meshes)
-    req = abi.default_collision_request()
     ref, _ = oracle.mixed_collide_batch(b.shapes, b.verts, ML, b.s1, b.s2, b.tf1, b.tf2, req, max_contacts=10 ** 5, n_threads=16)
     got = _device_collide(pkg, b, req)
     assert not ((got["status"] >> 30) & 1).any()
-    near = np.abs(ref["distance"]) < 1e-9
+    near = boundary_band(ref, case.margin, allowed=case.allowed, name="long-walks-" + kind)
     ok = (got["num_contacts"] == ref["num_contacts"]) | near
     assert ok.all(), int((~ok).sum())
     m = ~near
@@ -581,15 +578,15 @@ def test_gpu_mesh_solid_collide_at_baseline_size(pkg, oracle):
     """cfg4s as bench.py runs it -- 100 000 collide() queries, mixed solids, default request -- against the oracle: contact flags and
     first-contact triangle ids equal (outside a 1e-9 band around touching), penetration depths to the solver tolerance."""
     abi, wl, bb = pkg.abi, pkg.workloads, pkg.bvh_builder
-    b = wl.mesh_vs_solid("mixed", n=100000, seed=1)
+    b, req, case = boundary_batches.make(pkg, "solids-100000")
+    assert len(b) == 100000
     ML = bb.MeshLibrary(b.meshes)
-    req = wl.make_request(b, abi)
     import os
     ref, _ = oracle.mixed_collide_batch(b.shapes, b.verts, ML, b.s1, b.s2, b.tf1, b.tf2, req, max_contacts=10 ** 6,
                                         n_threads=min(128, os.cpu_count() or 16))
     got = _device_collide(pkg, b, req)
     assert not ((got["status"] >> 30) & 1).any()
-    near = np.abs(ref["distance"]) < 1e-9
+    near = boundary_band(ref, case.margin, allowed=case.allowed, name="solids-100000")
     assert ((got["num_contacts"] == ref["num_contacts"]) | near).all()
     m = ~near
     assert np.array_equal(got["b1"][m], ref["b1"][m]) and np.array_equal(got["b2"][m], ref["b2"][m])
@@ -659,9 +656,8 @@ def test_mesh_vs_flats_headers_match_oracle(pkg, oracle, hostsim):
 @pytest.mark.gpu
 def test_gpu_mesh_vs_flats(pkg, oracle):
     abi, wl, bb = pkg.abi, pkg.workloads, pkg.bvh_builder
-    b = _scene(pkg, n=3000, seed=12, flats_only=True)
+    b, req, case = boundary_batches.make(pkg, "flats")
     ML = bb.MeshLibrary(b.meshes)
-    req = abi.default_collision_request()
     ref = oracle.mixed_collide_batch(b.shapes, b.verts, ML, b.s1, b.s2, b.tf1, b.tf2, req, n_threads=16)
     dref = oracle.mixed_distance_batch(b.shapes, b.verts, ML, b.s1, b.s2, b.tf1, b.tf2, None, n_threads=16)
     lib = wl.make_library(pkg, b)
@@ -672,7 +668,7 @@ def test_gpu_mesh_vs_flats(pkg, oracle):
         lib.close()
     kinds = b.shapes["type"]
     mixed = (kinds[b.s1] == abi.BV_OBBRSS) != (kinds[b.s2] == abi.BV_OBBRSS)
-    near = np.abs(ref["distance"]) < 1e-9
+    near = boundary_band(ref, case.margin, allowed=case.allowed, name="flats")
     m = mixed & ~near
     assert np.array_equal(got["num_contacts"][m], ref["num_contacts"][m])
     assert np.array_equal(got["b1"][m], ref["b1"][m]) and np.array_equal(got["b2"][m], ref["b2"][m])
@@ -692,9 +688,8 @@ def test_gpu_mixed_scene_beside_equals_in_line(pkg, oracle):
     byte the records of the in-line order, twice, and all equal the oracle's decisions (contact flags, first-contact triangle ids); distance()
     over the same batch likewise."""
     abi, wl, bb = pkg.abi, pkg.workloads, pkg.bvh_builder
-    b = wl.mixed_scene(n=40_000, seed=3)
+    b, req, case = boundary_batches.make(pkg, "mixed-scene")
     assert min(b.mix.values()) > 0.1
-    req = abi.default_collision_request()
     dreq = abi.default_distance_request()
     recs, drecs = {}, {}
     for beside in (4, 2, 1, 0):
@@ -713,7 +708,7 @@ def test_gpu_mixed_scene_beside_equals_in_line(pkg, oracle):
     ref = oracle.mixed_collide_batch(b.shapes, b.verts, ML, b.s1, b.s2, b.tf1, b.tf2, req, n_threads=32)
     got = recs[2]
     assert not np.any((got["status"] >> 31) & 1)
-    clear = np.abs(ref["distance"]) > 1e-9
+    clear = ~boundary_band(ref, case.margin, allowed=case.allowed, name="mixed-scene")
     assert np.array_equal((got["num_contacts"] > 0)[clear], (ref["num_contacts"] > 0)[clear])
     mesh_pair = (b.shapes["type"][b.s1] == abi.BV_OBBRSS) | (b.shapes["type"][b.s2] == abi.BV_OBBRSS)
     hit = clear & mesh_pair & (ref["num_contacts"] > 0)

@@ -5,7 +5,8 @@ import os
 import numpy as np
 import pytest
 
-from compare import check_parity, check_properties
+import boundary_batches
+from compare import boundary_band, check_parity, check_properties
 
 pytestmark = pytest.mark.gpu
 
@@ -511,15 +512,22 @@ def test_split_batches_are_bit_identical(pkg, torch_cuda, case):
     lib.close()
 
 
-@pytest.mark.parametrize("case", ["cfg2_box_capsule", "cfg5_mixed", "cfg3_convex_convex"])
+def host_pipeline_batch(pkg, case):
+    b = getattr(pkg.workloads, case)(n=300000)
+    return b, pkg.workloads.make_request(b, pkg.abi)
+
+
+HOST_PIPELINE_CASES = ["cfg2_box_capsule", "cfg5_mixed", "cfg3_convex_convex"]  # (workloads, at 300 000 pairs: tests/test_bvh_boundary_cpu.py too)
+
+
+@pytest.mark.parametrize("case", HOST_PIPELINE_CASES)
 def test_host_pipeline_equals_device_path(pkg, torch_cuda, case):
     """The host-buffer entry points (chunked H2D | kernels | D2H pipeline, what hpp::fcl::collide()/distance() callers
     get) return byte-identical records, warm-start guesses and bucket populations to one device-resident call, for
     any chunk size (ragged last chunk, more chunks than pipeline slots, split chunks)."""
     torch = torch_cuda
     abi, wl = pkg.abi, pkg.workloads
-    b = getattr(wl, case)(n=300000)
-    req = wl.make_request(b, abi)
+    b, req = host_pipeline_batch(pkg, case)
     lib = pkg.Library(b.lib)
     dev = torch.device("cuda:0")
     n = len(b)
@@ -549,7 +557,10 @@ def test_host_pipeline_equals_device_path(pkg, torch_cuda, case):
     assert np.array_equal(np.isfinite(got["distance"]), np.isfinite(ref["distance"]))
     dd = np.abs(got["distance"][ok] - ref["distance"][ok])
     assert dd.max() < 1e-9, dd.max()
-    near = np.abs(ref["distance"]) < 1e-9
+    # (the band is taken on the DEVICE's matrix-pose records here, this test's reference -- not on the oracle's.  It is empty: the oracle has no
+    # record of these batches within 1e-9 of touching, tests/test_bvh_boundary_cpu.py, the nearest is 1.8e-7 away, and the fp64 kernels give the
+    # oracle's distances bit for bit, test_fp64_parity.  So no flag is excused)
+    near = boundary_band(ref, 0.0, allowed=0, name=case + " (device records)")
     assert np.all((abi.status_contact(got["status"]) == abi.status_contact(ref["status"])) | near)
     lib.close()
 
@@ -571,9 +582,10 @@ def _run_bvh(pkg, oracle, b, req, max_contacts=0, options=None):
         lib.close()
 
 
-def _check_bvh_records(abi, got, ref, name):
+def _check_bvh_records(abi, got, ref, name, margin=0.0, allowed=0):
+    """margin: the request's security_margin, where the decision falls; allowed: the oracle's records within 1e-9 of it (boundary_band)."""
     assert not np.any((got["status"] >> 30) & 1), name + ": traversal stack overflow"
-    near = np.abs(ref["distance"]) < 1e-9
+    near = boundary_band(ref, margin, allowed=allowed, name=name)
     same_nc = got["num_contacts"] == ref["num_contacts"]
     assert np.all(same_nc | near), "%s: contact counts differ on %d queries" % (name, (~(same_nc | near)).sum())
     ok = same_nc & ~near
@@ -598,10 +610,10 @@ def test_bvh_collide_first_contact(pkg, oracle, seg, n, form):
         pytest.skip("the fp32 filter form lost its A/B (profiles/r03_b) and is not in the product build: tools/build_variant.sh ab host,k_bvh,k_epa "
                     "-DHFCL_KEEP_AB_FORMS=1, then HFCL_LIB_PATH=build/ab/lib_ab.so")
     if form == "filter":
-        b0 = wl.cfg4_mesh_mesh(n=n, seg=seg, ring=seg, n_variants=4)
-        plain, _, _ = _run_bvh(pkg, oracle, b0, wl.make_request(b0, abi))
-    b = wl.cfg4_mesh_mesh(n=n, seg=seg, ring=seg, n_variants=4)
-    req = wl.make_request(b, abi)
+        b0, req0, _ = boundary_batches.make(pkg, "bvh-first-%d" % seg)
+        plain, _, _ = _run_bvh(pkg, oracle, b0, req0)
+    b, req, _ = boundary_batches.make(pkg, "bvh-first-%d" % seg)
+    assert len(b) == n
     got, ref, kt = _run_bvh(pkg, oracle, b, req, options={"bvh_filter": 1} if form == "filter" else None)
     _check_bvh_records(abi, got, ref, "bvh-first-%d" % seg)
     if form == "filter":
@@ -623,9 +635,8 @@ def test_bvh_collide_baseline_size(pkg, oracle, n):
     stack entries per trip, k_bvh_coop).  Every record against the oracle: contact counts, first-contact triangle ids in DFS
     order, depth and witness data."""
     abi, wl = pkg.abi, pkg.workloads
-    b = wl.cfg4_mesh_mesh(n=n)
-    assert len(b.meshes) == 8 and all(len(m.triangles) == 5000 for m in b.meshes)
-    req = wl.make_request(b, abi)
+    b, req, _ = boundary_batches.make(pkg, "bvh-cfg4-%d" % n)
+    assert len(b) == n and len(b.meshes) == 8 and all(len(m.triangles) == 5000 for m in b.meshes)
     ML = pkg.bvh_builder.MeshLibrary(b.meshes)
     lib = wl.make_library(pkg, b)
     try:
@@ -655,8 +666,7 @@ def test_bvh_collide_forms_agree(pkg, oracle, form):
                "rounds": {"bvh_budget0_coop": 24, "bvh_walk_rounds": 4, "bvh_walk_k": [2, 3, 4, 16], "bvh_walk_budget": [24, 24, 48]},
                "inline": {"bvh_budget0_coop": 24, "bvh_walk_rounds": 0},
                "levels": {"bvh_coop": 0}, "whole": {"bvh_coop": 0, "bvh_levels": 1}}[form]
-    b = wl.cfg4_mesh_mesh(n=30_000, seed=21)
-    req = wl.make_request(b, abi)
+    b, req, _ = boundary_batches.make(pkg, "bvh-forms")
     ML = pkg.bvh_builder.MeshLibrary(b.meshes)
     ref = oracle.bvh_collide_batch(ML, b.s1, b.s2, b.tf1, b.tf2, req, n_threads=32)
     lib = wl.make_library(pkg, b, options=options)
@@ -699,12 +709,13 @@ def test_bvh_collide_all_contacts(pkg, oracle):
 def test_bvh_security_margin_and_mixed_batch(pkg, oracle):
     """margin > 0 widens contacts; a batch mixing mesh pairs and primitive pairs goes to the right kernels."""
     abi, wl, g = pkg.abi, pkg.workloads, pkg.geometry
-    b = wl.cfg4_mesh_mesh(n=3000, seg=12, ring=12, n_variants=2)
-    req = wl.make_request(b, abi, security_margin=0.05)
+    b, req, case = boundary_batches.make(pkg, "bvh-margin")
+    assert req.security_margin == 0.05
     got, ref, kt = _run_bvh(pkg, oracle, b, req)
-    _check_bvh_records(abi, got, ref, "bvh-margin")
-    req0 = wl.make_request(b, abi)
-    got0, ref0, _ = _run_bvh(pkg, oracle, b, req0)
+    _check_bvh_records(abi, got, ref, "bvh-margin", margin=case.margin)  # (the decision falls at d = security_margin)
+    b0, req0, _ = boundary_batches.make(pkg, "bvh-margin-0")  # (the same pairs, no margin)
+    got0, ref0, _ = _run_bvh(pkg, oracle, b0, req0)
+    _check_bvh_records(abi, got0, ref0, "bvh-margin-0")
     assert (got["num_contacts"] > 0).sum() >= (got0["num_contacts"] > 0).sum()
 
 
@@ -802,30 +813,15 @@ def test_bvh_distance_at_baseline_size(pkg, oracle, n):
     print("cfg4d %d queries: walks continued by waves / re-run in order: %s" % (n, reruns))
 
 
-def _mesh_batch(pkg, meshes, n, seed, half_width):
-    wl, g = pkg.workloads, pkg.geometry
-    rng = np.random.default_rng(seed)
-    lib = g.ShapeLibrary()
-    for k, m in enumerate(meshes):
-        lib.add_bvh(k, len(m.vertices))
-    s1, s2 = rng.integers(0, len(meshes), n), rng.integers(0, len(meshes), n)
-    q1, T1, q2, T2 = wl._poses(rng, n, half_width)
-    b = wl.Batch("mesh_pairs", lib, s1, s2, q1, T1, q2, T2, "collide")
-    b.meshes = meshes
-    return b
-
-
 def test_bvh_models_beyond_16_bit_node_ids(pkg, oracle):
     """A BVHModel of 72 200 triangles (144 399 nodes: node ids no longer fit 16 bits, BV_node.h:57 uses int): collide()
     and distance() against the oracle, no traversal flagged as overflowed."""
     abi, bb = pkg.abi, pkg.bvh_builder
-    big = bb.Mesh(*bb.bumpy_sphere(190, 190, r=1.0, amp=0.1, freq=3, phase=0.3))
-    small = bb.Mesh(*bb.bumpy_sphere(20, 20, r=0.7, amp=0.1, freq=2, phase=0.1))
+    b, req, _ = boundary_batches.make(pkg, "bvh-wide")
+    big = b.meshes[0]
     assert len(big.nodes) > 65535
-    b = _mesh_batch(pkg, [big, small], 600, 3, 1.1)
     ML = bb.MeshLibrary(b.meshes)
     lib = pkg.workloads.make_library(pkg, b)
-    req = pkg.workloads.make_request(b, abi)
     got = lib.collide(b.s1, b.s2, b.tf1, b.tf2, req)
     ref = oracle.bvh_collide_batch(ML, b.s1, b.s2, b.tf1, b.tf2, req, n_threads=16)
     _check_bvh_records(abi, got, ref, "bvh-wide")
@@ -836,19 +832,8 @@ def test_bvh_models_beyond_16_bit_node_ids(pkg, oracle):
     assert np.abs(gd["distance"] - rd["distance"]).max() < 1e-9
     lib.close()
     # the same model against solids: the one-query-per-lane walk and its wave continuation carry 32-bit node ids in their entries
-    g = pkg.geometry
-    rng = np.random.default_rng(5)
-    L = g.ShapeLibrary()
-    L.add_bvh(0, len(big.vertices))
-    for _ in range(8):
-        L.add_box(*map(float, rng.uniform(0.2, 0.8, 3)))
-        L.add_capsule(float(rng.uniform(0.1, 0.3)), float(rng.uniform(0.2, 0.8)))
-    n = 1500
-    q1, T1, q2, T2 = pkg.workloads._poses(rng, n, 1.4)
-    bs = pkg.workloads.Batch("big_mesh_x_solid", L, np.zeros(n, dtype=np.int64), rng.integers(1, 17, n), q1, T1, q2, T2, "collide")
-    bs.meshes = [big]
+    bs, creq, case = boundary_batches.make(pkg, "bvh-wide-solids")
     MLs = bb.MeshLibrary(bs.meshes)
-    creq = abi.default_collision_request()
     refs, _ = oracle.mixed_collide_batch(bs.shapes, bs.verts, MLs, bs.s1, bs.s2, bs.tf1, bs.tf2, creq, max_contacts=10 ** 4, n_threads=16)
     libs = pkg.workloads.make_library(pkg, bs)
     try:
@@ -858,7 +843,7 @@ def test_bvh_models_beyond_16_bit_node_ids(pkg, oracle):
         libs.close()
     rds = oracle.mixed_distance_batch(bs.shapes, bs.verts, MLs, bs.s1, bs.s2, bs.tf1, bs.tf2, None, n_threads=16)
     assert not np.any((gots["status"] >> 30) & 1) and not np.any((gds["status"] >> 30) & 1)
-    near = np.abs(refs["distance"]) < 1e-9
+    near = boundary_band(refs, case.margin, allowed=case.allowed, name="bvh-wide-solids")
     assert ((gots["num_contacts"] == refs["num_contacts"]) | near).all()
     assert np.array_equal(gots["b1"][~near], refs["b1"][~near])
     assert 0.1 < (refs["num_contacts"] > 0).mean() < 0.9
@@ -875,20 +860,12 @@ def test_bvh_degenerate_deep_tree(pkg, oracle, force_wide):
     suspends into tasks (default form), or continues in a per-lane global slab (wide form: models beyond 65535 nodes or
     deeper than the task levels hold; forced here with the option bvh_force_wide).  collide() and distance() vs the oracle."""
     abi, bb = pkg.abi, pkg.bvh_builder
-    nt, r = 1200, 3.2
-    x = r ** (np.arange(nt // 2 + 2) - float(nt // 2 + 1))  # largest coordinate 1
-    v = np.zeros((2 * (nt // 2 + 2), 3))
-    k = np.arange(len(v) // 2)
-    v[0::2] = np.stack([x[k], 0 * x[k], 0.02 * x[k]], 1)
-    v[1::2] = np.stack([x[k], 0.3 * x[k], -0.02 * x[k]], 1)
-    t = np.array([[i, i + 1, i + 2] for i in range(nt)], dtype=np.uint32)
-    m = bb.Mesh(v, t)
+    b, req, _ = boundary_batches.make(pkg, "bvh-deep")
+    m = b.meshes[0]
     depth = 1 + int(_depths(m.nodes).max())
     assert depth > 100, depth
-    b = _mesh_batch(pkg, [m], 256, 4, 0.05)
     ML = bb.MeshLibrary(b.meshes)
     lib = pkg.workloads.make_library(pkg, b, options={"bvh_force_wide": 1} if force_wide else None)
-    req = pkg.workloads.make_request(b, abi)
     got = lib.collide(b.s1, b.s2, b.tf1, b.tf2, req)
     ref = oracle.bvh_collide_batch(ML, b.s1, b.s2, b.tf1, b.tf2, req, n_threads=16)
     _check_bvh_records(abi, got, ref, "bvh-deep")
