@@ -5,6 +5,7 @@ test/python_unit/api.py, collision.py, collision_manager.py -- runs on `import h
 
 Plumbing only: every query is a batch of one (or, through `collide_pairs` / the collision manager, one batch)
 on the HIP library.  No CPU fallback."""
+import functools
 import os
 
 import numpy as np
@@ -740,6 +741,18 @@ def _fill_collision(result, o1, o2, request, rec, guess, contacts, pair_index=0)
         request.updateGuess(result)
 
 
+def _one_listed_query(call, container, shape, tf_container, tf_shape, request, swapped, **kw):
+    """One query through a height-field / octree batch call of the library; what the engine refuses of it is the reference's
+    std::invalid_argument."""
+    try:
+        return call([container], [shape], tf_container._abi().reshape(1, 12), tf_shape._abi().reshape(1, 12), request._abi(),
+                    swapped=[1 if swapped else 0], **kw)
+    except engine.EngineError as e:
+        if e.code in (abi.ERR_INVALID_ARGUMENT, abi.ERR_UNSUPPORTED_PAIR, abi.ERR_LIMIT):
+            raise ValueError(str(e))
+        raise
+
+
 def _collide_hfield(o1, tf1, o2, tf2, request, result):
     """(HeightFieldAABB, solid) or (solid, HeightFieldAABB) through hfcl_hfield_collide_batch.  The result gets every contact and the
     call's distance_lower_bound; its nearest_points / normal are the record's: the first contact's when there is one."""
@@ -747,15 +760,8 @@ def _collide_hfield(o1, tf1, o2, tf2, request, result):
     field, tfh, solid, tfs = (o2, tf2, o1, tf1) if swapped else (o1, tf1, o2, tf2)
     ctx = _context()
     sid, hid = ctx.add(solid), ctx.add_hfield(field)
-    lib = ctx.library()
-    cap = int(min(request.num_max_contacts, 1 << 16))
-    try:
-        rec, dlb, contacts, _ = lib.hfield_collide([hid], [sid], tfh._abi().reshape(1, 12), tfs._abi().reshape(1, 12), request._abi(),
-                                                   swapped=[1 if swapped else 0], max_contacts=cap)
-    except engine.EngineError as e:
-        if e.code in (abi.ERR_INVALID_ARGUMENT, abi.ERR_UNSUPPORTED_PAIR, abi.ERR_LIMIT):
-            raise ValueError(str(e))
-        raise
+    rec, dlb, contacts, _ = _one_listed_query(ctx.library().hfield_collide, hid, sid, tfh, tfs, request, swapped,
+                                              max_contacts=int(min(request.num_max_contacts, 1 << 16)))
     if abi.status_skipped(rec[0]["status"]):
         return result.numContacts()
     if dlb[0] < result.distance_lower_bound:
@@ -776,17 +782,10 @@ def _collide_octree(o1, tf1, o2, tf2, request, result):
     ctx = _context()
     sid, tid = ctx.add(solid), ctx.add_octree(tree)
     lib = ctx.library()
-    cap = int(min(request.num_max_contacts, 1 << 16))
     # a BVHModel<OBBRSS> goes through hfcl_octree_mesh_collide_batch (hppfcl_amd_octree_mesh.h): the same record conventions, the
     # triangle in b2, the solver's own points in the contacts
     call = lib.octree_mesh_collide if isinstance(solid, BVHModelOBBRSS) else lib.octree_collide
-    try:
-        rec, dlb, contacts, _ = call([tid], [sid], tft._abi().reshape(1, 12), tfs._abi().reshape(1, 12), request._abi(),
-                                     swapped=[1 if swapped else 0], max_contacts=cap)
-    except engine.EngineError as e:
-        if e.code in (abi.ERR_INVALID_ARGUMENT, abi.ERR_UNSUPPORTED_PAIR, abi.ERR_LIMIT):
-            raise ValueError(str(e))
-        raise
+    rec, dlb, contacts, _ = _one_listed_query(call, tid, sid, tft, tfs, request, swapped, max_contacts=int(min(request.num_max_contacts, 1 << 16)))
     if abi.status_skipped(rec[0]["status"]):
         return result.numContacts()
     if dlb[0] < result.distance_lower_bound:
@@ -800,30 +799,29 @@ def _collide_octree(o1, tf1, o2, tf2, request, result):
     return result.numContacts()
 
 
+def _distance_octree_through(call, o1, tf1, o2, tf2, request, result):
+    """distance() of a checked (OcTree, other) / (other, OcTree) pair through `call`, a batch method of engine.Library: the walk starts
+    fresh and the result is merged by DistanceResult::update -- o1 the tree and b1 its node, whichever the caller's order."""
+    swapped = not isinstance(o1, OcTree)
+    tree, tft, other, tfo = (o2, tf2, o1, tf1) if swapped else (o1, tf1, o2, tf2)
+    ctx = _context()
+    sid, tid = ctx.add(other), ctx.add_octree(tree)
+    r = _one_listed_query(functools.partial(call, ctx.library()), tid, sid, tft, tfo, request, swapped)[0]
+    d = float(r["distance"])
+    if result.min_distance > d:  # DistanceResult::update
+        result.min_distance, result.o1, result.o2 = d, tree, other
+        result.b1, result.b2 = int(r["b1"]), int(r["b2"])
+        result.normal = np.array(r["normal"])
+        result.nearest_points = [np.array(r["p1"]), np.array(r["p2"])]
+    return d
+
+
 def _distance_octree(o1, tf1, o2, tf2, request, result):
     """(OcTree, solid) or (solid, OcTree) through hfcl_octree_distance_batch: the reference's ordered walk.  Either order gets the
     octree-first result (src/distance.cpp swaps back only for BVH and height fields): result.o1 is the tree, b1 its node.  The walk of
     the reference runs on the caller's DistanceResult, so a minimum it already holds would prune this walk too; here the walk starts
     fresh and the result is merged by DistanceResult::update."""
-    swapped = not isinstance(o1, OcTree)
-    tree, tft, solid, tfs = (o2, tf2, o1, tf1) if swapped else (o1, tf1, o2, tf2)
-    ctx = _context()
-    sid, tid = ctx.add(solid), ctx.add_octree(tree)
-    lib = ctx.library()
-    try:
-        rec = lib.octree_distance([tid], [sid], tft._abi().reshape(1, 12), tfs._abi().reshape(1, 12), request._abi(), swapped=[1 if swapped else 0])
-    except engine.EngineError as e:
-        if e.code in (abi.ERR_INVALID_ARGUMENT, abi.ERR_UNSUPPORTED_PAIR, abi.ERR_LIMIT):
-            raise ValueError(str(e))
-        raise
-    r = rec[0]
-    d = float(r["distance"])
-    if result.min_distance > d:  # DistanceResult::update
-        result.min_distance, result.o1, result.o2 = d, tree, solid
-        result.b1, result.b2 = int(r["b1"]), int(r["b2"])
-        result.normal = np.array(r["normal"])
-        result.nearest_points = [np.array(r["p1"]), np.array(r["p2"])]
-    return d
+    return _distance_octree_through(engine.Library.octree_distance, o1, tf1, o2, tf2, request, result)
 
 
 def distance_octree_mesh(o1, tf1, o2, tf2, request, result):
@@ -837,25 +835,7 @@ def distance_octree_mesh(o1, tf1, o2, tf2, request, result):
         raise ValueError("Distance function between node type %d and node type %d is not yet supported." % (o1.getNodeType(), o2.getNodeType()))
     if result.min_distance <= 0:  # DistanceRequest::isSatisfied
         return result.min_distance
-    swapped = not t1
-    tree, tft, mesh, tfm = (o2, tf2, o1, tf1) if swapped else (o1, tf1, o2, tf2)
-    ctx = _context()
-    sid, tid = ctx.add(mesh), ctx.add_octree(tree)
-    lib = ctx.library()
-    try:
-        rec = lib.octree_mesh_distance([tid], [sid], tft._abi().reshape(1, 12), tfm._abi().reshape(1, 12), request._abi(), swapped=[1 if swapped else 0])
-    except engine.EngineError as e:
-        if e.code in (abi.ERR_INVALID_ARGUMENT, abi.ERR_UNSUPPORTED_PAIR, abi.ERR_LIMIT):
-            raise ValueError(str(e))
-        raise
-    r = rec[0]
-    d = float(r["distance"])
-    if result.min_distance > d:  # DistanceResult::update
-        result.min_distance, result.o1, result.o2 = d, tree, mesh
-        result.b1, result.b2 = int(r["b1"]), int(r["b2"])
-        result.normal = np.array(r["normal"])
-        result.nearest_points = [np.array(r["p1"]), np.array(r["p2"])]
-    return d
+    return _distance_octree_through(engine.Library.octree_mesh_distance, o1, tf1, o2, tf2, request, result)
 
 
 def collide(*args):

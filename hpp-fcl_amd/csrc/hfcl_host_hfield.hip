@@ -134,6 +134,7 @@ struct HfHost {
   static uint64_t item_cap(const hfcl_lib* lib) { return lib->opt.hfield_items ? lib->opt.hfield_items : LISTED_ITEM_SOFT_CAP; }
   static constexpr auto request = hf_request;
   static constexpr auto supported = hfcl_hfield_pair_supported;
+  static constexpr auto check = listed_no_check;
   static constexpr auto count = launch_hf_count;
   static constexpr auto solve = launch_hf_solve;
 };

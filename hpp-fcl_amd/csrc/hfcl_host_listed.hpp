@@ -1,14 +1,22 @@
 // hfcl_host_listed.hpp -- host side of the listed-leaf pipeline (the kernels: hfcl_listed.hpp), written once for its kinds: the chunk
 // driver of the device form (count, scan, list, solve, fold), the bodies of the *_collide_batch_device / *_collide_batch entry points,
-// and the chunked copy / compute / copy of a host form.  Included by hfcl_host_hfield.hip and hfcl_host_octree.hip, each of which
-// defines its kind: a struct of static functions and strings --
+// and the chunked copy / compute / copy of a host form.  Behind them the same three pieces for the octrees' distance() calls (one launch
+// per chunk, no workspace of their own, nothing read back).  Included by hfcl_host_hfield.hip and hfcl_host_octree.hip, each of which
+// defines its kinds: structs of static functions and strings.  Both kinds of kind have --
 //   Args, ws(lib), n_containers(lib)     the kernels' parameter block, the library's workspace of the kind, its registered containers
-//   upload(lib), fill(lib, a), ids(a, p) the kind's tables on the device; its part of the block; its array of container ids
-//   chunk(lib), item_cap(lib)            the kind's options
+//   upload(lib), fill(lib, a)            the kind's tables on the device; its part of the block
+//   chunk(lib)                           queries per chunk
+//   supported(type)                      a shape the kind has an evaluator for
+//   check(who, lib, shape, n)            what it refuses of a batch beyond that (listed_no_check: nothing); shape: null in a device form
+//   noun, a_noun                         "octree", "an octree"
+// a collide kind --
+//   ids(a, p), item_cap(lib), limit_who  its array of container ids; its items option; its name in the driver's limit message
 //   request(who, req, q, skip_all)       what every form checks of a request before any work
-//   supported(type)                      a solid the kind has an evaluator for
 //   count(st, a), solve(st, a, ...)      the kind's launches
-//   limit_who, noun, a_noun              its name in the driver's limit message, "octree", "an octree"
+// a distance kind (its ws(lib) is a collide kind's: the host form borrows the staging buffers and the count buffer) --
+//   ptrs(a, ids, tf_c, tf_2)             the chunk's container ids and the two pose arrays, by their names in the block
+//   request(who, req, q), launch(st, a)  the request checks, "null request" included; the one launch of a chunk
+//   timer                                its entry of last_kernel_breakdown()
 #pragma once
 #include "hfcl_host.hpp"
 
@@ -133,6 +141,9 @@ inline int listed_check_arrays(const char* who, const void* id, const void* shap
   return HFCL_OK;
 }
 
+// A kind's check() that refuses nothing
+inline int listed_no_check(const char*, hfcl_lib*, const uint32_t*, size_t) { return HFCL_OK; }
+
 // What a host form refuses of its queries: an id outside the library, a solid without an evaluator ("<verb> function between <a_noun> and ...")
 inline int listed_check_queries(const char* who, const hfcl_lib* lib, const uint32_t* id, size_t n_containers, const uint32_t* shape, size_t n,
                                 const char* noun, const char* a_noun, const char* verb, int (*supported)(int32_t)) {
@@ -196,6 +207,8 @@ int listed_collide_device(const char* who, hfcl_lib* lib, const uint32_t* d_id, 
   QParams<double> q;
   bool skip_all = false;
   if (int rc = K::request(who, req, q, skip_all)) return rc;
+  if (n)  // (before the count is zeroed, as a refusal of the request)
+    if (int rc = K::check(who, lib, nullptr, n)) return rc;
   if (n_contacts_out) *n_contacts_out = 0;
   if (n == 0) return HFCL_OK;
   if (int rc = listed_check_arrays(who, d_id, d_shape, d_tf_c, d_tf_s, d_out, n)) return rc;
@@ -221,6 +234,8 @@ int listed_collide_host(const char* who, hfcl_lib* lib, const uint32_t* id, cons
   QParams<double> q;
   bool skip_all = false;
   if (int rc = K::request(who, req, q, skip_all)) return rc;
+  if (n && shape)  // (no shape array: refused below as a null buffer)
+    if (int rc = K::check(who, lib, shape, n)) return rc;
   if (n_contacts_out) *n_contacts_out = 0;
   if (n == 0) return HFCL_OK;
   if (int rc = listed_check_arrays(who, id, shape, tf_c, tf_s, out, n)) return rc;
@@ -244,5 +259,95 @@ int listed_collide_host(const char* who, hfcl_lib* lib, const uint32_t* id, cons
     rc = HFCL_ERR_HIP;
   }
   hipStreamSynchronize(st);
+  return rc;
+}
+
+// ---- distance(): one launch per chunk ---------------------------------------------------------------------------------------------
+// one entry of last_kernel_breakdown() around the launches of a call (a name of its own: hfcl_host_batch.hip has a Timed)
+struct ListedTimed {
+  hfcl_lib* lib = nullptr;
+  hipStream_t st;
+  ListedTimed(hfcl_lib* l, const char* name, hipStream_t s) : st(s) {
+    for (auto& t : l->timers) t.used = false;
+    if (!l->kernel_timing) return;
+    lib = l;
+    (void)hipEventRecord(timer_slot(lib, 0, name)->e0, st);
+  }
+  ~ListedTimed() {
+    if (lib) (void)hipEventRecord(lib->timers[0].e1, st);
+  }
+  ListedTimed(const ListedTimed&) = delete;
+};
+
+// The call on device pointers: queries [0, n) in chunks, one launch each; nothing is read back
+template <class D>
+int listed_distance_run(hfcl_lib* lib, const uint32_t* d_id, const uint32_t* d_shape, const double* d_tfc, const double* d_tf2, size_t n,
+                        const uint8_t* d_swapped, const QParams<double>& q, hfcl_result* d_out, uint32_t* d_visited, hipStream_t st) {
+  if (int rc = D::upload(lib)) return rc;
+  typename D::Args a;
+  a.shapes = lib->d_shapes64;
+  a.n_shapes = uint32_t(lib->n_shapes);
+  D::fill(lib, a);
+  a.q = q;
+  const size_t chunk = std::min(D::chunk(lib), n);
+  ListedTimed t(lib, D::timer, st);
+  for (size_t q0 = 0; q0 < n; q0 += chunk) {
+    D::ptrs(a, d_id + q0, d_tfc + 12 * q0, d_tf2 + 12 * q0);
+    a.shape = d_shape + q0;
+    a.swapped = d_swapped ? d_swapped + q0 : nullptr;
+    a.out = d_out + q0;
+    a.n_visited = d_visited ? d_visited + q0 : nullptr;
+    a.m = uint32_t(std::min(chunk, n - q0));
+    D::launch(st, a);
+  }
+  HIP_TRY(hipGetLastError());
+  return HFCL_OK;
+}
+
+// What both distance bodies refuse first: no device, a null library, the request
+template <class D>
+int listed_distance_checks(const char* who, hfcl_lib* lib, const hfcl_distance_request* req, QParams<double>& q) {
+  if (int rc = no_device()) return rc;
+  if (!lib) {
+    set_error(std::string(who) + ": null library");
+    return HFCL_ERR_INVALID_ARGUMENT;
+  }
+  return D::request(who, req, q);
+}
+
+// The body of a kind's *_distance_batch_device
+template <class D>
+int listed_distance_device(const char* who, hfcl_lib* lib, const uint32_t* d_id, const uint32_t* d_shape, const double* d_tf_c, const double* d_tf_2,
+                           size_t n, const uint8_t* d_swapped, const hfcl_distance_request* req, hfcl_result* d_out, uint32_t* d_visited, hipStream_t st) {
+  QParams<double> q;
+  if (int rc = listed_distance_checks<D>(who, lib, req, q)) return rc;
+  if (n == 0) return HFCL_OK;
+  if (int rc = listed_check_arrays(who, d_id, d_shape, d_tf_c, d_tf_2, d_out, n)) return rc;
+  if (int rc = D::check(who, lib, nullptr, n)) return rc;
+  HIP_TRY(hipSetDevice(lib->device));
+  return listed_distance_run<D>(lib, d_id, d_shape, d_tf_c, d_tf_2, n, d_swapped, q, d_out, d_visited, st);
+}
+
+// The body of a kind's *_distance_batch: staged in pieces of the chunk option -- the staging buffers are the collide call's of the kind's
+// workspace, the visited counts go through its count buffer
+template <class D>
+int listed_distance_host(const char* who, hfcl_lib* lib, const uint32_t* id, const uint32_t* shape, const double* tf_c, const double* tf_2, size_t n,
+                         const uint8_t* swapped, const hfcl_distance_request* req, hfcl_result* out, uint32_t* n_visited) {
+  QParams<double> q;
+  if (int rc = listed_distance_checks<D>(who, lib, req, q)) return rc;
+  if (n == 0) return HFCL_OK;
+  if (int rc = listed_check_arrays(who, id, shape, tf_c, tf_2, out, n)) return rc;
+  if (int rc = D::check(who, lib, shape, n)) return rc;
+  if (int rc = listed_check_queries(who, lib, id, D::n_containers(lib), shape, n, D::noun, D::a_noun, "Distance", D::supported)) return rc;
+  HIP_TRY(hipSetDevice(lib->device));
+  auto& w = D::ws(lib);
+  if (!w.st) HIP_TRY(w.st.create());
+  const size_t chunk = std::min(D::chunk(lib), n);
+  HIP_TRY(w.d_counts.grow(chunk));
+  const int rc = listed_staged(who, w, chunk, id, shape, tf_c, tf_2, n, swapped, out, n_visited, w.d_counts.get(), [&](size_t, size_t m) {
+    return listed_distance_run<D>(lib, w.s_id, w.s_shape, w.s_tf_a, w.s_tf_s, m, swapped ? w.s_swapped.get() : nullptr, q, w.s_out,
+                                  n_visited ? w.d_counts.get() : nullptr, w.st);
+  });
+  hipStreamSynchronize(w.st);
   return rc;
 }

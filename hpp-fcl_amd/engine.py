@@ -442,6 +442,43 @@ class Library:
             raise EngineError(abi.ERR_INVALID_ARGUMENT, last_error())
         return idx
 
+    # ---- what the height-field and octree batch calls share (fn: the C entry point) ----
+    def _listed_collide(self, fn, ids, shape, tf_container, tf_shape, req, swapped, max_contacts, want_bound):
+        """A *_collide_batch call from host arrays: (records, distance_lower_bound or None, contacts[CONTACT_DTYPE], n_produced)."""
+        req = req or abi.default_collision_request()
+        ids, shape, tfc, tfs, swapped, n = _listed_arrays(ids, shape, tf_container, tf_shape, swapped)
+        out = np.zeros(n, dtype=abi.RESULT_DTYPE)
+        dlb = np.zeros(n) if want_bound else None
+        contacts = np.zeros(int(max_contacts), dtype=abi.CONTACT_DTYPE)
+        nc = C.c_size_t(0)
+        _check(fn(self._h, abi.ptr(ids), abi.ptr(shape), abi.ptr(tfc), abi.ptr(tfs), C.c_size_t(n), abi.ptr(swapped), C.byref(req), abi.ptr(out),
+                  abi.ptr(dlb), abi.ptr(contacts) if max_contacts else None, C.c_size_t(int(max_contacts)), C.byref(nc)))
+        return out, dlb, contacts[:min(nc.value, int(max_contacts))], int(nc.value)
+
+    def _listed_collide_device(self, fn, d_ids, d_shape, d_tf_container, d_tf_shape, n, req, d_out, d_swapped, d_bound, d_contacts, max_contacts,
+                               want_count, stream):
+        """A *_collide_batch_device call: the number of contacts produced when want_count, else None."""
+        nc = C.c_size_t(0)
+        _check(fn(self._h, _dptr(d_ids), _dptr(d_shape), _dptr(d_tf_container), _dptr(d_tf_shape), C.c_size_t(n), _dptr(d_swapped), C.byref(req),
+                  _dptr(d_out), _dptr(d_bound), _dptr(d_contacts), C.c_size_t(int(max_contacts)), C.byref(nc) if want_count else None,
+                  C.c_void_p(stream)))
+        return int(nc.value) if want_count else None
+
+    def _listed_distance(self, fn, ids, shape, tf_container, tf_shape, req, swapped, want_visited):
+        """A *_distance_batch call from host arrays: the records, or (records, n_visited) when want_visited."""
+        req = req or abi.default_distance_request()
+        ids, shape, tfc, tfs, swapped, n = _listed_arrays(ids, shape, tf_container, tf_shape, swapped)
+        out = np.zeros(n, dtype=abi.RESULT_DTYPE)
+        visited = np.zeros(n, dtype=np.uint32) if want_visited else None
+        _check(fn(self._h, abi.ptr(ids), abi.ptr(shape), abi.ptr(tfc), abi.ptr(tfs), C.c_size_t(n), abi.ptr(swapped), C.byref(req), abi.ptr(out),
+                  abi.ptr(visited)))
+        return (out, visited) if want_visited else out
+
+    def _listed_distance_device(self, fn, d_ids, d_shape, d_tf_container, d_tf_shape, n, req, d_out, d_swapped, d_visited, stream):
+        """A *_distance_batch_device call."""
+        _check(fn(self._h, _dptr(d_ids), _dptr(d_shape), _dptr(d_tf_container), _dptr(d_tf_shape), C.c_size_t(n), _dptr(d_swapped), C.byref(req),
+                  _dptr(d_out), _dptr(d_visited), C.c_void_p(stream)))
+
     # ---- height fields (hfcl_lib_add_hfield, hfcl_hfield_collide_batch*) ----
     def add_hfield(self, x_dim, y_dim, heights, min_height=0.0):
         """Register a HeightField<AABB>; heights: (ny, nx), row 0 = the north edge.  Returns its index on this library."""
@@ -470,27 +507,14 @@ class Library:
     def hfield_collide(self, hfield, shape, tf_hfield, tf_shape, req=None, swapped=None, max_contacts=0, want_bound=True):
         """Batched collide(HeightField<AABB>, solid) -- swapped[i] = 1: collide(solid, HeightField) -- from host arrays.  Returns
         (records, distance_lower_bound or None, contacts[CONTACT_DTYPE], n_produced)."""
-        req = req or abi.default_collision_request()
-        hfield, shape, tfh, tfs, swapped, n = _listed_arrays(hfield, shape, tf_hfield, tf_shape, swapped)
-        out = np.zeros(n, dtype=abi.RESULT_DTYPE)
-        dlb = np.zeros(n) if want_bound else None
-        contacts = np.zeros(int(max_contacts), dtype=abi.CONTACT_DTYPE)
-        nc = C.c_size_t(0)
-        _check(dll().hfcl_hfield_collide_batch(self._h, abi.ptr(hfield), abi.ptr(shape), abi.ptr(tfh), abi.ptr(tfs), C.c_size_t(n),
-                                               abi.ptr(swapped), C.byref(req), abi.ptr(out), abi.ptr(dlb),
-                                               abi.ptr(contacts) if max_contacts else None, C.c_size_t(int(max_contacts)), C.byref(nc)))
-        return out, dlb, contacts[:min(nc.value, int(max_contacts))], int(nc.value)
+        return self._listed_collide(dll().hfcl_hfield_collide_batch, hfield, shape, tf_hfield, tf_shape, req, swapped, max_contacts, want_bound)
 
     def hfield_collide_device(self, d_hfield, d_shape, d_tf_hfield, d_tf_shape, n, req, d_out, d_swapped=None, d_bound=None, d_contacts=None,
                               max_contacts=0, want_count=False, stream=0):
         """The same call on device pointers (torch tensors or raw pointers).  Returns the number of contacts produced when want_count
         (the call then waits for the stream), else None."""
-        nc = C.c_size_t(0)
-        _check(dll().hfcl_hfield_collide_batch_device(self._h, _dptr(d_hfield), _dptr(d_shape), _dptr(d_tf_hfield), _dptr(d_tf_shape),
-                                                      C.c_size_t(n), _dptr(d_swapped), C.byref(req), _dptr(d_out), _dptr(d_bound),
-                                                      _dptr(d_contacts), C.c_size_t(int(max_contacts)), C.byref(nc) if want_count else None,
-                                                      C.c_void_p(stream)))
-        return int(nc.value) if want_count else None
+        return self._listed_collide_device(dll().hfcl_hfield_collide_batch_device, d_hfield, d_shape, d_tf_hfield, d_tf_shape, n, req, d_out,
+                                           d_swapped, d_bound, d_contacts, max_contacts, want_count, stream)
 
     # ---- octrees (hfcl_lib_add_octree, hfcl_octree_collide_batch*) ----
     def add_octree(self, nodes, resolution, depth=abi.OCTREE_MAX_DEPTH, occupancy_threshold=0.5, free_threshold=0.0):
@@ -524,73 +548,40 @@ class Library:
         """Batched collide(OcTree, solid) -- swapped[i] = 1: the caller's order was collide(solid, OcTree), which the reference answers
         with the octree-first result (bit 23 of the status alone changes) -- from host arrays.  Returns (records,
         distance_lower_bound or None, contacts[CONTACT_DTYPE], n_produced)."""
-        req = req or abi.default_collision_request()
-        octree, shape, tft, tfs, swapped, n = _listed_arrays(octree, shape, tf_octree, tf_shape, swapped)
-        out = np.zeros(n, dtype=abi.RESULT_DTYPE)
-        dlb = np.zeros(n) if want_bound else None
-        contacts = np.zeros(int(max_contacts), dtype=abi.CONTACT_DTYPE)
-        nc = C.c_size_t(0)
-        _check(dll().hfcl_octree_collide_batch(self._h, abi.ptr(octree), abi.ptr(shape), abi.ptr(tft), abi.ptr(tfs), C.c_size_t(n),
-                                               abi.ptr(swapped), C.byref(req), abi.ptr(out), abi.ptr(dlb),
-                                               abi.ptr(contacts) if max_contacts else None, C.c_size_t(int(max_contacts)), C.byref(nc)))
-        return out, dlb, contacts[:min(nc.value, int(max_contacts))], int(nc.value)
+        return self._listed_collide(dll().hfcl_octree_collide_batch, octree, shape, tf_octree, tf_shape, req, swapped, max_contacts, want_bound)
 
     def octree_collide_device(self, d_octree, d_shape, d_tf_octree, d_tf_shape, n, req, d_out, d_swapped=None, d_bound=None, d_contacts=None,
                               max_contacts=0, want_count=False, stream=0):
         """The same call on device pointers (torch tensors or raw pointers).  Returns the number of contacts produced when want_count
         (the call then waits for the stream), else None."""
-        nc = C.c_size_t(0)
-        _check(dll().hfcl_octree_collide_batch_device(self._h, _dptr(d_octree), _dptr(d_shape), _dptr(d_tf_octree), _dptr(d_tf_shape),
-                                                      C.c_size_t(n), _dptr(d_swapped), C.byref(req), _dptr(d_out), _dptr(d_bound),
-                                                      _dptr(d_contacts), C.c_size_t(int(max_contacts)), C.byref(nc) if want_count else None,
-                                                      C.c_void_p(stream)))
-        return int(nc.value) if want_count else None
+        return self._listed_collide_device(dll().hfcl_octree_collide_batch_device, d_octree, d_shape, d_tf_octree, d_tf_shape, n, req, d_out,
+                                           d_swapped, d_bound, d_contacts, max_contacts, want_count, stream)
 
     def octree_mesh_collide(self, octree, shape, tf_octree, tf_mesh, req=None, swapped=None, max_contacts=0, want_bound=True):
         """Batched collide(OcTree, BVHModel<OBBRSS>) from host arrays: shape[i] is a BV_OBBRSS row of the library whose bvh_index names
         a mesh registered with add_bvh.  swapped[i] = 1: the caller's order was collide(mesh, OcTree), which the reference answers with
         the octree-first result (bit 23 of the status alone changes).  Returns (records, distance_lower_bound or None,
         contacts[CONTACT_DTYPE] -- b1 the octree node, b2 the triangle --, n_produced)."""
-        req = req or abi.default_collision_request()
-        octree, shape, tft, tfm, swapped, n = _listed_arrays(octree, shape, tf_octree, tf_mesh, swapped)
-        out = np.zeros(n, dtype=abi.RESULT_DTYPE)
-        dlb = np.zeros(n) if want_bound else None
-        contacts = np.zeros(int(max_contacts), dtype=abi.CONTACT_DTYPE)
-        nc = C.c_size_t(0)
-        _check(dll().hfcl_octree_mesh_collide_batch(self._h, abi.ptr(octree), abi.ptr(shape), abi.ptr(tft), abi.ptr(tfm), C.c_size_t(n),
-                                                    abi.ptr(swapped), C.byref(req), abi.ptr(out), abi.ptr(dlb),
-                                                    abi.ptr(contacts) if max_contacts else None, C.c_size_t(int(max_contacts)), C.byref(nc)))
-        return out, dlb, contacts[:min(nc.value, int(max_contacts))], int(nc.value)
+        return self._listed_collide(dll().hfcl_octree_mesh_collide_batch, octree, shape, tf_octree, tf_mesh, req, swapped, max_contacts, want_bound)
 
     def octree_mesh_collide_device(self, d_octree, d_shape, d_tf_octree, d_tf_mesh, n, req, d_out, d_swapped=None, d_bound=None, d_contacts=None,
                                    max_contacts=0, want_count=False, stream=0):
         """The same call on device pointers (torch tensors or raw pointers).  Returns the number of contacts produced when want_count
         (the call then waits for the stream), else None."""
-        nc = C.c_size_t(0)
-        _check(dll().hfcl_octree_mesh_collide_batch_device(self._h, _dptr(d_octree), _dptr(d_shape), _dptr(d_tf_octree), _dptr(d_tf_mesh),
-                                                           C.c_size_t(n), _dptr(d_swapped), C.byref(req), _dptr(d_out), _dptr(d_bound),
-                                                           _dptr(d_contacts), C.c_size_t(int(max_contacts)), C.byref(nc) if want_count else None,
-                                                           C.c_void_p(stream)))
-        return int(nc.value) if want_count else None
+        return self._listed_collide_device(dll().hfcl_octree_mesh_collide_batch_device, d_octree, d_shape, d_tf_octree, d_tf_mesh, n, req, d_out,
+                                           d_swapped, d_bound, d_contacts, max_contacts, want_count, stream)
 
     def octree_distance(self, octree, shape, tf_octree, tf_shape, req=None, swapped=None, want_visited=False):
         """Batched distance(OcTree, solid) from host arrays: the result of the reference's ordered walk (hppfcl_amd_octree_distance.h).
         swapped[i] = 1: the caller's order was distance(solid, OcTree), which the reference answers with the octree-first result (bit
         23 of the status alone changes).  Returns the records, or (records, n_visited) -- the leaves each walk solved -- when
         want_visited."""
-        req = req or abi.default_distance_request()
-        octree, shape, tft, tfs, swapped, n = _listed_arrays(octree, shape, tf_octree, tf_shape, swapped)
-        out = np.zeros(n, dtype=abi.RESULT_DTYPE)
-        visited = np.zeros(n, dtype=np.uint32) if want_visited else None
-        _check(dll().hfcl_octree_distance_batch(self._h, abi.ptr(octree), abi.ptr(shape), abi.ptr(tft), abi.ptr(tfs), C.c_size_t(n),
-                                                abi.ptr(swapped), C.byref(req), abi.ptr(out), abi.ptr(visited)))
-        return (out, visited) if want_visited else out
+        return self._listed_distance(dll().hfcl_octree_distance_batch, octree, shape, tf_octree, tf_shape, req, swapped, want_visited)
 
     def octree_distance_device(self, d_octree, d_shape, d_tf_octree, d_tf_shape, n, req, d_out, d_swapped=None, d_visited=None, stream=0):
         """The same call on device pointers (torch tensors or raw pointers): asynchronous on `stream`, nothing is read back."""
-        _check(dll().hfcl_octree_distance_batch_device(self._h, _dptr(d_octree), _dptr(d_shape), _dptr(d_tf_octree), _dptr(d_tf_shape),
-                                                       C.c_size_t(n), _dptr(d_swapped), C.byref(req), _dptr(d_out), _dptr(d_visited),
-                                                       C.c_void_p(stream)))
+        self._listed_distance_device(dll().hfcl_octree_distance_batch_device, d_octree, d_shape, d_tf_octree, d_tf_shape, n, req, d_out,
+                                     d_swapped, d_visited, stream)
 
     def octree_mesh_distance(self, octree, shape, tf_octree, tf_mesh, req=None, swapped=None, want_visited=False):
         """Batched distance(OcTree, BVHModel<OBBRSS>) from host arrays: the result of the reference's ordered dual walk
@@ -598,19 +589,12 @@ class Library:
         add_bvh.  swapped[i] = 1: the caller's order was distance(mesh, OcTree), which the reference answers with the octree-first
         result (bit 23 of the status alone changes).  b1 is the octree node, b2 the triangle.  Returns the records, or (records,
         n_visited) -- the (leaf, triangle) pairs each walk solved -- when want_visited."""
-        req = req or abi.default_distance_request()
-        octree, shape, tft, tfm, swapped, n = _listed_arrays(octree, shape, tf_octree, tf_mesh, swapped)
-        out = np.zeros(n, dtype=abi.RESULT_DTYPE)
-        visited = np.zeros(n, dtype=np.uint32) if want_visited else None
-        _check(dll().hfcl_octree_mesh_distance_batch(self._h, abi.ptr(octree), abi.ptr(shape), abi.ptr(tft), abi.ptr(tfm), C.c_size_t(n),
-                                                     abi.ptr(swapped), C.byref(req), abi.ptr(out), abi.ptr(visited)))
-        return (out, visited) if want_visited else out
+        return self._listed_distance(dll().hfcl_octree_mesh_distance_batch, octree, shape, tf_octree, tf_mesh, req, swapped, want_visited)
 
     def octree_mesh_distance_device(self, d_octree, d_shape, d_tf_octree, d_tf_mesh, n, req, d_out, d_swapped=None, d_visited=None, stream=0):
         """The same call on device pointers (torch tensors or raw pointers): asynchronous on `stream`, nothing is read back."""
-        _check(dll().hfcl_octree_mesh_distance_batch_device(self._h, _dptr(d_octree), _dptr(d_shape), _dptr(d_tf_octree), _dptr(d_tf_mesh),
-                                                            C.c_size_t(n), _dptr(d_swapped), C.byref(req), _dptr(d_out), _dptr(d_visited),
-                                                            C.c_void_p(stream)))
+        self._listed_distance_device(dll().hfcl_octree_mesh_distance_batch_device, d_octree, d_shape, d_tf_octree, d_tf_mesh, n, req, d_out,
+                                     d_swapped, d_visited, stream)
 
     def collide_contacts(self, s1, s2, tf1, tf2, req, max_contacts):
         """Batched collide() returning (records, contacts[CONTACT_DTYPE], n_produced)."""
